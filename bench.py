@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark of the DDIM hot path on MI355X (contract: see the task description / DESIGN.md "Measurement").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = one optimiser step of the reference's ``_train_one_batch`` (zero_grad, train_step incl. drawing t and noise,
 backward, clip 10, AdamW) on one batch of 32 synthetic MS2+MS1 windows (RT=400 x MZ=64) per GPU -- BASELINE.json configs[1]
 ("same model, 10k synthetic windows, batch=32, 1xMI355X"), computed in fp32 (the reference's precision; the bf16 in that
 config line is not used).  Inputs are resident in HBM before the timed region.  ``value`` = windows/s over all ranks
-(weak scaling: per-GPU batch fixed).  The same JSON line also carries the 50-step DDIM sampling throughput
-(configs[3], batch 512/GPU), the roofline of the dominant kernel, and the CPU baseline (oracle on the host cores).
+(weak scaling: per-GPU batch fixed).  A plain run times this train leg alone.  With ``--full`` the same JSON line also
+carries the 50-step DDIM sampling throughput (configs[3], batch 512/GPU), the roofline of the dominant kernel, the
+configs[4] and CustomTransformer legs and the CPU baseline (oracle on the host cores).  ``--dump-outputs DIR`` writes what
+the last timed step computed (loss, pre-clip gradient norm, gradients, updated parameters) as DIR/<name>.npy in float32.
 """
 import argparse
 import json
@@ -530,7 +532,13 @@ def main():
     ap.add_argument("--no-large-window", action="store_true", help="skip the configs[4] leg (2000 x 256 windows, batch 8; single-GPU runs only)")
     ap.add_argument("--train-only", action="store_true", help="only the train leg (clean per-kernel profiles of the train step)")
     ap.add_argument("--sample-batch", type=int, default=SAMPLE_BATCH)
+    ap.add_argument("--full", action="store_true", help="run every leg, not only the headline train leg (the --no-* options and "
+                                                         "--train-only then leave legs out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, gradient norm, gradients and updated "
+                                                          "parameters as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if not args.full:
+        args.train_only = True  # a plain run: set-up, warm-up, the timed train steps and the result line, nothing else
     if args.train_only:
         args.no_sample = args.no_cpu = args.no_transformer = args.no_large_window = True
 
@@ -581,6 +589,12 @@ def main():
     dt = float(tt)
     train_wps = world * TRAIN_BATCH * args.steps / dt
     last_loss = float(loss)
+    if args.dump_outputs and rank == 0:
+        # the state right after the last timed step (the --full legs below train the same model further)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        outs = {"loss": loss, "grad_norm": dm.last_grad_norm, "grads": net.flat_grads(), "params": net.flat_params}
+        for name, v in outs.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), v.detach().float().cpu().numpy())
 
     # ------------------------------------------------------------------ the same step over >= 5 s (clock settle; whatever --steps was)
     sustained = None

@@ -6,6 +6,7 @@ import json
 import os
 import re
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,6 +86,7 @@ def test_bench_cli_surface():
     src = open(os.path.join(REPO, "bench.py")).read()
     for flag in ("--gpus", "--steps", "--warmup"):
         assert re.search(r'add_argument\("%s", type=int' % flag, src), flag
+    assert 'add_argument("--full", action="store_true"' in src and 'add_argument("--dump-outputs", metavar="DIR"' in src
     assert "init_process_group(\"nccl\"" in src and "127.0.0.1" in src and "ReduceOp.MAX" in src
 
 
@@ -122,12 +124,36 @@ def test_bench_with_sampling_leg_under_torch_distributed_run_with_one_rank():
     leg's barriers and the final gather every rank runs the sampling leg on its shard of the 512 windows and the MAX over ranks of its time is
     taken; the legs that call _train_one_batch on one rank alone (small batch, large window, CPU, transformer) stay gated on world == 1 -- here
     the world IS 1 but the process group is live, so their collectives run too.  Bounded: 3 train steps, a 64-window sampling batch."""
-    d = _run_bench_under_torchrun(["--steps", "3", "--warmup", "1", "--no-cpu", "--no-transformer", "--no-large-window", "--sample-batch", "64"])
+    d = _run_bench_under_torchrun(["--full", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-transformer", "--no-large-window", "--sample-batch", "64"])
     assert d["n_gpus"] == 1 and d["config"]["parallelism"] == "dp1" and d["steps"] == 3
     assert d["value"] > 0 and abs(d["last_loss"]) < 1e3
     sm = d["sample"]
     assert sm["batch_per_gpu"] == 64 and sm["steps"] == 50 and sm["value"] > 0 and abs(sm["value"] - 64 / sm["seconds"]) < 0.01 * sm["value"]
     assert d["small_batch"]["b1"]["ms_per_step"] > 0  # (a rank-0-only leg that issues the flat all-reduce inside the live group)
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_the_train_leg_alone_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) prints the headline fields and none of the other legs; --dump-outputs writes the last timed step's loss,
+    gradient norm, gradients and updated parameters as float32 .npy files, the loss being the line's last_loss."""
+    import subprocess
+    import sys
+
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "windows/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) < 0.01 * d["value"]
+    for k in ("sustained", "small_batch", "sample", "roofline", "roofline_hbm", "cpu_baseline", "batch_formation", "large_window", "transformer"):
+        assert d[k] is None, k
+    a = {n: np.load(out / f"{n}.npy") for n in ("loss", "grad_norm", "grads", "params")}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["grads"].shape == a["params"].shape and a["params"].size > 100_000 and float(a["grad_norm"]) > 0
+    assert abs(float(a["loss"]) - d["last_loss"]) <= 2e-6 * max(1.0, abs(d["last_loss"]))
 
 
 @pytest.mark.gpu

@@ -6,7 +6,7 @@ export DQ_HIP_LIB=$PWD/diffusion-deconvolution-dia-msms-data_amd/build/dev/libdq
 mkdir -p gpurun_out
 for V in "" "$@"; do
   if [ -n "$V" ]; then export $VAR=$V; else unset $VAR; fi
-  python3 bench.py --no-cpu --no-transformer --no-large-window --no-sample --steps 200 2> /dev/null | python3 -c "
+  python3 bench.py --full --no-cpu --no-transformer --no-large-window --no-sample --steps 200 2> /dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 sb = d.get('small_batch') or {}

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compiled kernels of the shipped libdq_hip.so (tools/kernel_resources.py --csv) against the kernels anything launched
-(gpurun_out/<tag>_census_launched.txt from tools/kernel_census.sh: the GPU test suite + the whole bench under rocprofv3).
-usage: tools/kernel_census.py gpurun_out/r05_census_launched.txt [--list]"""
+(<out>/<tag>_census_launched.txt from tools/kernel_census.sh: the GPU test suite + the whole bench under rocprofv3).
+usage: tools/kernel_census.py out/r05_census_launched.txt [--list]"""
 import re
 import subprocess
 import sys
