@@ -139,9 +139,14 @@ struct ResBwd {
   float* gpart = nullptr; int64_t gpart_floats = 0; int* gblocks = nullptr;
   int C = 0, rows = 0, n = 0, rows_per_sample = 1;
 };
-bool res_fusable(int n, int C, int rows_per_sample);  // rows_per_sample == 1: the bottleneck (one RT row per sample: <= 512 positions, any length at 16 channels)
+// Which ResnetBlock kernel runs (in order of preference): k_res_{rt,mm,cp,v4,rows,wg}.hip, k_res.hip (PLAIN) or the conv launches of dq_unet.hip
+// (UNFUSED).  wg: the block's buffers were laid out for k_res_bwd_wg (ResBuf::wpart_floats != 0).
+enum ResFwdForm { RES_FWD_RT, RES_FWD_MM, RES_FWD_CP, RES_FWD_V4, RES_FWD_PLAIN, RES_FWD_UNFUSED };
+ResFwdForm res_fwd_form(int C, int cinA, int cinB, bool has_wr, int n, int rows_per_sample);
+enum ResBwdForm { RES_BWD_WG, RES_BWD_RT, RES_BWD_ROWS, RES_BWD_CP, RES_BWD_PLAIN, RES_BWD_UNFUSED };
+ResBwdForm res_bwd_form(const ResBwd& a, bool wg);
 // k_res_rt.hip: the bottleneck's 16-channel blocks (one RT row per sample, identity residual, no skip input) with the RT position as the lane
-// column of v_mfma_f32_16x16x4; launch_res_fwd / _bwd dispatch to it
+// column of v_mfma_f32_16x16x4
 bool res_rt_usable(int C, int cinA, int cinB, bool has_wr, int rows_per_sample);
 // the front of the bottleneck's Residual(PreNorm(Attention)) behind the first block: xn = RMSNorm(out) gn -> qv = W_qv xn (B, 256, RT), RoPE on
 // q; k = W_k ms1f (B, 128, RT) + RoPE when kk is given
@@ -163,12 +168,12 @@ struct ResRtPre {
   const float* rope = nullptr; float* gn_part = nullptr; int64_t gn_part_floats = 0;
 };
 int launch_res_rt_bwd(const ResBwd& a, hipStream_t s, const ResRtPre* q = nullptr, const ResRtOut* ao = nullptr);
-// k_res_cp.hip: channel-parallel variant for the deep levels (n <= 8, C = 12 / 16); launch_res_fwd / _bwd dispatch to it
+// k_res_cp.hip: channel-parallel variant for the deep levels (n <= 8, C = 12 / 16)
 bool res_cp_usable(int n, int C, int cinA, int cinB);
 int launch_res_fwd_cp(const ResFwd& a, hipStream_t s);
 int launch_res_bwd_cp(const ResBwd& a, hipStream_t s);
 // k_res_rows.hip: the deep levels' backward data path with the m/z row as the lane column of v_mfma_f32_16x16x4 (12 / 16 channels, rows of
-// 2 / 4 / 8 positions, 16-byte aligned tensors); launch_res_bwd dispatches to it
+// 2 / 4 / 8 positions, 16-byte aligned tensors)
 bool res_rows_bwd_usable(const ResBwd& a);
 int launch_res_rows_bwd(const ResBwd& a, hipStream_t s);
 // k_res_v4.hip: 4-positions-per-thread forward for the wide levels (C = 4 / 8, n >= 8)
@@ -364,18 +369,20 @@ struct LinAttn {
   // image of Wq | Wk); without it every block of the forward derives them itself (a 64-load-deep prologue per 4 rows)
   const float* prep = nullptr;
 };
+// rows the register-resident kernels take (k_linattn.hip / k_la_bwd.hip); any other length goes through the sweep kernels (k_la_long.hip)
+inline bool la_short_row(int n) { return n <= 64 && (n & (n - 1)) == 0; }
 int launch_linattn_fwd(const LinAttn& a, hipStream_t s);
 // k_la_small.hip: rows of 2 / 4 (/ 8) positions at 8 / 12 / 16 channels with a prepared image (LinAttn::prep): every product on
-// v_mfma_f32_32x32x2 with lane = (channel half, row) and one group of registers per position (launch_linattn_fwd dispatches to it)
+// v_mfma_f32_32x32x2 with lane = (channel half, row) and one group of registers per position
 bool la_small_usable(int C, int n);
-int la_small_min_rows();  // launch_linattn_fwd takes this path from that many rows on
+int la_small_min_rows();  // la_fwd_form takes this path from that many rows on
 int launch_la_small_fwd(const LinAttn& a, hipStream_t s);
 // k_la_rows_bwd.hip: the backward in the same spirit (one m/z row per lane column, every product on v_mfma_f32_16x16x4_f32); one slot per
-// wave in the la_slot(C) layout; launch_linattn_bwd dispatches to it when the layer's prepared weights are at hand
+// wave in the la_slot(C) layout, when the layer's prepared weights are at hand
 struct LinAttnBwd;
 bool la_rows_bwd_usable(int C, int n);
 int la_rows_bwd_min_rows();
-// k_la_rows_fwd.hip: the forward in the same layout (rows of 2 / 4 positions below la_small_min_rows; launch_linattn_fwd dispatches to it)
+// k_la_rows_fwd.hip: the forward in the same layout (rows of 2 / 4 positions below la_small_min_rows)
 bool la_rows_fwd_usable(int C, int n);
 int launch_la_rows_fwd(const LinAttn& a, hipStream_t s);
 int launch_la_rows_bwd(const LinAttnBwd& a, int max_slots, int* slots_out, hipStream_t s);

@@ -48,6 +48,22 @@ int occ_blocks_per_cu(const void* fn, int threads, size_t lds) {
 // ---------------------------------------------------------------------------------------------------------------
 // arena
 // ---------------------------------------------------------------------------------------------------------------
+// The buffers of one ResnetBlock over B samples of rows_per_sample rows: take(floats) -> offset; take_out: the output's (layout_arena: zero_out)
+template <class Take, class TakeOut>
+ResBuf layout_res(int B, int rows_per_sample, int cin, int c, int n, Take take, TakeOut take_out) {
+  ResBuf r;
+  const int64_t t = (int64_t)B * rows_per_sample * c * n;
+  // (blocks whose backward forms the weight gradients itself recompute a1 from u1: no a1 tensor)
+  const bool wg = B > 0 && res_wg_usable(n, c, c, cin - c, rows_per_sample);
+  r.u1 = take(t); r.a1 = wg ? r.u1 : take(t); r.u2 = take(t);
+  if (wg) { r.wpart_floats = res_wg_part_floats(c, cin, cin != c, B, rows_per_sample, n); r.wpart = take(r.wpart_floats); }
+  r.out = take_out(t);
+  // per-block partial sums [dg2 | dg1 | dscale | dshift]: the fused grids, or the <= 64 blocks per sample of k_block_bwd on the unfused path
+  r.gpart_floats = (int64_t)B * std::max<int64_t>({((int64_t)rows_per_sample * n + 255) / 256, (rows_per_sample + 15) / 16, 64}) * 4 * c;
+  r.gpart = take(r.gpart_floats);
+  return r;
+}
+
 void layout_arena(const Plan& p, int B, int RT, Arena& a) {
   // Two regions: [0, zero_floats) holds every tensor whose GRADIENT twin is accumulated into (+=) and therefore has to start
   // at zero each backward; the rest (pre-norm saves, whose twins are written with "=", and pure scratch) follows, so that the
@@ -62,20 +78,10 @@ void layout_arena(const Plan& p, int B, int RT, Arena& a) {
   const int64_t R = (int64_t)B * RT;
   // zero_out: the gradient of the block's output is accumulated into before anything stores to it (the bottleneck blocks'
   // step-by-step backward); everywhere else the first writer of a gradient tensor stores (unet_backward), so the twin of that
-  // tensor needs no clearing -- the zero-fill per backward went from 452 MB to the few small tensors that are left in `take`
-  auto res = [&](int64_t rows, int cin, int c, int n, bool zero_out = false) {
-    ResBuf r;
-    // (blocks whose backward forms the weight gradients itself recompute a1 from u1: no a1 tensor)
-    const bool wg = B > 0 && res_wg_usable(n, c, c, cin - c, (int)(rows / B));
-    r.u1 = take_nz(rows * c * n); r.a1 = wg ? r.u1 : take_nz(rows * c * n); r.u2 = take_nz(rows * c * n);
-    if (wg) { r.wpart_floats = res_wg_part_floats(c, cin, cin != c, B, (int)(rows / B), n); r.wpart = take_nz(r.wpart_floats); }
-    r.out = zero_out ? take(rows * c * n) : take_nz(rows * c * n);
-    // one slot per ResnetBlock (the ordered reduce runs on the side stream and may lag behind the next block's backward)
-    // per-block partial sums [dg2 | dg1 | dscale | dshift]: k_res_bwd / k_res_bwd_cp grids, or the <= 64 blocks per sample of
-    // k_block_bwd on the step-by-step path
-    r.gpart_floats = (int64_t)B * std::max<int64_t>({(rows / B * n + 255) / 256, (rows / B + 15) / 16, 64}) * 4 * c;
-    r.gpart = take_nz(r.gpart_floats);
-    return r;
+  // tensor needs no clearing -- the zero-fill per backward went from 452 MB to the few small tensors that are left in `take`.
+  // One gpart slot per ResnetBlock (the ordered reduce runs on the side stream and may lag behind the next block's backward).
+  auto res = [&](int rows_per_sample, int cin, int c, int n, bool zero_out = false) {
+    return layout_res(B, rows_per_sample, cin, c, n, take_nz, [&](int64_t f) { return zero_out ? take(f) : take_nz(f); });
   };
   a.tbuf = take((int64_t)B * TBUF_FLOATS);
   a.ss = take((int64_t)B * p.ss_total);
@@ -86,7 +92,7 @@ void layout_arena(const Plan& p, int B, int RT, Arena& a) {
   for (int lv = 0; lv < p.levels; ++lv) {
     const LevelP& l = p.downs[lv];
     LevelBuf b;
-    b.r0 = res(R, l.r0.cin, l.r0.cout, l.n); b.r1 = res(R, l.r1.cin, l.r1.cout, l.n);
+    b.r0 = res(RT, l.r0.cin, l.r0.cout, l.n); b.r1 = res(RT, l.r1.cin, l.r1.cout, l.n);
     b.la = take_nz(R * l.la.C * l.n); b.la_pre = take_nz(R * l.la.C * l.n); b.la_tmp = take_nz(R * l.la.C * l.n);
     b.rs = take_nz(R * l.resample.cout * l.n_next);
     if (B > 0 && conv_wg_usable(l.resample.cout, l.last ? LEVEL_PRE_S1 : LEVEL_PRE_DOWN, l.resample.cin, l.n_next, RT)) {
@@ -117,17 +123,17 @@ void layout_arena(const Plan& p, int B, int RT, Arena& a) {
     a.w_gemm_part = take_nz(gp + 64);
   }
   a.mid_in = take(R * (p.wide_mid ? 1 : p.mid_c));
-  a.mid1 = res(B, p.wide_mid ? 4 : p.mid_c, p.wide_mid ? 4 : p.mid_c, RT, true);
+  a.mid1 = res(1, p.wide_mid ? 4 : p.mid_c, p.wide_mid ? 4 : p.mid_c, RT, true);
   a.xn = take(R * (p.wide_mid ? 1 : p.mid_c));
   a.qv = take(R * 2 * HID); a.kk = take(R * HID); a.o = take(R * HID);
   a.lse = take(R * HEADS); a.delta = take(R * HEADS);
   a.attn_out = take(R * (p.wide_mid ? 1 : p.mid_c));
-  a.mid2 = res(B, p.wide_mid ? 4 : p.mid_c, p.wide_mid ? 4 : p.mid_c, RT, true);
+  a.mid2 = res(1, p.wide_mid ? 4 : p.mid_c, p.wide_mid ? 4 : p.mid_c, RT, true);
   a.mid_back = take(R * p.mid_c);
   for (int ui = 0; ui < p.levels; ++ui) {
     const LevelP& l = p.ups[ui];
     LevelBuf b;
-    b.r0 = res(R, l.r0.cin, l.r0.cout, l.n); b.r1 = res(R, l.r1.cin, l.r1.cout, l.n);
+    b.r0 = res(RT, l.r0.cin, l.r0.cout, l.n); b.r1 = res(RT, l.r1.cin, l.r1.cout, l.n);
     b.la = take_nz(R * l.la.C * l.n); b.la_pre = take_nz(R * l.la.C * l.n); b.la_tmp = take_nz(R * l.la.C * l.n);
     b.rs = take_nz(R * l.resample.cout * l.n_next);
     if (B > 0 && conv_wg_usable(l.resample.cout, l.last ? LEVEL_PRE_S1 : LEVEL_PRE_UP, l.resample.cin, l.n_next, RT)) {
@@ -136,7 +142,7 @@ void layout_arena(const Plan& p, int B, int RT, Arena& a) {
     }
     a.ups.push_back(b);
   }
-  a.fin = res(R, 2 * p.dim, p.dim, p.mz);
+  a.fin = res(RT, 2 * p.dim, p.dim, p.mz);
   a.eps = take(R * p.mz);
   a.xa = take_nz(R * p.mz);   // sampling ping-pong / train-step x_t
   a.xb = take_nz(R * p.mz);
@@ -245,8 +251,8 @@ static inline bool side_flush_here(int lv) { return (lv & 1) == 0; }
 
 // ResnetBlock forward (unet1d.py:302-323): input = cat(A, B)
 int res_fwd(const Ctx& c, const ResP& r, const ResBuf& b, const float* inA, int cinA, const float* inB, int cinB, int rows, int n,
-            int rows_per_sample, const ResRtQkv* qkv = nullptr, const ResRtOut* aout = nullptr) {  // qkv / aout: the attention's front rides behind the block / its back in front of it (k_res_rt.hip; the caller checked res_rt_usable)
-  if (res_fusable(n, r.cout, rows_per_sample)) {  // m/z levels, and a bottleneck of up to 512 RT positions: one fused launch
+            int rows_per_sample, const ResRtQkv* qkv = nullptr, const ResRtOut* aout = nullptr) {  // qkv / aout: the attention's front rides behind the block / its back in front of it (k_res_rt.hip; the caller checked for RES_FWD_RT)
+  if (res_fwd_form(r.cout, cinA, cinB, r.res.cout != 0, n, rows_per_sample) != RES_FWD_UNFUSED) {  // one fused launch
     ResFwd k;
     k.inA = inA; k.inB = inB; k.cinA = cinA; k.cinB = cinB;
     k.w1 = c.prm(r.c1.w); k.b1 = c.prm(r.c1.b); k.g1 = c.prm(r.g1);
@@ -260,6 +266,7 @@ int res_fwd(const Ctx& c, const ResP& r, const ResBuf& b, const float* inA, int 
     return launch_res_fwd(k, c.s);
   }
   DQ_REQUIRE(!qkv && !aout, "res_fwd: the attention front / back needs the fused 16-channel block");
+  DQ_REQUIRE(b.a1 != b.u1, "res_fwd: a block laid out for the fused weight-gradient backward has no a1 tensor (cat(x, skip) with x of cout channels)");
   ConvFwd f;
   f.inA = inA; f.inB = inB; f.cinA = cinA; f.cinB = cinB;
   f.w = c.prm(r.c1.w); f.bias = c.prm(r.c1.b); f.cout = r.cout; f.K = 3; f.mode = CONV_S1;
@@ -330,46 +337,42 @@ int res_bwd(const Ctx& c, const ResP& r, const ResBuf& b, const float* inA, floa
             int rows, int n, int rows_per_sample, int storeA = 0, int storeB = 0, const ResRtPre* pre = nullptr, int* gblocks_out = nullptr,
             const ResRtOut* aout = nullptr) {
   const float* dout = c.g(b.out);
-  // (a block laid out for the fused weight-gradient kernel keeps no a1 tensor -- the arena assumes cat(x, skip) with x of cout channels, as
-  // everywhere in the network; another split of the same cin cannot be served from that layout)
-  DQ_REQUIRE(!b.wpart_floats || res_wg_usable(n, r.cout, cinA, cinB, rows_per_sample),
-             "ResnetBlock backward: the first input tensor must carry the block's output channel count (cat(x, skip) with x of cout channels)");
-  if (b.wpart_floats) {
-    // wide m/z levels: the data path AND the block's weight gradients in one launch; its slots are summed by one launch per pass
-    ResBwdWg k;
-    k.dout = dout; k.u1 = c.w(b.u1); k.u2 = c.w(b.u2); k.inA = inA; k.inB = inB; k.cinA = cinA; k.cinB = cinB;
-    k.w1 = c.prm(r.c1.w); k.w2 = c.prm(r.c2.w); k.wr = r.res.cout ? c.prm(r.res.w) : nullptr;
-    k.g1 = c.prm(r.g1); k.g2 = c.prm(r.g2); k.ss = c.w(c.ar.ss) + r.ss_off; k.ss_stride = c.p.ss_total;
-    k.dA = dA; k.dB = dB; k.dA_store = storeA; k.dB_store = storeB;
-    k.part = c.w(b.wpart); k.part_floats = b.wpart_floats;
+  ResBwd k;
+  k.dout = dout; k.u1 = c.w(b.u1); k.u2 = c.w(b.u2);
+  k.w1 = c.prm(r.c1.w); k.w2 = c.prm(r.c2.w); k.wr = r.res.cout ? c.prm(r.res.w) : nullptr;
+  k.g1 = c.prm(r.g1); k.g2 = c.prm(r.g2); k.ss = c.w(c.ar.ss) + r.ss_off; k.ss_stride = c.p.ss_total;
+  k.du1 = c.g(b.u1); k.du2 = c.g(b.u2); k.dA = dA; k.dB = dB; k.cinA = cinA; k.cinB = cinB;
+  k.dA_store = storeA; k.dB_store = storeB;
+  k.dg1 = c.dprm(r.g1); k.dg2 = c.dprm(r.g2); k.dss = c.g(c.ar.ss) + r.ss_off;
+  k.C = r.cout; k.rows = rows; k.n = n; k.rows_per_sample = rows_per_sample;
+  const ResBwdForm form = res_bwd_form(k, b.wpart_floats != 0);
+  if (form == RES_BWD_WG) {
+    // wide m/z levels: the data path AND the block's weight gradients in one launch; its slots are summed by one launch per pass.  (The
+    // layout keeps no a1 tensor for such a block: it assumes cat(x, skip) with x of cout channels, as everywhere in the network.)
+    ResBwdWg w;
+    w.dout = dout; w.u1 = k.u1; w.u2 = k.u2; w.inA = inA; w.inB = inB; w.cinA = cinA; w.cinB = cinB;
+    w.w1 = k.w1; w.w2 = k.w2; w.wr = k.wr; w.g1 = k.g1; w.g2 = k.g2; w.ss = k.ss; w.ss_stride = k.ss_stride;
+    w.dA = dA; w.dB = dB; w.dA_store = storeA; w.dB_store = storeB; w.part = c.w(b.wpart); w.part_floats = b.wpart_floats;
     // the slot order is the order of the block's tensors in the flat buffer (dq_plan.cpp, Builder::res)
     const int64_t cw = (int64_t)r.cout * r.cin * 3, C = r.cout;
     DQ_REQUIRE(r.c1.b == r.c1.w + cw && r.g1 == r.c1.b + C && r.c2.w == r.g1 + C && r.c2.b == r.c2.w + C * C * 3 && r.g2 == r.c2.b + C &&
                (!r.res.cout || (r.res.w == r.g2 + C && r.res.b == r.res.w + C * r.cin)), "res_bwd: the block's parameters are not contiguous");
-    k.dparams = c.dprm(r.c1.w); k.dss = c.g(c.ar.ss) + r.ss_off;
-    k.C = r.cout; k.rows = rows; k.n = n; k.rows_per_sample = rows_per_sample;
+    w.dparams = c.dprm(r.c1.w); w.dss = k.dss; w.C = r.cout; w.rows = rows; w.n = n; w.rows_per_sample = rows_per_sample;
     ResWgReduce red;
-    DQ_TRY(launch_res_bwd_wg(k, c.s, &red));
+    DQ_TRY(launch_res_bwd_wg(w, c.s, &red));
     if (c.wg_defer) { c.wg_defer->push_back(red); return 0; }
     return launch_res_wg_reduce(&red, 1, c.s);
   }
-  if (res_fusable(n, r.cout, rows_per_sample)) {
-    // m/z levels (and a bottleneck of up to 512 RT positions): the whole data path in one launch, then the three weight-gradient launches
-    ResBwd k;
-    k.dout = dout; k.u1 = c.w(b.u1); k.u2 = c.w(b.u2);
-    k.w1 = c.prm(r.c1.w); k.w2 = c.prm(r.c2.w); k.wr = r.res.cout ? c.prm(r.res.w) : nullptr;
-    k.g1 = c.prm(r.g1); k.g2 = c.prm(r.g2); k.ss = c.w(c.ar.ss) + r.ss_off; k.ss_stride = c.p.ss_total;
-    k.du1 = c.g(b.u1); k.du2 = c.g(b.u2); k.dA = dA; k.dB = dB; k.cinA = cinA; k.cinB = cinB;
-    k.dA_store = storeA; k.dB_store = storeB;
-    k.dg1 = c.dprm(r.g1); k.dg2 = c.dprm(r.g2); k.dss = c.g(c.ar.ss) + r.ss_off;
-    k.C = r.cout; k.rows = rows; k.n = n; k.rows_per_sample = rows_per_sample;
+  if (form != RES_BWD_UNFUSED) {
+    // the whole data path in one launch, then the three weight-gradient launches
     int gblocks = 0;
     k.gpart = c.w(b.gpart); k.gpart_floats = b.gpart_floats; k.gblocks = &gblocks;
-    if (pre || aout) DQ_TRY(launch_res_rt_bwd(k, c.s, pre, aout));  // (the caller checked res_rt_usable: d out formed by the launch's prologue / d o by its epilogue)
+    if (pre || aout) DQ_TRY(launch_res_rt_bwd(k, c.s, pre, aout));  // (the caller checked for RES_FWD_RT: d out formed by the launch's prologue / d o by its epilogue)
     else DQ_TRY(launch_res_bwd(k, c.s));
     if (gblocks_out) *gblocks_out = gblocks;
     return res_bwd_side(c, r, b, inA, cinA, inB, cinB, rows, n, rows_per_sample, gblocks);
   }
+  DQ_REQUIRE(!pre && !aout, "res_bwd: the attention front / back needs the fused 16-channel block");
   // block2: norm -> silu
   BlockBwd bb;
   bb.u = c.w(b.u2); bb.dy = dout; bb.du = c.g(b.u2); bb.C = r.cout; bb.rows = rows; bb.n = n; bb.rows_per_sample = rows_per_sample;
@@ -482,9 +485,6 @@ bool tiny_bwd_desc(const Ctx& c, bool up, TinyBwd* out) {
   *out = t;
   return true;
 }
-
-// rows the register-resident kernels handle (k_linattn.hip / k_la_bwd.hip); anything else goes through the sweep kernels (k_la_long.hip)
-bool la_short_row(int n) { return n <= 64 && (n & (n - 1)) == 0; }
 
 // slot: this layer's index in the prepared-weights buffer (la_prepare_all), or -1
 int la_fwd(const Ctx& c, const LAP& l, const float* x, float* y, float* ypre, int rows, int n, int slot = -1) {
@@ -1076,7 +1076,7 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
   } else {
     if (!mid_in_done) DQ_TRY(launch_fold(cur, c.w(a.mid_in), B, RT, p.mid_c, 1, 0, c.s));
     // 16 channels (the default U-Net): PreNorm, to_qv, to_k and RoPE ride behind mid_block1 (k_res_rt.hip)
-    const bool qkv_fused = res_rt_usable(p.mid_c, p.mid_c, 0, p.mid1.res.cout != 0, 1) && HID == 128 && p.cond_dim == 8 &&
+    const bool qkv_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid1.res.cout != 0, RT, 1) == RES_FWD_RT && HID == 128 && p.cond_dim == 8 &&
                            !DQ_DEV_FLAG("DQ_NO_MID_QKV", '1');  // (dev switch)
     if (qkv_fused) {
       ResRtQkv q;
@@ -1102,7 +1102,7 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
       const int64_t qvbs = (int64_t)2 * HID * RT, kbs = (int64_t)HID * RT;
       DQ_TRY(launch_attn_fwd(c.w(a.qv), qvbs, c.w(a.kk), kbs, c.w(a.qv) + kbs, qvbs, c.w(a.o), c.w(a.lse), B, RT, c.s));
       // 16 channels: to_out (1x1 + bias) and the residual are formed in FRONT of mid_block2, inside its launch (k_res_rt.hip)
-      out_fused = res_rt_usable(p.mid_c, p.mid_c, 0, p.mid2.res.cout != 0, 1) && HID == 128 && !DQ_DEV_FLAG("DQ_NO_MID_OUT", '1');  // (dev switch)
+      out_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid2.res.cout != 0, RT, 1) == RES_FWD_RT && HID == 128 && !DQ_DEV_FLAG("DQ_NO_MID_OUT", '1');  // (dev switch)
       if (!out_fused) {
       const ConvP ao = proj(p.ao_w, p.mid_c, HID);
       if (conv_is_gemm(c, ao, CONV_S1, RT, RT) && (prep_ok || ((uintptr_t)c.prm(ao.w) & 15) == 0)) {
@@ -1260,7 +1260,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
   } else {
     if (!use_tb_up) DQ_TRY(launch_fold(c.g(a.mid_back), c.g(a.mid2.out), B, RT, p.mid_c, 1, 1, c.s));  // (the tiny backward wrote d mid2.out itself)
     // 16 channels: d o = W_o^T d attn_out follows mid_block2's d x inside its launch (k_res_rt.hip); to_out's weight gradient stays below
-    const bool out_bwd_fused = res_rt_usable(p.mid_c, p.mid_c, 0, p.mid2.res.cout != 0, 1) && HID == 128 && !DQ_DEV_FLAG("DQ_NO_MID_OUT", '1');  // (dev switch)
+    const bool out_bwd_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid2.res.cout != 0, RT, 1) == RES_FWD_RT && HID == 128 && !DQ_DEV_FLAG("DQ_NO_MID_OUT", '1');  // (dev switch)
     if (out_bwd_fused) {
       ResRtOut ao;
       ao.w = c.prm(p.ao_w); ao.d_o = c.g(a.o);
@@ -1287,7 +1287,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
       // the side queue -- behind the next flush's fork event, i.e. behind mid_block1's backward, which has read d q by then.
       // (without a side queue -- the captured step, a plan without an owner -- the same launches follow mid_block1's backward on the main stream:
       // the arithmetic, and with it every bit of the step, does not depend on the schedule)
-      const bool pre_fused = res_rt_usable(p.mid_c, p.mid_c, 0, p.mid1.res.cout != 0, 1) && HID == 128 &&
+      const bool pre_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid1.res.cout != 0, RT, 1) == RES_FWD_RT && HID == 128 &&
                              a.bb_part_floats >= (int64_t)64 * B * p.mid_c && !DQ_DEV_FLAG("DQ_NO_MID_PRE", '1');  // (dev switch)
       if (pre_fused) {
         const ConvP kp = proj(p.k_w, HID, p.cond_dim), qp = proj(p.qv_w, 2 * HID, p.mid_c);
@@ -2057,15 +2057,8 @@ int block_ws(BlockWs& w, int cin, int cout, int rows, int n, int rows_per_sample
   w.B = rows / rows_per_sample;
   int64_t off = 0;
   auto take = [&](int64_t f) { int64_t o = off; off += (f + 63) / 64 * 64; return o; };
-  const int64_t t = (int64_t)rows * cout * n;
   w.ar.ss = take((int64_t)w.B * w.plan.ss_total);
-  w.rb.u1 = take(t); w.rb.a1 = take(t); w.rb.u2 = take(t); w.rb.out = take(t);
-  if (res_wg_usable(n, cout, cout, cin - cout, rows_per_sample)) {
-    w.rb.wpart_floats = res_wg_part_floats(cout, cin, cin != cout, w.B, rows_per_sample, n);
-    w.rb.wpart = take(w.rb.wpart_floats);
-  }
-  w.rb.gpart_floats = (int64_t)w.B * std::max<int64_t>({((int64_t)rows_per_sample * n + 255) / 256, (rows_per_sample + 15) / 16, 64}) * 4 * cout;
-  w.rb.gpart = take(w.rb.gpart_floats);
+  w.rb = layout_res(w.B, rows_per_sample, cin, cout, n, take, take);
   w.ar.wg_floats = (int64_t)WGRAD_MAX_PARTS * ((int64_t)cout * std::max(cin, cout) * 3 + cout) * 3;
   w.ar.wg = take(w.ar.wg_floats);
   w.ar.B = w.B; w.ar.RT = rows_per_sample;

@@ -1393,6 +1393,22 @@ int launch_linattn_dw_reduce_multi(const LaReduceItem* items, int count, hipStre
   return 0;
 }
 
+namespace {
+// Which kernel runs the backward: k_la_long.hip, k_la_rows_bwd.hip or the register-resident one, each only when its launcher takes every argument
+enum LaBwdForm { LA_BWD_LONG, LA_BWD_ROWS, LA_BWD_REG };
+LaBwdForm la_bwd_form(const LinAttnBwd& a) {
+  const int C = a.f.C, rows = a.f.rows, n = a.f.n;
+  if (!la_short_row(n)) return LA_BWD_LONG;
+  // rows of 2 / 4 positions at 8 / 12 / 16 channels: one m/z row per lane column (k_la_rows_bwd.hip), when the layer's prepared weights are at
+  // hand; otherwise the register-resident kernel, which reads them with scalar loads
+  if (a.f.prep && la_rows_bwd_usable(C, n) && rows >= la_rows_bwd_min_rows() &&
+      (((uintptr_t)a.f.prep | (uintptr_t)a.f.x | (uintptr_t)a.ypre | (uintptr_t)a.dy | (uintptr_t)a.dx) & 15) == 0 &&
+      (int64_t)rows * C * n * 4 < (1ll << 32))
+    return LA_BWD_ROWS;
+  return LA_BWD_REG;
+}
+}  // namespace
+
 // a.f.y is unused; needs: a.ypre (saved pre-norm output), the (rows, C, n) scratch dxh (and dyp for rows longer than 64) and
 // the partial-slot scratch
 int launch_linattn_bwd(const LinAttnBwd& a, hipStream_t s) {
@@ -1401,11 +1417,12 @@ int launch_linattn_bwd(const LinAttnBwd& a, hipStream_t s) {
   if (a.f.rows == 0) return 0;
   const int C = a.f.C, rows = a.f.rows, n = a.f.n;
   if (a.waves_out) *a.waves_out = 0;
-  const bool short_rows = n <= 64 && (n & (n - 1)) == 0;  // (a slot per block; the sweep kernel of longer rows: 512 C floats per wave)
-  DQ_REQUIRE(a.part && a.part_floats >= (short_rows ? la_part_reserve(C) : (int64_t)LA_MAX_WAVES * 512 * C),
+  // (a slot per block; the sweep kernel of longer rows: 512 C floats per wave)
+  DQ_REQUIRE(a.part && a.part_floats >= (la_short_row(n) ? la_part_reserve(C) : (int64_t)LA_MAX_WAVES * 512 * C),
              "linattn_bwd: partial-sum scratch missing or too small");
   static_assert((int64_t)LA_MAX_WAVES * 512 * 4 >= 2048 * (int64_t)la_slot(4) + 64, "slot scratch: a resident round of slots must fit");
-  if (n > 64 || (n & (n - 1)) != 0) {
+  const LaBwdForm form = la_bwd_form(a);
+  if (form == LA_BWD_LONG) {
     // rows of 128 / 256 positions: the sweep kernel between two pointwise norm-backward launches
     // (these launches accumulate into dx: a caller that asked for a plain store gets a cleared dx first)
     DQ_REQUIRE(a.part_floats >= (int64_t)LA_MAX_WAVES * 512 * C, "linattn_bwd: partial-sum scratch too small for the sweep kernel");
@@ -1429,9 +1446,7 @@ int launch_linattn_bwd(const LinAttnBwd& a, hipStream_t s) {
     b1.part = a.part; b1.part_floats = a.part_floats;  // (free again: the slot reduce above has consumed it, in stream order)
     return launch_block_bwd(b1, s);
   }
-  // rows of 2 / 4 positions at 8 / 12 / 16 channels: one m/z row per lane column (k_la_rows_bwd.hip), when the layer's prepared weights are at hand
-  if (a.f.prep && la_rows_bwd_usable(C, n) && rows >= la_rows_bwd_min_rows() &&
-      (((uintptr_t)a.f.x | (uintptr_t)a.ypre | (uintptr_t)a.dy | (uintptr_t)a.dx) & 15) == 0) {
+  if (form == LA_BWD_ROWS) {
     const int slots_max = (int)std::min<int64_t>((a.part_floats - 4 * C * C) / la_slot(C), C <= 8 ? 2048 : 1024);
     int slots = 0;
     if (int rc = launch_la_rows_bwd(a, slots_max, &slots, s)) return rc;

@@ -751,17 +751,32 @@ int launch_linattn_prepare(const LaPrepItem* items, int count, hipStream_t s, co
   return 0;
 }
 
-int launch_linattn_fwd(const LinAttn& a, hipStream_t s) {
-  DQ_REQUIRE(a.x && a.y && a.w_qkv && a.w_out && a.b_out && a.g_pre && a.g_out, "linattn_fwd: missing operand");
-  if (a.rows == 0) return 0;
-  if (a.n > 64 || (a.n & (a.n - 1)) != 0) return launch_linattn_fwd_long(a, s);  // long rows, and lengths that are not a power of two
+namespace {
+// Which kernel runs the forward: k_la_long.hip, k_la_small.hip, k_la_rows_fwd.hip or the register-resident one, each only when its launcher
+// takes every argument
+enum LaFwdForm { LA_FWD_LONG, LA_FWD_SMALL, LA_FWD_ROWS, LA_FWD_REG };
+LaFwdForm la_fwd_form(const LinAttn& a) {
+  if (!la_short_row(a.n)) return LA_FWD_LONG;
   if (a.prep && la_small_usable(a.C, a.n) && a.rows >= la_small_min_rows() &&
-      (((uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)a.ypre) & 15) == 0)  // (its tiles move as 16-byte runs)
-    return launch_la_small_fwd(a, s);
+      (((uintptr_t)a.prep | (uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)a.ypre) & 15) == 0)  // (its tiles move as 16-byte runs)
+    return LA_FWD_SMALL;
   // rows of 2 / 4 positions below that threshold (training batches): one m/z row per lane column (k_la_rows_fwd.hip), wherever the rows
   // backward is in use (the same option switches both: a run with the register-resident forms forced keeps the register forward)
   if (a.prep && la_rows_fwd_usable(a.C, a.n) && a.rows >= la_rows_bwd_min_rows() && (((uintptr_t)a.x | (uintptr_t)a.prep) & 15) == 0)
-    return launch_la_rows_fwd(a, s);
+    return LA_FWD_ROWS;
+  return LA_FWD_REG;
+}
+}  // namespace
+
+int launch_linattn_fwd(const LinAttn& a, hipStream_t s) {
+  DQ_REQUIRE(a.x && a.y && a.w_qkv && a.w_out && a.b_out && a.g_pre && a.g_out, "linattn_fwd: missing operand");
+  if (a.rows == 0) return 0;
+  switch (la_fwd_form(a)) {
+    case LA_FWD_LONG: return launch_linattn_fwd_long(a, s);
+    case LA_FWD_SMALL: return launch_la_small_fwd(a, s);
+    case LA_FWD_ROWS: return launch_la_rows_fwd(a, s);
+    case LA_FWD_REG: break;
+  }
   switch (a.C) {
     case 4: return linattn_fwd_n<4>(a, s);
     case 8: return linattn_fwd_n<8>(a, s);

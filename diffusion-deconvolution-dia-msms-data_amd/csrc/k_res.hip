@@ -6,8 +6,8 @@
 // registers; the +-1 neighbours a k=3 conv needs of an intermediate (a1 forward; dU2, dU1 backward) are exchanged through
 // LDS inside the block.  A block covers 256 consecutive positions of ONE sample (grid = (blocks per sample, B)); rows never
 // straddle blocks because the row length divides 256 -- or, at the bottleneck, because a sample IS one row (its RT axis, up to 512
-// positions) and gets one block of 256 / 512 threads; the launcher refuses anything else (longer RT axes keep the unfused path).
-// Weight gradients stay in k_conv_wgrad (they read dU1 / dU2 written here).
+// positions) and gets one block of 256 / 512 threads.  Weight gradients stay in k_conv_wgrad (they read dU1 / dU2 written here).
+// res_fwd_form / res_bwd_form below choose between these kernels, the specialised ones of k_res_*.hip and the unfused path of dq_unet.hip.
 #include "dq_common.h"
 #include "dq_kernels.h"
 #include "k_res_common.h"
@@ -181,27 +181,34 @@ __global__ void __launch_bounds__(BS) k_res_fwd(ResFwd a) {
   for (int co = 0; co < C; ++co) a.out[obase + (int64_t)co * a.n] = o[co];
 }
 
-// m/z levels: many rows per sample, the row length divides the block's 256 positions.  Bottleneck: ONE row per sample (its RT axis) of
-// up to 512 positions = one block per sample, whatever the length (no row can straddle a block then).
-bool res_fusable(int n, int C, int rows_per_sample) {
-  if (!(C == 4 || C == 8 || C == 12 || C == 16) || n < 1) return false;
-  return rows_per_sample == 1 ? (n <= 512 || C == 16) : (n <= 256 && (256 % n) == 0);  // (C == 16: k_res_rt.hip takes any RT length)
-}
 namespace {
+// k_res_fwd / k_res_bwd: m/z levels with many rows per sample whose length divides the block's 256 positions, or the bottleneck's ONE row
+// per sample (its RT axis) of up to 512 positions = one block per sample
+bool res_plain_rows(int n, int C, int rows_per_sample) {
+  if (!(C == 4 || C == 8 || C == 12 || C == 16) || n < 1) return false;
+  return rows_per_sample == 1 ? n <= 512 : (n <= 256 && (256 % n) == 0);
+}
 int res_block_size(int n, int rows_per_sample) { return rows_per_sample == 1 && n > 256 ? 512 : 256; }
 }
 
+ResFwdForm res_fwd_form(int C, int cinA, int cinB, bool has_wr, int n, int rows_per_sample) {
+  if (res_rt_usable(C, cinA, cinB, has_wr, rows_per_sample)) return RES_FWD_RT;            // the bottleneck's blocks
+  if (res_mm_usable(n, C, cinA, cinB, rows_per_sample, has_wr)) return RES_FWD_MM;         // m/z rows of up to 64 positions
+  if (rows_per_sample > 1 && res_cp_usable(n, C, cinA, cinB)) return RES_FWD_CP;
+  if (rows_per_sample > 1 && res_v4_usable(n, C, cinA, cinB)) return RES_FWD_V4;
+  if (res_plain_rows(n, C, rows_per_sample) && cinA == C && cinB <= C) return RES_FWD_PLAIN;
+  return RES_FWD_UNFUSED;
+}
+
 int launch_res_fwd(const ResFwd& a, hipStream_t s) {
-  DQ_REQUIRE(res_fusable(a.n, a.C, a.rows_per_sample), "res_fwd: row length must divide 256 (or one row of <= 512 per sample) and C be 4/8/12/16");
   DQ_REQUIRE(a.rows % a.rows_per_sample == 0, "res_fwd: rows must be a multiple of rows_per_sample");
   DQ_REQUIRE(a.wr || (a.cinA == a.C && a.cinB == 0), "res_fwd: identity residual needs C input channels");
-  if (res_rt_usable(a.C, a.cinA, a.cinB, a.wr != nullptr, a.rows_per_sample)) return launch_res_rt_fwd(a, s);  // the bottleneck's blocks
-  // m/z rows of up to 64 positions: the convolutions on the matrix pipe (k_res_mm.hip)
-  if (res_mm_usable(a.n, a.C, a.cinA, a.cinB, a.rows_per_sample, a.wr != nullptr)) return launch_res_fwd_mm(a, s);
-  if (a.rows_per_sample > 1 && res_cp_usable(a.n, a.C, a.cinA, a.cinB)) return launch_res_fwd_cp(a, s);
-  if (a.rows_per_sample > 1 && res_v4_usable(a.n, a.C, a.cinA, a.cinB)) return launch_res_fwd_v4(a, s);
-  DQ_REQUIRE(a.cinA == a.C && a.cinB <= a.C && (a.cinB == 0 || a.inB), "res_fwd: input must be C channels (+ at most C skip channels)");
-  DQ_REQUIRE(a.rows_per_sample > 1 || a.n <= 512, "res_fwd: one RT row per sample longer than 512 positions needs the 16-channel identity block");
+  const ResFwdForm form = res_fwd_form(a.C, a.cinA, a.cinB, a.wr != nullptr, a.n, a.rows_per_sample);
+  if (form == RES_FWD_RT) return launch_res_rt_fwd(a, s);
+  if (form == RES_FWD_MM) return launch_res_fwd_mm(a, s);
+  if (form == RES_FWD_CP) return launch_res_fwd_cp(a, s);
+  if (form == RES_FWD_V4) return launch_res_fwd_v4(a, s);
+  DQ_REQUIRE(form == RES_FWD_PLAIN && (a.cinB == 0 || a.inB), "res_fwd: no fused kernel takes this block (dq_unet.hip runs it unfused) or skip input missing");
   const int B = a.rows / a.rows_per_sample;
   const int BS = res_block_size(a.n, a.rows_per_sample);
   dim3 grid(cdiv((int64_t)a.rows_per_sample * a.n, BS), B), block(BS);
@@ -359,16 +366,25 @@ __global__ void __launch_bounds__(BS) k_res_bwd(ResBwd a) {
   }
 }
 
+ResBwdForm res_bwd_form(const ResBwd& a, bool wg) {
+  if (wg) return RES_BWD_WG;
+  if (res_rt_usable(a.C, a.cinA, a.cinB, a.wr != nullptr, a.rows_per_sample)) return RES_BWD_RT;  // the bottleneck's blocks
+  if (res_rows_bwd_usable(a)) return RES_BWD_ROWS;                                               // the deep levels: m/z row = lane column
+  if (a.rows_per_sample > 1 && res_cp_usable(a.n, a.C, a.cinA, a.cinB)) return RES_BWD_CP;
+  if (res_plain_rows(a.n, a.C, a.rows_per_sample) && a.cinA + a.cinB <= 2 * a.C) return RES_BWD_PLAIN;
+  return RES_BWD_UNFUSED;
+}
+
 int launch_res_bwd(const ResBwd& a, hipStream_t s) {
-  DQ_REQUIRE(res_fusable(a.n, a.C, a.rows_per_sample), "res_bwd: row length must divide 256 (or one row of <= 512 per sample) and C be 4/8/12/16");
   DQ_REQUIRE(a.rows % a.rows_per_sample == 0, "res_bwd: rows must be a multiple of rows_per_sample");
   DQ_REQUIRE(a.wr || (a.cinA == a.C && a.cinB == 0), "res_bwd: identity residual needs C input channels");
   DQ_REQUIRE(a.cinA + a.cinB <= 2 * a.C, "res_bwd: a block input wider than two C-channel tensors is not built");
   if (a.gblocks) *a.gblocks = 0;
-  if (res_rt_usable(a.C, a.cinA, a.cinB, a.wr != nullptr, a.rows_per_sample)) return launch_res_rt_bwd(a, s);  // the bottleneck's blocks
-  DQ_REQUIRE(a.rows_per_sample > 1 || a.n <= 512, "res_bwd: one RT row per sample longer than 512 positions needs the 16-channel identity block");
-  if (res_rows_bwd_usable(a)) return launch_res_rows_bwd(a, s);  // the deep levels: m/z row = lane column
-  if (a.rows_per_sample > 1 && res_cp_usable(a.n, a.C, a.cinA, a.cinB)) return launch_res_bwd_cp(a, s);
+  const ResBwdForm form = res_bwd_form(a, false);
+  if (form == RES_BWD_RT) return launch_res_rt_bwd(a, s);
+  if (form == RES_BWD_ROWS) return launch_res_rows_bwd(a, s);
+  if (form == RES_BWD_CP) return launch_res_bwd_cp(a, s);
+  DQ_REQUIRE(form == RES_BWD_PLAIN, "res_bwd: no fused kernel takes this block (dq_unet.hip runs it unfused)");
   const int B = a.rows / a.rows_per_sample;
   const int BS = res_block_size(a.n, a.rows_per_sample);
   dim3 grid(cdiv((int64_t)a.rows_per_sample * a.n, BS), B), block(BS);

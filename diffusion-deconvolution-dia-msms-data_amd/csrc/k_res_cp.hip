@@ -396,6 +396,7 @@ bool res_cp_usable(int n, int C, int cinA, int cinB) {
 }
 
 int launch_res_fwd_cp(const ResFwd& a, hipStream_t s) {
+  DQ_REQUIRE(a.rows_per_sample > 1 && res_cp_usable(a.n, a.C, a.cinA, a.cinB), "res_fwd_cp: unsupported shape");
   const int B = a.rows / a.rows_per_sample;
   // training batches: one 16-row group per block (parallelism); sampling batches: up to 8 groups per block while >= ~2048
   // blocks remain, so that the per-block weight staging amortises
@@ -411,6 +412,7 @@ int launch_res_fwd_cp(const ResFwd& a, hipStream_t s) {
 }
 
 int launch_res_bwd_cp(const ResBwd& a, hipStream_t s) {
+  DQ_REQUIRE(a.rows_per_sample > 1 && res_cp_usable(a.n, a.C, a.cinA, a.cinB), "res_bwd_cp: unsupported shape");
   const int B = a.rows / a.rows_per_sample;
   dim3 grid(cdiv(a.rows_per_sample, GR), B), block(256);
   ResBwd k = a;  // partial sums of the norm gains and scale / shift (see ResBwd::gpart)

@@ -210,6 +210,7 @@ bool res_v4_usable(int n, int C, int cinA, int cinB) {
 }
 
 int launch_res_fwd_v4(const ResFwd& a, hipStream_t s) {
+  DQ_REQUIRE(a.rows_per_sample > 1 && res_v4_usable(a.n, a.C, a.cinA, a.cinB), "res_fwd_v4: unsupported shape");
   const int B = a.rows / a.rows_per_sample;
   dim3 grid(cdiv((int64_t)a.rows_per_sample * (a.n / 4), 256), B), block(256);
   if (a.C == 4) {

@@ -159,7 +159,13 @@ def test_resnet_block_fixture_forward(N, golden, name, split):
                                                        # longer than the 512 the thread-per-position kernel took
                                                        (16, 16, 1, 5, 1, 0), (16, 16, 2, 3, 1, 0), (16, 16, 11, 3, 1, 0), (16, 16, 12, 2, 1, 0), (16, 16, 13, 4, 1, 0),
                                                        (16, 16, 14, 2, 1, 0), (16, 16, 15, 2, 1, 0), (16, 16, 47, 2, 1, 0), (16, 16, 49, 2, 1, 0), (16, 16, 57, 2, 1, 0),
-                                                       (16, 16, 413, 2, 1, 0), (16, 16, 700, 2, 1, 0), (16, 16, 2000, 1, 1, 0)])
+                                                       (16, 16, 413, 2, 1, 0), (16, 16, 700, 2, 1, 0), (16, 16, 2000, 1, 1, 0),
+                                                       # a 16-channel block with a skip input and a res_conv over an RT axis longer than 512: the
+                                                       # unfused conv path
+                                                       (32, 16, 700, 2, 1, 16),
+                                                       # the deep levels' rows backward (k_res_rows.hip, >= 16 rows per CU) with a partly filled last
+                                                       # 16-row tile per sample (98 rows per sample)
+                                                       (24, 12, 4, 4214, 98, 12)])
 def test_resnet_block_backward_vs_oracle_autograd(N, cin, cout, n, rows, rps, split):
     """every dispatch of the ResnetBlock (fused m/z-row kernels, channel-parallel deep levels, the step-by-step bottleneck path
     with rows_per_sample = 1): forward, dX, all weight gradients and d(scale, shift) against autograd over the oracle"""
