@@ -111,7 +111,7 @@ int launch_conv_wgrad(const ConvWgrad& a, hipStream_t s);
 // up to three stride-1 convs over the same (rows, n) in one launch + one merged reduce (each with its own scratch region)
 int launch_conv_wgrad_multi(const ConvWgrad* w, int count, hipStream_t s);
 
-// ---- k_res.hip : fused ResnetBlock over m/z rows whose length divides 256
+// ---- a ResnetBlock's operands (k_res*.hip; k_level.hip reads the fields of its blocks)
 struct ResFwd {
   const float* inA = nullptr; const float* inB = nullptr; int cinA = 0, cinB = 0;  // input = cat(A, B)
   const float* w1 = nullptr; const float* b1 = nullptr; const float* g1 = nullptr;   // block1 conv (C, cin, 3), bias, norm gain
@@ -139,10 +139,11 @@ struct ResBwd {
   float* gpart = nullptr; int64_t gpart_floats = 0; int* gblocks = nullptr;
   int C = 0, rows = 0, n = 0, rows_per_sample = 1;
 };
-// Which ResnetBlock kernel runs (in order of preference): k_res_{rt,mm,cp,v4,rows,wg}.hip, k_res.hip (PLAIN) or the conv launches of dq_unet.hip
-// (UNFUSED).  wg: the block's buffers were laid out for k_res_bwd_wg (ResBuf::wpart_floats != 0).
-enum ResFwdForm { RES_FWD_RT, RES_FWD_MM, RES_FWD_CP, RES_FWD_V4, RES_FWD_PLAIN, RES_FWD_UNFUSED };
-ResFwdForm res_fwd_form(int C, int cinA, int cinB, bool has_wr, int n, int rows_per_sample);
+// Which ResnetBlock kernel runs (in order of preference).  Forward: k_res_rt.hip, a one-block k_level_fwd launch (LEVEL), k_res_v4.hip or the
+// conv launches of dq_unet.hip (UNFUSED).  Backward: k_res_{wg,rt,rows,cp}.hip, k_res.hip (PLAIN) or UNFUSED; wg: the block's buffers were
+// laid out for k_res_bwd_wg (ResBuf::wpart_floats != 0).
+enum ResFwdForm { RES_FWD_RT, RES_FWD_LEVEL, RES_FWD_V4, RES_FWD_UNFUSED };
+ResFwdForm res_fwd_form(int C, int cinA, int cinB, bool has_wr, int rows, int n, int rows_per_sample);
 enum ResBwdForm { RES_BWD_WG, RES_BWD_RT, RES_BWD_ROWS, RES_BWD_CP, RES_BWD_PLAIN, RES_BWD_UNFUSED };
 ResBwdForm res_bwd_form(const ResBwd& a, bool wg);
 // k_res_rt.hip: the bottleneck's 16-channel blocks (one RT row per sample, identity residual, no skip input) with the RT position as the lane
@@ -168,9 +169,8 @@ struct ResRtPre {
   const float* rope = nullptr; float* gn_part = nullptr; int64_t gn_part_floats = 0;
 };
 int launch_res_rt_bwd(const ResBwd& a, hipStream_t s, const ResRtPre* q = nullptr, const ResRtOut* ao = nullptr);
-// k_res_cp.hip: channel-parallel variant for the deep levels (n <= 8, C = 12 / 16)
+// k_res_cp.hip: channel-parallel backward for the deep levels (n <= 8, C = 12 / 16)
 bool res_cp_usable(int n, int C, int cinA, int cinB);
-int launch_res_fwd_cp(const ResFwd& a, hipStream_t s);
 int launch_res_bwd_cp(const ResBwd& a, hipStream_t s);
 // k_res_rows.hip: the deep levels' backward data path with the m/z row as the lane column of v_mfma_f32_16x16x4 (12 / 16 channels, rows of
 // 2 / 4 / 8 positions, 16-byte aligned tensors)
@@ -179,9 +179,6 @@ int launch_res_rows_bwd(const ResBwd& a, hipStream_t s);
 // k_res_v4.hip: 4-positions-per-thread forward for the wide levels (C = 4 / 8, n >= 8)
 bool res_v4_usable(int n, int C, int cinA, int cinB);
 int launch_res_fwd_v4(const ResFwd& a, hipStream_t s);
-// k_res_mm.hip: forward with the convolutions on the 4x4x1 matrix pipe (rows of 1..64 positions, C = 4 / 8 / 12 / 16)
-bool res_mm_usable(int n, int C, int cinA, int cinB, int rows_per_sample, bool has_wr);
-int launch_res_fwd_mm(const ResFwd& a, hipStream_t s);
 enum LevelPre { LEVEL_PRE_NONE = 0, LEVEL_PRE_DOWN = 1, LEVEL_PRE_UP = 2, LEVEL_PRE_S1 = 3, LEVEL_PRE_INIT = 4 };
 // k_level.hip: [resample conv that produces the level's input] -> ResnetBlock (-> ResnetBlock) in ONE launch, convolutions on the
 // matrix pipe (rows of 1..64 positions).  blk[i].inA / cinA are unused (a block's first input is in registers); blk[i].out == null:
@@ -218,14 +215,16 @@ struct LevelFwd {
   // parameter values -- the kernel's workgroups then copy it to LDS instead of gathering it from the parameter tensors themselves
   const float* img = nullptr;
 };
-bool level_fwd_usable(int C, int n, int rows_per_sample, int pre_mode, int cp, int nblocks, const ResFwd* blk);
+// the shapes launch_level_fwd takes: block b's input is cat(x of C channels, cinB[b] skip channels), has_wr[b]: it has a res_conv
+bool level_fwd_usable(int C, int rows, int n, int rows_per_sample, int pre_mode, int cp, int nblocks, const int* cinB, const bool* has_wr);
+bool level_fwd_usable(const LevelFwd& a);
 int launch_level_fwd(const LevelFwd& a, hipStream_t s);
 constexpr int LEVEL_LOSS_PARTS = 8192;     // floats behind LevelFwd::loss_part (one per wave of a resident round: 6 x 256 workgroups x 4)
 constexpr int LEVEL_IMG_MAX = 20;          // launches per launch_level_images call
 constexpr int LEVEL_IMG_FLOATS = 8192;     // upper bound of level_img_floats over the built instantiations (16 channels, 32-channel blocks)
 int64_t level_img_floats(const LevelFwd& a);
 int launch_level_images(const LevelFwd* calls, int count, hipStream_t s);  // writes calls[i].img (must be set) for every call, ONE launch
-int launch_res_fwd(const ResFwd& a, hipStream_t s);
+int launch_res_fwd(const ResFwd& a, hipStream_t s);  // the RT and V4 forms
 int launch_res_bwd(const ResBwd& a, hipStream_t s);
 
 // k_tiny.hip: the levels with rows of 1 or 2 positions as a chain of dense layers on v_mfma_f32_32x32x2 (lane = (position | row half, row),

@@ -249,23 +249,38 @@ static inline bool side_flush_here(int lv) { return (lv & 1) == 0; }
     if (_rc) return _rc;        \
   } while (0)
 
+// a ResnetBlock's operands but its first input (what a block of the level kernel reads): the second input (skip channels), the parameters and
+// where its results go (wpart: the backward recomputes a1)
+ResFwd level_block(const Ctx& c, const ResP& r, const ResBuf& b, const float* inB, int cinB, bool write_out) {
+  ResFwd k;
+  k.inB = cinB ? inB : nullptr; k.cinB = cinB;
+  k.w1 = c.prm(r.c1.w); k.b1 = c.prm(r.c1.b); k.g1 = c.prm(r.g1);
+  k.w2 = c.prm(r.c2.w); k.b2 = c.prm(r.c2.b); k.g2 = c.prm(r.g2);
+  if (r.res.cout) { k.wr = c.prm(r.res.w); k.br = c.prm(r.res.b); }
+  k.ss = c.w(c.ar.ss) + r.ss_off; k.ss_stride = c.p.ss_total;
+  if (c.save) { k.u1 = c.w(b.u1); k.a1 = b.wpart_floats ? nullptr : c.w(b.a1); k.u2 = c.w(b.u2); }
+  k.out = (write_out || c.save) ? c.w(b.out) : nullptr;
+  return k;
+}
+
 // ResnetBlock forward (unet1d.py:302-323): input = cat(A, B)
 int res_fwd(const Ctx& c, const ResP& r, const ResBuf& b, const float* inA, int cinA, const float* inB, int cinB, int rows, int n,
             int rows_per_sample, const ResRtQkv* qkv = nullptr, const ResRtOut* aout = nullptr) {  // qkv / aout: the attention's front rides behind the block / its back in front of it (k_res_rt.hip; the caller checked for RES_FWD_RT)
-  if (res_fwd_form(r.cout, cinA, cinB, r.res.cout != 0, n, rows_per_sample) != RES_FWD_UNFUSED) {  // one fused launch
-    ResFwd k;
-    k.inA = inA; k.inB = inB; k.cinA = cinA; k.cinB = cinB;
-    k.w1 = c.prm(r.c1.w); k.b1 = c.prm(r.c1.b); k.g1 = c.prm(r.g1);
-    k.w2 = c.prm(r.c2.w); k.b2 = c.prm(r.c2.b); k.g2 = c.prm(r.g2);
-    if (r.res.cout) { k.wr = c.prm(r.res.w); k.br = c.prm(r.res.b); }
-    k.ss = c.w(c.ar.ss) + r.ss_off; k.ss_stride = c.p.ss_total;
-    if (c.save) { k.u1 = c.w(b.u1); k.a1 = b.wpart_floats ? nullptr : c.w(b.a1); k.u2 = c.w(b.u2); }  // (wpart: the backward recomputes a1)
-    k.out = c.w(b.out);
+  const ResFwdForm form = res_fwd_form(r.cout, cinA, cinB, r.res.cout != 0, rows, n, rows_per_sample);
+  DQ_REQUIRE(form == RES_FWD_RT || (!qkv && !aout), "res_fwd: the attention front / back needs the fused 16-channel block");
+  if (form != RES_FWD_UNFUSED) {  // one fused launch
+    ResFwd k = level_block(c, r, b, inB, cinB, /*write_out=*/true);
+    if (form == RES_FWD_LEVEL) {  // one block of the level kernel, no input stage
+      LevelFwd f;
+      f.params = c.P; f.in = inA; f.pre = LEVEL_PRE_NONE; f.nblocks = 1; f.blk[0] = k;
+      f.C = r.cout; f.rows = rows; f.n = n; f.rows_per_sample = rows_per_sample;
+      return launch_level_fwd(f, c.s);
+    }
+    k.inA = inA; k.cinA = cinA;
     k.C = r.cout; k.rows = rows; k.n = n; k.rows_per_sample = rows_per_sample;
     if (qkv || aout) return launch_res_rt_fwd(k, c.s, qkv, aout);
     return launch_res_fwd(k, c.s);
   }
-  DQ_REQUIRE(!qkv && !aout, "res_fwd: the attention front / back needs the fused 16-channel block");
   DQ_REQUIRE(b.a1 != b.u1, "res_fwd: a block laid out for the fused weight-gradient backward has no a1 tensor (cat(x, skip) with x of cout channels)");
   ConvFwd f;
   f.inA = inA; f.inB = inB; f.cinA = cinA; f.cinB = cinB;
@@ -828,18 +843,6 @@ bool level_kernels_enabled() {
   const bool on = !DQ_DEV_FLAG("DQ_NO_LEVEL_FWD", '1');  // (dev switch)
   return on;
 }
-// a block of the level kernel: its second input (skip channels) and where its results go
-ResFwd level_block(const Ctx& c, const ResP& r, const ResBuf& b, const float* inB, int cinB, bool write_out) {
-  ResFwd k;
-  k.inB = cinB ? inB : nullptr; k.cinB = cinB;
-  k.w1 = c.prm(r.c1.w); k.b1 = c.prm(r.c1.b); k.g1 = c.prm(r.g1);
-  k.w2 = c.prm(r.c2.w); k.b2 = c.prm(r.c2.b); k.g2 = c.prm(r.g2);
-  if (r.res.cout) { k.wr = c.prm(r.res.w); k.br = c.prm(r.res.b); }
-  k.ss = c.w(c.ar.ss) + r.ss_off; k.ss_stride = c.p.ss_total;
-  if (c.save) { k.u1 = c.w(b.u1); k.a1 = b.wpart_floats ? nullptr : c.w(b.a1); k.u2 = c.w(b.u2); }
-  k.out = (write_out || c.save) ? c.w(b.out) : nullptr;
-  return k;
-}
 struct LevelCall {
   int pre = LEVEL_PRE_NONE; const ConvP* pc = nullptr; const float* in = nullptr; float* pre_out = nullptr;
   int C = 0, n = 0, nblocks = 0;
@@ -876,8 +879,7 @@ bool level_ok(const Ctx& c, const LevelCall& lc) {
   for (int i = 0; i < lc.nblocks; ++i)
     if (lc.r[i]->cout != lc.C || lc.r[i]->cin != lc.C + lc.cinB[i]) return false;
   if (lc.pc && (lc.pc->cout != lc.C || lc.pc->b < 0)) return false;
-  const LevelFwd f = level_desc(c, lc);
-  return level_fwd_usable(f.C, f.n, f.rows_per_sample, f.pre, f.cp, f.nblocks, f.blk);
+  return level_fwd_usable(level_desc(c, lc));
 }
 
 int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t* t, int t_scalar, const float* init_cond,
@@ -1076,7 +1078,7 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
   } else {
     if (!mid_in_done) DQ_TRY(launch_fold(cur, c.w(a.mid_in), B, RT, p.mid_c, 1, 0, c.s));
     // 16 channels (the default U-Net): PreNorm, to_qv, to_k and RoPE ride behind mid_block1 (k_res_rt.hip)
-    const bool qkv_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid1.res.cout != 0, RT, 1) == RES_FWD_RT && HID == 128 && p.cond_dim == 8 &&
+    const bool qkv_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid1.res.cout != 0, B, RT, 1) == RES_FWD_RT && HID == 128 && p.cond_dim == 8 &&
                            !DQ_DEV_FLAG("DQ_NO_MID_QKV", '1');  // (dev switch)
     if (qkv_fused) {
       ResRtQkv q;
@@ -1102,7 +1104,7 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
       const int64_t qvbs = (int64_t)2 * HID * RT, kbs = (int64_t)HID * RT;
       DQ_TRY(launch_attn_fwd(c.w(a.qv), qvbs, c.w(a.kk), kbs, c.w(a.qv) + kbs, qvbs, c.w(a.o), c.w(a.lse), B, RT, c.s));
       // 16 channels: to_out (1x1 + bias) and the residual are formed in FRONT of mid_block2, inside its launch (k_res_rt.hip)
-      out_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid2.res.cout != 0, RT, 1) == RES_FWD_RT && HID == 128 && !DQ_DEV_FLAG("DQ_NO_MID_OUT", '1');  // (dev switch)
+      out_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid2.res.cout != 0, B, RT, 1) == RES_FWD_RT && HID == 128 && !DQ_DEV_FLAG("DQ_NO_MID_OUT", '1');  // (dev switch)
       if (!out_fused) {
       const ConvP ao = proj(p.ao_w, p.mid_c, HID);
       if (conv_is_gemm(c, ao, CONV_S1, RT, RT) && (prep_ok || ((uintptr_t)c.prm(ao.w) & 15) == 0)) {
@@ -1260,7 +1262,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
   } else {
     if (!use_tb_up) DQ_TRY(launch_fold(c.g(a.mid_back), c.g(a.mid2.out), B, RT, p.mid_c, 1, 1, c.s));  // (the tiny backward wrote d mid2.out itself)
     // 16 channels: d o = W_o^T d attn_out follows mid_block2's d x inside its launch (k_res_rt.hip); to_out's weight gradient stays below
-    const bool out_bwd_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid2.res.cout != 0, RT, 1) == RES_FWD_RT && HID == 128 && !DQ_DEV_FLAG("DQ_NO_MID_OUT", '1');  // (dev switch)
+    const bool out_bwd_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid2.res.cout != 0, B, RT, 1) == RES_FWD_RT && HID == 128 && !DQ_DEV_FLAG("DQ_NO_MID_OUT", '1');  // (dev switch)
     if (out_bwd_fused) {
       ResRtOut ao;
       ao.w = c.prm(p.ao_w); ao.d_o = c.g(a.o);
@@ -1287,7 +1289,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
       // the side queue -- behind the next flush's fork event, i.e. behind mid_block1's backward, which has read d q by then.
       // (without a side queue -- the captured step, a plan without an owner -- the same launches follow mid_block1's backward on the main stream:
       // the arithmetic, and with it every bit of the step, does not depend on the schedule)
-      const bool pre_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid1.res.cout != 0, RT, 1) == RES_FWD_RT && HID == 128 &&
+      const bool pre_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid1.res.cout != 0, B, RT, 1) == RES_FWD_RT && HID == 128 &&
                              a.bb_part_floats >= (int64_t)64 * B * p.mid_c && !DQ_DEV_FLAG("DQ_NO_MID_PRE", '1');  // (dev switch)
       if (pre_fused) {
         const ConvP kp = proj(p.k_w, HID, p.cond_dim), qp = proj(p.qv_w, 2 * HID, p.mid_c);
@@ -2152,7 +2154,7 @@ int dq_level_fwd(const float* params, int pre, const float* x, int cp, const flo
   }
   // a workspace with room for the operand image behind the scale / shift vectors: built by its own launch first, as the network path does
   const int64_t img_at = ((int64_t)2 * B * p.ss_total + 63) / 64 * 64;
-  if (((uintptr_t)workspace & 15) == 0 && workspace_floats >= img_at + level_img_floats(f) && level_fwd_usable(C, n, rows_per_sample, pre, f.cp, nblocks, f.blk)) {
+  if (((uintptr_t)workspace & 15) == 0 && workspace_floats >= img_at + level_img_floats(f) && level_fwd_usable(f)) {
     f.img = workspace + img_at;
     DQ_TRY(launch_level_images(&f, 1, s));
   }

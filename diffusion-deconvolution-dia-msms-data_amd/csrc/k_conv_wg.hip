@@ -4,7 +4,7 @@
 // twice.
 //
 // Thread = output position q of the conv (a wave = 64 consecutive positions = whole rows, n <= 64):
-//   data gradient  : the transposed conv in the lane = position form of k_res_mm.hip (B operand = the register holding dY[co], one DPP
+//   data gradient  : the transposed conv in the lane = position form of k_level.hip (B operand = the register holding dY[co], one DPP
 //                    wave shift for the neighbours; A operand = W[co][4 gi + (lane & 3)][k] from an LDS operand image):
 //                      DOWN: d in[2 q] = sum_co W[.][.][1] dY[q] + W[.][.][3] dY[q - 1],  d in[2 q + 1] = sum_co W[.][.][2] dY[q] + W[.][.][0] dY[q + 1]
 //                            (stored as one 8-byte pair per channel)

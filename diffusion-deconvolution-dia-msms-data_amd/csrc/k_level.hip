@@ -1,9 +1,22 @@
 // One launch for the convolutional part of a U-Net level (reference dquartic/model/unet1d.py:1134-1142, 1150-1158, 1160-1163):
 //   [ the resample conv that produces the level's input: Downsample k4 s2 | Upsample nearest x2 + k3 | k3 (last levels) ]
 //   -> ResnetBlock -> ResnetBlock
-// with every convolution on the 4x4x1 matrix pipe in the lane = position layout of k_res_mm.hip.  The level's input never goes
-// to memory in inference (the resampled tensor `rs` and, on the way down, the re-read of block 1's output disappear), and the four
-// launches of a level become two (this + the LinearAttention).
+// with every convolution on the 4x4x1 matrix pipe.  The level's input never goes to memory in inference (the resampled tensor `rs` and,
+// on the way down, the re-read of block 1's output disappear), and the four launches of a level become two (this + the LinearAttention).
+// One block without an input stage is also how a lone ResnetBlock over such rows runs (res_fwd_form's LEVEL form, k_res.hip).
+//
+// Why the matrix pipe: with a thread per position and the channels in registers, every FMA of a conv needs its weight as a wave-uniform
+// operand.  The 200..1,700 weights of a block fit neither the scalar registers nor (unrolled) the vector registers, so such kernels
+// (k_res_v4.hip) read them from LDS as broadcasts -- about one LDS instruction per FMA instruction -- and run at 0.2-0.3 of the HBM rate
+// they are meant to stream at.  v_mfma_f32_4x4x1 turns the roles around: of its 16 independent (4 x 1)(1 x 4) outer products, block
+// blk = lane / 4 takes  A[i] = W[4 g + i][c][k]  from lane (blk, i) and  B[j] = x[c][position of lane (blk, j) + k - 1]  from lane
+// (blk, j) and adds  A[i] B[j]  to register i of lane (blk, j).  With lane = position that is: the B operand IS the register that holds
+// input channel c (shifted by one lane for the outer taps: two DPP wave shifts per channel), the result lands as "output channel 4 g + i
+// of this lane's position in register i" -- the layout the norm / activation code wants -- and the weight operand is one register per
+// (g, c, k) job whose value depends only on lane & 3: an LDS image [job / 4][lane & 3][job % 4], read 16 bytes (four jobs) at a time.
+// One LDS instruction per four MFMAs (1,024 multiply-adds each) instead of one per 64-lane FMA; the VALU is left with the norms and
+// activations.  Same MAC rate as unpacked VALU FMAs, on the otherwise idle pipe, bit-for-bit an fp32 FMA chain per output.  A wave owns
+// 64 consecutive positions of one sample = 64 / n whole rows (n = 1 .. 64, a power of two): no conv neighbour crosses a wave.
 //
 // Input stage, lane q = output position of the level (row length n):
 //   DOWN: out[q] = sum_k w[k] in[2 q - 1 + k]   -- the lane loads in[2 q], in[2 q + 1] (8 bytes); in[2 q - 1] is lane q - 1's second
@@ -661,16 +674,20 @@ static int num_cus() {
   return v;
 }
 
-bool level_fwd_usable(int C, int n, int rows_per_sample, int pre_mode, int cp, int nblocks, const ResFwd* blk) {
+bool level_fwd_usable(int C, int rows, int n, int rows_per_sample, int pre_mode, int cp, int nblocks, const int* cinB, const bool* has_wr) {
   if (!(C == 4 || C == 8 || C == 12 || C == 16) || n < 1 || n > 64 || (n & (n - 1)) != 0 || rows_per_sample <= 1) return false;
   if (nblocks < 1 || nblocks > 2) return false;
   if (!level_cp_built(C, pre_mode, cp)) return false;
   if (pre_mode == LEVEL_PRE_UP && n < 2) return false;
-  for (int b = 0; b < nblocks; ++b) {
-    const ResFwd& r = blk[b];
-    if (r.cinB % 4 != 0 || r.cinB < 0 || r.cinB > C || (r.cinB > 0) != (r.wr != nullptr)) return false;
-  }
-  return true;
+  for (int b = 0; b < nblocks; ++b)
+    if (cinB[b] % 4 != 0 || cinB[b] < 0 || cinB[b] > C || (cinB[b] > 0) != has_wr[b]) return false;
+  // tensors of 2^31 elements or more are not built (32-bit offsets)
+  return (int64_t)rows * 2 * std::max(C, cp) * std::max(n, 2) * 4 < (1ll << 32);
+}
+bool level_fwd_usable(const LevelFwd& a) {
+  const int cinB[2] = {a.blk[0].cinB, a.blk[1].cinB};
+  const bool has_wr[2] = {a.blk[0].wr != nullptr, a.blk[1].wr != nullptr};
+  return level_fwd_usable(a.C, a.rows, a.n, a.rows_per_sample, a.pre, a.cp, a.nblocks, cinB, has_wr);
 }
 
 static int level_img_item(const LevelFwd& a, LevelImgSrc* m) {
@@ -697,7 +714,7 @@ int launch_level_images(const LevelFwd* calls, int count, hipStream_t s) {
   for (int i = 0; i < count; ++i) {
     const LevelFwd& a = calls[i];
     DQ_REQUIRE(a.img && ((uintptr_t)a.img & 15) == 0 && a.params, "level images: missing / misaligned image buffer");
-    DQ_REQUIRE(level_fwd_usable(a.C, a.n, a.rows_per_sample, a.pre, a.cp, a.nblocks, a.blk), "level images: unsupported shape");
+    DQ_REQUIRE(level_fwd_usable(a), "level images: unsupported shape");
     DQ_REQUIRE(a.params == calls[0].params, "level images: the launches must share one parameter buffer");
     level_img_item(a, &mm.it[i].m);
     mm.it[i].dst = const_cast<float*>(a.img);
@@ -711,7 +728,7 @@ int launch_level_images(const LevelFwd* calls, int count, hipStream_t s) {
 }
 
 int launch_level_fwd(const LevelFwd& a, hipStream_t s) {
-  DQ_REQUIRE(level_fwd_usable(a.C, a.n, a.rows_per_sample, a.pre, a.cp, a.nblocks, a.blk), "level_fwd: unsupported shape");
+  DQ_REQUIRE(level_fwd_usable(a), "level_fwd: unsupported shape");
   DQ_REQUIRE(a.rows % a.rows_per_sample == 0 && a.in && a.params, "level_fwd: bad rows / missing input");
   DQ_REQUIRE(a.pre == LEVEL_PRE_NONE || (a.pw && a.pb), "level_fwd: the input stage needs its conv weight and bias");
   LevelFwdK k;
@@ -745,7 +762,6 @@ int launch_level_fwd(const LevelFwd& a, hipStream_t s) {
   const int tiles_ps = cdiv((int64_t)a.rows_per_sample * a.n, 64);
   const int64_t total = (int64_t)tiles_ps * B;
   DQ_REQUIRE(total < (1ll << 31), "level_fwd: too many tiles");
-  DQ_REQUIRE((int64_t)a.rows * 2 * std::max(a.C, a.cp) * std::max(a.n, 2) * 4 < (1ll << 32), "level_fwd: tensors of 2^31 elements or more are not built (32-bit offsets)");
   int ln = 0;
   while ((1 << ln) < a.n) ++ln;
   const int cin[2] = {a.C + a.blk[0].cinB, a.C + a.blk[1].cinB};

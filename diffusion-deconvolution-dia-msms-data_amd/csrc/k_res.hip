@@ -1,13 +1,12 @@
-// Fused ResnetBlock kernels for the m/z levels (reference dquartic/model/unet1d.py:271-323):
-//   forward : conv3 -> RMSNorm -> (scale+1, shift) -> SiLU -> conv3 -> RMSNorm -> SiLU, + res_conv(x) | x      (one launch)
-//   backward: the whole data path  d out -> dU2 -> d a1 -> dU1 -> d x  incl. the residual branch, d g1/g2 and the per-sample
-//             d(scale)/d(shift)                                                                                 (one launch)
-// instead of 2 and 5-6 launches of the generic kernels in k_conv.hip.  Thread = (row, position), all channels in
-// registers; the +-1 neighbours a k=3 conv needs of an intermediate (a1 forward; dU2, dU1 backward) are exchanged through
-// LDS inside the block.  A block covers 256 consecutive positions of ONE sample (grid = (blocks per sample, B)); rows never
-// straddle blocks because the row length divides 256 -- or, at the bottleneck, because a sample IS one row (its RT axis, up to 512
-// positions) and gets one block of 256 / 512 threads.  Weight gradients stay in k_conv_wgrad (they read dU1 / dU2 written here).
-// res_fwd_form / res_bwd_form below choose between these kernels, the specialised ones of k_res_*.hip and the unfused path of dq_unet.hip.
+// Fused ResnetBlock backward for the m/z levels (reference dquartic/model/unet1d.py:271-323): the whole data path
+//   d out -> dU2 -> d a1 -> dU1 -> d x  incl. the residual branch, d g1/g2 and the per-sample d(scale)/d(shift)          (one launch)
+// instead of 5-6 launches of the generic kernels in k_conv.hip.  Thread = (row, position), all channels in registers; the +-1 neighbours
+// a k=3 conv needs of an intermediate (dU2, dU1) are exchanged through LDS inside the block.  A block covers 256 consecutive positions of
+// ONE sample (grid = (blocks per sample, B)); rows never straddle blocks because the row length divides 256 -- or, at the bottleneck,
+// because a sample IS one row (its RT axis, up to 512 positions) and gets one block of 256 / 512 threads.  Weight gradients stay in
+// k_conv_wgrad (they read dU1 / dU2 written here).
+// res_fwd_form / res_bwd_form below choose between this kernel, the specialised ones of k_res_*.hip and k_level.hip, and the unfused
+// path of dq_unet.hip.
 #include "dq_common.h"
 #include "dq_kernels.h"
 #include "k_res_common.h"
@@ -53,136 +52,8 @@ __device__ __forceinline__ void stage_res_weights(float* w2s, float* w1s, float*
   for (int u = 0; u < NR; ++u) { const int i = u * BS + (int)threadIdx.x; if (i < nr) wrs[i] = vr[u]; }
 }
 
-// HB: the block has skip channels (cat(A, B)).  Without them (the bottleneck's blocks, the down path) the B-side registers do not exist:
-// <16, 512> held 255 registers + 60 spilled ones with them (two waves per SIMD at 512 threads).
-template <int C, int BS, bool HB>
-__global__ void __launch_bounds__(BS) k_res_fwd(ResFwd a) {
-  __shared__ float sh[C][BS + 2];
-  // the block's weights in LDS (broadcast reads): as scalar loads from memory inside the channel loops nothing overlapped their latency
-  // -- 33 us for the bottleneck's 16-channel block, one workgroup per sample
-  __shared__ float w2s[C * C * 3], w1s[C * 2 * C * 3], wrs[C * 2 * C];
-  const int cin = a.cinA + a.cinB;  // <= 2 C (checked by the launcher)
-  stage_res_weights<C, BS>(w2s, w1s, wrs, a.w2, a.w1, a.wr, cin);
-  __syncthreads();
-  const int b = blockIdx.y;
-  const int per_sample = a.rows_per_sample * a.n;
-  const bool wave_local = a.n <= 64 && (64 % a.n) == 0;
-  const int it = blockIdx.x * BS + threadIdx.x;
-  const bool live = it < per_sample;
-  const int row = b * a.rows_per_sample + (live ? it / a.n : 0), p = live ? it % a.n : 0;
-  const float sqC = sqrtf((float)C);
-  float acc[C];
-  // ---- conv1 (k3, zero padding) over cat(A, B)
-#pragma unroll
-  for (int co = 0; co < C; ++co) acc[co] = a.b1[co];
-  // cat(A, B) has cinA == C channels from A (launcher-checked) and cinB <= C from B: every load of the thread is issued
-  // up front from compile-time-unrolled loops -- a runtime ci loop serialised one exposed global latency per channel
-  float xa[C][3], xb[HB ? C : 1][3];
-#pragma unroll
-  for (int ci = 0; ci < C; ++ci) {
-    const float* src = a.inA + ((int64_t)row * C + ci) * a.n;
-    xa[ci][0] = (live && p > 0) ? src[p - 1] : 0.f;
-    xa[ci][1] = live ? src[p] : 0.f;
-    xa[ci][2] = (live && p + 1 < a.n) ? src[p + 1] : 0.f;
-  }
-#pragma unroll
-  for (int ci = 0; ci < (HB ? C : 0); ++ci) {
-    const bool ok = live && ci < a.cinB;
-    const float* src = a.inB + ((int64_t)row * a.cinB + ci) * a.n;
-    xb[ci][0] = (ok && p > 0) ? src[p - 1] : 0.f;
-    xb[ci][1] = ok ? src[p] : 0.f;
-    xb[ci][2] = (ok && p + 1 < a.n) ? src[p + 1] : 0.f;
-  }
-#pragma unroll
-  for (int ci = 0; ci < C; ++ci)
-#pragma unroll
-    for (int co = 0; co < C; ++co) {
-      const float* w = w1s + (co * cin + ci) * 3;
-      acc[co] = fmaf(w[0], xa[ci][0], fmaf(w[1], xa[ci][1], fmaf(w[2], xa[ci][2], acc[co])));
-    }
-  if (HB && a.cinB) {
-#pragma unroll
-    for (int ci = 0; ci < (HB ? C : 0); ++ci) {
-      if (ci < a.cinB) {
-#pragma unroll
-        for (int co = 0; co < C; ++co) {
-          const float* w = w1s + (co * cin + C + ci) * 3;
-          acc[co] = fmaf(w[0], xb[ci][0], fmaf(w[1], xb[ci][1], fmaf(w[2], xb[ci][2], acc[co])));
-        }
-      }
-    }
-  }
-  const int64_t obase = ((int64_t)row * C) * a.n + p;
-  if (live && a.u1) {
-#pragma unroll
-    for (int co = 0; co < C; ++co) a.u1[obase + (int64_t)co * a.n] = acc[co];
-  }
-  {
-    float ssq = 0.f;
-#pragma unroll
-    for (int co = 0; co < C; ++co) ssq = fmaf(acc[co], acc[co], ssq);
-    const float inv = rms_inv(ssq, sqC);
-    const float* ss = a.ss + (int64_t)b * a.ss_stride;
-#pragma unroll
-    for (int co = 0; co < C; ++co) acc[co] = silu_f(fmaf(acc[co] * inv * a.g1[co], ss[co] + 1.0f, ss[C + co]));
-  }
-  if (live && a.a1) {
-#pragma unroll
-    for (int co = 0; co < C; ++co) a.a1[obase + (int64_t)co * a.n] = acc[co];
-  }
-  // ---- neighbours of a1 through LDS (zero outside the row)
-#pragma unroll
-  for (int co = 0; co < C; ++co) sh[co][threadIdx.x + 1] = live ? acc[co] : 0.f;
-  exch_sync(wave_local);
-  float o[C];
-#pragma unroll
-  for (int co = 0; co < C; ++co) o[co] = a.b2[co];
-  const bool hasL = p > 0, hasR = p + 1 < a.n;
-#pragma unroll 1
-  for (int ci = 0; ci < C; ++ci) {  // not unrolled: C*C*3 weights would not fit in registers
-    const float x0 = hasL ? sh[ci][threadIdx.x] : 0.f, x1 = sh[ci][threadIdx.x + 1], x2 = hasR ? sh[ci][threadIdx.x + 2] : 0.f;
-    const float* w = w2s + ci * 3;
-#pragma unroll
-    for (int co = 0; co < C; ++co) o[co] = fmaf(w[co * C * 3 + 0], x0, fmaf(w[co * C * 3 + 1], x1, fmaf(w[co * C * 3 + 2], x2, o[co])));
-  }
-  if (!live) return;
-  if (a.u2) {
-#pragma unroll
-    for (int co = 0; co < C; ++co) a.u2[obase + (int64_t)co * a.n] = o[co];
-  }
-  {
-    float ssq = 0.f;
-#pragma unroll
-    for (int co = 0; co < C; ++co) ssq = fmaf(o[co], o[co], ssq);
-    const float inv = rms_inv(ssq, sqC);
-#pragma unroll
-    for (int co = 0; co < C; ++co) o[co] = silu_f(o[co] * inv * a.g2[co]);
-  }
-  // ---- residual: 1x1 conv over cat(A, B) or identity
-  if (a.wr) {
-#pragma unroll
-    for (int co = 0; co < C; ++co) o[co] += a.br[co];
-#pragma unroll
-    for (int ci = 0; ci < C; ++ci)
-#pragma unroll
-      for (int co = 0; co < C; ++co) o[co] = fmaf(wrs[co * cin + ci], xa[ci][1], o[co]);
-#pragma unroll
-    for (int ci = 0; ci < (HB ? C : 0); ++ci) {
-      if (ci < a.cinB) {
-#pragma unroll
-        for (int co = 0; co < C; ++co) o[co] = fmaf(wrs[co * cin + C + ci], xb[ci][1], o[co]);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int co = 0; co < C; ++co) o[co] += xa[co][1];
-  }
-#pragma unroll
-  for (int co = 0; co < C; ++co) a.out[obase + (int64_t)co * a.n] = o[co];
-}
-
 namespace {
-// k_res_fwd / k_res_bwd: m/z levels with many rows per sample whose length divides the block's 256 positions, or the bottleneck's ONE row
+// k_res_bwd: m/z levels with many rows per sample whose length divides the block's 256 positions, or the bottleneck's ONE row
 // per sample (its RT axis) of up to 512 positions = one block per sample
 bool res_plain_rows(int n, int C, int rows_per_sample) {
   if (!(C == 4 || C == 8 || C == 12 || C == 16) || n < 1) return false;
@@ -191,38 +62,21 @@ bool res_plain_rows(int n, int C, int rows_per_sample) {
 int res_block_size(int n, int rows_per_sample) { return rows_per_sample == 1 && n > 256 ? 512 : 256; }
 }
 
-ResFwdForm res_fwd_form(int C, int cinA, int cinB, bool has_wr, int n, int rows_per_sample) {
-  if (res_rt_usable(C, cinA, cinB, has_wr, rows_per_sample)) return RES_FWD_RT;            // the bottleneck's blocks
-  if (res_mm_usable(n, C, cinA, cinB, rows_per_sample, has_wr)) return RES_FWD_MM;         // m/z rows of up to 64 positions
-  if (rows_per_sample > 1 && res_cp_usable(n, C, cinA, cinB)) return RES_FWD_CP;
+ResFwdForm res_fwd_form(int C, int cinA, int cinB, bool has_wr, int rows, int n, int rows_per_sample) {
+  if (res_rt_usable(C, cinA, cinB, has_wr, rows_per_sample)) return RES_FWD_RT;  // the bottleneck's blocks
+  // m/z rows of up to 64 positions: one block, no input stage
+  if (cinA == C && level_fwd_usable(C, rows, n, rows_per_sample, LEVEL_PRE_NONE, 0, 1, &cinB, &has_wr)) return RES_FWD_LEVEL;
   if (rows_per_sample > 1 && res_v4_usable(n, C, cinA, cinB)) return RES_FWD_V4;
-  if (res_plain_rows(n, C, rows_per_sample) && cinA == C && cinB <= C) return RES_FWD_PLAIN;
   return RES_FWD_UNFUSED;
 }
 
 int launch_res_fwd(const ResFwd& a, hipStream_t s) {
   DQ_REQUIRE(a.rows % a.rows_per_sample == 0, "res_fwd: rows must be a multiple of rows_per_sample");
   DQ_REQUIRE(a.wr || (a.cinA == a.C && a.cinB == 0), "res_fwd: identity residual needs C input channels");
-  const ResFwdForm form = res_fwd_form(a.C, a.cinA, a.cinB, a.wr != nullptr, a.n, a.rows_per_sample);
+  const ResFwdForm form = res_fwd_form(a.C, a.cinA, a.cinB, a.wr != nullptr, a.rows, a.n, a.rows_per_sample);
   if (form == RES_FWD_RT) return launch_res_rt_fwd(a, s);
-  if (form == RES_FWD_MM) return launch_res_fwd_mm(a, s);
-  if (form == RES_FWD_CP) return launch_res_fwd_cp(a, s);
-  if (form == RES_FWD_V4) return launch_res_fwd_v4(a, s);
-  DQ_REQUIRE(form == RES_FWD_PLAIN && (a.cinB == 0 || a.inB), "res_fwd: no fused kernel takes this block (dq_unet.hip runs it unfused) or skip input missing");
-  const int B = a.rows / a.rows_per_sample;
-  const int BS = res_block_size(a.n, a.rows_per_sample);
-  dim3 grid(cdiv((int64_t)a.rows_per_sample * a.n, BS), B), block(BS);
-#define DQ_RF(CC)                                                                \
-  case CC:                                                                       \
-    if (BS == 512 && a.cinB) hipLaunchKernelGGL((k_res_fwd<CC, 512, true>), grid, block, 0, s, a);  \
-    else if (BS == 512) hipLaunchKernelGGL((k_res_fwd<CC, 512, false>), grid, block, 0, s, a);      \
-    else if (a.cinB) hipLaunchKernelGGL((k_res_fwd<CC, 256, true>), grid, block, 0, s, a);          \
-    else hipLaunchKernelGGL((k_res_fwd<CC, 256, false>), grid, block, 0, s, a);                     \
-    break;
-  switch (a.C) { DQ_RF(4) DQ_RF(8) DQ_RF(12) DQ_RF(16) }
-#undef DQ_RF
-  DQ_LAUNCH_CHECK();
-  return 0;
+  DQ_REQUIRE(form == RES_FWD_V4, "res_fwd: the LEVEL form runs through launch_level_fwd, the UNFUSED one through dq_unet.hip");
+  return launch_res_fwd_v4(a, s);
 }
 
 // -----------------------------------------------------------------------------------------------------------------

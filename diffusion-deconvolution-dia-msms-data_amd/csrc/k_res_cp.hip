@@ -1,24 +1,20 @@
-// Fused ResnetBlock for the DEEP m/z levels (rows of 1..8 positions, 12 or 16 channels; reference
+// Fused ResnetBlock backward data path for the DEEP m/z levels (rows of 1..8 positions, 12 or 16 channels; reference
 // dquartic/model/unet1d.py:271-323), "channel-parallel" mapping.
 //
 // At these levels a (row, position) thread of k_res.hip runs a serial chain of ~1,500 dependent FMAs while the whole level
 // only has 12,800 x n of them: 256 waves on 1,024 SIMDs, pure latency.  Here 16 lanes own one ROW and lane = channel: a lane
-// computes ITS output channel of both convs for the row's n positions, the channel reductions of RMSNorm are 4 DPP-style
-// exchanges inside the 16-lane group, and the operand a lane needs from all channels (the row's input, then the block-1
-// activation) is staged in LDS as [position + halo][channel] and read as broadcast 16-byte loads.  Weights are staged once
-// per block as [ci/4][tap][co][4 ci] so a lane's 4 weights for 4 input channels are one ds_read_b128.  16x more waves, each
-// 16x shorter.  A block = 16 rows of ONE sample (per-sample scale/shift and their gradients need no search).
-// Same arithmetic order over (ci, tap) as k_res.hip up to the 4-channel grouping of the FMA chain; results agree to fp32
-// rounding (parity tests: tests/test_hip_forward.py, tests/test_hip_backward.py run every level through these kernels).
+// computes ITS channel of the two transposed convs (d a1, then d x) for the row's n positions, the channel reductions of the
+// RMSNorm backward are 4 DPP-style exchanges inside the 16-lane group, and the operands a lane needs from all channels (dU2, dU1,
+// d out) are staged in LDS as [position + halo][channel] and read as broadcast 16-byte loads.  Weights are staged once per block,
+// transposed, as [co/4][tap][ci][4 co] so a lane's 4 weights for 4 output channels are one ds_read_b128.  16x more waves, each
+// 16x shorter.  A block = 16 rows of ONE sample (the per-sample d(scale)/d(shift) sums need no search).
 #include "dq_common.h"
 #include "dq_kernels.h"
-#include <algorithm>
 
 namespace dq {
 
 namespace {
 constexpr int GR = 16;   // rows (16-lane groups) per 256-thread block
-constexpr int CI = 32;   // staged input channels (cat(A, B): <= 16 + 16)
 
 // sum over the 16 lanes of a group (all lanes receive it)
 __device__ __forceinline__ float gsum16(float v) {  // four DPP adds inside the 16-lane row, no LDS
@@ -33,30 +29,10 @@ __device__ __forceinline__ float gsum16(float v) {  // four DPP adds inside the 
   return v;
 }
 
-// stage W (cout x cin x K, row-major [co][ci][k]) as dst[((ci4 * K + k) * 16 + co) * 4 + (ci & 3)], zero padded to 16 x cin_pad
-// (256 threads.  Every element's load is requested before the first store, no load is predicated: as a loop striding by blockDim.x -- not
-// unrollable -- of `decode, branch, load, store` the three weight tensors of a block cost 14 memory round trips in a row per workgroup:
-// the 14 channel-parallel backward launches of a train step 276 -> 251 us.)
-template <int K>
-__device__ __forceinline__ void stage_w(float* dst, const float* __restrict__ w, int cout, int cin, int cin_pad) {
-  constexpr int NIT = 32 * K * 16 / 256;  // cin_pad <= 32
-  float v[NIT];
-  const int total = cin_pad * K * 16;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = it * 256 + (int)threadIdx.x;
-    const int q = i & 3, co = (i >> 2) & 15, k = (i >> 6) % K, ci = ((i >> 6) / K) * 4 + q;
-    const bool ok = i < total && co < cout && ci < cin;
-    v[it] = w[ok ? (co * cin + ci) * K + k : 0];
-  }
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = it * 256 + (int)threadIdx.x;
-    const int q = i & 3, co = (i >> 2) & 15, ci = ((i >> 6) / K) * 4 + q;
-    if (i < total) dst[i] = (co < cout && ci < cin) ? v[it] : 0.f;
-  }
-}
-// transposed roles for the backward data path: dst[((co4 * K + k) * 32 + ci) * 4 + (co & 3)] = W[co][ci][k]
+// stage W (cout x cin x K, row-major [co][ci][k]) with the roles of the backward data path: dst[((co4 * K + k) * 32 + ci) * 4 + (co & 3)] =
+// W[co][ci][k], zero padded to 16 x 32.  (256 threads.  Every element's load is requested before the first store, no load is predicated: as a
+// loop striding by blockDim.x -- not unrollable -- of `decode, branch, load, store` the three weight tensors of a block cost 14 memory round
+// trips in a row per workgroup: the 14 channel-parallel backward launches of a train step 276 -> 251 us.)
 template <int K>
 __device__ __forceinline__ void stage_wt(float* dst, const float* __restrict__ w, int cout, int cin) {
   constexpr int NIT = 16 * K * 32 / 256;
@@ -75,140 +51,6 @@ __device__ __forceinline__ void stage_wt(float* dst, const float* __restrict__ w
   }
 }
 }  // namespace
-
-template <int C, int N>
-__global__ void __launch_bounds__(256) k_res_fwd_cp(ResFwd a, int iters) {  // iters: 16-row groups per block (weights staged once)
-  __shared__ __attribute__((aligned(16))) float w1s[CI * 3 * 16];
-  __shared__ __attribute__((aligned(16))) float w2s[16 * 3 * 16];
-  __shared__ __attribute__((aligned(16))) float wrs[CI * 16];
-  __shared__ __attribute__((aligned(16))) float xs[GR][N + 2][CI];
-  __shared__ __attribute__((aligned(16))) float ys[GR][N + 2][16];
-  const int cin = a.cinA + a.cinB, cin4 = (cin + 3) >> 2;
-  const int g = threadIdx.x >> 4, co = threadIdx.x & 15;
-  const int b = blockIdx.y;
-  const bool act = co < C;
-
-  stage_w<3>(w1s, a.w1, C, cin, cin4 * 4);
-  stage_w<3>(w2s, a.w2, C, C, 16);
-  if (a.wr) stage_w<1>(wrs, a.wr, C, cin, cin4 * 4);
-  for (int i = threadIdx.x; i < GR * (N + 2) * CI; i += blockDim.x) (&xs[0][0][0])[i] = 0.f;
-  for (int i = threadIdx.x; i < GR * (N + 2) * 16; i += blockDim.x) (&ys[0][0][0])[i] = 0.f;
-  // Large batches: a block walks `iters` groups of 16 rows with the weights staged once.  A group's xs / ys slice is only ever
-  // touched by its own 16 lanes; the halo slots and the unused channels are never written again and stay zero.
-#pragma unroll 1
-  for (int itr = 0; itr < iters; ++itr) {
-  const int rs = (blockIdx.x * iters + itr) * GR + g;
-  const bool live = rs < a.rows_per_sample;
-  const int row = b * a.rows_per_sample + (live ? rs : 0);
-  __syncthreads();
-  if (live) {
-#pragma unroll
-    for (int p = 0; p < N; ++p) {
-      if (co < a.cinA) xs[g][p + 1][co] = a.inA[((int64_t)row * a.cinA + co) * N + p];
-      if (co < a.cinB) xs[g][p + 1][a.cinA + co] = a.inB[((int64_t)row * a.cinB + co) * N + p];
-    }
-  }
-  __syncthreads();
-
-  const float sqC = sqrtf((float)C);
-  float acc[N];
-  // ---- conv1 (k3, zero padding) over cat(A, B): this lane's output channel
-  {
-    const float bias = act ? a.b1[co] : 0.f;
-#pragma unroll
-    for (int p = 0; p < N; ++p) acc[p] = bias;
-    for (int c4 = 0; c4 < cin4; ++c4) {
-      float4 x4[N + 2];
-#pragma unroll
-      for (int q = 0; q < N + 2; ++q) x4[q] = *reinterpret_cast<const float4*>(&xs[g][q][c4 * 4]);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float4 w4 = *reinterpret_cast<const float4*>(&w1s[((c4 * 3 + k) * 16 + co) * 4]);
-#pragma unroll
-        for (int p = 0; p < N; ++p)
-          acc[p] = fmaf(w4.x, x4[p + k].x, fmaf(w4.y, x4[p + k].y, fmaf(w4.z, x4[p + k].z, fmaf(w4.w, x4[p + k].w, acc[p]))));
-      }
-    }
-  }
-  const int64_t obase = ((int64_t)row * C + co) * N;
-  if (live && act && a.u1) {
-#pragma unroll
-    for (int p = 0; p < N; ++p) a.u1[obase + p] = acc[p];
-  }
-  {
-    const float g1 = act ? a.g1[co] : 0.f;
-    const float* ss = a.ss + (int64_t)b * a.ss_stride;
-    const float sc = act ? ss[co] + 1.0f : 0.f, sh = act ? ss[C + co] : 0.f;
-#pragma unroll
-    for (int p = 0; p < N; ++p) {
-      const float ssq = gsum16(acc[p] * acc[p]);
-      const float inv = rms_inv(ssq, sqC);
-      acc[p] = act ? silu_f(fmaf(acc[p] * inv * g1, sc, sh)) : 0.f;
-    }
-  }
-  if (live && act && a.a1) {
-#pragma unroll
-    for (int p = 0; p < N; ++p) a.a1[obase + p] = acc[p];
-  }
-#pragma unroll
-  for (int p = 0; p < N; ++p) ys[g][p + 1][co] = acc[p];
-  __syncthreads();
-  // ---- conv2 (k3) over the block-1 activation
-  float o[N];
-  {
-    const float bias = act ? a.b2[co] : 0.f;
-#pragma unroll
-    for (int p = 0; p < N; ++p) o[p] = bias;
-#pragma unroll
-    for (int c4 = 0; c4 < C / 4; ++c4) {
-      float4 y4[N + 2];
-#pragma unroll
-      for (int q = 0; q < N + 2; ++q) y4[q] = *reinterpret_cast<const float4*>(&ys[g][q][c4 * 4]);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float4 w4 = *reinterpret_cast<const float4*>(&w2s[((c4 * 3 + k) * 16 + co) * 4]);
-#pragma unroll
-        for (int p = 0; p < N; ++p)
-          o[p] = fmaf(w4.x, y4[p + k].x, fmaf(w4.y, y4[p + k].y, fmaf(w4.z, y4[p + k].z, fmaf(w4.w, y4[p + k].w, o[p]))));
-      }
-    }
-  }
-  if (live && act && a.u2) {
-#pragma unroll
-    for (int p = 0; p < N; ++p) a.u2[obase + p] = o[p];
-  }
-  {
-    const float g2 = act ? a.g2[co] : 0.f;
-#pragma unroll
-    for (int p = 0; p < N; ++p) {
-      const float ssq = gsum16(o[p] * o[p]);
-      const float inv = rms_inv(ssq, sqC);
-      o[p] = silu_f(o[p] * inv * g2);
-    }
-  }
-  // ---- residual: 1x1 conv over cat(A, B) or identity
-  if (a.wr) {
-    const float br = act ? a.br[co] : 0.f;
-#pragma unroll
-    for (int p = 0; p < N; ++p) o[p] += br;
-    for (int c4 = 0; c4 < cin4; ++c4) {
-      const float4 w4 = *reinterpret_cast<const float4*>(&wrs[(c4 * 16 + co) * 4]);
-#pragma unroll
-      for (int p = 0; p < N; ++p) {
-        const float4 x4 = *reinterpret_cast<const float4*>(&xs[g][p + 1][c4 * 4]);
-        o[p] = fmaf(w4.x, x4.x, fmaf(w4.y, x4.y, fmaf(w4.z, x4.z, fmaf(w4.w, x4.w, o[p]))));
-      }
-    }
-  } else {
-#pragma unroll
-    for (int p = 0; p < N; ++p) o[p] += xs[g][p + 1][co];
-  }
-  if (live && act) {
-#pragma unroll
-    for (int p = 0; p < N; ++p) a.out[obase + p] = o[p];
-  }
-  }  // itr
-}
 
 // -----------------------------------------------------------------------------------------------------------------
 // backward data path (same outputs as k_res_bwd: dU2, dU1 for the weight-gradient kernels, dA/dB +=, per-block partial sums of dg1/dg2/dss)
@@ -393,22 +235,6 @@ __global__ void __launch_bounds__(256) k_res_bwd_cp(ResBwd a) {
 
 bool res_cp_usable(int n, int C, int cinA, int cinB) {
   return (C == 12 || C == 16) && (n == 1 || n == 2 || n == 4 || n == 8) && cinA <= 16 && cinB <= 16;
-}
-
-int launch_res_fwd_cp(const ResFwd& a, hipStream_t s) {
-  DQ_REQUIRE(a.rows_per_sample > 1 && res_cp_usable(a.n, a.C, a.cinA, a.cinB), "res_fwd_cp: unsupported shape");
-  const int B = a.rows / a.rows_per_sample;
-  // training batches: one 16-row group per block (parallelism); sampling batches: up to 8 groups per block while >= ~2048
-  // blocks remain, so that the per-block weight staging amortises
-  const int groups = cdiv(a.rows_per_sample, GR);
-  const int iters = std::max(1, std::min({8, groups, (int)((int64_t)groups * B / 2048)}));
-  dim3 grid(cdiv(groups, iters), B), block(256);
-#define DQ_CP(CC, NN) \
-  if (a.C == CC && a.n == NN) { hipLaunchKernelGGL((k_res_fwd_cp<CC, NN>), grid, block, 0, s, a, iters); DQ_LAUNCH_CHECK(); return 0; }
-  DQ_CP(12, 1) DQ_CP(12, 2) DQ_CP(12, 4) DQ_CP(12, 8) DQ_CP(16, 1) DQ_CP(16, 2) DQ_CP(16, 4) DQ_CP(16, 8)
-#undef DQ_CP
-  set_error("res_fwd_cp: unsupported (C, n)");
-  return 2;
 }
 
 int launch_res_bwd_cp(const ResBwd& a, hipStream_t s) {

@@ -1,8 +1,8 @@
 // Fused ResnetBlock FORWARD for the wide m/z levels (4 or 8 channels, rows of 8..256 positions; reference
 // dquartic/model/unet1d.py:271-323): a thread owns 4 CONSECUTIVE positions of one row.
 //
-// Same fusion as k_res_fwd (conv3 -> RMSNorm -> (scale+1, shift) -> SiLU -> conv3 -> RMSNorm -> SiLU -> + res_conv(x) | x, one
-// launch), but every global access is a 16-byte load / store (a quarter of the memory instructions of the one-position
+// The whole block in one launch (conv3 -> RMSNorm -> (scale+1, shift) -> SiLU -> conv3 -> RMSNorm -> SiLU -> + res_conv(x) | x),
+// every global access a 16-byte load / store (a quarter of the memory instructions of a thread-per-position
 // mapping, which left these HBM-streaming kernels at ~1.2 TB/s at sampling batch sizes), the +-1 neighbours of the conv
 // inputs come from the thread's own registers except at the two edges of its group (two scalar loads for x; the block-1
 // activation's edges go through LDS, ordered by a wave-level fence: a row's n/4 <= 64 threads always sit in one wave).

@@ -12,7 +12,7 @@
 //     consecutive positions, so the operand of tap k - 1 / k + 1 is the centre operand of the previous / next step (one LDS read
 //     per step and input-channel quad serves three MFMAs); the (co quad, ci quad, tap) jobs are split over the four waves,
 //   * the data path's own (transposed) convolutions  d a1 = W2^T * dU2,  d x = W1^T * dU1 + Wr^T d out  run on the matrix pipe too, in the
-//     lane = position form of k_res_mm.hip: B operand = the register holding dU[co] (one DPP wave shift for the outer taps), A
+//     lane = position form of k_level.hip: B operand = the register holding dU[co] (one DPP wave shift for the outer taps), A
 //     operand = W[co][4 g + (lane & 3)][k] from an LDS operand image, result = "channel 4 g + i of this lane's position in register i".
 //     (As VALU FMAs with the weights read from LDS as broadcasts -- one LDS instruction per FMA -- this kernel took 3-4x longer than
 //     the data path + the separate weight-gradient launches it replaces.)

@@ -165,7 +165,10 @@ def test_resnet_block_fixture_forward(N, golden, name, split):
                                                        (32, 16, 700, 2, 1, 16),
                                                        # the deep levels' rows backward (k_res_rows.hip, >= 16 rows per CU) with a partly filled last
                                                        # 16-row tile per sample (98 rows per sample)
-                                                       (24, 12, 4, 4214, 98, 12)])
+                                                       (24, 12, 4, 4214, 98, 12),
+                                                       # the unfused forward with several rows per sample: rows of 128 at 12 channels (backward
+                                                       # k_res_bwd), a 6-channel skip (backward k_res_bwd_cp); k_res_fwd_v4 with a skip input
+                                                       (12, 12, 128, 8, 4, 0), (22, 16, 4, 96, 48, 16), (8, 4, 128, 12, 4, 4)])
 def test_resnet_block_backward_vs_oracle_autograd(N, cin, cout, n, rows, rps, split):
     """every dispatch of the ResnetBlock (fused m/z-row kernels, channel-parallel deep levels, the step-by-step bottleneck path
     with rows_per_sample = 1): forward, dX, all weight gradients and d(scale, shift) against autograd over the oracle"""
