@@ -52,6 +52,13 @@ __device__ __forceinline__ float silu_grad_f(float x) {
   float s = fast_rcp(1.0f + __expf(-x));
   return s * (1.0f + x * (1.0f - s));
 }
+// torch.nn.Softplus() (beta 1, threshold 20), the arithmetic of PyTorch's kernels: x > 20 ? x : log1p(exp(x)); its derivative
+// x > 20 ? 1 : z / (z + 1), z = exp(x) (full-precision expf / log1pf: the network's output, compared at 1e-4)
+__device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
+__device__ __forceinline__ float softplus_grad_f(float x) {
+  const float z = expf(x);
+  return x > 20.f ? 1.f : z / (z + 1.f);
+}
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float gelu_grad_f(float x) {
   return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * __expf(-0.5f * x * x);

@@ -42,7 +42,7 @@ int launch_copy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst
 
 // ---- k_conv.hip
 enum ConvMode { CONV_S1 = 0, CONV_DOWN = 1, CONV_UP = 2 };  // stride-1 'same' | k4 s2 p1 | nearest x2 then k3 p1
-enum Act { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2 };
+enum Act { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_SOFTPLUS = 3 };  // ACT_SOFTPLUS: the network's final_conv only (k_conv_fwd<1, 1, 0>)
 
 struct ConvFwd {
   // input = channel-concat of A (cinA) and B (cinB); tensors are (rows, C, n) with n contiguous
@@ -110,6 +110,11 @@ constexpr int WGRAD_MAX_PARTS = 512;
 int launch_conv_wgrad(const ConvWgrad& a, hipStream_t s);
 // up to three stride-1 convs over the same (rows, n) in one launch + one merged reduce (each with its own scratch region)
 int launch_conv_wgrad_multi(const ConvWgrad* w, int count, hipStream_t s);
+
+// backward of the Softplus behind final_conv (1x1, cin -> 1, with bias): dpre (rows, n) = dy * softplus'(pre), the pre-activation
+// recomputed from the conv's input fin (rows, cin, n), weight w (cin) and bias b (1) -- nothing of the forward is stored for it
+int launch_softplus_head_bwd(const float* fin, const float* w, const float* b, int cin, const float* dy, float* dpre, int rows, int n,
+                             hipStream_t s);
 
 // ---- a ResnetBlock's operands (k_res*.hip; k_level.hip reads the fields of its blocks)
 struct ResFwd {
@@ -180,6 +185,7 @@ int launch_res_rows_bwd(const ResBwd& a, hipStream_t s);
 bool res_v4_usable(int n, int C, int cinA, int cinB);
 int launch_res_fwd_v4(const ResFwd& a, hipStream_t s);
 enum LevelPre { LEVEL_PRE_NONE = 0, LEVEL_PRE_DOWN = 1, LEVEL_PRE_UP = 2, LEVEL_PRE_S1 = 3, LEVEL_PRE_INIT = 4 };
+enum FinalAct { FINAL_IDENTITY = 0, FINAL_SOFTPLUS = 1 };  // = DQ_FINAL_* of include/dq_hip.h (Plan::final_act)
 // k_level.hip: [resample conv that produces the level's input] -> ResnetBlock (-> ResnetBlock) in ONE launch, convolutions on the
 // matrix pipe (rows of 1..64 positions).  blk[i].inA / cinA are unused (a block's first input is in registers); blk[i].out == null:
 // that block's output is not written (inference, up path); pre_out: where the input stage's result is kept (training) or null.
@@ -206,10 +212,14 @@ struct LevelFwd {
   const float* x_t = nullptr; float* x_out = nullptr; const float* coef = nullptr; const int* step_ptr = nullptr; int pred_x0 = 0;
   // training head (with ew / eb; the block's output is still written): loss_z = the regression target (rows, n).  d = eps - z; the squared-error
   // sums go to loss_part, one float per WAVE of the grid (*loss_parts_out receives their number: sum them in index order); grad_out (rows, n) =
-  // d * loss_gscale (= d loss / d eps) and dout (rows, 4, n) = ew[c] * grad_out (final_conv's backward data path): what k_conv_fwd<1,1,0>,
+  // d * loss_gscale (= d loss / d eps) -- times softplus'(pre) under final_act = FINAL_SOFTPLUS: always d loss / d (final_conv's output, before
+  // the activation) -- and dout (rows, 4, n) = ew[c] * grad_out (final_conv's backward data path): what k_conv_fwd<1,1,0>,
   // k_mse_fwd_bwd and k_conv_bwd_data<4,1,0> did in three launches behind this one
   const float* loss_z = nullptr; float* loss_part = nullptr; float* grad_out = nullptr; float* dout = nullptr; float loss_gscale = 0.f;
   int* loss_parts_out = nullptr;
+  // output activation of the head (FINAL_IDENTITY | FINAL_SOFTPLUS, with ew): with Softplus, eps_out, the DDIM update and the training
+  // head's loss see y = softplus(final_conv(out))
+  int final_act = 0;
   int C = 0, rows = 0, n = 0, rows_per_sample = 1;
   // nullable: this launch's MFMA operand image (level_img_floats floats, 16-byte aligned) as launch_level_images built it from the SAME
   // parameter values -- the kernel's workgroups then copy it to LDS instead of gathering it from the parameter tensors themselves

@@ -56,6 +56,7 @@ struct Plan {
   int cond_dim = 0;       // attn_cond_init_dim = 2*dim (unet1d.py:970)
   int ss_total = 0;       // floats per sample in the ss vector (all ResnetBlock mlps + init_cond_proj)
   int ss_init = 0;        // offset of init_cond_proj's [scale, shift]
+  int final_act = 0;      // output activation behind final_conv (DQ_FINAL_IDENTITY | DQ_FINAL_SOFTPLUS; dq_plan_set_final_act)
 
   std::vector<ParamInfo> params;
   int64_t total_floats = 0;

@@ -653,8 +653,10 @@ int gemm_weight(const Ctx& c, const ConvP& cp, const float** w, int slot) {
 }
 
 // wslot: aligned weight slot prepared by the forward (-1: none; the GEMM route is then only taken for an aligned weight)
-int conv_plain_fwd(const Ctx& c, const ConvP& cp, int mode, const float* in, float* out, int rows, int n_in, int n_out, int wslot = -1) {
-  if (conv_is_gemm(c, cp, mode, n_in, n_out) && (wslot >= 0 || ((uintptr_t)c.prm(cp.w) & 15) == 0)) {
+// act: ACT_NONE, or ACT_SOFTPLUS for final_conv of a pos_output_only network (the epilogue of its k_conv_fwd<1, 1, 0>)
+int conv_plain_fwd(const Ctx& c, const ConvP& cp, int mode, const float* in, float* out, int rows, int n_in, int n_out, int wslot = -1,
+                   int act = ACT_NONE) {
+  if (act == ACT_NONE && conv_is_gemm(c, cp, mode, n_in, n_out) && (wslot >= 0 || ((uintptr_t)c.prm(cp.w) & 15) == 0)) {
     Gemm g;
     DQ_TRY(gemm_weight(c, cp, &g.A, wslot));
     g.lda = cp.cin; g.B = in; g.b_kmajor = 0; g.ldb = n_in; g.C = out; g.ldc = n_in;
@@ -663,7 +665,7 @@ int conv_plain_fwd(const Ctx& c, const ConvP& cp, int mode, const float* in, flo
   }
   ConvFwd f;
   f.inA = in; f.cinA = cp.cin; f.w = c.prm(cp.w); f.bias = cp.b >= 0 ? c.prm(cp.b) : nullptr;
-  f.cout = cp.cout; f.K = cp.k; f.mode = mode; f.rows = rows; f.n_in = n_in; f.n_out = n_out; f.y_out = out;
+  f.cout = cp.cout; f.K = cp.k; f.mode = mode; f.rows = rows; f.n_in = n_in; f.n_out = n_out; f.y_out = out; f.act = act;
   return launch_conv_fwd(f, c.s);
 }
 
@@ -863,7 +865,7 @@ LevelFwd level_desc(const Ctx& c, const LevelCall& lc) {
     }
   }
   if (lc.head) {
-    f.ew = c.prm(lc.head->w); f.eb = c.prm(lc.head->b);
+    f.ew = c.prm(lc.head->w); f.eb = c.prm(lc.head->b); f.final_act = c.p.final_act;
     if (c.step_io && c.step_io->x_t) {
       f.x_t = c.step_io->x_t; f.x_out = c.step_io->x_out; f.coef = c.step_io->coef; f.step_ptr = c.step_io->step_ptr; f.pred_x0 = c.step_io->pred_x0;
       f.eps_out = c.step_io->want_eps ? lc.eps_out : nullptr;  // (the trajectory's eps, when the caller keeps one)
@@ -1181,7 +1183,7 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
     if (level_ok(c, lh)) DQ_TRY(launch_level_fwd(with_img(lh, 2 * L), c.s));
     else DQ_TRY(res_fwd(c, p.fin, a.fin, cur, p.dim, c.w(a.h0), p.dim, R, p.mz, RT));
   }
-  DQ_TRY(conv_plain_fwd(c, p.final_conv, CONV_S1, c.w(a.fin.out), out, R, p.mz, p.mz));
+  DQ_TRY(conv_plain_fwd(c, p.final_conv, CONV_S1, c.w(a.fin.out), out, R, p.mz, p.mz, -1, p.final_act == FINAL_SOFTPLUS ? ACT_SOFTPLUS : ACT_NONE));
   return 0;
 }
 
@@ -1230,7 +1232,18 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
   const bool use_tb_up = tiny_bwd_desc(c, true, &tb_up), use_tb_dn = tiny_bwd_desc(c, false, &tb_dn);
   // head
   // (d fin.out came with the forward's last launch when the training head ran: only the weight gradient is left)
-  DQ_TRY(conv_plain_bwd(c, p.final_conv, CONV_S1, c.w(a.fin.out), grad_out, (c.head_loss && c.head_loss->done) ? nullptr : c.g(a.fin.out), R, p.mz, p.mz, 0));
+  const bool head_done = c.head_loss && c.head_loss->done;
+  const float* d_pre = grad_out;  // d loss / d (final_conv's output)
+  if (p.final_act == FINAL_SOFTPLUS && !head_done) {
+    // pos_output_only: grad_out is d loss / d softplus(pre) -- every loss term (the MSE, the MS1 term) has accumulated into it.  The
+    // pre-activation is recomputed from fin.out; the result goes to the gradient twin of the `eps` slot, which no backward launch
+    // otherwise touches (the network output's gradient is the caller's grad_out), so the caller's buffer stays as it was
+    DQ_REQUIRE(p.final_conv.b >= 0, "unet_backward: the Softplus head needs final_conv's bias");
+    DQ_TRY(launch_softplus_head_bwd(c.w(a.fin.out), c.prm(p.final_conv.w), c.prm(p.final_conv.b), p.final_conv.cin, grad_out, c.g(a.eps), R,
+                                    p.mz, c.s));
+    d_pre = c.g(a.eps);
+  }
+  DQ_TRY(conv_plain_bwd(c, p.final_conv, CONV_S1, c.w(a.fin.out), d_pre, head_done ? nullptr : c.g(a.fin.out), R, p.mz, p.mz, 0));
   const LevelBuf& lastup = a.ups[L - 1];
   DQ_TRY(res_bwd(c, p.fin, a.fin, c.w(lastup.rs), c.g(lastup.rs), p.dim, c.w(a.h0), c.g(a.h0), p.dim, R, p.mz, RT, 1, 1));  // first writers of d rs, d h0
   // up path, reversed
@@ -1646,6 +1659,19 @@ int dq_plan_param_info(const dq_plan* plan, int i, char* name, int name_cap, int
   return 0;
 }
 
+static_assert(FINAL_IDENTITY == DQ_FINAL_IDENTITY && FINAL_SOFTPLUS == DQ_FINAL_SOFTPLUS, "FinalAct mirrors include/dq_hip.h");
+int dq_plan_set_final_act(dq_plan* plan, int act) {
+  DQ_REQUIRE(plan, "dq_plan_set_final_act: null plan");
+  DQ_REQUIRE(act == DQ_FINAL_IDENTITY || act == DQ_FINAL_SOFTPLUS,
+             "dq_plan_set_final_act: act must be 0 (DQ_FINAL_IDENTITY) or 1 (DQ_FINAL_SOFTPLUS), got " + std::to_string(act));
+  // a captured sampling step has the head's kernels baked in: never replay one captured under the other activation
+  if (plan->step_exec) { (void)hipGraphExecDestroy(plan->step_exec); plan->step_exec = nullptr; }
+  if (plan->step_graph) { (void)hipGraphDestroy(plan->step_graph); plan->step_graph = nullptr; }
+  plan->plan.final_act = act;
+  return 0;
+}
+int dq_plan_final_act(const dq_plan* plan) { return plan ? plan->plan.final_act : -1; }
+
 int64_t dq_unet_workspace_bytes(dq_plan* plan, int B, int RT, int training) {
   if (!plan || B < 0 || RT < 0) return -1;
   Arena a;
@@ -1954,6 +1980,7 @@ int64_t dq_debug_tensor_offset(dq_plan* plan, const char* name) {
   if (n == "attn_out") return a.attn_out;
   if (n == "mid2") return a.mid2.out;
   if (n == "fin") return a.fin.out;
+  if (n == "eps") return a.eps;  // (its gradient twin: d loss / d final_conv's output when the Softplus head's backward ran)
   for (int i = 0; i < (int)a.downs.size(); ++i) {
     if (n == "down" + std::to_string(i)) return a.downs[i].rs;
     if (n == "down" + std::to_string(i) + ".r0") return a.downs[i].r0.out;

@@ -125,6 +125,9 @@ __global__ void __launch_bounds__(256) k_conv_fwd(ConvFwd a) {
 #pragma unroll
     for (int co = 0; co < COUT; ++co) acc[co] = gelu_f(acc[co]);
   }
+  if constexpr (COUT == 1 && K == 1 && MODE == CONV_S1) {  // final_conv of a pos_output_only network (only this instantiation has it)
+    if (a.act == ACT_SOFTPLUS) acc[0] = softplus_f(acc[0]);
+  }
   if (a.resA) {
     if (a.res_w) {
       const int rcin = a.rcinA + a.rcinB;
@@ -173,6 +176,7 @@ int launch_conv_fwd(const ConvFwd& a, hipStream_t s) {
   if (a.mode == CONV_DOWN) DQ_REQUIRE(a.n_in == 2 * a.n_out && a.K == 4, "conv_fwd: downsample needs n_in == 2*n_out, K == 4");
   if (a.mode == CONV_UP) DQ_REQUIRE(2 * a.n_in == a.n_out && a.K == 3, "conv_fwd: upsample needs n_out == 2*n_in, K == 3");
   if (a.resA && !a.res_w) DQ_REQUIRE(a.rcinA == a.cout && a.rcinB == 0, "conv_fwd: identity residual needs cout channels");
+  DQ_REQUIRE(a.act != ACT_SOFTPLUS || (a.cout == 1 && a.K == 1 && a.mode == CONV_S1), "conv_fwd: Softplus is built for the 1x1 conv to one channel");
   const bool chunkable = !a.g && !a.ss && !(a.resA && a.res_w);
   switch (a.cout) {
     case 1: return conv_fwd_dispatch<1>(a, 1, s);
@@ -529,6 +533,32 @@ int launch_conv_bwd_data(const ConvBwdData& a, hipStream_t s) {
 #undef DQ_BD
   set_error("conv_bwd_data: unsupported (K, mode)");
   return 2;
+}
+
+// -------------------------------------------------------------------------------------------------
+// backward of the Softplus behind final_conv (pos_output_only): one thread per (row, position).  The pre-activation is recomputed
+// from final_conv's input, in the forward's fmaf order (bias first, then channel 0, 1, ...): the value the forward activated, bit for
+// bit, without a stored copy.  dpre = dy * softplus'(pre).
+// -------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_softplus_head_bwd(const float* __restrict__ fin, const float* __restrict__ w, const float* __restrict__ b,
+                                                           int cin, const float* __restrict__ dy, float* __restrict__ dpre, int rows, int n) {
+  const int64_t item = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (item >= (int64_t)rows * n) return;
+  const int64_t row = item / n, p = item - row * n;
+  const float* f = fin + row * cin * n + p;
+  float pre = b[0];
+  for (int c = 0; c < cin; ++c) pre = fmaf(w[c], f[(int64_t)c * n], pre);
+  dpre[item] = dy[item] * softplus_grad_f(pre);
+}
+
+int launch_softplus_head_bwd(const float* fin, const float* w, const float* b, int cin, const float* dy, float* dpre, int rows, int n,
+                             hipStream_t s) {
+  DQ_REQUIRE(fin && w && b && dy && dpre && cin > 0 && rows >= 0 && n > 0, "softplus_head_bwd: missing operand");
+  const int64_t total = (int64_t)rows * n;
+  if (total == 0) return 0;
+  hipLaunchKernelGGL(k_softplus_head_bwd, dim3(cdiv(total, 256)), dim3(256), 0, s, fin, w, b, cin, dy, dpre, rows, n);
+  DQ_LAUNCH_CHECK();
+  return 0;
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -28,6 +28,7 @@
 //         (the final ResnetBlock concatenates it)
 // Head epilogue (the launch that ends with final_res_block): eps = final_conv (1x1, C -> 1) of the block output and, while sampling, the
 // DDIM update x_{t-1} = f(x_t, eps) of model.py:265-289 -- the block output, eps and the separate update launch never touch memory.
+// A pos_output_only network (unet1d.py:1084, 1166) applies Softplus to final_conv's output before anything reads it (FA instantiations).
 // Every global read of a tile (stage input, the skip channels of cat(x, skip), unet1d.py:1151, 1154) is requested before the first use.
 #include "dq_common.h"
 #include "dq_kernels.h"
@@ -85,7 +86,7 @@ struct LevelFwdK {
   // head epilogue (ep_w >= 0): final_conv weight / bias offsets in P; eps_out nullable; DDIM update when x_t is set
   int ep_w, ep_b, pred_x0;
   float* eps_out; const float* x_t; float* x_out; const float* coef; const int* step_ptr;
-  // training head: target, per-wave squared-error sums, d loss / d eps, d loss / d (block output)
+  // training head: target, per-wave squared-error sums, d loss / d (final_conv's output), d loss / d (block output)
   const float* loss_z; float* loss_part; float* grad_out; float* dout; float loss_gscale;
 };
 
@@ -147,7 +148,9 @@ __global__ void __launch_bounds__(256) k_level_images(LevelImgMulti mm, const fl
 // TH: the train step's code is compiled in -- the INIT stage that stores cat0 and may form x_t (LevelFwd::cat0_out, qs_*), the training head behind
 // the final block (LevelFwd::loss_z).  Instantiations of their own, so that the inference kernels keep their registers (as a run-time branch the
 // head took every C = 4 kernel from 77 to 87: five instead of six workgroups per CU)
-template <int C, int PRE, int CP, bool N64, bool TH = false>
+// FA: the head's output activation (LevelFwd::final_act, FINAL_IDENTITY | FINAL_SOFTPLUS), compiled in for the same reason: the
+// identity instantiations are the code they were before the option existed
+template <int C, int PRE, int CP, bool N64, bool TH = false, int FA = FINAL_IDENTITY>
 __global__ void __launch_bounds__(256) k_level_fwd(LevelFwdK a, const float* __restrict__ P, const float* __restrict__ ssb, int tiles_ps, int total_tiles,
                                                    int ln_rt, const float* __restrict__ img) {  // ssb: the per-sample scale / shift vectors; ln_rt = log2(n)
   // N64: the row length is a compile-time 64 -- a channel's plane offset (c * 256 bytes) then folds into the instructions' immediate offsets
@@ -623,7 +626,8 @@ __global__ void __launch_bounds__(256) k_level_fwd(LevelFwdK a, const float* __r
         if (a.ep_w >= 0 && bi == a.nblocks - 1) {  // head: final_conv (1x1, 4 -> 1) and, while sampling, the DDIM update
           const float4 w4 = *reinterpret_cast<const float4*>(prm + C * 15);
           const float eb = prm[C * 15 + 4];
-          const float ev = fmaf(w4.w, o[3], fmaf(w4.z, o[2], fmaf(w4.y, o[1], fmaf(w4.x, o[0], eb))));
+          const float pre = fmaf(w4.w, o[3], fmaf(w4.z, o[2], fmaf(w4.y, o[1], fmaf(w4.x, o[0], eb))));
+          const float ev = FA == FINAL_SOFTPLUS ? softplus_f(pre) : pre;  // the network output (final_act, unet1d.py:1166)
           const unsigned eoff = ((row << ln) + p) * 4u;
           if (live) {
             float ep = ev;  // what eps_out receives: the network output, or -- while sampling with the x0 objective -- the derived eps
@@ -641,7 +645,8 @@ __global__ void __launch_bounds__(256) k_level_fwd(LevelFwdK a, const float* __r
             const float d = ev - z;
             if (live) {
               lacc += d * d;
-              const float gv = d * a.loss_gscale;
+              float gv = d * a.loss_gscale;
+              if constexpr (FA == FINAL_SOFTPLUS) gv *= softplus_grad_f(pre);  // d loss / d pre: the value grad_out and d fin.out carry
               *reinterpret_cast<float*>(reinterpret_cast<char*>(a.grad_out) + eoff) = gv;
               st(a.dout, 0, obase, w4.x * gv); st(a.dout, 1, obase, w4.y * gv); st(a.dout, 2, obase, w4.z * gv); st(a.dout, 3, obase, w4.w * gv);
             }
@@ -737,6 +742,7 @@ int launch_level_fwd(const LevelFwd& a, hipStream_t s) {
   DQ_REQUIRE(!a.ew || (a.C == 4 && a.eb && (a.eps_out || a.x_t || a.loss_z) && (!a.x_t || (a.x_out && a.coef))), "level_fwd: incomplete head epilogue");
   DQ_REQUIRE(!a.loss_z || (a.ew && !a.x_t && a.loss_part && a.grad_out && a.dout && a.loss_parts_out), "level_fwd: incomplete training head");
   DQ_REQUIRE(!a.cat0_out || (a.pre == LEVEL_PRE_INIT && !a.loss_z), "level_fwd: cat0_out belongs to the first-layer stage");
+  DQ_REQUIRE(a.final_act == FINAL_IDENTITY || (a.final_act == FINAL_SOFTPLUS && a.ew), "level_fwd: an output activation needs the head epilogue");
   k.cat0_out = a.cat0_out;
   DQ_REQUIRE(!a.qs_noise || (a.cat0_out && a.qs_ab && a.qs_t), "level_fwd: q_sample in the first-layer stage needs the schedule, the timesteps and cat0_out");
   k.qs_noise = a.qs_noise; k.qs_ab = a.qs_ab; k.qs_t = a.qs_t; k.qs_norm = a.qs_norm;
@@ -797,6 +803,19 @@ int launch_level_fwd(const LevelFwd& a, hipStream_t s) {
   if (a.C == CC && a.pre == PP && cp == PC) {                                                                                 \
     if (CC == 4 && a.n == 64) DQ_LVN(CC, PP, PC, (CC == 4))                                                                    \
     DQ_LVN(CC, PP, PC, false)                                                                                                 \
+  }
+  if (a.final_act == FINAL_SOFTPLUS) {  // the Softplus head (pos_output_only): the final block's launch, k3 stage conv from 4 or 8 channels
+    DQ_REQUIRE(a.C == 4 && a.pre == LEVEL_PRE_S1 && (cp == 4 || (cp == 8 && !a.loss_z)), "level_fwd: the Softplus head is built for the (4, k3 conv, 4 | 8) launch");
+    if (a.loss_z) {
+      if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, true, FINAL_SOFTPLUS>))
+      DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, true, FINAL_SOFTPLUS>))
+    }
+    if (cp == 4) {
+      if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, false, FINAL_SOFTPLUS>))
+      DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, false, FINAL_SOFTPLUS>))
+    }
+    if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 8, true, false, FINAL_SOFTPLUS>))
+    DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 8, false, false, FINAL_SOFTPLUS>))
   }
   if (a.loss_z) {  // the training head has its own instantiations (the network's final block: k3 stage conv from 4 channels)
     DQ_REQUIRE(a.C == 4 && a.pre == LEVEL_PRE_S1 && cp == 4, "level_fwd: the training head is built for the (4, k3 conv, 4) launch");

@@ -11,6 +11,7 @@ _lib = None
 ABI_VERSION = 10  # DQ_ABI_VERSION of include/dq_hip.h this table was written against
 PRED_TYPES = {"eps": 0, "x0": 1}  # DQ_PRED_EPS / DQ_PRED_X0
 PRECISIONS = {"fp32": 0, "bf16x3": 1}  # DQ_PRECISION_FP32 / DQ_PRECISION_BF16X3
+FINAL_ACTS = {"identity": 0, "softplus": 1}  # DQ_FINAL_IDENTITY / DQ_FINAL_SOFTPLUS
 
 # name -> (restype, argtypes); this table is checked against include/dq_hip.h by tests/test_abi.py
 PROTOTYPES = {
@@ -22,6 +23,8 @@ PROTOTYPES = {
     "dq_plan_param_floats": (c_int64, [c_void_p]),
     "dq_plan_param_info": (c_int, [c_void_p, c_int, c_char_p, c_int, POINTER(c_int64), POINTER(c_int), POINTER(c_int64)]),
     "dq_unet_workspace_bytes": (c_int64, [c_void_p, c_int, c_int, c_int]),
+    "dq_plan_set_final_act": (c_int, [c_void_p, c_int]),
+    "dq_plan_final_act": (c_int, [c_void_p]),
     "dq_q_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]),
     "dq_ddim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "dq_ddim_step_x0": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

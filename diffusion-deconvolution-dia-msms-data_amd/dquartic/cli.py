@@ -95,7 +95,8 @@ def train(config_path, parquet_directory, ms2_data_path, ms1_data_path, batch_si
         u = m["UNet1d"]
         net = UNet1d(dim=u["dim"], channels=u["channels"], dim_mults=tuple(u["dim_mults"]), conditional=u["conditional"],
                      init_cond_channels=u["init_cond_channels"], attn_cond_channels=u["attn_cond_channels"],
-                     tfer_dim_mult=u["tfer_dim_mult"], downsample_dim=u["downsample_dim"], simple=u["simple"]).to(device)
+                     tfer_dim_mult=u["tfer_dim_mult"], downsample_dim=u["downsample_dim"], simple=u["simple"],
+                     pos_output_only=bool(u.get("pos_output_only", False))).to(device)  # (reference configs without the key: False)
     elif m["use_model"] == "CustomTransformer":  # reference cli.py:102-109; served through the 4-argument adapter
         from .model.building_blocks import CustomTransformer, DDIMTransformerAdapter
 

@@ -8,6 +8,8 @@ fallback: on a CPU tensor or without the library ``forward`` raises.
 
 Differences from the reference, all documented in DESIGN.md:
   * batches work (the reference only runs at B = 1, SURVEY F1): sample b's time embedding is applied to its own rows;
+  * ``pos_output_only=True`` (Softplus behind final_conv, reference unet1d.py:1084, 1166) is fused into whichever kernel forms the
+    network output, and its derivative into the head of the backward (DESIGN.md section 19); ``final_act`` is the reference's module;
   * only the working configuration family is built: simple=True, conditional=True, channels=1, init_cond_channels=1,
     attn_cond_channels=1, 4 heads x 32, dim = 4, dim*mult <= 16, downsample_dim divisible by 2**(len(dim_mults)-1) -- which
     includes the reference's shipped configuration (downsample_dim 40000: m/z rows of 40000 .. 625 positions and a
@@ -141,8 +143,8 @@ class UNet1d(_FlatBuffers, nn.Module):
             unsupported.append("channels/init_cond_channels/attn_cond_channels other than 1")
         if init_dim not in (None, dim) or out_dim not in (None, 1) or attn_cond_init_dim not in (None, 2 * dim):
             unsupported.append("non-default init_dim/out_dim/attn_cond_init_dim")
-        if learned_variance or pos_output_only or dropout != 0.0:
-            unsupported.append("learned_variance / pos_output_only / dropout")
+        if learned_variance or dropout != 0.0:
+            unsupported.append("learned_variance / dropout")
         if attn_heads != 4 or attn_dim_head != 32 or sinusoidal_pos_emb_theta != 10000:
             unsupported.append("attn_heads/attn_dim_head/theta other than 4/32/10000")
         if unsupported:
@@ -162,6 +164,11 @@ class UNet1d(_FlatBuffers, nn.Module):
         self._plan = lib.dq_plan_create(self.dim, len(self.dim_mults), mults, self.downsample_dim, 1000)
         if not self._plan:
             raise ValueError("UNet1d: " + (lib.dq_last_error() or b"?").decode())
+        # reference unet1d.py:1084, 1166: Softplus behind final_conv; fixed for the module's lifetime (the plan carries it into every
+        # forward, backward, train step and sampling call, fused or not)
+        self.pos_output_only = bool(pos_output_only)
+        N.check(lib.dq_plan_set_final_act(self._plan, N.FINAL_ACTS["softplus" if self.pos_output_only else "identity"]),
+                "dq_plan_set_final_act")
 
         # ---- parameters: views of one flat buffer, attached under the reference's state_dict names
         self._layout = []  # (name, offset, shape)
@@ -184,6 +191,8 @@ class UNet1d(_FlatBuffers, nn.Module):
                 _attach(self, "mid_attn.fn.fn.rotary_emb.freqs", nn.Parameter(freqs, requires_grad=False))
             _attach(self, pname, self._by_name[pname])
         self._reset_parameters()
+        # (no parameters: state_dict keys, order and the seeded initialisation are those of either reference variant)
+        self.final_act = nn.Softplus() if self.pos_output_only else nn.Identity()
         self._ws = {}
         self._ws_pool = {}  # training workspaces of the autograd bridge: one per forward that still awaits its backward
         self.use_rope = True

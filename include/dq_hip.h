@@ -77,6 +77,18 @@ int dq_plan_param_info(const dq_plan* plan, int i, char* name, int name_cap, int
  * training != 0 adds the gradient twin of the activation arena. */
 int64_t dq_unet_workspace_bytes(dq_plan* plan, int B, int RT, int training);
 
+/* Output activation of the network (UNet1d pos_output_only, unet1d.py:1084, 1166): what final_act applies to final_conv's output.
+ *   DQ_FINAL_IDENTITY (default): the network output is final_conv's output;
+ *   DQ_FINAL_SOFTPLUS: torch.nn.Softplus() (beta 1, threshold 20): y = x for x > 20, else log1p(exp(x)); dy/dx = 1 for x > 20,
+ *                      else sigmoid(x).
+ * Per plan.  It applies to every entry point that forms or differentiates the network output: dq_unet_fwd, dq_unet_bwd (grad_out is
+ * d loss / d y, the activated output), dq_train_step (its losses are taken on y) and dq_ddim_sample (eps or, with DQ_PRED_X0, x0 is y).
+ * Workspace sizes do not depend on it.  A call drops the plan's cached sampling graph.  Any other value: non-zero (dq_last_error). */
+enum { DQ_FINAL_IDENTITY = 0, DQ_FINAL_SOFTPLUS = 1 };
+int dq_plan_set_final_act(dq_plan* plan, int act);
+/* The plan's output activation (DQ_FINAL_*); -1 for a NULL plan. */
+int dq_plan_final_act(const dq_plan* plan);
+
 /* ---- K0: DDIMDiffusionModel.q_sample (model.py:225-242) ---------------------------------------------------------
  * x_t = sqrt(ab[t_b]) * x0' + sqrt(1 - ab[t_b]) * noise, x0' = 2*x0-1 if normalize_x0 (model.py:349) else x0. */
 int dq_q_sample(const float* alpha_bars_dev, const float* x0, const int64_t* t, const float* noise, float* x_t, int B,
@@ -322,7 +334,7 @@ int dq_attn_bwd(const float* q, const float* k, const float* v, const float* o, 
                 float* dq, float* dk, float* dv, int B, int RT, void* stream);
 
 /* Test hook: offset (in floats) of a named activation inside the workspace laid out by the last call on this plan
- * ("h0", "ms1f", "down3", "down3.la", "mid1", "attn_out", "up0", "fin", ...), or -1. */
+ * ("h0", "ms1f", "down3", "down3.la", "mid1", "attn_out", "up0", "fin", "eps", ...), or -1. */
 int64_t dq_debug_tensor_offset(dq_plan* plan, const char* name);
 
 /* Test hook: from now on the backward's side stream ends with a store of `value` to `addr`, delayed by delay_us microseconds, right in
