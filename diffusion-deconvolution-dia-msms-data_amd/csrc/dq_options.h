@@ -12,6 +12,10 @@ enum Option {
   OPT_LA_SMALL_MIN_ROWS = 0,
   // the same choice for the backward (k_la_rows_bwd.hip against k_la_bwd.hip); < 0 (default): every row count
   OPT_LA_ROWS_BWD_MIN_ROWS = 1,
+  // rows from which the ResnetBlock backward over rows of 2 / 4 / 8 positions at 12 / 16 channels runs in the m/z-row-as-lane-column form
+  // (k_res_rows.hip) instead of the channel-parallel one (k_res_cp.hip).  < 0 (default): the device rule -- one 16-row tile per compute unit
+  // (16 x compute units: 4,096 on MI355X)
+  OPT_RES_ROWS_BWD_MIN_ROWS = 2,
   OPT_COUNT
 };
 int64_t option(Option o);

@@ -166,9 +166,9 @@ void build_resblock_plan(Plan& p, ResP& r, int cin, int cout) {
 
 namespace dq {
 namespace {
-std::atomic<int64_t> g_options[OPT_COUNT] = {{-1}, {-1}};
+std::atomic<int64_t> g_options[OPT_COUNT] = {{-1}, {-1}, {-1}};
 std::atomic<unsigned> g_options_epoch{0};
-const char* const g_option_keys[OPT_COUNT] = {"la_small_min_rows", "la_rows_bwd_min_rows"};
+const char* const g_option_keys[OPT_COUNT] = {"la_small_min_rows", "la_rows_bwd_min_rows", "res_rows_bwd_min_rows"};
 }  // namespace
 int64_t option(Option o) { return g_options[o].load(std::memory_order_relaxed); }
 unsigned options_epoch() { return g_options_epoch.load(std::memory_order_relaxed); }

@@ -348,18 +348,25 @@ int res_bwd_side(const Ctx& c, const ResP& r, const ResBuf& b, const float* inA,
 // ResnetBlock backward: d(out) is complete in the twin of b.out; adds into dA / dB (twins of the inputs; null => skipped)
 // storeA / storeB: this block is the first writer of dA / dB in the backward pass (fused path only; the step-by-step path
 // below accumulates into the cleared buffers as before)
-int res_bwd(const Ctx& c, const ResP& r, const ResBuf& b, const float* inA, float* dA, int cinA, const float* inB, float* dB, int cinB,
-            int rows, int n, int rows_per_sample, int storeA = 0, int storeB = 0, const ResRtPre* pre = nullptr, int* gblocks_out = nullptr,
-            const ResRtOut* aout = nullptr) {
-  const float* dout = c.g(b.out);
+// the data-path operands of a ResnetBlock backward (what res_bwd_form decides on; dq_resblock_forms asks the same question)
+ResBwd res_bwd_args(const Ctx& c, const ResP& r, const ResBuf& b, float* dA, int cinA, float* dB, int cinB, int rows, int n, int rows_per_sample,
+                    int storeA, int storeB) {
   ResBwd k;
-  k.dout = dout; k.u1 = c.w(b.u1); k.u2 = c.w(b.u2);
+  k.dout = c.g(b.out); k.u1 = c.w(b.u1); k.u2 = c.w(b.u2);
   k.w1 = c.prm(r.c1.w); k.w2 = c.prm(r.c2.w); k.wr = r.res.cout ? c.prm(r.res.w) : nullptr;
   k.g1 = c.prm(r.g1); k.g2 = c.prm(r.g2); k.ss = c.w(c.ar.ss) + r.ss_off; k.ss_stride = c.p.ss_total;
   k.du1 = c.g(b.u1); k.du2 = c.g(b.u2); k.dA = dA; k.dB = dB; k.cinA = cinA; k.cinB = cinB;
   k.dA_store = storeA; k.dB_store = storeB;
   k.dg1 = c.dprm(r.g1); k.dg2 = c.dprm(r.g2); k.dss = c.g(c.ar.ss) + r.ss_off;
   k.C = r.cout; k.rows = rows; k.n = n; k.rows_per_sample = rows_per_sample;
+  return k;
+}
+
+int res_bwd(const Ctx& c, const ResP& r, const ResBuf& b, const float* inA, float* dA, int cinA, const float* inB, float* dB, int cinB,
+            int rows, int n, int rows_per_sample, int storeA = 0, int storeB = 0, const ResRtPre* pre = nullptr, int* gblocks_out = nullptr,
+            const ResRtOut* aout = nullptr) {
+  const float* dout = c.g(b.out);
+  ResBwd k = res_bwd_args(c, r, b, dA, cinA, dB, cinB, rows, n, rows_per_sample, storeA, storeB);
   const ResBwdForm form = res_bwd_form(k, b.wpart_floats != 0);
   if (form == RES_BWD_WG) {
     // wide m/z levels: the data path AND the block's weight gradients in one launch; its slots are summed by one launch per pass.  (The
@@ -1770,6 +1777,14 @@ int64_t dq_get_option(const char* key) {
   if (i < 0) { set_error("dq_get_option: unknown key"); return INT64_MIN; }
   return option((Option)i);
 }
+int64_t dq_get_option_effective(const char* key) {
+  switch (option_index(key)) {
+    case OPT_LA_SMALL_MIN_ROWS: return la_small_min_rows();
+    case OPT_LA_ROWS_BWD_MIN_ROWS: return la_rows_bwd_min_rows();
+    case OPT_RES_ROWS_BWD_MIN_ROWS: return res_rows_bwd_min_rows();
+    default: set_error("dq_get_option_effective: unknown key"); return -1;
+  }
+}
 
 int dq_debug_side_tail_store(dq_plan* plan, float* addr, float value, int delay_us) {
   DQ_REQUIRE(plan && delay_us >= 0 && delay_us <= 100000, "dq_debug_side_tail_store: null plan / delay out of range");
@@ -2120,6 +2135,23 @@ int dq_resblock_fwd(const float* params, const float* xA, int cinA, const float*
   DQ_TRY(launch_ss_heads(temb, params + w.r.mlp_w, params + w.r.mlp_b, c.w(w.ar.ss), w.B, 2 * cout, s));  // unet1d.py:315-318
   DQ_TRY(res_fwd(c, w.r, w.rb, xA, cinA, cinB ? xB : nullptr, cinB, rows, n, rows_per_sample));
   return launch_copy(out, c.w(w.rb.out), (int64_t)rows * cout * n, s);
+}
+
+static_assert(RES_FWD_RT == DQ_RES_FWD_RT && RES_FWD_LEVEL == DQ_RES_FWD_LEVEL && RES_FWD_V4 == DQ_RES_FWD_V4 && RES_FWD_UNFUSED == DQ_RES_FWD_UNFUSED,
+              "ResFwdForm mirrors include/dq_hip.h");
+static_assert(RES_BWD_WG == DQ_RES_BWD_WG && RES_BWD_RT == DQ_RES_BWD_RT && RES_BWD_ROWS == DQ_RES_BWD_ROWS && RES_BWD_CP == DQ_RES_BWD_CP &&
+              RES_BWD_PLAIN == DQ_RES_BWD_PLAIN && RES_BWD_UNFUSED == DQ_RES_BWD_UNFUSED, "ResBwdForm mirrors include/dq_hip.h");
+int dq_resblock_forms(int cinA, int cinB, int cout, int rows, int n, int rows_per_sample, int* fwd_form, int* bwd_form) {
+  DQ_REQUIRE(fwd_form && bwd_form && cinA > 0 && cinB >= 0, "dq_resblock_forms: null argument / bad channel split");
+  BlockWs w;
+  DQ_TRY(block_ws(w, cinA + cinB, cout, rows, n, rows_per_sample));
+  *fwd_form = res_fwd_form(cout, cinA, cinB, w.r.res.cout != 0, rows, n, rows_per_sample);
+  // the caller's tensors and the workspace as 16-byte aligned stand-ins (nothing is dereferenced): the operands dq_resblock_bwd hands over
+  float* const base = reinterpret_cast<float*>(uintptr_t{1} << 20);
+  Ctx c{w.plan, w.ar, base, base, base + w.half, base, w.B, rows_per_sample, nullptr};
+  const ResBwd k = res_bwd_args(c, w.r, w.rb, base, cinA, cinB ? base : nullptr, cinB, rows, n, rows_per_sample, 0, 0);
+  *bwd_form = res_bwd_form(k, w.rb.wpart_floats != 0);
+  return 0;
 }
 
 int dq_resblock_bwd(const float* params, const float* xA, int cinA, const float* xB, int cinB, const float* dout, float* dxA, float* dxB,

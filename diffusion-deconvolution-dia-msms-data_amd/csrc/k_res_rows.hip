@@ -16,6 +16,9 @@
 #include "dq_common.h"
 #include "dq_dev.h"
 #include "dq_kernels.h"
+#include "dq_options.h"
+#include <algorithm>
+#include <climits>
 #include <cstdint>
 
 namespace dq {
@@ -281,12 +284,21 @@ int device_cus() {
 
 }  // namespace
 
+// One wave does a 16-row tile here where k_res_cp.hip spreads it over four (lane = channel): 4x fewer wave-instructions, but a 1.2 - 1.5x
+// longer chain per tile -- the better form from about one tile per CU on (measured at batch 1 / 4 / 32: 75 -> 89, -> +14, 149 -> 106 us per step).
+// dq_set_option("res_rows_bwd_min_rows", rows) overrides the rule (tests run this form at a few rows).  The grid is (cdiv(rows_per_sample, 64),
+// B) workgroups with no resident-round sizing, and its partial-sum slots fit the block's gpart at every row count (ResBuf: >= cdiv(rps, 16)
+// per sample), so any threshold is safe.
+int res_rows_bwd_min_rows() {
+  const int64_t o = option(OPT_RES_ROWS_BWD_MIN_ROWS);
+  if (o >= 0) return (int)std::min<int64_t>(o, INT32_MAX);
+  return 16 * device_cus();
+}
+
 bool res_rows_bwd_usable(const ResBwd& a) {
   if (DQ_DEV_FLAG("DQ_NO_RES_ROWS", '1')) return false;  // (dev switch)
   if (!(a.C == 12 || a.C == 16) || !(a.n == 2 || a.n == 4 || a.n == 8) || a.rows_per_sample < 2) return false;
-  // One wave does a 16-row tile here where k_res_cp.hip spreads it over four (lane = channel): 4x fewer wave-instructions, but a 1.2 - 1.5x
-  // longer chain per tile -- the better form from about one tile per CU on (measured at batch 1 / 4 / 32: 75 -> 89, -> +14, 149 -> 106 us per step)
-  if (a.rows < 16 * device_cus()) return false;
+  if (a.rows < res_rows_bwd_min_rows()) return false;
   if (a.cinA < 4 || a.cinA > 16 || (a.cinA & 3) || a.cinB < 0 || a.cinB > 16 || (a.cinB & 3)) return false;
   if (!a.wr && !(a.cinA == a.C && a.cinB == 0)) return false;
   // 16-byte accesses of a row's positions (rows of 2 positions: 8-byte)

@@ -12,6 +12,8 @@ ABI_VERSION = 10  # DQ_ABI_VERSION of include/dq_hip.h this table was written ag
 PRED_TYPES = {"eps": 0, "x0": 1}  # DQ_PRED_EPS / DQ_PRED_X0
 PRECISIONS = {"fp32": 0, "bf16x3": 1}  # DQ_PRECISION_FP32 / DQ_PRECISION_BF16X3
 FINAL_ACTS = {"identity": 0, "softplus": 1}  # DQ_FINAL_IDENTITY / DQ_FINAL_SOFTPLUS
+RES_FWD_FORMS = ("rt", "level", "v4", "unfused")  # DQ_RES_FWD_* (index = value)
+RES_BWD_FORMS = ("wg", "rt", "rows", "cp", "plain", "unfused")  # DQ_RES_BWD_*
 
 # name -> (restype, argtypes); this table is checked against include/dq_hip.h by tests/test_abi.py
 PROTOTYPES = {
@@ -40,6 +42,7 @@ PROTOTYPES = {
     "dq_plan_set_side_stream": (c_int, [c_void_p, c_int]),
     "dq_set_option": (c_int, [c_char_p, c_int64]),
     "dq_get_option": (c_int64, [c_char_p]),
+    "dq_get_option_effective": (c_int64, [c_char_p]),
     "dq_adamw_clip_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float, c_float, c_double,
                                    c_double, c_double, c_double, c_double, c_int, c_void_p, c_void_p]),
     "dq_train_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
@@ -86,6 +89,7 @@ PROTOTYPES = {
     "dq_level_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_int64, c_void_p]),
     "dq_resblock_dout_offset": (c_int64, [c_int] * 5),
     "dq_resblock_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_int64, c_void_p]),
+    "dq_resblock_forms": (c_int, [c_int] * 6 + [POINTER(c_int), POINTER(c_int)]),
     "dq_resblock_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 4 + [c_void_p, c_int64, c_void_p]),
     "dq_rope": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_void_p]),
     "dq_attn_fwd": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p]),
@@ -137,6 +141,19 @@ def set_option(key: str, value: int) -> None:
 
 def get_option(key: str) -> int:
     return int(lib().dq_get_option(key.encode()))
+
+
+def get_option_effective(key: str) -> int:
+    """``dq_get_option_effective``: the threshold the library applies now (the default rule resolved); -1 for an unknown key."""
+    return int(lib().dq_get_option_effective(key.encode()))
+
+
+def resblock_forms(cinA: int, cinB: int, cout: int, rows: int, n: int, rows_per_sample: int):
+    """``dq_resblock_forms``: the (forward, backward) kernel forms the stand-alone ResnetBlock calls take for this shape now, as names of
+    RES_FWD_FORMS / RES_BWD_FORMS."""
+    f, b = c_int(-1), c_int(-1)
+    check(lib().dq_resblock_forms(cinA, cinB, cout, rows, n, rows_per_sample, ctypes.byref(f), ctypes.byref(b)), "dq_resblock_forms")
+    return RES_FWD_FORMS[f.value], RES_BWD_FORMS[b.value]
 
 
 def check(rc, what):

@@ -44,7 +44,8 @@ const char* dq_last_error(void);
  * building blocks (dq_rmsnorm_fwd, dq_time_mlp_fwd, dq_scale_shift_fwd, dq_prep_inputs_fwd, dq_conv_fwd, dq_resblock_*,
  * dq_rope, dq_attn_*); dq_train_step takes ms1_loss_weight, dq_ms1_loss_fwd_bwd;
  * dq_tfm_set_precision, dq_gemm_bf16x3.  8: dq_tfm_bwd_buckets, dq_tfm_num_buckets, dq_tfm_bucket_info.  9: dq_linattn_prepare,
- * dq_linattn_fwd_prepared.  10: dq_set_option, dq_get_option, dq_debug_side_tail_store. */
+ * dq_linattn_fwd_prepared.  10: dq_set_option, dq_get_option, dq_debug_side_tail_store (later, additive: dq_plan_set_final_act,
+ * dq_plan_final_act, dq_get_option_effective, dq_resblock_forms). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 10
 
@@ -54,9 +55,15 @@ int dq_abi_version(void);
  *                           one-register-group-per-position form (k_la_small.hip) instead of the register-resident one (k_linattn.hip);
  *                           < 0 (default): the device rule, one 32-row tile per SIMD (32,768 rows on MI355X)
  *   "la_rows_bwd_min_rows"  the same for its backward (k_la_rows_bwd.hip against k_la_bwd.hip); < 0 (default): every row count
+ *   "res_rows_bwd_min_rows" rows (B * rows_per_sample) from which the ResnetBlock backward over m/z rows of 2 / 4 / 8 positions at 12 / 16
+ *                           channels runs with the row as the lane column (k_res_rows.hip) instead of channel-parallel (k_res_cp.hip);
+ *                           < 0 (default): the device rule, one 16-row tile per compute unit (4,096 rows on MI355X)
  * Both forms compute the same function (parity tests run both at every size).  Unknown key: non-zero / INT64_MIN. */
 int dq_set_option(const char* key, int64_t value);
 int64_t dq_get_option(const char* key);
+/* The threshold the library applies right now for the key above: the set value (clamped to INT32_MAX), or with the option < 0 the
+ * resolved default rule.  Unknown key: -1. */
+int64_t dq_get_option_effective(const char* key);
 
 /* DDIMDiffusionModel.pred_type (model.py:205-213, 269-280, 354-389); any other value is rejected ("Unknown pred_type"). */
 enum { DQ_PRED_EPS = 0, DQ_PRED_X0 = 1 };
@@ -309,6 +316,13 @@ int64_t dq_resblock_dout_offset(int cin, int cout, int rows, int n, int rows_per
 int dq_resblock_bwd(const float* params, const float* xA, int cinA, const float* xB, int cinB, const float* dout, float* dxA, float* dxB,
                     float* grads, float* dss, int cout, int rows, int n, int rows_per_sample, float* workspace, int64_t workspace_floats,
                     void* stream);
+/* Which kernels dq_resblock_fwd / dq_resblock_bwd take for this shape under the current options (16-byte aligned caller tensors assumed):
+ * *fwd_form = DQ_RES_FWD_*, *bwd_form = DQ_RES_BWD_*.  Forward: k_res_rt.hip (RT), a one-block k_level.hip launch (LEVEL), k_res_v4.hip (V4),
+ * the conv launches (UNFUSED).  Backward: k_res_wg.hip (WG), k_res_rt.hip (RT), k_res_rows.hip (ROWS), k_res_cp.hip (CP), k_res.hip (PLAIN),
+ * the step-by-step launches (UNFUSED).  Launches nothing.  Bad shape: non-zero. */
+enum { DQ_RES_FWD_RT = 0, DQ_RES_FWD_LEVEL = 1, DQ_RES_FWD_V4 = 2, DQ_RES_FWD_UNFUSED = 3 };
+enum { DQ_RES_BWD_WG = 0, DQ_RES_BWD_RT = 1, DQ_RES_BWD_ROWS = 2, DQ_RES_BWD_CP = 3, DQ_RES_BWD_PLAIN = 4, DQ_RES_BWD_UNFUSED = 5 };
+int dq_resblock_forms(int cinA, int cinB, int cout, int rows, int n, int rows_per_sample, int* fwd_form, int* bwd_form);
 /* The convolutional part of a U-Net level in ONE launch (unet1d.py:1134-1142, 1150-1158, 1160-1163; k_level.hip):
  *   out_i = ResnetBlock_i(cat(h, skip_i)),  h = stage(x) for i = 0, h = out_0 for i = 1
  * pre: 0 none (x is (rows, C, n)), 1 Downsample k4 s2 (x is (rows, cp, 2n)), 2 Upsample nearest x2 + k3 (x is (rows, cp, n/2)), 3 k3 conv

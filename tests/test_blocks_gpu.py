@@ -147,29 +147,35 @@ def test_resnet_block_fixture_forward(N, golden, name, split):
     assert rel(out, g[f"{name}/y"]) < 5e-6, name
 
 
-@pytest.mark.parametrize("cin,cout,n,rows,rps,split", [(4, 4, 64, 70, 35, 0), (8, 8, 32, 40, 20, 0), (16, 8, 16, 36, 12, 8), (24, 12, 4, 150, 50, 12),
-                                                       (32, 16, 1, 66, 33, 16), (8, 4, 64, 26, 13, 4), (16, 16, 96, 2, 1, 0), (16, 16, 400, 3, 1, 0),
-                                                       (12, 8, 8, 90, 45, 8), (8, 8, 8, 64, 32, 0), (8, 4, 32, 48, 24, 4), (16, 8, 256, 6, 3, 8),
-                                                       # 12 / 16 channels with the weight gradients in the same launch (k_res_bwd_wg, wide path):
-                                                       # identity residual, narrower skip than the block, several tiles per sample, rows of 1..8
-                                                       (12, 12, 8, 66, 33, 0), (16, 16, 2, 130, 65, 0), (28, 16, 2, 160, 80, 16), (16, 12, 8, 70, 35, 12),
-                                                       (24, 12, 8, 200, 100, 12), (32, 16, 4, 300, 150, 16), (16, 16, 1, 600, 300, 0),
-                                                       # the bottleneck's 16-channel blocks, RT position = lane column (k_res_rt.hip): RT axes shorter
-                                                       # than a tile, one short of / one over a tile and a workgroup (14 / 56 forward, 12 / 48 backward),
-                                                       # longer than the 512 the thread-per-position kernel took
-                                                       (16, 16, 1, 5, 1, 0), (16, 16, 2, 3, 1, 0), (16, 16, 11, 3, 1, 0), (16, 16, 12, 2, 1, 0), (16, 16, 13, 4, 1, 0),
-                                                       (16, 16, 14, 2, 1, 0), (16, 16, 15, 2, 1, 0), (16, 16, 47, 2, 1, 0), (16, 16, 49, 2, 1, 0), (16, 16, 57, 2, 1, 0),
-                                                       (16, 16, 413, 2, 1, 0), (16, 16, 700, 2, 1, 0), (16, 16, 2000, 1, 1, 0),
-                                                       # a 16-channel block with a skip input and a res_conv over an RT axis longer than 512: the
-                                                       # unfused conv path
-                                                       (32, 16, 700, 2, 1, 16),
-                                                       # the deep levels' rows backward (k_res_rows.hip, >= 16 rows per CU) with a partly filled last
-                                                       # 16-row tile per sample (98 rows per sample)
-                                                       (24, 12, 4, 4214, 98, 12),
-                                                       # the unfused forward with several rows per sample: rows of 128 at 12 channels (backward
-                                                       # k_res_bwd), a 6-channel skip (backward k_res_bwd_cp); k_res_fwd_v4 with a skip input
-                                                       (12, 12, 128, 8, 4, 0), (22, 16, 4, 96, 48, 16), (8, 4, 128, 12, 4, 4)])
-def test_resnet_block_backward_vs_oracle_autograd(N, cin, cout, n, rows, rps, split):
+# form: the backward kernel each case must reach (dq_resblock_forms under the default options) -- k_res_wg.hip, k_res_cp.hip, k_res_rt.hip,
+# k_res_rows.hip, k_res.hip (plain) or the step-by-step launches (unfused)
+RES_BWD_CASES = [
+    # 4 / 8 channels, rows of 8 - 64 positions: the weight gradients in the same launch (k_res_bwd_wg); rows of 256 at 8 channels: k_res_bwd
+    (4, 4, 64, 70, 35, 0, "wg"), (8, 8, 32, 40, 20, 0, "wg"), (16, 8, 16, 36, 12, 8, "wg"), (8, 4, 64, 26, 13, 4, "wg"),
+    (12, 8, 8, 90, 45, 8, "wg"), (8, 8, 8, 64, 32, 0, "wg"), (8, 4, 32, 48, 24, 4, "wg"), (16, 8, 256, 6, 3, 8, "plain"),
+    # 12 / 16 channels below the row form's threshold: channel-parallel (k_res_bwd_cp) -- identity residual, narrower skip than the block,
+    # several tiles per sample, rows of 1..8 (their k_res_bwd_wg instantiations exist in the development build only)
+    (24, 12, 4, 150, 50, 12, "cp"), (32, 16, 1, 66, 33, 16, "cp"),
+    (12, 12, 8, 66, 33, 0, "cp"), (16, 16, 2, 130, 65, 0, "cp"), (28, 16, 2, 160, 80, 16, "cp"), (16, 12, 8, 70, 35, 12, "cp"),
+    (24, 12, 8, 200, 100, 12, "cp"), (32, 16, 4, 300, 150, 16, "cp"), (16, 16, 1, 600, 300, 0, "cp"),
+    # the bottleneck's 16-channel blocks, RT position = lane column (k_res_rt.hip): RT axes shorter than a tile, one short of / one over a
+    # tile and a workgroup (14 / 56 forward, 12 / 48 backward), longer than the 512 the thread-per-position kernel took
+    (16, 16, 96, 2, 1, 0, "rt"), (16, 16, 400, 3, 1, 0, "rt"),
+    (16, 16, 1, 5, 1, 0, "rt"), (16, 16, 2, 3, 1, 0, "rt"), (16, 16, 11, 3, 1, 0, "rt"), (16, 16, 12, 2, 1, 0, "rt"), (16, 16, 13, 4, 1, 0, "rt"),
+    (16, 16, 14, 2, 1, 0, "rt"), (16, 16, 15, 2, 1, 0, "rt"), (16, 16, 47, 2, 1, 0, "rt"), (16, 16, 49, 2, 1, 0, "rt"), (16, 16, 57, 2, 1, 0, "rt"),
+    (16, 16, 413, 2, 1, 0, "rt"), (16, 16, 700, 2, 1, 0, "rt"), (16, 16, 2000, 1, 1, 0, "rt"),
+    # a 16-channel block with a skip input and a res_conv over an RT axis longer than 512: the unfused conv path
+    (32, 16, 700, 2, 1, 16, "unfused"),
+    # the deep levels' rows backward (k_res_rows.hip, >= 16 rows per CU) with a partly filled last 16-row tile per sample (98 rows per
+    # sample); tests/test_res_forms.py runs every instantiation of it
+    (24, 12, 4, 4214, 98, 12, "rows"),
+    # the unfused forward with several rows per sample: rows of 128 at 12 channels (backward k_res_bwd), a 6-channel skip (backward
+    # k_res_bwd_cp); k_res_fwd_v4 with a skip input (backward k_res_bwd)
+    (12, 12, 128, 8, 4, 0, "plain"), (22, 16, 4, 96, 48, 16, "cp"), (8, 4, 128, 12, 4, 4, "plain")]
+
+
+@pytest.mark.parametrize("cin,cout,n,rows,rps,split,form", RES_BWD_CASES, ids=["-".join(map(str, c[:6])) for c in RES_BWD_CASES])
+def test_resnet_block_backward_vs_oracle_autograd(N, cin, cout, n, rows, rps, split, form):
     """every dispatch of the ResnetBlock (fused m/z-row kernels, channel-parallel deep levels, the step-by-step bottleneck path
     with rows_per_sample = 1): forward, dX, all weight gradients and d(scale, shift) against autograd over the oracle"""
     from oracle import dq_oracle as O
@@ -183,6 +189,8 @@ def test_resnet_block_backward_vs_oracle_autograd(N, cin, cout, n, rows, rps, sp
     if cin != cout:
         wd["res_conv.weight"], wd["res_conv.bias"] = r(cout, cin, 1) * 0.3, r(cout) * 0.1
     x, temb, gy = r(rows, cin, n), r(B, 16), r(rows, cout, n)
+    cinA = split if split else cin
+    assert N.resblock_forms(cinA, cin - cinA, cout, rows, n, rps)[1] == form
     p = {"b." + k: v.clone().requires_grad_() for k, v in wd.items()}
     xo = x.clone().requires_grad_()
     yo = O.resnet_block(p, "b", xo, temb, rps)

@@ -253,3 +253,29 @@ def test_train_signatures_keep_the_reference_positional_order(tmp_path):
     (tmp_path / "c").mkdir()
     h2.train(Loader([(z, z[..., 0], z, z[..., 0])]), 1, 2, 0, 5e-3, False, str(tmp_path / "c" / "b.ckpt"))
     assert h2.seen == [5e-3, 5e-3]                                 # warmup_epochs <= 0: constant lr (reference :498-559)
+
+
+def test_dispatch_options_and_resblock_forms_without_a_gpu():
+    """dq_get_option_effective resolves / clamps the thresholds, and dq_resblock_forms answers from the shape and the options alone
+    (it launches nothing); the default rule itself needs the device (tests/test_res_forms.py)"""
+    from dquartic import _native as N
+
+    key = "res_rows_bwd_min_rows"
+    assert N.get_option(key) == -1 and N.get_option_effective("no_such_key") == -1
+    assert N.get_option_effective("la_rows_bwd_min_rows") == 0  # its default rule: every row count
+    try:
+        N.set_option(key, 1 << 40)
+        assert N.get_option(key) == 1 << 40 and N.get_option_effective(key) == 2 ** 31 - 1
+        assert N.resblock_forms(12, 8, 12, 34 * 1000, 8, 34) == ("level", "cp")
+        N.set_option(key, 0)
+        assert N.get_option_effective(key) == 0
+        assert N.resblock_forms(12, 8, 12, 2 * 17, 8, 17) == ("level", "rows")      # an up block at 34 rows
+        assert N.resblock_forms(16, 0, 16, 3 * 2, 2, 2) == ("level", "rows")        # a down block at 6 rows
+        assert N.resblock_forms(8, 0, 12, 3 * 34, 4, 34) == ("unfused", "rows")     # res_conv without a skip
+        assert N.resblock_forms(16, 6, 16, 3 * 34, 4, 34)[1] == "cp"                # a skip of 6 channels
+        assert N.resblock_forms(16, 0, 16, 3, 4, 1) == ("rt", "rt")                 # the bottleneck
+        with pytest.raises(RuntimeError, match="dq_resblock"):
+            N.resblock_forms(12, 0, 12, 35, 4, 34)                                  # rows not a multiple of rows_per_sample
+    finally:
+        N.set_option(key, -1)
+    assert N.get_option(key) == -1

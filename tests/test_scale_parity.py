@@ -105,6 +105,31 @@ def test_train_one_batch_at_bench_size_vs_oracle(la_form):
     assert abs(float(dm.optimizer.last_grad_norm) - gn_ref) < 1e-4 * gn_ref
 
 
+def test_train_step_at_reference_window_vs_oracle():
+    """The reference's own window length, RT = 34 (MZ 64), at batch 128: 4,352 rows per level, so the deep levels' ResnetBlock backward
+    takes the row form under the library's own rule (k_res_rows.hip), with a 2-row last tile in every sample of every such block.  Loss and
+    all 395 gradients vs the per-sample oracle."""
+    from dquartic import _native as N
+    from dquartic.model.model import DDIMDiffusionModel
+
+    B, RT, MZ = 128, 34, 64
+    assert N.get_option("res_rows_bwd_min_rows") < 0 and B * RT >= N.get_option_effective("res_rows_bwd_min_rows")
+    for cinA, cinB, C, n in ((12, 0, 12, 4), (12, 0, 12, 2), (16, 12, 16, 2), (12, 12, 12, 4), (12, 8, 12, 8)):  # the row-form blocks at MZ 64
+        assert N.resblock_forms(cinA, cinB, C, B * RT, n, RT)[1] == "rows", (cinA, cinB, C, n)
+    net, params = _net(MZ, 15)
+    dm = DDIMDiffusionModel(model_class=net.cuda(), device="cuda")
+    g = torch.Generator().manual_seed(9)
+    x0, c2, c1 = torch.rand(B, RT, MZ, generator=g), torch.rand(B, RT, MZ, generator=g), torch.rand(B, RT, generator=g)
+    t = torch.randint(0, 1000, (B,), generator=g)
+    nz = torch.randn(B, RT, MZ, generator=g)
+    lo, _, po = _oracle_grads(params, MZ, x0, c2, c1, t, nz)
+    net.train()
+    loss = dm.train_step_fused(x0.cuda(), c2.cuda(), c1.cuda(), t=t.cuda(), noise=nz.cuda())
+    assert abs(float(loss) - lo) < 2e-5 * abs(lo), (float(loss), lo)
+    worst = _check_grads(net, po)
+    print("batch-128 RT-34 train step: loss", float(loss), "oracle", lo, "worst grad", worst)
+
+
 def test_train_step_is_bitwise_repeatable():
     """two dq_train_step calls on the same inputs: identical loss and flat gradient, bit for bit (no order-dependent float
     atomics anywhere on the path; SURVEY section 5 'race detection')"""
@@ -181,7 +206,7 @@ def test_sample_batch512_graph_vs_oracle_and_batch_independence(la_form):
     # to the fp32 tolerance instead.
     from dquartic import _native as N
     if la_form == "default":
-        assert B * RT >= N.get_option("la_small_min_rows") and N.get_option("la_small_min_rows") < 0  # (the rule, not a forced value)
+        assert B * RT >= N.get_option_effective("la_small_min_rows") and N.get_option("la_small_min_rows") < 0  # (the rule, not a forced value)
         with torch.no_grad():
             s_rule, _ = dm.sample(xd[:2].contiguous(), c2d[:2].contiguous(), c1d[:2].contiguous(), num_steps=NS)
         assert float((s_rule - s[:2]).abs().max() / s[:2].abs().max()) < 5e-4
