@@ -289,7 +289,7 @@ int tiny_bwd_slots(const TinyBwd& t);
 int64_t tiny_bwd_img_floats(const TinyBwd& t);
 int launch_tiny_bwd_images(const TinyBwd* calls, int count, hipStream_t s);
 int launch_tiny_bwd(const TinyBwd& t, hipStream_t s);
-// k_res_wg.hip: ResnetBlock backward of the wide levels (C = 4 / 8, rows of 8..256 positions) with the block's weight gradients formed
+// k_res_wg.hip: ResnetBlock backward of the wide levels (C = 4 / 8 only, rows of 8..64 positions) with the block's weight gradients formed
 // in the same launch on the 4x4x1 matrix pipe.  Every workgroup leaves [c1.w | c1.b | g1 | c2.w | c2.b | g2 | res.w | res.b | dscale |
 // dshift] in its own slot of `part`; launch_res_wg_reduce adds the slots up in block order into the flat gradient buffer (the
 // block's parameters are contiguous there, in this order) and into the per-sample d(scale, shift).

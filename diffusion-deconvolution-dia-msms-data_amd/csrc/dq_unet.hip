@@ -181,9 +181,6 @@ namespace {
 bool tail_fork_enabled() {
   return !DQ_DEV_FLAG("DQ_NO_TAIL_FORK", '1');  // (dev switch)
 }
-bool side_stream_enabled() {
-  return !DQ_DEV_FLAG("DQ_NO_SIDE_STREAM", '1');  // (dev switch)
-}
 
 struct Ctx {
   const Plan& p;
@@ -1721,7 +1718,7 @@ int dq_unet_bwd(dq_plan* plan, const float* params, const float* rope_freqs, con
   DQ_REQUIRE(workspace_bytes >= 2 * (int64_t)sizeof(float) * plan->arena.floats, "dq_unet_bwd: workspace too small (training=1)");
   float* W = (float*)workspace;
   Ctx c{plan->plan, plan->arena, params, W, W + plan->arena.floats, grads, B, RT, (hipStream_t)stream};
-  c.owner = (side_stream_enabled() && !plan->no_side) ? plan : nullptr;
+  c.owner = plan->no_side ? nullptr : plan;
   plan->twin_zeroed = nullptr;  // (only a forked forward of the SAME dq_train_step call clears the twin ahead of its backward)
   return unet_backward(c, rope_freqs, init_cond, cond_mul, cond_add, plan->dev, grad_out, grad_x);
 }
@@ -1815,7 +1812,7 @@ int dq_train_step(dq_plan* plan, const float* params, const float* rope_freqs, c
   hipStream_t s = (hipStream_t)stream;
   float* W = (float*)workspace;
   Ctx c{plan->plan, a, params, W, W + a.floats, grads, B, RT, s};
-  c.owner = (side_stream_enabled() && !plan->no_side) ? plan : nullptr;
+  c.owner = plan->no_side ? nullptr : plan;
   const int64_t per = (int64_t)RT * plan->plan.mz;
   const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
   const bool qs_fused_on = !DQ_DEV_FLAG("DQ_NO_QSAMPLE_FUSE", '1');  // (dev switch)

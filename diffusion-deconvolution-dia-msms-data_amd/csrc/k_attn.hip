@@ -16,7 +16,6 @@
 //   dK/dV     (keys on lanes):     S = xty(Qt, Kt), dP = xty(dOt, Vt) ; dV = xty(dOx, P) ; dK = xty(Qx, dS)
 // 3.4 % of the network FLOPs at 64x400.
 #include "dq_common.h"
-#include "dq_dev.h"
 #include "dq_kernels.h"
 #include "dq_mfma.h"
 #include <cstdlib>
@@ -128,22 +127,21 @@ __device__ __forceinline__ f32x16 rows_scalar(const float* __restrict__ v, int R
   return t;
 }
 
-// How many waves share one block of 32 queries (forward, dQ), each taking every NW-th key block: the sweep over the other side is a
-// serial chain of RT / 32 steps per wave, and at a training batch (32 samples x 4 heads x 13 blocks = 1664 waves on 1024 SIMDs) nothing
-// hides its latencies.  The next block's tiles are in flight while the current one multiplies (forward / dQ / dK,dV at batch 32: 48 / 70 /
-// 157 -> 44 / 62 / 130 us; the products themselves -- dependent chains of sixteen 64-cycle fp32 MFMAs -- bound the three launches at
-// 18 / 27 / 36 us).  With a sampling batch the grid fills the SIMDs many times over and one wave per block (no merge) is the form.
-// ---- forward: NW waves = the same 32 queries of one (sample, head); their online-softmax partials (m, l, O^T) meet in LDS and are
-// merged by wave 0 in wave order (fixed order: repeatable)
+// One wave per block of 32 queries (forward, dQ): it sweeps every key block, a serial chain of RT / 32 steps, with the next block's tiles in
+// flight while the current one multiplies (forward / dQ / dK,dV at batch 32: 48 / 70 / 157 -> 44 / 62 / 130 us; the products themselves --
+// dependent chains of sixteen 64-cycle fp32 MFMAs -- bound the three launches at 18 / 27 / 36 us).  Four waves per query block, each taking
+// every fourth key block with the partials merged in LDS, were measured at batch 32: forward 44 us either way, dQ 62 -> 89 us (its 253
+// registers leave two waves per SIMD either way, and the merge comes on top).  Nor may the split follow the grid size: a window's result
+// must not depend on the batch it is computed in (the merge adds the partial softmaxes in another order, and tests/test_scale_parity.py
+// holds batch 2 against batch 512 bit for bit).
+// ---- forward: one wave = 32 queries of one (sample, head), online softmax over the key blocks
 // (Round-4 measurements, batch 512: with every key block reading block 0's tiles -- L1-hot -- the launch takes 512 instead of 602 us, so the
 // tile loads are 15 % of it; two accumulation chains per product change nothing forward and spill backward; launch bounds of 4 / 5 waves per
 // SIMD spill 41 / 80 registers: 1,012 / 1,441 us.  The sweep runs at ~3,500 cycles per key block and SIMD against 2,048 cycles of MFMA.)
-template <int NW>
-__global__ void __launch_bounds__(64 * NW) k_attn_fwd(const float* __restrict__ q, int64_t q_bs, const float* __restrict__ k, int64_t k_bs,
-                                                      const float* __restrict__ v, int64_t v_bs, float* __restrict__ o,
-                                                      float* __restrict__ lse, int RT) {
+__global__ void __launch_bounds__(64) k_attn_fwd(const float* __restrict__ q, int64_t q_bs, const float* __restrict__ k, int64_t k_bs,
+                                                 const float* __restrict__ v, int64_t v_bs, float* __restrict__ o,
+                                                 float* __restrict__ lse, int RT) {
   const int lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int bh = blockIdx.y, b = bh >> 2, h = bh & 3;
   const int i0 = blockIdx.x * 32, i = i0 + col;
   const float* qb = q + b * q_bs + (int64_t)h * 32 * RT;
@@ -152,13 +150,16 @@ __global__ void __launch_bounds__(64 * NW) k_attn_fwd(const float* __restrict__ 
   const f32x16 Qt = tile_ch_rows<false>(qb, RT, i0, col, half, ATT_SCALE);  // rows d, col i
   f32x16 Oa = {0};                                                   // rows e, col i
   float m = -INFINITY, l = 0.f;
-  const int jlast = (RT - 1) / 32 * 32;  // (prefetches past the end re-read the last block and are not used)
-  f32x16 Kn = tile_ch_rows<false>(kb, RT, min(wv * 32, jlast), col, half, 1.f);   // rows d, col j
-  f32x16 Vn = tile_pos_rows(vb, RT, min(wv * 32, jlast), col, half, 1.f);  // rows j, col e
-  for (int j0 = wv * 32; j0 < RT; j0 += 32 * NW) {
+  // the key block a prefetch reads (past the end: the last block again, not used).  The first prefetch goes through the same clamp: with
+  // the constant 0 in its place the compiler keeps 24 registers more here (165 -> 189: one wave per SIMD less)
+  const int jlast = (RT - 1) / 32 * 32;
+  auto kblk = [&](int j) { return min(j, jlast); };
+  f32x16 Kn = tile_ch_rows<false>(kb, RT, kblk(0), col, half, 1.f);   // rows d, col j
+  f32x16 Vn = tile_pos_rows(vb, RT, kblk(0), col, half, 1.f);  // rows j, col e
+  for (int j0 = 0; j0 < RT; j0 += 32) {
     const f32x16 Kt = Kn, Vx = Vn;
-    Kn = tile_ch_rows<false>(kb, RT, min(j0 + 32 * NW, jlast), col, half, 1.f);
-    Vn = tile_pos_rows(vb, RT, min(j0 + 32 * NW, jlast), col, half, 1.f);
+    Kn = tile_ch_rows<false>(kb, RT, kblk(j0 + 32), col, half, 1.f);
+    Vn = tile_pos_rows(vb, RT, kblk(j0 + 32), col, half, 1.f);
     f32x16 St = xty(Kt, Qt, f32x16{0});                           // rows j, col i
     float mx = -INFINITY;
 #pragma unroll
@@ -182,32 +183,6 @@ __global__ void __launch_bounds__(64 * NW) k_attn_fwd(const float* __restrict__ 
     for (int r = 0; r < 16; ++r) Oa[r] *= al;
     Oa = xty(Vx, St, Oa);  // rows e, col i
   }
-  if constexpr (NW > 1) {
-    __shared__ float part[NW - 1][18][64];
-    if (wv > 0) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) part[wv - 1][r][lane] = Oa[r];
-      part[wv - 1][16][lane] = m;
-      part[wv - 1][17][lane] = l;
-    }
-    __syncthreads();
-    if (wv > 0) return;
-    float mt = m;  // (wave 0 always has key block 0: finite)
-#pragma unroll
-    for (int w = 0; w < NW - 1; ++w) mt = fmaxf(mt, part[w][16][lane]);
-    const float s0 = __builtin_amdgcn_exp2f((m - mt) * LOG2E);
-    l *= s0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) Oa[r] *= s0;
-#pragma unroll
-    for (int w = 0; w < NW - 1; ++w) {
-      const float sw = __builtin_amdgcn_exp2f((part[w][16][lane] - mt) * LOG2E);  // (a wave without key blocks: m = -inf, weight 0)
-      l = fmaf(part[w][17][lane], sw, l);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) Oa[r] = fmaf(part[w][r][lane], sw, Oa[r]);
-    }
-    m = mt;
-  }
   if (i < RT) {
     const float rl = 1.0f / l;
     float* ob = o + (int64_t)b * 128 * RT + (int64_t)h * 32 * RT;
@@ -217,41 +192,21 @@ __global__ void __launch_bounds__(64 * NW) k_attn_fwd(const float* __restrict__ 
   }
 }
 
-// waves per query / key block: four while the grid would leave SIMDs short of work, one otherwise
-// waves per query block: ONE.  Four (each wave every fourth key block, partials merged in LDS) were measured at batch 32: forward 44 us
-// either way, dQ 62 -> 89 us (its 253 registers leave two waves per SIMD either way, and the merge comes on top).  The four-wave forms
-// stay selectable (DQ_ATTN_NW_F / DQ_ATTN_NW_Q = 4; tests/test_blocks_gpu.py is run with them).
-#ifdef DQ_DEV_SWITCHES
-static int attn_split(int B, int RT, bool query_side) {
-  const int env_f = DQ_DEV_FLAG("DQ_ATTN_NW_F", '4') ? 4 : 0, env_q = DQ_DEV_FLAG("DQ_ATTN_NW_Q", '4') ? 4 : 0;  // (dev switches)
-  (void)B; (void)RT;
-  // (not chosen by grid size: a window's result must not depend on the batch it is computed in -- the four-wave merge adds the
-  // partial softmaxes in another order, and tests/test_scale_parity.py holds batch 2 against batch 512 bit for bit)
-  return query_side ? (env_q ? env_q : 1) : (env_f ? env_f : 1);
-}
-#endif
-
 int launch_attn_fwd(const float* q, int64_t q_bs, const float* k, int64_t k_bs, const float* v, int64_t v_bs, float* o, float* lse,
                     int B, int RT, hipStream_t s) {
   if (B == 0 || RT == 0) return 0;
-#ifdef DQ_DEV_SWITCHES
-  if (attn_split(B, RT, false) == 4) hipLaunchKernelGGL(k_attn_fwd<4>, dim3(cdiv(RT, 32), B * 4), dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, o, lse, RT);
-  else
-#endif
-  hipLaunchKernelGGL(k_attn_fwd<1>, dim3(cdiv(RT, 32), B * 4), dim3(64), 0, s, q, q_bs, k, k_bs, v, v_bs, o, lse, RT);
+  hipLaunchKernelGGL(k_attn_fwd, dim3(cdiv(RT, 32), B * 4), dim3(64), 0, s, q, q_bs, k, k_bs, v, v_bs, o, lse, RT);
   DQ_LAUNCH_CHECK();
   return 0;
 }
 
 // ---- backward, query side: delta_i = dO_i . O_i ; dQ_i = 32^-0.5 * sum_j P_ij (dP_ij - delta_i) K_j
-template <int NW>
-__global__ void __launch_bounds__(64 * NW) k_attn_bwd_q(const float* __restrict__ q, int64_t q_bs, const float* __restrict__ k,
-                                                        int64_t k_bs, const float* __restrict__ v, int64_t v_bs,
-                                                        const float* __restrict__ o, const float* __restrict__ d_o,
-                                                        const float* __restrict__ lse, float* __restrict__ delta,
-                                                        float* __restrict__ dq, int64_t dq_bs, int RT) {
+__global__ void __launch_bounds__(64) k_attn_bwd_q(const float* __restrict__ q, int64_t q_bs, const float* __restrict__ k,
+                                                   int64_t k_bs, const float* __restrict__ v, int64_t v_bs,
+                                                   const float* __restrict__ o, const float* __restrict__ d_o,
+                                                   const float* __restrict__ lse, float* __restrict__ delta,
+                                                   float* __restrict__ dq, int64_t dq_bs, int RT) {
   const int lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int bh = blockIdx.y, b = bh >> 2, h = bh & 3;
   const int i0 = blockIdx.x * 32, i = i0 + col;
   const float* qb = q + b * q_bs + (int64_t)h * 32 * RT;
@@ -260,9 +215,10 @@ __global__ void __launch_bounds__(64 * NW) k_attn_bwd_q(const float* __restrict_
   const float* ob = o + (int64_t)b * 128 * RT + (int64_t)h * 32 * RT;
   const float* dob = d_o + (int64_t)b * 128 * RT + (int64_t)h * 32 * RT;
   const int jlast = (RT - 1) / 32 * 32;
-  f32x16 Kn = tile_ch_rows(kb, RT, min(wv * 32, jlast), col, half, 1.f);   // rows d, col j
-  f32x16 Vn = tile_ch_rows(vb, RT, min(wv * 32, jlast), col, half, 1.f);   // rows e, col j
-  f32x16 Xn = tile_pos_rows(kb, RT, min(wv * 32, jlast), col, half, 1.f);  // rows j, col d
+  auto kblk = [&](int j) { return min(j, jlast); };  // (as in k_attn_fwd, the first prefetch included)
+  f32x16 Kn = tile_ch_rows(kb, RT, kblk(0), col, half, 1.f);   // rows d, col j
+  f32x16 Vn = tile_ch_rows(vb, RT, kblk(0), col, half, 1.f);   // rows e, col j
+  f32x16 Xn = tile_pos_rows(kb, RT, kblk(0), col, half, 1.f);  // rows j, col d
   const f32x16 Qt = tile_ch_rows(qb, RT, i0, col, half, ATT_SCALE);  // rows d, col i
   const f32x16 dOt = tile_ch_rows(dob, RT, i0, col, half, 1.f);      // rows e, col i
   float dl = 0.f;
@@ -274,11 +230,11 @@ __global__ void __launch_bounds__(64 * NW) k_attn_bwd_q(const float* __restrict_
   }
   const float ls = i < RT ? lse[(int64_t)bh * RT + i] : INFINITY;
   f32x16 dQa = {0};  // rows d, col i
-  for (int j0 = wv * 32; j0 < RT; j0 += 32 * NW) {
+  for (int j0 = 0; j0 < RT; j0 += 32) {
     const f32x16 Kt = Kn, Vt = Vn, Kx = Xn;
-    Kn = tile_ch_rows(kb, RT, min(j0 + 32 * NW, jlast), col, half, 1.f);
-    Vn = tile_ch_rows(vb, RT, min(j0 + 32 * NW, jlast), col, half, 1.f);
-    Xn = tile_pos_rows(kb, RT, min(j0 + 32 * NW, jlast), col, half, 1.f);
+    Kn = tile_ch_rows(kb, RT, kblk(j0 + 32), col, half, 1.f);
+    Vn = tile_ch_rows(vb, RT, kblk(j0 + 32), col, half, 1.f);
+    Xn = tile_pos_rows(kb, RT, kblk(j0 + 32), col, half, 1.f);
     f32x16 St = xty(Kt, Qt, f32x16{0});                           // rows j, col i
     const f32x16 dPt = xty(Vt, dOt, f32x16{0});                   // rows j, col i
 #pragma unroll
@@ -287,19 +243,6 @@ __global__ void __launch_bounds__(64 * NW) k_attn_bwd_q(const float* __restrict_
       St[r] = p * (dPt[r] - dl);  // dS^T
     }
     dQa = xty(Kx, St, dQa);
-  }
-  if constexpr (NW > 1) {
-    __shared__ float part[NW - 1][16][64];
-    if (wv > 0) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) part[wv - 1][r][lane] = dQa[r];
-    }
-    __syncthreads();
-    if (wv > 0) return;
-#pragma unroll
-    for (int w = 0; w < NW - 1; ++w)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dQa[r] += part[w][r][lane];
   }
   if (i < RT) {
     float* dqb = dq + b * dq_bs + (int64_t)h * 32 * RT;
@@ -384,11 +327,7 @@ int launch_attn_bwd(const float* q, int64_t q_bs, const float* k, int64_t k_bs, 
                     int64_t dv_bs, int B, int RT, hipStream_t s) {
   if (B == 0 || RT == 0) return 0;
   dim3 grid(cdiv(RT, 32), B * 4);
-#ifdef DQ_DEV_SWITCHES
-  if (attn_split(B, RT, true) == 4) hipLaunchKernelGGL(k_attn_bwd_q<4>, grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, o, d_o, lse, delta, dq, dq_bs, RT);
-  else
-#endif
-  hipLaunchKernelGGL(k_attn_bwd_q<1>, grid, dim3(64), 0, s, q, q_bs, k, k_bs, v, v_bs, o, d_o, lse, delta, dq, dq_bs, RT);
+  hipLaunchKernelGGL(k_attn_bwd_q, grid, dim3(64), 0, s, q, q_bs, k, k_bs, v, v_bs, o, d_o, lse, delta, dq, dq_bs, RT);
   DQ_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_attn_bwd_kv, grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, d_o, lse, delta, dk, dk_bs, dv, dv_bs, RT);
   DQ_LAUNCH_CHECK();

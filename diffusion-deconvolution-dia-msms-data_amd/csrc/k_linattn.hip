@@ -20,7 +20,6 @@
 //   (again C rows, 4x4x1).  Both softmax normalisations are applied to the C-row results (M, P / R), not to the 32-row tiles.
 //   The W2 contraction and the post-norm run on the VALU for this lane's own channels; HBM traffic: x in, y out (+ ypre).
 #include "dq_common.h"
-#include "dq_dev.h"
 #include "dq_kernels.h"
 #include "dq_mfma.h"
 #include "dq_probe.h"
@@ -551,13 +550,7 @@ static int la_num_cus() {
   static const int v = [] { int d = 0; hipDeviceProp_t pr; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) ? pr.multiProcessorCount : 256; }();
   return v;
 }
-#ifdef DQ_DEV_SWITCHES
-#define DQ_LA_FP32_TOO 1
-#else
-#define DQ_LA_FP32_TOO 0
-#endif
-// split-bf16 K = C projections for 4 / 8 channels; DQ_LA_PROJ=fp32 in the dev build keeps the fp32 matrix-pipe form of rounds 1-3
-bool la_proj_bf16() { return !DQ_DEV_FLAG("DQ_LA_PROJ", 'f'); }
+// split-bf16 K = C projections for 4 / 8 channels
 template <int C>
 static int linattn_fwd_n(const LinAttn& a, hipStream_t s) {
 #define DQ_LA(NN)                                                                      \
@@ -567,11 +560,7 @@ static int linattn_fwd_n(const LinAttn& a, hipStream_t s) {
     constexpr bool CAN_BF = C <= 8 && NN > 1 && !(C == 8 && NN <= 8);                  \
     const int units = cdiv(a.rows, RW);                                                \
     const int grid = cdiv(units, 4);  /* one unit per wave: a wave walking several units with the next unit's x in flight was measured slower */ \
-    /* (the fp32-projection instantiation of a shape whose default is split-bf16 exists in the dev build only: DQ_LA_PROJ=fp32) */ \
-    if (DQ_LA_FP32_TOO && !(CAN_BF && la_proj_bf16()))                                 \
-      hipLaunchKernelGGL((k_linattn_fwd<C, NN, CAN_BF && !DQ_LA_FP32_TOO>), dim3(grid), dim3(256), 0, s, a); \
-    else                                                                               \
-      hipLaunchKernelGGL((k_linattn_fwd<C, NN, CAN_BF>), dim3(grid), dim3(256), 0, s, a); \
+    hipLaunchKernelGGL((k_linattn_fwd<C, NN, CAN_BF>), dim3(grid), dim3(256), 0, s, a); \
     break;                                                                             \
   }
   switch (a.n) {

@@ -14,7 +14,6 @@
 // Same contract as k_res_bwd / k_res_bwd_cp (ResBwd): dU1 / dU2 written for the weight-gradient kernels, d(input) stored or accumulated
 // into dA / dB, every workgroup's [d g2 | d g1 | d scale | d shift] sums in its own gpart slot (launch_part_reduce: ordered, repeatable).
 #include "dq_common.h"
-#include "dq_dev.h"
 #include "dq_kernels.h"
 #include "dq_options.h"
 #include <algorithm>
@@ -296,7 +295,6 @@ int res_rows_bwd_min_rows() {
 }
 
 bool res_rows_bwd_usable(const ResBwd& a) {
-  if (DQ_DEV_FLAG("DQ_NO_RES_ROWS", '1')) return false;  // (dev switch)
   if (!(a.C == 12 || a.C == 16) || !(a.n == 2 || a.n == 4 || a.n == 8) || a.rows_per_sample < 2) return false;
   if (a.rows < res_rows_bwd_min_rows()) return false;
   if (a.cinA < 4 || a.cinA > 16 || (a.cinA & 3) || a.cinB < 0 || a.cinB > 16 || (a.cinB & 3)) return false;

@@ -1,4 +1,4 @@
-// ResnetBlock backward for the wide m/z levels (4 / 8 channels, rows of 8..256 positions) WITH the block's weight gradients
+// ResnetBlock backward for the wide m/z levels (4 / 8 channels, rows of 8..64 positions) WITH the block's weight gradients
 // formed in the same launch (reference dquartic/model/unet1d.py:271-323; autograd of it is what model_interface.py:1120 runs).
 //
 // k_res_bwd (k_res.hip) leaves dU2 / dU1 in memory and three weight-gradient launches (+ reduces) on the side stream re-read
@@ -23,12 +23,10 @@
 //     dshift] -- the order of the flat parameter buffer -- for k_res_wg_reduce to add up in block order: no atomics, bitwise
 //     repeatable.
 #include "dq_common.h"
-#include "dq_dev.h"
 #include "dq_kernels.h"
 #include "k_res_common.h"
 #include "dq_probe.h"
 #include <algorithm>
-#include <cstdlib>
 
 namespace dq {
 
@@ -51,7 +49,7 @@ constexpr int RUN = 16;  // consecutive positions a 4-lane block of the MFMA wal
 // an odd multiple of 4 modulo the 32 banks of a 4-byte LDS read.
 template <int C>
 struct Img {
-  static constexpr int ST = C == 4 ? 4 : (C == 8 ? 12 : 20);  // (floats per position: an odd number of 16-byte slots)
+  static constexpr int ST = C == 4 ? 4 : 12;  // (floats per position: an odd number of 16-byte slots)
   static constexpr int FLOATS = (TILE + 2) * ST + ((TILE + 2) / RUN + 1) * 4;
   __device__ static __forceinline__ int at(int q) { return q * ST + (q >> 4) * 4; }  // q = position in the tile + 1
 };
@@ -63,11 +61,11 @@ __device__ __forceinline__ constexpr int run_off(int s) { return s * ST + (s == 
 }  // namespace
 
 template <int C, bool WR>
-__global__ void __launch_bounds__(256, C >= 12 ? 1 : 2) k_res_bwd_wg(ResBwdWg a) {
+__global__ void __launch_bounds__(256, 2) k_res_bwd_wg(ResBwdWg a) {
   using I = Img<C>;
   constexpr int ST = I::ST, CQ = C / 4;
-  // (dynamic LDS: 12 / 16 channels need 84 - 140 KB -- one workgroup per CU, whose 512 registers per lane the 47 accumulator quads of a
-  // 16-channel block with a residual conv need anyway)
+  // (dynamic LDS: the 8-channel images take 52 KB without a residual conv and 79 KB with one, res_wg_lds_bytes -- above the 48 KB of a
+  // static declaration)
   extern __shared__ __attribute__((aligned(16))) float lds_all[];
   float* i_du2 = lds_all;
   float* i_du1 = i_du2 + I::FLOATS;
@@ -140,20 +138,15 @@ __global__ void __launch_bounds__(256, C >= 12 ? 1 : 2) k_res_bwd_wg(ResBwdWg a)
   const bool v_10 = doW1 && h10 < cinq, v_11 = doW1 && h11 >= 0 && h11 < cinq;
   auto ximg = [&](int h) -> const float* { return (h < CQ || !WR ? i_xa + 4 * (h < CQ ? h : 0) : i_xb + 4 * (h - CQ)) + lb; };
 
-  // 12 / 16 channels (WIDE): wave = output-channel quad (12 channels: the fourth wave repeats quad 0 and is not flushed); it runs every
-  // input-channel quad of dW2 (CQ), dWr and dW1 (GI of cat(A, B)).  Rows of any power-of-two length <= 64: the taps' zero padding per step
-  // and lane from the position's place in its row.
-  constexpr bool WIDE = C >= 12;
-  constexpr int NQ2 = WIDE ? CQ : 1, NQ1 = WIDE ? GI : 2;
-  const int gw = WIDE ? (wv < CQ ? wv : 0) : g;   // this wave's output-channel quad
-  const bool w_on = !WIDE || wv < CQ;             // its accumulators are flushed
-  f32x4 aW2[NQ2][3], aWr[NQ1], aW1[NQ1][3], aB2 = {0.f, 0.f, 0.f, 0.f}, aBr = aB2, aB1 = aB2;
+  // MFMA accumulators [input-channel quad of this wave's jobs][tap]: one quad of dW2, up to two of dW1 / dWr.  (The one-quad loop stays a
+  // loop: written as three plain stores, the init changed the register allocation and schedule of the 4-channel kernels.)
+  f32x4 aW2[1][3], aWr[2], aW1[2][3], aB2 = {0.f, 0.f, 0.f, 0.f}, aBr = aB2, aB1 = aB2;
 #pragma unroll
-  for (int h = 0; h < NQ2; ++h)
+  for (int h = 0; h < 1; ++h)
 #pragma unroll
     for (int k = 0; k < 3; ++k) aW2[h][k] = aB2;
 #pragma unroll
-  for (int h = 0; h < NQ1; ++h) {
+  for (int h = 0; h < 2; ++h) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) aW1[h][k] = aB2;
     aWr[h] = aB2;
@@ -230,42 +223,6 @@ __global__ void __launch_bounds__(256, C >= 12 ? 1 : 2) k_res_bwd_wg(ResBwdWg a)
     __syncthreads();
     DQ_PSTAMP(100000 + C * 10 + (WR ? 1 : 0), 3);
     // ---- matrix pipe: dW2 (+ db2), dWr (+ dbr)
-    if constexpr (WIDE) {
-      // zero padding of the outer taps: position 16 blk + s is the first / last of its row (per lane; n is a power of two)
-      auto first_in_row = [&](int s) { return ((blk * RUN + s) & (n - 1)) == 0; };
-      auto last_in_row = [&](int s) { return ((blk * RUN + s) & (n - 1)) == n - 1; };
-      {
-        const float* A = i_du2 + lb + 4 * gw;
-        float bprev[CQ], bcur[CQ];
-#pragma unroll
-        for (int h = 0; h < CQ; ++h) { bprev[h] = (i_a1 + lb + 4 * h)[-ST]; bcur[h] = (i_a1 + lb + 4 * h)[0]; }
-#pragma unroll
-        for (int s = 0; s < RUN; ++s) {
-          const float av = A[run_off<ST>(s)];
-          const bool fl = first_in_row(s), ll = last_in_row(s);
-#pragma unroll
-          for (int h = 0; h < CQ; ++h) {
-            const float* Bp = i_a1 + lb + 4 * h;
-            const float bnext = s + 1 < RUN ? Bp[run_off<ST>(s + 1 < RUN ? s + 1 : s)] : Bp[RUN * ST + 4];
-            aW2[h][0] = mfma4(av, fl ? 0.f : bprev[h], aW2[h][0]);
-            aW2[h][1] = mfma4(av, bcur[h], aW2[h][1]);
-            aW2[h][2] = mfma4(av, ll ? 0.f : bnext, aW2[h][2]);
-            bprev[h] = bcur[h]; bcur[h] = bnext;
-          }
-          aB2 = mfma4(av, 1.f, aB2);
-        }
-      }
-      if constexpr (WR) {
-        const float* A = i_do + lb + 4 * gw;
-#pragma unroll
-        for (int s = 0; s < RUN; ++s) {
-          const float av = A[run_off<ST>(s)];
-#pragma unroll
-          for (int h = 0; h < GI; ++h) aWr[h] = mfma4(av, (h < CQ ? i_xa + 4 * h : i_xb + 4 * (h - CQ))[lb + run_off<ST>(s)], aWr[h]);
-          aBr = mfma4(av, 1.f, aBr);
-        }
-      }
-    } else {
     if (doW2) {
       const float* A = i_du2 + lb + 4 * g;
       const float* Bp = i_a1 + lb + 4 * hW2;
@@ -298,7 +255,6 @@ __global__ void __launch_bounds__(256, C >= 12 ? 1 : 2) k_res_bwd_wg(ResBwdWg a)
       }
      }
     }
-    }  // narrow
     DQ_PSTAMP(100000 + C * 10 + (WR ? 1 : 0), 4);
     // ---- d a1[ci][p] = sum_co sum_k W2[co][ci][k] dU2[co][p + 1 - k]  (matrix pipe; tap k reads position p + 1 - k)
     float da1[C];
@@ -343,32 +299,6 @@ __global__ void __launch_bounds__(256, C >= 12 ? 1 : 2) k_res_bwd_wg(ResBwdWg a)
     __syncthreads();
     DQ_PSTAMP(100000 + C * 10 + (WR ? 1 : 0), 7);
     // ---- matrix pipe: dW1 (+ db1)
-    if constexpr (WIDE) {
-      auto first_in_row = [&](int s) { return ((blk * RUN + s) & (n - 1)) == 0; };
-      auto last_in_row = [&](int s) { return ((blk * RUN + s) & (n - 1)) == n - 1; };
-      const float* A = i_du1 + lb + 4 * gw;
-      float xprev[GI], xcur[GI];
-#pragma unroll
-      for (int h = 0; h < GI; ++h) {
-        const float* X = (h < CQ ? i_xa + 4 * h : i_xb + 4 * (h - CQ)) + lb;
-        xprev[h] = X[-ST]; xcur[h] = X[0];
-      }
-#pragma unroll
-      for (int s = 0; s < RUN; ++s) {
-        const float av = A[run_off<ST>(s)];
-        const bool fl = first_in_row(s), ll = last_in_row(s);
-#pragma unroll
-        for (int h = 0; h < GI; ++h) {
-          const float* X = (h < CQ ? i_xa + 4 * h : i_xb + 4 * (h - CQ)) + lb;
-          const float xnext = s + 1 < RUN ? X[run_off<ST>(s + 1 < RUN ? s + 1 : s)] : X[RUN * ST + 4];
-          aW1[h][0] = mfma4(av, fl ? 0.f : xprev[h], aW1[h][0]);
-          aW1[h][1] = mfma4(av, xcur[h], aW1[h][1]);
-          aW1[h][2] = mfma4(av, ll ? 0.f : xnext, aW1[h][2]);
-          xprev[h] = xcur[h]; xcur[h] = xnext;
-        }
-        aB1 = mfma4(av, 1.f, aB1);
-      }
-    } else {
     if (doW1) {
       const float* A = i_du1 + lb + 4 * g;
       const float* X0 = ximg(v_10 ? h10 : 0);
@@ -394,7 +324,6 @@ __global__ void __launch_bounds__(256, C >= 12 ? 1 : 2) k_res_bwd_wg(ResBwdWg a)
         p0 = c0; c0 = n0; p1 = c1; c1 = n1;
       }
     }
-    }  // narrow
     DQ_PSTAMP(100000 + C * 10 + (WR ? 1 : 0), 8);
     // ---- d x[ci][p] = sum_co sum_k W1[co][ci][k] dU1[co][p + 1 - k]  (+ residual branch) into dA / dB  (matrix pipe)
     // The input-channel quads of cat(A, B) in two passes (A's, then B's): half the accumulators live at a time -- with all 2 C / 4 quads
@@ -474,35 +403,16 @@ __global__ void __launch_bounds__(256, C >= 12 ? 1 : 2) k_res_bwd_wg(ResBwdWg a)
     const f32x4 t = blocks_sum(acc);
     if (lane < 4) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) part[base + ((4 * gw + i) * ld + 4 * h + lane) * kdim + k] = t[i];
+      for (int i = 0; i < 4; ++i) part[base + ((4 * g + i) * ld + 4 * h + lane) * kdim + k] = t[i];
     }
   };
   auto put_b = [&](f32x4 acc, int base) {
     const f32x4 t = blocks_sum(acc);
     if (lane == 0) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) part[base + 4 * gw + i] = t[i];
+      for (int i = 0; i < 4; ++i) part[base + 4 * g + i] = t[i];
     }
   };
-  if constexpr (WIDE) {
-    if (w_on) {  // wave-uniform
-#pragma unroll
-      for (int h = 0; h < CQ; ++h)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) put_w(aW2[h][k], oC2W, h, 3, k, C);
-      put_b(aB2, oC2B);
-#pragma unroll
-      for (int h = 0; h < GI; ++h) {
-        if (h < cinq) {
-#pragma unroll
-          for (int k = 0; k < 3; ++k) put_w(aW1[h][k], oC1W, h, 3, k, cin);
-          if constexpr (WR) put_w(aWr[h], oRW, h, 1, 0, cin);
-        }
-      }
-      put_b(aB1, oC1B);
-      if constexpr (WR) put_b(aBr, oRB);
-    }
-  } else {
   if (doW2) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) put_w(aW2[0][k], oC2W, hW2, 3, k, C);
@@ -520,7 +430,6 @@ __global__ void __launch_bounds__(256, C >= 12 ? 1 : 2) k_res_bwd_wg(ResBwdWg a)
     for (int k = 0; k < 3; ++k) put_w(aW1[1][k], oC1W, h11, 3, k, cin);
   }
   if (doB1) put_b(aB1, oC1B);
-  }  // narrow
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     const float s0 = wave_sum(dg2[c]), s1 = wave_sum(dg1[c]), s2 = wave_sum(dsc[c]), s3 = wave_sum(dsh[c]);
@@ -580,16 +489,13 @@ __global__ void __launch_bounds__(256) k_res_wg_reduce(ResWgReduceMulti m) {
 }
 
 bool res_wg_usable(int n, int C, int cinA, int cinB, int rows_per_sample) {
-  // (rows of up to 64 positions: a row lives inside one wave, whose DPP shifts are the conv's neighbours; 4 / 8 channels: rows of 8 or
-  // more, the run-of-16 walk of their weight-gradient phases special-cases only rows of 8)
-  if (!(C == 4 || C == 8 || C == 12 || C == 16)) return false;
-  // 12 / 16 channels (rows of 1..8 positions at the default widths): built and parity-tested, NOT the default -- measured inside the train
-  // step (B = 32) the 14 launches take 496 us against 279 us of k_res_bwd_cp + their weight-gradient launches on the side stream: one
-  // 256-position tile per workgroup leaves staging (15,000 clocks), the channel-strided loads of rows of 2 positions (28,000) and the flush of
-  // 47 accumulator quads (24,000) with nothing to overlap them.  DQ_WG_WIDE=1 selects it (tests/test_blocks_gpu.py runs both).
-  if (C >= 12 && !DQ_DEV_FLAG("DQ_WG_WIDE", '1')) return false;  // (dev switch; the 12 / 16-channel instantiations exist in the dev build only)
-  const int nmin = C >= 12 ? 1 : 8;
-  return n >= nmin && n <= 64 && (n & (n - 1)) == 0 && rows_per_sample > 1 && cinA == C && (cinB == 0 || (cinB % 4 == 0 && cinB <= C));
+  // (rows of up to 64 positions: a row lives inside one wave, whose DPP shifts are the conv's neighbours; rows of 8 or more: the run-of-16
+  // walk of the weight-gradient phases special-cases only rows of 8)
+  // 4 / 8 channels only.  A 12 / 16-channel form was built and measured slower inside the train step (B = 32): 496 us for its 14 launches
+  // against 279 us of k_res_bwd_cp + their weight-gradient launches on the side stream -- one 256-position tile per workgroup left staging,
+  // the channel-strided loads of rows of 2 positions and the flush of 47 accumulator quads with nothing to overlap them.
+  if (!(C == 4 || C == 8)) return false;
+  return n >= 8 && n <= 64 && (n & (n - 1)) == 0 && rows_per_sample > 1 && cinA == C && (cinB == 0 || (cinB % 4 == 0 && cinB <= C));
 }
 
 template <int C, bool WR>
@@ -633,13 +539,10 @@ int launch_res_bwd_wg(const ResBwdWg& a_in, hipStream_t s, ResWgReduce* red_out)
   size_t lds = 0;
 #define DQ_WGK(CC, WW) if (a.C == CC && wr == WW) { fn = (const void*)k_res_bwd_wg<CC, WW>; lds = res_wg_lds_bytes<CC, WW>(); }
   DQ_WGK(4, true) DQ_WGK(4, false) DQ_WGK(8, true) DQ_WGK(8, false)
-#ifdef DQ_DEV_SWITCHES  // (12 / 16 channels: built, parity-tested under DQ_WG_WIDE=1, slower than k_res_bwd_cp at those row lengths -- dev build only)
-  DQ_WGK(12, true) DQ_WGK(12, false) DQ_WGK(16, true) DQ_WGK(16, false)
-#endif
 #undef DQ_WGK
   DQ_REQUIRE(fn && lds <= 160 * 1024, "res_bwd_wg: no kernel for this shape");
   {
-    static int occ[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+    static int occ[2][2] = {{0, 0}, {0, 0}};
     int& o = occ[a.C / 4 - 1][wr];
     if (!o) {
       if (lds > 48 * 1024) DQ_HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -660,9 +563,6 @@ int launch_res_bwd_wg(const ResBwdWg& a_in, hipStream_t s, ResWgReduce* red_out)
   dim3 grid(gx, B), block(256);
 #define DQ_WGL(CC, WW) if (a.C == CC && wr == WW) hipLaunchKernelGGL((k_res_bwd_wg<CC, WW>), grid, block, lds, s, a);
   DQ_WGL(4, true) DQ_WGL(4, false) DQ_WGL(8, true) DQ_WGL(8, false)
-#ifdef DQ_DEV_SWITCHES
-  DQ_WGL(12, true) DQ_WGL(12, false) DQ_WGL(16, true) DQ_WGL(16, false)
-#endif
 #undef DQ_WGL
   DQ_LAUNCH_CHECK();
   if (red_out) {

@@ -154,7 +154,7 @@ RES_BWD_CASES = [
     (4, 4, 64, 70, 35, 0, "wg"), (8, 8, 32, 40, 20, 0, "wg"), (16, 8, 16, 36, 12, 8, "wg"), (8, 4, 64, 26, 13, 4, "wg"),
     (12, 8, 8, 90, 45, 8, "wg"), (8, 8, 8, 64, 32, 0, "wg"), (8, 4, 32, 48, 24, 4, "wg"), (16, 8, 256, 6, 3, 8, "plain"),
     # 12 / 16 channels below the row form's threshold: channel-parallel (k_res_bwd_cp) -- identity residual, narrower skip than the block,
-    # several tiles per sample, rows of 1..8 (their k_res_bwd_wg instantiations exist in the development build only)
+    # several tiles per sample, rows of 1..8
     (24, 12, 4, 150, 50, 12, "cp"), (32, 16, 1, 66, 33, 16, "cp"),
     (12, 12, 8, 66, 33, 0, "cp"), (16, 16, 2, 130, 65, 0, "cp"), (28, 16, 2, 160, 80, 16, "cp"), (16, 12, 8, 70, 35, 12, "cp"),
     (24, 12, 8, 200, 100, 12, "cp"), (32, 16, 4, 300, 150, 16, "cp"), (16, 16, 1, 600, 300, 0, "cp"),

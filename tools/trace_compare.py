@@ -1,5 +1,5 @@
-"""Per-kernel totals of one train step from two rocprofv3 --kernel-trace CSVs: everything on one stream (DQ_NO_SIDE_STREAM=1) against
-the default (weight gradients on the side stream).   python tools/trace_compare.py <serial.csv> <side.csv>"""
+"""Per-kernel totals of one train step from two rocprofv3 --kernel-trace CSVs: everything on one stream (dq_plan_set_side_stream(plan, 0))
+against the default (weight gradients on the side stream).   python tools/trace_compare.py <serial.csv> <side.csv>"""
 import collections
 import csv
 import re
