@@ -381,6 +381,9 @@ struct LinAttn {
 };
 // rows the register-resident kernels take (k_linattn.hip / k_la_bwd.hip); any other length goes through the sweep kernels (k_la_long.hip)
 inline bool la_short_row(int n) { return n <= 64 && (n & (n - 1)) == 0; }
+// the kernel launch_linattn_fwd takes for these operands (values mirror DQ_LA_FWD_* of include/dq_hip.h; dq_linattn_forms asks the same)
+enum LaFwdForm { LA_FWD_LONG, LA_FWD_SMALL, LA_FWD_ROWS, LA_FWD_REG };
+LaFwdForm la_fwd_form(const LinAttn& a);
 int launch_linattn_fwd(const LinAttn& a, hipStream_t s);
 // k_la_small.hip: rows of 2 / 4 (/ 8) positions at 8 / 12 / 16 channels with a prepared image (LinAttn::prep): every product on
 // v_mfma_f32_32x32x2 with lane = (channel half, row) and one group of registers per position
@@ -429,6 +432,9 @@ int launch_linattn_fwd_long(const LinAttn& a, hipStream_t s);
 int launch_linattn_bwd_long(const float* x, const float* dyp, float* dxh, const float* w_qkv, const float* w_out, const float* g_pre,
                             float* part, int C, int rows, int n, int* waves_out, hipStream_t s);
 constexpr int LA_MAX_WAVES = 2048;  // the backward grid is one resident round: <= 1024 waves, one partial slot each
+// the kernel launch_linattn_bwd takes for these operands (values mirror DQ_LA_BWD_* of include/dq_hip.h)
+enum LaBwdForm { LA_BWD_LONG, LA_BWD_ROWS, LA_BWD_REG };
+LaBwdForm la_bwd_form(const LinAttnBwd& a);
 int launch_linattn_bwd(const LinAttnBwd& a, hipStream_t s);
 // the deferred slot reductions of up to LA_REDUCE_MAX LinearAttention backwards in ONE launch (grad += ordered slot sums)
 // w2sum: 4 C C floats of scratch (the summed dW2 of the four heads; the launcher places it right behind the layer's slots);

@@ -2028,15 +2028,38 @@ int dq_linattn_fwd_prepared(const float* x, float* y, float* ypre, const float* 
   return launch_linattn_fwd(a, (hipStream_t)stream);
 }
 
-int dq_linattn_bwd(const float* x, const float* ypre, const float* dy, float* dx, const float* w_qkv, const float* w_out,
-                   const float* b_out, const float* g_pre, const float* g_out, float* dw_qkv, float* dw_out, float* db_out,
-                   float* dg_pre, float* dg_out, float* scratch, int C, int rows, int n, void* stream) {
+static_assert(LA_FWD_LONG == DQ_LA_FWD_LONG && LA_FWD_SMALL == DQ_LA_FWD_SMALL && LA_FWD_ROWS == DQ_LA_FWD_ROWS && LA_FWD_REG == DQ_LA_FWD_REG,
+              "LaFwdForm mirrors include/dq_hip.h");
+static_assert(LA_BWD_LONG == DQ_LA_BWD_LONG && LA_BWD_ROWS == DQ_LA_BWD_ROWS && LA_BWD_REG == DQ_LA_BWD_REG, "LaBwdForm mirrors include/dq_hip.h");
+int dq_linattn_forms(int C, int rows, int n, int prepared, int* fwd_form, int* bwd_form) {
+  DQ_REQUIRE(fwd_form && bwd_form && (C == 4 || C == 8 || C == 12 || C == 16) && rows >= 0 && n > 0,
+             "dq_linattn_forms: null argument / unsupported channel count / bad shape");
+  DQ_REQUIRE(!prepared || la_short_row(n), "dq_linattn_forms: prepared weights are used by rows of 1 .. 64 positions (powers of two)");
+  // the caller's tensors and the prepared weights as 16-byte aligned stand-ins (nothing is dereferenced): the operands dq_linattn_fwd /
+  // dq_linattn_fwd_prepared / dq_linattn_bwd hand over (the backward prepares the weights itself for short rows)
+  float* const base = reinterpret_cast<float*>(uintptr_t{1} << 20);
+  LinAttn f;
+  f.x = f.y = f.ypre = base; f.w_qkv = f.w_out = f.b_out = f.g_pre = f.g_out = base; f.C = C; f.rows = rows; f.n = n;
+  f.prep = prepared ? base : nullptr;
+  *fwd_form = la_fwd_form(f);
+  LinAttnBwd b;
+  b.f = f;
+  b.f.prep = la_short_row(n) ? base : nullptr;
+  b.ypre = b.dy = b.dyp = b.dxh = b.dx = base;
+  *bwd_form = la_bwd_form(b);
+  return 0;
+}
+
+static int linattn_bwd(const float* x, const float* ypre, const float* dy, float* dx, const float* w_qkv, const float* w_out,
+                       const float* b_out, const float* g_pre, const float* g_out, float* dw_qkv, float* dw_out, float* db_out,
+                       float* dg_pre, float* dg_out, float* scratch, int C, int rows, int n, int dx_store, hipStream_t s) {
   LinAttnBwd a;
   a.f.x = x; a.f.w_qkv = w_qkv; a.f.w_out = w_out; a.f.b_out = b_out; a.f.g_pre = g_pre; a.f.g_out = g_out; a.f.C = C; a.f.rows = rows;
   a.f.n = n;
   a.ypre = ypre; a.dyp = scratch; a.dxh = scratch + (int64_t)rows * C * n;
   a.part = scratch + 2 * (int64_t)rows * C * n; a.part_floats = (int64_t)LA_MAX_WAVES * 512 * C;
   a.dy = dy; a.dx = dx; a.dw_qkv = dw_qkv; a.dw_out = dw_out; a.db_out = db_out; a.dg_pre = dg_pre; a.dg_out = dg_out;
+  a.dx_store = dx_store;
   if (la_short_row(n) && C % 4 == 0 && C <= 16) {
     // the prepared weights of the network path (W2, the bounded-logit flag: k_linattn_prepare), so that this entry point runs the very
     // kernel code a train step runs: carved from the tail of the slot scratch, of which short rows use a few per cent
@@ -2044,10 +2067,23 @@ int dq_linattn_bwd(const float* x, const float* ypre, const float* dy, float* dx
     a.part_floats -= PREP;
     float* prep = a.part + a.part_floats;
     const LaPrepItem it{w_qkv, w_out, C, prep, g_pre};
-    DQ_TRY(launch_linattn_prepare(&it, 1, (hipStream_t)stream));
+    DQ_TRY(launch_linattn_prepare(&it, 1, s));
     a.f.prep = prep;
   }
-  return launch_linattn_bwd(a, (hipStream_t)stream);
+  return launch_linattn_bwd(a, s);
+}
+int dq_linattn_bwd(const float* x, const float* ypre, const float* dy, float* dx, const float* w_qkv, const float* w_out,
+                   const float* b_out, const float* g_pre, const float* g_out, float* dw_qkv, float* dw_out, float* db_out,
+                   float* dg_pre, float* dg_out, float* scratch, int C, int rows, int n, void* stream) {
+  return linattn_bwd(x, ypre, dy, dx, w_qkv, w_out, b_out, g_pre, g_out, dw_qkv, dw_out, db_out, dg_pre, dg_out, scratch, C, rows, n, 0,
+                     (hipStream_t)stream);
+}
+// dx written, not accumulated: the mode la_bwd runs the backward in inside the network
+int dq_linattn_bwd_store(const float* x, const float* ypre, const float* dy, float* dx, const float* w_qkv, const float* w_out,
+                         const float* b_out, const float* g_pre, const float* g_out, float* dw_qkv, float* dw_out, float* db_out,
+                         float* dg_pre, float* dg_out, float* scratch, int C, int rows, int n, void* stream) {
+  return linattn_bwd(x, ypre, dy, dx, w_qkv, w_out, b_out, g_pre, g_out, dw_qkv, dw_out, db_out, dg_pre, dg_out, scratch, C, rows, n, 1,
+                     (hipStream_t)stream);
 }
 
 // ---- stand-alone building blocks for the per-block parity tests (tests/test_blocks_gpu.py) ---------------------------------

@@ -1393,9 +1393,7 @@ int launch_linattn_dw_reduce_multi(const LaReduceItem* items, int count, hipStre
   return 0;
 }
 
-namespace {
 // Which kernel runs the backward: k_la_long.hip, k_la_rows_bwd.hip or the register-resident one, each only when its launcher takes every argument
-enum LaBwdForm { LA_BWD_LONG, LA_BWD_ROWS, LA_BWD_REG };
 LaBwdForm la_bwd_form(const LinAttnBwd& a) {
   const int C = a.f.C, rows = a.f.rows, n = a.f.n;
   if (!la_short_row(n)) return LA_BWD_LONG;
@@ -1407,7 +1405,6 @@ LaBwdForm la_bwd_form(const LinAttnBwd& a) {
     return LA_BWD_ROWS;
   return LA_BWD_REG;
 }
-}  // namespace
 
 // a.f.y is unused; needs: a.ypre (saved pre-norm output), the (rows, C, n) scratch dxh (and dyp for rows longer than 64) and
 // the partial-slot scratch

@@ -623,7 +623,6 @@ int launch_linattn_bwd_long(const float* x, const float* dyp, float* dxh, const 
     return 0;                                                                      \
   }
   DQ_LBL(4, 128) DQ_LBL(4, 256) DQ_LBL(8, 128) DQ_LBL(8, 256) DQ_LBL(12, 128) DQ_LBL(16, 128)
-  DQ_LBL(4, 64) DQ_LBL(4, 32) DQ_LBL(8, 32) DQ_LBL(8, 64)
 #undef DQ_LBL
   switch (C) {  // any other row length (see launch_linattn_fwd_long)
     case 4: hipLaunchKernelGGL((k_linattn_bwd_long<4, 0>), grid, block, 0, s, k); break;

@@ -740,10 +740,8 @@ int launch_linattn_prepare(const LaPrepItem* items, int count, hipStream_t s, co
   return 0;
 }
 
-namespace {
 // Which kernel runs the forward: k_la_long.hip, k_la_small.hip, k_la_rows_fwd.hip or the register-resident one, each only when its launcher
 // takes every argument
-enum LaFwdForm { LA_FWD_LONG, LA_FWD_SMALL, LA_FWD_ROWS, LA_FWD_REG };
 LaFwdForm la_fwd_form(const LinAttn& a) {
   if (!la_short_row(a.n)) return LA_FWD_LONG;
   if (a.prep && la_small_usable(a.C, a.n) && a.rows >= la_small_min_rows() &&
@@ -755,7 +753,6 @@ LaFwdForm la_fwd_form(const LinAttn& a) {
     return LA_FWD_ROWS;
   return LA_FWD_REG;
 }
-}  // namespace
 
 int launch_linattn_fwd(const LinAttn& a, hipStream_t s) {
   DQ_REQUIRE(a.x && a.y && a.w_qkv && a.w_out && a.b_out && a.g_pre && a.g_out, "linattn_fwd: missing operand");

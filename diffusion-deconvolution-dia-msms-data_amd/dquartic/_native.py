@@ -14,6 +14,8 @@ PRECISIONS = {"fp32": 0, "bf16x3": 1}  # DQ_PRECISION_FP32 / DQ_PRECISION_BF16X3
 FINAL_ACTS = {"identity": 0, "softplus": 1}  # DQ_FINAL_IDENTITY / DQ_FINAL_SOFTPLUS
 RES_FWD_FORMS = ("rt", "level", "v4", "unfused")  # DQ_RES_FWD_* (index = value)
 RES_BWD_FORMS = ("wg", "rt", "rows", "cp", "plain", "unfused")  # DQ_RES_BWD_*
+LA_FWD_FORMS = ("long", "small", "rows", "register")  # DQ_LA_FWD_*
+LA_BWD_FORMS = ("long", "rows", "register")  # DQ_LA_BWD_*
 
 # name -> (restype, argtypes); this table is checked against include/dq_hip.h by tests/test_abi.py
 PROTOTYPES = {
@@ -76,6 +78,8 @@ PROTOTYPES = {
     "dq_tfm_set_precision": (c_int, [c_void_p, c_int]),
     "dq_linattn_fwd": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_void_p]),
     "dq_linattn_bwd": (c_int, [c_void_p] * 15 + [c_int, c_int, c_int, c_void_p]),
+    "dq_linattn_bwd_store": (c_int, [c_void_p] * 15 + [c_int, c_int, c_int, c_void_p]),
+    "dq_linattn_forms": (c_int, [c_int] * 4 + [POINTER(c_int), POINTER(c_int)]),
     "dq_linattn_prep_floats": (c_int64, []),
     "dq_linattn_prepare": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "dq_linattn_fwd_prepared": (c_int, [c_void_p] * 9 + [c_int, c_int, c_int, c_void_p]),
@@ -154,6 +158,14 @@ def resblock_forms(cinA: int, cinB: int, cout: int, rows: int, n: int, rows_per_
     f, b = c_int(-1), c_int(-1)
     check(lib().dq_resblock_forms(cinA, cinB, cout, rows, n, rows_per_sample, ctypes.byref(f), ctypes.byref(b)), "dq_resblock_forms")
     return RES_FWD_FORMS[f.value], RES_BWD_FORMS[b.value]
+
+
+def linattn_forms(C: int, rows: int, n: int, prepared: bool = True):
+    """``dq_linattn_forms``: the (forward, backward) kernel forms of the stand-alone LinearAttention calls for this shape now, as names of
+    LA_FWD_FORMS / LA_BWD_FORMS; the forward is dq_linattn_fwd_prepared's (prepared) or dq_linattn_fwd's."""
+    f, b = c_int(-1), c_int(-1)
+    check(lib().dq_linattn_forms(C, rows, n, int(prepared), ctypes.byref(f), ctypes.byref(b)), "dq_linattn_forms")
+    return LA_FWD_FORMS[f.value], LA_BWD_FORMS[b.value]
 
 
 def check(rc, what):

@@ -45,7 +45,7 @@ const char* dq_last_error(void);
  * dq_rope, dq_attn_*); dq_train_step takes ms1_loss_weight, dq_ms1_loss_fwd_bwd;
  * dq_tfm_set_precision, dq_gemm_bf16x3.  8: dq_tfm_bwd_buckets, dq_tfm_num_buckets, dq_tfm_bucket_info.  9: dq_linattn_prepare,
  * dq_linattn_fwd_prepared.  10: dq_set_option, dq_get_option, dq_debug_side_tail_store (later, additive: dq_plan_set_final_act,
- * dq_plan_final_act, dq_get_option_effective, dq_resblock_forms). */
+ * dq_plan_final_act, dq_get_option_effective, dq_resblock_forms, dq_linattn_forms, dq_linattn_bwd_store). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 10
 
@@ -281,6 +281,19 @@ int dq_linattn_fwd_prepared(const float* x, float* y, float* ypre, const float* 
 int dq_linattn_bwd(const float* x, const float* ypre, const float* dy, float* dx, const float* w_qkv, const float* w_out,
                    const float* b_out, const float* g_pre, const float* g_out, float* dw_qkv, float* dw_out, float* db_out,
                    float* dg_pre, float* dg_out, float* scratch, int C, int rows, int n, void* stream);
+/* The same backward with dx written instead of accumulated (its prior contents are ignored), the way the network runs it; parameter
+ * gradients still +=. */
+int dq_linattn_bwd_store(const float* x, const float* ypre, const float* dy, float* dx, const float* w_qkv, const float* w_out,
+                         const float* b_out, const float* g_pre, const float* g_out, float* dw_qkv, float* dw_out, float* db_out,
+                         float* dg_pre, float* dg_out, float* scratch, int C, int rows, int n, void* stream);
+/* Which kernels the calls above take for this shape under the current options (16-byte aligned caller tensors assumed): *fwd_form =
+ * DQ_LA_FWD_* of dq_linattn_fwd_prepared (prepared != 0; rows of 1 .. 64 positions, powers of two) or of dq_linattn_fwd (prepared == 0),
+ * *bwd_form = DQ_LA_BWD_* of dq_linattn_bwd / dq_linattn_bwd_store.  Forward: k_la_long.hip (LONG), k_la_small.hip (SMALL),
+ * k_la_rows_fwd.hip (ROWS), k_linattn.hip (REG).  Backward: k_la_long.hip between two norm-backward launches (LONG), k_la_rows_bwd.hip
+ * (ROWS), k_la_bwd.hip (REG).  Launches nothing.  Bad shape: non-zero. */
+enum { DQ_LA_FWD_LONG = 0, DQ_LA_FWD_SMALL = 1, DQ_LA_FWD_ROWS = 2, DQ_LA_FWD_REG = 3 };
+enum { DQ_LA_BWD_LONG = 0, DQ_LA_BWD_ROWS = 1, DQ_LA_BWD_REG = 2 };
+int dq_linattn_forms(int C, int rows, int n, int prepared, int* fwd_form, int* bwd_form);
 /* RMSNorm (unet1d.py:113-140): y = x / max(||x||_2 over C, 1e-12) * g * sqrt(C) on (rows, C, n); C in {4, 8, 12, 16, 32}. */
 int dq_rmsnorm_fwd(const float* x, const float* g, float* y, int C, int rows, int n, void* stream);
 /* SinusoidalPosEmb(4) -> Linear(4,16) -> GELU -> Linear(16,16) (unet1d.py:196-218, 956-960): t (B) int64 -> sinu_out (B,4),

@@ -202,8 +202,9 @@ def resnet_block(p: Params, prefix: str, x: torch.Tensor, temb: torch.Tensor, ro
     return h + x
 
 
-def linear_attention(p: Params, prefix: str, x: torch.Tensor) -> torch.Tensor:
-    """Residual(PreNorm(LinearAttention)) (unet1d.py:64-79, 143-176, 466-496).  ``prefix`` is e.g. 'downs.0.2'."""
+def linear_attention(p: Params, prefix: str, x: torch.Tensor, return_pre: bool = False):
+    """Residual(PreNorm(LinearAttention)) (unet1d.py:64-79, 143-176, 466-496).  ``prefix`` is e.g. 'downs.0.2'.
+    ``return_pre``: return (y, y_pre), y_pre being the output of to_out[0] (before its RMSNorm), which the kernels save for the backward."""
     R, C, n = x.shape
     y = rmsnorm(x, p[prefix + ".fn.norm.g"])
     qkv = F.conv1d(y, p[prefix + ".fn.fn.to_qkv.weight"])  # no bias
@@ -212,9 +213,9 @@ def linear_attention(p: Params, prefix: str, x: torch.Tensor) -> torch.Tensor:
     k = k.softmax(dim=-1)
     ctx = torch.einsum("bhdn,bhen->bhde", k, v)
     out = torch.einsum("bhde,bhdn->bhen", ctx, q).reshape(R, HEADS * DIM_HEAD, n)
-    out = F.conv1d(out, p[prefix + ".fn.fn.to_out.0.weight"], p[prefix + ".fn.fn.to_out.0.bias"])
-    out = rmsnorm(out, p[prefix + ".fn.fn.to_out.1.g"])
-    return out + x
+    pre = F.conv1d(out, p[prefix + ".fn.fn.to_out.0.weight"], p[prefix + ".fn.fn.to_out.0.bias"])
+    out = rmsnorm(pre, p[prefix + ".fn.fn.to_out.1.g"])
+    return (out + x, pre) if return_pre else out + x
 
 
 def rope_freqs(dim: int = DIM_HEAD // 2, theta: float = 10000.0) -> torch.Tensor:
