@@ -341,6 +341,16 @@ def unet_forward(
 # --------------------------------------------------------------------------------------
 # diffusion process (model.py:244-406)
 # --------------------------------------------------------------------------------------
+def ms1_term(d: torch.Tensor, ms1: torch.Tensor) -> torch.Tensor:
+    """The additional term of ``Diffusion.train_loss`` with ms1_loss_weight > 0 (semantics: its docstring), per sample.
+    d (B, RT, MZ): x_t - eps_pred ('eps') or x0_pred ('x0'); ms1 (B, RT): the normalised MS1 chromatogram.  Returns (B,)."""
+    tgt = ms1 / ms1.max(dim=-1, keepdim=True).values
+    add = torch.zeros_like(d[:, 0, 0])
+    for sic in (d.sum(dim=-1), d.mean(dim=-1), d.max(dim=-1).values):
+        add = add + ((sic / sic.max(dim=-1, keepdim=True).values - tgt) ** 2).mean(dim=-1)
+    return add
+
+
 @dataclass
 class Diffusion:
     params: Params
@@ -410,12 +420,7 @@ class Diffusion:
         per = ((out - target) ** 2).flatten(1).mean(dim=1)
         if ms1_loss_weight > 0.0:
             d = (x_t - out) if self.pred_type == "eps" else out
-            ms1 = c1 if c1.dim() == 2 else c1[..., 0]
-            tgt = ms1 / ms1.max(dim=-1, keepdim=True).values
-            add = torch.zeros_like(per)
-            for sic in (d.sum(dim=-1), d.mean(dim=-1), d.max(dim=-1).values):
-                add = add + ((sic / sic.max(dim=-1, keepdim=True).values - tgt) ** 2).mean(dim=-1)
-            per = (1 - ms1_loss_weight) * per + ms1_loss_weight * add
+            per = (1 - ms1_loss_weight) * per + ms1_loss_weight * ms1_term(d, c1 if c1.dim() == 2 else c1[..., 0])
         elif self.pred_type == "eps":
             return F.mse_loss(out, noise), out
         return (per * self.loss_weight[t]).mean(), out
@@ -464,6 +469,28 @@ def adamw_step(p, g, m, v, step: int, lr: float, b1=0.9, b2=0.999, eps=1e-8, wd=
     bc2 = 1 - b2 ** step
     denom = (v.sqrt() / math.sqrt(bc2)).add_(eps)
     p.addcdiv_(m, denom, value=-lr / bc1)
+
+
+def adamw_clip_step(p, g, m, v, grad_scale, max_norm, lr, b1, b2, eps, wd, step: int, fp32_scalars: bool = True):
+    """One ``clip_grad_norm_(max_norm)`` + ``torch.optim.AdamW`` step (single-tensor form, model_interface.py:1121-1122) on flat
+    tensors, out of place, in the dtype of ``p`` (float64 for the oracle).  The gradient is first multiplied by ``grad_scale``; the
+    L2 norm is that of the scaled gradient; ``max_norm <= 0`` disables clipping.  Returns (p, m, v, norm).
+    fp32_scalars: the scalar factors enter as the fp32 values the library applies (they are formed in double, then cast:
+    1 - lr*wd, lr / bc1, sqrt(bc2), 1 - b1, b2, 1 - b2, eps and the 1e-6 of the clip coefficient); False keeps them in double,
+    which is torch's own arithmetic (tests/test_oracle_golden.py pins that form to torch.optim.AdamW)."""
+    import numpy as np
+
+    f = (lambda x: float(np.float32(x))) if fp32_scalars else float
+    g = g * float(grad_scale)
+    norm = torch.sqrt((g * g).sum())
+    if max_norm > 0:
+        g = g * torch.clamp(float(max_norm) / (norm + f(1e-6)), max=1.0)
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    m = m + f(1.0 - b1) * (g - m)                      # exp_avg.lerp_(grad, 1 - beta1)
+    v = f(b2) * v + f(1.0 - b2) * g * g                # exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+    denom = v.sqrt() / f(math.sqrt(bc2)) + f(eps)
+    p = p * f(1.0 - lr * wd) - f(lr / bc1) * (m / denom)
+    return p, m, v, norm
 
 
 def trainable_keys(p: Params) -> List[str]:
