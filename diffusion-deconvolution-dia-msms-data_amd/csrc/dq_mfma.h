@@ -1,4 +1,5 @@
-// Wave-level MFMA helpers shared by the LinearAttention kernels (v_mfma_f32_32x32x2_f32, exact fp32).
+// Wave-level MFMA helpers shared by the LinearAttention and bottleneck-attention kernels (v_mfma_f32_32x32x2_f32, exact fp32; and the
+// split-bf16 form on v_mfma_f32_32x32x16_bf16 at the end of the file).
 //   A operand: lane l supplies A[i = l & 31][k = l >> 5] ; B operand: lane l supplies B[k = l >> 5][j = l & 31]
 //   C/D: register r of lane l holds D[row = rmap(r, l >> 5)][col = l & 31]
 // An accumulator X (rows in registers, column on the lane) feeds, register by register, a product that sums over X's
@@ -37,18 +38,25 @@ __device__ __forceinline__ f32x16 xty(const f32x16& x, const f32x16& y, f32x16 a
   return acc;
 }
 
-// 32x32 transpose of an accumulator tile through a wave-private LDS tile [32][33] (conflict-free both ways)
-__device__ __forceinline__ f32x16 transpose_tile(f32x16 a, float* tile, int col, int half) {
+// 32x32 transpose of an accumulator tile through a wave-private LDS tile [32][33] (conflict-free both ways), in two halves: the tile is
+// put down where its registers end their life and taken up, transposed, where the transposed form is first needed
+__device__ __forceinline__ void transpose_put(const f32x16& a, float* tile, int col, int half) {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
   for (int r = 0; r < 16; ++r) tile[rmap(r, half) * 33 + col] = a[r];
+}
+__device__ __forceinline__ f32x16 transpose_get(const float* tile, int col, int half) {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
   f32x16 o;
 #pragma unroll
   for (int r = 0; r < 16; ++r) o[r] = tile[col * 33 + rmap(r, half)];
   return o;
+}
+__device__ __forceinline__ f32x16 transpose_tile(f32x16 a, float* tile, int col, int half) {
+  transpose_put(a, tile, col, half);
+  return transpose_get(tile, col, half);
 }
 
 // keep element (row in registers, column on the lane) only where row / N == col / N  (pairs inside one m/z row)
@@ -61,6 +69,63 @@ __device__ __forceinline__ f32x16 mask_same_row(f32x16 a, int col, int half) {
     a[r] = rr == cr ? a[r] : 0.f;
   }
   return a;
+}
+
+// ---- split-bf16: an fp32 value is EXACTLY the sum of three bf16 values (H = bf16(v), M = bf16(v - H), L = v - H - M: 8 + 8 + 8
+// significant bits), so a product x y is the sum of nine part products, each exact in fp32.  The six at or above 2^-16 of the largest -- HH,
+// HM, MH, MM, HL, LH -- are kept; the three dropped ones (ML, LM, LL) are < 2^-23 of |x||y| together in the worst case: a few fp32
+// roundings.  v_mfma_f32_32x32x16_bf16 (32 cycles for K = 16) accumulates in fp32.
+//   A operand: element j (0..7) of lane l is A[i = l & 31][k = 8 (l >> 5) + j] ; B operand: B[k = 8 (l >> 5) + j][n = l & 31] ; C/D as above
+//   (tools/probe/mfma32x32x16_bf16.hip pins the map and the chaining below with exact integer data).
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) { union { u32x4 u; bf16x8 b; } c; c.u = v; return c.b; }
+__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a), as_bf16x8(b), c, 0, 0, 0); }
+
+// A 32 x 32 tile (rows in the 16 registers of a lane, column on the lane) as the operand of a product that sums over its ROW index: registers
+// 8 s .. 8 s + 7 are the lane's eight K elements of K-step s (s = 0, 1), i.e. K slot (s, half, j) is row rmap(8 s + j, half) -- the same
+// permutation of the 32 rows for every tile in this layout, so two such tiles multiply slot by slot.  Three planes of 2 x 4 dwords.
+struct Split16 { u32x4 h[2], m[2], l[2]; };
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+// The parts are ROUNDED to nearest (v_cvt_pk_bf16_f32, two values per instruction): |M| <= 2^-9 and |L| <= 2^-17 of the value's binade with
+// either sign, so the dropped terms are a quarter of what truncated parts would leave and do not lean one way.  Every subtraction is exact.
+__device__ __forceinline__ Split16 split_tile(const f32x16& x) {
+  Split16 t;
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {  // 9 vector instructions per two values: 3 conversions, 4 unpacks, 2 v_pk_add_f32
+      const f32x2 v = {x[8 * s + 2 * p], x[8 * s + 2 * p + 1]};
+      const bf16x2 h = __builtin_convertvector(v, bf16x2);
+      const f32x2 r = v - __builtin_convertvector(h, f32x2);
+      const bf16x2 m = __builtin_convertvector(r, bf16x2);
+      const bf16x2 l = __builtin_convertvector(r - __builtin_convertvector(m, f32x2), bf16x2);  // exact: <= 8 significant bits are left
+      t.h[s][p] = __builtin_bit_cast(unsigned, h);  // low half = the first value
+      t.m[s][p] = __builtin_bit_cast(unsigned, m);
+      t.l[s][p] = __builtin_bit_cast(unsigned, l);
+    }
+  return t;
+}
+// X^T Y of two split tiles, six terms x two K-steps, the small terms first: twelve dependent 32-cycle MFMAs (sixteen of 64 cycles in xty).
+// MIRROR swaps the roles of x and y in the order of the terms, so that xty6<true>(y, x) adds the same part products in the same order as
+// xty6(x, y) and is its transpose BIT FOR BIT: the backward kernels recompute the forward's scores, and P = exp(S - lse) is only as good as
+// the two evaluations of S agree (one ulp of a score of 2^20 is a factor of e^(1/8) in P).
+template <bool MIRROR = false>
+__device__ __forceinline__ f32x16 xty6(const Split16& x, const Split16& y, f32x16 acc) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) acc = MIRROR ? mfma_bf16(x.h[s], y.l[s], acc) : mfma_bf16(x.l[s], y.h[s], acc);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) acc = MIRROR ? mfma_bf16(x.l[s], y.h[s], acc) : mfma_bf16(x.h[s], y.l[s], acc);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) acc = mfma_bf16(x.m[s], y.m[s], acc);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) acc = MIRROR ? mfma_bf16(x.h[s], y.m[s], acc) : mfma_bf16(x.m[s], y.h[s], acc);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) acc = MIRROR ? mfma_bf16(x.m[s], y.h[s], acc) : mfma_bf16(x.h[s], y.m[s], acc);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) acc = mfma_bf16(x.h[s], y.h[s], acc);
+  return acc;
 }
 
 }  // namespace dq

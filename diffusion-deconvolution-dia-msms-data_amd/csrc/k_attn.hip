@@ -6,14 +6,17 @@
 //
 // q, k, v, o live in conv layout (B, heads*32, RT), RT contiguous.  Flash-style: the RT x RT score matrix never exists in
 // memory.  One WAVE owns a block of 32 queries (forward, dQ) or 32 keys (dK, dV) of one (sample, head) and sweeps the other
-// side in blocks of 32; every product is a 32x32 tile on v_mfma_f32_32x32x2_f32 (exact fp32), with the orientations chosen
+// side in blocks of 32; every product is a 32x32 tile in the six-term split-bf16 form on v_mfma_f32_32x32x16_bf16 (dq_mfma.h: xty6, exact to
+// a few fp32 roundings; twelve 32-cycle MFMAs per product where the fp32 instruction took sixteen of 64), with the orientations chosen
 // so that (a) every operand tile is loaded straight from global memory in one of two register layouts -- "rows = channel,
 // col = position" (16 coalesced row loads) or "rows = position, col = channel" (4 x 16-B loads per lane) -- and (b) each
-// accumulator is directly the next product's operand (sum_r mfma(X.r, Y.r) = X^T Y, dq_mfma.h).  The softmax runs over the
-// 16 registers of a lane + its partner lane^32.  No LDS, no barriers; several waves per SIMD hide the load latency.
-//   forward   (queries on lanes):  S^T = K^T.. xty(Kt, Qt) ; online softmax over rows ; O^T = xty(Vx, P^T)
-//   dQ kernel (queries on lanes):  S^T, dP^T = xty(Vt, dOt), dS^T = P^T o (dP^T - delta) ; dQ = xty(Kx, dS^T)
-//   dK/dV     (keys on lanes):     S = xty(Qt, Kt), dP = xty(dOt, Vt) ; dV = xty(dOx, P) ; dK = xty(Qx, dS)
+// accumulator is directly the next product's operand (registers 8 s .. 8 s + 7 are K-step s of X^T Y, dq_mfma.h).  A tile becomes an
+// operand through split_tile (4.5 vector instructions per value): the wave's own block is split once before the sweep, the swept tiles and the
+// P / dS accumulators inside it.  The softmax runs over the 16 registers of a lane + its partner lane^32.  Forward and dQ: no LDS, no
+// barriers; several waves per SIMD hide the load latency.
+//   forward   (queries on lanes):  S^T = xty6(Kt, Qt) ; online softmax over rows ; O^T = xty6(Vx, P^T)
+//   dQ kernel (queries on lanes):  S^T, dP^T = xty6(Vt, dOt), dS^T = P^T o (dP^T - delta) ; dQ = xty6(Kx, dS^T)
+//   dK/dV     (keys on lanes):     S = xty6<true>(Qt, Kt) (the forward's S^T bit for bit), dP = xty6<true>(dOt, Vt) ; dV = xty6(dOx, P) ; dK = xty6(Qx, dS)
 // 3.4 % of the network FLOPs at 64x400.
 #include "dq_common.h"
 #include "dq_kernels.h"
@@ -128,8 +131,8 @@ __device__ __forceinline__ f32x16 rows_scalar(const float* __restrict__ v, int R
 }
 
 // One wave per block of 32 queries (forward, dQ): it sweeps every key block, a serial chain of RT / 32 steps, with the next block's tiles in
-// flight while the current one multiplies (forward / dQ / dK,dV at batch 32: 48 / 70 / 157 -> 44 / 62 / 130 us; the products themselves --
-// dependent chains of sixteen 64-cycle fp32 MFMAs -- bound the three launches at 18 / 27 / 36 us).  Four waves per query block, each taking
+// flight while the current one multiplies (forward / dQ / dK,dV at batch 32, fp32 products: 48 / 70 / 157 -> 44 / 62 / 130 us; the split-bf16
+// products since: stand-alone forward 48.6 -> 40.1 us, dQ + dK/dV 152.6 -> 135.3 us).  Four waves per query block, each taking
 // every fourth key block with the partials merged in LDS, were measured at batch 32: forward 44 us either way, dQ 62 -> 89 us (its 253
 // registers leave two waves per SIMD either way, and the merge comes on top).  Nor may the split follow the grid size: a window's result
 // must not depend on the batch it is computed in (the merge adds the partial softmaxes in another order, and tests/test_scale_parity.py
@@ -137,7 +140,8 @@ __device__ __forceinline__ f32x16 rows_scalar(const float* __restrict__ v, int R
 // ---- forward: one wave = 32 queries of one (sample, head), online softmax over the key blocks
 // (Round-4 measurements, batch 512: with every key block reading block 0's tiles -- L1-hot -- the launch takes 512 instead of 602 us, so the
 // tile loads are 15 % of it; two accumulation chains per product change nothing forward and spill backward; launch bounds of 4 / 5 waves per
-// SIMD spill 41 / 80 registers: 1,012 / 1,441 us.  The sweep runs at ~3,500 cycles per key block and SIMD against 2,048 cycles of MFMA.)
+// SIMD spill 41 / 80 registers: 1,012 / 1,441 us.  The sweep ran at ~3,500 cycles per key block and SIMD against 2,048 cycles of fp32 MFMA;
+// the split-bf16 products are 768 cycles of MFMA and ~220 vector instructions of splitting per key block.)
 __global__ void __launch_bounds__(64) k_attn_fwd(const float* __restrict__ q, int64_t q_bs, const float* __restrict__ k, int64_t k_bs,
                                                  const float* __restrict__ v, int64_t v_bs, float* __restrict__ o,
                                                  float* __restrict__ lse, int RT) {
@@ -147,7 +151,7 @@ __global__ void __launch_bounds__(64) k_attn_fwd(const float* __restrict__ q, in
   const float* qb = q + b * q_bs + (int64_t)h * 32 * RT;
   const float* kb = k + b * k_bs + (int64_t)h * 32 * RT;
   const float* vb = v + b * v_bs + (int64_t)h * 32 * RT;
-  const f32x16 Qt = tile_ch_rows<false>(qb, RT, i0, col, half, ATT_SCALE);  // rows d, col i
+  const Split16 Qs = split_tile(tile_ch_rows<false>(qb, RT, i0, col, half, ATT_SCALE));  // rows d, col i
   f32x16 Oa = {0};                                                   // rows e, col i
   float m = -INFINITY, l = 0.f;
   // the key block a prefetch reads (past the end: the last block again, not used).  The first prefetch goes through the same clamp: with
@@ -160,7 +164,7 @@ __global__ void __launch_bounds__(64) k_attn_fwd(const float* __restrict__ q, in
     const f32x16 Kt = Kn, Vx = Vn;
     Kn = tile_ch_rows<false>(kb, RT, kblk(j0 + 32), col, half, 1.f);
     Vn = tile_pos_rows(vb, RT, kblk(j0 + 32), col, half, 1.f);
-    f32x16 St = xty(Kt, Qt, f32x16{0});                           // rows j, col i
+    f32x16 St = xty6(split_tile(Kt), Qs, f32x16{0});              // rows j, col i
     float mx = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -181,7 +185,7 @@ __global__ void __launch_bounds__(64) k_attn_fwd(const float* __restrict__ q, in
     m = mn;
 #pragma unroll
     for (int r = 0; r < 16; ++r) Oa[r] *= al;
-    Oa = xty(Vx, St, Oa);  // rows e, col i
+    Oa = xty6(split_tile(Vx), split_tile(St), Oa);  // rows e, col i
   }
   if (i < RT) {
     const float rl = 1.0f / l;
@@ -219,8 +223,9 @@ __global__ void __launch_bounds__(64) k_attn_bwd_q(const float* __restrict__ q, 
   f32x16 Kn = tile_ch_rows(kb, RT, kblk(0), col, half, 1.f);   // rows d, col j
   f32x16 Vn = tile_ch_rows(vb, RT, kblk(0), col, half, 1.f);   // rows e, col j
   f32x16 Xn = tile_pos_rows(kb, RT, kblk(0), col, half, 1.f);  // rows j, col d
-  const f32x16 Qt = tile_ch_rows(qb, RT, i0, col, half, ATT_SCALE);  // rows d, col i
-  const f32x16 dOt = tile_ch_rows(dob, RT, i0, col, half, 1.f);      // rows e, col i
+  const Split16 Qs = split_tile(tile_ch_rows(qb, RT, i0, col, half, ATT_SCALE));  // rows d, col i
+  const f32x16 dOt = tile_ch_rows(dob, RT, i0, col, half, 1.f);                    // rows e, col i
+  const Split16 dOs = split_tile(dOt);
   float dl = 0.f;
   {
     const f32x16 Ot = tile_ch_rows(ob, RT, i0, col, half, 1.f);
@@ -235,14 +240,14 @@ __global__ void __launch_bounds__(64) k_attn_bwd_q(const float* __restrict__ q, 
     Kn = tile_ch_rows(kb, RT, kblk(j0 + 32), col, half, 1.f);
     Vn = tile_ch_rows(vb, RT, kblk(j0 + 32), col, half, 1.f);
     Xn = tile_pos_rows(kb, RT, kblk(j0 + 32), col, half, 1.f);
-    f32x16 St = xty(Kt, Qt, f32x16{0});                           // rows j, col i
-    const f32x16 dPt = xty(Vt, dOt, f32x16{0});                   // rows j, col i
+    f32x16 St = xty6(split_tile(Kt), Qs, f32x16{0});              // rows j, col i
+    const f32x16 dPt = xty6(split_tile(Vt), dOs, f32x16{0});      // rows j, col i
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float p = (j0 + rmap(r, half) < RT) ? __builtin_amdgcn_exp2f((St[r] - ls) * LOG2E) : 0.f;
       St[r] = p * (dPt[r] - dl);  // dS^T
     }
-    dQa = xty(Kx, St, dQa);
+    dQa = xty6(split_tile(Kx), split_tile(St), dQa);
   }
   if (i < RT) {
     float* dqb = dq + b * dq_bs + (int64_t)h * 32 * RT;
@@ -272,37 +277,42 @@ __global__ void __launch_bounds__(256, 2) k_attn_bwd_kv(const float* __restrict_
   const float* dlb = delta + (int64_t)bh * RT;
   const int ilast = (RT - 1) / 32 * 32;
   f32x16 Qn = tile_ch_rows(qb, RT, min(wv * 32, ilast), col, half, ATT_SCALE), dOn = tile_ch_rows(dob, RT, min(wv * 32, ilast), col, half, 1.f);
-  const f32x16 Kt = tile_ch_rows(kb, RT, j0, col, half, 1.f);  // rows d, col j
-  const f32x16 Vt = tile_ch_rows(vb, RT, j0, col, half, 1.f);  // rows e, col j
+  const Split16 Ks = split_tile(tile_ch_rows(kb, RT, j0, col, half, 1.f));  // rows d, col j
+  const Split16 Vs = split_tile(tile_ch_rows(vb, RT, j0, col, half, 1.f));  // rows e, col j
   f32x16 dKa = {0}, dVa = {0};                                 // rows d / e, col j
   // The (rows i, col d) orientations of Q and dO come from the (rows d, col i) tiles through a wave-private LDS transpose.
-  __shared__ float ttiles[4][32 * 33];
+  __shared__ float ttiles[4][2][32 * 33];
   __shared__ float acc_lds[3][2][16][64];  // partial (dK, dV) of waves 1..3
-  float* ttile = ttiles[wv];
+  float* tq = ttiles[wv][0];
+  float* tdo = ttiles[wv][1];
   for (int i0 = wv * 32; i0 < RT; i0 += 128) {
-    const f32x16 Qt = Qn, dOt = dOn;  // rows d / e, col i
     // (the per-query scalars are requested here and first used behind the two score products: registers for their prefetch are not there)
     const f32x16 lsr = rows_scalar(lsb, RT, i0, half, INFINITY);  // exp(s - inf) = 0 masks the tail
     const f32x16 dlr = rows_scalar(dlb, RT, i0, half, 0.f);
-    Qn = tile_ch_rows(qb, RT, min(i0 + 128, ilast), col, half, ATT_SCALE);
-    dOn = tile_ch_rows(dob, RT, min(i0 + 128, ilast), col, half, 1.f);
-    // The P side first (S, P, dV), then the dS side (dP, dS, dK): each transposed tile is formed right in front of its product, so that
-    // Q / Q^T and dO / dO^T are not all live at once (the kernel held 6 registers more than its 256 and spilled them).
-    f32x16 S = xty(Qt, Kt, f32x16{0});              // rows i, col j
-#pragma unroll
-    for (int r = 0; r < 16; ++r) S[r] = __builtin_amdgcn_exp2f((S[r] - lsr[r]) * LOG2E);  // P
+    // Both score products first: a fp32 tile is put down in LDS for its transpose and split for its product, and its registers are free
+    // from there on (with Q / Q^T, dO / dO^T and their bf16 planes live side by side the kernel does not fit its 256 registers).
+    f32x16 S, dP;
     {
-      const f32x16 dOx = transpose_tile(dOt, ttile, col, half);  // rows i, col e
-      dVa = xty(dOx, S, dVa);
+      const f32x16 Qt = Qn;  // rows d, col i
+      Qn = tile_ch_rows(qb, RT, min(i0 + 128, ilast), col, half, ATT_SCALE);
+      transpose_put(Qt, tq, col, half);
+      S = xty6<true>(split_tile(Qt), Ks, f32x16{0});  // rows i, col j: the transpose of the forward's S^T bit for bit
+    }
+    {
+      const f32x16 dOt = dOn;  // rows e, col i
+      dOn = tile_ch_rows(dob, RT, min(i0 + 128, ilast), col, half, 1.f);
+      transpose_put(dOt, tdo, col, half);
+      dP = xty6<true>(split_tile(dOt), Vs, f32x16{0});  // rows i, col j
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      S[r] = __builtin_amdgcn_exp2f((S[r] - lsr[r]) * LOG2E);  // P
+      dP[r] = S[r] * (dP[r] - dlr[r]);                         // dS
     }
     __builtin_amdgcn_sched_barrier(0);
-    f32x16 dP = xty(dOt, Vt, f32x16{0});            // rows i, col j
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dP[r] = S[r] * (dP[r] - dlr[r]);  // dS
-    {
-      const f32x16 Qx = transpose_tile(Qt, ttile, col, half);    // rows i, col d
-      dKa = xty(Qx, dP, dKa);
-    }
+    dVa = xty6(split_tile(transpose_get(tdo, col, half)), split_tile(S), dVa);   // dO as rows i, col e
+    __builtin_amdgcn_sched_barrier(0);
+    dKa = xty6(split_tile(transpose_get(tq, col, half)), split_tile(dP), dKa);   // Q as rows i, col d
   }
   if (wv > 0) {
 #pragma unroll

@@ -48,10 +48,8 @@ __device__ __forceinline__ void wave_fence() {
 // case and ~2^-23 typically: a few fp32 roundings (every forward fixture and trajectory tolerance holds unchanged, tests/test_hip_forward.py).  A K = 4 projection is two 32-cycle bf16 MFMAs instead of two 64-cycle fp32 ones, a K = 8 projection three instead of four.
 // Slot order inside a lane half: channel j of the half (la_chan) owns slots 6j .. 6j+5 = dwords 3j .. 3j+2:
 //   x parts (H, H | M, M | H, L)   weight parts (H, M | H, M | L, H)
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+// (bf16x8, u32x4, as_bf16x8: dq_mfma.h)
 __host__ __device__ __forceinline__ constexpr int la_nu(int C) { return (3 * (C / 2) + 3) / 4; }  // bf16 MFMAs per projection
-__device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) { union { u32x4 u; bf16x8 b; } c; c.u = v; return c.b; }
 // the three packed dwords of one x value
 __device__ __forceinline__ void la_split_x(float v, unsigned& d0, unsigned& d1, unsigned& d2) {
   const unsigned vb = __float_as_uint(v);
