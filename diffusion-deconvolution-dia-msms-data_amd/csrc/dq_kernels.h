@@ -107,6 +107,8 @@ struct ConvWgrad {
   float* scratch = nullptr; int64_t scratch_floats = 0;  // >= WGRAD_MAX_PARTS * (cout*cin*K + cout) floats
 };
 constexpr int WGRAD_MAX_PARTS = 512;
+// the ordered sum of nblk slots [dW (nelem_w) | dbias (cout)] into dw / dbias (+=): k_wgrad_reduce on its own
+int launch_wgrad_reduce(const float* part, int nblk, int nelem_w, int cout, float* dw, float* dbias, hipStream_t s);
 int launch_conv_wgrad(const ConvWgrad& a, hipStream_t s);
 // up to three stride-1 convs over the same (rows, n) in one launch + one merged reduce (each with its own scratch region)
 int launch_conv_wgrad_multi(const ConvWgrad* w, int count, hipStream_t s);
@@ -349,6 +351,29 @@ int launch_fold(const float* in, float* out, int B, int RT, int cn, int to_mid, 
 int launch_prep_inputs(const float* x, const float* cond, const float* ms1, const float* ss, int ss_stride, int ss_off, float cm,
                        float ca, float* cat0, float* ms1n, int B, int RT, int MZ, hipStream_t s);
 int launch_ms1_norm(const float* ms1, float cm, float ca, float* ms1n, int64_t n, hipStream_t s);  // ms1n = ms1 * cm + ca
+// ---- k_ms1_feat.hip: attn_cond_proj.1.0 (k7 'same', M1 -> 8 channels) + GELU on a multi-channel MS1 (B, RT, M1), M1 contiguous (M1 > 1)
+constexpr int MS1_MAX_CHANNELS = 4096;
+constexpr int MS1_FWD_TP = 8, MS1_FWD_WAVES = 4;      // positions per wave / waves per workgroup of the forward
+constexpr int MS1_WG_T = 64, MS1_WG_MAX_PARTS = 256;  // positions per unit / most slots of the weight gradient
+struct Ms1FeatFwd {
+  const float* ms1 = nullptr;                          // (B, RT, M1), raw: normalised on the fly as v * cm + ca
+  const float* w = nullptr; const float* bias = nullptr;  // (8, M1, 7), (8)
+  float cm = 1.f, ca = 0.f;
+  float* ms1n_out = nullptr;  // nullable: the normalised MS1 (B, RT, M1) the weight gradient reads (training)
+  float* u_out = nullptr;     // nullable: pre-activation (B, 8, RT)
+  float* a_out = nullptr;     // GELU(u) (B, 8, RT)
+  int B = 0, RT = 0, M1 = 0;
+};
+int launch_ms1_feat_fwd(const Ms1FeatFwd& a, hipStream_t s);
+struct Ms1FeatWgrad {
+  const float* ms1n = nullptr; const float* du = nullptr;  // (B, RT, M1) normalised, (B, 8, RT)
+  float* dw = nullptr; float* dbias = nullptr;             // += (8, M1, 7), (8)
+  float* part = nullptr; int64_t part_floats = 0;          // >= ms1_feat_wgrad_part_floats(B, RT, M1)
+  int B = 0, RT = 0, M1 = 0;
+};
+int ms1_feat_wgrad_parts(int B, int RT, int M1);  // slots (= workgroups) of the launch
+int64_t ms1_feat_wgrad_part_floats(int B, int RT, int M1);
+int launch_ms1_feat_wgrad(const Ms1FeatWgrad& a, hipStream_t s);
 // d(scale), d(shift) of init_cond_proj from dcat0 channel 0 (+= into dss; part: >= 64 * B floats of per-block partials)
 int launch_prep_inputs_bwd(const float* dcat0, const float* cond, float cm, float ca, float* dss, int ss_stride, int ss_off, int B,
                            int RT, int MZ, float* part, int64_t part_floats, hipStream_t s);

@@ -1,5 +1,5 @@
 // Parameter layout + op list for UNet1d(simple=True, conditional=True, channels=1, init_cond_channels=1,
-// attn_cond_channels=1).  Order and names follow the reference module registration order
+// attn_cond_channels=1..4096).  Order and names follow the reference module registration order
 // (dquartic/model/unet1d.py:949-1082): init_conv, time_mlp, init_cond_proj, attn_cond_proj, downs, ups,
 // mid_block1, mid_attn, mid_block2, final_res_block, final_conv.  The non-trainable RoPE frequencies
 // (mid_attn.fn.fn.rotary_emb.freqs) are NOT part of the flat buffer.
@@ -67,14 +67,15 @@ struct Builder {
 
 }  // namespace
 
-std::string build_plan(Plan& p, int dim, int n_mults, const int* mults, int mz, int T) {
+std::string build_plan(Plan& p, int dim, int n_mults, const int* mults, int mz, int T, int attn_cond_channels) {
   if (dim < 4 || dim % 4) return "dim must be a positive multiple of 4";
   if (n_mults < 1 || n_mults > 10) return "dim_mults must have 1..10 entries";
   const int L = n_mults;
   if (mz <= 0 || mz % (1 << (L - 1))) return "MZ (downsample_dim) must be divisible by 2**(len(dim_mults)-1)";
   if (T < 1) return "num_timesteps must be >= 1";
+  if (attn_cond_channels < 1 || attn_cond_channels > 4096) return "attn_cond_channels must lie in 1..4096, got " + std::to_string(attn_cond_channels);
   p = Plan();
-  p.dim = dim; p.levels = L; p.mz = mz; p.time_dim = 4 * dim; p.T = T;
+  p.dim = dim; p.levels = L; p.mz = mz; p.time_dim = 4 * dim; p.T = T; p.ms1_channels = attn_cond_channels;
   p.dims.push_back(dim);
   for (int i = 0; i < L; ++i) {
     if (mults[i] < 1) return "dim_mults entries must be >= 1";
@@ -106,7 +107,7 @@ std::string build_plan(Plan& p, int dim, int n_mults, const int* mults, int mz, 
   p.ss_init = p.ss_total;
   p.ss_lins.push_back({p.icp_w, p.icp_b, 2, p.ss_init});
   p.ss_total += 2;
-  p.ms1_c0 = b.conv("attn_cond_proj.1.0", p.cond_dim, 1, 7);
+  p.ms1_c0 = b.conv("attn_cond_proj.1.0", p.cond_dim, p.ms1_channels, 7);
   p.ms1_c1 = b.conv("attn_cond_proj.1.2", p.cond_dim, p.cond_dim, 1);
 
   int n = mz;

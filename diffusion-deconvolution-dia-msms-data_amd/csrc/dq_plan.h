@@ -54,6 +54,7 @@ struct Plan {
   int mid_c = 0;          // mid_dim * downsampled_n
   bool wide_mid = false;  // mid_c not in {16, 32, 64}: the bottleneck runs on im2col + GEMM + channel-axis norm (k_wide.hip)
   int cond_dim = 0;       // attn_cond_init_dim = 2*dim (unet1d.py:970)
+  int ms1_channels = 1;   // attn_cond_channels: the MS1 conditioning is (B, RT, ms1_channels) (unet1d.py:976, 1122-1130)
   int ss_total = 0;       // floats per sample in the ss vector (all ResnetBlock mlps + init_cond_proj)
   int ss_init = 0;        // offset of init_cond_proj's [scale, shift]
   int final_act = 0;      // output activation behind final_conv (DQ_FINAL_IDENTITY | DQ_FINAL_SOFTPLUS; dq_plan_set_final_act)
@@ -64,7 +65,7 @@ struct Plan {
   ConvP init_conv;                  // (dim, 2, 7)
   int64_t t1_w, t1_b, t2_w, t2_b;   // time_mlp.1 / .3
   int64_t icp_w, icp_b;             // init_cond_proj.to_scale_shift.1  (2, time_dim)
-  ConvP ms1_c0, ms1_c1;             // attn_cond_proj.1.0 (k7) / .1.2 (k1)
+  ConvP ms1_c0, ms1_c1;             // attn_cond_proj.1.0 (8, ms1_channels, 7) / .1.2 (k1)
   std::vector<LevelP> downs, ups;
   ResP mid1, mid2;
   int64_t qv_w, k_w, ao_w, ao_b, ag;  // mid_attn: to_qv (256,mid_c), to_k (128,cond_dim), to_out (mid_c,128)+b, norm.g
@@ -77,7 +78,7 @@ struct Plan {
 };
 
 // Builds the plan; returns empty string on success, else an error message.
-std::string build_plan(Plan& p, int dim, int n_mults, const int* mults, int mz, int T);
+std::string build_plan(Plan& p, int dim, int n_mults, const int* mults, int mz, int T, int attn_cond_channels = 1);
 
 void build_resblock_plan(Plan& p, ResP& r, int cin, int cout);  // one ResnetBlock as its own flat parameter buffer
 

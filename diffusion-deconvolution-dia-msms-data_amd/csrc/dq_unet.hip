@@ -86,7 +86,10 @@ void layout_arena(const Plan& p, int B, int RT, Arena& a) {
   a.tbuf = take((int64_t)B * TBUF_FLOATS);
   a.ss = take((int64_t)B * p.ss_total);
   a.cat0 = take(R * 2 * p.mz);
-  a.ms1n = take(R);
+  const int M1 = p.ms1_channels;
+  // (M1 > 1: the normalised (B, RT, M1) conditioning a training forward keeps for the weight gradient -- no gradient with respect to MS1 is
+  // formed, so it stays out of the region whose twin is cleared every backward; M1 = 1 keeps its place)
+  a.ms1n = M1 > 1 ? take_nz(R * M1) : take(R);
   a.ms1_u = take(R * p.cond_dim); a.ms1_a = take(R * p.cond_dim); a.ms1f = take(R * p.cond_dim);
   a.h0 = take_nz(R * p.dim * p.mz);
   for (int lv = 0; lv < p.levels; ++lv) {
@@ -169,7 +172,8 @@ void layout_arena(const Plan& p, int B, int RT, Arena& a) {
   a.ms1_scratch = take_nz(5 * R + B + 64);  // the MS1 loss term (ms1_loss_weight > 0): per-row sums / maxima and their gradients
   a.wtmp = take_nz(3 * WTMP_SLOT);  // 16-byte aligned copy of a projection weight for the GEMM route of the wide 1x1 convs
   a.ts_tab = take_nz(1024); a.step = take_nz(64);  // graph replay: timestep table (int32) and the device-side step counter
-  a.c2_stage = take_nz(R * p.mz); a.c1_stage = take_nz(R);  // conditions staged at fixed addresses for the captured step
+  a.c2_stage = take_nz(R * p.mz); a.c1_stage = take_nz(R * M1);  // conditions staged at fixed addresses for the captured step
+  if (M1 > 1 && B > 0) { a.ms1_wpart_floats = ms1_feat_wgrad_part_floats(B, RT, M1); a.ms1_wpart = take_nz(a.ms1_wpart_floats); }
   a.zero_floats = off;
   a.floats = off_nz;
   zero_total = off;
@@ -915,6 +919,7 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
   };
   const bool init_fused = down_call(0).pre == LEVEL_PRE_INIT && level_ok(c, down_call(0));
   const bool skip_ms1 = c.step_io && c.step_io->skip_ms1;
+  const int M1 = p.ms1_channels;
   // up path (unet1d.py:1150-1158): first pop = post-attention skip, second pop = post-block1 skip
   auto up_call = [&](int ui) {  // ui == L: the final ResnetBlock behind the last level's k3 conv (unet1d.py:1160-1163)
     LevelCall lc;
@@ -1026,21 +1031,28 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
   if (c.qsample && !(init_fused && c.save))  // (the INIT stage of a train step forms x_t itself)
     DQ_TRY(launch_q_sample(c.qsample->alpha_bars, c.qsample->x0, c.qsample->t, c.qsample->noise, const_cast<float*>(x), B, c.qsample->per, c.qsample->normalize, c.s));
   if (init_fused) {
-    if (!skip_ms1) DQ_TRY(launch_ms1_norm(attn_cond, cm, ca, c.w(a.ms1n), (int64_t)B * RT, ps));  // (ps: the side stream of a forked train step, with the MS1 path)
+    if (!skip_ms1 && M1 == 1) DQ_TRY(launch_ms1_norm(attn_cond, cm, ca, c.w(a.ms1n), (int64_t)B * RT, ps));  // (ps: the side stream of a forked train step, with the MS1 path)
   } else {
     // (forked: the MS1 normalisation goes with the MS1 path to the side stream)
-    DQ_TRY(launch_prep_inputs(x, init_cond, attn_cond, c.w(a.ss), p.ss_total, p.ss_init, cm, ca, c.w(a.cat0), fwd_fork ? nullptr : c.w(a.ms1n), B, RT, p.mz, c.s));
+    DQ_TRY(launch_prep_inputs(x, init_cond, attn_cond, c.w(a.ss), p.ss_total, p.ss_init, cm, ca, c.w(a.cat0), (fwd_fork || M1 > 1) ? nullptr : c.w(a.ms1n), B, RT, p.mz, c.s));
     DQ_TRY(conv_plain_fwd(c, p.init_conv, CONV_S1, c.w(a.cat0), c.w(a.h0), R, p.mz, p.mz));
   }
   // K3: MS1 features (unet1d.py:1120-1130): (B,1,RT) -> conv k7 -> GELU -> conv k1
   if (!skip_ms1) {
     Ctx cs = c;
     cs.s = ps;
+    if (M1 > 1) {  // (B, RT, M1) read as it is: k_ms1_feat.hip
+      Ms1FeatFwd f;
+      f.ms1 = attn_cond; f.w = c.prm(p.ms1_c0.w); f.bias = c.prm(p.ms1_c0.b); f.cm = cm; f.ca = ca; f.B = B; f.RT = RT; f.M1 = M1;
+      f.ms1n_out = c.save ? c.w(a.ms1n) : nullptr; f.u_out = c.save ? c.w(a.ms1_u) : nullptr; f.a_out = c.w(a.ms1_a);
+      DQ_TRY(launch_ms1_feat_fwd(f, ps));
+    } else {
     if (fwd_fork && !init_fused) DQ_TRY(launch_ms1_norm(attn_cond, cm, ca, c.w(a.ms1n), (int64_t)B * RT, ps));
     ConvFwd f;
     f.inA = c.w(a.ms1n); f.cinA = 1; f.w = c.prm(p.ms1_c0.w); f.bias = c.prm(p.ms1_c0.b); f.cout = p.cond_dim; f.K = 7;
     f.rows = B; f.n_in = RT; f.n_out = RT; f.u_out = c.save ? c.w(a.ms1_u) : nullptr; f.y_out = c.w(a.ms1_a); f.act = ACT_GELU;
     DQ_TRY(launch_conv_fwd(f, ps));
+    }
     DQ_TRY(conv_plain_fwd(cs, p.ms1_c1, CONV_S1, c.w(a.ms1_a), c.w(a.ms1f), B, RT, RT));
   }
   if (fwd_fork) {
@@ -1380,6 +1392,12 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
     gb.u = cc.w(a.ms1_u); gb.dy = cc.g(a.ms1_a); gb.du = cc.g(a.ms1_u); gb.C = p.cond_dim; gb.rows = B; gb.n = RT; gb.rows_per_sample = 1;
     gb.act = ACT_GELU;
     DQ_TRY(launch_block_bwd(gb, cc.s));
+    if (p.ms1_channels > 1) {  // weight / bias gradient from the (B, RT, M1) conditioning the forward kept (no gradient with respect to MS1)
+      Ms1FeatWgrad w;
+      w.ms1n = cc.w(a.ms1n); w.du = cc.g(a.ms1_u); w.dw = cc.dprm(p.ms1_c0.w); w.dbias = cc.dprm(p.ms1_c0.b);
+      w.part = cc.w(a.ms1_wpart); w.part_floats = a.ms1_wpart_floats; w.B = B; w.RT = RT; w.M1 = p.ms1_channels;
+      return launch_ms1_feat_wgrad(w, cc.s);
+    }
     return conv_plain_bwd(cc, p.ms1_c0, CONV_S1, cc.w(a.ms1n), cc.g(a.ms1_u), nullptr, B, RT, RT, 0);
   };
   if (c.owner && c.side_defer && tail_fork_enabled()) {
@@ -1624,9 +1642,9 @@ extern "C" {
 const char* dq_last_error(void) { return g_err.c_str(); }
 int dq_abi_version(void) { return DQ_ABI_VERSION; }
 
-dq_plan* dq_plan_create(int dim, int n_mults, const int* dim_mults, int mz, int num_timesteps) {
+dq_plan* dq_plan_create_ex(int dim, int n_mults, const int* dim_mults, int mz, int num_timesteps, int attn_cond_channels) {
   dq_plan* h = new dq_plan();
-  std::string err = build_plan(h->plan, dim, n_mults, dim_mults, mz, num_timesteps);
+  std::string err = build_plan(h->plan, dim, n_mults, dim_mults, mz, num_timesteps, attn_cond_channels);
   if (!err.empty()) {
     set_error("dq_plan_create: " + err);
     delete h;
@@ -1634,6 +1652,10 @@ dq_plan* dq_plan_create(int dim, int n_mults, const int* dim_mults, int mz, int 
   }
   return h;
 }
+dq_plan* dq_plan_create(int dim, int n_mults, const int* dim_mults, int mz, int num_timesteps) {
+  return dq_plan_create_ex(dim, n_mults, dim_mults, mz, num_timesteps, 1);
+}
+int dq_plan_attn_cond_channels(const dq_plan* plan) { return plan ? plan->plan.ms1_channels : -1; }
 
 void dq_plan_destroy(dq_plan* plan) {
   if (!plan) return;
@@ -1734,6 +1756,7 @@ int dq_ms1_loss_fwd_bwd(const float* pred, const float* x_t, const float* ms1_co
                         float* scratch, int B, int RT, int MZ, void* stream) {
   DQ_REQUIRE(pred && ms1_cond && loss_inout && scratch, "dq_ms1_loss_fwd_bwd: null argument");
   DQ_REQUIRE(ms1_loss_weight > 0.f && ms1_loss_weight <= 1.f, "dq_ms1_loss_fwd_bwd: ms1_loss_weight must lie in (0, 1]");
+  // (this entry has no plan: ms1_cond is the (B, RT) chromatogram the term is defined on; a multi-channel MS1 has no such term yet)
   return launch_ms1_loss(pred, x_t, ms1_cond, cond_mul, cond_add, loss_weight_dev, t, ms1_loss_weight, B, RT, MZ, grad_inout, loss_inout,
                          scratch, (hipStream_t)stream);
 }
@@ -1805,6 +1828,8 @@ int dq_train_step(dq_plan* plan, const float* params, const float* rope_freqs, c
   DQ_REQUIRE(pred_type == DQ_PRED_EPS || loss_weight_dev, "dq_train_step: pred_type x0 needs the loss-weight (SNR) table");
   DQ_REQUIRE(B > 0 && RT > 0, "dq_train_step: B and RT must be positive");
   DQ_REQUIRE(ms1_loss_weight >= 0.f && ms1_loss_weight <= 1.f, "dq_train_step: ms1_loss_weight must lie in [0, 1]");
+  DQ_REQUIRE(ms1_loss_weight == 0.f || plan->plan.ms1_channels == 1,
+             "dq_train_step: ms1_loss_weight > 0 with attn_cond_channels > 1 is not built (the MS1 term is defined on a chromatogram)");
   plan->twin_zeroed = nullptr;  // (a step that failed between its forked forward and its backward must not leave "already cleared" behind)
   DQ_TRY(ensure_arena(plan, B, RT));
   const Arena& a = plan->arena;
@@ -1903,11 +1928,18 @@ int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, 
       DQ_TRY(unet_forward(cp, rope_freqs, nullptr, nullptr, 0, nullptr, nullptr, cm, ca, plan->dev, nullptr));
       io.prepared = true;
     }
+    if (p.ms1_channels > 1) {
+      Ms1FeatFwd f;
+      f.ms1 = ms1; f.w = cx.prm(p.ms1_c0.w); f.bias = cx.prm(p.ms1_c0.b); f.cm = cm; f.ca = ca; f.B = B; f.RT = RT; f.M1 = p.ms1_channels;
+      f.a_out = cx.w(a.ms1_a);
+      DQ_TRY(launch_ms1_feat_fwd(f, cx.s));
+    } else {
     DQ_TRY(launch_ms1_norm(ms1, cm, ca, cx.w(a.ms1n), (int64_t)B * RT, cx.s));
     ConvFwd f;
     f.inA = cx.w(a.ms1n); f.cinA = 1; f.w = cx.prm(p.ms1_c0.w); f.bias = cx.prm(p.ms1_c0.b); f.cout = p.cond_dim; f.K = 7;
     f.rows = B; f.n_in = RT; f.n_out = RT; f.y_out = cx.w(a.ms1_a); f.act = ACT_GELU;
     DQ_TRY(launch_conv_fwd(f, cx.s));
+    }
     DQ_TRY(conv_plain_fwd(cx, p.ms1_c1, CONV_S1, cx.w(a.ms1_a), cx.w(a.ms1f), B, RT, RT));
     DQ_TRY(conv_plain_fwd(cx, proj(p.k_w, HID, p.cond_dim), CONV_S1, cx.w(a.ms1f), cx.w(a.kk), B, RT, RT, prep_ok ? 1 : -1));
     if (rope_freqs) DQ_TRY(launch_rope(cx.w(a.kk), rope_freqs, B, (int64_t)HID * RT, RT, 1.f, cx.s));
@@ -1922,7 +1954,7 @@ int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, 
     DQ_HIP_OK(hipMemcpyAsync(ts_tab, ts, sizeof(int32_t) * num_steps, hipMemcpyHostToDevice, s));
     DQ_HIP_OK(hipMemsetAsync(step, 0, sizeof(int), s));
     DQ_HIP_OK(hipMemcpyAsync(c.w(a.c2_stage), ms2_cond, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c1_stage), ms1_cond, sizeof(float) * (int64_t)B * RT, hipMemcpyDeviceToDevice, s));
+    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c1_stage), ms1_cond, sizeof(float) * (int64_t)B * RT * plan->plan.ms1_channels, hipMemcpyDeviceToDevice, s));
     DQ_HIP_OK(hipStreamSynchronize(s));  // ts is caller memory; also keeps the capture below free of pending copies
     DQ_TRY(ms1_prologue(c, c.w(a.c1_stage)));
     io.x_t = xa; io.x_out = xa; io.step_ptr = step; io.want_eps = false;  // in place: element-wise, read and written by the same lane
@@ -2106,6 +2138,24 @@ int dq_time_mlp_fwd(const float* w1, const float* b1, const float* w2, const flo
 int dq_scale_shift_fwd(const float* temb, const float* w, const float* b, float* ss, int B, int m, void* stream) {
   DQ_REQUIRE(temb && w && b && ss, "dq_scale_shift_fwd: null argument");
   return launch_ss_heads(temb, w, b, ss, B, m, (hipStream_t)stream);
+}
+
+int dq_ms1_feat_fwd(const float* ms1, const float* w, const float* bias, float cond_mul, float cond_add, float* ms1n_out, float* u_out,
+                    float* a_out, int B, int RT, int M1, void* stream) {
+  Ms1FeatFwd f;
+  f.ms1 = ms1; f.w = w; f.bias = bias; f.cm = cond_mul; f.ca = cond_add; f.ms1n_out = ms1n_out; f.u_out = u_out; f.a_out = a_out;
+  f.B = B; f.RT = RT; f.M1 = M1;
+  return launch_ms1_feat_fwd(f, (hipStream_t)stream);
+}
+int64_t dq_ms1_feat_wgrad_scratch_floats(int B, int RT, int M1) {
+  if (B <= 0 || RT <= 0 || M1 < 1 || M1 > MS1_MAX_CHANNELS) return -1;
+  return ms1_feat_wgrad_part_floats(B, RT, M1);
+}
+int dq_ms1_feat_wgrad(const float* ms1n, const float* du, float* dw, float* dbias, float* scratch, int64_t scratch_floats, int B, int RT,
+                      int M1, void* stream) {
+  Ms1FeatWgrad g;
+  g.ms1n = ms1n; g.du = du; g.dw = dw; g.dbias = dbias; g.part = scratch; g.part_floats = scratch_floats; g.B = B; g.RT = RT; g.M1 = M1;
+  return launch_ms1_feat_wgrad(g, (hipStream_t)stream);
 }
 
 int dq_prep_inputs_fwd(const float* x, const float* cond, const float* ms1, const float* ss, float cond_mul, float cond_add, float* cat0,

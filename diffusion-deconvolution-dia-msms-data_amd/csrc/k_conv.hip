@@ -960,6 +960,12 @@ int launch_conv_wgrad_multi(const ConvWgrad* w, int count, hipStream_t s) {
   return 0;
 }
 
+int launch_wgrad_reduce(const float* part, int nblk, int nelem_w, int cout, float* dw, float* dbias, hipStream_t s) {
+  hipLaunchKernelGGL(k_wgrad_reduce, dim3(cdiv(nelem_w + cout, 16)), dim3(256), 0, s, part, nblk, nelem_w, cout, dw, dbias);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_conv_wgrad(const ConvWgrad& a, hipStream_t s) {
   DQ_REQUIRE(a.du && a.inA && a.dw && a.scratch && a.cout > 0 && a.cinA > 0, "conv_wgrad: missing operand");
   const int cin = a.cinA + a.cinB;

@@ -22,6 +22,8 @@ PROTOTYPES = {
     "dq_last_error": (c_char_p, []),
     "dq_abi_version": (c_int, []),
     "dq_plan_create": (c_void_p, [c_int, c_int, POINTER(c_int), c_int, c_int]),
+    "dq_plan_create_ex": (c_void_p, [c_int, c_int, POINTER(c_int), c_int, c_int, c_int]),
+    "dq_plan_attn_cond_channels": (c_int, [c_void_p]),
     "dq_plan_destroy": (None, [c_void_p]),
     "dq_plan_num_params": (c_int, [c_void_p]),
     "dq_plan_param_floats": (c_int64, [c_void_p]),
@@ -86,6 +88,9 @@ PROTOTYPES = {
     "dq_rmsnorm_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dq_time_mlp_fwd": (c_int, [c_void_p] * 8 + [c_int, c_void_p]),
     "dq_scale_shift_fwd": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),
+    "dq_ms1_feat_fwd": (c_int, [c_void_p] * 3 + [c_float, c_float] + [c_void_p] * 3 + [c_int, c_int, c_int, c_void_p]),
+    "dq_ms1_feat_wgrad_scratch_floats": (c_int64, [c_int, c_int, c_int]),
+    "dq_ms1_feat_wgrad": (c_int, [c_void_p] * 5 + [c_int64, c_int, c_int, c_int, c_void_p]),
     "dq_prep_inputs_fwd": (c_int, [c_void_p] * 4 + [c_float, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dq_conv_fwd": (c_int, [c_void_p] * 4 + [c_int, c_void_p] + [c_int] * 7 + [c_void_p]),
     "dq_resblock_workspace_floats": (c_int64, [c_int] * 5),

@@ -68,7 +68,8 @@ def train(config_path, parquet_directory, ms2_data_path, ms1_data_path, batch_si
 
         dataset = SyntheticDIAMSDataset(n_windows=int(syn.get("n_windows", 32)), RT=int(syn.get("RT", 400)),
                                         MZ=int(syn.get("MZ", m["UNet1d"]["downsample_dim"])), normalize=config["data"]["normalize"],
-                                        rank=rank, world=world)
+                                        rank=rank, world=world,
+                                        ms1_channels=None if syn.get("ms1_channels") is None else int(syn["ms1_channels"]))
     else:
         from .utils.data_loader import DIAMSDataset
 

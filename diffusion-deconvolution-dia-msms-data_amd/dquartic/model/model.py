@@ -61,6 +61,10 @@ def extract(a, t, x_shape):  # model.py:131-148
     return out.reshape(b, *((1,) * (len(x_shape) - 1)))
 
 
+# the MS1 term compares per-RT summaries of the prediction with a chromatogram: undefined for a (RT, M1) MS1
+_MS1_TERM_MULTI = "ms1_loss_weight > 0 with attn_cond_channels > 1 is not implemented (the MS1 loss term is defined on a 1-D chromatogram)"
+
+
 class DDIMDiffusionModel(ModelInterface):
     def __init__(self, model_class, num_timesteps=1000, beta_schedule_type="cosine", pred_type="eps", auto_normalize=True,
                  ms1_loss_weight=0.0, device="cuda", **kwargs):
@@ -185,10 +189,8 @@ class DDIMDiffusionModel(ModelInterface):
     def _sample_native(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False):
         net: UNet1d = self.model
         f32 = lambda v: v.detach().to(torch.float32).contiguous()
-        x_T, c2, c1 = f32(x_T), f32(ms2_cond), f32(ms1_cond)
-        if c1.dim() == 3:
-            c1 = c1[..., 0].contiguous()
         B, RT, MZ = x_T.shape
+        x_T, c2, c1 = f32(x_T), f32(ms2_cond), f32(net._check_inputs(ms1_cond, B, RT))
         flat = net.flat_params
         ws = net.workspace(B, RT, False)
         ts = self.sampler_timesteps(self.num_timesteps, num_steps).to(torch.int32)
@@ -215,6 +217,8 @@ class DDIMDiffusionModel(ModelInterface):
         path; the fused path is ``train_step_fused``)."""
         if self.pred_type not in N.PRED_TYPES:
             raise ValueError(f"Unknown pred_type: {self.pred_type}")
+        if float(ms1_loss_weight or 0.0) > 0.0 and getattr(self.model, "attn_cond_channels", 1) > 1:
+            raise NotImplementedError(_MS1_TERM_MULTI)
         batch_size = x_0.size(0)
         if t is None:
             t = torch.randint(0, self.num_timesteps, (batch_size,), device=x_0.device).long()
@@ -250,10 +254,10 @@ class DDIMDiffusionModel(ModelInterface):
         if not self.native:
             raise RuntimeError("train_step_fused needs this package's UNet1d or a DDIMTransformerAdapter")
         f32 = lambda v: v.detach().to(torch.float32).contiguous()
-        x_0, c2, c1 = f32(x_0), f32(ms2_cond), f32(ms1_cond)
-        if c1.dim() == 3:
-            c1 = c1[..., 0].contiguous()
         B, RT, MZ = x_0.shape
+        if float(ms1_loss_weight or 0.0) > 0.0 and net.attn_cond_channels > 1:
+            raise NotImplementedError(_MS1_TERM_MULTI)
+        x_0, c2, c1 = f32(x_0), f32(ms2_cond), f32(net._check_inputs(ms1_cond, B, RT))
         if t is None:
             t = torch.randint(0, self.num_timesteps, (B,), device=x_0.device).long()
         if noise is None:

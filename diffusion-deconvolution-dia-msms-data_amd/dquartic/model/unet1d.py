@@ -11,13 +11,14 @@ Differences from the reference, all documented in DESIGN.md:
   * ``pos_output_only=True`` (Softplus behind final_conv, reference unet1d.py:1084, 1166) is fused into whichever kernel forms the
     network output, and its derivative into the head of the backward (DESIGN.md section 19); ``final_act`` is the reference's module;
   * only the working configuration family is built: simple=True, conditional=True, channels=1, init_cond_channels=1,
-    attn_cond_channels=1, 4 heads x 32, dim = 4, dim*mult <= 16, downsample_dim divisible by 2**(len(dim_mults)-1) -- which
+    attn_cond_channels in 1..4096 (a multi-channel MS1 ``(B, RT, M1)``), 4 heads x 32, dim = 4, dim*mult <= 16, downsample_dim divisible by 2**(len(dim_mults)-1) -- which
     includes the reference's shipped configuration (downsample_dim 40000: m/z rows of 40000 .. 625 positions and a
     10,000-channel bottleneck) -- anything else raises at construction;
   * all trainable tensors are views of ONE flat fp32 buffer (``flat_params``), gradients of one flat ``flat_grads``.
 """
 import ctypes
 import math
+import operator
 from typing import List, Optional
 
 import torch
@@ -139,8 +140,14 @@ class UNet1d(_FlatBuffers, nn.Module):
             unsupported.append("simple=False (crashes in the reference too, SURVEY F3)")
         if not conditional:
             unsupported.append("conditional=False")
-        if channels != 1 or init_cond_channels != 1 or attn_cond_channels != 1:
-            unsupported.append("channels/init_cond_channels/attn_cond_channels other than 1")
+        if channels != 1 or init_cond_channels != 1:
+            unsupported.append("channels/init_cond_channels other than 1")
+        try:  # any integral type (a numpy integer from a config loader), not bool / float / None
+            m1 = None if isinstance(attn_cond_channels, bool) else operator.index(attn_cond_channels)
+        except TypeError:
+            m1 = None
+        if m1 is None or not 1 <= m1 <= 4096:
+            unsupported.append(f"attn_cond_channels outside 1..4096 (got {attn_cond_channels!r})")
         if init_dim not in (None, dim) or out_dim not in (None, 1) or attn_cond_init_dim not in (None, 2 * dim):
             unsupported.append("non-default init_dim/out_dim/attn_cond_init_dim")
         if learned_variance or dropout != 0.0:
@@ -152,6 +159,7 @@ class UNet1d(_FlatBuffers, nn.Module):
 
         self.channels = channels
         self.conditional = conditional
+        self.attn_cond_channels = m1
         self.out_dim = 1
         self.dim = int(dim)
         self.dim_mults = tuple(int(m) for m in dim_mults)
@@ -161,7 +169,7 @@ class UNet1d(_FlatBuffers, nn.Module):
 
         lib = N.lib()
         mults = (ctypes.c_int * len(self.dim_mults))(*self.dim_mults)
-        self._plan = lib.dq_plan_create(self.dim, len(self.dim_mults), mults, self.downsample_dim, 1000)
+        self._plan = lib.dq_plan_create_ex(self.dim, len(self.dim_mults), mults, self.downsample_dim, 1000, self.attn_cond_channels)
         if not self._plan:
             raise ValueError("UNet1d: " + (lib.dq_last_error() or b"?").decode())
         # reference unet1d.py:1084, 1166: Softplus behind final_conv; fixed for the module's lifetime (the plan carries it into every
@@ -286,6 +294,20 @@ class UNet1d(_FlatBuffers, nn.Module):
             pass
 
     # ------------------------------------------------------------------ forward
+    def _check_inputs(self, attn_cond, B, RT):
+        """The MS1 conditioning as the library reads it: ``(B, RT, M1)`` with M1 = attn_cond_channels contiguous (the reference folds it to
+        ``(B, M1, RT)``, unet1d.py:1122-1130); at M1 = 1 also the ``(B, RT)`` chromatogram.  Raises before anything is launched."""
+        M1 = self.attn_cond_channels
+        if attn_cond.dim() == 2 and M1 == 1:
+            attn_cond = attn_cond[..., None]
+        if attn_cond.dim() != 3 or tuple(attn_cond.shape[:2]) != (B, RT):
+            raise ValueError(f"UNet1d: attn_cond must be (B, RT, {M1}) = ({B}, {RT}, {M1})" + (" or (B, RT)" if M1 == 1 else "")
+                             + f", got {tuple(attn_cond.shape)}")
+        if attn_cond.shape[-1] != M1:
+            raise ValueError(f"UNet1d: attn_cond has a trailing dimension of {attn_cond.shape[-1]}, the network was built with "
+                             f"attn_cond_channels={M1}")
+        return attn_cond
+
     def _prep(self, x, time, init_cond, attn_cond):
         if not x.is_cuda:
             raise RuntimeError("UNet1d (MI355X build): tensors must live on the GPU; there is no CPU fallback")
@@ -300,12 +322,9 @@ class UNet1d(_FlatBuffers, nn.Module):
             init_cond = init_cond[None]
         if attn_cond is None:
             raise ValueError("UNet1d: attn_cond (MS1) is required when conditional=True (the reference's None path is inconsistent)")
-        if attn_cond.dim() == 3:
-            if attn_cond.shape[-1] != 1:
-                raise ValueError("UNet1d: 3-D attn_cond needs a trailing dimension of attn_cond_channels=1")
-            attn_cond = attn_cond[..., 0]
-        if tuple(init_cond.shape) != (B, RT, MZ) or tuple(attn_cond.shape) != (B, RT):
-            raise ValueError("UNet1d: init_cond must be (B,RT,MZ) and attn_cond (B,RT)")
+        attn_cond = self._check_inputs(attn_cond, B, RT)
+        if tuple(init_cond.shape) != (B, RT, MZ):
+            raise ValueError("UNet1d: init_cond must be (B,RT,MZ)")
         time = time.reshape(-1).to(device=x.device, dtype=torch.int64)
         if time.numel() == 1 and B > 1:
             time = time.expand(B)

@@ -9,17 +9,26 @@ precursor trace ``ms1[rt] = sum_k I_k * exp(...)``.  ``SyntheticDIAMSDataset`` t
 contract (data_loader.py:60-90): ``__getitem__`` ignores its index, draws a random PAIR of windows, min-max
 normalises the pair (MS2: min/max over both windows; MS1: min/max of window 1, applied to both) and returns
 ``(ms2_1, ms1_1, ms2_2, ms1_2)``; ``reset_epoch()`` exists because the harness calls it.
+
+``ms1_channels=M1`` (optional) yields the MS1 slice the reference's data generator writes, ``(RT, M1)``: each peptide's precursor trace is
+spread over ``M1`` isotope-like channels -- a first channel ~ U{0..M1-1} and up to four following ones with intensities falling by a
+factor ~ U(0.3, 0.8) each.  These draws come from a generator of their own (seed ``987654 + i``), so the MS2 window and, without the
+argument, the 1-D chromatogram are the same numbers as ever.
 """
 import numpy as np
 import torch
 from torch.utils.data import Dataset
 
 
-def make_window(i: int, RT: int = 400, MZ: int = 64):
+def make_window(i: int, RT: int = 400, MZ: int = 64, ms1_channels=None):
     rng = np.random.default_rng(1234 + i)
     rt = np.arange(RT, dtype=np.float32)[:, None]
     ms2 = np.zeros((RT, MZ), np.float32)
-    ms1 = np.zeros((RT,), np.float32)
+    M1 = None if ms1_channels is None else int(ms1_channels)
+    if M1 is not None and M1 < 1:
+        raise ValueError("ms1_channels must be >= 1")
+    ms1 = np.zeros((RT,) if M1 is None else (RT, M1), np.float32)
+    rng1 = None if M1 is None else np.random.default_rng(987654 + i)  # (its own stream: the draws above and below stay what they were)
     for _ in range(int(rng.integers(3, 13))):
         apex = rng.uniform(0, RT)
         sigma = rng.uniform(3, 15)
@@ -28,15 +37,22 @@ def make_window(i: int, RT: int = 400, MZ: int = 64):
         bins = rng.integers(0, MZ, size=nfrag)
         inten = rng.lognormal(0.0, 1.0, size=nfrag).astype(np.float32)
         np.add.at(ms2, (slice(None), bins), prof * inten[None, :])
-        ms1 += float(rng.lognormal(0.0, 1.0)) * prof[:, 0]
+        inten1 = float(rng.lognormal(0.0, 1.0))
+        if M1 is None:
+            ms1 += inten1 * prof[:, 0]
+        else:  # the precursor's isotope envelope: consecutive channels, falling intensities
+            first = int(rng1.integers(0, M1))
+            for k in range(min(5, M1 - first)):
+                ms1[:, first + k] += np.float32(inten1) * prof[:, 0]
+                inten1 *= float(rng1.uniform(0.3, 0.8))
     return ms2, ms1
 
 
-def make_pool(n: int, RT: int = 400, MZ: int = 64, start: int = 0):
+def make_pool(n: int, RT: int = 400, MZ: int = 64, start: int = 0, ms1_channels=None):
     ms2 = np.empty((n, RT, MZ), np.float32)
-    ms1 = np.empty((n, RT), np.float32)
+    ms1 = np.empty((n, RT) if ms1_channels is None else (n, RT, int(ms1_channels)), np.float32)
     for i in range(n):
-        ms2[i], ms1[i] = make_window(start + i, RT, MZ)
+        ms2[i], ms1[i] = make_window(start + i, RT, MZ, ms1_channels)
     return ms2, ms1
 
 
@@ -50,13 +66,14 @@ def normalize_pair(ms2_1, ms1_1, ms2_2, ms1_2):
 
 
 class SyntheticDIAMSDataset(Dataset):
-    def __init__(self, n_windows: int = 32, RT: int = 400, MZ: int = 64, normalize="minmax", seed: int = 0, rank: int = 0, world: int = 1):
+    def __init__(self, n_windows: int = 32, RT: int = 400, MZ: int = 64, normalize="minmax", seed: int = 0, rank: int = 0, world: int = 1,
+                 ms1_channels=None):
         if normalize is None:
             raise ValueError("normalize must be 'minmax' (the reference raises on None, data_loader.py:80-81)")
         # rank r of `world` owns windows i with i % world == r
         ids = [i for i in range(n_windows) if i % world == rank]
         self.ms2 = np.stack([make_window(i, RT, MZ)[0] for i in ids])
-        self.ms1 = np.stack([make_window(i, RT, MZ)[1] for i in ids])
+        self.ms1 = np.stack([make_window(i, RT, MZ, ms1_channels)[1] for i in ids])
         self.normalize = normalize
         self._rng = np.random.default_rng(seed + 7919 * rank)
 

@@ -45,7 +45,8 @@ const char* dq_last_error(void);
  * dq_rope, dq_attn_*); dq_train_step takes ms1_loss_weight, dq_ms1_loss_fwd_bwd;
  * dq_tfm_set_precision, dq_gemm_bf16x3.  8: dq_tfm_bwd_buckets, dq_tfm_num_buckets, dq_tfm_bucket_info.  9: dq_linattn_prepare,
  * dq_linattn_fwd_prepared.  10: dq_set_option, dq_get_option, dq_debug_side_tail_store (later, additive: dq_plan_set_final_act,
- * dq_plan_final_act, dq_get_option_effective, dq_resblock_forms, dq_linattn_forms, dq_linattn_bwd_store). */
+ * dq_plan_final_act, dq_get_option_effective, dq_resblock_forms, dq_linattn_forms, dq_linattn_bwd_store, dq_plan_create_ex,
+ * dq_plan_attn_cond_channels, dq_ms1_feat_fwd, dq_ms1_feat_wgrad, dq_ms1_feat_wgrad_scratch_floats). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 10
 
@@ -70,10 +71,18 @@ enum { DQ_PRED_EPS = 0, DQ_PRED_X0 = 1 };
 
 /* ---- network description -------------------------------------------------------------------------------------
  * Replaces UNet1d.__init__ (unet1d.py:918-1084) for simple=True, conditional=True, channels=1,
- * init_cond_channels=1, attn_cond_channels=1: builds the layer list and the flat parameter layout.
+ * init_cond_channels=1: builds the layer list and the flat parameter layout.
  * mz == downsample_dim.  num_timesteps is informational (kept for ABI continuity): the schedule tables come with each call.
- * Returns NULL on an unsupported configuration (see dq_last_error). */
+ * Returns NULL on an unsupported configuration (see dq_last_error).  dq_plan_create is dq_plan_create_ex(..., 1). */
 dq_plan* dq_plan_create(int dim, int n_mults, const int* dim_mults, int mz, int num_timesteps);
+/* attn_cond_channels = M1 in 1..4096 (anything else: NULL, the error names the argument): the MS1 conditioning of every entry point
+ * that takes attn_cond / ms1_cond is (B, RT, M1) with M1 contiguous -- what the reference folds to (B, M1, RT) in front of
+ * attn_cond_proj (unet1d.py:1122-1130) -- and attn_cond_proj.1.0.weight is (8, M1, 7).  M1 = 1 is the (B, RT) chromatogram and the code
+ * path of dq_plan_create, launch for launch.  M1 > 1: k_ms1_feat.hip reads the (B, RT, M1) layout directly; ms1_loss_weight > 0 is rejected
+ * (dq_train_step), the MS1 term being defined on a chromatogram. */
+dq_plan* dq_plan_create_ex(int dim, int n_mults, const int* dim_mults, int mz, int num_timesteps, int attn_cond_channels);
+/* The plan's attn_cond_channels; -1 for a NULL plan. */
+int dq_plan_attn_cond_channels(const dq_plan* plan);
 void dq_plan_destroy(dq_plan* plan);
 /* Number of trainable tensors / total trainable floats in the flat buffer. */
 int dq_plan_num_params(const dq_plan* plan);
@@ -112,7 +121,7 @@ int dq_ddim_step_x0(const float* x_t, const float* x0_pred, float* x_prev, float
 
 /* ---- K1-K8: UNet1d.forward (unet1d.py:1086-1166) ---------------------------------------------------------------
  * params: flat parameter buffer; rope_freqs: the 8 non-trainable RoPE frequencies (device).
- * x, init_cond (B,RT,MZ); attn_cond (B,RT); t (B) int64 or NULL => every sample uses t_scalar.
+ * x, init_cond (B,RT,MZ); attn_cond (B,RT,M1), M1 = the plan's attn_cond_channels ((B,RT) at M1 = 1); t (B) int64 or NULL => every sample uses t_scalar.
  * init_cond/attn_cond are mapped v*cond_mul+cond_add on the fly (2,-1 reproduces model.py:310-311/350-351; 1,0 = raw).
  * out (B,RT,MZ) receives the prediction.  save_for_bwd != 0 also keeps the pre-norm tensors dq_unet_bwd reads. */
 int dq_unet_fwd(dq_plan* plan, const float* params, const float* rope_freqs, const float* x, const int64_t* t, int t_scalar,
@@ -303,7 +312,18 @@ int dq_time_mlp_fwd(const float* w1, const float* b1, const float* w2, const flo
 /* SiLU -> Linear(16, m) head hanging off the time embedding (ResnetBlock.mlp unet1d.py:292-296; ConditionalScaleShift
  * :662-678): temb (B,16), w (m,16), b (m) -> ss (B,m). */
 int dq_scale_shift_fwd(const float* temb, const float* w, const float* b, float* ss, int B, int m, void* stream);
-/* The first layer's inputs (unet1d.py:1107-1115, 1122-1124): cat0 (B*RT, 2, MZ) = [ (cond*cond_mul+cond_add) * (scale_b + 1) +
+/* attn_cond_proj.1.0 + GELU on a multi-channel MS1 (k_ms1_feat.hip; unet1d.py:976, 1122-1130), 1 <= M1 <= 4096: ms1 (B, RT, M1) raw,
+ * w (8, M1, 7), bias (8):  u[b][c][rt] = bias[c] + sum_tap sum_m w[c][m][tap] * n(ms1[b][rt+tap-3][m]),  n(v) = v*cond_mul+cond_add, rows
+ * outside 0..RT-1 contributing nothing.  a_out (B, 8, RT) = GELU(u); u_out (B, 8, RT) and ms1n_out (B, RT, M1) = n(ms1) nullable. */
+int dq_ms1_feat_fwd(const float* ms1, const float* w, const float* bias, float cond_mul, float cond_add, float* ms1n_out, float* u_out,
+                    float* a_out, int B, int RT, int M1, void* stream);
+/* Its weight and bias gradient: dw (8, M1, 7) += sum_{b,rt} du[b][c][rt] * ms1n[b][rt+tap-3][m], dbias (8) += sum du, from the NORMALISED
+ * ms1n (B, RT, M1) and du (B, 8, RT).  One slot per workgroup in `scratch` (dq_ms1_feat_wgrad_scratch_floats floats; -1 for arguments
+ * out of range) and an ordered sum: no float atomics, bitwise repeatable. */
+int64_t dq_ms1_feat_wgrad_scratch_floats(int B, int RT, int M1);
+int dq_ms1_feat_wgrad(const float* ms1n, const float* du, float* dw, float* dbias, float* scratch, int64_t scratch_floats, int B, int RT,
+                      int M1, void* stream);
+/* The first layer's inputs at attn_cond_channels = 1 (unet1d.py:1107-1115, 1122-1124): cat0 (B*RT, 2, MZ) = [ (cond*cond_mul+cond_add) * (scale_b + 1) +
  * shift_b , x ], ms1n (B, RT) = ms1*cond_mul+cond_add; ss (B, 2) = [scale, shift] per sample. */
 int dq_prep_inputs_fwd(const float* x, const float* cond, const float* ms1, const float* ss, float cond_mul, float cond_add, float* cat0,
                        float* ms1n, int B, int RT, int MZ, void* stream);
