@@ -110,6 +110,7 @@ constexpr int WGRAD_MAX_PARTS = 512;
 // the ordered sum of nblk slots [dW (nelem_w) | dbias (cout)] into dw / dbias (+=): k_wgrad_reduce on its own
 int launch_wgrad_reduce(const float* part, int nblk, int nelem_w, int cout, float* dw, float* dbias, hipStream_t s);
 int launch_conv_wgrad(const ConvWgrad& a, hipStream_t s);
+bool conv_wgrad_vec4(const ConvWgrad& a);  // launch_conv_wgrad takes k_conv_wgrad_v4 (4 positions per thread and step), not k_conv_wgrad
 // up to three stride-1 convs over the same (rows, n) in one launch + one merged reduce (each with its own scratch region)
 int launch_conv_wgrad_multi(const ConvWgrad* w, int count, hipStream_t s);
 

@@ -646,9 +646,12 @@ int tiny_bwd_run(const Ctx& c, TinyBwd t, bool up) {
 // channels over (B, C, RT)) is a per-sample matrix product Y_b (cout x n) = W (cout x cin) X_b (cin x n): it goes to the fp32
 // matrix-core GEMM (k_gemm.hip), batched over the samples.  The per-thread channel loop of the generic conv kernels is a serial
 // chain of 128-256 dependent FMAs there (47 us forward, 108 us data gradient at batch 32; ~10 us as a GEMM).
-bool conv_is_gemm(const Ctx& c, const ConvP& cp, int mode, int n_in, int n_out) {
-  return cp.k == 1 && mode == CONV_S1 && cp.b < 0 && n_in == n_out && n_in % 4 == 0 && cp.cin % 4 == 0 && (cp.cout >= 64 || cp.cin >= 64) &&
-         (int64_t)cp.cout * cp.cin <= WTMP_SLOT;
+bool conv_is_gemm(int cout, int cin, int k, bool has_bias, int mode, int n_in, int n_out) {
+  return k == 1 && mode == CONV_S1 && !has_bias && n_in == n_out && n_in % 4 == 0 && cin % 4 == 0 && (cout >= 64 || cin >= 64) &&
+         (int64_t)cout * cin <= WTMP_SLOT;
+}
+bool conv_is_gemm(const Ctx&, const ConvP& cp, int mode, int n_in, int n_out) {
+  return conv_is_gemm(cp.cout, cp.cin, cp.k, cp.b >= 0, mode, n_in, n_out);
 }
 // the GEMM reads its operands with 16-byte loads; a weight slice of the flat parameter buffer that does not start on a 16-byte
 // boundary is copied (<= 32 KB, device to device, same stream) to an aligned slot of the arena first
@@ -677,49 +680,116 @@ int conv_plain_fwd(const Ctx& c, const ConvP& cp, int mode, const float* in, flo
   return launch_conv_fwd(f, c.s);
 }
 
-int conv_plain_bwd(const Ctx& c, const ConvP& cp, int mode, const float* in, const float* dout, float* din, int rows, int n_in,
-                   int n_out, int accumulate, int wslot = -1, bool with_wgrad = true) {
-  if (with_wgrad) {
-    ConvWgrad wg;
-    wg.scratch = c.w(c.ar.wg); wg.scratch_floats = c.ar.wg_floats;
-    wg.du = dout; wg.inA = in; wg.cinA = cp.cin; wg.cout = cp.cout; wg.K = cp.k; wg.mode = mode; wg.rows = rows; wg.n_in = n_in;
-    wg.n_out = n_out; wg.dw = c.dprm(cp.w); wg.dbias = cp.b >= 0 ? c.dprm(cp.b) : nullptr;
-    DQ_TRY(wgrad_async(c, wg));
+// ---- backward of a plain conv, free of the network's context: the operands, and where the weight-gradient launches go.  The network
+// (conv_plain_bwd / resample_bwd below) and the stand-alone dq_conv_bwd fill one of these, so both take the same kernels by the same rule.
+struct ConvBwdOps {
+  const float* w = nullptr;        // (cout, cinA + cinB, K)
+  const float* w_gemm = nullptr;   // the same weight behind a 16-byte aligned address (w itself, or the forward's copy); null: none
+  float* dw = nullptr; float* dbias = nullptr;  // += ; dbias null: the conv has no bias
+  const float* inA = nullptr; const float* inB = nullptr; int cinA = 0, cinB = 0;  // forward input = cat(A, B)
+  float* dinA = nullptr; float* dinB = nullptr; int accumulate = 0;                // its gradient (either nullable): = or +=
+  const float* dout = nullptr;
+  int cout = 0, K = 1, mode = CONV_S1, rows = 0, n_in = 0, n_out = 0, rows_per_sample = 1;
+  float* wg = nullptr; int64_t wg_floats = 0;        // partial blocks of launch_conv_wgrad
+  float* cpart = nullptr; int64_t cpart_floats = 0;  // per-workgroup slots of k_conv_bwd_wg; 0: that path was not laid out
+  bool with_wgrad = true;
+  std::function<int(const ConvWgrad&)> wgrad;        // issues the weight-gradient launch (the network: its side stream); empty: on the call's stream
+  std::vector<ResWgReduce>* wg_defer = nullptr;      // collects k_conv_bwd_wg's slot reduction instead of launching it
+};
+enum ConvBwdDataForm { CONV_BWD_DATA_WG, CONV_BWD_DATA_GEMM, CONV_BWD_DATA_PLAIN };
+enum ConvWgradForm { CONV_WGRAD_WG, CONV_WGRAD_V4, CONV_WGRAD_SCALAR };
+int conv_level_pre(int mode, int K) {  // the LEVEL_PRE_* stage a (mode, K) conv is, or -1
+  if (mode == CONV_DOWN && K == 4) return LEVEL_PRE_DOWN;
+  if (mode == CONV_UP && K == 3) return LEVEL_PRE_UP;
+  return mode == CONV_S1 && K == 3 ? LEVEL_PRE_S1 : -1;
+}
+// data, weight and bias gradient in one k_conv_bwd_wg launch: a single input, slots laid out, and the bias gradient right behind the weight's
+bool conv_bwd_takes_wg(const ConvBwdOps& o, int pre) {
+  const bool off = DQ_DEV_FLAG("DQ_NO_CONV_WG", '1');  // (dev switch)
+  return !off && o.cpart_floats && o.cinB == 0 && o.dbias == o.dw + (int64_t)o.cout * o.cinA * o.K &&
+         conv_wg_usable(o.cout, pre, o.cinA, o.n_out, o.rows_per_sample);
+}
+// dX_b (cin x n) (+)= W^T (cin x cout) dY_b (cout x n) on the GEMM (a bias does not enter the DATA gradient: to_out's ran on the generic
+// kernel because of it, 32 us against ~6 us on the GEMM)
+bool conv_bwd_data_is_gemm(const ConvBwdOps& o) {
+  return o.cinB == 0 && conv_is_gemm(o.cout, o.cinA, o.K, false, o.mode, o.n_in, o.n_out) && o.w_gemm;
+}
+ConvWgrad conv_bwd_wgrad_args(const ConvBwdOps& o) {
+  ConvWgrad wg;
+  wg.scratch = o.wg; wg.scratch_floats = o.wg_floats;
+  wg.du = o.dout; wg.inA = o.inA; wg.inB = o.inB; wg.cinA = o.cinA; wg.cinB = o.cinB; wg.cout = o.cout; wg.K = o.K; wg.mode = o.mode;
+  wg.rows = o.rows; wg.n_in = o.n_in; wg.n_out = o.n_out; wg.dw = o.dw; wg.dbias = o.dbias;
+  return wg;
+}
+void conv_bwd_forms(const ConvBwdOps& o, int* data_form, int* wgrad_form) {
+  const int pre = conv_level_pre(o.mode, o.K);
+  if (pre >= 0 && conv_bwd_takes_wg(o, pre)) { *data_form = CONV_BWD_DATA_WG; *wgrad_form = CONV_WGRAD_WG; return; }
+  *data_form = conv_bwd_data_is_gemm(o) ? CONV_BWD_DATA_GEMM : CONV_BWD_DATA_PLAIN;
+  *wgrad_form = conv_wgrad_vec4(conv_bwd_wgrad_args(o)) ? CONV_WGRAD_V4 : CONV_WGRAD_SCALAR;
+}
+
+int conv_plain_bwd(const ConvBwdOps& o, hipStream_t s) {
+  if (o.with_wgrad) {
+    const ConvWgrad wg = conv_bwd_wgrad_args(o);
+    DQ_TRY(o.wgrad ? o.wgrad(wg) : launch_conv_wgrad(wg, s));
   }
-  ConvP nobias = cp;
-  nobias.b = -1;  // (a bias does not enter the DATA gradient: to_out's ran on the generic kernel because of it, 32 us against ~6 us on the GEMM)
-  if (din && conv_is_gemm(c, nobias, mode, n_in, n_out) && (wslot >= 0 || ((uintptr_t)c.prm(cp.w) & 15) == 0)) {  // dX_b (cin x n) (+)= W^T (cin x cout) dY_b (cout x n)
+  if (o.dinA && conv_bwd_data_is_gemm(o)) {
     Gemm g;
-    DQ_TRY(gemm_weight(c, cp, &g.A, wslot));
-    g.a_kmajor = 0; g.lda = cp.cin; g.B = dout; g.b_kmajor = 0; g.ldb = n_in; g.C = din; g.ldc = n_in;
-    g.M = cp.cin; g.N = n_in; g.K = cp.cout; g.batch = rows; g.sBo = (int64_t)cp.cout * n_in; g.sCo = (int64_t)cp.cin * n_in;
-    g.accumulate = accumulate;
-    return launch_gemm(g, c.s);
+    g.A = o.w_gemm;
+    g.a_kmajor = 0; g.lda = o.cinA; g.B = o.dout; g.b_kmajor = 0; g.ldb = o.n_in; g.C = o.dinA; g.ldc = o.n_in;
+    g.M = o.cinA; g.N = o.n_in; g.K = o.cout; g.batch = o.rows; g.sBo = (int64_t)o.cout * o.n_in; g.sCo = (int64_t)o.cinA * o.n_in;
+    g.accumulate = o.accumulate;
+    return launch_gemm(g, s);
   }
-  if (din) {
+  if (o.dinA || o.dinB) {
     ConvBwdData bd;
-    bd.du = dout; bd.w = c.prm(cp.w); bd.cout = cp.cout; bd.K = cp.k; bd.mode = mode; bd.rows = rows; bd.n_in = n_in; bd.n_out = n_out;
-    bd.dinA = din; bd.cinA = cp.cin; bd.accumulate = accumulate;
-    DQ_TRY(launch_conv_bwd_data(bd, c.s));
+    bd.du = o.dout; bd.w = o.w; bd.cout = o.cout; bd.K = o.K; bd.mode = o.mode; bd.rows = o.rows; bd.n_in = o.n_in; bd.n_out = o.n_out;
+    bd.dinA = o.dinA; bd.dinB = o.dinB; bd.cinA = o.cinA; bd.cinB = o.cinB; bd.accumulate = o.accumulate;
+    DQ_TRY(launch_conv_bwd_data(bd, s));
   }
   return 0;
 }
 
 // backward of a level's resample conv: one launch for the data and the weight / bias gradient when the shape allows it
-int resample_bwd(const Ctx& c, const ConvP& cp, int pre, const LevelBuf& b, int n_in, int n_out, int accumulate) {
-  const bool off = DQ_DEV_FLAG("DQ_NO_CONV_WG", '1');  // (dev switch)
-  if (!off && b.cpart_floats && cp.b == cp.w + (int64_t)cp.cout * cp.cin * cp.k && conv_wg_usable(cp.cout, pre, cp.cin, n_out, c.RT)) {
+int resample_bwd(const ConvBwdOps& o, int pre, hipStream_t s) {
+  if (conv_bwd_takes_wg(o, pre)) {
     ConvBwdWg k;
-    k.dy = c.g(b.rs); k.in = c.w(b.la); k.w = c.prm(cp.w); k.din = c.g(b.la); k.accumulate = accumulate;
-    k.part = c.w(b.cpart); k.part_floats = b.cpart_floats; k.dparams = c.dprm(cp.w);
-    k.C = cp.cout; k.pre = pre; k.cp = cp.cin; k.rows = c.B * c.RT; k.n = n_out; k.rows_per_sample = c.RT;
+    k.dy = o.dout; k.in = o.inA; k.w = o.w; k.din = o.dinA; k.accumulate = o.accumulate;
+    k.part = o.cpart; k.part_floats = o.cpart_floats; k.dparams = o.dw;
+    k.C = o.cout; k.pre = pre; k.cp = o.cinA; k.rows = o.rows; k.n = o.n_out; k.rows_per_sample = o.rows_per_sample;
     ResWgReduce red;
-    DQ_TRY(launch_conv_bwd_wg(k, c.s, &red));
-    if (c.wg_defer) { c.wg_defer->push_back(red); return 0; }
-    return launch_res_wg_reduce(&red, 1, c.s);
+    DQ_TRY(launch_conv_bwd_wg(k, s, &red));
+    if (o.wg_defer) { o.wg_defer->push_back(red); return 0; }
+    return launch_res_wg_reduce(&red, 1, s);
   }
+  return conv_plain_bwd(o, s);
+}
+
+// the network's operands of a conv's backward
+// wslot: aligned weight slot prepared by the forward (-1: none; the GEMM route is then only taken for an aligned weight)
+ConvBwdOps conv_bwd_ops(const Ctx& c, const ConvP& cp, int mode, const float* in, const float* dout, float* din, int rows, int n_in, int n_out,
+                        int accumulate, int wslot, bool with_wgrad) {
+  ConvBwdOps o;
+  o.w = c.prm(cp.w); o.dw = c.dprm(cp.w); o.dbias = cp.b >= 0 ? c.dprm(cp.b) : nullptr;
+  if (wslot >= 0) gemm_weight(c, cp, &o.w_gemm, wslot);
+  else if (((uintptr_t)o.w & 15) == 0) o.w_gemm = o.w;
+  o.inA = in; o.cinA = cp.cin; o.dinA = din; o.accumulate = accumulate; o.dout = dout;
+  o.cout = cp.cout; o.K = cp.k; o.mode = mode; o.rows = rows; o.n_in = n_in; o.n_out = n_out; o.rows_per_sample = c.RT;
+  o.wg = c.w(c.ar.wg); o.wg_floats = c.ar.wg_floats;
+  o.with_wgrad = with_wgrad;
+  o.wgrad = [&c](const ConvWgrad& w) { return wgrad_async(c, w); };
+  o.wg_defer = c.wg_defer;
+  return o;
+}
+int conv_plain_bwd(const Ctx& c, const ConvP& cp, int mode, const float* in, const float* dout, float* din, int rows, int n_in,
+                   int n_out, int accumulate, int wslot = -1, bool with_wgrad = true) {
+  return conv_plain_bwd(conv_bwd_ops(c, cp, mode, in, dout, din, rows, n_in, n_out, accumulate, wslot, with_wgrad), c.s);
+}
+int resample_bwd(const Ctx& c, const ConvP& cp, int pre, const LevelBuf& b, int n_in, int n_out, int accumulate) {
   const int mode = pre == LEVEL_PRE_DOWN ? CONV_DOWN : (pre == LEVEL_PRE_UP ? CONV_UP : CONV_S1);
-  return conv_plain_bwd(c, cp, mode, c.w(b.la), c.g(b.rs), c.g(b.la), c.B * c.RT, n_in, n_out, accumulate);
+  ConvBwdOps o = conv_bwd_ops(c, cp, mode, c.w(b.la), c.g(b.rs), c.g(b.la), c.B * c.RT, n_in, n_out, accumulate, -1, true);
+  o.cpart = b.cpart_floats ? c.w(b.cpart) : nullptr; o.cpart_floats = b.cpart_floats;
+  return resample_bwd(o, pre, c.s);
 }
 
 ConvP proj(int64_t w, int cout, int cin) { ConvP c; c.w = w; c.b = -1; c.cout = cout; c.cin = cin; c.k = 1; return c; }
@@ -2173,6 +2243,73 @@ int dq_conv_fwd(const float* x, const float* w, const float* bias, const float* 
   f.inA = x; f.cinA = cin; f.w = w; f.bias = bias; f.cout = cout; f.K = K; f.mode = mode; f.rows = rows; f.n_in = n_in; f.n_out = n_out;
   f.y_out = y; f.g = norm_g; f.act = act;
   return launch_conv_fwd(f, (hipStream_t)stream);
+}
+
+namespace {
+// the stand-alone conv backward: the operands of dq_conv_bwd as the network's own dispatch takes them.  Workspace: [weight-gradient partial
+// blocks | k_conv_bwd_wg's slots (where the shape admits that kernel)]
+int conv_bwd_standalone(ConvBwdOps& o, const float* xA, int cinA, const float* xB, int cinB, const float* w, const float* dy, float* dxA,
+                        float* dxB, float* dparams, int has_bias, int cout, int K, int mode, int rows, int n_in, int n_out, int rows_per_sample,
+                        int accumulate, float* workspace, int64_t* workspace_floats) {
+  DQ_REQUIRE(cout > 0 && cinA > 0 && cinB >= 0 && rows > 0 && n_in > 0 && n_out > 0 && rows_per_sample > 0 && rows % rows_per_sample == 0,
+             "dq_conv_bwd: bad shape");
+  DQ_REQUIRE((mode == CONV_S1 && (K == 1 || K == 3 || K == 7) && n_in == n_out) || (mode == CONV_DOWN && K == 4 && n_in == 2 * n_out) ||
+             (mode == CONV_UP && K == 3 && n_out == 2 * n_in), "dq_conv_bwd: (mode, K, n_in, n_out) must be stride 1 (K 1 / 3 / 7, n_out = n_in), down (K 4, n_in = 2 n_out) or up (K 3, n_out = 2 n_in)");
+  const int cin = cinA + cinB;
+  const int64_t nelem_w = (int64_t)cout * cin * K;
+  o.w = w; o.w_gemm = ((uintptr_t)w & 15) == 0 ? w : nullptr;
+  o.dw = dparams; o.dbias = has_bias ? dparams + nelem_w : nullptr;
+  o.inA = xA; o.inB = cinB ? xB : nullptr; o.cinA = cinA; o.cinB = cinB; o.dinA = dxA; o.dinB = cinB ? dxB : nullptr; o.accumulate = accumulate != 0;
+  o.dout = dy; o.cout = cout; o.K = K; o.mode = mode; o.rows = rows; o.n_in = n_in; o.n_out = n_out; o.rows_per_sample = rows_per_sample;
+  o.wg_floats = ((int64_t)WGRAD_MAX_PARTS * (nelem_w + cout) + 63) / 64 * 64;
+  o.wg = workspace;
+  const int pre = conv_level_pre(mode, K);
+  if (pre >= 0 && cinB == 0 && conv_wg_usable(cout, pre, cinA, n_out, rows_per_sample)) {
+    o.cpart_floats = conv_wg_part_floats(cout, pre, cinA, rows / rows_per_sample, rows_per_sample, n_out);
+    o.cpart = workspace + o.wg_floats;
+  }
+  *workspace_floats = o.wg_floats + o.cpart_floats;
+  return 0;
+}
+}  // namespace
+
+int64_t dq_conv_bwd_workspace_floats(int cout, int cinA, int cinB, int K, int mode, int rows, int n_in, int n_out, int rows_per_sample) {
+  ConvBwdOps o;
+  int64_t need = 0;
+  if (conv_bwd_standalone(o, nullptr, cinA, nullptr, cinB, nullptr, nullptr, nullptr, nullptr, nullptr, 1, cout, K, mode, rows, n_in, n_out,
+                          rows_per_sample, 0, nullptr, &need)) return -1;
+  return need;
+}
+
+static_assert(CONV_BWD_DATA_WG == DQ_CONV_BWD_DATA_WG && CONV_BWD_DATA_GEMM == DQ_CONV_BWD_DATA_GEMM && CONV_BWD_DATA_PLAIN == DQ_CONV_BWD_DATA_PLAIN &&
+              CONV_WGRAD_WG == DQ_CONV_WGRAD_WG && CONV_WGRAD_V4 == DQ_CONV_WGRAD_V4 && CONV_WGRAD_SCALAR == DQ_CONV_WGRAD_SCALAR,
+              "ConvBwdDataForm / ConvWgradForm mirror include/dq_hip.h");
+int dq_conv_bwd_forms(int cout, int cinA, int cinB, int K, int mode, int rows, int n_in, int n_out, int rows_per_sample, int has_bias,
+                      int w_aligned, int* data_form, int* wgrad_form) {
+  DQ_REQUIRE(data_form && wgrad_form, "dq_conv_bwd_forms: null argument");
+  // the caller's tensors and the workspace as 16-byte aligned stand-ins (nothing is dereferenced), the weight one float off when !w_aligned
+  float* const base = reinterpret_cast<float*>(uintptr_t{1} << 20);
+  ConvBwdOps o;
+  int64_t need = 0;
+  DQ_TRY(conv_bwd_standalone(o, base, cinA, base, cinB, base + (w_aligned ? 0 : 1), base, base, base, base, has_bias, cout, K, mode, rows, n_in,
+                             n_out, rows_per_sample, 0, base, &need));
+  conv_bwd_forms(o, data_form, wgrad_form);
+  return 0;
+}
+
+int dq_conv_bwd(const float* xA, int cinA, const float* xB, int cinB, const float* w, const float* dy, float* dxA, float* dxB, float* dparams,
+                int has_bias, int cout, int K, int mode, int rows, int n_in, int n_out, int rows_per_sample, int accumulate, float* workspace,
+                int64_t workspace_floats, void* stream) {
+  DQ_REQUIRE(xA && (cinB == 0 || xB) && w && dy && dparams && workspace, "dq_conv_bwd: null argument");
+  DQ_REQUIRE(((uintptr_t)workspace & 15) == 0, "dq_conv_bwd: the workspace must be 16-byte aligned");
+  ConvBwdOps o;
+  int64_t need = 0;
+  DQ_TRY(conv_bwd_standalone(o, xA, cinA, xB, cinB, w, dy, dxA, dxB, dparams, has_bias, cout, K, mode, rows, n_in, n_out, rows_per_sample,
+                             accumulate, workspace, &need));
+  DQ_REQUIRE(workspace_floats >= need, "dq_conv_bwd: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int pre = conv_level_pre(mode, K);
+  return pre >= 0 ? resample_bwd(o, pre, s) : conv_plain_bwd(o, s);  // (everything on s: no side stream)
 }
 
 namespace {

@@ -966,6 +966,12 @@ int launch_wgrad_reduce(const float* part, int nblk, int nelem_w, int cout, floa
   return 0;
 }
 
+// (K = 7 -- init_conv and the first MS1 conv -- joined in round 4: as one position per thread and step the init_conv launch was six dependent
+// memory round trips per thread, 25 us at the tail of the side queue, which the end of the backward waits for)
+bool conv_wgrad_vec4(const ConvWgrad& a) {
+  return a.mode == CONV_S1 && (a.K == 1 || a.K == 3 || a.K == 7) && a.n_out % 4 == 0 && a.n_in == a.n_out;
+}
+
 int launch_conv_wgrad(const ConvWgrad& a, hipStream_t s) {
   DQ_REQUIRE(a.du && a.inA && a.dw && a.scratch && a.cout > 0 && a.cinA > 0, "conv_wgrad: missing operand");
   const int cin = a.cinA + a.cinB;
@@ -976,9 +982,7 @@ int launch_conv_wgrad(const ConvWgrad& a, hipStream_t s) {
   const int n_cob = cdiv(a.cout, COB), n_cib = cdiv(cin, CIB);
   const int nelem_w = a.cout * cin * a.K;
   // <= WGRAD_MAX_PARTS partial blocks per element; ~4 items per thread, ~2048 blocks in flight where the problem allows it
-  // (K = 7 -- init_conv and the first MS1 conv -- joined in round 4: as one position per thread and step the init_conv launch was six dependent
-  // memory round trips per thread, 25 us at the tail of the side queue, which the end of the backward waits for)
-  const bool vec4 = a.mode == CONV_S1 && (a.K == 1 || a.K == 3 || a.K == 7) && a.n_out % 4 == 0 && a.n_in == a.n_out;
+  const bool vec4 = conv_wgrad_vec4(a);
   const int gx = std::max(1, std::min({cdiv(total, 256 * (vec4 ? 8 : 4)), WGRAD_MAX_PARTS, std::max(1, wgrad_blocks() / (n_cob * n_cib))}));
   DQ_REQUIRE((int64_t)gx * (nelem_w + a.cout) <= a.scratch_floats, "conv_wgrad: scratch too small");
   dim3 grid(gx, n_cob * n_cib), block(256);

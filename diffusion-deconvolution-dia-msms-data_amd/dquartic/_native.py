@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DQ_HIP_LIB", os.path.join(os.path.dirname(_HERE), "libdq_hip.so"))
 
 _lib = None
-ABI_VERSION = 10  # DQ_ABI_VERSION of include/dq_hip.h this table was written against
+ABI_VERSION = 11  # DQ_ABI_VERSION of include/dq_hip.h this table was written against
 PRED_TYPES = {"eps": 0, "x0": 1}  # DQ_PRED_EPS / DQ_PRED_X0
 PRECISIONS = {"fp32": 0, "bf16x3": 1}  # DQ_PRECISION_FP32 / DQ_PRECISION_BF16X3
 FINAL_ACTS = {"identity": 0, "softplus": 1}  # DQ_FINAL_IDENTITY / DQ_FINAL_SOFTPLUS
@@ -16,6 +16,8 @@ RES_FWD_FORMS = ("rt", "level", "v4", "unfused")  # DQ_RES_FWD_* (index = value)
 RES_BWD_FORMS = ("wg", "rt", "rows", "cp", "plain", "unfused")  # DQ_RES_BWD_*
 LA_FWD_FORMS = ("long", "small", "rows", "register")  # DQ_LA_FWD_*
 LA_BWD_FORMS = ("long", "rows", "register")  # DQ_LA_BWD_*
+CONV_BWD_DATA_FORMS = ("wg", "gemm", "plain")  # DQ_CONV_BWD_DATA_*
+CONV_WGRAD_FORMS = ("wg", "v4", "scalar")  # DQ_CONV_WGRAD_*
 
 # name -> (restype, argtypes); this table is checked against include/dq_hip.h by tests/test_abi.py
 PROTOTYPES = {
@@ -93,6 +95,9 @@ PROTOTYPES = {
     "dq_ms1_feat_wgrad": (c_int, [c_void_p] * 5 + [c_int64, c_int, c_int, c_int, c_void_p]),
     "dq_prep_inputs_fwd": (c_int, [c_void_p] * 4 + [c_float, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dq_conv_fwd": (c_int, [c_void_p] * 4 + [c_int, c_void_p] + [c_int] * 7 + [c_void_p]),
+    "dq_conv_bwd_workspace_floats": (c_int64, [c_int] * 9),
+    "dq_conv_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 9 + [c_void_p, c_int64, c_void_p]),
+    "dq_conv_bwd_forms": (c_int, [c_int] * 11 + [POINTER(c_int), POINTER(c_int)]),
     "dq_resblock_workspace_floats": (c_int64, [c_int] * 5),
     "dq_level_param_floats": (c_int64, [c_int] * 5),
     "dq_level_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_int64, c_void_p]),
@@ -171,6 +176,16 @@ def linattn_forms(C: int, rows: int, n: int, prepared: bool = True):
     f, b = c_int(-1), c_int(-1)
     check(lib().dq_linattn_forms(C, rows, n, int(prepared), ctypes.byref(f), ctypes.byref(b)), "dq_linattn_forms")
     return LA_FWD_FORMS[f.value], LA_BWD_FORMS[b.value]
+
+
+def conv_bwd_forms(cout: int, cinA: int, cinB: int, K: int, mode: int, rows: int, n_in: int, n_out: int, rows_per_sample: int,
+                   has_bias: bool = True, w_aligned: bool = True):
+    """``dq_conv_bwd_forms``: the (data gradient, weight gradient) kernel forms ``dq_conv_bwd`` takes for this shape, as names of
+    CONV_BWD_DATA_FORMS / CONV_WGRAD_FORMS."""
+    d, g = c_int(-1), c_int(-1)
+    check(lib().dq_conv_bwd_forms(cout, cinA, cinB, K, mode, rows, n_in, n_out, rows_per_sample, int(has_bias), int(w_aligned),
+                                  ctypes.byref(d), ctypes.byref(g)), "dq_conv_bwd_forms")
+    return CONV_BWD_DATA_FORMS[d.value], CONV_WGRAD_FORMS[g.value]
 
 
 def check(rc, what):

@@ -46,9 +46,10 @@ const char* dq_last_error(void);
  * dq_tfm_set_precision, dq_gemm_bf16x3.  8: dq_tfm_bwd_buckets, dq_tfm_num_buckets, dq_tfm_bucket_info.  9: dq_linattn_prepare,
  * dq_linattn_fwd_prepared.  10: dq_set_option, dq_get_option, dq_debug_side_tail_store (later, additive: dq_plan_set_final_act,
  * dq_plan_final_act, dq_get_option_effective, dq_resblock_forms, dq_linattn_forms, dq_linattn_bwd_store, dq_plan_create_ex,
- * dq_plan_attn_cond_channels, dq_ms1_feat_fwd, dq_ms1_feat_wgrad, dq_ms1_feat_wgrad_scratch_floats). */
+ * dq_plan_attn_cond_channels, dq_ms1_feat_fwd, dq_ms1_feat_wgrad, dq_ms1_feat_wgrad_scratch_floats).  11: dq_conv_bwd,
+ * dq_conv_bwd_workspace_floats, dq_conv_bwd_forms. */
 int dq_abi_version(void);
-#define DQ_ABI_VERSION 10
+#define DQ_ABI_VERSION 11
 
 /* Process-wide tuning options (no reference counterpart: the reference has one code path per op).  The library reads NO environment
  * variable for its dispatch; what can be tuned is set here, takes effect from the next call on, and invalidates cached sampling graphs.
@@ -332,6 +333,25 @@ int dq_prep_inputs_fwd(const float* x, const float* cond, const float* ms1, cons
  * (:82-96).  act: 0 none, 1 SiLU, 2 GELU.  bias / norm_g nullable. */
 int dq_conv_fwd(const float* x, const float* w, const float* bias, const float* norm_g, int act, float* y, int cout, int cin, int K, int mode,
                 int rows, int n_in, int n_out, void* stream);
+/* Backward of dq_conv_fwd without norm / act (norm_g = NULL, act = 0) on the input cat(xA (rows, cinA, n_in), xB (rows, cinB, n_in)) (xB
+ * nullable with cinB = 0), through the network's own dispatch: the one-launch k_conv_bwd_wg (k_conv_wg.hip) where a level's resample conv
+ * takes it, else the data gradient on the batched GEMM (the bottleneck attention's bias-free 1x1 projections; needs a 16-byte aligned w) or
+ * k_conv_bwd_data, and the weight gradient by k_conv_wgrad[_v4] + k_wgrad_reduce -- all on `stream`.
+ * w (cout, cinA + cinB, K); dy (rows, cout, n_out) = d loss / d y.  dxA / dxB (nullable): accumulate != 0: +=, else plain stores.
+ * dparams: [dW (cout, cinA + cinB, K) | dbias (cout) iff has_bias], contiguous as in the flat gradient buffer, += always.
+ * rows_per_sample: RT at the m/z levels (rows = B * rows_per_sample).  workspace: dq_conv_bwd_workspace_floats floats, 16-byte aligned
+ * (-1 for a bad shape). */
+int64_t dq_conv_bwd_workspace_floats(int cout, int cinA, int cinB, int K, int mode, int rows, int n_in, int n_out, int rows_per_sample);
+int dq_conv_bwd(const float* xA, int cinA, const float* xB, int cinB, const float* w, const float* dy, float* dxA, float* dxB, float* dparams,
+                int has_bias, int cout, int K, int mode, int rows, int n_in, int n_out, int rows_per_sample, int accumulate, float* workspace,
+                int64_t workspace_floats, void* stream);
+/* Which kernels dq_conv_bwd takes for this shape (w 16-byte aligned iff w_aligned != 0, every other tensor aligned): *data_form =
+ * DQ_CONV_BWD_DATA_* (k_conv_bwd_wg | the batched GEMM | k_conv_bwd_data), *wgrad_form = DQ_CONV_WGRAD_* (k_conv_bwd_wg | k_conv_wgrad_v4 |
+ * k_conv_wgrad).  WG is both or neither.  Launches nothing.  Bad shape: non-zero. */
+enum { DQ_CONV_BWD_DATA_WG = 0, DQ_CONV_BWD_DATA_GEMM = 1, DQ_CONV_BWD_DATA_PLAIN = 2 };
+enum { DQ_CONV_WGRAD_WG = 0, DQ_CONV_WGRAD_V4 = 1, DQ_CONV_WGRAD_SCALAR = 2 };
+int dq_conv_bwd_forms(int cout, int cinA, int cinB, int K, int mode, int rows, int n_in, int n_out, int rows_per_sample, int has_bias,
+                      int w_aligned, int* data_form, int* wgrad_form);
 /* ResnetBlock (unet1d.py:271-323) on input cat(xA (rows,cinA,n), xB (rows,cinB,n)) (xB nullable with cinB = 0) with the time
  * embedding temb (rows / rows_per_sample, 16).  params: the block's tensors in state_dict order as ONE flat buffer
  * [mlp.1.weight, mlp.1.bias, block1.proj.weight, block1.proj.bias, block1.norm.g, block2.proj.weight, block2.proj.bias,

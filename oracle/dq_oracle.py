@@ -303,6 +303,8 @@ def unet_forward(
         cur = resnet_block(p, pre + ".1", cur, temb, RT)
         cur = linear_attention(p, pre + ".2", cur)
         hs.append(cur)
+        if taps is not None:
+            taps[f"down{lv}.in"] = cur  # (the resample conv's input: tests/test_conv_forms.py checks its own reference against this conv)
         if lv < L - 1:  # Downsample k4 s2 p1 (unet1d.py:110)
             cur = F.conv1d(cur, p[pre + ".3.weight"], p[pre + ".3.bias"], stride=2, padding=1)
         else:  # last level: k3 p1 (unet1d.py:1021)
@@ -325,6 +327,8 @@ def unet_forward(
         cur = resnet_block(p, pre + ".0", torch.cat((cur, hs.pop()), dim=1), temb, RT)
         cur = resnet_block(p, pre + ".1", torch.cat((cur, hs.pop()), dim=1), temb, RT)
         cur = linear_attention(p, pre + ".2", cur)
+        if taps is not None:
+            taps[f"up{ui}.in"] = cur
         if ui < L - 1:  # nearest x2 then k3 p1 (unet1d.py:93-96)
             cur = F.interpolate(cur, scale_factor=2, mode="nearest")
             cur = F.conv1d(cur, p[pre + ".3.1.weight"], p[pre + ".3.1.bias"], padding=1)
