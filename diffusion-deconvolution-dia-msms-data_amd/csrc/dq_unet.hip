@@ -10,6 +10,7 @@
 #include "../../include/dq_hip.h"
 
 #include <algorithm>
+#include <array>
 #include <functional>
 #include <cmath>
 #include <cstdlib>
@@ -202,8 +203,10 @@ struct Ctx {
   // set by unet_backward: the side-stream launches (weight gradients, norm-gain reduces) are collected and issued by side_flush
   // behind ONE event per group instead of one per ResnetBlock / conv (an event record costs ~4 us on the main stream: 29 + 14
   // of them were 0.13 ms per step); everything they read is final when it is queued and stays untouched until the join
-  struct SideItem { int kind; ConvWgrad w[3]; int count; PartReduce red; std::function<int(hipStream_t)> fn; };  // kind 3: fn(side stream)
-  std::vector<SideItem>* side_defer = nullptr;
+  // forks: the item runs behind the group's fork event (all but the ResnetBlock partial-sum reduce, which opens no fork of its own: it goes
+  // to the side stream if that exists, else to the main stream)
+  struct SideFn { std::function<int(hipStream_t)> fn; bool forks = true; };
+  std::vector<SideFn>* side_defer = nullptr;
   // set by unet_backward: the slot reductions of the ResnetBlock backwards that form their own weight gradients (k_res_bwd_wg),
   // collected for ONE launch at the end of the pass (null: each is reduced right behind its launch)
   std::vector<ResWgReduce>* wg_defer = nullptr;
@@ -249,6 +252,31 @@ static inline bool side_flush_here(int lv) { return (lv & 1) == 0; }
     int _rc = (expr);           \
     if (_rc) return _rc;        \
   } while (0)
+
+// "On the side queue if there is one": a piece of the backward that nothing on the main chain waits for.  `allowed` is the call site's own
+// condition; with it and a side queue at hand (unet_backward of a plan with an owner) the piece is queued for the next side_flush, else it runs now.
+inline bool side_open(const Ctx& c, bool allowed) { return allowed && c.owner && c.side_defer; }
+// a bare launch: fn(the side stream) behind the flush, or fn(c.s) now
+int on_side(const Ctx& c, bool allowed, std::function<int(hipStream_t)> fn, bool forks = true) {
+  if (!side_open(c, allowed)) return fn(c.s);
+  c.side_defer->push_back(Ctx::SideFn{std::move(fn), forks});
+  return 0;
+}
+// a piece of the pass: body(a copy of c without owner / queue whose stream is the side stream) behind the flush -- everything it launches,
+// its weight gradients included, stays on that stream --, or body(c) now
+int on_side(const Ctx& c, bool allowed, const std::function<int(const Ctx&)>& body) {
+  if (!side_open(c, allowed)) return body(c);
+  Ctx side = c;
+  side.owner = nullptr; side.side_defer = nullptr;
+  c.side_defer->push_back(Ctx::SideFn{[side, body](hipStream_t ss) mutable { side.s = ss; return body(side); }, true});
+  return 0;
+}
+// the collected ResnetBlock / resample-conv slot reductions (one launch for the network's <= 32 such blocks)
+int res_wg_reduce_all(const std::vector<ResWgReduce>& items, hipStream_t s) {
+  for (size_t i = 0; i < items.size(); i += RES_WG_REDUCE_MAX)
+    DQ_TRY(launch_res_wg_reduce(items.data() + i, (int)std::min<size_t>(RES_WG_REDUCE_MAX, items.size() - i), s));
+  return 0;
+}
 
 // a ResnetBlock's operands but its first input (what a block of the level kernel reads): the second input (skip channels), the parameters and
 // where its results go (wpart: the backward recomputes a1)
@@ -334,14 +362,7 @@ int res_bwd_side(const Ctx& c, const ResP& r, const ResBuf& b, const float* inA,
   if (gblocks > 0) {
     const PartReduce red = res_part_reduce(c.w(b.gpart), gblocks, rows / rows_per_sample, r.cout, c.dprm(r.g2), c.dprm(r.g1),
                                            c.g(c.ar.ss) + r.ss_off, c.p.ss_total);
-    if (c.side_defer && c.owner) {
-      Ctx::SideItem it{};
-      it.kind = 2; it.red = red;
-      c.side_defer->push_back(it);
-    } else {
-      hipStream_t rs = (c.owner && c.owner->side_stream) ? c.owner->side_stream : c.s;
-      DQ_TRY(launch_part_reduce(red, rs));
-    }
+    DQ_TRY(on_side(c, true, [red](hipStream_t rs) { return launch_part_reduce(red, rs); }, /*forks=*/false));
   }
   return 0;
 }
@@ -557,14 +578,10 @@ int la_flush(const Ctx& c) {
 int la_flush_side(const Ctx& c) {
   Ctx::LaDefer* d = c.la_defer;
   const bool off = DQ_DEV_FLAG("DQ_NO_LA_FLUSH_SIDE", '1');  // (dev switch)
-  if (off || !d || d->count == 0 || !c.owner || !c.side_defer || !tail_fork_enabled()) return 0;
+  if (!d || d->count == 0 || !side_open(c, !off && tail_fork_enabled())) return 0;  // (else they stay for la_flush)
   std::vector<LaReduceItem> items(d->items, d->items + d->count);
-  Ctx::SideItem it{};
-  it.kind = 3;
-  it.fn = [items](hipStream_t ss) { return launch_linattn_dw_reduce_multi(items.data(), (int)items.size(), ss); };
-  c.side_defer->push_back(it);
   d->count = 0;
-  return 0;
+  return on_side(c, true, [items](hipStream_t ss) { return launch_linattn_dw_reduce_multi(items.data(), (int)items.size(), ss); });
 }
 
 int la_bwd(const Ctx& c, const LAP& l, const LevelBuf& b, const float* x, const float* dy, float* dx, int rows, int n, int slot = -1) {
@@ -917,6 +934,151 @@ int mid_backward_wide(const Ctx& c, const float* rope) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// the narrow (register-resident) bottleneck: mid_block1, Residual(PreNorm(Attention(use_xattn))), mid_block2 over (B, mid_c, RT) tensors
+// (unet1d.py:1144-1148).  The folds into and out of that layout stay with the passes: the tiny levels next to the bottleneck may have done them.
+// ---------------------------------------------------------------------------------------------------------------
+// 16 channels (the default U-Net): which pieces of the attention ride in the neighbouring ResnetBlock's launch (k_res_rt.hip).  Both passes ask
+// here, so the backward agrees with what the forward of the same step stored.
+struct MidForms {
+  bool qkv_fused;  // forward: PreNorm, to_qv, to_k and RoPE behind mid_block1
+  bool out_fused;  // forward: to_out + bias + the residual in front of mid_block2; backward: d o = W_o^T d attn_out behind mid_block2's d x
+  bool pre_fused;  // backward: RoPE^T, d xn = W_qv^T d qv, the PreNorm backward and the residual add in front of mid_block1's backward
+};
+MidForms mid_forms(const Plan& p, const Arena& a, int B, int RT) {
+  auto rt = [&](const ResP& r) { return res_fwd_form(p.mid_c, p.mid_c, 0, r.res.cout != 0, B, RT, 1) == RES_FWD_RT && HID == 128; };
+  MidForms f;
+  f.qkv_fused = rt(p.mid1) && p.cond_dim == 8 && !DQ_DEV_FLAG("DQ_NO_MID_QKV", '1');  // (dev switch)
+  f.out_fused = rt(p.mid2) && !DQ_DEV_FLAG("DQ_NO_MID_OUT", '1');  // (dev switch)
+  f.pre_fused = rt(p.mid1) && a.bb_part_floats >= (int64_t)64 * B * p.mid_c && !DQ_DEV_FLAG("DQ_NO_MID_PRE", '1');  // (dev switch)
+  return f;
+}
+
+// mid_in -> mid2.out.  skip_ms1: the sampling prologue formed (and rotated) k already; prep_ok: the prepare launch filled the aligned weight slots
+int mid_forward(const Ctx& c, const float* rope, bool skip_ms1, bool prep_ok) {
+  const Plan& p = c.p;
+  const Arena& a = c.ar;
+  const int B = c.B, RT = c.RT;
+  const MidForms mf = mid_forms(p, a, B, RT);
+  // 16 channels (the default U-Net): PreNorm, to_qv, to_k and RoPE ride behind mid_block1 (k_res_rt.hip)
+  if (mf.qkv_fused) {
+    ResRtQkv q;
+    q.gn = c.prm(p.ag); q.wqv = c.prm(p.qv_w); q.xn = c.save ? c.w(a.xn) : nullptr; q.qv = c.w(a.qv); q.rope = rope;
+    if (!skip_ms1) { q.wk = c.prm(p.k_w); q.ms1f = c.w(a.ms1f); q.kk = c.w(a.kk); }
+    DQ_TRY(res_fwd(c, p.mid1, a.mid1, c.w(a.mid_in), p.mid_c, nullptr, 0, B, RT, 1, &q));
+  } else {
+    DQ_TRY(res_fwd(c, p.mid1, a.mid1, c.w(a.mid_in), p.mid_c, nullptr, 0, B, RT, 1));
+    // Residual(PreNorm(Attention(use_xattn))) (unet1d.py:552-567)
+    DQ_TRY(launch_rmsnorm_fwd(c.w(a.mid1.out), c.prm(p.ag), c.w(a.xn), p.mid_c, B, RT, c.s));
+    DQ_TRY(conv_plain_fwd(c, proj(p.qv_w, 2 * HID, p.mid_c), CONV_S1, c.w(a.xn), c.w(a.qv), B, RT, RT, prep_ok ? 0 : -1));
+    if (!skip_ms1) DQ_TRY(conv_plain_fwd(c, proj(p.k_w, HID, p.cond_dim), CONV_S1, c.w(a.ms1f), c.w(a.kk), B, RT, RT, prep_ok ? 1 : -1));
+    if (rope) {
+      // q = first 128 channels of each sample's 256; k rides in the same launch unless the sampling prologue rotated it already
+      if (!skip_ms1) DQ_TRY(launch_rope2(c.w(a.qv), (int64_t)2 * HID * RT, c.w(a.kk), (int64_t)HID * RT, rope, B, RT, 1.f, c.s));
+      else DQ_TRY(launch_rope(c.w(a.qv), rope, B, (int64_t)2 * HID * RT, RT, 1.f, c.s));
+    }
+  }
+  const int64_t qvbs = (int64_t)2 * HID * RT, kbs = (int64_t)HID * RT;
+  DQ_TRY(launch_attn_fwd(c.w(a.qv), qvbs, c.w(a.kk), kbs, c.w(a.qv) + kbs, qvbs, c.w(a.o), c.w(a.lse), B, RT, c.s));
+  // 16 channels: to_out (1x1 + bias) and the residual are formed in FRONT of mid_block2, inside its launch (k_res_rt.hip)
+  if (mf.out_fused) {
+    ResRtOut ao;
+    ao.o = c.w(a.o); ao.w = c.prm(p.ao_w); ao.b = c.prm(p.ao_b); ao.res = c.w(a.mid1.out); ao.out = c.w(a.attn_out);
+    return res_fwd(c, p.mid2, a.mid2, c.w(a.attn_out), p.mid_c, nullptr, 0, B, RT, 1, nullptr, &ao);
+  }
+  const ConvP ao = proj(p.ao_w, p.mid_c, HID);
+  if (conv_is_gemm(c, ao, CONV_S1, RT, RT) && (prep_ok || ((uintptr_t)c.prm(ao.w) & 15) == 0)) {
+    // to_out (1x1 conv, 128 -> mid_c channels, with bias) + the residual: attn_out = x ; attn_out += W o + b as a GEMM per sample
+    Gemm g;
+    DQ_TRY(gemm_weight(c, ao, &g.A, 2));
+    g.lda = HID; g.B = c.w(a.o); g.b_kmajor = 0; g.ldb = RT; g.C = c.w(a.attn_out); g.ldc = RT; g.M = p.mid_c; g.N = RT; g.K = HID;
+    g.batch = B; g.sBo = (int64_t)HID * RT; g.sCo = (int64_t)p.mid_c * RT; g.bias_m = c.prm(p.ao_b);
+    g.add = c.w(a.mid1.out); g.splits = 1;  // the residual is read by the epilogue (was: a copy launch + "+=")
+    DQ_TRY(launch_gemm(g, c.s));
+  } else {
+    ConvFwd f;
+    f.inA = c.w(a.o); f.cinA = HID; f.w = c.prm(p.ao_w); f.bias = c.prm(p.ao_b); f.cout = p.mid_c; f.K = 1;
+    f.rows = B; f.n_in = RT; f.n_out = RT; f.y_out = c.w(a.attn_out);
+    f.resA = c.w(a.mid1.out); f.rcinA = p.mid_c;
+    DQ_TRY(launch_conv_fwd(f, c.s));
+  }
+  return res_fwd(c, p.mid2, a.mid2, c.w(a.attn_out), p.mid_c, nullptr, 0, B, RT, 1);
+}
+
+// d(mid2.out) is complete; leaves d(mid_in) and all bottleneck parameter gradients (+=).  grad_x: the caller asked for d loss / d x: what would
+// ride on the side queue then stays on the main stream, as in unet_backward
+int mid_backward(const Ctx& c, const float* rope, bool grad_x) {
+  const Plan& p = c.p;
+  const Arena& a = c.ar;
+  const int B = c.B, RT = c.RT;
+  const MidForms mf = mid_forms(p, a, B, RT);
+  // 16 channels: d o = W_o^T d attn_out follows mid_block2's d x inside its launch (k_res_rt.hip); to_out's weight gradient stays below
+  if (mf.out_fused) {
+    ResRtOut ao;
+    ao.w = c.prm(p.ao_w); ao.d_o = c.g(a.o);
+    DQ_TRY(res_bwd(c, p.mid2, a.mid2, c.w(a.attn_out), c.g(a.attn_out), p.mid_c, nullptr, nullptr, 0, B, RT, 1, 0, 0, nullptr, nullptr, &ao));
+  } else {
+    DQ_TRY(res_bwd(c, p.mid2, a.mid2, c.w(a.attn_out), c.g(a.attn_out), p.mid_c, nullptr, nullptr, 0, B, RT, 1));
+  }
+  const int64_t qvbs = (int64_t)2 * HID * RT, kbs = (int64_t)HID * RT;
+  // to_out (1x1 + bias) and the residual
+  ConvP ao = proj(p.ao_w, p.mid_c, HID);
+  ao.b = p.ao_b;
+  const int ws_ok = (int)(p.downs.size() + p.ups.size()) <= LA_PREP_MAX ? 0 : -3;  // aligned weight slots as the forward of this step filled them (0: q|v, 1: k, 2: to_out)
+  DQ_TRY(conv_plain_bwd(c, ao, CONV_S1, c.w(a.o), c.g(a.attn_out), mf.out_fused ? nullptr : c.g(a.o), B, RT, RT, 0, ws_ok + 2));  // (fused: the weight / bias gradient only)
+  // (d mid1.out = d attn_out [the residual] + the PreNorm path: formed by the PreNorm backward below, which reads d attn_out as its addend --
+  // was a k_axpy launch here plus one behind that kernel)
+  DQ_TRY(launch_attn_bwd(c.w(a.qv), qvbs, c.w(a.kk), kbs, c.w(a.qv) + kbs, qvbs, c.w(a.o), c.g(a.o), c.w(a.lse), c.w(a.delta),
+                         c.g(a.qv), qvbs, c.g(a.kk), kbs, c.g(a.qv) + kbs, qvbs, B, RT, c.s));
+  const bool side = !grad_x && tail_fork_enabled();  // (the conditions under which the MS1 path's backward rides on the side queue too)
+  if (!mf.pre_fused) {
+    if (rope) {
+      DQ_TRY(launch_rope2(c.g(a.qv), (int64_t)2 * HID * RT, c.g(a.kk), (int64_t)HID * RT, rope, B, RT, -1.f, c.s));
+    }
+    DQ_TRY(conv_plain_bwd(c, proj(p.k_w, HID, p.cond_dim), CONV_S1, c.w(a.ms1f), c.g(a.kk), c.g(a.ms1f), B, RT, RT, 0, ws_ok + 1));
+    DQ_TRY(conv_plain_bwd(c, proj(p.qv_w, 2 * HID, p.mid_c), CONV_S1, c.w(a.xn), c.g(a.qv), c.g(a.xn), B, RT, RT, 0, ws_ok));
+    // PreNorm backward: xn = rmsnorm(mid1.out) * g  (pointwise kernel, no scale/shift, no activation)
+    BlockBwd nb;
+    // (du accumulates straight into d mid1.out -- the residual branch's gradient is there already: was a separate k_axpy launch behind this one)
+    nb.u = c.w(a.mid1.out); nb.dy = c.g(a.xn); nb.du = c.g(a.mid1.out); nb.accumulate = 1; nb.add_src = c.g(a.attn_out); nb.C = p.mid_c; nb.rows = B; nb.n = RT; nb.rows_per_sample = 1;
+    nb.g = c.prm(p.ag); nb.dg = c.dprm(p.ag);
+    nb.part = c.w(a.bb_part); nb.part_floats = a.bb_part_floats;
+    // (the gain's slot reduction feeds nothing on the chain: with the next side-stream flush.  The slot's other users: the MS1 path's backward, on
+    // the side stream behind it, and the input-affine backward at the end of the pass -- on the side stream too, or on the main stream behind the
+    // event that marks the side queue's state in front of the tail: unet_backward's `ev_ss`)
+    PartReduce gred;
+    const bool defer = side_open(c, side);
+    if (defer) nb.defer_reduce = &gred;
+    DQ_TRY(launch_block_bwd(nb, c.s));
+    if (defer && gred.part) DQ_TRY(on_side(c, true, [gred](hipStream_t ss) { return launch_part_reduce(gred, ss); }));  // (behind the flush's fork event whatever precedes it)
+    return res_bwd(c, p.mid1, a.mid1, c.w(a.mid_in), c.g(a.mid_in), p.mid_c, nullptr, nullptr, 0, B, RT, 1);
+  }
+  // 16 channels with a side queue at hand: RoPE^T, d xn = W_qv^T d qv, the PreNorm backward and the residual add run as the PROLOGUE of
+  // mid_block1's backward (k_res_rt.hip), which reads d q in the rotated frame.  What is left needs nothing of the main chain any more:
+  // RoPE^T in memory (the weight gradients of to_qv / to_k want d q, d k in the unrotated frame), d ms1f and both weight gradients go to
+  // the side queue -- behind the next flush's fork event, i.e. behind mid_block1's backward, which has read d q by then.
+  // (without a side queue -- the captured step, a plan without an owner -- the same launches follow mid_block1's backward on the main stream:
+  // the arithmetic, and with it every bit of the step, does not depend on the schedule)
+  const ConvP kp = proj(p.k_w, HID, p.cond_dim), qp = proj(p.qv_w, 2 * HID, p.mid_c);
+  auto mid_rest = [&a, rope, B, RT, kp, qp, ws_ok](const Ctx& cc) -> int {  // (on cc.s; weight gradients wherever cc sends them)
+    if (rope) DQ_TRY(launch_rope2(cc.g(a.qv), (int64_t)2 * HID * RT, cc.g(a.kk), (int64_t)HID * RT, rope, B, RT, -1.f, cc.s));
+    DQ_TRY(conv_plain_bwd(cc, kp, CONV_S1, cc.w(a.ms1f), cc.g(a.kk), cc.g(a.ms1f), B, RT, RT, 0, ws_ok + 1));
+    return conv_plain_bwd(cc, qp, CONV_S1, cc.w(a.xn), cc.g(a.qv), nullptr, B, RT, RT, 0, ws_ok);  // (weight gradient only)
+  };
+  ResRtPre q;
+  q.dqv = c.g(a.qv); q.wqv = c.prm(p.qv_w); q.x = c.w(a.mid1.out); q.gn = c.prm(p.ag); q.add = c.g(a.attn_out); q.rope = rope;
+  q.gn_part = c.w(a.bb_part); q.gn_part_floats = a.bb_part_floats;
+  int gblocks = 0;
+  DQ_TRY(res_bwd(c, p.mid1, a.mid1, c.w(a.mid_in), c.g(a.mid_in), p.mid_c, nullptr, nullptr, 0, B, RT, 1, 0, 0, &q, &gblocks));
+  PartReduce gred;  // d (PreNorm gain): the workgroups' sums in block order
+  gred.part = c.w(a.bb_part); gred.B = B; gred.gx = gblocks; gred.nv = p.mid_c; gred.nseg = 1;
+  gred.seg_start[0] = 0; gred.seg_len[0] = p.mid_c; gred.seg_dst[0] = c.dprm(p.ag);
+  // without the side queue: on the main stream (d ms1f is read there next); the two weight gradients go where they always go (wgrad_async: the
+  // side queue's shared partial-sum scratch belongs to one stream)
+  DQ_TRY(on_side(c, side, mid_rest));
+  return on_side(c, side, [gred](hipStream_t ss) { return launch_part_reduce(gred, ss); });
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // one launch per level for [the resample conv that produces the level's input] + the level's ResnetBlocks (k_level.hip)
 // ---------------------------------------------------------------------------------------------------------------
 bool level_kernels_enabled() {
@@ -1117,11 +1279,11 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
       f.ms1n_out = c.save ? c.w(a.ms1n) : nullptr; f.u_out = c.save ? c.w(a.ms1_u) : nullptr; f.a_out = c.w(a.ms1_a);
       DQ_TRY(launch_ms1_feat_fwd(f, ps));
     } else {
-    if (fwd_fork && !init_fused) DQ_TRY(launch_ms1_norm(attn_cond, cm, ca, c.w(a.ms1n), (int64_t)B * RT, ps));
-    ConvFwd f;
-    f.inA = c.w(a.ms1n); f.cinA = 1; f.w = c.prm(p.ms1_c0.w); f.bias = c.prm(p.ms1_c0.b); f.cout = p.cond_dim; f.K = 7;
-    f.rows = B; f.n_in = RT; f.n_out = RT; f.u_out = c.save ? c.w(a.ms1_u) : nullptr; f.y_out = c.w(a.ms1_a); f.act = ACT_GELU;
-    DQ_TRY(launch_conv_fwd(f, ps));
+      if (fwd_fork && !init_fused) DQ_TRY(launch_ms1_norm(attn_cond, cm, ca, c.w(a.ms1n), (int64_t)B * RT, ps));
+      ConvFwd f;
+      f.inA = c.w(a.ms1n); f.cinA = 1; f.w = c.prm(p.ms1_c0.w); f.bias = c.prm(p.ms1_c0.b); f.cout = p.cond_dim; f.K = 7;
+      f.rows = B; f.n_in = RT; f.n_out = RT; f.u_out = c.save ? c.w(a.ms1_u) : nullptr; f.y_out = c.w(a.ms1_a); f.act = ACT_GELU;
+      DQ_TRY(launch_conv_fwd(f, ps));
     }
     DQ_TRY(conv_plain_fwd(cs, p.ms1_c1, CONV_S1, c.w(a.ms1_a), c.w(a.ms1f), B, RT, RT));
   }
@@ -1165,60 +1327,7 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
     DQ_TRY(mid_forward_wide(c, rope, cur));
   } else {
     if (!mid_in_done) DQ_TRY(launch_fold(cur, c.w(a.mid_in), B, RT, p.mid_c, 1, 0, c.s));
-    // 16 channels (the default U-Net): PreNorm, to_qv, to_k and RoPE ride behind mid_block1 (k_res_rt.hip)
-    const bool qkv_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid1.res.cout != 0, B, RT, 1) == RES_FWD_RT && HID == 128 && p.cond_dim == 8 &&
-                           !DQ_DEV_FLAG("DQ_NO_MID_QKV", '1');  // (dev switch)
-    if (qkv_fused) {
-      ResRtQkv q;
-      q.gn = c.prm(p.ag); q.wqv = c.prm(p.qv_w); q.xn = c.save ? c.w(a.xn) : nullptr; q.qv = c.w(a.qv); q.rope = rope;
-      if (!skip_ms1) { q.wk = c.prm(p.k_w); q.ms1f = c.w(a.ms1f); q.kk = c.w(a.kk); }
-      DQ_TRY(res_fwd(c, p.mid1, a.mid1, c.w(a.mid_in), p.mid_c, nullptr, 0, B, RT, 1, &q));
-    } else {
-      DQ_TRY(res_fwd(c, p.mid1, a.mid1, c.w(a.mid_in), p.mid_c, nullptr, 0, B, RT, 1));
-    }
-    bool out_fused = false;
-    {
-      // Residual(PreNorm(Attention(use_xattn))) (unet1d.py:552-567)
-      if (!qkv_fused) {
-      DQ_TRY(launch_rmsnorm_fwd(c.w(a.mid1.out), c.prm(p.ag), c.w(a.xn), p.mid_c, B, RT, c.s));
-      DQ_TRY(conv_plain_fwd(c, proj(p.qv_w, 2 * HID, p.mid_c), CONV_S1, c.w(a.xn), c.w(a.qv), B, RT, RT, prep_ok ? 0 : -1));
-      if (!skip_ms1) DQ_TRY(conv_plain_fwd(c, proj(p.k_w, HID, p.cond_dim), CONV_S1, c.w(a.ms1f), c.w(a.kk), B, RT, RT, prep_ok ? 1 : -1));
-      if (rope) {
-        // q = first 128 channels of each sample's 256; k rides in the same launch unless the sampling prologue rotated it already
-        if (!skip_ms1) DQ_TRY(launch_rope2(c.w(a.qv), (int64_t)2 * HID * RT, c.w(a.kk), (int64_t)HID * RT, rope, B, RT, 1.f, c.s));
-        else DQ_TRY(launch_rope(c.w(a.qv), rope, B, (int64_t)2 * HID * RT, RT, 1.f, c.s));
-      }
-      }
-      const int64_t qvbs = (int64_t)2 * HID * RT, kbs = (int64_t)HID * RT;
-      DQ_TRY(launch_attn_fwd(c.w(a.qv), qvbs, c.w(a.kk), kbs, c.w(a.qv) + kbs, qvbs, c.w(a.o), c.w(a.lse), B, RT, c.s));
-      // 16 channels: to_out (1x1 + bias) and the residual are formed in FRONT of mid_block2, inside its launch (k_res_rt.hip)
-      out_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid2.res.cout != 0, B, RT, 1) == RES_FWD_RT && HID == 128 && !DQ_DEV_FLAG("DQ_NO_MID_OUT", '1');  // (dev switch)
-      if (!out_fused) {
-      const ConvP ao = proj(p.ao_w, p.mid_c, HID);
-      if (conv_is_gemm(c, ao, CONV_S1, RT, RT) && (prep_ok || ((uintptr_t)c.prm(ao.w) & 15) == 0)) {
-        // to_out (1x1 conv, 128 -> mid_c channels, with bias) + the residual: attn_out = x ; attn_out += W o + b as a GEMM per sample
-        Gemm g;
-        DQ_TRY(gemm_weight(c, ao, &g.A, 2));
-        g.lda = HID; g.B = c.w(a.o); g.b_kmajor = 0; g.ldb = RT; g.C = c.w(a.attn_out); g.ldc = RT; g.M = p.mid_c; g.N = RT; g.K = HID;
-        g.batch = B; g.sBo = (int64_t)HID * RT; g.sCo = (int64_t)p.mid_c * RT; g.bias_m = c.prm(p.ao_b);
-        g.add = c.w(a.mid1.out); g.splits = 1;  // the residual is read by the epilogue (was: a copy launch + "+=")
-        DQ_TRY(launch_gemm(g, c.s));
-      } else {
-        ConvFwd f;
-        f.inA = c.w(a.o); f.cinA = HID; f.w = c.prm(p.ao_w); f.bias = c.prm(p.ao_b); f.cout = p.mid_c; f.K = 1;
-        f.rows = B; f.n_in = RT; f.n_out = RT; f.y_out = c.w(a.attn_out);
-        f.resA = c.w(a.mid1.out); f.rcinA = p.mid_c;
-        DQ_TRY(launch_conv_fwd(f, c.s));
-      }
-          }
-    }
-    if (out_fused) {
-      ResRtOut ao;
-      ao.o = c.w(a.o); ao.w = c.prm(p.ao_w); ao.b = c.prm(p.ao_b); ao.res = c.w(a.mid1.out); ao.out = c.w(a.attn_out);
-      DQ_TRY(res_fwd(c, p.mid2, a.mid2, c.w(a.attn_out), p.mid_c, nullptr, 0, B, RT, 1, nullptr, &ao));
-    } else {
-      DQ_TRY(res_fwd(c, p.mid2, a.mid2, c.w(a.attn_out), p.mid_c, nullptr, 0, B, RT, 1));
-    }
+    DQ_TRY(mid_forward(c, rope, skip_ms1, prep_ok));
     if (!(is_tiny_up(0) && tiny_upc(0).in_folded)) DQ_TRY(launch_fold(c.w(a.mid2.out), c.w(a.mid_back), B, RT, p.mid_c, 0, 0, c.s));
   }
   cur = c.w(a.mid_back);
@@ -1276,7 +1385,7 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
 int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, float cm, float ca, const DevTables& dt,
                   const float* grad_out, float* grad_x) {
   Ctx::LaDefer la_defer;
-  std::vector<Ctx::SideItem> side_items;
+  std::vector<Ctx::SideFn> side_items;
   std::vector<ResWgReduce> wg_items;
   Ctx c = c_in;
   c.la_defer = &la_defer;
@@ -1284,13 +1393,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
   if (c.owner) c.side_defer = &side_items;
   if (c.loss_sum.out) {
     const Ctx::LossSum ls = c.loss_sum;
-    if (c.side_defer) {
-      Ctx::SideItem it{};
-      it.kind = 3; it.fn = [ls](hipStream_t ss) { return launch_sum_partials(ls.partials, ls.count, ls.scale, ls.out, ss); };
-      side_items.push_back(it);
-    } else {
-      DQ_TRY(launch_sum_partials(ls.partials, ls.count, ls.scale, ls.out, c.s));
-    }
+    DQ_TRY(on_side(c, true, [ls](hipStream_t ss) { return launch_sum_partials(ls.partials, ls.count, ls.scale, ls.out, ss); }));
   }
   const Plan& p = c.p;
   const Arena& a = c.ar;
@@ -1299,19 +1402,12 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
   if (c.owner && c.owner->twin_zeroed == c.G) c.owner->twin_zeroed = nullptr;
   else DQ_TRY(launch_zero(c.G, a.zero_floats, c.s));
   // the ResnetBlock / resample-conv slot reductions collected so far as one side-stream item
-  auto wg_to_side = [&c, &wg_items, &side_items]() {
+  auto wg_to_side = [&c, &wg_items]() -> int {
     const bool wg_off = DQ_DEV_FLAG("DQ_NO_LA_FLUSH_SIDE", '1');  // (dev switch)
-    if (wg_off || !c.owner || !c.side_defer || !tail_fork_enabled() || wg_items.empty()) return;
-    std::vector<ResWgReduce> part(wg_items);
-    Ctx::SideItem it{};
-    it.kind = 3;
-    it.fn = [part](hipStream_t ss) {
-      for (size_t i = 0; i < part.size(); i += RES_WG_REDUCE_MAX)
-        if (int rc = launch_res_wg_reduce(part.data() + i, (int)std::min<size_t>(RES_WG_REDUCE_MAX, part.size() - i), ss)) return rc;
-      return 0;
-    };
-    side_items.push_back(it);
-    wg_items.clear();
+    if (wg_items.empty() || !side_open(c, !wg_off && tail_fork_enabled())) return 0;  // (else they stay for the end of the pass)
+    std::vector<ResWgReduce> part;
+    part.swap(wg_items);
+    return on_side(c, true, [part](hipStream_t ss) { return res_wg_reduce_all(part, ss); });
   };
   // the two levels with rows of one position: their backward data path in one launch each (k_tiny.hip), when their forward ran there
   TinyBwd tb_up, tb_dn;
@@ -1342,14 +1438,14 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
     if (ui == 0 && use_tb_up && tb_up.up_w)  // (the tiny backward applies Upsample^T itself: only the conv's weight / bias gradient is left, on the side stream)
       DQ_TRY(conv_plain_bwd(c, l.resample, CONV_UP, c.w(b.la), c.g(b.rs), nullptr, R, l.n, l.n_next, 0));
     else
-    DQ_TRY(resample_bwd(c, l.resample, l.last ? LEVEL_PRE_S1 : LEVEL_PRE_UP, b, l.n, l.n_next, 0));  // only writer of d la (up): store
+      DQ_TRY(resample_bwd(c, l.resample, l.last ? LEVEL_PRE_S1 : LEVEL_PRE_UP, b, l.n, l.n_next, 0));  // only writer of d la (up): store
     if (ui == 0 && use_tb_up) {
       DQ_TRY(tiny_bwd_run(c, tb_up, true));  // LinearAttention + both ResnetBlocks; the input gradient lands in the bottleneck's layout
     } else {
-    DQ_TRY(la_bwd(c, l.la, b, c.w(b.r1.out), c.g(b.la), c.g(b.r1.out), R, l.n, L + ui));
-    // the up path is the first writer of its own tensors AND of the skip tensors (the down path accumulates into them later)
-    DQ_TRY(res_bwd(c, l.r1, b.r1, c.w(b.r0.out), c.g(b.r0.out), cx, c.w(a.downs[lv].r0.out), c.g(a.downs[lv].r0.out), cs, R, l.n, RT, 1, 1));
-    DQ_TRY(res_bwd(c, l.r0, b.r0, c.w(in_off), c.g(in_off), cx, c.w(a.downs[lv].la), c.g(a.downs[lv].la), cs, R, l.n, RT, 1, 1));
+      DQ_TRY(la_bwd(c, l.la, b, c.w(b.r1.out), c.g(b.la), c.g(b.r1.out), R, l.n, L + ui));
+      // the up path is the first writer of its own tensors AND of the skip tensors (the down path accumulates into them later)
+      DQ_TRY(res_bwd(c, l.r1, b.r1, c.w(b.r0.out), c.g(b.r0.out), cx, c.w(a.downs[lv].r0.out), c.g(a.downs[lv].r0.out), cs, R, l.n, RT, 1, 1));
+      DQ_TRY(res_bwd(c, l.r0, b.r0, c.w(in_off), c.g(in_off), cx, c.w(a.downs[lv].la), c.g(a.downs[lv].la), cs, R, l.n, RT, 1, 1));
     }
     // the resample-conv and ResnetBlock weight gradients of two levels behind one event: an event record holds the main queue for ~6 us
     // (kernel trace)
@@ -1360,97 +1456,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
     DQ_TRY(mid_backward_wide(c, rope));
   } else {
     if (!use_tb_up) DQ_TRY(launch_fold(c.g(a.mid_back), c.g(a.mid2.out), B, RT, p.mid_c, 1, 1, c.s));  // (the tiny backward wrote d mid2.out itself)
-    // 16 channels: d o = W_o^T d attn_out follows mid_block2's d x inside its launch (k_res_rt.hip); to_out's weight gradient stays below
-    const bool out_bwd_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid2.res.cout != 0, B, RT, 1) == RES_FWD_RT && HID == 128 && !DQ_DEV_FLAG("DQ_NO_MID_OUT", '1');  // (dev switch)
-    if (out_bwd_fused) {
-      ResRtOut ao;
-      ao.w = c.prm(p.ao_w); ao.d_o = c.g(a.o);
-      DQ_TRY(res_bwd(c, p.mid2, a.mid2, c.w(a.attn_out), c.g(a.attn_out), p.mid_c, nullptr, nullptr, 0, B, RT, 1, 0, 0, nullptr, nullptr, &ao));
-    } else {
-      DQ_TRY(res_bwd(c, p.mid2, a.mid2, c.w(a.attn_out), c.g(a.attn_out), p.mid_c, nullptr, nullptr, 0, B, RT, 1));
-    }
-    bool mid_pre = false;  // the back of the attention front rides in mid_block1's backward
-    std::function<int(const Ctx&)> mid_rest;  // ... and what the main chain then no longer waits for
-    {
-      const int64_t qvbs = (int64_t)2 * HID * RT, kbs = (int64_t)HID * RT;
-      // to_out (1x1 + bias) and the residual
-      ConvP ao = proj(p.ao_w, p.mid_c, HID);
-      ao.b = p.ao_b;
-      const int ws_ok = (int)(p.downs.size() + p.ups.size()) <= LA_PREP_MAX ? 0 : -3;  // aligned weight slots as the forward of this step filled them (0: q|v, 1: k, 2: to_out)
-      DQ_TRY(conv_plain_bwd(c, ao, CONV_S1, c.w(a.o), c.g(a.attn_out), out_bwd_fused ? nullptr : c.g(a.o), B, RT, RT, 0, ws_ok + 2));  // (fused: the weight / bias gradient only)
-      // (d mid1.out = d attn_out [the residual] + the PreNorm path: formed by the PreNorm backward below, which reads d attn_out as its addend --
-      // was a k_axpy launch here plus one behind that kernel)
-      DQ_TRY(launch_attn_bwd(c.w(a.qv), qvbs, c.w(a.kk), kbs, c.w(a.qv) + kbs, qvbs, c.w(a.o), c.g(a.o), c.w(a.lse), c.w(a.delta),
-                             c.g(a.qv), qvbs, c.g(a.kk), kbs, c.g(a.qv) + kbs, qvbs, B, RT, c.s));
-      // 16 channels with a side queue at hand: RoPE^T, d xn = W_qv^T d qv, the PreNorm backward and the residual add run as the PROLOGUE of
-      // mid_block1's backward (k_res_rt.hip), which reads d q in the rotated frame.  What is left needs nothing of the main chain any more:
-      // RoPE^T in memory (the weight gradients of to_qv / to_k want d q, d k in the unrotated frame), d ms1f and both weight gradients go to
-      // the side queue -- behind the next flush's fork event, i.e. behind mid_block1's backward, which has read d q by then.
-      // (without a side queue -- the captured step, a plan without an owner -- the same launches follow mid_block1's backward on the main stream:
-      // the arithmetic, and with it every bit of the step, does not depend on the schedule)
-      const bool pre_fused = res_fwd_form(p.mid_c, p.mid_c, 0, p.mid1.res.cout != 0, B, RT, 1) == RES_FWD_RT && HID == 128 &&
-                             a.bb_part_floats >= (int64_t)64 * B * p.mid_c && !DQ_DEV_FLAG("DQ_NO_MID_PRE", '1');  // (dev switch)
-      if (pre_fused) {
-        const ConvP kp = proj(p.k_w, HID, p.cond_dim), qp = proj(p.qv_w, 2 * HID, p.mid_c);
-        mid_rest = [&a, rope, B, RT, kp, qp, ws_ok](const Ctx& cc) -> int {  // (on cc.s; weight gradients wherever cc sends them)
-          if (rope) DQ_TRY(launch_rope2(cc.g(a.qv), (int64_t)2 * HID * RT, cc.g(a.kk), (int64_t)HID * RT, rope, B, RT, -1.f, cc.s));
-          DQ_TRY(conv_plain_bwd(cc, kp, CONV_S1, cc.w(a.ms1f), cc.g(a.kk), cc.g(a.ms1f), B, RT, RT, 0, ws_ok + 1));
-          return conv_plain_bwd(cc, qp, CONV_S1, cc.w(a.xn), cc.g(a.qv), nullptr, B, RT, RT, 0, ws_ok);  // (weight gradient only)
-        };
-      } else {
-      if (rope) {
-        DQ_TRY(launch_rope2(c.g(a.qv), (int64_t)2 * HID * RT, c.g(a.kk), (int64_t)HID * RT, rope, B, RT, -1.f, c.s));
-      }
-      DQ_TRY(conv_plain_bwd(c, proj(p.k_w, HID, p.cond_dim), CONV_S1, c.w(a.ms1f), c.g(a.kk), c.g(a.ms1f), B, RT, RT, 0, ws_ok + 1));
-      DQ_TRY(conv_plain_bwd(c, proj(p.qv_w, 2 * HID, p.mid_c), CONV_S1, c.w(a.xn), c.g(a.qv), c.g(a.xn), B, RT, RT, 0, ws_ok));
-      // PreNorm backward: xn = rmsnorm(mid1.out) * g  (pointwise kernel, no scale/shift, no activation)
-      BlockBwd nb;
-      // (du accumulates straight into d mid1.out -- the residual branch's gradient is there already: was a separate k_axpy launch behind this one)
-      nb.u = c.w(a.mid1.out); nb.dy = c.g(a.xn); nb.du = c.g(a.mid1.out); nb.accumulate = 1; nb.add_src = c.g(a.attn_out); nb.C = p.mid_c; nb.rows = B; nb.n = RT; nb.rows_per_sample = 1;
-      nb.g = c.prm(p.ag); nb.dg = c.dprm(p.ag);
-      nb.part = c.w(a.bb_part); nb.part_floats = a.bb_part_floats;
-      // (the gain's slot reduction feeds nothing on the chain: with the next side-stream flush.  The slot's other users: the MS1 path's backward, on
-      // the side stream behind it, and the input-affine backward at the end of the pass -- on the side stream too, or on the main stream behind the
-      // event that marks the side queue's state in front of the tail: unet_backward's `ev_ss`)
-      PartReduce gred;
-      const bool defer = c.owner && c.side_defer && !grad_x && tail_fork_enabled();
-      if (defer) nb.defer_reduce = &gred;
-      DQ_TRY(launch_block_bwd(nb, c.s));
-      if (defer && gred.part) {
-        Ctx::SideItem it{};
-        it.kind = 3; it.fn = [gred](hipStream_t ss) { return launch_part_reduce(gred, ss); };  // (kind 3: behind the flush's fork event whatever precedes it)
-        c.side_defer->push_back(it);
-      }
-          }
-      mid_pre = pre_fused;
-    }
-    if (mid_pre) {
-      ResRtPre q;
-      q.dqv = c.g(a.qv); q.wqv = c.prm(p.qv_w); q.x = c.w(a.mid1.out); q.gn = c.prm(p.ag); q.add = c.g(a.attn_out); q.rope = rope;
-      q.gn_part = c.w(a.bb_part); q.gn_part_floats = a.bb_part_floats;
-      int gblocks = 0;
-      DQ_TRY(res_bwd(c, p.mid1, a.mid1, c.w(a.mid_in), c.g(a.mid_in), p.mid_c, nullptr, nullptr, 0, B, RT, 1, 0, 0, &q, &gblocks));
-      PartReduce gred;  // d (PreNorm gain): the workgroups' sums in block order
-      gred.part = c.w(a.bb_part); gred.B = B; gred.gx = gblocks; gred.nv = p.mid_c; gred.nseg = 1;
-      gred.seg_start[0] = 0; gred.seg_len[0] = p.mid_c; gred.seg_dst[0] = c.dprm(p.ag);
-      if (c.owner && c.side_defer && !grad_x && tail_fork_enabled()) {  // (the conditions under which the MS1 path's backward rides on the side queue too)
-        Ctx sc = c;
-        sc.owner = nullptr; sc.side_defer = nullptr;
-        Ctx::SideItem it{};
-        it.kind = 3;
-        it.fn = [sc, mid_rest](hipStream_t ss) mutable { sc.s = ss; return mid_rest(sc); };
-        c.side_defer->push_back(it);
-        it.fn = [gred](hipStream_t ss) { return launch_part_reduce(gred, ss); };
-        c.side_defer->push_back(it);
-      } else {
-        // on the main stream (d ms1f is read there next); the two weight gradients go where they always go (wgrad_async: the side queue's
-        // shared partial-sum scratch belongs to one stream)
-        DQ_TRY(mid_rest(c));
-        DQ_TRY(launch_part_reduce(gred, c.s));
-      }
-    } else {
-      DQ_TRY(res_bwd(c, p.mid1, a.mid1, c.w(a.mid_in), c.g(a.mid_in), p.mid_c, nullptr, nullptr, 0, B, RT, 1));
-    }
+    DQ_TRY(mid_backward(c, rope, grad_x != nullptr));
     if (!use_tb_dn) DQ_TRY(launch_fold(c.g(a.mid_in), c.g(a.downs[L - 1].rs), B, RT, p.mid_c, 0, 0, c.s));  // first and only writer: store (the tiny backward reads d mid_in itself)
   }
   // MS1 feature path (unet1d.py:1120-1130): its gradient d ms1f is final behind the bottleneck (to_k is its only consumer) and nothing on
@@ -1470,15 +1476,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
     }
     return conv_plain_bwd(cc, p.ms1_c0, CONV_S1, cc.w(a.ms1n), cc.g(a.ms1_u), nullptr, B, RT, RT, 0);
   };
-  if (c.owner && c.side_defer && tail_fork_enabled()) {
-    Ctx sc = c;
-    sc.owner = nullptr; sc.side_defer = nullptr;
-    Ctx::SideItem it{};
-    it.kind = 3; it.fn = [sc, ms1_bwd](hipStream_t ss) mutable { sc.s = ss; return ms1_bwd(sc); };
-    side_items.push_back(it);
-  } else {
-    DQ_TRY(ms1_bwd(c));
-  }
+  DQ_TRY(on_side(c, tail_fork_enabled(), ms1_bwd));
   // down path, reversed
   for (int lv = L - 1; lv >= 0; --lv) {
     const LevelP& l = p.downs[lv];
@@ -1491,7 +1489,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
       continue;
     }
     if (!(lv == L - 2 && use_tb_dn))  // (that Downsample's backward rode in the launch above)
-    DQ_TRY(resample_bwd(c, l.resample, l.last ? LEVEL_PRE_S1 : LEVEL_PRE_DOWN, b, l.n, l.n_next, 1));
+      DQ_TRY(resample_bwd(c, l.resample, l.last ? LEVEL_PRE_S1 : LEVEL_PRE_DOWN, b, l.n, l.n_next, 1));
     if (lv == 0) DQ_TRY(side_flush(c));  // (last level: the resample conv's weight gradient under the LinearAttention backward, not in the tail)
     DQ_TRY(la_bwd(c, l.la, b, c.w(b.r1.out), c.g(b.la), c.g(b.r1.out), R, l.n, lv));
     DQ_TRY(res_bwd(c, l.r1, b.r1, c.w(b.r0.out), c.g(b.r0.out), C, nullptr, nullptr, 0, R, l.n, RT));
@@ -1503,7 +1501,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
     if (lv == 2 && p.mz <= 64) {  // (short rows only: the sweep kernels of longer rows use the whole slot buffer per layer)
       DQ_TRY(la_flush_side(c));
       // the ResnetBlock / resample-conv slot reductions collected so far ride along (every block has its own slots and its own parameters)
-      wg_to_side();
+      DQ_TRY(wg_to_side());
     }
     if (side_flush_here(lv)) DQ_TRY(side_flush(c));
   }
@@ -1516,7 +1514,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
                                   a.bb_part_floats, cc.s);
   };
   const bool tail_swap = !DQ_DEV_FLAG("DQ_NO_TAIL_SWAP", '1');  // (dev switch)
-  if (tail_swap && c.owner && c.side_defer && !grad_x && tail_fork_enabled()) {
+  if (side_open(c, tail_swap && !grad_x && tail_fork_enabled())) {
     // The chain that ends the pass is  d h0 -> d cat0 (init conv, data) -> d(scale, shift) of init_cond_proj -> time-embedding backward -> norm -> update;
     // the LinearAttention slot reductions and the init conv's weight gradient only have to be there for the norm.  So the MAIN queue runs that chain and
     // the side queue those (they stood on the main queue in front of the join, the chain's first half on the side queue behind the
@@ -1535,20 +1533,11 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
     DQ_TRY(launch_prep_inputs_bwd(c.g(a.cat0), init_cond, cm, ca, c.g(a.ss), p.ss_total, p.ss_init, B, RT, p.mz, c.w(a.bb_part), a.bb_part_floats,
                                   c.s));
     DQ_TRY(la_flush(c));  // (nothing left unless DQ_NO_LA_FLUSH_SIDE)
-    for (size_t i = 0; i < wg_items.size(); i += RES_WG_REDUCE_MAX)
-      DQ_TRY(launch_res_wg_reduce(wg_items.data() + i, (int)std::min<size_t>(RES_WG_REDUCE_MAX, wg_items.size() - i), c.s));
+    DQ_TRY(res_wg_reduce_all(wg_items, c.s));
     DQ_TRY(launch_time_embed_bwd(p, dt, c.P, c.dP, c.w(a.tbuf), c.g(a.ss), B, c.s));
     return join_side(c);
   }
-  if (c.owner && c.side_defer && !grad_x && tail_fork_enabled()) {
-    Ctx sc = c;
-    sc.owner = nullptr; sc.side_defer = nullptr;
-    Ctx::SideItem it{};
-    it.kind = 3; it.fn = [sc, init_bwd](hipStream_t ss) mutable { sc.s = ss; return init_bwd(sc); };
-    side_items.push_back(it);
-  } else {
-    DQ_TRY(init_bwd(c));
-  }
+  DQ_TRY(on_side(c, !grad_x && tail_fork_enabled(), init_bwd));
   if (grad_x) {
     // channel 1 of d(cat0) is d loss / d x
     DQ_HIP_OK(hipMemcpy2DAsync(grad_x, sizeof(float) * p.mz, c.g(a.cat0) + p.mz, sizeof(float) * 2 * p.mz, sizeof(float) * p.mz, R,
@@ -1559,8 +1548,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
   // ~80 us) start only when the ~100 us reduce had finished -- an exposed tail in front of the join
   DQ_TRY(side_flush(c));
   DQ_TRY(la_flush(c));
-  for (size_t i = 0; i < wg_items.size(); i += RES_WG_REDUCE_MAX)  // (one launch for the network's <= 32 such blocks)
-    DQ_TRY(launch_res_wg_reduce(wg_items.data() + i, (int)std::min<size_t>(RES_WG_REDUCE_MAX, wg_items.size() - i), c.s));
+  DQ_TRY(res_wg_reduce_all(wg_items, c.s));
   DQ_TRY(join_side(c));
   // time embedding: all scale/shift heads + the MLP -- after the join: the per-sample d(scale, shift) of the fused ResnetBlocks are
   // summed on the side stream
@@ -1599,63 +1587,28 @@ int side_mark(const Ctx& c, hipEvent_t* ev) {
   return 0;
 }
 
+// (a context with an owner always has the queue: unet_backward installs it, and what the queue runs has neither)
 int wgrad_async(const Ctx& c, const ConvWgrad& w) {
-  dq_plan* pl = c.owner;
-  if (!pl) return launch_conv_wgrad(w, c.s);
-  if (c.side_defer) {
-    Ctx::SideItem it{};
-    it.kind = 0; it.w[0] = w; it.count = 1;
-    c.side_defer->push_back(it);
-    return 0;
-  }
-  DQ_TRY(ensure_side(pl));
-  hipEvent_t ev = pl->events[pl->ev_next++ % dq_plan::NUM_EVENTS];
-  DQ_HIP_OK(hipEventRecord(ev, c.s));
-  DQ_HIP_OK(hipStreamWaitEvent(pl->side_stream, ev, 0));
-  pl->side_used = true;
-  return launch_conv_wgrad(w, pl->side_stream);
+  return on_side(c, true, [w](hipStream_t s) { return launch_conv_wgrad(w, s); });
 }
 
 int wgrad_async_multi(const Ctx& c, ConvWgrad* w, int count) {
-  dq_plan* pl = c.owner;
-  if (!pl) return launch_conv_wgrad_multi(w, count, c.s);
-  if (c.side_defer) {
-    Ctx::SideItem it{};
-    it.kind = 1; it.count = count;
-    for (int i = 0; i < count; ++i) it.w[i] = w[i];
-    c.side_defer->push_back(it);
-    return 0;
-  }
-  if (!pl->side_stream) {  // created by the first wgrad_async of a plan (the head convs come before any ResnetBlock)
-    for (int i = 0; i < count; ++i) DQ_TRY(wgrad_async(c, w[i]));
-    return 0;
-  }
-  hipEvent_t ev = pl->events[pl->ev_next++ % dq_plan::NUM_EVENTS];
-  DQ_HIP_OK(hipEventRecord(ev, c.s));
-  DQ_HIP_OK(hipStreamWaitEvent(pl->side_stream, ev, 0));
-  pl->side_used = true;
-  return launch_conv_wgrad_multi(w, count, pl->side_stream);
+  DQ_REQUIRE(count >= 1 && count <= 3, "wgrad_async_multi: one to three convs");
+  std::array<ConvWgrad, 3> ws;
+  std::copy(w, w + count, ws.begin());
+  return on_side(c, true, [ws, count](hipStream_t s) { return launch_conv_wgrad_multi(ws.data(), count, s); });
 }
 
 // issue the queued side-stream work behind one event recorded now on the main stream
 int side_flush(const Ctx& c) {
   dq_plan* pl = c.owner;
   if (!pl || !c.side_defer || c.side_defer->empty()) return 0;
-  std::vector<Ctx::SideItem> items;
-  items.swap(*c.side_defer);
-  Ctx now = c;
-  now.side_defer = nullptr;  // the calls below launch for real
-  bool first = true;
-  for (Ctx::SideItem& it : items) {
-    if (it.kind == 2) {
-      hipStream_t rs = pl->side_stream ? pl->side_stream : c.s;
-      DQ_TRY(launch_part_reduce(it.red, rs));
-      continue;
-    }
-    if (first) { DQ_TRY(fork_side(now)); first = false; }  // one event for the whole group (creates the stream on first use)
-    if (it.kind == 0) DQ_TRY(launch_conv_wgrad(it.w[0], pl->side_stream));
-    else if (it.kind == 1) DQ_TRY(launch_conv_wgrad_multi(it.w, it.count, pl->side_stream));
-    else DQ_TRY(it.fn(pl->side_stream));
+  std::vector<Ctx::SideFn> items;
+  items.swap(*c.side_defer);  // (nothing an item calls can re-enter the queue)
+  bool forked = false;
+  for (Ctx::SideFn& it : items) {
+    if (it.forks && !forked) { DQ_TRY(fork_side(c)); forked = true; }  // one event for the whole group (creates the stream on first use)
+    DQ_TRY(it.fn(pl->side_stream ? pl->side_stream : c.s));  // (no side stream yet: only in front of a group's first forking item)
   }
   return 0;
 }
