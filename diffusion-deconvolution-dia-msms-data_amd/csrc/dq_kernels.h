@@ -36,6 +36,16 @@ int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, f
 int launch_adamw_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm,
                           const float* lr_dev, double b1, double b2, double eps, double wd, int* step_dev, float* gnorm_out, hipStream_t s);
 
+// both steps with an exponential moving average of the parameters updated in the same pass: ema <- ema + w_t (p_new - ema),
+// w_t = (float)(1 - beta_t), beta_t = min(ema_decay, (1 + t) / (10 + t)) with ema_warmup, ema_decay without (p, m, v, the norm: bit for bit
+// the results of the two above; the device variant keeps w_t at index 3 of its scalars)
+int launch_adamw_clip_ema(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm, double lr,
+                          double b1, double b2, double eps, double wd, int step, float* gnorm_out, float* ema, float ema_decay,
+                          int ema_warmup, hipStream_t s);
+int launch_adamw_clip_ema_dev(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm,
+                              const float* lr_dev, double b1, double b2, double eps, double wd, int* step_dev, float* gnorm_out, float* ema,
+                              float ema_decay, int ema_warmup, hipStream_t s);
+
 int launch_axpy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst += src
 int launch_zero(float* dst, int64_t n, hipStream_t s);  // dst = 0 (a kernel, not a memset node)
 int launch_copy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst = src (a kernel, not a memcpy node)

@@ -1809,6 +1809,23 @@ int dq_adamw_clip_step_dev(float* params, const float* grads, float* exp_avg, fl
                                step_dev, gnorm_out, (hipStream_t)stream);
 }
 
+int dq_adamw_clip_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch,
+                           float grad_scale, float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           int step, float* gnorm_out, float* ema, float ema_decay, int ema_warmup, void* stream) {
+  DQ_REQUIRE(params && grads && exp_avg && exp_avg_sq && scratch, "dq_adamw_clip_ema_step: null argument");
+  return launch_adamw_clip_ema(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, lr, beta1, beta2, eps, weight_decay,
+                               step, gnorm_out, ema, ema_decay, ema_warmup, (hipStream_t)stream);
+}
+
+int dq_adamw_clip_ema_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch,
+                               float grad_scale, float max_norm, const float* lr_dev, double beta1, double beta2, double eps,
+                               double weight_decay, int* step_dev, float* gnorm_out, float* ema, float ema_decay, int ema_warmup,
+                               void* stream) {
+  DQ_REQUIRE(params && grads && exp_avg && exp_avg_sq && scratch && lr_dev && step_dev, "dq_adamw_clip_ema_step_dev: null argument");
+  return launch_adamw_clip_ema_dev(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, lr_dev, beta1, beta2, eps,
+                                   weight_decay, step_dev, gnorm_out, ema, ema_decay, ema_warmup, (hipStream_t)stream);
+}
+
 int dq_set_option(const char* key, int64_t value) {
   const int i = option_index(key);
   DQ_REQUIRE(i >= 0, "dq_set_option: unknown key");

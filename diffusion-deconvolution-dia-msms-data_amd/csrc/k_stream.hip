@@ -495,4 +495,121 @@ int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, f
   return 0;
 }
 
+// ---- K11 + EMA: the same step, and e <- e + w (p_new - e) from the p the update has just formed, in the same pass over the buffers
+// (36 B / param: the four reads and three writes above, plus one read and one write of e; a lerp over the flat buffer afterwards reads p
+// again: 40 B and a launch).  Per element the AdamW arithmetic is k_adamw_clip's expression for expression (-ffp-contract=off: no
+// contraction either way), so p, m, v are its results bit for bit; the EMA is one fp32 subtraction and one fmaf.
+__device__ __forceinline__ void adamw_ema_elem(float& p, float g, float& m, float& v, float& e, float coef, float decay, float step_size,
+                                               float one_m_b1, float b2, float one_m_b2, float eps, float bc2_sqrt, float ema_w) {
+  const float gi = g * coef;
+  float pi = p * decay;
+  const float mo = m;
+  const float mi = mo + one_m_b1 * (gi - mo);
+  const float vi = fmaf(one_m_b2 * gi, gi, b2 * v);
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  pi -= step_size * (mi / denom);
+  p = pi; m = mi; v = vi;
+  e = fmaf(ema_w, pi - e, e);
+}
+// hyp null: the step's scalars are the launch arguments (host variant); else hyp[0..3] = decay, step_size, bc2_sqrt, ema_w (device variant).
+// 16-byte accesses when all five buffers are 16-byte aligned (the way k_sumsq picks its path: the 191 M-parameter transformer's step is a
+// bandwidth job of 36 B / param), scalar accesses for the tail and for every other alignment.
+__global__ void __launch_bounds__(256) k_adamw_clip_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, float* __restrict__ e, int64_t n,
+                                                        const float* __restrict__ partials, int n_partials, float gscale, float max_norm,
+                                                        const float* __restrict__ hyp, float decay, float step_size, float bc2_sqrt,
+                                                        float ema_w, float one_m_b1, float b2, float one_m_b2, float eps,
+                                                        float* __restrict__ gnorm_out) {
+  __shared__ float s_coef;
+  if (threadIdx.x < 64) {
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < n_partials; i += 64) acc += partials[i];
+    acc = wave_sum(acc);
+    if (threadIdx.x == 0) {
+      const float nrm = sqrtf(acc);
+      const float c = max_norm / (nrm + 1e-6f);
+      s_coef = (max_norm > 0.f) ? fminf(c, 1.0f) : 1.0f;
+      if (blockIdx.x == 0 && gnorm_out) gnorm_out[0] = nrm;
+    }
+  }
+  __syncthreads();
+  const float coef = s_coef * gscale;
+  if (hyp) { decay = hyp[0]; step_size = hyp[1]; bc2_sqrt = hyp[2]; ema_w = hyp[3]; }
+  const bool aligned = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)e) & 15) == 0);
+  const int64_t n4 = aligned ? n / 4 : 0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t first = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  float4* p4 = reinterpret_cast<float4*>(p); const float4* g4 = reinterpret_cast<const float4*>(g);
+  float4* m4 = reinterpret_cast<float4*>(m); float4* v4 = reinterpret_cast<float4*>(v); float4* e4 = reinterpret_cast<float4*>(e);
+  for (int64_t i = first; i < n4; i += stride) {
+    float4 pp = p4[i], mm = m4[i], vv = v4[i], ee = e4[i];
+    const float4 gg = g4[i];
+    adamw_ema_elem(pp.x, gg.x, mm.x, vv.x, ee.x, coef, decay, step_size, one_m_b1, b2, one_m_b2, eps, bc2_sqrt, ema_w);
+    adamw_ema_elem(pp.y, gg.y, mm.y, vv.y, ee.y, coef, decay, step_size, one_m_b1, b2, one_m_b2, eps, bc2_sqrt, ema_w);
+    adamw_ema_elem(pp.z, gg.z, mm.z, vv.z, ee.z, coef, decay, step_size, one_m_b1, b2, one_m_b2, eps, bc2_sqrt, ema_w);
+    adamw_ema_elem(pp.w, gg.w, mm.w, vv.w, ee.w, coef, decay, step_size, one_m_b1, b2, one_m_b2, eps, bc2_sqrt, ema_w);
+    p4[i] = pp; m4[i] = mm; v4[i] = vv; e4[i] = ee;
+  }
+  for (int64_t i = n4 * 4 + first; i < n; i += stride) {
+    float pi = p[i], mi = m[i], vi = v[i], ei = e[i];
+    adamw_ema_elem(pi, g[i], mi, vi, ei, coef, decay, step_size, one_m_b1, b2, one_m_b2, eps, bc2_sqrt, ema_w);
+    p[i] = pi; m[i] = mi; v[i] = vi; e[i] = ei;
+  }
+}
+
+// beta_t = min(beta, (1 + t) / (10 + t)) with warm-up, beta without; w_t = (float)(1 - beta_t), in double on the host and in k_adamw_ema_hyper
+__host__ __device__ inline float ema_weight(double beta, int warmup, int t) {
+  const double bt = warmup ? fmin(beta, (1.0 + (double)t) / (10.0 + (double)t)) : beta;
+  return (float)(1.0 - bt);
+}
+// k_adamw_hyper's three scalars (the same expressions) and the EMA weight behind them at hyp[3]
+__global__ void k_adamw_ema_hyper(int* __restrict__ step, const float* __restrict__ lr_dev, double b1, double b2, double wd, double ema_beta,
+                                  int ema_warmup, float* __restrict__ hyp) {
+  const int t = step[0] + 1;
+  step[0] = t;
+  const double lr = (double)lr_dev[0] + (double)lr_dev[1];
+  const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
+  hyp[0] = (float)(1.0 - lr * wd);
+  hyp[1] = (float)(lr / bc1);
+  hyp[2] = (float)sqrt(bc2);
+  hyp[3] = ema_weight(ema_beta, ema_warmup, t);
+}
+
+static bool ema_decay_ok(float beta) { return beta >= 0.f && beta < 1.f; }  // (false for NaN)
+
+int launch_adamw_clip_ema_dev(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm,
+                              const float* lr_dev, double b1, double b2, double eps, double wd, int* step_dev, float* gnorm_out, float* ema,
+                              float ema_decay, int ema_warmup, hipStream_t s) {
+  DQ_REQUIRE(n > 0 && lr_dev && step_dev, "adamw: need n > 0, the device learning rate and the device step counter");
+  DQ_REQUIRE(ema, "adamw + ema: the EMA buffer is null");
+  DQ_REQUIRE(ema_decay_ok(ema_decay), "adamw + ema: ema_decay must satisfy 0 <= ema_decay < 1");
+  const int grid = (int)std::min<int64_t>(cdiv(n, 256), MSE_MAX_BLOCKS - 8);
+  float* hyp = partials + (MSE_MAX_BLOCKS - 8);
+  hipLaunchKernelGGL(k_adamw_ema_hyper, dim3(1), dim3(1), 0, s, step_dev, lr_dev, b1, b2, wd, (double)ema_decay, ema_warmup, hyp);
+  DQ_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_sumsq, dim3(grid), dim3(256), 0, s, g, n, gscale, partials);
+  DQ_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_adamw_clip_ema, dim3(grid), dim3(256), 0, s, p, g, m, v, ema, n, partials, grid, gscale, max_norm, hyp, 0.f, 0.f, 0.f,
+                     0.f, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, gnorm_out);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_adamw_clip_ema(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm, double lr,
+                          double b1, double b2, double eps, double wd, int step, float* gnorm_out, float* ema, float ema_decay,
+                          int ema_warmup, hipStream_t s) {
+  DQ_REQUIRE(n > 0 && step >= 1, "adamw: need n > 0 and step >= 1");
+  DQ_REQUIRE(ema, "adamw + ema: the EMA buffer is null");
+  DQ_REQUIRE(ema_decay_ok(ema_decay), "adamw + ema: ema_decay must satisfy 0 <= ema_decay < 1");
+  const int grid = (int)std::min<int64_t>(cdiv(n, 256), MSE_MAX_BLOCKS - 8);
+  hipLaunchKernelGGL(k_sumsq, dim3(grid), dim3(256), 0, s, g, n, gscale, partials);
+  DQ_LAUNCH_CHECK();
+  const double bc1 = 1.0 - std::pow(b1, step), bc2 = 1.0 - std::pow(b2, step);
+  hipLaunchKernelGGL(k_adamw_clip_ema, dim3(grid), dim3(256), 0, s, p, g, m, v, ema, n, partials, grid, gscale, max_norm,
+                     (const float*)nullptr, (float)(1.0 - lr * wd), (float)(lr / bc1), (float)std::sqrt(bc2),
+                     ema_weight((double)ema_decay, ema_warmup, step), (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, gnorm_out);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace dq

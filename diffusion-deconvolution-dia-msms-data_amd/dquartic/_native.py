@@ -51,6 +51,10 @@ PROTOTYPES = {
     "dq_get_option_effective": (c_int64, [c_char_p]),
     "dq_adamw_clip_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float, c_float, c_double,
                                    c_double, c_double, c_double, c_double, c_int, c_void_p, c_void_p]),
+    "dq_adamw_clip_ema_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float, c_float, c_double,
+                                       c_double, c_double, c_double, c_double, c_int, c_void_p, c_void_p, c_float, c_int, c_void_p]),
+    "dq_adamw_clip_ema_step_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float, c_float, c_void_p,
+                                           c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p]),
     "dq_train_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                               c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "dq_ms1_loss_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p,

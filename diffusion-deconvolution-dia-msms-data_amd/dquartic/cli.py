@@ -109,6 +109,7 @@ def train(config_path, parquet_directory, ms2_data_path, ms1_data_path, batch_si
     dm = DDIMDiffusionModel(model_class=net, num_timesteps=m["num_timesteps"], beta_schedule_type=m["beta_schedule_type"],
                             pred_type=m["pred_type"], auto_normalize=m["auto_normalize"], ms1_loss_weight=m["ms1_loss_weight"],
                             device=device)
+    enable_ema_from_config(dm, m)
     wb = None
     if config["wandb"]["use_wandb"] and rank == 0:
         try:
@@ -125,6 +126,18 @@ def train(config_path, parquet_directory, ms2_data_path, ms1_data_path, batch_si
         wb.finish()
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def enable_ema_from_config(dm, m) -> bool:
+    """``model.ema_decay`` (absent or null: off) and ``model.ema_warmup`` (default true) of a train config: keep an exponential moving
+    average of the weights inside the optimiser step (``ModelInterface.enable_ema``).  The optimiser is created here, at the configured
+    learning rate, because the average lives in it; ``train`` then finds it in place.  Returns whether EMA was enabled."""
+    decay = m.get("ema_decay")
+    if decay is None:
+        return False
+    dm._set_lr(m["learning_rate"])
+    dm.enable_ema(float(decay), bool(m.get("ema_warmup", True)))
+    return True
 
 
 @cli.command()

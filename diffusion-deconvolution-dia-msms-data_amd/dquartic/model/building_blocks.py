@@ -196,7 +196,7 @@ class CustomTransformer(_FlatBuffers, nn.Module):
             ws = self.workspace(B, S1, S2, training)
         sin, cos, freqs = self.tables(max(S1, S2), xs.device)
         out = torch.empty_like(xs)
-        N.check(N.lib().dq_tfm_fwd(self._tfm, N.ptr(self._flat), N.ptr(sin), N.ptr(cos), N.ptr(freqs), N.ptr(xs), N.ptr(ts), N.ptr(cs),
+        N.check(N.lib().dq_tfm_fwd(self._tfm, N.ptr(self.read_params(training)), N.ptr(sin), N.ptr(cos), N.ptr(freqs), N.ptr(xs), N.ptr(ts), N.ptr(cs),
                                    N.ptr(out), 1 if training else 0, N.ptr(ws), ws.numel(), B, S1, S2, N.stream_ptr()), "dq_tfm_fwd")
         return out
 

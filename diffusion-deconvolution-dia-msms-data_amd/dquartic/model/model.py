@@ -191,7 +191,7 @@ class DDIMDiffusionModel(ModelInterface):
         f32 = lambda v: v.detach().to(torch.float32).contiguous()
         B, RT, MZ = x_T.shape
         x_T, c2, c1 = f32(x_T), f32(ms2_cond), f32(net._check_inputs(ms1_cond, B, RT))
-        flat = net.flat_params
+        flat = net.read_params()  # (the averaged weights inside ModelInterface.ema_scope())
         ws = net.workspace(B, RT, False)
         ts = self.sampler_timesteps(self.num_timesteps, num_steps).to(torch.int32)
         ts_c = (ctypes.c_int32 * num_steps)(*ts.tolist())
@@ -264,7 +264,7 @@ class DDIMDiffusionModel(ModelInterface):
             noise = torch.randn_like(x_0)
         t = t.to(device=x_0.device, dtype=torch.int64).contiguous()
         noise = f32(noise)
-        flat = net.flat_params
+        flat = net.read_params(training=True)  # (raises inside ema_scope(): the average is not trained)
         grads = net.flat_grads(zero=zero_grads)
         ws = net.workspace(B, RT, True)
         loss = torch.empty((), dtype=torch.float32, device=x_0.device)

@@ -12,8 +12,10 @@ calls on flat buffers (``dq_train_step`` + ``dq_adamw_clip_step``) instead of au
 initialised the flat gradient is all-reduced (RCCL) between them; wandb / plotting are optional and imported lazily;
 the "latest" checkpoint goes next to ``checkpoint_path`` ('.' when it has no directory, not the filesystem root).
 """
+import contextlib
 import math
 import os
+from collections import OrderedDict
 from typing import List
 
 import numpy as np
@@ -79,9 +81,15 @@ class CallbackHandler:
 class FlatAdamW(torch.optim.Optimizer):
     """``torch.optim.AdamW`` semantics (torch defaults) executed by ``dq_adamw_clip_step`` on the network's flat
     parameter / gradient buffers, with the global-norm clip of ``clip_grad_norm_`` folded in.  ``state_dict()`` has the
-    torch AdamW layout (per-parameter ``step, exp_avg, exp_avg_sq``), so checkpoints interchange with the reference."""
+    torch AdamW layout (per-parameter ``step, exp_avg, exp_avg_sq``), so checkpoints interchange with the reference.
 
-    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_norm=10.0):
+    ``ema_decay`` (None: off) keeps an exponential moving average of the weights in a flat buffer with the layout of ``flat_params``, updated
+    by the optimiser kernel itself from the parameter it has just formed (``dq_adamw_clip_ema_step`` / ``_dev``):
+    after step t, ``e += w_t (p - e)`` with ``w_t = float32(1 - beta_t)``, ``beta_t = min(ema_decay, (1 + t) / (10 + t))`` under
+    ``ema_warmup`` and ``ema_decay`` without.  The decay reaches the kernel as a float32.  The average is not part of ``state_dict()``
+    (that stays torch's AdamW layout): ``ema_state_dict()`` / ``load_ema_state_dict()`` carry it."""
+
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_norm=10.0, ema_decay=None, ema_warmup=True):
         self.net = net
         params = [p for _, p in net.trainable_named()]
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -91,6 +99,66 @@ class FlatAdamW(torch.optim.Optimizer):
         self._step = 0
         self._step_dev = self._lr_dev = None   # device copies of the step count / learning rate (step_dev(): graph-replayable step)
         self._lr_dev_value = None
+        self.ema_decay, self.ema_warmup, self._ema = None, True, None
+        if ema_decay is not None:
+            self.enable_ema(ema_decay, ema_warmup)
+
+    # ---- exponential moving average of the weights
+    def enable_ema(self, decay, warmup=True):
+        """Start (or re-parametrise) the average.  A new average is a copy of the parameters at this moment; an existing one is kept."""
+        if isinstance(decay, bool) or not isinstance(decay, (int, float, np.floating, np.integer)):
+            raise TypeError(f"FlatAdamW: ema_decay must be a number, got {decay!r}")
+        decay = float(decay)
+        if not (0.0 <= decay < 1.0 and float(np.float32(decay)) < 1.0):  # (also false for NaN; the kernel takes the decay as a float32)
+            raise ValueError(f"FlatAdamW: ema_decay must satisfy 0 <= ema_decay < 1 (as a float32), got {decay!r}")
+        self.ema_decay, self.ema_warmup = decay, bool(warmup)
+        if self._ema is None:
+            self._ema = self.net.flat_params.detach().clone()
+        return self
+
+    def disable_ema(self):
+        self.ema_decay, self._ema = None, None
+        return self
+
+    @property
+    def ema_enabled(self) -> bool:
+        return self.ema_decay is not None
+
+    def ema_buffer(self) -> torch.Tensor:
+        """The flat average, on the parameters' device (it follows them like the moments do)."""
+        if self._ema is None:
+            raise RuntimeError("FlatAdamW: EMA is not enabled (enable_ema(decay) or ema_decay=...)")
+        flat = self.net.flat_params
+        if self._ema.device != flat.device:
+            self._ema = self._ema.to(flat.device)
+        return self._ema
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """The average becomes a copy of the current parameters (after weights were loaded from a file that has no average)."""
+        self.ema_buffer().copy_(self.net.flat_params)
+
+    def ema_state_dict(self):
+        """``{parameter name: view of the average}`` with the keys, order and shapes of the model's ``state_dict()``: it loads into the
+        reference's module with ``load_state_dict``.  Entries the optimiser does not train (the U-Net's RoPE frequencies) are the model's own."""
+        ema = self.ema_buffer()
+        views = {name: ema[o:o + math.prod(shape)].view(shape) for name, o, shape in self.net._layout}
+        return OrderedDict((k, views.get(k, v)) for k, v in self.net.state_dict().items())
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd):
+        ema = self.ema_buffer()
+        missing = [name for name, _, _ in self.net._layout if name not in sd]
+        if missing:
+            raise KeyError(f"load_ema_state_dict: missing {missing[:3]}{' ...' if len(missing) > 3 else ''}")
+        for name, o, shape in self.net._layout:
+            src = torch.as_tensor(sd[name])
+            if tuple(src.shape) != tuple(shape):
+                raise ValueError(f"load_ema_state_dict: {name} has shape {tuple(src.shape)}, the network's is {tuple(shape)}")
+            ema[o:o + math.prod(shape)].copy_(src.reshape(-1))
+
+    def _ema_args(self):
+        return N.ptr(self.ema_buffer()), float(self.ema_decay), 1 if self.ema_warmup else 0
 
     def _buffers(self):
         flat = self.net.flat_params
@@ -98,6 +166,8 @@ class FlatAdamW(torch.optim.Optimizer):
             old_m, old_v = self._m, self._v
             self._m = torch.zeros_like(flat) if old_m is None else old_m.to(flat.device)
             self._v = torch.zeros_like(flat) if old_v is None else old_v.to(flat.device)
+            if self._ema is not None:
+                self._ema = self._ema.to(flat.device)
             self._scratch = torch.empty(1024, dtype=torch.float32, device=flat.device)
             self._gnorm = torch.zeros((), dtype=torch.float32, device=flat.device)
             self._publish_state()
@@ -115,6 +185,12 @@ class FlatAdamW(torch.optim.Optimizer):
         grads = self.net.flat_grads()
         g = self.param_groups[0]
         self._step += 1
+        if self.ema_enabled:
+            N.check(N.lib().dq_adamw_clip_ema_step(N.ptr(flat), N.ptr(grads), N.ptr(self._m), N.ptr(self._v), flat.numel(), N.ptr(self._scratch),
+                                                   float(self.grad_scale), float(self.max_norm), float(g["lr"]), float(g["betas"][0]),
+                                                   float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), int(self._step),
+                                                   N.ptr(self._gnorm), *self._ema_args(), N.stream_ptr()), "dq_adamw_clip_ema_step")
+            return None
         N.check(N.lib().dq_adamw_clip_step(N.ptr(flat), N.ptr(grads), N.ptr(self._m), N.ptr(self._v), flat.numel(), N.ptr(self._scratch),
                                            float(self.grad_scale), float(self.max_norm), float(g["lr"]), float(g["betas"][0]),
                                            float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), int(self._step),
@@ -149,6 +225,13 @@ class FlatAdamW(torch.optim.Optimizer):
         g = self.param_groups[0]
         if count:
             self._step += 1
+        if self.ema_enabled:
+            N.check(N.lib().dq_adamw_clip_ema_step_dev(N.ptr(flat), N.ptr(grads), N.ptr(self._m), N.ptr(self._v), flat.numel(),
+                                                       N.ptr(self._scratch), float(self.grad_scale), float(self.max_norm), N.ptr(self._lr_dev),
+                                                       float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                                                       N.ptr(self._step_dev), N.ptr(self._gnorm), *self._ema_args(), N.stream_ptr()),
+                    "dq_adamw_clip_ema_step_dev")
+            return None
         N.check(N.lib().dq_adamw_clip_step_dev(N.ptr(flat), N.ptr(grads), N.ptr(self._m), N.ptr(self._v), flat.numel(), N.ptr(self._scratch),
                                                float(self.grad_scale), float(self.max_norm), N.ptr(self._lr_dev), float(g["betas"][0]),
                                                float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), N.ptr(self._step_dev),
@@ -245,6 +328,7 @@ class TrainStepGraph:
     def __init__(self, dm, x_0, ms2_cond, ms1_cond, ms1_loss_weight=0.0, keep_side=False):
         self.dm, self.opt, self.net = dm, dm.optimizer, dm.model
         self.key = (tuple(x_0.shape), tuple(ms1_cond.shape), float(ms1_loss_weight or 0.0), float(dm.optimizer.grad_scale))
+        self._ema_key = (dm.optimizer.ema_decay, dm.optimizer.ema_warmup)  # launch arguments of the captured optimiser step
         self.x0, self.c2, self.c1 = (torch.empty_like(v, dtype=torch.float32).copy_(v) for v in (x_0, ms2_cond, ms1_cond))
         self.w = float(ms1_loss_weight or 0.0)
         self.keep_side = bool(keep_side)  # keep the fork / join inside the captured step (measured slower than the single chain: off)
@@ -254,7 +338,8 @@ class TrainStepGraph:
         # warm-up on a side stream (workspaces, occupancy queries, lazy stream creation: nothing may allocate during capture) -- on a
         # SNAPSHOT of the training state: parameters, moments, step count and the generator state are put back afterwards, so that
         # building the graph is not a training step
-        snap = (self.net.flat_params.detach().clone(), self.opt._m.clone(), self.opt._v.clone(), self.opt._step, torch.cuda.get_rng_state(x_0.device))
+        snap = (self.net.flat_params.detach().clone(), self.opt._m.clone(), self.opt._v.clone(), self.opt._step, torch.cuda.get_rng_state(x_0.device),
+                self.opt.ema_buffer().clone() if self.opt.ema_enabled else None)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -264,6 +349,8 @@ class TrainStepGraph:
         torch.cuda.synchronize()
         with torch.no_grad():
             self.net.flat_params.copy_(snap[0]); self.opt._m.copy_(snap[1]); self.opt._v.copy_(snap[2])
+            if snap[5] is not None:
+                self.opt.ema_buffer().copy_(snap[5])
         self.opt._step = snap[3]
         self.opt.sync_step_dev()
         torch.cuda.set_rng_state(snap[4], x_0.device)
@@ -272,17 +359,18 @@ class TrainStepGraph:
         # the ones whose identity carries the training state are part of matches(): a `.to()` / storage-replacing load re-creates the flat
         # buffers, and a graph that still pointed at the old ones would train dead memory
         B, RT = int(x_0.shape[0]), int(x_0.shape[1])
-        self._held = self._live_buffers() + (self.net.workspace(B, RT, True), self.opt._scratch, self.opt._gnorm, self.opt._lr_dev,
-                                             self.opt._step_dev, dm.alpha_bars)
+        self._ws = self.net.workspace(B, RT, True)
+        self._held = self._live_buffers() + (self._ws, self.opt._scratch, self.opt._gnorm, self.opt._lr_dev, self.opt._step_dev, dm.alpha_bars)
         self._ptrs = tuple(t.data_ptr() for t in self._live_buffers())
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss = self._body(count=False)
-        if tuple(t.data_ptr() for t in self._live_buffers()) != self._ptrs or self.net.workspace(B, RT, True) is not self._held[4]:
+        if tuple(t.data_ptr() for t in self._live_buffers()) != self._ptrs or self.net.workspace(B, RT, True) is not self._ws:
             raise RuntimeError("TrainStepGraph: a training buffer moved while the step was being captured")
 
     def _live_buffers(self):
-        return (self.net.flat_params, self.net.flat_grads(), self.opt._m, self.opt._v)
+        live = (self.net.flat_params, self.net.flat_grads(), self.opt._m, self.opt._v)
+        return live + (self.opt.ema_buffer(),) if self.opt.ema_enabled else live  # (EMA switched on or off since the capture: no match)
 
     def _body(self, count):
         loss = self.dm.train_step_fused(self.x0, self.c2, self.c1, zero_grads=True, ms1_loss_weight=self.w)
@@ -291,6 +379,7 @@ class TrainStepGraph:
 
     def matches(self, x_0, ms1_cond, ms1_loss_weight, grad_scale):
         return (self.key == (tuple(x_0.shape), tuple(ms1_cond.shape), float(ms1_loss_weight or 0.0), float(grad_scale))
+                and self._ema_key == (self.opt.ema_decay, self.opt.ema_warmup)
                 and tuple(t.data_ptr() for t in self._live_buffers()) == self._ptrs)
 
     def step(self, x_0, ms2_cond, ms1_cond):
@@ -406,6 +495,8 @@ class ModelInterface(object):
                 self.optimizer._buffers()
                 d.broadcast(self.optimizer._m, src=src)
                 d.broadcast(self.optimizer._v, src=src)
+                if self.optimizer.ema_enabled:
+                    d.broadcast(self.optimizer.ema_buffer(), src=src)
                 step = torch.tensor([float(self.optimizer._step)], device=self.optimizer._m.device)
                 d.broadcast(step, src=src)
                 self.optimizer._step = int(step.item())
@@ -453,6 +544,11 @@ class ModelInterface(object):
             self.model.load_state_dict(ck["model_state_dict"])
             if self.optimizer is not None and ck.get("optimizer_state_dict") is not None:
                 self.optimizer.load_state_dict(ck["optimizer_state_dict"])
+            if self.ema_enabled:  # the file's average, or -- a file written without one -- a fresh average of the loaded weights
+                if ck.get("ema_state_dict") is not None:
+                    self.optimizer.load_ema_state_dict(ck["ema_state_dict"])
+                else:
+                    self.optimizer.reset_ema()
             if scheduler is not None and ck.get("scheduler_state_dict") is not None:
                 scheduler.lambda_lr.load_state_dict(ck["scheduler_state_dict"])
             epoch, best_loss = ck["epoch"], ck["best_loss"]
@@ -463,18 +559,65 @@ class ModelInterface(object):
         return epoch, best_loss, scheduler
 
     def save_checkpoint(self, scheduler, epoch, best_loss, checkpoint_path):
-        torch.save({"epoch": epoch, "model_state_dict": self.model.state_dict(), "optimizer_state_dict": self.optimizer.state_dict(),
-                    "scheduler_state_dict": (scheduler.lambda_lr.state_dict() if scheduler is not None else None),
-                    "best_loss": best_loss}, checkpoint_path)
+        ck = {"epoch": epoch, "model_state_dict": self.model.state_dict(), "optimizer_state_dict": self.optimizer.state_dict(),
+              "scheduler_state_dict": (scheduler.lambda_lr.state_dict() if scheduler is not None else None), "best_loss": best_loss}
+        if self.ema_enabled:  # (only then: without EMA the file has the reference's keys and nothing else)
+            ck.update(ema_state_dict=self.optimizer.ema_state_dict(), ema_decay=self.optimizer.ema_decay, ema_warmup=self.optimizer.ema_warmup)
+        torch.save(ck, checkpoint_path)
 
-    def predict(self, dataloader, mixture_weights=(0.5, 0.5), num_steps=1000):
-        """Reference :630-668: one dict per batch with the first item's prediction (``_predict_one_batch`` returns item 0)."""
+    # ---- exponential moving average of the weights (new work: the reference has none)
+    @property
+    def ema_enabled(self) -> bool:
+        return isinstance(self.optimizer, FlatAdamW) and self.optimizer.ema_enabled
+
+    def enable_ema(self, decay: float = 0.999, warmup: bool = True):
+        """Keep an exponential moving average of the weights, updated inside the fused optimiser step (``FlatAdamW``).  Valid once the
+        optimiser exists (``_set_optimizer`` / ``_set_lr``); ``ema_scope()`` / ``predict`` then evaluate the averaged weights."""
+        if not isinstance(self.optimizer, FlatAdamW):
+            raise RuntimeError("enable_ema needs the FlatAdamW optimiser of a native network (call it after _set_optimizer / _set_lr); "
+                               f"the optimiser is {type(self.optimizer).__name__}")
+        self.optimizer.enable_ema(decay, warmup)
+
+    def disable_ema(self):
+        if isinstance(self.optimizer, FlatAdamW):
+            self.optimizer.disable_ema()
+
+    def _flat_net(self):
+        """The module that owns the flat buffers and makes the native calls (the transformer behind its adapter)."""
+        return getattr(self.model, "transformer", self.model)
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """Inside the scope every native call of the network reads the EMA buffer in place of ``flat_params`` -- by pointer, nothing is
+        copied: ``UNet1d.forward`` under ``no_grad``, ``sample()`` (``dq_ddim_sample``, eager and captured), the ``CustomTransformer``'s
+        forward behind its adapter.  A forward that would record autograd history and a train step raise inside it (the average is not
+        trained).  The training weights are never written, so on exit they are what they were.  The plan keeps ONE captured sampling
+        graph, keyed by the parameter pointer among other things: alternating sampling inside and outside the scope recaptures it each
+        time; sample from one side in a row."""
+        if not self.ema_enabled:
+            raise RuntimeError("ema_scope: EMA is not enabled (enable_ema)")
+        net = self._flat_net()
+        net.flat_params  # (a pending .to() / load re-creates the flat buffer here, outside the scope)
+        prev = net._param_override
+        net._param_override = self.optimizer.ema_buffer()
+        try:
+            yield self
+        finally:
+            net._param_override = prev
+
+    def _ema_or_null_scope(self, use_ema):
+        use = self.ema_enabled if use_ema is None else bool(use_ema)
+        return self.ema_scope() if use else contextlib.nullcontext()
+
+    def predict(self, dataloader, mixture_weights=(0.5, 0.5), num_steps=1000, use_ema=None):
+        """Reference :630-668: one dict per batch with the first item's prediction (``_predict_one_batch`` returns item 0).
+        ``use_ema``: sample from the averaged weights; None (default) = when EMA is enabled."""
         self.model.eval()
         preds = []
         for ms2_1, ms1_1, ms2_2, ms1_2 in dataloader:
             x_0, ms1_cond = ms2_1.to(self.device), ms1_1.to(self.device)
             ms2_cond = (ms2_1 * mixture_weights[0]).to(self.device) + (ms2_2 * mixture_weights[1]).to(self.device)
-            pred, _ = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps)
+            pred, _ = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, use_ema=use_ema)
             preds.append({"ms2_1": ms2_1.cpu().numpy(), "ms1_1": ms1_1.cpu().numpy(), "mixture": ms2_cond.cpu().numpy(), "pred": pred})
         return np.array(preds, dtype=object)
 
@@ -589,10 +732,11 @@ class ModelInterface(object):
             self.optimizer.step()
         return loss.item() if sync else loss.detach()
 
-    def _predict_one_batch(self, x_0, ms2_cond=None, ms1_cond=None, num_steps=1000):
-        """Reference :1125-1150: eval + no_grad + sample(randn_like(x_0)); returns item 0 of the batch as numpy."""
+    def _predict_one_batch(self, x_0, ms2_cond=None, ms1_cond=None, num_steps=1000, use_ema=None):
+        """Reference :1125-1150: eval + no_grad + sample(randn_like(x_0)); returns item 0 of the batch as numpy.  ``use_ema`` as in
+        ``predict``."""
         self.model.eval()
-        with torch.no_grad():
+        with torch.no_grad(), self._ema_or_null_scope(use_ema):
             sample, pred_noise = self.sample(torch.randn_like(x_0), ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps)
         return sample[0].cpu().detach().numpy(), pred_noise[0].cpu().detach().numpy()
 

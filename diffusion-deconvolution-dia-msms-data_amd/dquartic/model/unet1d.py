@@ -55,6 +55,21 @@ class _FlatBuffers:
 
     _flat_stale = True
     _grad_stale = True
+    _param_override = None  # ModelInterface.ema_scope(): a flat buffer of the same layout the forward-only native calls read instead
+
+    def read_params(self, training: bool = False) -> torch.Tensor:
+        """The flat buffer a native call reads its weights from: ``flat_params``, or inside ``ModelInterface.ema_scope()`` the averaged
+        weights.  ``training``: the call saves activations for a backward or is a train step -- not on the average."""
+        flat = self._flat_buffer()
+        ov = self._param_override
+        if ov is None:
+            return flat
+        if training:
+            raise RuntimeError("inside ema_scope() the network reads the averaged weights, which are not trained: a forward that records "
+                               "autograd history (use torch.no_grad()) or a train step cannot run there")
+        if ov.device != flat.device or ov.numel() != flat.numel() or ov.dtype != torch.float32 or not ov.is_contiguous():
+            raise RuntimeError("ema_scope: the averaged weights no longer match the network's flat parameter buffer (moved or resized inside the scope)")
+        return ov
 
     def _apply(self, fn, recurse=True):
         self._flat_stale = True
@@ -352,7 +367,7 @@ class UNet1d(_FlatBuffers, nn.Module):
             ws = self.workspace(B, RT, training)
         out = torch.empty_like(xs)
         fr = self.rope_freqs()
-        N.check(N.lib().dq_unet_fwd(self._plan, N.ptr(self._flat), N.ptr(fr), N.ptr(xs), N.ptr(ts), 0, N.ptr(ic), N.ptr(ac),
+        N.check(N.lib().dq_unet_fwd(self._plan, N.ptr(self.read_params(training)), N.ptr(fr), N.ptr(xs), N.ptr(ts), 0, N.ptr(ic), N.ptr(ac),
                                     cond_mul, cond_add, N.ptr(out), 1 if training else 0, N.ptr(ws), ws.numel(), B, RT,
                                     N.stream_ptr()), "dq_unet_fwd")
         return out

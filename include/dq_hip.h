@@ -47,7 +47,7 @@ const char* dq_last_error(void);
  * dq_linattn_fwd_prepared.  10: dq_set_option, dq_get_option, dq_debug_side_tail_store (later, additive: dq_plan_set_final_act,
  * dq_plan_final_act, dq_get_option_effective, dq_resblock_forms, dq_linattn_forms, dq_linattn_bwd_store, dq_plan_create_ex,
  * dq_plan_attn_cond_channels, dq_ms1_feat_fwd, dq_ms1_feat_wgrad, dq_ms1_feat_wgrad_scratch_floats).  11: dq_conv_bwd,
- * dq_conv_bwd_workspace_floats, dq_conv_bwd_forms. */
+ * dq_conv_bwd_workspace_floats, dq_conv_bwd_forms (later, additive: dq_adamw_clip_ema_step, dq_adamw_clip_ema_step_dev). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 11
 
@@ -160,6 +160,23 @@ int dq_adamw_clip_step(float* params, const float* grads, float* exp_avg, float*
 int dq_adamw_clip_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch, float grad_scale,
                            float max_norm, const float* lr_dev, double beta1, double beta2, double eps, double weight_decay, int* step_dev,
                            float* gnorm_out, void* stream);
+/* Both steps with an exponential moving average of the parameters kept in the same pass over the buffers (no reference counterpart: the
+ * reference trains without one).  ema: n device floats with the layout of params.  After the AdamW update of step t (1-based; the device
+ * variant: the incremented *step_dev), with p the updated parameter:
+ *   beta_t = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay      (double; ema_decay is promoted from the float passed)
+ *   w_t    = (float)(1.0 - beta_t)
+ *   ema    = fmaf(w_t, p - ema, ema)                                           (one fp32 subtraction, one fmaf)
+ * 0 <= ema_decay < 1, anything else (NaN included) and a null ema are errors and launch nothing.  params, exp_avg, exp_avg_sq and
+ * gnorm_out receive bit for bit what dq_adamw_clip_step / dq_adamw_clip_step_dev write, for any n and alignment; the update runs with
+ * 16-byte accesses when params, grads, exp_avg, exp_avg_sq and ema are all 16-byte aligned.  The device variant keeps w_t behind its three
+ * scalars (scratch[1016 + 3]).  scratch as above. */
+int dq_adamw_clip_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch,
+                           float grad_scale, float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           int step, float* gnorm_out, float* ema, float ema_decay, int ema_warmup, void* stream);
+int dq_adamw_clip_ema_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch,
+                               float grad_scale, float max_norm, const float* lr_dev, double beta1, double beta2, double eps,
+                               double weight_decay, int* step_dev, float* gnorm_out, float* ema, float ema_decay, int ema_warmup,
+                               void* stream);
 /* on = 0: the backward's remaining weight-gradient launches run on the caller's stream instead of the plan's side stream (a captured train
  * step is then one chain; the fork / join inside a graph was measured slower than the chain).  Default 1. */
 int dq_plan_set_side_stream(dq_plan* plan, int on);
