@@ -16,6 +16,13 @@ int launch_ddim_step(const float* x_t, const float* eps, float* x_prev, const fl
 // x_prev may alias x_t (element-wise); step_ptr (nullable): row index into coef_dev; pred_x0: ``eps`` is the network's x0
 // prediction and the derived eps goes to eps_out (nullable)
 int launch_inc_step(int* p, hipStream_t s);
+// ---- k_noise.hip: Philox4x32-10 / Box-Muller normals keyed by (seed, window id, element, draw index); seed and ids (nullable: 0 .. B-1) in
+// device memory.  launch_ddim_step_sto: launch_ddim_step plus sigma * z (coef rows [sa, sb, sap, c], sigma one float per row; step_ptr
+// nullable: row index and draw index 1 + step on the device, else row 0 and `draw`)
+int launch_randn(float* out, const int64_t* ids, const uint64_t* seed_dev, int draw, int B, int64_t per_window, hipStream_t s);
+int launch_ddim_step_sto(const float* x_t, const float* eps, float* x_prev, float* eps_out, const float* coef_dev, const float* sigma_dev,
+                         const int64_t* ids, const uint64_t* seed_dev, int draw, int pred_x0, int B, int64_t per_window,
+                         const int* step_ptr, hipStream_t s);
 int launch_sample_finish(const float* x, const float* ms2_cond, float* out_x, float* out_noise, int64_t n, int normalize,
                          hipStream_t s);
 int launch_mse_fwd_bwd(const float* eps, const float* noise, float* loss_out, float* grad_out, float* partials, int64_t n,

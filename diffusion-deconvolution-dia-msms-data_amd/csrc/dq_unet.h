@@ -43,6 +43,9 @@ struct Arena {
   std::vector<LevelBuf> downs, ups;
   int64_t mid_in, xn, qv, kk, o, lse, delta, attn_out, mid_back, eps, partials, head_part, loss, coef, xa, xb, wg, wg_floats, la_part, la_part_floats, ts_tab, step, c2_stage, c1_stage, wtmp, la_prep, wimg, timg, bb_part, bb_part_floats, ms1_scratch;
   int64_t ms1_wpart = 0, ms1_wpart_floats = 0;  // attn_cond_channels > 1: the slots of k_ms1_feat_wgrad
+  // stochastic sampling (eta > 0; k_noise.hip): sigma per step beside `coef`; the seed (uint64) and the window ids (B int64) staged at fixed
+  // addresses for the captured step.  Last in the arena: every other offset is what it was without them.
+  int64_t sigma = 0, seed_stage = 0, ids_stage = 0;
   ResBuf mid1, mid2, fin;
   // wide bottleneck (Plan::wide_mid): P = RT padded to a multiple of 4; every tensor below is (B, channels, P)
   int P = 0;
@@ -75,5 +78,6 @@ struct dq_plan {
   hipStream_t cap_stream = nullptr;  // capture-only stream (the caller's may be the uncapturable legacy default stream)
   const void* g_params = nullptr; const void* g_rope = nullptr; const void* g_ws = nullptr;
   int g_B = 0, g_RT = 0, g_norm = -1, g_pred = -1;
+  int g_sto = -1;  // the captured step ends in k_ddim_step_sto (eta > 0) or in the deterministic update (eta == 0)
   unsigned g_opt_epoch = 0;  // dq::options_epoch() at capture time (a dq_set_option call may change the dispatch baked into the graph)
 };

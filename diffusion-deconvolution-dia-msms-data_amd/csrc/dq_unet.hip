@@ -175,6 +175,7 @@ void layout_arena(const Plan& p, int B, int RT, Arena& a) {
   a.ts_tab = take_nz(1024); a.step = take_nz(64);  // graph replay: timestep table (int32) and the device-side step counter
   a.c2_stage = take_nz(R * p.mz); a.c1_stage = take_nz(R * M1);  // conditions staged at fixed addresses for the captured step
   if (M1 > 1 && B > 0) { a.ms1_wpart_floats = ms1_feat_wgrad_part_floats(B, RT, M1); a.ms1_wpart = take_nz(a.ms1_wpart_floats); }
+  a.sigma = take_nz(1024); a.seed_stage = take_nz(64); a.ids_stage = take_nz(2 * (int64_t)B);  // stochastic sampling (256-B aligned: 8-byte words fit)
   a.zero_floats = off;
   a.floats = off_nz;
   zero_total = off;
@@ -1743,6 +1744,53 @@ int dq_ddim_step_x0(const float* x_t, const float* x0_pred, float* x_prev, float
   return launch_ddim_step(x_t, x0_pred, x_prev, coef_dev, n, nullptr, (hipStream_t)stream, 1, eps_out);
 }
 
+int dq_randn(float* out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int B, int64_t per_window, void* stream) {
+  return launch_randn(out, window_ids_dev, seed_dev, draw, B, per_window, (hipStream_t)stream);
+}
+
+int dq_ddim_step_sto(const float* x_t, const float* net_out, float* x_prev, float* eps_out, const float* coef_dev,
+                     const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window,
+                     void* stream) {
+  DQ_REQUIRE(x_t && net_out && x_prev && coef_dev && seed_dev, "dq_ddim_step_sto: null argument");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_ddim_step_sto: Unknown pred_type");
+  return launch_ddim_step_sto(x_t, net_out, x_prev, pred_type == DQ_PRED_X0 ? eps_out : nullptr, coef_dev, coef_dev + 4, window_ids_dev,
+                              seed_dev, draw, pred_type == DQ_PRED_X0, B, per_window, nullptr, (hipStream_t)stream);
+}
+
+// The sampler's per-step coefficients (host only).  eta == 0: the fp32 expressions of model.py:265-267, 284-286 as they always were.
+// eta > 0: sa, sb, sap the same fp32 expressions (x0 and eps are derived as before); sigma and c in double from the fp32 table values.
+int dq_ddim_coef_table(const float* alpha_bars_host, int num_timesteps, const int32_t* timesteps_host, int num_steps, float eta,
+                       float* coef_out, float* sigma_out) {
+  DQ_REQUIRE(alpha_bars_host && timesteps_host && coef_out && sigma_out, "dq_ddim_coef_table: null argument");
+  DQ_REQUIRE(num_timesteps >= 1 && num_steps >= 1, "dq_ddim_coef_table: num_timesteps and num_steps must be >= 1");
+  DQ_REQUIRE(eta >= 0.f && eta <= 1.f, "dq_ddim_coef_table: eta must satisfy 0 <= eta <= 1");  // (false for NaN)
+  for (int i = 0; i < num_steps; ++i) {
+    const int t = timesteps_host[i];
+    DQ_REQUIRE(t >= 0 && t < num_timesteps, "dq_ddim_coef_table: timestep out of range");
+    const float ab = alpha_bars_host[t];
+    coef_out[4 * i + 0] = std::sqrt(ab);
+    coef_out[4 * i + 1] = std::sqrt(1.0f - ab);
+    sigma_out[i] = 0.f;
+    if (t > 0) {
+      const float abp = alpha_bars_host[t - 1];
+      coef_out[4 * i + 2] = std::sqrt(abp);
+      coef_out[4 * i + 3] = std::sqrt(1.0f - abp);
+      if (eta > 0.f) {
+        const double a = (double)ab, ap = (double)abp;
+        // (a degenerate schedule -- alpha_bar of 0 or 1, or one that rises -- gets sigma = 0 instead of a NaN)
+        const double ratio = ap > 0.0 ? std::min(a / ap, 1.0) : 1.0;
+        const double sg = (1.0 - a) > 0.0 ? (double)eta * std::sqrt((1.0 - ap) / (1.0 - a)) * std::sqrt(1.0 - ratio) : 0.0;
+        coef_out[4 * i + 3] = (float)std::sqrt(std::max(0.0, 1.0 - ap - sg * sg));
+        sigma_out[i] = (float)sg;
+      }
+    } else {
+      coef_out[4 * i + 2] = -1.f;
+      coef_out[4 * i + 3] = 0.f;
+    }
+  }
+  return 0;
+}
+
 int dq_unet_fwd(dq_plan* plan, const float* params, const float* rope_freqs, const float* x, const int64_t* t, int t_scalar,
                 const float* init_cond, const float* attn_cond, float cond_mul, float cond_add, float* out, int save_for_bwd,
                 void* workspace, int64_t workspace_bytes, int B, int RT, void* stream) {
@@ -1915,8 +1963,22 @@ int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, 
                    const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
                    const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
                    int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream) {
-  DQ_REQUIRE(plan && params && alpha_bars_host && x_T && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
+  DQ_REQUIRE(x_T, "dq_ddim_sample: null argument");
+  return dq_ddim_sample_ex(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type,
+                           timesteps_host, num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream,
+                           0.f, nullptr, nullptr);
+}
+
+int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                      const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                      const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                      int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                      const uint64_t* seed_dev, const int64_t* window_ids_dev) {
+  DQ_REQUIRE(plan && params && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
              "dq_ddim_sample: null argument");
+  DQ_REQUIRE(eta >= 0.f && eta <= 1.f, "dq_ddim_sample: eta must satisfy 0 <= eta <= 1");  // (false for NaN)
+  const bool sto = eta > 0.f;  // the update draws noise: k_ddim_step_sto behind the forward instead of the update in the head launch
+  DQ_REQUIRE(seed_dev || (x_T && !sto), "dq_ddim_sample: eta > 0 and a null x_T need the seed (device memory)");
   DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_ddim_sample: Unknown pred_type");
   const int px0 = pred_type == DQ_PRED_X0;
   DQ_REQUIRE(B > 0 && RT > 0 && num_steps >= 1 && num_steps <= 1024, "dq_ddim_sample: need B, RT > 0 and 1 <= num_steps <= 1024");
@@ -1932,29 +1994,18 @@ int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, 
   const int64_t n = (int64_t)B * RT * plan->plan.mz;
   const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
   const int32_t* ts = timesteps_host;  // trunc(linspace(T-1, 0, num_steps)) formed by the caller exactly as model.py:313 does
-  // coefficient table (model.py:265-267, 284-286), fp32 like the reference
-  std::vector<float> coef(4 * (size_t)num_steps);
-  for (int i = 0; i < num_steps; ++i) {
-    const int t = ts[i];
-    DQ_REQUIRE(t >= 0 && t < T, "dq_ddim_sample: timestep out of range");
-    const float ab = alpha_bars_host[t];
-    coef[4 * i + 0] = std::sqrt(ab);
-    coef[4 * i + 1] = std::sqrt(1.0f - ab);
-    if (t > 0) {
-      const float abp = alpha_bars_host[t - 1];
-      coef[4 * i + 2] = std::sqrt(abp);
-      coef[4 * i + 3] = std::sqrt(1.0f - abp);
-    } else {
-      coef[4 * i + 2] = -1.f;
-      coef[4 * i + 3] = 0.f;
-    }
-  }
+  // coefficient table (model.py:265-267, 284-286), fp32 like the reference; with eta > 0 also sigma per step (dq_ddim_coef_table)
+  std::vector<float> coef(4 * (size_t)num_steps), sigma((size_t)num_steps);
+  DQ_TRY(dq_ddim_coef_table(alpha_bars_host, T, ts, num_steps, eta, coef.data(), sigma.data()));
   DQ_HIP_OK(hipMemcpyAsync(c.w(a.coef), coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice, s));
+  if (sto) DQ_HIP_OK(hipMemcpyAsync(c.w(a.sigma), sigma.data(), sizeof(float) * sigma.size(), hipMemcpyHostToDevice, s));
   // the host vector must outlive the copy: pageable H2D copies are staged synchronously by the runtime, but make it explicit
   DQ_HIP_OK(hipStreamSynchronize(s));
   float* xa = c.w(a.xa);
   float* xb = c.w(a.xb);
-  DQ_HIP_OK(hipMemcpyAsync(xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  const int64_t per = (int64_t)RT * plan->plan.mz;
+  if (x_T) DQ_HIP_OK(hipMemcpyAsync(xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  else DQ_TRY(launch_randn(xa, window_ids_dev, seed_dev, 0, B, per, s));  // draw index 0 is x_T's
   // The MS1 feature path (unet1d.py:1120-1130), to_k and RoPE(k) (:555, 561) depend on neither t nor x_t: once per call, not per step
   Ctx::StepIO io;
   io.pred_x0 = px0; io.coef = c.w(a.coef);
@@ -1995,11 +2046,24 @@ int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, 
     DQ_HIP_OK(hipMemsetAsync(step, 0, sizeof(int), s));
     DQ_HIP_OK(hipMemcpyAsync(c.w(a.c2_stage), ms2_cond, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
     DQ_HIP_OK(hipMemcpyAsync(c.w(a.c1_stage), ms1_cond, sizeof(float) * (int64_t)B * RT * plan->plan.ms1_channels, hipMemcpyDeviceToDevice, s));
+    uint64_t* seed_st = reinterpret_cast<uint64_t*>(c.w(a.seed_stage));
+    int64_t* ids_st = reinterpret_cast<int64_t*>(c.w(a.ids_stage));
+    std::vector<int64_t> iota;
+    if (sto) {  // seed and ids staged like the conditions: a new seed or other windows replay the same graph (null ids: 0 .. B-1)
+      DQ_HIP_OK(hipMemcpyAsync(seed_st, seed_dev, sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+      if (window_ids_dev) DQ_HIP_OK(hipMemcpyAsync(ids_st, window_ids_dev, sizeof(int64_t) * B, hipMemcpyDeviceToDevice, s));
+      else {
+        iota.resize(B);
+        for (int b = 0; b < B; ++b) iota[b] = b;
+        DQ_HIP_OK(hipMemcpyAsync(ids_st, iota.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, s));
+      }
+    }
     DQ_HIP_OK(hipStreamSynchronize(s));  // ts is caller memory; also keeps the capture below free of pending copies
     DQ_TRY(ms1_prologue(c, c.w(a.c1_stage)));
-    io.x_t = xa; io.x_out = xa; io.step_ptr = step; io.want_eps = false;  // in place: element-wise, read and written by the same lane
+    io.x_t = sto ? nullptr : xa; io.x_out = xa; io.step_ptr = step; io.want_eps = false;  // in place: element-wise, read and written by the same lane
     const bool valid = plan->step_exec && plan->g_params == params && plan->g_rope == rope_freqs && plan->g_ws == workspace &&
-                       plan->g_B == B && plan->g_RT == RT && plan->g_norm == auto_normalize && plan->g_pred == pred_type && plan->g_opt_epoch == options_epoch();
+                       plan->g_B == B && plan->g_RT == RT && plan->g_norm == auto_normalize && plan->g_pred == pred_type &&
+                       plan->g_sto == (int)sto && plan->g_opt_epoch == options_epoch();
     if (!valid) {
       if (plan->step_exec) { (void)hipGraphExecDestroy(plan->step_exec); plan->step_exec = nullptr; }
       if (plan->step_graph) { (void)hipGraphDestroy(plan->step_graph); plan->step_graph = nullptr; }
@@ -2012,7 +2076,8 @@ int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, 
       cc.step_io = &io;
       DQ_HIP_OK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
       int rc = unet_forward(cc, rope_freqs, xa, nullptr, 0, c.w(a.c2_stage), c.w(a.c1_stage), cm, ca, plan->dev, c.w(a.eps), ts_tab, step);
-      if (!rc && !io.fused_update) rc = launch_ddim_step(xa, c.w(a.eps), xa, c.w(a.coef), n, step, cs, px0, nullptr);  // in place: element-wise
+      if (!rc && sto) rc = launch_ddim_step_sto(xa, c.w(a.eps), xa, nullptr, c.w(a.coef), c.w(a.sigma), ids_st, seed_st, 0, px0, B, per, step, cs);
+      else if (!rc && !io.fused_update) rc = launch_ddim_step(xa, c.w(a.eps), xa, c.w(a.coef), n, step, cs, px0, nullptr);  // in place: element-wise
       if (!rc) rc = launch_inc_step(step, cs);
       hipGraph_t g = nullptr;
       const hipError_t ce = hipStreamEndCapture(cs, &g);
@@ -2020,7 +2085,7 @@ int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, 
       DQ_HIP_OK(ce);
       plan->step_graph = g;
       DQ_HIP_OK(hipGraphInstantiate(&plan->step_exec, g, nullptr, nullptr, 0));
-      plan->g_params = params; plan->g_rope = rope_freqs; plan->g_ws = workspace; plan->g_B = B; plan->g_RT = RT; plan->g_norm = auto_normalize; plan->g_pred = pred_type; plan->g_opt_epoch = options_epoch();
+      plan->g_params = params; plan->g_rope = rope_freqs; plan->g_ws = workspace; plan->g_B = B; plan->g_RT = RT; plan->g_norm = auto_normalize; plan->g_pred = pred_type; plan->g_sto = (int)sto; plan->g_opt_epoch = options_epoch();
     }
     for (int i = 0; i < num_steps; ++i) DQ_HIP_OK(hipGraphLaunch(plan->step_exec, s));
     DQ_TRY(launch_sample_finish(xa, ms2_cond, out_x, out_noise, n, auto_normalize, s));
@@ -2032,9 +2097,12 @@ int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, 
     // eps objective: the network output IS the trajectory's eps; x0 objective: the derived eps goes to the trajectory
     float* eps = traj_eps ? traj_eps + (int64_t)i * n : c.w(a.eps);
     float* xn = traj_x ? traj_x + (int64_t)i * n : xb;
-    io.x_t = xa; io.x_out = xn; io.coef = c.w(a.coef) + 4 * i; io.step_ptr = nullptr; io.want_eps = traj_eps != nullptr; io.fused_update = false;
+    io.x_t = sto ? nullptr : xa; io.x_out = xn; io.coef = c.w(a.coef) + 4 * i; io.step_ptr = nullptr; io.want_eps = traj_eps != nullptr; io.fused_update = false;
     DQ_TRY(unet_forward(c, rope_freqs, xa, nullptr, ts[i], ms2_cond, ms1_cond, cm, ca, plan->dev, eps));  // model.py:271 / :276
-    if (!io.fused_update)
+    if (sto)  // step i draws at index 1 + i
+      DQ_TRY(launch_ddim_step_sto(xa, eps, xn, (traj_eps && px0) ? traj_eps + (int64_t)i * n : nullptr, c.w(a.coef) + 4 * i, c.w(a.sigma) + i,
+                                  window_ids_dev, seed_dev, 1 + i, px0, B, per, nullptr, s));
+    else if (!io.fused_update)
       DQ_TRY(launch_ddim_step(xa, eps, xn, c.w(a.coef) + 4 * i, n, nullptr, s, px0, (traj_eps && px0) ? traj_eps + (int64_t)i * n : nullptr));  // model.py:273-289
     if (traj_x) {
       DQ_HIP_OK(hipMemcpyAsync(xa, xn, sizeof(float) * n, hipMemcpyDeviceToDevice, s));

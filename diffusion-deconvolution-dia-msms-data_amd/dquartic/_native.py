@@ -62,6 +62,13 @@ PROTOTYPES = {
     "dq_ddim_sample": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
                                c_void_p]),
+    "dq_randn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
+    "dq_ddim_step_sto": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64,
+                                 c_void_p]),
+    "dq_ddim_coef_table": (c_int, [POINTER(c_float), c_int, POINTER(c_int32), c_int, c_float, POINTER(c_float), POINTER(c_float)]),
+    "dq_ddim_sample_ex": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                  POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
+                                  c_void_p, c_float, c_void_p, c_void_p]),
     "dq_pair_batch_scratch_bytes": (c_int64, [c_int]),
     "dq_pair_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int64, c_float, c_float, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -133,9 +133,48 @@ class DDIMDiffusionModel(ModelInterface):
         b = torch.sqrt(1.0 - self.alpha_bars[t])[:, None, None]
         return a * x_0 + b * noise
 
+    # ------------------------------------------------------------------ stochastic sampling
+    @staticmethod
+    def _check_eta(eta):
+        eta = float(eta)
+        if not 0.0 <= eta <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError(f"eta must satisfy 0 <= eta <= 1, got {eta!r}")
+        return eta
+
+    @staticmethod
+    def _seed_tensor(seed, device):
+        """The 64-bit seed as the one device word the kernels read (an int64 tensor carrying the uint64 bit pattern).  None: one draw
+        from torch's generator."""
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+        seed = int(seed) & (2 ** 64 - 1)
+        return torch.tensor([seed - 2 ** 64 if seed >= 2 ** 63 else seed], dtype=torch.int64, device=device)
+
+    @staticmethod
+    def _ids_tensor(window_ids, B, device):
+        if window_ids is None:
+            return None
+        ids = torch.as_tensor(window_ids, dtype=torch.int64).reshape(-1).to(device).contiguous()
+        if ids.numel() != B:
+            raise ValueError(f"window_ids must have one id per window of the batch ({B}), got {ids.numel()}")
+        return ids
+
+    def ddim_coef_table(self, timesteps, eta=0.0):
+        """``dq_ddim_coef_table`` (host only): per step the rows [sqrt(ab), sqrt(1-ab), sqrt(ab_prev), c] and sigma as two float32 CPU
+        tensors (num_steps, 4) and (num_steps,)."""
+        ts = [int(v) for v in timesteps]
+        ts_c = (ctypes.c_int32 * len(ts))(*ts)
+        coef, sigma = (ctypes.c_float * (4 * len(ts)))(), (ctypes.c_float * len(ts))()
+        N.check(N.lib().dq_ddim_coef_table(self._alpha_bars_host(), int(self.num_timesteps), ts_c, len(ts), float(eta), coef, sigma),
+                "dq_ddim_coef_table")
+        return torch.tensor(list(coef), dtype=torch.float32).reshape(-1, 4), torch.tensor(list(sigma), dtype=torch.float32)
+
     # ------------------------------------------------------------------ reverse process
-    def p_sample(self, x_t, t, init_cond=None, attn_cond=None):
-        """model.py:244-291.  ``t`` is a python int; conditions are already normalised."""
+    def p_sample(self, x_t, t, init_cond=None, attn_cond=None, eta=0.0, seed=None, window_ids=None, draw=None):
+        """model.py:244-291.  ``t`` is a python int; conditions are already normalised.  ``eta > 0`` (device tensors, no autograd through
+        the step): the update of ``dq_ddim_step_sto`` with the noise of (``seed``, ``window_ids``, draw index ``draw``: step i of a loop
+        draws at 1 + i)."""
+        eta = self._check_eta(eta)
         batch_size = x_t.size(0)
         t_tensor = torch.full((batch_size,), int(t), device=x_t.device, dtype=torch.long)
         ab = self.alpha_bars[t]
@@ -144,6 +183,21 @@ class DDIMDiffusionModel(ModelInterface):
             raise ValueError(f"Unknown pred_type: {self.pred_type}")
         out = self.model(x_t, t_tensor, init_cond, attn_cond)  # eps_pred or x0_pred (model.py:271 / :276)
         wants_grad = torch.is_grad_enabled() and (x_t.requires_grad or out.requires_grad)
+        if eta > 0.0:
+            if not x_t.is_cuda or wants_grad:
+                raise NotImplementedError("p_sample: eta > 0 runs in the native update kernel only (device tensors, no autograd through the step)")
+            if seed is None or draw is None:
+                raise ValueError("p_sample: eta > 0 needs seed and draw (the step's draw index: 1 + i for step i of a loop)")
+            cf, sg = self.ddim_coef_table([t], eta)
+            coef = torch.cat([cf.reshape(-1), sg]).to(x_t.device)
+            xt, o = x_t.detach().float().contiguous(), out.detach().float().contiguous()
+            x_prev = torch.empty_like(xt)
+            eps_pred = torch.empty_like(xt) if self.pred_type == "x0" else None
+            ids_dev, seed_dev = self._ids_tensor(window_ids, batch_size, x_t.device), self._seed_tensor(seed, x_t.device)
+            N.check(N.lib().dq_ddim_step_sto(N.ptr(xt), N.ptr(o), N.ptr(x_prev), N.ptr(eps_pred), N.ptr(coef), N.ptr(ids_dev), N.ptr(seed_dev),
+                                             int(draw), N.PRED_TYPES[self.pred_type], batch_size, xt[0].numel(), N.stream_ptr()),
+                    "dq_ddim_step_sto")
+            return x_prev, (out if self.pred_type == "eps" else eps_pred)
         if x_t.is_cuda and not wants_grad:
             if t > 0:
                 abp = self.alpha_bars[t - 1]
@@ -172,10 +226,25 @@ class DDIMDiffusionModel(ModelInterface):
             x_prev = x0_pred
         return x_prev, eps_pred
 
-    def sample(self, x_t, ms2_cond=None, ms1_cond=None, num_steps=1000, return_trajectory=False):
-        """model.py:293-324: returns (denoised, mixture - denoised).  Native loop when the network is UNet1d."""
-        if self.native and x_t.is_cuda and ms2_cond is not None and ms1_cond is not None:
-            return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory)
+    def sample(self, x_t, ms2_cond=None, ms1_cond=None, num_steps=1000, return_trajectory=False, eta=0.0, seed=None, window_ids=None,
+               shape=None):
+        """model.py:293-324: returns (denoised, mixture - denoised).  Native loop when the network is UNet1d.
+
+        ``eta`` in [0, 1]: 0 is the deterministic DDIM update, 1 ancestral (DDPM-like) sampling; the per-step noise
+        is a counter-based generator inside the update kernel, keyed by (``seed``, window id, element, step), so a window's result does
+        not depend on its place in the batch.  ``seed``: a 64-bit int (None with ``eta > 0``: drawn once from torch's generator);
+        ``window_ids``: one int64 id per window (None: 0 .. B-1).  ``x_t=None`` draws x_T from the same generator (needs ``seed``); the
+        shape is ``shape`` or ``ms2_cond``'s.  Native path only.  The defaults are the call as it always was."""
+        eta = self._check_eta(eta)
+        stochastic = eta > 0.0 or x_t is None or seed is not None or window_ids is not None
+        if self.native and ms2_cond is not None and ms1_cond is not None and (x_t.is_cuda if x_t is not None else ms2_cond.is_cuda):
+            if not stochastic:
+                return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory)
+            return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
+                                       shape=shape)
+        if stochastic:
+            raise NotImplementedError("sample: eta > 0, seed, window_ids and x_t=None need the native sampler (this package's UNet1d on "
+                                      "the GPU with both conditions); the generic loop is the deterministic update only")
         ms2n = self.normalize(ms2_cond) if ms2_cond is not None else None
         ms1n = self.normalize(ms1_cond) if ms1_cond is not None else None
         pred_noise = None
@@ -186,18 +255,38 @@ class DDIMDiffusionModel(ModelInterface):
             pred_noise = self.unnormalize(ms2n) - x_t
         return x_t, pred_noise
 
-    def _sample_native(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False):
+    def _sample_native(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False, eta=None, seed=None, window_ids=None, shape=None):
+        """``eta`` None: ``dq_ddim_sample`` (the call as it always was); else ``dq_ddim_sample_ex``."""
         net: UNet1d = self.model
         f32 = lambda v: v.detach().to(torch.float32).contiguous()
-        B, RT, MZ = x_T.shape
-        x_T, c2, c1 = f32(x_T), f32(ms2_cond), f32(net._check_inputs(ms1_cond, B, RT))
+        if x_T is None:
+            if seed is None and not eta:
+                raise ValueError("sample: x_t=None needs a seed (x_T is drawn from it)")
+            B, RT, MZ = tuple(shape) if shape is not None else tuple(ms2_cond.shape)
+            c2 = f32(ms2_cond)
+        else:
+            B, RT, MZ = x_T.shape
+            x_T, c2 = f32(x_T), f32(ms2_cond)
+        c1 = f32(net._check_inputs(ms1_cond, B, RT))
         flat = net.read_params()  # (the averaged weights inside ModelInterface.ema_scope())
         ws = net.workspace(B, RT, False)
         ts = self.sampler_timesteps(self.num_timesteps, num_steps).to(torch.int32)
         ts_c = (ctypes.c_int32 * num_steps)(*ts.tolist())
-        out_x, out_n = torch.empty_like(x_T), torch.empty_like(x_T)
-        traj_x = torch.empty((num_steps, B, RT, MZ), device=x_T.device) if return_trajectory else None
-        traj_e = torch.empty((num_steps, B, RT, MZ), device=x_T.device) if return_trajectory else None
+        out_x, out_n = torch.empty_like(c2), torch.empty_like(c2)
+        traj_x = torch.empty((num_steps, B, RT, MZ), device=c2.device) if return_trajectory else None
+        traj_e = torch.empty((num_steps, B, RT, MZ), device=c2.device) if return_trajectory else None
+        if eta is not None:
+            seed_dev = self._seed_tensor(seed, c2.device) if (seed is not None or eta > 0.0 or x_T is None) else None
+            ids_dev = self._ids_tensor(window_ids, B, c2.device)
+            self.last_seed = None if seed_dev is None else int(seed_dev.item()) & (2 ** 64 - 1)  # (what a seed=None call drew)
+            N.check(N.lib().dq_ddim_sample_ex(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), self._alpha_bars_host(), int(self.num_timesteps),
+                                              N.ptr(x_T), N.ptr(c2), N.ptr(c1), 1 if self.auto_normalize else 0,
+                                              N.PRED_TYPES[self.pred_type], ts_c, num_steps, N.ptr(out_x), N.ptr(out_n), N.ptr(traj_x),
+                                              N.ptr(traj_e), 1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws), ws.numel(),
+                                              B, RT, N.stream_ptr(), float(eta), N.ptr(seed_dev), N.ptr(ids_dev)), "dq_ddim_sample_ex")
+            if return_trajectory:
+                return out_x, out_n, traj_x, traj_e
+            return out_x, out_n
         N.check(N.lib().dq_ddim_sample(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), self._alpha_bars_host(), int(self.num_timesteps),
                                        N.ptr(x_T), N.ptr(c2),
                                        N.ptr(c1), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], ts_c, num_steps,

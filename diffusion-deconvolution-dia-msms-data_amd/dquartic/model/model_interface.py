@@ -420,7 +420,7 @@ class ModelInterface(object):
     def train_step(self, x_0, ms2_cond=None, ms1_cond=None, noise=None, ms1_loss_weight=0.0):
         raise NotImplementedError
 
-    def sample(self, x_t, ms2_cond=None, ms1_cond=None, num_steps=1000):
+    def sample(self, x_t, ms2_cond=None, ms1_cond=None, num_steps=1000, **kwargs):
         raise NotImplementedError
 
     def train(self, dataloader, batch_size, epochs, warmup_epochs: int = 5, learning_rate: float = 1e-4, use_wandb: bool = False,
@@ -609,16 +609,40 @@ class ModelInterface(object):
         use = self.ema_enabled if use_ema is None else bool(use_ema)
         return self.ema_scope() if use else contextlib.nullcontext()
 
-    def predict(self, dataloader, mixture_weights=(0.5, 0.5), num_steps=1000, use_ema=None):
+    def predict(self, dataloader, mixture_weights=(0.5, 0.5), num_steps=1000, use_ema=None, eta=0.0, seed=None, n_draws=1):
         """Reference :630-668: one dict per batch with the first item's prediction (``_predict_one_batch`` returns item 0).
-        ``use_ema``: sample from the averaged weights; None (default) = when EMA is enabled."""
+        ``use_ema``: sample from the averaged weights; None (default) = when EMA is enabled.
+
+        Stochastic sampling (the defaults are the call as it always was, x_T from ``torch.randn_like``): with
+        ``eta > 0``, a ``seed`` or ``n_draws > 1``, x_T and the per-step noise come from the sampler's counter-based generator under
+        ``seed`` (None: drawn once from torch's generator), and the window id of item b of batch k is its running index in the dataloader
+        -- a window's prediction does not depend on the batch size.  Draw j (0-based) samples under ``seed + j``, so it is what
+        ``n_draws=1, seed=seed + j`` returns.  ``n_draws > 1`` adds ``"pred_mean"`` and ``"pred_std"`` (per element, over the draws,
+        population form) to each dict; ``"pred"`` stays draw 0.  With ``n_draws == 1`` those two keys are absent."""
         self.model.eval()
+        n_draws = int(n_draws)
+        if n_draws < 1:
+            raise ValueError(f"n_draws must be >= 1, got {n_draws}")
+        stochastic = float(eta) > 0.0 or seed is not None or n_draws > 1
+        if stochastic and seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
         preds = []
+        first = 0
         for ms2_1, ms1_1, ms2_2, ms1_2 in dataloader:
             x_0, ms1_cond = ms2_1.to(self.device), ms1_1.to(self.device)
             ms2_cond = (ms2_1 * mixture_weights[0]).to(self.device) + (ms2_2 * mixture_weights[1]).to(self.device)
-            pred, _ = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, use_ema=use_ema)
-            preds.append({"ms2_1": ms2_1.cpu().numpy(), "ms1_1": ms1_1.cpu().numpy(), "mixture": ms2_cond.cpu().numpy(), "pred": pred})
+            d = {"ms2_1": ms2_1.cpu().numpy(), "ms1_1": ms1_1.cpu().numpy(), "mixture": ms2_cond.cpu().numpy()}
+            if not stochastic:
+                d["pred"], _ = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, use_ema=use_ema)
+            else:
+                ids = torch.arange(first, first + x_0.shape[0], dtype=torch.int64)
+                out = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, use_ema=use_ema, eta=eta,
+                                              seed=seed, n_draws=n_draws, window_ids=ids)
+                d["pred"] = out[0]
+                if n_draws > 1:
+                    d["pred_mean"], d["pred_std"] = out[2], out[3]
+            first += x_0.shape[0]
+            preds.append(d)
         return np.array(preds, dtype=object)
 
     # ---- internals
@@ -732,13 +756,29 @@ class ModelInterface(object):
             self.optimizer.step()
         return loss.item() if sync else loss.detach()
 
-    def _predict_one_batch(self, x_0, ms2_cond=None, ms1_cond=None, num_steps=1000, use_ema=None):
+    def _predict_one_batch(self, x_0, ms2_cond=None, ms1_cond=None, num_steps=1000, use_ema=None, eta=0.0, seed=None, n_draws=1,
+                           window_ids=None):
         """Reference :1125-1150: eval + no_grad + sample(randn_like(x_0)); returns item 0 of the batch as numpy.  ``use_ema`` as in
-        ``predict``."""
+        ``predict``.  With ``eta > 0``, a ``seed`` or ``n_draws > 1`` (see ``predict``): x_T and the step noise from the sampler's
+        generator, draw j under ``seed + j``; ``n_draws > 1`` returns (sample, pred_noise, mean, std) of item 0, sample / pred_noise
+        being draw 0's and mean / std taken per element over the draws' samples (torch reductions: this is not the hot path)."""
         self.model.eval()
+        if not (float(eta) > 0.0 or seed is not None or int(n_draws) > 1):
+            with torch.no_grad(), self._ema_or_null_scope(use_ema):
+                sample, pred_noise = self.sample(torch.randn_like(x_0), ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps)
+            return sample[0].cpu().detach().numpy(), pred_noise[0].cpu().detach().numpy()
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+        draws = []
         with torch.no_grad(), self._ema_or_null_scope(use_ema):
-            sample, pred_noise = self.sample(torch.randn_like(x_0), ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps)
-        return sample[0].cpu().detach().numpy(), pred_noise[0].cpu().detach().numpy()
+            for j in range(int(n_draws)):
+                draws.append(self.sample(None, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, eta=eta, seed=int(seed) + j,
+                                         window_ids=window_ids, shape=tuple(x_0.shape)))
+        first = (draws[0][0][0].cpu().numpy(), draws[0][1][0].cpu().numpy())
+        if int(n_draws) == 1:
+            return first
+        stack = torch.stack([s[0] for s, _ in draws])
+        return first + (stack.mean(dim=0).cpu().numpy(), stack.std(dim=0, unbiased=False).cpu().numpy())
 
     def log_single_prediction(self, *args, **kwargs):
         raise NotImplementedError("wandb prediction tables / pyopenms_viz plots are outside the hot path (SURVEY section 2)")

@@ -47,7 +47,8 @@ const char* dq_last_error(void);
  * dq_linattn_fwd_prepared.  10: dq_set_option, dq_get_option, dq_debug_side_tail_store (later, additive: dq_plan_set_final_act,
  * dq_plan_final_act, dq_get_option_effective, dq_resblock_forms, dq_linattn_forms, dq_linattn_bwd_store, dq_plan_create_ex,
  * dq_plan_attn_cond_channels, dq_ms1_feat_fwd, dq_ms1_feat_wgrad, dq_ms1_feat_wgrad_scratch_floats).  11: dq_conv_bwd,
- * dq_conv_bwd_workspace_floats, dq_conv_bwd_forms (later, additive: dq_adamw_clip_ema_step, dq_adamw_clip_ema_step_dev). */
+ * dq_conv_bwd_workspace_floats, dq_conv_bwd_forms (later, additive: dq_adamw_clip_ema_step, dq_adamw_clip_ema_step_dev; dq_randn,
+ * dq_ddim_step_sto, dq_ddim_coef_table, dq_ddim_sample_ex). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 11
 
@@ -217,6 +218,37 @@ int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, 
                    const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
                    const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
                    int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream);
+
+/* ---- stochastic sampling (no reference counterpart) -----------------------------------------
+ * Noise is Philox4x32-10 (Random123 constants) evaluated inside the kernels: for element e of its window (0 <= e < per_window < 2^32),
+ * draw index d, window id w (int64) and seed s (uint64): counter (e, d, w lo, w hi), key (s lo, s hi); output words r0, r1 give
+ * u1 = ((r0 >> 9) + 0.5) 2^-23, u2 = (r1 >> 8) 2^-24, z = sqrtf(-2 logf(u1)) cosf(6.2831855f u2).  d = 0 is x_T's, step i of the loop
+ * (0-based) draws at d = 1 + i.  seed_dev (1 uint64) and window_ids_dev (B int64; NULL: 0 .. B-1) are DEVICE memory: a window draws the
+ * same noise at any batch position, and a captured step is replayed unchanged under a new seed.
+ * dq_randn: out (B, per_window) = z at draw index `draw`; out 4-byte aligned (16-byte stores when it is 16-byte aligned). */
+int dq_randn(float* out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int B, int64_t per_window, void* stream);
+/* K9 with noise: x0 / eps as dq_ddim_step (DQ_PRED_EPS) or dq_ddim_step_x0 (DQ_PRED_X0; eps_out nullable, ignored under DQ_PRED_EPS) form
+ * them, then x_prev = sap*x0 + c*eps + sigma*z.  coef_dev: 5 device floats [sa, sb, sap, c, sigma]; sap < 0 means t == 0: x_prev = x0, no
+ * noise drawn (dq_ddim_step's result bit for bit).  per_window a multiple of 4; tensors 16-byte aligned; x_prev may alias x_t. */
+int dq_ddim_step_sto(const float* x_t, const float* net_out, float* x_prev, float* eps_out, const float* coef_dev,
+                     const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window,
+                     void* stream);
+/* The sampler's coefficient rows (host only, no GPU call; the function dq_ddim_sample / _ex use): per step i at t = timesteps_host[i],
+ * coef_out[4i..] = [sqrt(ab), sqrt(1-ab), sqrt(abp), c] and sigma_out[i], ab = alpha_bars[t], abp = alpha_bars[t-1];
+ *   sigma = eta sqrt((1-abp)/(1-ab)) sqrt(1 - ab/abp), c = sqrt(max(0, 1 - abp - sigma^2))   (double, from the fp32 table values);
+ * eta == 0: c = sqrt(1-abp) in fp32 (model.py:284-286, what dq_ddim_sample always used) and sigma = 0.  t == 0: [.., -1, 0], sigma 0.
+ * 0 <= eta <= 1, anything else (NaN included): non-zero (dq_last_error). */
+int dq_ddim_coef_table(const float* alpha_bars_host, int num_timesteps, const int32_t* timesteps_host, int num_steps, float eta,
+                       float* coef_out, float* sigma_out);
+/* dq_ddim_sample with the DDIM eta (Song et al. 2021, eq. 16; eta = 1: ancestral DDPM-like sampling): dq_ddim_sample is this call with
+ * eta = 0 and NULL seed / ids.  eta > 0: the update runs as dq_ddim_step_sto behind the forward (one more launch per step); needs seed_dev.
+ * x_T may be NULL (needs seed_dev): x_T = dq_randn at draw index 0.  The graph path stages seed and ids inside the workspace; graphs
+ * captured with eta > 0 and eta == 0 are cached apart, the value of eta itself lives in the coefficient tables. */
+int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                      const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                      const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                      int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                      const uint64_t* seed_dev, const int64_t* window_ids_dev);
 
 /* ---- batch formation from an HBM-resident dataset (the step right before the hot path) ------------
  * Replaces, for B (window 1, window 2) pairs, DIAMSDataset.__getitem__'s min-max normalisation (utils/data_loader.py:70-79:
