@@ -214,10 +214,8 @@ struct Ctx {
   // sampling (dq_ddim_sample): the DDIM update rides in the head launch (x_out may alias x_t), and the step-invariant MS1 feature path
   // (unet1d.py:1120-1130) + to_k + RoPE(k) were computed once before the loop
   struct StepIO { const float* x_t = nullptr; float* x_out = nullptr; const float* coef = nullptr; const int* step_ptr = nullptr; int pred_x0 = 0;
-                  bool skip_ms1 = false; bool fused_update = false; bool want_eps = true;
-                  bool prepared = false; };  // prepared: the once-per-parameter-state launches (la_prepare_all, operand images) ran before the loop
+                  bool prologue = false; bool fused_update = false; bool want_eps = true; };  // prologue: unet_prepare and the MS1 path ran before the loop
   StepIO* step_io = nullptr;
-  bool prepare_only = false;  // unet_forward: run just those launches and return
   // dq_train_step: the scalar loss (sum of the MSE kernel's partials) is needed by nobody on the gradient chain: it rides on the side stream
   struct LossSum { const float* partials = nullptr; int count = 0; float scale = 0.f; float* out = nullptr; };
   LossSum loss_sum;
@@ -473,24 +471,28 @@ int res_bwd(const Ctx& c, const ResP& r, const ResBuf& b, const float* inA, floa
 }
 
 
+// the parameter pointers of a LinearAttention layer in a LinAttn, TinyFwd or TinyBwd (b_out: where the descriptor keeps the output bias, if it does)
+template <class T> void la_operands(const Ctx& c, const LAP& l, T& t, const float** b_out = nullptr) {
+  t.w_qkv = c.prm(l.qkv_w); t.w_out = c.prm(l.out_w); t.g_pre = c.prm(l.g_pre); t.g_out = c.prm(l.g_out);
+  if (b_out) *b_out = c.prm(l.out_b);
+}
+
 // The tiny backward (k_tiny.hip) of the two levels with rows of one position: `up` = the first up level (its input gradient goes straight into
 // the bottleneck's layout), otherwise the last down level (with its k3 conv and the Downsample in front of it).  Image slots 4 / 5 of the
 // tiny-image region.  Gradient-arena pointers are filled only when the context has one (the forward builds the images from the weights alone).
-bool tiny_bwd_desc(const Ctx& c, bool up, TinyBwd* out) {
+// Whether a pass takes it is LevelPlan::use_tb_up / use_tb_dn; up_w (LevelPlan::tb_up_w): the Upsample transpose rides along.
+TinyBwd tiny_bwd_desc(const Ctx& c, bool up, bool up_w) {
   const Plan& p = c.p;
   const Arena& a = c.ar;
   const int L = p.levels;
-  if (L < 2 || p.wide_mid || p.mid_n != 1) return false;
   const LevelP& l = up ? p.ups[0] : p.downs[L - 1];
   const LevelBuf& b = up ? a.ups[0] : a.downs[L - 1];
-  if (l.n != 1 || l.la.C != 16 || l.r0.cout != 16 || l.r1.cout != 16) return false;
   TinyBwd t;
   t.params = c.P; t.img = c.w(a.timg) + (int64_t)(up ? 4 : 5) * TINY_IMG_FLOATS;
   t.C = 16; t.rows = c.B * c.RT; t.rows_per_sample = c.RT;
   t.pre = up ? LEVEL_PRE_NONE : LEVEL_PRE_DOWN;
   t.cs = l.r0.cin - l.r0.cout;
-  if (l.r1.cin != l.r0.cin) return false;
-  t.w_qkv = c.prm(l.la.qkv_w); t.w_out = c.prm(l.la.out_w); t.g_pre = c.prm(l.la.g_pre); t.g_out = c.prm(l.la.g_out);
+  la_operands(c, l.la, t);
   t.x = c.w(b.r1.out); t.ypre = c.w(b.la_pre);
   const ResP* rp[2] = {&l.r0, &l.r1};
   const ResBuf* rb[2] = {&b.r0, &b.r1};
@@ -505,8 +507,7 @@ bool tiny_bwd_desc(const Ctx& c, bool up, TinyBwd* out) {
   }
   if (up) {
     // the Upsample conv behind the level (nearest x2 + k3, 16 -> 16): its backward data path in the same launch, its weight gradient on the side stream
-    const bool upt_on = !DQ_DEV_FLAG("DQ_NO_TINY_UPT", '1');  // (dev switch)
-    if (upt_on && !l.last && l.resample.k == 3 && l.resample.cin == 16 && l.resample.cout == 16 && l.n_next == 2) {
+    if (up_w) {
       t.up_w = c.prm(l.resample.w);
       if (c.G) t.dup = c.g(b.rs);
     }
@@ -517,7 +518,6 @@ bool tiny_bwd_desc(const Ctx& c, bool up, TinyBwd* out) {
     }
   } else {
     const LevelP& lp = p.downs[L - 2];
-    if (l.resample.k != 3 || l.resample.cout != 16 || l.resample.cin != 16 || lp.resample.k != 4 || lp.resample.cout != 16 || lp.n != 2) return false;
     t.cp = lp.resample.cin;
     t.post_w = c.prm(l.resample.w); t.stage_w = c.prm(lp.resample.w);
     if (c.G) {
@@ -526,22 +526,19 @@ bool tiny_bwd_desc(const Ctx& c, bool up, TinyBwd* out) {
       t.r0out_g = c.g(b.r0.out);
     }
   }
-  if (!tiny_bwd_usable(t)) return false;
-  *out = t;
-  return true;
+  return t;
 }
 
 // slot: this layer's index in the prepared-weights buffer (la_prepare_all), or -1
 int la_fwd(const Ctx& c, const LAP& l, const float* x, float* y, float* ypre, int rows, int n, int slot = -1) {
   LinAttn a;
-  a.x = x; a.y = y; a.ypre = ypre; a.w_qkv = c.prm(l.qkv_w); a.w_out = c.prm(l.out_w); a.b_out = c.prm(l.out_b);
-  a.g_pre = c.prm(l.g_pre); a.g_out = c.prm(l.g_out); a.C = l.C; a.rows = rows; a.n = n;
+  a.x = x; a.y = y; a.ypre = ypre; la_operands(c, l, a, &a.b_out); a.C = l.C; a.rows = rows; a.n = n;
   if (slot >= 0 && la_short_row(n)) a.prep = c.w(c.ar.la_prep) + (int64_t)slot * LA_PREP_FLOATS;
   return launch_linattn_fwd(a, c.s);
 }
 // W2 = Wo Wv and the MFMA operand image of Wq | Wk of every LinearAttention layer, once per forward (one launch) instead of once
 // per block of every layer's kernel
-int la_prepare_all(const Ctx& c, hipStream_t ps) {
+int la_prepare_all(const Ctx& c, bool prep_ok, hipStream_t ps) {
   const Plan& p = c.p;
   LaPrepItem items[LA_PREP_MAX];
   int count = 0;
@@ -549,7 +546,7 @@ int la_prepare_all(const Ctx& c, hipStream_t ps) {
     items[count] = LaPrepItem{c.prm(l.qkv_w), c.prm(l.out_w), l.C, c.w(c.ar.la_prep) + (int64_t)count * LA_PREP_FLOATS, c.prm(l.g_pre)};
     ++count;
   };
-  if ((int)(p.downs.size() + p.ups.size()) > LA_PREP_MAX) return 0;  // (callers then pass slot -1)
+  if (!prep_ok) return 0;  // (LevelPlan::prep_ok: callers then pass slot -1)
   for (const LevelP& l : p.downs) add(l.la);
   for (const LevelP& l : p.ups) add(l.la);
   // aligned copies of the bottleneck attention's projection weights for the GEMM route (slots 0: q|v, 1: k, 2: to_out), when
@@ -589,11 +586,10 @@ int la_bwd(const Ctx& c, const LAP& l, const LevelBuf& b, const float* x, const 
   LinAttnBwd a;
   a.ypre = c.w(b.la_pre); a.dyp = c.g(b.la_pre); a.dxh = c.g(b.la_tmp);
   a.part = c.w(c.ar.la_part); a.part_floats = c.ar.la_part_floats;
-  a.f.x = x; a.f.w_qkv = c.prm(l.qkv_w); a.f.w_out = c.prm(l.out_w); a.f.b_out = c.prm(l.out_b);
-  a.f.g_pre = c.prm(l.g_pre); a.f.g_out = c.prm(l.g_out); a.f.C = l.C; a.f.rows = rows; a.f.n = n;
+  a.f.x = x; la_operands(c, l, a.f, &a.f.b_out); a.f.C = l.C; a.f.rows = rows; a.f.n = n;
   a.dy = dy; a.dx = dx;
   // W2 of this layer as the forward of this step prepared it (la_prepare_all): same weights, same numbers
-  if (slot >= 0 && la_short_row(n) && (int)(c.p.downs.size() + c.p.ups.size()) <= LA_PREP_MAX) a.f.prep = c.w(c.ar.la_prep) + (int64_t)slot * LA_PREP_FLOATS;
+  if (slot >= 0 && la_short_row(n)) a.f.prep = c.w(c.ar.la_prep) + (int64_t)slot * LA_PREP_FLOATS;
   a.dw_qkv = c.dprm(l.qkv_w); a.dw_out = c.dprm(l.out_w); a.db_out = c.dprm(l.out_b); a.dg_pre = c.dprm(l.g_pre);
   a.dg_out = c.dprm(l.g_out);
   a.dx_store = 1;  // the block's input feeds nothing else: this launch is the only writer of its gradient (not pre-cleared)
@@ -1006,8 +1002,8 @@ int mid_forward(const Ctx& c, const float* rope, bool skip_ms1, bool prep_ok) {
 }
 
 // d(mid2.out) is complete; leaves d(mid_in) and all bottleneck parameter gradients (+=).  grad_x: the caller asked for d loss / d x: what would
-// ride on the side queue then stays on the main stream, as in unet_backward
-int mid_backward(const Ctx& c, const float* rope, bool grad_x) {
+// ride on the side queue then stays on the main stream, as in unet_backward; prep_ok: as for mid_forward, from the same LevelPlan
+int mid_backward(const Ctx& c, const float* rope, bool grad_x, bool prep_ok) {
   const Plan& p = c.p;
   const Arena& a = c.ar;
   const int B = c.B, RT = c.RT;
@@ -1024,7 +1020,7 @@ int mid_backward(const Ctx& c, const float* rope, bool grad_x) {
   // to_out (1x1 + bias) and the residual
   ConvP ao = proj(p.ao_w, p.mid_c, HID);
   ao.b = p.ao_b;
-  const int ws_ok = (int)(p.downs.size() + p.ups.size()) <= LA_PREP_MAX ? 0 : -3;  // aligned weight slots as the forward of this step filled them (0: q|v, 1: k, 2: to_out)
+  const int ws_ok = prep_ok ? 0 : -3;  // aligned weight slots as the forward of this step filled them (0: q|v, 1: k, 2: to_out)
   DQ_TRY(conv_plain_bwd(c, ao, CONV_S1, c.w(a.o), c.g(a.attn_out), mf.out_fused ? nullptr : c.g(a.o), B, RT, RT, 0, ws_ok + 2));  // (fused: the weight / bias gradient only)
   // (d mid1.out = d attn_out [the residual] + the PreNorm path: formed by the PreNorm backward below, which reads d attn_out as its addend --
   // was a k_axpy launch here plus one behind that kernel)
@@ -1082,24 +1078,67 @@ int mid_backward(const Ctx& c, const float* rope, bool grad_x) {
 // ---------------------------------------------------------------------------------------------------------------
 // one launch per level for [the resample conv that produces the level's input] + the level's ResnetBlocks (k_level.hip)
 // ---------------------------------------------------------------------------------------------------------------
-bool level_kernels_enabled() {
-  const bool on = !DQ_DEV_FLAG("DQ_NO_LEVEL_FWD", '1');  // (dev switch)
-  return on;
-}
+// One launch of the walk as Plan and Arena describe it: the input stage, the ResnetBlocks and where their operands lie (arena offsets; -1: none)
 struct LevelCall {
-  int pre = LEVEL_PRE_NONE; const ConvP* pc = nullptr; const float* in = nullptr; float* pre_out = nullptr;
+  int pre = LEVEL_PRE_NONE; const ConvP* pc = nullptr; int64_t in = -1, pre_out = -1;
   int C = 0, n = 0, nblocks = 0;
   const ResP* r[2] = {nullptr, nullptr}; const ResBuf* rb[2] = {nullptr, nullptr};
-  const float* inB[2] = {nullptr, nullptr}; int cinB[2] = {0, 0}; bool write_out[2] = {true, true};
-  const float* cond = nullptr; float cm = 1.f, ca = 0.f;      // LEVEL_PRE_INIT
+  int64_t inB[2] = {-1, -1}; int cinB[2] = {0, 0}; bool write_out[2] = {true, true};
+  const float* x = nullptr; const float* cond = nullptr; float cm = 1.f, ca = 0.f;  // LEVEL_PRE_INIT: the caller's x_t and mixture (the walk sets them)
   const ConvP* head = nullptr; float* eps_out = nullptr;      // head epilogue (final_conv)
 };
-LevelFwd level_desc(const Ctx& c, const LevelCall& lc) {
+// A level whose ResnetBlocks the level kernel takes also computes its own input from the previous level's LinearAttention
+// output (Downsample, unet1d.py:1141): that conv is then not launched and, in inference, its result never exists in memory.
+// Level 0 with `init`: the mixture conditioning + concat + init_conv (unet1d.py:1107-1118) are that launch's input stage.
+LevelCall down_call(const Plan& p, const Arena& a, int lv, bool init) {
+  LevelCall lc;
+  const LevelP& l = p.downs[lv];
+  lc.C = l.r0.cout; lc.n = l.n; lc.nblocks = 2;
+  lc.r[0] = &l.r0; lc.r[1] = &l.r1; lc.rb[0] = &a.downs[lv].r0; lc.rb[1] = &a.downs[lv].r1;
+  if (lv > 0) { lc.pre = LEVEL_PRE_DOWN; lc.pc = &p.downs[lv - 1].resample; lc.in = a.downs[lv - 1].la; lc.pre_out = a.downs[lv - 1].rs; }
+  else if (init) { lc.pre = LEVEL_PRE_INIT; lc.pc = &p.init_conv; lc.pre_out = a.h0; }
+  else lc.in = a.h0;
+  return lc;
+}
+// up path (unet1d.py:1150-1158): first pop = post-attention skip, second pop = post-block1 skip
+LevelCall up_call(const Plan& p, const Arena& a, int ui) {  // ui == L: the final ResnetBlock behind the last level's k3 conv (unet1d.py:1160-1163)
+  LevelCall lc;
+  const int L = p.levels;
+  if (ui < L) {
+    const LevelP& l = p.ups[ui];
+    const int lv = L - 1 - ui, cs = l.r0.cin - l.r0.cout;
+    lc.C = l.r0.cout; lc.n = l.n; lc.nblocks = 2;
+    lc.r[0] = &l.r0; lc.r[1] = &l.r1; lc.rb[0] = &a.ups[ui].r0; lc.rb[1] = &a.ups[ui].r1;
+    lc.inB[0] = a.downs[lv].la; lc.inB[1] = a.downs[lv].r0.out; lc.cinB[0] = lc.cinB[1] = cs;
+    lc.write_out[0] = false;  // (inference: only the second block's output leaves the launch)
+  } else {
+    lc.C = p.fin.cout; lc.n = p.mz; lc.nblocks = 1;
+    lc.r[0] = &p.fin; lc.rb[0] = &a.fin; lc.inB[0] = a.h0; lc.cinB[0] = p.dim;
+  }
+  if (ui == 0) { lc.in = a.mid_back; }
+  else {
+    const LevelP& lp = p.ups[ui - 1];
+    lc.pre = lp.last ? LEVEL_PRE_S1 : LEVEL_PRE_UP; lc.pc = &lp.resample; lc.in = a.ups[ui - 1].la; lc.pre_out = a.ups[ui - 1].rs;
+  }
+  return lc;
+}
+// what the *_usable predicates and level_img_floats read of a descriptor: its shape, and WHETHER a pointer is set (SHAPE_ONLY stands for "set")
+const float SHAPE_ONLY[1] = {0.f};
+LevelFwd level_shape(const LevelCall& lc, int B, int RT) {
   LevelFwd f;
-  f.params = c.P; f.in = lc.in; f.pre = lc.pre; f.nblocks = lc.nblocks; f.C = lc.C; f.rows = c.B * c.RT; f.n = lc.n; f.rows_per_sample = c.RT;
-  if (lc.pc) { f.cp = lc.pc->cin; f.pw = c.prm(lc.pc->w); f.pb = lc.pc->b >= 0 ? c.prm(lc.pc->b) : nullptr; f.pre_out = c.save ? lc.pre_out : nullptr; }
+  f.params = SHAPE_ONLY; f.pre = lc.pre; f.nblocks = lc.nblocks; f.C = lc.C; f.rows = B * RT; f.n = lc.n; f.rows_per_sample = RT;
+  if (lc.pc) f.cp = lc.pc->cin;
+  for (int i = 0; i < lc.nblocks; ++i) { f.blk[i].cinB = lc.cinB[i]; f.blk[i].wr = lc.r[i]->res.cout ? SHAPE_ONLY : nullptr; }
+  return f;
+}
+// img_slot: the launch's slot of the operand-image region (LevelForm::img), or -1
+LevelFwd level_desc(const Ctx& c, const LevelCall& lc, int img_slot = -1) {
+  LevelFwd f = level_shape(lc, c.B, c.RT);
+  f.params = c.P; f.in = lc.in >= 0 ? c.w(lc.in) : lc.x;
+  float* pre_out = lc.pre_out >= 0 ? c.w(lc.pre_out) : nullptr;
+  if (lc.pc) { f.pw = c.prm(lc.pc->w); f.pb = lc.pc->b >= 0 ? c.prm(lc.pc->b) : nullptr; f.pre_out = c.save ? pre_out : nullptr; }
   if (lc.pre == LEVEL_PRE_INIT) {
-    f.cond = lc.cond; f.cm = lc.cm; f.ca = lc.ca; f.ss_init = c.w(c.ar.ss) + c.p.ss_init; f.pre_out = lc.pre_out;
+    f.cond = lc.cond; f.cm = lc.cm; f.ca = lc.ca; f.ss_init = c.w(c.ar.ss) + c.p.ss_init; f.pre_out = pre_out;
     f.cat0_out = c.save ? c.w(c.ar.cat0) : nullptr;  // (train step: kept for init_conv's weight gradient and the input affine's backward)
     if (c.qsample && f.cat0_out) {
       f.in = c.qsample->x0; f.qs_noise = c.qsample->noise; f.qs_ab = c.qsample->alpha_bars; f.qs_t = c.qsample->t; f.qs_norm = c.qsample->normalize;
@@ -1114,15 +1153,169 @@ LevelFwd level_desc(const Ctx& c, const LevelCall& lc) {
       f.eps_out = lc.eps_out;
     }
   }
-  for (int i = 0; i < lc.nblocks; ++i) f.blk[i] = level_block(c, *lc.r[i], *lc.rb[i], lc.inB[i], lc.cinB[i], lc.write_out[i]);
+  for (int i = 0; i < lc.nblocks; ++i)
+    f.blk[i] = level_block(c, *lc.r[i], *lc.rb[i], lc.cinB[i] ? c.w(lc.inB[i]) : nullptr, lc.cinB[i], lc.write_out[i]);
+  if (img_slot >= 0) f.img = c.w(c.ar.wimg) + (int64_t)img_slot * LEVEL_IMG_FLOATS;
   return f;
 }
-bool level_ok(const Ctx& c, const LevelCall& lc) {
-  if (!level_kernels_enabled()) return false;
+
+// Which launch takes each level, decided ONCE per pass: unet_forward, unet_backward and the sampler's prologue build a LevelPlan with level_plan
+// and everything they call reads it.  Nothing else asks a *_usable predicate during the walk, so the backward agrees with what the forward of
+// the same step ran and stored (same Plan, Arena, batch and switches => same plan).
+enum LevelKind { LEVEL_UNFUSED, LEVEL_KERNEL, LEVEL_TINY };  // res_fwd calls | k_level_fwd | k_tiny_fwd
+struct LevelForm {
+  LevelKind kind = LEVEL_UNFUSED;
+  int img = -1;  // operand-image slot: LEVEL_KERNEL in Arena::wimg (level on the way down, L + ui on the way up, 2 L the head; -1: the kernel gathers
+                 // its weights itself), LEVEL_TINY in Arena::timg (0..3; slots 4, 5 are the backward's)
+  // LEVEL_TINY at n == 1: the LinearAttention rides along; the last down level also applies its k3 conv and writes the bottleneck's (B, C, RT)
+  // layout directly (no k_conv_fwd, no k_fold); the first up level reads that layout (no k_fold behind the bottleneck either)
+  bool la = false, post_w = false, in_folded = false;
+  bool resample = true;  // the level's own resample conv is launched (false: it is the input stage of the next launch, or post_w)
+};
+struct LevelPlan {
+  LevelForm dn[16], up[17];  // up[L]: the final ResnetBlock (build_plan: L <= 10)
+  bool prep_ok = false;      // la_prepare_all has a slot for every LinearAttention layer (and fills the aligned weight slots of the bottleneck's GEMMs)
+  bool init_fused = false;   // level 0's launch forms its own input (LEVEL_PRE_INIT)
+  bool head_shape = false, head_train = false;  // the final block's launch can apply final_conv; head_train: and the loss + d fin.out of a train step
+  bool use_tb_up = false, use_tb_dn = false, tb_up_w = false;  // backward of the first up / last down level in one k_tiny_bwd launch; the Upsample transpose rides along
+};
+bool level_ok(const LevelCall& lc, int B, int RT) {
+  if (DQ_DEV_FLAG("DQ_NO_LEVEL_FWD", '1')) return false;  // (dev switch)
   for (int i = 0; i < lc.nblocks; ++i)
     if (lc.r[i]->cout != lc.C || lc.r[i]->cin != lc.C + lc.cinB[i]) return false;
   if (lc.pc && (lc.pc->cout != lc.C || lc.pc->b < 0)) return false;
-  return level_fwd_usable(level_desc(c, lc));
+  return level_fwd_usable(level_shape(lc, B, RT));
+}
+bool tiny_bwd_ok(const Plan& p, int B, int RT, bool up, bool* up_w) {
+  const int L = p.levels;
+  if (L < 2 || p.wide_mid || p.mid_n != 1) return false;
+  const LevelP& l = up ? p.ups[0] : p.downs[L - 1];
+  const ConvP& rs = l.resample;
+  if (l.n != 1 || l.la.C != 16 || l.r0.cout != 16 || l.r1.cout != 16 || l.r1.cin != l.r0.cin) return false;
+  TinyBwd t;
+  t.params = SHAPE_ONLY; t.C = 16; t.rows = B * RT; t.rows_per_sample = RT; t.pre = up ? LEVEL_PRE_NONE : LEVEL_PRE_DOWN; t.cs = l.r0.cin - l.r0.cout;
+  if (!up) {
+    const LevelP& lp = p.downs[L - 2];
+    if (rs.k != 3 || rs.cout != 16 || rs.cin != 16 || lp.resample.k != 4 || lp.resample.cout != 16 || lp.n != 2) return false;
+    t.cp = lp.resample.cin;
+  }
+  if (!tiny_bwd_usable(t)) return false;
+  const bool upt_on = !DQ_DEV_FLAG("DQ_NO_TINY_UPT", '1');  // (dev switch)
+  if (up) *up_w = upt_on && !l.last && rs.k == 3 && rs.cin == 16 && rs.cout == 16 && l.n_next == 2;  // the Upsample conv behind the level (nearest x2 + k3, 16 -> 16)
+  return true;
+}
+// save: the pass keeps what a backward needs (a backward itself: true); twin: it has the gradient arena at hand
+LevelPlan level_plan(const Plan& p, const Arena& a, int B, int RT, bool save, bool twin) {
+  LevelPlan lp;
+  const int L = p.levels;
+  lp.prep_ok = (int)(p.downs.size() + p.ups.size()) <= LA_PREP_MAX;
+  // the levels with rows of 1 or 2 positions (k_tiny.hip): stage + both ResnetBlocks as a chain of dense layers
+  const bool mid1 = !p.wide_mid && p.mid_n == 1;
+  int n_tiny = 0;
+  auto tiny = [&](LevelForm& f, const LevelCall& lc, bool la, bool post_w, bool in_folded) {
+    TinyFwd t;
+    t.lv = level_shape(lc, B, RT); t.la = la; t.post_w = post_w ? SHAPE_ONLY : nullptr; t.in_folded = in_folded;
+    if (L > 16 || n_tiny >= 4 || !tiny_fwd_usable(t)) return;
+    f.kind = LEVEL_TINY; f.img = n_tiny++; f.la = la; f.post_w = post_w; f.in_folded = in_folded;
+  };
+  for (int lv = 1; lv < L; ++lv) {
+    const LevelP& l = p.downs[lv];
+    const bool la = l.n == 1 && lv == L - 1 && mid1 && l.resample.k == 3 && l.resample.b >= 0 && l.resample.cout == l.la.C;
+    tiny(lp.dn[lv], down_call(p, a, lv, false), la, la, false);
+  }
+  for (int ui = 0; ui < L; ++ui) {
+    const bool la = p.ups[ui].n == 1 && ui == 0 && mid1;
+    tiny(lp.up[ui], up_call(p, a, ui), la, false, la);
+  }
+  // everything else the level kernel can take (k_level.hip), with an operand image when the region has a slot for every launch
+  auto level = [&](LevelForm& f, const LevelCall& lc, int slot) {
+    if (f.kind == LEVEL_TINY || !level_ok(lc, B, RT)) return;
+    f.kind = LEVEL_KERNEL;
+    if (2 * L + 1 <= LEVEL_IMG_MAX && level_img_floats(level_shape(lc, B, RT)) <= LEVEL_IMG_FLOATS) f.img = slot;
+  };
+  const bool train_init = !DQ_DEV_FLAG("DQ_NO_TRAIN_INIT", '1');  // (dev switch)
+  const bool init = (!save || train_init) && p.dim == 4 && p.init_conv.cout == 4 && p.init_conv.cin == 2 && p.init_conv.k == 7 && p.init_conv.b >= 0;
+  level(lp.dn[0], down_call(p, a, 0, init), 0);
+  lp.init_fused = init && lp.dn[0].kind == LEVEL_KERNEL;
+  for (int lv = 1; lv < L; ++lv) level(lp.dn[lv], down_call(p, a, lv, false), lv);
+  for (int ui = 0; ui <= L; ++ui) level(lp.up[ui], up_call(p, a, ui), L + ui);
+  // a launch that is not a chain of res_fwd calls applies the resample conv in front of it itself
+  for (int lv = 0; lv < L; ++lv) lp.dn[lv].resample = lv + 1 < L ? lp.dn[lv + 1].kind == LEVEL_UNFUSED : !lp.dn[lv].post_w;
+  for (int ui = 0; ui < L; ++ui) lp.up[ui].resample = lp.up[ui + 1].kind == LEVEL_UNFUSED;
+  // head (unet1d.py:1160-1166)
+  lp.head_shape = p.dim == 4 && p.final_conv.cout == 1 && p.final_conv.cin == 4 && p.final_conv.k == 1 && p.final_conv.b >= 0 && lp.up[L].kind == LEVEL_KERNEL;
+  // (built for the (4, k3 conv, 4) launch; one partial sum per wave: beyond a resident round the grid is B workgroups)
+  lp.head_train = save && twin && lp.head_shape && p.ups[L - 1].last && p.ups[L - 1].resample.cin == 4 && (int64_t)B * 4 <= LEVEL_LOSS_PARTS;
+  // the tiny backward reads what the tiny forward of the same level stored, through images the same forward built
+  lp.use_tb_up = save && lp.up[0].kind == LEVEL_TINY && tiny_bwd_ok(p, B, RT, true, &lp.tb_up_w);
+  lp.use_tb_dn = save && lp.dn[L - 1].kind == LEVEL_TINY && tiny_bwd_ok(p, B, RT, false, nullptr);
+  return lp;
+}
+
+// the k_tiny_fwd launch of a LEVEL_TINY level
+TinyFwd tiny_desc(const Ctx& c, const LevelPlan& lp, bool up, int i) {
+  const Arena& a = c.ar;
+  const LevelForm& f = up ? lp.up[i] : lp.dn[i];
+  const LevelP& l = up ? c.p.ups[i] : c.p.downs[i];
+  const LevelBuf& b = up ? a.ups[i] : a.downs[i];
+  TinyFwd t;
+  t.lv = level_desc(c, up ? up_call(c.p, a, i) : down_call(c.p, a, i, false));
+  t.img = c.w(a.timg) + (int64_t)f.img * TINY_IMG_FLOATS;
+  if (f.la) { t.la = 1; la_operands(c, l.la, t, &t.b_out); t.la_y = c.w(b.la); t.la_ypre = c.save ? c.w(b.la_pre) : nullptr; }
+  if (f.post_w) { t.post_w = c.prm(l.resample.w); t.post_b = c.prm(l.resample.b); t.post_out = c.w(a.mid_in); }
+  if (f.in_folded) { t.in_folded = 1; t.lv.in = c.w(a.mid2.out); t.in_copy = c.save ? c.w(a.mid_back) : nullptr; }
+  return t;
+}
+
+// The launches that depend on the parameter values only -- W2 / the q | k operand images of the LinearAttention layers, the MFMA operand
+// images of the level and tiny launches, the transposed images of the tiny backward -- once per parameter state: every forward in training,
+// once per dq_ddim_sample call.  ps: the stream of all but the level images (the side stream of a forked train step); ev_prep (forked only):
+// receives an event behind la_prepare_all -- level 0's LinearAttention waits for THAT, the tiny images are needed five levels later.
+int unet_prepare(const Ctx& c, const LevelPlan& lp, hipStream_t ps, hipEvent_t* ev_prep = nullptr) {
+  const Plan& p = c.p;
+  const Arena& a = c.ar;
+  const int L = p.levels;
+  DQ_TRY(la_prepare_all(c, lp.prep_ok, ps));
+  if (ev_prep) DQ_TRY(side_mark(c, ev_prep));
+  LevelFwd calls[LEVEL_IMG_MAX];
+  int nc = 0, nt = 0, nb = 0;
+  for (int lv = 0; lv < L; ++lv)
+    if (lp.dn[lv].kind == LEVEL_KERNEL && lp.dn[lv].img >= 0) calls[nc++] = level_desc(c, down_call(p, a, lv, lp.init_fused), lp.dn[lv].img);
+  for (int ui = 0; ui <= L; ++ui)
+    if (lp.up[ui].kind == LEVEL_KERNEL && lp.up[ui].img >= 0) calls[nc++] = level_desc(c, up_call(p, a, ui), lp.up[ui].img);
+  DQ_TRY(launch_level_images(calls, nc, c.s));
+  TinyFwd tc[TINY_IMG_MAX];
+  for (int lv = 0; lv < L; ++lv) if (lp.dn[lv].kind == LEVEL_TINY) tc[nt++] = tiny_desc(c, lp, false, lv);
+  for (int ui = 0; ui < L; ++ui) if (lp.up[ui].kind == LEVEL_TINY) tc[nt++] = tiny_desc(c, lp, true, ui);
+  DQ_TRY(launch_tiny_images(tc, nt, ps));
+  if (!c.save) return 0;
+  TinyBwd tb[2];
+  if (lp.use_tb_up) tb[nb++] = tiny_bwd_desc(c, true, lp.tb_up_w);
+  if (lp.use_tb_dn) tb[nb++] = tiny_bwd_desc(c, false, false);
+  return launch_tiny_bwd_images(tb, nb, ps);
+}
+
+// MS1 features (unet1d.py:1120-1130) on stream s: (B, RT, M1) -> conv k7 -> GELU -> conv k1 = ms1f; what the backward reads is kept only when c.save.
+// norm (one channel): the normalised chromatogram is formed here (else k_prep_inputs left it in ms1n)
+int ms1_features(const Ctx& c, const float* ms1, float cm, float ca, bool norm, hipStream_t s) {
+  const Plan& p = c.p;
+  const Arena& a = c.ar;
+  const int B = c.B, RT = c.RT, M1 = p.ms1_channels;
+  if (M1 > 1) {  // (B, RT, M1) read as it is: k_ms1_feat.hip
+    Ms1FeatFwd f;
+    f.ms1 = ms1; f.w = c.prm(p.ms1_c0.w); f.bias = c.prm(p.ms1_c0.b); f.cm = cm; f.ca = ca; f.B = B; f.RT = RT; f.M1 = M1;
+    f.ms1n_out = c.save ? c.w(a.ms1n) : nullptr; f.u_out = c.save ? c.w(a.ms1_u) : nullptr; f.a_out = c.w(a.ms1_a);
+    DQ_TRY(launch_ms1_feat_fwd(f, s));
+  } else {
+    if (norm) DQ_TRY(launch_ms1_norm(ms1, cm, ca, c.w(a.ms1n), (int64_t)B * RT, s));
+    ConvFwd f;
+    f.inA = c.w(a.ms1n); f.cinA = 1; f.w = c.prm(p.ms1_c0.w); f.bias = c.prm(p.ms1_c0.b); f.cout = p.cond_dim; f.K = 7;
+    f.rows = B; f.n_in = RT; f.n_out = RT; f.u_out = c.save ? c.w(a.ms1_u) : nullptr; f.y_out = c.w(a.ms1_a); f.act = ACT_GELU;
+    DQ_TRY(launch_conv_fwd(f, s));
+  }
+  Ctx cs = c;
+  cs.s = s;
+  return conv_plain_fwd(cs, p.ms1_c1, CONV_S1, c.w(a.ms1_a), c.w(a.ms1f), B, RT, RT);
 }
 
 int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t* t, int t_scalar, const float* init_cond,
@@ -1131,256 +1324,113 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
   const Plan& p = c.p;
   const Arena& a = c.ar;
   const int B = c.B, RT = c.RT, R = B * RT, L = p.levels;
-  const bool prep_ok = (int)(p.downs.size() + p.ups.size()) <= LA_PREP_MAX;
-  // A level whose ResnetBlocks the level kernel takes also computes its own input from the previous level's LinearAttention
-  // output (Downsample, unet1d.py:1141): that conv is then not launched and, in inference, its result never exists in memory.
-  // Level 0 in inference: the mixture conditioning + concat + init_conv (unet1d.py:1107-1118) are that launch's input stage.
-  auto down_call = [&](int lv) {
-    LevelCall lc;
-    const LevelP& l = p.downs[lv];
-    lc.C = l.r0.cout; lc.n = l.n; lc.nblocks = 2;
-    lc.r[0] = &l.r0; lc.r[1] = &l.r1; lc.rb[0] = &a.downs[lv].r0; lc.rb[1] = &a.downs[lv].r1;
-    if (lv == 0) {
-      const bool train_init = !DQ_DEV_FLAG("DQ_NO_TRAIN_INIT", '1');  // (dev switch)
-      if ((!c.save || train_init) && p.dim == 4 && p.init_conv.cout == 4 && p.init_conv.cin == 2 && p.init_conv.k == 7 && p.init_conv.b >= 0) {
-        lc.pre = LEVEL_PRE_INIT; lc.pc = &p.init_conv; lc.in = x; lc.cond = init_cond; lc.cm = cm; lc.ca = ca; lc.pre_out = c.w(a.h0);
-      } else {
-        lc.in = c.w(a.h0);
-      }
-    } else { lc.pre = LEVEL_PRE_DOWN; lc.pc = &p.downs[lv - 1].resample; lc.in = c.w(a.downs[lv - 1].la); lc.pre_out = c.w(a.downs[lv - 1].rs); }
-    return lc;
-  };
-  const bool init_fused = down_call(0).pre == LEVEL_PRE_INIT && level_ok(c, down_call(0));
-  const bool skip_ms1 = c.step_io && c.step_io->skip_ms1;
-  const int M1 = p.ms1_channels;
-  // up path (unet1d.py:1150-1158): first pop = post-attention skip, second pop = post-block1 skip
-  auto up_call = [&](int ui) {  // ui == L: the final ResnetBlock behind the last level's k3 conv (unet1d.py:1160-1163)
-    LevelCall lc;
-    if (ui < L) {
-      const LevelP& l = p.ups[ui];
-      const int lv = L - 1 - ui, cs = l.r0.cin - l.r0.cout;
-      lc.C = l.r0.cout; lc.n = l.n; lc.nblocks = 2;
-      lc.r[0] = &l.r0; lc.r[1] = &l.r1; lc.rb[0] = &a.ups[ui].r0; lc.rb[1] = &a.ups[ui].r1;
-      lc.inB[0] = c.w(a.downs[lv].la); lc.inB[1] = c.w(a.downs[lv].r0.out); lc.cinB[0] = lc.cinB[1] = cs;
-      lc.write_out[0] = false;  // (inference: only the second block's output leaves the launch)
-    } else {
-      lc.C = p.fin.cout; lc.n = p.mz; lc.nblocks = 1;
-      lc.r[0] = &p.fin; lc.rb[0] = &a.fin; lc.inB[0] = c.w(a.h0); lc.cinB[0] = p.dim;
-    }
-    if (ui == 0) { lc.in = c.w(a.mid_back); }
-    else {
-      const LevelP& lp = p.ups[ui - 1];
-      lc.pre = lp.last ? LEVEL_PRE_S1 : LEVEL_PRE_UP; lc.pc = &lp.resample; lc.in = c.w(a.ups[ui - 1].la); lc.pre_out = c.w(a.ups[ui - 1].rs);
-    }
-    return lc;
-  };
-  // The launches that depend on the parameter values only -- W2 / the q | k operand images of the LinearAttention layers, the MFMA operand
-  // images of the level kernels (slot = level on the way down, L + ui on the way up, 2 L = the head) -- run once per parameter state:
-  // every forward in training, once per dq_ddim_sample call (its prologue calls this function with prepare_only).
-  // The levels with rows of 1 or 2 positions (k_tiny.hip): stage + both ResnetBlocks as a chain of dense layers; at n == 1 the (linear)
-  // LinearAttention rides along, the last down level also applies its k3 conv and writes the bottleneck's (B, C, RT) layout directly
-  // (no k_conv_fwd, no k_fold), and the first up level reads that layout (no k_fold behind the bottleneck either).
-  int tiny_dn[16], tiny_up[16], n_tiny = 0;
-  auto tiny_down = [&](int lv) {
-    TinyFwd t;
-    const LevelP& l = p.downs[lv];
-    t.lv = level_desc(c, down_call(lv));
-    if (l.n == 1 && lv == L - 1 && !p.wide_mid && p.mid_n == 1 && l.resample.k == 3 && l.resample.b >= 0 && l.resample.cout == l.la.C) {
-      t.la = 1; t.w_qkv = c.prm(l.la.qkv_w); t.w_out = c.prm(l.la.out_w); t.b_out = c.prm(l.la.out_b); t.g_pre = c.prm(l.la.g_pre); t.g_out = c.prm(l.la.g_out);
-      t.la_y = c.w(a.downs[lv].la); t.la_ypre = c.save ? c.w(a.downs[lv].la_pre) : nullptr;
-      t.post_w = c.prm(l.resample.w); t.post_b = c.prm(l.resample.b); t.post_out = c.w(a.mid_in);
-    }
-    return t;
-  };
-  auto tiny_upc = [&](int ui) {
-    TinyFwd t;
-    const LevelP& l = p.ups[ui];
-    t.lv = level_desc(c, up_call(ui));
-    if (l.n == 1 && ui == 0 && !p.wide_mid && p.mid_n == 1) {
-      t.la = 1; t.w_qkv = c.prm(l.la.qkv_w); t.w_out = c.prm(l.la.out_w); t.b_out = c.prm(l.la.out_b); t.g_pre = c.prm(l.la.g_pre); t.g_out = c.prm(l.la.g_out);
-      t.la_y = c.w(a.ups[ui].la); t.la_ypre = c.save ? c.w(a.ups[ui].la_pre) : nullptr;
-      t.in_folded = 1; t.lv.in = c.w(a.mid2.out); t.in_copy = c.save ? c.w(a.mid_back) : nullptr;
-    }
-    return t;
-  };
-  for (int lv = 0; lv < L && lv < 16; ++lv) {
-    tiny_dn[lv] = -1;
-    if (lv > 0 && L <= 16 && n_tiny < 4 && tiny_fwd_usable(tiny_down(lv))) tiny_dn[lv] = n_tiny++;  // (slots 4, 5: the backward's images)
-  }
-  for (int ui = 0; ui < L && ui < 16; ++ui) {
-    tiny_up[ui] = -1;
-    if (L <= 16 && n_tiny < 4 && tiny_fwd_usable(tiny_upc(ui))) tiny_up[ui] = n_tiny++;
-  }
-  auto tiny_img = [&](int slot) -> const float* { return c.w(a.timg) + (int64_t)slot * TINY_IMG_FLOATS; };
-  auto is_tiny_dn = [&](int lv) { return lv < L && lv < 16 && tiny_dn[lv] >= 0; };
-  auto is_tiny_up = [&](int ui) { return ui < L && ui < 16 && tiny_up[ui] >= 0; };
-  const bool imgs_ok = 2 * L + 1 <= LEVEL_IMG_MAX;
-  auto img_slot = [&](int slot) -> const float* { return imgs_ok ? c.w(a.wimg) + (int64_t)slot * LEVEL_IMG_FLOATS : nullptr; };
-  auto with_img = [&](const LevelCall& lc, int slot) {
-    LevelFwd f = level_desc(c, lc);
-    f.img = img_slot(slot);
-    if (f.img && level_img_floats(f) > LEVEL_IMG_FLOATS) f.img = nullptr;
-    return f;
-  };
+  const LevelPlan lp = level_plan(p, a, B, RT, c.save, c.G != nullptr);
+  const bool skip_ms1 = c.step_io && c.step_io->prologue;  // the sampler's prologue ran: the once-per-parameter-state launches, the MS1 features, to_k, RoPE(k)
   // Training steps (dq_train_step: side stream + gradient twin at hand): what the first level does not wait for runs on the side stream --
   // the LinearAttention / tiny-level operand preparation, the MS1 feature path (needed at the bottleneck) and the clearing of the
   // gradient twin's accumulated-into region (needed by the backward) were ~55 us at the head of the main queue, in front of or between
   // launches that do not depend on them.  One event forks; the main stream waits for `ev_prep` in front of the first LinearAttention and
   // for `ev_rest` in front of the first launch that reads the MS1 features.
   const bool fwd_fork_on = !DQ_DEV_FLAG("DQ_NO_FWD_FORK", '1');  // (dev switch)
-  const bool fwd_fork = fwd_fork_on && c.owner && c.save && c.G && !c.step_io && !c.prepare_only;
+  const bool fwd_fork = fwd_fork_on && c.owner && c.save && c.G && !c.step_io;
   hipStream_t ps = c.s;
   hipEvent_t ev_prep = nullptr, ev_rest = nullptr;
-  bool wait_prep = false, wait_rest = false;
+  bool wait_prep = fwd_fork, wait_rest = false;
   if (fwd_fork) { DQ_TRY(fork_side(c)); ps = c.owner->side_stream; }
-  if (!(c.step_io && c.step_io->prepared)) {
-    DQ_TRY(la_prepare_all(c, ps));
-    if (fwd_fork) { DQ_TRY(side_mark(c, &ev_prep)); wait_prep = true; }  // (level 0's LinearAttention waits for THIS; the tiny images below are needed five levels later: ev_rest)
-    LevelFwd calls[LEVEL_IMG_MAX];
-    int nc = 0;
-    for (int lv = 0; lv < L; ++lv)
-      if (!is_tiny_dn(lv) && level_ok(c, down_call(lv))) { const LevelFwd f = with_img(down_call(lv), lv); if (f.img) calls[nc++] = f; }
-    for (int ui = 0; ui <= L; ++ui)
-      if (!is_tiny_up(ui) && level_ok(c, up_call(ui))) { const LevelFwd f = with_img(up_call(ui), L + ui); if (f.img) calls[nc++] = f; }
-    DQ_TRY(launch_level_images(calls, nc, c.s));
-    TinyFwd tc[TINY_IMG_MAX];
-    int nt = 0;
-    for (int lv = 0; lv < L; ++lv) if (is_tiny_dn(lv)) { tc[nt] = tiny_down(lv); tc[nt].img = tiny_img(tiny_dn[lv]); ++nt; }
-    for (int ui = 0; ui < L; ++ui) if (is_tiny_up(ui)) { tc[nt] = tiny_upc(ui); tc[nt].img = tiny_img(tiny_up[ui]); ++nt; }
-    DQ_TRY(launch_tiny_images(tc, nt, ps));
-    if (c.save) {  // the transposed images of the tiny backward (same parameter state)
-      TinyBwd tb[2];
-      int nb = 0;
-      if (is_tiny_up(0) && tiny_bwd_desc(c, true, &tb[nb])) ++nb;
-      if (is_tiny_dn(L - 1) && tiny_bwd_desc(c, false, &tb[nb])) ++nb;
-      DQ_TRY(launch_tiny_bwd_images(tb, nb, ps));
-    }
-  }
-  if (c.prepare_only) return 0;
-  if (fwd_fork && !wait_prep) { DQ_TRY(side_mark(c, &ev_prep)); wait_prep = true; }  // (a prepared sampling loop does not come here with a fork)
-  // K1: time embedding + every scale/shift head (unet1d.py:1105, 315-318, 677)
+  if (!skip_ms1) DQ_TRY(unet_prepare(c, lp, ps, fwd_fork ? &ev_prep : nullptr));  // (a fork has no step_io: it always prepares)
+  // ---- input stage.  K1: time embedding + every scale/shift head (unet1d.py:1105, 315-318, 677)
   DQ_TRY(launch_time_embed_fwd(p, dt, c.P, t, t_scalar, c.w(a.tbuf), c.w(a.ss), B, step_tab, step_ptr, c.s));
-  // K2: mixture conditioning + concat (unet1d.py:1107-1115), then init_conv k7 (:1117)
-  if (c.qsample && !(init_fused && c.save))  // (the INIT stage of a train step forms x_t itself)
+  // K2: mixture conditioning + concat (unet1d.py:1107-1115), then init_conv k7 (:1117) -- level 0's INIT stage, or two launches here
+  if (c.qsample && !(lp.init_fused && c.save))  // (the INIT stage of a train step forms x_t itself)
     DQ_TRY(launch_q_sample(c.qsample->alpha_bars, c.qsample->x0, c.qsample->t, c.qsample->noise, const_cast<float*>(x), B, c.qsample->per, c.qsample->normalize, c.s));
-  if (init_fused) {
-    if (!skip_ms1 && M1 == 1) DQ_TRY(launch_ms1_norm(attn_cond, cm, ca, c.w(a.ms1n), (int64_t)B * RT, ps));  // (ps: the side stream of a forked train step, with the MS1 path)
-  } else {
-    // (forked: the MS1 normalisation goes with the MS1 path to the side stream)
-    DQ_TRY(launch_prep_inputs(x, init_cond, attn_cond, c.w(a.ss), p.ss_total, p.ss_init, cm, ca, c.w(a.cat0), (fwd_fork || M1 > 1) ? nullptr : c.w(a.ms1n), B, RT, p.mz, c.s));
+  const bool ms1n_here = !lp.init_fused && !fwd_fork && p.ms1_channels == 1;  // (forked: the MS1 normalisation goes with the MS1 path to the side stream)
+  if (!lp.init_fused) {
+    DQ_TRY(launch_prep_inputs(x, init_cond, attn_cond, c.w(a.ss), p.ss_total, p.ss_init, cm, ca, c.w(a.cat0), ms1n_here ? c.w(a.ms1n) : nullptr, B, RT, p.mz, c.s));
     DQ_TRY(conv_plain_fwd(c, p.init_conv, CONV_S1, c.w(a.cat0), c.w(a.h0), R, p.mz, p.mz));
   }
-  // K3: MS1 features (unet1d.py:1120-1130): (B,1,RT) -> conv k7 -> GELU -> conv k1
-  if (!skip_ms1) {
-    Ctx cs = c;
-    cs.s = ps;
-    if (M1 > 1) {  // (B, RT, M1) read as it is: k_ms1_feat.hip
-      Ms1FeatFwd f;
-      f.ms1 = attn_cond; f.w = c.prm(p.ms1_c0.w); f.bias = c.prm(p.ms1_c0.b); f.cm = cm; f.ca = ca; f.B = B; f.RT = RT; f.M1 = M1;
-      f.ms1n_out = c.save ? c.w(a.ms1n) : nullptr; f.u_out = c.save ? c.w(a.ms1_u) : nullptr; f.a_out = c.w(a.ms1_a);
-      DQ_TRY(launch_ms1_feat_fwd(f, ps));
-    } else {
-      if (fwd_fork && !init_fused) DQ_TRY(launch_ms1_norm(attn_cond, cm, ca, c.w(a.ms1n), (int64_t)B * RT, ps));
-      ConvFwd f;
-      f.inA = c.w(a.ms1n); f.cinA = 1; f.w = c.prm(p.ms1_c0.w); f.bias = c.prm(p.ms1_c0.b); f.cout = p.cond_dim; f.K = 7;
-      f.rows = B; f.n_in = RT; f.n_out = RT; f.u_out = c.save ? c.w(a.ms1_u) : nullptr; f.y_out = c.w(a.ms1_a); f.act = ACT_GELU;
-      DQ_TRY(launch_conv_fwd(f, ps));
-    }
-    DQ_TRY(conv_plain_fwd(cs, p.ms1_c1, CONV_S1, c.w(a.ms1_a), c.w(a.ms1f), B, RT, RT));
-  }
+  // K3: MS1 features, unless the sampling prologue formed them
+  if (!skip_ms1) DQ_TRY(ms1_features(c, attn_cond, cm, ca, !ms1n_here, ps));
   if (fwd_fork) {
     DQ_TRY(launch_zero(c.G, a.zero_floats, ps));  // (unet_backward skips its own clearing: dq_plan::twin_zeroed)
     c.owner->twin_zeroed = c.G;
     DQ_TRY(side_mark(c, &ev_rest));
     wait_rest = true;
   }
-  // down path (unet1d.py:1134-1142)
+  // ---- down path (unet1d.py:1134-1142)
   const float* cur = c.w(a.h0);
-  bool mid_in_done = false;
   for (int lv = 0; lv < L; ++lv) {
     const LevelP& l = p.downs[lv];
     const LevelBuf& b = a.downs[lv];
+    const LevelForm& f = lp.dn[lv];
     const int C = l.r0.cin;
-    const LevelCall lc = down_call(lv);
-    bool la_done = false;
-    if (is_tiny_dn(lv)) {
+    if (f.kind == LEVEL_TINY) {
       if (wait_rest) { DQ_HIP_OK(hipStreamWaitEvent(c.s, ev_rest, 0)); wait_rest = false; c.owner->side_used = false; }  // (its operand image came from the side stream)
-      TinyFwd t = tiny_down(lv);
-      t.img = tiny_img(tiny_dn[lv]);
-      DQ_TRY(launch_tiny_fwd(t, c.s));
-      la_done = t.la != 0;
-      if (t.post_w) { mid_in_done = true; continue; }  // (the last level: its k3 conv went into the bottleneck's layout)
-    } else if (level_ok(c, lc)) {
-      DQ_TRY(launch_level_fwd(with_img(lc, lv), c.s));
+      DQ_TRY(launch_tiny_fwd(tiny_desc(c, lp, false, lv), c.s));
+      if (f.post_w) continue;  // (the last level: its k3 conv went into the bottleneck's layout)
+    } else if (f.kind == LEVEL_KERNEL) {
+      LevelCall lc = down_call(p, a, lv, lp.init_fused);
+      if (lc.pre == LEVEL_PRE_INIT) { lc.x = x; lc.cond = init_cond; lc.cm = cm; lc.ca = ca; }
+      DQ_TRY(launch_level_fwd(level_desc(c, lc, f.img), c.s));
     } else {
       DQ_TRY(res_fwd(c, l.r0, b.r0, cur, C, nullptr, 0, R, l.n, RT));
       DQ_TRY(res_fwd(c, l.r1, b.r1, c.w(b.r0.out), C, nullptr, 0, R, l.n, RT));
     }
     if (wait_prep) { DQ_HIP_OK(hipStreamWaitEvent(c.s, ev_prep, 0)); wait_prep = false; }  // (in front of lv 0's LinearAttention: the tiny levels come later)
-    if (!la_done) DQ_TRY(la_fwd(c, l.la, c.w(b.r1.out), c.w(b.la), c.save ? c.w(b.la_pre) : nullptr, R, l.n, prep_ok ? lv : -1));
-    if (lv + 1 < L && (is_tiny_dn(lv + 1) || level_ok(c, down_call(lv + 1)))) continue;  // the next level's launch applies this level's Downsample itself
+    if (!f.la) DQ_TRY(la_fwd(c, l.la, c.w(b.r1.out), c.w(b.la), c.save ? c.w(b.la_pre) : nullptr, R, l.n, lp.prep_ok ? lv : -1));
+    if (!f.resample) continue;  // the next level's launch applies this level's Downsample itself
     DQ_TRY(conv_plain_fwd(c, l.resample, l.last ? CONV_S1 : CONV_DOWN, c.w(b.la), c.w(b.rs), R, l.n, l.n_next));
     cur = c.w(b.rs);
   }
-  // bottleneck (unet1d.py:1144-1148)
+  // ---- bottleneck (unet1d.py:1144-1148)
   if (wait_rest) { DQ_HIP_OK(hipStreamWaitEvent(c.s, ev_rest, 0)); wait_rest = false; c.owner->side_used = false; }
   if (p.wide_mid) {
     DQ_TRY(mid_forward_wide(c, rope, cur));
   } else {
-    if (!mid_in_done) DQ_TRY(launch_fold(cur, c.w(a.mid_in), B, RT, p.mid_c, 1, 0, c.s));
-    DQ_TRY(mid_forward(c, rope, skip_ms1, prep_ok));
-    if (!(is_tiny_up(0) && tiny_upc(0).in_folded)) DQ_TRY(launch_fold(c.w(a.mid2.out), c.w(a.mid_back), B, RT, p.mid_c, 0, 0, c.s));
+    if (!lp.dn[L - 1].post_w) DQ_TRY(launch_fold(cur, c.w(a.mid_in), B, RT, p.mid_c, 1, 0, c.s));
+    DQ_TRY(mid_forward(c, rope, skip_ms1, lp.prep_ok));
+    if (!lp.up[0].in_folded) DQ_TRY(launch_fold(c.w(a.mid2.out), c.w(a.mid_back), B, RT, p.mid_c, 0, 0, c.s));
   }
+  // ---- up path (unet1d.py:1150-1158)
   cur = c.w(a.mid_back);
   for (int ui = 0; ui < L; ++ui) {
     const LevelP& l = p.ups[ui];
     const LevelBuf& b = a.ups[ui];
+    const LevelForm& f = lp.up[ui];
     const int lv = L - 1 - ui;
     const int cx = l.r0.cout, cs = l.r0.cin - l.r0.cout;
-    const LevelCall lc = up_call(ui);
-    bool la_done = false;
-    if (is_tiny_up(ui)) {
-      TinyFwd t = tiny_upc(ui);
-      t.img = tiny_img(tiny_up[ui]);
-      DQ_TRY(launch_tiny_fwd(t, c.s));
-      la_done = t.la != 0;
-    } else if (level_ok(c, lc)) {
-      DQ_TRY(launch_level_fwd(with_img(lc, L + ui), c.s));
+    if (f.kind == LEVEL_TINY) {
+      DQ_TRY(launch_tiny_fwd(tiny_desc(c, lp, true, ui), c.s));
+    } else if (f.kind == LEVEL_KERNEL) {
+      DQ_TRY(launch_level_fwd(level_desc(c, up_call(p, a, ui), f.img), c.s));
     } else {
       DQ_TRY(res_fwd(c, l.r0, b.r0, cur, cx, c.w(a.downs[lv].la), cs, R, l.n, RT));
       DQ_TRY(res_fwd(c, l.r1, b.r1, c.w(b.r0.out), cx, c.w(a.downs[lv].r0.out), cs, R, l.n, RT));
     }
-    if (!la_done) DQ_TRY(la_fwd(c, l.la, c.w(b.r1.out), c.w(b.la), c.save ? c.w(b.la_pre) : nullptr, R, l.n, prep_ok ? L + ui : -1));
-    if (is_tiny_up(ui + 1) || level_ok(c, up_call(ui + 1))) continue;  // the next launch applies this level's Upsample / k3 conv itself
+    if (!f.la) DQ_TRY(la_fwd(c, l.la, c.w(b.r1.out), c.w(b.la), c.save ? c.w(b.la_pre) : nullptr, R, l.n, lp.prep_ok ? L + ui : -1));
+    if (!f.resample) continue;  // the next launch applies this level's Upsample / k3 conv itself
     DQ_TRY(conv_plain_fwd(c, l.resample, l.last ? CONV_S1 : CONV_UP, c.w(b.la), c.w(b.rs), R, l.n, l.n_next));
     cur = c.w(b.rs);
   }
-  // head (unet1d.py:1160-1166)
-  {
-    LevelCall lh = up_call(L);
-    const bool head_shape = p.dim == 4 && p.final_conv.cout == 1 && p.final_conv.cin == 4 && p.final_conv.k == 1 && p.final_conv.b >= 0 && level_ok(c, lh);
-    const bool head_fused = !c.save && head_shape;
-    if (c.save && c.head_loss && c.G && head_shape && lh.pre == LEVEL_PRE_S1 && lh.pc && lh.pc->cin == 4 &&
-        (int64_t)B * 4 <= LEVEL_LOSS_PARTS) {  // (one partial sum per wave: beyond a resident round the grid is B workgroups)
-      // train step: final_conv, loss and d fin.out in the final block's launch (its output IS stored); built for the (4, k3 conv, 4) launch
-      lh.head = &p.final_conv; lh.eps_out = nullptr;
-      LevelFwd f = with_img(lh, 2 * L);
-      Ctx::HeadLoss& hl = *c.head_loss;
-      f.loss_z = hl.z; f.grad_out = hl.grad_out; f.dout = c.g(a.fin.out); f.loss_part = hl.part; f.loss_gscale = hl.gscale; f.loss_parts_out = &hl.nparts;
-      DQ_TRY(launch_level_fwd(f, c.s));
-      hl.done = true;
-      return 0;
-    }
-    if (head_fused) {  // inference: final_conv (and, while sampling, the DDIM update) in the final block's launch; its output is not stored
-      lh.head = &p.final_conv; lh.eps_out = out; lh.write_out[0] = false;
-      if (c.step_io && c.step_io->x_t) c.step_io->fused_update = true;
-      return launch_level_fwd(with_img(lh, 2 * L), c.s);
-    }
-    if (level_ok(c, lh)) DQ_TRY(launch_level_fwd(with_img(lh, 2 * L), c.s));
-    else DQ_TRY(res_fwd(c, p.fin, a.fin, cur, p.dim, c.w(a.h0), p.dim, R, p.mz, RT));
+  // ---- head (unet1d.py:1160-1166)
+  LevelCall lh = up_call(p, a, L);
+  if (lp.head_train && c.head_loss) {
+    // train step: final_conv, loss and d fin.out in the final block's launch (its output IS stored)
+    lh.head = &p.final_conv;
+    LevelFwd f = level_desc(c, lh, lp.up[L].img);
+    Ctx::HeadLoss& hl = *c.head_loss;
+    f.loss_z = hl.z; f.grad_out = hl.grad_out; f.dout = c.g(a.fin.out); f.loss_part = hl.part; f.loss_gscale = hl.gscale; f.loss_parts_out = &hl.nparts;
+    DQ_TRY(launch_level_fwd(f, c.s));
+    hl.done = true;
+    return 0;
   }
-  DQ_TRY(conv_plain_fwd(c, p.final_conv, CONV_S1, c.w(a.fin.out), out, R, p.mz, p.mz, -1, p.final_act == FINAL_SOFTPLUS ? ACT_SOFTPLUS : ACT_NONE));
-  return 0;
+  if (!c.save && lp.head_shape) {  // inference: final_conv (and, while sampling, the DDIM update) in the final block's launch; its output is not stored
+    lh.head = &p.final_conv; lh.eps_out = out; lh.write_out[0] = false;
+    if (c.step_io && c.step_io->x_t) c.step_io->fused_update = true;
+    return launch_level_fwd(level_desc(c, lh, lp.up[L].img), c.s);
+  }
+  if (lp.up[L].kind == LEVEL_KERNEL) DQ_TRY(launch_level_fwd(level_desc(c, lh, lp.up[L].img), c.s));
+  else DQ_TRY(res_fwd(c, p.fin, a.fin, cur, p.dim, c.w(a.h0), p.dim, R, p.mz, RT));
+  return conv_plain_fwd(c, p.final_conv, CONV_S1, c.w(a.fin.out), out, R, p.mz, p.mz, -1, p.final_act == FINAL_SOFTPLUS ? ACT_SOFTPLUS : ACT_NONE);
 }
 
 int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, float cm, float ca, const DevTables& dt,
@@ -1399,6 +1449,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
   const Plan& p = c.p;
   const Arena& a = c.ar;
   const int B = c.B, RT = c.RT, R = B * RT, L = p.levels;
+  const LevelPlan lp = level_plan(p, a, B, RT, true, true);  // (what the forward of this step built with save: the same levels took the same launches)
   // only the accumulated-into region of the twin (offsets are multiples of 64 floats); a forked forward of the same step cleared it already
   if (c.owner && c.owner->twin_zeroed == c.G) c.owner->twin_zeroed = nullptr;
   else DQ_TRY(launch_zero(c.G, a.zero_floats, c.s));
@@ -1411,8 +1462,6 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
     return on_side(c, true, [part](hipStream_t ss) { return res_wg_reduce_all(part, ss); });
   };
   // the two levels with rows of one position: their backward data path in one launch each (k_tiny.hip), when their forward ran there
-  TinyBwd tb_up, tb_dn;
-  const bool use_tb_up = tiny_bwd_desc(c, true, &tb_up), use_tb_dn = tiny_bwd_desc(c, false, &tb_dn);
   // head
   // (d fin.out came with the forward's last launch when the training head ran: only the weight gradient is left)
   const bool head_done = c.head_loss && c.head_loss->done;
@@ -1436,14 +1485,14 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
     const int lv = L - 1 - ui;
     const int cx = l.r0.cout, cs = l.r0.cin - l.r0.cout;
     const int64_t in_off = ui == 0 ? a.mid_back : a.ups[ui - 1].rs;
-    if (ui == 0 && use_tb_up && tb_up.up_w)  // (the tiny backward applies Upsample^T itself: only the conv's weight / bias gradient is left, on the side stream)
+    if (ui == 0 && lp.use_tb_up && lp.tb_up_w)  // (the tiny backward applies Upsample^T itself: only the conv's weight / bias gradient is left, on the side stream)
       DQ_TRY(conv_plain_bwd(c, l.resample, CONV_UP, c.w(b.la), c.g(b.rs), nullptr, R, l.n, l.n_next, 0));
     else
       DQ_TRY(resample_bwd(c, l.resample, l.last ? LEVEL_PRE_S1 : LEVEL_PRE_UP, b, l.n, l.n_next, 0));  // only writer of d la (up): store
-    if (ui == 0 && use_tb_up) {
-      DQ_TRY(tiny_bwd_run(c, tb_up, true));  // LinearAttention + both ResnetBlocks; the input gradient lands in the bottleneck's layout
+    if (ui == 0 && lp.use_tb_up) {
+      DQ_TRY(tiny_bwd_run(c, tiny_bwd_desc(c, true, lp.tb_up_w), true));  // LinearAttention + both ResnetBlocks; the input gradient lands in the bottleneck's layout
     } else {
-      DQ_TRY(la_bwd(c, l.la, b, c.w(b.r1.out), c.g(b.la), c.g(b.r1.out), R, l.n, L + ui));
+      DQ_TRY(la_bwd(c, l.la, b, c.w(b.r1.out), c.g(b.la), c.g(b.r1.out), R, l.n, lp.prep_ok ? L + ui : -1));
       // the up path is the first writer of its own tensors AND of the skip tensors (the down path accumulates into them later)
       DQ_TRY(res_bwd(c, l.r1, b.r1, c.w(b.r0.out), c.g(b.r0.out), cx, c.w(a.downs[lv].r0.out), c.g(a.downs[lv].r0.out), cs, R, l.n, RT, 1, 1));
       DQ_TRY(res_bwd(c, l.r0, b.r0, c.w(in_off), c.g(in_off), cx, c.w(a.downs[lv].la), c.g(a.downs[lv].la), cs, R, l.n, RT, 1, 1));
@@ -1456,9 +1505,9 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
   if (p.wide_mid) {
     DQ_TRY(mid_backward_wide(c, rope));
   } else {
-    if (!use_tb_up) DQ_TRY(launch_fold(c.g(a.mid_back), c.g(a.mid2.out), B, RT, p.mid_c, 1, 1, c.s));  // (the tiny backward wrote d mid2.out itself)
-    DQ_TRY(mid_backward(c, rope, grad_x != nullptr));
-    if (!use_tb_dn) DQ_TRY(launch_fold(c.g(a.mid_in), c.g(a.downs[L - 1].rs), B, RT, p.mid_c, 0, 0, c.s));  // first and only writer: store (the tiny backward reads d mid_in itself)
+    if (!lp.use_tb_up) DQ_TRY(launch_fold(c.g(a.mid_back), c.g(a.mid2.out), B, RT, p.mid_c, 1, 1, c.s));  // (the tiny backward wrote d mid2.out itself)
+    DQ_TRY(mid_backward(c, rope, grad_x != nullptr, lp.prep_ok));
+    if (!lp.use_tb_dn) DQ_TRY(launch_fold(c.g(a.mid_in), c.g(a.downs[L - 1].rs), B, RT, p.mid_c, 0, 0, c.s));  // first and only writer: store (the tiny backward reads d mid_in itself)
   }
   // MS1 feature path (unet1d.py:1120-1130): its gradient d ms1f is final behind the bottleneck (to_k is its only consumer) and nothing on
   // the main chain reads what it produces -- data path and weight gradients go to the side stream with the next flush, instead of standing
@@ -1484,15 +1533,15 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
     const LevelBuf& b = a.downs[lv];
     const int C = l.r0.cin;
     const int64_t in_off = lv == 0 ? a.h0 : a.downs[lv - 1].rs;
-    if (lv == L - 1 && use_tb_dn) {  // k3 conv, LinearAttention, both ResnetBlocks and the Downsample in front of the level: one launch
-      DQ_TRY(tiny_bwd_run(c, tb_dn, false));
+    if (lv == L - 1 && lp.use_tb_dn) {  // k3 conv, LinearAttention, both ResnetBlocks and the Downsample in front of the level: one launch
+      DQ_TRY(tiny_bwd_run(c, tiny_bwd_desc(c, false, false), false));
       if (side_flush_here(lv)) DQ_TRY(side_flush(c));
       continue;
     }
-    if (!(lv == L - 2 && use_tb_dn))  // (that Downsample's backward rode in the launch above)
+    if (!(lv == L - 2 && lp.use_tb_dn))  // (that Downsample's backward rode in the launch above)
       DQ_TRY(resample_bwd(c, l.resample, l.last ? LEVEL_PRE_S1 : LEVEL_PRE_DOWN, b, l.n, l.n_next, 1));
     if (lv == 0) DQ_TRY(side_flush(c));  // (last level: the resample conv's weight gradient under the LinearAttention backward, not in the tail)
-    DQ_TRY(la_bwd(c, l.la, b, c.w(b.r1.out), c.g(b.la), c.g(b.r1.out), R, l.n, lv));
+    DQ_TRY(la_bwd(c, l.la, b, c.w(b.r1.out), c.g(b.la), c.g(b.r1.out), R, l.n, lp.prep_ok ? lv : -1));
     DQ_TRY(res_bwd(c, l.r1, b.r1, c.w(b.r0.out), c.g(b.r0.out), C, nullptr, nullptr, 0, R, l.n, RT));
     // (the last level's weight gradients are the tail of the side stream, in front of the join: hand them over block by block, so that
     // r1's run under r0's data path instead of behind it)
@@ -2009,32 +2058,15 @@ int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freq
   // The MS1 feature path (unet1d.py:1120-1130), to_k and RoPE(k) (:555, 561) depend on neither t nor x_t: once per call, not per step
   Ctx::StepIO io;
   io.pred_x0 = px0; io.coef = c.w(a.coef);
+  const LevelPlan lp = level_plan(plan->plan, a, B, RT, false, false);
   auto ms1_prologue = [&](const Ctx& cx, const float* ms1) -> int {
     const Plan& p = cx.p;
-    if (p.wide_mid) return 0;  // (the wide bottleneck keeps its projections inside the step)
-    const bool prep_ok = (int)(p.downs.size() + p.ups.size()) <= LA_PREP_MAX;
-    {  // W2 / operand images / the aligned copy of to_k's weight for the GEMM route: unet_forward's once-per-parameter-state launches
-      Ctx cp = cx;
-      cp.save = false; cp.prepare_only = true; cp.step_io = nullptr;
-      DQ_TRY(unet_forward(cp, rope_freqs, nullptr, nullptr, 0, nullptr, nullptr, cm, ca, plan->dev, nullptr));
-      io.prepared = true;
-    }
-    if (p.ms1_channels > 1) {
-      Ms1FeatFwd f;
-      f.ms1 = ms1; f.w = cx.prm(p.ms1_c0.w); f.bias = cx.prm(p.ms1_c0.b); f.cm = cm; f.ca = ca; f.B = B; f.RT = RT; f.M1 = p.ms1_channels;
-      f.a_out = cx.w(a.ms1_a);
-      DQ_TRY(launch_ms1_feat_fwd(f, cx.s));
-    } else {
-    DQ_TRY(launch_ms1_norm(ms1, cm, ca, cx.w(a.ms1n), (int64_t)B * RT, cx.s));
-    ConvFwd f;
-    f.inA = cx.w(a.ms1n); f.cinA = 1; f.w = cx.prm(p.ms1_c0.w); f.bias = cx.prm(p.ms1_c0.b); f.cout = p.cond_dim; f.K = 7;
-    f.rows = B; f.n_in = RT; f.n_out = RT; f.y_out = cx.w(a.ms1_a); f.act = ACT_GELU;
-    DQ_TRY(launch_conv_fwd(f, cx.s));
-    }
-    DQ_TRY(conv_plain_fwd(cx, p.ms1_c1, CONV_S1, cx.w(a.ms1_a), cx.w(a.ms1f), B, RT, RT));
-    DQ_TRY(conv_plain_fwd(cx, proj(p.k_w, HID, p.cond_dim), CONV_S1, cx.w(a.ms1f), cx.w(a.kk), B, RT, RT, prep_ok ? 1 : -1));
+    if (p.wide_mid) return 0;  // (the wide bottleneck keeps its projections inside the step, and prepares there)
+    DQ_TRY(unet_prepare(cx, lp, cx.s));  // W2 / operand images / the aligned copy of to_k's weight for the GEMM route
+    DQ_TRY(ms1_features(cx, ms1, cm, ca, true, cx.s));
+    DQ_TRY(conv_plain_fwd(cx, proj(p.k_w, HID, p.cond_dim), CONV_S1, cx.w(a.ms1f), cx.w(a.kk), B, RT, RT, lp.prep_ok ? 1 : -1));
     if (rope_freqs) DQ_TRY(launch_rope(cx.w(a.kk), rope_freqs, B, (int64_t)HID * RT, RT, 1.f, cx.s));
-    io.skip_ms1 = true;
+    io.prologue = true;
     return 0;
   };
   if (use_graph && !traj_x && !traj_eps) {
