@@ -2146,6 +2146,28 @@ int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freq
   return 0;
 }
 
+// The LevelPlan a pass at (B, RT) builds: the SAME level_plan() call as unet_forward (save, twin as the pass has them), unet_backward (1, 1)
+// and the sampler's prologue (0, 0), on an arena laid out as dq_unet_workspace_bytes lays it out -- no workspace, no launch, no device.
+int dq_debug_level_plan(dq_plan* plan, int B, int RT, int save, int twin, int32_t* out, int cap) {
+  if (!plan || !out || B <= 0 || RT <= 0) return -1;
+  const int L = plan->plan.levels;
+  const int need = 1 + DQ_LEVEL_PLAN_FORM_INTS * (2 * L + 1) + DQ_LEVEL_PLAN_FLAG_INTS;
+  if (cap < need) return -1;
+  Arena a;
+  layout_arena(plan->plan, B, RT, a);
+  const LevelPlan lp = level_plan(plan->plan, a, B, RT, save != 0, twin != 0);
+  static_assert(LEVEL_UNFUSED == DQ_LEVEL_UNFUSED && LEVEL_KERNEL == DQ_LEVEL_KERNEL && LEVEL_TINY == DQ_LEVEL_TINY, "LevelKind mirrors include/dq_hip.h");
+  int n = 0;
+  out[n++] = L;
+  auto put = [&](const LevelForm& f) {
+    out[n++] = f.kind; out[n++] = f.img; out[n++] = f.la; out[n++] = f.post_w; out[n++] = f.in_folded; out[n++] = f.resample;
+  };
+  for (int lv = 0; lv < L; ++lv) put(lp.dn[lv]);
+  for (int ui = 0; ui <= L; ++ui) put(lp.up[ui]);
+  for (bool b : {lp.prep_ok, lp.init_fused, lp.head_shape, lp.head_train, lp.use_tb_up, lp.use_tb_dn, lp.tb_up_w}) out[n++] = b;
+  return n;
+}
+
 int64_t dq_debug_tensor_offset(dq_plan* plan, const char* name) {
   if (!plan || !name) return -1;
   const Arena& a = plan->arena;

@@ -29,9 +29,30 @@ __global__ void __launch_bounds__(256) k_q_sample(const float* __restrict__ alph
   }
 }
 
+// the same per element for a window whose RT*MZ is no multiple of 4 (MZ = 2 with an odd RT): a float4 would straddle two windows
+__global__ void __launch_bounds__(256) k_q_sample_1(const float* __restrict__ alpha_bars, const float* __restrict__ x0,
+                                                    const int64_t* __restrict__ t, const float* __restrict__ noise,
+                                                    float* __restrict__ x_t, int B, int64_t per, int normalize) {
+  const int64_t total = (int64_t)B * per;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const float ab = alpha_bars[t[i / per]];
+    const float sa = sqrtf(ab), sb = sqrtf(1.0f - ab);
+    float x = x0[i];
+    if (normalize) x = x * 2.f - 1.f;
+    x_t[i] = sa * x + sb * noise[i];
+  }
+}
+
 int launch_q_sample(const float* alpha_bars, const float* x0, const int64_t* t, const float* noise, float* x_t, int B,
                     int64_t per_sample, int normalize, hipStream_t s) {
-  DQ_REQUIRE(per_sample % 4 == 0, "q_sample: RT*MZ must be a multiple of 4");
+  DQ_REQUIRE(B >= 0 && per_sample >= 0, "q_sample: negative size");
+  if (per_sample % 4 != 0) {
+    const int grid = (int)std::min<int64_t>(cdiv(B * per_sample, 256), 2048);
+    if (grid == 0) return 0;
+    hipLaunchKernelGGL(k_q_sample_1, dim3(grid), dim3(256), 0, s, alpha_bars, x0, t, noise, x_t, B, per_sample, normalize);
+    DQ_LAUNCH_CHECK();
+    return 0;
+  }
   const int64_t per4 = per_sample / 4, total = B * per4;
   if (total == 0) return 0;
   const int grid = (int)std::min<int64_t>(cdiv(total, 256), 2048);
@@ -69,6 +90,24 @@ __global__ void __launch_bounds__(256) k_ddim_step(const float* __restrict__ x_t
   }
 }
 
+// an element count that is no multiple of 4: the same expressions, one element per lane and step
+template <bool PRED_X0>
+__global__ void __launch_bounds__(256) k_ddim_step_1(const float* __restrict__ x_t, const float* __restrict__ eps,
+                                                     float* __restrict__ x_prev, float* __restrict__ eps_out,
+                                                     const float* __restrict__ coef, int64_t n, const int* __restrict__ step_ptr) {
+  if (step_ptr) coef += 4 * step_ptr[0];
+  const float sa = coef[0], sb = coef[1], sap = coef[2], sbp = coef[3];
+  const bool last = sap < 0.f;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float xv = x_t[i], ev = eps[i];
+    float x0, ep;
+    if (PRED_X0) { x0 = ev; ep = (xv - sa * x0) / sb; }
+    else         { ep = ev; x0 = (xv - sb * ep) / sa; }
+    x_prev[i] = last ? x0 : sap * x0 + sbp * ep;
+    if (PRED_X0 && eps_out) eps_out[i] = ep;
+  }
+}
+
 __global__ void k_inc_step(int* p) { p[0] += 1; }
 
 int launch_inc_step(int* p, hipStream_t s) {
@@ -79,8 +118,15 @@ int launch_inc_step(int* p, hipStream_t s) {
 
 int launch_ddim_step(const float* x_t, const float* eps, float* x_prev, const float* coef_dev, int64_t n, const int* step_ptr,
                      hipStream_t s, int pred_x0, float* eps_out) {
-  DQ_REQUIRE(n % 4 == 0, "ddim_step: element count must be a multiple of 4");
+  DQ_REQUIRE(n >= 0, "ddim_step: negative element count");
   if (n == 0) return 0;
+  if (n % 4 != 0) {
+    const int grid1 = (int)std::min<int64_t>(cdiv(n, 256), 2048);
+    if (pred_x0) hipLaunchKernelGGL(k_ddim_step_1<true>, dim3(grid1), dim3(256), 0, s, x_t, eps, x_prev, eps_out, coef_dev, n, step_ptr);
+    else hipLaunchKernelGGL(k_ddim_step_1<false>, dim3(grid1), dim3(256), 0, s, x_t, eps, x_prev, eps_out, coef_dev, n, step_ptr);
+    DQ_LAUNCH_CHECK();
+    return 0;
+  }
   const int grid = (int)std::min<int64_t>(cdiv(n / 4, 256), 2048);
   if (pred_x0) hipLaunchKernelGGL(k_ddim_step<true>, dim3(grid), dim3(256), 0, s, x_t, eps, x_prev, eps_out, coef_dev, n / 4, step_ptr);
   else hipLaunchKernelGGL(k_ddim_step<false>, dim3(grid), dim3(256), 0, s, x_t, eps, x_prev, eps_out, coef_dev, n / 4, step_ptr);
@@ -110,10 +156,27 @@ __global__ void __launch_bounds__(256) k_sample_finish(const float* __restrict__
   }
 }
 
+__global__ void __launch_bounds__(256) k_sample_finish_1(const float* __restrict__ x, const float* __restrict__ ms2_cond,
+                                                         float* __restrict__ out_x, float* __restrict__ out_noise, int64_t n,
+                                                         int normalize) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float v = x[i], c = ms2_cond[i];
+    const float o = normalize ? (v + 1.f) * 0.5f : v;
+    out_x[i] = o;
+    out_noise[i] = normalize ? ((c * 2.f - 1.f) + 1.f) * 0.5f - o : c - v;
+  }
+}
+
 int launch_sample_finish(const float* x, const float* ms2_cond, float* out_x, float* out_noise, int64_t n, int normalize,
                          hipStream_t s) {
-  DQ_REQUIRE(n % 4 == 0, "sample_finish: element count must be a multiple of 4");
+  DQ_REQUIRE(n >= 0, "sample_finish: negative element count");
   if (n == 0) return 0;
+  if (n % 4 != 0) {  // (an element count that is no multiple of 4: one element per lane and step)
+    hipLaunchKernelGGL(k_sample_finish_1, dim3((int)std::min<int64_t>(cdiv(n, 256), 2048)), dim3(256), 0, s, x, ms2_cond, out_x, out_noise, n,
+                       normalize);
+    DQ_LAUNCH_CHECK();
+    return 0;
+  }
   const int grid = (int)std::min<int64_t>(cdiv(n / 4, 256), 2048);
   hipLaunchKernelGGL(k_sample_finish, dim3(grid), dim3(256), 0, s, x, ms2_cond, out_x, out_noise, n / 4, normalize);
   DQ_LAUNCH_CHECK();
@@ -146,6 +209,26 @@ __global__ void __launch_bounds__(256) k_mse_fwd_bwd(const float* __restrict__ e
       g.x = d.x * gs; g.y = d.y * gs; g.z = d.z * gs; g.w = d.w * gs;
       reinterpret_cast<float4*>(grad)[i] = g;
     }
+  }
+  __shared__ float red[4];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+// n or the per-sample count no multiple of 4: one element per lane and step, the same partial sums per block
+__global__ void __launch_bounds__(256) k_mse_fwd_bwd_1(const float* __restrict__ eps, const float* __restrict__ noise,
+                                                       float* __restrict__ grad, float* __restrict__ partials, int64_t n,
+                                                       float gscale, const float* __restrict__ lw, const int64_t* __restrict__ t,
+                                                       int64_t per, float tm, float ta) {
+  float acc = 0.f;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float z = noise[i], w = 1.f;
+    if (lw) { w = lw[t[i / per]]; z = z * tm + ta; }
+    const float d = eps[i] - z;
+    acc += w * (d * d);
+    if (grad) grad[i] = d * (gscale * w);
   }
   __shared__ float red[4];
   acc = wave_sum(acc);
@@ -203,12 +286,17 @@ int launch_sum_partials(const float* partials, int count, float scale, float* ou
 
 int launch_mse_fwd_bwd(const float* eps, const float* noise, float* loss_out, float* grad_out, float* partials, int64_t n,
                        hipStream_t s, const float* lw, const int64_t* t, int64_t per_sample, float tm, float ta, int* defer_sum) {
-  DQ_REQUIRE(n % 4 == 0 && n > 0, "mse: element count must be a positive multiple of 4");
-  DQ_REQUIRE(!lw || (t && per_sample > 0 && per_sample % 4 == 0 && n % per_sample == 0),
-             "mse: the weighted form needs t and a per-sample element count that is a multiple of 4");
-  const int grid = (int)std::min<int64_t>(cdiv(n / 4, 256), MSE_MAX_BLOCKS);
-  hipLaunchKernelGGL(k_mse_fwd_bwd, dim3(grid), dim3(256), 0, s, eps, noise, grad_out, partials, n / 4, 2.0f / (float)n, lw, t,
-                     lw ? per_sample / 4 : (int64_t)1, tm, ta);
+  DQ_REQUIRE(n > 0, "mse: element count must be positive");
+  DQ_REQUIRE(!lw || (t && per_sample > 0 && n % per_sample == 0),
+             "mse: the weighted form needs t and a per-sample element count that divides n");
+  const bool vec = n % 4 == 0 && (!lw || per_sample % 4 == 0);
+  const int grid = (int)std::min<int64_t>(cdiv(vec ? n / 4 : n, 256), MSE_MAX_BLOCKS);
+  if (vec)
+    hipLaunchKernelGGL(k_mse_fwd_bwd, dim3(grid), dim3(256), 0, s, eps, noise, grad_out, partials, n / 4, 2.0f / (float)n, lw, t,
+                       lw ? per_sample / 4 : (int64_t)1, tm, ta);
+  else
+    hipLaunchKernelGGL(k_mse_fwd_bwd_1, dim3(grid), dim3(256), 0, s, eps, noise, grad_out, partials, n, 2.0f / (float)n, lw, t,
+                       lw ? per_sample : (int64_t)1, tm, ta);
   DQ_LAUNCH_CHECK();
   if (defer_sum) { *defer_sum = grid; return 0; }  // the caller sums the partials later (launch_sum_partials(partials, grid, 1 / n, loss_out))
   return launch_sum_partials(partials, grid, 1.0f / (float)n, loss_out, s);

@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DQ_HIP_LIB", os.path.join(os.path.dirname(_HERE), "libdq_hip.so"))
 
 _lib = None
-ABI_VERSION = 11  # DQ_ABI_VERSION of include/dq_hip.h this table was written against
+ABI_VERSION = 12  # DQ_ABI_VERSION of include/dq_hip.h this table was written against
 PRED_TYPES = {"eps": 0, "x0": 1}  # DQ_PRED_EPS / DQ_PRED_X0
 PRECISIONS = {"fp32": 0, "bf16x3": 1}  # DQ_PRECISION_FP32 / DQ_PRECISION_BF16X3
 FINAL_ACTS = {"identity": 0, "softplus": 1}  # DQ_FINAL_IDENTITY / DQ_FINAL_SOFTPLUS
@@ -18,6 +18,9 @@ LA_FWD_FORMS = ("long", "small", "rows", "register")  # DQ_LA_FWD_*
 LA_BWD_FORMS = ("long", "rows", "register")  # DQ_LA_BWD_*
 CONV_BWD_DATA_FORMS = ("wg", "gemm", "plain")  # DQ_CONV_BWD_DATA_*
 CONV_WGRAD_FORMS = ("wg", "v4", "scalar")  # DQ_CONV_WGRAD_*
+LEVEL_KINDS = ("unfused", "kernel", "tiny")  # DQ_LEVEL_* (index = value)
+LEVEL_FORM_FIELDS = ("kind", "img", "la", "post_w", "in_folded", "resample")  # DQ_LEVEL_PLAN_FORM_INTS, in the order dq_debug_level_plan writes them
+LEVEL_PLAN_FLAGS = ("prep_ok", "init_fused", "head_shape", "head_train", "use_tb_up", "use_tb_dn", "tb_up_w")  # DQ_LEVEL_PLAN_FLAG_INTS
 
 # name -> (restype, argtypes); this table is checked against include/dq_hip.h by tests/test_abi.py
 PROTOTYPES = {
@@ -73,6 +76,7 @@ PROTOTYPES = {
     "dq_pair_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int64, c_float, c_float, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "dq_debug_tensor_offset": (c_int64, [c_void_p, c_char_p]),
+    "dq_debug_level_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int]),
     "dq_debug_side_tail_store": (c_int, [c_void_p, c_void_p, c_float, c_int]),
     "dq_tfm_create": (c_void_p, [c_int, c_int, c_int, c_int]),
     "dq_tfm_destroy": (None, [c_void_p]),
@@ -197,6 +201,30 @@ def conv_bwd_forms(cout: int, cinA: int, cinB: int, K: int, mode: int, rows: int
     check(lib().dq_conv_bwd_forms(cout, cinA, cinB, K, mode, rows, n_in, n_out, rows_per_sample, int(has_bias), int(w_aligned),
                                   ctypes.byref(d), ctypes.byref(g)), "dq_conv_bwd_forms")
     return CONV_BWD_DATA_FORMS[d.value], CONV_WGRAD_FORMS[g.value]
+
+
+def level_plan(plan, B: int, RT: int, save: bool, twin: bool) -> dict:
+    """``dq_debug_level_plan``: the launch the library gives every U-Net level in a pass over (B, RT) windows.  ``dn`` (levels 0 .. L-1)
+    and ``up`` (levels 0 .. L-1, then the final ResnetBlock) are lists of dicts with the LEVEL_FORM_FIELDS (``kind`` as a name of
+    LEVEL_KINDS, ``img`` an int, the rest bools); the pass-wide LEVEL_PLAN_FLAGS are bools at the top level."""
+    cap = 1 + len(LEVEL_FORM_FIELDS) * 21 + len(LEVEL_PLAN_FLAGS)
+    buf = (c_int32 * cap)()
+    n = lib().dq_debug_level_plan(plan, int(B), int(RT), int(bool(save)), int(bool(twin)), buf, cap)
+    if n < 0:
+        raise RuntimeError(f"dq_debug_level_plan failed for B={B}, RT={RT}")
+    L, nf = buf[0], len(LEVEL_FORM_FIELDS)
+    if n != 1 + nf * (2 * L + 1) + len(LEVEL_PLAN_FLAGS):
+        raise RuntimeError(f"dq_debug_level_plan wrote {n} ints for {L} levels")
+
+    def form(i):
+        v = buf[1 + nf * i: 1 + nf * (i + 1)]
+        f = {k: bool(x) for k, x in zip(LEVEL_FORM_FIELDS, v)}
+        f["kind"], f["img"] = LEVEL_KINDS[v[0]], int(v[1])
+        return f
+
+    out = {"levels": int(L), "dn": [form(i) for i in range(L)], "up": [form(L + i) for i in range(L + 1)]}
+    out.update({k: bool(x) for k, x in zip(LEVEL_PLAN_FLAGS, buf[1 + nf * (2 * L + 1): n])})
+    return out
 
 
 def check(rc, what):

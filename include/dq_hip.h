@@ -48,9 +48,9 @@ const char* dq_last_error(void);
  * dq_plan_final_act, dq_get_option_effective, dq_resblock_forms, dq_linattn_forms, dq_linattn_bwd_store, dq_plan_create_ex,
  * dq_plan_attn_cond_channels, dq_ms1_feat_fwd, dq_ms1_feat_wgrad, dq_ms1_feat_wgrad_scratch_floats).  11: dq_conv_bwd,
  * dq_conv_bwd_workspace_floats, dq_conv_bwd_forms (later, additive: dq_adamw_clip_ema_step, dq_adamw_clip_ema_step_dev; dq_randn,
- * dq_ddim_step_sto, dq_ddim_coef_table, dq_ddim_sample_ex). */
+ * dq_ddim_step_sto, dq_ddim_coef_table, dq_ddim_sample_ex).  12: dq_debug_level_plan. */
 int dq_abi_version(void);
-#define DQ_ABI_VERSION 11
+#define DQ_ABI_VERSION 12
 
 /* Process-wide tuning options (no reference counterpart: the reference has one code path per op).  The library reads NO environment
  * variable for its dispatch; what can be tuned is set here, takes effect from the next call on, and invalidates cached sampling graphs.
@@ -452,6 +452,21 @@ int dq_attn_bwd(const float* q, const float* k, const float* v, const float* o, 
 /* Test hook: offset (in floats) of a named activation inside the workspace laid out by the last call on this plan
  * ("h0", "ms1f", "down3", "down3.la", "mid1", "attn_out", "up0", "fin", "eps", ...), or -1. */
 int64_t dq_debug_tensor_offset(dq_plan* plan, const char* name);
+
+/* Test hook: which launch takes each U-Net level in a pass over (B, RT) windows -- the plan unet_forward / unet_backward / the sampler's
+ * prologue build for themselves (the same rules, evaluated by the same function), without a workspace, a launch or a device.
+ * save: the pass keeps what a backward needs (training forward, and the backward itself); twin: it has the gradient arena at hand
+ * (dq_train_step: 1, 1; dq_unet_fwd with training: 1, 1; inference and dq_ddim_sample: 0, 0).  out receives
+ *   out[0]                          L, the number of levels;
+ *   DQ_LEVEL_PLAN_FORM_INTS ints    per launch, for the down levels 0 .. L-1, then the up levels 0 .. L-1, then the final ResnetBlock:
+ *                                   kind (DQ_LEVEL_*), img (operand-image slot or -1), la, post_w, in_folded (the n = 1 extras of a
+ *                                   DQ_LEVEL_TINY launch), resample (0: the level's resample conv is not launched -- it is the input
+ *                                   stage of the next launch, or post_w);
+ *   DQ_LEVEL_PLAN_FLAG_INTS ints    prep_ok, init_fused, head_shape, head_train, use_tb_up, use_tb_dn, tb_up_w.
+ * Returns the number of ints written, or -1 (null argument, B or RT < 1, cap too small: 1 + 6 (2 L + 1) + 7 <= 134 ints). */
+enum { DQ_LEVEL_UNFUSED = 0, DQ_LEVEL_KERNEL = 1, DQ_LEVEL_TINY = 2 };
+enum { DQ_LEVEL_PLAN_FORM_INTS = 6, DQ_LEVEL_PLAN_FLAG_INTS = 7 };
+int dq_debug_level_plan(dq_plan* plan, int B, int RT, int save, int twin, int32_t* out, int cap);
 
 /* Test hook: from now on the backward's side stream ends with a store of `value` to `addr`, delayed by delay_us microseconds, right in
  * front of the join with the caller's stream (addr = NULL switches it off).  A launch the caller makes on its own stream after

@@ -285,6 +285,13 @@ def test_stream_kernel_case_tables():
 
     assert edges([B * per for B, per in K.Q_CASES], 4, 2048, 4) and edges(K.DDIM_SIZES, 4, 2048, 4)
     assert edges(K.MSE_SIZES, 4, 1024, 4) and edges([B * per for B, per in K.WMSE_CASES], 4, 1024, 4)
+    # sizes that are no multiple of 4 take one element per thread and trip: the V = 1 edges that are such sizes, and beyond a sweep
+    def odd_edges(sizes, G):
+        return {n for n in (255, 257, G * 256 - 1, G * 256 + 1)} <= set(sizes) and any(s % 4 and s > G * 256 for s in sizes)
+
+    assert odd_edges(K.DDIM_SIZES, 2048) and odd_edges(K.MSE_SIZES, 1024)
+    assert any(per % 4 and B * per % 4 == 0 for B, per in K.Q_CASES) and any(per % 4 and B * per > 2048 * 256 for B, per in K.Q_CASES)
+    assert any(per % 4 and B * per % 4 == 0 for B, per in K.WMSE_CASES) and any(per % 4 and B * per > 1024 * 256 for B, per in K.WMSE_CASES)
     sizes = [n for n, _, _ in K.ADAMW_MATRIX]
     assert edges(sizes, 1, 1016, 1) and edges(sizes + [4], 4, 1016, 4)
     assert {j for n, _, j in K.ADAMW_MATRIX if n == 1016 * 256 + 1} == set(range(len(K.ADAMW_VARIANTS)))

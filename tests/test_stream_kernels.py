@@ -8,7 +8,9 @@ k_adamw_clip_dev).
 Sizes come from the launch code: T = 256 threads, V elements per thread and trip, G the grid cap (constants below).  Every entry point
 runs at the smallest legal size, T*V -+ V and T*V, G*T*V -+ V, and two sweeps of the capped grid plus a ragged remainder; k_sumsq also at
 n = 4 * (5 * G * T + 77) + r, r in 1..3 (its paired loop twice, then the single loop, then a scalar tail), with grads aligned and one
-float off 16 bytes (its designed scalar branch).  Outputs are views between canaries, plain-store outputs start as NaN, scratch buffers
+float off 16 bytes (its designed scalar branch).  q_sample, the DDIM update and the MSE send an element count (q_sample, weighted MSE: a
+per-sample count) that is no multiple of 4 to siblings with V = 1 (k_q_sample_1, k_ddim_step_1, k_mse_fwd_bwd_1): those run at the V = 1
+edges that are such sizes, and at 3 x 37 x 2, the shape tests/test_level_plan.py met them at.  Outputs are views between canaries, plain-store outputs start as NaN, scratch buffers
 have exactly the documented size (NaN, then a canary compared through an int view).
 
 References: oracle.dq_oracle (q_sample, ddim_update, ddim_update_x0, ms1_term, adamw_clip_step) and the plain MSE formula, in float64
@@ -128,6 +130,9 @@ def timesteps(B, pattern):
 
 # (B, per_sample): per_sample = 4, blocks serving many samples, a sample spanning sweeps
 Q_CASES = [(1, 4), (7, 4), (5, 204), (4, 256), (1, 1028), (257, 4), (1, 2097148), (524287, 4), (3, 699052), (5, 839128)]
+# per_sample % 4 != 0 (k_q_sample_1, one element per thread and trip): the smallest, MZ = 2 at RT = 37, B * per_sample a multiple of 4 all
+# the same, a block + 1, beyond one sweep of the capped grid
+Q_CASES += [(1, 1), (3, 74), (2, 6), (1, 257), (3, 174767)]
 
 
 def q_case(B, per, normalize, kind, fp32=False):
@@ -147,7 +152,9 @@ def q_case(B, per, normalize, kind, fp32=False):
     return c
 
 
-DDIM_SIZES = edge_sizes(4, GRID_STREAM, 4)
+# n % 4 != 0 (k_ddim_step_1, V = 1): the same edges where they are no multiple of 4, and 3 x 37 x 2
+ODD = lambda sizes: [n for n in sizes if n % 4]
+DDIM_SIZES = edge_sizes(4, GRID_STREAM, 4) + ODD(edge_sizes(1, GRID_STREAM, 1)) + [222]
 DDIM_T = [999, 998, 500, 1, 0]  # 999: / sqrt(ab) = 4.9e-5; 0: the coef[2] < 0 branch
 
 
@@ -182,15 +189,17 @@ def ddim_case(n, t, fp32=False):
     return c
 
 
-MSE_SIZES = edge_sizes(4, MSE_MAX_BLOCKS, 4)
+MSE_SIZES = edge_sizes(4, MSE_MAX_BLOCKS, 4) + ODD(edge_sizes(1, MSE_MAX_BLOCKS, 1)) + [222]  # (n % 4 != 0: k_mse_fwd_bwd_1, V = 1)
 # (B, per_sample): from per_sample = 4 (a block serves 256 samples) to one sample spanning several sweeps of the 1024-block grid
 WMSE_CASES = [(1, 4), (255, 4), (4, 256), (1, 1028), (3, 349524), (262145, 4), (1, 2098484), (7, 299784)]
+WMSE_CASES += [(1, 1), (3, 74), (2, 6), (257, 1), (7, 74899)]  # per_sample % 4 != 0 (V = 1), B * per_sample = 12 included
 WMSE_MAPS = [(2.0, -1.0), (1.0, 0.0)]
 
 
-def mse_units(n):
-    grid = min(cdiv(n // 4, T_), MSE_MAX_BLOCKS)
-    return reduction_units(4 * cdiv(n // 4, grid * T_), grid)
+def mse_units(n, V=4):
+    """V = 4 elements per thread and trip; 1 where n (weighted form: per_sample) is no multiple of 4"""
+    grid = min(cdiv(n // V, T_), MSE_MAX_BLOCKS)
+    return reduction_units(V * cdiv(n // V, grid * T_), grid)
 
 
 def mse_case(B, per, tm=None, ta=None, fp32=False):
@@ -213,7 +222,7 @@ def mse_case(B, per, tm=None, ta=None, fp32=False):
     c["grad"] = 2 * d * w / n
     absd = E.abs() + (Z * tm).abs() + abs(ta)
     c["S_grad"] = 2 * absd * w / n
-    c["loss_bound"] = min(mse_units(n) * U * float((w * absd * absd).sum() / n), CAP_LOSS * abs(c["loss"]))
+    c["loss_bound"] = min(mse_units(n, 1 if per % 4 else 4) * U * float((w * absd * absd).sum() / n), CAP_LOSS * abs(c["loss"]))
     if fp32:
         w32 = c["lw"][c["t"]][:, None] if weighted else 1.0
         d32 = e - (z * tm + ta)
@@ -684,13 +693,12 @@ def test_rejections_leave_the_outputs_alone(N):
     pa, pb = N.ptr(a), N.ptr(b)
     adam = (0.9, 0.999, 1e-8, 0.01)
     calls = {
-        "q_sample, per_sample 6": lambda: L.dq_q_sample(N.ptr(ab), pa, N.ptr(t), pb, o, 2, 6, 1, s),
-        "ddim_step, n 6": lambda: L.dq_ddim_step(pa, pb, o, N.ptr(coef), 6, s),
-        "ddim_step_x0, n 10": lambda: L.dq_ddim_step_x0(pa, pb, o, o2, N.ptr(coef), 10, s),
-        "mse, n 6": lambda: L.dq_mse_loss_fwd_bwd(pa, pb, o2, o, scp, 6, s),
+        "q_sample, per_sample -4": lambda: L.dq_q_sample(N.ptr(ab), pa, N.ptr(t), pb, o, 2, -4, 1, s),
+        "ddim_step, n -4": lambda: L.dq_ddim_step(pa, pb, o, N.ptr(coef), -4, s),
+        "ddim_step_x0, n -4": lambda: L.dq_ddim_step_x0(pa, pb, o, o2, N.ptr(coef), -4, s),
+        "mse, n -4": lambda: L.dq_mse_loss_fwd_bwd(pa, pb, o2, o, scp, -4, s),
         "mse, n 0": lambda: L.dq_mse_loss_fwd_bwd(pa, pb, o2, o, scp, 0, s),
-        "weighted mse, n 18": lambda: L.dq_mse_loss_weighted_fwd_bwd(pa, pb, 1.0, 0.0, N.ptr(lw), N.ptr(t), o2, o, scp, 3, 6, s),
-        "weighted mse, per_sample 6 (n 12)": lambda: L.dq_mse_loss_weighted_fwd_bwd(pa, pb, 1.0, 0.0, N.ptr(lw), N.ptr(t), o2, o, scp, 2, 6, s),
+        "weighted mse, per_sample 0": lambda: L.dq_mse_loss_weighted_fwd_bwd(pa, pb, 1.0, 0.0, N.ptr(lw), N.ptr(t), o2, o, scp, 3, 0, s),
         "weighted mse, B 0": lambda: L.dq_mse_loss_weighted_fwd_bwd(pa, pb, 1.0, 0.0, N.ptr(lw), N.ptr(t), o2, o, scp, 0, 8, s),
         "adamw, n 0": lambda: L.dq_adamw_clip_step(o, pa, o2, o2, 0, scp, 1.0, 10.0, 1e-3, *adam, 1, None, s),
         "adamw, step 0": lambda: L.dq_adamw_clip_step(o, pa, o2, o2, 16, scp, 1.0, 10.0, 1e-3, *adam, 0, None, s),
