@@ -53,6 +53,22 @@ int launch_adamw_clip_ema_dev(float* p, const float* g, float* m, float* v, int6
                               const float* lr_dev, double b1, double b2, double eps, double wd, int* step_dev, float* gnorm_out, float* ema,
                               float ema_decay, int ema_warmup, hipStream_t s);
 
+// held-out loss (k_stream.hip): per_window[b] = MSE of window b against target' = target * tm + ta, loss_out = mean_b lw[t_b] * MSE_b
+// (lw null: 1), fp64 sums in a fixed order; scratch: mse_per_window_scratch_bytes = 8 * B * ceil(per / MSE_PW_SLICE) bytes
+constexpr int MSE_PW_SLICE = 8192;  // elements of a window one block of k_mse_per_window sums
+int64_t mse_per_window_scratch_bytes(int B, int64_t per);
+int launch_mse_per_window(const float* out, const float* target, float tm, float ta, const float* lw, const int64_t* t, float* per_window,
+                          float* loss_out, void* scratch, int64_t scratch_bytes, int B, int64_t per, hipStream_t s);
+// ---- k_metrics.hip: per-window reconstruction metrics of pred against target (B, RT, MZ) -> out (B, METRIC_COUNT)
+constexpr int METRIC_COUNT = 9;         // DQ_METRIC_COUNT
+constexpr int METRIC_ROW_SEG = 4096;    // m/z columns of a scan one wave of k_metric_rows sums
+constexpr int METRIC_COL_ROWS = 64;     // scans of a column one lane of k_metric_cols sums
+constexpr int METRIC_ROW_MOMENTS = 10;  // doubles per (scan, segment)
+constexpr int METRIC_COL_MOMENTS = 5;   // doubles per (column, scan chunk)
+int64_t recon_metrics_scratch_bytes(int B, int RT, int MZ);
+int launch_recon_metrics(const float* pred, const float* target, float* out, void* scratch, int64_t scratch_bytes, int B, int RT, int MZ,
+                         hipStream_t s);
+
 int launch_axpy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst += src
 int launch_zero(float* dst, int64_t n, hipStream_t s);  // dst = 0 (a kernel, not a memset node)
 int launch_copy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst = src (a kernel, not a memcpy node)

@@ -2008,6 +2008,50 @@ int dq_train_step(dq_plan* plan, const float* params, const float* rope_freqs, c
   return 0;
 }
 
+// The forward-only counterpart of dq_train_step: q_sample, the network forward in its no-save mode (the inference arena alone: no gradient
+// twin, no side queue, dq_plan::twin_zeroed untouched), then the per-window MSE.  The slice sums live in the arena's second sampling buffer
+// (xb: B * per floats rounded up to 64, which an inference forward never touches); a window of fewer than 8192 elements needs one
+// double, so only a B * per below 64 with per == 1 could fall short, and the launcher checks the size it is given.
+int dq_eval_step(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_dev, const float* x0,
+                 const float* ms2_cond, const float* ms1_cond, const int64_t* t, const float* noise, int auto_normalize, int pred_type,
+                 const float* loss_weight_dev, float* loss_out, float* per_window_out, void* workspace, int64_t workspace_bytes, int B, int RT,
+                 void* stream) {
+  DQ_REQUIRE(plan && params && alpha_bars_dev && x0 && ms2_cond && ms1_cond && t && noise && loss_out && per_window_out && workspace,
+             "dq_eval_step: null argument");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_eval_step: Unknown pred_type");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || loss_weight_dev, "dq_eval_step: pred_type x0 needs the loss-weight (SNR) table");
+  DQ_REQUIRE(B > 0 && RT > 0, "dq_eval_step: B and RT must be positive");
+  DQ_TRY(ensure_arena(plan, B, RT));
+  const Arena& a = plan->arena;
+  DQ_REQUIRE(workspace_bytes >= (int64_t)sizeof(float) * a.floats, "dq_eval_step: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  Ctx c{plan->plan, a, params, (float*)workspace, nullptr, nullptr, B, RT, s};
+  c.save = false;
+  const int64_t per = (int64_t)RT * plan->plan.mz;
+  const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
+  DQ_TRY(launch_q_sample(alpha_bars_dev, x0, t, noise, c.w(a.xa), B, per, auto_normalize, s));                 // model.py:349-352
+  DQ_TRY(unet_forward(c, rope_freqs, c.w(a.xa), t, 0, ms2_cond, ms1_cond, cm, ca, plan->dev, c.w(a.eps)));  // model.py:359
+  const bool px0 = pred_type == DQ_PRED_X0;  // model.py:361 / 372-376: the target is the noise, or the normalised x0 weighted by loss_weight[t_b]
+  return launch_mse_per_window(c.w(a.eps), px0 ? x0 : noise, px0 ? cm : 1.f, px0 ? ca : 0.f, px0 ? loss_weight_dev : nullptr, t,
+                               per_window_out, loss_out, c.w(a.xb), (int64_t)sizeof(float) * ((B * per + 63) / 64 * 64), B, per, s);
+}
+
+int64_t dq_mse_per_window_scratch_bytes(int B, int64_t per) { return mse_per_window_scratch_bytes(B, per); }
+
+int dq_mse_per_window(const float* out, const float* target, float tm, float ta, const float* lw, const int64_t* t, float* per_window_out,
+                      float* loss_out, void* scratch, int B, int64_t per, void* stream) {
+  DQ_REQUIRE(B > 0 && per > 0, "dq_mse_per_window: B and per must be positive");
+  return launch_mse_per_window(out, target, tm, ta, lw, t, per_window_out, loss_out, scratch, mse_per_window_scratch_bytes(B, per), B, per,
+                               (hipStream_t)stream);
+}
+
+int64_t dq_recon_metrics_scratch_bytes(int B, int RT, int MZ) { return recon_metrics_scratch_bytes(B, RT, MZ); }
+
+int dq_recon_metrics(const float* pred, const float* target, float* out, void* scratch, int64_t scratch_bytes, int B, int RT, int MZ,
+                     void* stream) {
+  return launch_recon_metrics(pred, target, out, scratch, scratch_bytes, B, RT, MZ, (hipStream_t)stream);
+}
+
 int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
                    const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
                    const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,

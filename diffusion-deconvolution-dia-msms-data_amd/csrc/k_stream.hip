@@ -302,6 +302,78 @@ int launch_mse_fwd_bwd(const float* eps, const float* noise, float* loss_out, fl
   return launch_sum_partials(partials, grid, 1.0f / (float)n, loss_out, s);
 }
 
+// ---- held-out loss (dq_mse_per_window, dq_eval_step): per-window MSE and its weighted mean, forward only : 8 B / element
+// target' = target * tm + ta in fp32 (one multiply, one add: what k_mse_fwd_bwd forms), d = (double)out - (double)target', d * d summed in
+// fp64.  One block per (slice of MSE_PW_SLICE elements, window): the partition of a window depends on `per` alone, never on B, and the
+// slices are added in index order -- no atomics, so a window's value does not depend on the batch around it.  scratch: one double per slice.
+__global__ void __launch_bounds__(256) k_mse_per_window(const float* __restrict__ out, const float* __restrict__ target, float tm, float ta,
+                                                        double* __restrict__ slices, int64_t per, int nslices) {
+  const int64_t b = blockIdx.y;
+  const int64_t i0 = (int64_t)blockIdx.x * MSE_PW_SLICE, i1 = min(per, i0 + MSE_PW_SLICE);
+  const float* __restrict__ o = out + b * per;
+  const float* __restrict__ z = target + b * per;
+  double acc = 0.0;
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+    const float zt = z[i] * tm + ta;
+    const double d = (double)o[i] - (double)zt;
+    acc += d * d;
+  }
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s, 64);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) slices[b * nslices + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// per_window[b] = (float)(sum of the window's slices / per); loss = (float)(sum_b lw[t_b] * (sum_b / per) / B), both sums in fp64 in index
+// order (256 windows at a time are staged in LDS, thread 0 adds them up), each result rounded to fp32 once.  lw == nullptr: weight 1.
+__global__ void __launch_bounds__(256) k_mse_per_window_finish(const double* __restrict__ slices, const float* __restrict__ lw,
+                                                               const int64_t* __restrict__ t, float* __restrict__ per_window,
+                                                               float* __restrict__ loss, int B, int64_t per, int nslices) {
+  __shared__ double stage[256];
+  double total = 0.0;
+  for (int base = 0; base < B; base += 256) {
+    const int b = base + threadIdx.x;
+    if (b < B) {
+      double sum = 0.0;
+      for (int g = 0; g < nslices; ++g) sum += slices[(int64_t)b * nslices + g];
+      const double mse = sum / (double)per;
+      per_window[b] = (float)mse;
+      stage[threadIdx.x] = lw ? (double)lw[t[b]] * mse : mse;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int m = min(256, B - base);
+      for (int j = 0; j < m; ++j) total += stage[j];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = (float)(total / (double)B);
+}
+
+int64_t mse_per_window_scratch_bytes(int B, int64_t per) {
+  if (B < 1 || per < 1) return -1;
+  return (int64_t)sizeof(double) * B * ((per + MSE_PW_SLICE - 1) / MSE_PW_SLICE);
+}
+
+int launch_mse_per_window(const float* out, const float* target, float tm, float ta, const float* lw, const int64_t* t, float* per_window,
+                          float* loss_out, void* scratch, int64_t scratch_bytes, int B, int64_t per, hipStream_t s) {
+  DQ_REQUIRE(out && target && per_window && loss_out && scratch, "mse_per_window: null argument");
+  DQ_REQUIRE(B > 0 && B <= 65535 && per > 0, "mse_per_window: need 0 < B <= 65535 and per > 0");
+  DQ_REQUIRE(!lw || t, "mse_per_window: the weighted form needs t");
+  DQ_REQUIRE(scratch_bytes >= mse_per_window_scratch_bytes(B, per), "mse_per_window: scratch too small (dq_mse_per_window_scratch_bytes)");
+  DQ_REQUIRE(((uintptr_t)scratch & 7) == 0, "mse_per_window: scratch must be 8-byte aligned");
+  const int64_t nslices = (per + MSE_PW_SLICE - 1) / MSE_PW_SLICE;
+  DQ_REQUIRE(nslices <= INT32_MAX, "mse_per_window: window too large");
+  hipLaunchKernelGGL(k_mse_per_window, dim3((unsigned)nslices, B), dim3(256), 0, s, out, target, tm, ta, (double*)scratch, per, (int)nslices);
+  DQ_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_mse_per_window_finish, dim3(1), dim3(256), 0, s, (const double*)scratch, lw, t, per_window, loss_out, B, per,
+                     (int)nslices);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
+
 // ---- the MS1 term of train_step (reference model.py:364-371, 379-386, 398-402; semantics chosen in DESIGN.md section 12 because
 // the reference's branch raises): per sample b, with D = x_t - eps_pred ('eps') or x0_pred ('x0'),
 //   additional_b = sum over f in {sum, mean, max over m/z} of mean_rt (s_f[rt] / max_rt s_f - ms1n[rt] / max_rt ms1n)^2

@@ -20,6 +20,7 @@ CONV_BWD_DATA_FORMS = ("wg", "gemm", "plain")  # DQ_CONV_BWD_DATA_*
 CONV_WGRAD_FORMS = ("wg", "v4", "scalar")  # DQ_CONV_WGRAD_*
 LEVEL_KINDS = ("unfused", "kernel", "tiny")  # DQ_LEVEL_* (index = value)
 LEVEL_FORM_FIELDS = ("kind", "img", "la", "post_w", "in_folded", "resample")  # DQ_LEVEL_PLAN_FORM_INTS, in the order dq_debug_level_plan writes them
+METRIC_NAMES = ("mse", "mae", "cosine", "sa", "pearson", "scan_sa", "scan_count", "xic_r", "xic_count")  # DQ_METRIC_* (index = column of dq_recon_metrics' output)
 LEVEL_PLAN_FLAGS = ("prep_ok", "init_fused", "head_shape", "head_train", "use_tb_up", "use_tb_dn", "tb_up_w")  # DQ_LEVEL_PLAN_FLAG_INTS
 
 # name -> (restype, argtypes); this table is checked against include/dq_hip.h by tests/test_abi.py
@@ -60,6 +61,13 @@ PROTOTYPES = {
                                            c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p]),
     "dq_train_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                               c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "dq_eval_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "dq_mse_per_window_scratch_bytes": (c_int64, [c_int, c_int64]),
+    "dq_mse_per_window": (c_int, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                                  c_void_p]),
+    "dq_recon_metrics_scratch_bytes": (c_int64, [c_int, c_int, c_int]),
+    "dq_recon_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "dq_ms1_loss_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
                                     c_void_p, c_int, c_int, c_int, c_void_p]),
     "dq_ddim_sample": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -1,9 +1,11 @@
 """``dquartic`` command line -- same commands and options as the reference's ``dquartic/cli.py`` (:26-188):
 ``dquartic train CONFIG [--parquet_directory --ms2-data-path --ms1-data-path --batch-size --checkpoint-path --use-wandb
---threads]`` and ``dquartic generate-config PATH``.  ``generate-train-data`` (offline sqMass ETL) is outside the hot path
+--threads]`` and ``dquartic generate-config PATH``; ``dquartic evaluate CONFIG --checkpoint PATH`` (this build) prints held-out loss and
+reconstruction metrics.  ``generate-train-data`` (offline sqMass ETL) is outside the hot path
 and reports so.  Under ``torch.distributed.run`` (WORLD_SIZE > 1) training is data-parallel: one process per GPU, the
 dataset is sharded by rank and the flat gradient is all-reduced over RCCL."""
 import ast
+import json
 import os
 
 import click
@@ -12,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from .model.model import DDIMDiffusionModel
 from .model.unet1d import UNet1d
-from .utils.config_loader import generate_train_config, load_train_config
+from .utils.config_loader import generate_train_config, load_train_config, validation_config
 
 
 class PythonLiteralOption(click.Option):
@@ -63,18 +65,7 @@ def train(config_path, parquet_directory, ms2_data_path, ms1_data_path, batch_si
                                use_wandb=use_wandb, threads=threads)
     m = config["model"]
     syn = config["data"].get("synthetic")
-    if syn:
-        from .utils.synthetic import SyntheticDIAMSDataset
-
-        dataset = SyntheticDIAMSDataset(n_windows=int(syn.get("n_windows", 32)), RT=int(syn.get("RT", 400)),
-                                        MZ=int(syn.get("MZ", m["UNet1d"]["downsample_dim"])), normalize=config["data"]["normalize"],
-                                        rank=rank, world=world,
-                                        ms1_channels=None if syn.get("ms1_channels") is None else int(syn["ms1_channels"]))
-    else:
-        from .utils.data_loader import DIAMSDataset
-
-        dataset = DIAMSDataset(config["data"]["parquet_directory"], config["data"]["ms2_data_path"], config["data"]["ms1_data_path"],
-                               normalize=config["data"]["normalize"])
+    dataset = build_dataset(config["data"], m, rank, world)
     per_rank = max(1, int(m["batch_size"]) // world)
     device = torch.device("cuda", local)
     if resident_dataset and not syn:
@@ -92,6 +83,60 @@ def train(config_path, parquet_directory, ms2_data_path, ms1_data_path, batch_si
                             drop_last=len(dataset) // world > per_rank)
     else:
         loader = DataLoader(dataset, batch_size=per_rank, shuffle=True, num_workers=int(config["threads"]), drop_last=len(dataset) > per_rank)
+    dm = build_model(m, device)
+    enable_ema_from_config(dm, m)
+    val = validation_config(config)
+    val_loader = None if val is None else build_validation_loader(val, m, per_rank, rank, world)
+    wb = None
+    if config["wandb"]["use_wandb"] and rank == 0:
+        try:
+            import wandb as wb
+
+            w = config["wandb"]
+            wb.init(project=w["wandb_project"], name=w["wandb_name"], id=w["wandb_id"], resume=w["wandb_resume"],
+                    config={"architecture": w["wandb_architecture"], "dataset": w["wandb_dataset"], **m}, mode=w["wandb_mode"])
+        except ImportError:
+            click.echo("wandb is not installed; continuing without it")
+            wb = None
+    if val_loader is None:
+        dm.train(loader, m["batch_size"], m["num_epochs"], m["warmup_epochs"], m["learning_rate"], wb is not None, m["checkpoint_path"])
+    else:
+        dm.train(loader, m["batch_size"], m["num_epochs"], m["warmup_epochs"], m["learning_rate"], wb is not None, m["checkpoint_path"],
+                 val_dataloader=val_loader, val_every=val["val_every"])
+    if wb is not None:
+        wb.finish()
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+def build_dataset(data, m, rank=0, world=1):
+    """The dataset a ``data`` section (or a completed ``data.validation`` block) describes: the built-in synthetic one, or the files."""
+    syn = data.get("synthetic")
+    if syn:
+        from .utils.synthetic import SyntheticDIAMSDataset
+
+        return SyntheticDIAMSDataset(n_windows=int(syn.get("n_windows", 32)), RT=int(syn.get("RT", 400)),
+                                     MZ=int(syn.get("MZ", m["UNet1d"]["downsample_dim"])), normalize=data["normalize"],
+                                     rank=rank, world=world,
+                                     ms1_channels=None if syn.get("ms1_channels") is None else int(syn["ms1_channels"]),
+                                     start=int(syn.get("start", 0)))
+    from .utils.data_loader import DIAMSDataset
+
+    return DIAMSDataset(data["parquet_directory"], data["ms2_data_path"], data["ms1_data_path"], normalize=data["normalize"])
+
+
+def build_validation_loader(val, m, batch_size, rank=0, world=1):
+    """The held-out loader of a completed ``data.validation`` block (``validation_config``): ``n_pairs`` index pairs of its windows drawn
+    from a generator of their own under the block's ``seed`` (``FrozenPairDataset``: the same pairs in every process and run), served in
+    order -- what makes two ``evaluate`` runs comparable."""
+    from .utils.synthetic import FrozenPairDataset
+
+    return DataLoader(FrozenPairDataset(build_dataset(val, m, rank, world), val["n_pairs"], seed=val.get("seed", 0)),
+                      batch_size=batch_size, shuffle=False)
+
+
+def build_model(m, device):
+    """The network and diffusion process a ``model`` section describes."""
     if m["use_model"] == "UNet1d":
         u = m["UNet1d"]
         net = UNet1d(dim=u["dim"], channels=u["channels"], dim_mults=tuple(u["dim_mults"]), conditional=u["conditional"],
@@ -106,26 +151,9 @@ def train(config_path, parquet_directory, ms2_data_path, ms1_data_path, batch_si
                                                        num_layers=c["num_layers"])).to(device)
     else:
         raise click.ClickException(f"Invalid model class: {m['use_model']}")  # reference cli.py:111 (ValueError there)
-    dm = DDIMDiffusionModel(model_class=net, num_timesteps=m["num_timesteps"], beta_schedule_type=m["beta_schedule_type"],
-                            pred_type=m["pred_type"], auto_normalize=m["auto_normalize"], ms1_loss_weight=m["ms1_loss_weight"],
-                            device=device)
-    enable_ema_from_config(dm, m)
-    wb = None
-    if config["wandb"]["use_wandb"] and rank == 0:
-        try:
-            import wandb as wb
-
-            w = config["wandb"]
-            wb.init(project=w["wandb_project"], name=w["wandb_name"], id=w["wandb_id"], resume=w["wandb_resume"],
-                    config={"architecture": w["wandb_architecture"], "dataset": w["wandb_dataset"], **m}, mode=w["wandb_mode"])
-        except ImportError:
-            click.echo("wandb is not installed; continuing without it")
-            wb = None
-    dm.train(loader, m["batch_size"], m["num_epochs"], m["warmup_epochs"], m["learning_rate"], wb is not None, m["checkpoint_path"])
-    if wb is not None:
-        wb.finish()
-    if world > 1:
-        torch.distributed.destroy_process_group()
+    return DDIMDiffusionModel(model_class=net, num_timesteps=m["num_timesteps"], beta_schedule_type=m["beta_schedule_type"],
+                              pred_type=m["pred_type"], auto_normalize=m["auto_normalize"], ms1_loss_weight=m["ms1_loss_weight"],
+                              device=device)
 
 
 def enable_ema_from_config(dm, m) -> bool:
@@ -138,6 +166,48 @@ def enable_ema_from_config(dm, m) -> bool:
     dm._set_lr(m["learning_rate"])
     dm.enable_ema(float(decay), bool(m.get("ema_warmup", True)))
     return True
+
+
+@cli.command()
+@click.argument("config-path", type=click.Path(exists=True), required=True)
+@click.option("--checkpoint", required=True, type=click.Path(exists=True), help="Checkpoint written by train (model_state_dict; its EMA when it has one)")
+@click.option("--num-steps", default=None, type=int, help="Also sample every window with this many DDIM steps and report reconstruction metrics")
+@click.option("--eta", default=0.0, type=float, help="DDIM eta of that sampling (0: deterministic update, 1: ancestral)")
+@click.option("--seed", default=0, type=int, help="Seed of the evaluation noise and of the sampling")
+@click.option("--use-ema/--no-use-ema", default=None, help="Evaluate the averaged weights (default: when the checkpoint has an average)")
+@click.option("--max-batches", default=None, type=int, help="Stop after this many batches")
+@click.option("--out", "out_path", default=None, type=click.Path(), help="Write the full result, per-window metrics included, as JSON")
+def evaluate(config_path, checkpoint, num_steps, eta, seed, use_ema, max_batches, out_path):
+    """Held-out loss (and, with --num-steps, reconstruction metrics) of a checkpoint on the config's data.validation set.  The pairs of
+    that set come from the block's own seed, not from --seed: runs that differ in --seed, --eta, --num-steps or --use-ema score the same
+    pairs.  Without a validation block the config's data section is scored, with a notice.  Prints one JSON line."""
+    if not torch.cuda.is_available():
+        raise click.ClickException("no GPU visible: this build runs the hot path on MI355X only (no CPU fallback)")
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(device)
+    config = load_train_config(config_path)
+    m = config["model"]
+    val = validation_config(config)
+    if val is None:
+        click.echo("Notice: the config has no data.validation block; evaluating pairs of the TRAINING data section -- the result is "
+                   "not a held-out loss", err=True)
+        val = {**config["data"], "n_pairs": None, "seed": 0}
+    loader = build_validation_loader(val, m, max(1, int(m["batch_size"])))
+    dm = build_model(m, device)
+    ck = torch.load(checkpoint, map_location=device, weights_only=False)
+    dm.model.load_state_dict(ck["model_state_dict"])
+    if ck.get("ema_state_dict") is not None and use_ema is not False:
+        dm._set_lr(m["learning_rate"])
+        dm.enable_ema(float(ck.get("ema_decay", 0.999)), bool(ck.get("ema_warmup", True)))
+        dm.optimizer.load_ema_state_dict(ck["ema_state_dict"])
+    elif use_ema:
+        raise click.ClickException(f"--use-ema: {checkpoint} holds no averaged weights")
+    res = dm.evaluate(loader, n_t=4, seed=seed, num_steps=num_steps, eta=eta, use_ema=use_ema, max_batches=max_batches)
+    per_window = res.pop("per_window", None)
+    click.echo(json.dumps(res))
+    if out_path is not None:
+        with open(out_path, "w") as f:
+            json.dump({**res, **({} if per_window is None else {"per_window": per_window.tolist()})}, f)
 
 
 @cli.command()

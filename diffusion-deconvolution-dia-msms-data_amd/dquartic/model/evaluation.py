@@ -1,0 +1,69 @@
+"""Held-out evaluation helpers (no reference counterpart: the reference's TODOS list "eval metrics ... separate from
+training").  The host side is small and pure -- which timestep a window is evaluated at, how per-window metrics are averaged -- and the
+arithmetic on the tensors is native: ``dq_randn`` for the noise, ``dq_recon_metrics`` for the metrics."""
+import numpy as np
+import torch
+
+from .. import _native as N
+
+GOLDEN_CONJUGATE = (5.0 ** 0.5 - 1.0) / 2.0  # frac(w * this) is a low-discrepancy sequence over the windows w = 0, 1, 2, ...
+
+
+def stratified_timesteps(window_ids, k: int, n_t: int, num_timesteps: int) -> np.ndarray:
+    """Timestep of repeat ``k`` (0 <= k < n_t) of each window: ``floor(((w * phi mod 1) + k) / n_t * T)`` with phi the golden-ratio
+    conjugate.  RNG-free: a window is evaluated at the same ``n_t`` timesteps whatever the batch it arrives in, one in each of the
+    ``n_t`` equal buckets of [0, T), and the offsets inside the buckets spread evenly over the windows.  int64, in [0, T)."""
+    n_t, T, k = int(n_t), int(num_timesteps), int(k)
+    if n_t < 1 or T < 1 or not 0 <= k < n_t:
+        raise ValueError(f"stratified_timesteps: need n_t >= 1, num_timesteps >= 1 and 0 <= k < n_t, got n_t={n_t}, T={T}, k={k}")
+    w = np.asarray(window_ids, dtype=np.int64).reshape(-1)
+    frac = np.mod(w.astype(np.float64) * GOLDEN_CONJUGATE, 1.0)
+    t = np.floor((frac + k) / n_t * T).astype(np.int64)
+    return np.minimum(t, T - 1)  # (frac < 1, so only a rounding of the float64 expression could reach T)
+
+
+def bucket_edges(n_t: int, num_timesteps: int):
+    """The ``n_t + 1`` edges k T / n_t of the timestep buckets: repeat k of a window is evaluated at the integer part of a point of
+    [edges[k], edges[k + 1])."""
+    return [k * int(num_timesteps) / int(n_t) for k in range(int(n_t) + 1)]
+
+
+def aggregate_metrics(per_window) -> dict:
+    """Means over the windows of an ``(n_windows, 9)`` array of ``dq_recon_metrics`` rows, keyed by ``_native.METRIC_NAMES``.  ``scan_sa``
+    and ``xic_r`` are means over a window's valid scans / XICs, so across windows they are weighted by ``scan_count`` / ``xic_count`` (the
+    mean over all valid scans / XICs of the set; 0 when there is none); everything else, the counts included, is a plain mean.  float64."""
+    a = np.asarray(per_window, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != len(N.METRIC_NAMES) or a.shape[0] < 1:
+        raise ValueError(f"aggregate_metrics: need an (n_windows >= 1, {len(N.METRIC_NAMES)}) array, got shape {a.shape}")
+    out = {name: float(a[:, i].mean()) for i, name in enumerate(N.METRIC_NAMES)}
+    for score, count in (("scan_sa", "scan_count"), ("xic_r", "xic_count")):
+        s, c = a[:, N.METRIC_NAMES.index(score)], a[:, N.METRIC_NAMES.index(count)]
+        out[score] = float((s * c).sum() / c.sum()) if c.sum() > 0 else 0.0
+    return out
+
+
+def window_noise(seed_dev: torch.Tensor, window_ids_dev: torch.Tensor, draw: int, shape) -> torch.Tensor:
+    """``dq_randn``: standard normals of ``shape`` (B, ...) keyed by (seed, window id, element, draw index): a window's noise is the same in
+    any batch."""
+    out = torch.empty(tuple(shape), dtype=torch.float32, device=window_ids_dev.device)
+    B = int(shape[0])
+    N.check(N.lib().dq_randn(N.ptr(out), N.ptr(window_ids_dev), N.ptr(seed_dev), int(draw), B, out[0].numel(), N.stream_ptr()), "dq_randn")
+    return out
+
+
+def recon_metrics(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """``dq_recon_metrics``: per-window reconstruction metrics of ``pred`` against ``target`` (both (B, RT, MZ) on the GPU) as a (B, 9)
+    float32 device tensor, columns in the order of ``_native.METRIC_NAMES``."""
+    if pred.shape != target.shape or pred.dim() != 3:
+        raise ValueError(f"recon_metrics: pred and target must both be (B, RT, MZ), got {tuple(pred.shape)} and {tuple(target.shape)}")
+    if not pred.is_cuda:
+        raise NotImplementedError("recon_metrics runs in the native library only (device tensors)")
+    p, t = pred.detach().to(torch.float32).contiguous(), target.detach().to(device=pred.device, dtype=torch.float32).contiguous()
+    B, RT, MZ = p.shape
+    nbytes = N.lib().dq_recon_metrics_scratch_bytes(B, RT, MZ)
+    if nbytes < 0:
+        raise RuntimeError("dq_recon_metrics_scratch_bytes failed")
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=p.device)
+    out = torch.empty((B, len(N.METRIC_NAMES)), dtype=torch.float32, device=p.device)
+    N.check(N.lib().dq_recon_metrics(N.ptr(p), N.ptr(t), N.ptr(out), N.ptr(scratch), nbytes, B, RT, MZ, N.stream_ptr()), "dq_recon_metrics")
+    return out

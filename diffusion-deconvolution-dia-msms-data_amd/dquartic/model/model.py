@@ -365,6 +365,40 @@ class DDIMDiffusionModel(ModelInterface):
                                       N.stream_ptr()), "dq_train_step")
         return loss
 
+    @torch.no_grad()
+    def eval_step(self, x_0, ms2_cond, ms1_cond, t=None, noise=None):
+        """Forward-only counterpart of ``train_step_fused`` (``dq_eval_step``): normalise, q_sample, U-Net forward
+        without anything kept for a backward, per-window MSE.  Returns ``(loss, per_window)`` as device tensors: ``per_window`` (B) is the
+        unweighted MSE of each window against its target (the noise for ``eps``, the normalised ``x_0`` for ``x0``), ``loss`` (0-dim) the
+        mean over windows of ``loss_weight[t_b] * per_window[b]``.  The MSE part only: the MS1 term of the training loss is not evaluated.
+        It sets no ``.grad``, needs no optimiser, uses the inference workspace and reads the averaged weights inside ``ema_scope()``.
+        ``noise`` is used as passed.  Native network only."""
+        net: UNet1d = self.model
+        if not self.native:
+            raise NotImplementedError("eval_step runs in the native library only (this package's UNet1d); "
+                                      f"the network is {type(self.model).__name__}")
+        if self.pred_type not in N.PRED_TYPES:
+            raise ValueError(f"Unknown pred_type: {self.pred_type}")
+        f32 = lambda v: v.detach().to(torch.float32).contiguous()
+        B, RT, MZ = x_0.shape
+        x_0, c2, c1 = f32(x_0), f32(ms2_cond), f32(net._check_inputs(ms1_cond, B, RT))
+        if t is None:
+            t = torch.randint(0, self.num_timesteps, (B,), device=x_0.device).long()
+        if noise is None:
+            noise = torch.randn_like(x_0)
+        t = t.to(device=x_0.device, dtype=torch.int64).contiguous()
+        noise = f32(noise)
+        flat = net.read_params()  # (the averaged weights inside ModelInterface.ema_scope())
+        ws = net.workspace(B, RT, False)
+        loss = torch.empty((), dtype=torch.float32, device=x_0.device)
+        per_window = torch.empty(B, dtype=torch.float32, device=x_0.device)
+        ab = self.alpha_bars.to(x_0.device)
+        lw = self.loss_weight.to(device=x_0.device, dtype=torch.float32).contiguous()
+        N.check(N.lib().dq_eval_step(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), N.ptr(ab), N.ptr(x_0), N.ptr(c2), N.ptr(c1), N.ptr(t),
+                                     N.ptr(noise), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], N.ptr(lw), N.ptr(loss),
+                                     N.ptr(per_window), N.ptr(ws), ws.numel(), B, RT, N.stream_ptr()), "dq_eval_step")
+        return loss, per_window
+
     def _train_step_fused_tfm(self, x_0, ms1_cond, t=None, noise=None, zero_grads=True, ms1_loss_weight=0.0):
         """train_step for the CustomTransformer behind its adapter: the same sequence as the U-Net's dq_train_step (normalise +
         q_sample, network forward, MSE and its gradient, network backward into the flat gradient buffer), each stage one native

@@ -424,9 +424,12 @@ class ModelInterface(object):
         raise NotImplementedError
 
     def train(self, dataloader, batch_size, epochs, warmup_epochs: int = 5, learning_rate: float = 1e-4, use_wandb: bool = False,
-              checkpoint_path: str = "best_model.ckpt", **kwargs):
+              checkpoint_path: str = "best_model.ckpt", *, val_dataloader=None, val_every: int = 1, **kwargs):
         """Epoch loop (reference :453-559).  ``warmup_epochs > 0`` uses the warm-up/cosine schedule, else a constant lr.
-        ``batch_size`` is accepted and unused, as in the reference (the dataloader carries it)."""
+        ``batch_size`` is accepted and unused, as in the reference (the dataloader carries it).  ``val_dataloader`` / ``val_every``: see
+        ``train_with_warmup``."""
+        if val_dataloader is not None:
+            kwargs.update(val_dataloader=val_dataloader, val_every=val_every)
         if warmup_epochs > 0:
             self.train_with_warmup(dataloader, epochs, num_warmup_steps=int(warmup_epochs), learning_rate=learning_rate,
                                    use_wandb=use_wandb, checkpoint_path=checkpoint_path, **kwargs)
@@ -435,10 +438,19 @@ class ModelInterface(object):
                                    checkpoint_path=checkpoint_path, constant_lr=True, **kwargs)
 
     def train_with_warmup(self, dataloader, num_epochs, num_warmup_steps=5, learning_rate=1e-4, use_wandb=True,
-                          log_every_n_epochs=100, checkpoint_path="best_model.ckpt", *, constant_lr: bool = False, **kwargs):
+                          log_every_n_epochs=100, checkpoint_path="best_model.ckpt", *, constant_lr: bool = False, val_dataloader=None,
+                          val_every: int = 1, **kwargs):
         """Reference :348-450, same positional order (dataloader, num_epochs, num_warmup_steps, learning_rate, use_wandb,
         log_every_n_epochs, checkpoint_path).  ``constant_lr`` (keyword-only, this build) is how ``train`` runs its
-        ``warmup_epochs <= 0`` branch (reference :498-559) through the same loop."""
+        ``warmup_epochs <= 0`` branch (reference :498-559) through the same loop.
+
+        ``val_dataloader`` (keyword-only, this build; None: everything as it always was): after every ``val_every``-th epoch
+        ``evaluate(val_dataloader)`` runs, its ``val_loss`` is printed and logged beside the epoch loss, the "best" checkpoint is chosen by
+        it instead of the noisy training loss (``best_loss`` then holds a validation loss), and the checkpoints gain a ``val_loss``
+        entry."""
+        val_every = int(val_every)
+        if val_dataloader is not None and val_every < 1:
+            raise ValueError(f"val_every must be >= 1, got {val_every}")
         self.use_wandb_epoch = bool(use_wandb)
         wandb = _wandb() if use_wandb else None
         self._prepare_training(learning_rate)
@@ -452,6 +464,10 @@ class ModelInterface(object):
         # only (node-local disks), the ranks would otherwise run epoch loops of different lengths and hang in the per-step all-reduce
         start_epoch, best_loss = self._sync_resume_state(start_epoch, best_loss, lr_scheduler)
         best_epoch = start_epoch
+        val_loss = None  # the last held-out loss (val_dataloader)
+        if val_dataloader is not None and not getattr(self, "_resumed_with_val_loss", True):
+            # resumed from a checkpoint written without validation: its best_loss is a training loss, which a held-out loss is not compared with
+            best_loss = float("inf")
         rank0 = _rank() == 0
         for epoch in range(start_epoch, num_epochs):
             if hasattr(getattr(dataloader, "sampler", None), "set_epoch"):
@@ -463,16 +479,21 @@ class ModelInterface(object):
                 lr_scheduler.step(epoch, np.mean(batch_loss))
             avg = self._global_mean(float(np.mean(batch_loss)))  # DP: the mean over ranks (one float, logging only)
             lr_now = self.optimizer.param_groups[0]["lr"]
+            # With a validation loader the epoch's score is the held-out loss (on every rank: evaluate() averages over the ranks, so the
+            # "best" decision agrees); an epoch between two validations has no score and writes the "latest" checkpoint only.
+            validated = val_dataloader is not None and (epoch + 1) % val_every == 0
+            if validated:
+                val_loss = self.evaluate(val_dataloader)["val_loss"]  # (hands the network back in training mode)
+            score = avg if val_dataloader is None else (val_loss if validated else None)
             if wandb is not None and rank0:
-                wandb.log({"epoch": epoch, "train/loss": avg, "learning_rate": lr_now})
+                wandb.log({"epoch": epoch, "train/loss": avg, "learning_rate": lr_now, **({"val/loss": val_loss} if validated else {})})
             if rank0:
-                print(f"[Training] Epoch={epoch + 1}, lr={lr_now}, loss={avg}")
-                self.save_checkpoint(lr_scheduler, epoch, avg, latest)
-                if avg < best_loss:
-                    best_loss, best_epoch = avg, epoch + 1
-                    self.save_checkpoint(lr_scheduler, epoch, best_loss, checkpoint_path)
-            elif avg < best_loss:
-                best_loss, best_epoch = avg, epoch + 1
+                print(f"[Training] Epoch={epoch + 1}, lr={lr_now}, loss={avg}" + (f", val_loss={val_loss}" if validated else ""))
+                self.save_checkpoint(lr_scheduler, epoch, best_loss if score is None else score, latest, val_loss=val_loss)
+            if score is not None and score < best_loss:
+                best_loss, best_epoch = score, epoch + 1
+                if rank0:
+                    self.save_checkpoint(lr_scheduler, epoch, best_loss, checkpoint_path, val_loss=val_loss)
             if not self.callback_handler.epoch_callback(epoch=epoch, epoch_loss=avg):
                 print(f"Training stopped at epoch {epoch}")
                 break
@@ -552,17 +573,21 @@ class ModelInterface(object):
             if scheduler is not None and ck.get("scheduler_state_dict") is not None:
                 scheduler.lambda_lr.load_state_dict(ck["scheduler_state_dict"])
             epoch, best_loss = ck["epoch"], ck["best_loss"]
+            self._resumed_with_val_loss = "val_loss" in ck  # (train with a validation loader: is best_loss a held-out loss?)
             print(f"Resumed from ({checkpoint_path}) epoch {epoch}, best loss {best_loss:.6f}")
         else:
             print(f"No checkpoint ({checkpoint_path}) found. Starting from scratch.")
             epoch, best_loss = 0, float("inf")
+            self._resumed_with_val_loss = True
         return epoch, best_loss, scheduler
 
-    def save_checkpoint(self, scheduler, epoch, best_loss, checkpoint_path):
+    def save_checkpoint(self, scheduler, epoch, best_loss, checkpoint_path, val_loss=None):
         ck = {"epoch": epoch, "model_state_dict": self.model.state_dict(), "optimizer_state_dict": self.optimizer.state_dict(),
               "scheduler_state_dict": (scheduler.lambda_lr.state_dict() if scheduler is not None else None), "best_loss": best_loss}
         if self.ema_enabled:  # (only then: without EMA the file has the reference's keys and nothing else)
             ck.update(ema_state_dict=self.optimizer.ema_state_dict(), ema_decay=self.optimizer.ema_decay, ema_warmup=self.optimizer.ema_warmup)
+        if val_loss is not None:  # (only when training validates: the held-out loss of evaluate() at this epoch)
+            ck["val_loss"] = val_loss
         torch.save(ck, checkpoint_path)
 
     # ---- exponential moving average of the weights (new work: the reference has none)
@@ -644,6 +669,74 @@ class ModelInterface(object):
             first += x_0.shape[0]
             preds.append(d)
         return np.array(preds, dtype=object)
+
+    def evaluate(self, dataloader, mixture_weights=(0.5, 0.5), n_t=4, seed=0, num_steps=None, eta=0.0, use_ema=None, max_batches=None):
+        """Held-out evaluation (new work: the reference has none).  Returns a dict.
+
+        Loss: every window of the loader is evaluated ``n_t`` times by ``eval_step`` -- repeat k at the timestep
+        ``evaluation.stratified_timesteps`` gives it (one in each of the ``n_t`` equal buckets of [0, T), no RNG) with the noise of
+        ``dq_randn(seed, window id, draw = k)``, the window id being the window's running index in the loader as in ``predict``.  Given
+        the loader's windows the numbers are therefore reproducible and do not depend on the batch size.  ``val_loss`` is the mean of
+        ``loss_weight[t] * MSE`` over all (window, repeat) pairs, ``val_loss_by_t`` = {"edges": the n_t + 1 bucket edges, "mse": per
+        bucket the mean of the UNWEIGHTED per-window MSE}, ``n_windows`` the number of windows seen.  The MSE part of the training loss
+        only (no MS1 term).
+
+        ``num_steps`` (None: loss only): every window is also sampled, ``sample(None, ..., num_steps, eta=eta, seed=seed,
+        window_ids=ids)``, and ``dq_recon_metrics(sample, x_0)`` gives nine numbers per window (``_native.METRIC_NAMES``): the dict gains
+        their means over the windows (``scan_sa`` / ``xic_r`` weighted by ``scan_count`` / ``xic_count``) under those names and the
+        ``(n_windows, 9)`` float32 array as ``per_window``.
+
+        ``use_ema`` as in ``predict``; ``max_batches``: stop after that many batches.  Under ``torch.distributed`` each rank evaluates
+        its own loader and the scalars are averaged over the ranks (``_global_mean``); ``per_window`` and ``n_windows`` stay the rank's."""
+        from . import evaluation as E
+
+        n_t = int(n_t)
+        if n_t < 1:
+            raise ValueError(f"n_t must be >= 1, got {n_t}")
+        was_training = self.model.training
+        self.model.eval()
+        T = int(self.num_timesteps)
+        lw_host = self.loss_weight.detach().to("cpu", torch.float32).numpy().astype(np.float64)
+        mse, ts, rows = [[] for _ in range(n_t)], [[] for _ in range(n_t)], []
+        first = 0
+        seed_dev = None
+        try:
+            with torch.no_grad(), self._ema_or_null_scope(use_ema):
+                for batch_idx, (ms2_1, ms1_1, ms2_2, ms1_2) in enumerate(dataloader):
+                    if max_batches is not None and batch_idx >= int(max_batches):
+                        break
+                    x_0, ms1_cond = ms2_1.to(self.device), ms1_1.to(self.device)
+                    ms2_cond = (ms2_1 * mixture_weights[0]).to(self.device) + (ms2_2 * mixture_weights[1]).to(self.device)
+                    ids = np.arange(first, first + x_0.shape[0], dtype=np.int64)
+                    ids_dev = torch.from_numpy(ids).to(x_0.device)
+                    if seed_dev is None:
+                        seed_dev = self._seed_tensor(int(seed), x_0.device)
+                    for k in range(n_t):
+                        t = E.stratified_timesteps(ids, k, n_t, T)
+                        noise = E.window_noise(seed_dev, ids_dev, k, x_0.shape)
+                        _, per_window = self.eval_step(x_0, ms2_cond, ms1_cond, t=torch.from_numpy(t).to(x_0.device), noise=noise)
+                        mse[k].append(per_window)
+                        ts[k].append(t)
+                    if num_steps is not None:
+                        sample, _ = self.sample(None, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=int(num_steps), eta=eta, seed=int(seed),
+                                                window_ids=ids_dev, shape=tuple(x_0.shape))
+                        rows.append(E.recon_metrics(sample, x_0))
+                    first += x_0.shape[0]
+        finally:
+            self.model.train(was_training)
+        if first == 0:
+            raise ValueError("evaluate: the dataloader yielded no batch")
+        # one host copy per repeat after the loop; the means are float64 sums over the windows in loader order (no batch in them)
+        mse = np.stack([torch.cat(m).cpu().numpy().astype(np.float64) for m in mse])  # (n_t, n_windows)
+        weights = np.stack([lw_host[np.concatenate(t)] for t in ts])
+        out = {"val_loss": self._global_mean(float((weights * mse).mean())),
+               "val_loss_by_t": {"edges": E.bucket_edges(n_t, T), "mse": [self._global_mean(float(m.mean())) for m in mse]},
+               "n_windows": int(first), "n_t": n_t, "seed": int(seed)}
+        if num_steps is not None:
+            per_window = torch.cat(rows).cpu().numpy()
+            out.update({k: self._global_mean(v) for k, v in E.aggregate_metrics(per_window).items()})
+            out.update(num_steps=int(num_steps), eta=float(eta), per_window=per_window)
+        return out
 
     # ---- internals
     def _init_for_training(self):

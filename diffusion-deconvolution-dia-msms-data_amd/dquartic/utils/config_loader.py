@@ -2,7 +2,8 @@
 ``dquartic/utils/config_loader.py`` (:4-57 load with CLI overrides, :60-119 default-config writer).
 Additions (all optional, defaulting to the reference behaviour): ``data.synthetic`` = {"n_windows", "RT", "MZ"} selects the
 built-in synthetic dataset instead of files; integer-like CLI overrides that arrive as strings (``--batch-size``,
-``--threads`` have no click type in the reference, cli.py:39,42) are coerced to int."""
+``--threads`` have no click type in the reference, cli.py:39,42) are coerced to int; ``data.validation`` (absent from the default
+config) describes a held-out set with the keys of ``data`` itself -- see ``validation_config``."""
 import copy
 import json
 
@@ -50,6 +51,44 @@ def load_train_config(config_path: str, **kwargs):
     cfg["model"]["batch_size"] = int(cfg["model"]["batch_size"])
     cfg["threads"] = int(cfg.get("threads", 0))
     return cfg
+
+
+_DATA_KEYS = ("parquet_directory", "ms2_data_path", "ms1_data_path", "normalize", "synthetic")
+_VALIDATION_ONLY_KEYS = ("n_pairs", "val_every", "seed")
+VALIDATION_SYNTHETIC_START = 1_000_000  # default first window of a synthetic held-out pool: far from any training pool 0 .. n_windows-1
+
+
+def validation_config(cfg):
+    """The ``data.validation`` block of a loaded train config as a complete data section, or None when the config has none.  It takes
+    the keys of ``data`` (``parquet_directory, ms2_data_path, ms1_data_path, normalize, synthetic``; ``normalize`` defaults to the training
+    set's, the paths to None) plus ``n_pairs`` (how many index pairs of its windows form the held-out set; default: one per window),
+    ``seed`` (of the generator those index pairs are drawn from; default 0 -- the set is the same in every run) and ``val_every``
+    (validate after every that-many-th epoch; default 1).  A ``synthetic`` block without ``start`` gets
+    ``VALIDATION_SYNTHETIC_START`` so that its windows are not the training pool's.  Unknown keys raise."""
+    val = cfg.get("data", {}).get("validation")
+    if val is None:
+        return None
+    if not isinstance(val, dict):
+        raise ValueError("data.validation must be an object with the keys of data")
+    unknown = sorted(set(val) - set(_DATA_KEYS) - set(_VALIDATION_ONLY_KEYS))
+    if unknown:
+        raise ValueError(f"data.validation: unknown key(s) {unknown}; it takes {list(_DATA_KEYS + _VALIDATION_ONLY_KEYS)}")
+    out = {"parquet_directory": None, "ms2_data_path": None, "ms1_data_path": None, "normalize": cfg["data"].get("normalize", "minmax"),
+           "synthetic": None, "n_pairs": None, "val_every": 1, "seed": 0}
+    out.update(copy.deepcopy(val))
+    if out["synthetic"]:
+        out["synthetic"].setdefault("start", VALIDATION_SYNTHETIC_START)
+    elif not (out["parquet_directory"] or out["ms2_data_path"]):
+        raise ValueError("data.validation needs a data source: parquet_directory / ms2_data_path + ms1_data_path, or synthetic")
+    if out["n_pairs"] is not None:
+        out["n_pairs"] = int(out["n_pairs"])
+        if out["n_pairs"] < 1:
+            raise ValueError("data.validation.n_pairs must be >= 1")
+    out["seed"] = int(out["seed"])
+    out["val_every"] = int(out["val_every"])
+    if out["val_every"] < 1:
+        raise ValueError("data.validation.val_every must be >= 1")
+    return out
 
 
 def generate_train_config(config_path: str):

@@ -76,13 +76,25 @@ class DIAMSDataset(Dataset):
             self.used_pairs.add(pair)
             return i, j
 
+    def valid_pair(self, i, j) -> bool:
+        """May windows i and j form a pair?  Distinct, and (parquet) not the same slice of the same isolation target."""
+        if i == j:
+            return False
+        return self.data_type == "npy" or not (self.meta[i][2] == self.meta[j][2] and self.meta[i][3] == self.meta[j][3])
+
     def __getitem__(self, idx):
         if self.data_type == "npy":
             i, j = self._draw_pair(len(self.ms2_data))
-            ms2_1, ms1_1, ms2_2, ms1_2 = self.ms2_data[i], self.ms1_data[i], self.ms2_data[j], self.ms1_data[j]
         else:
             same = lambda a, b: self.meta[a][2] == self.meta[b][2] and self.meta[a][3] == self.meta[b][3]
             i, j = self._draw_pair(len(self.meta), same)
+        return self.pair(i, j)
+
+    def pair(self, i, j):
+        """The normalised item of the windows (i, j): what ``__getitem__`` returns for the pair it drew (a held-out set names its pairs)."""
+        if self.data_type == "npy":
+            ms2_1, ms1_1, ms2_2, ms1_2 = self.ms2_data[i], self.ms1_data[i], self.ms2_data[j], self.ms1_data[j]
+        else:
             ms1_1, ms2_1 = self._get_parquet_data(self.meta[i])
             ms1_2, ms2_2 = self._get_parquet_data(self.meta[j])
         if self.normalize == "minmax":

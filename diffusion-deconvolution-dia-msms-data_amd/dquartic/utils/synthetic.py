@@ -67,11 +67,12 @@ def normalize_pair(ms2_1, ms1_1, ms2_2, ms1_2):
 
 class SyntheticDIAMSDataset(Dataset):
     def __init__(self, n_windows: int = 32, RT: int = 400, MZ: int = 64, normalize="minmax", seed: int = 0, rank: int = 0, world: int = 1,
-                 ms1_channels=None):
+                 ms1_channels=None, start: int = 0):
         if normalize is None:
             raise ValueError("normalize must be 'minmax' (the reference raises on None, data_loader.py:80-81)")
-        # rank r of `world` owns windows i with i % world == r
-        ids = [i for i in range(n_windows) if i % world == rank]
+        # rank r of `world` owns windows i with i % world == r; `start` shifts the pool (a held-out set: windows the
+        # training pool 0 .. n_windows-1 does not contain)
+        ids = [int(start) + i for i in range(n_windows) if i % world == rank]
         self.ms2 = np.stack([make_window(i, RT, MZ)[0] for i in ids])
         self.ms1 = np.stack([make_window(i, RT, MZ, ms1_channels)[1] for i in ids])
         self.normalize = normalize
@@ -85,5 +86,44 @@ class SyntheticDIAMSDataset(Dataset):
 
     def __getitem__(self, idx):
         a, b = self._rng.choice(len(self.ms2), size=2, replace=len(self.ms2) < 2)
+        return self.pair(a, b)
+
+    def valid_pair(self, a, b) -> bool:
+        return a != b or len(self.ms2) < 2
+
+    def pair(self, a, b):
+        """The normalised item of the windows (a, b) of the pool."""
         out = normalize_pair(self.ms2[a], self.ms1[a], self.ms2[b], self.ms1[b])
         return tuple(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for v in out)
+
+
+class FrozenPairDataset(Dataset):
+    """A held-out set: ``n_pairs`` named pairs of ``dataset``'s windows.  The reference's dataset contract ignores the index and returns a
+    fresh random pair on every access, drawn from a process-wide generator (data_loader.py:60-69) -- what training wants and what a
+    held-out set must not do.  Here the index pairs ``(i, j)`` are drawn once from a generator of their own,
+    ``numpy.random.default_rng(seed)``, so they depend on ``(len(dataset), n_pairs, seed)`` and on nothing else: the same pairs in the
+    same order in every process, every run and every restart, which is what makes two ``evaluate`` runs comparable.  Item k is
+    ``dataset.pair(*index_pairs[k])``, formed on access: nothing is kept in host memory but the indices.  ``dataset`` needs ``pair(i,
+    j)`` and ``valid_pair(i, j)`` (``DIAMSDataset``, ``SyntheticDIAMSDataset``).  ``n_pairs`` None: one pair per window of the dataset."""
+
+    def __init__(self, dataset, n_pairs=None, seed: int = 0):
+        n_windows = len(dataset)
+        n = n_windows if n_pairs is None else int(n_pairs)
+        if n < 1 or n_windows < 1:
+            raise ValueError(f"FrozenPairDataset: need at least one pair and one window, got {n} pairs of {n_windows} windows")
+        rng = np.random.default_rng(int(seed))
+        self.dataset, self.seed, self.index_pairs = dataset, int(seed), []
+        tries = 0
+        while len(self.index_pairs) < n:
+            i, j = (int(v) for v in rng.integers(0, n_windows, size=2))
+            tries += 1
+            if dataset.valid_pair(i, j):
+                self.index_pairs.append((i, j))
+            elif tries > 1000 * n + 1000:
+                raise ValueError("FrozenPairDataset: the dataset has no two windows that may form a pair")
+
+    def __len__(self):
+        return len(self.index_pairs)
+
+    def __getitem__(self, idx):
+        return self.dataset.pair(*self.index_pairs[idx])

@@ -205,6 +205,55 @@ int dq_train_step(dq_plan* plan, const float* params, const float* rope_freqs, c
                   int pred_type, const float* loss_weight_dev, float ms1_loss_weight, float* grads, float* loss_out, void* workspace,
                   int64_t workspace_bytes, int B, int RT, void* stream);
 
+/* ---- held-out evaluation (no reference counterpart: the reference's TODOS list "eval metrics ... separate from training"; DESIGN.md
+ * section 24).  Additive at ABI version 12: dq_eval_step, dq_mse_per_window, dq_mse_per_window_scratch_bytes, dq_recon_metrics,
+ * dq_recon_metrics_scratch_bytes.
+ * dq_eval_step: the forward-only counterpart of dq_train_step -- q_sample (normalising as auto_normalize says), the network forward without
+ * anything kept for a backward, then dq_mse_per_window.  Arguments as dq_train_step without grads and ms1_loss_weight; two outputs:
+ *   per_window_out  B device floats: the unweighted MSE of window b between the network output and its target (DQ_PRED_EPS: the noise;
+ *                   DQ_PRED_X0: the normalised x0);
+ *   loss_out        1 device float: mean_b loss_weight_dev[t_b] * per_window[b]; the table is required for DQ_PRED_X0 and ignored (may be
+ *                   NULL: all ones) for DQ_PRED_EPS, as in the train step.
+ * It reports the MSE part only: the MS1 term of the training loss (ms1_loss_weight > 0) is not evaluated.  workspace: the INFERENCE size,
+ * dq_unet_workspace_bytes(plan, B, RT, 0).  It touches no gradient buffer and nothing of the backward's side queue: called between two
+ * train steps it leaves the second bit for bit what it would have been.  params is read by pointer (pass the EMA buffer to evaluate the
+ * averaged weights).  A window's per_window value does not depend on the batch it is computed in. */
+int dq_eval_step(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_dev, const float* x0,
+                 const float* ms2_cond, const float* ms1_cond, const int64_t* t, const float* noise, int auto_normalize, int pred_type,
+                 const float* loss_weight_dev, float* loss_out, float* per_window_out, void* workspace, int64_t workspace_bytes, int B, int RT,
+                 void* stream);
+/* The reduction of dq_eval_step on caller-supplied tensors (k_mse_per_window, k_stream.hip): out, target (B, per) fp32;
+ * target' = target * tm + ta in fp32 as in dq_mse_loss_weighted_fwd_bwd; per element d = (double)out - (double)target', d * d summed in fp64.
+ * A window is cut into slices of 8192 elements (a function of per alone, never of B), one workgroup each; the slice sums are added in index
+ * order (no atomics) and per_window_out[b] = (float)(sum / per) is rounded once.  loss_out = (float)(sum_b lw[t_b] * (sum_b / per) / B), the
+ * sum over windows in fp64 in index order; lw NULL: all ones (t is then not read).  0 < B <= 65535.
+ * scratch: dq_mse_per_window_scratch_bytes(B, per) = 8 * B * ceil(per / 8192) bytes, 8-byte aligned (-1 for B or per < 1). */
+int64_t dq_mse_per_window_scratch_bytes(int B, int64_t per);
+int dq_mse_per_window(const float* out, const float* target, float tm, float ta, const float* lw, const int64_t* t, float* per_window_out,
+                      float* loss_out, void* scratch, int B, int64_t per, void* stream);
+/* Reconstruction metrics of pred against target, both (B, RT, MZ) fp32 (k_metrics.hip): out (B, DQ_METRIC_COUNT) floats per window, every sum
+ * in fp64 over the fp32 inputs (n = RT * MZ), every output rounded to fp32 once:
+ *   0 mse         sum (P - T)^2 / n
+ *   1 mae         sum |P - T| / n
+ *   2 cosine      sum P T / sqrt(sum P^2 * sum T^2); 0 if either norm is 0
+ *   3 sa          1 - 2 acos(clamp(cosine, -1, 1)) / pi   (spectral angle)
+ *   4 pearson     Pearson r over all n elements, from sums shifted by the window's first element (a constant window has variance exactly 0);
+ *                 0 if either variance is 0
+ *   5 scan_sa     mean over the valid scans of sa between P[r, :] and T[r, :]; a scan (RT row) is valid if sum T[r, :]^2 > 0, a valid scan
+ *                 with an all-zero P row scores 0; 0 without a valid scan
+ *   6 scan_count  number of valid scans
+ *   7 xic_r       mean over the valid XICs of Pearson r along RT between P[:, c] and T[:, c] (sums shifted by the column's first element); an
+ *                 XIC (m/z column) is valid if Var_r T[:, c] > 0 and scores 0 when Var_r P[:, c] = 0; 0 without a valid XIC
+ *   8 xic_count   number of valid XICs
+ * RT, MZ any positive values.  No atomics; the work partition depends on (RT, MZ) only: a window's row is bit for bit the same in any batch.
+ * scratch: dq_recon_metrics_scratch_bytes(B, RT, MZ) = 8 * B * (10 * RT * ceil(MZ / 4096) + 5 * MZ * ceil(RT / 64)) bytes, 8-byte aligned
+ * (-1 for a size < 1). */
+enum { DQ_METRIC_MSE = 0, DQ_METRIC_MAE = 1, DQ_METRIC_COSINE = 2, DQ_METRIC_SA = 3, DQ_METRIC_PEARSON = 4, DQ_METRIC_SCAN_SA = 5,
+       DQ_METRIC_SCAN_COUNT = 6, DQ_METRIC_XIC_R = 7, DQ_METRIC_XIC_COUNT = 8, DQ_METRIC_COUNT = 9 };
+int64_t dq_recon_metrics_scratch_bytes(int B, int RT, int MZ);
+int dq_recon_metrics(const float* pred, const float* target, float* out, void* scratch, int64_t scratch_bytes, int B, int RT, int MZ,
+                     void* stream);
+
 /* ---- DDIMDiffusionModel.sample (model.py:293-324) --------------------------------------------------------------
  * Runs the whole strided loop natively over timesteps_host[num_steps] (host ints; the caller forms them as
  * trunc(linspace(T-1, 0, num_steps)), model.py:313): each step = network forward + K9 (landing on alpha_bars[t-1],
