@@ -14,7 +14,10 @@ namespace dq {
 //   b_kmajor = 0: B(k, n) = B[k * ldb + n]   (a row-major (K, N) matrix: the W of dX = dY W, the V of P V)
 // C(m, n) = C[m * ldc + n].  Batched over z = zo * inner + zi with element offsets zo * s?o + zi * s?i per operand
 // (attention: zo = sample, zi = head).  K beyond the split / M, N beyond the tile are zero-filled / masked.
-// Requirements (checked): lda, ldb, K multiples of 4 and 16-byte aligned bases (vector loads along the contiguous axis).
+// Requirements (checked by launch_gemm): lda, ldb, the batch strides of A and B and (kbatch > 1) sAk, sBk multiples of 4 floats, A and B
+// 16-byte aligned (vector loads along the contiguous axis); K > 0, inner > 0, kbatch >= 1.  K itself may be ANY positive length (the
+// last vector of a row is loaded element by element; wide_wgrad passes K = RT); ldc, the strides of C and its alignment are free
+// (scalar stores).  The (a_kmajor = 0, b_kmajor = 1) layout is not built; `add` needs accumulate = 0 and an unsplit plan.
 // arithmetic of a product: exact fp32 on v_mfma_f32_32x32x2_f32, or three bf16 passes over split operands (k_gemm.hip: k_gemm_s3)
 enum GemmPrecision { GEMM_FP32 = 0, GEMM_BF16X3 = 1 };
 struct Gemm {
@@ -38,6 +41,11 @@ struct Gemm {
   int precision = -1;  // GemmPrecision, or -1 = the calling thread's default (set_gemm_precision; GEMM_FP32 unless changed)
 };
 int launch_gemm(const Gemm& g, hipStream_t s);
+// What launch_gemm does with a product: the tile height and up to two launches over disjoint ranges of the (cdiv(M, bm) x cdiv(N, 128))
+// tile grid (k_gemm.hip: choose()).  kv is the reduction length the splits cut (kbatch > 1: kbatch blocks of K rounded up to the k-tile).
+struct GemmPart { int tile_base = 0, ntiles = 0, splits = 1, k_per_split = 0; };
+struct GemmShape { int bm = 128; GemmPart full, rest; int kv = 0; int64_t scratch = 0; };  // scratch: floats launch_gemm asks of `partial`
+GemmShape gemm_plan(int M, int N, int K, int batch, int kbatch, int splits);  // M, N, K, batch, kbatch >= 1; splits = 0: chosen
 int set_gemm_precision(int precision);  // thread-local default of launch_gemm; returns the previous one
 int64_t gemm_partial_floats(int M, int N, int K, int batch);  // upper bound of what launch_gemm will ask of `partial`
 

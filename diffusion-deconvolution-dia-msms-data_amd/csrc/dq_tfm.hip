@@ -176,21 +176,53 @@ using namespace dq;
 extern "C" {
 
 int64_t dq_gemm_scratch_floats(int M, int N, int K) { return std::max<int64_t>(gemm_partial_floats(M, N, K, 1), 4); }
-int dq_gemm(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
-            int a_kmajor, int b_kmajor, int accumulate, int splits, float* scratch, int64_t scratch_floats, void* stream) {
+// the descriptor of the C ABI -> the launcher's own (field for field)
+static int run_desc(const dq_gemm_desc& d, void* stream) {
+  DQ_REQUIRE(d.precision == DQ_PRECISION_FP32 || d.precision == DQ_PRECISION_BF16X3, "dq_gemm_ex: precision must be DQ_PRECISION_FP32 or DQ_PRECISION_BF16X3");
   Gemm g;
-  g.A = A; g.B = B; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.a_kmajor = a_kmajor; g.b_kmajor = b_kmajor; g.accumulate = accumulate; g.splits = splits; g.partial = scratch; g.partial_floats = scratch_floats;
+  g.A = d.A; g.B = d.B; g.C = d.C; g.M = d.M; g.N = d.N; g.K = d.K; g.lda = d.lda; g.ldb = d.ldb; g.ldc = d.ldc;
+  g.a_kmajor = d.a_kmajor; g.b_kmajor = d.b_kmajor; g.batch = d.batch; g.inner = d.inner;
+  g.sAo = d.sAo; g.sAi = d.sAi; g.sBo = d.sBo; g.sBi = d.sBi; g.sCo = d.sCo; g.sCi = d.sCi;
+  g.kbatch = d.kbatch; g.sAk = d.sAk; g.sBk = d.sBk;
+  g.bias = d.bias; g.bias_m = d.bias_m; g.alpha = d.alpha; g.accumulate = d.accumulate; g.add = d.add;
+  g.splits = d.splits; g.partial = d.scratch; g.partial_floats = d.scratch_floats;
+  g.precision = d.precision == DQ_PRECISION_BF16X3 ? GEMM_BF16X3 : GEMM_FP32;
   return launch_gemm(g, (hipStream_t)stream);
 }
-
+static dq_gemm_desc plain_desc(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int64_t lda, int64_t ldb,
+                               int64_t ldc, int a_kmajor, int b_kmajor, int accumulate, int splits, float* scratch, int64_t scratch_floats,
+                               int precision) {
+  dq_gemm_desc d = {};
+  d.A = A; d.B = B; d.C = C; d.bias = bias; d.M = M; d.N = N; d.K = K; d.lda = lda; d.ldb = ldb; d.ldc = ldc;
+  d.a_kmajor = a_kmajor; d.b_kmajor = b_kmajor; d.batch = 1; d.inner = 1; d.kbatch = 1; d.alpha = 1.f;
+  d.accumulate = accumulate; d.splits = splits; d.scratch = scratch; d.scratch_floats = scratch_floats; d.precision = precision;
+  return d;
+}
+int dq_gemm(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
+            int a_kmajor, int b_kmajor, int accumulate, int splits, float* scratch, int64_t scratch_floats, void* stream) {
+  return run_desc(plain_desc(A, B, C, bias, M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor, accumulate, splits, scratch, scratch_floats,
+                             DQ_PRECISION_FP32), stream);
+}
 int dq_gemm_bf16x3(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
                    int a_kmajor, int b_kmajor, int accumulate, int splits, float* scratch, int64_t scratch_floats, void* stream) {
-  Gemm g;
-  g.A = A; g.B = B; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.a_kmajor = a_kmajor; g.b_kmajor = b_kmajor; g.accumulate = accumulate; g.splits = splits; g.partial = scratch; g.partial_floats = scratch_floats;
-  g.precision = GEMM_BF16X3;
-  return launch_gemm(g, (hipStream_t)stream);
+  return run_desc(plain_desc(A, B, C, bias, M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor, accumulate, splits, scratch, scratch_floats,
+                             DQ_PRECISION_BF16X3), stream);
+}
+int dq_gemm_ex(const dq_gemm_desc* desc, void* stream) {
+  DQ_REQUIRE(desc, "dq_gemm_ex: null descriptor");
+  return run_desc(*desc, stream);
+}
+int dq_debug_gemm_plan(int M, int N, int K, int batch, int kbatch, int splits, int32_t* out, int cap, int64_t* scratch_floats) {
+  if (!out || cap < DQ_GEMM_PLAN_INTS || M < 1 || N < 1 || K < 1 || batch < 1 || kbatch < 1 || splits < 0) return -1;
+  const GemmShape sh = gemm_plan(M, N, K, batch, kbatch, splits);
+  int n = 0;
+  out[n++] = sh.bm;
+  out[n++] = sh.kv;
+  for (const GemmPart* p : {&sh.full, &sh.rest}) {
+    out[n++] = p->tile_base; out[n++] = p->ntiles; out[n++] = p->splits; out[n++] = p->k_per_split;
+  }
+  if (scratch_floats) *scratch_floats = sh.scratch;
+  return n;
 }
 
 int dq_tfm_set_precision(dq_tfm* tfm, int precision) {

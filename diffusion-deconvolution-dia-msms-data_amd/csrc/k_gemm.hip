@@ -419,8 +419,8 @@ __global__ void __launch_bounds__(256) k_gemm_split_reduce(GemmK g, int ntiles, 
 
 // A product is run as up to two launches over disjoint tile ranges: the whole rounds of 256 tiles (one per CU) unsplit, and the
 // remaining tiles -- or all of them when there are fewer than 256 -- with the reduction split so that they, too, cover the machine.
-struct Part { int tile_base = 0, ntiles = 0, splits = 1, k_per_split = 0; };
-struct Shape { int bm = 128; Part full, rest; };
+using Part = GemmPart;
+using Shape = GemmShape;
 constexpr int MAX_SPLIT_TILES = 1024;  // tiles x splits of a split launch: bounds the scratch at 1024 x 128 x 128 floats
 // Tile height and the split of the remainder by a small cost model of the 256-CU machine: blocks are dealt to the CUs in rounds,
 // a block costs (k-steps x MFMA cycles of its tile + a fixed prologue / epilogue), a split adds the second kernel and its
@@ -493,10 +493,15 @@ int launch_part(GemmK k, const Part& p, int bm, hipStream_t s, int precision) {
 int64_t part_scratch(const Part& p, int bm, int batch) { return p.splits > 1 ? (int64_t)p.splits * batch * p.ntiles * bm * 128 : 0; }
 }  // namespace
 
-int64_t gemm_partial_floats(int M, int N, int K, int batch) {
-  const Shape sh = choose(M, N, K, batch, 0);
-  return std::max(part_scratch(sh.full, sh.bm, batch), part_scratch(sh.rest, sh.bm, batch));
+GemmShape gemm_plan(int M, int N, int K, int batch, int kbatch, int splits) {
+  const int kv = kbatch > 1 ? kbatch * (cdiv(K, BK) * BK) : K;  // a k-tile never straddles two blocks of a k-batched product
+  Shape sh = choose(M, N, kv, batch, splits);
+  sh.kv = kv;
+  sh.scratch = std::max(part_scratch(sh.full, sh.bm, batch), part_scratch(sh.rest, sh.bm, batch));
+  return sh;
 }
+
+int64_t gemm_partial_floats(int M, int N, int K, int batch) { return gemm_plan(M, N, K, batch, 1, 0).scratch; }
 
 static thread_local int g_default_precision = GEMM_FP32;
 int set_gemm_precision(int precision) {
@@ -515,7 +520,7 @@ int launch_gemm(const Gemm& g, hipStream_t s) {
   DQ_REQUIRE((g.sAo % 4 == 0) && (g.sAi % 4 == 0) && (g.sBo % 4 == 0) && (g.sBi % 4 == 0), "gemm: batch strides of A and B must be multiples of 4");
   DQ_REQUIRE(g.kbatch >= 1 && (g.kbatch == 1 || (g.sAk % 4 == 0 && g.sBk % 4 == 0)), "gemm: bad k-batch count / strides");
   const int kp = cdiv(g.K, BK) * BK;
-  const Shape sh = choose(g.M, g.N, g.kbatch > 1 ? g.kbatch * kp : g.K, g.batch, g.splits);
+  const Shape sh = gemm_plan(g.M, g.N, g.K, g.batch, g.kbatch, g.splits);
   GemmK k;
   k.A = g.A; k.B = g.B; k.C = g.C; k.M = g.M; k.N = g.N; k.K = g.K; k.lda = g.lda; k.ldb = g.ldb; k.ldc = g.ldc;
   k.batch = g.batch; k.inner = g.inner; k.sAo = g.sAo; k.sAi = g.sAi; k.sBo = g.sBo; k.sBi = g.sBi; k.sCo = g.sCo; k.sCi = g.sCi;
@@ -523,7 +528,7 @@ int launch_gemm(const Gemm& g, hipStream_t s) {
   DQ_REQUIRE(!g.add || (!g.accumulate && std::max(sh.full.splits, sh.rest.splits) <= 1), "gemm: `add` needs an unsplit, non-accumulating product");
   k.splits = 1; k.k_per_split = 0; k.partial = g.partial; k.tile_base = 0; k.mt = cdiv(g.M, sh.bm);
   k.kb = g.kbatch; k.kp = kp; k.sAk = g.sAk; k.sBk = g.sBk;
-  const int64_t need = std::max(part_scratch(sh.full, sh.bm, g.batch), part_scratch(sh.rest, sh.bm, g.batch));
+  const int64_t need = sh.scratch;
   if (need > 0) DQ_REQUIRE(g.partial && g.partial_floats >= need, "gemm: split-K scratch missing or too small");
   DQ_REQUIRE((int64_t)k.batch * std::max(sh.full.splits, sh.rest.splits) <= 65535, "gemm: batch x splits exceeds the grid");
   for (const Part* p : {&sh.full, &sh.rest}) {

@@ -21,6 +21,7 @@ CONV_WGRAD_FORMS = ("wg", "v4", "scalar")  # DQ_CONV_WGRAD_*
 LEVEL_KINDS = ("unfused", "kernel", "tiny")  # DQ_LEVEL_* (index = value)
 LEVEL_FORM_FIELDS = ("kind", "img", "la", "post_w", "in_folded", "resample")  # DQ_LEVEL_PLAN_FORM_INTS, in the order dq_debug_level_plan writes them
 METRIC_NAMES = ("mse", "mae", "cosine", "sa", "pearson", "scan_sa", "scan_count", "xic_r", "xic_count")  # DQ_METRIC_* (index = column of dq_recon_metrics' output)
+GEMM_PLAN_PART_FIELDS = ("tile_base", "ntiles", "splits", "k_per_split")  # of `full`, then of `rest`, after bm and kv (DQ_GEMM_PLAN_INTS)
 LEVEL_PLAN_FLAGS = ("prep_ok", "init_fused", "head_shape", "head_train", "use_tb_up", "use_tb_dn", "tb_up_w")  # DQ_LEVEL_PLAN_FLAG_INTS
 
 # name -> (restype, argtypes); this table is checked against include/dq_hip.h by tests/test_abi.py
@@ -99,6 +100,8 @@ PROTOTYPES = {
                         c_void_p]),
     "dq_gemm_bf16x3": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64,
                                c_void_p]),
+    "dq_gemm_ex": (c_int, [c_void_p, c_void_p]),
+    "dq_debug_gemm_plan": (c_int, [c_int] * 6 + [POINTER(c_int32), c_int, POINTER(c_int64)]),
     "dq_tfm_bwd_buckets": (c_int, [c_void_p] * 8 + [c_int] + [c_void_p] * 3 + [c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dq_tfm_num_buckets": (c_int, [c_void_p]),
     "dq_tfm_bucket_info": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
@@ -233,6 +236,42 @@ def level_plan(plan, B: int, RT: int, save: bool, twin: bool) -> dict:
     out = {"levels": int(L), "dn": [form(i) for i in range(L)], "up": [form(L + i) for i in range(L + 1)]}
     out.update({k: bool(x) for k, x in zip(LEVEL_PLAN_FLAGS, buf[1 + nf * (2 * L + 1): n])})
     return out
+
+
+class GemmDesc(ctypes.Structure):
+    """``dq_gemm_desc`` of include/dq_hip.h, field for field."""
+    _fields_ = ([(k, c_void_p) for k in ("A", "B", "C", "bias", "bias_m", "add", "scratch")]
+                + [(k, c_int64) for k in ("scratch_floats", "lda", "ldb", "ldc", "sAo", "sAi", "sBo", "sBi", "sCo", "sCi", "sAk", "sBk")]
+                + [(k, c_int32) for k in ("M", "N", "K", "a_kmajor", "b_kmajor", "batch", "inner", "kbatch", "accumulate", "splits", "precision")]
+                + [("alpha", c_float)])
+
+
+def gemm_desc(**fields) -> GemmDesc:
+    """A ``dq_gemm_desc`` with the defaults of a plain fp32 product (k-major operands, batch = inner = kbatch = 1, alpha = 1), then ``fields``;
+    pointers are given as integers (``tensor.data_ptr()``) or None."""
+    d = GemmDesc(a_kmajor=1, b_kmajor=1, batch=1, inner=1, kbatch=1, alpha=1.0)
+    for k, v in fields.items():
+        if not hasattr(d, k):
+            raise AttributeError(f"dq_gemm_desc has no field {k!r}")
+        setattr(d, k, v)
+    return d
+
+
+def gemm_ex(desc: GemmDesc, stream=None) -> int:
+    """``dq_gemm_ex``: returns the library's code (0 = done); the caller decides whether a refusal is an error (``check``)."""
+    return int(lib().dq_gemm_ex(ctypes.byref(desc), stream))
+
+
+def gemm_plan(M: int, N: int, K: int, batch: int = 1, kbatch: int = 1, splits: int = 0) -> dict:
+    """``dq_debug_gemm_plan``: ``bm``, ``kv``, the ``full`` and ``rest`` launches (dicts of GEMM_PLAN_PART_FIELDS) and the ``scratch``
+    floats of the product, as the launcher itself plans it."""
+    buf, scratch = (c_int32 * 10)(), c_int64(-1)
+    n = lib().dq_debug_gemm_plan(int(M), int(N), int(K), int(batch), int(kbatch), int(splits), buf, 10, ctypes.byref(scratch))
+    if n != 2 + 2 * len(GEMM_PLAN_PART_FIELDS):
+        raise RuntimeError(f"dq_debug_gemm_plan failed for M={M}, N={N}, K={K}, batch={batch}, kbatch={kbatch}, splits={splits}")
+    nf = len(GEMM_PLAN_PART_FIELDS)
+    return {"bm": int(buf[0]), "kv": int(buf[1]), "full": dict(zip(GEMM_PLAN_PART_FIELDS, (int(x) for x in buf[2:2 + nf]))),
+            "rest": dict(zip(GEMM_PLAN_PART_FIELDS, (int(x) for x in buf[2 + nf:2 + 2 * nf]))), "scratch": int(scratch.value)}
 
 
 def check(rc, what):

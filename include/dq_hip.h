@@ -48,7 +48,8 @@ const char* dq_last_error(void);
  * dq_plan_final_act, dq_get_option_effective, dq_resblock_forms, dq_linattn_forms, dq_linattn_bwd_store, dq_plan_create_ex,
  * dq_plan_attn_cond_channels, dq_ms1_feat_fwd, dq_ms1_feat_wgrad, dq_ms1_feat_wgrad_scratch_floats).  11: dq_conv_bwd,
  * dq_conv_bwd_workspace_floats, dq_conv_bwd_forms (later, additive: dq_adamw_clip_ema_step, dq_adamw_clip_ema_step_dev; dq_randn,
- * dq_ddim_step_sto, dq_ddim_coef_table, dq_ddim_sample_ex).  12: dq_debug_level_plan. */
+ * dq_ddim_step_sto, dq_ddim_coef_table, dq_ddim_sample_ex).  12: dq_debug_level_plan (later, additive: dq_gemm_ex,
+ * dq_debug_gemm_plan). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -369,6 +370,42 @@ int dq_gemm(const float* A, const float* B, float* C, const float* bias, int M, 
 int dq_gemm_bf16x3(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int64_t lda, int64_t ldb,
                    int64_t ldc, int a_kmajor, int b_kmajor, int accumulate, int splits, float* scratch, int64_t scratch_floats,
                    void* stream);
+/* The same launcher with every operand mode the library itself uses, on a caller-filled descriptor (additive at ABI version 12; exported
+ * for the parity tests).  Zero-initialise the struct, then set batch = inner = kbatch = 1 and alpha = 1 for a plain product.
+ *   C[z](m, n) (+)= alpha * sum over b < kbatch, k < K of A[z][b](m, k) B[z][b](k, n) + bias[n] + bias_m[m] (+ add[z](m, n))
+ * z = zo * inner + zi < batch; operand offsets in floats: A[z][b] = A + zo sAo + zi sAi + b sAk, B likewise, C[z] = C + zo sCo + zi sCi;
+ * add is laid out like C.  Required (refused with an error otherwise): lda, ldb, the strides of A and B multiples of 4, A and B 16-byte
+ * aligned, K > 0 (any length), inner > 0, kbatch >= 1, not (a_kmajor = 0 with b_kmajor = 1), add only with accumulate = 0 and an unsplit
+ * plan, batch x splits <= 65535, scratch of at least the floats dq_debug_gemm_plan reports.  M, N or batch <= 0: nothing to do, returns 0.
+ * Rows / columns beyond M, N, K are never read into a result, and nothing outside the (M x N) window of a C[z] is written. */
+typedef struct dq_gemm_desc {
+  const float* A; const float* B; float* C;
+  const float* bias;   /* (N), nullable */
+  const float* bias_m; /* (M), nullable */
+  const float* add;    /* nullable */
+  float* scratch;      /* split-K partial tiles; nullable when the plan is unsplit */
+  int64_t scratch_floats;
+  int64_t lda, ldb, ldc;
+  int64_t sAo, sAi, sBo, sBi, sCo, sCi;
+  int64_t sAk, sBk;
+  int32_t M, N, K;
+  int32_t a_kmajor, b_kmajor;
+  int32_t batch, inner, kbatch;
+  int32_t accumulate;
+  int32_t splits;      /* 0: chosen by the library; > 0: forced (capped at the number of k-tiles) */
+  int32_t precision;   /* DQ_PRECISION_FP32 or DQ_PRECISION_BF16X3 */
+  float alpha;
+} dq_gemm_desc;
+int dq_gemm_ex(const dq_gemm_desc* desc, void* stream);
+/* Test hook: what the launcher does with a product of this shape -- evaluated by the launcher's own planning function, without a launch
+ * or a device.  A product runs as up to two launches over disjoint ranges of its tile grid (cdiv(M, bm) x cdiv(N, 128) tiles, m fastest):
+ * `full`, the whole rounds of 256 tiles, unsplit, and `rest`, the remaining tiles, possibly with the reduction split.  out receives
+ * DQ_GEMM_PLAN_INTS ints: bm (32, 64 or 128), kv (the reduction length the splits cut: K, or kbatch * (K rounded up to 32) when
+ * kbatch > 1), then tile_base, ntiles, splits, k_per_split of `full` and of `rest`.  *scratch_floats (nullable) receives the floats
+ * dq_gemm_ex asks of `scratch` for this product (0: none), for any batch -- dq_gemm_scratch_floats covers batch = kbatch = 1, splits = 0.
+ * Returns the number of ints written, or -1 (null out, cap too small, M, N, K, batch or kbatch < 1, splits < 0). */
+enum { DQ_GEMM_PLAN_INTS = 10 };
+int dq_debug_gemm_plan(int M, int N, int K, int batch, int kbatch, int splits, int32_t* out, int cap, int64_t* scratch_floats);
 
 /* ---- building blocks exported for the per-block parity tests (tests/test_blocks_gpu.py) ------------------------
  * Each runs the SAME kernels / dispatch the network uses, on caller-supplied tensors, so that the reference's per-block
