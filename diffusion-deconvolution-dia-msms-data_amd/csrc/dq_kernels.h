@@ -23,6 +23,11 @@ int launch_randn(float* out, const int64_t* ids, const uint64_t* seed_dev, int d
 int launch_ddim_step_sto(const float* x_t, const float* eps, float* x_prev, float* eps_out, const float* coef_dev, const float* sigma_dev,
                          const int64_t* ids, const uint64_t* seed_dev, int draw, int pred_x0, int B, int64_t per_window,
                          const int* step_ptr, hipStream_t s);
+// ---- k_solver.hip: x_prev = cx*x + c0*x0 + c1*hist over rows [sa, sb, cx, c0] of coef_dev and c1_dev (one float per row; step_ptr nullable:
+// row index on the device); x0 clamped to [-clip, clip] when clip > 0; hist (nullable when every c1 is 0) receives x0; eps_out nullable;
+// x_prev may alias x_t, eps_out may alias net.  16-byte accesses when n % 4 == 0 and every tensor is 16-byte aligned.
+int launch_solver_step(const float* x_t, const float* net, float* x_prev, float* hist, float* eps_out, const float* coef_dev,
+                       const float* c1_dev, float clip, int pred_x0, int64_t n, const int* step_ptr, hipStream_t s);
 int launch_sample_finish(const float* x, const float* ms2_cond, float* out_x, float* out_noise, int64_t n, int normalize,
                          hipStream_t s);
 int launch_mse_fwd_bwd(const float* eps, const float* noise, float* loss_out, float* grad_out, float* partials, int64_t n,

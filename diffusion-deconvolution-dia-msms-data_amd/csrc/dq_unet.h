@@ -78,6 +78,9 @@ struct dq_plan {
   hipStream_t cap_stream = nullptr;  // capture-only stream (the caller's may be the uncapturable legacy default stream)
   const void* g_params = nullptr; const void* g_rope = nullptr; const void* g_ws = nullptr;
   int g_B = 0, g_RT = 0, g_norm = -1, g_pred = -1;
-  int g_sto = -1;  // the captured step ends in k_ddim_step_sto (eta > 0) or in the deterministic update (eta == 0)
+  // the captured step's update: 0 the deterministic update (eta == 0; the reference and the strided table alike), 1 k_ddim_step_sto
+  // (eta > 0), 2 / 3 k_solver_step without / with the x0 history; g_clip: the clamp baked into k_solver_step's arguments (0: off)
+  int g_sto = -1;
+  float g_clip = 0.f;
   unsigned g_opt_epoch = 0;  // dq::options_epoch() at capture time (a dq_set_option call may change the dispatch baked into the graph)
 };

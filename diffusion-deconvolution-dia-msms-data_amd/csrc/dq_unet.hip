@@ -1840,6 +1840,85 @@ int dq_ddim_coef_table(const float* alpha_bars_host, int num_timesteps, const in
   return 0;
 }
 
+// Rows of the step-consistent samplers (host only).  Step i at t = ts[i] lands on ts[i + 1]; the last step of the list
+// returns x0 whatever its t.  kind DQ_SAMPLER_DDIM: dq_ddim_coef_table's expressions with abp = alpha_bars[ts[i + 1]].  kind
+// DQ_SAMPLER_DPMPP_2M: [sa, sb, cx, c0] and c1 in double from the fp32 table values; SOLVER_ORDER1: the same rows with c1 = 0 everywhere
+// (strided DDIM as a solver row: what clip_x0 runs).
+namespace {
+constexpr int SOLVER_ORDER1 = 3;
+
+int sampler_rows(const float* ab_tab, int T, const int32_t* ts, int n, int kind, float eta, float* coef_out, float* extra_out, const char* who) {
+  for (int i = 0; i < n; ++i) {
+    if (ts[i] < 0 || ts[i] >= T) { dq::set_error(std::string(who) + ": timestep out of range"); return 1; }
+    if (i > 0 && ts[i] >= ts[i - 1]) { dq::set_error(std::string(who) + ": the timesteps of this sampler must be strictly decreasing"); return 1; }
+  }
+  double h_prev = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const float ab = ab_tab[ts[i]];
+    const bool last = i == n - 1;
+    extra_out[i] = 0.f;
+    if (kind == DQ_SAMPLER_DDIM) {
+      coef_out[4 * i + 0] = std::sqrt(ab);
+      coef_out[4 * i + 1] = std::sqrt(1.0f - ab);
+      if (last) { coef_out[4 * i + 2] = -1.f; coef_out[4 * i + 3] = 0.f; continue; }
+      const float abp = ab_tab[ts[i + 1]];
+      coef_out[4 * i + 2] = std::sqrt(abp);
+      coef_out[4 * i + 3] = std::sqrt(1.0f - abp);
+      if (eta > 0.f) {  // (dq_ddim_coef_table's sigma and c, with this abp)
+        const double a = (double)ab, ap = (double)abp;
+        const double ratio = ap > 0.0 ? std::min(a / ap, 1.0) : 1.0;
+        const double sg = (1.0 - a) > 0.0 ? (double)eta * std::sqrt((1.0 - ap) / (1.0 - a)) * std::sqrt(1.0 - ratio) : 0.0;
+        coef_out[4 * i + 3] = (float)std::sqrt(std::max(0.0, 1.0 - ap - sg * sg));
+        extra_out[i] = (float)sg;
+      }
+      continue;
+    }
+    const double al = std::sqrt((double)ab), sg = std::sqrt(1.0 - (double)ab);
+    coef_out[4 * i + 0] = (float)al;
+    coef_out[4 * i + 1] = (float)sg;
+    if (last) { coef_out[4 * i + 2] = -1.f; coef_out[4 * i + 3] = 0.f; continue; }
+    const double abp = (double)ab_tab[ts[i + 1]];
+    const double alp = std::sqrt(abp), sgp = std::sqrt(1.0 - abp);
+    // h = lambda_{i+1} - lambda_i, lambda = log(alpha / sigma); a schedule end with sigma or alpha exactly 0 gives h = inf: 1 - e^-h = 1
+    const double h = std::log(alp / sgp) - std::log(al / sg);
+    const double em = std::isnan(h) ? 1.0 : -std::expm1(-h);
+    const double base = alp * em;
+    double c0 = base, c1 = 0.0;
+    const bool second = kind == DQ_SAMPLER_DPMPP_2M && i >= 1 && std::isfinite(h) && h > 0.0 && std::isfinite(h_prev) && h_prev > 0.0;
+    if (second) {
+      const double r = h_prev / h;
+      c0 = base * (1.0 + 1.0 / (2.0 * r));
+      c1 = -base / (2.0 * r);
+    }
+    coef_out[4 * i + 2] = sg > 0.0 ? (float)(sgp / sg) : 0.f;
+    coef_out[4 * i + 3] = (float)c0;
+    extra_out[i] = (float)c1;
+    h_prev = h;
+  }
+  return 0;
+}
+}  // namespace
+
+int dq_sampler_coef_table(const float* alpha_bars_host, int num_timesteps, const int32_t* timesteps_host, int num_steps, int sampler,
+                          float eta, float* coef_out, float* extra_out) {
+  DQ_REQUIRE(alpha_bars_host && timesteps_host && coef_out && extra_out, "dq_sampler_coef_table: null argument");
+  DQ_REQUIRE(num_timesteps >= 1 && num_steps >= 1, "dq_sampler_coef_table: num_timesteps and num_steps must be >= 1");
+  DQ_REQUIRE(sampler == DQ_SAMPLER_REFERENCE || sampler == DQ_SAMPLER_DDIM || sampler == DQ_SAMPLER_DPMPP_2M,
+             "dq_sampler_coef_table: unknown sampler");
+  DQ_REQUIRE(eta >= 0.f && eta <= 1.f, "dq_sampler_coef_table: eta must satisfy 0 <= eta <= 1");  // (false for NaN)
+  if (sampler == DQ_SAMPLER_REFERENCE) return dq_ddim_coef_table(alpha_bars_host, num_timesteps, timesteps_host, num_steps, eta, coef_out, extra_out);
+  DQ_REQUIRE(sampler != DQ_SAMPLER_DPMPP_2M || eta == 0.f, "dq_sampler_coef_table: DPM-Solver++(2M) is deterministic: eta must be 0");
+  return sampler_rows(alpha_bars_host, num_timesteps, timesteps_host, num_steps, sampler, eta, coef_out, extra_out, "dq_sampler_coef_table");
+}
+
+int dq_solver_step(const float* x_t, const float* net_out, float* x_prev, float* x0_hist, float* eps_out, const float* coef_dev, float clip_x0,
+                   int pred_type, int64_t n, void* stream) {
+  DQ_REQUIRE(x_t && net_out && x_prev && coef_dev, "dq_solver_step: null argument");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_solver_step: Unknown pred_type");
+  return launch_solver_step(x_t, net_out, x_prev, x0_hist, eps_out, coef_dev, coef_dev + 4, clip_x0, pred_type == DQ_PRED_X0, n, nullptr,
+                            (hipStream_t)stream);
+}
+
 int dq_unet_fwd(dq_plan* plan, const float* params, const float* rope_freqs, const float* x, const int64_t* t, int t_scalar,
                 const float* init_cond, const float* attn_cond, float cond_mul, float cond_add, float* out, int save_for_bwd,
                 void* workspace, int64_t workspace_bytes, int B, int RT, void* stream) {
@@ -2067,10 +2146,34 @@ int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freq
                       const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
                       int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
                       const uint64_t* seed_dev, const int64_t* window_ids_dev) {
+  return dq_ddim_sample_solver(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type,
+                               timesteps_host, num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT,
+                               stream, eta, seed_dev, window_ids_dev, DQ_SAMPLER_REFERENCE, 0.f);
+}
+
+int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                      const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                      const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                      int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                      const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0) {
   DQ_REQUIRE(plan && params && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
              "dq_ddim_sample: null argument");
   DQ_REQUIRE(eta >= 0.f && eta <= 1.f, "dq_ddim_sample: eta must satisfy 0 <= eta <= 1");  // (false for NaN)
   const bool sto = eta > 0.f;  // the update draws noise: k_ddim_step_sto behind the forward instead of the update in the head launch
+  // step-consistent samplers: refused here, before anything touches the device
+  DQ_REQUIRE(sampler == DQ_SAMPLER_REFERENCE || sampler == DQ_SAMPLER_DDIM || sampler == DQ_SAMPLER_DPMPP_2M, "dq_ddim_sample: unknown sampler");
+  const bool clip = clip_x0 > 0.f;  // (<= 0 and NaN: off)
+  DQ_REQUIRE(sampler != DQ_SAMPLER_DPMPP_2M || !sto, "dq_ddim_sample: DPM-Solver++(2M) is deterministic: eta must be 0");
+  DQ_REQUIRE(!clip || sampler != DQ_SAMPLER_REFERENCE, "dq_ddim_sample: clip_x0 needs the ddim or dpmpp_2m sampler");
+  DQ_REQUIRE(!clip || !sto, "dq_ddim_sample: clip_x0 needs eta == 0");
+  if (sampler != DQ_SAMPLER_REFERENCE)
+    for (int i = 1; i < num_steps; ++i)
+      DQ_REQUIRE(timesteps_host[i] < timesteps_host[i - 1], "dq_ddim_sample: the timesteps of this sampler must be strictly decreasing");
+  // the update: k_solver_step behind the forward (2M, or a clamped x0 at first order); else the reference's kernels over this sampler's table
+  const bool solver = sampler == DQ_SAMPLER_DPMPP_2M || clip;
+  const bool keep_hist = sampler == DQ_SAMPLER_DPMPP_2M;
+  const int upd = solver ? (keep_hist ? 3 : 2) : (int)sto;
+  if (!clip) clip_x0 = 0.f;
   DQ_REQUIRE(seed_dev || (x_T && !sto), "dq_ddim_sample: eta > 0 and a null x_T need the seed (device memory)");
   DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_ddim_sample: Unknown pred_type");
   const int px0 = pred_type == DQ_PRED_X0;
@@ -2089,9 +2192,10 @@ int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freq
   const int32_t* ts = timesteps_host;  // trunc(linspace(T-1, 0, num_steps)) formed by the caller exactly as model.py:313 does
   // coefficient table (model.py:265-267, 284-286), fp32 like the reference; with eta > 0 also sigma per step (dq_ddim_coef_table)
   std::vector<float> coef(4 * (size_t)num_steps), sigma((size_t)num_steps);
-  DQ_TRY(dq_ddim_coef_table(alpha_bars_host, T, ts, num_steps, eta, coef.data(), sigma.data()));
+  if (sampler == DQ_SAMPLER_REFERENCE) DQ_TRY(dq_ddim_coef_table(alpha_bars_host, T, ts, num_steps, eta, coef.data(), sigma.data()));
+  else DQ_TRY(sampler_rows(alpha_bars_host, T, ts, num_steps, solver && !keep_hist ? SOLVER_ORDER1 : sampler, eta, coef.data(), sigma.data(), "dq_ddim_sample"));
   DQ_HIP_OK(hipMemcpyAsync(c.w(a.coef), coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice, s));
-  if (sto) DQ_HIP_OK(hipMemcpyAsync(c.w(a.sigma), sigma.data(), sizeof(float) * sigma.size(), hipMemcpyHostToDevice, s));
+  if (sto || solver) DQ_HIP_OK(hipMemcpyAsync(c.w(a.sigma), sigma.data(), sizeof(float) * sigma.size(), hipMemcpyHostToDevice, s));
   // the host vector must outlive the copy: pageable H2D copies are staged synchronously by the runtime, but make it explicit
   DQ_HIP_OK(hipStreamSynchronize(s));
   float* xa = c.w(a.xa);
@@ -2136,10 +2240,10 @@ int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freq
     }
     DQ_HIP_OK(hipStreamSynchronize(s));  // ts is caller memory; also keeps the capture below free of pending copies
     DQ_TRY(ms1_prologue(c, c.w(a.c1_stage)));
-    io.x_t = sto ? nullptr : xa; io.x_out = xa; io.step_ptr = step; io.want_eps = false;  // in place: element-wise, read and written by the same lane
+    io.x_t = (sto || solver) ? nullptr : xa; io.x_out = xa; io.step_ptr = step; io.want_eps = false;  // in place: element-wise, read and written by the same lane
     const bool valid = plan->step_exec && plan->g_params == params && plan->g_rope == rope_freqs && plan->g_ws == workspace &&
                        plan->g_B == B && plan->g_RT == RT && plan->g_norm == auto_normalize && plan->g_pred == pred_type &&
-                       plan->g_sto == (int)sto && plan->g_opt_epoch == options_epoch();
+                       plan->g_sto == upd && plan->g_clip == clip_x0 && plan->g_opt_epoch == options_epoch();
     if (!valid) {
       if (plan->step_exec) { (void)hipGraphExecDestroy(plan->step_exec); plan->step_exec = nullptr; }
       if (plan->step_graph) { (void)hipGraphDestroy(plan->step_graph); plan->step_graph = nullptr; }
@@ -2152,7 +2256,9 @@ int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freq
       cc.step_io = &io;
       DQ_HIP_OK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
       int rc = unet_forward(cc, rope_freqs, xa, nullptr, 0, c.w(a.c2_stage), c.w(a.c1_stage), cm, ca, plan->dev, c.w(a.eps), ts_tab, step);
-      if (!rc && sto) rc = launch_ddim_step_sto(xa, c.w(a.eps), xa, nullptr, c.w(a.coef), c.w(a.sigma), ids_st, seed_st, 0, px0, B, per, step, cs);
+      if (!rc && solver)  // history in xb, updated in place; c1 per row rides in the sigma table
+        rc = launch_solver_step(xa, c.w(a.eps), xa, keep_hist ? xb : nullptr, nullptr, c.w(a.coef), c.w(a.sigma), clip_x0, px0, n, step, cs);
+      else if (!rc && sto) rc = launch_ddim_step_sto(xa, c.w(a.eps), xa, nullptr, c.w(a.coef), c.w(a.sigma), ids_st, seed_st, 0, px0, B, per, step, cs);
       else if (!rc && !io.fused_update) rc = launch_ddim_step(xa, c.w(a.eps), xa, c.w(a.coef), n, step, cs, px0, nullptr);  // in place: element-wise
       if (!rc) rc = launch_inc_step(step, cs);
       hipGraph_t g = nullptr;
@@ -2161,7 +2267,7 @@ int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freq
       DQ_HIP_OK(ce);
       plan->step_graph = g;
       DQ_HIP_OK(hipGraphInstantiate(&plan->step_exec, g, nullptr, nullptr, 0));
-      plan->g_params = params; plan->g_rope = rope_freqs; plan->g_ws = workspace; plan->g_B = B; plan->g_RT = RT; plan->g_norm = auto_normalize; plan->g_pred = pred_type; plan->g_sto = (int)sto; plan->g_opt_epoch = options_epoch();
+      plan->g_params = params; plan->g_rope = rope_freqs; plan->g_ws = workspace; plan->g_B = B; plan->g_RT = RT; plan->g_norm = auto_normalize; plan->g_pred = pred_type; plan->g_sto = upd; plan->g_clip = clip_x0; plan->g_opt_epoch = options_epoch();
     }
     for (int i = 0; i < num_steps; ++i) DQ_HIP_OK(hipGraphLaunch(plan->step_exec, s));
     DQ_TRY(launch_sample_finish(xa, ms2_cond, out_x, out_noise, n, auto_normalize, s));
@@ -2172,17 +2278,20 @@ int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freq
   for (int i = 0; i < num_steps; ++i) {
     // eps objective: the network output IS the trajectory's eps; x0 objective: the derived eps goes to the trajectory
     float* eps = traj_eps ? traj_eps + (int64_t)i * n : c.w(a.eps);
-    float* xn = traj_x ? traj_x + (int64_t)i * n : xb;
-    io.x_t = sto ? nullptr : xa; io.x_out = xn; io.coef = c.w(a.coef) + 4 * i; io.step_ptr = nullptr; io.want_eps = traj_eps != nullptr; io.fused_update = false;
+    float* xn = traj_x ? traj_x + (int64_t)i * n : (solver ? xa : xb);  // the solver loop keeps x in xa: xb holds the x0 history
+    io.x_t = (sto || solver) ? nullptr : xa; io.x_out = xn; io.coef = c.w(a.coef) + 4 * i; io.step_ptr = nullptr; io.want_eps = traj_eps != nullptr; io.fused_update = false;
     DQ_TRY(unet_forward(c, rope_freqs, xa, nullptr, ts[i], ms2_cond, ms1_cond, cm, ca, plan->dev, eps));  // model.py:271 / :276
-    if (sto)  // step i draws at index 1 + i
+    if (solver)
+      DQ_TRY(launch_solver_step(xa, eps, xn, keep_hist ? xb : nullptr, (traj_eps && (px0 || clip)) ? traj_eps + (int64_t)i * n : nullptr,
+                                c.w(a.coef) + 4 * i, c.w(a.sigma) + i, clip_x0, px0, n, nullptr, s));
+    else if (sto)  // step i draws at index 1 + i
       DQ_TRY(launch_ddim_step_sto(xa, eps, xn, (traj_eps && px0) ? traj_eps + (int64_t)i * n : nullptr, c.w(a.coef) + 4 * i, c.w(a.sigma) + i,
                                   window_ids_dev, seed_dev, 1 + i, px0, B, per, nullptr, s));
     else if (!io.fused_update)
       DQ_TRY(launch_ddim_step(xa, eps, xn, c.w(a.coef) + 4 * i, n, nullptr, s, px0, (traj_eps && px0) ? traj_eps + (int64_t)i * n : nullptr));  // model.py:273-289
     if (traj_x) {
       DQ_HIP_OK(hipMemcpyAsync(xa, xn, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-    } else {
+    } else if (!solver) {
       std::swap(xa, xb);
     }
   }

@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("DQ_HIP_LIB", os.path.join(os.path.dirname(_HERE), "li
 _lib = None
 ABI_VERSION = 12  # DQ_ABI_VERSION of include/dq_hip.h this table was written against
 PRED_TYPES = {"eps": 0, "x0": 1}  # DQ_PRED_EPS / DQ_PRED_X0
+SAMPLERS = {"reference": 0, "ddim": 1, "dpmpp_2m": 2}  # DQ_SAMPLER_*
 PRECISIONS = {"fp32": 0, "bf16x3": 1}  # DQ_PRECISION_FP32 / DQ_PRECISION_BF16X3
 FINAL_ACTS = {"identity": 0, "softplus": 1}  # DQ_FINAL_IDENTITY / DQ_FINAL_SOFTPLUS
 RES_FWD_FORMS = ("rt", "level", "v4", "unfused")  # DQ_RES_FWD_* (index = value)
@@ -81,6 +82,11 @@ PROTOTYPES = {
     "dq_ddim_sample_ex": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                   POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
                                   c_void_p, c_float, c_void_p, c_void_p]),
+    "dq_sampler_coef_table": (c_int, [POINTER(c_float), c_int, POINTER(c_int32), c_int, c_int, c_float, POINTER(c_float), POINTER(c_float)]),
+    "dq_solver_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int64, c_void_p]),
+    "dq_ddim_sample_solver": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                      POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
+                                      c_void_p, c_float, c_void_p, c_void_p, c_int, c_float]),
     "dq_pair_batch_scratch_bytes": (c_int64, [c_int]),
     "dq_pair_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int64, c_float, c_float, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -272,6 +278,11 @@ def gemm_plan(M: int, N: int, K: int, batch: int = 1, kbatch: int = 1, splits: i
     nf = len(GEMM_PLAN_PART_FIELDS)
     return {"bm": int(buf[0]), "kv": int(buf[1]), "full": dict(zip(GEMM_PLAN_PART_FIELDS, (int(x) for x in buf[2:2 + nf]))),
             "rest": dict(zip(GEMM_PLAN_PART_FIELDS, (int(x) for x in buf[2 + nf:2 + 2 * nf]))), "scratch": int(scratch.value)}
+
+
+def last_error():
+    msg = lib().dq_last_error()
+    return msg.decode() if msg else "?"
 
 
 def check(rc, what):

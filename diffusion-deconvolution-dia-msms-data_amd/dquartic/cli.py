@@ -173,11 +173,14 @@ def enable_ema_from_config(dm, m) -> bool:
 @click.option("--checkpoint", required=True, type=click.Path(exists=True), help="Checkpoint written by train (model_state_dict; its EMA when it has one)")
 @click.option("--num-steps", default=None, type=int, help="Also sample every window with this many DDIM steps and report reconstruction metrics")
 @click.option("--eta", default=0.0, type=float, help="DDIM eta of that sampling (0: deterministic update, 1: ancestral)")
+@click.option("--sampler", default="reference", type=click.Choice(["reference", "ddim", "dpmpp_2m"]),
+              help="Update of that sampling: the reference's, strided DDIM, or DPM-Solver++(2M)")
+@click.option("--clip-x0", default=None, type=float, help="Clamp every step's x0 estimate to [-C, C] (ddim / dpmpp_2m, eta 0)")
 @click.option("--seed", default=0, type=int, help="Seed of the evaluation noise and of the sampling")
 @click.option("--use-ema/--no-use-ema", default=None, help="Evaluate the averaged weights (default: when the checkpoint has an average)")
 @click.option("--max-batches", default=None, type=int, help="Stop after this many batches")
 @click.option("--out", "out_path", default=None, type=click.Path(), help="Write the full result, per-window metrics included, as JSON")
-def evaluate(config_path, checkpoint, num_steps, eta, seed, use_ema, max_batches, out_path):
+def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, seed, use_ema, max_batches, out_path):
     """Held-out loss (and, with --num-steps, reconstruction metrics) of a checkpoint on the config's data.validation set.  The pairs of
     that set come from the block's own seed, not from --seed: runs that differ in --seed, --eta, --num-steps or --use-ema score the same
     pairs.  Without a validation block the config's data section is scored, with a notice.  Prints one JSON line."""
@@ -202,7 +205,8 @@ def evaluate(config_path, checkpoint, num_steps, eta, seed, use_ema, max_batches
         dm.optimizer.load_ema_state_dict(ck["ema_state_dict"])
     elif use_ema:
         raise click.ClickException(f"--use-ema: {checkpoint} holds no averaged weights")
-    res = dm.evaluate(loader, n_t=4, seed=seed, num_steps=num_steps, eta=eta, use_ema=use_ema, max_batches=max_batches)
+    res = dm.evaluate(loader, n_t=4, seed=seed, num_steps=num_steps, eta=eta, use_ema=use_ema, max_batches=max_batches, sampler=sampler,
+                      clip_x0=clip_x0)
     per_window = res.pop("per_window", None)
     click.echo(json.dumps(res))
     if out_path is not None:

@@ -169,6 +169,43 @@ class DDIMDiffusionModel(ModelInterface):
                 "dq_ddim_coef_table")
         return torch.tensor(list(coef), dtype=torch.float32).reshape(-1, 4), torch.tensor(list(sigma), dtype=torch.float32)
 
+    # ------------------------------------------------------------------ step-consistent samplers
+    @staticmethod
+    def _check_sampler(sampler, eta, clip_x0):
+        """(sampler id, clip value or 0.0).  Raises ValueError for an unknown name and for the combinations no kernel runs."""
+        if sampler not in N.SAMPLERS:
+            raise ValueError(f"Unknown sampler: {sampler!r} (one of {sorted(N.SAMPLERS)})")
+        clip = 0.0 if clip_x0 is None else float(clip_x0)
+        if clip_x0 is not None and not clip > 0.0:  # (NaN fails the comparison)
+            raise ValueError(f"clip_x0 must be > 0 or None, got {clip_x0!r}")
+        if sampler == "dpmpp_2m" and eta > 0.0:
+            raise ValueError("sampler 'dpmpp_2m' is deterministic: eta must be 0")
+        if clip > 0.0 and sampler == "reference":
+            raise ValueError("clip_x0 needs sampler 'ddim' or 'dpmpp_2m'")
+        if clip > 0.0 and eta > 0.0:
+            raise ValueError("clip_x0 needs eta == 0")
+        return N.SAMPLERS[sampler], clip
+
+    @staticmethod
+    def _check_decreasing(ts):
+        if any(b >= a for a, b in zip(ts[:-1], ts[1:])):
+            raise ValueError("the timesteps of the 'ddim' and 'dpmpp_2m' samplers must be strictly decreasing (num_steps <= num_timesteps)")
+
+    def sampler_coef_table(self, timesteps, sampler="reference", eta=0.0):
+        """``dq_sampler_coef_table`` (host only): two float32 CPU tensors (num_steps, 4) and (num_steps,).  'reference': what
+        ``ddim_coef_table`` returns; 'ddim': the same rows landing on ``alpha_bars[timesteps[i + 1]]`` and sigma; 'dpmpp_2m': rows
+        [sa, sb, cx, c0] and c1 of ``x_prev = cx x + c0 x0 + c1 x0_hist``.  The last row returns x0."""
+        if sampler not in N.SAMPLERS:
+            raise ValueError(f"Unknown sampler: {sampler!r} (one of {sorted(N.SAMPLERS)})")
+        ts = [int(v) for v in timesteps]
+        ts_c = (ctypes.c_int32 * len(ts))(*ts)
+        coef, extra = (ctypes.c_float * (4 * len(ts)))(), (ctypes.c_float * len(ts))()
+        rc = N.lib().dq_sampler_coef_table(self._alpha_bars_host(), int(self.num_timesteps), ts_c, len(ts), N.SAMPLERS[sampler], float(eta),
+                                           coef, extra)
+        if rc:
+            raise ValueError(N.last_error())
+        return torch.tensor(list(coef), dtype=torch.float32).reshape(-1, 4), torch.tensor(list(extra), dtype=torch.float32)
+
     # ------------------------------------------------------------------ reverse process
     def p_sample(self, x_t, t, init_cond=None, attn_cond=None, eta=0.0, seed=None, window_ids=None, draw=None):
         """model.py:244-291.  ``t`` is a python int; conditions are already normalised.  ``eta > 0`` (device tensors, no autograd through
@@ -227,16 +264,29 @@ class DDIMDiffusionModel(ModelInterface):
         return x_prev, eps_pred
 
     def sample(self, x_t, ms2_cond=None, ms1_cond=None, num_steps=1000, return_trajectory=False, eta=0.0, seed=None, window_ids=None,
-               shape=None):
+               shape=None, sampler="reference", clip_x0=None):
         """model.py:293-324: returns (denoised, mixture - denoised).  Native loop when the network is UNet1d.
 
         ``eta`` in [0, 1]: 0 is the deterministic DDIM update, 1 ancestral (DDPM-like) sampling; the per-step noise
         is a counter-based generator inside the update kernel, keyed by (``seed``, window id, element, step), so a window's result does
         not depend on its place in the batch.  ``seed``: a 64-bit int (None with ``eta > 0``: drawn once from torch's generator);
         ``window_ids``: one int64 id per window (None: 0 .. B-1).  ``x_t=None`` draws x_T from the same generator (needs ``seed``); the
-        shape is ``shape`` or ``ms2_cond``'s.  Native path only.  The defaults are the call as it always was."""
+        shape is ``shape`` or ``ms2_cond``'s.  Native path only.  The defaults are the call as it always was.
+
+        ``sampler``: "reference" lands every step on ``alpha_bars[t - 1]`` as the reference does (exact only at
+        ``num_steps == num_timesteps``); "ddim" lands step i on the list's next timestep; "dpmpp_2m" is DPM-Solver++(2M) over the same
+        list (``eta`` must be 0).  The last step of either returns the x0 estimate.  ``clip_x0 = c > 0`` (those two samplers, ``eta == 0``)
+        clamps every step's x0 estimate to [-c, c].  Native path only."""
         eta = self._check_eta(eta)
+        sampler_id, clip = self._check_sampler(sampler, eta, clip_x0)
         stochastic = eta > 0.0 or x_t is None or seed is not None or window_ids is not None
+        if sampler_id != 0:
+            self._check_decreasing(self.sampler_timesteps(self.num_timesteps, num_steps).tolist())
+            if not (self.native and ms2_cond is not None and ms1_cond is not None and (x_t.is_cuda if x_t is not None else ms2_cond.is_cuda)):
+                raise NotImplementedError("sample: the 'ddim' and 'dpmpp_2m' samplers and clip_x0 need the native sampler (this package's "
+                                          "UNet1d on the GPU with both conditions); the generic loop is the reference update only")
+            return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
+                                       shape=shape, sampler=sampler_id, clip_x0=clip)
         if self.native and ms2_cond is not None and ms1_cond is not None and (x_t.is_cuda if x_t is not None else ms2_cond.is_cuda):
             if not stochastic:
                 return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory)
@@ -255,8 +305,10 @@ class DDIMDiffusionModel(ModelInterface):
             pred_noise = self.unnormalize(ms2n) - x_t
         return x_t, pred_noise
 
-    def _sample_native(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False, eta=None, seed=None, window_ids=None, shape=None):
-        """``eta`` None: ``dq_ddim_sample`` (the call as it always was); else ``dq_ddim_sample_ex``."""
+    def _sample_native(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False, eta=None, seed=None, window_ids=None, shape=None,
+                       sampler=0, clip_x0=0.0):
+        """``eta`` None: ``dq_ddim_sample`` (the call as it always was); else ``dq_ddim_sample_ex``; ``sampler`` != 0:
+        ``dq_ddim_sample_solver``."""
         net: UNet1d = self.model
         f32 = lambda v: v.detach().to(torch.float32).contiguous()
         if x_T is None:
@@ -279,6 +331,16 @@ class DDIMDiffusionModel(ModelInterface):
             seed_dev = self._seed_tensor(seed, c2.device) if (seed is not None or eta > 0.0 or x_T is None) else None
             ids_dev = self._ids_tensor(window_ids, B, c2.device)
             self.last_seed = None if seed_dev is None else int(seed_dev.item()) & (2 ** 64 - 1)  # (what a seed=None call drew)
+            if sampler:
+                N.check(N.lib().dq_ddim_sample_solver(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), self._alpha_bars_host(),
+                                                      int(self.num_timesteps), N.ptr(x_T), N.ptr(c2), N.ptr(c1), 1 if self.auto_normalize else 0,
+                                                      N.PRED_TYPES[self.pred_type], ts_c, num_steps, N.ptr(out_x), N.ptr(out_n), N.ptr(traj_x),
+                                                      N.ptr(traj_e), 1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws),
+                                                      ws.numel(), B, RT, N.stream_ptr(), float(eta), N.ptr(seed_dev), N.ptr(ids_dev),
+                                                      int(sampler), float(clip_x0)), "dq_ddim_sample_solver")
+                if return_trajectory:
+                    return out_x, out_n, traj_x, traj_e
+                return out_x, out_n
             N.check(N.lib().dq_ddim_sample_ex(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), self._alpha_bars_host(), int(self.num_timesteps),
                                               N.ptr(x_T), N.ptr(c2), N.ptr(c1), 1 if self.auto_normalize else 0,
                                               N.PRED_TYPES[self.pred_type], ts_c, num_steps, N.ptr(out_x), N.ptr(out_n), N.ptr(traj_x),

@@ -634,7 +634,8 @@ class ModelInterface(object):
         use = self.ema_enabled if use_ema is None else bool(use_ema)
         return self.ema_scope() if use else contextlib.nullcontext()
 
-    def predict(self, dataloader, mixture_weights=(0.5, 0.5), num_steps=1000, use_ema=None, eta=0.0, seed=None, n_draws=1):
+    def predict(self, dataloader, mixture_weights=(0.5, 0.5), num_steps=1000, use_ema=None, eta=0.0, seed=None, n_draws=1,
+                sampler="reference", clip_x0=None):
         """Reference :630-668: one dict per batch with the first item's prediction (``_predict_one_batch`` returns item 0).
         ``use_ema``: sample from the averaged weights; None (default) = when EMA is enabled.
 
@@ -643,7 +644,9 @@ class ModelInterface(object):
         ``seed`` (None: drawn once from torch's generator), and the window id of item b of batch k is its running index in the dataloader
         -- a window's prediction does not depend on the batch size.  Draw j (0-based) samples under ``seed + j``, so it is what
         ``n_draws=1, seed=seed + j`` returns.  ``n_draws > 1`` adds ``"pred_mean"`` and ``"pred_std"`` (per element, over the draws,
-        population form) to each dict; ``"pred"`` stays draw 0.  With ``n_draws == 1`` those two keys are absent."""
+        population form) to each dict; ``"pred"`` stays draw 0.  With ``n_draws == 1`` those two keys are absent.
+
+        ``sampler`` / ``clip_x0``: passed to ``sample``; with the defaults nothing else changes."""
         self.model.eval()
         n_draws = int(n_draws)
         if n_draws < 1:
@@ -658,11 +661,12 @@ class ModelInterface(object):
             ms2_cond = (ms2_1 * mixture_weights[0]).to(self.device) + (ms2_2 * mixture_weights[1]).to(self.device)
             d = {"ms2_1": ms2_1.cpu().numpy(), "ms1_1": ms1_1.cpu().numpy(), "mixture": ms2_cond.cpu().numpy()}
             if not stochastic:
-                d["pred"], _ = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, use_ema=use_ema)
+                d["pred"], _ = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, use_ema=use_ema,
+                                                       **_sampler_kwargs(sampler, clip_x0))
             else:
                 ids = torch.arange(first, first + x_0.shape[0], dtype=torch.int64)
                 out = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, use_ema=use_ema, eta=eta,
-                                              seed=seed, n_draws=n_draws, window_ids=ids)
+                                              seed=seed, n_draws=n_draws, window_ids=ids, **_sampler_kwargs(sampler, clip_x0))
                 d["pred"] = out[0]
                 if n_draws > 1:
                     d["pred_mean"], d["pred_std"] = out[2], out[3]
@@ -670,7 +674,8 @@ class ModelInterface(object):
             preds.append(d)
         return np.array(preds, dtype=object)
 
-    def evaluate(self, dataloader, mixture_weights=(0.5, 0.5), n_t=4, seed=0, num_steps=None, eta=0.0, use_ema=None, max_batches=None):
+    def evaluate(self, dataloader, mixture_weights=(0.5, 0.5), n_t=4, seed=0, num_steps=None, eta=0.0, use_ema=None, max_batches=None,
+                 sampler="reference", clip_x0=None):
         """Held-out evaluation (new work: the reference has none).  Returns a dict.
 
         Loss: every window of the loader is evaluated ``n_t`` times by ``eval_step`` -- repeat k at the timestep
@@ -684,7 +689,8 @@ class ModelInterface(object):
         ``num_steps`` (None: loss only): every window is also sampled, ``sample(None, ..., num_steps, eta=eta, seed=seed,
         window_ids=ids)``, and ``dq_recon_metrics(sample, x_0)`` gives nine numbers per window (``_native.METRIC_NAMES``): the dict gains
         their means over the windows (``scan_sa`` / ``xic_r`` weighted by ``scan_count`` / ``xic_count``) under those names and the
-        ``(n_windows, 9)`` float32 array as ``per_window``.
+        ``(n_windows, 9)`` float32 array as ``per_window``.  ``sampler`` / ``clip_x0`` go to that ``sample`` call
+        and appear in the dict only when they are not the defaults.
 
         ``use_ema`` as in ``predict``; ``max_batches``: stop after that many batches.  Under ``torch.distributed`` each rank evaluates
         its own loader and the scalars are averaged over the ranks (``_global_mean``); ``per_window`` and ``n_windows`` stay the rank's."""
@@ -719,7 +725,7 @@ class ModelInterface(object):
                         ts[k].append(t)
                     if num_steps is not None:
                         sample, _ = self.sample(None, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=int(num_steps), eta=eta, seed=int(seed),
-                                                window_ids=ids_dev, shape=tuple(x_0.shape))
+                                                window_ids=ids_dev, shape=tuple(x_0.shape), **_sampler_kwargs(sampler, clip_x0))
                         rows.append(E.recon_metrics(sample, x_0))
                     first += x_0.shape[0]
         finally:
@@ -736,6 +742,10 @@ class ModelInterface(object):
             per_window = torch.cat(rows).cpu().numpy()
             out.update({k: self._global_mean(v) for k, v in E.aggregate_metrics(per_window).items()})
             out.update(num_steps=int(num_steps), eta=float(eta), per_window=per_window)
+            if sampler != "reference":
+                out["sampler"] = str(sampler)
+            if clip_x0 is not None:
+                out["clip_x0"] = float(clip_x0)
         return out
 
     # ---- internals
@@ -850,7 +860,7 @@ class ModelInterface(object):
         return loss.item() if sync else loss.detach()
 
     def _predict_one_batch(self, x_0, ms2_cond=None, ms1_cond=None, num_steps=1000, use_ema=None, eta=0.0, seed=None, n_draws=1,
-                           window_ids=None):
+                           window_ids=None, sampler="reference", clip_x0=None):
         """Reference :1125-1150: eval + no_grad + sample(randn_like(x_0)); returns item 0 of the batch as numpy.  ``use_ema`` as in
         ``predict``.  With ``eta > 0``, a ``seed`` or ``n_draws > 1`` (see ``predict``): x_T and the step noise from the sampler's
         generator, draw j under ``seed + j``; ``n_draws > 1`` returns (sample, pred_noise, mean, std) of item 0, sample / pred_noise
@@ -858,7 +868,8 @@ class ModelInterface(object):
         self.model.eval()
         if not (float(eta) > 0.0 or seed is not None or int(n_draws) > 1):
             with torch.no_grad(), self._ema_or_null_scope(use_ema):
-                sample, pred_noise = self.sample(torch.randn_like(x_0), ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps)
+                sample, pred_noise = self.sample(torch.randn_like(x_0), ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps,
+                                                 **_sampler_kwargs(sampler, clip_x0))
             return sample[0].cpu().detach().numpy(), pred_noise[0].cpu().detach().numpy()
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
@@ -866,7 +877,7 @@ class ModelInterface(object):
         with torch.no_grad(), self._ema_or_null_scope(use_ema):
             for j in range(int(n_draws)):
                 draws.append(self.sample(None, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, eta=eta, seed=int(seed) + j,
-                                         window_ids=window_ids, shape=tuple(x_0.shape)))
+                                         window_ids=window_ids, shape=tuple(x_0.shape), **_sampler_kwargs(sampler, clip_x0)))
         first = (draws[0][0][0].cpu().numpy(), draws[0][1][0].cpu().numpy())
         if int(n_draws) == 1:
             return first
@@ -877,6 +888,17 @@ class ModelInterface(object):
         raise NotImplementedError("wandb prediction tables / pyopenms_viz plots are outside the hot path (SURVEY section 2)")
 
     plot_single_prediction = log_single_prediction
+
+
+def _sampler_kwargs(sampler, clip_x0):
+    """The two step-consistent-sampler options as keyword arguments of ``sample`` -- none at the defaults, so that a subclass whose
+    ``sample`` predates them is still called as it always was."""
+    kw = {}
+    if sampler != "reference":
+        kw["sampler"] = sampler
+    if clip_x0 is not None:
+        kw["clip_x0"] = clip_x0
+    return kw
 
 
 def _wandb():

@@ -49,7 +49,7 @@ const char* dq_last_error(void);
  * dq_plan_attn_cond_channels, dq_ms1_feat_fwd, dq_ms1_feat_wgrad, dq_ms1_feat_wgrad_scratch_floats).  11: dq_conv_bwd,
  * dq_conv_bwd_workspace_floats, dq_conv_bwd_forms (later, additive: dq_adamw_clip_ema_step, dq_adamw_clip_ema_step_dev; dq_randn,
  * dq_ddim_step_sto, dq_ddim_coef_table, dq_ddim_sample_ex).  12: dq_debug_level_plan (later, additive: dq_gemm_ex,
- * dq_debug_gemm_plan). */
+ * dq_debug_gemm_plan; DQ_SAMPLER_*, dq_sampler_coef_table, dq_solver_step, dq_ddim_sample_solver). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -299,6 +299,43 @@ int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freq
                       const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
                       int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
                       const uint64_t* seed_dev, const int64_t* window_ids_dev);
+
+/* ---- step-consistent sampling (no reference counterpart) ------------------------------------
+ * The reference's update at timestep t lands on alpha_bars[t-1] while the next step relabels the state as the next entry of the strided
+ * list: exact only at num_steps == num_timesteps.  The samplers below land step i of the list ts[0..n-1] on alpha_bars[ts[i+1]];
+ * the last step of the list returns the x0 estimate, whatever its t.  Their lists must be strictly decreasing.
+ *   DQ_SAMPLER_REFERENCE  the update as it always was (dq_ddim_coef_table)
+ *   DQ_SAMPLER_DDIM       the same update with abp = alpha_bars[ts[i+1]] (any eta in [0, 1])
+ *   DQ_SAMPLER_DPMPP_2M   DPM-Solver++(2M) (Lu et al. 2022; data prediction, multistep, first order on the first step; eta == 0):
+ *                         x_prev = cx x + c0 x0 + c1 x0_hist, with a = sqrt(ab), s = sqrt(1-ab), lambda = log(a / s), h = lambda_{i+1} - lambda_i,
+ *                         r = h_{i-1} / h_i:  cx = s_{i+1} / s_i,  c0 = a_{i+1} (1 - e^-h) (1 + 1/(2r)),  c1 = -a_{i+1} (1 - e^-h) / (2r);
+ *                         first step: c0 = a_{i+1} (1 - e^-h), c1 = 0 (the strided DDIM step); last row: cx = -1 (x_prev = x0).
+ *                         Formed in double from the fp32 table values (expm1), rounded to fp32 once. */
+enum { DQ_SAMPLER_REFERENCE = 0, DQ_SAMPLER_DDIM = 1, DQ_SAMPLER_DPMPP_2M = 2 };
+/* The samplers' coefficient rows (host only, no GPU call).  Sampler 0: dq_ddim_coef_table's output exactly (extra_out = sigma).  Sampler 1:
+ * rows [sqrt(ab), sqrt(1-ab), sqrt(abp), c] and extra_out = sigma with dq_ddim_coef_table's expressions at abp = alpha_bars[ts[i+1]]; last
+ * row [.., -1, 0].  Sampler 2: rows [sa, sb, cx, c0], extra_out = c1.  Non-zero (dq_last_error): timesteps that do not strictly decrease
+ * (samplers 1, 2), eta != 0 with sampler 2, eta outside [0, 1], an unknown sampler. */
+int dq_sampler_coef_table(const float* alpha_bars_host, int num_timesteps, const int32_t* timesteps_host, int num_steps, int sampler,
+                          float eta, float* coef_out, float* extra_out);
+/* One solver update on caller-supplied tensors (k_solver.hip).  coef_dev: 5 device floats [sa, sb, cx, c0, c1].  x0 = net_out (DQ_PRED_X0)
+ * or (x_t - sb net_out) / sa (DQ_PRED_EPS); clip_x0 > 0: x0 clamped to [-clip_x0, clip_x0] first; x_prev = (cx x_t + c0 x0) + c1 x0_hist,
+ * or x0 when cx < 0.  x0_hist (nullable only when c1 == 0; not read when c1 == 0) receives x0.  eps_out (nullable): (x_t - sa x0) / sb under
+ * DQ_PRED_X0 and for a clamped element, else net_out.  x_prev may alias x_t and eps_out net_out.  Any n; tensors 4-byte aligned (16-byte
+ * accesses when n % 4 == 0 and all are 16-byte aligned). */
+int dq_solver_step(const float* x_t, const float* net_out, float* x_prev, float* x0_hist, float* eps_out, const float* coef_dev, float clip_x0,
+                   int pred_type, int64_t n, void* stream);
+/* dq_ddim_sample_ex with a sampler and the clamp: (DQ_SAMPLER_REFERENCE, clip_x0 <= 0) is dq_ddim_sample_ex, call for call.
+ * DQ_SAMPLER_DDIM with clip off runs the reference's kernels and captured graph over the strided table (eta > 0: dq_ddim_step_sto).
+ * DQ_SAMPLER_DPMPP_2M, and DQ_SAMPLER_DDIM with clip_x0 > 0 (first-order rows), run dq_solver_step behind the forward (one more launch per
+ * step), x in place and the x0 history in the workspace.  Refused before any device call: eta > 0 with DQ_SAMPLER_DPMPP_2M or with
+ * clip_x0 > 0, clip_x0 > 0 with DQ_SAMPLER_REFERENCE, timesteps that do not strictly decrease (samplers 1, 2).  Captured steps are cached
+ * by update kind and clip value. */
+int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                          const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                          const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                          int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                          const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0);
 
 /* ---- batch formation from an HBM-resident dataset (the step right before the hot path) ------------
  * Replaces, for B (window 1, window 2) pairs, DIAMSDataset.__getitem__'s min-max normalisation (utils/data_loader.py:70-79:
