@@ -4,10 +4,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include "dq_error.h"  // set_error, DQ_REQUIRE
 
 namespace dq {
-
-void set_error(const std::string& msg);
 
 #define DQ_HIP_OK(expr)                                                                            \
   do {                                                                                             \
@@ -26,14 +25,6 @@ void set_error(const std::string& msg);
       dq::set_error(std::string("kernel launch failed: ") + hipGetErrorString(_e) + " (" + __FILE__ + ":" + \
                     std::to_string(__LINE__) + ")");                                               \
       return 1;                                                                                    \
-    }                                                                                              \
-  } while (0)
-
-#define DQ_REQUIRE(cond, msg)                                                                      \
-  do {                                                                                             \
-    if (!(cond)) {                                                                                 \
-      dq::set_error(std::string(msg) + " [" #cond "] (" + __FILE__ + ":" + std::to_string(__LINE__) + ")"); \
-      return 2;                                                                                    \
     }                                                                                              \
   } while (0)
 

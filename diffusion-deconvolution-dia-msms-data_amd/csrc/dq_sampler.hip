@@ -1,0 +1,232 @@
+// The sampling entry points of the C ABI (include/dq_hip.h): the stand-alone updates, and the sampling loop with its captured step -- the
+// network forward of dq_unet.hip (dq_net.h) with one of four updates in or behind its head launch, over the tables of dq_sampler_tables.cpp.
+#include "dq_net.h"
+#include "dq_options.h"
+#include "dq_sampler_tables.h"
+#include "../../include/dq_hip.h"
+
+#include <utility>
+#include <vector>
+
+using namespace dq;
+
+namespace {
+
+// What every step's update of one sampling call shares: the tables (extra: sigma per row, or the solver's c1), the x0 history of the 2M
+// solver (updated in place), the clamp (0: off) and the shape
+struct StepUpdateArgs {
+  StepUpdate kind;
+  const float* coef; const float* extra;
+  float* hist;
+  float clip;
+  int px0, B;
+  int64_t per;
+};
+
+// The noise of the stochastic update: the windows' ids and the seed (device memory) and the draw index (the kernel adds the step counter)
+struct StepNoise { const int64_t* ids; const uint64_t* seed; int draw; };
+
+// The update of one step behind the network forward: x_out from x and the network output.  The row is `row` of the tables (the eager loop)
+// or, with step_ptr, the one the device-side step counter names (the captured step: row 0).  eps_out (nullable): where the step's eps goes
+// when it is not the network output itself; fused: the deterministic update went with the head launch (StepIO::fused_update), nothing is
+// left to do.
+int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net_out, float* x_out, float* eps_out, int row, const int* step_ptr,
+                       const StepNoise& z, bool fused, hipStream_t s) {
+  const float* coef = u.coef + 4 * row;
+  const float* extra = u.extra + row;
+  const int64_t n = u.B * u.per;
+  switch (u.kind) {
+    case StepUpdate::SOLVER_1:
+    case StepUpdate::SOLVER_2M:
+      return launch_solver_step(x, net_out, x_out, u.kind == StepUpdate::SOLVER_2M ? u.hist : nullptr, eps_out, coef, extra, u.clip, u.px0, n, step_ptr, s);
+    case StepUpdate::STOCHASTIC:
+      return launch_ddim_step_sto(x, net_out, x_out, eps_out, coef, extra, z.ids, z.seed, z.draw, u.px0, u.B, u.per, step_ptr, s);
+    case StepUpdate::DDIM:
+      return fused ? 0 : launch_ddim_step(x, net_out, x_out, coef, n, step_ptr, s, u.px0, eps_out);  // model.py:273-289
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dq_ddim_step(const float* x_t, const float* eps, float* x_prev, const float* coef_dev, int64_t n, void* stream) {
+  return launch_ddim_step(x_t, eps, x_prev, coef_dev, n, nullptr, (hipStream_t)stream);
+}
+
+int dq_ddim_step_x0(const float* x_t, const float* x0_pred, float* x_prev, float* eps_out, const float* coef_dev, int64_t n,
+                    void* stream) {
+  DQ_REQUIRE(x_t && x0_pred && x_prev && coef_dev, "dq_ddim_step_x0: null argument");
+  return launch_ddim_step(x_t, x0_pred, x_prev, coef_dev, n, nullptr, (hipStream_t)stream, 1, eps_out);
+}
+
+int dq_randn(float* out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int B, int64_t per_window, void* stream) {
+  return launch_randn(out, window_ids_dev, seed_dev, draw, B, per_window, (hipStream_t)stream);
+}
+
+int dq_ddim_step_sto(const float* x_t, const float* net_out, float* x_prev, float* eps_out, const float* coef_dev,
+                     const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window,
+                     void* stream) {
+  DQ_REQUIRE(x_t && net_out && x_prev && coef_dev && seed_dev, "dq_ddim_step_sto: null argument");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_ddim_step_sto: Unknown pred_type");
+  return launch_ddim_step_sto(x_t, net_out, x_prev, pred_type == DQ_PRED_X0 ? eps_out : nullptr, coef_dev, coef_dev + 4, window_ids_dev,
+                              seed_dev, draw, pred_type == DQ_PRED_X0, B, per_window, nullptr, (hipStream_t)stream);
+}
+
+int dq_solver_step(const float* x_t, const float* net_out, float* x_prev, float* x0_hist, float* eps_out, const float* coef_dev, float clip_x0,
+                   int pred_type, int64_t n, void* stream) {
+  DQ_REQUIRE(x_t && net_out && x_prev && coef_dev, "dq_solver_step: null argument");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_solver_step: Unknown pred_type");
+  return launch_solver_step(x_t, net_out, x_prev, x0_hist, eps_out, coef_dev, coef_dev + 4, clip_x0, pred_type == DQ_PRED_X0, n, nullptr,
+                            (hipStream_t)stream);
+}
+
+int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                   const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                   const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                   int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream) {
+  DQ_REQUIRE(x_T, "dq_ddim_sample: null argument");
+  return dq_ddim_sample_ex(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type,
+                           timesteps_host, num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream,
+                           0.f, nullptr, nullptr);
+}
+
+int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                      const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                      const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                      int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                      const uint64_t* seed_dev, const int64_t* window_ids_dev) {
+  return dq_ddim_sample_solver(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type,
+                               timesteps_host, num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT,
+                               stream, eta, seed_dev, window_ids_dev, DQ_SAMPLER_REFERENCE, 0.f);
+}
+
+int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                      const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                      const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                      int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                      const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0) {
+  DQ_REQUIRE(plan && params && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
+             "dq_ddim_sample: null argument");
+  DQ_REQUIRE(eta >= 0.f && eta <= 1.f, "dq_ddim_sample: eta must satisfy 0 <= eta <= 1");  // (false for NaN)
+  const bool sto = eta > 0.f;  // the update draws noise
+  // step-consistent samplers: refused here, before anything touches the device
+  DQ_REQUIRE(sampler == DQ_SAMPLER_REFERENCE || sampler == DQ_SAMPLER_DDIM || sampler == DQ_SAMPLER_DPMPP_2M, "dq_ddim_sample: unknown sampler");
+  const bool clip = clip_x0 > 0.f;  // (<= 0 and NaN: off)
+  DQ_REQUIRE(sampler != DQ_SAMPLER_DPMPP_2M || !sto, "dq_ddim_sample: DPM-Solver++(2M) is deterministic: eta must be 0");
+  DQ_REQUIRE(!clip || sampler != DQ_SAMPLER_REFERENCE, "dq_ddim_sample: clip_x0 needs the ddim or dpmpp_2m sampler");
+  DQ_REQUIRE(!clip || !sto, "dq_ddim_sample: clip_x0 needs eta == 0");
+  if (sampler != DQ_SAMPLER_REFERENCE)
+    for (int i = 1; i < num_steps; ++i)
+      DQ_REQUIRE(timesteps_host[i] < timesteps_host[i - 1], "dq_ddim_sample: the timesteps of this sampler must be strictly decreasing");
+  // the update: k_solver_step behind the forward (2M, or a clamped x0 at first order); else the reference's kernels over this sampler's table
+  const StepUpdate kind = sampler == DQ_SAMPLER_DPMPP_2M ? StepUpdate::SOLVER_2M : clip ? StepUpdate::SOLVER_1 : sto ? StepUpdate::STOCHASTIC : StepUpdate::DDIM;
+  const bool in_head = kind == StepUpdate::DDIM;  // the head launch takes the update when it can (StepIO::x_t); the others run behind the forward
+  const bool in_place = kind == StepUpdate::SOLVER_1 || kind == StepUpdate::SOLVER_2M;  // the solver loop keeps x in xa: xb holds the x0 history
+  if (!clip) clip_x0 = 0.f;
+  DQ_REQUIRE(seed_dev || (x_T && !sto), "dq_ddim_sample: eta > 0 and a null x_T need the seed (device memory)");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_ddim_sample: Unknown pred_type");
+  const int px0 = pred_type == DQ_PRED_X0;
+  DQ_REQUIRE(B > 0 && RT > 0 && num_steps >= 1 && num_steps <= 1024, "dq_ddim_sample: need B, RT > 0 and 1 <= num_steps <= 1024");
+  DQ_TRY(ensure_arena(plan, B, RT));
+  const Arena& a = plan->arena;
+  DQ_REQUIRE(workspace_bytes >= (int64_t)sizeof(float) * a.floats, "dq_ddim_sample: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  float* W = (float*)workspace;
+  Ctx c{plan->plan, a, params, W, nullptr, nullptr, B, RT, s};
+  c.save = false;
+  const int T = num_timesteps;  // length of alpha_bars_host (DDIMDiffusionModel.num_timesteps: the schedule is the caller's)
+  DQ_REQUIRE(T >= 1, "dq_ddim_sample: num_timesteps must be >= 1");
+  const int64_t per = (int64_t)RT * plan->plan.mz, n = B * per;
+  const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
+  const int32_t* ts = timesteps_host;  // trunc(linspace(T-1, 0, num_steps)) formed by the caller exactly as model.py:313 does
+  // coefficient table, fp32 like the reference, and sigma (eta > 0) or c1 (the solver) per step
+  std::vector<float> coef(4 * (size_t)num_steps), extra((size_t)num_steps);
+  if (sampler == DQ_SAMPLER_REFERENCE) DQ_TRY(dq_ddim_coef_table(alpha_bars_host, T, ts, num_steps, eta, coef.data(), extra.data()));
+  else DQ_TRY(sampler_rows(alpha_bars_host, T, ts, num_steps, kind == StepUpdate::SOLVER_1 ? SOLVER_ORDER1 : sampler, eta, coef.data(), extra.data(), "dq_ddim_sample"));
+  DQ_HIP_OK(hipMemcpyAsync(c.w(a.coef), coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice, s));
+  if (!in_head) DQ_HIP_OK(hipMemcpyAsync(c.w(a.sigma), extra.data(), sizeof(float) * extra.size(), hipMemcpyHostToDevice, s));
+  // the host vector must outlive the copy: pageable H2D copies are staged synchronously by the runtime, but make it explicit
+  DQ_HIP_OK(hipStreamSynchronize(s));
+  float* xa = c.w(a.xa);
+  float* xb = c.w(a.xb);
+  if (x_T) DQ_HIP_OK(hipMemcpyAsync(xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  else DQ_TRY(launch_randn(xa, window_ids_dev, seed_dev, 0, B, per, s));  // draw index 0 is x_T's
+  const StepUpdateArgs upd{kind, c.w(a.coef), c.w(a.sigma), xb, clip_x0, px0, B, per};
+  Ctx::StepIO io;
+  io.pred_x0 = px0; io.coef = c.w(a.coef);
+  if (use_graph && !traj_x && !traj_eps) {
+    // ---- hipGraph path: one step captured once (all pointers inside the arena / parameter buffers), replayed per step.
+    // The step index lives on the device: k_time_fwd reads ts_tab[*step], the update its coefficient row, k_inc_step bumps it.
+    int* ts_tab = reinterpret_cast<int*>(c.w(a.ts_tab));
+    int* step = reinterpret_cast<int*>(c.w(a.step));
+    DQ_HIP_OK(hipMemcpyAsync(ts_tab, ts, sizeof(int32_t) * num_steps, hipMemcpyHostToDevice, s));
+    DQ_HIP_OK(hipMemsetAsync(step, 0, sizeof(int), s));
+    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c2_stage), ms2_cond, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c1_stage), ms1_cond, sizeof(float) * (int64_t)B * RT * plan->plan.ms1_channels, hipMemcpyDeviceToDevice, s));
+    uint64_t* seed_st = reinterpret_cast<uint64_t*>(c.w(a.seed_stage));
+    int64_t* ids_st = reinterpret_cast<int64_t*>(c.w(a.ids_stage));
+    std::vector<int64_t> iota;
+    if (sto) {  // seed and ids staged like the conditions: a new seed or other windows replay the same graph (null ids: 0 .. B-1)
+      DQ_HIP_OK(hipMemcpyAsync(seed_st, seed_dev, sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+      if (window_ids_dev) DQ_HIP_OK(hipMemcpyAsync(ids_st, window_ids_dev, sizeof(int64_t) * B, hipMemcpyDeviceToDevice, s));
+      else {
+        iota.resize(B);
+        for (int b = 0; b < B; ++b) iota[b] = b;
+        DQ_HIP_OK(hipMemcpyAsync(ids_st, iota.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, s));
+      }
+    }
+    DQ_HIP_OK(hipStreamSynchronize(s));  // ts is caller memory; also keeps the capture below free of pending copies
+    DQ_TRY(unet_sample_prologue(c, c.w(a.c1_stage), cm, ca, rope_freqs, &io.prologue));
+    io.x_t = in_head ? xa : nullptr; io.x_out = xa; io.step_ptr = step; io.want_eps = false;  // in place: element-wise, read and written by the same lane
+    StepKey key;
+    key.params = params; key.rope = rope_freqs; key.ws = workspace; key.B = B; key.RT = RT; key.normalize = auto_normalize; key.pred = pred_type;
+    key.update = kind; key.clip = clip_x0; key.opt_epoch = options_epoch();
+    if (!plan->step_exec || !(plan->step_key == key)) {
+      drop_step_graph(plan);
+      // the caller's stream may be the legacy default stream, which cannot be captured: capture on a stream of our own
+      // (nothing executes during capture) and launch the instantiated graph on the caller's stream
+      if (!plan->cap_stream) DQ_HIP_OK(hipStreamCreateWithFlags(&plan->cap_stream, hipStreamNonBlocking));
+      hipStream_t cs = plan->cap_stream;
+      Ctx cc{plan->plan, a, params, W, nullptr, nullptr, B, RT, cs};
+      cc.save = false;
+      cc.step_io = &io;
+      DQ_HIP_OK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+      int rc = unet_forward(cc, rope_freqs, xa, nullptr, 0, c.w(a.c2_stage), c.w(a.c1_stage), cm, ca, plan->dev, c.w(a.eps), ts_tab, step);
+      // (no eps out of a captured step; the staged ids and seed, at draw 0: the kernel adds the step counter)
+      if (!rc) rc = launch_step_update(upd, xa, c.w(a.eps), xa, nullptr, 0, step, StepNoise{ids_st, seed_st, 0}, io.fused_update, cs);
+      if (!rc) rc = launch_inc_step(step, cs);
+      hipGraph_t g = nullptr;
+      const hipError_t ce = hipStreamEndCapture(cs, &g);
+      if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+      DQ_HIP_OK(ce);
+      plan->step_graph = g;
+      DQ_HIP_OK(hipGraphInstantiate(&plan->step_exec, g, nullptr, nullptr, 0));
+      plan->step_key = key;
+    }
+    for (int i = 0; i < num_steps; ++i) DQ_HIP_OK(hipGraphLaunch(plan->step_exec, s));
+    DQ_TRY(launch_sample_finish(xa, ms2_cond, out_x, out_noise, n, auto_normalize, s));
+    return 0;
+  }
+  DQ_TRY(unet_sample_prologue(c, ms1_cond, cm, ca, rope_freqs, &io.prologue));
+  c.step_io = &io;
+  for (int i = 0; i < num_steps; ++i) {
+    // eps objective: the network output IS the trajectory's eps; x0 objective, or a clamped x0: the derived eps goes to the trajectory
+    float* eps = traj_eps ? traj_eps + (int64_t)i * n : c.w(a.eps);
+    float* xn = traj_x ? traj_x + (int64_t)i * n : (in_place ? xa : xb);
+    io.x_t = in_head ? xa : nullptr; io.x_out = xn; io.coef = c.w(a.coef) + 4 * i; io.step_ptr = nullptr; io.want_eps = traj_eps != nullptr; io.fused_update = false;
+    DQ_TRY(unet_forward(c, rope_freqs, xa, nullptr, ts[i], ms2_cond, ms1_cond, cm, ca, plan->dev, eps));  // model.py:271 / :276
+    // (the caller's ids and seed; step i draws at index 1 + i)
+    DQ_TRY(launch_step_update(upd, xa, eps, xn, (traj_eps && (px0 || clip)) ? eps : nullptr, i, nullptr, StepNoise{window_ids_dev, seed_dev, 1 + i}, io.fused_update, s));
+    if (traj_x) {
+      DQ_HIP_OK(hipMemcpyAsync(xa, xn, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    } else if (!in_place) {
+      std::swap(xa, xb);
+    }
+  }
+  DQ_TRY(launch_sample_finish(xa, ms2_cond, out_x, out_noise, n, auto_normalize, s));  // model.py:319-322
+  return 0;
+}
+
+}  // extern "C"

@@ -54,6 +54,25 @@ struct Arena {
 };
 void layout_arena(const Plan& p, int B, int RT, Arena& a);
 
+// The update of one sampling step (dq_sampler.hip): DDIM is the deterministic update (eta == 0; the reference and the strided table alike), in
+// the head launch or k_ddim_step behind it; STOCHASTIC k_ddim_step_sto (eta > 0); SOLVER_1 / SOLVER_2M k_solver_step without / with the x0
+// history (a clamped x0 at first order / DPM-Solver++(2M))
+enum class StepUpdate { DDIM, STOCHASTIC, SOLVER_1, SOLVER_2M };
+
+// Everything a captured sampling step has baked into its kernel arguments or its dispatch.  clip: the clamp of k_solver_step (0: off);
+// opt_epoch: options_epoch() at capture time (a dq_set_option call may change the dispatch)
+struct StepKey {
+  const void* params = nullptr; const void* rope = nullptr; const void* ws = nullptr;
+  int B = 0, RT = 0, normalize = -1, pred = -1;
+  StepUpdate update = StepUpdate::DDIM;
+  float clip = 0.f;
+  unsigned opt_epoch = 0;
+  bool operator==(const StepKey& o) const {
+    return params == o.params && rope == o.rope && ws == o.ws && B == o.B && RT == o.RT && normalize == o.normalize && pred == o.pred &&
+           update == o.update && clip == o.clip && opt_epoch == o.opt_epoch;
+  }
+};
+
 }  // namespace dq
 
 struct dq_plan {
@@ -76,11 +95,11 @@ struct dq_plan {
   float* debug_tail_addr = nullptr; float debug_tail_value = 0.f; int debug_tail_us = 0;  // dq_debug_side_tail_store (test hook)
   bool no_side = false;  // dq_plan_set_side_stream(plan, 0): weight-gradient launches on the caller's stream (captured train steps)
   hipStream_t cap_stream = nullptr;  // capture-only stream (the caller's may be the uncapturable legacy default stream)
-  const void* g_params = nullptr; const void* g_rope = nullptr; const void* g_ws = nullptr;
-  int g_B = 0, g_RT = 0, g_norm = -1, g_pred = -1;
-  // the captured step's update: 0 the deterministic update (eta == 0; the reference and the strided table alike), 1 k_ddim_step_sto
-  // (eta > 0), 2 / 3 k_solver_step without / with the x0 history; g_clip: the clamp baked into k_solver_step's arguments (0: off)
-  int g_sto = -1;
-  float g_clip = 0.f;
-  unsigned g_opt_epoch = 0;  // dq::options_epoch() at capture time (a dq_set_option call may change the dispatch baked into the graph)
+  dq::StepKey step_key;  // what step_exec was captured for
 };
+
+// drops the captured sampling step: the next graph call captures again
+inline void drop_step_graph(dq_plan* plan) {
+  if (plan->step_exec) { (void)hipGraphExecDestroy(plan->step_exec); plan->step_exec = nullptr; }
+  if (plan->step_graph) { (void)hipGraphDestroy(plan->step_graph); plan->step_graph = nullptr; }
+}

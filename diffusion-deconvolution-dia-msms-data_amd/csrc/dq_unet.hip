@@ -1,11 +1,10 @@
-// Host orchestration of the U-Net forward/backward, the fused train step and the DDIM sampling loop, and the
-// C ABI (include/dq_hip.h).  Follows UNet1d.forward (dquartic/model/unet1d.py:1086-1166) op by op; the comments
-// name the reference lines each stage replaces.
-#include "dq_common.h"
+// Host orchestration of the U-Net: the arena layout, the op wrappers, the level-launch plan and the two passes (what the entry points of
+// dq_api.hip and dq_sampler.hip call is declared in dq_net.h), and the stand-alone op entry points of the C ABI that need this file's
+// private types.  Follows UNet1d.forward (dquartic/model/unet1d.py:1086-1166) op by op; the comments name the reference lines each stage
+// replaces.
 #include "dq_dev.h"
 #include "dq_tfm.h"
-#include "dq_kernels.h"
-#include "dq_unet.h"
+#include "dq_net.h"
 #include "dq_options.h"
 #include "../../include/dq_hip.h"
 
@@ -21,9 +20,6 @@
 namespace dq {
 
 constexpr int64_t WTMP_SLOT = 2 * HID * 64;  // floats per aligned weight slot (conv_is_gemm admits no larger weight)
-
-static thread_local std::string g_err;
-void set_error(const std::string& msg) { g_err = msg; }
 
 int occ_blocks_per_cu(const void* fn, int threads, size_t lds) {
   struct Key { const void* fn; size_t lds; int threads, dev; };
@@ -182,56 +178,11 @@ void layout_arena(const Plan& p, int B, int RT, Arena& a) {
   }  // pass
 }
 
-namespace {
-
 bool tail_fork_enabled() {
   return !DQ_DEV_FLAG("DQ_NO_TAIL_FORK", '1');  // (dev switch)
 }
 
-struct Ctx {
-  const Plan& p;
-  const Arena& ar;
-  const float* P;   // params
-  float* W;         // forward arena
-  float* G;         // gradient twin of the arena (null in inference)
-  float* dP;        // flat grads
-  int B, RT;
-  hipStream_t s;
-  bool save = true;  // keep what the backward needs (pre-norm conv outputs, LinearAttention pre-norm output)
-  dq_plan* owner = nullptr;  // side stream + events for the weight-gradient kernels (null => everything on s)
-  struct LaDefer { LaReduceItem items[LA_REDUCE_MAX]; int count = 0; int64_t cursor = 0; };
-  LaDefer* la_defer = nullptr;  // set by unet_backward: LinearAttention slot reductions collected for one launch at the end
-  // set by unet_backward: the side-stream launches (weight gradients, norm-gain reduces) are collected and issued by side_flush
-  // behind ONE event per group instead of one per ResnetBlock / conv (an event record costs ~4 us on the main stream: 29 + 14
-  // of them were 0.13 ms per step); everything they read is final when it is queued and stays untouched until the join
-  // forks: the item runs behind the group's fork event (all but the ResnetBlock partial-sum reduce, which opens no fork of its own: it goes
-  // to the side stream if that exists, else to the main stream)
-  struct SideFn { std::function<int(hipStream_t)> fn; bool forks = true; };
-  std::vector<SideFn>* side_defer = nullptr;
-  // set by unet_backward: the slot reductions of the ResnetBlock backwards that form their own weight gradients (k_res_bwd_wg),
-  // collected for ONE launch at the end of the pass (null: each is reduced right behind its launch)
-  std::vector<ResWgReduce>* wg_defer = nullptr;
-  // sampling (dq_ddim_sample): the DDIM update rides in the head launch (x_out may alias x_t), and the step-invariant MS1 feature path
-  // (unet1d.py:1120-1130) + to_k + RoPE(k) were computed once before the loop
-  struct StepIO { const float* x_t = nullptr; float* x_out = nullptr; const float* coef = nullptr; const int* step_ptr = nullptr; int pred_x0 = 0;
-                  bool prologue = false; bool fused_update = false; bool want_eps = true; };  // prologue: unet_prepare and the MS1 path ran before the loop
-  StepIO* step_io = nullptr;
-  // dq_train_step: the scalar loss (sum of the MSE kernel's partials) is needed by nobody on the gradient chain: it rides on the side stream
-  struct LossSum { const float* partials = nullptr; int count = 0; float scale = 0.f; float* out = nullptr; };
-  LossSum loss_sum;
-  // dq_train_step: final_conv, the squared error against `z` and the first two steps of the backward (d eps -> grad_out, d fin.out) ride in
-  // the final block's launch when it can take them (k_level_fwd's training head); `done` / `nparts` tell the caller
-  struct HeadLoss { const float* z = nullptr; float* grad_out = nullptr; float* part = nullptr; float gscale = 0.f; int nparts = 0; bool done = false; };
-  HeadLoss* head_loss = nullptr;
-  // dq_train_step: x_t = q_sample(x0, t, noise) (model.py:349-352) is formed by level 0's INIT stage when that stage runs (`x` of unet_forward is
-  // then only the buffer x_t would have gone to); otherwise unet_forward launches k_q_sample into `x` first
-  struct QSample { const float* alpha_bars = nullptr; const float* x0 = nullptr; const int64_t* t = nullptr; const float* noise = nullptr; int normalize = 0; int64_t per = 0; };
-  const QSample* qsample = nullptr;
-  float* w(int64_t off) const { return W + off; }
-  float* g(int64_t off) const { return G + off; }
-  const float* prm(int64_t off) const { return P + off; }
-  float* dprm(int64_t off) const { return dP + off; }
-};
+namespace {
 
 // The weight-gradient kernels depend only on tensors that are final when they are issued (dU, forward activations) and
 // nothing on the data-gradient chain depends on them: they run on a side stream, forked by an event, joined at the end.
@@ -245,12 +196,6 @@ int side_mark(const Ctx& c, hipEvent_t* ev);      // an event behind what the si
 // flush after every second level (measured, ms per step: every level 4.876, the three widest + every second deeper one 4.858, every
 // second 4.836, every third 4.90 -- the side stream then starts too late); level 0 always flushes
 static inline bool side_flush_here(int lv) { return (lv & 1) == 0; }
-
-#define DQ_TRY(expr)            \
-  do {                          \
-    int _rc = (expr);           \
-    if (_rc) return _rc;        \
-  } while (0)
 
 // "On the side queue if there is one": a piece of the backward that nothing on the main chain waits for.  `allowed` is the call site's own
 // condition; with it and a side queue at hand (unet_backward of a plan with an owner) the piece is queued for the next side_flush, else it runs now.
@@ -1318,9 +1263,10 @@ int ms1_features(const Ctx& c, const float* ms1, float cm, float ca, bool norm, 
   return conv_plain_fwd(cs, p.ms1_c1, CONV_S1, c.w(a.ms1_a), c.w(a.ms1f), B, RT, RT);
 }
 
+}  // namespace
+
 int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t* t, int t_scalar, const float* init_cond,
-                 const float* attn_cond, float cm, float ca, const DevTables& dt, float* out, const int* step_tab = nullptr,
-                 const int* step_ptr = nullptr) {
+                 const float* attn_cond, float cm, float ca, const DevTables& dt, float* out, const int* step_tab, const int* step_ptr) {
   const Plan& p = c.p;
   const Arena& a = c.ar;
   const int B = c.B, RT = c.RT, R = B * RT, L = p.levels;
@@ -1605,6 +1551,24 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
   return launch_time_embed_bwd(p, dt, c.P, c.dP, c.w(a.tbuf), c.g(a.ss), B, c.s);
 }
 
+// The step-invariant part of a sampling call (dq_sampler.hip), once in front of its steps: the once-per-parameter-state launches, the MS1
+// feature path (unet1d.py:1120-1130), to_k and RoPE(k) (:555, 561) depend on neither t nor x_t.  unet_forward skips them under StepIO::prologue.
+int unet_sample_prologue(const Ctx& c, const float* ms1, float cm, float ca, const float* rope, bool* ran) {
+  const Plan& p = c.p;
+  const Arena& a = c.ar;
+  *ran = false;
+  if (p.wide_mid) return 0;  // (the wide bottleneck keeps its projections inside the step, and prepares there)
+  const LevelPlan lp = level_plan(p, a, c.B, c.RT, false, false);
+  DQ_TRY(unet_prepare(c, lp, c.s));  // W2 / operand images / the aligned copy of to_k's weight for the GEMM route
+  DQ_TRY(ms1_features(c, ms1, cm, ca, true, c.s));
+  DQ_TRY(conv_plain_fwd(c, proj(p.k_w, HID, p.cond_dim), CONV_S1, c.w(a.ms1f), c.w(a.kk), c.B, c.RT, c.RT, lp.prep_ok ? 1 : -1));
+  if (rope) DQ_TRY(launch_rope(c.w(a.kk), rope, c.B, (int64_t)HID * c.RT, c.RT, 1.f, c.s));
+  *ran = true;
+  return 0;
+}
+
+namespace {
+
 int ensure_side(dq_plan* pl) {
   if (pl->side_stream) return 0;
     // Own priority class => own hardware queue.  Normal-priority streams share a small round-robin pool of HSA queues,
@@ -1685,6 +1649,8 @@ int join_side(const Ctx& c) {
   return 0;
 }
 
+}  // namespace
+
 // Lays out the arena for (B, RT) and, on the first call of a plan, uploads the ~10 KB offset tables of the scale/shift
 // heads (the only device allocation the library ever makes; dq_plan_create itself never touches the GPU).
 int ensure_arena(dq_plan* plan, int B, int RT) {
@@ -1705,599 +1671,11 @@ int ensure_arena(dq_plan* plan, int B, int RT) {
   return 0;
 }
 
-}  // namespace
 }  // namespace dq
 
 using namespace dq;
 
 extern "C" {
-
-const char* dq_last_error(void) { return g_err.c_str(); }
-int dq_abi_version(void) { return DQ_ABI_VERSION; }
-
-dq_plan* dq_plan_create_ex(int dim, int n_mults, const int* dim_mults, int mz, int num_timesteps, int attn_cond_channels) {
-  dq_plan* h = new dq_plan();
-  std::string err = build_plan(h->plan, dim, n_mults, dim_mults, mz, num_timesteps, attn_cond_channels);
-  if (!err.empty()) {
-    set_error("dq_plan_create: " + err);
-    delete h;
-    return nullptr;
-  }
-  return h;
-}
-dq_plan* dq_plan_create(int dim, int n_mults, const int* dim_mults, int mz, int num_timesteps) {
-  return dq_plan_create_ex(dim, n_mults, dim_mults, mz, num_timesteps, 1);
-}
-int dq_plan_attn_cond_channels(const dq_plan* plan) { return plan ? plan->plan.ms1_channels : -1; }
-
-void dq_plan_destroy(dq_plan* plan) {
-  if (!plan) return;
-  if (plan->dev.ss_w_off) (void)hipFree(plan->dev.ss_w_off);
-  if (plan->dev.ss_b_off) (void)hipFree(plan->dev.ss_b_off);
-  if (plan->step_exec) (void)hipGraphExecDestroy(plan->step_exec);
-  if (plan->step_graph) (void)hipGraphDestroy(plan->step_graph);
-  if (plan->cap_stream) (void)hipStreamDestroy(plan->cap_stream);
-  if (plan->side_stream) {
-    (void)hipStreamDestroy(plan->side_stream);
-    for (auto& e : plan->events) if (e) (void)hipEventDestroy(e);
-  }
-  delete plan;
-}
-
-int dq_plan_num_params(const dq_plan* plan) { return (int)plan->plan.params.size(); }
-int64_t dq_plan_param_floats(const dq_plan* plan) { return plan->plan.total_floats; }
-
-int dq_plan_param_info(const dq_plan* plan, int i, char* name, int name_cap, int64_t* offset, int* ndim, int64_t* shape) {
-  DQ_REQUIRE(plan && i >= 0 && i < (int)plan->plan.params.size(), "dq_plan_param_info: index out of range");
-  const ParamInfo& pi = plan->plan.params[i];
-  DQ_REQUIRE((int)pi.name.size() + 1 <= name_cap, "dq_plan_param_info: name buffer too small");
-  std::strcpy(name, pi.name.c_str());
-  *offset = pi.offset;
-  *ndim = pi.ndim;
-  for (int k = 0; k < 4; ++k) shape[k] = pi.shape[k];
-  return 0;
-}
-
-static_assert(FINAL_IDENTITY == DQ_FINAL_IDENTITY && FINAL_SOFTPLUS == DQ_FINAL_SOFTPLUS, "FinalAct mirrors include/dq_hip.h");
-int dq_plan_set_final_act(dq_plan* plan, int act) {
-  DQ_REQUIRE(plan, "dq_plan_set_final_act: null plan");
-  DQ_REQUIRE(act == DQ_FINAL_IDENTITY || act == DQ_FINAL_SOFTPLUS,
-             "dq_plan_set_final_act: act must be 0 (DQ_FINAL_IDENTITY) or 1 (DQ_FINAL_SOFTPLUS), got " + std::to_string(act));
-  // a captured sampling step has the head's kernels baked in: never replay one captured under the other activation
-  if (plan->step_exec) { (void)hipGraphExecDestroy(plan->step_exec); plan->step_exec = nullptr; }
-  if (plan->step_graph) { (void)hipGraphDestroy(plan->step_graph); plan->step_graph = nullptr; }
-  plan->plan.final_act = act;
-  return 0;
-}
-int dq_plan_final_act(const dq_plan* plan) { return plan ? plan->plan.final_act : -1; }
-
-int64_t dq_unet_workspace_bytes(dq_plan* plan, int B, int RT, int training) {
-  if (!plan || B < 0 || RT < 0) return -1;
-  Arena a;
-  layout_arena(plan->plan, B, RT, a);
-  return (int64_t)sizeof(float) * a.floats * (training ? 2 : 1);
-}
-
-int dq_q_sample(const float* alpha_bars_dev, const float* x0, const int64_t* t, const float* noise, float* x_t, int B,
-                int64_t per_sample, int normalize_x0, void* stream) {
-  return launch_q_sample(alpha_bars_dev, x0, t, noise, x_t, B, per_sample, normalize_x0, (hipStream_t)stream);
-}
-
-int dq_ddim_step(const float* x_t, const float* eps, float* x_prev, const float* coef_dev, int64_t n, void* stream) {
-  return launch_ddim_step(x_t, eps, x_prev, coef_dev, n, nullptr, (hipStream_t)stream);
-}
-
-int dq_ddim_step_x0(const float* x_t, const float* x0_pred, float* x_prev, float* eps_out, const float* coef_dev, int64_t n,
-                    void* stream) {
-  DQ_REQUIRE(x_t && x0_pred && x_prev && coef_dev, "dq_ddim_step_x0: null argument");
-  return launch_ddim_step(x_t, x0_pred, x_prev, coef_dev, n, nullptr, (hipStream_t)stream, 1, eps_out);
-}
-
-int dq_randn(float* out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int B, int64_t per_window, void* stream) {
-  return launch_randn(out, window_ids_dev, seed_dev, draw, B, per_window, (hipStream_t)stream);
-}
-
-int dq_ddim_step_sto(const float* x_t, const float* net_out, float* x_prev, float* eps_out, const float* coef_dev,
-                     const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window,
-                     void* stream) {
-  DQ_REQUIRE(x_t && net_out && x_prev && coef_dev && seed_dev, "dq_ddim_step_sto: null argument");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_ddim_step_sto: Unknown pred_type");
-  return launch_ddim_step_sto(x_t, net_out, x_prev, pred_type == DQ_PRED_X0 ? eps_out : nullptr, coef_dev, coef_dev + 4, window_ids_dev,
-                              seed_dev, draw, pred_type == DQ_PRED_X0, B, per_window, nullptr, (hipStream_t)stream);
-}
-
-// The sampler's per-step coefficients (host only).  eta == 0: the fp32 expressions of model.py:265-267, 284-286 as they always were.
-// eta > 0: sa, sb, sap the same fp32 expressions (x0 and eps are derived as before); sigma and c in double from the fp32 table values.
-int dq_ddim_coef_table(const float* alpha_bars_host, int num_timesteps, const int32_t* timesteps_host, int num_steps, float eta,
-                       float* coef_out, float* sigma_out) {
-  DQ_REQUIRE(alpha_bars_host && timesteps_host && coef_out && sigma_out, "dq_ddim_coef_table: null argument");
-  DQ_REQUIRE(num_timesteps >= 1 && num_steps >= 1, "dq_ddim_coef_table: num_timesteps and num_steps must be >= 1");
-  DQ_REQUIRE(eta >= 0.f && eta <= 1.f, "dq_ddim_coef_table: eta must satisfy 0 <= eta <= 1");  // (false for NaN)
-  for (int i = 0; i < num_steps; ++i) {
-    const int t = timesteps_host[i];
-    DQ_REQUIRE(t >= 0 && t < num_timesteps, "dq_ddim_coef_table: timestep out of range");
-    const float ab = alpha_bars_host[t];
-    coef_out[4 * i + 0] = std::sqrt(ab);
-    coef_out[4 * i + 1] = std::sqrt(1.0f - ab);
-    sigma_out[i] = 0.f;
-    if (t > 0) {
-      const float abp = alpha_bars_host[t - 1];
-      coef_out[4 * i + 2] = std::sqrt(abp);
-      coef_out[4 * i + 3] = std::sqrt(1.0f - abp);
-      if (eta > 0.f) {
-        const double a = (double)ab, ap = (double)abp;
-        // (a degenerate schedule -- alpha_bar of 0 or 1, or one that rises -- gets sigma = 0 instead of a NaN)
-        const double ratio = ap > 0.0 ? std::min(a / ap, 1.0) : 1.0;
-        const double sg = (1.0 - a) > 0.0 ? (double)eta * std::sqrt((1.0 - ap) / (1.0 - a)) * std::sqrt(1.0 - ratio) : 0.0;
-        coef_out[4 * i + 3] = (float)std::sqrt(std::max(0.0, 1.0 - ap - sg * sg));
-        sigma_out[i] = (float)sg;
-      }
-    } else {
-      coef_out[4 * i + 2] = -1.f;
-      coef_out[4 * i + 3] = 0.f;
-    }
-  }
-  return 0;
-}
-
-// Rows of the step-consistent samplers (host only).  Step i at t = ts[i] lands on ts[i + 1]; the last step of the list
-// returns x0 whatever its t.  kind DQ_SAMPLER_DDIM: dq_ddim_coef_table's expressions with abp = alpha_bars[ts[i + 1]].  kind
-// DQ_SAMPLER_DPMPP_2M: [sa, sb, cx, c0] and c1 in double from the fp32 table values; SOLVER_ORDER1: the same rows with c1 = 0 everywhere
-// (strided DDIM as a solver row: what clip_x0 runs).
-namespace {
-constexpr int SOLVER_ORDER1 = 3;
-
-int sampler_rows(const float* ab_tab, int T, const int32_t* ts, int n, int kind, float eta, float* coef_out, float* extra_out, const char* who) {
-  for (int i = 0; i < n; ++i) {
-    if (ts[i] < 0 || ts[i] >= T) { dq::set_error(std::string(who) + ": timestep out of range"); return 1; }
-    if (i > 0 && ts[i] >= ts[i - 1]) { dq::set_error(std::string(who) + ": the timesteps of this sampler must be strictly decreasing"); return 1; }
-  }
-  double h_prev = 0.0;
-  for (int i = 0; i < n; ++i) {
-    const float ab = ab_tab[ts[i]];
-    const bool last = i == n - 1;
-    extra_out[i] = 0.f;
-    if (kind == DQ_SAMPLER_DDIM) {
-      coef_out[4 * i + 0] = std::sqrt(ab);
-      coef_out[4 * i + 1] = std::sqrt(1.0f - ab);
-      if (last) { coef_out[4 * i + 2] = -1.f; coef_out[4 * i + 3] = 0.f; continue; }
-      const float abp = ab_tab[ts[i + 1]];
-      coef_out[4 * i + 2] = std::sqrt(abp);
-      coef_out[4 * i + 3] = std::sqrt(1.0f - abp);
-      if (eta > 0.f) {  // (dq_ddim_coef_table's sigma and c, with this abp)
-        const double a = (double)ab, ap = (double)abp;
-        const double ratio = ap > 0.0 ? std::min(a / ap, 1.0) : 1.0;
-        const double sg = (1.0 - a) > 0.0 ? (double)eta * std::sqrt((1.0 - ap) / (1.0 - a)) * std::sqrt(1.0 - ratio) : 0.0;
-        coef_out[4 * i + 3] = (float)std::sqrt(std::max(0.0, 1.0 - ap - sg * sg));
-        extra_out[i] = (float)sg;
-      }
-      continue;
-    }
-    const double al = std::sqrt((double)ab), sg = std::sqrt(1.0 - (double)ab);
-    coef_out[4 * i + 0] = (float)al;
-    coef_out[4 * i + 1] = (float)sg;
-    if (last) { coef_out[4 * i + 2] = -1.f; coef_out[4 * i + 3] = 0.f; continue; }
-    const double abp = (double)ab_tab[ts[i + 1]];
-    const double alp = std::sqrt(abp), sgp = std::sqrt(1.0 - abp);
-    // h = lambda_{i+1} - lambda_i, lambda = log(alpha / sigma); a schedule end with sigma or alpha exactly 0 gives h = inf: 1 - e^-h = 1
-    const double h = std::log(alp / sgp) - std::log(al / sg);
-    const double em = std::isnan(h) ? 1.0 : -std::expm1(-h);
-    const double base = alp * em;
-    double c0 = base, c1 = 0.0;
-    const bool second = kind == DQ_SAMPLER_DPMPP_2M && i >= 1 && std::isfinite(h) && h > 0.0 && std::isfinite(h_prev) && h_prev > 0.0;
-    if (second) {
-      const double r = h_prev / h;
-      c0 = base * (1.0 + 1.0 / (2.0 * r));
-      c1 = -base / (2.0 * r);
-    }
-    coef_out[4 * i + 2] = sg > 0.0 ? (float)(sgp / sg) : 0.f;
-    coef_out[4 * i + 3] = (float)c0;
-    extra_out[i] = (float)c1;
-    h_prev = h;
-  }
-  return 0;
-}
-}  // namespace
-
-int dq_sampler_coef_table(const float* alpha_bars_host, int num_timesteps, const int32_t* timesteps_host, int num_steps, int sampler,
-                          float eta, float* coef_out, float* extra_out) {
-  DQ_REQUIRE(alpha_bars_host && timesteps_host && coef_out && extra_out, "dq_sampler_coef_table: null argument");
-  DQ_REQUIRE(num_timesteps >= 1 && num_steps >= 1, "dq_sampler_coef_table: num_timesteps and num_steps must be >= 1");
-  DQ_REQUIRE(sampler == DQ_SAMPLER_REFERENCE || sampler == DQ_SAMPLER_DDIM || sampler == DQ_SAMPLER_DPMPP_2M,
-             "dq_sampler_coef_table: unknown sampler");
-  DQ_REQUIRE(eta >= 0.f && eta <= 1.f, "dq_sampler_coef_table: eta must satisfy 0 <= eta <= 1");  // (false for NaN)
-  if (sampler == DQ_SAMPLER_REFERENCE) return dq_ddim_coef_table(alpha_bars_host, num_timesteps, timesteps_host, num_steps, eta, coef_out, extra_out);
-  DQ_REQUIRE(sampler != DQ_SAMPLER_DPMPP_2M || eta == 0.f, "dq_sampler_coef_table: DPM-Solver++(2M) is deterministic: eta must be 0");
-  return sampler_rows(alpha_bars_host, num_timesteps, timesteps_host, num_steps, sampler, eta, coef_out, extra_out, "dq_sampler_coef_table");
-}
-
-int dq_solver_step(const float* x_t, const float* net_out, float* x_prev, float* x0_hist, float* eps_out, const float* coef_dev, float clip_x0,
-                   int pred_type, int64_t n, void* stream) {
-  DQ_REQUIRE(x_t && net_out && x_prev && coef_dev, "dq_solver_step: null argument");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_solver_step: Unknown pred_type");
-  return launch_solver_step(x_t, net_out, x_prev, x0_hist, eps_out, coef_dev, coef_dev + 4, clip_x0, pred_type == DQ_PRED_X0, n, nullptr,
-                            (hipStream_t)stream);
-}
-
-int dq_unet_fwd(dq_plan* plan, const float* params, const float* rope_freqs, const float* x, const int64_t* t, int t_scalar,
-                const float* init_cond, const float* attn_cond, float cond_mul, float cond_add, float* out, int save_for_bwd,
-                void* workspace, int64_t workspace_bytes, int B, int RT, void* stream) {
-  DQ_REQUIRE(plan && params && x && init_cond && attn_cond && out && workspace, "dq_unet_fwd: null argument");
-  DQ_REQUIRE(B > 0 && RT > 0, "dq_unet_fwd: B and RT must be positive");
-  DQ_TRY(ensure_arena(plan, B, RT));
-  DQ_REQUIRE(workspace_bytes >= (int64_t)sizeof(float) * plan->arena.floats, "dq_unet_fwd: workspace too small");
-  Ctx c{plan->plan, plan->arena, params, (float*)workspace, nullptr, nullptr, B, RT, (hipStream_t)stream};
-  c.save = save_for_bwd != 0;
-  return unet_forward(c, rope_freqs, x, t, t_scalar, init_cond, attn_cond, cond_mul, cond_add, plan->dev, out);
-}
-
-int dq_unet_bwd(dq_plan* plan, const float* params, const float* rope_freqs, const float* init_cond, float cond_mul,
-                float cond_add, const float* grad_out, float* grads, float* grad_x, void* workspace, int64_t workspace_bytes,
-                int B, int RT, void* stream) {
-  DQ_REQUIRE(plan && params && init_cond && grad_out && grads && workspace, "dq_unet_bwd: null argument");
-  DQ_TRY(ensure_arena(plan, B, RT));
-  DQ_REQUIRE(workspace_bytes >= 2 * (int64_t)sizeof(float) * plan->arena.floats, "dq_unet_bwd: workspace too small (training=1)");
-  float* W = (float*)workspace;
-  Ctx c{plan->plan, plan->arena, params, W, W + plan->arena.floats, grads, B, RT, (hipStream_t)stream};
-  c.owner = plan->no_side ? nullptr : plan;
-  plan->twin_zeroed = nullptr;  // (only a forked forward of the SAME dq_train_step call clears the twin ahead of its backward)
-  return unet_backward(c, rope_freqs, init_cond, cond_mul, cond_add, plan->dev, grad_out, grad_x);
-}
-
-int dq_mse_loss_fwd_bwd(const float* eps, const float* noise, float* loss_out, float* grad_out, float* scratch, int64_t n,
-                        void* stream) {
-  DQ_REQUIRE(eps && noise && loss_out && scratch, "dq_mse_loss_fwd_bwd: null argument");
-  return launch_mse_fwd_bwd(eps, noise, loss_out, grad_out, scratch, n, (hipStream_t)stream);
-}
-
-int dq_ms1_loss_fwd_bwd(const float* pred, const float* x_t, const float* ms1_cond, float cond_mul, float cond_add,
-                        const float* loss_weight_dev, const int64_t* t, float ms1_loss_weight, float* loss_inout, float* grad_inout,
-                        float* scratch, int B, int RT, int MZ, void* stream) {
-  DQ_REQUIRE(pred && ms1_cond && loss_inout && scratch, "dq_ms1_loss_fwd_bwd: null argument");
-  DQ_REQUIRE(ms1_loss_weight > 0.f && ms1_loss_weight <= 1.f, "dq_ms1_loss_fwd_bwd: ms1_loss_weight must lie in (0, 1]");
-  // (this entry has no plan: ms1_cond is the (B, RT) chromatogram the term is defined on; a multi-channel MS1 has no such term yet)
-  return launch_ms1_loss(pred, x_t, ms1_cond, cond_mul, cond_add, loss_weight_dev, t, ms1_loss_weight, B, RT, MZ, grad_inout, loss_inout,
-                         scratch, (hipStream_t)stream);
-}
-
-int dq_mse_loss_weighted_fwd_bwd(const float* pred, const float* target, float target_mul, float target_add,
-                                 const float* loss_weight_dev, const int64_t* t, float* loss_out, float* grad_out, float* scratch,
-                                 int B, int64_t per_sample, void* stream) {
-  DQ_REQUIRE(pred && target && loss_weight_dev && t && loss_out && scratch, "dq_mse_loss_weighted_fwd_bwd: null argument");
-  DQ_REQUIRE(B > 0 && per_sample > 0, "dq_mse_loss_weighted_fwd_bwd: B and per_sample must be positive");
-  return launch_mse_fwd_bwd(pred, target, loss_out, grad_out, scratch, (int64_t)B * per_sample, (hipStream_t)stream, loss_weight_dev,
-                            t, per_sample, target_mul, target_add);
-}
-
-int dq_adamw_clip_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch,
-                       float grad_scale, float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
-                       int step, float* gnorm_out, void* stream) {
-  DQ_REQUIRE(params && grads && exp_avg && exp_avg_sq && scratch, "dq_adamw_clip_step: null argument");
-  return launch_adamw_clip(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, lr, beta1, beta2, eps,
-                           weight_decay, step, gnorm_out, (hipStream_t)stream);
-}
-
-int dq_adamw_clip_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch, float grad_scale,
-                           float max_norm, const float* lr_dev, double beta1, double beta2, double eps, double weight_decay, int* step_dev,
-                           float* gnorm_out, void* stream) {
-  DQ_REQUIRE(params && grads && exp_avg && exp_avg_sq && scratch && lr_dev && step_dev, "dq_adamw_clip_step_dev: null argument");
-  return launch_adamw_clip_dev(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, lr_dev, beta1, beta2, eps, weight_decay,
-                               step_dev, gnorm_out, (hipStream_t)stream);
-}
-
-int dq_adamw_clip_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch,
-                           float grad_scale, float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
-                           int step, float* gnorm_out, float* ema, float ema_decay, int ema_warmup, void* stream) {
-  DQ_REQUIRE(params && grads && exp_avg && exp_avg_sq && scratch, "dq_adamw_clip_ema_step: null argument");
-  return launch_adamw_clip_ema(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, lr, beta1, beta2, eps, weight_decay,
-                               step, gnorm_out, ema, ema_decay, ema_warmup, (hipStream_t)stream);
-}
-
-int dq_adamw_clip_ema_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch,
-                               float grad_scale, float max_norm, const float* lr_dev, double beta1, double beta2, double eps,
-                               double weight_decay, int* step_dev, float* gnorm_out, float* ema, float ema_decay, int ema_warmup,
-                               void* stream) {
-  DQ_REQUIRE(params && grads && exp_avg && exp_avg_sq && scratch && lr_dev && step_dev, "dq_adamw_clip_ema_step_dev: null argument");
-  return launch_adamw_clip_ema_dev(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, lr_dev, beta1, beta2, eps,
-                                   weight_decay, step_dev, gnorm_out, ema, ema_decay, ema_warmup, (hipStream_t)stream);
-}
-
-int dq_set_option(const char* key, int64_t value) {
-  const int i = option_index(key);
-  DQ_REQUIRE(i >= 0, "dq_set_option: unknown key");
-  set_option(i, value);
-  return 0;
-}
-int64_t dq_get_option(const char* key) {
-  const int i = option_index(key);
-  if (i < 0) { set_error("dq_get_option: unknown key"); return INT64_MIN; }
-  return option((Option)i);
-}
-int64_t dq_get_option_effective(const char* key) {
-  switch (option_index(key)) {
-    case OPT_LA_SMALL_MIN_ROWS: return la_small_min_rows();
-    case OPT_LA_ROWS_BWD_MIN_ROWS: return la_rows_bwd_min_rows();
-    case OPT_RES_ROWS_BWD_MIN_ROWS: return res_rows_bwd_min_rows();
-    default: set_error("dq_get_option_effective: unknown key"); return -1;
-  }
-}
-
-int dq_debug_side_tail_store(dq_plan* plan, float* addr, float value, int delay_us) {
-  DQ_REQUIRE(plan && delay_us >= 0 && delay_us <= 100000, "dq_debug_side_tail_store: null plan / delay out of range");
-  plan->debug_tail_addr = addr; plan->debug_tail_value = value; plan->debug_tail_us = delay_us;
-  return 0;
-}
-
-int dq_plan_set_side_stream(dq_plan* plan, int on) {
-  DQ_REQUIRE(plan, "dq_plan_set_side_stream: null plan");
-  plan->no_side = on ? false : true;
-  return 0;
-}
-
-int dq_train_step(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_dev, const float* x0,
-                  const float* ms2_cond, const float* ms1_cond, const int64_t* t, const float* noise, int auto_normalize,
-                  int pred_type, const float* loss_weight_dev, float ms1_loss_weight, float* grads, float* loss_out, void* workspace,
-                  int64_t workspace_bytes, int B, int RT, void* stream) {
-  DQ_REQUIRE(plan && params && alpha_bars_dev && x0 && ms2_cond && ms1_cond && t && noise && grads && loss_out && workspace,
-             "dq_train_step: null argument");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_train_step: Unknown pred_type");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || loss_weight_dev, "dq_train_step: pred_type x0 needs the loss-weight (SNR) table");
-  DQ_REQUIRE(B > 0 && RT > 0, "dq_train_step: B and RT must be positive");
-  DQ_REQUIRE(ms1_loss_weight >= 0.f && ms1_loss_weight <= 1.f, "dq_train_step: ms1_loss_weight must lie in [0, 1]");
-  DQ_REQUIRE(ms1_loss_weight == 0.f || plan->plan.ms1_channels == 1,
-             "dq_train_step: ms1_loss_weight > 0 with attn_cond_channels > 1 is not built (the MS1 term is defined on a chromatogram)");
-  plan->twin_zeroed = nullptr;  // (a step that failed between its forked forward and its backward must not leave "already cleared" behind)
-  DQ_TRY(ensure_arena(plan, B, RT));
-  const Arena& a = plan->arena;
-  DQ_REQUIRE(workspace_bytes >= 2 * (int64_t)sizeof(float) * a.floats, "dq_train_step: workspace too small (training=1)");
-  hipStream_t s = (hipStream_t)stream;
-  float* W = (float*)workspace;
-  Ctx c{plan->plan, a, params, W, W + a.floats, grads, B, RT, s};
-  c.owner = plan->no_side ? nullptr : plan;
-  const int64_t per = (int64_t)RT * plan->plan.mz;
-  const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
-  const bool qs_fused_on = !DQ_DEV_FLAG("DQ_NO_QSAMPLE_FUSE", '1');  // (dev switch)
-  Ctx::QSample qs;
-  qs.alpha_bars = alpha_bars_dev; qs.x0 = x0; qs.t = t; qs.noise = noise; qs.normalize = auto_normalize; qs.per = per;
-  if (qs_fused_on && ms1_loss_weight == 0.f) c.qsample = &qs;  // model.py:349-352 (the MS1 term reads x_t: it keeps the launch)
-  else DQ_TRY(launch_q_sample(alpha_bars_dev, x0, t, noise, c.w(a.xa), B, per, auto_normalize, s));
-  const bool head_loss_on = !DQ_DEV_FLAG("DQ_NO_HEAD_LOSS", '1');  // (dev switch)
-  Ctx::HeadLoss hl;
-  if (head_loss_on && pred_type == DQ_PRED_EPS && ms1_loss_weight == 0.f) {
-    hl.z = noise; hl.grad_out = c.w(a.xb); hl.part = c.w(a.head_part); hl.gscale = 2.0f / (float)(B * per);  // (launch_mse_fwd_bwd's scale)
-    c.head_loss = &hl;
-  }
-  DQ_TRY(unet_forward(c, rope_freqs, c.w(a.xa), t, 0, ms2_cond, ms1_cond, cm, ca, plan->dev, c.w(a.eps)));   // model.py:359
-  // the gradient twin is zeroed inside unet_backward, so the loss gradient goes to a forward-arena buffer (xb)
-  if (hl.done) {  // (loss and its gradient came with the forward's last launch; the sum of the partials rides on the side stream: unet_backward)
-    c.loss_sum.partials = hl.part; c.loss_sum.count = hl.nparts; c.loss_sum.scale = 1.0f / (float)(B * per); c.loss_sum.out = loss_out;
-  } else if (pred_type == DQ_PRED_X0)  // model.py:372-376, 404: target = normalised x0, per-sample weight loss_weight[t_b]
-    DQ_TRY(launch_mse_fwd_bwd(c.w(a.eps), x0, loss_out, c.w(a.xb), c.w(a.partials), B * per, s, loss_weight_dev, t, per, cm, ca));
-  else if (c.owner && ms1_loss_weight == 0.f && tail_fork_enabled()) {
-    int nparts = 0;  // (the sum of the partials -> loss_out rides on the side stream: unet_backward)
-    DQ_TRY(launch_mse_fwd_bwd(c.w(a.eps), noise, loss_out, c.w(a.xb), c.w(a.partials), B * per, s, nullptr, nullptr, 0, 1.f, 0.f, &nparts));
-    c.loss_sum.partials = c.w(a.partials); c.loss_sum.count = nparts; c.loss_sum.scale = 1.0f / (float)(B * per); c.loss_sum.out = loss_out;
-  } else
-    DQ_TRY(launch_mse_fwd_bwd(c.w(a.eps), noise, loss_out, c.w(a.xb), c.w(a.partials), B * per, s));         // model.py:361
-  if (ms1_loss_weight > 0.f)  // model.py:364-371 / 379-386, 398-402 (semantics: DESIGN.md section 12)
-    DQ_TRY(launch_ms1_loss(c.w(a.eps), pred_type == DQ_PRED_X0 ? nullptr : c.w(a.xa), ms1_cond, cm, ca,
-                           pred_type == DQ_PRED_X0 ? loss_weight_dev : nullptr, t, ms1_loss_weight, B, RT, plan->plan.mz, c.w(a.xb), loss_out,
-                           c.w(a.ms1_scratch), s));
-  DQ_TRY(unet_backward(c, rope_freqs, ms2_cond, cm, ca, plan->dev, c.w(a.xb), nullptr));
-  return 0;
-}
-
-// The forward-only counterpart of dq_train_step: q_sample, the network forward in its no-save mode (the inference arena alone: no gradient
-// twin, no side queue, dq_plan::twin_zeroed untouched), then the per-window MSE.  The slice sums live in the arena's second sampling buffer
-// (xb: B * per floats rounded up to 64, which an inference forward never touches); a window of fewer than 8192 elements needs one
-// double, so only a B * per below 64 with per == 1 could fall short, and the launcher checks the size it is given.
-int dq_eval_step(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_dev, const float* x0,
-                 const float* ms2_cond, const float* ms1_cond, const int64_t* t, const float* noise, int auto_normalize, int pred_type,
-                 const float* loss_weight_dev, float* loss_out, float* per_window_out, void* workspace, int64_t workspace_bytes, int B, int RT,
-                 void* stream) {
-  DQ_REQUIRE(plan && params && alpha_bars_dev && x0 && ms2_cond && ms1_cond && t && noise && loss_out && per_window_out && workspace,
-             "dq_eval_step: null argument");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_eval_step: Unknown pred_type");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || loss_weight_dev, "dq_eval_step: pred_type x0 needs the loss-weight (SNR) table");
-  DQ_REQUIRE(B > 0 && RT > 0, "dq_eval_step: B and RT must be positive");
-  DQ_TRY(ensure_arena(plan, B, RT));
-  const Arena& a = plan->arena;
-  DQ_REQUIRE(workspace_bytes >= (int64_t)sizeof(float) * a.floats, "dq_eval_step: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  Ctx c{plan->plan, a, params, (float*)workspace, nullptr, nullptr, B, RT, s};
-  c.save = false;
-  const int64_t per = (int64_t)RT * plan->plan.mz;
-  const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
-  DQ_TRY(launch_q_sample(alpha_bars_dev, x0, t, noise, c.w(a.xa), B, per, auto_normalize, s));                 // model.py:349-352
-  DQ_TRY(unet_forward(c, rope_freqs, c.w(a.xa), t, 0, ms2_cond, ms1_cond, cm, ca, plan->dev, c.w(a.eps)));  // model.py:359
-  const bool px0 = pred_type == DQ_PRED_X0;  // model.py:361 / 372-376: the target is the noise, or the normalised x0 weighted by loss_weight[t_b]
-  return launch_mse_per_window(c.w(a.eps), px0 ? x0 : noise, px0 ? cm : 1.f, px0 ? ca : 0.f, px0 ? loss_weight_dev : nullptr, t,
-                               per_window_out, loss_out, c.w(a.xb), (int64_t)sizeof(float) * ((B * per + 63) / 64 * 64), B, per, s);
-}
-
-int64_t dq_mse_per_window_scratch_bytes(int B, int64_t per) { return mse_per_window_scratch_bytes(B, per); }
-
-int dq_mse_per_window(const float* out, const float* target, float tm, float ta, const float* lw, const int64_t* t, float* per_window_out,
-                      float* loss_out, void* scratch, int B, int64_t per, void* stream) {
-  DQ_REQUIRE(B > 0 && per > 0, "dq_mse_per_window: B and per must be positive");
-  return launch_mse_per_window(out, target, tm, ta, lw, t, per_window_out, loss_out, scratch, mse_per_window_scratch_bytes(B, per), B, per,
-                               (hipStream_t)stream);
-}
-
-int64_t dq_recon_metrics_scratch_bytes(int B, int RT, int MZ) { return recon_metrics_scratch_bytes(B, RT, MZ); }
-
-int dq_recon_metrics(const float* pred, const float* target, float* out, void* scratch, int64_t scratch_bytes, int B, int RT, int MZ,
-                     void* stream) {
-  return launch_recon_metrics(pred, target, out, scratch, scratch_bytes, B, RT, MZ, (hipStream_t)stream);
-}
-
-int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                   const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                   const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                   int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream) {
-  DQ_REQUIRE(x_T, "dq_ddim_sample: null argument");
-  return dq_ddim_sample_ex(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type,
-                           timesteps_host, num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream,
-                           0.f, nullptr, nullptr);
-}
-
-int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                      const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                      const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                      int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                      const uint64_t* seed_dev, const int64_t* window_ids_dev) {
-  return dq_ddim_sample_solver(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type,
-                               timesteps_host, num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT,
-                               stream, eta, seed_dev, window_ids_dev, DQ_SAMPLER_REFERENCE, 0.f);
-}
-
-int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                      const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                      const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                      int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                      const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0) {
-  DQ_REQUIRE(plan && params && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
-             "dq_ddim_sample: null argument");
-  DQ_REQUIRE(eta >= 0.f && eta <= 1.f, "dq_ddim_sample: eta must satisfy 0 <= eta <= 1");  // (false for NaN)
-  const bool sto = eta > 0.f;  // the update draws noise: k_ddim_step_sto behind the forward instead of the update in the head launch
-  // step-consistent samplers: refused here, before anything touches the device
-  DQ_REQUIRE(sampler == DQ_SAMPLER_REFERENCE || sampler == DQ_SAMPLER_DDIM || sampler == DQ_SAMPLER_DPMPP_2M, "dq_ddim_sample: unknown sampler");
-  const bool clip = clip_x0 > 0.f;  // (<= 0 and NaN: off)
-  DQ_REQUIRE(sampler != DQ_SAMPLER_DPMPP_2M || !sto, "dq_ddim_sample: DPM-Solver++(2M) is deterministic: eta must be 0");
-  DQ_REQUIRE(!clip || sampler != DQ_SAMPLER_REFERENCE, "dq_ddim_sample: clip_x0 needs the ddim or dpmpp_2m sampler");
-  DQ_REQUIRE(!clip || !sto, "dq_ddim_sample: clip_x0 needs eta == 0");
-  if (sampler != DQ_SAMPLER_REFERENCE)
-    for (int i = 1; i < num_steps; ++i)
-      DQ_REQUIRE(timesteps_host[i] < timesteps_host[i - 1], "dq_ddim_sample: the timesteps of this sampler must be strictly decreasing");
-  // the update: k_solver_step behind the forward (2M, or a clamped x0 at first order); else the reference's kernels over this sampler's table
-  const bool solver = sampler == DQ_SAMPLER_DPMPP_2M || clip;
-  const bool keep_hist = sampler == DQ_SAMPLER_DPMPP_2M;
-  const int upd = solver ? (keep_hist ? 3 : 2) : (int)sto;
-  if (!clip) clip_x0 = 0.f;
-  DQ_REQUIRE(seed_dev || (x_T && !sto), "dq_ddim_sample: eta > 0 and a null x_T need the seed (device memory)");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_ddim_sample: Unknown pred_type");
-  const int px0 = pred_type == DQ_PRED_X0;
-  DQ_REQUIRE(B > 0 && RT > 0 && num_steps >= 1 && num_steps <= 1024, "dq_ddim_sample: need B, RT > 0 and 1 <= num_steps <= 1024");
-  DQ_TRY(ensure_arena(plan, B, RT));
-  const Arena& a = plan->arena;
-  DQ_REQUIRE(workspace_bytes >= (int64_t)sizeof(float) * a.floats, "dq_ddim_sample: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W = (float*)workspace;
-  Ctx c{plan->plan, a, params, W, nullptr, nullptr, B, RT, s};
-  c.save = false;
-  const int T = num_timesteps;  // length of alpha_bars_host (DDIMDiffusionModel.num_timesteps: the schedule is the caller's)
-  DQ_REQUIRE(T >= 1, "dq_ddim_sample: num_timesteps must be >= 1");
-  const int64_t n = (int64_t)B * RT * plan->plan.mz;
-  const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
-  const int32_t* ts = timesteps_host;  // trunc(linspace(T-1, 0, num_steps)) formed by the caller exactly as model.py:313 does
-  // coefficient table (model.py:265-267, 284-286), fp32 like the reference; with eta > 0 also sigma per step (dq_ddim_coef_table)
-  std::vector<float> coef(4 * (size_t)num_steps), sigma((size_t)num_steps);
-  if (sampler == DQ_SAMPLER_REFERENCE) DQ_TRY(dq_ddim_coef_table(alpha_bars_host, T, ts, num_steps, eta, coef.data(), sigma.data()));
-  else DQ_TRY(sampler_rows(alpha_bars_host, T, ts, num_steps, solver && !keep_hist ? SOLVER_ORDER1 : sampler, eta, coef.data(), sigma.data(), "dq_ddim_sample"));
-  DQ_HIP_OK(hipMemcpyAsync(c.w(a.coef), coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice, s));
-  if (sto || solver) DQ_HIP_OK(hipMemcpyAsync(c.w(a.sigma), sigma.data(), sizeof(float) * sigma.size(), hipMemcpyHostToDevice, s));
-  // the host vector must outlive the copy: pageable H2D copies are staged synchronously by the runtime, but make it explicit
-  DQ_HIP_OK(hipStreamSynchronize(s));
-  float* xa = c.w(a.xa);
-  float* xb = c.w(a.xb);
-  const int64_t per = (int64_t)RT * plan->plan.mz;
-  if (x_T) DQ_HIP_OK(hipMemcpyAsync(xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-  else DQ_TRY(launch_randn(xa, window_ids_dev, seed_dev, 0, B, per, s));  // draw index 0 is x_T's
-  // The MS1 feature path (unet1d.py:1120-1130), to_k and RoPE(k) (:555, 561) depend on neither t nor x_t: once per call, not per step
-  Ctx::StepIO io;
-  io.pred_x0 = px0; io.coef = c.w(a.coef);
-  const LevelPlan lp = level_plan(plan->plan, a, B, RT, false, false);
-  auto ms1_prologue = [&](const Ctx& cx, const float* ms1) -> int {
-    const Plan& p = cx.p;
-    if (p.wide_mid) return 0;  // (the wide bottleneck keeps its projections inside the step, and prepares there)
-    DQ_TRY(unet_prepare(cx, lp, cx.s));  // W2 / operand images / the aligned copy of to_k's weight for the GEMM route
-    DQ_TRY(ms1_features(cx, ms1, cm, ca, true, cx.s));
-    DQ_TRY(conv_plain_fwd(cx, proj(p.k_w, HID, p.cond_dim), CONV_S1, cx.w(a.ms1f), cx.w(a.kk), B, RT, RT, lp.prep_ok ? 1 : -1));
-    if (rope_freqs) DQ_TRY(launch_rope(cx.w(a.kk), rope_freqs, B, (int64_t)HID * RT, RT, 1.f, cx.s));
-    io.prologue = true;
-    return 0;
-  };
-  if (use_graph && !traj_x && !traj_eps) {
-    // ---- hipGraph path: one step captured once (all pointers inside the arena / parameter buffers), replayed per step.
-    // The step index lives on the device: k_time_fwd reads ts_tab[*step], the DDIM update its coefficient row, k_inc_step bumps it.
-    int* ts_tab = reinterpret_cast<int*>(c.w(a.ts_tab));
-    int* step = reinterpret_cast<int*>(c.w(a.step));
-    DQ_HIP_OK(hipMemcpyAsync(ts_tab, ts, sizeof(int32_t) * num_steps, hipMemcpyHostToDevice, s));
-    DQ_HIP_OK(hipMemsetAsync(step, 0, sizeof(int), s));
-    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c2_stage), ms2_cond, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c1_stage), ms1_cond, sizeof(float) * (int64_t)B * RT * plan->plan.ms1_channels, hipMemcpyDeviceToDevice, s));
-    uint64_t* seed_st = reinterpret_cast<uint64_t*>(c.w(a.seed_stage));
-    int64_t* ids_st = reinterpret_cast<int64_t*>(c.w(a.ids_stage));
-    std::vector<int64_t> iota;
-    if (sto) {  // seed and ids staged like the conditions: a new seed or other windows replay the same graph (null ids: 0 .. B-1)
-      DQ_HIP_OK(hipMemcpyAsync(seed_st, seed_dev, sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-      if (window_ids_dev) DQ_HIP_OK(hipMemcpyAsync(ids_st, window_ids_dev, sizeof(int64_t) * B, hipMemcpyDeviceToDevice, s));
-      else {
-        iota.resize(B);
-        for (int b = 0; b < B; ++b) iota[b] = b;
-        DQ_HIP_OK(hipMemcpyAsync(ids_st, iota.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, s));
-      }
-    }
-    DQ_HIP_OK(hipStreamSynchronize(s));  // ts is caller memory; also keeps the capture below free of pending copies
-    DQ_TRY(ms1_prologue(c, c.w(a.c1_stage)));
-    io.x_t = (sto || solver) ? nullptr : xa; io.x_out = xa; io.step_ptr = step; io.want_eps = false;  // in place: element-wise, read and written by the same lane
-    const bool valid = plan->step_exec && plan->g_params == params && plan->g_rope == rope_freqs && plan->g_ws == workspace &&
-                       plan->g_B == B && plan->g_RT == RT && plan->g_norm == auto_normalize && plan->g_pred == pred_type &&
-                       plan->g_sto == upd && plan->g_clip == clip_x0 && plan->g_opt_epoch == options_epoch();
-    if (!valid) {
-      if (plan->step_exec) { (void)hipGraphExecDestroy(plan->step_exec); plan->step_exec = nullptr; }
-      if (plan->step_graph) { (void)hipGraphDestroy(plan->step_graph); plan->step_graph = nullptr; }
-      // the caller's stream may be the legacy default stream, which cannot be captured: capture on a stream of our own
-      // (nothing executes during capture) and launch the instantiated graph on the caller's stream
-      if (!plan->cap_stream) DQ_HIP_OK(hipStreamCreateWithFlags(&plan->cap_stream, hipStreamNonBlocking));
-      hipStream_t cs = plan->cap_stream;
-      Ctx cc{plan->plan, a, params, W, nullptr, nullptr, B, RT, cs};
-      cc.save = false;
-      cc.step_io = &io;
-      DQ_HIP_OK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-      int rc = unet_forward(cc, rope_freqs, xa, nullptr, 0, c.w(a.c2_stage), c.w(a.c1_stage), cm, ca, plan->dev, c.w(a.eps), ts_tab, step);
-      if (!rc && solver)  // history in xb, updated in place; c1 per row rides in the sigma table
-        rc = launch_solver_step(xa, c.w(a.eps), xa, keep_hist ? xb : nullptr, nullptr, c.w(a.coef), c.w(a.sigma), clip_x0, px0, n, step, cs);
-      else if (!rc && sto) rc = launch_ddim_step_sto(xa, c.w(a.eps), xa, nullptr, c.w(a.coef), c.w(a.sigma), ids_st, seed_st, 0, px0, B, per, step, cs);
-      else if (!rc && !io.fused_update) rc = launch_ddim_step(xa, c.w(a.eps), xa, c.w(a.coef), n, step, cs, px0, nullptr);  // in place: element-wise
-      if (!rc) rc = launch_inc_step(step, cs);
-      hipGraph_t g = nullptr;
-      const hipError_t ce = hipStreamEndCapture(cs, &g);
-      if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-      DQ_HIP_OK(ce);
-      plan->step_graph = g;
-      DQ_HIP_OK(hipGraphInstantiate(&plan->step_exec, g, nullptr, nullptr, 0));
-      plan->g_params = params; plan->g_rope = rope_freqs; plan->g_ws = workspace; plan->g_B = B; plan->g_RT = RT; plan->g_norm = auto_normalize; plan->g_pred = pred_type; plan->g_sto = upd; plan->g_clip = clip_x0; plan->g_opt_epoch = options_epoch();
-    }
-    for (int i = 0; i < num_steps; ++i) DQ_HIP_OK(hipGraphLaunch(plan->step_exec, s));
-    DQ_TRY(launch_sample_finish(xa, ms2_cond, out_x, out_noise, n, auto_normalize, s));
-    return 0;
-  }
-  DQ_TRY(ms1_prologue(c, ms1_cond));
-  c.step_io = &io;
-  for (int i = 0; i < num_steps; ++i) {
-    // eps objective: the network output IS the trajectory's eps; x0 objective: the derived eps goes to the trajectory
-    float* eps = traj_eps ? traj_eps + (int64_t)i * n : c.w(a.eps);
-    float* xn = traj_x ? traj_x + (int64_t)i * n : (solver ? xa : xb);  // the solver loop keeps x in xa: xb holds the x0 history
-    io.x_t = (sto || solver) ? nullptr : xa; io.x_out = xn; io.coef = c.w(a.coef) + 4 * i; io.step_ptr = nullptr; io.want_eps = traj_eps != nullptr; io.fused_update = false;
-    DQ_TRY(unet_forward(c, rope_freqs, xa, nullptr, ts[i], ms2_cond, ms1_cond, cm, ca, plan->dev, eps));  // model.py:271 / :276
-    if (solver)
-      DQ_TRY(launch_solver_step(xa, eps, xn, keep_hist ? xb : nullptr, (traj_eps && (px0 || clip)) ? traj_eps + (int64_t)i * n : nullptr,
-                                c.w(a.coef) + 4 * i, c.w(a.sigma) + i, clip_x0, px0, n, nullptr, s));
-    else if (sto)  // step i draws at index 1 + i
-      DQ_TRY(launch_ddim_step_sto(xa, eps, xn, (traj_eps && px0) ? traj_eps + (int64_t)i * n : nullptr, c.w(a.coef) + 4 * i, c.w(a.sigma) + i,
-                                  window_ids_dev, seed_dev, 1 + i, px0, B, per, nullptr, s));
-    else if (!io.fused_update)
-      DQ_TRY(launch_ddim_step(xa, eps, xn, c.w(a.coef) + 4 * i, n, nullptr, s, px0, (traj_eps && px0) ? traj_eps + (int64_t)i * n : nullptr));  // model.py:273-289
-    if (traj_x) {
-      DQ_HIP_OK(hipMemcpyAsync(xa, xn, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-    } else if (!solver) {
-      std::swap(xa, xb);
-    }
-  }
-  DQ_TRY(launch_sample_finish(xa, ms2_cond, out_x, out_noise, n, auto_normalize, s));  // model.py:319-322
-  return 0;
-}
 
 // The LevelPlan a pass at (B, RT) builds: the SAME level_plan() call as unet_forward (save, twin as the pass has them), unet_backward (1, 1)
 // and the sampler's prologue (0, 0), on an arena laid out as dq_unet_workspace_bytes lays it out -- no workspace, no launch, no device.

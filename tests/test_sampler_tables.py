@@ -96,6 +96,21 @@ def test_sampler_0_is_dq_ddim_coef_table(kind):
 
 
 @pytest.mark.parametrize("kind", ["cosine", "linear"])
+@pytest.mark.parametrize("T", [1, 2, 3, 7, 50, 1000])
+def test_full_list_reference_is_strided_ddim(kind, T):
+    """on ts = T-1 .. 0 the two landings coincide (ts[i + 1] == t - 1, and the last of the list is t == 0): one row builder serves both
+    tables, so they are equal bit for bit"""
+    ab = alpha_bars(kind, T)
+    ts = list(range(T - 1, -1, -1))
+    for eta in (0.0, 0.5, 1.0):
+        rc0, c0, e0 = sampler_table(ab, ts, "reference", eta)
+        rc1, c1, e1 = sampler_table(ab, ts, "ddim", eta)
+        assert rc0 == 0 and rc1 == 0
+        assert c0.tobytes() == c1.tobytes() and e0.tobytes() == e1.tobytes(), (kind, T, eta)
+        assert c0[-1, 2] == -1 and (c0[:-1, 2] >= 0).all()
+
+
+@pytest.mark.parametrize("kind", ["cosine", "linear"])
 @pytest.mark.parametrize("sampler,eta", [("ddim", 0.0), ("ddim", 0.5), ("ddim", 1.0), ("dpmpp_2m", 0.0)])
 def test_rows_within_one_ulp_of_float64(kind, sampler, eta):
     ab = alpha_bars(kind)

@@ -310,6 +310,31 @@ def test_sampler_steps_graph_and_cache(pred):
 
 
 @pytest.mark.parametrize("pred", ["eps", "x0"])
+def test_cache_key_over_all_four_updates(pred):
+    """one plan, the four update kinds of the captured step (deterministic, stochastic, first-order solver, 2M) over both tables, in two
+    interleaved orders: every call replays or recaptures the step of ITS setting -- equal to that setting's eager result, bit for bit"""
+    dm, _, xT, c2, c1 = _model(pred)
+    x, a, b = xT[:2].cuda(), c2[:2].cuda(), c1[:2].cuda()
+    settings = [dict(), dict(eta=1.0, seed=77), dict(sampler="ddim"), dict(sampler="ddim", eta=1.0, seed=77), dict(sampler="ddim", clip_x0=1.0),
+                dict(sampler="dpmpp_2m")]
+    try:
+        with torch.no_grad():
+            dm.use_graph = False
+            eager = [dm.sample(x, a, b, num_steps=NS, **kw) for kw in settings]
+            dm.use_graph = True
+            for order in ([0, 1, 2, 3, 4, 5, 0], [5, 3, 1, 4, 0, 2, 3, 5, 1]):  # every setting follows a different one in each order
+                for k in order:
+                    sg, ng = dm.sample(x, a, b, num_steps=NS, **settings[k])
+                    assert torch.equal(sg, eager[k][0]) and torch.equal(ng, eager[k][1]), (order, settings[k])
+    finally:
+        dm.use_graph = True
+    # the settings are six different samplers: a stale step of another setting would not have passed unnoticed
+    for i in range(len(settings)):
+        for j in range(i):
+            assert not torch.equal(eager[i][0], eager[j][0]), (settings[i], settings[j])
+
+
+@pytest.mark.parametrize("pred", ["eps", "x0"])
 def test_strided_ddim_eta1(pred):
     dm, _, xT, c2, c1 = _model(pred)
     x, a, b = xT[:2].cuda(), c2[:2].cuda(), c1[:2].cuda()
