@@ -52,7 +52,7 @@ struct Plan {
   std::vector<int> dims;  // [init_dim, dim*mult...]
   int mid_n = 0;          // downsampled_n (unet1d.py:1027)
   int mid_c = 0;          // mid_dim * downsampled_n
-  bool wide_mid = false;  // mid_c not in {16, 32, 64}: the bottleneck runs on im2col + GEMM + channel-axis norm (k_wide.hip)
+  bool wide_mid = false;  // mid_c not in {16, 32}: the bottleneck runs on im2col + GEMM + channel-axis norm (k_wide.hip)
   int cond_dim = 0;       // attn_cond_init_dim = 2*dim (unet1d.py:970)
   int ms1_channels = 1;   // attn_cond_channels: the MS1 conditioning is (B, RT, ms1_channels) (unet1d.py:976, 1122-1130)
   int ss_total = 0;       // floats per sample in the ss vector (all ResnetBlock mlps + init_cond_proj)

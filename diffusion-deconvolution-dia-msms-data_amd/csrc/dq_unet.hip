@@ -1263,6 +1263,43 @@ int ms1_features(const Ctx& c, const float* ms1, float cm, float ca, bool norm, 
   return conv_plain_fwd(cs, p.ms1_c1, CONV_S1, c.w(a.ms1_a), c.w(a.ms1f), B, RT, RT);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// the scaffolding of a backward pass: what its pieces queue instead of launching at once, the clearing of the twin, the end of the pass.
+// unet_backward and the bottleneck-only entry (dq_debug_mid_bwd) run inside the same three functions.
+// ---------------------------------------------------------------------------------------------------------------
+struct BwdQueues {
+  Ctx::LaDefer la;                 // LinearAttention slot reductions: one launch at the end (la_flush / la_flush_side)
+  std::vector<Ctx::SideFn> side;   // side-stream launches behind the next side_flush (only with an owner: else they run where they are issued)
+  std::vector<ResWgReduce> wg;     // slot reductions of the ResnetBlock backwards that form their own weight gradients
+};
+Ctx bwd_open(const Ctx& c_in, BwdQueues& q) {
+  Ctx c = c_in;
+  c.la_defer = &q.la;
+  c.wg_defer = &q.wg;
+  if (c.owner) c.side_defer = &q.side;
+  return c;
+}
+// only the accumulated-into region of the twin (offsets are multiples of 64 floats); a forked forward of the same step cleared it already.
+// keep >= 0: the extent [keep, keep + keep_floats) holds what the caller put there (the bottleneck-only entry's d mid2.out) and stays
+int bwd_clear_twin(const Ctx& c, int64_t keep = -1, int64_t keep_floats = 0) {
+  if (c.owner && c.owner->twin_zeroed == c.G) { c.owner->twin_zeroed = nullptr; return 0; }
+  const int64_t z = c.ar.zero_floats;
+  if (keep < 0) return launch_zero(c.G, z, c.s);
+  const int64_t end = std::min(z, (keep + keep_floats + 63) / 64 * 64);
+  if (keep > 0) DQ_TRY(launch_zero(c.G, std::min(keep, z), c.s));
+  if (end < z) DQ_TRY(launch_zero(c.G + end, z - end, c.s));
+  return 0;
+}
+// The end of a pass: the last weight-gradient launches go to the side stream BEFORE the LinearAttention slot reduce is queued on the main
+// stream: the side stream waits for an event recorded here, and recorded behind the reduce it made those launches (init_conv, the MS1 convs:
+// ~80 us) start only when the ~100 us reduce had finished -- an exposed tail in front of the join
+int bwd_close(const Ctx& c, BwdQueues& q) {
+  DQ_TRY(side_flush(c));
+  DQ_TRY(la_flush(c));
+  DQ_TRY(res_wg_reduce_all(q.wg, c.s));
+  return join_side(c);
+}
+
 }  // namespace
 
 int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t* t, int t_scalar, const float* init_cond,
@@ -1381,13 +1418,9 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
 
 int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, float cm, float ca, const DevTables& dt,
                   const float* grad_out, float* grad_x) {
-  Ctx::LaDefer la_defer;
-  std::vector<Ctx::SideFn> side_items;
-  std::vector<ResWgReduce> wg_items;
-  Ctx c = c_in;
-  c.la_defer = &la_defer;
-  c.wg_defer = &wg_items;
-  if (c.owner) c.side_defer = &side_items;
+  BwdQueues queues;
+  const Ctx c = bwd_open(c_in, queues);
+  std::vector<ResWgReduce>& wg_items = queues.wg;
   if (c.loss_sum.out) {
     const Ctx::LossSum ls = c.loss_sum;
     DQ_TRY(on_side(c, true, [ls](hipStream_t ss) { return launch_sum_partials(ls.partials, ls.count, ls.scale, ls.out, ss); }));
@@ -1396,9 +1429,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
   const Arena& a = c.ar;
   const int B = c.B, RT = c.RT, R = B * RT, L = p.levels;
   const LevelPlan lp = level_plan(p, a, B, RT, true, true);  // (what the forward of this step built with save: the same levels took the same launches)
-  // only the accumulated-into region of the twin (offsets are multiples of 64 floats); a forked forward of the same step cleared it already
-  if (c.owner && c.owner->twin_zeroed == c.G) c.owner->twin_zeroed = nullptr;
-  else DQ_TRY(launch_zero(c.G, a.zero_floats, c.s));
+  DQ_TRY(bwd_clear_twin(c));
   // the ResnetBlock / resample-conv slot reductions collected so far as one side-stream item
   auto wg_to_side = [&c, &wg_items]() -> int {
     const bool wg_off = DQ_DEV_FLAG("DQ_NO_LA_FLUSH_SIDE", '1');  // (dev switch)
@@ -1539,13 +1570,7 @@ int unet_backward(const Ctx& c_in, const float* rope, const float* init_cond, fl
     DQ_HIP_OK(hipMemcpy2DAsync(grad_x, sizeof(float) * p.mz, c.g(a.cat0) + p.mz, sizeof(float) * 2 * p.mz, sizeof(float) * p.mz, R,
                                hipMemcpyDeviceToDevice, c.s));
   }
-  // the last weight-gradient launches go to the side stream BEFORE the LinearAttention slot reduce is queued on the main stream: the
-  // side stream waits for an event recorded here, and recorded behind the reduce it made those launches (init_conv, the MS1 convs:
-  // ~80 us) start only when the ~100 us reduce had finished -- an exposed tail in front of the join
-  DQ_TRY(side_flush(c));
-  DQ_TRY(la_flush(c));
-  DQ_TRY(res_wg_reduce_all(wg_items, c.s));
-  DQ_TRY(join_side(c));
+  DQ_TRY(bwd_close(c, queues));
   // time embedding: all scale/shift heads + the MLP -- after the join: the per-sample d(scale, shift) of the fused ResnetBlocks are
   // summed on the side stream
   return launch_time_embed_bwd(p, dt, c.P, c.dP, c.w(a.tbuf), c.g(a.ss), B, c.s);
@@ -1699,6 +1724,80 @@ int dq_debug_level_plan(dq_plan* plan, int B, int RT, int save, int twin, int32_
   return n;
 }
 
+// Lays the plan's cached arena out for (B, RT), as the first pass at that shape would (host only: no device table is uploaded here), so that
+// dq_debug_tensor_offset answers for the shape before any call at it -- a caller of dq_debug_mid_fwd fills workspace slots first.
+int dq_debug_layout(dq_plan* plan, int B, int RT) {
+  if (!plan || B <= 0 || RT <= 0) return -1;
+  if (plan->arena.B != B || plan->arena.RT != RT) layout_arena(plan->plan, B, RT, plan->arena);
+  return 0;
+}
+
+// What mid_forms() answers for a pass at (B, RT) -- the function mid_forward / mid_backward ask --, on a local arena laid out as
+// dq_unet_workspace_bytes lays it out, with the few plan constants a caller of the two entries below needs: no workspace, no launch, no
+// device, no change of the plan.
+int dq_debug_mid_forms(dq_plan* plan, int B, int RT, int32_t* out, int cap) {
+  if (!plan || !out || B <= 0 || RT <= 0 || cap < DQ_MID_FORMS_INTS) return -1;
+  const Plan& p = plan->plan;
+  Arena a;
+  layout_arena(p, B, RT, a);
+  MidForms mf{false, false, false};
+  if (!p.wide_mid) mf = mid_forms(p, a, B, RT);
+  int n = 0;
+  out[n++] = mf.qkv_fused; out[n++] = mf.out_fused; out[n++] = mf.pre_fused; out[n++] = p.wide_mid; out[n++] = p.mid_c; out[n++] = p.cond_dim;
+  out[n++] = level_plan(p, a, B, RT, false, false).prep_ok;  // (depends on the plan alone: the same for every pass)
+  out[n++] = p.mid1.ss_off; out[n++] = p.mid2.ss_off; out[n++] = p.ss_total;
+  static_assert(DQ_MID_FORMS_INTS == 10, "dq_debug_mid_forms writes DQ_MID_FORMS_INTS ints");
+  return n;
+}
+
+// The narrow bottleneck alone, forward: the time embedding (tbuf and every scale / shift head), then -- unless skip_ms1, as in unet_forward,
+// where the sampler's prologue has done it -- unet_prepare (of which the bottleneck reads the aligned copies of the attention's projection
+// weights; the level and tiny operand images it also writes belong to launches this entry never makes), then mid_forward on the mid_in / ms1f
+// the caller wrote into their workspace slots.  skip_ms1: the rotated kk too is the caller's, and a call without skip_ms1 has run on this
+// workspace with these parameters before (the prepared weight slots are its).
+int dq_debug_mid_fwd(dq_plan* plan, const float* params, const float* rope_freqs, const int64_t* t, int save_for_bwd, int skip_ms1,
+                     void* workspace, int64_t workspace_bytes, int B, int RT, void* stream) {
+  DQ_REQUIRE(plan && params && t && workspace, "dq_debug_mid_fwd: null argument");
+  DQ_REQUIRE(B > 0 && RT > 0, "dq_debug_mid_fwd: B and RT must be positive");
+  DQ_REQUIRE(!plan->plan.wide_mid, "dq_debug_mid_fwd: the wide bottleneck (k_wide.hip) is not this entry's");
+  Arena probe;
+  layout_arena(plan->plan, B, RT, probe);
+  DQ_REQUIRE(workspace_bytes >= (int64_t)sizeof(float) * probe.floats, "dq_debug_mid_fwd: workspace too small");
+  DQ_TRY(ensure_arena(plan, B, RT));
+  Ctx c{plan->plan, plan->arena, params, (float*)workspace, nullptr, nullptr, B, RT, (hipStream_t)stream};
+  c.save = save_for_bwd != 0;
+  const LevelPlan lp = level_plan(c.p, c.ar, B, RT, c.save, false);
+  DQ_TRY(launch_time_embed_fwd(c.p, plan->dev, c.P, t, 0, c.w(c.ar.tbuf), c.w(c.ar.ss), B, nullptr, nullptr, c.s));
+  if (!skip_ms1) DQ_TRY(unet_prepare(c, lp, c.s));
+  return mid_forward(c, rope_freqs, skip_ms1 != 0, lp.prep_ok);
+}
+
+// The narrow bottleneck alone, backward: d mid2.out is what the caller wrote into the twin of mid2 (everything else of the twin's
+// accumulated-into region is cleared, as unet_backward clears it); mid_backward inside unet_backward's scaffolding (bwd_open / bwd_close), with
+// the side queue (grad_x_mode 0) or all on the caller's stream (1).  No time-embedding backward, no MS1 path: the twin keeps d mid_in, d ms1f
+// and, in the twin of ss, both blocks' per-sample d(scale, shift); grads receives += of the bottleneck's parameter gradients.
+int dq_debug_mid_bwd(dq_plan* plan, const float* params, const float* rope_freqs, float* grads, int grad_x_mode, void* workspace,
+                     int64_t workspace_bytes, int B, int RT, void* stream) {
+  DQ_REQUIRE(plan && params && grads && workspace, "dq_debug_mid_bwd: null argument");
+  DQ_REQUIRE(B > 0 && RT > 0, "dq_debug_mid_bwd: B and RT must be positive");
+  DQ_REQUIRE(!plan->plan.wide_mid, "dq_debug_mid_bwd: the wide bottleneck (k_wide.hip) is not this entry's");
+  Arena probe;
+  layout_arena(plan->plan, B, RT, probe);
+  DQ_REQUIRE(workspace_bytes >= 2 * (int64_t)sizeof(float) * probe.floats, "dq_debug_mid_bwd: workspace too small (training=1)");
+  DQ_TRY(ensure_arena(plan, B, RT));
+  const Arena& a = plan->arena;
+  float* W = (float*)workspace;
+  Ctx c_in{plan->plan, a, params, W, W + a.floats, grads, B, RT, (hipStream_t)stream};
+  c_in.owner = plan->no_side ? nullptr : plan;
+  plan->twin_zeroed = nullptr;
+  BwdQueues queues;
+  const Ctx c = bwd_open(c_in, queues);
+  const LevelPlan lp = level_plan(c.p, a, B, RT, true, true);
+  DQ_TRY(bwd_clear_twin(c, a.mid2.out, (int64_t)B * c.p.mid_c * RT));
+  DQ_TRY(mid_backward(c, rope_freqs, grad_x_mode != 0, lp.prep_ok));
+  return bwd_close(c, queues);
+}
+
 int64_t dq_debug_tensor_offset(dq_plan* plan, const char* name) {
   if (!plan || !name) return -1;
   const Arena& a = plan->arena;
@@ -1716,6 +1815,14 @@ int64_t dq_debug_tensor_offset(dq_plan* plan, const char* name) {
   if (n == "o") return a.o;
   if (n == "attn_out") return a.attn_out;
   if (n == "mid2") return a.mid2.out;
+  if (n == "mid1.u1") return a.mid1.u1;
+  if (n == "mid1.u2") return a.mid1.u2;
+  if (n == "mid1.a1") return a.mid1.a1;
+  if (n == "mid2.u1") return a.mid2.u1;
+  if (n == "mid2.u2") return a.mid2.u2;
+  if (n == "mid2.a1") return a.mid2.a1;
+  if (n == "lse") return a.lse;
+  if (n == "@twin") return a.floats;  // the gradient twin G starts this many floats behind the workspace's start (a training workspace)
   if (n == "fin") return a.fin.out;
   if (n == "eps") return a.eps;  // (its gradient twin: d loss / d final_conv's output when the Softplus head's backward ran)
   for (int i = 0; i < (int)a.downs.size(); ++i) {

@@ -23,6 +23,7 @@ LEVEL_KINDS = ("unfused", "kernel", "tiny")  # DQ_LEVEL_* (index = value)
 LEVEL_FORM_FIELDS = ("kind", "img", "la", "post_w", "in_folded", "resample")  # DQ_LEVEL_PLAN_FORM_INTS, in the order dq_debug_level_plan writes them
 METRIC_NAMES = ("mse", "mae", "cosine", "sa", "pearson", "scan_sa", "scan_count", "xic_r", "xic_count")  # DQ_METRIC_* (index = column of dq_recon_metrics' output)
 GEMM_PLAN_PART_FIELDS = ("tile_base", "ntiles", "splits", "k_per_split")  # of `full`, then of `rest`, after bm and kv (DQ_GEMM_PLAN_INTS)
+MID_FORMS_FIELDS = ("qkv_fused", "out_fused", "pre_fused", "wide_mid", "mid_c", "cond_dim", "prep_ok", "ss_mid1", "ss_mid2", "ss_total")  # DQ_MID_FORMS_INTS, in dq_debug_mid_forms' order
 LEVEL_PLAN_FLAGS = ("prep_ok", "init_fused", "head_shape", "head_train", "use_tb_up", "use_tb_dn", "tb_up_w")  # DQ_LEVEL_PLAN_FLAG_INTS
 
 # name -> (restype, argtypes); this table is checked against include/dq_hip.h by tests/test_abi.py
@@ -93,6 +94,10 @@ PROTOTYPES = {
     "dq_debug_tensor_offset": (c_int64, [c_void_p, c_char_p]),
     "dq_debug_level_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int]),
     "dq_debug_side_tail_store": (c_int, [c_void_p, c_void_p, c_float, c_int]),
+    "dq_debug_layout": (c_int, [c_void_p, c_int, c_int]),
+    "dq_debug_mid_forms": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32), c_int]),
+    "dq_debug_mid_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "dq_debug_mid_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "dq_tfm_create": (c_void_p, [c_int, c_int, c_int, c_int]),
     "dq_tfm_destroy": (None, [c_void_p]),
     "dq_tfm_num_params": (c_int, [c_void_p]),
@@ -241,6 +246,19 @@ def level_plan(plan, B: int, RT: int, save: bool, twin: bool) -> dict:
 
     out = {"levels": int(L), "dn": [form(i) for i in range(L)], "up": [form(L + i) for i in range(L + 1)]}
     out.update({k: bool(x) for k, x in zip(LEVEL_PLAN_FLAGS, buf[1 + nf * (2 * L + 1): n])})
+    return out
+
+
+def mid_forms(plan, B: int, RT: int) -> dict:
+    """``dq_debug_mid_forms``: which pieces of the bottleneck attention ride in a ResnetBlock's launch in a pass over (B, RT) windows (bools),
+    with ``mid_c``, ``cond_dim``, the blocks' offsets in a sample's scale / shift vector and its length (ints): MID_FORMS_FIELDS."""
+    buf = (c_int32 * len(MID_FORMS_FIELDS))()
+    n = lib().dq_debug_mid_forms(plan, int(B), int(RT), buf, len(MID_FORMS_FIELDS))
+    if n != len(MID_FORMS_FIELDS):
+        raise RuntimeError(f"dq_debug_mid_forms failed for B={B}, RT={RT}")
+    out = dict(zip(MID_FORMS_FIELDS, (int(x) for x in buf)))
+    for k in ("qkv_fused", "out_fused", "pre_fused", "wide_mid", "prep_ok"):
+        out[k] = bool(out[k])
     return out
 
 

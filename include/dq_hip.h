@@ -49,7 +49,8 @@ const char* dq_last_error(void);
  * dq_plan_attn_cond_channels, dq_ms1_feat_fwd, dq_ms1_feat_wgrad, dq_ms1_feat_wgrad_scratch_floats).  11: dq_conv_bwd,
  * dq_conv_bwd_workspace_floats, dq_conv_bwd_forms (later, additive: dq_adamw_clip_ema_step, dq_adamw_clip_ema_step_dev; dq_randn,
  * dq_ddim_step_sto, dq_ddim_coef_table, dq_ddim_sample_ex).  12: dq_debug_level_plan (later, additive: dq_gemm_ex,
- * dq_debug_gemm_plan; DQ_SAMPLER_*, dq_sampler_coef_table, dq_solver_step, dq_ddim_sample_solver). */
+ * dq_debug_gemm_plan; DQ_SAMPLER_*, dq_sampler_coef_table, dq_solver_step, dq_ddim_sample_solver; dq_debug_layout, dq_debug_mid_forms,
+ * dq_debug_mid_fwd, dq_debug_mid_bwd). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -573,8 +574,40 @@ int dq_attn_bwd(const float* q, const float* k, const float* v, const float* o, 
                 float* dq, float* dk, float* dv, int B, int RT, void* stream);
 
 /* Test hook: offset (in floats) of a named activation inside the workspace laid out by the last call on this plan
- * ("h0", "ms1f", "down3", "down3.la", "mid1", "attn_out", "up0", "fin", "eps", ...), or -1. */
+ * ("h0", "ms1f", "down3", "down3.la", "mid1", "mid1.u1", "mid2.a1", "lse", "attn_out", "up0", "fin", "eps", ...), or -1.  "@twin": the
+ * distance in floats from the start of a training workspace to its gradient twin (a tensor's gradient lies at the tensor's offset there). */
 int64_t dq_debug_tensor_offset(dq_plan* plan, const char* name);
+
+/* Test hook: lays the plan's workspace out for (B, RT) as the first pass at that shape would, on the host alone: dq_debug_tensor_offset
+ * answers for that shape afterwards, before any call at it.  Returns 0, or -1 (null plan, B or RT < 1). */
+int dq_debug_layout(dq_plan* plan, int B, int RT);
+
+/* Test hooks: the narrow bottleneck (mid_block1, Residual(PreNorm(Attention)), mid_block2 over (B, mid_c, RT), mid_c 16 or 32) alone.
+ *
+ * dq_debug_mid_forms: what both passes decide for (B, RT), without a workspace, a launch or a device.  out receives DQ_MID_FORMS_INTS ints:
+ *   qkv_fused, out_fused, pre_fused (the attention's front / back / the front's transpose ride in a ResnetBlock's launch), wide_mid, mid_c,
+ *   cond_dim, prep_ok (the prepare launch fills the aligned weight slots), the offsets of mid_block1's and mid_block2's [scale | shift] in a
+ *   sample's ss vector, ss_total (that vector's length).  Returns the number of ints written, or -1 (null argument, B or RT < 1, cap too small).
+ *
+ * dq_debug_mid_fwd: the caller has laid out the workspace (dq_unet_workspace_bytes) and written mid_in (B, mid_c, RT) and ms1f (B, cond_dim, RT)
+ * -- with skip_ms1, also the rotated kk (B, 128, RT) -- at their dq_debug_tensor_offset.  Runs the time embedding for t (B int64 on the
+ * device; fills every scale / shift head), unless skip_ms1 the once-per-parameter-state launches (a skip_ms1 call follows a call without it
+ * on the same workspace and parameters, as a sampling step follows the prologue), then the bottleneck: mid1, xn, qv, kk, o, lse, attn_out,
+ * mid2 and, with save_for_bwd, the blocks' u1 / a1 / u2 are in the workspace afterwards.  Refuses a wide bottleneck, a short workspace and
+ * null arguments before any device call.
+ *
+ * dq_debug_mid_bwd: behind a dq_debug_mid_fwd with save_for_bwd on the same training workspace, the caller has written d mid2.out into the
+ * twin of "mid2" (the twin starts dq_debug_tensor_offset(plan, "@twin") floats behind the workspace).  The rest of the twin's
+ * accumulated-into region is cleared, then the bottleneck's backward runs as it does inside dq_unet_bwd: grad_x_mode 0 with the side queue,
+ * 1 with everything on `stream`, as when the caller asked for d loss / d x.  Everything is joined onto `stream` at return.  Neither the
+ * time-embedding backward nor the MS1 path's runs: the twins of mid_in, ms1f and o hold their gradients, the twin of "ss" the two blocks'
+ * per-sample d(scale, shift), and grads (the flat layout) has received += of mid_block1.*, mid_block2.* (but mlp.*) and mid_attn.*. */
+enum { DQ_MID_FORMS_INTS = 10 };
+int dq_debug_mid_forms(dq_plan* plan, int B, int RT, int32_t* out, int cap);
+int dq_debug_mid_fwd(dq_plan* plan, const float* params, const float* rope_freqs, const int64_t* t, int save_for_bwd, int skip_ms1,
+                     void* workspace, int64_t workspace_bytes, int B, int RT, void* stream);
+int dq_debug_mid_bwd(dq_plan* plan, const float* params, const float* rope_freqs, float* grads, int grad_x_mode, void* workspace,
+                     int64_t workspace_bytes, int B, int RT, void* stream);
 
 /* Test hook: which launch takes each U-Net level in a pass over (B, RT) windows -- the plan unet_forward / unet_backward / the sampler's
  * prologue build for themselves (the same rules, evaluated by the same function), without a workspace, a launch or a device.
