@@ -62,10 +62,15 @@ int launch_cond_embed_bwd(const float* dc, const float* x_cond, const float* w, 
 int launch_time_features(const int64_t* t, const float* freqs, float* e, int B, int H, hipStream_t s);
 int launch_gelu(const float* x, float* y, int64_t n, hipStream_t s);
 int launch_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, hipStream_t s);  // dx = dy * gelu'(x)
-// y = x + r (saved, nullable r), out = LayerNorm(y) * g + b ; stats (rows, 2) = mean, rstd
+// The kernels a LayerNorm launch takes, forward and backward row pass alike: H <= 256 a wave per row with 4 registers per lane (REG4);
+// 256 < H <= 1024 a block per row on float4 (BLK) when `vec` (H % 4 == 0 and every row operand 16-byte aligned), else a wave per row with
+// 16 registers per lane (REG16); beyond 1024 a wave per row looping over memory (ROWS).
+enum LayerNormForm { LN_REG4 = 0, LN_REG16 = 1, LN_BLK = 2, LN_ROWS = 3 };
+int layernorm_form(int H, bool vec);
+// y = x + r (saved, nullable r), out = LayerNorm(y) * g + b ; stats (rows, 2) = mean, rstd (nullable)
 int launch_layernorm_fwd(const float* x, const float* r, const float* g, const float* b, float* y, float* out, float* stats, int rows, int H,
                          hipStream_t s);
-// dy (+)= d LayerNorm ; dg, db += ; scratch: 2 * H * LN_BWD_BLOCKS floats
+// dy = d LayerNorm (a plain store) ; dg, db (+)= ; scratch: 2 * H * LN_BWD_BLOCKS floats
 constexpr int LN_BWD_BLOCKS = 256;
 int launch_layernorm_bwd(const float* y, const float* stats, const float* g, const float* dout, float* dy, float* dg, float* db, float* scratch,
                          int rows, int H, hipStream_t s, int accumulate = 1);

@@ -446,3 +446,80 @@ int dq_tfm_bucket_info(const dq_tfm* p, int i, int64_t* offset, int64_t* count) 
 }
 
 }  // extern "C"
+
+// ---- the kernels between the GEMMs, one launcher each on tensors the caller chooses (exported for the parity tests: tests/test_tfm_kernels.py).
+// Thin: argument checks, then the launcher of dq_tfm.h that dq_tfm_fwd / dq_tfm_bwd call; nothing is allocated.
+extern "C" {
+
+int dq_tfm_layernorm_form(int H, int aligned16) { return H > 0 ? layernorm_form(H, H % 4 == 0 && aligned16 != 0) : -1; }
+
+int dq_tfm_rope_add(float* x, const float* sin_t, const float* cos_t, const float* temb, int B, int S, int H, int inverse, void* stream) {
+  DQ_REQUIRE(x && sin_t && cos_t, "dq_tfm_rope_add: null argument");
+  DQ_REQUIRE(B > 0 && S > 0 && H > 0 && H % 2 == 0, "dq_tfm_rope_add: B, S positive, H positive and even");
+  DQ_REQUIRE(((uintptr_t)x & 7) == 0, "dq_tfm_rope_add: x must be 8-byte aligned (channel pairs move as float2)");
+  return launch_rope_add(x, sin_t, cos_t, temb, B, S, H, inverse, (hipStream_t)stream);
+}
+int dq_tfm_cond_embed(const float* x_cond, const float* w, const float* bias, const float* sin_t, const float* cos_t, float* c, int B, int S,
+                      int H, void* stream) {
+  DQ_REQUIRE(x_cond && w && bias && sin_t && cos_t && c, "dq_tfm_cond_embed: null argument");
+  DQ_REQUIRE(B > 0 && S > 0 && H > 0 && H % 2 == 0, "dq_tfm_cond_embed: B, S positive, H positive and even");
+  DQ_REQUIRE(((uintptr_t)c & 7) == 0, "dq_tfm_cond_embed: c must be 8-byte aligned (channel pairs move as float2)");
+  return launch_cond_embed(x_cond, w, bias, sin_t, cos_t, c, B, S, H, (hipStream_t)stream);
+}
+int dq_tfm_cond_embed_bwd(const float* dc, const float* x_cond, const float* w, const float* sin_t, const float* cos_t, float* dw, float* db,
+                          float* dx_cond, float* scratch, int64_t scratch_floats, int B, int S, int H, int accumulate, void* stream) {
+  DQ_REQUIRE(dc && x_cond && w && sin_t && cos_t && dw && db && scratch, "dq_tfm_cond_embed_bwd: null argument");
+  DQ_REQUIRE(B > 0 && S > 0 && H > 0 && H % 2 == 0, "dq_tfm_cond_embed_bwd: B, S positive, H positive and even");
+  DQ_REQUIRE(((uintptr_t)dc & 7) == 0, "dq_tfm_cond_embed_bwd: dc must be 8-byte aligned (channel pairs move as float2)");
+  DQ_REQUIRE(scratch_floats >= (int64_t)2 * H * 64, "dq_tfm_cond_embed_bwd: scratch needs 2 * H * 64 floats");
+  return launch_cond_embed_bwd(dc, x_cond, w, sin_t, cos_t, dw, db, dx_cond, scratch, B, S, H, (hipStream_t)stream, accumulate ? 1 : 0);
+}
+int dq_tfm_time_features(const int64_t* t, const float* freqs, float* e, int B, int H, void* stream) {
+  DQ_REQUIRE(t && freqs && e, "dq_tfm_time_features: null argument");
+  DQ_REQUIRE(B > 0 && H > 0 && H % 2 == 0, "dq_tfm_time_features: B positive, H positive and even");
+  return launch_time_features(t, freqs, e, B, H, (hipStream_t)stream);
+}
+int dq_tfm_gelu(const float* x, float* y, int64_t n, void* stream) {
+  DQ_REQUIRE(x && y && n >= 0, "dq_tfm_gelu: null argument");
+  return launch_gelu(x, y, n, (hipStream_t)stream);
+}
+int dq_tfm_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream) {
+  DQ_REQUIRE(x && dy && dx && n >= 0, "dq_tfm_gelu_bwd: null argument");
+  return launch_gelu_bwd(x, dy, dx, n, (hipStream_t)stream);
+}
+int dq_tfm_layernorm_fwd(const float* x, const float* r, const float* g, const float* b, float* y, float* out, float* stats, int rows, int H,
+                         void* stream) {
+  DQ_REQUIRE(x && g && b && y && out, "dq_tfm_layernorm_fwd: null argument");
+  DQ_REQUIRE(rows > 0 && H > 0, "dq_tfm_layernorm_fwd: rows and H must be positive");
+  return launch_layernorm_fwd(x, r, g, b, y, out, stats, rows, H, (hipStream_t)stream);
+}
+int dq_tfm_layernorm_bwd(const float* y, const float* stats, const float* g, const float* dout, float* dy, float* dg, float* db, float* scratch,
+                         int64_t scratch_floats, int rows, int H, int accumulate, void* stream) {
+  DQ_REQUIRE(y && stats && g && dout && dy && dg && db && scratch, "dq_tfm_layernorm_bwd: null argument");
+  DQ_REQUIRE(rows > 0 && H > 0, "dq_tfm_layernorm_bwd: rows and H must be positive");
+  DQ_REQUIRE(scratch_floats >= (int64_t)2 * H * LN_BWD_BLOCKS, "dq_tfm_layernorm_bwd: scratch needs 2 * H * 256 floats");
+  return launch_layernorm_bwd(y, stats, g, dout, dy, dg, db, scratch, rows, H, (hipStream_t)stream, accumulate ? 1 : 0);
+}
+int dq_tfm_softmax_rows(float* p, int64_t rows, int n, int ld, float scale, void* stream) {
+  DQ_REQUIRE(p, "dq_tfm_softmax_rows: null argument");
+  DQ_REQUIRE(rows > 0 && n > 0 && ld >= n, "dq_tfm_softmax_rows: rows, n positive, ld >= n");
+  return launch_softmax_rows(p, rows, n, ld, scale, (hipStream_t)stream);
+}
+int dq_tfm_softmax_rows_bwd(const float* p, float* dp, int64_t rows, int n, int ld, float scale, void* stream) {
+  DQ_REQUIRE(p && dp, "dq_tfm_softmax_rows_bwd: null argument");
+  DQ_REQUIRE(rows > 0 && n > 0 && ld >= n, "dq_tfm_softmax_rows_bwd: rows, n positive, ld >= n");
+  return launch_softmax_rows_bwd(p, dp, rows, n, ld, scale, (hipStream_t)stream);
+}
+int dq_tfm_colsum(const float* x, int M, int N, int64_t ld, float* out, float* scratch, int64_t scratch_floats, int accumulate, void* stream) {
+  DQ_REQUIRE(x && out && scratch, "dq_tfm_colsum: null argument");
+  DQ_REQUIRE(M > 0 && N > 0 && ld >= N, "dq_tfm_colsum: M, N positive, ld >= N");
+  DQ_REQUIRE(scratch_floats >= (int64_t)COLSUM_BLOCKS * N, "dq_tfm_colsum: scratch needs 64 * N floats");
+  return launch_colsum(x, M, N, ld, out, scratch, (hipStream_t)stream, accumulate ? 1 : 0);
+}
+int dq_tfm_seqsum(const float* x, int B, int S, int N, float* out, void* stream) {
+  DQ_REQUIRE(x && out, "dq_tfm_seqsum: null argument");
+  DQ_REQUIRE(B > 0 && S > 0 && N > 0, "dq_tfm_seqsum: B, S, N must be positive");
+  return launch_seqsum(x, B, S, N, out, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -404,14 +404,21 @@ int launch_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, hipSt
   DQ_LAUNCH_CHECK();
   return 0;
 }
+int layernorm_form(int H, bool vec) {
+  if (H <= 256) return LN_REG4;
+  if (H <= 1024) return vec ? LN_BLK : LN_REG16;
+  return LN_ROWS;
+}
 int launch_layernorm_fwd(const float* x, const float* r, const float* g, const float* b, float* y, float* out, float* stats, int rows, int H,
                          hipStream_t s) {
   if (rows == 0) return 0;
   const bool vec = H % 4 == 0 && ((((uintptr_t)x | (uintptr_t)r | (uintptr_t)g | (uintptr_t)b | (uintptr_t)y | (uintptr_t)out) & 15) == 0);
-  if (vec && H > 256 && H <= 1024) hipLaunchKernelGGL(k_layernorm_fwd_blk, dim3(rows), dim3(256), 0, s, x, r, g, b, y, out, stats, H);
-  else if (H <= 256) hipLaunchKernelGGL(k_layernorm_fwd_reg<4>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, r, g, b, y, out, stats, rows, H);
-  else if (H <= 1024) hipLaunchKernelGGL(k_layernorm_fwd_reg<16>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, r, g, b, y, out, stats, rows, H);
-  else hipLaunchKernelGGL(k_layernorm_fwd, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, r, g, b, y, out, stats, rows, H);
+  switch (layernorm_form(H, vec)) {
+    case LN_BLK: hipLaunchKernelGGL(k_layernorm_fwd_blk, dim3(rows), dim3(256), 0, s, x, r, g, b, y, out, stats, H); break;
+    case LN_REG4: hipLaunchKernelGGL(k_layernorm_fwd_reg<4>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, r, g, b, y, out, stats, rows, H); break;
+    case LN_REG16: hipLaunchKernelGGL(k_layernorm_fwd_reg<16>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, r, g, b, y, out, stats, rows, H); break;
+    default: hipLaunchKernelGGL(k_layernorm_fwd, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, r, g, b, y, out, stats, rows, H); break;
+  }
   DQ_LAUNCH_CHECK();
   return 0;
 }
@@ -419,10 +426,12 @@ int launch_layernorm_bwd(const float* y, const float* stats, const float* g, con
                          int rows, int H, hipStream_t s, int accumulate) {
   if (rows == 0) return 0;
   const bool vec = H % 4 == 0 && ((((uintptr_t)y | (uintptr_t)g | (uintptr_t)dout | (uintptr_t)dy) & 15) == 0);
-  if (vec && H > 256 && H <= 1024) hipLaunchKernelGGL(k_layernorm_bwd_rows_blk, dim3(rows), dim3(256), 0, s, y, stats, g, dout, dy, H);
-  else if (H <= 256) hipLaunchKernelGGL(k_layernorm_bwd_rows_reg<4>, dim3(cdiv(rows, 4)), dim3(256), 0, s, y, stats, g, dout, dy, rows, H);
-  else if (H <= 1024) hipLaunchKernelGGL(k_layernorm_bwd_rows_reg<16>, dim3(cdiv(rows, 4)), dim3(256), 0, s, y, stats, g, dout, dy, rows, H);
-  else hipLaunchKernelGGL(k_layernorm_bwd_rows, dim3(cdiv(rows, 4)), dim3(256), 0, s, y, stats, g, dout, dy, rows, H);
+  switch (layernorm_form(H, vec)) {
+    case LN_BLK: hipLaunchKernelGGL(k_layernorm_bwd_rows_blk, dim3(rows), dim3(256), 0, s, y, stats, g, dout, dy, H); break;
+    case LN_REG4: hipLaunchKernelGGL(k_layernorm_bwd_rows_reg<4>, dim3(cdiv(rows, 4)), dim3(256), 0, s, y, stats, g, dout, dy, rows, H); break;
+    case LN_REG16: hipLaunchKernelGGL(k_layernorm_bwd_rows_reg<16>, dim3(cdiv(rows, 4)), dim3(256), 0, s, y, stats, g, dout, dy, rows, H); break;
+    default: hipLaunchKernelGGL(k_layernorm_bwd_rows, dim3(cdiv(rows, 4)), dim3(256), 0, s, y, stats, g, dout, dy, rows, H); break;
+  }
   const int nb = std::min(rows, LN_BWD_BLOCKS);
   hipLaunchKernelGGL(k_layernorm_bwd_cols, dim3(cdiv(H, 256), nb), dim3(256), 0, s, y, stats, dout, scratch, rows, H);
   if (db == dg + H) {  // gain and bias adjacent (the flat parameter layout): the [dg | db] partial rows reduce in one launch

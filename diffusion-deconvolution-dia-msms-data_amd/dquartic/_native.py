@@ -117,6 +117,19 @@ PROTOTYPES = {
     "dq_tfm_num_buckets": (c_int, [c_void_p]),
     "dq_tfm_bucket_info": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "dq_tfm_set_precision": (c_int, [c_void_p, c_int]),
+    "dq_tfm_layernorm_form": (c_int, [c_int, c_int]),
+    "dq_tfm_rope_add": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
+    "dq_tfm_cond_embed": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
+    "dq_tfm_cond_embed_bwd": (c_int, [c_void_p] * 9 + [c_int64] + [c_int] * 4 + [c_void_p]),
+    "dq_tfm_time_features": (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p]),
+    "dq_tfm_gelu": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "dq_tfm_gelu_bwd": (c_int, [c_void_p] * 3 + [c_int64, c_void_p]),
+    "dq_tfm_layernorm_fwd": (c_int, [c_void_p] * 7 + [c_int, c_int, c_void_p]),
+    "dq_tfm_layernorm_bwd": (c_int, [c_void_p] * 8 + [c_int64] + [c_int] * 3 + [c_void_p]),
+    "dq_tfm_softmax_rows": (c_int, [c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
+    "dq_tfm_softmax_rows_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
+    "dq_tfm_colsum": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "dq_tfm_seqsum": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p, c_void_p]),
     "dq_linattn_fwd": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_void_p]),
     "dq_linattn_bwd": (c_int, [c_void_p] * 15 + [c_int, c_int, c_int, c_void_p]),
     "dq_linattn_bwd_store": (c_int, [c_void_p] * 15 + [c_int, c_int, c_int, c_void_p]),

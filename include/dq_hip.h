@@ -50,7 +50,9 @@ const char* dq_last_error(void);
  * dq_conv_bwd_workspace_floats, dq_conv_bwd_forms (later, additive: dq_adamw_clip_ema_step, dq_adamw_clip_ema_step_dev; dq_randn,
  * dq_ddim_step_sto, dq_ddim_coef_table, dq_ddim_sample_ex).  12: dq_debug_level_plan (later, additive: dq_gemm_ex,
  * dq_debug_gemm_plan; DQ_SAMPLER_*, dq_sampler_coef_table, dq_solver_step, dq_ddim_sample_solver; dq_debug_layout, dq_debug_mid_forms,
- * dq_debug_mid_fwd, dq_debug_mid_bwd). */
+ * dq_debug_mid_fwd, dq_debug_mid_bwd; dq_tfm_layernorm_form and the stand-alone kernels of the transformer: dq_tfm_rope_add,
+ * dq_tfm_cond_embed, dq_tfm_cond_embed_bwd, dq_tfm_time_features, dq_tfm_gelu, dq_tfm_gelu_bwd, dq_tfm_layernorm_fwd,
+ * dq_tfm_layernorm_bwd, dq_tfm_softmax_rows, dq_tfm_softmax_rows_bwd, dq_tfm_colsum, dq_tfm_seqsum). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -397,6 +399,44 @@ int dq_tfm_bucket_info(const dq_tfm* tfm, int i, int64_t* offset, int64_t* count
  * faster mode with its own stated tolerance, never the default. */
 enum { DQ_PRECISION_FP32 = 0, DQ_PRECISION_BF16X3 = 1 };
 int dq_tfm_set_precision(dq_tfm* tfm, int precision);
+/* The kernels between the transformer's GEMMs (csrc/k_tfm.hip), one launcher each on tensors the caller chooses (additive at ABI
+ * version 12; exported for the parity tests).  Asynchronous on `stream`, nothing is allocated; null operands, non-positive sizes, an odd H
+ * where channel pairs are rotated and a short scratch are refused with an error.  All tensors fp32 and contiguous unless a stride is given.
+ *   rope_add:       x (B, S, H) in place: adjacent channel pairs rotated by the tables sin / cos (S, H/2), then += temb[b] (B, H; nullable);
+ *                   inverse != 0: the transposed rotation (the gradient), temb ignored.  x 8-byte aligned.
+ *   cond_embed:     c (B, S, H) = rope(x_cond[b][s] * w + bias), w and bias (H); its backward from dc (B, S, H): dw, db (H each) and
+ *                   dx_cond (B, S; nullable, a plain store).  scratch: 2 * H * 64 floats.  c and dc 8-byte aligned.
+ *   time_features:  e (B, H) = [sin(t_b f) | cos(t_b f)], t (B) int64, f (H/2), the product t_b f formed in fp32.
+ *   gelu:           y = x Phi(x) (exact erf form); gelu_bwd: dx = dy * gelu'(x), dx may be dy itself.
+ *   layernorm_fwd:  y = x + r (r nullable), out = (y - mean) * rstd * g + b over rows of H (biased variance, eps 1e-5 inside the root),
+ *                   stats (rows, 2) = mean, rstd (nullable).  layernorm_bwd: dy (rows, H) a plain store; dg, db (H each) from y, stats and
+ *                   dout.  scratch: 2 * H * 256 floats.  dq_tfm_layernorm_form: which kernels both take for rows of H floats whose row
+ *                   operands are (aligned16 != 0) or are not all 16-byte aligned -- forward: x, r, g, b, y, out; backward: y, g, dout, dy.
+ *   softmax_rows:   rows of n floats at stride ld, in place: p = softmax(scale * p); columns n .. ld-1 are neither read nor written.
+ *                   softmax_rows_bwd: dp = p * (dp - sum(p dp)) * scale in place of dp.
+ *   colsum:         out[n] = sum over m < M of x[m * ld + n]; scratch: 64 * N floats.  seqsum: out (B, N) = sum over s of x (B, S, N).
+ * accumulate != 0: `+=` into dw / db, dg / db, out; 0: plain stores. */
+enum { DQ_LN_REG4 = 0, DQ_LN_REG16 = 1, DQ_LN_BLK = 2, DQ_LN_ROWS = 3 };
+int dq_tfm_layernorm_form(int H, int aligned16);
+int dq_tfm_rope_add(float* x, const float* rope_sin, const float* rope_cos, const float* temb, int B, int S, int H, int inverse,
+                    void* stream);
+int dq_tfm_cond_embed(const float* x_cond, const float* w, const float* bias, const float* rope_sin, const float* rope_cos, float* c,
+                      int B, int S, int H, void* stream);
+int dq_tfm_cond_embed_bwd(const float* dc, const float* x_cond, const float* w, const float* rope_sin, const float* rope_cos, float* dw,
+                          float* db, float* dx_cond, float* scratch, int64_t scratch_floats, int B, int S, int H, int accumulate,
+                          void* stream);
+int dq_tfm_time_features(const int64_t* t, const float* freqs, float* e, int B, int H, void* stream);
+int dq_tfm_gelu(const float* x, float* y, int64_t n, void* stream);
+int dq_tfm_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream);
+int dq_tfm_layernorm_fwd(const float* x, const float* r, const float* g, const float* b, float* y, float* out, float* stats, int rows,
+                         int H, void* stream);
+int dq_tfm_layernorm_bwd(const float* y, const float* stats, const float* g, const float* dout, float* dy, float* dg, float* db,
+                         float* scratch, int64_t scratch_floats, int rows, int H, int accumulate, void* stream);
+int dq_tfm_softmax_rows(float* p, int64_t rows, int n, int ld, float scale, void* stream);
+int dq_tfm_softmax_rows_bwd(const float* p, float* dp, int64_t rows, int n, int ld, float scale, void* stream);
+int dq_tfm_colsum(const float* x, int M, int N, int64_t ld, float* out, float* scratch, int64_t scratch_floats, int accumulate,
+                  void* stream);
+int dq_tfm_seqsum(const float* x, int B, int S, int N, float* out, void* stream);
 /* The fp32 matrix-core GEMM underneath (exported for the parity tests and the roofline measurement):
  * C (M,N; ldc) = A B (+ bias[n]) with A(m,k) = a_kmajor ? A[m*lda+k] : A[k*lda+m] and B(k,n) = b_kmajor ? B[n*ldb+k] :
  * B[k*ldb+n]; splits = 0 lets the library choose a split-K factor; scratch: dq_gemm_scratch_floats(M,N,K) floats. */
