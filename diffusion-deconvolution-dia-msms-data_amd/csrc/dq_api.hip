@@ -1,17 +1,41 @@
-// The C ABI (include/dq_hip.h) but the samplers (dq_sampler.hip, dq_sampler_tables.cpp) and the entry points that need the network file's
-// private types (dq_unet.hip): errors, plan lifetime and queries, options, the thin wrappers of the stream kernels, and the network passes --
-// forward, backward, the fused train step and the evaluation step.
+// The C ABI (include/dq_hip.h) but the samplers (dq_sampler.hip, dq_sampler_tables.cpp), the stand-alone op entry points (dq_ops_api.hip) and
+// the debug entry points that need the network file's private types (dq_unet.hip): errors and the occupancy cache, plan lifetime and queries,
+// options, the thin wrappers of the stream kernels, and the network passes -- forward, backward, the fused train step and the evaluation step.
 #include "dq_dev.h"
 #include "dq_net.h"
 #include "dq_options.h"
 #include "../../include/dq_hip.h"
 
+#include <algorithm>
 #include <cstring>
+#include <mutex>
 #include <string>
+#include <vector>
 
 namespace dq {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
+
+int occ_blocks_per_cu(const void* fn, int threads, size_t lds) {
+  struct Key { const void* fn; size_t lds; int threads, dev; };
+  struct Ent { Key k; int nb; };
+  static std::mutex mu;
+  static std::vector<Ent> cache;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { set_error("occ_blocks_per_cu: hipGetDevice failed"); return -1; }
+  std::lock_guard<std::mutex> lock(mu);
+  for (const Ent& e : cache)
+    if (e.k.fn == fn && e.k.lds == lds && e.k.threads == threads && e.k.dev == dev) return e.nb;
+  if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    set_error("occ_blocks_per_cu: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    return -1;
+  }
+  int nb = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, threads, lds);
+  if (e != hipSuccess) { set_error(std::string("hipOccupancyMaxActiveBlocksPerMultiprocessor failed: ") + hipGetErrorString(e)); return -1; }
+  cache.push_back({{fn, lds, threads, dev}, std::max(1, nb)});
+  return std::max(1, nb);
+}
 }  // namespace dq
 
 using namespace dq;

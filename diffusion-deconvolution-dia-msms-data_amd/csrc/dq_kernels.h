@@ -186,7 +186,7 @@ struct ResBwd {
   int C = 0, rows = 0, n = 0, rows_per_sample = 1;
 };
 // Which ResnetBlock kernel runs (in order of preference).  Forward: k_res_rt.hip, a one-block k_level_fwd launch (LEVEL), k_res_v4.hip or the
-// conv launches of dq_unet.hip (UNFUSED).  Backward: k_res_{wg,rt,rows,cp}.hip, k_res.hip (PLAIN) or UNFUSED; wg: the block's buffers were
+// conv launches of dq_ops.hip (UNFUSED).  Backward: k_res_{wg,rt,rows,cp}.hip, k_res.hip (PLAIN) or UNFUSED; wg: the block's buffers were
 // laid out for k_res_bwd_wg (ResBuf::wpart_floats != 0).
 enum ResFwdForm { RES_FWD_RT, RES_FWD_LEVEL, RES_FWD_V4, RES_FWD_UNFUSED };
 ResFwdForm res_fwd_form(int C, int cinA, int cinB, bool has_wr, int rows, int n, int rows_per_sample);
@@ -488,7 +488,6 @@ struct LinAttnBwd {
   // launch reduced them itself: the long-row path); the caller sums them later with launch_linattn_dw_reduce_multi, and then
   // part_floats only needs la_part_reserve(C)
   int defer_reduce = 0; int* waves_out = nullptr;
-  float** w2sum_out = nullptr;  // deferred: receives the address of the 4 C C floats (inside `part`) the reduce leaves the summed dW2 in
   float* dw_qkv = nullptr; float* dw_out = nullptr; float* db_out = nullptr; float* dg_pre = nullptr; float* dg_out = nullptr;
 };
 // rows of 128 / 256 positions (k_la_long.hip)
@@ -507,6 +506,15 @@ struct LaReduceItem {
   const float* part; int nslots, C; float* dw_qkv; float* dw_out; float* dg_out; float* db_out; float* dg_pre;
   float* w2sum; const float* w_qkv; const float* w_out;
 };
+// floats of one partial slot of a LinearAttention backward (k_la_bwd.hip, k_la_rows_bwd.hip, k_tiny.hip; a slot per workgroup or per wave):
+// dWq | dWk (256 C) | dW2 of the four heads (4 C C) | d g_out | d b_out | d g_pre; la_slot_gains: where the three gain / bias sums start
+constexpr int la_slot_gains(int C) { return 256 * C + 4 * C * C; }
+constexpr int la_slot(int C) { return la_slot_gains(C) + 3 * C; }
+// the reduce item of a launch that left `slots` slots at `part`: the summed-dW2 scratch lies right behind them
+inline LaReduceItem la_reduce_item(float* part, int slots, int C, float* dw_qkv, float* dw_out, float* dg_out, float* db_out, float* dg_pre,
+                                   const float* w_qkv, const float* w_out) {
+  return LaReduceItem{part, slots, C, dw_qkv, dw_out, dg_out, db_out, dg_pre, part + (int64_t)slots * la_slot(C), w_qkv, w_out};
+}
 constexpr int LA_REDUCE_MAX = 16;
 int64_t la_part_reserve(int C);  // floats of slot scratch one deferred launch with C channels can use
 int launch_linattn_dw_reduce_multi(const LaReduceItem* items, int count, hipStream_t s);

@@ -65,7 +65,7 @@ struct LinAttnBwdK {
   const float* x; const float* ypre; const float* dy;  // (rows, C, n): block input, saved pre-norm output, d loss / d y
   float* dx;                                            // += d loss / d x (incl. the residual)
   const float* w_qkv; const float* w_out; const float* g_pre; const float* g_out;
-  float* part;  // partial slots (per block; per wave for rows of one position): [slot][la_slot(C)] = dWq | dWk (256 C) | dW2 per head (4 C C) | d g_out | d b_out | d g_pre
+  float* part;  // partial slots (per block; per wave for rows of one position): [slot][la_slot(C)] (dq_kernels.h)
   int rows; int units_per_wave;  // units per BLOCK in k_linattn_bwd (its four waves share them), per wave in k_linattn_bwd1
   const float* prep;  // nullable: this layer's LA_PREP_FLOATS prepared by launch_linattn_prepare (W2 = 4 C C floats, the bounded-logit flag)
   int dx_store;       // dx is written, not accumulated into (its old contents are not read)
@@ -78,7 +78,6 @@ struct LinAttnBwdK {
 #else
 #define DQ_STAMP(i) do {} while (0)
 #endif
-constexpr int la_slot(int C) { return 256 * C + 4 * C * C + 3 * C; }  // dWq | dWk (256 C) | dW2 of the four heads (4 C C) | d g_out | d b_out | d g_pre
 
 // v_mfma_f32_4x4x1_16b_f32: 16 independent 4x4 outer products.  Block = lane >> 2; a lane supplies A_blk[i = lane & 3] and
 // B_blk[j = lane & 3]; register i of lane (blk, j) receives A_blk[i] * B_blk[j] (mapping measured: tools/probe/mfma4x4.hip).
@@ -968,7 +967,7 @@ __global__ void __launch_bounds__(256, (DQ_LA_4_3W && C == 4 && N == 64) ? 3 : (
     wfence();
     DQ_STAMP(11);
     for (int i = lane; i < C * C; i += 64) slot[256 * C + hd * C * C + i] = w2g[i];
-    constexpr int GB = 256 * C + 4 * C * C;  // [d g_out | d b_out | d g_pre]
+    constexpr int GB = la_slot_gains(C);  // [d g_out | d b_out | d g_pre]
     if (first || last) {  // norm gains / bias: sum over the 32 positions-lanes of this half, one lane stores
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
@@ -1174,7 +1173,7 @@ __global__ void __launch_bounds__(256) k_linattn_bwd1(LinAttnBwdK a) {
 #pragma unroll
     for (int hd = 0; hd < 4; ++hd) slot[256 * C + hd * C * C + i] = v;
   }
-  constexpr int GB = 256 * C + 4 * C * C;  // [d g_out | d b_out | d g_pre]
+  constexpr int GB = la_slot_gains(C);  // [d g_out | d b_out | d g_pre]
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int c = la_chan(C, j, half);
@@ -1364,11 +1363,9 @@ static int linattn_bwd_n(const LinAttnBwdK& k, int n, const LinAttnBwd& g, hipSt
   /* (4 C C floats behind the slots hold the summed dW2 between the reduce and k_linattn_dwvo) */
   if (g.defer_reduce) {
     *g.waves_out = slots;
-    if (g.w2sum_out) *g.w2sum_out = kk.part + (int64_t)slots * la_slot(C);
     return 0;
   }
-  const LaReduceItem it{kk.part, slots, C, g.dw_qkv, g.dw_out, g.dg_out, g.db_out, g.dg_pre, kk.part + (int64_t)slots * la_slot(C),
-                        k.w_qkv, k.w_out};
+  const LaReduceItem it = la_reduce_item(kk.part, slots, C, g.dw_qkv, g.dw_out, g.dg_out, g.db_out, g.dg_pre, k.w_qkv, k.w_out);
   return launch_linattn_dw_reduce_multi(&it, 1, s);
 }
 
@@ -1449,10 +1446,9 @@ int launch_linattn_bwd(const LinAttnBwd& a, hipStream_t s) {
     if (int rc = launch_la_rows_bwd(a, slots_max, &slots, s)) return rc;
     if (a.defer_reduce) {
       *a.waves_out = slots;
-      if (a.w2sum_out) *a.w2sum_out = a.part + (int64_t)slots * la_slot(C);
       return 0;
     }
-    const LaReduceItem it{a.part, slots, C, a.dw_qkv, a.dw_out, a.dg_out, a.db_out, a.dg_pre, a.part + (int64_t)slots * la_slot(C), a.f.w_qkv, a.f.w_out};
+    const LaReduceItem it = la_reduce_item(a.part, slots, C, a.dw_qkv, a.dw_out, a.dg_out, a.db_out, a.dg_pre, a.f.w_qkv, a.f.w_out);
     return launch_linattn_dw_reduce_multi(&it, 1, s);
   }
   LinAttnBwdK k;

@@ -72,11 +72,9 @@ __device__ __forceinline__ float row16_sum(float v) {
 struct LaRowsBwdK {
   const float* x; const float* ypre; const float* dy; float* dx;
   const float* prep; const float* g_pre; const float* g_out;
-  float* part;  // one slot per workgroup, layout la_slot(C) of k_la_bwd.hip
+  float* part;  // one slot per workgroup, layout la_slot(C) of dq_kernels.h
   int rows, ntiles, dx_store;
 };
-
-constexpr int la_slot_floats(int C) { return 256 * C + 4 * C * C + 3 * C; }
 
 // A workgroup = four waves = the FOUR HEADS of the same 16-row tiles (as in k_la_bwd.hip): a wave keeps its head's 36 operand values per
 // lane and its head's weight-gradient accumulators in registers for the whole launch; the four d xh contributions meet in LDS behind one
@@ -500,7 +498,7 @@ __global__ void __launch_bounds__(256, 2) k_la_rows_bwd(LaRowsBwdK a) {
   DQ_PSTAMP((500000 + C * 100 + N), 9);
   // ---- flush: one slot per workgroup, layout la_slot(C) = dWq | dWk (256 C) | dW2 of the four heads (4 C C) | d g_out | d b_out | d g_pre;
   // each wave its head's sections
-  float* slot = a.part + (int64_t)blockIdx.x * la_slot_floats(C);
+  float* slot = a.part + (int64_t)blockIdx.x * la_slot(C);
   if (row < C) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -519,7 +517,7 @@ __global__ void __launch_bounds__(256, 2) k_la_rows_bwd(LaRowsBwdK a) {
       if (cp < C && c >= 0) slot[256 * C + hd * C * C + cp * C + c] = gw[r];
     }
   }
-  constexpr int GB = 256 * C + 4 * C * C;
+  constexpr int GB = la_slot_gains(C);
   if (hd == 0 || hd == 3) {
 #pragma unroll
     for (int r = 0; r < CPL; ++r) {

@@ -6,7 +6,7 @@
 // because a sample IS one row (its RT axis, up to 512 positions) and gets one block of 256 / 512 threads.  Weight gradients stay in
 // k_conv_wgrad (they read dU1 / dU2 written here).
 // res_fwd_form / res_bwd_form below choose between this kernel, the specialised ones of k_res_*.hip and k_level.hip, and the unfused
-// path of dq_unet.hip.
+// path of dq_ops.hip.
 #include "dq_common.h"
 #include "dq_kernels.h"
 #include "k_res_common.h"

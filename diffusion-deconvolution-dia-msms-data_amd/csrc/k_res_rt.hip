@@ -478,7 +478,7 @@ __global__ void __launch_bounds__(256) k_res_rt_bwd(ResBwd a, ResRtPre q, ResRtO
   }
 }
 
-// tiles per wave so that a sample has at most 64 workgroups (the gpart slot count the arena reserves per sample, dq_unet.hip)
+// tiles per wave so that a sample has at most 64 workgroups (the gpart slot count the arena reserves per sample: layout_res, dq_ops.h)
 int rt_tiles_per_wave(int n, int own) { return std::max(1, cdiv(n, 4 * own * 64)); }
 
 }  // namespace

@@ -457,7 +457,6 @@ struct TinyBwdK {
   TinyBwdBlkK blk[2];                                  // [0] = ResnetBlock 0, [1] = ResnetBlock 1
   int rows_per_sample, ss_stride;
 };
-constexpr int tiny_la_slot(int C) { return 256 * C + 4 * C * C + 3 * C; }  // = la_slot(C) of k_la_bwd.hip
 
 // UPT: the Upsample conv behind the level (its backward data path in front of everything else)
 template <int C, int PRE, int CP, int CS, bool UPT>
@@ -741,7 +740,7 @@ __global__ void __launch_bounds__(256) k_tiny_bwd(TinyBwdK a, const float* __res
   }
   __syncthreads();
   const int wg = blockIdx.y * gridDim.x + blockIdx.x;
-  float* slot = a.la_part + (int64_t)wg * tiny_la_slot(C);
+  float* slot = a.la_part + (int64_t)wg * la_slot(C);
   for (int i = threadIdx.x; i < 256 * C; i += 256) slot[i] = 0.f;  // d Wq | d Wk
   for (int i = threadIdx.x; i < NACC + C * C; i += 256) {
     float v = 0.f;
@@ -752,7 +751,7 @@ __global__ void __launch_bounds__(256) k_tiny_bwd(TinyBwdK a, const float* __res
       const int e = i - NACC;
       v = (w2c[e] + w2c[C * C + e]) + (w2c[2 * C * C + e] + w2c[3 * C * C + e]);
     }
-    if (i < 3 * C) slot[256 * C + 4 * C * C + i] = v;                                   // d g_out | d b_out | d g_pre
+    if (i < 3 * C) slot[la_slot_gains(C) + i] = v;                                   // d g_out | d b_out | d g_pre
     else if (i < NACC) {
       const int bi = (i - 3 * C) / (4 * C), e = (i - 3 * C) % (4 * C), what = e / C, c = e % C;
       // order per block: d g2 | d g1 | d scale | d shift  == ResBwd::gpart order
@@ -1000,7 +999,7 @@ int launch_tiny_bwd(const TinyBwd& t, hipStream_t s) {
   k.rows_per_sample = t.rows_per_sample; k.dup = t.dup;
   const float* ssb = t.blk[0].ss;
   k.ss_stride = t.blk[0].ss_stride;
-  DQ_REQUIRE(t.la_part_floats >= (int64_t)gx * B * tiny_la_slot(C) + 4 * C * C, "tiny_bwd: LinearAttention slot region too small");
+  DQ_REQUIRE(t.la_part_floats >= (int64_t)gx * B * la_slot(C) + 4 * C * C, "tiny_bwd: LinearAttention slot region too small");
   for (int b = 0; b < 2; ++b) {
     const TinyBwd::Blk& r = t.blk[b];
     DQ_REQUIRE(r.w1 && r.w2 && r.g1 && r.g2 && r.ss && r.u1 && r.u2 && r.du1 && r.du2 && r.gpart && (t.cs == 0 || r.wr), "tiny_bwd: missing block operand");

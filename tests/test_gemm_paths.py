@@ -265,7 +265,7 @@ def test_attention_products(N, which):
 @pytest.mark.parametrize("Bsz", [1, 3])
 @pytest.mark.parametrize("RT", [33, 413])
 def test_wide_gemm_pattern(N, RT, Bsz, a_layout):
-    """dq_unet.hip: wide_gemm -- a shared weight (sAo = 0) against (Bsz, rows, P) tensors, N = RT < P = RT rounded up to 4."""
+    """dq_ops.hip: wide_gemm -- a shared weight (sAo = 0) against (Bsz, rows, P) tensors, N = RT < P = RT rounded up to 4."""
     M, K, P = 40, 120, up4(RT)
     p = Product(M, RT, K, a_layout + "n", sA=(0, 0), ldb=P, sB=(K * P, 0), ldc=P, sC=(M * P, 0), batch=Bsz)
     d = Data(p, seed=RT + Bsz)
@@ -281,7 +281,7 @@ def test_wide_gemm_pattern(N, RT, Bsz, a_layout):
 @pytest.mark.parametrize("Bsz", [1, 3])
 @pytest.mark.parametrize("RT", [31, 33, 413])
 def test_wide_wgrad_pattern(N, RT, Bsz, MN):
-    """dq_unet.hip: wide_wgrad -- dW (M, N) += sum over the samples of dY_b (M, RT) X_b^T, both k-major (Bsz, ., P) tensors, K = RT any length."""
+    """dq_ops.hip: wide_wgrad -- dW (M, N) += sum over the samples of dY_b (M, RT) X_b^T, both k-major (Bsz, ., P) tensors, K = RT any length."""
     M, Nn = MN
     P = up4(RT)
     p = Product(M, Nn, RT, "kk", lda=P, ldb=P, ldc=Nn, kbatch=Bsz, sAk=M * P, sBk=Nn * P)
