@@ -2,6 +2,7 @@
 // network forward of dq_unet.hip (dq_net.h) with one of four updates in or behind its head launch, over the tables of dq_sampler_tables.cpp.
 #include "dq_net.h"
 #include "dq_options.h"
+#include "dq_sampler.h"
 #include "dq_sampler_tables.h"
 #include "../../include/dq_hip.h"
 
@@ -10,26 +11,8 @@
 
 using namespace dq;
 
-namespace {
+namespace dq {
 
-// What every step's update of one sampling call shares: the tables (extra: sigma per row, or the solver's c1), the x0 history of the 2M
-// solver (updated in place), the clamp (0: off) and the shape
-struct StepUpdateArgs {
-  StepUpdate kind;
-  const float* coef; const float* extra;
-  float* hist;
-  float clip;
-  int px0, B;
-  int64_t per;
-};
-
-// The noise of the stochastic update: the windows' ids and the seed (device memory) and the draw index (the kernel adds the step counter)
-struct StepNoise { const int64_t* ids; const uint64_t* seed; int draw; };
-
-// The update of one step behind the network forward: x_out from x and the network output.  The row is `row` of the tables (the eager loop)
-// or, with step_ptr, the one the device-side step counter names (the captured step: row 0).  eps_out (nullable): where the step's eps goes
-// when it is not the network output itself; fused: the deterministic update went with the head launch (StepIO::fused_update), nothing is
-// left to do.
 int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net_out, float* x_out, float* eps_out, int row, const int* step_ptr,
                        const StepNoise& z, bool fused, hipStream_t s) {
   const float* coef = u.coef + 4 * row;
@@ -47,7 +30,57 @@ int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net
   return 0;
 }
 
-}  // namespace
+int sampler_check(const char* who, bool args_ok, float eta, int sampler, float clip_x0, const int32_t* timesteps_host, int num_steps,
+                  bool have_seed, bool have_xT, int pred_type, SamplerChoice* out) {
+  const std::string w(who);
+  DQ_REQUIRE(args_ok, w + ": null argument");
+  DQ_REQUIRE(eta >= 0.f && eta <= 1.f, w + ": eta must satisfy 0 <= eta <= 1");  // (false for NaN)
+  const bool sto = eta > 0.f;  // the update draws noise
+  // step-consistent samplers (DESIGN.md section 26): refused here, before anything touches the device
+  DQ_REQUIRE(sampler == DQ_SAMPLER_REFERENCE || sampler == DQ_SAMPLER_DDIM || sampler == DQ_SAMPLER_DPMPP_2M, w + ": unknown sampler");
+  const bool clip = clip_x0 > 0.f;  // (<= 0 and NaN: off)
+  DQ_REQUIRE(sampler != DQ_SAMPLER_DPMPP_2M || !sto, w + ": DPM-Solver++(2M) is deterministic: eta must be 0");
+  DQ_REQUIRE(!clip || sampler != DQ_SAMPLER_REFERENCE, w + ": clip_x0 needs the ddim or dpmpp_2m sampler");
+  DQ_REQUIRE(!clip || !sto, w + ": clip_x0 needs eta == 0");
+  if (sampler != DQ_SAMPLER_REFERENCE && num_steps <= 1024)  // (a step count out of range is the caller's refusal: its list is not read)
+    for (int i = 1; i < num_steps; ++i)
+      DQ_REQUIRE(timesteps_host[i] < timesteps_host[i - 1], w + ": the timesteps of this sampler must be strictly decreasing");
+  // the update: k_solver_step behind the forward (2M, or a clamped x0 at first order); else the reference's kernels over this sampler's table
+  out->kind = sampler == DQ_SAMPLER_DPMPP_2M ? StepUpdate::SOLVER_2M : clip ? StepUpdate::SOLVER_1 : sto ? StepUpdate::STOCHASTIC : StepUpdate::DDIM;
+  out->sto = sto; out->clip = clip; out->clip_x0 = clip ? clip_x0 : 0.f;
+  DQ_REQUIRE(have_seed || (have_xT && !sto), w + ": eta > 0 and a null x_T need the seed (device memory)");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, w + ": Unknown pred_type");
+  out->px0 = pred_type == DQ_PRED_X0;
+  return 0;
+}
+
+int sampler_upload_tables(const char* who, const float* alpha_bars_host, int T, const int32_t* ts, int num_steps, int sampler, const SamplerChoice& c,
+                          float eta, float* coef_dev, float* extra_dev, hipStream_t s) {
+  // coefficient table, fp32 like the reference, and sigma (eta > 0) or c1 (the solver) per step
+  std::vector<float> coef(4 * (size_t)num_steps), extra((size_t)num_steps);
+  if (sampler == DQ_SAMPLER_REFERENCE) DQ_TRY(dq_ddim_coef_table(alpha_bars_host, T, ts, num_steps, eta, coef.data(), extra.data()));
+  else DQ_TRY(sampler_rows(alpha_bars_host, T, ts, num_steps, c.kind == StepUpdate::SOLVER_1 ? SOLVER_ORDER1 : sampler, eta, coef.data(), extra.data(), who));
+  DQ_HIP_OK(hipMemcpyAsync(coef_dev, coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice, s));
+  if (extra_dev) DQ_HIP_OK(hipMemcpyAsync(extra_dev, extra.data(), sizeof(float) * extra.size(), hipMemcpyHostToDevice, s));
+  // the host vector must outlive the copy: pageable H2D copies are staged synchronously by the runtime, but make it explicit
+  DQ_HIP_OK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int sampler_stage_noise(uint64_t* seed_stage, int64_t* ids_stage, const uint64_t* seed_dev, const int64_t* window_ids_dev, int B, hipStream_t s) {
+  DQ_HIP_OK(hipMemcpyAsync(seed_stage, seed_dev, sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+  if (window_ids_dev) {
+    DQ_HIP_OK(hipMemcpyAsync(ids_stage, window_ids_dev, sizeof(int64_t) * B, hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  std::vector<int64_t> iota((size_t)B);
+  for (int b = 0; b < B; ++b) iota[b] = b;
+  DQ_HIP_OK(hipMemcpyAsync(ids_stage, iota.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, s));
+  DQ_HIP_OK(hipStreamSynchronize(s));  // (the vector is this function's own)
+  return 0;
+}
+
+}  // namespace dq
 
 extern "C" {
 
@@ -107,27 +140,15 @@ int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_
                       const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
                       int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
                       const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0) {
-  DQ_REQUIRE(plan && params && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
-             "dq_ddim_sample: null argument");
-  DQ_REQUIRE(eta >= 0.f && eta <= 1.f, "dq_ddim_sample: eta must satisfy 0 <= eta <= 1");  // (false for NaN)
-  const bool sto = eta > 0.f;  // the update draws noise
-  // step-consistent samplers (DESIGN.md section 26): refused here, before anything touches the device
-  DQ_REQUIRE(sampler == DQ_SAMPLER_REFERENCE || sampler == DQ_SAMPLER_DDIM || sampler == DQ_SAMPLER_DPMPP_2M, "dq_ddim_sample: unknown sampler");
-  const bool clip = clip_x0 > 0.f;  // (<= 0 and NaN: off)
-  DQ_REQUIRE(sampler != DQ_SAMPLER_DPMPP_2M || !sto, "dq_ddim_sample: DPM-Solver++(2M) is deterministic: eta must be 0");
-  DQ_REQUIRE(!clip || sampler != DQ_SAMPLER_REFERENCE, "dq_ddim_sample: clip_x0 needs the ddim or dpmpp_2m sampler");
-  DQ_REQUIRE(!clip || !sto, "dq_ddim_sample: clip_x0 needs eta == 0");
-  if (sampler != DQ_SAMPLER_REFERENCE)
-    for (int i = 1; i < num_steps; ++i)
-      DQ_REQUIRE(timesteps_host[i] < timesteps_host[i - 1], "dq_ddim_sample: the timesteps of this sampler must be strictly decreasing");
-  // the update: k_solver_step behind the forward (2M, or a clamped x0 at first order); else the reference's kernels over this sampler's table
-  const StepUpdate kind = sampler == DQ_SAMPLER_DPMPP_2M ? StepUpdate::SOLVER_2M : clip ? StepUpdate::SOLVER_1 : sto ? StepUpdate::STOCHASTIC : StepUpdate::DDIM;
+  SamplerChoice sc;
+  DQ_TRY(sampler_check("dq_ddim_sample", plan && params && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
+                       eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, &sc));
+  const StepUpdate kind = sc.kind;
+  const bool sto = sc.sto, clip = sc.clip;
+  clip_x0 = sc.clip_x0;
+  const int px0 = sc.px0;
   const bool in_head = kind == StepUpdate::DDIM;  // the head launch takes the update when it can (StepIO::x_t); the others run behind the forward
   const bool in_place = kind == StepUpdate::SOLVER_1 || kind == StepUpdate::SOLVER_2M;  // the solver loop keeps x in xa: xb holds the x0 history
-  if (!clip) clip_x0 = 0.f;
-  DQ_REQUIRE(seed_dev || (x_T && !sto), "dq_ddim_sample: eta > 0 and a null x_T need the seed (device memory)");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_ddim_sample: Unknown pred_type");
-  const int px0 = pred_type == DQ_PRED_X0;
   DQ_REQUIRE(B > 0 && RT > 0 && num_steps >= 1 && num_steps <= 1024, "dq_ddim_sample: need B, RT > 0 and 1 <= num_steps <= 1024");
   DQ_TRY(ensure_arena(plan, B, RT));
   const Arena& a = plan->arena;
@@ -141,14 +162,7 @@ int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_
   const int64_t per = (int64_t)RT * plan->plan.mz, n = B * per;
   const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
   const int32_t* ts = timesteps_host;  // trunc(linspace(T-1, 0, num_steps)) formed by the caller exactly as model.py:313 does
-  // coefficient table, fp32 like the reference, and sigma (eta > 0) or c1 (the solver) per step
-  std::vector<float> coef(4 * (size_t)num_steps), extra((size_t)num_steps);
-  if (sampler == DQ_SAMPLER_REFERENCE) DQ_TRY(dq_ddim_coef_table(alpha_bars_host, T, ts, num_steps, eta, coef.data(), extra.data()));
-  else DQ_TRY(sampler_rows(alpha_bars_host, T, ts, num_steps, kind == StepUpdate::SOLVER_1 ? SOLVER_ORDER1 : sampler, eta, coef.data(), extra.data(), "dq_ddim_sample"));
-  DQ_HIP_OK(hipMemcpyAsync(c.w(a.coef), coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice, s));
-  if (!in_head) DQ_HIP_OK(hipMemcpyAsync(c.w(a.sigma), extra.data(), sizeof(float) * extra.size(), hipMemcpyHostToDevice, s));
-  // the host vector must outlive the copy: pageable H2D copies are staged synchronously by the runtime, but make it explicit
-  DQ_HIP_OK(hipStreamSynchronize(s));
+  DQ_TRY(sampler_upload_tables("dq_ddim_sample", alpha_bars_host, T, ts, num_steps, sampler, sc, eta, c.w(a.coef), in_head ? nullptr : c.w(a.sigma), s));
   float* xa = c.w(a.xa);
   float* xb = c.w(a.xb);
   if (x_T) DQ_HIP_OK(hipMemcpyAsync(xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
@@ -167,16 +181,7 @@ int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_
     DQ_HIP_OK(hipMemcpyAsync(c.w(a.c1_stage), ms1_cond, sizeof(float) * (int64_t)B * RT * plan->plan.ms1_channels, hipMemcpyDeviceToDevice, s));
     uint64_t* seed_st = reinterpret_cast<uint64_t*>(c.w(a.seed_stage));
     int64_t* ids_st = reinterpret_cast<int64_t*>(c.w(a.ids_stage));
-    std::vector<int64_t> iota;
-    if (sto) {  // seed and ids staged like the conditions: a new seed or other windows replay the same graph (null ids: 0 .. B-1)
-      DQ_HIP_OK(hipMemcpyAsync(seed_st, seed_dev, sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-      if (window_ids_dev) DQ_HIP_OK(hipMemcpyAsync(ids_st, window_ids_dev, sizeof(int64_t) * B, hipMemcpyDeviceToDevice, s));
-      else {
-        iota.resize(B);
-        for (int b = 0; b < B; ++b) iota[b] = b;
-        DQ_HIP_OK(hipMemcpyAsync(ids_st, iota.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, s));
-      }
-    }
+    if (sto) DQ_TRY(sampler_stage_noise(seed_st, ids_st, seed_dev, window_ids_dev, B, s));  // staged like the conditions (null ids: 0 .. B-1)
     DQ_HIP_OK(hipStreamSynchronize(s));  // ts is caller memory; also keeps the capture below free of pending copies
     DQ_TRY(unet_sample_prologue(c, c.w(a.c1_stage), cm, ca, rope_freqs, &io.prologue));
     io.x_t = in_head ? xa : nullptr; io.x_out = xa; io.step_ptr = step; io.want_eps = false;  // in place: element-wise, read and written by the same lane

@@ -55,6 +55,12 @@ int launch_rope_add(float* x, const float* sin_t, const float* cos_t, const floa
 // c[b][s][:] = rope(x_cond[b][s] * w + bias)
 int launch_cond_embed(const float* x_cond, const float* w, const float* bias, const float* sin_t, const float* cos_t, float* c, int B, int S,
                       int H, hipStream_t s);
+// sampling variants (dq_tfm_sample): the rotation plus row `row` (step_ptr nullable: the row the device-side counter names) of a
+// (num_steps, H) time-embedding table, added to every sample's rows; the conditional embedding of x_cond * cm + ca
+int launch_rope_add_row(float* x, const float* sin_t, const float* cos_t, const float* temb_tab, int row, const int* step_ptr, int B, int S,
+                        int H, hipStream_t s);
+int launch_cond_embed_affine(const float* x_cond, float cm, float ca, const float* w, const float* bias, const float* sin_t, const float* cos_t,
+                             float* c, int B, int S, int H, hipStream_t s);
 // backward of launch_cond_embed: dw, db (+=, H each) and dx_cond (nullable, (B, S)) from dc (B, S, H); scratch: 2 * H * 64 floats
 int launch_cond_embed_bwd(const float* dc, const float* x_cond, const float* w, const float* sin_t, const float* cos_t, float* dw, float* db,
                           float* dx_cond, float* scratch, int B, int S, int H, hipStream_t s, int accumulate = 1);
@@ -82,5 +88,17 @@ constexpr int COLSUM_BLOCKS = 64;
 int launch_colsum(const float* x, int M, int N, int64_t ld, float* out, float* scratch, hipStream_t s, int accumulate = 1);
 // out[b][n] = sum_s x[(b * S + s) * N + n]  (time-embedding gradient: plain store)
 int launch_seqsum(const float* x, int B, int S, int N, float* out, hipStream_t s);
+
+// ---- k_tfm_attn.hip: the inference attention in one launch: o (B, S1, H) = softmax(q k^T / sqrt(dh)) v per (sample, head), q (B, S1, H),
+// kv (B, Sk, 2H) = K | V halves; fp32 VALU, max-subtracted, bitwise repeatable.  tfm_attn_form: TFM_ATTN_FUSED when the kernel takes the
+// shape (dh % 4 == 0 and K, V and the waves' q / p rows fit the CU's 160 KiB of LDS: tfm_attn_lds_bytes), else TFM_ATTN_GEMM (scores GEMM,
+// softmax rows, PV GEMM); -1 for a non-positive size.  Host only.
+enum TfmAttnForm { TFM_ATTN_GEMM = 0, TFM_ATTN_FUSED = 1 };
+int64_t tfm_attn_lds_bytes(int Sk, int dh);
+int tfm_attn_form(int S1, int Sk, int dh);
+// raises the kernel's dynamic-LDS limit on the CURRENT device, once per device (thread-safe); launch_tfm_attn_fwd calls it, a caller that
+// captures the launch calls it before the capture
+int tfm_attn_prepare();
+int launch_tfm_attn_fwd(const float* q, const float* kv, float* o, int B, int S1, int Sk, int H, int heads, hipStream_t s);
 
 }  // namespace dq

@@ -5,6 +5,7 @@
 #include "../../include/dq_hip.h"
 #include "dq_common.h"
 #include "dq_tfm.h"
+#include "dq_tfm_net.h"
 #include "dq_kernels.h"
 #include <cmath>
 #include <cstring>
@@ -13,48 +14,7 @@
 
 namespace dq {
 
-struct TfmParam { std::string name; int64_t offset; int ndim; int64_t shape[2]; int64_t numel; };
-struct TfmLayer { int64_t in_w, in_b, out_w, out_b, n1_g, n1_b, f0_w, f0_b, f2_w, f2_b, n2_g, n2_b; };
-
-}  // namespace dq
-
-struct dq_tfm {
-  int D = 0, H = 0, heads = 0, layers = 0;
-  std::vector<dq::TfmParam> params;
-  int64_t total = 0;
-  int64_t in_w, in_b, out_w, out_b, c_w, c_b, t1_w, t1_b, t2_w, t2_b;
-  std::vector<dq::TfmLayer> L;
-  // which training workspaces hold a forward's saved activations (one entry per workspace; several forwards may be in flight before
-  // their backwards run: micro-batches whose losses are summed).  An entry stays until the same workspace takes another forward.
-  struct Saved { const void* ws; int B, S1, S2; };
-  std::vector<Saved> saved;
-  int precision = dq::GEMM_FP32;  // arithmetic of the dense products (dq_tfm_set_precision)
-};
-
-namespace dq {
-namespace {
-
-int64_t add(dq_tfm& p, const std::string& name, int64_t a, int64_t b = 0) {
-  TfmParam pi;
-  pi.name = name; pi.offset = p.total; pi.ndim = b ? 2 : 1; pi.shape[0] = a; pi.shape[1] = b ? b : 1; pi.numel = a * (b ? b : 1);
-  p.total += pi.numel;
-  p.params.push_back(pi);
-  return pi.offset;
-}
-
-constexpr int64_t PARTIAL_FLOATS = (int64_t)(768 + 256) * 128 * 128;  // bound of launch_gemm's split-K scratch (k_gemm.hip: choose())
-
-// workspace: carved in a fixed order; `training` keeps one set of layer buffers per layer (read by the backward)
-struct Ws {
-  float *cp, *tfeat, *th, *tg, *temb, *x0, *tmp, *partial, *colscr, *lnscr;
-  struct Layer { float *comb, *q, *kv, *prob, *ao, *y1, *st1, *x1, *hpre, *hact, *y2, *st2, *xo; };
-  std::vector<Layer> L;
-  // backward only
-  float *dxa, *dxb, *dh, *dq, *dkv, *dprob, *dao, *dcomb, *dcp, *dtemb, *dtg;
-  int64_t floats = 0;
-};
-inline int64_t up4(int64_t v) { return (v + 3) & ~(int64_t)3; }
-
+// (Ws: dq_tfm_net.h) carved in a fixed order; `training` keeps one set of layer buffers per layer (read by the backward)
 Ws carve(const dq_tfm& p, float* base, int B, int S1, int S2, bool training) {
   Ws w;
   int64_t off = 0;
@@ -62,7 +22,7 @@ Ws carve(const dq_tfm& p, float* base, int B, int S1, int S2, bool training) {
   const int64_t H = p.H, R1 = (int64_t)B * S1, R2 = (int64_t)B * S2, Sk = S1 + S2, ldp = up4(Sk);
   w.cp = take(R2 * H); w.tfeat = take(B * H); w.th = take(B * 4 * H); w.tg = take(B * 4 * H); w.temb = take(B * H);
   w.x0 = take(R1 * H); w.tmp = take(R1 * H);
-  w.partial = take(PARTIAL_FLOATS);
+  w.partial = take(TFM_PARTIAL_FLOATS);
   w.colscr = take(std::max<int64_t>((int64_t)COLSUM_BLOCKS * std::max<int64_t>(p.D, 4 * H), 2 * H * 64));
   w.lnscr = take((int64_t)2 * H * LN_BWD_BLOCKS);
   const int nl = training ? p.layers : 1;
@@ -82,26 +42,33 @@ Ws carve(const dq_tfm& p, float* base, int B, int S1, int S2, bool training) {
   return w;
 }
 
+namespace {
+
+int64_t add(dq_tfm& p, const std::string& name, int64_t a, int64_t b = 0) {
+  TfmParam pi;
+  pi.name = name; pi.offset = p.total; pi.ndim = b ? 2 : 1; pi.shape[0] = a; pi.shape[1] = b ? b : 1; pi.numel = a * (b ? b : 1);
+  p.total += pi.numel;
+  p.params.push_back(pi);
+  return pi.offset;
+}
+
 // y (M, N) = x (M, K) W^T + b   with W an nn.Linear weight (N, K)
 int linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K, const Ws& ws, hipStream_t s) {
-  Gemm g;
-  g.A = x; g.B = w; g.C = y; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N; g.bias = b;
-  g.partial = ws.partial; g.partial_floats = PARTIAL_FLOATS;
-  return launch_gemm(g, s);
+  return tfm_linear(x, w, b, y, M, N, K, ws.partial, s);
 }
 // dW (N, K) += dy^T x ; db (N) += column sums of dy ; dx (M, K) (+)= dy W  (dx nullable)
 int linear_bwd(const float* x, const float* w, const float* dy, float* dw, float* db, float* dx, int dx_accumulate, int M, int N, int K,
                const Ws& ws, hipStream_t s, int acc) {
   Gemm g;
   g.A = dy; g.a_kmajor = 0; g.lda = N; g.B = x; g.b_kmajor = 0; g.ldb = K; g.C = dw; g.ldc = K; g.M = N; g.N = K; g.K = M; g.accumulate = acc;
-  g.partial = ws.partial; g.partial_floats = PARTIAL_FLOATS;
+  g.partial = ws.partial; g.partial_floats = TFM_PARTIAL_FLOATS;
   if (int rc = launch_gemm(g, s)) return rc;
   if (db)
     if (int rc = launch_colsum(dy, M, N, N, db, ws.colscr, s, acc)) return rc;
   if (dx) {
     Gemm h;
     h.A = dy; h.lda = N; h.B = w; h.b_kmajor = 0; h.ldb = K; h.C = dx; h.ldc = K; h.M = M; h.N = K; h.K = N; h.accumulate = dx_accumulate;
-    h.partial = ws.partial; h.partial_floats = PARTIAL_FLOATS;
+    h.partial = ws.partial; h.partial_floats = TFM_PARTIAL_FLOATS;
     if (int rc = launch_gemm(h, s)) return rc;
   }
   return 0;
@@ -127,14 +94,26 @@ __global__ void __launch_bounds__(256) k_split_comb(const float* __restrict__ dc
 }
 inline unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>(cdiv(n, 256), 8192); }
 
-struct AttnDims { int B, S1, Sk, H, heads, dh; int64_t ldp; };
-// batched (sample, head) products of the attention; `which`: 0 scores = Q K^T, 1 O = P V, 2 dP = dO V^T, 3 dV = P^T dO,
-// 4 dQ = dS K, 5 dK = dS^T Q
-int attn_gemm(int which, const AttnDims& d, const float* q, const float* kv, float* prob, float* o, const Ws& ws, hipStream_t s) {
+int check_shapes(const dq_tfm* p, int B, int S1, int S2) {
+  DQ_REQUIRE(p, "tfm: null handle");
+  DQ_REQUIRE(B > 0 && S1 > 0 && S2 > 0, "tfm: batch and both sequence lengths must be positive");
+  return 0;
+}
+
+}  // namespace
+
+int tfm_linear(const float* x, const float* w, const float* b, float* y, int M, int N, int K, float* partial, hipStream_t s) {
+  Gemm g;
+  g.A = x; g.B = w; g.C = y; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N; g.bias = b;
+  g.partial = partial; g.partial_floats = TFM_PARTIAL_FLOATS;
+  return launch_gemm(g, s);
+}
+
+int attn_gemm(int which, const AttnDims& d, const float* q, const float* kv, float* prob, float* o, float* partial, hipStream_t s) {
   Gemm g;
   g.batch = d.B * d.heads; g.inner = d.heads;
   const int64_t qs = (int64_t)d.S1 * d.H, kvs = (int64_t)d.Sk * 2 * d.H, ps = (int64_t)d.S1 * d.ldp;
-  g.partial = ws.partial; g.partial_floats = PARTIAL_FLOATS; g.splits = 1;
+  g.partial = partial; g.partial_floats = TFM_PARTIAL_FLOATS; g.splits = 1;
   switch (which) {
     case 0: case 2:  // (S1 x dh) (Sk x dh)^T -> (S1 x Sk): A = q or dO, B = K (which 0) or V (which 2) rows
       g.A = q; g.lda = d.H; g.sAo = qs; g.sAi = d.dh;
@@ -155,20 +134,13 @@ int attn_gemm(int which, const AttnDims& d, const float* q, const float* kv, flo
   return launch_gemm(g, s);
 }
 
-// the handle's precision as the thread's GEMM default for the duration of one call
-struct PrecisionScope {
-  int old;
-  explicit PrecisionScope(int p) : old(set_gemm_precision(p)) {}
-  ~PrecisionScope() { set_gemm_precision(old); }
-};
-
-int check_shapes(const dq_tfm* p, int B, int S1, int S2) {
-  DQ_REQUIRE(p, "tfm: null handle");
-  DQ_REQUIRE(B > 0 && S1 > 0 && S2 > 0, "tfm: batch and both sequence lengths must be positive");
-  return 0;
+int tfm_attention_fwd(int form, const AttnDims& d, const float* q, const float* kv, float* prob, float* o, float* partial, hipStream_t s) {
+  if (form == TFM_ATTN_FUSED) return launch_tfm_attn_fwd(q, kv, o, d.B, d.S1, d.Sk, d.H, d.heads, s);
+  if (int rc = attn_gemm(0, d, q, kv, prob, nullptr, partial, s)) return rc;
+  if (int rc = launch_softmax_rows(prob, (int64_t)d.B * d.heads * d.S1, d.Sk, (int)d.ldp, 1.0f / sqrtf((float)d.dh), s)) return rc;
+  return attn_gemm(1, d, nullptr, kv, prob, o, partial, s);
 }
 
-}  // namespace
 }  // namespace dq
 
 using namespace dq;
@@ -229,6 +201,7 @@ int dq_tfm_set_precision(dq_tfm* tfm, int precision) {
   DQ_REQUIRE(tfm, "dq_tfm_set_precision: null handle");
   DQ_REQUIRE(precision == DQ_PRECISION_FP32 || precision == DQ_PRECISION_BF16X3, "dq_tfm_set_precision: precision must be DQ_PRECISION_FP32 or DQ_PRECISION_BF16X3");
   tfm->precision = precision == DQ_PRECISION_BF16X3 ? GEMM_BF16X3 : GEMM_FP32;
+  drop_tfm_step_graph(tfm);  // (a captured sampling step has the arithmetic of its capture time baked in)
   return 0;
 }
 
@@ -261,7 +234,12 @@ dq_tfm* dq_tfm_create(int input_dim, int hidden_dim, int num_heads, int num_laye
   }
   return p;
 }
-void dq_tfm_destroy(dq_tfm* p) { delete p; }
+void dq_tfm_destroy(dq_tfm* p) {
+  if (!p) return;
+  drop_tfm_step_graph(p);
+  if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
+  delete p;
+}
 int dq_tfm_num_params(const dq_tfm* p) { return p ? (int)p->params.size() : 0; }
 int64_t dq_tfm_param_floats(const dq_tfm* p) { return p ? p->total : 0; }
 int dq_tfm_param_info(const dq_tfm* p, int i, char* name, int name_cap, int64_t* offset, int* ndim, int64_t* shape) {
@@ -310,9 +288,9 @@ int dq_tfm_fwd(dq_tfm* p, const float* params, const float* rope_sin, const floa
     // nn.MultiheadAttention (:164-166): q from x_t, k | v from [x_cond ; x_t]
     if (int rc = linear_fwd(x, P + a.in_w, P + a.in_b, b.q, R1, H, H, w, s)) return rc;
     if (int rc = linear_fwd(b.comb, P + a.in_w + (int64_t)H * H, P + a.in_b + H, b.kv, B * Sk, 2 * H, H, w, s)) return rc;
-    if (int rc = attn_gemm(0, ad, b.q, b.kv, b.prob, nullptr, w, s)) return rc;
+    if (int rc = attn_gemm(0, ad, b.q, b.kv, b.prob, nullptr, w.partial, s)) return rc;
     if (int rc = launch_softmax_rows(b.prob, (int64_t)B * p->heads * S1, Sk, (int)ad.ldp, 1.0f / sqrtf((float)ad.dh), s)) return rc;
-    if (int rc = attn_gemm(1, ad, nullptr, b.kv, b.prob, b.ao, w, s)) return rc;
+    if (int rc = attn_gemm(1, ad, nullptr, b.kv, b.prob, b.ao, w.partial, s)) return rc;
     if (int rc = linear_fwd(b.ao, P + a.out_w, P + a.out_b, w.tmp, R1, H, H, w, s)) return rc;
     if (int rc = launch_layernorm_fwd(x, w.tmp, P + a.n1_g, P + a.n1_b, b.y1, b.x1, b.st1, R1, H, s)) return rc;  // :168
     if (int rc = linear_fwd(b.x1, P + a.f0_w, P + a.f0_b, b.hpre, R1, 4 * H, H, w, s)) return rc;                    // :171
@@ -386,11 +364,11 @@ static int tfm_bwd_impl(dq_tfm* p, const float* params, const float* rope_sin, c
     float* d2 = dx;
     if (int rc = launch_layernorm_bwd(b.y1, b.st1, P + a.n1_g, d1, d2, G + a.n1_g, G + a.n1_b, w.lnscr, R1, H, s, acc)) return rc;
     if (int rc = linear_bwd(b.ao, P + a.out_w, d2, G + a.out_w, G + a.out_b, w.dao, 0, R1, H, H, w, s, acc)) return rc;
-    if (int rc = attn_gemm(2, ad, w.dao, b.kv, w.dprob, nullptr, w, s)) return rc;            // dP = dO V^T
-    if (int rc = attn_gemm(3, ad, w.dao, nullptr, b.prob, w.dkv, w, s)) return rc;             // dV = P^T dO
+    if (int rc = attn_gemm(2, ad, w.dao, b.kv, w.dprob, nullptr, w.partial, s)) return rc;            // dP = dO V^T
+    if (int rc = attn_gemm(3, ad, w.dao, nullptr, b.prob, w.dkv, w.partial, s)) return rc;             // dV = P^T dO
     if (int rc = launch_softmax_rows_bwd(b.prob, w.dprob, (int64_t)B * p->heads * S1, Sk, (int)ad.ldp, 1.0f / sqrtf((float)ad.dh), s)) return rc;
-    if (int rc = attn_gemm(4, ad, nullptr, b.kv, w.dprob, w.dq, w, s)) return rc;              // dQ = dS K
-    if (int rc = attn_gemm(5, ad, b.q, nullptr, w.dprob, w.dkv, w, s)) return rc;              // dK = dS^T Q
+    if (int rc = attn_gemm(4, ad, nullptr, b.kv, w.dprob, w.dq, w.partial, s)) return rc;              // dQ = dS K
+    if (int rc = attn_gemm(5, ad, b.q, nullptr, w.dprob, w.dkv, w.partial, s)) return rc;              // dK = dS^T Q
     if (int rc = linear_bwd(xin, P + a.in_w, w.dq, G + a.in_w, G + a.in_b, d2, 1, R1, H, H, w, s, acc)) return rc;  // ... + through q
     if (int rc = linear_bwd(b.comb, P + a.in_w + (int64_t)H * H, w.dkv, G + a.in_w + (int64_t)H * H, G + a.in_b + H, w.dcomb, 0, B * Sk, 2 * H, H,
                             w, s, acc))

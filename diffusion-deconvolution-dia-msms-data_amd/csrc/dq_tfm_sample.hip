@@ -1,0 +1,233 @@
+// Sampling from the CustomTransformer inside the library: dq_tfm_sample walks all timesteps -- a sampling forward of
+// the network and one update of dq_sampler.h per step, eagerly or as one captured step replayed -- and the stand-alone entry of the fused
+// inference attention (k_tfm_attn.hip).  What does not depend on the step is computed once per call, before the loop: the conditional
+// embedding cp of the MS1 chromatogram, every layer's K | V rows of it, and the time embedding of every step.  dq_tfm_fwd / dq_tfm_bwd
+// (dq_tfm.hip) are the training path and know nothing of this file.
+#include "../../include/dq_hip.h"
+#include "dq_common.h"
+#include "dq_kernels.h"
+#include "dq_net.h"  // DQ_TRY
+#include "dq_options.h"
+#include "dq_sampler.h"
+#include "dq_tfm.h"
+#include "dq_tfm_net.h"
+#include <cmath>
+#include <utility>
+#include <vector>
+
+namespace dq {
+namespace {
+
+// workspace of a sampling call: the inference buffers of carve() (its comb and kv stay unused), then the L persistent kv_l, the time table
+// and its inputs, then the sampler's state; carved in a fixed order
+struct SampleWs {
+  Ws net;
+  std::vector<float*> kv;  // per layer (B, Sk, 2H): rows [0, S2) the call's conditional K | V, rows [S2, Sk) the step's
+  int64_t* t64;            // (num_steps) the timesteps as the time-feature kernel reads them
+  float *tfeat, *th, *tg, *ttab;  // time MLP over all steps: (ns, H), (ns, 4H), (ns, 4H), (ns, H)
+  float *xa, *xb, *eps, *coef, *sigma;
+  int *ts_tab, *step;
+  uint64_t* seed_stage;
+  int64_t* ids_stage;
+  int64_t floats = 0;
+};
+
+SampleWs carve_sample(const dq_tfm& p, float* base, int B, int S1, int S2, int ns) {
+  SampleWs w;
+  w.net = carve(p, base, B, S1, S2, false);
+  int64_t off = w.net.floats;
+  auto take = [&](int64_t n) { float* r = base ? base + off : nullptr; off += up4(n); return r; };
+  const int64_t H = p.H, Sk = S1 + S2, n = (int64_t)B * S1 * p.D;
+  for (int l = 0; l < p.layers; ++l) w.kv.push_back(take(B * Sk * 2 * H));
+  w.t64 = reinterpret_cast<int64_t*>(take(2 * (int64_t)ns));
+  w.tfeat = take(ns * H); w.th = take(ns * 4 * H); w.tg = take(ns * 4 * H); w.ttab = take(ns * H);
+  w.xa = take(n); w.xb = take(n); w.eps = take(n);
+  w.coef = take(4 * (int64_t)ns); w.sigma = take(ns);
+  w.ts_tab = reinterpret_cast<int*>(take(ns));
+  w.step = reinterpret_cast<int*>(take(4));
+  w.seed_stage = reinterpret_cast<uint64_t*>(take(4));
+  w.ids_stage = reinterpret_cast<int64_t*>(take(2 * (int64_t)B));
+  w.floats = off;
+  return w;
+}
+
+// What one sampling call's forwards share
+struct SampleNet {
+  const dq_tfm* p; const float* P; const float* sin_t; const float* cos_t;
+  const SampleWs* w;
+  int B, S1, S2, form;
+};
+
+// K | V rows of `rows` (B, M, H) under layer l's projection into rows [row0, row0 + M) of kv_l: one product batched over the samples (B == 1: a
+// plain product, which the launcher may split along the reduction)
+int kv_rows(const SampleNet& c, int l, const float* rows, int M, int row0, hipStream_t s) {
+  const int H = c.p->H, Sk = c.S1 + c.S2;
+  const TfmLayer& a = c.p->L[l];
+  Gemm g;
+  g.A = rows; g.lda = H; g.sAo = (int64_t)M * H;
+  g.B = c.P + a.in_w + (int64_t)H * H; g.ldb = H; g.bias = c.P + a.in_b + H;
+  g.C = c.w->kv[l] + (int64_t)row0 * 2 * H; g.ldc = 2 * H; g.sCo = (int64_t)Sk * 2 * H;
+  g.batch = c.B; g.M = M; g.N = 2 * H; g.K = H;
+  g.partial = c.w->net.partial; g.partial_floats = TFM_PARTIAL_FLOATS;
+  return launch_gemm(g, s);
+}
+
+// once per call, eagerly: cp = rope((cm x_cond + ca) w + b), every layer's K | V rows of it, the time embedding of every step
+int sample_prologue(const SampleNet& c, const float* ms1, float cm, float ca, const float* time_freqs, int ns, hipStream_t s) {
+  const dq_tfm& p = *c.p;
+  const Ws& n = c.w->net;
+  const int H = p.H;
+  DQ_TRY(launch_cond_embed_affine(ms1, cm, ca, c.P + p.c_w, c.P + p.c_b, c.sin_t, c.cos_t, n.cp, c.B, c.S2, H, s));
+  for (int l = 0; l < p.layers; ++l) DQ_TRY(kv_rows(c, l, n.cp, c.S2, 0, s));
+  // time embedding (building_blocks.py:92-112) with "batch" = the steps
+  DQ_TRY(launch_time_features(c.w->t64, time_freqs, c.w->tfeat, ns, H, s));
+  DQ_TRY(tfm_linear(c.w->tfeat, c.P + p.t1_w, c.P + p.t1_b, c.w->th, ns, 4 * H, H, n.partial, s));
+  DQ_TRY(launch_gelu(c.w->th, c.w->tg, (int64_t)ns * 4 * H, s));
+  DQ_TRY(tfm_linear(c.w->tg, c.P + p.t2_w, c.P + p.t2_b, c.w->ttab, ns, H, 4 * H, n.partial, s));
+  return 0;
+}
+
+// one step's network output from x (B, S1, D): time row `row`, or the one the device-side counter names
+int sample_forward(const SampleNet& c, const float* x_in, int row, const int* step_ptr, float* out, hipStream_t s) {
+  const dq_tfm& p = *c.p;
+  const Ws& n = c.w->net;
+  const Ws::Layer& b = n.L[0];
+  const int H = p.H, D = p.D, R1 = c.B * c.S1, Sk = c.S1 + c.S2;
+  const float* P = c.P;
+  DQ_TRY(tfm_linear(x_in, P + p.in_w, P + p.in_b, n.x0, R1, H, D, n.partial, s));
+  DQ_TRY(launch_rope_add_row(n.x0, c.sin_t, c.cos_t, c.w->ttab, row, step_ptr, c.B, c.S1, H, s));
+  const AttnDims ad{c.B, c.S1, Sk, H, p.heads, H / p.heads, up4(Sk)};
+  const float* x = n.x0;
+  for (int l = 0; l < p.layers; ++l) {
+    const TfmLayer& a = p.L[l];
+    DQ_TRY(tfm_linear(x, P + a.in_w, P + a.in_b, b.q, R1, H, H, n.partial, s));
+    DQ_TRY(kv_rows(c, l, x, c.S1, c.S2, s));
+    DQ_TRY(tfm_attention_fwd(c.form, ad, b.q, c.w->kv[l], b.prob, b.ao, n.partial, s));
+    DQ_TRY(tfm_linear(b.ao, P + a.out_w, P + a.out_b, n.tmp, R1, H, H, n.partial, s));
+    DQ_TRY(launch_layernorm_fwd(x, n.tmp, P + a.n1_g, P + a.n1_b, b.y1, b.x1, nullptr, R1, H, s));
+    DQ_TRY(tfm_linear(b.x1, P + a.f0_w, P + a.f0_b, b.hpre, R1, 4 * H, H, n.partial, s));
+    DQ_TRY(launch_gelu(b.hpre, b.hact, (int64_t)R1 * 4 * H, s));
+    DQ_TRY(tfm_linear(b.hact, P + a.f2_w, P + a.f2_b, n.tmp, R1, H, 4 * H, n.partial, s));
+    DQ_TRY(launch_layernorm_fwd(b.x1, n.tmp, P + a.n2_g, P + a.n2_b, b.y2, b.xo, nullptr, R1, H, s));
+    x = b.xo;
+  }
+  return tfm_linear(x, P + p.out_w, P + p.out_b, out, R1, D, H, n.partial, s);
+}
+
+}  // namespace
+}  // namespace dq
+
+using namespace dq;
+
+extern "C" {
+
+int dq_tfm_attn_form(int S1, int Sk, int dh) { return tfm_attn_form(S1, Sk, dh); }
+
+int dq_tfm_attn_fwd(const float* q, const float* kv, float* o, float* prob_scratch, int B, int S1, int Sk, int H, int heads, int form,
+                    void* stream) {
+  DQ_REQUIRE(q && kv && o, "dq_tfm_attn_fwd: null argument");
+  DQ_REQUIRE(B > 0 && S1 > 0 && Sk > 0 && H > 0 && heads > 0 && H % heads == 0 && (H / heads) % 4 == 0,
+             "dq_tfm_attn_fwd: sizes must be positive, H divisible by heads, the head width a multiple of 4");
+  DQ_REQUIRE(form >= -1 && form <= 1, "dq_tfm_attn_fwd: form must be -1 (chosen), 0 (three launches) or 1 (fused)");
+  DQ_REQUIRE((((uintptr_t)q | (uintptr_t)kv | (uintptr_t)o) & 15) == 0, "dq_tfm_attn_fwd: q, kv and o must be 16-byte aligned");
+  const int dh = H / heads, chosen = tfm_attn_form(S1, Sk, dh);
+  DQ_REQUIRE(form != TFM_ATTN_FUSED || chosen == TFM_ATTN_FUSED, "dq_tfm_attn_fwd: the fused form does not take this shape (dq_tfm_attn_form): K, V and the waves' rows exceed the LDS of a CU");
+  const int f = form < 0 ? chosen : form;
+  DQ_REQUIRE(f == TFM_ATTN_FUSED || prob_scratch, "dq_tfm_attn_fwd: the three-launch form needs prob_scratch (B heads S1 up4(Sk) floats)");
+  const AttnDims ad{B, S1, Sk, H, heads, dh, up4(Sk)};
+  return tfm_attention_fwd(f, ad, q, kv, prob_scratch, o, nullptr, (hipStream_t)stream);  // (the attention products are never split: no scratch)
+}
+
+int64_t dq_tfm_sample_workspace_bytes(const dq_tfm* p, int B, int S1, int S2, int num_steps) {
+  if (!p || B <= 0 || S1 <= 0 || S2 <= 0 || num_steps < 1 || num_steps > 1024) return 0;
+  return carve_sample(*p, nullptr, B, S1, S2, num_steps).floats * (int64_t)sizeof(float);
+}
+
+int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const float* rope_cos, const float* time_freqs,
+                  const float* alpha_bars_host, int num_timesteps, const float* x_T, const float* ms2_cond, const float* ms1_cond,
+                  int auto_normalize, int pred_type, const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x,
+                  float* traj_eps, int use_graph, void* workspace, int64_t workspace_bytes, int B, int S1, int S2, void* stream, float eta,
+                  const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0) {
+  SamplerChoice sc;
+  DQ_TRY(sampler_check("dq_tfm_sample", p && params && rope_sin && rope_cos && time_freqs && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host &&
+                                            out_x && out_noise && workspace,
+                       eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, &sc));
+  DQ_REQUIRE(B > 0 && S1 > 0 && S2 > 0 && num_steps >= 1 && num_steps <= 1024, "dq_tfm_sample: need B, S1, S2 > 0 and 1 <= num_steps <= 1024");
+  const int T = num_timesteps;
+  DQ_REQUIRE(T >= 1, "dq_tfm_sample: num_timesteps must be >= 1");
+  DQ_REQUIRE(((uintptr_t)params & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "dq_tfm_sample: params and workspace must be 16-byte aligned");
+  const SampleWs w = carve_sample(*p, (float*)workspace, B, S1, S2, num_steps);
+  DQ_REQUIRE(workspace_bytes >= w.floats * (int64_t)sizeof(float), "dq_tfm_sample: workspace too small (dq_tfm_sample_workspace_bytes)");
+  PrecisionScope prec(p->precision);
+  hipStream_t s = (hipStream_t)stream;
+  const StepUpdate kind = sc.kind;
+  const bool in_place = kind == StepUpdate::SOLVER_1 || kind == StepUpdate::SOLVER_2M;  // the solver loop keeps x in xa: xb holds the x0 history
+  const int px0 = sc.px0;
+  const int64_t per = (int64_t)S1 * p->D, n = B * per;
+  const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
+  const int32_t* ts = timesteps_host;
+  SampleNet net{p, params, rope_sin, rope_cos, &w, B, S1, S2, tfm_attn_form(S1, S1 + S2, p->H / p->heads)};
+  // the steps' timesteps for the time table (the copy is done when the table upload below returns: it synchronises the stream)
+  std::vector<int64_t> t64((size_t)num_steps);
+  for (int i = 0; i < num_steps; ++i) t64[i] = ts[i];
+  DQ_HIP_OK(hipMemcpyAsync(w.t64, t64.data(), sizeof(int64_t) * t64.size(), hipMemcpyHostToDevice, s));
+  DQ_TRY(sampler_upload_tables("dq_tfm_sample", alpha_bars_host, T, ts, num_steps, sampler, sc, eta, w.coef, w.sigma, s));
+  float* xa = w.xa;
+  float* xb = w.xb;
+  if (x_T) DQ_HIP_OK(hipMemcpyAsync(xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  else DQ_TRY(launch_randn(xa, window_ids_dev, seed_dev, 0, B, per, s));  // draw index 0 is x_T's
+  const StepUpdateArgs upd{kind, w.coef, w.sigma, xb, sc.clip_x0, px0, B, per};
+  if (net.form == TFM_ATTN_FUSED) DQ_TRY(tfm_attn_prepare());  // (the LDS limit of this device, before any capture)
+  // every call, outside any capture: a changed MS1, or changed weights behind the same pointer, cannot meet a stale cache
+  DQ_TRY(sample_prologue(net, ms1_cond, cm, ca, time_freqs, num_steps, s));
+  if (use_graph && !traj_x && !traj_eps) {
+    // ---- one step captured once (every pointer inside the workspace / parameter buffers), replayed per step.  The step index lives on the
+    // device: the time row and the update's coefficient row are read at *step, k_inc_step bumps it.  A linear graph: one stream, no branches.
+    DQ_HIP_OK(hipMemsetAsync(w.step, 0, sizeof(int), s));
+    if (sc.sto) DQ_TRY(sampler_stage_noise(w.seed_stage, w.ids_stage, seed_dev, window_ids_dev, B, s));
+    TfmStepKey key;
+    key.params = params; key.ws = workspace; key.rope_sin = rope_sin; key.rope_cos = rope_cos; key.B = B; key.S1 = S1; key.S2 = S2;
+    key.num_steps = num_steps;
+    key.normalize = auto_normalize; key.pred = pred_type; key.precision = p->precision; key.update = kind; key.clip = sc.clip_x0;
+    key.opt_epoch = options_epoch();
+    if (!p->step_exec || !(p->step_key == key)) {
+      drop_tfm_step_graph(p);
+      // the caller's stream may be the legacy default stream, which cannot be captured: capture on a stream of our own (nothing executes
+      // during capture) and launch the instantiated graph on the caller's stream
+      if (!p->cap_stream) DQ_HIP_OK(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
+      hipStream_t cs = p->cap_stream;
+      DQ_HIP_OK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+      int rc = sample_forward(net, xa, 0, w.step, w.eps, cs);
+      // (x in place: element-wise; the staged ids and seed at draw 0: the kernel adds the step counter)
+      if (!rc) rc = launch_step_update(upd, xa, w.eps, xa, nullptr, 0, w.step, StepNoise{w.ids_stage, w.seed_stage, 0}, false, cs);
+      if (!rc) rc = launch_inc_step(w.step, cs);
+      hipGraph_t g = nullptr;
+      const hipError_t ce = hipStreamEndCapture(cs, &g);
+      if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+      DQ_HIP_OK(ce);
+      p->step_graph = g;
+      DQ_HIP_OK(hipGraphInstantiate(&p->step_exec, g, nullptr, nullptr, 0));
+      p->step_key = key;
+    }
+    for (int i = 0; i < num_steps; ++i) DQ_HIP_OK(hipGraphLaunch(p->step_exec, s));
+    DQ_TRY(launch_sample_finish(xa, ms2_cond, out_x, out_noise, n, auto_normalize, s));
+    return 0;
+  }
+  for (int i = 0; i < num_steps; ++i) {
+    // eps objective: the network output IS the trajectory's eps; x0 objective, or a clamped x0: the derived eps goes to the trajectory
+    float* eps = traj_eps ? traj_eps + (int64_t)i * n : w.eps;
+    float* xn = traj_x ? traj_x + (int64_t)i * n : (in_place ? xa : xb);
+    DQ_TRY(sample_forward(net, xa, i, nullptr, eps, s));
+    // (the caller's ids and seed; step i draws at index 1 + i)
+    DQ_TRY(launch_step_update(upd, xa, eps, xn, (traj_eps && (px0 || sc.clip)) ? eps : nullptr, i, nullptr, StepNoise{window_ids_dev, seed_dev, 1 + i}, false, s));
+    if (traj_x) {
+      DQ_HIP_OK(hipMemcpyAsync(xa, xn, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    } else if (!in_place) {
+      std::swap(xa, xb);
+    }
+  }
+  DQ_TRY(launch_sample_finish(xa, ms2_cond, out_x, out_noise, n, auto_normalize, s));
+  return 0;
+}
+
+}  // extern "C"

@@ -356,6 +356,46 @@ __global__ void __launch_bounds__(256) k_seqsum(const float* __restrict__ x, int
   out[i] = s;
 }
 
+// sampling (dq_tfm_sample): k_rope_add forward with the time embedding of ONE step for every sample: row `row` of the (num_steps, H) table,
+// or the row the device-side step counter names
+__global__ void __launch_bounds__(256) k_rope_add_row(float* __restrict__ x, const float* __restrict__ sin_t, const float* __restrict__ cos_t,
+                                                      const float* __restrict__ temb_tab, int row, const int* __restrict__ step_ptr, int B, int S,
+                                                      int H) {
+  const int half = H >> 1;
+  const int64_t total = (int64_t)B * S * half;
+  const float* temb = temb_tab + (int64_t)(step_ptr ? *step_ptr : row) * H;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = e / half;
+    const int j = (int)(e - r * half), sidx = (int)(r % S);
+    float2* p = reinterpret_cast<float2*>(x + r * H) + j;
+    const float2 v = *p;
+    const float sn = sin_t[sidx * half + j], cs = cos_t[sidx * half + j];
+    float2 o;
+    o.x = v.x * cs - v.y * sn;
+    o.y = v.x * sn + v.y * cs;
+    o.x += temb[2 * j]; o.y += temb[2 * j + 1];
+    *p = o;
+  }
+}
+// k_cond_embed on (x_cond * cm + ca): the sampler's normalisation of the MS1 condition (2c - 1) in the same launch
+__global__ void __launch_bounds__(256) k_cond_embed_affine(const float* __restrict__ xc, float cm, float ca, const float* __restrict__ w,
+                                                           const float* __restrict__ bias, const float* __restrict__ sin_t,
+                                                           const float* __restrict__ cos_t, float* __restrict__ c, int B, int S, int H) {
+  const int half = H >> 1;
+  const int64_t total = (int64_t)B * S * half;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = e / half;
+    const int j = (int)(e - row * half), sidx = (int)(row % S);
+    const float xv = xc[row] * cm + ca;
+    const float v1 = xv * w[2 * j] + bias[2 * j], v2 = xv * w[2 * j + 1] + bias[2 * j + 1];
+    const float sn = sin_t[sidx * half + j], cs = cos_t[sidx * half + j];
+    float2 o;
+    o.x = v1 * cs - v2 * sn;
+    o.y = v1 * sn + v2 * cs;
+    reinterpret_cast<float2*>(c + row * H)[j] = o;
+  }
+}
+
 inline unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>(cdiv(n, 256), 8192); }
 }  // namespace
 
@@ -372,6 +412,23 @@ int launch_cond_embed(const float* x_cond, const float* w, const float* bias, co
   const int64_t total = (int64_t)B * S * (H / 2);
   if (total == 0) return 0;
   hipLaunchKernelGGL(k_cond_embed, dim3(grid_for(total)), dim3(256), 0, s, x_cond, w, bias, sin_t, cos_t, c, B, S, H);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
+int launch_rope_add_row(float* x, const float* sin_t, const float* cos_t, const float* temb_tab, int row, const int* step_ptr, int B, int S,
+                        int H, hipStream_t s) {
+  DQ_REQUIRE(H % 2 == 0, "rope: hidden_dim must be even");
+  const int64_t total = (int64_t)B * S * (H / 2);
+  if (total == 0) return 0;
+  hipLaunchKernelGGL(k_rope_add_row, dim3(grid_for(total)), dim3(256), 0, s, x, sin_t, cos_t, temb_tab, row, step_ptr, B, S, H);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
+int launch_cond_embed_affine(const float* x_cond, float cm, float ca, const float* w, const float* bias, const float* sin_t, const float* cos_t,
+                             float* c, int B, int S, int H, hipStream_t s) {
+  const int64_t total = (int64_t)B * S * (H / 2);
+  if (total == 0) return 0;
+  hipLaunchKernelGGL(k_cond_embed_affine, dim3(grid_for(total)), dim3(256), 0, s, x_cond, cm, ca, w, bias, sin_t, cos_t, c, B, S, H);
   DQ_LAUNCH_CHECK();
   return 0;
 }

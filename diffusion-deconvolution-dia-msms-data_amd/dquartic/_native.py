@@ -17,6 +17,7 @@ RES_FWD_FORMS = ("rt", "level", "v4", "unfused")  # DQ_RES_FWD_* (index = value)
 RES_BWD_FORMS = ("wg", "rt", "rows", "cp", "plain", "unfused")  # DQ_RES_BWD_*
 LA_FWD_FORMS = ("long", "small", "rows", "register")  # DQ_LA_FWD_*
 LA_BWD_FORMS = ("long", "rows", "register")  # DQ_LA_BWD_*
+TFM_ATTN_FORMS = ("gemm", "fused")  # DQ_TFM_ATTN_* (index = value)
 CONV_BWD_DATA_FORMS = ("wg", "gemm", "plain")  # DQ_CONV_BWD_DATA_*
 CONV_WGRAD_FORMS = ("wg", "v4", "scalar")  # DQ_CONV_WGRAD_*
 LEVEL_KINDS = ("unfused", "kernel", "tiny")  # DQ_LEVEL_* (index = value)
@@ -130,6 +131,11 @@ PROTOTYPES = {
     "dq_tfm_softmax_rows_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
     "dq_tfm_colsum": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "dq_tfm_seqsum": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p, c_void_p]),
+    "dq_tfm_attn_form": (c_int, [c_int, c_int, c_int]),
+    "dq_tfm_attn_fwd": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
+    "dq_tfm_sample_workspace_bytes": (c_int64, [c_void_p, c_int, c_int, c_int, c_int]),
+    "dq_tfm_sample": (c_int, [c_void_p] * 5 + [POINTER(c_float), c_int] + [c_void_p] * 3 + [c_int, c_int, POINTER(c_int32), c_int] + [c_void_p] * 4
+                      + [c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_float]),
     "dq_linattn_fwd": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_void_p]),
     "dq_linattn_bwd": (c_int, [c_void_p] * 15 + [c_int, c_int, c_int, c_void_p]),
     "dq_linattn_bwd_store": (c_int, [c_void_p] * 15 + [c_int, c_int, c_int, c_void_p]),

@@ -151,9 +151,12 @@ def build_model(m, device):
                                                        num_layers=c["num_layers"])).to(device)
     else:
         raise click.ClickException(f"Invalid model class: {m['use_model']}")  # reference cli.py:111 (ValueError there)
-    return DDIMDiffusionModel(model_class=net, num_timesteps=m["num_timesteps"], beta_schedule_type=m["beta_schedule_type"],
-                              pred_type=m["pred_type"], auto_normalize=m["auto_normalize"], ms1_loss_weight=m["ms1_loss_weight"],
-                              device=device)
+    dm = DDIMDiffusionModel(model_class=net, num_timesteps=m["num_timesteps"], beta_schedule_type=m["beta_schedule_type"],
+                            pred_type=m["pred_type"], auto_normalize=m["auto_normalize"], ms1_loss_weight=m["ms1_loss_weight"],
+                            device=device)
+    if m["use_model"] == "CustomTransformer":  # "native_sampler": true sends every sample() to the library's loop (off by default)
+        dm.native_tfm_sampler = bool(m["CustomTransformer"].get("native_sampler", False))
+    return dm
 
 
 def enable_ema_from_config(dm, m) -> bool:

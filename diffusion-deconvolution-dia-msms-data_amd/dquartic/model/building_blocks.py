@@ -65,6 +65,7 @@ class CustomTransformer(_FlatBuffers, nn.Module):
         self._reset_parameters()
         self.precision = "fp32"
         self._ws = {}
+        self._sample_ws = {}
         self._ws_pool = {}  # training workspaces of the autograd bridge: one per forward that still awaits its backward
         self._tables = {}
 
@@ -116,6 +117,21 @@ class CustomTransformer(_FlatBuffers, nn.Module):
             self._ws = {k: v for k, v in self._ws.items() if k[3] != bool(training)}
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             self._ws[key] = ws
+        return ws
+
+    def sample_workspace(self, B, S1, S2, num_steps):
+        """The workspace of ``dq_tfm_sample`` for this shape and step count (``dq_tfm_sample_workspace_bytes``), cached like
+        ``workspace()``: one at a time."""
+        dev = self._flat.device
+        key = (B, S1, S2, int(num_steps), str(dev))
+        ws = self._sample_ws.get(key)
+        if ws is None:
+            nbytes = N.lib().dq_tfm_sample_workspace_bytes(self._tfm, B, S1, S2, int(num_steps))
+            if nbytes <= 0:
+                raise RuntimeError("dq_tfm_sample_workspace_bytes failed (need B, S1, S2 > 0 and 1 <= num_steps <= 1024)")
+            self._sample_ws = {}
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self._sample_ws[key] = ws
         return ws
 
     def set_precision(self, precision: str):

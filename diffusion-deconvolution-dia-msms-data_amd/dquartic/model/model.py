@@ -95,6 +95,9 @@ class DDIMDiffusionModel(ModelInterface):
         self.ms1_loss_weight = ms1_loss_weight
         self._ab_host = None
         self.use_graph = True  # sample(): replay one hipGraph-captured step per timestep (an attribute, not an environment switch)
+        # sample() on a CustomTransformer behind its adapter: True sends every call to the library's loop (dq_tfm_sample); False (default)
+        # only the calls the generic loop cannot serve (eta > 0, seed, window_ids, x_t=None, another sampler, clip_x0, return_trajectory)
+        self.native_tfm_sampler = False
 
     # ------------------------------------------------------------------ helpers
     @property
@@ -265,7 +268,9 @@ class DDIMDiffusionModel(ModelInterface):
 
     def sample(self, x_t, ms2_cond=None, ms1_cond=None, num_steps=1000, return_trajectory=False, eta=0.0, seed=None, window_ids=None,
                shape=None, sampler="reference", clip_x0=None):
-        """model.py:293-324: returns (denoised, mixture - denoised).  Native loop when the network is UNet1d.
+        """model.py:293-324: returns (denoised, mixture - denoised).  Native loop when the network is UNet1d; for a CustomTransformer behind
+        ``DDIMTransformerAdapter`` the library's loop (``dq_tfm_sample``) serves every call when
+        ``native_tfm_sampler`` is set, and otherwise exactly the calls the generic loop refuses (the options below, ``return_trajectory``).
 
         ``eta`` in [0, 1]: 0 is the deterministic DDIM update, 1 ancestral (DDPM-like) sampling; the per-step noise
         is a counter-based generator inside the update kernel, keyed by (``seed``, window id, element, step), so a window's result does
@@ -282,19 +287,26 @@ class DDIMDiffusionModel(ModelInterface):
         stochastic = eta > 0.0 or x_t is None or seed is not None or window_ids is not None
         if sampler_id != 0:
             self._check_decreasing(self.sampler_timesteps(self.num_timesteps, num_steps).tolist())
-            if not (self.native and ms2_cond is not None and ms1_cond is not None and (x_t.is_cuda if x_t is not None else ms2_cond.is_cuda)):
+        on_gpu = ms2_cond is not None and ms1_cond is not None and (x_t.is_cuda if x_t is not None else ms2_cond.is_cuda)
+        if on_gpu and self._native_tfm and (self.native_tfm_sampler or stochastic or sampler_id != 0 or return_trajectory):
+            return self._sample_native_tfm(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
+                                           shape=shape, sampler=sampler_id, clip_x0=clip)
+        if sampler_id != 0:
+            if not (self.native and on_gpu):
                 raise NotImplementedError("sample: the 'ddim' and 'dpmpp_2m' samplers and clip_x0 need the native sampler (this package's "
-                                          "UNet1d on the GPU with both conditions); the generic loop is the reference update only")
+                                          "UNet1d, or its CustomTransformer behind DDIMTransformerAdapter, on the GPU with both "
+                                          "conditions); the generic loop is the reference update only")
             return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
                                        shape=shape, sampler=sampler_id, clip_x0=clip)
-        if self.native and ms2_cond is not None and ms1_cond is not None and (x_t.is_cuda if x_t is not None else ms2_cond.is_cuda):
+        if self.native and on_gpu:
             if not stochastic:
                 return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory)
             return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
                                        shape=shape)
         if stochastic:
-            raise NotImplementedError("sample: eta > 0, seed, window_ids and x_t=None need the native sampler (this package's UNet1d on "
-                                      "the GPU with both conditions); the generic loop is the deterministic update only")
+            raise NotImplementedError("sample: eta > 0, seed, window_ids and x_t=None need the native sampler (this package's UNet1d, or "
+                                      "its CustomTransformer behind DDIMTransformerAdapter, on the GPU with both conditions); the "
+                                      "generic loop is the deterministic update only")
         ms2n = self.normalize(ms2_cond) if ms2_cond is not None else None
         ms1n = self.normalize(ms1_cond) if ms1_cond is not None else None
         pred_noise = None
@@ -355,6 +367,52 @@ class DDIMDiffusionModel(ModelInterface):
                                        N.ptr(out_x), N.ptr(out_n),
                                        N.ptr(traj_x), N.ptr(traj_e), 1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws),
                                        ws.numel(), B, RT, N.stream_ptr()), "dq_ddim_sample")
+        if return_trajectory:
+            return out_x, out_n, traj_x, traj_e
+        return out_x, out_n
+
+    @property
+    def _native_tfm(self) -> bool:
+        from .building_blocks import CustomTransformer, DDIMTransformerAdapter
+
+        return isinstance(self.model, DDIMTransformerAdapter) and isinstance(self.model.transformer, CustomTransformer)
+
+    def _sample_native_tfm(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False, eta=0.0, seed=None, window_ids=None, shape=None,
+                           sampler=0, clip_x0=0.0):
+        """``dq_tfm_sample``: the whole loop in the library for the transformer behind its adapter (``ms1_cond`` (B, RT) or (B, RT, 1) is
+        its conditional sequence; ``ms2_cond`` only enters ``mixture - denoised``)."""
+        tfm = self.model.transformer
+        f32 = lambda v: v.detach().to(torch.float32).contiguous()
+        if x_T is None:
+            if seed is None and not eta:
+                raise ValueError("sample: x_t=None needs a seed (x_T is drawn from it)")
+            B, S1, D = tuple(shape) if shape is not None else tuple(ms2_cond.shape)
+        else:
+            B, S1, D = x_T.shape
+            x_T = f32(x_T)
+        c2, c1 = f32(ms2_cond), f32(ms1_cond)
+        if c1.dim() == 3:
+            c1 = c1[..., 0].contiguous()
+        if D != tfm.input_dim or tuple(c2.shape) != (B, S1, D):
+            raise ValueError(f"sample: x_t and ms2_cond must be (batch, seqlen1, input_dim={tfm.input_dim})")
+        if c1.dim() != 2 or c1.shape[0] != B:
+            raise ValueError("sample: ms1_cond must be (batch, seqlen2) or (batch, seqlen2, 1)")
+        S2 = c1.shape[1]
+        flat = tfm.read_params(False)  # (the averaged weights inside ModelInterface.ema_scope())
+        ws = tfm.sample_workspace(B, S1, S2, num_steps)
+        sin, cos, freqs = tfm.tables(max(S1, S2), c2.device)
+        ts_c = (ctypes.c_int32 * num_steps)(*self.sampler_timesteps(self.num_timesteps, num_steps).to(torch.int32).tolist())
+        out_x, out_n = torch.empty_like(c2), torch.empty_like(c2)
+        traj_x = torch.empty((num_steps, B, S1, D), device=c2.device) if return_trajectory else None
+        traj_e = torch.empty((num_steps, B, S1, D), device=c2.device) if return_trajectory else None
+        seed_dev = self._seed_tensor(seed, c2.device) if (seed is not None or eta > 0.0 or x_T is None) else None
+        ids_dev = self._ids_tensor(window_ids, B, c2.device)
+        self.last_seed = None if seed_dev is None else int(seed_dev.item()) & (2 ** 64 - 1)  # (what a seed=None call drew)
+        N.check(N.lib().dq_tfm_sample(tfm._tfm, N.ptr(flat), N.ptr(sin), N.ptr(cos), N.ptr(freqs), self._alpha_bars_host(), int(self.num_timesteps),
+                                      N.ptr(x_T), N.ptr(c2), N.ptr(c1), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], ts_c,
+                                      num_steps, N.ptr(out_x), N.ptr(out_n), N.ptr(traj_x), N.ptr(traj_e),
+                                      1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws), ws.numel(), B, S1, S2, N.stream_ptr(),
+                                      float(eta), N.ptr(seed_dev), N.ptr(ids_dev), int(sampler), float(clip_x0)), "dq_tfm_sample")
         if return_trajectory:
             return out_x, out_n, traj_x, traj_e
         return out_x, out_n

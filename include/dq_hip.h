@@ -52,7 +52,8 @@ const char* dq_last_error(void);
  * dq_debug_gemm_plan; DQ_SAMPLER_*, dq_sampler_coef_table, dq_solver_step, dq_ddim_sample_solver; dq_debug_layout, dq_debug_mid_forms,
  * dq_debug_mid_fwd, dq_debug_mid_bwd; dq_tfm_layernorm_form and the stand-alone kernels of the transformer: dq_tfm_rope_add,
  * dq_tfm_cond_embed, dq_tfm_cond_embed_bwd, dq_tfm_time_features, dq_tfm_gelu, dq_tfm_gelu_bwd, dq_tfm_layernorm_fwd,
- * dq_tfm_layernorm_bwd, dq_tfm_softmax_rows, dq_tfm_softmax_rows_bwd, dq_tfm_colsum, dq_tfm_seqsum). */
+ * dq_tfm_layernorm_bwd, dq_tfm_softmax_rows, dq_tfm_softmax_rows_bwd, dq_tfm_colsum, dq_tfm_seqsum; the transformer's sampler:
+ * dq_tfm_attn_form, dq_tfm_attn_fwd, dq_tfm_sample_workspace_bytes, dq_tfm_sample). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -437,6 +438,33 @@ int dq_tfm_softmax_rows_bwd(const float* p, float* dp, int64_t rows, int n, int 
 int dq_tfm_colsum(const float* x, int M, int N, int64_t ld, float* out, float* scratch, int64_t scratch_floats, int accumulate,
                   void* stream);
 int dq_tfm_seqsum(const float* x, int B, int S, int N, float* out, void* stream);
+/* The inference attention of the transformer's sampling path (csrc/k_tfm_attn.hip; additive at ABI version 12): per (sample, head)
+ * o = softmax(q k^T / sqrt(dh)) v with q (B, S1, H), kv (B, Sk, 2H) = the K | V halves, o (B, S1, H), dh = H / heads; all 16-byte aligned.
+ * Two forms, both fp32 with a max-subtracted softmax and bitwise repeatable: DQ_TFM_ATTN_FUSED one launch that writes nothing but o (fp32
+ * VALU also when the handle's GEMMs run in bf16x3); DQ_TFM_ATTN_GEMM the training path's three launches (scores GEMM, softmax rows, PV GEMM)
+ * through prob_scratch (B * heads * S1 * up4(Sk) floats; unused and nullable for the fused form).  dq_tfm_attn_form (host only, no device
+ * needed): the form a sampling forward takes -- fused when dh % 4 == 0 and
+ *   4 * (Sk * (2 dh + 4) + 4 dh + 4 up4(Sk)) <= 160 KiB   (K, V and four waves' q and p rows in one CU's LDS),
+ * which holds for every Sk <= 68 at dh <= 128; -1 for a non-positive size.  dq_tfm_attn_fwd: form -1 = the chosen one, 0 / 1 forced;
+ * a forced fused form on a shape the predicate refuses is an error, never a silent fallback. */
+enum { DQ_TFM_ATTN_GEMM = 0, DQ_TFM_ATTN_FUSED = 1 };
+int dq_tfm_attn_form(int S1, int Sk, int dh);
+int dq_tfm_attn_fwd(const float* q, const float* kv, float* o, float* prob_scratch, int B, int S1, int Sk, int H, int heads, int form,
+                    void* stream);
+/* Sampling from the transformer in one call (csrc/dq_tfm_sample.hip): dq_ddim_sample_solver's loop -- the same
+ * tables, updates, draw indexing (x_T at 0, step i at 1 + i), refusals (worded alike, before anything touches the device) and final
+ * un-normalisation -- around a sampling forward of this network.  x_T (B, S1, input_dim; NULL: drawn from the seed), ms2_cond like x_T (the
+ * network ignores it: out_noise = mixture - out_x), ms1_cond (B, S2).  Once per call, before the loop: the conditional embedding of ms1_cond
+ * (2c - 1 first when auto_normalize), every layer's K | V rows of it, and the time embedding of every step; a step then projects only the x_t
+ * rows and runs the attention by dq_tfm_attn_form.  use_graph != 0 without trajectories: one step is captured once, cached on the handle
+ * (dropped by dq_tfm_set_precision and dq_tfm_destroy) and replayed num_steps times; seed and ids are staged in the workspace.
+ * workspace: dq_tfm_sample_workspace_bytes(tfm, B, S1, S2, num_steps) bytes, 16-byte aligned. */
+int64_t dq_tfm_sample_workspace_bytes(const dq_tfm* tfm, int B, int S1, int S2, int num_steps);
+int dq_tfm_sample(dq_tfm* tfm, const float* params, const float* rope_sin, const float* rope_cos, const float* time_freqs,
+                  const float* alpha_bars_host, int num_timesteps, const float* x_T, const float* ms2_cond, const float* ms1_cond,
+                  int auto_normalize, int pred_type, const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise,
+                  float* traj_x, float* traj_eps, int use_graph, void* workspace, int64_t workspace_bytes, int B, int S1, int S2,
+                  void* stream, float eta, const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0);
 /* The fp32 matrix-core GEMM underneath (exported for the parity tests and the roofline measurement):
  * C (M,N; ldc) = A B (+ bias[n]) with A(m,k) = a_kmajor ? A[m*lda+k] : A[k*lda+m] and B(k,n) = b_kmajor ? B[n*ldb+k] :
  * B[k*ldb+n]; splits = 0 lets the library choose a split-K factor; scratch: dq_gemm_scratch_floats(M,N,K) floats. */
