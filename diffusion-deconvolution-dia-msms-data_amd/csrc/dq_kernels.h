@@ -422,6 +422,7 @@ int launch_prep_inputs_bwd(const float* dcat0, const float* cond, float cm, floa
 int launch_im2col3(const float* x, float* xcol, int B, int C, int RT, int P, hipStream_t s);                  // (B,C,P) -> (B,3C,P)
 int launch_col2im3(const float* dxcol, float* dx, int B, int C, int RT, int P, int accumulate, hipStream_t s);  // transpose of it
 int launch_repitch(float* dst, int dpitch, const float* src, int spitch, int64_t rows, int n, hipStream_t s);
+int launch_zero_pads(float* x, int64_t rows, int RT, int P, hipStream_t s);  // (rows, P): columns t >= RT <- 0
 int launch_wnorm_fwd(const float* u, const float* g, const float* ss, int ss_stride, int act, const float* res, float* y, int B, int C,
                      int RT, int P, hipStream_t s);
 // scratch: B * (2 P + 2 C) floats; dg / dss / dbias +=

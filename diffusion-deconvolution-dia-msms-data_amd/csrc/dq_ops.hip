@@ -550,7 +550,9 @@ int wide_gemm(const Ctx& c, const float* A, int a_kmajor, int64_t lda, const flo
   g.M = M; g.N = N; g.K = K; g.batch = c.B; g.sBo = b_rows * c.ar.P; g.sCo = c_rows * c.ar.P;
   g.bias_m = bias_m; g.accumulate = accumulate;
   g.partial = c.w(c.ar.w_gemm_part); g.partial_floats = c.ar.w_gemm_part_floats;
-  return launch_gemm(g, c.s);
+  DQ_TRY(launch_gemm(g, c.s));
+  // the product stores its N valid columns: a stored C is a first writer and owes the slot its zero pads (an accumulated-into C has them)
+  return accumulate ? 0 : launch_zero_pads(C, (int64_t)c.B * c_rows, N, c.ar.P, c.s);
 }
 // dW (M x N; ldc = N) += sum_b dY_b (M x RT) X_b^T (RT x N): dY, X are (B, ., P) tensors.  ONE product whose reduction runs over the
 // samples (Gemm::kbatch): dW -- 1.2 GB for the shipped 10000 x 30000 conv -- is read and written once, not once per sample.

@@ -358,4 +358,59 @@ int dq_attn_bwd(const float* q, const float* k, const float* v, const float* o, 
   return launch_attn_bwd(q, bs, k, bs, v, bs, o, d_o, lse, delta, dq_, bs, dk, bs, dv, bs, B, RT, (hipStream_t)stream);
 }
 
+// ---- the wide bottleneck's kernels (k_wide.hip) alone, for tests/test_wide_mid.py: the launchers wide_res_fwd / wide_res_bwd / mid_*_wide call,
+// on caller tensors (B, C, P).  Every entry checks its arguments before it launches.
+namespace {
+bool wide_shape_ok(int B, int C, int RT, int P) { return B > 0 && C > 0 && RT > 0 && P >= RT && P < RT + 4 && P % 4 == 0; }
+}  // namespace
+
+int dq_wide_im2col3(const float* x, float* xcol, int B, int C, int RT, int P, void* stream) {
+  DQ_REQUIRE(x && xcol, "dq_wide_im2col3: null argument");
+  DQ_REQUIRE(wide_shape_ok(B, C, RT, P), "dq_wide_im2col3: B, C, RT positive, P the multiple of 4 in [RT, RT + 4)");
+  return launch_im2col3(x, xcol, B, C, RT, P, (hipStream_t)stream);
+}
+int dq_wide_col2im3(const float* dxcol, float* dx, int B, int C, int RT, int P, int accumulate, void* stream) {
+  DQ_REQUIRE(dxcol && dx, "dq_wide_col2im3: null argument");
+  DQ_REQUIRE(wide_shape_ok(B, C, RT, P), "dq_wide_col2im3: B, C, RT positive, P the multiple of 4 in [RT, RT + 4)");
+  return launch_col2im3(dxcol, dx, B, C, RT, P, accumulate != 0, (hipStream_t)stream);
+}
+int dq_wide_repitch(float* dst, int dpitch, const float* src, int spitch, int64_t rows, int n, void* stream) {
+  DQ_REQUIRE(dst && src, "dq_wide_repitch: null argument");
+  DQ_REQUIRE(rows > 0 && n > 0 && dpitch >= n && spitch >= n && dpitch < n + 4 && spitch < n + 4 && (dpitch % 4 == 0 || spitch % 4 == 0),
+             "dq_wide_repitch: rows, n positive, both pitches in [n, n + 4), the padded one a multiple of 4");
+  return launch_repitch(dst, dpitch, src, spitch, rows, n, (hipStream_t)stream);
+}
+int dq_wide_norm_fwd(const float* u, const float* g, const float* ss, int ss_stride, int act, const float* res, float* y, int B, int C, int RT,
+                     int P, void* stream) {
+  DQ_REQUIRE(u && g && y, "dq_wide_norm_fwd: null argument");
+  DQ_REQUIRE(wide_shape_ok(B, C, RT, P), "dq_wide_norm_fwd: B, C, RT positive, P the multiple of 4 in [RT, RT + 4)");
+  DQ_REQUIRE(!ss || ss_stride >= 2 * C, "dq_wide_norm_fwd: a sample's [scale | shift] is 2 C floats: ss_stride >= 2 C");
+  DQ_REQUIRE(act == ACT_NONE || act == ACT_SILU, "dq_wide_norm_fwd: act must be 0 (none) or 1 (SiLU)");
+  return launch_wnorm_fwd(u, g, ss, ss_stride, act, res, y, B, C, RT, P, (hipStream_t)stream);
+}
+int64_t dq_wide_norm_bwd_scratch_floats(int B, int C, int P) {
+  if (B <= 0 || C <= 0 || P <= 0) return -1;
+  return (int64_t)B * (2 * (int64_t)P + 2 * (int64_t)C);
+}
+int dq_wide_norm_bwd(const float* u, const float* dy, const float* g, const float* ss, int ss_stride, int act, float* du, float* dg, float* dss,
+                     float* dbias, float* scratch, int64_t scratch_floats, int B, int C, int RT, int P, void* stream) {
+  DQ_REQUIRE(u && dy && g && du && dg && scratch, "dq_wide_norm_bwd: null argument");
+  DQ_REQUIRE(wide_shape_ok(B, C, RT, P), "dq_wide_norm_bwd: B, C, RT positive, P the multiple of 4 in [RT, RT + 4)");
+  DQ_REQUIRE(!ss || dss, "dq_wide_norm_bwd: scale / shift needs a gradient buffer (dss)");
+  DQ_REQUIRE(!ss || ss_stride >= 2 * C, "dq_wide_norm_bwd: a sample's [scale | shift] is 2 C floats: ss_stride >= 2 C");
+  DQ_REQUIRE(act == ACT_NONE || act == ACT_SILU, "dq_wide_norm_bwd: act must be 0 (none) or 1 (SiLU)");
+  DQ_REQUIRE(scratch_floats >= dq_wide_norm_bwd_scratch_floats(B, C, P), "dq_wide_norm_bwd: scratch too small");
+  return launch_wnorm_bwd(u, dy, g, ss, ss_stride, act, du, dg, dss, dbias, scratch, B, C, RT, P, (hipStream_t)stream);
+}
+int dq_wide_rowsum(const float* x, int64_t rows, int RT, int P, float* out, void* stream) {
+  DQ_REQUIRE(x && out, "dq_wide_rowsum: null argument");
+  DQ_REQUIRE(rows > 0 && wide_shape_ok(1, 1, RT, P), "dq_wide_rowsum: rows, RT positive, P the multiple of 4 in [RT, RT + 4)");
+  return launch_rowsum(x, rows, RT, P, out, (hipStream_t)stream);
+}
+int dq_wide_sum_b(const float* part, int B, int C, float* dst, void* stream) {
+  DQ_REQUIRE(part && dst, "dq_wide_sum_b: null argument");
+  DQ_REQUIRE(B > 0 && C > 0, "dq_wide_sum_b: B and C must be positive");
+  return launch_sum_b(part, B, C, dst, (hipStream_t)stream);
+}
+
 }  // extern "C"

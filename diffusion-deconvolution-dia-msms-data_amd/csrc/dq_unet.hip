@@ -1083,52 +1083,78 @@ int dq_debug_mid_forms(dq_plan* plan, int B, int RT, int32_t* out, int cap) {
   return n;
 }
 
-// The narrow bottleneck alone, forward: the time embedding (tbuf and every scale / shift head), then -- unless skip_ms1, as in unet_forward,
-// where the sampler's prologue has done it -- unet_prepare (of which the bottleneck reads the aligned copies of the attention's projection
-// weights; the level and tiny operand images it also writes belong to launches this entry never makes), then mid_forward on the mid_in / ms1f
-// the caller wrote into their workspace slots.  skip_ms1: the rotated kk too is the caller's, and a call without skip_ms1 has run on this
-// workspace with these parameters before (the prepared weight slots are its).
-int dq_debug_mid_fwd(dq_plan* plan, const float* params, const float* rope_freqs, const int64_t* t, int save_for_bwd, int skip_ms1,
-                     void* workspace, int64_t workspace_bytes, int B, int RT, void* stream) {
-  DQ_REQUIRE(plan && params && t && workspace, "dq_debug_mid_fwd: null argument");
-  DQ_REQUIRE(B > 0 && RT > 0, "dq_debug_mid_fwd: B and RT must be positive");
-  DQ_REQUIRE(!plan->plan.wide_mid, "dq_debug_mid_fwd: the wide bottleneck (k_wide.hip) is not this entry's");
+// The bottleneck alone, forward: the time embedding (tbuf and every scale / shift head), then -- unless skip_ms1, as in unet_forward, where
+// the sampler's prologue has done it -- unet_prepare (of which the narrow bottleneck reads the aligned copies of the attention's projection
+// weights; the level and tiny operand images it also writes belong to launches these entries never make), then the bottleneck as
+// unet_forward calls it.  Narrow (dq_debug_mid_fwd): mid_forward on the mid_in / ms1f the caller wrote into their workspace slots; skip_ms1:
+// the rotated kk too is the caller's, and a call without skip_ms1 has run on this workspace with these parameters before (the prepared
+// weight slots are its).  Wide (dq_debug_wide_mid_fwd): mid_forward_wide on the last down level's output, folds included.
+static int debug_mid_fwd(const char* who, bool wide, dq_plan* plan, const float* params, const float* rope_freqs, const int64_t* t,
+                         int save_for_bwd, int skip_ms1, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream) {
+  const std::string w(who);
+  DQ_REQUIRE(plan && params && t && workspace, w + ": null argument");
+  DQ_REQUIRE(B > 0 && RT > 0, w + ": B and RT must be positive");
+  DQ_REQUIRE(plan->plan.wide_mid == wide, w + (wide ? ": the narrow bottleneck (16 / 32 channels) is not this entry's"
+                                                    : ": the wide bottleneck (k_wide.hip) is not this entry's"));
   Arena probe;
   layout_arena(plan->plan, B, RT, probe);
-  DQ_REQUIRE(workspace_bytes >= (int64_t)sizeof(float) * probe.floats, "dq_debug_mid_fwd: workspace too small");
+  DQ_REQUIRE(workspace_bytes >= (int64_t)sizeof(float) * probe.floats, w + ": workspace too small");
   DQ_TRY(ensure_arena(plan, B, RT));
   Ctx c{plan->plan, plan->arena, params, (float*)workspace, nullptr, nullptr, B, RT, (hipStream_t)stream};
   c.save = save_for_bwd != 0;
   const LevelPlan lp = level_plan(c.p, c.ar, B, RT, c.save, false);
   DQ_TRY(launch_time_embed_fwd(c.p, plan->dev, c.P, t, 0, c.w(c.ar.tbuf), c.w(c.ar.ss), B, nullptr, nullptr, c.s));
   if (!skip_ms1) DQ_TRY(unet_prepare(c, lp, c.s));
+  if (wide) return mid_forward_wide(c, rope_freqs, c.w(c.ar.downs[c.p.levels - 1].rs));
   return mid_forward(c, rope_freqs, skip_ms1 != 0, lp.prep_ok);
 }
 
-// The narrow bottleneck alone, backward: d mid2.out is what the caller wrote into the twin of mid2 (everything else of the twin's
-// accumulated-into region is cleared, as unet_backward clears it); mid_backward inside unet_backward's scaffolding (bwd_open / bwd_close), with
-// the side queue (grad_x_mode 0) or all on the caller's stream (1).  No time-embedding backward, no MS1 path: the twin keeps d mid_in, d ms1f
-// and, in the twin of ss, both blocks' per-sample d(scale, shift); grads receives += of the bottleneck's parameter gradients.
-int dq_debug_mid_bwd(dq_plan* plan, const float* params, const float* rope_freqs, float* grads, int grad_x_mode, void* workspace,
-                     int64_t workspace_bytes, int B, int RT, void* stream) {
-  DQ_REQUIRE(plan && params && grads && workspace, "dq_debug_mid_bwd: null argument");
-  DQ_REQUIRE(B > 0 && RT > 0, "dq_debug_mid_bwd: B and RT must be positive");
-  DQ_REQUIRE(!plan->plan.wide_mid, "dq_debug_mid_bwd: the wide bottleneck (k_wide.hip) is not this entry's");
+// The bottleneck alone, backward: the gradient of the bottleneck's output is what the caller wrote into the twin (narrow: of mid2; wide: of
+// mid_back); everything else of the twin's accumulated-into region is cleared, as unet_backward clears it; then mid_backward /
+// mid_backward_wide inside unet_backward's scaffolding (bwd_open / bwd_close), with the side queue (grad_x_mode 0) or all on the caller's
+// stream (1).  No time-embedding backward, no MS1 path: the twin keeps d mid_in (wide: d of the last down level's output), d ms1f and, in
+// the twin of ss, both blocks' per-sample d(scale, shift); grads receives += of the bottleneck's parameter gradients.
+static int debug_mid_bwd(const char* who, bool wide, dq_plan* plan, const float* params, const float* rope_freqs, float* grads,
+                         int grad_x_mode, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream) {
+  const std::string w(who);
+  DQ_REQUIRE(plan && params && grads && workspace, w + ": null argument");
+  DQ_REQUIRE(B > 0 && RT > 0, w + ": B and RT must be positive");
+  DQ_REQUIRE(plan->plan.wide_mid == wide, w + (wide ? ": the narrow bottleneck (16 / 32 channels) is not this entry's"
+                                                    : ": the wide bottleneck (k_wide.hip) is not this entry's"));
   Arena probe;
   layout_arena(plan->plan, B, RT, probe);
-  DQ_REQUIRE(workspace_bytes >= 2 * (int64_t)sizeof(float) * probe.floats, "dq_debug_mid_bwd: workspace too small (training=1)");
+  DQ_REQUIRE(workspace_bytes >= 2 * (int64_t)sizeof(float) * probe.floats, w + ": workspace too small (training=1)");
   DQ_TRY(ensure_arena(plan, B, RT));
   const Arena& a = plan->arena;
   float* W = (float*)workspace;
   Ctx c_in{plan->plan, a, params, W, W + a.floats, grads, B, RT, (hipStream_t)stream};
-  c_in.owner = plan->no_side ? nullptr : plan;
+  // (the wide bottleneck's backward takes no grad_x: what it queues rides on the side queue whenever the pass has one)
+  c_in.owner = plan->no_side || (wide && grad_x_mode) ? nullptr : plan;
   plan->twin_zeroed = nullptr;
   BwdQueues queues;
   const Ctx c = bwd_open(c_in, queues);
   const LevelPlan lp = level_plan(c.p, a, B, RT, true, true);
-  DQ_TRY(bwd_clear_twin(c, a.mid2.out, (int64_t)B * c.p.mid_c * RT));
-  DQ_TRY(mid_backward(c, rope_freqs, grad_x_mode != 0, lp.prep_ok));
+  DQ_TRY(bwd_clear_twin(c, wide ? a.mid_back : a.mid2.out, (int64_t)B * c.p.mid_c * RT));
+  if (wide) DQ_TRY(mid_backward_wide(c, rope_freqs));
+  else DQ_TRY(mid_backward(c, rope_freqs, grad_x_mode != 0, lp.prep_ok));
   return bwd_close(c, queues);
+}
+
+int dq_debug_mid_fwd(dq_plan* plan, const float* params, const float* rope_freqs, const int64_t* t, int save_for_bwd, int skip_ms1,
+                     void* workspace, int64_t workspace_bytes, int B, int RT, void* stream) {
+  return debug_mid_fwd("dq_debug_mid_fwd", false, plan, params, rope_freqs, t, save_for_bwd, skip_ms1, workspace, workspace_bytes, B, RT, stream);
+}
+int dq_debug_mid_bwd(dq_plan* plan, const float* params, const float* rope_freqs, float* grads, int grad_x_mode, void* workspace,
+                     int64_t workspace_bytes, int B, int RT, void* stream) {
+  return debug_mid_bwd("dq_debug_mid_bwd", false, plan, params, rope_freqs, grads, grad_x_mode, workspace, workspace_bytes, B, RT, stream);
+}
+int dq_debug_wide_mid_fwd(dq_plan* plan, const float* params, const float* rope_freqs, const int64_t* t, int save_for_bwd, void* workspace,
+                          int64_t workspace_bytes, int B, int RT, void* stream) {
+  return debug_mid_fwd("dq_debug_wide_mid_fwd", true, plan, params, rope_freqs, t, save_for_bwd, 0, workspace, workspace_bytes, B, RT, stream);
+}
+int dq_debug_wide_mid_bwd(dq_plan* plan, const float* params, const float* rope_freqs, float* grads, int grad_x_mode, void* workspace,
+                          int64_t workspace_bytes, int B, int RT, void* stream) {
+  return debug_mid_bwd("dq_debug_wide_mid_bwd", true, plan, params, rope_freqs, grads, grad_x_mode, workspace, workspace_bytes, B, RT, stream);
 }
 
 int64_t dq_debug_tensor_offset(dq_plan* plan, const char* name) {
@@ -1155,6 +1181,25 @@ int64_t dq_debug_tensor_offset(dq_plan* plan, const char* name) {
   if (n == "mid2.u2") return a.mid2.u2;
   if (n == "mid2.a1") return a.mid2.a1;
   if (n == "lse") return a.lse;
+  if (n == "mid_back") return a.mid_back;
+  if (a.P > 0) {  // the wide bottleneck's (B, channels, P) slots
+    if (n == "w_mid_in") return a.w_mid_in;
+    if (n == "w_xn") return a.w_xn;
+    if (n == "w_qv") return a.w_qv;
+    if (n == "w_o") return a.w_o;
+    if (n == "w_attn_out") return a.w_attn_out;
+    if (n == "w_xcol") return a.w_xcol;  // (scratch: the im2col buffer, the norm backward's sums, the GEMM's partial products)
+    if (n == "w_stats") return a.w_stats;
+    if (n == "w_gemm_part") return a.w_gemm_part;
+    for (int i = 0; i < 2; ++i) {
+      const WideResBuf& w = i ? a.wmid2 : a.wmid1;
+      const std::string k = i ? "wmid2" : "wmid1";
+      if (n == k) return w.out;
+      if (n == k + ".u1") return w.u1;
+      if (n == k + ".a1") return w.a1;
+      if (n == k + ".u2") return w.u2;
+    }
+  }
   if (n == "@twin") return a.floats;  // the gradient twin G starts this many floats behind the workspace's start (a training workspace)
   if (n == "fin") return a.fin.out;
   if (n == "eps") return a.eps;  // (its gradient twin: d loss / d final_conv's output when the Softplus head's backward ran)

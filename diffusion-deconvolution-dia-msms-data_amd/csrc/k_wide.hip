@@ -4,8 +4,15 @@
 // channels, and 80 at an odd test shape (MZ = 320).  For those the two ResnetBlocks and the attention projections run as
 //   im2col (k = 3, zero padded)  ->  fp32 matrix-core GEMM (k_gemm.hip)  ->  RMSNorm over the channel axis + scale/shift + SiLU
 // with the pieces below.  Tensors are (B, C, P): P = the RT axis padded to a multiple of 4 floats (the GEMM reads 16-byte
-// vectors along rows), t < RT valid.  Every kernel here writes ZERO into the pad columns of its outputs.
-// All reductions are fixed-order (no atomics).
+// vectors along rows), t < RT valid.  All reductions are fixed-order (no atomics).
+// Contracts (tests/test_wide_mid.py pins each, kernel by kernel and through the whole bottleneck):
+//   - pads are always written, always zero: every kernel here stores 0 into the pad columns of its outputs whatever they held (the slots are
+//     never cleared) and never lets an input's pad column reach a valid output; a GEMM stores its N = RT columns only, so wide_gemm
+//     (dq_ops.hip) sends launch_zero_pads behind every product that is a slot's first writer;
+//   - du may alias dy in launch_wnorm_bwd (the PreNorm backward runs in place): k_wnorm_bwd_stats stores to the scratch alone, and in
+//     k_wnorm_bwd_apply the thread that stores du[t] is the only reader of dy[t] and has read it;
+//   - d g, d bias and the per-sample d(scale, shift) are += : dss straight from k_wnorm_bwd_apply (one wave owns a (b, c)), d g and d bias
+//     as ONE `dst += sum over b` of the per-sample partials (k_sum_b).
 #include "dq_common.h"
 #include "dq_kernels.h"
 
@@ -75,6 +82,22 @@ int launch_repitch(float* dst, int dpitch, const float* src, int spitch, int64_t
   const int64_t total = rows * dpitch;
   if (total == 0) return 0;
   hipLaunchKernelGGL(k_repitch, dim3(cdiv(total, 256)), dim3(256), 0, s, dst, dpitch, src, spitch, n, total);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
+
+// x (rows, P): zero into the pad columns t >= RT.  Behind a product whose output is a (B, C, P) tensor: the GEMM stores its N = RT columns
+// and nothing else, and the slot is never cleared (take_nz).
+__global__ void __launch_bounds__(256) k_zero_pads(float* __restrict__ x, int RT, int P, int64_t total) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int npad = P - RT;
+  x[(i / npad) * P + RT + (int)(i % npad)] = 0.f;
+}
+int launch_zero_pads(float* x, int64_t rows, int RT, int P, hipStream_t s) {
+  const int64_t total = rows * (P - RT);
+  if (total <= 0) return 0;
+  hipLaunchKernelGGL(k_zero_pads, dim3(cdiv(total, 256)), dim3(256), 0, s, x, RT, P, total);
   DQ_LAUNCH_CHECK();
   return 0;
 }

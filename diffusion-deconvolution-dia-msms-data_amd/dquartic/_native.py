@@ -99,6 +99,8 @@ PROTOTYPES = {
     "dq_debug_mid_forms": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32), c_int]),
     "dq_debug_mid_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "dq_debug_mid_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "dq_debug_wide_mid_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "dq_debug_wide_mid_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "dq_tfm_create": (c_void_p, [c_int, c_int, c_int, c_int]),
     "dq_tfm_destroy": (None, [c_void_p]),
     "dq_tfm_num_params": (c_int, [c_void_p]),
@@ -164,6 +166,14 @@ PROTOTYPES = {
     "dq_rope": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_void_p]),
     "dq_attn_fwd": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p]),
     "dq_attn_bwd": (c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p]),
+    "dq_wide_im2col3": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "dq_wide_col2im3": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
+    "dq_wide_repitch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_void_p]),
+    "dq_wide_norm_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "dq_wide_norm_bwd_scratch_floats": (c_int64, [c_int] * 3),
+    "dq_wide_norm_bwd": (c_int, [c_void_p] * 4 + [c_int, c_int] + [c_void_p] * 5 + [c_int64] + [c_int] * 4 + [c_void_p]),
+    "dq_wide_rowsum": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "dq_wide_sum_b": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 
 

@@ -53,7 +53,9 @@ const char* dq_last_error(void);
  * dq_debug_mid_fwd, dq_debug_mid_bwd; dq_tfm_layernorm_form and the stand-alone kernels of the transformer: dq_tfm_rope_add,
  * dq_tfm_cond_embed, dq_tfm_cond_embed_bwd, dq_tfm_time_features, dq_tfm_gelu, dq_tfm_gelu_bwd, dq_tfm_layernorm_fwd,
  * dq_tfm_layernorm_bwd, dq_tfm_softmax_rows, dq_tfm_softmax_rows_bwd, dq_tfm_colsum, dq_tfm_seqsum; the transformer's sampler:
- * dq_tfm_attn_form, dq_tfm_attn_fwd, dq_tfm_sample_workspace_bytes, dq_tfm_sample). */
+ * dq_tfm_attn_form, dq_tfm_attn_fwd, dq_tfm_sample_workspace_bytes, dq_tfm_sample; the wide bottleneck alone: dq_wide_im2col3,
+ * dq_wide_col2im3, dq_wide_repitch, dq_wide_norm_fwd, dq_wide_norm_bwd, dq_wide_norm_bwd_scratch_floats, dq_wide_rowsum, dq_wide_sum_b,
+ * dq_debug_wide_mid_fwd, dq_debug_wide_mid_bwd). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -641,8 +643,39 @@ int dq_attn_fwd(const float* q, const float* k, const float* v, float* o, float*
 int dq_attn_bwd(const float* q, const float* k, const float* v, const float* o, const float* d_o, const float* lse, float* delta,
                 float* dq, float* dk, float* dv, int B, int RT, void* stream);
 
+/* ---- the wide bottleneck's kernels alone (csrc/k_wide.hip; tests/test_wide_mid.py) ------------------------------------------------
+ * The launchers the wide bottleneck (every mid_c but 16 and 32) is made of, on caller tensors.  A tensor is (B, C, P): P = RT rounded up to a
+ * multiple of 4 floats (RT <= P < RT + 4), columns t < RT valid, the rest pad.  Every kernel writes ZERO into the pad columns of its outputs
+ * and never lets an input's pad columns reach a valid output.  All reductions are fixed-order: a repeated call is bitwise identical.  Each
+ * entry refuses null required operands, non-positive sizes, a P that is not the multiple of 4 in [RT, RT + 4) and (dq_wide_norm_bwd) a
+ * short scratch before any launch.
+ *
+ * dq_wide_im2col3: xcol (B, 3 C, P), xcol[b][3 c + k][t] = x[b][c][t + k - 1], zero outside [0, RT): Conv1d(k 3, padding 1) as a product.
+ * dq_wide_col2im3: its transpose, dx[b][c][t] (+)= sum_k dxcol[b][3 c + k][t - k + 1]; accumulate != 0: += on the valid columns.
+ * dq_wide_repitch: dst (rows, dpitch) <- src (rows, spitch), n valid columns, the rest of a dst row zero (one pitch is n .. n + 3 rounded to
+ *   a multiple of 4, the other anything in [n, n + 4): the attention kernels read rows of RT floats).
+ * dq_wide_norm_fwd: y = act(u / max(||u[b][:][t]||_2, 1e-12) * g[c] * sqrt(C) * (ss[b][c] + 1) + ss[b][C + c]) + res  (unet1d.py:113-140,
+ *   302-323).  ss (nullable): sample b's [scale (C) | shift (C)] at ss + b * ss_stride; act 0 none, 1 SiLU; res (nullable) (B, C, P).
+ * dq_wide_norm_bwd: du (B, C, P) = d loss / d u from dy = d loss / d y (without the residual); dg (C) += ; dss (same layout and stride as
+ *   ss; required with ss) += d [scale | shift]; dbias (C, nullable) += sum over (b, t) of du (the bias gradient of the conv that made u).
+ *   du may be dy (in place).  Where ||u|| < 1e-12 the forward is linear in u (the clamp) and so is du.  scratch:
+ *   dq_wide_norm_bwd_scratch_floats(B, C, P) = B (2 P + 2 C) floats (-1 for non-positive sizes).
+ * dq_wide_rowsum: out[r] = sum over t < RT of x (rows, P)[r][t].
+ * dq_wide_sum_b: dst[c] += sum over b (in order) of part (B, C)[b][c]. */
+int dq_wide_im2col3(const float* x, float* xcol, int B, int C, int RT, int P, void* stream);
+int dq_wide_col2im3(const float* dxcol, float* dx, int B, int C, int RT, int P, int accumulate, void* stream);
+int dq_wide_repitch(float* dst, int dpitch, const float* src, int spitch, int64_t rows, int n, void* stream);
+int dq_wide_norm_fwd(const float* u, const float* g, const float* ss, int ss_stride, int act, const float* res, float* y, int B, int C, int RT,
+                     int P, void* stream);
+int64_t dq_wide_norm_bwd_scratch_floats(int B, int C, int P);
+int dq_wide_norm_bwd(const float* u, const float* dy, const float* g, const float* ss, int ss_stride, int act, float* du, float* dg, float* dss,
+                     float* dbias, float* scratch, int64_t scratch_floats, int B, int C, int RT, int P, void* stream);
+int dq_wide_rowsum(const float* x, int64_t rows, int RT, int P, float* out, void* stream);
+int dq_wide_sum_b(const float* part, int B, int C, float* dst, void* stream);
+
 /* Test hook: offset (in floats) of a named activation inside the workspace laid out by the last call on this plan
- * ("h0", "ms1f", "down3", "down3.la", "mid1", "mid1.u1", "mid2.a1", "lse", "attn_out", "up0", "fin", "eps", ...), or -1.  "@twin": the
+ * ("h0", "ms1f", "down3", "down3.la", "mid1", "mid1.u1", "mid2.a1", "lse", "attn_out", "mid_back", "up0", "fin", "eps", ...; on a wide plan also its (B, channels, P) slots "w_mid_in", "wmid1", "wmid1.u1", "wmid1.a1",
+ * "wmid1.u2", the same of "wmid2", "w_xn", "w_qv", "w_o", "w_attn_out" and its scratch "w_xcol", "w_stats", "w_gemm_part"), or -1.  "@twin": the
  * distance in floats from the start of a training workspace to its gradient twin (a tensor's gradient lies at the tensor's offset there). */
 int64_t dq_debug_tensor_offset(dq_plan* plan, const char* name);
 
@@ -676,6 +709,23 @@ int dq_debug_mid_fwd(dq_plan* plan, const float* params, const float* rope_freqs
                      void* workspace, int64_t workspace_bytes, int B, int RT, void* stream);
 int dq_debug_mid_bwd(dq_plan* plan, const float* params, const float* rope_freqs, float* grads, int grad_x_mode, void* workspace,
                      int64_t workspace_bytes, int B, int RT, void* stream);
+
+/* Test hooks: the wide bottleneck (Plan::wide_mid, every mid_c but 16 and 32) alone: mid_forward_wide / mid_backward_wide as the passes call
+ * them, inside the scaffolding of dq_debug_mid_fwd / dq_debug_mid_bwd (time embedding, arena, the backward's queues, the clearing of the twin).
+ *
+ * dq_debug_wide_mid_fwd: the caller has written the last down level's output (B * RT, mid_c / mid_n, mid_n) into "down{L-1}" and ms1f
+ * (B, cond_dim, RT) into "ms1f".  Afterwards "mid_back" (B * RT, mid_c / mid_n, mid_n) holds the bottleneck's output, every wide slot its
+ * tensor (pads zero), "qv", "kk", "o", "lse" the attention's.
+ *
+ * dq_debug_wide_mid_bwd: behind it on the same training workspace, the caller has written d mid_back into the twin of "mid_back".
+ * grad_x_mode 0: with the side queue, 1: everything on `stream`.  The twins of "down{L-1}", "ms1f", "ss" and of every wide slot hold their
+ * gradients; grads has received += of mid_block1.*, mid_block2.* (but mlp.*) and mid_attn.*.
+ *
+ * Both refuse a narrow bottleneck, a short workspace, null arguments and B or RT < 1 before any device call. */
+int dq_debug_wide_mid_fwd(dq_plan* plan, const float* params, const float* rope_freqs, const int64_t* t, int save_for_bwd, void* workspace,
+                          int64_t workspace_bytes, int B, int RT, void* stream);
+int dq_debug_wide_mid_bwd(dq_plan* plan, const float* params, const float* rope_freqs, float* grads, int grad_x_mode, void* workspace,
+                          int64_t workspace_bytes, int B, int RT, void* stream);
 
 /* Test hook: which launch takes each U-Net level in a pass over (B, RT) windows -- the plan unet_forward / unet_backward / the sampler's
  * prologue build for themselves (the same rules, evaluated by the same function), without a workspace, a launch or a device.
