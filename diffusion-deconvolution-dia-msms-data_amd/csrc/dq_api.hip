@@ -64,8 +64,7 @@ void dq_plan_destroy(dq_plan* plan) {
   if (!plan) return;
   if (plan->dev.ss_w_off) (void)hipFree(plan->dev.ss_w_off);
   if (plan->dev.ss_b_off) (void)hipFree(plan->dev.ss_b_off);
-  drop_step_graph(plan);
-  if (plan->cap_stream) (void)hipStreamDestroy(plan->cap_stream);
+  plan->step.destroy();
   if (plan->side_stream) {
     (void)hipStreamDestroy(plan->side_stream);
     for (auto& e : plan->events) if (e) (void)hipEventDestroy(e);
@@ -93,7 +92,7 @@ int dq_plan_set_final_act(dq_plan* plan, int act) {
   DQ_REQUIRE(act == DQ_FINAL_IDENTITY || act == DQ_FINAL_SOFTPLUS,
              "dq_plan_set_final_act: act must be 0 (DQ_FINAL_IDENTITY) or 1 (DQ_FINAL_SOFTPLUS), got " + std::to_string(act));
   // a captured sampling step has the head's kernels baked in: never replay one captured under the other activation
-  drop_step_graph(plan);
+  plan->step.drop();
   plan->plan.final_act = act;
   return 0;
 }

@@ -1,9 +1,12 @@
 // What the sampling loops share (dq_sampler.hip): the refusals made before anything touches the device, the upload of a sampler's tables,
-// the staging of seed and window ids for a captured step, and the update behind a network forward.  The U-Net loop (dq_ddim_sample_solver)
-// and the transformer loop (dq_tfm_sample, dq_tfm_sample.hip) differ in the forward they put in front of it.  Internal: not installed.
+// the staging of seed and window ids for a captured step, the update behind a network forward, and the loop itself -- the captured step
+// with its replay, and the eager steps.  The U-Net loop (dq_ddim_sample_solver) and the transformer loop (dq_tfm_sample, dq_tfm_sample.hip)
+// differ in the forward they put in front of the update, literally: each hands the two functions below its StepForward, and in what it stages in front
+// of the loop.  Internal: not installed.
 #pragma once
 #include "dq_common.h"
-#include "dq_unet.h"  // StepUpdate
+#include "dq_unet.h"  // StepUpdate, StepGraph
+#include <functional>
 
 namespace dq {
 
@@ -42,4 +45,25 @@ int sampler_upload_tables(const char* who, const float* alpha_bars_host, int T, 
 // after the copies are done
 int sampler_stage_noise(uint64_t* seed_stage, int64_t* ids_stage, const uint64_t* seed_dev, const int64_t* window_ids_dev, int B, hipStream_t s);
 
+// One step's network forward on stream s, the one thing a loop brings of its own: the network output of x into net_out, at timestep and
+// table row `row` (the eager loop) or, with step_ptr, at the ones the device-side step counter names (the captured step).  A forward that
+// takes the update into its own launch writes the next x to x_out and sets *fused; want_eps: net_out is read behind the step (a trajectory).
+using StepForward = std::function<int(const float* x, float* x_out, int row, const int* step_ptr, float* net_out, bool want_eps, bool* fused, hipStream_t s)>;
+// What one call's steps run over.  xa: x_T on entry; upd.hist is xb: the 2M solver's x0 history, otherwise the other half of the ping-pong.
+// clip: the x0 estimate is clamped (the derived eps goes to the trajectory, as for the x0 objective).  The rest is launch_sample_finish's.
+struct SampleLoop {
+  StepForward forward;
+  StepUpdateArgs upd;
+  float *xa, *eps;
+  bool clip;
+  int num_steps;
+  const float* ms2_cond; float *out_x, *out_noise; int normalize;
+};
+// The captured step: unless `reusable` (the caller's g.exec && stored key == key) drops g's graph and captures forward, update (x in place,
+// the staged noise at draw 0: the kernel adds the step counter) and launch_inc_step(step) on g.cap_stream; then num_steps replays on s and
+// launch_sample_finish.  *captured: it captured anew and instantiated -- only then does the caller store its key, whatever is returned.
+int replay_captured_step(StepGraph& g, bool reusable, const SampleLoop& L, int* step, const StepNoise& staged, hipStream_t s, bool* captured);
+// The eager steps: x per step into its trajectory slot (copied back to xa), in place (the solvers) or ping-pong; eps into its trajectory slot
+// or the scratch; the caller's ids and seed, step i drawing at index 1 + i; then launch_sample_finish.
+int eager_steps(const SampleLoop& L, float* traj_x, float* traj_eps, const int64_t* window_ids_dev, const uint64_t* seed_dev, hipStream_t s);
 }  // namespace dq

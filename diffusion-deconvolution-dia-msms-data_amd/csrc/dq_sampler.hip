@@ -80,6 +80,57 @@ int sampler_stage_noise(uint64_t* seed_stage, int64_t* ids_stage, const uint64_t
   return 0;
 }
 
+// (the one loop of both networks, dq_tfm_sample.hip's too: dq_sampler.h)
+static int finish(const SampleLoop& L, const float* x, hipStream_t s) {
+  return launch_sample_finish(x, L.ms2_cond, L.out_x, L.out_noise, L.upd.B * L.upd.per, L.normalize, s);  // model.py:319-322
+}
+
+int replay_captured_step(StepGraph& g, bool reusable, const SampleLoop& L, int* step, const StepNoise& staged, hipStream_t s, bool* captured) {
+  *captured = false;
+  if (!reusable) {
+    g.drop();
+    // the caller's stream may be the legacy default stream, which cannot be captured: capture on a stream of our own (created on first use;
+    // nothing executes during capture) and launch the instantiated graph on the caller's stream
+    if (!g.cap_stream) DQ_HIP_OK(hipStreamCreateWithFlags(&g.cap_stream, hipStreamNonBlocking));
+    hipStream_t cs = g.cap_stream;
+    DQ_HIP_OK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+    bool fused = false;
+    int rc = L.forward(L.xa, L.xa, 0, step, L.eps, false, &fused, cs);  // (x in place: element-wise, read and written by the same lane; no eps out)
+    if (!rc) rc = launch_step_update(L.upd, L.xa, L.eps, L.xa, nullptr, 0, step, staged, fused, cs);
+    if (!rc) rc = launch_inc_step(step, cs);
+    hipGraph_t graph = nullptr;
+    const hipError_t ce = hipStreamEndCapture(cs, &graph);
+    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }  // (the forward failed: the capture is ended, its graph gone)
+    DQ_HIP_OK(ce);
+    g.graph = graph;
+    DQ_HIP_OK(hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
+    *captured = true;
+  }
+  for (int i = 0; i < L.num_steps; ++i) DQ_HIP_OK(hipGraphLaunch(g.exec, s));
+  return finish(L, L.xa, s);
+}
+
+int eager_steps(const SampleLoop& L, float* traj_x, float* traj_eps, const int64_t* window_ids_dev, const uint64_t* seed_dev, hipStream_t s) {
+  const StepUpdateArgs& u = L.upd;
+  const bool in_place = u.kind == StepUpdate::SOLVER_1 || u.kind == StepUpdate::SOLVER_2M;  // the solver loop keeps x in xa: xb holds the x0 history
+  const int64_t n = u.B * u.per;
+  float *xa = L.xa, *xb = u.hist;
+  for (int i = 0; i < L.num_steps; ++i) {
+    // eps objective: the network output IS the trajectory's eps; x0 objective, or a clamped x0: the derived eps goes to the trajectory
+    float* eps = traj_eps ? traj_eps + (int64_t)i * n : L.eps;
+    float* xn = traj_x ? traj_x + (int64_t)i * n : (in_place ? xa : xb);
+    bool fused = false;
+    DQ_TRY(L.forward(xa, xn, i, nullptr, eps, traj_eps != nullptr, &fused, s));  // model.py:271 / :276
+    DQ_TRY(launch_step_update(u, xa, eps, xn, (traj_eps && (u.px0 || L.clip)) ? eps : nullptr, i, nullptr, StepNoise{window_ids_dev, seed_dev, 1 + i}, fused, s));
+    if (traj_x) {
+      DQ_HIP_OK(hipMemcpyAsync(xa, xn, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    } else if (!in_place) {
+      std::swap(xa, xb);
+    }
+  }
+  return finish(L, xa, s);
+}
+
 }  // namespace dq
 
 extern "C" {
@@ -144,11 +195,8 @@ int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_
   DQ_TRY(sampler_check("dq_ddim_sample", plan && params && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
                        eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, &sc));
   const StepUpdate kind = sc.kind;
-  const bool sto = sc.sto, clip = sc.clip;
   clip_x0 = sc.clip_x0;
-  const int px0 = sc.px0;
   const bool in_head = kind == StepUpdate::DDIM;  // the head launch takes the update when it can (StepIO::x_t); the others run behind the forward
-  const bool in_place = kind == StepUpdate::SOLVER_1 || kind == StepUpdate::SOLVER_2M;  // the solver loop keeps x in xa: xb holds the x0 history
   DQ_REQUIRE(B > 0 && RT > 0 && num_steps >= 1 && num_steps <= 1024, "dq_ddim_sample: need B, RT > 0 and 1 <= num_steps <= 1024");
   DQ_TRY(ensure_arena(plan, B, RT));
   const Arena& a = plan->arena;
@@ -164,16 +212,25 @@ int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_
   const int32_t* ts = timesteps_host;  // trunc(linspace(T-1, 0, num_steps)) formed by the caller exactly as model.py:313 does
   DQ_TRY(sampler_upload_tables("dq_ddim_sample", alpha_bars_host, T, ts, num_steps, sampler, sc, eta, c.w(a.coef), in_head ? nullptr : c.w(a.sigma), s));
   float* xa = c.w(a.xa);
-  float* xb = c.w(a.xb);
   if (x_T) DQ_HIP_OK(hipMemcpyAsync(xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
   else DQ_TRY(launch_randn(xa, window_ids_dev, seed_dev, 0, B, per, s));  // draw index 0 is x_T's
-  const StepUpdateArgs upd{kind, c.w(a.coef), c.w(a.sigma), xb, clip_x0, px0, B, per};
-  Ctx::StepIO io;
-  io.pred_x0 = px0; io.coef = c.w(a.coef);
+  Ctx::StepIO io; io.pred_x0 = sc.px0;
+  // The step index of a captured step lives on the device: k_time_fwd reads ts_tab[*step], the update its coefficient row, k_inc_step bumps it.
+  int* ts_tab = reinterpret_cast<int*>(c.w(a.ts_tab));
+  // the forward of this network: captured over the staged conditions (all pointers inside the arena / parameter buffers), eagerly over the caller's
+  const StepForward forward = [&](const float* x, float* x_out, int row, const int* step_ptr, float* net_out, bool want_eps, bool* fused, hipStream_t fs) {
+    Ctx fc{plan->plan, a, params, W, nullptr, nullptr, B, RT, fs};
+    fc.save = false; fc.step_io = &io;
+    io.x_t = in_head ? x : nullptr; io.x_out = x_out; io.coef = c.w(a.coef) + 4 * row; io.step_ptr = step_ptr; io.want_eps = want_eps; io.fused_update = false;
+    const int rc = step_ptr ? unet_forward(fc, rope_freqs, x, nullptr, 0, c.w(a.c2_stage), c.w(a.c1_stage), cm, ca, plan->dev, net_out, ts_tab, step_ptr)
+                            : unet_forward(fc, rope_freqs, x, nullptr, ts[row], ms2_cond, ms1_cond, cm, ca, plan->dev, net_out);
+    *fused = io.fused_update;
+    return rc;
+  };
+  const SampleLoop loop{forward, StepUpdateArgs{kind, c.w(a.coef), c.w(a.sigma), c.w(a.xb), clip_x0, sc.px0, B, per}, xa, c.w(a.eps), sc.clip,
+                        num_steps, ms2_cond, out_x, out_noise, auto_normalize};
   if (use_graph && !traj_x && !traj_eps) {
-    // ---- hipGraph path: one step captured once (all pointers inside the arena / parameter buffers), replayed per step.
-    // The step index lives on the device: k_time_fwd reads ts_tab[*step], the update its coefficient row, k_inc_step bumps it.
-    int* ts_tab = reinterpret_cast<int*>(c.w(a.ts_tab));
+    // ---- hipGraph path: one step captured once, replayed per step
     int* step = reinterpret_cast<int*>(c.w(a.step));
     DQ_HIP_OK(hipMemcpyAsync(ts_tab, ts, sizeof(int32_t) * num_steps, hipMemcpyHostToDevice, s));
     DQ_HIP_OK(hipMemsetAsync(step, 0, sizeof(int), s));
@@ -181,57 +238,19 @@ int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_
     DQ_HIP_OK(hipMemcpyAsync(c.w(a.c1_stage), ms1_cond, sizeof(float) * (int64_t)B * RT * plan->plan.ms1_channels, hipMemcpyDeviceToDevice, s));
     uint64_t* seed_st = reinterpret_cast<uint64_t*>(c.w(a.seed_stage));
     int64_t* ids_st = reinterpret_cast<int64_t*>(c.w(a.ids_stage));
-    if (sto) DQ_TRY(sampler_stage_noise(seed_st, ids_st, seed_dev, window_ids_dev, B, s));  // staged like the conditions (null ids: 0 .. B-1)
+    if (sc.sto) DQ_TRY(sampler_stage_noise(seed_st, ids_st, seed_dev, window_ids_dev, B, s));  // staged like the conditions (null ids: 0 .. B-1)
     DQ_HIP_OK(hipStreamSynchronize(s));  // ts is caller memory; also keeps the capture below free of pending copies
     DQ_TRY(unet_sample_prologue(c, c.w(a.c1_stage), cm, ca, rope_freqs, &io.prologue));
-    io.x_t = in_head ? xa : nullptr; io.x_out = xa; io.step_ptr = step; io.want_eps = false;  // in place: element-wise, read and written by the same lane
     StepKey key;
     key.params = params; key.rope = rope_freqs; key.ws = workspace; key.B = B; key.RT = RT; key.normalize = auto_normalize; key.pred = pred_type;
     key.update = kind; key.clip = clip_x0; key.opt_epoch = options_epoch();
-    if (!plan->step_exec || !(plan->step_key == key)) {
-      drop_step_graph(plan);
-      // the caller's stream may be the legacy default stream, which cannot be captured: capture on a stream of our own
-      // (nothing executes during capture) and launch the instantiated graph on the caller's stream
-      if (!plan->cap_stream) DQ_HIP_OK(hipStreamCreateWithFlags(&plan->cap_stream, hipStreamNonBlocking));
-      hipStream_t cs = plan->cap_stream;
-      Ctx cc{plan->plan, a, params, W, nullptr, nullptr, B, RT, cs};
-      cc.save = false;
-      cc.step_io = &io;
-      DQ_HIP_OK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-      int rc = unet_forward(cc, rope_freqs, xa, nullptr, 0, c.w(a.c2_stage), c.w(a.c1_stage), cm, ca, plan->dev, c.w(a.eps), ts_tab, step);
-      // (no eps out of a captured step; the staged ids and seed, at draw 0: the kernel adds the step counter)
-      if (!rc) rc = launch_step_update(upd, xa, c.w(a.eps), xa, nullptr, 0, step, StepNoise{ids_st, seed_st, 0}, io.fused_update, cs);
-      if (!rc) rc = launch_inc_step(step, cs);
-      hipGraph_t g = nullptr;
-      const hipError_t ce = hipStreamEndCapture(cs, &g);
-      if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-      DQ_HIP_OK(ce);
-      plan->step_graph = g;
-      DQ_HIP_OK(hipGraphInstantiate(&plan->step_exec, g, nullptr, nullptr, 0));
-      plan->step_key = key;
-    }
-    for (int i = 0; i < num_steps; ++i) DQ_HIP_OK(hipGraphLaunch(plan->step_exec, s));
-    DQ_TRY(launch_sample_finish(xa, ms2_cond, out_x, out_noise, n, auto_normalize, s));
-    return 0;
+    bool captured;  // (the key only after instantiation succeeded)
+    const int rc = replay_captured_step(plan->step, plan->step.exec && plan->step_key == key, loop, step, StepNoise{ids_st, seed_st, 0}, s, &captured);
+    if (captured) plan->step_key = key;
+    return rc;
   }
   DQ_TRY(unet_sample_prologue(c, ms1_cond, cm, ca, rope_freqs, &io.prologue));
-  c.step_io = &io;
-  for (int i = 0; i < num_steps; ++i) {
-    // eps objective: the network output IS the trajectory's eps; x0 objective, or a clamped x0: the derived eps goes to the trajectory
-    float* eps = traj_eps ? traj_eps + (int64_t)i * n : c.w(a.eps);
-    float* xn = traj_x ? traj_x + (int64_t)i * n : (in_place ? xa : xb);
-    io.x_t = in_head ? xa : nullptr; io.x_out = xn; io.coef = c.w(a.coef) + 4 * i; io.step_ptr = nullptr; io.want_eps = traj_eps != nullptr; io.fused_update = false;
-    DQ_TRY(unet_forward(c, rope_freqs, xa, nullptr, ts[i], ms2_cond, ms1_cond, cm, ca, plan->dev, eps));  // model.py:271 / :276
-    // (the caller's ids and seed; step i draws at index 1 + i)
-    DQ_TRY(launch_step_update(upd, xa, eps, xn, (traj_eps && (px0 || clip)) ? eps : nullptr, i, nullptr, StepNoise{window_ids_dev, seed_dev, 1 + i}, io.fused_update, s));
-    if (traj_x) {
-      DQ_HIP_OK(hipMemcpyAsync(xa, xn, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-    } else if (!in_place) {
-      std::swap(xa, xb);
-    }
-  }
-  DQ_TRY(launch_sample_finish(xa, ms2_cond, out_x, out_noise, n, auto_normalize, s));  // model.py:319-322
-  return 0;
+  return eager_steps(loop, traj_x, traj_eps, window_ids_dev, seed_dev, s);
 }
 
 }  // extern "C"

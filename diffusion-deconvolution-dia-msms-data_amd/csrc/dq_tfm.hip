@@ -201,7 +201,7 @@ int dq_tfm_set_precision(dq_tfm* tfm, int precision) {
   DQ_REQUIRE(tfm, "dq_tfm_set_precision: null handle");
   DQ_REQUIRE(precision == DQ_PRECISION_FP32 || precision == DQ_PRECISION_BF16X3, "dq_tfm_set_precision: precision must be DQ_PRECISION_FP32 or DQ_PRECISION_BF16X3");
   tfm->precision = precision == DQ_PRECISION_BF16X3 ? GEMM_BF16X3 : GEMM_FP32;
-  drop_tfm_step_graph(tfm);  // (a captured sampling step has the arithmetic of its capture time baked in)
+  tfm->step.drop();  // (a captured sampling step has the arithmetic of its capture time baked in)
   return 0;
 }
 
@@ -236,8 +236,7 @@ dq_tfm* dq_tfm_create(int input_dim, int hidden_dim, int num_heads, int num_laye
 }
 void dq_tfm_destroy(dq_tfm* p) {
   if (!p) return;
-  drop_tfm_step_graph(p);
-  if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
+  p->step.destroy();
   delete p;
 }
 int dq_tfm_num_params(const dq_tfm* p) { return p ? (int)p->params.size() : 0; }

@@ -3,7 +3,7 @@
 #pragma once
 #include "dq_common.h"
 #include "dq_tfm.h"
-#include "dq_unet.h"  // StepUpdate
+#include "dq_unet.h"  // StepUpdate, StepGraph
 #include <string>
 #include <vector>
 
@@ -39,20 +39,11 @@ struct dq_tfm {
   struct Saved { const void* ws; int B, S1, S2; };
   std::vector<Saved> saved;
   int precision = dq::GEMM_FP32;  // arithmetic of the dense products (dq_tfm_set_precision)
-  // hipGraph of ONE sampling step (dq_tfm_sample: forward + update + step counter), replayed num_steps times; valid while step_key holds
-  hipGraphExec_t step_exec = nullptr;
-  hipGraph_t step_graph = nullptr;
-  hipStream_t cap_stream = nullptr;  // capture-only stream (the caller's may be the uncapturable legacy default stream)
+  dq::StepGraph step;  // the captured sampling step of dq_tfm_sample; valid while step_key holds
   dq::TfmStepKey step_key;
 };
 
 namespace dq {
-
-// drops the captured sampling step: the next graph call captures again
-inline void drop_tfm_step_graph(dq_tfm* p) {
-  if (p->step_exec) { (void)hipGraphExecDestroy(p->step_exec); p->step_exec = nullptr; }
-  if (p->step_graph) { (void)hipGraphDestroy(p->step_graph); p->step_graph = nullptr; }
-}
 
 constexpr int64_t TFM_PARTIAL_FLOATS = (int64_t)(768 + 256) * 128 * 128;  // bound of launch_gemm's split-K scratch (k_gemm.hip: choose())
 inline int64_t up4(int64_t v) { return (v + 3) & ~(int64_t)3; }

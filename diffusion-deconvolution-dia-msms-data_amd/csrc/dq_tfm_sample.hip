@@ -12,7 +12,6 @@
 #include "dq_tfm.h"
 #include "dq_tfm_net.h"
 #include <cmath>
-#include <utility>
 #include <vector>
 
 namespace dq {
@@ -160,9 +159,6 @@ int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const f
   DQ_REQUIRE(workspace_bytes >= w.floats * (int64_t)sizeof(float), "dq_tfm_sample: workspace too small (dq_tfm_sample_workspace_bytes)");
   PrecisionScope prec(p->precision);
   hipStream_t s = (hipStream_t)stream;
-  const StepUpdate kind = sc.kind;
-  const bool in_place = kind == StepUpdate::SOLVER_1 || kind == StepUpdate::SOLVER_2M;  // the solver loop keeps x in xa: xb holds the x0 history
-  const int px0 = sc.px0;
   const int64_t per = (int64_t)S1 * p->D, n = B * per;
   const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
   const int32_t* ts = timesteps_host;
@@ -172,11 +168,14 @@ int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const f
   for (int i = 0; i < num_steps; ++i) t64[i] = ts[i];
   DQ_HIP_OK(hipMemcpyAsync(w.t64, t64.data(), sizeof(int64_t) * t64.size(), hipMemcpyHostToDevice, s));
   DQ_TRY(sampler_upload_tables("dq_tfm_sample", alpha_bars_host, T, ts, num_steps, sampler, sc, eta, w.coef, w.sigma, s));
-  float* xa = w.xa;
-  float* xb = w.xb;
-  if (x_T) DQ_HIP_OK(hipMemcpyAsync(xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-  else DQ_TRY(launch_randn(xa, window_ids_dev, seed_dev, 0, B, per, s));  // draw index 0 is x_T's
-  const StepUpdateArgs upd{kind, w.coef, w.sigma, xb, sc.clip_x0, px0, B, per};
+  if (x_T) DQ_HIP_OK(hipMemcpyAsync(w.xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  else DQ_TRY(launch_randn(w.xa, window_ids_dev, seed_dev, 0, B, per, s));  // draw index 0 is x_T's
+  const StepForward forward = [&](const float* x, float*, int row, const int* step_ptr, float* net_out, bool, bool* fused, hipStream_t fs) {
+    *fused = false;  // (the update is never in this network's launches)
+    return sample_forward(net, x, row, step_ptr, net_out, fs);
+  };
+  const SampleLoop loop{forward, StepUpdateArgs{sc.kind, w.coef, w.sigma, w.xb, sc.clip_x0, sc.px0, B, per}, w.xa, w.eps, sc.clip,
+                        num_steps, ms2_cond, out_x, out_noise, auto_normalize};
   if (net.form == TFM_ATTN_FUSED) DQ_TRY(tfm_attn_prepare());  // (the LDS limit of this device, before any capture)
   // every call, outside any capture: a changed MS1, or changed weights behind the same pointer, cannot meet a stale cache
   DQ_TRY(sample_prologue(net, ms1_cond, cm, ca, time_freqs, num_steps, s));
@@ -187,47 +186,14 @@ int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const f
     if (sc.sto) DQ_TRY(sampler_stage_noise(w.seed_stage, w.ids_stage, seed_dev, window_ids_dev, B, s));
     TfmStepKey key;
     key.params = params; key.ws = workspace; key.rope_sin = rope_sin; key.rope_cos = rope_cos; key.B = B; key.S1 = S1; key.S2 = S2;
-    key.num_steps = num_steps;
-    key.normalize = auto_normalize; key.pred = pred_type; key.precision = p->precision; key.update = kind; key.clip = sc.clip_x0;
+    key.num_steps = num_steps; key.normalize = auto_normalize; key.pred = pred_type; key.precision = p->precision; key.update = sc.kind; key.clip = sc.clip_x0;
     key.opt_epoch = options_epoch();
-    if (!p->step_exec || !(p->step_key == key)) {
-      drop_tfm_step_graph(p);
-      // the caller's stream may be the legacy default stream, which cannot be captured: capture on a stream of our own (nothing executes
-      // during capture) and launch the instantiated graph on the caller's stream
-      if (!p->cap_stream) DQ_HIP_OK(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
-      hipStream_t cs = p->cap_stream;
-      DQ_HIP_OK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-      int rc = sample_forward(net, xa, 0, w.step, w.eps, cs);
-      // (x in place: element-wise; the staged ids and seed at draw 0: the kernel adds the step counter)
-      if (!rc) rc = launch_step_update(upd, xa, w.eps, xa, nullptr, 0, w.step, StepNoise{w.ids_stage, w.seed_stage, 0}, false, cs);
-      if (!rc) rc = launch_inc_step(w.step, cs);
-      hipGraph_t g = nullptr;
-      const hipError_t ce = hipStreamEndCapture(cs, &g);
-      if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-      DQ_HIP_OK(ce);
-      p->step_graph = g;
-      DQ_HIP_OK(hipGraphInstantiate(&p->step_exec, g, nullptr, nullptr, 0));
-      p->step_key = key;
-    }
-    for (int i = 0; i < num_steps; ++i) DQ_HIP_OK(hipGraphLaunch(p->step_exec, s));
-    DQ_TRY(launch_sample_finish(xa, ms2_cond, out_x, out_noise, n, auto_normalize, s));
-    return 0;
+    bool captured;
+    const int rc = replay_captured_step(p->step, p->step.exec && p->step_key == key, loop, w.step, StepNoise{w.ids_stage, w.seed_stage, 0}, s, &captured);
+    if (captured) p->step_key = key;
+    return rc;
   }
-  for (int i = 0; i < num_steps; ++i) {
-    // eps objective: the network output IS the trajectory's eps; x0 objective, or a clamped x0: the derived eps goes to the trajectory
-    float* eps = traj_eps ? traj_eps + (int64_t)i * n : w.eps;
-    float* xn = traj_x ? traj_x + (int64_t)i * n : (in_place ? xa : xb);
-    DQ_TRY(sample_forward(net, xa, i, nullptr, eps, s));
-    // (the caller's ids and seed; step i draws at index 1 + i)
-    DQ_TRY(launch_step_update(upd, xa, eps, xn, (traj_eps && (px0 || sc.clip)) ? eps : nullptr, i, nullptr, StepNoise{window_ids_dev, seed_dev, 1 + i}, false, s));
-    if (traj_x) {
-      DQ_HIP_OK(hipMemcpyAsync(xa, xn, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-    } else if (!in_place) {
-      std::swap(xa, xb);
-    }
-  }
-  DQ_TRY(launch_sample_finish(xa, ms2_cond, out_x, out_noise, n, auto_normalize, s));
-  return 0;
+  return eager_steps(loop, traj_x, traj_eps, window_ids_dev, seed_dev, s);
 }
 
 }  // extern "C"

@@ -73,6 +73,17 @@ struct StepKey {
   }
 };
 
+// hipGraph of ONE sampling step (network forward + update + step counter), replayed num_steps times; valid while every pointer baked into
+// its kernel arguments is unchanged (the owner's key).  cap_stream: capture-only (the caller's may be the uncapturable legacy default stream)
+struct StepGraph {
+  hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; hipStream_t cap_stream = nullptr;
+  void drop() {  // drops the captured step: the next graph call captures again
+    if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
+    if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
+  }
+  void destroy() { drop(); if (cap_stream) { (void)hipStreamDestroy(cap_stream); cap_stream = nullptr; } }
+};
+
 }  // namespace dq
 
 struct dq_plan {
@@ -81,10 +92,8 @@ struct dq_plan {
   float* alpha_bars_dev = nullptr;          // (T) fp32, for q_sample
   std::vector<float> alpha_bars_host;
   dq::Arena arena;                           // cached for the last (B, RT)
-  // hipGraph of ONE sampling step (network forward + DDIM update + step counter), replayed num_steps times; valid while
-  // every pointer baked into its kernel arguments is unchanged
-  hipGraphExec_t step_exec = nullptr;
-  hipGraph_t step_graph = nullptr;
+  dq::StepGraph step;    // the captured sampling step
+  dq::StepKey step_key;  // what it was captured for
   // side stream for the weight-gradient kernels of the backward (forked / joined with events from this ring)
   static constexpr int NUM_EVENTS = 256;
   hipStream_t side_stream = nullptr;
@@ -94,12 +103,4 @@ struct dq_plan {
   const void* twin_zeroed = nullptr;  // the gradient twin a forked forward (dq_train_step) cleared on the side stream; consumed by unet_backward
   float* debug_tail_addr = nullptr; float debug_tail_value = 0.f; int debug_tail_us = 0;  // dq_debug_side_tail_store (test hook)
   bool no_side = false;  // dq_plan_set_side_stream(plan, 0): weight-gradient launches on the caller's stream (captured train steps)
-  hipStream_t cap_stream = nullptr;  // capture-only stream (the caller's may be the uncapturable legacy default stream)
-  dq::StepKey step_key;  // what step_exec was captured for
 };
-
-// drops the captured sampling step: the next graph call captures again
-inline void drop_step_graph(dq_plan* plan) {
-  if (plan->step_exec) { (void)hipGraphExecDestroy(plan->step_exec); plan->step_exec = nullptr; }
-  if (plan->step_graph) { (void)hipGraphDestroy(plan->step_graph); plan->step_graph = nullptr; }
-}

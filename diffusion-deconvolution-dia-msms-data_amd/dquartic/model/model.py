@@ -291,18 +291,14 @@ class DDIMDiffusionModel(ModelInterface):
         if on_gpu and self._native_tfm and (self.native_tfm_sampler or stochastic or sampler_id != 0 or return_trajectory):
             return self._sample_native_tfm(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
                                            shape=shape, sampler=sampler_id, clip_x0=clip)
-        if sampler_id != 0:
-            if not (self.native and on_gpu):
-                raise NotImplementedError("sample: the 'ddim' and 'dpmpp_2m' samplers and clip_x0 need the native sampler (this package's "
-                                          "UNet1d, or its CustomTransformer behind DDIMTransformerAdapter, on the GPU with both "
-                                          "conditions); the generic loop is the reference update only")
-            return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
-                                       shape=shape, sampler=sampler_id, clip_x0=clip)
         if self.native and on_gpu:
-            if not stochastic:
-                return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory)
-            return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
-                                       shape=shape)
+            # (the default call passes eta=None: dq_ddim_sample, the call as it always was)
+            return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta if stochastic or sampler_id != 0 else None,
+                                       seed=seed, window_ids=window_ids, shape=shape, sampler=sampler_id, clip_x0=clip)
+        if sampler_id != 0:
+            raise NotImplementedError("sample: the 'ddim' and 'dpmpp_2m' samplers and clip_x0 need the native sampler (this package's "
+                                      "UNet1d, or its CustomTransformer behind DDIMTransformerAdapter, on the GPU with both "
+                                      "conditions); the generic loop is the reference update only")
         if stochastic:
             raise NotImplementedError("sample: eta > 0, seed, window_ids and x_t=None need the native sampler (this package's UNet1d, or "
                                       "its CustomTransformer behind DDIMTransformerAdapter, on the GPU with both conditions); the "
@@ -317,59 +313,58 @@ class DDIMDiffusionModel(ModelInterface):
             pred_noise = self.unnormalize(ms2n) - x_t
         return x_t, pred_noise
 
-    def _sample_native(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False, eta=None, seed=None, window_ids=None, shape=None,
-                       sampler=0, clip_x0=0.0):
-        """``eta`` None: ``dq_ddim_sample`` (the call as it always was); else ``dq_ddim_sample_ex``; ``sampler`` != 0:
-        ``dq_ddim_sample_solver``."""
-        net: UNet1d = self.model
+    # what the two native loops stage alike
+    @staticmethod
+    def _stage_x(x_T, ms2_cond, eta, seed, shape):
+        """(x_T or None, ms2_cond) as contiguous fp32 and the call's (batch, rows, width): x_T's, else ``shape`` or ``ms2_cond``'s."""
         f32 = lambda v: v.detach().to(torch.float32).contiguous()
         if x_T is None:
             if seed is None and not eta:
                 raise ValueError("sample: x_t=None needs a seed (x_T is drawn from it)")
-            B, RT, MZ = tuple(shape) if shape is not None else tuple(ms2_cond.shape)
-            c2 = f32(ms2_cond)
+            B, S, D = tuple(shape) if shape is not None else tuple(ms2_cond.shape)
         else:
-            B, RT, MZ = x_T.shape
-            x_T, c2 = f32(x_T), f32(ms2_cond)
-        c1 = f32(net._check_inputs(ms1_cond, B, RT))
+            B, S, D = x_T.shape
+            x_T = f32(x_T)
+        return x_T, f32(ms2_cond), B, S, D
+
+    def _stage_noise(self, x_T, eta, seed, window_ids, B, device):
+        """The seed and window-id tensors of a call (None where the loop reads none); records ``last_seed``."""
+        seed_dev = self._seed_tensor(seed, device) if (seed is not None or eta > 0.0 or x_T is None) else None
+        ids_dev = self._ids_tensor(window_ids, B, device)
+        self.last_seed = None if seed_dev is None else int(seed_dev.item()) & (2 ** 64 - 1)  # (what a seed=None call drew)
+        return seed_dev, ids_dev
+
+    @staticmethod
+    def _sample_outputs(c2, num_steps, dims, return_trajectory):
+        """[out_x, out_noise, traj_x, traj_eps]: the trajectories (num_steps, *dims), or None"""
+        return [torch.empty_like(c2), torch.empty_like(c2)] + [
+            torch.empty((num_steps, *dims), device=c2.device) if return_trajectory else None for _ in range(2)]
+
+    def _sample_native(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False, eta=None, seed=None, window_ids=None, shape=None,
+                       sampler=0, clip_x0=0.0):
+        """``eta`` None: ``dq_ddim_sample`` (the call as it always was); else ``dq_ddim_sample_ex``; ``sampler`` != 0:
+        ``dq_ddim_sample_solver``.  The three take one argument list; the later ones append to it."""
+        net: UNet1d = self.model
+        x_T, c2, B, RT, MZ = self._stage_x(x_T, ms2_cond, eta, seed, shape)
+        c1 = net._check_inputs(ms1_cond, B, RT).detach().to(torch.float32).contiguous()
         flat = net.read_params()  # (the averaged weights inside ModelInterface.ema_scope())
         ws = net.workspace(B, RT, False)
         ts = self.sampler_timesteps(self.num_timesteps, num_steps).to(torch.int32)
         ts_c = (ctypes.c_int32 * num_steps)(*ts.tolist())
-        out_x, out_n = torch.empty_like(c2), torch.empty_like(c2)
-        traj_x = torch.empty((num_steps, B, RT, MZ), device=c2.device) if return_trajectory else None
-        traj_e = torch.empty((num_steps, B, RT, MZ), device=c2.device) if return_trajectory else None
+        outs = self._sample_outputs(c2, num_steps, (B, RT, MZ), return_trajectory)
+        args = [net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), self._alpha_bars_host(), int(self.num_timesteps), N.ptr(x_T), N.ptr(c2),
+                N.ptr(c1), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], ts_c, num_steps, *(N.ptr(v) for v in outs),
+                1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws), ws.numel(), B, RT, N.stream_ptr()]
+        entry = "dq_ddim_sample"
         if eta is not None:
-            seed_dev = self._seed_tensor(seed, c2.device) if (seed is not None or eta > 0.0 or x_T is None) else None
-            ids_dev = self._ids_tensor(window_ids, B, c2.device)
-            self.last_seed = None if seed_dev is None else int(seed_dev.item()) & (2 ** 64 - 1)  # (what a seed=None call drew)
+            seed_dev, ids_dev = self._stage_noise(x_T, eta, seed, window_ids, B, c2.device)
+            args += [float(eta), N.ptr(seed_dev), N.ptr(ids_dev)]
+            entry = "dq_ddim_sample_ex"
             if sampler:
-                N.check(N.lib().dq_ddim_sample_solver(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), self._alpha_bars_host(),
-                                                      int(self.num_timesteps), N.ptr(x_T), N.ptr(c2), N.ptr(c1), 1 if self.auto_normalize else 0,
-                                                      N.PRED_TYPES[self.pred_type], ts_c, num_steps, N.ptr(out_x), N.ptr(out_n), N.ptr(traj_x),
-                                                      N.ptr(traj_e), 1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws),
-                                                      ws.numel(), B, RT, N.stream_ptr(), float(eta), N.ptr(seed_dev), N.ptr(ids_dev),
-                                                      int(sampler), float(clip_x0)), "dq_ddim_sample_solver")
-                if return_trajectory:
-                    return out_x, out_n, traj_x, traj_e
-                return out_x, out_n
-            N.check(N.lib().dq_ddim_sample_ex(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), self._alpha_bars_host(), int(self.num_timesteps),
-                                              N.ptr(x_T), N.ptr(c2), N.ptr(c1), 1 if self.auto_normalize else 0,
-                                              N.PRED_TYPES[self.pred_type], ts_c, num_steps, N.ptr(out_x), N.ptr(out_n), N.ptr(traj_x),
-                                              N.ptr(traj_e), 1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws), ws.numel(),
-                                              B, RT, N.stream_ptr(), float(eta), N.ptr(seed_dev), N.ptr(ids_dev)), "dq_ddim_sample_ex")
-            if return_trajectory:
-                return out_x, out_n, traj_x, traj_e
-            return out_x, out_n
-        N.check(N.lib().dq_ddim_sample(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), self._alpha_bars_host(), int(self.num_timesteps),
-                                       N.ptr(x_T), N.ptr(c2),
-                                       N.ptr(c1), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], ts_c, num_steps,
-                                       N.ptr(out_x), N.ptr(out_n),
-                                       N.ptr(traj_x), N.ptr(traj_e), 1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws),
-                                       ws.numel(), B, RT, N.stream_ptr()), "dq_ddim_sample")
-        if return_trajectory:
-            return out_x, out_n, traj_x, traj_e
-        return out_x, out_n
+                args += [int(sampler), float(clip_x0)]
+                entry = "dq_ddim_sample_solver"
+        N.check(getattr(N.lib(), entry)(*args), entry)
+        return tuple(outs) if return_trajectory else tuple(outs[:2])
 
     @property
     def _native_tfm(self) -> bool:
@@ -382,15 +377,8 @@ class DDIMDiffusionModel(ModelInterface):
         """``dq_tfm_sample``: the whole loop in the library for the transformer behind its adapter (``ms1_cond`` (B, RT) or (B, RT, 1) is
         its conditional sequence; ``ms2_cond`` only enters ``mixture - denoised``)."""
         tfm = self.model.transformer
-        f32 = lambda v: v.detach().to(torch.float32).contiguous()
-        if x_T is None:
-            if seed is None and not eta:
-                raise ValueError("sample: x_t=None needs a seed (x_T is drawn from it)")
-            B, S1, D = tuple(shape) if shape is not None else tuple(ms2_cond.shape)
-        else:
-            B, S1, D = x_T.shape
-            x_T = f32(x_T)
-        c2, c1 = f32(ms2_cond), f32(ms1_cond)
+        x_T, c2, B, S1, D = self._stage_x(x_T, ms2_cond, eta, seed, shape)
+        c1 = ms1_cond.detach().to(torch.float32).contiguous()
         if c1.dim() == 3:
             c1 = c1[..., 0].contiguous()
         if D != tfm.input_dim or tuple(c2.shape) != (B, S1, D):
@@ -402,20 +390,14 @@ class DDIMDiffusionModel(ModelInterface):
         ws = tfm.sample_workspace(B, S1, S2, num_steps)
         sin, cos, freqs = tfm.tables(max(S1, S2), c2.device)
         ts_c = (ctypes.c_int32 * num_steps)(*self.sampler_timesteps(self.num_timesteps, num_steps).to(torch.int32).tolist())
-        out_x, out_n = torch.empty_like(c2), torch.empty_like(c2)
-        traj_x = torch.empty((num_steps, B, S1, D), device=c2.device) if return_trajectory else None
-        traj_e = torch.empty((num_steps, B, S1, D), device=c2.device) if return_trajectory else None
-        seed_dev = self._seed_tensor(seed, c2.device) if (seed is not None or eta > 0.0 or x_T is None) else None
-        ids_dev = self._ids_tensor(window_ids, B, c2.device)
-        self.last_seed = None if seed_dev is None else int(seed_dev.item()) & (2 ** 64 - 1)  # (what a seed=None call drew)
+        outs = self._sample_outputs(c2, num_steps, (B, S1, D), return_trajectory)
+        seed_dev, ids_dev = self._stage_noise(x_T, eta, seed, window_ids, B, c2.device)
         N.check(N.lib().dq_tfm_sample(tfm._tfm, N.ptr(flat), N.ptr(sin), N.ptr(cos), N.ptr(freqs), self._alpha_bars_host(), int(self.num_timesteps),
                                       N.ptr(x_T), N.ptr(c2), N.ptr(c1), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], ts_c,
-                                      num_steps, N.ptr(out_x), N.ptr(out_n), N.ptr(traj_x), N.ptr(traj_e),
-                                      1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws), ws.numel(), B, S1, S2, N.stream_ptr(),
-                                      float(eta), N.ptr(seed_dev), N.ptr(ids_dev), int(sampler), float(clip_x0)), "dq_tfm_sample")
-        if return_trajectory:
-            return out_x, out_n, traj_x, traj_e
-        return out_x, out_n
+                                      num_steps, *(N.ptr(v) for v in outs), 1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws),
+                                      ws.numel(), B, S1, S2, N.stream_ptr(), float(eta), N.ptr(seed_dev), N.ptr(ids_dev), int(sampler),
+                                      float(clip_x0)), "dq_tfm_sample")
+        return tuple(outs) if return_trajectory else tuple(outs[:2])
 
     # ------------------------------------------------------------------ training objective
     def train_step(self, x_0, ms2_cond=None, ms1_cond=None, noise=None, ms1_loss_weight=0.0, t=None):

@@ -455,7 +455,8 @@ int dq_tfm_attn_fwd(const float* q, const float* kv, float* o, float* prob_scrat
                     void* stream);
 /* Sampling from the transformer in one call (csrc/dq_tfm_sample.hip): dq_ddim_sample_solver's loop -- the same
  * tables, updates, draw indexing (x_T at 0, step i at 1 + i), refusals (worded alike, before anything touches the device) and final
- * un-normalisation -- around a sampling forward of this network.  x_T (B, S1, input_dim; NULL: drawn from the seed), ms2_cond like x_T (the
+ * un-normalisation -- around a sampling forward of this network; the same code, not a copy (csrc/dq_sampler.h: the captured step and the
+ * eager steps take the network's forward as a callable).  x_T (B, S1, input_dim; NULL: drawn from the seed), ms2_cond like x_T (the
  * network ignores it: out_noise = mixture - out_x), ms1_cond (B, S2).  Once per call, before the loop: the conditional embedding of ms1_cond
  * (2c - 1 first when auto_normalize), every layer's K | V rows of it, and the time embedding of every step; a step then projects only the x_t
  * rows and runs the attention by dq_tfm_attn_form.  use_graph != 0 without trajectories: one step is captured once, cached on the handle
