@@ -315,6 +315,21 @@ int dq_mse_per_window(const float* out, const float* target, float tm, float ta,
                                (hipStream_t)stream);
 }
 
+int dq_q_sample_repeats(const float* alpha_bars_dev, const float* x0, const int64_t* t, const float* noise, const uint64_t* seed_dev,
+                        const int64_t* window_ids_dev, int first_draw, float* x_t, int B, int repeats, int64_t per_window, int normalize_x0,
+                        void* stream) {
+  return launch_q_sample_repeats(alpha_bars_dev, x0, t, noise, window_ids_dev, seed_dev, first_draw, x_t, B, repeats, per_window, normalize_x0,
+                                 (hipStream_t)stream);
+}
+
+int dq_mse_per_window_repeats(const float* out, const float* target, int target_windows, float tm, float ta, const uint64_t* seed_dev,
+                              const int64_t* window_ids_dev, int first_draw, const float* lw, const int64_t* t, float* per_window_out,
+                              float* loss_out, void* scratch, int B, int repeats, int64_t per, void* stream) {
+  DQ_REQUIRE(B > 0 && repeats > 0 && (int64_t)repeats * B <= 65535 && per > 0, "dq_mse_per_window_repeats: need B, repeats, per > 0 and repeats * B <= 65535");
+  return launch_mse_per_window_repeats(out, target, target_windows, tm, ta, window_ids_dev, seed_dev, first_draw, lw, t, per_window_out, loss_out,
+                                       scratch, mse_per_window_scratch_bytes(repeats * B, per), B, repeats, per, (hipStream_t)stream);
+}
+
 int64_t dq_recon_metrics_scratch_bytes(int B, int RT, int MZ) { return recon_metrics_scratch_bytes(B, RT, MZ); }
 
 int dq_recon_metrics(const float* pred, const float* target, float* out, void* scratch, int64_t scratch_bytes, int B, int RT, int MZ,

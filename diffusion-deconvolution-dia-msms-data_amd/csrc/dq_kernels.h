@@ -64,6 +64,17 @@ constexpr int MSE_PW_SLICE = 8192;  // elements of a window one block of k_mse_p
 int64_t mse_per_window_scratch_bytes(int B, int64_t per);
 int launch_mse_per_window(const float* out, const float* target, float tm, float ta, const float* lw, const int64_t* t, float* per_window,
                           float* loss_out, void* scratch, int64_t scratch_bytes, int B, int64_t per, hipStream_t s);
+// ---- k_tfm_eval.hip: the two above over R repeats of B windows stacked repeat-major (sample n = r * B + b; x0 (B, per) shared by the
+// repeats, t (R, B)); noise / target nullable: drawn in the kernel at draw index first_draw + r from seed_dev and ids (nullable: 0 .. B-1).
+// per % 4 == 0 and 16-byte aligned tensors for the head.  The tail's target has Bt windows (B: shared by the repeats, R * B: one each);
+// per_window (R, B), loss_out (R); scratch: mse_per_window_scratch_bytes(R * B, per).
+int launch_q_sample_repeats(const float* alpha_bars, const float* x0, const int64_t* t, const float* noise, const int64_t* ids,
+                            const uint64_t* seed_dev, int first_draw, float* x_t, int B, int R, int64_t per, int normalize, hipStream_t s);
+int launch_mse_per_window_repeats(const float* out, const float* target, int Bt, float tm, float ta, const int64_t* ids, const uint64_t* seed_dev,
+                                  int first_draw, const float* lw, const int64_t* t, float* per_window, float* loss_out, void* scratch,
+                                  int64_t scratch_bytes, int B, int R, int64_t per, hipStream_t s);
+// kv (R * B, Sk, 2H): rows [0, S2) of samples 0 .. B-1 copied to samples B .. R * B - 1 (R == 1: no launch)
+int launch_tfm_kv_broadcast(float* kv, int B, int R, int S2, int Sk, int H, hipStream_t s);
 // ---- k_metrics.hip: per-window reconstruction metrics of pred against target (B, RT, MZ) -> out (B, METRIC_COUNT)
 constexpr int METRIC_COUNT = 9;         // DQ_METRIC_COUNT
 constexpr int METRIC_ROW_SEG = 4096;    // m/z columns of a scan one wave of k_metric_rows sums

@@ -3,6 +3,9 @@
 // inference attention (k_tfm_attn.hip).  What does not depend on the step is computed once per call, before the loop: the conditional
 // embedding cp of the MS1 chromatogram, every layer's K | V rows of it, and the time embedding of every step.  dq_tfm_fwd / dq_tfm_bwd
 // (dq_tfm.hip) are the training path and know nothing of this file.
+// Held-out evaluation: dq_tfm_eval_step runs the same prologue and the same forward once over R repeats of a batch
+// stacked into R * B samples -- the conditional rows computed for the B windows and copied to the other repeats, the time table one row per
+// sample -- between the stacked noising head and the stacked per-window MSE of k_tfm_eval.hip.
 #include "../../include/dq_hip.h"
 #include "dq_common.h"
 #include "dq_kernels.h"
@@ -50,58 +53,95 @@ SampleWs carve_sample(const dq_tfm& p, float* base, int B, int S1, int S2, int n
   return w;
 }
 
-// What one sampling call's forwards share
-struct SampleNet {
-  const dq_tfm* p; const float* P; const float* sin_t; const float* cos_t;
-  const SampleWs* w;
-  int B, S1, S2, form;
+// workspace of an evaluation call over N = R * B stacked samples: the inference buffers of carve() at batch N (its time buffers hold the
+// per-sample time table; its comb and kv stay unused), the L kv_l, x_t, the network output (unused when the caller passes net_out) and the
+// slice sums of the per-window MSE
+struct EvalWs {
+  Ws net;
+  std::vector<float*> kv;  // per layer (N, Sk, 2H)
+  float *xt, *out;
+  double* slices;
+  int64_t floats = 0;
 };
 
-// K | V rows of `rows` (B, M, H) under layer l's projection into rows [row0, row0 + M) of kv_l: one product batched over the samples (B == 1: a
-// plain product, which the launcher may split along the reduction)
-int kv_rows(const SampleNet& c, int l, const float* rows, int M, int row0, hipStream_t s) {
+EvalWs carve_eval(const dq_tfm& p, float* base, int B, int S1, int S2, int R) {
+  EvalWs w;
+  const int N = R * B;
+  w.net = carve(p, base, N, S1, S2, false);
+  int64_t off = w.net.floats;
+  auto take = [&](int64_t n) { float* r = base ? base + off : nullptr; off += up4(n); return r; };
+  const int64_t H = p.H, Sk = S1 + S2, per = (int64_t)S1 * p.D;
+  for (int l = 0; l < p.layers; ++l) w.kv.push_back(take(N * Sk * 2 * H));
+  w.xt = take(N * per); w.out = take(N * per);
+  w.slices = reinterpret_cast<double*>(take(mse_per_window_scratch_bytes(N, per) / (int64_t)sizeof(float)));
+  w.floats = off;
+  return w;
+}
+
+// What one call's forwards share.  B samples go through the network; the conditional rows are computed for the first Bc of them and copied
+// to the rest (sampling: Bc == B; evaluation: B / Bc repeats of Bc windows).  The time table ttab has one row per step (sampling: the
+// forward adds the row it is told to every sample) or, with time_per_sample, one row per sample.
+struct SampleNet {
+  const dq_tfm* p; const float* P; const float* sin_t; const float* cos_t;
+  const Ws* net;       // the inference buffers of carve() at batch B
+  float* const* kv;    // per layer (B, Sk, 2H): rows [0, S2) the call's conditional K | V, rows [S2, Sk) the forward's
+  const int64_t* t64;  // the timesteps the time table is built from
+  float *tfeat, *th, *tg, *ttab;
+  int B, S1, S2, form;
+  int Bc;
+  bool time_per_sample;
+};
+
+// K | V rows of `rows` (batch, M, H) under layer l's projection into rows [row0, row0 + M) of kv_l's first `batch` samples: one product batched
+// over the samples (batch == 1: a plain product, which the launcher may split along the reduction)
+int kv_rows(const SampleNet& c, int l, const float* rows, int M, int row0, int batch, hipStream_t s) {
   const int H = c.p->H, Sk = c.S1 + c.S2;
   const TfmLayer& a = c.p->L[l];
   Gemm g;
   g.A = rows; g.lda = H; g.sAo = (int64_t)M * H;
   g.B = c.P + a.in_w + (int64_t)H * H; g.ldb = H; g.bias = c.P + a.in_b + H;
-  g.C = c.w->kv[l] + (int64_t)row0 * 2 * H; g.ldc = 2 * H; g.sCo = (int64_t)Sk * 2 * H;
-  g.batch = c.B; g.M = M; g.N = 2 * H; g.K = H;
-  g.partial = c.w->net.partial; g.partial_floats = TFM_PARTIAL_FLOATS;
+  g.C = c.kv[l] + (int64_t)row0 * 2 * H; g.ldc = 2 * H; g.sCo = (int64_t)Sk * 2 * H;
+  g.batch = batch; g.M = M; g.N = 2 * H; g.K = H;
+  g.partial = c.net->partial; g.partial_floats = TFM_PARTIAL_FLOATS;
   return launch_gemm(g, s);
 }
 
-// once per call, eagerly: cp = rope((cm x_cond + ca) w + b), every layer's K | V rows of it, the time embedding of every step
-int sample_prologue(const SampleNet& c, const float* ms1, float cm, float ca, const float* time_freqs, int ns, hipStream_t s) {
+// once per call, eagerly: cp = rope((cm x_cond + ca) w + b) of the Bc windows, every layer's K | V rows of it (copied to the other B / Bc - 1
+// repeats), the time embedding of the nt timesteps at t64
+int sample_prologue(const SampleNet& c, const float* ms1, float cm, float ca, const float* time_freqs, int nt, hipStream_t s) {
   const dq_tfm& p = *c.p;
-  const Ws& n = c.w->net;
+  const Ws& n = *c.net;
   const int H = p.H;
-  DQ_TRY(launch_cond_embed_affine(ms1, cm, ca, c.P + p.c_w, c.P + p.c_b, c.sin_t, c.cos_t, n.cp, c.B, c.S2, H, s));
-  for (int l = 0; l < p.layers; ++l) DQ_TRY(kv_rows(c, l, n.cp, c.S2, 0, s));
-  // time embedding (building_blocks.py:92-112) with "batch" = the steps
-  DQ_TRY(launch_time_features(c.w->t64, time_freqs, c.w->tfeat, ns, H, s));
-  DQ_TRY(tfm_linear(c.w->tfeat, c.P + p.t1_w, c.P + p.t1_b, c.w->th, ns, 4 * H, H, n.partial, s));
-  DQ_TRY(launch_gelu(c.w->th, c.w->tg, (int64_t)ns * 4 * H, s));
-  DQ_TRY(tfm_linear(c.w->tg, c.P + p.t2_w, c.P + p.t2_b, c.w->ttab, ns, H, 4 * H, n.partial, s));
+  DQ_TRY(launch_cond_embed_affine(ms1, cm, ca, c.P + p.c_w, c.P + p.c_b, c.sin_t, c.cos_t, n.cp, c.Bc, c.S2, H, s));
+  for (int l = 0; l < p.layers; ++l) {
+    DQ_TRY(kv_rows(c, l, n.cp, c.S2, 0, c.Bc, s));
+    DQ_TRY(launch_tfm_kv_broadcast(c.kv[l], c.Bc, c.B / c.Bc, c.S2, c.S1 + c.S2, H, s));  // (one repeat: no launch)
+  }
+  // time embedding (building_blocks.py:92-112) with "batch" = the steps, or the stacked samples
+  DQ_TRY(launch_time_features(c.t64, time_freqs, c.tfeat, nt, H, s));
+  DQ_TRY(tfm_linear(c.tfeat, c.P + p.t1_w, c.P + p.t1_b, c.th, nt, 4 * H, H, n.partial, s));
+  DQ_TRY(launch_gelu(c.th, c.tg, (int64_t)nt * 4 * H, s));
+  DQ_TRY(tfm_linear(c.tg, c.P + p.t2_w, c.P + p.t2_b, c.ttab, nt, H, 4 * H, n.partial, s));
   return 0;
 }
 
-// one step's network output from x (B, S1, D): time row `row`, or the one the device-side counter names
+// the network output from x (B, S1, D): time row `row`, or the one the device-side counter names; with time_per_sample each sample's own
 int sample_forward(const SampleNet& c, const float* x_in, int row, const int* step_ptr, float* out, hipStream_t s) {
   const dq_tfm& p = *c.p;
-  const Ws& n = c.w->net;
+  const Ws& n = *c.net;
   const Ws::Layer& b = n.L[0];
   const int H = p.H, D = p.D, R1 = c.B * c.S1, Sk = c.S1 + c.S2;
   const float* P = c.P;
   DQ_TRY(tfm_linear(x_in, P + p.in_w, P + p.in_b, n.x0, R1, H, D, n.partial, s));
-  DQ_TRY(launch_rope_add_row(n.x0, c.sin_t, c.cos_t, c.w->ttab, row, step_ptr, c.B, c.S1, H, s));
+  if (c.time_per_sample) DQ_TRY(launch_rope_add(n.x0, c.sin_t, c.cos_t, c.ttab, c.B, c.S1, H, 0, s));
+  else DQ_TRY(launch_rope_add_row(n.x0, c.sin_t, c.cos_t, c.ttab, row, step_ptr, c.B, c.S1, H, s));
   const AttnDims ad{c.B, c.S1, Sk, H, p.heads, H / p.heads, up4(Sk)};
   const float* x = n.x0;
   for (int l = 0; l < p.layers; ++l) {
     const TfmLayer& a = p.L[l];
     DQ_TRY(tfm_linear(x, P + a.in_w, P + a.in_b, b.q, R1, H, H, n.partial, s));
-    DQ_TRY(kv_rows(c, l, x, c.S1, c.S2, s));
-    DQ_TRY(tfm_attention_fwd(c.form, ad, b.q, c.w->kv[l], b.prob, b.ao, n.partial, s));
+    DQ_TRY(kv_rows(c, l, x, c.S1, c.S2, c.B, s));
+    DQ_TRY(tfm_attention_fwd(c.form, ad, b.q, c.kv[l], b.prob, b.ao, n.partial, s));
     DQ_TRY(tfm_linear(b.ao, P + a.out_w, P + a.out_b, n.tmp, R1, H, H, n.partial, s));
     DQ_TRY(launch_layernorm_fwd(x, n.tmp, P + a.n1_g, P + a.n1_b, b.y1, b.x1, nullptr, R1, H, s));
     DQ_TRY(tfm_linear(b.x1, P + a.f0_w, P + a.f0_b, b.hpre, R1, 4 * H, H, n.partial, s));
@@ -162,7 +202,8 @@ int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const f
   const int64_t per = (int64_t)S1 * p->D, n = B * per;
   const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
   const int32_t* ts = timesteps_host;
-  SampleNet net{p, params, rope_sin, rope_cos, &w, B, S1, S2, tfm_attn_form(S1, S1 + S2, p->H / p->heads)};
+  const SampleNet net{p, params, rope_sin, rope_cos, &w.net, w.kv.data(), w.t64, w.tfeat, w.th, w.tg, w.ttab, B, S1, S2,
+                      tfm_attn_form(S1, S1 + S2, p->H / p->heads), B, false};
   // the steps' timesteps for the time table (the copy is done when the table upload below returns: it synchronises the stream)
   std::vector<int64_t> t64((size_t)num_steps);
   for (int i = 0; i < num_steps; ++i) t64[i] = ts[i];
@@ -194,6 +235,55 @@ int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const f
     return rc;
   }
   return eager_steps(loop, traj_x, traj_eps, window_ids_dev, seed_dev, s);
+}
+
+int dq_tfm_kv_broadcast(float* kv, int B, int repeats, int S2, int Sk, int H, void* stream) {
+  return launch_tfm_kv_broadcast(kv, B, repeats, S2, Sk, H, (hipStream_t)stream);
+}
+
+int64_t dq_tfm_eval_workspace_bytes(const dq_tfm* p, int B, int S1, int S2, int repeats) {
+  if (!p || B <= 0 || S1 <= 0 || S2 <= 0 || repeats < 1 || (int64_t)repeats * B > 65535) return 0;
+  return carve_eval(*p, nullptr, B, S1, S2, repeats).floats * (int64_t)sizeof(float);
+}
+
+int dq_tfm_eval_step(dq_tfm* p, const float* params, const float* rope_sin, const float* rope_cos, const float* time_freqs,
+                     const float* alpha_bars_dev, const float* x0, const float* ms1_cond, const int64_t* t, const float* noise,
+                     const uint64_t* seed_dev, const int64_t* window_ids_dev, int first_draw, int auto_normalize, int pred_type,
+                     const float* loss_weight_dev, float* loss_out, float* per_window_out, float* net_out, void* workspace,
+                     int64_t workspace_bytes, int B, int S1, int S2, int repeats, void* stream) {
+  DQ_REQUIRE(p && params && rope_sin && rope_cos && time_freqs && alpha_bars_dev && x0 && ms1_cond && t && loss_out && per_window_out && workspace,
+             "dq_tfm_eval_step: null argument");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_tfm_eval_step: Unknown pred_type");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || loss_weight_dev, "dq_tfm_eval_step: pred_type x0 needs the loss-weight (SNR) table");
+  DQ_REQUIRE(B > 0 && S1 > 0 && S2 > 0, "dq_tfm_eval_step: B, S1 and S2 must be positive");
+  DQ_REQUIRE(repeats >= 1, "dq_tfm_eval_step: repeats must be >= 1");
+  DQ_REQUIRE((int64_t)repeats * B <= 65535, "dq_tfm_eval_step: repeats * B must not exceed 65535");
+  DQ_REQUIRE(noise || seed_dev, "dq_tfm_eval_step: a null noise needs the seed (device memory)");
+  DQ_REQUIRE(first_draw >= 0, "dq_tfm_eval_step: first_draw must be >= 0");
+  DQ_REQUIRE(((uintptr_t)params & 15) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)x0 & 15) == 0 && ((uintptr_t)noise & 15) == 0 &&
+                 ((uintptr_t)net_out & 15) == 0,
+             "dq_tfm_eval_step: params, workspace, x0, noise and net_out must be 16-byte aligned");
+  const int R = repeats, N = R * B;
+  DQ_REQUIRE((int64_t)N * (S1 + S2) <= INT32_MAX / 4, "dq_tfm_eval_step: repeats * B * (S1 + S2) too large");
+  const EvalWs w = carve_eval(*p, (float*)workspace, B, S1, S2, R);
+  DQ_REQUIRE(workspace_bytes >= w.floats * (int64_t)sizeof(float), "dq_tfm_eval_step: workspace too small (dq_tfm_eval_workspace_bytes)");
+  PrecisionScope prec(p->precision);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t per = (int64_t)S1 * p->D;
+  const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
+  // the time table: one row per stacked sample, in carve()'s time buffers (batch N); t is read where it lies
+  const SampleNet net{p, params, rope_sin, rope_cos, &w.net, w.kv.data(), t, w.net.tfeat, w.net.th, w.net.tg, w.net.temb, N, S1, S2,
+                      tfm_attn_form(S1, S1 + S2, p->H / p->heads), B, true};
+  float* out = net_out ? net_out : w.out;
+  if (net.form == TFM_ATTN_FUSED) DQ_TRY(tfm_attn_prepare());
+  DQ_TRY(launch_q_sample_repeats(alpha_bars_dev, x0, t, noise, window_ids_dev, seed_dev, first_draw, w.xt, B, R, per, auto_normalize, s));
+  // every call, eagerly: nothing of it outlives the call, so a changed MS1 or changed weights behind the same pointer meet no stale state
+  DQ_TRY(sample_prologue(net, ms1_cond, cm, ca, time_freqs, N, s));
+  DQ_TRY(sample_forward(net, w.xt, 0, nullptr, out, s));
+  const bool px0 = pred_type == DQ_PRED_X0;  // the target: the normalised x0 shared by the repeats, or the noise (read, or drawn again)
+  return launch_mse_per_window_repeats(out, px0 ? x0 : noise, px0 ? B : N, px0 ? cm : 1.f, px0 ? ca : 0.f, window_ids_dev, seed_dev, first_draw,
+                                       px0 ? loss_weight_dev : nullptr, t, per_window_out, loss_out, w.slices,
+                                       mse_per_window_scratch_bytes(N, per), B, R, per, s);
 }
 
 }  // extern "C"

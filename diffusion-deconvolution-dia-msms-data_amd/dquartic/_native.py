@@ -138,6 +138,12 @@ PROTOTYPES = {
     "dq_tfm_sample_workspace_bytes": (c_int64, [c_void_p, c_int, c_int, c_int, c_int]),
     "dq_tfm_sample": (c_int, [c_void_p] * 5 + [POINTER(c_float), c_int] + [c_void_p] * 3 + [c_int, c_int, POINTER(c_int32), c_int] + [c_void_p] * 4
                       + [c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_float]),
+    "dq_tfm_eval_workspace_bytes": (c_int64, [c_void_p, c_int, c_int, c_int, c_int]),
+    "dq_tfm_eval_step": (c_int, [c_void_p] * 12 + [c_int] * 3 + [c_void_p] * 5 + [c_int64] + [c_int] * 4 + [c_void_p]),
+    "dq_q_sample_repeats": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
+    "dq_mse_per_window_repeats": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_int] + [c_void_p] * 5
+                                  + [c_int, c_int, c_int64, c_void_p]),
+    "dq_tfm_kv_broadcast": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p]),
     "dq_linattn_fwd": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_void_p]),
     "dq_linattn_bwd": (c_int, [c_void_p] * 15 + [c_int, c_int, c_int, c_void_p]),
     "dq_linattn_bwd_store": (c_int, [c_void_p] * 15 + [c_int, c_int, c_int, c_void_p]),

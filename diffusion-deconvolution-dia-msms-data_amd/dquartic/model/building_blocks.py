@@ -66,6 +66,7 @@ class CustomTransformer(_FlatBuffers, nn.Module):
         self.precision = "fp32"
         self._ws = {}
         self._sample_ws = {}
+        self._eval_ws = {}
         self._ws_pool = {}  # training workspaces of the autograd bridge: one per forward that still awaits its backward
         self._tables = {}
 
@@ -132,6 +133,22 @@ class CustomTransformer(_FlatBuffers, nn.Module):
             self._sample_ws = {}
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             self._sample_ws[key] = ws
+        return ws
+
+    def eval_workspace(self, B, S1, S2, repeats):
+        """The workspace of ``dq_tfm_eval_step`` for this shape and repeat count (``dq_tfm_eval_workspace_bytes``), cached like
+        ``sample_workspace()``: one at a time.  It lives where the parameters live now (the flat buffer is re-established first: after
+        ``.cuda()`` the old one is still on the host until the first call that reads it)."""
+        dev = self._flat_buffer().device
+        key = (B, S1, S2, int(repeats), str(dev))
+        ws = self._eval_ws.get(key)
+        if ws is None:
+            nbytes = N.lib().dq_tfm_eval_workspace_bytes(self._tfm, B, S1, S2, int(repeats))
+            if nbytes <= 0:
+                raise RuntimeError("dq_tfm_eval_workspace_bytes failed (need B, S1, S2 > 0, repeats >= 1 and repeats * B <= 65535)")
+            self._eval_ws = {}
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self._eval_ws[key] = ws
         return ws
 
     def set_precision(self, precision: str):

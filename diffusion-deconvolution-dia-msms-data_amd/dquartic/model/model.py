@@ -474,11 +474,21 @@ class DDIMDiffusionModel(ModelInterface):
         unweighted MSE of each window against its target (the noise for ``eps``, the normalised ``x_0`` for ``x0``), ``loss`` (0-dim) the
         mean over windows of ``loss_weight[t_b] * per_window[b]``.  The MSE part only: the MS1 term of the training loss is not evaluated.
         It sets no ``.grad``, needs no optimiser, uses the inference workspace and reads the averaged weights inside ``ema_scope()``.
-        ``noise`` is used as passed.  Native network only."""
+        ``noise`` is used as passed.  Native network only: this package's UNet1d, or its CustomTransformer behind
+        ``DDIMTransformerAdapter`` (``dq_tfm_eval_step`` at one repeat; ``ms1_cond`` (B, RT) or (B, RT, 1),
+        ``ms2_cond`` unused: that network has no input for it)."""
+        if self._native_tfm:
+            B = x_0.shape[0]
+            if t is None:
+                t = torch.randint(0, self.num_timesteps, (B,), device=x_0.device).long()
+            if noise is None:
+                noise = torch.randn_like(x_0)
+            loss, per_window = self._eval_steps_tfm(x_0, ms1_cond, t.reshape(1, -1), noise=noise)
+            return loss[0], per_window[0]
         net: UNet1d = self.model
         if not self.native:
-            raise NotImplementedError("eval_step runs in the native library only (this package's UNet1d); "
-                                      f"the network is {type(self.model).__name__}")
+            raise NotImplementedError("eval_step runs in the native library only (this package's UNet1d, or its CustomTransformer behind "
+                                      f"DDIMTransformerAdapter); the network is {type(self.model).__name__}")
         if self.pred_type not in N.PRED_TYPES:
             raise ValueError(f"Unknown pred_type: {self.pred_type}")
         f32 = lambda v: v.detach().to(torch.float32).contiguous()
@@ -499,6 +509,72 @@ class DDIMDiffusionModel(ModelInterface):
         N.check(N.lib().dq_eval_step(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), N.ptr(ab), N.ptr(x_0), N.ptr(c2), N.ptr(c1), N.ptr(t),
                                      N.ptr(noise), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], N.ptr(lw), N.ptr(loss),
                                      N.ptr(per_window), N.ptr(ws), ws.numel(), B, RT, N.stream_ptr()), "dq_eval_step")
+        return loss, per_window
+
+    @torch.no_grad()
+    def eval_steps(self, x_0, ms2_cond, ms1_cond, t, seed_dev, window_ids_dev, first_draw=0):
+        """``eval_step`` for R repeats of one batch: ``t`` (R, B), repeat r under the noise ``dq_randn(seed, window id, draw = first_draw +
+        r)``.  Returns ``(loss (R), per_window (R, B))`` as device tensors.  The CustomTransformer behind its adapter takes all repeats in
+        one native call (``dq_tfm_eval_step``: one stacked forward, the noise drawn inside its kernels and never materialised); UNet1d one
+        ``eval_step`` per repeat on ``evaluation.window_noise``.  Native network only."""
+        from . import evaluation as E
+
+        if not (self.native or self._native_tfm):
+            raise NotImplementedError("eval_steps runs in the native library only (this package's UNet1d, or its CustomTransformer behind "
+                                      f"DDIMTransformerAdapter); the network is {type(self.model).__name__}")
+        t = torch.as_tensor(t)
+        if t.dim() != 2 or t.shape[1] != x_0.shape[0]:
+            raise ValueError(f"eval_steps: t must be (repeats, batch = {x_0.shape[0]}), got {tuple(t.shape)}")
+        if self._native_tfm:
+            return self._eval_steps_tfm(x_0, ms1_cond, t, seed_dev=seed_dev, window_ids_dev=window_ids_dev, first_draw=int(first_draw))
+        losses, per_window = [], []
+        for k in range(t.shape[0]):
+            noise = E.window_noise(seed_dev, window_ids_dev, int(first_draw) + k, x_0.shape)
+            loss, pw = self.eval_step(x_0, ms2_cond, ms1_cond, t=t[k].to(x_0.device), noise=noise)
+            losses.append(loss)
+            per_window.append(pw)
+        return torch.stack(losses), torch.stack(per_window)
+
+    def _eval_steps_tfm(self, x_0, ms1_cond, t, noise=None, seed_dev=None, window_ids_dev=None, first_draw=0):
+        """``dq_tfm_eval_step``: ``t`` (R, B); ``noise`` (R, B, S1, D) as passed, or None: drawn in the kernels from ``seed_dev`` /
+        ``window_ids_dev`` at draw index ``first_draw + r``."""
+        if self.pred_type not in N.PRED_TYPES:
+            raise ValueError(f"Unknown pred_type: {self.pred_type}")
+        tfm = self.model.transformer
+        if not x_0.is_cuda:
+            raise RuntimeError("CustomTransformer (MI355X build): tensors must live on the GPU; there is no CPU fallback")
+        f32 = lambda v: v.detach().to(torch.float32).contiguous()
+        x_0, c1 = f32(x_0), f32(ms1_cond)
+        if c1.dim() == 3:
+            c1 = c1[..., 0].contiguous()
+        if x_0.dim() != 3 or x_0.shape[-1] != tfm.input_dim:
+            raise ValueError(f"eval_step: x_0 must be (batch, seqlen1, input_dim={tfm.input_dim})")
+        B, S1, _ = x_0.shape
+        if c1.dim() != 2 or c1.shape[0] != B:
+            raise ValueError("eval_step: ms1_cond must be (batch, seqlen2) or (batch, seqlen2, 1)")
+        S2 = c1.shape[1]
+        dev = x_0.device
+        t = t.to(device=dev, dtype=torch.int64).contiguous()
+        R = t.shape[0]
+        if t.dim() != 2 or t.shape[1] != B:
+            raise ValueError(f"eval_step: t must be (repeats, batch = {B}), got {tuple(t.shape)}")
+        if noise is not None:
+            noise = f32(noise)
+            if noise.numel() != R * x_0.numel():
+                raise ValueError("eval_step: noise must have the shape of x_0 per repeat")
+        elif seed_dev is None:
+            raise ValueError("eval_steps: the noise is drawn from seed_dev (an int64 device tensor, DDIMDiffusionModel._seed_tensor)")
+        flat = tfm.read_params(False)  # (the averaged weights inside ModelInterface.ema_scope())
+        ws = tfm.eval_workspace(B, S1, S2, R)
+        sin, cos, freqs = tfm.tables(max(S1, S2), dev)
+        loss = torch.empty(R, dtype=torch.float32, device=dev)
+        per_window = torch.empty(R, B, dtype=torch.float32, device=dev)
+        ab = self.alpha_bars.to(dev)
+        lw = self.loss_weight.to(device=dev, dtype=torch.float32).contiguous()
+        N.check(N.lib().dq_tfm_eval_step(tfm._tfm, N.ptr(flat), N.ptr(sin), N.ptr(cos), N.ptr(freqs), N.ptr(ab), N.ptr(x_0), N.ptr(c1), N.ptr(t),
+                                         N.ptr(noise), N.ptr(seed_dev), N.ptr(window_ids_dev), int(first_draw), 1 if self.auto_normalize else 0,
+                                         N.PRED_TYPES[self.pred_type], N.ptr(lw), N.ptr(loss), N.ptr(per_window), None, N.ptr(ws), ws.numel(),
+                                         B, S1, S2, R, N.stream_ptr()), "dq_tfm_eval_step")
         return loss, per_window
 
     def _train_step_fused_tfm(self, x_0, ms1_cond, t=None, noise=None, zero_grads=True, ms1_loss_weight=0.0):

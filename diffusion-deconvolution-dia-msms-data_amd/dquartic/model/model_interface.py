@@ -678,10 +678,12 @@ class ModelInterface(object):
                  sampler="reference", clip_x0=None):
         """Held-out evaluation (new work: the reference has none).  Returns a dict.
 
-        Loss: every window of the loader is evaluated ``n_t`` times by ``eval_step`` -- repeat k at the timestep
+        Loss: every window of the loader is evaluated ``n_t`` times by ``eval_steps`` -- repeat k at the timestep
         ``evaluation.stratified_timesteps`` gives it (one in each of the ``n_t`` equal buckets of [0, T), no RNG) with the noise of
         ``dq_randn(seed, window id, draw = k)``, the window id being the window's running index in the loader as in ``predict``.  Given
-        the loader's windows the numbers are therefore reproducible and do not depend on the batch size.  ``val_loss`` is the mean of
+        the loader's windows the numbers are therefore reproducible and, for UNet1d, do not depend on the batch size; for the
+        CustomTransformer (all repeats of a batch in one stacked forward) they are reproducible bit for bit at a given
+        batch size and agree across batch sizes to fp32 rounding only: its GEMM plans follow the row count.  ``val_loss`` is the mean of
         ``loss_weight[t] * MSE`` over all (window, repeat) pairs, ``val_loss_by_t`` = {"edges": the n_t + 1 bucket edges, "mse": per
         bucket the mean of the UNWEIGHTED per-window MSE}, ``n_windows`` the number of windows seen.  The MSE part of the training loss
         only (no MS1 term).
@@ -717,12 +719,11 @@ class ModelInterface(object):
                     ids_dev = torch.from_numpy(ids).to(x_0.device)
                     if seed_dev is None:
                         seed_dev = self._seed_tensor(int(seed), x_0.device)
+                    t = np.stack([E.stratified_timesteps(ids, k, n_t, T) for k in range(n_t)])  # (n_t, B): repeat k draws at index k
+                    _, per_window = self.eval_steps(x_0, ms2_cond, ms1_cond, torch.from_numpy(t).to(x_0.device), seed_dev, ids_dev)
                     for k in range(n_t):
-                        t = E.stratified_timesteps(ids, k, n_t, T)
-                        noise = E.window_noise(seed_dev, ids_dev, k, x_0.shape)
-                        _, per_window = self.eval_step(x_0, ms2_cond, ms1_cond, t=torch.from_numpy(t).to(x_0.device), noise=noise)
-                        mse[k].append(per_window)
-                        ts[k].append(t)
+                        mse[k].append(per_window[k])
+                        ts[k].append(t[k])
                     if num_steps is not None:
                         sample, _ = self.sample(None, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=int(num_steps), eta=eta, seed=int(seed),
                                                 window_ids=ids_dev, shape=tuple(x_0.shape), **_sampler_kwargs(sampler, clip_x0))

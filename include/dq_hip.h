@@ -55,7 +55,8 @@ const char* dq_last_error(void);
  * dq_tfm_layernorm_bwd, dq_tfm_softmax_rows, dq_tfm_softmax_rows_bwd, dq_tfm_colsum, dq_tfm_seqsum; the transformer's sampler:
  * dq_tfm_attn_form, dq_tfm_attn_fwd, dq_tfm_sample_workspace_bytes, dq_tfm_sample; the wide bottleneck alone: dq_wide_im2col3,
  * dq_wide_col2im3, dq_wide_repitch, dq_wide_norm_fwd, dq_wide_norm_bwd, dq_wide_norm_bwd_scratch_floats, dq_wide_rowsum, dq_wide_sum_b,
- * dq_debug_wide_mid_fwd, dq_debug_wide_mid_bwd). */
+ * dq_debug_wide_mid_fwd, dq_debug_wide_mid_bwd; the transformer's held-out evaluation: dq_tfm_eval_workspace_bytes, dq_tfm_eval_step,
+ * dq_q_sample_repeats, dq_mse_per_window_repeats, dq_tfm_kv_broadcast). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -468,6 +469,44 @@ int dq_tfm_sample(dq_tfm* tfm, const float* params, const float* rope_sin, const
                   int auto_normalize, int pred_type, const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise,
                   float* traj_x, float* traj_eps, int use_graph, void* workspace, int64_t workspace_bytes, int B, int S1, int S2,
                   void* stream, float eta, const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0);
+/* Held-out evaluation of the transformer in one call per batch (csrc/dq_tfm_sample.hip, csrc/k_tfm_eval.hip, DESIGN.md section 31;
+ * additive at ABI version 12): dq_eval_step's semantics for `repeats` = R repeats of a batch of B windows stacked into N = R * B samples,
+ * sample n = r * B + b (repeat-major), through ONE forward -- dq_tfm_sample's prologue and forward, the same code.
+ *   x0 (B, S1, input_dim), shared by the repeats and not replicated; ms1_cond (B, S2) raw (2c - 1 first when auto_normalize); t (R, B) int64
+ *   on the device; noise (R, B, S1, input_dim) or NULL: then seed_dev is required and the noise of (r, b) is
+ *   philox_normal(seed, window_ids ? ids[b] : b, e, first_draw + r) -- what dq_randn(draw = first_draw + r) writes -- evaluated inside the
+ *   kernels and never written to memory.  There is no ms2_cond: this network has no input for it.
+ *   per_window_out (R, B): the unweighted MSE of the network output against its target (DQ_PRED_EPS: the noise; DQ_PRED_X0: x0 * cm + ca);
+ *   loss_out (R): (float)(sum_b lw[t[r, b]] * mse[r, b] / B), summed in fp64 in index order; loss_weight_dev is required for x0 and ignored
+ *   for eps.  The MSE part only.  net_out (nullable): receives the network output (R, B, S1, input_dim); otherwise it lives in the workspace.
+ * The conditional embedding and every layer's K | V rows of it are computed once for the B windows and copied to the other R - 1 repeats
+ * (R == 1: no copy); the time MLP runs once over the N timesteps.  Eager only, nothing cached across calls; neither the handle's saved
+ * forwards nor any training workspace is touched; honours dq_tfm_set_precision.  Refused with a message: a null required argument, an
+ * unknown pred_type, repeats < 1, R * B > 65535, noise == NULL without seed_dev, first_draw < 0, params / workspace / x0 (noise, net_out)
+ * not 16-byte aligned, a workspace below dq_tfm_eval_workspace_bytes(tfm, B, S1, S2, repeats) (0 on a bad argument; host only).
+ * Two identical calls give identical bits; a window's value at another B or R agrees to rounding only (the GEMM plan follows the row count). */
+int64_t dq_tfm_eval_workspace_bytes(const dq_tfm* tfm, int B, int S1, int S2, int repeats);
+int dq_tfm_eval_step(dq_tfm* tfm, const float* params, const float* rope_sin, const float* rope_cos, const float* time_freqs,
+                     const float* alpha_bars_dev, const float* x0, const float* ms1_cond, const int64_t* t, const float* noise,
+                     const uint64_t* seed_dev, const int64_t* window_ids_dev, int first_draw, int auto_normalize, int pred_type,
+                     const float* loss_weight_dev, float* loss_out, float* per_window_out, float* net_out, void* workspace,
+                     int64_t workspace_bytes, int B, int S1, int S2, int repeats, void* stream);
+/* Its three streaming kernels alone (csrc/k_tfm_eval.hip).  per_window % 4 == 0 and 16-byte aligned tensors for the first, like
+ * dq_ddim_step_sto.
+ * dq_q_sample_repeats: x_t (R, B, per_window) = sa * norm(x0[b]) + sb * z[r, b] with sa, sb from alpha_bars[t[r, b]]: dq_q_sample's
+ * arithmetic on x0 (B, per_window); z read from noise (R, B, per_window) or, noise == NULL, drawn at draw index first_draw + r.
+ * dq_mse_per_window_repeats: dq_mse_per_window per repeat on out (R, B, per): the target has target_windows = B (shared by the repeats) or
+ * R * B windows, or is drawn (target == NULL: the noise above); per_window_out (R, B), loss_out (R); scratch:
+ * dq_mse_per_window_scratch_bytes(R * B, per) bytes.  Bit for bit dq_mse_per_window applied to each repeat.
+ * dq_tfm_kv_broadcast: kv (R * B, Sk, 2H), 16-byte aligned: rows [0, S2) of samples 0 .. B-1 copied to samples B .. R * B - 1; nothing else
+ * is written, and nothing at all when repeats == 1. */
+int dq_q_sample_repeats(const float* alpha_bars_dev, const float* x0, const int64_t* t, const float* noise, const uint64_t* seed_dev,
+                        const int64_t* window_ids_dev, int first_draw, float* x_t, int B, int repeats, int64_t per_window, int normalize_x0,
+                        void* stream);
+int dq_mse_per_window_repeats(const float* out, const float* target, int target_windows, float tm, float ta, const uint64_t* seed_dev,
+                              const int64_t* window_ids_dev, int first_draw, const float* lw, const int64_t* t, float* per_window_out,
+                              float* loss_out, void* scratch, int B, int repeats, int64_t per, void* stream);
+int dq_tfm_kv_broadcast(float* kv, int B, int repeats, int S2, int Sk, int H, void* stream);
 /* The fp32 matrix-core GEMM underneath (exported for the parity tests and the roofline measurement):
  * C (M,N; ldc) = A B (+ bias[n]) with A(m,k) = a_kmajor ? A[m*lda+k] : A[k*lda+m] and B(k,n) = b_kmajor ? B[n*ldb+k] :
  * B[k*ldb+n]; splits = 0 lets the library choose a split-K factor; scratch: dq_gemm_scratch_floats(M,N,K) floats. */
