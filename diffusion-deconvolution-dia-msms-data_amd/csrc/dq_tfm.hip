@@ -7,6 +7,7 @@
 #include "dq_tfm.h"
 #include "dq_tfm_net.h"
 #include "dq_kernels.h"
+#include "dq_net.h"  // DQ_TRY
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -15,31 +16,34 @@
 namespace dq {
 
 // (Ws: dq_tfm_net.h) carved in a fixed order; `training` keeps one set of layer buffers per layer (read by the backward)
-Ws carve(const dq_tfm& p, float* base, int B, int S1, int S2, bool training) {
+Ws carve(const dq_tfm& p, Carver& c, int B, int S1, int S2, bool training) {
   Ws w;
-  int64_t off = 0;
-  auto take = [&](int64_t n) { float* r = base ? base + off : nullptr; off += up4(n); return r; };
   const int64_t H = p.H, R1 = (int64_t)B * S1, R2 = (int64_t)B * S2, Sk = S1 + S2, ldp = up4(Sk);
-  w.cp = take(R2 * H); w.tfeat = take(B * H); w.th = take(B * 4 * H); w.tg = take(B * 4 * H); w.temb = take(B * H);
-  w.x0 = take(R1 * H); w.tmp = take(R1 * H);
-  w.partial = take(TFM_PARTIAL_FLOATS);
-  w.colscr = take(std::max<int64_t>((int64_t)COLSUM_BLOCKS * std::max<int64_t>(p.D, 4 * H), 2 * H * 64));
-  w.lnscr = take((int64_t)2 * H * LN_BWD_BLOCKS);
+  w.cp = c.take(R2 * H); w.time.tfeat = c.take(B * H); w.time.th = c.take(B * 4 * H); w.time.tg = c.take(B * 4 * H); w.time.temb = c.take(B * H);
+  w.x0 = c.take(R1 * H); w.tmp = c.take(R1 * H);
+  w.partial = c.take(TFM_PARTIAL_FLOATS);
+  w.colscr = c.take(std::max<int64_t>((int64_t)COLSUM_BLOCKS * std::max<int64_t>(p.D, 4 * H), 2 * H * 64));
+  w.lnscr = c.take((int64_t)2 * H * LN_BWD_BLOCKS);
   const int nl = training ? p.layers : 1;
   for (int l = 0; l < nl; ++l) {
     Ws::Layer a;
-    a.comb = take(B * Sk * H); a.q = take(R1 * H); a.kv = take(B * Sk * 2 * H); a.prob = take((int64_t)B * p.heads * S1 * ldp);
-    a.ao = take(R1 * H); a.y1 = take(R1 * H); a.st1 = take(R1 * 2); a.x1 = take(R1 * H); a.hpre = take(R1 * 4 * H);
-    a.hact = take(R1 * 4 * H); a.y2 = take(R1 * H); a.st2 = take(R1 * 2); a.xo = take(R1 * H);
+    a.comb = c.take(B * Sk * H); a.q = c.take(R1 * H); a.kv = c.take(B * Sk * 2 * H); a.prob = c.take((int64_t)B * p.heads * S1 * ldp);
+    a.ao = c.take(R1 * H); a.y1 = c.take(R1 * H); a.st1 = c.take(R1 * 2); a.x1 = c.take(R1 * H); a.hpre = c.take(R1 * 4 * H);
+    a.hact = c.take(R1 * 4 * H); a.y2 = c.take(R1 * H); a.st2 = c.take(R1 * 2); a.xo = c.take(R1 * H);
     w.L.push_back(a);
   }
   if (training) {
-    w.dxa = take(R1 * H); w.dxb = take(R1 * H); w.dh = take(R1 * 4 * H); w.dq = take(R1 * H); w.dkv = take(B * Sk * 2 * H);
-    w.dprob = take((int64_t)B * p.heads * S1 * ldp); w.dao = take(R1 * H); w.dcomb = take(B * Sk * H); w.dcp = take(R2 * H);
-    w.dtemb = take(B * H); w.dtg = take(B * 4 * H);
+    w.dxa = c.take(R1 * H); w.dxb = c.take(R1 * H); w.dh = c.take(R1 * 4 * H); w.dq = c.take(R1 * H); w.dkv = c.take(B * Sk * 2 * H);
+    w.dprob = c.take((int64_t)B * p.heads * S1 * ldp); w.dao = c.take(R1 * H); w.dcomb = c.take(B * Sk * H); w.dcp = c.take(R2 * H);
+    w.dtemb = c.take(B * H); w.dtg = c.take(B * 4 * H);
   }
-  w.floats = off;
   return w;
+}
+
+std::vector<float*> carve_kv(const dq_tfm& p, Carver& c, int B, int Sk) {
+  std::vector<float*> kv;
+  for (int l = 0; l < p.layers; ++l) kv.push_back(c.take((int64_t)B * Sk * 2 * p.H));
+  return kv;
 }
 
 namespace {
@@ -52,10 +56,7 @@ int64_t add(dq_tfm& p, const std::string& name, int64_t a, int64_t b = 0) {
   return pi.offset;
 }
 
-// y (M, N) = x (M, K) W^T + b   with W an nn.Linear weight (N, K)
-int linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K, const Ws& ws, hipStream_t s) {
-  return tfm_linear(x, w, b, y, M, N, K, ws.partial, s);
-}
+// with W an nn.Linear weight (N, K) (y = x W^T + b: tfm_linear):
 // dW (N, K) += dy^T x ; db (N) += column sums of dy ; dx (M, K) (+)= dy W  (dx nullable)
 int linear_bwd(const float* x, const float* w, const float* dy, float* dw, float* db, float* dx, int dx_accumulate, int M, int N, int K,
                const Ws& ws, hipStream_t s, int acc) {
@@ -141,61 +142,68 @@ int tfm_attention_fwd(int form, const AttnDims& d, const float* q, const float* 
   return attn_gemm(1, d, nullptr, kv, prob, o, partial, s);
 }
 
+int tfm_time_mlp(const dq_tfm& p, const float* P, const int64_t* t, const float* time_freqs, const TimeBufs& b, int n, float* partial, hipStream_t s) {
+  const int H = p.H;
+  DQ_TRY(launch_time_features(t, time_freqs, b.tfeat, n, H, s));
+  DQ_TRY(tfm_linear(b.tfeat, P + p.t1_w, P + p.t1_b, b.th, n, 4 * H, H, partial, s));
+  DQ_TRY(launch_gelu(b.th, b.tg, (int64_t)n * 4 * H, s));
+  return tfm_linear(b.tg, P + p.t2_w, P + p.t2_b, b.temb, n, H, 4 * H, partial, s);
+}
+
+int tfm_kv_rows(const dq_tfm& p, const float* P, int l, const float* rows, int M, int row0, int batch, float* kv_l, int Sk, float* partial,
+                hipStream_t s) {
+  const int H = p.H;
+  const TfmLayer& a = p.L[l];
+  Gemm g;
+  g.A = rows; g.lda = H; g.sAo = (int64_t)M * H;
+  g.B = P + a.in_w + (int64_t)H * H; g.ldb = H; g.bias = P + a.in_b + H;
+  g.C = kv_l + (int64_t)row0 * 2 * H; g.ldc = 2 * H; g.sCo = (int64_t)Sk * 2 * H;
+  g.batch = batch; g.M = M; g.N = 2 * H; g.K = H;
+  g.partial = partial; g.partial_floats = TFM_PARTIAL_FLOATS;
+  return launch_gemm(g, s);
+}
+
+int tfm_walk(const TfmWalk& k, const float* x_in, float* out, hipStream_t s) {
+  const dq_tfm& p = *k.p;
+  const Ws& w = *k.w;
+  const float* P = k.P;
+  const int B = k.B, S1 = k.S1, S2 = k.S2, H = p.H, D = p.D, R1 = B * S1, Sk = S1 + S2;
+  // projections + RoPE (+ time embedding on the x_t side) (building_blocks.py:238-253)
+  DQ_TRY(tfm_linear(x_in, P + p.in_w, P + p.in_b, w.x0, R1, H, D, w.partial, s));
+  if (k.time_per_sample) DQ_TRY(launch_rope_add(w.x0, k.sin_t, k.cos_t, k.temb, B, S1, H, 0, s));
+  else DQ_TRY(launch_rope_add_row(w.x0, k.sin_t, k.cos_t, k.temb, k.time_row, k.step_ptr, B, S1, H, s));
+  if (k.x_cond) DQ_TRY(launch_cond_embed(k.x_cond, P + p.c_w, P + p.c_b, k.sin_t, k.cos_t, w.cp, B, S2, H, s));
+  const AttnDims ad{B, S1, Sk, H, p.heads, H / p.heads, up4(Sk)};
+  const float* x = w.x0;
+  for (int l = 0; l < p.layers; ++l) {
+    const TfmLayer& a = p.L[l];
+    const Ws::Layer& b = w.L[k.per_layer ? l : 0];
+    // nn.MultiheadAttention (:164-166): q from x_t, k | v from [x_cond ; x_t] (:161: cat([x_cond, x_t], dim=1))
+    float* kv = k.x_cond ? b.kv : k.kv[l];
+    if (k.x_cond) {
+      hipLaunchKernelGGL(k_build_comb, dim3(grid_for((int64_t)B * Sk * H)), dim3(256), 0, s, w.cp, x, b.comb, B, S1, S2, H);
+      DQ_LAUNCH_CHECK();
+    }
+    DQ_TRY(tfm_linear(x, P + a.in_w, P + a.in_b, b.q, R1, H, H, w.partial, s));
+    if (k.x_cond) DQ_TRY(tfm_linear(b.comb, P + a.in_w + (int64_t)H * H, P + a.in_b + H, kv, B * Sk, 2 * H, H, w.partial, s));
+    else DQ_TRY(tfm_kv_rows(p, P, l, x, S1, S2, B, kv, Sk, w.partial, s));
+    DQ_TRY(tfm_attention_fwd(k.attn_form, ad, b.q, kv, b.prob, b.ao, w.partial, s));
+    DQ_TRY(tfm_linear(b.ao, P + a.out_w, P + a.out_b, w.tmp, R1, H, H, w.partial, s));
+    DQ_TRY(launch_layernorm_fwd(x, w.tmp, P + a.n1_g, P + a.n1_b, b.y1, b.x1, k.ln_stats ? b.st1 : nullptr, R1, H, s));  // :168
+    DQ_TRY(tfm_linear(b.x1, P + a.f0_w, P + a.f0_b, b.hpre, R1, 4 * H, H, w.partial, s));                                 // :171
+    DQ_TRY(launch_gelu(b.hpre, b.hact, (int64_t)R1 * 4 * H, s));
+    DQ_TRY(tfm_linear(b.hact, P + a.f2_w, P + a.f2_b, w.tmp, R1, H, 4 * H, w.partial, s));
+    DQ_TRY(launch_layernorm_fwd(b.x1, w.tmp, P + a.n2_g, P + a.n2_b, b.y2, b.xo, k.ln_stats ? b.st2 : nullptr, R1, H, s));  // :172
+    x = b.xo;
+  }
+  return tfm_linear(x, P + p.out_w, P + p.out_b, out, R1, D, H, w.partial, s);  // :258
+}
+
 }  // namespace dq
 
 using namespace dq;
 
 extern "C" {
-
-int64_t dq_gemm_scratch_floats(int M, int N, int K) { return std::max<int64_t>(gemm_partial_floats(M, N, K, 1), 4); }
-// the descriptor of the C ABI -> the launcher's own (field for field)
-static int run_desc(const dq_gemm_desc& d, void* stream) {
-  DQ_REQUIRE(d.precision == DQ_PRECISION_FP32 || d.precision == DQ_PRECISION_BF16X3, "dq_gemm_ex: precision must be DQ_PRECISION_FP32 or DQ_PRECISION_BF16X3");
-  Gemm g;
-  g.A = d.A; g.B = d.B; g.C = d.C; g.M = d.M; g.N = d.N; g.K = d.K; g.lda = d.lda; g.ldb = d.ldb; g.ldc = d.ldc;
-  g.a_kmajor = d.a_kmajor; g.b_kmajor = d.b_kmajor; g.batch = d.batch; g.inner = d.inner;
-  g.sAo = d.sAo; g.sAi = d.sAi; g.sBo = d.sBo; g.sBi = d.sBi; g.sCo = d.sCo; g.sCi = d.sCi;
-  g.kbatch = d.kbatch; g.sAk = d.sAk; g.sBk = d.sBk;
-  g.bias = d.bias; g.bias_m = d.bias_m; g.alpha = d.alpha; g.accumulate = d.accumulate; g.add = d.add;
-  g.splits = d.splits; g.partial = d.scratch; g.partial_floats = d.scratch_floats;
-  g.precision = d.precision == DQ_PRECISION_BF16X3 ? GEMM_BF16X3 : GEMM_FP32;
-  return launch_gemm(g, (hipStream_t)stream);
-}
-static dq_gemm_desc plain_desc(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int64_t lda, int64_t ldb,
-                               int64_t ldc, int a_kmajor, int b_kmajor, int accumulate, int splits, float* scratch, int64_t scratch_floats,
-                               int precision) {
-  dq_gemm_desc d = {};
-  d.A = A; d.B = B; d.C = C; d.bias = bias; d.M = M; d.N = N; d.K = K; d.lda = lda; d.ldb = ldb; d.ldc = ldc;
-  d.a_kmajor = a_kmajor; d.b_kmajor = b_kmajor; d.batch = 1; d.inner = 1; d.kbatch = 1; d.alpha = 1.f;
-  d.accumulate = accumulate; d.splits = splits; d.scratch = scratch; d.scratch_floats = scratch_floats; d.precision = precision;
-  return d;
-}
-int dq_gemm(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
-            int a_kmajor, int b_kmajor, int accumulate, int splits, float* scratch, int64_t scratch_floats, void* stream) {
-  return run_desc(plain_desc(A, B, C, bias, M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor, accumulate, splits, scratch, scratch_floats,
-                             DQ_PRECISION_FP32), stream);
-}
-int dq_gemm_bf16x3(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
-                   int a_kmajor, int b_kmajor, int accumulate, int splits, float* scratch, int64_t scratch_floats, void* stream) {
-  return run_desc(plain_desc(A, B, C, bias, M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor, accumulate, splits, scratch, scratch_floats,
-                             DQ_PRECISION_BF16X3), stream);
-}
-int dq_gemm_ex(const dq_gemm_desc* desc, void* stream) {
-  DQ_REQUIRE(desc, "dq_gemm_ex: null descriptor");
-  return run_desc(*desc, stream);
-}
-int dq_debug_gemm_plan(int M, int N, int K, int batch, int kbatch, int splits, int32_t* out, int cap, int64_t* scratch_floats) {
-  if (!out || cap < DQ_GEMM_PLAN_INTS || M < 1 || N < 1 || K < 1 || batch < 1 || kbatch < 1 || splits < 0) return -1;
-  const GemmShape sh = gemm_plan(M, N, K, batch, kbatch, splits);
-  int n = 0;
-  out[n++] = sh.bm;
-  out[n++] = sh.kv;
-  for (const GemmPart* p : {&sh.full, &sh.rest}) {
-    out[n++] = p->tile_base; out[n++] = p->ntiles; out[n++] = p->splits; out[n++] = p->k_per_split;
-  }
-  if (scratch_floats) *scratch_floats = sh.scratch;
-  return n;
-}
 
 int dq_tfm_set_precision(dq_tfm* tfm, int precision) {
   DQ_REQUIRE(tfm, "dq_tfm_set_precision: null handle");
@@ -252,7 +260,9 @@ int dq_tfm_param_info(const dq_tfm* p, int i, char* name, int name_cap, int64_t*
 }
 int64_t dq_tfm_workspace_bytes(const dq_tfm* p, int B, int S1, int S2, int training) {
   if (!p || B <= 0 || S1 <= 0 || S2 <= 0) return 0;
-  return carve(*p, nullptr, B, S1, S2, training != 0).floats * (int64_t)sizeof(float);
+  Carver c{nullptr};
+  carve(*p, c, B, S1, S2, training != 0);
+  return c.off * (int64_t)sizeof(float);
 }
 
 int dq_tfm_fwd(dq_tfm* p, const float* params, const float* rope_sin, const float* rope_cos, const float* time_freqs, const float* x_t,
@@ -263,42 +273,15 @@ int dq_tfm_fwd(dq_tfm* p, const float* params, const float* rope_sin, const floa
   DQ_REQUIRE(((uintptr_t)params & 15) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)x_t & 15) == 0, "dq_tfm_fwd: params, x_t and workspace must be 16-byte aligned");
   PrecisionScope prec(p->precision);
   const bool training = save_for_bwd != 0;
-  Ws w = carve(*p, (float*)workspace, B, S1, S2, training);
-  DQ_REQUIRE(workspace_bytes >= w.floats * (int64_t)sizeof(float), "dq_tfm_fwd: workspace too small (dq_tfm_workspace_bytes)");
+  Carver c{(float*)workspace};
+  const Ws w = carve(*p, c, B, S1, S2, training);
+  DQ_REQUIRE(workspace_bytes >= c.off * (int64_t)sizeof(float), "dq_tfm_fwd: workspace too small (dq_tfm_workspace_bytes)");
   hipStream_t s = (hipStream_t)stream;
-  const int H = p->H, D = p->D, R1 = B * S1, Sk = S1 + S2;
-  const float* P = params;
-  // time embedding (building_blocks.py:92-112)
-  if (int rc = launch_time_features(t, time_freqs, w.tfeat, B, H, s)) return rc;
-  if (int rc = linear_fwd(w.tfeat, P + p->t1_w, P + p->t1_b, w.th, B, 4 * H, H, w, s)) return rc;
-  if (int rc = launch_gelu(w.th, w.tg, (int64_t)B * 4 * H, s)) return rc;
-  if (int rc = linear_fwd(w.tg, P + p->t2_w, P + p->t2_b, w.temb, B, H, 4 * H, w, s)) return rc;
-  // projections + RoPE (+ time embedding on the x_t side) (:238-253)
-  if (int rc = linear_fwd(x_t, P + p->in_w, P + p->in_b, w.x0, R1, H, D, w, s)) return rc;
-  if (int rc = launch_rope_add(w.x0, rope_sin, rope_cos, w.temb, B, S1, H, 0, s)) return rc;
-  if (int rc = launch_cond_embed(x_cond, P + p->c_w, P + p->c_b, rope_sin, rope_cos, w.cp, B, S2, H, s)) return rc;
-  const AttnDims ad{B, S1, Sk, H, p->heads, H / p->heads, up4(Sk)};
-  const float* x = w.x0;
-  for (int l = 0; l < p->layers; ++l) {
-    const TfmLayer& a = p->L[l];
-    const Ws::Layer& b = w.L[training ? l : 0];
-    hipLaunchKernelGGL(k_build_comb, dim3(grid_for((int64_t)B * Sk * H)), dim3(256), 0, s, w.cp, x, b.comb, B, S1, S2, H);
-    DQ_LAUNCH_CHECK();
-    // nn.MultiheadAttention (:164-166): q from x_t, k | v from [x_cond ; x_t]
-    if (int rc = linear_fwd(x, P + a.in_w, P + a.in_b, b.q, R1, H, H, w, s)) return rc;
-    if (int rc = linear_fwd(b.comb, P + a.in_w + (int64_t)H * H, P + a.in_b + H, b.kv, B * Sk, 2 * H, H, w, s)) return rc;
-    if (int rc = attn_gemm(0, ad, b.q, b.kv, b.prob, nullptr, w.partial, s)) return rc;
-    if (int rc = launch_softmax_rows(b.prob, (int64_t)B * p->heads * S1, Sk, (int)ad.ldp, 1.0f / sqrtf((float)ad.dh), s)) return rc;
-    if (int rc = attn_gemm(1, ad, nullptr, b.kv, b.prob, b.ao, w.partial, s)) return rc;
-    if (int rc = linear_fwd(b.ao, P + a.out_w, P + a.out_b, w.tmp, R1, H, H, w, s)) return rc;
-    if (int rc = launch_layernorm_fwd(x, w.tmp, P + a.n1_g, P + a.n1_b, b.y1, b.x1, b.st1, R1, H, s)) return rc;  // :168
-    if (int rc = linear_fwd(b.x1, P + a.f0_w, P + a.f0_b, b.hpre, R1, 4 * H, H, w, s)) return rc;                    // :171
-    if (int rc = launch_gelu(b.hpre, b.hact, (int64_t)R1 * 4 * H, s)) return rc;
-    if (int rc = linear_fwd(b.hact, P + a.f2_w, P + a.f2_b, w.tmp, R1, H, 4 * H, w, s)) return rc;
-    if (int rc = launch_layernorm_fwd(b.x1, w.tmp, P + a.n2_g, P + a.n2_b, b.y2, b.xo, b.st2, R1, H, s)) return rc;  // :172
-    x = b.xo;
-  }
-  if (int rc = linear_fwd(x, P + p->out_w, P + p->out_b, out, R1, D, H, w, s)) return rc;  // :258
+  DQ_TRY(tfm_time_mlp(*p, params, t, time_freqs, w.time, B, w.partial, s));
+  // its own K | V per layer from [cp ; x], the attention through `prob` (the backward reads it), every sample its own time row
+  TfmWalk walk{p, params, rope_sin, rope_cos, &w, B, S1, S2};
+  walk.per_layer = training; walk.ln_stats = true; walk.x_cond = x_cond; walk.temb = w.time.temb; walk.time_per_sample = true;
+  DQ_TRY(tfm_walk(walk, x_t, out, s));
   for (size_t i = 0; i < p->saved.size(); ++i)
     if (p->saved[i].ws == workspace) { p->saved.erase(p->saved.begin() + i); break; }  // (an inference forward overwrites what was saved there)
   if (training) {
@@ -336,8 +319,9 @@ static int tfm_bwd_impl(dq_tfm* p, const float* params, const float* rope_sin, c
   }
   DQ_REQUIRE(((uintptr_t)grads & 15) == 0 && ((uintptr_t)dout & 15) == 0, "dq_tfm_bwd: grads and dout must be 16-byte aligned");
   PrecisionScope prec(p->precision);
-  Ws w = carve(*p, (float*)workspace, B, S1, S2, true);
-  DQ_REQUIRE(workspace_bytes >= w.floats * (int64_t)sizeof(float), "dq_tfm_bwd: workspace too small");
+  Carver c{(float*)workspace};
+  const Ws w = carve(*p, c, B, S1, S2, true);
+  DQ_REQUIRE(workspace_bytes >= c.off * (int64_t)sizeof(float), "dq_tfm_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int acc = accumulate ? 1 : 0;  // 0: every parameter gradient is written exactly once by this backward -> plain stores
   const int H = p->H, D = p->D, R1 = B * S1, R2 = B * S2, Sk = S1 + S2;
@@ -387,9 +371,9 @@ static int tfm_bwd_impl(dq_tfm* p, const float* params, const float* rope_sin, c
   if (int rc = linear_bwd(x_t, P + p->in_w, dx, G + p->in_w, G + p->in_b, dx_t, 0, R1, H, D, w, s, acc)) return rc;
   if (int rc = launch_cond_embed_bwd(w.dcp, x_cond, P + p->c_w, rope_sin, rope_cos, G + p->c_w, G + p->c_b, dx_cond, w.colscr, B, S2, H, s, acc)) return rc;
   // time MLP
-  if (int rc = linear_bwd(w.tg, P + p->t2_w, w.dtemb, G + p->t2_w, G + p->t2_b, w.dtg, 0, B, H, 4 * H, w, s, acc)) return rc;
-  if (int rc = launch_gelu_bwd(w.th, w.dtg, w.dtg, (int64_t)B * 4 * H, s)) return rc;
-  if (int rc = linear_bwd(w.tfeat, P + p->t1_w, w.dtg, G + p->t1_w, G + p->t1_b, nullptr, 0, B, 4 * H, H, w, s, acc)) return rc;
+  if (int rc = linear_bwd(w.time.tg, P + p->t2_w, w.dtemb, G + p->t2_w, G + p->t2_b, w.dtg, 0, B, H, 4 * H, w, s, acc)) return rc;
+  if (int rc = launch_gelu_bwd(w.time.th, w.dtg, w.dtg, (int64_t)B * 4 * H, s)) return rc;
+  if (int rc = linear_bwd(w.time.tfeat, P + p->t1_w, w.dtg, G + p->t1_w, G + p->t1_b, nullptr, 0, B, 4 * H, H, w, s, acc)) return rc;
   if (on_bucket) {
     int64_t off, cnt;
     tfm_bucket(*p, p->layers, &off, &cnt);
@@ -420,83 +404,6 @@ int dq_tfm_bucket_info(const dq_tfm* p, int i, int64_t* offset, int64_t* count) 
   DQ_REQUIRE(p && offset && count && i >= 0 && i <= p->layers, "dq_tfm_bucket_info: bucket index out of range");
   tfm_bucket(*p, i, offset, count);
   return 0;
-}
-
-}  // extern "C"
-
-// ---- the kernels between the GEMMs, one launcher each on tensors the caller chooses (exported for the parity tests: tests/test_tfm_kernels.py).
-// Thin: argument checks, then the launcher of dq_tfm.h that dq_tfm_fwd / dq_tfm_bwd call; nothing is allocated.
-extern "C" {
-
-int dq_tfm_layernorm_form(int H, int aligned16) { return H > 0 ? layernorm_form(H, H % 4 == 0 && aligned16 != 0) : -1; }
-
-int dq_tfm_rope_add(float* x, const float* sin_t, const float* cos_t, const float* temb, int B, int S, int H, int inverse, void* stream) {
-  DQ_REQUIRE(x && sin_t && cos_t, "dq_tfm_rope_add: null argument");
-  DQ_REQUIRE(B > 0 && S > 0 && H > 0 && H % 2 == 0, "dq_tfm_rope_add: B, S positive, H positive and even");
-  DQ_REQUIRE(((uintptr_t)x & 7) == 0, "dq_tfm_rope_add: x must be 8-byte aligned (channel pairs move as float2)");
-  return launch_rope_add(x, sin_t, cos_t, temb, B, S, H, inverse, (hipStream_t)stream);
-}
-int dq_tfm_cond_embed(const float* x_cond, const float* w, const float* bias, const float* sin_t, const float* cos_t, float* c, int B, int S,
-                      int H, void* stream) {
-  DQ_REQUIRE(x_cond && w && bias && sin_t && cos_t && c, "dq_tfm_cond_embed: null argument");
-  DQ_REQUIRE(B > 0 && S > 0 && H > 0 && H % 2 == 0, "dq_tfm_cond_embed: B, S positive, H positive and even");
-  DQ_REQUIRE(((uintptr_t)c & 7) == 0, "dq_tfm_cond_embed: c must be 8-byte aligned (channel pairs move as float2)");
-  return launch_cond_embed(x_cond, w, bias, sin_t, cos_t, c, B, S, H, (hipStream_t)stream);
-}
-int dq_tfm_cond_embed_bwd(const float* dc, const float* x_cond, const float* w, const float* sin_t, const float* cos_t, float* dw, float* db,
-                          float* dx_cond, float* scratch, int64_t scratch_floats, int B, int S, int H, int accumulate, void* stream) {
-  DQ_REQUIRE(dc && x_cond && w && sin_t && cos_t && dw && db && scratch, "dq_tfm_cond_embed_bwd: null argument");
-  DQ_REQUIRE(B > 0 && S > 0 && H > 0 && H % 2 == 0, "dq_tfm_cond_embed_bwd: B, S positive, H positive and even");
-  DQ_REQUIRE(((uintptr_t)dc & 7) == 0, "dq_tfm_cond_embed_bwd: dc must be 8-byte aligned (channel pairs move as float2)");
-  DQ_REQUIRE(scratch_floats >= (int64_t)2 * H * 64, "dq_tfm_cond_embed_bwd: scratch needs 2 * H * 64 floats");
-  return launch_cond_embed_bwd(dc, x_cond, w, sin_t, cos_t, dw, db, dx_cond, scratch, B, S, H, (hipStream_t)stream, accumulate ? 1 : 0);
-}
-int dq_tfm_time_features(const int64_t* t, const float* freqs, float* e, int B, int H, void* stream) {
-  DQ_REQUIRE(t && freqs && e, "dq_tfm_time_features: null argument");
-  DQ_REQUIRE(B > 0 && H > 0 && H % 2 == 0, "dq_tfm_time_features: B positive, H positive and even");
-  return launch_time_features(t, freqs, e, B, H, (hipStream_t)stream);
-}
-int dq_tfm_gelu(const float* x, float* y, int64_t n, void* stream) {
-  DQ_REQUIRE(x && y && n >= 0, "dq_tfm_gelu: null argument");
-  return launch_gelu(x, y, n, (hipStream_t)stream);
-}
-int dq_tfm_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream) {
-  DQ_REQUIRE(x && dy && dx && n >= 0, "dq_tfm_gelu_bwd: null argument");
-  return launch_gelu_bwd(x, dy, dx, n, (hipStream_t)stream);
-}
-int dq_tfm_layernorm_fwd(const float* x, const float* r, const float* g, const float* b, float* y, float* out, float* stats, int rows, int H,
-                         void* stream) {
-  DQ_REQUIRE(x && g && b && y && out, "dq_tfm_layernorm_fwd: null argument");
-  DQ_REQUIRE(rows > 0 && H > 0, "dq_tfm_layernorm_fwd: rows and H must be positive");
-  return launch_layernorm_fwd(x, r, g, b, y, out, stats, rows, H, (hipStream_t)stream);
-}
-int dq_tfm_layernorm_bwd(const float* y, const float* stats, const float* g, const float* dout, float* dy, float* dg, float* db, float* scratch,
-                         int64_t scratch_floats, int rows, int H, int accumulate, void* stream) {
-  DQ_REQUIRE(y && stats && g && dout && dy && dg && db && scratch, "dq_tfm_layernorm_bwd: null argument");
-  DQ_REQUIRE(rows > 0 && H > 0, "dq_tfm_layernorm_bwd: rows and H must be positive");
-  DQ_REQUIRE(scratch_floats >= (int64_t)2 * H * LN_BWD_BLOCKS, "dq_tfm_layernorm_bwd: scratch needs 2 * H * 256 floats");
-  return launch_layernorm_bwd(y, stats, g, dout, dy, dg, db, scratch, rows, H, (hipStream_t)stream, accumulate ? 1 : 0);
-}
-int dq_tfm_softmax_rows(float* p, int64_t rows, int n, int ld, float scale, void* stream) {
-  DQ_REQUIRE(p, "dq_tfm_softmax_rows: null argument");
-  DQ_REQUIRE(rows > 0 && n > 0 && ld >= n, "dq_tfm_softmax_rows: rows, n positive, ld >= n");
-  return launch_softmax_rows(p, rows, n, ld, scale, (hipStream_t)stream);
-}
-int dq_tfm_softmax_rows_bwd(const float* p, float* dp, int64_t rows, int n, int ld, float scale, void* stream) {
-  DQ_REQUIRE(p && dp, "dq_tfm_softmax_rows_bwd: null argument");
-  DQ_REQUIRE(rows > 0 && n > 0 && ld >= n, "dq_tfm_softmax_rows_bwd: rows, n positive, ld >= n");
-  return launch_softmax_rows_bwd(p, dp, rows, n, ld, scale, (hipStream_t)stream);
-}
-int dq_tfm_colsum(const float* x, int M, int N, int64_t ld, float* out, float* scratch, int64_t scratch_floats, int accumulate, void* stream) {
-  DQ_REQUIRE(x && out && scratch, "dq_tfm_colsum: null argument");
-  DQ_REQUIRE(M > 0 && N > 0 && ld >= N, "dq_tfm_colsum: M, N positive, ld >= N");
-  DQ_REQUIRE(scratch_floats >= (int64_t)COLSUM_BLOCKS * N, "dq_tfm_colsum: scratch needs 64 * N floats");
-  return launch_colsum(x, M, N, ld, out, scratch, (hipStream_t)stream, accumulate ? 1 : 0);
-}
-int dq_tfm_seqsum(const float* x, int B, int S, int N, float* out, void* stream) {
-  DQ_REQUIRE(x && out, "dq_tfm_seqsum: null argument");
-  DQ_REQUIRE(B > 0 && S > 0 && N > 0, "dq_tfm_seqsum: B, S, N must be positive");
-  return launch_seqsum(x, B, S, N, out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 // Sampling from the CustomTransformer inside the library: dq_tfm_sample walks all timesteps -- a sampling forward of
 // the network and one update of dq_sampler.h per step, eagerly or as one captured step replayed -- and the stand-alone entry of the fused
 // inference attention (k_tfm_attn.hip).  What does not depend on the step is computed once per call, before the loop: the conditional
-// embedding cp of the MS1 chromatogram, every layer's K | V rows of it, and the time embedding of every step.  dq_tfm_fwd / dq_tfm_bwd
-// (dq_tfm.hip) are the training path and know nothing of this file.
+// embedding cp of the MS1 chromatogram, every layer's K | V rows of it, and the time embedding of every step.  The forward itself is the
+// one walk of the network (tfm_walk, dq_tfm.hip) that dq_tfm_fwd makes too, here with its K | V rows cached.
 // Held-out evaluation: dq_tfm_eval_step runs the same prologue and the same forward once over R repeats of a batch
 // stacked into R * B samples -- the conditional rows computed for the B windows and copied to the other repeats, the time table one row per
 // sample -- between the stacked noising head and the stacked per-window MSE of k_tfm_eval.hip.
@@ -26,7 +26,7 @@ struct SampleWs {
   Ws net;
   std::vector<float*> kv;  // per layer (B, Sk, 2H): rows [0, S2) the call's conditional K | V, rows [S2, Sk) the step's
   int64_t* t64;            // (num_steps) the timesteps as the time-feature kernel reads them
-  float *tfeat, *th, *tg, *ttab;  // time MLP over all steps: (ns, H), (ns, 4H), (ns, 4H), (ns, H)
+  TimeBufs time;           // time MLP over all steps: temb is the (num_steps, H) table
   float *xa, *xb, *eps, *coef, *sigma;
   int *ts_tab, *step;
   uint64_t* seed_stage;
@@ -36,20 +36,19 @@ struct SampleWs {
 
 SampleWs carve_sample(const dq_tfm& p, float* base, int B, int S1, int S2, int ns) {
   SampleWs w;
-  w.net = carve(p, base, B, S1, S2, false);
-  int64_t off = w.net.floats;
-  auto take = [&](int64_t n) { float* r = base ? base + off : nullptr; off += up4(n); return r; };
-  const int64_t H = p.H, Sk = S1 + S2, n = (int64_t)B * S1 * p.D;
-  for (int l = 0; l < p.layers; ++l) w.kv.push_back(take(B * Sk * 2 * H));
-  w.t64 = reinterpret_cast<int64_t*>(take(2 * (int64_t)ns));
-  w.tfeat = take(ns * H); w.th = take(ns * 4 * H); w.tg = take(ns * 4 * H); w.ttab = take(ns * H);
-  w.xa = take(n); w.xb = take(n); w.eps = take(n);
-  w.coef = take(4 * (int64_t)ns); w.sigma = take(ns);
-  w.ts_tab = reinterpret_cast<int*>(take(ns));
-  w.step = reinterpret_cast<int*>(take(4));
-  w.seed_stage = reinterpret_cast<uint64_t*>(take(4));
-  w.ids_stage = reinterpret_cast<int64_t*>(take(2 * (int64_t)B));
-  w.floats = off;
+  Carver c{base};
+  w.net = carve(p, c, B, S1, S2, false);
+  const int64_t H = p.H, n = (int64_t)B * S1 * p.D;
+  w.kv = carve_kv(p, c, B, S1 + S2);
+  w.t64 = c.take<int64_t>(ns);
+  w.time.tfeat = c.take(ns * H); w.time.th = c.take(ns * 4 * H); w.time.tg = c.take(ns * 4 * H); w.time.temb = c.take(ns * H);
+  w.xa = c.take(n); w.xb = c.take(n); w.eps = c.take(n);
+  w.coef = c.take(4 * (int64_t)ns); w.sigma = c.take(ns);
+  w.ts_tab = c.take<int>(ns);
+  w.step = c.take<int>(4);
+  w.seed_stage = c.take<uint64_t>(2);
+  w.ids_stage = c.take<int64_t>(B);
+  w.floats = c.off;
   return w;
 }
 
@@ -66,91 +65,40 @@ struct EvalWs {
 
 EvalWs carve_eval(const dq_tfm& p, float* base, int B, int S1, int S2, int R) {
   EvalWs w;
+  Carver c{base};
   const int N = R * B;
-  w.net = carve(p, base, N, S1, S2, false);
-  int64_t off = w.net.floats;
-  auto take = [&](int64_t n) { float* r = base ? base + off : nullptr; off += up4(n); return r; };
-  const int64_t H = p.H, Sk = S1 + S2, per = (int64_t)S1 * p.D;
-  for (int l = 0; l < p.layers; ++l) w.kv.push_back(take(N * Sk * 2 * H));
-  w.xt = take(N * per); w.out = take(N * per);
-  w.slices = reinterpret_cast<double*>(take(mse_per_window_scratch_bytes(N, per) / (int64_t)sizeof(float)));
-  w.floats = off;
+  const int64_t per = (int64_t)S1 * p.D;
+  w.net = carve(p, c, N, S1, S2, false);
+  w.kv = carve_kv(p, c, N, S1 + S2);
+  w.xt = c.take(N * per); w.out = c.take(N * per);
+  w.slices = c.take<double>(mse_per_window_scratch_bytes(N, per) / (int64_t)sizeof(double));
+  w.floats = c.off;
   return w;
 }
 
-// What one call's forwards share.  B samples go through the network; the conditional rows are computed for the first Bc of them and copied
-// to the rest (sampling: Bc == B; evaluation: B / Bc repeats of Bc windows).  The time table ttab has one row per step (sampling: the
-// forward adds the row it is told to every sample) or, with time_per_sample, one row per sample.
-struct SampleNet {
-  const dq_tfm* p; const float* P; const float* sin_t; const float* cos_t;
-  const Ws* net;       // the inference buffers of carve() at batch B
-  float* const* kv;    // per layer (B, Sk, 2H): rows [0, S2) the call's conditional K | V, rows [S2, Sk) the forward's
-  const int64_t* t64;  // the timesteps the time table is built from
-  float *tfeat, *th, *tg, *ttab;
-  int B, S1, S2, form;
-  int Bc;
-  bool time_per_sample;
-};
-
-// K | V rows of `rows` (batch, M, H) under layer l's projection into rows [row0, row0 + M) of kv_l's first `batch` samples: one product batched
-// over the samples (batch == 1: a plain product, which the launcher may split along the reduction)
-int kv_rows(const SampleNet& c, int l, const float* rows, int M, int row0, int batch, hipStream_t s) {
-  const int H = c.p->H, Sk = c.S1 + c.S2;
-  const TfmLayer& a = c.p->L[l];
-  Gemm g;
-  g.A = rows; g.lda = H; g.sAo = (int64_t)M * H;
-  g.B = c.P + a.in_w + (int64_t)H * H; g.ldb = H; g.bias = c.P + a.in_b + H;
-  g.C = c.kv[l] + (int64_t)row0 * 2 * H; g.ldc = 2 * H; g.sCo = (int64_t)Sk * 2 * H;
-  g.batch = batch; g.M = M; g.N = 2 * H; g.K = H;
-  g.partial = c.net->partial; g.partial_floats = TFM_PARTIAL_FLOATS;
-  return launch_gemm(g, s);
+// A call's forwards as the walk sees them: the cached form of K | V (the conditional rows of k.kv are the prologue's), every layer in buffer
+// set 0, no LayerNorm stats; time_per_sample says how the walk adds temb -- sampling: a (num_steps, H) table, the step's row to every
+// sample; evaluation: one row per stacked sample
+TfmWalk cached_walk(const dq_tfm* p, const float* P, const float* sin_t, const float* cos_t, const Ws& net, float* const* kv, const float* temb,
+                    bool time_per_sample, int B, int S1, int S2) {
+  TfmWalk k{p, P, sin_t, cos_t, &net, B, S1, S2};
+  k.kv = kv; k.attn_form = tfm_attn_form(S1, S1 + S2, p->H / p->heads); k.temb = temb; k.time_per_sample = time_per_sample;
+  return k;
 }
 
-// once per call, eagerly: cp = rope((cm x_cond + ca) w + b) of the Bc windows, every layer's K | V rows of it (copied to the other B / Bc - 1
-// repeats), the time embedding of the nt timesteps at t64
-int sample_prologue(const SampleNet& c, const float* ms1, float cm, float ca, const float* time_freqs, int nt, hipStream_t s) {
-  const dq_tfm& p = *c.p;
-  const Ws& n = *c.net;
-  const int H = p.H;
-  DQ_TRY(launch_cond_embed_affine(ms1, cm, ca, c.P + p.c_w, c.P + p.c_b, c.sin_t, c.cos_t, n.cp, c.Bc, c.S2, H, s));
+// once per call, eagerly: cp = rope((cm x_cond + ca) w + b) of the first Bc of the walk's B samples, every layer's K | V rows of it (copied to
+// the other B / Bc - 1 repeats; sampling: Bc == B), the time embedding of the nt timesteps at t64 into tb.temb (== k.temb)
+int sample_prologue(const TfmWalk& k, int Bc, const float* ms1, float cm, float ca, const float* time_freqs, const int64_t* t64, int nt,
+                    const TimeBufs& tb, hipStream_t s) {
+  const dq_tfm& p = *k.p;
+  const Ws& n = *k.w;
+  const int H = p.H, Sk = k.S1 + k.S2;
+  DQ_TRY(launch_cond_embed_affine(ms1, cm, ca, k.P + p.c_w, k.P + p.c_b, k.sin_t, k.cos_t, n.cp, Bc, k.S2, H, s));
   for (int l = 0; l < p.layers; ++l) {
-    DQ_TRY(kv_rows(c, l, n.cp, c.S2, 0, c.Bc, s));
-    DQ_TRY(launch_tfm_kv_broadcast(c.kv[l], c.Bc, c.B / c.Bc, c.S2, c.S1 + c.S2, H, s));  // (one repeat: no launch)
+    DQ_TRY(tfm_kv_rows(p, k.P, l, n.cp, k.S2, 0, Bc, k.kv[l], Sk, n.partial, s));
+    DQ_TRY(launch_tfm_kv_broadcast(k.kv[l], Bc, k.B / Bc, k.S2, Sk, H, s));  // (one repeat: no launch)
   }
-  // time embedding (building_blocks.py:92-112) with "batch" = the steps, or the stacked samples
-  DQ_TRY(launch_time_features(c.t64, time_freqs, c.tfeat, nt, H, s));
-  DQ_TRY(tfm_linear(c.tfeat, c.P + p.t1_w, c.P + p.t1_b, c.th, nt, 4 * H, H, n.partial, s));
-  DQ_TRY(launch_gelu(c.th, c.tg, (int64_t)nt * 4 * H, s));
-  DQ_TRY(tfm_linear(c.tg, c.P + p.t2_w, c.P + p.t2_b, c.ttab, nt, H, 4 * H, n.partial, s));
-  return 0;
-}
-
-// the network output from x (B, S1, D): time row `row`, or the one the device-side counter names; with time_per_sample each sample's own
-int sample_forward(const SampleNet& c, const float* x_in, int row, const int* step_ptr, float* out, hipStream_t s) {
-  const dq_tfm& p = *c.p;
-  const Ws& n = *c.net;
-  const Ws::Layer& b = n.L[0];
-  const int H = p.H, D = p.D, R1 = c.B * c.S1, Sk = c.S1 + c.S2;
-  const float* P = c.P;
-  DQ_TRY(tfm_linear(x_in, P + p.in_w, P + p.in_b, n.x0, R1, H, D, n.partial, s));
-  if (c.time_per_sample) DQ_TRY(launch_rope_add(n.x0, c.sin_t, c.cos_t, c.ttab, c.B, c.S1, H, 0, s));
-  else DQ_TRY(launch_rope_add_row(n.x0, c.sin_t, c.cos_t, c.ttab, row, step_ptr, c.B, c.S1, H, s));
-  const AttnDims ad{c.B, c.S1, Sk, H, p.heads, H / p.heads, up4(Sk)};
-  const float* x = n.x0;
-  for (int l = 0; l < p.layers; ++l) {
-    const TfmLayer& a = p.L[l];
-    DQ_TRY(tfm_linear(x, P + a.in_w, P + a.in_b, b.q, R1, H, H, n.partial, s));
-    DQ_TRY(kv_rows(c, l, x, c.S1, c.S2, c.B, s));
-    DQ_TRY(tfm_attention_fwd(c.form, ad, b.q, c.kv[l], b.prob, b.ao, n.partial, s));
-    DQ_TRY(tfm_linear(b.ao, P + a.out_w, P + a.out_b, n.tmp, R1, H, H, n.partial, s));
-    DQ_TRY(launch_layernorm_fwd(x, n.tmp, P + a.n1_g, P + a.n1_b, b.y1, b.x1, nullptr, R1, H, s));
-    DQ_TRY(tfm_linear(b.x1, P + a.f0_w, P + a.f0_b, b.hpre, R1, 4 * H, H, n.partial, s));
-    DQ_TRY(launch_gelu(b.hpre, b.hact, (int64_t)R1 * 4 * H, s));
-    DQ_TRY(tfm_linear(b.hact, P + a.f2_w, P + a.f2_b, n.tmp, R1, H, 4 * H, n.partial, s));
-    DQ_TRY(launch_layernorm_fwd(b.x1, n.tmp, P + a.n2_g, P + a.n2_b, b.y2, b.xo, nullptr, R1, H, s));
-    x = b.xo;
-  }
-  return tfm_linear(x, P + p.out_w, P + p.out_b, out, R1, D, H, n.partial, s);
+  return tfm_time_mlp(p, k.P, t64, time_freqs, tb, nt, n.partial, s);  // "batch" = the steps, or the stacked samples
 }
 
 }  // namespace
@@ -202,8 +150,7 @@ int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const f
   const int64_t per = (int64_t)S1 * p->D, n = B * per;
   const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
   const int32_t* ts = timesteps_host;
-  const SampleNet net{p, params, rope_sin, rope_cos, &w.net, w.kv.data(), w.t64, w.tfeat, w.th, w.tg, w.ttab, B, S1, S2,
-                      tfm_attn_form(S1, S1 + S2, p->H / p->heads), B, false};
+  const TfmWalk net = cached_walk(p, params, rope_sin, rope_cos, w.net, w.kv.data(), w.time.temb, false, B, S1, S2);
   // the steps' timesteps for the time table (the copy is done when the table upload below returns: it synchronises the stream)
   std::vector<int64_t> t64((size_t)num_steps);
   for (int i = 0; i < num_steps; ++i) t64[i] = ts[i];
@@ -213,13 +160,15 @@ int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const f
   else DQ_TRY(launch_randn(w.xa, window_ids_dev, seed_dev, 0, B, per, s));  // draw index 0 is x_T's
   const StepForward forward = [&](const float* x, float*, int row, const int* step_ptr, float* net_out, bool, bool* fused, hipStream_t fs) {
     *fused = false;  // (the update is never in this network's launches)
-    return sample_forward(net, x, row, step_ptr, net_out, fs);
+    TfmWalk step = net;
+    step.time_row = row; step.step_ptr = step_ptr;
+    return tfm_walk(step, x, net_out, fs);
   };
   const SampleLoop loop{forward, StepUpdateArgs{sc.kind, w.coef, w.sigma, w.xb, sc.clip_x0, sc.px0, B, per}, w.xa, w.eps, sc.clip,
                         num_steps, ms2_cond, out_x, out_noise, auto_normalize};
-  if (net.form == TFM_ATTN_FUSED) DQ_TRY(tfm_attn_prepare());  // (the LDS limit of this device, before any capture)
+  if (net.attn_form == TFM_ATTN_FUSED) DQ_TRY(tfm_attn_prepare());  // (the LDS limit of this device, before any capture)
   // every call, outside any capture: a changed MS1, or changed weights behind the same pointer, cannot meet a stale cache
-  DQ_TRY(sample_prologue(net, ms1_cond, cm, ca, time_freqs, num_steps, s));
+  DQ_TRY(sample_prologue(net, B, ms1_cond, cm, ca, time_freqs, w.t64, num_steps, w.time, s));
   if (use_graph && !traj_x && !traj_eps) {
     // ---- one step captured once (every pointer inside the workspace / parameter buffers), replayed per step.  The step index lives on the
     // device: the time row and the update's coefficient row are read at *step, k_inc_step bumps it.  A linear graph: one stream, no branches.
@@ -272,14 +221,13 @@ int dq_tfm_eval_step(dq_tfm* p, const float* params, const float* rope_sin, cons
   const int64_t per = (int64_t)S1 * p->D;
   const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
   // the time table: one row per stacked sample, in carve()'s time buffers (batch N); t is read where it lies
-  const SampleNet net{p, params, rope_sin, rope_cos, &w.net, w.kv.data(), t, w.net.tfeat, w.net.th, w.net.tg, w.net.temb, N, S1, S2,
-                      tfm_attn_form(S1, S1 + S2, p->H / p->heads), B, true};
+  const TfmWalk net = cached_walk(p, params, rope_sin, rope_cos, w.net, w.kv.data(), w.net.time.temb, true, N, S1, S2);
   float* out = net_out ? net_out : w.out;
-  if (net.form == TFM_ATTN_FUSED) DQ_TRY(tfm_attn_prepare());
+  if (net.attn_form == TFM_ATTN_FUSED) DQ_TRY(tfm_attn_prepare());
   DQ_TRY(launch_q_sample_repeats(alpha_bars_dev, x0, t, noise, window_ids_dev, seed_dev, first_draw, w.xt, B, R, per, auto_normalize, s));
   // every call, eagerly: nothing of it outlives the call, so a changed MS1 or changed weights behind the same pointer meet no stale state
-  DQ_TRY(sample_prologue(net, ms1_cond, cm, ca, time_freqs, N, s));
-  DQ_TRY(sample_forward(net, w.xt, 0, nullptr, out, s));
+  DQ_TRY(sample_prologue(net, B, ms1_cond, cm, ca, time_freqs, t, N, w.net.time, s));
+  DQ_TRY(tfm_walk(net, w.xt, out, s));
   const bool px0 = pred_type == DQ_PRED_X0;  // the target: the normalised x0 shared by the repeats, or the noise (read, or drawn again)
   return launch_mse_per_window_repeats(out, px0 ? x0 : noise, px0 ? B : N, px0 ? cm : 1.f, px0 ? ca : 0.f, window_ids_dev, seed_dev, first_draw,
                                        px0 ? loss_weight_dev : nullptr, t, per_window_out, loss_out, w.slices,

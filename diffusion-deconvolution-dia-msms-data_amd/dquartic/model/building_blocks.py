@@ -64,10 +64,7 @@ class CustomTransformer(_FlatBuffers, nn.Module):
             _attach(self, pname, p)
         self._reset_parameters()
         self.precision = "fp32"
-        self._ws = {}
-        self._sample_ws = {}
-        self._eval_ws = {}
-        self._ws_pool = {}  # training workspaces of the autograd bridge: one per forward that still awaits its backward
+        self._init_workspaces()
         self._tables = {}
 
     @torch.no_grad()
@@ -107,49 +104,26 @@ class CustomTransformer(_FlatBuffers, nn.Module):
     def flat_params(self) -> torch.Tensor:
         return self._flat_buffer()
 
+    _WS_FAIL = "dq_tfm_workspace_bytes failed"
+
+    def _workspace_bytes(self, B, S1, S2, training):
+        return N.lib().dq_tfm_workspace_bytes(self._tfm, B, S1, S2, 1 if training else 0)
+
     def workspace(self, B, S1, S2, training):
-        dev = self._flat.device
-        key = (B, S1, S2, bool(training), str(dev))
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = N.lib().dq_tfm_workspace_bytes(self._tfm, B, S1, S2, 1 if training else 0)
-            if nbytes <= 0:
-                raise RuntimeError("dq_tfm_workspace_bytes failed")
-            self._ws = {k: v for k, v in self._ws.items() if k[3] != bool(training)}
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self._ws[key] = ws
-        return ws
+        return self._cached_workspace("train" if training else "infer", (B, S1, S2), lambda: self._workspace_bytes(B, S1, S2, training),
+                                      self._WS_FAIL)
 
     def sample_workspace(self, B, S1, S2, num_steps):
-        """The workspace of ``dq_tfm_sample`` for this shape and step count (``dq_tfm_sample_workspace_bytes``), cached like
-        ``workspace()``: one at a time."""
-        dev = self._flat.device
-        key = (B, S1, S2, int(num_steps), str(dev))
-        ws = self._sample_ws.get(key)
-        if ws is None:
-            nbytes = N.lib().dq_tfm_sample_workspace_bytes(self._tfm, B, S1, S2, int(num_steps))
-            if nbytes <= 0:
-                raise RuntimeError("dq_tfm_sample_workspace_bytes failed (need B, S1, S2 > 0 and 1 <= num_steps <= 1024)")
-            self._sample_ws = {}
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self._sample_ws[key] = ws
-        return ws
+        """The workspace of ``dq_tfm_sample`` for this shape and step count, cached like ``workspace()``: one at a time."""
+        return self._cached_workspace("sample", (B, S1, S2, int(num_steps)),
+                                      lambda: N.lib().dq_tfm_sample_workspace_bytes(self._tfm, B, S1, S2, int(num_steps)),
+                                      "dq_tfm_sample_workspace_bytes failed (need B, S1, S2 > 0 and 1 <= num_steps <= 1024)")
 
     def eval_workspace(self, B, S1, S2, repeats):
-        """The workspace of ``dq_tfm_eval_step`` for this shape and repeat count (``dq_tfm_eval_workspace_bytes``), cached like
-        ``sample_workspace()``: one at a time.  It lives where the parameters live now (the flat buffer is re-established first: after
-        ``.cuda()`` the old one is still on the host until the first call that reads it)."""
-        dev = self._flat_buffer().device
-        key = (B, S1, S2, int(repeats), str(dev))
-        ws = self._eval_ws.get(key)
-        if ws is None:
-            nbytes = N.lib().dq_tfm_eval_workspace_bytes(self._tfm, B, S1, S2, int(repeats))
-            if nbytes <= 0:
-                raise RuntimeError("dq_tfm_eval_workspace_bytes failed (need B, S1, S2 > 0, repeats >= 1 and repeats * B <= 65535)")
-            self._eval_ws = {}
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self._eval_ws[key] = ws
-        return ws
+        """The workspace of ``dq_tfm_eval_step`` for this shape and repeat count, cached like ``workspace()``: one at a time."""
+        return self._cached_workspace("eval", (B, S1, S2, int(repeats)),
+                                      lambda: N.lib().dq_tfm_eval_workspace_bytes(self._tfm, B, S1, S2, int(repeats)),
+                                      "dq_tfm_eval_workspace_bytes failed (need B, S1, S2 > 0, repeats >= 1 and repeats * B <= 65535)")
 
     def set_precision(self, precision: str):
         """Arithmetic of the dense products: "fp32" (default; exact fp32 on the matrix cores -- the precision parity is stated in) or
@@ -160,25 +134,6 @@ class CustomTransformer(_FlatBuffers, nn.Module):
         N.check(N.lib().dq_tfm_set_precision(self._tfm, N.PRECISIONS[precision]), "dq_tfm_set_precision")
         self.precision = precision
         return self
-
-    def checkout_train_workspace(self, B, S1, S2):
-        """A training workspace owned by ONE forward of the autograd bridge until its backward returns it (see UNet1d)."""
-        dev = self._flat.device
-        key = (B, S1, S2, str(dev))
-        pool = self._ws_pool.get(key)
-        if pool:
-            return pool.pop()
-        nbytes = N.lib().dq_tfm_workspace_bytes(self._tfm, B, S1, S2, 1)
-        if nbytes <= 0:
-            raise RuntimeError("dq_tfm_workspace_bytes failed")
-        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
-
-    def return_train_workspace(self, B, S1, S2, ws):
-        key = (B, S1, S2, str(ws.device))
-        self._ws_pool = {k: v for k, v in self._ws_pool.items() if k == key}
-        pool = self._ws_pool.setdefault(key, [])
-        if len(pool) < 2:
-            pool.append(ws)
 
     def tables(self, S, device):
         key = (S, str(device))

@@ -55,6 +55,10 @@ def identity(t, *args, **kwargs):  # model.py:115-125
     return t
 
 
+def _f32(v):
+    return v.detach().to(torch.float32).contiguous()
+
+
 def extract(a, t, x_shape):  # model.py:131-148
     b, *_ = t.shape
     out = a.gather(-1, t)
@@ -313,19 +317,45 @@ class DDIMDiffusionModel(ModelInterface):
             pred_noise = self.unnormalize(ms2n) - x_t
         return x_t, pred_noise
 
-    # what the two native loops stage alike
+    # what the native calls stage alike
+    def _stage_step(self, x_0, t, noise, draw_noise=True):
+        """A step's batch as the library reads it: ``(x_0, t, noise, alpha_bars, loss_weight)``, contiguous fp32 / int64 on ``x_0``'s device.
+        What was not passed is drawn in the reference's order: ``randint`` for ``t`` first, then ``randn_like`` for the noise (not with
+        ``draw_noise=False``: the noise stays None)."""
+        x_0 = _f32(x_0)
+        dev = x_0.device
+        if t is None:
+            t = torch.randint(0, self.num_timesteps, (x_0.shape[0],), device=dev).long()
+        if noise is None and draw_noise:
+            noise = torch.randn_like(x_0)
+        return (x_0, t.to(device=dev, dtype=torch.int64).contiguous(), None if noise is None else _f32(noise), self.alpha_bars.to(dev),
+                self.loss_weight.to(device=dev, dtype=torch.float32).contiguous())
+
+    @staticmethod
+    def _stage_tfm(tfm, ms1_cond, who, what, *shapes):
+        """The transformer's inputs: every shape of ``shapes`` (``what`` in the refusal) must be the same (batch, seqlen1, input_dim);
+        ``ms1_cond`` (B, S2) or (B, S2, 1) comes back as contiguous fp32 (B, S2).  Returns ``(c1, B, S1, S2, D)``."""
+        c1 = _f32(ms1_cond)
+        if c1.dim() == 3:
+            c1 = c1[..., 0].contiguous()
+        if len(shapes[0]) != 3 or shapes[0][-1] != tfm.input_dim or any(tuple(v) != tuple(shapes[0]) for v in shapes):
+            raise ValueError(f"{who}: {what} must be (batch, seqlen1, input_dim={tfm.input_dim})")
+        B, S1, D = shapes[0]
+        if c1.dim() != 2 or c1.shape[0] != B:
+            raise ValueError(f"{who}: ms1_cond must be (batch, seqlen2) or (batch, seqlen2, 1)")
+        return c1, B, S1, c1.shape[1], D
+
     @staticmethod
     def _stage_x(x_T, ms2_cond, eta, seed, shape):
         """(x_T or None, ms2_cond) as contiguous fp32 and the call's (batch, rows, width): x_T's, else ``shape`` or ``ms2_cond``'s."""
-        f32 = lambda v: v.detach().to(torch.float32).contiguous()
         if x_T is None:
             if seed is None and not eta:
                 raise ValueError("sample: x_t=None needs a seed (x_T is drawn from it)")
             B, S, D = tuple(shape) if shape is not None else tuple(ms2_cond.shape)
         else:
             B, S, D = x_T.shape
-            x_T = f32(x_T)
-        return x_T, f32(ms2_cond), B, S, D
+            x_T = _f32(x_T)
+        return x_T, _f32(ms2_cond), B, S, D
 
     def _stage_noise(self, x_T, eta, seed, window_ids, B, device):
         """The seed and window-id tensors of a call (None where the loop reads none); records ``last_seed``."""
@@ -378,14 +408,7 @@ class DDIMDiffusionModel(ModelInterface):
         its conditional sequence; ``ms2_cond`` only enters ``mixture - denoised``)."""
         tfm = self.model.transformer
         x_T, c2, B, S1, D = self._stage_x(x_T, ms2_cond, eta, seed, shape)
-        c1 = ms1_cond.detach().to(torch.float32).contiguous()
-        if c1.dim() == 3:
-            c1 = c1[..., 0].contiguous()
-        if D != tfm.input_dim or tuple(c2.shape) != (B, S1, D):
-            raise ValueError(f"sample: x_t and ms2_cond must be (batch, seqlen1, input_dim={tfm.input_dim})")
-        if c1.dim() != 2 or c1.shape[0] != B:
-            raise ValueError("sample: ms1_cond must be (batch, seqlen2) or (batch, seqlen2, 1)")
-        S2 = c1.shape[1]
+        c1, _, _, S2, _ = self._stage_tfm(tfm, ms1_cond, "sample", "x_t and ms2_cond", (B, S1, D), c2.shape)
         flat = tfm.read_params(False)  # (the averaged weights inside ModelInterface.ema_scope())
         ws = tfm.sample_workspace(B, S1, S2, num_steps)
         sin, cos, freqs = tfm.tables(max(S1, S2), c2.device)
@@ -444,23 +467,15 @@ class DDIMDiffusionModel(ModelInterface):
         net: UNet1d = self.model
         if not self.native:
             raise RuntimeError("train_step_fused needs this package's UNet1d or a DDIMTransformerAdapter")
-        f32 = lambda v: v.detach().to(torch.float32).contiguous()
         B, RT, MZ = x_0.shape
         if float(ms1_loss_weight or 0.0) > 0.0 and net.attn_cond_channels > 1:
             raise NotImplementedError(_MS1_TERM_MULTI)
-        x_0, c2, c1 = f32(x_0), f32(ms2_cond), f32(net._check_inputs(ms1_cond, B, RT))
-        if t is None:
-            t = torch.randint(0, self.num_timesteps, (B,), device=x_0.device).long()
-        if noise is None:
-            noise = torch.randn_like(x_0)
-        t = t.to(device=x_0.device, dtype=torch.int64).contiguous()
-        noise = f32(noise)
+        c2, c1 = _f32(ms2_cond), _f32(net._check_inputs(ms1_cond, B, RT))
+        x_0, t, noise, ab, lw = self._stage_step(x_0, t, noise)
         flat = net.read_params(training=True)  # (raises inside ema_scope(): the average is not trained)
         grads = net.flat_grads(zero=zero_grads)
         ws = net.workspace(B, RT, True)
         loss = torch.empty((), dtype=torch.float32, device=x_0.device)
-        ab = self.alpha_bars.to(x_0.device)
-        lw = self.loss_weight.to(device=x_0.device, dtype=torch.float32).contiguous()
         N.check(N.lib().dq_train_step(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), N.ptr(ab), N.ptr(x_0), N.ptr(c2), N.ptr(c1),
                                       N.ptr(t), N.ptr(noise), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], N.ptr(lw),
                                       float(ms1_loss_weight or 0.0), N.ptr(grads), N.ptr(loss), N.ptr(ws), ws.numel(), B, RT,
@@ -478,11 +493,7 @@ class DDIMDiffusionModel(ModelInterface):
         ``DDIMTransformerAdapter`` (``dq_tfm_eval_step`` at one repeat; ``ms1_cond`` (B, RT) or (B, RT, 1),
         ``ms2_cond`` unused: that network has no input for it)."""
         if self._native_tfm:
-            B = x_0.shape[0]
-            if t is None:
-                t = torch.randint(0, self.num_timesteps, (B,), device=x_0.device).long()
-            if noise is None:
-                noise = torch.randn_like(x_0)
+            x_0, t, noise, _, _ = self._stage_step(x_0, t, noise)
             loss, per_window = self._eval_steps_tfm(x_0, ms1_cond, t.reshape(1, -1), noise=noise)
             return loss[0], per_window[0]
         net: UNet1d = self.model
@@ -491,21 +502,13 @@ class DDIMDiffusionModel(ModelInterface):
                                       f"DDIMTransformerAdapter); the network is {type(self.model).__name__}")
         if self.pred_type not in N.PRED_TYPES:
             raise ValueError(f"Unknown pred_type: {self.pred_type}")
-        f32 = lambda v: v.detach().to(torch.float32).contiguous()
         B, RT, MZ = x_0.shape
-        x_0, c2, c1 = f32(x_0), f32(ms2_cond), f32(net._check_inputs(ms1_cond, B, RT))
-        if t is None:
-            t = torch.randint(0, self.num_timesteps, (B,), device=x_0.device).long()
-        if noise is None:
-            noise = torch.randn_like(x_0)
-        t = t.to(device=x_0.device, dtype=torch.int64).contiguous()
-        noise = f32(noise)
+        c2, c1 = _f32(ms2_cond), _f32(net._check_inputs(ms1_cond, B, RT))
+        x_0, t, noise, ab, lw = self._stage_step(x_0, t, noise)
         flat = net.read_params()  # (the averaged weights inside ModelInterface.ema_scope())
         ws = net.workspace(B, RT, False)
         loss = torch.empty((), dtype=torch.float32, device=x_0.device)
         per_window = torch.empty(B, dtype=torch.float32, device=x_0.device)
-        ab = self.alpha_bars.to(x_0.device)
-        lw = self.loss_weight.to(device=x_0.device, dtype=torch.float32).contiguous()
         N.check(N.lib().dq_eval_step(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), N.ptr(ab), N.ptr(x_0), N.ptr(c2), N.ptr(c1), N.ptr(t),
                                      N.ptr(noise), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], N.ptr(lw), N.ptr(loss),
                                      N.ptr(per_window), N.ptr(ws), ws.numel(), B, RT, N.stream_ptr()), "dq_eval_step")
@@ -543,23 +546,12 @@ class DDIMDiffusionModel(ModelInterface):
         tfm = self.model.transformer
         if not x_0.is_cuda:
             raise RuntimeError("CustomTransformer (MI355X build): tensors must live on the GPU; there is no CPU fallback")
-        f32 = lambda v: v.detach().to(torch.float32).contiguous()
-        x_0, c1 = f32(x_0), f32(ms1_cond)
-        if c1.dim() == 3:
-            c1 = c1[..., 0].contiguous()
-        if x_0.dim() != 3 or x_0.shape[-1] != tfm.input_dim:
-            raise ValueError(f"eval_step: x_0 must be (batch, seqlen1, input_dim={tfm.input_dim})")
-        B, S1, _ = x_0.shape
-        if c1.dim() != 2 or c1.shape[0] != B:
-            raise ValueError("eval_step: ms1_cond must be (batch, seqlen2) or (batch, seqlen2, 1)")
-        S2 = c1.shape[1]
-        dev = x_0.device
-        t = t.to(device=dev, dtype=torch.int64).contiguous()
-        R = t.shape[0]
+        c1, B, S1, S2, _ = self._stage_tfm(tfm, ms1_cond, "eval_step", "x_0", x_0.shape)
         if t.dim() != 2 or t.shape[1] != B:
             raise ValueError(f"eval_step: t must be (repeats, batch = {B}), got {tuple(t.shape)}")
+        x_0, t, noise, ab, lw = self._stage_step(x_0, t, noise, draw_noise=False)
+        dev, R = x_0.device, t.shape[0]
         if noise is not None:
-            noise = f32(noise)
             if noise.numel() != R * x_0.numel():
                 raise ValueError("eval_step: noise must have the shape of x_0 per repeat")
         elif seed_dev is None:
@@ -569,8 +561,6 @@ class DDIMDiffusionModel(ModelInterface):
         sin, cos, freqs = tfm.tables(max(S1, S2), dev)
         loss = torch.empty(R, dtype=torch.float32, device=dev)
         per_window = torch.empty(R, B, dtype=torch.float32, device=dev)
-        ab = self.alpha_bars.to(dev)
-        lw = self.loss_weight.to(device=dev, dtype=torch.float32).contiguous()
         N.check(N.lib().dq_tfm_eval_step(tfm._tfm, N.ptr(flat), N.ptr(sin), N.ptr(cos), N.ptr(freqs), N.ptr(ab), N.ptr(x_0), N.ptr(c1), N.ptr(t),
                                          N.ptr(noise), N.ptr(seed_dev), N.ptr(window_ids_dev), int(first_draw), 1 if self.auto_normalize else 0,
                                          N.PRED_TYPES[self.pred_type], N.ptr(lw), N.ptr(loss), N.ptr(per_window), None, N.ptr(ws), ws.numel(),
@@ -582,23 +572,13 @@ class DDIMDiffusionModel(ModelInterface):
         q_sample, network forward, MSE and its gradient, network backward into the flat gradient buffer), each stage one native
         call -- dq_q_sample, dq_tfm_fwd, dq_mse_loss(_weighted)_fwd_bwd, dq_tfm_bwd -- issued back to back on the current stream."""
         tfm = self.model.transformer
-        f32 = lambda v: v.detach().to(torch.float32).contiguous()
-        x_0, c1 = f32(x_0), f32(ms1_cond)
-        if c1.dim() == 3:
-            c1 = c1[..., 0].contiguous()
-        B = x_0.shape[0]
-        per = x_0[0].numel()
-        dev = x_0.device
-        if t is None:
-            t = torch.randint(0, self.num_timesteps, (B,), device=dev).long()
-        if noise is None:
-            noise = torch.randn_like(x_0)
-        t = t.to(device=dev, dtype=torch.int64).contiguous()
-        noise = f32(noise)
+        c1, B, _, _, _ = self._stage_tfm(tfm, ms1_cond, "train_step_fused", "x_0", x_0.shape)
+        x_0, t, noise, ab, lw = self._stage_step(x_0, t, noise)
+        per, dev = x_0[0].numel(), x_0.device
         norm = 1 if self.auto_normalize else 0
         lib = N.lib()
         x_t = torch.empty_like(x_0)
-        N.check(lib.dq_q_sample(N.ptr(self.alpha_bars.to(dev)), N.ptr(x_0), N.ptr(t), N.ptr(noise), N.ptr(x_t), B, per, norm, N.stream_ptr()),
+        N.check(lib.dq_q_sample(N.ptr(ab), N.ptr(x_0), N.ptr(t), N.ptr(noise), N.ptr(x_t), B, per, norm, N.stream_ptr()),
                 "dq_q_sample")
         c1n = self.normalize(c1).contiguous()  # (B, RT) values: the only torch op of the step
         tfm._ensure_flat()
@@ -612,15 +592,13 @@ class DDIMDiffusionModel(ModelInterface):
             N.check(lib.dq_mse_loss_fwd_bwd(N.ptr(out), N.ptr(noise), N.ptr(loss), N.ptr(dout), N.ptr(self._mse_scratch), out.numel(),
                                             N.stream_ptr()), "dq_mse_loss_fwd_bwd")
         else:
-            lw = self.loss_weight.to(device=dev, dtype=torch.float32).contiguous()
             N.check(lib.dq_mse_loss_weighted_fwd_bwd(N.ptr(out), N.ptr(x_0), 2.0 if norm else 1.0, -1.0 if norm else 0.0, N.ptr(lw), N.ptr(t),
                                                      N.ptr(loss), N.ptr(dout), N.ptr(self._mse_scratch), B, per, N.stream_ptr()),
                     "dq_mse_loss_weighted_fwd_bwd")
         if ms1_loss_weight > 0.0:  # the MS1 term on top of the MSE part (same kernels as the U-Net's train step)
             B_, RT_, MZ_ = x_0.shape
             sc = torch.empty(5 * B_ * RT_ + B_ + 64, dtype=torch.float32, device=dev)
-            lw_x0 = self.loss_weight.to(device=dev, dtype=torch.float32).contiguous() if self.pred_type == "x0" else None  # (kept alive past the call)
-            lwp = N.ptr(lw_x0)
+            lwp = N.ptr(lw) if self.pred_type == "x0" else None
             N.check(lib.dq_ms1_loss_fwd_bwd(N.ptr(out), N.ptr(x_t) if self.pred_type == "eps" else None, N.ptr(c1), 2.0 if norm else 1.0,
                                             -1.0 if norm else 0.0, lwp, N.ptr(t), float(ms1_loss_weight), N.ptr(loss), N.ptr(dout), N.ptr(sc),
                                             B_, RT_, MZ_, N.stream_ptr()), "dq_ms1_loss_fwd_bwd")

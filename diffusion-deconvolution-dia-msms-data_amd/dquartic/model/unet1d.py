@@ -125,8 +125,56 @@ class _FlatBuffers:
             self._grad_stale = False
         return self._flat_grad
 
+    # ---- workspaces of the native calls.  They live where the parameters live NOW: the flat buffer is re-established first (after
+    # ``.cuda()`` the old one is still on the host until the first call that reads it, and a workspace sized from it would be host memory
+    # handed to kernels).
+    def _init_workspaces(self):
+        self._ws_cache = {}  # kind ("infer", "train", "sample", "eval") -> (key, buffer): one buffer per kind
+        self._ws_pool = {}   # training workspaces of the autograd bridge: one per forward that still awaits its backward
+
+    def _alloc_workspace(self, nbytes: int, fail: str, evict: Optional[str] = None) -> torch.Tensor:
+        if nbytes <= 0:
+            raise RuntimeError(fail)
+        self._ws_cache.pop(evict, None)  # (before the allocation: the old and the new buffer need not fit side by side)
+        return torch.empty(nbytes, dtype=torch.uint8, device=self._flat_buffer().device)
+
+    def _cached_workspace(self, kind: str, shape, nbytes, fail: str) -> torch.Tensor:
+        """The one workspace of ``kind``: the identical buffer while ``shape`` (and the device) stays, else the old one is dropped and
+        ``nbytes()`` bytes are allocated; a size query that fails raises ``fail``."""
+        key = (*shape, str(self._flat_buffer().device))
+        hit = self._ws_cache.get(kind)
+        if hit is None or hit[0] != key:
+            hit = self._ws_cache[kind] = (key, self._alloc_workspace(nbytes(), fail, evict=kind))
+        return hit[1]
+
+    def cached_workspaces(self):
+        """{kind: buffer} of the workspaces held now."""
+        return {kind: ws for kind, (_, ws) in self._ws_cache.items()}
+
+    def drop_workspaces(self):
+        self._init_workspaces()
+
+    def checkout_train_workspace(self, *shape) -> torch.Tensor:
+        """A training workspace (saved activations + gradient scratch) owned by ONE forward of the autograd bridge until its backward
+        hands it back: two forwards with grad enabled before a backward (micro-batches whose losses are summed, a consistency term) each
+        keep their own saved activations instead of overwriting a shared buffer."""
+        pool = self._ws_pool.get((*shape, str(self._flat_buffer().device)))
+        if pool:
+            return pool.pop()
+        return self._alloc_workspace(self._workspace_bytes(*shape, True), self._WS_FAIL)
+
+    def return_train_workspace(self, *shape_ws):
+        *shape, ws = shape_ws
+        key = (*shape, str(ws.device))
+        self._ws_pool = {k: v for k, v in self._ws_pool.items() if k == key}  # keep buffers of the current shape only
+        pool = self._ws_pool.setdefault(key, [])
+        if len(pool) < 2:
+            pool.append(ws)
+
 
 class UNet1d(_FlatBuffers, nn.Module):
+    _WS_FAIL = "dq_unet_workspace_bytes failed"
+
     def __init__(
         self,
         dim,
@@ -216,8 +264,7 @@ class UNet1d(_FlatBuffers, nn.Module):
         self._reset_parameters()
         # (no parameters: state_dict keys, order and the seeded initialisation are those of either reference variant)
         self.final_act = nn.Softplus() if self.pos_output_only else nn.Identity()
-        self._ws = {}
-        self._ws_pool = {}  # training workspaces of the autograd bridge: one per forward that still awaits its backward
+        self._init_workspaces()
         self.use_rope = True
 
     # ------------------------------------------------------------------ initialisation
@@ -266,39 +313,11 @@ class UNet1d(_FlatBuffers, nn.Module):
             return None
         return self.mid_attn.fn.fn.rotary_emb.freqs
 
+    def _workspace_bytes(self, B: int, RT: int, training: bool) -> int:
+        return N.lib().dq_unet_workspace_bytes(self._plan, B, RT, 1 if training else 0)
+
     def workspace(self, B: int, RT: int, training: bool) -> torch.Tensor:
-        dev = self._flat.device
-        key = (B, RT, bool(training), str(dev))
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = N.lib().dq_unet_workspace_bytes(self._plan, B, RT, 1 if training else 0)
-            if nbytes < 0:
-                raise RuntimeError("dq_unet_workspace_bytes failed")
-            self._ws = {k: v for k, v in self._ws.items() if k[2] != bool(training)}  # keep one per mode
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self._ws[key] = ws
-        return ws
-
-    def checkout_train_workspace(self, B: int, RT: int) -> torch.Tensor:
-        """A training workspace (activation arena + gradient twin) owned by ONE forward of the autograd bridge until its
-        backward hands it back: two forwards with grad enabled before a backward (micro-batches whose losses are summed, a
-        consistency term) each keep their own saved activations instead of overwriting a shared buffer."""
-        dev = self._flat.device
-        key = (B, RT, str(dev))
-        pool = self._ws_pool.get(key)
-        if pool:
-            return pool.pop()
-        nbytes = N.lib().dq_unet_workspace_bytes(self._plan, B, RT, 1)
-        if nbytes < 0:
-            raise RuntimeError("dq_unet_workspace_bytes failed")
-        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
-
-    def return_train_workspace(self, B: int, RT: int, ws: torch.Tensor):
-        key = (B, RT, str(ws.device))
-        self._ws_pool = {k: v for k, v in self._ws_pool.items() if k == key}  # keep buffers of the current shape only
-        pool = self._ws_pool.setdefault(key, [])
-        if len(pool) < 2:
-            pool.append(ws)
+        return self._cached_workspace("train" if training else "infer", (B, RT), lambda: self._workspace_bytes(B, RT, training), self._WS_FAIL)
 
     def __del__(self):
         try:

@@ -195,7 +195,7 @@ def test_eval_step_needs_no_optimizer_and_sets_no_grad(N):
     dm.eval_step(x0, c2, c1, t=t, noise=nz)
     assert dm.optimizer is None
     assert all(p.grad is None for p in dm.model.parameters())
-    assert not any(k[2] for k in dm.model._ws)  # the inference workspace only
+    assert list(dm.model.cached_workspaces()) == ["infer"]  # the inference workspace only
 
 
 def test_a_window_does_not_depend_on_its_batch(N):

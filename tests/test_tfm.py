@@ -204,6 +204,26 @@ def test_hip_matches_oracle_at_larger_shapes(D, H, heads, layers, B, S1, S2):
         assert torch.equal(net(x.cuda(), t.cuda(), c.cuda()), y.detach())
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("S1,S2", [(5, 3), (1, 1)])
+def test_saving_and_plain_forward_are_the_same_bits(S1, S2):
+    """dq_tfm_fwd with save_for_bwd = 1 and = 0 is one walk with one flag (a buffer set per layer, or one shared by all): the same inputs
+    through different workspaces give the same bits."""
+    from dquartic.model.building_blocks import CustomTransformer
+
+    torch.manual_seed(3)
+    net = CustomTransformer(input_dim=8, hidden_dim=16, num_heads=2, num_layers=2).cuda()
+    g = torch.Generator().manual_seed(S1)
+    x, c, t = torch.randn(2, S1, 8, generator=g).cuda(), torch.randn(2, S2, generator=g).cuda(), torch.tensor([3, 977]).cuda()
+    net._ensure_flat()
+    saving = net._run_fwd(x, t, c, training=True)
+    plain = net._run_fwd(x, t, c, training=False)
+    held = net.cached_workspaces()
+    assert held["train"].data_ptr() != held["infer"].data_ptr()
+    assert torch.isfinite(saving).all() and float(saving.abs().max()) > 0
+    assert torch.equal(saving.view(torch.int32), plain.view(torch.int32))
+
+
 def test_adapter_state_dict_is_the_transformers():
     from dquartic.model.building_blocks import CustomTransformer, DDIMTransformerAdapter
 

@@ -39,6 +39,23 @@ def test_eval_workspace_bytes():
         lib.dq_tfm_destroy(tfm)
 
 
+@pytest.mark.parametrize("cfg,shape,num_steps,repeats,expect", [
+    ((64, 32, 2, 2), (3, 10, 7), 5, 3, (67300000, 67438336, 67355808, 67610160)),
+    ((8, 16, 2, 1), (1, 1, 1), 1, 1, (67160192, 67161504, 67161296, 67160528))])
+def test_workspace_bytes_are_pinned(cfg, shape, num_steps, repeats, expect):
+    """The four size queries go through one carver: the byte counts are the ones the three separate carvers gave (inference, training,
+    sampling, evaluation), read off the library before they were merged."""
+    lib = _lib()
+    tfm = lib.dq_tfm_create(*cfg)
+    assert tfm
+    try:
+        got = (lib.dq_tfm_workspace_bytes(tfm, *shape, 0), lib.dq_tfm_workspace_bytes(tfm, *shape, 1),
+               lib.dq_tfm_sample_workspace_bytes(tfm, *shape, num_steps), lib.dq_tfm_eval_workspace_bytes(tfm, *shape, repeats))
+        assert got == expect
+    finally:
+        lib.dq_tfm_destroy(tfm)
+
+
 class _Call:
     """dq_tfm_eval_step on dummy non-null HOST pointers: a call that passed its checks would fault, so every case here must be refused before
     anything touches the device."""
@@ -187,6 +204,7 @@ def test_eval_workspace_is_cached():
     assert a.dtype == torch.uint8 and a.numel() == _lib().dq_tfm_eval_workspace_bytes(net._tfm, 2, 4, 3, 4)
     assert net.eval_workspace(2, 4, 3, 4) is a
     b = net.eval_workspace(2, 4, 3, 1)
-    assert b is not a and net.eval_workspace(2, 4, 3, 1) is b and len(net._eval_ws) == 1
+    held = net.cached_workspaces()
+    assert b is not a and net.eval_workspace(2, 4, 3, 1) is b and list(held) == ["eval"] and held["eval"] is b
     with pytest.raises(RuntimeError):
         net.eval_workspace(2, 4, 3, 0)

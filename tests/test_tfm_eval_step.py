@@ -234,7 +234,7 @@ def test_needs_no_optimizer_and_sets_no_grad(N):
     l1, p1 = dm.eval_step(x0, None, c1)  # t and noise drawn from torch's generator
     assert not loss.requires_grad and not pw.requires_grad and torch.isfinite(l1) and p1.shape == (3,)
     assert dm.optimizer is None and all(p.grad is None for p in dm.model.parameters())
-    assert not any(k[3] for k in tfm._ws) and not tfm._ws_pool  # no training workspace came into being
+    assert "train" not in tfm.cached_workspaces() and not tfm._ws_pool  # no training workspace came into being
 
 
 def test_no_stale_state(N):

@@ -139,7 +139,7 @@ def main():
             json.dump(res, f, indent=1)
             f.write("\n")
         del x0, noise, x_t
-        tfm._eval_ws, tfm._ws = {}, {}
+        tfm.drop_workspaces()
         torch.cuda.empty_cache()
 
 
