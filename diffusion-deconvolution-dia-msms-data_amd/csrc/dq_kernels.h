@@ -28,6 +28,20 @@ int launch_ddim_step_sto(const float* x_t, const float* eps, float* x_prev, floa
 // x_prev may alias x_t, eps_out may alias net.  16-byte accesses when n % 4 == 0 and every tensor is 16-byte aligned.
 int launch_solver_step(const float* x_t, const float* net, float* x_prev, float* hist, float* eps_out, const float* coef_dev,
                        const float* c1_dev, float clip, int pred_x0, int64_t n, const int* step_ptr, hipStream_t s);
+// ---- the guided forms of the three updates (dq_guide.h): the same arithmetic on g = net_u + w (net_c - net_u) in place of
+// the network output; x_mirror (nullable) receives x_prev too; eps_out (nullable) the guided eps under either objective.  Any count and
+// any 4-byte aligned pointers (16-byte accesses when the counts are multiples of 4 and every pointer is 16-byte aligned).
+int launch_ddim_step_guided(const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* eps_out,
+                            const float* coef_dev, float w, int pred_x0, int64_t n, const int* step_ptr, hipStream_t s);
+int launch_ddim_step_sto_guided(const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* eps_out,
+                                const float* coef_dev, const float* sigma_dev, const int64_t* ids, const uint64_t* seed_dev, int draw, float w,
+                                int pred_x0, int B, int64_t per_window, const int* step_ptr, hipStream_t s);
+int launch_solver_step_guided(const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* hist,
+                              float* eps_out, const float* coef_dev, const float* c1_dev, float clip, float w, int pred_x0, int64_t n,
+                              const int* step_ptr, hipStream_t s);
+// ---- k_cond_drop.hip: out (B, per) = in with window b replaced by null_value iff the third Philox word of (seed, id, draw) < floor(p 2^32)
+int launch_cond_drop(const float* in, float* out, const int64_t* ids, const uint64_t* seed_dev, int draw, double p, float null_value, int B,
+                     int64_t per, hipStream_t s);
 int launch_sample_finish(const float* x, const float* ms2_cond, float* out_x, float* out_noise, int64_t n, int normalize,
                          hipStream_t s);
 int launch_mse_fwd_bwd(const float* eps, const float* noise, float* loss_out, float* grad_out, float* partials, int64_t n,

@@ -11,7 +11,9 @@
 namespace dq {
 
 // What every step's update of one sampling call shares: the tables (extra: sigma per row, or the solver's c1), the x0 history of the 2M
-// solver (updated in place), the clamp (0: off) and the shape
+// solver (updated in place), the clamp (0: off) and the shape.  guided: the forward ran at 2 B windows -- rows
+// [0, B) under the caller's condition, rows [B, 2B) under the null -- and the update combines the two outputs with the scale w inside its
+// kernel, over the B windows of the first half; x and the network output are then 2 * B * per floats each.
 struct StepUpdateArgs {
   StepUpdate kind;
   const float* coef; const float* extra;
@@ -19,6 +21,8 @@ struct StepUpdateArgs {
   float clip;
   int px0, B;
   int64_t per;
+  bool guided = false;
+  float w = 1.f;
 };
 
 // The noise of the stochastic update: the windows' ids and the seed (device memory) and the draw index (the kernel adds the step counter)
@@ -27,9 +31,11 @@ struct StepNoise { const int64_t* ids; const uint64_t* seed; int draw; };
 // The update of one step behind the network forward: x_out from x and the network output.  The row is `row` of the tables (the eager loop)
 // or, with step_ptr, the one the device-side step counter names (the captured step: row 0).  eps_out (nullable): where the step's eps goes
 // when it is not the network output itself; fused: the deterministic update went with the head launch (StepIO::fused_update), nothing is
-// left to do.
-int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net_out, float* x_out, float* eps_out, int row, const int* step_ptr,
-                       const StepNoise& z, bool fused, hipStream_t s);
+// left to do.  Guided (u.guided): net_out is the conditional output, net_u the unconditional one, x_mirror (nullable) receives x_out's values
+// as well (the unconditional half's x of the next forward), and eps_out (nullable) the guided eps; never fused (the head launch of window b
+// cannot see the output of window B + b).  Both are null otherwise.
+int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net_out, const float* net_u, float* x_out, float* x_mirror,
+                       float* eps_out, int row, const int* step_ptr, const StepNoise& z, bool fused, hipStream_t s);
 
 // What a call's (eta, sampler, clip_x0) select.  clip_x0: the clamp as the kernels take it (0: off)
 struct SamplerChoice { StepUpdate kind = StepUpdate::DDIM; bool sto = false, clip = false; float clip_x0 = 0.f; int px0 = 0; };

@@ -6,6 +6,9 @@
 #include "dq_sampler_tables.h"
 #include "../../include/dq_hip.h"
 
+#include <cmath>
+#include <cstring>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -13,11 +16,25 @@ using namespace dq;
 
 namespace dq {
 
-int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net_out, float* x_out, float* eps_out, int row, const int* step_ptr,
-                       const StepNoise& z, bool fused, hipStream_t s) {
+int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net_out, const float* net_u, float* x_out, float* x_mirror,
+                       float* eps_out, int row, const int* step_ptr, const StepNoise& z, bool fused, hipStream_t s) {
   const float* coef = u.coef + 4 * row;
   const float* extra = u.extra + row;
   const int64_t n = u.B * u.per;
+  if (u.guided) {  // (the same kernels' guided forms, never in the head launch)
+    switch (u.kind) {
+      case StepUpdate::SOLVER_1:
+      case StepUpdate::SOLVER_2M:
+        return launch_solver_step_guided(x, net_out, net_u, x_out, x_mirror, u.kind == StepUpdate::SOLVER_2M ? u.hist : nullptr, eps_out, coef, extra,
+                                         u.clip, u.w, u.px0, n, step_ptr, s);
+      case StepUpdate::STOCHASTIC:
+        return launch_ddim_step_sto_guided(x, net_out, net_u, x_out, x_mirror, eps_out, coef, extra, z.ids, z.seed, z.draw, u.w, u.px0, u.B, u.per,
+                                           step_ptr, s);
+      case StepUpdate::DDIM:
+        return launch_ddim_step_guided(x, net_out, net_u, x_out, x_mirror, eps_out, coef, u.w, u.px0, n, step_ptr, s);
+    }
+    return 0;
+  }
   switch (u.kind) {
     case StepUpdate::SOLVER_1:
     case StepUpdate::SOLVER_2M:
@@ -96,7 +113,9 @@ int replay_captured_step(StepGraph& g, bool reusable, const SampleLoop& L, int* 
     DQ_HIP_OK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
     bool fused = false;
     int rc = L.forward(L.xa, L.xa, 0, step, L.eps, false, &fused, cs);  // (x in place: element-wise, read and written by the same lane; no eps out)
-    if (!rc) rc = launch_step_update(L.upd, L.xa, L.eps, L.xa, nullptr, 0, step, staged, fused, cs);
+    const int64_t n = L.upd.B * L.upd.per;  // guided: the unconditional halves of the network output and of x lie n floats behind the conditional ones
+    if (!rc) rc = launch_step_update(L.upd, L.xa, L.eps, L.upd.guided ? L.eps + n : nullptr, L.xa, L.upd.guided ? L.xa + n : nullptr, nullptr, 0, step,
+                                     staged, fused, cs);
     if (!rc) rc = launch_inc_step(step, cs);
     hipGraph_t graph = nullptr;
     const hipError_t ce = hipStreamEndCapture(cs, &graph);
@@ -116,12 +135,17 @@ int eager_steps(const SampleLoop& L, float* traj_x, float* traj_eps, const int64
   const int64_t n = u.B * u.per;
   float *xa = L.xa, *xb = u.hist;
   for (int i = 0; i < L.num_steps; ++i) {
-    // eps objective: the network output IS the trajectory's eps; x0 objective, or a clamped x0: the derived eps goes to the trajectory
-    float* eps = traj_eps ? traj_eps + (int64_t)i * n : L.eps;
+    // eps objective: the network output IS the trajectory's eps; x0 objective, or a clamped x0: the derived eps goes to the trajectory.
+    // Guided: the network output is two halves in the scratch (2 n floats), the trajectory's eps is always the update's guided one
+    float* eps = (traj_eps && !u.guided) ? traj_eps + (int64_t)i * n : L.eps;
     float* xn = traj_x ? traj_x + (int64_t)i * n : (in_place ? xa : xb);
     bool fused = false;
     DQ_TRY(L.forward(xa, xn, i, nullptr, eps, traj_eps != nullptr, &fused, s));  // model.py:271 / :276
-    DQ_TRY(launch_step_update(u, xa, eps, xn, (traj_eps && (u.px0 || L.clip)) ? eps : nullptr, i, nullptr, StepNoise{window_ids_dev, seed_dev, 1 + i}, fused, s));
+    float* eps_out = !traj_eps ? nullptr : u.guided ? traj_eps + (int64_t)i * n : (u.px0 || L.clip) ? eps : nullptr;
+    // (the mirror: the second half of the buffer the next forward reads -- xa when the step's x goes to a trajectory slot and is copied back)
+    float* mirror = u.guided ? (traj_x ? xa : xn) + n : nullptr;
+    DQ_TRY(launch_step_update(u, xa, eps, u.guided ? eps + n : nullptr, xn, mirror, eps_out, i, nullptr, StepNoise{window_ids_dev, seed_dev, 1 + i},
+                              fused, s));
     if (traj_x) {
       DQ_HIP_OK(hipMemcpyAsync(xa, xn, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
     } else if (!in_place) {
@@ -132,6 +156,113 @@ int eager_steps(const SampleLoop& L, float* traj_x, float* traj_eps, const int64
 }
 
 }  // namespace dq
+
+namespace {
+
+// Classifier-free guidance on MS1: the scale w of g = u + w (c - u) and the raw MS1 value of the null condition
+struct Guidance { float w, null_ms1; };
+bool guidance_ok(float w) { return w >= 0.f && std::isfinite(w); }  // (false for NaN)
+
+static_assert((int)StepUpdate::DDIM == DQ_UPDATE_DDIM && (int)StepUpdate::STOCHASTIC == DQ_UPDATE_STOCHASTIC &&
+              (int)StepUpdate::SOLVER_1 == DQ_UPDATE_SOLVER_1 && (int)StepUpdate::SOLVER_2M == DQ_UPDATE_SOLVER_2M, "DQ_UPDATE_* are StepUpdate's values");
+
+// The U-Net's sampling call: dq_ddim_sample_solver (g null) and dq_ddim_sample_guided.  Guided, the arena and the forward run at NB = 2 B
+// windows: rows [0, B) carry the caller's MS1, rows [B, 2B) g->null_ms1 in every element (a raw value: it goes through the same cm, ca
+// normalisation); both halves see the same mixture and the same x, which the update keeps equal by writing x_prev to both (x_mirror).  The
+// conditions are staged in the workspace for every path, the update / hist / trajectories / outputs cover B windows, and the update never
+// rides in the head launch.
+int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps, const float* x_T,
+                const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type, const int32_t* timesteps_host, int num_steps,
+                float* out_x, float* out_noise, float* traj_x, float* traj_eps, int use_graph, void* workspace, int64_t workspace_bytes, int B,
+                int RT, void* stream, float eta, const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0,
+                const Guidance* g) {
+  const char* who = g ? "dq_ddim_sample_guided" : "dq_ddim_sample";
+  const std::string wh(who);
+  SamplerChoice sc;
+  DQ_TRY(sampler_check(who, plan && params && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
+                       eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, &sc));
+  DQ_REQUIRE(!g || guidance_ok(g->w), wh + ": the guidance scale must be finite and >= 0");
+  const StepUpdate kind = sc.kind;
+  clip_x0 = sc.clip_x0;
+  // the head launch takes the update when it can (StepIO::x_t); the others, and every guided one, run behind the forward
+  const bool in_head = kind == StepUpdate::DDIM && !g;
+  DQ_REQUIRE(B > 0 && RT > 0 && num_steps >= 1 && num_steps <= 1024, wh + ": need B, RT > 0 and 1 <= num_steps <= 1024");
+  DQ_REQUIRE(!g || B <= INT32_MAX / 2, wh + ": batch too large");
+  const int NB = g ? 2 * B : B;  // the windows of the arena and of the forward
+  DQ_TRY(ensure_arena(plan, NB, RT));
+  const Arena& a = plan->arena;
+  DQ_REQUIRE(workspace_bytes >= (int64_t)sizeof(float) * a.floats, wh + ": workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  float* W = (float*)workspace;
+  Ctx c{plan->plan, a, params, W, nullptr, nullptr, NB, RT, s};
+  c.save = false;
+  const int T = num_timesteps;  // length of alpha_bars_host (DDIMDiffusionModel.num_timesteps: the schedule is the caller's)
+  DQ_REQUIRE(T >= 1, wh + ": num_timesteps must be >= 1");
+  const int64_t per = (int64_t)RT * plan->plan.mz, n = B * per;
+  const int64_t n1 = (int64_t)B * RT * plan->plan.ms1_channels;  // the caller's MS1
+  const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
+  const int32_t* ts = timesteps_host;  // trunc(linspace(T-1, 0, num_steps)) formed by the caller exactly as model.py:313 does
+  DQ_TRY(sampler_upload_tables(who, alpha_bars_host, T, ts, num_steps, sampler, sc, eta, c.w(a.coef), in_head ? nullptr : c.w(a.sigma), s));
+  float* xa = c.w(a.xa);
+  if (x_T) DQ_HIP_OK(hipMemcpyAsync(xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  else DQ_TRY(launch_randn(xa, window_ids_dev, seed_dev, 0, B, per, s));  // draw index 0 is x_T's
+  if (g) DQ_HIP_OK(hipMemcpyAsync(xa + n, xa, sizeof(float) * n, hipMemcpyDeviceToDevice, s));  // the unconditional half starts from the same x_T
+  // the conditions staged at fixed addresses: for the captured step, and for every guided call (the mixture twice; the caller's MS1, then
+  // the null's raw value in every element of the second half)
+  const auto stage_conditions = [&]() -> int {
+    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c2_stage), ms2_cond, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c1_stage), ms1_cond, sizeof(float) * n1, hipMemcpyDeviceToDevice, s));
+    if (g) {
+      uint32_t bits;
+      std::memcpy(&bits, &g->null_ms1, sizeof bits);
+      DQ_HIP_OK(hipMemcpyAsync(c.w(a.c2_stage) + n, ms2_cond, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+      DQ_HIP_OK(hipMemsetD32Async((hipDeviceptr_t)(c.w(a.c1_stage) + n1), (int)bits, (size_t)n1, s));
+    }
+    return 0;
+  };
+  Ctx::StepIO io; io.pred_x0 = sc.px0;
+  // The step index of a captured step lives on the device: k_time_fwd reads ts_tab[*step], the update its coefficient row, k_inc_step bumps it.
+  int* ts_tab = reinterpret_cast<int*>(c.w(a.ts_tab));
+  // the forward of this network: captured over the staged conditions (all pointers inside the arena / parameter buffers), eagerly over the
+  // caller's, or guided over the staged ones again
+  const float* c2_eager = g ? c.w(a.c2_stage) : ms2_cond;
+  const float* c1_eager = g ? c.w(a.c1_stage) : ms1_cond;
+  const StepForward forward = [&](const float* x, float* x_out, int row, const int* step_ptr, float* net_out, bool want_eps, bool* fused, hipStream_t fs) {
+    Ctx fc{plan->plan, a, params, W, nullptr, nullptr, NB, RT, fs};
+    fc.save = false; fc.step_io = &io;
+    io.x_t = in_head ? x : nullptr; io.x_out = x_out; io.coef = c.w(a.coef) + 4 * row; io.step_ptr = step_ptr; io.want_eps = want_eps; io.fused_update = false;
+    const int rc = step_ptr ? unet_forward(fc, rope_freqs, x, nullptr, 0, c.w(a.c2_stage), c.w(a.c1_stage), cm, ca, plan->dev, net_out, ts_tab, step_ptr)
+                            : unet_forward(fc, rope_freqs, x, nullptr, ts[row], c2_eager, c1_eager, cm, ca, plan->dev, net_out);
+    *fused = io.fused_update;
+    return rc;
+  };
+  const SampleLoop loop{forward, StepUpdateArgs{kind, c.w(a.coef), c.w(a.sigma), c.w(a.xb), clip_x0, sc.px0, B, per, g != nullptr, g ? g->w : 1.f},
+                        xa, c.w(a.eps), sc.clip, num_steps, ms2_cond, out_x, out_noise, auto_normalize};
+  if (use_graph && !traj_x && !traj_eps) {
+    // ---- hipGraph path: one step captured once, replayed per step
+    int* step = reinterpret_cast<int*>(c.w(a.step));
+    DQ_HIP_OK(hipMemcpyAsync(ts_tab, ts, sizeof(int32_t) * num_steps, hipMemcpyHostToDevice, s));
+    DQ_HIP_OK(hipMemsetAsync(step, 0, sizeof(int), s));
+    DQ_TRY(stage_conditions());
+    uint64_t* seed_st = reinterpret_cast<uint64_t*>(c.w(a.seed_stage));
+    int64_t* ids_st = reinterpret_cast<int64_t*>(c.w(a.ids_stage));
+    if (sc.sto) DQ_TRY(sampler_stage_noise(seed_st, ids_st, seed_dev, window_ids_dev, B, s));  // staged like the conditions (null ids: 0 .. B-1)
+    DQ_HIP_OK(hipStreamSynchronize(s));  // ts is caller memory; also keeps the capture below free of pending copies
+    DQ_TRY(unet_sample_prologue(c, c.w(a.c1_stage), cm, ca, rope_freqs, &io.prologue));
+    StepKey key;
+    key.params = params; key.rope = rope_freqs; key.ws = workspace; key.B = B; key.RT = RT; key.normalize = auto_normalize; key.pred = pred_type;
+    key.update = kind; key.clip = clip_x0; key.guidance = g ? g->w : -1.f; key.opt_epoch = options_epoch();
+    bool captured;  // (the key only after instantiation succeeded)
+    const int rc = replay_captured_step(plan->step, plan->step.exec && plan->step_key == key, loop, step, StepNoise{ids_st, seed_st, 0}, s, &captured);
+    if (captured) plan->step_key = key;
+    return rc;
+  }
+  if (g) DQ_TRY(stage_conditions());
+  DQ_TRY(unet_sample_prologue(c, c1_eager, cm, ca, rope_freqs, &io.prologue));
+  return eager_steps(loop, traj_x, traj_eps, window_ids_dev, seed_dev, s);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -191,66 +322,44 @@ int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_
                       const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
                       int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
                       const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0) {
-  SamplerChoice sc;
-  DQ_TRY(sampler_check("dq_ddim_sample", plan && params && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
-                       eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, &sc));
-  const StepUpdate kind = sc.kind;
-  clip_x0 = sc.clip_x0;
-  const bool in_head = kind == StepUpdate::DDIM;  // the head launch takes the update when it can (StepIO::x_t); the others run behind the forward
-  DQ_REQUIRE(B > 0 && RT > 0 && num_steps >= 1 && num_steps <= 1024, "dq_ddim_sample: need B, RT > 0 and 1 <= num_steps <= 1024");
-  DQ_TRY(ensure_arena(plan, B, RT));
-  const Arena& a = plan->arena;
-  DQ_REQUIRE(workspace_bytes >= (int64_t)sizeof(float) * a.floats, "dq_ddim_sample: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W = (float*)workspace;
-  Ctx c{plan->plan, a, params, W, nullptr, nullptr, B, RT, s};
-  c.save = false;
-  const int T = num_timesteps;  // length of alpha_bars_host (DDIMDiffusionModel.num_timesteps: the schedule is the caller's)
-  DQ_REQUIRE(T >= 1, "dq_ddim_sample: num_timesteps must be >= 1");
-  const int64_t per = (int64_t)RT * plan->plan.mz, n = B * per;
-  const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
-  const int32_t* ts = timesteps_host;  // trunc(linspace(T-1, 0, num_steps)) formed by the caller exactly as model.py:313 does
-  DQ_TRY(sampler_upload_tables("dq_ddim_sample", alpha_bars_host, T, ts, num_steps, sampler, sc, eta, c.w(a.coef), in_head ? nullptr : c.w(a.sigma), s));
-  float* xa = c.w(a.xa);
-  if (x_T) DQ_HIP_OK(hipMemcpyAsync(xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-  else DQ_TRY(launch_randn(xa, window_ids_dev, seed_dev, 0, B, per, s));  // draw index 0 is x_T's
-  Ctx::StepIO io; io.pred_x0 = sc.px0;
-  // The step index of a captured step lives on the device: k_time_fwd reads ts_tab[*step], the update its coefficient row, k_inc_step bumps it.
-  int* ts_tab = reinterpret_cast<int*>(c.w(a.ts_tab));
-  // the forward of this network: captured over the staged conditions (all pointers inside the arena / parameter buffers), eagerly over the caller's
-  const StepForward forward = [&](const float* x, float* x_out, int row, const int* step_ptr, float* net_out, bool want_eps, bool* fused, hipStream_t fs) {
-    Ctx fc{plan->plan, a, params, W, nullptr, nullptr, B, RT, fs};
-    fc.save = false; fc.step_io = &io;
-    io.x_t = in_head ? x : nullptr; io.x_out = x_out; io.coef = c.w(a.coef) + 4 * row; io.step_ptr = step_ptr; io.want_eps = want_eps; io.fused_update = false;
-    const int rc = step_ptr ? unet_forward(fc, rope_freqs, x, nullptr, 0, c.w(a.c2_stage), c.w(a.c1_stage), cm, ca, plan->dev, net_out, ts_tab, step_ptr)
-                            : unet_forward(fc, rope_freqs, x, nullptr, ts[row], ms2_cond, ms1_cond, cm, ca, plan->dev, net_out);
-    *fused = io.fused_update;
-    return rc;
-  };
-  const SampleLoop loop{forward, StepUpdateArgs{kind, c.w(a.coef), c.w(a.sigma), c.w(a.xb), clip_x0, sc.px0, B, per}, xa, c.w(a.eps), sc.clip,
-                        num_steps, ms2_cond, out_x, out_noise, auto_normalize};
-  if (use_graph && !traj_x && !traj_eps) {
-    // ---- hipGraph path: one step captured once, replayed per step
-    int* step = reinterpret_cast<int*>(c.w(a.step));
-    DQ_HIP_OK(hipMemcpyAsync(ts_tab, ts, sizeof(int32_t) * num_steps, hipMemcpyHostToDevice, s));
-    DQ_HIP_OK(hipMemsetAsync(step, 0, sizeof(int), s));
-    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c2_stage), ms2_cond, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c1_stage), ms1_cond, sizeof(float) * (int64_t)B * RT * plan->plan.ms1_channels, hipMemcpyDeviceToDevice, s));
-    uint64_t* seed_st = reinterpret_cast<uint64_t*>(c.w(a.seed_stage));
-    int64_t* ids_st = reinterpret_cast<int64_t*>(c.w(a.ids_stage));
-    if (sc.sto) DQ_TRY(sampler_stage_noise(seed_st, ids_st, seed_dev, window_ids_dev, B, s));  // staged like the conditions (null ids: 0 .. B-1)
-    DQ_HIP_OK(hipStreamSynchronize(s));  // ts is caller memory; also keeps the capture below free of pending copies
-    DQ_TRY(unet_sample_prologue(c, c.w(a.c1_stage), cm, ca, rope_freqs, &io.prologue));
-    StepKey key;
-    key.params = params; key.rope = rope_freqs; key.ws = workspace; key.B = B; key.RT = RT; key.normalize = auto_normalize; key.pred = pred_type;
-    key.update = kind; key.clip = clip_x0; key.opt_epoch = options_epoch();
-    bool captured;  // (the key only after instantiation succeeded)
-    const int rc = replay_captured_step(plan->step, plan->step.exec && plan->step_key == key, loop, step, StepNoise{ids_st, seed_st, 0}, s, &captured);
-    if (captured) plan->step_key = key;
-    return rc;
-  }
-  DQ_TRY(unet_sample_prologue(c, ms1_cond, cm, ca, rope_freqs, &io.prologue));
-  return eager_steps(loop, traj_x, traj_eps, window_ids_dev, seed_dev, s);
+  return unet_sample(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type, timesteps_host,
+                     num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream, eta, seed_dev,
+                     window_ids_dev, sampler, clip_x0, nullptr);
+}
+
+int dq_ddim_sample_guided(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                          const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                          const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                          int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                          const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, float guidance_scale,
+                          float null_ms1) {
+  const Guidance g{guidance_scale, null_ms1};
+  return unet_sample(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type, timesteps_host,
+                     num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream, eta, seed_dev,
+                     window_ids_dev, sampler, clip_x0, &g);
+}
+
+int dq_guided_update(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
+                     float* eps_out, const float* coef_dev, float w, float clip_x0, const int64_t* window_ids_dev, const uint64_t* seed_dev,
+                     int draw, int pred_type, int B, int64_t per_window, void* stream) {
+  DQ_REQUIRE(x_t && net_c && net_u && x_prev && coef_dev, "dq_guided_update: null argument");
+  DQ_REQUIRE(kind == DQ_UPDATE_DDIM || kind == DQ_UPDATE_STOCHASTIC || kind == DQ_UPDATE_SOLVER_1 || kind == DQ_UPDATE_SOLVER_2M,
+             "dq_guided_update: unknown update kind");
+  DQ_REQUIRE(kind != DQ_UPDATE_STOCHASTIC || seed_dev, "dq_guided_update: the stochastic update needs the seed (device memory)");
+  DQ_REQUIRE(kind != DQ_UPDATE_SOLVER_2M || x0_hist, "dq_guided_update: the 2M update needs the x0 history");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_guided_update: Unknown pred_type");
+  DQ_REQUIRE(guidance_ok(w), "dq_guided_update: the guidance scale must be finite and >= 0");
+  DQ_REQUIRE(B >= 0 && per_window >= 0, "dq_guided_update: negative size");
+  // coefficient layout per kind: the stand-alone entries' (4 floats, or 5 with sigma / c1 behind them)
+  const StepUpdateArgs u{(StepUpdate)kind, coef_dev, coef_dev + 4, x0_hist, clip_x0, pred_type == DQ_PRED_X0, B, per_window, true, w};
+  return launch_step_update(u, x_t, net_c, net_u, x_prev, x_mirror, eps_out, 0, nullptr, StepNoise{window_ids_dev, seed_dev, draw}, false,
+                            (hipStream_t)stream);
+}
+
+int dq_ms1_cond_drop(const float* ms1_in, float* ms1_out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, double p,
+                     float null_value, int B, int64_t per_ms1, void* stream) {
+  DQ_REQUIRE(ms1_in && ms1_out && seed_dev, "dq_ms1_cond_drop: null argument");
+  return launch_cond_drop(ms1_in, ms1_out, window_ids_dev, seed_dev, draw, p, null_value, B, per_ms1, (hipStream_t)stream);
 }
 
 }  // extern "C"

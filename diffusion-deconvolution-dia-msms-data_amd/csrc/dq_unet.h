@@ -60,16 +60,18 @@ void layout_arena(const Plan& p, int B, int RT, Arena& a);
 enum class StepUpdate { DDIM, STOCHASTIC, SOLVER_1, SOLVER_2M };
 
 // Everything a captured sampling step has baked into its kernel arguments or its dispatch.  clip: the clamp of k_solver_step (0: off);
+// guidance: the scale the guided update takes by value (< 0: not a guided step; B is then the caller's, not the doubled, batch);
 // opt_epoch: options_epoch() at capture time (a dq_set_option call may change the dispatch)
 struct StepKey {
   const void* params = nullptr; const void* rope = nullptr; const void* ws = nullptr;
   int B = 0, RT = 0, normalize = -1, pred = -1;
   StepUpdate update = StepUpdate::DDIM;
   float clip = 0.f;
+  float guidance = -1.f;
   unsigned opt_epoch = 0;
   bool operator==(const StepKey& o) const {
     return params == o.params && rope == o.rope && ws == o.ws && B == o.B && RT == o.RT && normalize == o.normalize && pred == o.pred &&
-           update == o.update && clip == o.clip && opt_epoch == o.opt_epoch;
+           update == o.update && clip == o.clip && guidance == o.guidance && opt_epoch == o.opt_epoch;
   }
 };
 

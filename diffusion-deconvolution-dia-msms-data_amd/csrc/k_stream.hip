@@ -5,6 +5,7 @@
 // (clip_grad_norm_(10.0) + AdamW with torch defaults).
 // All kernels: 16 B per lane, grid-stride, no LDS.  Algorithmic bytes per element are stated per kernel.
 #include "dq_common.h"
+#include "dq_guide.h"
 #include "dq_kernels.h"
 #include <algorithm>
 #include <cmath>
@@ -61,30 +62,38 @@ int launch_q_sample(const float* alpha_bars, const float* x0, const int64_t* t, 
   return 0;
 }
 
-// ---- K9: x0 = (x_t - sb*eps)/sa ; x_prev = sap*x0 + sbp*eps (t>0) else x0 : 12 B / element
+// ---- K9: x0 = (x_t - sb*eps)/sa ; x_prev = sap*x0 + sbp*eps (t>0) else x0 : 12 B / element (guided, k_ddim_step_g: 20 B / element)
 // ``coef`` is a device table of 4 floats per step [sa, sb, sap, sbp]; sap < 0 marks the t == 0 step.
 // PRED_X0 (model.py:274-278): ``eps`` holds the network's x0 prediction, eps = (x_t - sa*x0)/sb is derived (and written to
 // eps_out when given: p_sample returns it).
+struct DdimRow { float sa, sb, sap, sbp; bool last; };
+
+__device__ __forceinline__ DdimRow ddim_row(const float* coef, const int* step_ptr) {
+  if (step_ptr) coef += 4 * step_ptr[0];  // graph replay: this step's row of the coefficient table
+  return DdimRow{coef[0], coef[1], coef[2], coef[3], coef[2] < 0.f};
+}
+
+// One element: x_prev from x and the network output v (or, guided, from g in its place: dq_guide.h); the step's eps by reference
+template <bool PRED_X0>
+__device__ __forceinline__ float ddim_elem(const DdimRow& r, float x, float v, float& ep) {
+  float x0;
+  if (PRED_X0) { x0 = v; ep = (x - r.sa * x0) / r.sb; }
+  else         { ep = v; x0 = (x - r.sb * ep) / r.sa; }
+  return r.last ? x0 : r.sap * x0 + r.sbp * ep;
+}
+
 template <bool PRED_X0>
 __global__ void __launch_bounds__(256) k_ddim_step(const float* __restrict__ x_t, const float* __restrict__ eps,
                                                    float* __restrict__ x_prev, float* __restrict__ eps_out,
                                                    const float* __restrict__ coef, int64_t n4, const int* __restrict__ step_ptr) {
-  if (step_ptr) coef += 4 * step_ptr[0];  // graph replay: this step's row of the coefficient table
-  const float sa = coef[0], sb = coef[1], sap = coef[2], sbp = coef[3];
-  const bool last = sap < 0.f;
+  const DdimRow r = ddim_row(coef, step_ptr);
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     const float4 x = reinterpret_cast<const float4*>(x_t)[i];
     const float4 e = reinterpret_cast<const float4*>(eps)[i];
     const float xv[4] = {x.x, x.y, x.z, x.w}, ev[4] = {e.x, e.y, e.z, e.w};
     float ov[4], dv[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float x0, ep;
-      if (PRED_X0) { x0 = ev[j]; ep = (xv[j] - sa * x0) / sb; }
-      else         { ep = ev[j]; x0 = (xv[j] - sb * ep) / sa; }
-      ov[j] = last ? x0 : sap * x0 + sbp * ep;
-      dv[j] = ep;
-    }
+    for (int j = 0; j < 4; ++j) ov[j] = ddim_elem<PRED_X0>(r, xv[j], ev[j], dv[j]);
     reinterpret_cast<float4*>(x_prev)[i] = make_float4(ov[0], ov[1], ov[2], ov[3]);
     if (PRED_X0 && eps_out) reinterpret_cast<float4*>(eps_out)[i] = make_float4(dv[0], dv[1], dv[2], dv[3]);
   }
@@ -95,16 +104,50 @@ template <bool PRED_X0>
 __global__ void __launch_bounds__(256) k_ddim_step_1(const float* __restrict__ x_t, const float* __restrict__ eps,
                                                      float* __restrict__ x_prev, float* __restrict__ eps_out,
                                                      const float* __restrict__ coef, int64_t n, const int* __restrict__ step_ptr) {
-  if (step_ptr) coef += 4 * step_ptr[0];
-  const float sa = coef[0], sb = coef[1], sap = coef[2], sbp = coef[3];
-  const bool last = sap < 0.f;
+  const DdimRow r = ddim_row(coef, step_ptr);
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float xv = x_t[i], ev = eps[i];
-    float x0, ep;
-    if (PRED_X0) { x0 = ev; ep = (xv - sa * x0) / sb; }
-    else         { ep = ev; x0 = (xv - sb * ep) / sa; }
-    x_prev[i] = last ? x0 : sap * x0 + sbp * ep;
+    float ep;
+    x_prev[i] = ddim_elem<PRED_X0>(r, x_t[i], eps[i], ep);
     if (PRED_X0 && eps_out) eps_out[i] = ep;
+  }
+}
+
+// The guided update (dq_guide.h): ddim_elem on g = u + w (c - u) in place of the network output, the result to x_prev
+// and, when x_mirror is given, to x_mirror as well (the unconditional half's copy of x for the next forward); eps_out (nullable) receives
+// the guided eps under either objective.  20 B / element with the mirror (reads x, c, u; writes x_prev, x_mirror), + 4 with eps_out.
+// Element-wise: x_prev may alias x_t, eps_out may alias net_c (and net_u net_c): no __restrict__ on the tensors.
+template <bool PRED_X0>
+__global__ void __launch_bounds__(256) k_ddim_step_g(const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror,
+                                                     float* eps_out, const float* __restrict__ coef, float w, int64_t n4,
+                                                     const int* __restrict__ step_ptr) {
+  const DdimRow r = ddim_row(coef, step_ptr);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 x = reinterpret_cast<const float4*>(x_t)[i];
+    const float4 c = reinterpret_cast<const float4*>(net_c)[i];
+    const float4 u = reinterpret_cast<const float4*>(net_u)[i];
+    const float xv[4] = {x.x, x.y, x.z, x.w}, cv[4] = {c.x, c.y, c.z, c.w}, uv[4] = {u.x, u.y, u.z, u.w};
+    float ov[4], dv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ov[j] = ddim_elem<PRED_X0>(r, xv[j], guide(cv[j], uv[j], w), dv[j]);
+    const float4 o = make_float4(ov[0], ov[1], ov[2], ov[3]);
+    reinterpret_cast<float4*>(x_prev)[i] = o;
+    if (x_mirror) reinterpret_cast<float4*>(x_mirror)[i] = o;
+    if (eps_out) reinterpret_cast<float4*>(eps_out)[i] = make_float4(dv[0], dv[1], dv[2], dv[3]);
+  }
+}
+
+// the same, one element per lane and step: counts that are no multiple of 4, pointers that are not 16-byte aligned
+template <bool PRED_X0>
+__global__ void __launch_bounds__(256) k_ddim_step_g_1(const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror,
+                                                       float* eps_out, const float* __restrict__ coef, float w, int64_t n,
+                                                       const int* __restrict__ step_ptr) {
+  const DdimRow r = ddim_row(coef, step_ptr);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float ep;
+    const float o = ddim_elem<PRED_X0>(r, x_t[i], guide(net_c[i], net_u[i], w), ep);
+    x_prev[i] = o;
+    if (x_mirror) x_mirror[i] = o;
+    if (eps_out) eps_out[i] = ep;
   }
 }
 
@@ -130,6 +173,27 @@ int launch_ddim_step(const float* x_t, const float* eps, float* x_prev, const fl
   const int grid = (int)std::min<int64_t>(cdiv(n / 4, 256), 2048);
   if (pred_x0) hipLaunchKernelGGL(k_ddim_step<true>, dim3(grid), dim3(256), 0, s, x_t, eps, x_prev, eps_out, coef_dev, n / 4, step_ptr);
   else hipLaunchKernelGGL(k_ddim_step<false>, dim3(grid), dim3(256), 0, s, x_t, eps, x_prev, eps_out, coef_dev, n / 4, step_ptr);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_ddim_step_guided(const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* eps_out,
+                            const float* coef_dev, float w, int pred_x0, int64_t n, const int* step_ptr, hipStream_t s) {
+  DQ_REQUIRE(x_t && net_c && net_u && x_prev && coef_dev, "ddim_step_guided: null argument");
+  DQ_REQUIRE(n >= 0, "ddim_step_guided: negative element count");
+  const uintptr_t bits = (uintptr_t)x_t | (uintptr_t)net_c | (uintptr_t)net_u | (uintptr_t)x_prev | (uintptr_t)x_mirror | (uintptr_t)eps_out;
+  DQ_REQUIRE((bits & 3) == 0, "ddim_step_guided: tensors must be 4-byte aligned");
+  if (n == 0) return 0;
+  if (n % 4 != 0 || (bits & 15) != 0) {
+    const int grid1 = (int)std::min<int64_t>(cdiv(n, 256), 2048);
+    if (pred_x0) hipLaunchKernelGGL(k_ddim_step_g_1<true>, dim3(grid1), dim3(256), 0, s, x_t, net_c, net_u, x_prev, x_mirror, eps_out, coef_dev, w, n, step_ptr);
+    else hipLaunchKernelGGL(k_ddim_step_g_1<false>, dim3(grid1), dim3(256), 0, s, x_t, net_c, net_u, x_prev, x_mirror, eps_out, coef_dev, w, n, step_ptr);
+    DQ_LAUNCH_CHECK();
+    return 0;
+  }
+  const int grid = (int)std::min<int64_t>(cdiv(n / 4, 256), 2048);
+  if (pred_x0) hipLaunchKernelGGL(k_ddim_step_g<true>, dim3(grid), dim3(256), 0, s, x_t, net_c, net_u, x_prev, x_mirror, eps_out, coef_dev, w, n / 4, step_ptr);
+  else hipLaunchKernelGGL(k_ddim_step_g<false>, dim3(grid), dim3(256), 0, s, x_t, net_c, net_u, x_prev, x_mirror, eps_out, coef_dev, w, n / 4, step_ptr);
   DQ_LAUNCH_CHECK();
   return 0;
 }

@@ -11,6 +11,7 @@ _lib = None
 ABI_VERSION = 12  # DQ_ABI_VERSION of include/dq_hip.h this table was written against
 PRED_TYPES = {"eps": 0, "x0": 1}  # DQ_PRED_EPS / DQ_PRED_X0
 SAMPLERS = {"reference": 0, "ddim": 1, "dpmpp_2m": 2}  # DQ_SAMPLER_*
+UPDATE_KINDS = {"ddim": 0, "stochastic": 1, "solver_1": 2, "solver_2m": 3}  # DQ_UPDATE_* (dq_guided_update)
 PRECISIONS = {"fp32": 0, "bf16x3": 1}  # DQ_PRECISION_FP32 / DQ_PRECISION_BF16X3
 FINAL_ACTS = {"identity": 0, "softplus": 1}  # DQ_FINAL_IDENTITY / DQ_FINAL_SOFTPLUS
 RES_FWD_FORMS = ("rt", "level", "v4", "unfused")  # DQ_RES_FWD_* (index = value)
@@ -89,6 +90,11 @@ PROTOTYPES = {
     "dq_ddim_sample_solver": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                       POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
                                       c_void_p, c_float, c_void_p, c_void_p, c_int, c_float]),
+    "dq_guided_update": (c_int, [c_int] + [c_void_p] * 8 + [c_float, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
+    "dq_ms1_cond_drop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_float, c_int, c_int64, c_void_p]),
+    "dq_ddim_sample_guided": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                      POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
+                                      c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_float, c_float]),
     "dq_pair_batch_scratch_bytes": (c_int64, [c_int]),
     "dq_pair_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int64, c_float, c_float, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

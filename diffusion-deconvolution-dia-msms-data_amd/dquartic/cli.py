@@ -85,6 +85,7 @@ def train(config_path, parquet_directory, ms2_data_path, ms1_data_path, batch_si
         loader = DataLoader(dataset, batch_size=per_rank, shuffle=True, num_workers=int(config["threads"]), drop_last=len(dataset) > per_rank)
     dm = build_model(m, device)
     enable_ema_from_config(dm, m)
+    enable_cond_dropout_from_config(dm, m)
     val = validation_config(config)
     val_loader = None if val is None else build_validation_loader(val, m, per_rank, rank, world)
     wb = None
@@ -171,6 +172,17 @@ def enable_ema_from_config(dm, m) -> bool:
     return True
 
 
+def enable_cond_dropout_from_config(dm, m) -> bool:
+    """``model.cond_drop_prob`` (absent, null or 0: off) with the optional ``model.cond_drop_seed`` (default 0) and ``model.null_ms1``
+    (default 0.0) of a train config: conditioning dropout for classifier-free guidance (``ModelInterface.set_cond_dropout``).  Returns
+    whether it was turned on."""
+    p = m.get("cond_drop_prob")
+    if p is None:
+        return False
+    dm.set_cond_dropout(float(p), seed=int(m.get("cond_drop_seed", 0)), null_ms1=float(m.get("null_ms1", 0.0)))
+    return dm.cond_dropout_enabled
+
+
 @cli.command()
 @click.argument("config-path", type=click.Path(exists=True), required=True)
 @click.option("--checkpoint", required=True, type=click.Path(exists=True), help="Checkpoint written by train (model_state_dict; its EMA when it has one)")
@@ -179,11 +191,14 @@ def enable_ema_from_config(dm, m) -> bool:
 @click.option("--sampler", default="reference", type=click.Choice(["reference", "ddim", "dpmpp_2m"]),
               help="Update of that sampling: the reference's, strided DDIM, or DPM-Solver++(2M)")
 @click.option("--clip-x0", default=None, type=float, help="Clamp every step's x0 estimate to [-C, C] (ddim / dpmpp_2m, eta 0)")
+@click.option("--guidance-scale", default=None, type=float,
+              help="Classifier-free guidance scale W of that sampling (UNet1d trained with model.cond_drop_prob; 1: the conditional model)")
+@click.option("--null-ms1", default=0.0, type=float, help="Raw MS1 value of the null condition (the training run's model.null_ms1)")
 @click.option("--seed", default=0, type=int, help="Seed of the evaluation noise and of the sampling")
 @click.option("--use-ema/--no-use-ema", default=None, help="Evaluate the averaged weights (default: when the checkpoint has an average)")
 @click.option("--max-batches", default=None, type=int, help="Stop after this many batches")
 @click.option("--out", "out_path", default=None, type=click.Path(), help="Write the full result, per-window metrics included, as JSON")
-def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, seed, use_ema, max_batches, out_path):
+def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, guidance_scale, null_ms1, seed, use_ema, max_batches, out_path):
     """Held-out loss (and, with --num-steps, reconstruction metrics) of a checkpoint on the config's data.validation set.  The pairs of
     that set come from the block's own seed, not from --seed: runs that differ in --seed, --eta, --num-steps or --use-ema score the same
     pairs.  Without a validation block the config's data section is scored, with a notice.  Prints one JSON line."""
@@ -209,7 +224,7 @@ def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, seed, us
     elif use_ema:
         raise click.ClickException(f"--use-ema: {checkpoint} holds no averaged weights")
     res = dm.evaluate(loader, n_t=4, seed=seed, num_steps=num_steps, eta=eta, use_ema=use_ema, max_batches=max_batches, sampler=sampler,
-                      clip_x0=clip_x0)
+                      clip_x0=clip_x0, guidance_scale=guidance_scale, null_ms1=null_ms1)
     per_window = res.pop("per_window", None)
     click.echo(json.dumps(res))
     if out_path is not None:

@@ -270,8 +270,22 @@ class DDIMDiffusionModel(ModelInterface):
             x_prev = x0_pred
         return x_prev, eps_pred
 
+    @staticmethod
+    def _check_guidance(guidance_scale):
+        """None for the call as it always was (``None`` and 1.0: the conditional model itself), else the scale as a float.  ValueError for
+        anything that is not a finite number >= 0 (as the float32 the kernels take it as)."""
+        if guidance_scale is None:
+            return None
+        try:
+            w = float(guidance_scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"guidance_scale must be a finite number >= 0 or None, got {guidance_scale!r}") from None
+        if not (w >= 0.0 and w <= float(torch.finfo(torch.float32).max)):  # (NaN fails both comparisons)
+            raise ValueError(f"guidance_scale must be a finite number >= 0 or None, got {guidance_scale!r}")
+        return None if w == 1.0 else w
+
     def sample(self, x_t, ms2_cond=None, ms1_cond=None, num_steps=1000, return_trajectory=False, eta=0.0, seed=None, window_ids=None,
-               shape=None, sampler="reference", clip_x0=None):
+               shape=None, sampler="reference", clip_x0=None, guidance_scale=None, null_ms1=0.0):
         """model.py:293-324: returns (denoised, mixture - denoised).  Native loop when the network is UNet1d; for a CustomTransformer behind
         ``DDIMTransformerAdapter`` the library's loop (``dq_tfm_sample``) serves every call when
         ``native_tfm_sampler`` is set, and otherwise exactly the calls the generic loop refuses (the options below, ``return_trajectory``).
@@ -285,13 +299,31 @@ class DDIMDiffusionModel(ModelInterface):
         ``sampler``: "reference" lands every step on ``alpha_bars[t - 1]`` as the reference does (exact only at
         ``num_steps == num_timesteps``); "ddim" lands step i on the list's next timestep; "dpmpp_2m" is DPM-Solver++(2M) over the same
         list (``eta`` must be 0).  The last step of either returns the x0 estimate.  ``clip_x0 = c > 0`` (those two samplers, ``eta == 0``)
-        clamps every step's x0 estimate to [-c, c].  Native path only."""
+        clamps every step's x0 estimate to [-c, c].  Native path only.
+
+        ``guidance_scale = w``: classifier-free guidance on MS1, the one input that names the component to extract.
+        Every step's update runs on ``g = u + w (c - u)``, c the network output under ``ms1_cond`` and u the output under the null
+        condition -- MS1 equal to the raw value ``null_ms1`` in every element, what ``set_cond_dropout`` trains the network on.  ``None``
+        and 1.0 are the call as it is without the option, bit for bit: 1.0 *is* the conditional model, no doubled batch is run for it.
+        Any other finite ``w >= 0`` (0: the unconditional model; > 1 pushes towards the component MS1 names) runs one forward at twice
+        the batch per step inside the library (``dq_ddim_sample_guided``) and combines with every option above.  UNet1d on the GPU
+        only: the generic loop and the CustomTransformer raise NotImplementedError."""
         eta = self._check_eta(eta)
         sampler_id, clip = self._check_sampler(sampler, eta, clip_x0)
+        guidance = self._check_guidance(guidance_scale)
         stochastic = eta > 0.0 or x_t is None or seed is not None or window_ids is not None
         if sampler_id != 0:
             self._check_decreasing(self.sampler_timesteps(self.num_timesteps, num_steps).tolist())
         on_gpu = ms2_cond is not None and ms1_cond is not None and (x_t.is_cuda if x_t is not None else ms2_cond.is_cuda)
+        if guidance is not None:
+            if self._native_tfm:
+                raise NotImplementedError("sample: guidance_scale is built for UNet1d (dq_ddim_sample_guided); guidance for the "
+                                          "CustomTransformer's sampler (dq_tfm_sample) is the follow-up")
+            if not (self.native and on_gpu):
+                raise NotImplementedError("sample: guidance_scale needs the native sampler (this package's UNet1d on the GPU with both "
+                                          "conditions); the generic loop is the unguided update only")
+            return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
+                                       shape=shape, sampler=sampler_id, clip_x0=clip, guidance=(guidance, float(null_ms1)))
         if on_gpu and self._native_tfm and (self.native_tfm_sampler or stochastic or sampler_id != 0 or return_trajectory):
             return self._sample_native_tfm(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
                                            shape=shape, sampler=sampler_id, clip_x0=clip)
@@ -371,14 +403,15 @@ class DDIMDiffusionModel(ModelInterface):
             torch.empty((num_steps, *dims), device=c2.device) if return_trajectory else None for _ in range(2)]
 
     def _sample_native(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False, eta=None, seed=None, window_ids=None, shape=None,
-                       sampler=0, clip_x0=0.0):
+                       sampler=0, clip_x0=0.0, guidance=None):
         """``eta`` None: ``dq_ddim_sample`` (the call as it always was); else ``dq_ddim_sample_ex``; ``sampler`` != 0:
-        ``dq_ddim_sample_solver``.  The three take one argument list; the later ones append to it."""
+        ``dq_ddim_sample_solver``; ``guidance`` = (scale, null_ms1) (``eta`` a number): ``dq_ddim_sample_guided`` on the workspace of twice
+        the batch.  The four take one argument list; the later ones append to it."""
         net: UNet1d = self.model
         x_T, c2, B, RT, MZ = self._stage_x(x_T, ms2_cond, eta, seed, shape)
         c1 = net._check_inputs(ms1_cond, B, RT).detach().to(torch.float32).contiguous()
         flat = net.read_params()  # (the averaged weights inside ModelInterface.ema_scope())
-        ws = net.workspace(B, RT, False)
+        ws = net.workspace(2 * B if guidance is not None else B, RT, False)
         ts = self.sampler_timesteps(self.num_timesteps, num_steps).to(torch.int32)
         ts_c = (ctypes.c_int32 * num_steps)(*ts.tolist())
         outs = self._sample_outputs(c2, num_steps, (B, RT, MZ), return_trajectory)
@@ -390,9 +423,12 @@ class DDIMDiffusionModel(ModelInterface):
             seed_dev, ids_dev = self._stage_noise(x_T, eta, seed, window_ids, B, c2.device)
             args += [float(eta), N.ptr(seed_dev), N.ptr(ids_dev)]
             entry = "dq_ddim_sample_ex"
-            if sampler:
+            if sampler or guidance is not None:
                 args += [int(sampler), float(clip_x0)]
                 entry = "dq_ddim_sample_solver"
+            if guidance is not None:
+                args += [float(guidance[0]), float(guidance[1])]
+                entry = "dq_ddim_sample_guided"
         N.check(getattr(N.lib(), entry)(*args), entry)
         return tuple(outs) if return_trajectory else tuple(outs[:2])
 

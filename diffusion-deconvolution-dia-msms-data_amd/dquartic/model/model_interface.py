@@ -383,7 +383,11 @@ class TrainStepGraph:
                 and tuple(t.data_ptr() for t in self._live_buffers()) == self._ptrs)
 
     def step(self, x_0, ms2_cond, ms1_cond):
-        self.x0.copy_(x_0); self.c2.copy_(ms2_cond); self.c1.copy_(ms1_cond)
+        self.x0.copy_(x_0); self.c2.copy_(ms2_cond)
+        if self.dm.cond_dropout_enabled:  # conditioning dropout in place of the copy, outside the captured graph (the step itself is unchanged)
+            self.dm._cond_drop_ms1(ms1_cond, out=self.c1)
+        else:
+            self.c1.copy_(ms1_cond)
         self.opt._dev_state()      # (a changed lr reaches its device copy here, outside the graph)
         self.opt._step += 1
         self.graph.replay()
@@ -405,6 +409,7 @@ class ModelInterface(object):
         self.ms1_loss_weight = None
         self.use_wandb = False
         self.last_grad_norm = None
+        self._cond_drop = None  # set_cond_dropout
 
     def __repr__(self):
         return f"{self.__class__.__name__} with {self.model.__class__.__name__} model with {self.get_parameter_num()} parameters on {self.device}"
@@ -607,6 +612,54 @@ class ModelInterface(object):
         if isinstance(self.optimizer, FlatAdamW):
             self.optimizer.disable_ema()
 
+    # ---- conditioning dropout for classifier-free guidance (new work: the reference has none)
+    @property
+    def cond_dropout_enabled(self) -> bool:
+        return getattr(self, "_cond_drop", None) is not None
+
+    def set_cond_dropout(self, p, seed=0, null_ms1=0.0):
+        """Train with the MS1 condition of a window replaced as a whole by the constant ``null_ms1`` (a raw value, normalised like real MS1)
+        with probability ``p``: what ``sample(..., guidance_scale=w, null_ms1=...)`` needs the network to have seen.  ``0 <= p < 1``;
+        ``p = 0`` turns it off again (the default).  UNet1d only.
+
+        ``_train_one_batch`` runs ``dq_ms1_cond_drop`` on the batch's MS1 in front of the step (under ``enable_train_graph`` in place of
+        the copy into the captured step's input, outside the graph).  The decision of window b of a step is a pure function of
+        (``seed`` + the data-parallel rank, b, the optimiser's step count before the step), so a run is reproducible; the validation
+        loss stays conditional and nothing is written into checkpoints."""
+        from .unet1d import UNet1d
+
+        try:
+            p = float(p)
+        except (TypeError, ValueError):
+            raise ValueError(f"cond_drop_prob must satisfy 0 <= p < 1, got {p!r}") from None
+        if not 0.0 <= p < 1.0:  # (NaN fails both comparisons)
+            raise ValueError(f"cond_drop_prob must satisfy 0 <= p < 1, got {p!r}")
+        if p == 0.0:
+            self._cond_drop = None
+            return
+        if not isinstance(self.model, UNet1d):
+            raise NotImplementedError("set_cond_dropout: conditioning dropout is built for UNet1d (the CustomTransformer's guided sampler is "
+                                      "the follow-up)")
+        self._cond_drop = {"p": p, "seed": int(seed), "null_ms1": float(null_ms1), "seed_dev": None}
+
+    def _cond_drop_ms1(self, ms1_cond, out=None):
+        """``dq_ms1_cond_drop`` of the batch's MS1 at draw = the optimiser's step count, ids = batch positions, seed + rank; ``out``: where
+        the result goes (a contiguous fp32 tensor of ``ms1_cond``'s shape; None: a new one)."""
+        cd = self._cond_drop
+        if not ms1_cond.is_cuda:
+            raise RuntimeError("conditioning dropout runs in the native kernel: the MS1 condition must be a device tensor")
+        src = ms1_cond.detach().to(torch.float32).contiguous()
+        if out is not None and not (out.is_contiguous() and out.dtype == torch.float32 and out.shape == src.shape):
+            return out.copy_(self._cond_drop_ms1(src))  # (a buffer the kernel cannot write in place: through a temporary)
+        if out is None:
+            out = torch.empty_like(src)
+        if cd["seed_dev"] is None or cd["seed_dev"].device != src.device:
+            cd["seed_dev"] = self._seed_tensor(cd["seed"] + _rank(), src.device)
+        draw = int(getattr(self.optimizer, "_step", 0))
+        N.check(N.lib().dq_ms1_cond_drop(N.ptr(src), N.ptr(out), None, N.ptr(cd["seed_dev"]), draw, cd["p"], cd["null_ms1"], int(src.shape[0]),
+                                         int(src[0].numel()), N.stream_ptr()), "dq_ms1_cond_drop")
+        return out
+
     def _flat_net(self):
         """The module that owns the flat buffers and makes the native calls (the transformer behind its adapter)."""
         return getattr(self.model, "transformer", self.model)
@@ -635,7 +688,7 @@ class ModelInterface(object):
         return self.ema_scope() if use else contextlib.nullcontext()
 
     def predict(self, dataloader, mixture_weights=(0.5, 0.5), num_steps=1000, use_ema=None, eta=0.0, seed=None, n_draws=1,
-                sampler="reference", clip_x0=None):
+                sampler="reference", clip_x0=None, *, guidance_scale=None, null_ms1=0.0):
         """Reference :630-668: one dict per batch with the first item's prediction (``_predict_one_batch`` returns item 0).
         ``use_ema``: sample from the averaged weights; None (default) = when EMA is enabled.
 
@@ -646,7 +699,8 @@ class ModelInterface(object):
         ``n_draws=1, seed=seed + j`` returns.  ``n_draws > 1`` adds ``"pred_mean"`` and ``"pred_std"`` (per element, over the draws,
         population form) to each dict; ``"pred"`` stays draw 0.  With ``n_draws == 1`` those two keys are absent.
 
-        ``sampler`` / ``clip_x0``: passed to ``sample``; with the defaults nothing else changes."""
+        ``sampler`` / ``clip_x0``: passed to ``sample``; with the defaults nothing else changes.  ``guidance_scale``
+        / ``null_ms1`` (keyword-only): classifier-free guidance, passed to ``sample`` too."""
         self.model.eval()
         n_draws = int(n_draws)
         if n_draws < 1:
@@ -662,11 +716,11 @@ class ModelInterface(object):
             d = {"ms2_1": ms2_1.cpu().numpy(), "ms1_1": ms1_1.cpu().numpy(), "mixture": ms2_cond.cpu().numpy()}
             if not stochastic:
                 d["pred"], _ = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, use_ema=use_ema,
-                                                       **_sampler_kwargs(sampler, clip_x0))
+                                                       **_sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1))
             else:
                 ids = torch.arange(first, first + x_0.shape[0], dtype=torch.int64)
                 out = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, use_ema=use_ema, eta=eta,
-                                              seed=seed, n_draws=n_draws, window_ids=ids, **_sampler_kwargs(sampler, clip_x0))
+                                              seed=seed, n_draws=n_draws, window_ids=ids, **_sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1))
                 d["pred"] = out[0]
                 if n_draws > 1:
                     d["pred_mean"], d["pred_std"] = out[2], out[3]
@@ -675,7 +729,7 @@ class ModelInterface(object):
         return np.array(preds, dtype=object)
 
     def evaluate(self, dataloader, mixture_weights=(0.5, 0.5), n_t=4, seed=0, num_steps=None, eta=0.0, use_ema=None, max_batches=None,
-                 sampler="reference", clip_x0=None):
+                 sampler="reference", clip_x0=None, *, guidance_scale=None, null_ms1=0.0):
         """Held-out evaluation (new work: the reference has none).  Returns a dict.
 
         Loss: every window of the loader is evaluated ``n_t`` times by ``eval_steps`` -- repeat k at the timestep
@@ -692,7 +746,8 @@ class ModelInterface(object):
         window_ids=ids)``, and ``dq_recon_metrics(sample, x_0)`` gives nine numbers per window (``_native.METRIC_NAMES``): the dict gains
         their means over the windows (``scan_sa`` / ``xic_r`` weighted by ``scan_count`` / ``xic_count``) under those names and the
         ``(n_windows, 9)`` float32 array as ``per_window``.  ``sampler`` / ``clip_x0`` go to that ``sample`` call
-        and appear in the dict only when they are not the defaults.
+        and appear in the dict only when they are not the defaults; so do ``guidance_scale`` / ``null_ms1`` (keyword-only; DESIGN.md
+        section 32: the scale can be tuned against these metrics).  The loss part is always the conditional one.
 
         ``use_ema`` as in ``predict``; ``max_batches``: stop after that many batches.  Under ``torch.distributed`` each rank evaluates
         its own loader and the scalars are averaged over the ranks (``_global_mean``); ``per_window`` and ``n_windows`` stay the rank's."""
@@ -726,7 +781,7 @@ class ModelInterface(object):
                         ts[k].append(t[k])
                     if num_steps is not None:
                         sample, _ = self.sample(None, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=int(num_steps), eta=eta, seed=int(seed),
-                                                window_ids=ids_dev, shape=tuple(x_0.shape), **_sampler_kwargs(sampler, clip_x0))
+                                                window_ids=ids_dev, shape=tuple(x_0.shape), **_sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1))
                         rows.append(E.recon_metrics(sample, x_0))
                     first += x_0.shape[0]
         finally:
@@ -747,6 +802,8 @@ class ModelInterface(object):
                 out["sampler"] = str(sampler)
             if clip_x0 is not None:
                 out["clip_x0"] = float(clip_x0)
+            if guidance_scale is not None:
+                out.update(guidance_scale=float(guidance_scale), null_ms1=float(null_ms1))
         return out
 
     # ---- internals
@@ -829,9 +886,11 @@ class ModelInterface(object):
                     del graphs[next(iter(graphs))]
                 self.optimizer.grad_scale = 1.0
                 tg = graphs[key] = TrainStepGraph(self, x_0, ms2_cond, ms1_cond, ms1_loss_weight, keep_side=getattr(self, "_train_graph_side", False))
-            loss = tg.step(x_0, ms2_cond, ms1_cond)
+            loss = tg.step(x_0, ms2_cond, ms1_cond)  # (conditioning dropout, when on: inside step(), in place of its copy of ms1_cond)
             self.last_grad_norm = self.optimizer.last_grad_norm
             return loss.item() if sync else loss
+        if self.cond_dropout_enabled and ms1_cond is not None:
+            ms1_cond = self._cond_drop_ms1(ms1_cond)  # (draw = the step count before this step)
         if fused:
             if noise is not None:
                 noise = self.normalize(noise)  # reference quirk: a passed noise is mapped 2n-1 (model.py:346)
@@ -861,7 +920,7 @@ class ModelInterface(object):
         return loss.item() if sync else loss.detach()
 
     def _predict_one_batch(self, x_0, ms2_cond=None, ms1_cond=None, num_steps=1000, use_ema=None, eta=0.0, seed=None, n_draws=1,
-                           window_ids=None, sampler="reference", clip_x0=None):
+                           window_ids=None, sampler="reference", clip_x0=None, *, guidance_scale=None, null_ms1=0.0):
         """Reference :1125-1150: eval + no_grad + sample(randn_like(x_0)); returns item 0 of the batch as numpy.  ``use_ema`` as in
         ``predict``.  With ``eta > 0``, a ``seed`` or ``n_draws > 1`` (see ``predict``): x_T and the step noise from the sampler's
         generator, draw j under ``seed + j``; ``n_draws > 1`` returns (sample, pred_noise, mean, std) of item 0, sample / pred_noise
@@ -870,7 +929,7 @@ class ModelInterface(object):
         if not (float(eta) > 0.0 or seed is not None or int(n_draws) > 1):
             with torch.no_grad(), self._ema_or_null_scope(use_ema):
                 sample, pred_noise = self.sample(torch.randn_like(x_0), ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps,
-                                                 **_sampler_kwargs(sampler, clip_x0))
+                                                 **_sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1))
             return sample[0].cpu().detach().numpy(), pred_noise[0].cpu().detach().numpy()
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
@@ -878,7 +937,7 @@ class ModelInterface(object):
         with torch.no_grad(), self._ema_or_null_scope(use_ema):
             for j in range(int(n_draws)):
                 draws.append(self.sample(None, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, eta=eta, seed=int(seed) + j,
-                                         window_ids=window_ids, shape=tuple(x_0.shape), **_sampler_kwargs(sampler, clip_x0)))
+                                         window_ids=window_ids, shape=tuple(x_0.shape), **_sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1)))
         first = (draws[0][0][0].cpu().numpy(), draws[0][1][0].cpu().numpy())
         if int(n_draws) == 1:
             return first
@@ -891,14 +950,17 @@ class ModelInterface(object):
     plot_single_prediction = log_single_prediction
 
 
-def _sampler_kwargs(sampler, clip_x0):
-    """The two step-consistent-sampler options as keyword arguments of ``sample`` -- none at the defaults, so that a subclass whose
-    ``sample`` predates them is still called as it always was."""
+def _sampler_kwargs(sampler, clip_x0, guidance_scale=None, null_ms1=0.0):
+    """The step-consistent-sampler and guidance options as keyword arguments of ``sample`` -- none at the defaults, so that a subclass
+    whose ``sample`` predates them is still called as it always was."""
     kw = {}
     if sampler != "reference":
         kw["sampler"] = sampler
     if clip_x0 is not None:
         kw["clip_x0"] = clip_x0
+    if guidance_scale is not None:
+        kw["guidance_scale"] = guidance_scale
+        kw["null_ms1"] = null_ms1
     return kw
 
 

@@ -56,7 +56,8 @@ const char* dq_last_error(void);
  * dq_tfm_attn_form, dq_tfm_attn_fwd, dq_tfm_sample_workspace_bytes, dq_tfm_sample; the wide bottleneck alone: dq_wide_im2col3,
  * dq_wide_col2im3, dq_wide_repitch, dq_wide_norm_fwd, dq_wide_norm_bwd, dq_wide_norm_bwd_scratch_floats, dq_wide_rowsum, dq_wide_sum_b,
  * dq_debug_wide_mid_fwd, dq_debug_wide_mid_bwd; the transformer's held-out evaluation: dq_tfm_eval_workspace_bytes, dq_tfm_eval_step,
- * dq_q_sample_repeats, dq_mse_per_window_repeats, dq_tfm_kv_broadcast). */
+ * dq_q_sample_repeats, dq_mse_per_window_repeats, dq_tfm_kv_broadcast; classifier-free guidance: DQ_UPDATE_*, dq_guided_update,
+ * dq_ms1_cond_drop, dq_ddim_sample_guided). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -343,6 +344,53 @@ int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_
                           const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
                           int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
                           const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0);
+
+/* ---- classifier-free guidance on MS1 (no reference counterpart) ------------------------------
+ * MS1 is the one input that names the component to extract (the mixture is the same whichever precursor is asked for).  A network trained
+ * with its MS1 randomly replaced by a null (dq_ms1_cond_drop) has a conditional output c and an unconditional output u; the guided sampler
+ * runs every update on g = u + w (c - u): one fp32 subtraction and one fused multiply-add per element inside the update kernels, the same
+ * rule for DQ_PRED_EPS and DQ_PRED_X0 (guidance commutes with the affine map between them).  w = 1 is the conditional model, w = 0 the
+ * unconditional one, w > 1 pushes towards the component MS1 names.  The null is a CONSTANT raw MS1 value in every element, normalised like
+ * real MS1: no learned token, the checkpoint layout stays the reference's.
+ *
+ * dq_guided_update: one guided update on caller-supplied tensors.  kind: which of the four updates the sampling loop runs; coef_dev: the
+ * layout of that kind's stand-alone entry -- DQ_UPDATE_DDIM 4 floats [sa, sb, sap, sbp] (dq_ddim_step / dq_ddim_step_x0), DQ_UPDATE_STOCHASTIC 5
+ * floats [sa, sb, sap, c, sigma] (dq_ddim_step_sto; needs seed_dev; window_ids_dev nullable: 0 .. B-1; draw as there), DQ_UPDATE_SOLVER_1 /
+ * DQ_UPDATE_SOLVER_2M 5 floats [sa, sb, cx, c0, c1] (dq_solver_step; clip_x0 > 0 clamps the guided x0; _2M reads (c1 != 0) and writes x0_hist,
+ * _1 ignores it).  net_c / net_u: the conditional / unconditional network outputs (B, per_window).  x_prev, and x_mirror when non-NULL,
+ * receive the same values; eps_out (nullable) the guided eps ((x_t - sa x0) / sb under DQ_PRED_X0 and for a clamped element, else g).
+ * x0_hist, clip_x0, window_ids_dev, seed_dev and draw are ignored by the kinds that do not use them.  x_prev may alias x_t, eps_out net_c,
+ * net_u net_c (then every output is the unguided entry's bit for bit).  Any sizes; tensors 4-byte aligned (16-byte accesses when
+ * per_window % 4 == 0 -- B * per_window % 4 == 0 for the kinds without noise -- and all are 16-byte aligned).  Refused before any launch: a
+ * NULL among x_t, net_c, net_u, x_prev, coef_dev (seed_dev: stochastic; x0_hist: 2M), an unknown kind or pred_type, w negative, NaN or
+ * infinite. */
+enum { DQ_UPDATE_DDIM = 0, DQ_UPDATE_STOCHASTIC = 1, DQ_UPDATE_SOLVER_1 = 2, DQ_UPDATE_SOLVER_2M = 3 };
+int dq_guided_update(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
+                     float* eps_out, const float* coef_dev, float w, float clip_x0, const int64_t* window_ids_dev, const uint64_t* seed_dev,
+                     int draw, int pred_type, int B, int64_t per_window, void* stream);
+/* Conditioning dropout (k_cond_drop.hip): ms1_out (B, per_ms1) = ms1_in, with window b replaced as a whole by null_value iff r2 < thresh.
+ * r2: the THIRD output word of Philox4x32-10 on counter (0, draw, id lo, id hi) under key (seed lo, seed hi), id = window_ids_dev[b] (NULL:
+ * b); the normals above use words 0 and 1 only, so the decision never correlates with a noise draw under the same seed.  thresh = (uint32)
+ * floor(p 2^32), in double; 0 <= p < 1 (anything else, NaN included: refused); p == 0 drops nothing.  A kept window is a bit copy;
+ * ms1_out may alias ms1_in.  seed_dev: 1 uint64 of DEVICE memory; draw >= 0; tensors 4-byte aligned (16-byte accesses when both are
+ * 16-byte aligned).  A window decides alone: the same under its id in any batch. */
+int dq_ms1_cond_drop(const float* ms1_in, float* ms1_out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, double p,
+                     float null_value, int B, int64_t per_ms1, void* stream);
+/* dq_ddim_sample_solver sampling from g: every option of that call (eta, seed, ids, x_T = NULL, the three samplers, clip_x0, trajectories,
+ * the captured step) with guidance_scale = w and the null's raw MS1 value null_ms1.  The arena and the forward run at 2B windows -- rows
+ * [0, B) carry ms1_cond, rows [B, 2B) null_ms1 in every element; both see the same mixture and the same x -- so workspace_bytes must be
+ * at least dq_unet_workspace_bytes(plan, 2 * B, RT, 0).  One forward and one update launch per step: the update runs behind the forward
+ * (never in the head launch) in its guided form (dq_guided_update) over the B windows of the first half and keeps the second half's x
+ * equal to the first's.  x_T, the outputs and the trajectories are B windows; traj_eps holds the guided eps.  w travels by value: captured
+ * steps are cached by it (the same w replays, another w captures again).  Refusals as dq_ddim_sample_solver's, in its order, then
+ * guidance_scale negative, NaN or infinite.  guidance_scale = 1 is the conditional model at twice the cost: callers wanting that call
+ * dq_ddim_sample_solver. */
+int dq_ddim_sample_guided(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                          const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                          const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                          int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                          const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, float guidance_scale,
+                          float null_ms1);
 
 /* ---- batch formation from an HBM-resident dataset (the step right before the hot path) ------------
  * Replaces, for B (window 1, window 2) pairs, DIAMSDataset.__getitem__'s min-max normalisation (utils/data_loader.py:70-79:
