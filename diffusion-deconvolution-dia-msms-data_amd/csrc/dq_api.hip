@@ -160,28 +160,41 @@ int dq_mse_loss_weighted_fwd_bwd(const float* pred, const float* target, float t
                             t, per_sample, target_mul, target_add);
 }
 
+// The four AdamW entries: one launch_adamw (k_adamw.hip), the host's scalars or the device's, with or without the average
+static AdamwStep adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch, float grad_scale,
+                            float max_norm, double beta1, double beta2, double eps, double weight_decay, float* gnorm_out) {
+  AdamwStep a;
+  a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = n; a.partials = scratch; a.gscale = grad_scale; a.max_norm = max_norm;
+  a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay; a.gnorm_out = gnorm_out;
+  return a;
+}
+
 int dq_adamw_clip_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch,
                        float grad_scale, float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
                        int step, float* gnorm_out, void* stream) {
   DQ_REQUIRE(params && grads && exp_avg && exp_avg_sq && scratch, "dq_adamw_clip_step: null argument");
-  return launch_adamw_clip(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, lr, beta1, beta2, eps,
-                           weight_decay, step, gnorm_out, (hipStream_t)stream);
+  AdamwStep a = adamw_step(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, beta1, beta2, eps, weight_decay, gnorm_out);
+  a.lr = lr; a.step = step;
+  return launch_adamw(a, (hipStream_t)stream);
 }
 
 int dq_adamw_clip_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch, float grad_scale,
                            float max_norm, const float* lr_dev, double beta1, double beta2, double eps, double weight_decay, int* step_dev,
                            float* gnorm_out, void* stream) {
   DQ_REQUIRE(params && grads && exp_avg && exp_avg_sq && scratch && lr_dev && step_dev, "dq_adamw_clip_step_dev: null argument");
-  return launch_adamw_clip_dev(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, lr_dev, beta1, beta2, eps, weight_decay,
-                               step_dev, gnorm_out, (hipStream_t)stream);
+  AdamwStep a = adamw_step(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, beta1, beta2, eps, weight_decay, gnorm_out);
+  a.lr_dev = lr_dev; a.step_dev = step_dev;
+  return launch_adamw(a, (hipStream_t)stream);
 }
 
 int dq_adamw_clip_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch,
                            float grad_scale, float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
                            int step, float* gnorm_out, float* ema, float ema_decay, int ema_warmup, void* stream) {
   DQ_REQUIRE(params && grads && exp_avg && exp_avg_sq && scratch, "dq_adamw_clip_ema_step: null argument");
-  return launch_adamw_clip_ema(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, lr, beta1, beta2, eps, weight_decay,
-                               step, gnorm_out, ema, ema_decay, ema_warmup, (hipStream_t)stream);
+  DQ_REQUIRE(ema, "adamw + ema: the EMA buffer is null");
+  AdamwStep a = adamw_step(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, beta1, beta2, eps, weight_decay, gnorm_out);
+  a.lr = lr; a.step = step; a.ema = ema; a.ema_decay = ema_decay; a.ema_warmup = ema_warmup;
+  return launch_adamw(a, (hipStream_t)stream);
 }
 
 int dq_adamw_clip_ema_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float* scratch,
@@ -189,8 +202,10 @@ int dq_adamw_clip_ema_step_dev(float* params, const float* grads, float* exp_avg
                                double weight_decay, int* step_dev, float* gnorm_out, float* ema, float ema_decay, int ema_warmup,
                                void* stream) {
   DQ_REQUIRE(params && grads && exp_avg && exp_avg_sq && scratch && lr_dev && step_dev, "dq_adamw_clip_ema_step_dev: null argument");
-  return launch_adamw_clip_ema_dev(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, lr_dev, beta1, beta2, eps,
-                                   weight_decay, step_dev, gnorm_out, ema, ema_decay, ema_warmup, (hipStream_t)stream);
+  DQ_REQUIRE(ema, "adamw + ema: the EMA buffer is null");
+  AdamwStep a = adamw_step(params, grads, exp_avg, exp_avg_sq, n, scratch, grad_scale, max_norm, beta1, beta2, eps, weight_decay, gnorm_out);
+  a.lr_dev = lr_dev; a.step_dev = step_dev; a.ema = ema; a.ema_decay = ema_decay; a.ema_warmup = ema_warmup;
+  return launch_adamw(a, (hipStream_t)stream);
 }
 
 int dq_set_option(const char* key, int64_t value) {

@@ -3,7 +3,7 @@
 // from the conditional output c and the unconditional output u, in fp32: one subtraction, then ONE fused multiply-add (fmaf is asked for
 // by name; the library is built with -ffp-contract=off, so the compiler contracts nothing on its own and nothing else in the update
 // changes).  c == u gives g == u exactly for every finite w (w * 0 + u), w == 0 gives u, w == 1 gives c up to the rounding of (c - u) + u.
-// The update kernels (k_stream.hip, k_noise.hip, k_solver.hip) run their arithmetic on g in place of the network output, for both
+// The update kernel (k_step_update, k_update.hip) runs its arithmetic on g in place of the network output, for both
 // objectives: guidance commutes with the affine map between eps and x0.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -11,37 +11,6 @@ constexpr int MSE_MAX_BLOCKS = 1024;  // size of the partial-sum scratch used by
 // ---- k_stream.hip
 int launch_q_sample(const float* alpha_bars, const float* x0, const int64_t* t, const float* noise, float* x_t, int B,
                     int64_t per_sample, int normalize, hipStream_t s);
-int launch_ddim_step(const float* x_t, const float* eps, float* x_prev, const float* coef_dev, int64_t n, const int* step_ptr,
-                     hipStream_t s, int pred_x0 = 0, float* eps_out = nullptr);
-// x_prev may alias x_t (element-wise); step_ptr (nullable): row index into coef_dev; pred_x0: ``eps`` is the network's x0
-// prediction and the derived eps goes to eps_out (nullable)
-int launch_inc_step(int* p, hipStream_t s);
-// ---- k_noise.hip: Philox4x32-10 / Box-Muller normals keyed by (seed, window id, element, draw index); seed and ids (nullable: 0 .. B-1) in
-// device memory.  launch_ddim_step_sto: launch_ddim_step plus sigma * z (coef rows [sa, sb, sap, c], sigma one float per row; step_ptr
-// nullable: row index and draw index 1 + step on the device, else row 0 and `draw`)
-int launch_randn(float* out, const int64_t* ids, const uint64_t* seed_dev, int draw, int B, int64_t per_window, hipStream_t s);
-int launch_ddim_step_sto(const float* x_t, const float* eps, float* x_prev, float* eps_out, const float* coef_dev, const float* sigma_dev,
-                         const int64_t* ids, const uint64_t* seed_dev, int draw, int pred_x0, int B, int64_t per_window,
-                         const int* step_ptr, hipStream_t s);
-// ---- k_solver.hip: x_prev = cx*x + c0*x0 + c1*hist over rows [sa, sb, cx, c0] of coef_dev and c1_dev (one float per row; step_ptr nullable:
-// row index on the device); x0 clamped to [-clip, clip] when clip > 0; hist (nullable when every c1 is 0) receives x0; eps_out nullable;
-// x_prev may alias x_t, eps_out may alias net.  16-byte accesses when n % 4 == 0 and every tensor is 16-byte aligned.
-int launch_solver_step(const float* x_t, const float* net, float* x_prev, float* hist, float* eps_out, const float* coef_dev,
-                       const float* c1_dev, float clip, int pred_x0, int64_t n, const int* step_ptr, hipStream_t s);
-// ---- the guided forms of the three updates (dq_guide.h): the same arithmetic on g = net_u + w (net_c - net_u) in place of
-// the network output; x_mirror (nullable) receives x_prev too; eps_out (nullable) the guided eps under either objective.  Any count and
-// any 4-byte aligned pointers (16-byte accesses when the counts are multiples of 4 and every pointer is 16-byte aligned).
-int launch_ddim_step_guided(const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* eps_out,
-                            const float* coef_dev, float w, int pred_x0, int64_t n, const int* step_ptr, hipStream_t s);
-int launch_ddim_step_sto_guided(const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* eps_out,
-                                const float* coef_dev, const float* sigma_dev, const int64_t* ids, const uint64_t* seed_dev, int draw, float w,
-                                int pred_x0, int B, int64_t per_window, const int* step_ptr, hipStream_t s);
-int launch_solver_step_guided(const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* hist,
-                              float* eps_out, const float* coef_dev, const float* c1_dev, float clip, float w, int pred_x0, int64_t n,
-                              const int* step_ptr, hipStream_t s);
-// ---- k_cond_drop.hip: out (B, per) = in with window b replaced by null_value iff the third Philox word of (seed, id, draw) < floor(p 2^32)
-int launch_cond_drop(const float* in, float* out, const int64_t* ids, const uint64_t* seed_dev, int draw, double p, float null_value, int B,
-                     int64_t per, hipStream_t s);
 int launch_sample_finish(const float* x, const float* ms2_cond, float* out_x, float* out_noise, int64_t n, int normalize,
                          hipStream_t s);
 int launch_mse_fwd_bwd(const float* eps, const float* noise, float* loss_out, float* grad_out, float* partials, int64_t n,
@@ -50,34 +19,70 @@ int launch_mse_fwd_bwd(const float* eps, const float* noise, float* loss_out, fl
 // defer_sum: the kernel leaves its per-block partials, *defer_sum receives their count and loss_out is NOT written -- the caller runs
 // launch_sum_partials(partials, count, 1 / n, loss_out, stream) when it suits (dq_train_step: on the side stream)
 int launch_sum_partials(const float* partials, int count, float scale, float* out, hipStream_t s);
-// the MS1 term of train_step with ms1_loss_weight = w > 0 (k_stream.hip): on entry loss_out / grad hold the MSE part, on exit the
+// the MS1 term of train_step with ms1_loss_weight = w > 0: on entry loss_out / grad hold the MSE part, on exit the
 // combined loss (1 - w) * MSE + w * additional and its gradient w.r.t. the network output; x_t null = x0 objective;
 // scratch: 5 * B * RT + B floats
 int launch_ms1_loss(const float* out, const float* x_t, const float* ms1, float cm, float ca, const float* lw, const int64_t* t, float w,
                     int B, int RT, int MZ, float* grad, float* loss_out, float* scratch, hipStream_t s);
-int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm,
-                      double lr, double b1, double b2, double eps, double wd, int step, float* gnorm_out, hipStream_t s);
-
-// the same with lr and the step count in device memory (graph replay): increments *step_dev, then uses it
-int launch_adamw_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm,
-                          const float* lr_dev, double b1, double b2, double eps, double wd, int* step_dev, float* gnorm_out, hipStream_t s);
-
-// both steps with an exponential moving average of the parameters updated in the same pass: ema <- ema + w_t (p_new - ema),
-// w_t = (float)(1 - beta_t), beta_t = min(ema_decay, (1 + t) / (10 + t)) with ema_warmup, ema_decay without (p, m, v, the norm: bit for bit
-// the results of the two above; the device variant keeps w_t at index 3 of its scalars)
-int launch_adamw_clip_ema(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm, double lr,
-                          double b1, double b2, double eps, double wd, int step, float* gnorm_out, float* ema, float ema_decay,
-                          int ema_warmup, hipStream_t s);
-int launch_adamw_clip_ema_dev(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm,
-                              const float* lr_dev, double b1, double b2, double eps, double wd, int* step_dev, float* gnorm_out, float* ema,
-                              float ema_decay, int ema_warmup, hipStream_t s);
-
-// held-out loss (k_stream.hip): per_window[b] = MSE of window b against target' = target * tm + ta, loss_out = mean_b lw[t_b] * MSE_b
+// held-out loss: per_window[b] = MSE of window b against target' = target * tm + ta, loss_out = mean_b lw[t_b] * MSE_b
 // (lw null: 1), fp64 sums in a fixed order; scratch: mse_per_window_scratch_bytes = 8 * B * ceil(per / MSE_PW_SLICE) bytes
 constexpr int MSE_PW_SLICE = 8192;  // elements of a window one block of k_mse_per_window sums
 int64_t mse_per_window_scratch_bytes(int B, int64_t per);
 int launch_mse_per_window(const float* out, const float* target, float tm, float ta, const float* lw, const int64_t* t, float* per_window,
                           float* loss_out, void* scratch, int64_t scratch_bytes, int B, int64_t per, hipStream_t s);
+int launch_axpy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst += src
+int launch_zero(float* dst, int64_t n, hipStream_t s);  // dst = 0 (a kernel, not a memset node)
+int launch_copy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst = src (a kernel, not a memcpy node)
+// ---- k_update.hip: the update of one sampling step, x_prev from x_t and the network output, for the three families
+//   DDIM        rows [sa, sb, sap, sbp] of coef (extra unused)
+//   STOCHASTIC  the same plus sigma * z: rows [sa, sb, sap, c], extra = sigma, one float per row; z from Philox4x32-10 / Box-Muller normals
+//               keyed by (seed, window id, element, draw index), seed and ids (nullable: 0 .. B-1) in device memory
+//   SOLVER      x_prev = cx*x + c0*x0 + c1*hist: rows [sa, sb, cx, c0], extra = c1, one float per row; x0 clamped to [-clip, clip] when
+//               clip > 0; hist (nullable when every c1 is 0) receives x0
+// step_ptr (nullable): the row index on the device (STOCHASTIC: and the draw index 1 + step), else row 0 and `draw`.  pred_x0: `net` is the
+// network's x0 prediction.  eps_out (nullable) receives the step's eps when it is not the network output itself (always, for a guided or
+// SOLVER step).  guided (dq_guide.h): the same arithmetic on g = net_u + w (net - net_u) in place of the network
+// output, x_mirror (nullable) receives x_prev too.  Element-wise: x_prev may alias x_t, eps_out the network output.  Any count and any
+// 4-byte aligned tensors, except that the unguided STOCHASTIC form wants per % 4 == 0 and 16-byte aligned tensors; 16-byte accesses iff
+// the count (STOCHASTIC: per) is a multiple of 4 and every tensor given is 16-byte aligned, one element per lane otherwise.
+enum class UpdateFamily { DDIM, STOCHASTIC, SOLVER };
+struct StepUpdateLaunch {
+  UpdateFamily family = UpdateFamily::DDIM;
+  bool guided = false;
+  int pred_x0 = 0;
+  const float* x_t = nullptr; const float* net = nullptr; const float* net_u = nullptr;
+  float* x_prev = nullptr; float* x_mirror = nullptr; float* hist = nullptr; float* eps_out = nullptr;
+  const float* coef = nullptr; const float* extra = nullptr;
+  const int64_t* ids = nullptr; const uint64_t* seed = nullptr; int draw = 0;
+  float clip = 0.f, w = 1.f;
+  int B = 0; int64_t per = 0;  // B windows of per elements (a plain count n: B = 1, per = n)
+  const int* step_ptr = nullptr;
+};
+int launch_update(const StepUpdateLaunch& a, hipStream_t s);
+int launch_inc_step(int* p, hipStream_t s);
+// ---- k_noise.hip: out (B, per_window) = the normals of draw index `draw` (the generator of the STOCHASTIC update above)
+int launch_randn(float* out, const int64_t* ids, const uint64_t* seed_dev, int draw, int B, int64_t per_window, hipStream_t s);
+// ---- k_cond_drop.hip: out (B, per) = in with window b replaced by null_value iff the third Philox word of (seed, id, draw) < floor(p 2^32)
+int launch_cond_drop(const float* in, float* out, const int64_t* ids, const uint64_t* seed_dev, int draw, double p, float null_value, int B,
+                     int64_t per, hipStream_t s);
+// ---- k_adamw.hip: global-norm clip + AdamW over flat buffers of n floats (partials: MSE_MAX_BLOCKS floats of scratch).  step_dev / lr_dev
+// null: lr and the step count t >= 1 are the host's; else both live in device memory (graph replay): *step_dev is incremented, then used,
+// lr_dev is a (hi, lo) float pair, and the step's scalars are kept at partials[MSE_MAX_BLOCKS - 8 ..].  ema (nullable): an exponential
+// moving average of the parameters updated in the same pass, ema <- ema + w_t (p_new - ema), w_t = (float)(1 - beta_t), beta_t =
+// min(ema_decay, (1 + t) / (10 + t)) with ema_warmup, ema_decay without (p, m, v, the norm: the same bits with and without it; the device
+// variant keeps w_t at index 3 of its scalars).  gnorm_out (nullable): the pre-clip norm.
+struct AdamwStep {
+  float* p = nullptr; const float* g = nullptr; float* m = nullptr; float* v = nullptr; float* ema = nullptr;
+  int64_t n = 0;
+  float* partials = nullptr;
+  float gscale = 1.f, max_norm = 0.f;
+  double lr = 0.0; int step = 0;                               // the host's scalars, or
+  const float* lr_dev = nullptr; int* step_dev = nullptr;    // the device's
+  double b1 = 0.0, b2 = 0.0, eps = 0.0, wd = 0.0;
+  float ema_decay = 0.f; int ema_warmup = 0;
+  float* gnorm_out = nullptr;
+};
+int launch_adamw(const AdamwStep& a, hipStream_t s);
 // ---- k_tfm_eval.hip: the two above over R repeats of B windows stacked repeat-major (sample n = r * B + b; x0 (B, per) shared by the
 // repeats, t (R, B)); noise / target nullable: drawn in the kernel at draw index first_draw + r from seed_dev and ids (nullable: 0 .. B-1).
 // per % 4 == 0 and 16-byte aligned tensors for the head.  The tail's target has Bt windows (B: shared by the repeats, R * B: one each);
@@ -98,10 +103,6 @@ constexpr int METRIC_COL_MOMENTS = 5;   // doubles per (column, scan chunk)
 int64_t recon_metrics_scratch_bytes(int B, int RT, int MZ);
 int launch_recon_metrics(const float* pred, const float* target, float* out, void* scratch, int64_t scratch_bytes, int B, int RT, int MZ,
                          hipStream_t s);
-
-int launch_axpy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst += src
-int launch_zero(float* dst, int64_t n, hipStream_t s);  // dst = 0 (a kernel, not a memset node)
-int launch_copy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst = src (a kernel, not a memcpy node)
 
 // ---- k_conv.hip
 enum ConvMode { CONV_S1 = 0, CONV_DOWN = 1, CONV_UP = 2 };  // stride-1 'same' | k4 s2 p1 | nearest x2 then k3 p1

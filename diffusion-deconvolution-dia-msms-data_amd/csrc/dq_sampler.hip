@@ -18,33 +18,18 @@ namespace dq {
 
 int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net_out, const float* net_u, float* x_out, float* x_mirror,
                        float* eps_out, int row, const int* step_ptr, const StepNoise& z, bool fused, hipStream_t s) {
-  const float* coef = u.coef + 4 * row;
-  const float* extra = u.extra + row;
-  const int64_t n = u.B * u.per;
-  if (u.guided) {  // (the same kernels' guided forms, never in the head launch)
-    switch (u.kind) {
-      case StepUpdate::SOLVER_1:
-      case StepUpdate::SOLVER_2M:
-        return launch_solver_step_guided(x, net_out, net_u, x_out, x_mirror, u.kind == StepUpdate::SOLVER_2M ? u.hist : nullptr, eps_out, coef, extra,
-                                         u.clip, u.w, u.px0, n, step_ptr, s);
-      case StepUpdate::STOCHASTIC:
-        return launch_ddim_step_sto_guided(x, net_out, net_u, x_out, x_mirror, eps_out, coef, extra, z.ids, z.seed, z.draw, u.w, u.px0, u.B, u.per,
-                                           step_ptr, s);
-      case StepUpdate::DDIM:
-        return launch_ddim_step_guided(x, net_out, net_u, x_out, x_mirror, eps_out, coef, u.w, u.px0, n, step_ptr, s);
-    }
-    return 0;
-  }
-  switch (u.kind) {
-    case StepUpdate::SOLVER_1:
-    case StepUpdate::SOLVER_2M:
-      return launch_solver_step(x, net_out, x_out, u.kind == StepUpdate::SOLVER_2M ? u.hist : nullptr, eps_out, coef, extra, u.clip, u.px0, n, step_ptr, s);
-    case StepUpdate::STOCHASTIC:
-      return launch_ddim_step_sto(x, net_out, x_out, eps_out, coef, extra, z.ids, z.seed, z.draw, u.px0, u.B, u.per, step_ptr, s);
-    case StepUpdate::DDIM:
-      return fused ? 0 : launch_ddim_step(x, net_out, x_out, coef, n, step_ptr, s, u.px0, eps_out);  // model.py:273-289
-  }
-  return 0;
+  if (fused && u.kind == StepUpdate::DDIM && !u.guided) return 0;  // (the head launch has done it; a guided update never rides there)
+  StepUpdateLaunch a;
+  a.family = u.kind == StepUpdate::DDIM ? UpdateFamily::DDIM : u.kind == StepUpdate::STOCHASTIC ? UpdateFamily::STOCHASTIC : UpdateFamily::SOLVER;
+  a.guided = u.guided; a.pred_x0 = u.px0;
+  a.x_t = x; a.net = net_out; a.net_u = u.guided ? net_u : nullptr;
+  a.x_prev = x_out; a.x_mirror = u.guided ? x_mirror : nullptr; a.eps_out = eps_out;
+  a.hist = u.kind == StepUpdate::SOLVER_2M ? u.hist : nullptr;  // (first order: no history)
+  a.coef = u.coef + 4 * row; a.extra = u.extra + row;
+  a.ids = z.ids; a.seed = z.seed; a.draw = z.draw;
+  a.clip = u.clip; a.w = u.w;
+  a.B = u.B; a.per = u.per; a.step_ptr = step_ptr;
+  return launch_update(a, s);  // model.py:273-289
 }
 
 int sampler_check(const char* who, bool args_ok, float eta, int sampler, float clip_x0, const int32_t* timesteps_host, int num_steps,
@@ -62,7 +47,7 @@ int sampler_check(const char* who, bool args_ok, float eta, int sampler, float c
   if (sampler != DQ_SAMPLER_REFERENCE && num_steps <= 1024)  // (a step count out of range is the caller's refusal: its list is not read)
     for (int i = 1; i < num_steps; ++i)
       DQ_REQUIRE(timesteps_host[i] < timesteps_host[i - 1], w + ": the timesteps of this sampler must be strictly decreasing");
-  // the update: k_solver_step behind the forward (2M, or a clamped x0 at first order); else the reference's kernels over this sampler's table
+  // the update: the Solver family (k_update.hip) behind the forward (2M, or a clamped x0 at first order); else the reference's kernels over this sampler's table
   out->kind = sampler == DQ_SAMPLER_DPMPP_2M ? StepUpdate::SOLVER_2M : clip ? StepUpdate::SOLVER_1 : sto ? StepUpdate::STOCHASTIC : StepUpdate::DDIM;
   out->sto = sto; out->clip = clip; out->clip_x0 = clip ? clip_x0 : 0.f;
   DQ_REQUIRE(have_seed || (have_xT && !sto), w + ": eta > 0 and a null x_T need the seed (device memory)");
@@ -262,18 +247,30 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
   return eager_steps(loop, traj_x, traj_eps, window_ids_dev, seed_dev, s);
 }
 
+// The stand-alone updates: one step over caller-supplied tensors, row 0 of coef_dev (with sigma / c1 as a fifth float behind it); a plain
+// element count n is one window of n elements
+StepUpdateLaunch one_update(UpdateFamily family, int pred_x0, const float* x_t, const float* net, float* x_prev, float* eps_out,
+                                   const float* coef_dev, int B, int64_t per) {
+  StepUpdateLaunch a;
+  a.family = family; a.pred_x0 = pred_x0;
+  a.x_t = x_t; a.net = net; a.x_prev = x_prev; a.eps_out = eps_out;
+  a.coef = coef_dev; a.extra = coef_dev + 4;
+  a.B = B; a.per = per;
+  return a;
+}
+
 }  // namespace
 
 extern "C" {
 
 int dq_ddim_step(const float* x_t, const float* eps, float* x_prev, const float* coef_dev, int64_t n, void* stream) {
-  return launch_ddim_step(x_t, eps, x_prev, coef_dev, n, nullptr, (hipStream_t)stream);
+  return launch_update(one_update(UpdateFamily::DDIM, 0, x_t, eps, x_prev, nullptr, coef_dev, 1, n), (hipStream_t)stream);
 }
 
 int dq_ddim_step_x0(const float* x_t, const float* x0_pred, float* x_prev, float* eps_out, const float* coef_dev, int64_t n,
                     void* stream) {
   DQ_REQUIRE(x_t && x0_pred && x_prev && coef_dev, "dq_ddim_step_x0: null argument");
-  return launch_ddim_step(x_t, x0_pred, x_prev, coef_dev, n, nullptr, (hipStream_t)stream, 1, eps_out);
+  return launch_update(one_update(UpdateFamily::DDIM, 1, x_t, x0_pred, x_prev, eps_out, coef_dev, 1, n), (hipStream_t)stream);
 }
 
 int dq_randn(float* out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int B, int64_t per_window, void* stream) {
@@ -285,16 +282,20 @@ int dq_ddim_step_sto(const float* x_t, const float* net_out, float* x_prev, floa
                      void* stream) {
   DQ_REQUIRE(x_t && net_out && x_prev && coef_dev && seed_dev, "dq_ddim_step_sto: null argument");
   DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_ddim_step_sto: Unknown pred_type");
-  return launch_ddim_step_sto(x_t, net_out, x_prev, pred_type == DQ_PRED_X0 ? eps_out : nullptr, coef_dev, coef_dev + 4, window_ids_dev,
-                              seed_dev, draw, pred_type == DQ_PRED_X0, B, per_window, nullptr, (hipStream_t)stream);
+  // (refused by launch_update: a per-window count that is no multiple of 4, tensors that are not 16-byte aligned)
+  StepUpdateLaunch a = one_update(UpdateFamily::STOCHASTIC, pred_type == DQ_PRED_X0, x_t, net_out, x_prev, pred_type == DQ_PRED_X0 ? eps_out : nullptr,
+                                  coef_dev, B, per_window);
+  a.ids = window_ids_dev; a.seed = seed_dev; a.draw = draw;
+  return launch_update(a, (hipStream_t)stream);
 }
 
 int dq_solver_step(const float* x_t, const float* net_out, float* x_prev, float* x0_hist, float* eps_out, const float* coef_dev, float clip_x0,
                    int pred_type, int64_t n, void* stream) {
   DQ_REQUIRE(x_t && net_out && x_prev && coef_dev, "dq_solver_step: null argument");
   DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_solver_step: Unknown pred_type");
-  return launch_solver_step(x_t, net_out, x_prev, x0_hist, eps_out, coef_dev, coef_dev + 4, clip_x0, pred_type == DQ_PRED_X0, n, nullptr,
-                            (hipStream_t)stream);
+  StepUpdateLaunch a = one_update(UpdateFamily::SOLVER, pred_type == DQ_PRED_X0, x_t, net_out, x_prev, eps_out, coef_dev, 1, n);
+  a.hist = x0_hist; a.clip = clip_x0;
+  return launch_update(a, (hipStream_t)stream);
 }
 
 int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,

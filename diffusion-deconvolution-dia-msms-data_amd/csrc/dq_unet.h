@@ -43,7 +43,7 @@ struct Arena {
   std::vector<LevelBuf> downs, ups;
   int64_t mid_in, xn, qv, kk, o, lse, delta, attn_out, mid_back, eps, partials, head_part, loss, coef, xa, xb, wg, wg_floats, la_part, la_part_floats, ts_tab, step, c2_stage, c1_stage, wtmp, la_prep, wimg, timg, bb_part, bb_part_floats, ms1_scratch;
   int64_t ms1_wpart = 0, ms1_wpart_floats = 0;  // attn_cond_channels > 1: the slots of k_ms1_feat_wgrad
-  // stochastic sampling (eta > 0; k_noise.hip): sigma per step beside `coef`; the seed (uint64) and the window ids (B int64) staged at fixed
+  // stochastic sampling (eta > 0; k_update.hip, k_noise.hip): sigma per step beside `coef`; the seed (uint64) and the window ids (B int64) staged at fixed
   // addresses for the captured step.  Last in the arena: every other offset is what it was without them.
   int64_t sigma = 0, seed_stage = 0, ids_stage = 0;
   ResBuf mid1, mid2, fin;
@@ -55,11 +55,11 @@ struct Arena {
 void layout_arena(const Plan& p, int B, int RT, Arena& a);
 
 // The update of one sampling step (dq_sampler.hip): DDIM is the deterministic update (eta == 0; the reference and the strided table alike), in
-// the head launch or k_ddim_step behind it; STOCHASTIC k_ddim_step_sto (eta > 0); SOLVER_1 / SOLVER_2M k_solver_step without / with the x0
+// the head launch or k_update.hip's Ddim family behind it; STOCHASTIC its Sto family (eta > 0); SOLVER_1 / SOLVER_2M its Solver family without / with the x0
 // history (a clamped x0 at first order / DPM-Solver++(2M))
 enum class StepUpdate { DDIM, STOCHASTIC, SOLVER_1, SOLVER_2M };
 
-// Everything a captured sampling step has baked into its kernel arguments or its dispatch.  clip: the clamp of k_solver_step (0: off);
+// Everything a captured sampling step has baked into its kernel arguments or its dispatch.  clip: the clamp of the Solver update (0: off);
 // guidance: the scale the guided update takes by value (< 0: not a guided step; B is then the caller's, not the doubled, batch);
 // opt_epoch: options_epoch() at capture time (a dq_set_option call may change the dispatch)
 struct StepKey {

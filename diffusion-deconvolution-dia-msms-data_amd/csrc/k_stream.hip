@@ -1,11 +1,8 @@
-// Streaming (HBM-bound) kernels of the DDIM process: q_sample (K0), DDIM update (K9), MSE loss + its
-// gradient (K10), global-norm clip + AdamW on the flat parameter buffer (K11).
-// Reference arithmetic: dquartic/model/model.py:239-242 (q_sample), :265-289 (p_sample update),
-// :319-322 (sample epilogue), :361 (mse_loss); dquartic/model/model_interface.py:1121-1122
-// (clip_grad_norm_(10.0) + AdamW with torch defaults).
-// All kernels: 16 B per lane, grid-stride, no LDS.  Algorithmic bytes per element are stated per kernel.
+// Streaming (HBM-bound) kernels of the DDIM process: q_sample (K0), the sample epilogue, MSE loss + its gradient (K10), the held-out
+// per-window MSE and the MS1 term of train_step.  (The sampler updates, K9: k_update.hip; clip + AdamW, K11: k_adamw.hip.)
+// Reference arithmetic: dquartic/model/model.py:239-242 (q_sample), :319-322 (sample epilogue), :361 (mse_loss), :364-402 (the MS1 term).
+// The element-wise kernels: 16 B per lane, grid-stride, no LDS.  Algorithmic bytes per element are stated per kernel.
 #include "dq_common.h"
-#include "dq_guide.h"
 #include "dq_kernels.h"
 #include <algorithm>
 #include <cmath>
@@ -58,142 +55,6 @@ int launch_q_sample(const float* alpha_bars, const float* x0, const int64_t* t, 
   if (total == 0) return 0;
   const int grid = (int)std::min<int64_t>(cdiv(total, 256), 2048);
   hipLaunchKernelGGL(k_q_sample, dim3(grid), dim3(256), 0, s, alpha_bars, x0, t, noise, x_t, B, per4, normalize);
-  DQ_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---- K9: x0 = (x_t - sb*eps)/sa ; x_prev = sap*x0 + sbp*eps (t>0) else x0 : 12 B / element (guided, k_ddim_step_g: 20 B / element)
-// ``coef`` is a device table of 4 floats per step [sa, sb, sap, sbp]; sap < 0 marks the t == 0 step.
-// PRED_X0 (model.py:274-278): ``eps`` holds the network's x0 prediction, eps = (x_t - sa*x0)/sb is derived (and written to
-// eps_out when given: p_sample returns it).
-struct DdimRow { float sa, sb, sap, sbp; bool last; };
-
-__device__ __forceinline__ DdimRow ddim_row(const float* coef, const int* step_ptr) {
-  if (step_ptr) coef += 4 * step_ptr[0];  // graph replay: this step's row of the coefficient table
-  return DdimRow{coef[0], coef[1], coef[2], coef[3], coef[2] < 0.f};
-}
-
-// One element: x_prev from x and the network output v (or, guided, from g in its place: dq_guide.h); the step's eps by reference
-template <bool PRED_X0>
-__device__ __forceinline__ float ddim_elem(const DdimRow& r, float x, float v, float& ep) {
-  float x0;
-  if (PRED_X0) { x0 = v; ep = (x - r.sa * x0) / r.sb; }
-  else         { ep = v; x0 = (x - r.sb * ep) / r.sa; }
-  return r.last ? x0 : r.sap * x0 + r.sbp * ep;
-}
-
-template <bool PRED_X0>
-__global__ void __launch_bounds__(256) k_ddim_step(const float* __restrict__ x_t, const float* __restrict__ eps,
-                                                   float* __restrict__ x_prev, float* __restrict__ eps_out,
-                                                   const float* __restrict__ coef, int64_t n4, const int* __restrict__ step_ptr) {
-  const DdimRow r = ddim_row(coef, step_ptr);
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 x = reinterpret_cast<const float4*>(x_t)[i];
-    const float4 e = reinterpret_cast<const float4*>(eps)[i];
-    const float xv[4] = {x.x, x.y, x.z, x.w}, ev[4] = {e.x, e.y, e.z, e.w};
-    float ov[4], dv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ov[j] = ddim_elem<PRED_X0>(r, xv[j], ev[j], dv[j]);
-    reinterpret_cast<float4*>(x_prev)[i] = make_float4(ov[0], ov[1], ov[2], ov[3]);
-    if (PRED_X0 && eps_out) reinterpret_cast<float4*>(eps_out)[i] = make_float4(dv[0], dv[1], dv[2], dv[3]);
-  }
-}
-
-// an element count that is no multiple of 4: the same expressions, one element per lane and step
-template <bool PRED_X0>
-__global__ void __launch_bounds__(256) k_ddim_step_1(const float* __restrict__ x_t, const float* __restrict__ eps,
-                                                     float* __restrict__ x_prev, float* __restrict__ eps_out,
-                                                     const float* __restrict__ coef, int64_t n, const int* __restrict__ step_ptr) {
-  const DdimRow r = ddim_row(coef, step_ptr);
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float ep;
-    x_prev[i] = ddim_elem<PRED_X0>(r, x_t[i], eps[i], ep);
-    if (PRED_X0 && eps_out) eps_out[i] = ep;
-  }
-}
-
-// The guided update (dq_guide.h): ddim_elem on g = u + w (c - u) in place of the network output, the result to x_prev
-// and, when x_mirror is given, to x_mirror as well (the unconditional half's copy of x for the next forward); eps_out (nullable) receives
-// the guided eps under either objective.  20 B / element with the mirror (reads x, c, u; writes x_prev, x_mirror), + 4 with eps_out.
-// Element-wise: x_prev may alias x_t, eps_out may alias net_c (and net_u net_c): no __restrict__ on the tensors.
-template <bool PRED_X0>
-__global__ void __launch_bounds__(256) k_ddim_step_g(const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror,
-                                                     float* eps_out, const float* __restrict__ coef, float w, int64_t n4,
-                                                     const int* __restrict__ step_ptr) {
-  const DdimRow r = ddim_row(coef, step_ptr);
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 x = reinterpret_cast<const float4*>(x_t)[i];
-    const float4 c = reinterpret_cast<const float4*>(net_c)[i];
-    const float4 u = reinterpret_cast<const float4*>(net_u)[i];
-    const float xv[4] = {x.x, x.y, x.z, x.w}, cv[4] = {c.x, c.y, c.z, c.w}, uv[4] = {u.x, u.y, u.z, u.w};
-    float ov[4], dv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ov[j] = ddim_elem<PRED_X0>(r, xv[j], guide(cv[j], uv[j], w), dv[j]);
-    const float4 o = make_float4(ov[0], ov[1], ov[2], ov[3]);
-    reinterpret_cast<float4*>(x_prev)[i] = o;
-    if (x_mirror) reinterpret_cast<float4*>(x_mirror)[i] = o;
-    if (eps_out) reinterpret_cast<float4*>(eps_out)[i] = make_float4(dv[0], dv[1], dv[2], dv[3]);
-  }
-}
-
-// the same, one element per lane and step: counts that are no multiple of 4, pointers that are not 16-byte aligned
-template <bool PRED_X0>
-__global__ void __launch_bounds__(256) k_ddim_step_g_1(const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror,
-                                                       float* eps_out, const float* __restrict__ coef, float w, int64_t n,
-                                                       const int* __restrict__ step_ptr) {
-  const DdimRow r = ddim_row(coef, step_ptr);
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float ep;
-    const float o = ddim_elem<PRED_X0>(r, x_t[i], guide(net_c[i], net_u[i], w), ep);
-    x_prev[i] = o;
-    if (x_mirror) x_mirror[i] = o;
-    if (eps_out) eps_out[i] = ep;
-  }
-}
-
-__global__ void k_inc_step(int* p) { p[0] += 1; }
-
-int launch_inc_step(int* p, hipStream_t s) {
-  hipLaunchKernelGGL(k_inc_step, dim3(1), dim3(1), 0, s, p);
-  DQ_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_ddim_step(const float* x_t, const float* eps, float* x_prev, const float* coef_dev, int64_t n, const int* step_ptr,
-                     hipStream_t s, int pred_x0, float* eps_out) {
-  DQ_REQUIRE(n >= 0, "ddim_step: negative element count");
-  if (n == 0) return 0;
-  if (n % 4 != 0) {
-    const int grid1 = (int)std::min<int64_t>(cdiv(n, 256), 2048);
-    if (pred_x0) hipLaunchKernelGGL(k_ddim_step_1<true>, dim3(grid1), dim3(256), 0, s, x_t, eps, x_prev, eps_out, coef_dev, n, step_ptr);
-    else hipLaunchKernelGGL(k_ddim_step_1<false>, dim3(grid1), dim3(256), 0, s, x_t, eps, x_prev, eps_out, coef_dev, n, step_ptr);
-    DQ_LAUNCH_CHECK();
-    return 0;
-  }
-  const int grid = (int)std::min<int64_t>(cdiv(n / 4, 256), 2048);
-  if (pred_x0) hipLaunchKernelGGL(k_ddim_step<true>, dim3(grid), dim3(256), 0, s, x_t, eps, x_prev, eps_out, coef_dev, n / 4, step_ptr);
-  else hipLaunchKernelGGL(k_ddim_step<false>, dim3(grid), dim3(256), 0, s, x_t, eps, x_prev, eps_out, coef_dev, n / 4, step_ptr);
-  DQ_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_ddim_step_guided(const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* eps_out,
-                            const float* coef_dev, float w, int pred_x0, int64_t n, const int* step_ptr, hipStream_t s) {
-  DQ_REQUIRE(x_t && net_c && net_u && x_prev && coef_dev, "ddim_step_guided: null argument");
-  DQ_REQUIRE(n >= 0, "ddim_step_guided: negative element count");
-  const uintptr_t bits = (uintptr_t)x_t | (uintptr_t)net_c | (uintptr_t)net_u | (uintptr_t)x_prev | (uintptr_t)x_mirror | (uintptr_t)eps_out;
-  DQ_REQUIRE((bits & 3) == 0, "ddim_step_guided: tensors must be 4-byte aligned");
-  if (n == 0) return 0;
-  if (n % 4 != 0 || (bits & 15) != 0) {
-    const int grid1 = (int)std::min<int64_t>(cdiv(n, 256), 2048);
-    if (pred_x0) hipLaunchKernelGGL(k_ddim_step_g_1<true>, dim3(grid1), dim3(256), 0, s, x_t, net_c, net_u, x_prev, x_mirror, eps_out, coef_dev, w, n, step_ptr);
-    else hipLaunchKernelGGL(k_ddim_step_g_1<false>, dim3(grid1), dim3(256), 0, s, x_t, net_c, net_u, x_prev, x_mirror, eps_out, coef_dev, w, n, step_ptr);
-    DQ_LAUNCH_CHECK();
-    return 0;
-  }
-  const int grid = (int)std::min<int64_t>(cdiv(n / 4, 256), 2048);
-  if (pred_x0) hipLaunchKernelGGL(k_ddim_step_g<true>, dim3(grid), dim3(256), 0, s, x_t, net_c, net_u, x_prev, x_mirror, eps_out, coef_dev, w, n / 4, step_ptr);
-  else hipLaunchKernelGGL(k_ddim_step_g<false>, dim3(grid), dim3(256), 0, s, x_t, net_c, net_u, x_prev, x_mirror, eps_out, coef_dev, w, n / 4, step_ptr);
   DQ_LAUNCH_CHECK();
   return 0;
 }
@@ -574,264 +435,6 @@ int launch_ms1_loss(const float* out, const float* x_t, const float* ms1, float 
   DQ_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_ms1_apply, dim3((int)std::min<int64_t>(cdiv(rows * MZ, 256), 4096)), dim3(256), 0, s, grad, dsum, dmax, ramax, lw, t,
                      addl, w, x_t ? -1.0f : 1.0f, B, RT, MZ, loss_out);
-  DQ_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---- K11: global L2 norm (two-stage, deterministic) + clip + AdamW, flat buffers.
-// norm pass: 4 B / param ; update pass: 28 B / param (read p,g,m,v ; write p,m,v).
-__global__ void __launch_bounds__(256) k_sumsq(const float* __restrict__ g, int64_t n, float gscale, float* __restrict__ partials) {
-  // 16-byte loads, four independent accumulators, two loads in flight: the 764 MB gradient of the transformer (191 M parameters)
-  // is a bandwidth job; the scalar one-accumulator loop ran it at 2.3 TB/s
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  const int64_t n4 = (((uintptr_t)g & 15) == 0) ? n / 4 : 0;
-  const float4* g4 = reinterpret_cast<const float4*>(g);
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  for (; i + stride < n4; i += 2 * stride) {
-    const float4 u = g4[i], w = g4[i + stride];
-    a0 = fmaf(u.x * gscale, u.x * gscale, a0); a1 = fmaf(u.y * gscale, u.y * gscale, a1);
-    a2 = fmaf(u.z * gscale, u.z * gscale, a2); a3 = fmaf(u.w * gscale, u.w * gscale, a3);
-    a0 = fmaf(w.x * gscale, w.x * gscale, a0); a1 = fmaf(w.y * gscale, w.y * gscale, a1);
-    a2 = fmaf(w.z * gscale, w.z * gscale, a2); a3 = fmaf(w.w * gscale, w.w * gscale, a3);
-  }
-  for (; i < n4; i += stride) {
-    const float4 u = g4[i];
-    a0 = fmaf(u.x * gscale, u.x * gscale, a0); a1 = fmaf(u.y * gscale, u.y * gscale, a1);
-    a2 = fmaf(u.z * gscale, u.z * gscale, a2); a3 = fmaf(u.w * gscale, u.w * gscale, a3);
-  }
-  for (int64_t j = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n; j += stride) {
-    const float v = g[j] * gscale;
-    a0 = fmaf(v, v, a0);
-  }
-  float acc = (a0 + a1) + (a2 + a3);
-  __shared__ float red[4];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-__global__ void __launch_bounds__(256) k_adamw_clip(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, int64_t n, const float* __restrict__ partials,
-                                                    int n_partials, float gscale, float max_norm, float decay, float step_size,
-                                                    float one_m_b1, float b2, float one_m_b2, float eps, float bc2_sqrt,
-                                                    float* __restrict__ gnorm_out) {
-  // every block re-derives the same clip coefficient from the same partials in the same order
-  __shared__ float s_coef;
-  if (threadIdx.x < 64) {
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < n_partials; i += 64) acc += partials[i];
-    acc = wave_sum(acc);
-    if (threadIdx.x == 0) {
-      const float nrm = sqrtf(acc);
-      const float c = max_norm / (nrm + 1e-6f);  // torch clip_grad_norm_: coef clamped to 1
-      s_coef = (max_norm > 0.f) ? fminf(c, 1.0f) : 1.0f;
-      if (blockIdx.x == 0 && gnorm_out) gnorm_out[0] = nrm;
-    }
-  }
-  __syncthreads();
-  const float coef = s_coef * gscale;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * coef;
-    float pi = p[i] * decay;
-    const float mo = m[i];
-    const float mi = mo + one_m_b1 * (gi - mo);          // torch: exp_avg.lerp_(grad, 1 - beta1)
-    const float vi = fmaf(one_m_b2 * gi, gi, b2 * v[i]);  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= step_size * (mi / denom);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
-
-// ---- the same step with the step count and the learning rate in DEVICE memory: nothing about the call changes from one step to the next, so
-// a captured graph of it can be replayed (the host-side variant bakes lr and the bias corrections of step t into its launch arguments).
-// hyp (8 floats behind the partial sums): decay, step_size, bc2_sqrt -- formed in double from the device step counter exactly as
-// launch_adamw_clip forms them on the host; the counter is incremented first (step t = 1 for the first call).
-__global__ void k_adamw_hyper(int* __restrict__ step, const float* __restrict__ lr_dev, double b1, double b2, double wd, float* __restrict__ hyp) {
-  const int t = step[0] + 1;
-  step[0] = t;
-  const double lr = (double)lr_dev[0] + (double)lr_dev[1];  // (hi, lo) float pair: ~48 bits of the host's double lr
-  const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
-  hyp[0] = (float)(1.0 - lr * wd);
-  hyp[1] = (float)(lr / bc1);
-  hyp[2] = (float)sqrt(bc2);
-}
-__global__ void __launch_bounds__(256) k_adamw_clip_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, int64_t n, const float* __restrict__ partials, int n_partials,
-                                                        float gscale, float max_norm, const float* __restrict__ hyp, float one_m_b1, float b2,
-                                                        float one_m_b2, float eps, float* __restrict__ gnorm_out) {
-  __shared__ float s_coef;
-  if (threadIdx.x < 64) {
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < n_partials; i += 64) acc += partials[i];
-    acc = wave_sum(acc);
-    if (threadIdx.x == 0) {
-      const float nrm = sqrtf(acc);
-      const float c = max_norm / (nrm + 1e-6f);
-      s_coef = (max_norm > 0.f) ? fminf(c, 1.0f) : 1.0f;
-      if (blockIdx.x == 0 && gnorm_out) gnorm_out[0] = nrm;
-    }
-  }
-  __syncthreads();
-  const float coef = s_coef * gscale;
-  const float decay = hyp[0], step_size = hyp[1], bc2_sqrt = hyp[2];
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * coef;
-    float pi = p[i] * decay;
-    const float mo = m[i];
-    const float mi = mo + one_m_b1 * (gi - mo);
-    const float vi = fmaf(one_m_b2 * gi, gi, b2 * v[i]);
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= step_size * (mi / denom);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
-int launch_adamw_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm,
-                          const float* lr_dev, double b1, double b2, double eps, double wd, int* step_dev, float* gnorm_out, hipStream_t s) {
-  DQ_REQUIRE(n > 0 && lr_dev && step_dev, "adamw: need n > 0, the device learning rate and the device step counter");
-  const int grid = (int)std::min<int64_t>(cdiv(n, 256), MSE_MAX_BLOCKS - 8);
-  float* hyp = partials + (MSE_MAX_BLOCKS - 8);  // (the partial-sum scratch has MSE_MAX_BLOCKS floats)
-  hipLaunchKernelGGL(k_adamw_hyper, dim3(1), dim3(1), 0, s, step_dev, lr_dev, b1, b2, wd, hyp);
-  DQ_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sumsq, dim3(grid), dim3(256), 0, s, g, n, gscale, partials);
-  DQ_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_adamw_clip_dev, dim3(grid), dim3(256), 0, s, p, g, m, v, n, partials, grid, gscale, max_norm, hyp, (float)(1.0 - b1), (float)b2,
-                     (float)(1.0 - b2), (float)eps, gnorm_out);
-  DQ_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm,
-                      double lr, double b1, double b2, double eps, double wd, int step, float* gnorm_out, hipStream_t s) {
-  DQ_REQUIRE(n > 0 && step >= 1, "adamw: need n > 0 and step >= 1");
-  // (the same grid as the device-state variant above, which keeps 8 floats of the scratch for its scalars: the norm's partial sums are then
-  // taken in the same order by both, for any n)
-  const int grid = (int)std::min<int64_t>(cdiv(n, 256), MSE_MAX_BLOCKS - 8);
-  hipLaunchKernelGGL(k_sumsq, dim3(grid), dim3(256), 0, s, g, n, gscale, partials);
-  DQ_LAUNCH_CHECK();
-  const double bc1 = 1.0 - std::pow(b1, step), bc2 = 1.0 - std::pow(b2, step);
-  // scalar factors are formed in double like torch's Python-side arithmetic, then applied in fp32
-  hipLaunchKernelGGL(k_adamw_clip, dim3(grid), dim3(256), 0, s, p, g, m, v, n, partials, grid, gscale, max_norm,
-                     (float)(1.0 - lr * wd), (float)(lr / bc1), (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps,
-                     (float)std::sqrt(bc2), gnorm_out);
-  DQ_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---- K11 + EMA: the same step, and e <- e + w (p_new - e) from the p the update has just formed, in the same pass over the buffers
-// (36 B / param: the four reads and three writes above, plus one read and one write of e; a lerp over the flat buffer afterwards reads p
-// again: 40 B and a launch).  Per element the AdamW arithmetic is k_adamw_clip's expression for expression (-ffp-contract=off: no
-// contraction either way), so p, m, v are its results bit for bit; the EMA is one fp32 subtraction and one fmaf.
-__device__ __forceinline__ void adamw_ema_elem(float& p, float g, float& m, float& v, float& e, float coef, float decay, float step_size,
-                                               float one_m_b1, float b2, float one_m_b2, float eps, float bc2_sqrt, float ema_w) {
-  const float gi = g * coef;
-  float pi = p * decay;
-  const float mo = m;
-  const float mi = mo + one_m_b1 * (gi - mo);
-  const float vi = fmaf(one_m_b2 * gi, gi, b2 * v);
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  pi -= step_size * (mi / denom);
-  p = pi; m = mi; v = vi;
-  e = fmaf(ema_w, pi - e, e);
-}
-// hyp null: the step's scalars are the launch arguments (host variant); else hyp[0..3] = decay, step_size, bc2_sqrt, ema_w (device variant).
-// 16-byte accesses when all five buffers are 16-byte aligned (the way k_sumsq picks its path: the 191 M-parameter transformer's step is a
-// bandwidth job of 36 B / param), scalar accesses for the tail and for every other alignment.
-__global__ void __launch_bounds__(256) k_adamw_clip_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, float* __restrict__ e, int64_t n,
-                                                        const float* __restrict__ partials, int n_partials, float gscale, float max_norm,
-                                                        const float* __restrict__ hyp, float decay, float step_size, float bc2_sqrt,
-                                                        float ema_w, float one_m_b1, float b2, float one_m_b2, float eps,
-                                                        float* __restrict__ gnorm_out) {
-  __shared__ float s_coef;
-  if (threadIdx.x < 64) {
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < n_partials; i += 64) acc += partials[i];
-    acc = wave_sum(acc);
-    if (threadIdx.x == 0) {
-      const float nrm = sqrtf(acc);
-      const float c = max_norm / (nrm + 1e-6f);
-      s_coef = (max_norm > 0.f) ? fminf(c, 1.0f) : 1.0f;
-      if (blockIdx.x == 0 && gnorm_out) gnorm_out[0] = nrm;
-    }
-  }
-  __syncthreads();
-  const float coef = s_coef * gscale;
-  if (hyp) { decay = hyp[0]; step_size = hyp[1]; bc2_sqrt = hyp[2]; ema_w = hyp[3]; }
-  const bool aligned = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)e) & 15) == 0);
-  const int64_t n4 = aligned ? n / 4 : 0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int64_t first = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  float4* p4 = reinterpret_cast<float4*>(p); const float4* g4 = reinterpret_cast<const float4*>(g);
-  float4* m4 = reinterpret_cast<float4*>(m); float4* v4 = reinterpret_cast<float4*>(v); float4* e4 = reinterpret_cast<float4*>(e);
-  for (int64_t i = first; i < n4; i += stride) {
-    float4 pp = p4[i], mm = m4[i], vv = v4[i], ee = e4[i];
-    const float4 gg = g4[i];
-    adamw_ema_elem(pp.x, gg.x, mm.x, vv.x, ee.x, coef, decay, step_size, one_m_b1, b2, one_m_b2, eps, bc2_sqrt, ema_w);
-    adamw_ema_elem(pp.y, gg.y, mm.y, vv.y, ee.y, coef, decay, step_size, one_m_b1, b2, one_m_b2, eps, bc2_sqrt, ema_w);
-    adamw_ema_elem(pp.z, gg.z, mm.z, vv.z, ee.z, coef, decay, step_size, one_m_b1, b2, one_m_b2, eps, bc2_sqrt, ema_w);
-    adamw_ema_elem(pp.w, gg.w, mm.w, vv.w, ee.w, coef, decay, step_size, one_m_b1, b2, one_m_b2, eps, bc2_sqrt, ema_w);
-    p4[i] = pp; m4[i] = mm; v4[i] = vv; e4[i] = ee;
-  }
-  for (int64_t i = n4 * 4 + first; i < n; i += stride) {
-    float pi = p[i], mi = m[i], vi = v[i], ei = e[i];
-    adamw_ema_elem(pi, g[i], mi, vi, ei, coef, decay, step_size, one_m_b1, b2, one_m_b2, eps, bc2_sqrt, ema_w);
-    p[i] = pi; m[i] = mi; v[i] = vi; e[i] = ei;
-  }
-}
-
-// beta_t = min(beta, (1 + t) / (10 + t)) with warm-up, beta without; w_t = (float)(1 - beta_t), in double on the host and in k_adamw_ema_hyper
-__host__ __device__ inline float ema_weight(double beta, int warmup, int t) {
-  const double bt = warmup ? fmin(beta, (1.0 + (double)t) / (10.0 + (double)t)) : beta;
-  return (float)(1.0 - bt);
-}
-// k_adamw_hyper's three scalars (the same expressions) and the EMA weight behind them at hyp[3]
-__global__ void k_adamw_ema_hyper(int* __restrict__ step, const float* __restrict__ lr_dev, double b1, double b2, double wd, double ema_beta,
-                                  int ema_warmup, float* __restrict__ hyp) {
-  const int t = step[0] + 1;
-  step[0] = t;
-  const double lr = (double)lr_dev[0] + (double)lr_dev[1];
-  const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
-  hyp[0] = (float)(1.0 - lr * wd);
-  hyp[1] = (float)(lr / bc1);
-  hyp[2] = (float)sqrt(bc2);
-  hyp[3] = ema_weight(ema_beta, ema_warmup, t);
-}
-
-static bool ema_decay_ok(float beta) { return beta >= 0.f && beta < 1.f; }  // (false for NaN)
-
-int launch_adamw_clip_ema_dev(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm,
-                              const float* lr_dev, double b1, double b2, double eps, double wd, int* step_dev, float* gnorm_out, float* ema,
-                              float ema_decay, int ema_warmup, hipStream_t s) {
-  DQ_REQUIRE(n > 0 && lr_dev && step_dev, "adamw: need n > 0, the device learning rate and the device step counter");
-  DQ_REQUIRE(ema, "adamw + ema: the EMA buffer is null");
-  DQ_REQUIRE(ema_decay_ok(ema_decay), "adamw + ema: ema_decay must satisfy 0 <= ema_decay < 1");
-  const int grid = (int)std::min<int64_t>(cdiv(n, 256), MSE_MAX_BLOCKS - 8);
-  float* hyp = partials + (MSE_MAX_BLOCKS - 8);
-  hipLaunchKernelGGL(k_adamw_ema_hyper, dim3(1), dim3(1), 0, s, step_dev, lr_dev, b1, b2, wd, (double)ema_decay, ema_warmup, hyp);
-  DQ_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sumsq, dim3(grid), dim3(256), 0, s, g, n, gscale, partials);
-  DQ_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_adamw_clip_ema, dim3(grid), dim3(256), 0, s, p, g, m, v, ema, n, partials, grid, gscale, max_norm, hyp, 0.f, 0.f, 0.f,
-                     0.f, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, gnorm_out);
-  DQ_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_adamw_clip_ema(float* p, const float* g, float* m, float* v, int64_t n, float* partials, float gscale, float max_norm, double lr,
-                          double b1, double b2, double eps, double wd, int step, float* gnorm_out, float* ema, float ema_decay,
-                          int ema_warmup, hipStream_t s) {
-  DQ_REQUIRE(n > 0 && step >= 1, "adamw: need n > 0 and step >= 1");
-  DQ_REQUIRE(ema, "adamw + ema: the EMA buffer is null");
-  DQ_REQUIRE(ema_decay_ok(ema_decay), "adamw + ema: ema_decay must satisfy 0 <= ema_decay < 1");
-  const int grid = (int)std::min<int64_t>(cdiv(n, 256), MSE_MAX_BLOCKS - 8);
-  hipLaunchKernelGGL(k_sumsq, dim3(grid), dim3(256), 0, s, g, n, gscale, partials);
-  DQ_LAUNCH_CHECK();
-  const double bc1 = 1.0 - std::pow(b1, step), bc2 = 1.0 - std::pow(b2, step);
-  hipLaunchKernelGGL(k_adamw_clip_ema, dim3(grid), dim3(256), 0, s, p, g, m, v, ema, n, partials, grid, gscale, max_norm,
-                     (const float*)nullptr, (float)(1.0 - lr * wd), (float)(lr / bc1), (float)std::sqrt(bc2),
-                     ema_weight((double)ema_decay, ema_warmup, step), (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, gnorm_out);
   DQ_LAUNCH_CHECK();
   return 0;
 }

@@ -15,7 +15,7 @@
 namespace dq {
 
 // x_t[n] = sa * norm(x0[n % B]) + sb * z[n] with sa, sb from alpha_bars[t[n]]: k_q_sample's expressions in k_q_sample's order.  The sample of
-// float4 i is i / per4, the element 4 * (i % per4) + j (k_ddim_step_sto's indexing).
+// float4 i is i / per4, the element 4 * (i % per4) + j (the indexing of k_update.hip's Sto family).
 __global__ void __launch_bounds__(256) k_q_sample_repeats(const float* __restrict__ alpha_bars, const float* __restrict__ x0,
                                                           const int64_t* __restrict__ t, const float* __restrict__ noise,
                                                           const int64_t* __restrict__ ids, const uint64_t* __restrict__ seed_p, uint32_t first_draw,

@@ -157,8 +157,17 @@ class FlatAdamW(torch.optim.Optimizer):
                 raise ValueError(f"load_ema_state_dict: {name} has shape {tuple(src.shape)}, the network's is {tuple(shape)}")
             ema[o:o + math.prod(shape)].copy_(src.reshape(-1))
 
-    def _ema_args(self):
-        return N.ptr(self.ema_buffer()), float(self.ema_decay), 1 if self.ema_warmup else 0
+    def _native_step(self, flat, dev: bool):
+        """One optimiser call: ``dq_adamw_clip[_ema]_step[_dev]``.  The four entries take the same arguments but for the step's scalars
+        (``dev``: lr and step count from device memory, else the host's) and the average's three behind the norm."""
+        g = self.param_groups[0]
+        name = "dq_adamw_clip" + ("_ema" if self.ema_enabled else "") + "_step" + ("_dev" if dev else "")
+        lr = N.ptr(self._lr_dev) if dev else float(g["lr"])
+        step = N.ptr(self._step_dev) if dev else int(self._step)
+        ema = (N.ptr(self.ema_buffer()), float(self.ema_decay), 1 if self.ema_warmup else 0) if self.ema_enabled else ()
+        N.check(getattr(N.lib(), name)(N.ptr(flat), N.ptr(self.net.flat_grads()), N.ptr(self._m), N.ptr(self._v), flat.numel(), N.ptr(self._scratch),
+                                       float(self.grad_scale), float(self.max_norm), lr, float(g["betas"][0]), float(g["betas"][1]),
+                                       float(g["eps"]), float(g["weight_decay"]), step, N.ptr(self._gnorm), *ema, N.stream_ptr()), name)
 
     def _buffers(self):
         flat = self.net.flat_params
@@ -182,19 +191,8 @@ class FlatAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         flat = self._buffers()
-        grads = self.net.flat_grads()
-        g = self.param_groups[0]
         self._step += 1
-        if self.ema_enabled:
-            N.check(N.lib().dq_adamw_clip_ema_step(N.ptr(flat), N.ptr(grads), N.ptr(self._m), N.ptr(self._v), flat.numel(), N.ptr(self._scratch),
-                                                   float(self.grad_scale), float(self.max_norm), float(g["lr"]), float(g["betas"][0]),
-                                                   float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), int(self._step),
-                                                   N.ptr(self._gnorm), *self._ema_args(), N.stream_ptr()), "dq_adamw_clip_ema_step")
-            return None
-        N.check(N.lib().dq_adamw_clip_step(N.ptr(flat), N.ptr(grads), N.ptr(self._m), N.ptr(self._v), flat.numel(), N.ptr(self._scratch),
-                                           float(self.grad_scale), float(self.max_norm), float(g["lr"]), float(g["betas"][0]),
-                                           float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), int(self._step),
-                                           N.ptr(self._gnorm), N.stream_ptr()), "dq_adamw_clip_step")
+        self._native_step(flat, dev=False)
         return None  # (the per-parameter "step" entries are refreshed by state_dict(): 395 tensor constructions per step cost ~1 ms of host time)
 
     def state_dict(self):
@@ -221,21 +219,9 @@ class FlatAdamW(torch.optim.Optimizer):
         """The same update with the step count and lr read from device memory (``dq_adamw_clip_step_dev``): the call is identical from
         step to step, so it can sit in a captured graph.  ``count=False`` while a graph is being captured (the replay counts instead)."""
         flat = self._dev_state()
-        grads = self.net.flat_grads()
-        g = self.param_groups[0]
         if count:
             self._step += 1
-        if self.ema_enabled:
-            N.check(N.lib().dq_adamw_clip_ema_step_dev(N.ptr(flat), N.ptr(grads), N.ptr(self._m), N.ptr(self._v), flat.numel(),
-                                                       N.ptr(self._scratch), float(self.grad_scale), float(self.max_norm), N.ptr(self._lr_dev),
-                                                       float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                                                       N.ptr(self._step_dev), N.ptr(self._gnorm), *self._ema_args(), N.stream_ptr()),
-                    "dq_adamw_clip_ema_step_dev")
-            return None
-        N.check(N.lib().dq_adamw_clip_step_dev(N.ptr(flat), N.ptr(grads), N.ptr(self._m), N.ptr(self._v), flat.numel(), N.ptr(self._scratch),
-                                               float(self.grad_scale), float(self.max_norm), N.ptr(self._lr_dev), float(g["betas"][0]),
-                                               float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), N.ptr(self._step_dev),
-                                               N.ptr(self._gnorm), N.stream_ptr()), "dq_adamw_clip_step_dev")
+        self._native_step(flat, dev=True)
         return None
 
     def sync_step_dev(self):

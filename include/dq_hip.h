@@ -326,7 +326,7 @@ enum { DQ_SAMPLER_REFERENCE = 0, DQ_SAMPLER_DDIM = 1, DQ_SAMPLER_DPMPP_2M = 2 };
  * (samplers 1, 2), eta != 0 with sampler 2, eta outside [0, 1], an unknown sampler. */
 int dq_sampler_coef_table(const float* alpha_bars_host, int num_timesteps, const int32_t* timesteps_host, int num_steps, int sampler,
                           float eta, float* coef_out, float* extra_out);
-/* One solver update on caller-supplied tensors (k_solver.hip).  coef_dev: 5 device floats [sa, sb, cx, c0, c1].  x0 = net_out (DQ_PRED_X0)
+/* One solver update on caller-supplied tensors (the Solver family of k_update.hip).  coef_dev: 5 device floats [sa, sb, cx, c0, c1].  x0 = net_out (DQ_PRED_X0)
  * or (x_t - sb net_out) / sa (DQ_PRED_EPS); clip_x0 > 0: x0 clamped to [-clip_x0, clip_x0] first; x_prev = (cx x_t + c0 x0) + c1 x0_hist,
  * or x0 when cx < 0.  x0_hist (nullable only when c1 == 0; not read when c1 == 0) receives x0.  eps_out (nullable): (x_t - sa x0) / sb under
  * DQ_PRED_X0 and for a clamped element, else net_out.  x_prev may alias x_t and eps_out net_out.  Any n; tensors 4-byte aligned (16-byte

@@ -1,4 +1,4 @@
-"""dq_adamw_clip_ema_step / dq_adamw_clip_ema_step_dev (csrc/k_stream.hip: k_adamw_clip_ema, k_adamw_ema_hyper): the fused clip + AdamW
+"""dq_adamw_clip_ema_step / dq_adamw_clip_ema_step_dev (csrc/k_adamw.hip: k_adamw_clip<true>, k_adamw_hyper): the fused clip + AdamW
 step that also keeps an exponential moving average e of the parameters.
 
   * p, m, v and the norm equal dq_adamw_clip_step's bit for bit from the same state: every size of SIZES (a block edge, the capped grid's

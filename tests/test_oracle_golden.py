@@ -237,7 +237,7 @@ def test_x0_train_loss_grads_and_batch(golden):
         O.Diffusion(d.params, d.cfg, pred_type="v")
 
 
-# ---- the float64 oracles of tests/test_stream_kernels.py (k_stream.hip) ----------------------------------------------------------------
+# ---- the float64 oracles of tests/test_stream_kernels.py (k_stream.hip, k_update.hip, k_adamw.hip) -------------------------------------
 
 @pytest.mark.parametrize("max_norm,gscale", [(10.0, 1.0), (1e6, 1.0), (0.0, 1.0), (10.0, 0.125)])
 def test_adamw_clip_step_oracle_is_torch_adamw(max_norm, gscale):
@@ -362,6 +362,14 @@ def test_stream_kernel_bounds_hold_the_fp32_restatement_to_half():
             p, m, v, norm = c["fp32"]
             for name, r in K.adamw_ratios(c, p, m, v).items():
                 note("adamw " + name, r)
+    for n in K.ADAMW_OFF16_SIZES:  # (the DDIM update's cases with every tensor one float off 16 bytes are cases of DDIM_SIZES)
+        assert n % 4 == 1
+        c = K.adamw_case(n, {}, fp32=True, seed=7)
+        p, m, v, norm = c["fp32"]
+        for name, r in K.adamw_ratios(c, p, m, v).items():
+            note("adamw " + name, r)
+        note("adamw gnorm", abs(float(norm) - c["ref_norm"]) / c["norm_bound"])
+    assert {4, 4 * K.T_ + 4} <= set(K.DDIM_SIZES)
     print("fp32 restatement, worst err / bound: " + " ".join(f"{k} {v:.3f}" for k, v in worst.items()))
     print(f"ms1 fp32 oracle distances: grad {dist['grad']:.2e} loss {dist['loss']:.2e}")
     assert all(v <= HALF.get(k, 0.5) for k, v in worst.items()), worst

@@ -1,16 +1,20 @@
-"""The streaming kernels of csrc/k_stream.hip at their loop edges, each against a float64 evaluation of the same fp32 inputs.
+"""The streaming kernels of csrc/k_stream.hip, the unguided DDIM update of csrc/k_update.hip and the optimiser step of csrc/k_adamw.hip at
+their loop edges, each against a float64 evaluation of the same fp32 inputs.
 
-Entry points (dquartic._native): dq_q_sample (k_q_sample), dq_ddim_step / dq_ddim_step_x0 (k_ddim_step<false|true>), dq_ddim_sample's
-epilogue (k_sample_finish), dq_mse_loss_fwd_bwd / dq_mse_loss_weighted_fwd_bwd (k_mse_fwd_bwd + k_sum_partials), dq_ms1_loss_fwd_bwd
-(k_ms1_rows / _sample / _apply), dq_adamw_clip_step (k_sumsq + k_adamw_clip), dq_adamw_clip_step_dev (k_adamw_hyper + k_sumsq +
-k_adamw_clip_dev).
+Entry points (dquartic._native): dq_q_sample (k_q_sample), dq_ddim_step / dq_ddim_step_x0 (k_step_update<Ddim, false|true, false, V>),
+dq_ddim_sample's epilogue (k_sample_finish), dq_mse_loss_fwd_bwd / dq_mse_loss_weighted_fwd_bwd (k_mse_fwd_bwd + k_sum_partials),
+dq_ms1_loss_fwd_bwd (k_ms1_rows / _sample / _apply), dq_adamw_clip_step (k_sumsq + k_adamw_clip<false>), dq_adamw_clip_step_dev
+(k_adamw_hyper + k_sumsq + k_adamw_clip<false>).
 
 Sizes come from the launch code: T = 256 threads, V elements per thread and trip, G the grid cap (constants below).  Every entry point
 runs at the smallest legal size, T*V -+ V and T*V, G*T*V -+ V, and two sweeps of the capped grid plus a ragged remainder; k_sumsq also at
 n = 4 * (5 * G * T + 77) + r, r in 1..3 (its paired loop twice, then the single loop, then a scalar tail), with grads aligned and one
 float off 16 bytes (its designed scalar branch).  q_sample, the DDIM update and the MSE send an element count (q_sample, weighted MSE: a
-per-sample count) that is no multiple of 4 to siblings with V = 1 (k_q_sample_1, k_ddim_step_1, k_mse_fwd_bwd_1): those run at the V = 1
-edges that are such sizes, and at 3 x 37 x 2, the shape tests/test_level_plan.py met them at.  Outputs are views between canaries, plain-store outputs start as NaN, scratch buffers
+per-sample count) that is no multiple of 4 to forms with V = 1 (k_q_sample_1, k_step_update<..., 1>, k_mse_fwd_bwd_1): those run at the
+V = 1 edges that are such sizes, and at 3 x 37 x 2, the shape tests/test_level_plan.py met them at.  The DDIM update takes V = 1 for
+tensors that are not 16-byte aligned as well (n = 4 and a block + 4, every tensor one float off).  k_adamw_clip moves 16 bytes per lane
+when p, g, m, v are all 16-byte aligned and has a scalar loop for the tail and for every other alignment: both plain entries run with p, m
+and v in turn one float off.  Outputs are views between canaries, plain-store outputs start as NaN, scratch buffers
 have exactly the documented size (NaN, then a canary compared through an int view).
 
 References: oracle.dq_oracle (q_sample, ddim_update, ddim_update_x0, ms1_term, adamw_clip_step) and the plain MSE formula, in float64
@@ -43,10 +47,10 @@ from conftest import sub
 
 pytestmark = pytest.mark.gpu
 
-T_ = 256                      # every launch in k_stream.hip: dim3(256)
-GRID_STREAM = 2048            # launch_q_sample / launch_ddim_step / launch_sample_finish: std::min(cdiv(n4, 256), 2048)
+T_ = 256                      # every launch in k_stream.hip, k_update.hip and k_adamw.hip: dim3(256)
+GRID_STREAM = 2048            # launch_q_sample / launch_update / launch_sample_finish: std::min(cdiv(n4, 256), 2048)
 MSE_MAX_BLOCKS = 1024         # dq_kernels.h: constexpr int MSE_MAX_BLOCKS (launch_mse_fwd_bwd's grid cap, the scratch size)
-GRID_ADAMW = MSE_MAX_BLOCKS - 8  # launch_adamw_clip / launch_adamw_clip_dev: std::min(cdiv(n, 256), MSE_MAX_BLOCKS - 8)
+GRID_ADAMW = MSE_MAX_BLOCKS - 8  # launch_adamw: std::min(cdiv(n, 256), MSE_MAX_BLOCKS - 8)
 GRID_MS1_APPLY = 4096         # launch_ms1_loss: k_ms1_apply's grid, std::min(cdiv(rows * MZ, 256), 4096)
 SCRATCH = 1024                # include/dq_hip.h: "scratch: >= 1024 device floats" (MSE, AdamW)
 U = 2.0 ** -24
@@ -152,7 +156,7 @@ def q_case(B, per, normalize, kind, fp32=False):
     return c
 
 
-# n % 4 != 0 (k_ddim_step_1, V = 1): the same edges where they are no multiple of 4, and 3 x 37 x 2
+# n % 4 != 0 (k_step_update<..., 1>, V = 1): the same edges where they are no multiple of 4, and 3 x 37 x 2
 ODD = lambda sizes: [n for n in sizes if n % 4]
 DDIM_SIZES = edge_sizes(4, GRID_STREAM, 4) + ODD(edge_sizes(1, GRID_STREAM, 1)) + [222]
 DDIM_T = [999, 998, 500, 1, 0]  # 999: / sqrt(ab) = 4.9e-5; 0: the coef[2] < 0 branch
@@ -305,8 +309,13 @@ def ms1_case(B, RT, MZ, form, weights, w, grad=True, ties=False, fp32=False):
 ADAMW_BASE = dict(mode="active", grad_scale=1.0, max_norm=10.0, lr=1e-3, step=10, wd=0.01, gnorm=True, zero=False)
 ADAMW_VARIANTS = [dict(), dict(mode="inactive"), dict(mode="disabled", max_norm=0.0), dict(mode="disabled", max_norm=-1.0),
                   dict(grad_scale=0.125), dict(grad_scale=0.125, mode="inactive"), dict(gnorm=False), dict(wd=0.0), dict(zero=True, step=1)]
-ADAMW_SIZES = sorted(set(edge_sizes(1, GRID_ADAMW, 1)) | set(edge_sizes(4, GRID_ADAMW, 4)) - {4})  # k_adamw_clip: V = 1; k_sumsq: V = 4
-ADAMW_ALL_VARIANTS_AT = (257, GRID_ADAMW * T_ + 1)  # a block + 1; the capped grid + 1 (k_adamw_clip's second trip)
+# k_adamw_clip and k_sumsq: V = 4 over n // 4 vectors, then a scalar loop (V = 1) over the n % 4 elements left.  The V = 4 edges walk the
+# vector loop, the V = 1 edges leave tails of 1 - 3 elements behind it
+ADAMW_SIZES = sorted(set(edge_sizes(1, GRID_ADAMW, 1)) | set(edge_sizes(4, GRID_ADAMW, 4)) - {4})
+ADAMW_ALL_VARIANTS_AT = (257, GRID_ADAMW * T_ + 1)  # a block + 1; the capped grid + 1
+# one of p, m, v a float off 16 bytes (k_adamw_clip's scalar loop over everything, V = 1): a block + 1, the capped grid's second scalar trip;
+# and the size at which the aligned run they are compared with takes its second vector trip plus a tail
+ADAMW_OFF16_SIZES = (257, GRID_ADAMW * T_ + 1, 4 * GRID_ADAMW * T_ + 5)
 SUMSQ_BIG = [4 * (5 * GRID_ADAMW * T_ + 77) + r for r in (1, 2, 3)]  # paired loop twice (three times for 77 threads), single loop, tail r
 ADAMW_LR, ADAMW_STEP = [1e-5, 1e-3, 0.1], [1, 2, 10, 1000, 1000000]
 
@@ -477,6 +486,31 @@ def test_ddim_step(N, n, t):
     assert torch.equal(x.cpu(), c["x"]) and torch.equal(e.cpu(), c["eps"]) and torch.equal(x0.cpu(), c["x0"])
 
 
+@pytest.mark.parametrize("t", DDIM_T)
+@pytest.mark.parametrize("n", [4, 4 * T_ + 4])
+def test_ddim_step_one_float_off_16_bytes(N, n, t):
+    """n % 4 == 0 with x_t, the network output, x_prev (and eps_out) one float off 16 bytes: the one-element form, never 16-byte accesses at
+    such addresses.  The bounds of test_ddim_step, and the aligned run's results bit for bit (the arithmetic of an element does not depend
+    on the form)."""
+    c = ddim_case(n, t)
+    coef = c["coef"].cuda()
+    res = {}
+    for off in (0, 1):
+        x, e, x0 = Pad(c["x"], off), Pad(c["eps"], off), Pad(c["x0"], off)
+        out, xp, eo = Pad(n, off), Pad(n, off), Pad(n, off)
+        call(N, "dq_ddim_step", N.ptr(x.view), N.ptr(e.view), N.ptr(out.view), N.ptr(coef), n)
+        call(N, "dq_ddim_step_x0", N.ptr(x.view), N.ptr(x0.view), N.ptr(xp.view), N.ptr(eo.view), N.ptr(coef), n)
+        assert all(b.intact() for b in (x, e, x0, out, xp, eo))
+        assert torch.equal(x.view.cpu(), c["x"]) and torch.equal(e.view.cpu(), c["eps"]) and torch.equal(x0.view.cpu(), c["x0"])
+        res[off] = (out.view.clone(), xp.view.clone(), eo.view.clone())
+    out, xp, eo = res[1]
+    r = {"eps-form": ratio(out, c["ref"], c["S"], K_DDIM, CAP_DDIM), "x0-form": ratio(xp, c["ref_xp"], c["S_xp"], K_DDIM_X0, CAP_DDIM),
+         "eps_out": ratio(eo, c["ref_eps"], c["S_eps"], K_DDIM_EPS, CAP_DDIM)}
+    print(f"ddim n {n} t {t}, one float off 16 bytes: err / bound " + " ".join(f"{k} {v:.3f}" for k, v in r.items()))
+    assert all(v <= 1.0 for v in r.values()), r
+    assert all(torch.equal(a, b) for a, b in zip(res[0], res[1]))
+
+
 # ---- MSE ----------------------------------------------------------------------------------------------------------------------------
 
 def _run_mse(N, c, weighted, B, per, tm, ta):
@@ -581,8 +615,11 @@ def test_ms1_term_ties_go_to_the_first_maximum(N, B, RT, MZ, form, weights, w, g
 # ---- AdamW --------------------------------------------------------------------------------------------------------------------------
 
 class AdamWBufs:
-    def __init__(self, c, offset=0):
-        self.p, self.m, self.v, self.g = Pad(c["p"]), Pad(c["m"]), Pad(c["v"]), Pad(c["g"], offset)
+    """offset: of the gradient; off16: the one of p, m, v that starts one float off 16 bytes"""
+
+    def __init__(self, c, offset=0, off16=None):
+        self.p, self.m, self.v = (Pad(c[k], 1 if k == off16 else 0) for k in ("p", "m", "v"))
+        self.g = Pad(c["g"], offset)
         self.sc, self.gn = Pad(SCRATCH), Pad(1)
 
     def intact(self, c):
@@ -640,12 +677,44 @@ def test_adamw_step_dev_is_bitwise_the_host_step(N, step, lr):
         assert int(step_dev) == step + k
         s = step + k
         bc1, bc2 = 1.0 - B1 ** s, 1.0 - B2 ** s
-        casts = np.array([1.0 - lr * cfg["wd"], lr / bc1, math.sqrt(bc2)]).astype(np.float32)  # launch_adamw_clip's (float)(...) arguments
+        casts = np.array([1.0 - lr * cfg["wd"], lr / bc1, math.sqrt(bc2)]).astype(np.float32)  # launch_adamw's (float)(...) scalars
         hyp = dev.sc.view[GRID_ADAMW:GRID_ADAMW + 3].cpu().numpy()
         assert np.array_equal(hyp, casts), (s, lr, hyp.tolist(), casts.tolist())
         for name in ("p", "m", "v", "gn"):
             assert torch.equal(getattr(dev, name).view, getattr(host, name).view), (name, s, lr, hyp.tolist(), casts.tolist())
     assert host.intact(c) and dev.intact(c)
+
+
+@pytest.mark.parametrize("entry", ["host", "dev"])
+@pytest.mark.parametrize("off16", ["p", "m", "v"])
+@pytest.mark.parametrize("n", ADAMW_OFF16_SIZES)
+def test_adamw_one_buffer_off_16_bytes(N, n, off16, entry):
+    """k_adamw_clip takes 16-byte accesses only when p, g, m and v are all 16-byte aligned: with one of p, m, v a float off, both plain
+    entries run its scalar loop over the whole buffer.  The bounds of test_adamw_clip_step (the per-element bound does not depend on the
+    path), and the aligned run's p, m, v and norm bit for bit."""
+    c = adamw_case(n, {}, seed=7)
+    cfg = c["cfg"]
+    runs = []
+    for off in (None, off16):
+        b = AdamWBufs(c, 0, off)
+        if entry == "host":
+            _host_step(N, c, b, n)
+        else:
+            hi = np.float32(cfg["lr"])
+            lr_dev = torch.tensor([float(hi), float(np.float32(cfg["lr"] - float(hi)))], device="cuda")
+            step_dev = torch.tensor([cfg["step"] - 1], dtype=torch.int32, device="cuda")
+            call(N, "dq_adamw_clip_step_dev", N.ptr(b.p.view), N.ptr(b.g.view), N.ptr(b.m.view), N.ptr(b.v.view), n, N.ptr(b.sc.view),
+                 cfg["grad_scale"], cfg["max_norm"], N.ptr(lr_dev), B1, B2, EPS, cfg["wd"], N.ptr(step_dev), N.ptr(b.gn.view))
+            assert int(step_dev) == cfg["step"]
+        assert b.intact(c)
+        runs.append(b)
+    al, b = runs
+    r = adamw_ratios(c, b.p.view, b.m.view, b.v.view)
+    r["gnorm"] = abs(float(b.gn.view) - c["ref_norm"]) / c["norm_bound"]
+    print(f"adamw {entry} n {n} {off16} one float off 16 bytes: err / bound " + " ".join(f"{k} {v:.3f}" for k, v in r.items()))
+    assert all(v <= 1.0 for v in r.values()), r
+    for name in ("p", "m", "v", "gn"):
+        assert torch.equal(getattr(b, name).view, getattr(al, name).view), name
 
 
 # ---- the sample epilogue ------------------------------------------------------------------------------------------------------------

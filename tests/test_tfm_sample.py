@@ -67,7 +67,7 @@ def _rows(dm, num_steps, sampler):
 
 
 def _update(x, out, row, c1, hist, pred, solver, clip):
-    """one update in the dtype of x (torch): the expressions of k_ddim_step / k_solver_step.  Returns x_prev and the x0 that is the history"""
+    """one update in the dtype of x (torch): the expressions of ddim_elem / solver_elem (csrc/k_update.hip).  Returns x_prev and the x0 that is the history"""
     sa, sb, a2, a3 = (float(v) for v in row)
     if pred == "x0":
         x0 = out
