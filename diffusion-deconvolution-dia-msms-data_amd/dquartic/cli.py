@@ -1,7 +1,8 @@
 """``dquartic`` command line -- same commands and options as the reference's ``dquartic/cli.py`` (:26-188):
 ``dquartic train CONFIG [--parquet_directory --ms2-data-path --ms1-data-path --batch-size --checkpoint-path --use-wandb
 --threads]`` and ``dquartic generate-config PATH``; ``dquartic evaluate CONFIG --checkpoint PATH`` (this build) prints held-out loss and
-reconstruction metrics.  ``generate-train-data`` (offline sqMass ETL) is outside the hot path
+reconstruction metrics.  A ``data.mixture`` block in the config (absent by default) makes ``train`` and ``evaluate`` form K-component
+mixtures with drawn weights on the GPU (``ResidentMixLoader``).  ``generate-train-data`` (offline sqMass ETL) is outside the hot path
 and reports so.  Under ``torch.distributed.run`` (WORLD_SIZE > 1) training is data-parallel: one process per GPU, the
 dataset is sharded by rank and the flat gradient is all-reduced over RCCL."""
 import ast
@@ -14,7 +15,7 @@ from torch.utils.data import DataLoader
 
 from .model.model import DDIMDiffusionModel
 from .model.unet1d import UNet1d
-from .utils.config_loader import generate_train_config, load_train_config, validation_config
+from .utils.config_loader import generate_train_config, load_train_config, mixture_config, validation_config
 
 
 class PythonLiteralOption(click.Option):
@@ -68,7 +69,16 @@ def train(config_path, parquet_directory, ms2_data_path, ms1_data_path, batch_si
     dataset = build_dataset(config["data"], m, rank, world)
     per_rank = max(1, int(m["batch_size"]) // world)
     device = torch.device("cuda", local)
-    if resident_dataset and not syn:
+    mix = mixture_config(config["data"].get("mixture"))
+    if mix is not None:
+        # K-component mixtures with drawn weights: always formed on the GPU from the resident dataset.  The
+        # synthetic dataset has sharded its window pool by rank itself; a file-backed one is shared and its epoch is divided.
+        from .utils.data_loader import ResidentMixLoader
+
+        shards = 1 if syn else world
+        loader = ResidentMixLoader(dataset, per_rank, device=device, drop_last=len(dataset) // shards > per_rank, rank=rank,
+                                   world_size=shards, **mix)
+    elif resident_dataset and not syn:
         from .utils.data_loader import ResidentPairLoader
 
         loader = ResidentPairLoader(dataset, per_rank, device=device, drop_last=len(dataset) // world > per_rank, rank=rank, world_size=world)
@@ -129,9 +139,16 @@ def build_dataset(data, m, rank=0, world=1):
 def build_validation_loader(val, m, batch_size, rank=0, world=1):
     """The held-out loader of a completed ``data.validation`` block (``validation_config``): ``n_pairs`` index pairs of its windows drawn
     from a generator of their own under the block's ``seed`` (``FrozenPairDataset``: the same pairs in every process and run), served in
-    order -- what makes two ``evaluate`` runs comparable."""
+    order -- what makes two ``evaluate`` runs comparable.  With a ``mixture`` in the block: the frozen form of ``ResidentMixLoader``, ``n_pairs``
+    K-component items (None: one per window) whose indices and weights depend on the mixture's seed alone."""
     from .utils.synthetic import FrozenPairDataset
 
+    if val.get("mixture") is not None:
+        from .utils.data_loader import ResidentMixLoader
+
+        dataset = build_dataset(val, m, rank, world)
+        return ResidentMixLoader(dataset, batch_size, frozen_items=len(dataset) if val["n_pairs"] is None else val["n_pairs"],
+                                 device=torch.device("cuda", torch.cuda.current_device()), **val["mixture"])
     return DataLoader(FrozenPairDataset(build_dataset(val, m, rank, world), val["n_pairs"], seed=val.get("seed", 0)),
                       batch_size=batch_size, shuffle=False)
 
@@ -212,7 +229,7 @@ def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, guidance
     if val is None:
         click.echo("Notice: the config has no data.validation block; evaluating pairs of the TRAINING data section -- the result is "
                    "not a held-out loss", err=True)
-        val = {**config["data"], "n_pairs": None, "seed": 0}
+        val = {**config["data"], "n_pairs": None, "seed": 0, "mixture": mixture_config(config["data"].get("mixture"))}
     loader = build_validation_loader(val, m, max(1, int(m["batch_size"])))
     dm = build_model(m, device)
     ck = torch.load(checkpoint, map_location=device, weights_only=False)
@@ -225,11 +242,12 @@ def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, guidance
         raise click.ClickException(f"--use-ema: {checkpoint} holds no averaged weights")
     res = dm.evaluate(loader, n_t=4, seed=seed, num_steps=num_steps, eta=eta, use_ema=use_ema, max_batches=max_batches, sampler=sampler,
                       clip_x0=clip_x0, guidance_scale=guidance_scale, null_ms1=null_ms1)
-    per_window = res.pop("per_window", None)
+    # the per-window arrays go to --out only; the printed line keeps the scalars and the buckets (val_loss_by_weight among them)
+    arrays = {k: res.pop(k).tolist() for k in ("per_window", "target_weight") if k in res}
     click.echo(json.dumps(res))
     if out_path is not None:
         with open(out_path, "w") as f:
-            json.dump({**res, **({} if per_window is None else {"per_window": per_window.tolist()})}, f)
+            json.dump({**res, **arrays}, f)
 
 
 @cli.command()

@@ -42,6 +42,29 @@ def aggregate_metrics(per_window) -> dict:
     return out
 
 
+TARGET_WEIGHT_EDGES = [0.0, 1 / 16, 1 / 8, 1 / 4, 1 / 2, 1.0]  # buckets of the target's share of its mixture, one octave each above 1/16
+
+
+def by_target_weight(target_weight, mse_per_window, per_window=None) -> dict:
+    """Held-out loss by target abundance: the windows are put into the buckets (edges[i], edges[i + 1]] of ``TARGET_WEIGHT_EDGES`` by their
+    target weight w_0 (closed on the right: a single-component window, w_0 = 1, lands in the last one; anything at or below 1/16 in the
+    first, anything above 1/2 in the last), and each bucket reports its count ``n`` and the mean of the per-window unweighted MSE, ``mse``.
+    With ``per_window`` (the ``(n_windows, 9)`` reconstruction metrics) it also reports ``sa``, the bucket's mean spectral angle.  An empty
+    bucket has ``n`` 0 and None for its means.  float64 sums in window order."""
+    w = np.asarray(target_weight, dtype=np.float64)
+    m = np.asarray(mse_per_window, dtype=np.float64)
+    if w.ndim != 1 or m.shape != w.shape:
+        raise ValueError(f"by_target_weight: need one weight and one MSE per window, got shapes {w.shape} and {m.shape}")
+    which = np.searchsorted(np.asarray(TARGET_WEIGHT_EDGES[1:-1]), w, side="left")  # w <= 1/16 -> 0, ..., w > 1/2 -> 4
+    nb = len(TARGET_WEIGHT_EDGES) - 1
+    mean = lambda v, k: float(v[which == k].mean()) if (which == k).any() else None
+    out = {"edges": list(TARGET_WEIGHT_EDGES), "mse": [mean(m, k) for k in range(nb)], "n": [int((which == k).sum()) for k in range(nb)]}
+    if per_window is not None:
+        sa = np.asarray(per_window, dtype=np.float64)[:, N.METRIC_NAMES.index("sa")]
+        out["sa"] = [mean(sa, k) for k in range(nb)]
+    return out
+
+
 def window_noise(seed_dev: torch.Tensor, window_ids_dev: torch.Tensor, draw: int, shape) -> torch.Tensor:
     """``dq_randn``: standard normals of ``shape`` (B, ...) keyed by (seed, window id, element, draw index): a window's noise is the same in
     any batch."""

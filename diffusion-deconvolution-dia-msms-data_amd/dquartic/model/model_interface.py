@@ -686,7 +686,9 @@ class ModelInterface(object):
         population form) to each dict; ``"pred"`` stays draw 0.  With ``n_draws == 1`` those two keys are absent.
 
         ``sampler`` / ``clip_x0``: passed to ``sample``; with the defaults nothing else changes.  ``guidance_scale``
-        / ``null_ms1`` (keyword-only): classifier-free guidance, passed to ``sample`` too."""
+        / ``null_ms1`` (keyword-only): classifier-free guidance, passed to ``sample`` too.
+
+        Batches that carry their weights (``ResidentMixLoader``) add ``"weights"``, the batch's ``(B, K)`` array."""
         self.model.eval()
         n_draws = int(n_draws)
         if n_draws < 1:
@@ -696,10 +698,11 @@ class ModelInterface(object):
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
         preds = []
         first = 0
-        for ms2_1, ms1_1, ms2_2, ms1_2 in dataloader:
-            x_0, ms1_cond = ms2_1.to(self.device), ms1_1.to(self.device)
-            ms2_cond = (ms2_1 * mixture_weights[0]).to(self.device) + (ms2_2 * mixture_weights[1]).to(self.device)
-            d = {"ms2_1": ms2_1.cpu().numpy(), "ms1_1": ms1_1.cpu().numpy(), "mixture": ms2_cond.cpu().numpy()}
+        for batch in dataloader:
+            x_0, ms2_cond, ms1_cond, weights = self._batch_inputs(batch, mixture_weights)
+            d = {"ms2_1": x_0.cpu().numpy(), "ms1_1": ms1_cond.cpu().numpy(), "mixture": ms2_cond.cpu().numpy()}
+            if weights is not None:
+                d["weights"] = weights.cpu().numpy()
             if not stochastic:
                 d["pred"], _ = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, use_ema=use_ema,
                                                        **_sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1))
@@ -736,7 +739,13 @@ class ModelInterface(object):
         section 32: the scale can be tuned against these metrics).  The loss part is always the conditional one.
 
         ``use_ema`` as in ``predict``; ``max_batches``: stop after that many batches.  Under ``torch.distributed`` each rank evaluates
-        its own loader and the scalars are averaged over the ranks (``_global_mean``); ``per_window`` and ``n_windows`` stay the rank's."""
+        its own loader and the scalars are averaged over the ranks (``_global_mean``); ``per_window`` and ``n_windows`` stay the rank's.
+
+        Batches that carry their weights (``ResidentMixLoader``; ``mixture_weights`` does not apply to them) add
+        ``target_weight``, the float32 ``(n_windows,)`` array of every window's w_0, and ``val_loss_by_weight`` = {"edges": [0, 1/16, 1/8,
+        1/4, 1/2, 1], "mse": per bucket the mean of the unweighted per-window MSE (over its ``n_t`` repeats), "n": the bucket's windows},
+        with ``num_steps`` also "sa", the bucket's mean spectral angle (``evaluation.by_target_weight``; an empty bucket reports 0 and
+        None).  Both stay the rank's.  Without such batches the dict has exactly the keys above."""
         from . import evaluation as E
 
         n_t = int(n_t)
@@ -746,16 +755,17 @@ class ModelInterface(object):
         self.model.eval()
         T = int(self.num_timesteps)
         lw_host = self.loss_weight.detach().to("cpu", torch.float32).numpy().astype(np.float64)
-        mse, ts, rows = [[] for _ in range(n_t)], [[] for _ in range(n_t)], []
+        mse, ts, rows, target_w = [[] for _ in range(n_t)], [[] for _ in range(n_t)], [], []
         first = 0
         seed_dev = None
         try:
             with torch.no_grad(), self._ema_or_null_scope(use_ema):
-                for batch_idx, (ms2_1, ms1_1, ms2_2, ms1_2) in enumerate(dataloader):
+                for batch_idx, batch in enumerate(dataloader):
                     if max_batches is not None and batch_idx >= int(max_batches):
                         break
-                    x_0, ms1_cond = ms2_1.to(self.device), ms1_1.to(self.device)
-                    ms2_cond = (ms2_1 * mixture_weights[0]).to(self.device) + (ms2_2 * mixture_weights[1]).to(self.device)
+                    x_0, ms2_cond, ms1_cond, weights = self._batch_inputs(batch, mixture_weights)
+                    if weights is not None:
+                        target_w.append(weights[:, 0])
                     ids = np.arange(first, first + x_0.shape[0], dtype=np.int64)
                     ids_dev = torch.from_numpy(ids).to(x_0.device)
                     if seed_dev is None:
@@ -790,6 +800,12 @@ class ModelInterface(object):
                 out["clip_x0"] = float(clip_x0)
             if guidance_scale is not None:
                 out.update(guidance_scale=float(guidance_scale), null_ms1=float(null_ms1))
+        if target_w:  # batches that carry their weights (ResidentMixLoader): the loss by the target's share of its mixture
+            tw = torch.cat(target_w).cpu().numpy().astype(np.float32)
+            if len(tw) != first:
+                raise ValueError("evaluate: some batches of the dataloader carry mixture weights and some do not")
+            out["target_weight"] = tw
+            out["val_loss_by_weight"] = E.by_target_weight(tw, mse.mean(axis=0), None if num_steps is None else out["per_window"])
         return out
 
     # ---- internals
@@ -826,18 +842,29 @@ class ModelInterface(object):
             warmup_epoch = epoch // 2
         return self.lr_scheduler_class(self.optimizer, num_warmup_steps=warmup_epoch, num_training_steps=epoch)
 
+    def _batch_inputs(self, batch, mixture_weights=(0.5, 0.5)):
+        """What the train, predict and evaluate loops take from a batch: ``(x_0, ms2_cond, ms1_cond, weights or None)``.
+
+        A batch whose mixture is final (``MixBatch`` of ``ResidentMixLoader``, DESIGN.md section 34: K components, per-window weights, the
+        target already scaled) is used as it is and ``mixture_weights`` does not apply; ``weights`` is its ``(B, K)`` tensor.  Anything
+        else is ``(ms2_1, ms1_1, ms2_2, ms1_2)``: the simulated mixed spectrum of the target window and the other window (reference
+        :1073-1075), which a resident loader (``ResidentPairLoader``) has already formed on the GPU, with the same bits, in the kernel that
+        normalised the pair."""
+        ms2_1, ms1_1, ms2_2, ms1_2 = batch
+        x_0, ms1_cond = ms2_1.to(self.device), ms1_1.to(self.device)
+        if getattr(batch, "mixture_final", False):
+            return x_0, batch.ms2_cond, ms1_cond, batch.weights
+        if getattr(batch, "ms2_cond", None) is not None and batch.mixture_weights == tuple(float(w) for w in mixture_weights):
+            ms2_cond = batch.ms2_cond
+        else:
+            ms2_cond = (ms2_1 * mixture_weights[0]).to(self.device) + (ms2_2 * mixture_weights[1]).to(self.device)
+        return x_0, ms2_cond, ms1_cond, None
+
     def _train_one_epoch(self, epoch, dataloader, mixture_weights=(0.5, 0.5)):
         self.model.train()
         batch_loss = []
         for batch_idx, batch in enumerate(dataloader):
-            ms2_1, ms1_1, ms2_2, ms1_2 = batch
-            x_0, ms1_cond = ms2_1.to(self.device), ms1_1.to(self.device)
-            # simulated mixed spectra from the target window and the other window (reference :1073-1075); a resident loader
-            # (utils/data_loader.py:ResidentPairLoader) has already formed it on the GPU in the kernel that normalised the pair
-            if getattr(batch, "ms2_cond", None) is not None and batch.mixture_weights == tuple(float(w) for w in mixture_weights):
-                ms2_cond = batch.ms2_cond
-            else:
-                ms2_cond = (ms2_1 * mixture_weights[0]).to(self.device) + (ms2_2 * mixture_weights[1]).to(self.device)
+            x_0, ms2_cond, ms1_cond, _ = self._batch_inputs(batch, mixture_weights)
             loss = self._train_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, noise=None, ms1_loss_weight=self.ms1_loss_weight)
             batch_loss.append(loss)
             self.callback_handler.batch_callback(batch_idx, loss)

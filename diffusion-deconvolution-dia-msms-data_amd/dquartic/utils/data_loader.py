@@ -112,6 +112,33 @@ class DIAMSDataset(Dataset):
 # min-max + collate + H2D copy of a DataLoader becomes the bottleneck, so the whole dataset lives in HBM (288 GB hold
 # ~2.8 M windows of 400 x 64) and a batch is formed by one native call (csrc/k_pairs.hip: dq_pair_batch).
 # ----------------------------------------------------------------------------------------------------------------------
+def _resident_tensors(dataset_or_arrays, device):
+    """The windows a resident loader keeps in HBM: ``(ms2 (N, RT, MZ), ms1 (N, ...))`` as float32 device tensors, from a ``DIAMSDataset``
+    (npy: its arrays; parquet: every slice materialised once), a dataset that holds ``ms2`` / ``ms1`` arrays (``SyntheticDIAMSDataset``)
+    or an ``(ms2, ms1)`` pair of arrays.  A dataset must normalise by "minmax", the one rule the kernels implement."""
+    import warnings
+
+    ds = dataset_or_arrays
+    if isinstance(ds, (tuple, list)):
+        ms2, ms1 = (np.asarray(a) for a in ds)
+    else:
+        if getattr(ds, "normalize", None) != "minmax":
+            raise ValueError("Invalid normalization method. Valid options are: None, 'minmax'.")  # data_loader.py:81
+        if getattr(ds, "data_type", None) == "parquet":
+            rows = [ds._get_parquet_data(e) for e in ds.meta]
+            ms1, ms2 = np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows])
+        elif hasattr(ds, "ms2_data"):
+            ms2, ms1 = np.asarray(ds.ms2_data), np.asarray(ds.ms1_data)
+        else:
+            ms2, ms1 = np.asarray(ds.ms2), np.asarray(ds.ms1)
+    if ms2.ndim != 3 or len(ms1) != len(ms2):
+        raise ValueError(f"expected ms2 (N, RT, MZ) and ms1 (N, ...), got {ms2.shape} and {ms1.shape}")
+    with warnings.catch_warnings():  # read-only mmap views are only read (uploaded) here
+        warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
+        return (torch.from_numpy(np.ascontiguousarray(ms2, dtype=np.float32)).to(device),
+                torch.from_numpy(np.ascontiguousarray(ms1, dtype=np.float32)).to(device))
+
+
 class PairBatch(tuple):
     """``(ms2_1, ms1_1, ms2_2, ms1_2)`` -- what a ``DataLoader(DIAMSDataset)`` batch unpacks to -- already on the device,
     plus ``ms2_cond`` = the mixture for ``mixture_weights`` (formed in the same kernel)."""
@@ -136,29 +163,16 @@ class ResidentPairLoader:
     def __init__(self, dataset, batch_size, device="cuda", mixture_weights=(0.5, 0.5), drop_last=False, rank=0, world_size=1):
         from .. import _native as N
 
-        if getattr(dataset, "normalize", None) != "minmax":
-            raise ValueError("Invalid normalization method. Valid options are: None, 'minmax'.")  # data_loader.py:81
-        if getattr(dataset, "data_type", "npy") == "npy":
-            ms2, ms1 = np.asarray(dataset.ms2_data), np.asarray(dataset.ms1_data)
-            self._same = None
-        else:  # parquet backend: materialise every slice once
-            rows = [dataset._get_parquet_data(e) for e in dataset.meta]
-            ms1, ms2 = np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows])
-            meta = dataset.meta
-            self._same = lambda a, b: meta[a][2] == meta[b][2] and meta[a][3] == meta[b][3]
-        if ms2.ndim != 3 or len(ms1) != len(ms2):
-            raise ValueError(f"expected ms2 (N, RT, MZ) and ms1 (N, ...), got {ms2.shape} and {ms1.shape}")
         self._N = N
         self.dataset, self.batch_size, self.device = dataset, int(batch_size), torch.device(device)
         self.mixture_weights = tuple(float(w) for w in mixture_weights)
         self.drop_last, self.rank, self.world_size = bool(drop_last), int(rank), int(world_size)
+        self._same = None
+        if getattr(dataset, "data_type", "npy") != "npy":  # parquet backend: never the same slice of the same isolation target
+            meta = dataset.meta
+            self._same = lambda a, b: meta[a][2] == meta[b][2] and meta[a][3] == meta[b][3]
         N.lib()  # fail loudly now if the native library is missing
-        import warnings
-
-        with warnings.catch_warnings():  # read-only mmap views are only read (uploaded) here
-            warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
-            self.ms2 = torch.from_numpy(np.ascontiguousarray(ms2, dtype=np.float32)).to(self.device)
-            self.ms1 = torch.from_numpy(np.ascontiguousarray(ms1, dtype=np.float32)).to(self.device)
+        self.ms2, self.ms1 = _resident_tensors(dataset, self.device)
         self.n, self.RT, self.MZ = self.ms2.shape
         self.ms1_shape = tuple(self.ms1.shape[1:])
         self.ms1_per = int(np.prod(self.ms1_shape)) if self.ms1_shape else 1
@@ -195,3 +209,172 @@ class ResidentPairLoader:
             pairs = [self.dataset._draw_pair(self.n, self._same) for _ in range(B)]
             left -= B
             yield self.form([p[0] for p in pairs], [p[1] for p in pairs])
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# K-component mixtures with per-window weights (csrc/k_mix.hip: dq_mix_batch).  Not in the reference, whose
+# mixture is one pair at (0.5, 0.5): a window here mixes 1..K distinct windows of the resident dataset at abundances drawn on
+# the device, and the target is the first component's CONTRIBUTION to the mixture.
+# ----------------------------------------------------------------------------------------------------------------------
+MIX_MAX_COMPONENTS = 8  # dq_mix_batch: K in 2..8
+
+
+def _mix_components(n_components, n_windows=None):
+    """``(kmin, kmax)`` of an ``n_components`` argument, checked: 1 <= kmin <= kmax, 2 <= kmax <= 8 (the rule of the ``data.mixture``
+    config block: K = kmax is the kernel's K), and, given ``n_windows``, enough windows for kmax distinct ones."""
+    kmin, kmax = (int(v) for v in n_components)
+    if not (1 <= kmin <= kmax and 2 <= kmax <= MIX_MAX_COMPONENTS):
+        raise ValueError(f"n_components must satisfy 1 <= kmin <= kmax and 2 <= kmax <= {MIX_MAX_COMPONENTS}, got {(kmin, kmax)}")
+    if n_windows is not None and n_windows < kmax:
+        raise ValueError(f"a mixture of {kmax} distinct windows needs at least {kmax} windows, got {n_windows}")
+    return kmin, kmax
+
+
+def draw_mix_indices(n_windows, n_items, n_components, rng, valid_pair=None):
+    """Which windows form each of ``n_items`` mixtures: ``(idx, count)`` with ``idx`` int64 ``(K, n_items)`` (row j = component j, row 0
+    the target) and ``count`` int32 ``(n_items,)``.  ``n_components = (kmin, kmax)``, K = kmax.  Per item, from ``rng`` (a
+    ``numpy.random.Generator``) in this order: the count, uniform in [kmin, kmax]; the target, uniform over the windows; then component
+    after component, redrawn until it differs from every earlier one of the item and ``valid_pair(target, j)`` holds (None: any distinct
+    window).  Rows ``j >= count`` hold -1: the kernel never reads them, and whatever would is refused by its bounds check.  A pure host
+    function of its arguments."""
+    n_windows, n_items = int(n_windows), int(n_items)
+    kmin, kmax = _mix_components(n_components, n_windows)
+    if n_items < 1:
+        raise ValueError(f"need at least one item, got {n_items}")
+    idx = np.full((kmax, n_items), -1, dtype=np.int64)
+    count = np.empty(n_items, dtype=np.int32)
+    for b in range(n_items):
+        count[b] = int(rng.integers(kmin, kmax + 1))
+        for _ in range(100):  # a target that finds its partners within 100 tries each, another target otherwise
+            comp = [int(rng.integers(0, n_windows))]
+            tries = 0
+            while len(comp) < count[b] and tries < 100 * kmax:
+                j = int(rng.integers(0, n_windows))
+                tries += 1
+                if j not in comp and (valid_pair is None or valid_pair(comp[0], j)):
+                    comp.append(j)
+            if len(comp) == count[b]:
+                break
+        else:
+            raise ValueError(f"draw_mix_indices: found no window with {int(count[b]) - 1} windows it may be mixed with")
+        idx[:count[b], b] = comp
+    return idx, count
+
+
+class MixBatch(PairBatch):
+    """``(ms2_target, ms1_target, ms2_rest, None)`` on the device: where a pair batch has the target window, its MS1, the other window
+    and that one's MS1, this has the target (scaled by its weight under ``scale_target``), its MS1, the weighted sum of everything else,
+    and nothing.  ``ms2_cond`` is the mixture, ``weights`` the ``(B, K)`` tensor of every window's w_j (0 for absent components), and
+    ``mixture_final`` says that the mixture is not to be formed again from the items (``ModelInterface._batch_inputs``)."""
+
+    mixture_final = True
+
+    def __new__(cls, items, ms2_cond, weights):
+        self = super().__new__(cls, items, ms2_cond, ())
+        self.weights = weights
+        return self
+
+
+class ResidentMixLoader:
+    """Batches of K-component mixtures from a dataset held in HBM, one ``dq_mix_batch`` call each.
+
+    ``dataset_or_arrays``: a ``DIAMSDataset`` (npy or parquet), a ``SyntheticDIAMSDataset``, or an ``(ms2, ms1)`` pair of arrays
+    ``(N, RT, MZ)`` / ``(N, ...)``.  ``n_components = (kmin, kmax)``: every window mixes a count of distinct windows uniform in that range
+    (``draw_mix_indices``; pairs obey the dataset's ``valid_pair``).  ``weights`` None: the kernel draws them, uniformly within an octave
+    and over ``max_ratio_log2`` octaves, normalised to sum 1 (so max w / min w < 2 ** max_ratio_log2); otherwise kmax fixed
+    weights, used as they are.  ``scale_target``: the target is ``n_0 * w_0``, the first component's contribution to the mixture, rather
+    than ``n_0``.
+
+    Training form (``frozen_items`` None): one epoch = ``len(dataset) // world_size`` windows; the indices come from a host generator of
+    ``(seed, rank)`` that runs on from epoch to epoch, the weights from ``seed + rank`` with the running batch number as the draw index
+    and the batch positions as ids.  A loader built again with the same arguments yields the same batches.
+    Held-out form (``frozen_items = n``): the indices of n items are drawn once from ``numpy.random.default_rng(seed)``; item k draws its
+    weights under id k at draw 0 -- the same set in every run, every process and at every batch size."""
+
+    def __init__(self, dataset_or_arrays, batch_size, n_components=(2, 4), max_ratio_log2=3, seed=0, scale_target=True, weights=None,
+                 frozen_items=None, device="cuda", drop_last=False, rank=0, world_size=1):
+        from .. import _native as N
+
+        ds = dataset_or_arrays
+        self._valid = None if isinstance(ds, (tuple, list)) else ds.valid_pair
+        kmin, kmax = _mix_components(n_components)
+        self.n_components, self.K = (kmin, kmax), kmax
+        self.max_ratio_log2 = int(max_ratio_log2)
+        if not 0 <= self.max_ratio_log2 <= 16:
+            raise ValueError(f"max_ratio_log2 must be 0..16, got {max_ratio_log2}")
+        if weights is not None and len(weights) != self.K:
+            raise ValueError(f"weights: need {self.K} fixed weights, got {len(weights)}")
+        self.weights = None if weights is None else tuple(float(w) for w in weights)
+        self._N = N
+        self.dataset, self.batch_size, self.device = ds, int(batch_size), torch.device(device)
+        if not 1 <= self.batch_size <= 65535:
+            raise ValueError(f"batch_size must be 1..65535, got {batch_size}")
+        self.seed, self.scale_target = int(seed), bool(scale_target)
+        self.drop_last, self.rank, self.world_size = bool(drop_last), int(rank), int(world_size)
+        N.lib()  # fail loudly now if the native library is missing
+        self.ms2, self.ms1 = _resident_tensors(ds, self.device)
+        _mix_components(n_components, len(self.ms2))
+        self.n, self.RT, self.MZ = self.ms2.shape
+        self.ms1_shape = tuple(self.ms1.shape[1:])
+        self.ms1_per = int(np.prod(self.ms1_shape)) if self.ms1_shape else 1
+        self._scratch = torch.empty(max(1, N.lib().dq_mix_batch_scratch_bytes(self.batch_size, self.K) // 4), dtype=torch.float32,
+                                    device=self.device)
+        self.frozen = None
+        if frozen_items is not None:
+            self.frozen = draw_mix_indices(self.n, int(frozen_items), self.n_components, np.random.default_rng(self.seed), self._valid)
+            weight_seed = self.seed
+        else:
+            self._rng = np.random.default_rng((self.seed, self.rank))
+            weight_seed = self.seed + self.rank
+        weight_seed &= 2 ** 64 - 1
+        self._seed_dev = torch.tensor([weight_seed - 2 ** 64 if weight_seed >= 2 ** 63 else weight_seed], dtype=torch.int64, device=self.device)
+        self._draw = 0  # the running batch number of the training form
+
+    def _items(self):
+        return self.frozen[0].shape[1] if self.frozen is not None else max(1, len(self.ms2) // self.world_size)
+
+    def __len__(self):
+        n = self._items()
+        return n // self.batch_size if self.drop_last and self.frozen is None else (n + self.batch_size - 1) // self.batch_size
+
+    def form(self, idx, count=None, draw=0, window_ids=None):
+        """One native call for explicit indices ``(K, B)`` and counts ``(B,)`` (None: K everywhere) -> ``MixBatch``."""
+        N = self._N
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        if idx.ndim != 2 or idx.shape[0] != self.K or not 1 <= idx.shape[1] <= self.batch_size:
+            raise ValueError(f"need a ({self.K}, 1..{self.batch_size}) index array, got shape {idx.shape}")
+        B = idx.shape[1]
+        idx_dev = torch.from_numpy(idx).to(self.device, non_blocking=True)
+        count_dev = None if count is None else torch.from_numpy(np.ascontiguousarray(count, dtype=np.int32)).to(self.device, non_blocking=True)
+        if count_dev is not None and count_dev.shape != (B,):
+            raise ValueError(f"need {B} counts, got shape {tuple(count_dev.shape)}")
+        ids_dev = None if window_ids is None else torch.as_tensor(np.ascontiguousarray(window_ids, dtype=np.int64)).to(self.device, non_blocking=True)
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
+        tgt, cond, rest = new(B, self.RT, self.MZ), new(B, self.RT, self.MZ), new(B, self.RT, self.MZ)
+        m1, w = new(B, *self.ms1_shape), new(B, self.K)
+        import ctypes
+
+        fixed = None if self.weights is None else (ctypes.c_float * self.K)(*self.weights)
+        N.check(N.lib().dq_mix_batch(N.ptr(self.ms2), N.ptr(self.ms1), self.n, N.ptr(idx_dev), N.ptr(count_dev), B, self.K, self.RT, self.MZ,
+                                     self.ms1_per, fixed, self.max_ratio_log2, N.ptr(self._seed_dev), N.ptr(ids_dev), int(draw),
+                                     int(self.scale_target), N.ptr(tgt), N.ptr(m1), N.ptr(cond), N.ptr(rest), N.ptr(w),
+                                     N.ptr(self._scratch), self._scratch.numel() * 4, N.stream_ptr()), "dq_mix_batch")
+        return MixBatch((tgt, m1, rest, None), cond, w)
+
+    def __iter__(self):
+        if self.frozen is not None:
+            idx, count = self.frozen
+            for first in range(0, idx.shape[1], self.batch_size):
+                last = min(first + self.batch_size, idx.shape[1])
+                yield self.form(idx[:, first:last], count[first:last], draw=0, window_ids=np.arange(first, last, dtype=np.int64))
+            return
+        left = self._items()
+        while left > 0:
+            B = min(self.batch_size, left)
+            if B < self.batch_size and self.drop_last:
+                return
+            idx, count = draw_mix_indices(self.n, B, self.n_components, self._rng, self._valid)
+            left -= B
+            batch = self.form(idx, count, draw=self._draw)
+            self._draw += 1
+            yield batch

@@ -57,7 +57,7 @@ const char* dq_last_error(void);
  * dq_wide_col2im3, dq_wide_repitch, dq_wide_norm_fwd, dq_wide_norm_bwd, dq_wide_norm_bwd_scratch_floats, dq_wide_rowsum, dq_wide_sum_b,
  * dq_debug_wide_mid_fwd, dq_debug_wide_mid_bwd; the transformer's held-out evaluation: dq_tfm_eval_workspace_bytes, dq_tfm_eval_step,
  * dq_q_sample_repeats, dq_mse_per_window_repeats, dq_tfm_kv_broadcast; classifier-free guidance: DQ_UPDATE_*, dq_guided_update,
- * dq_ms1_cond_drop, dq_ddim_sample_guided). */
+ * dq_ms1_cond_drop, dq_ddim_sample_guided; K-component mixtures: dq_mix_batch_scratch_bytes, dq_mix_batch). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -405,6 +405,32 @@ int64_t dq_pair_batch_scratch_bytes(int B);
 int dq_pair_batch(const float* ms2_data, const float* ms1_data, int64_t n_windows, const int64_t* idx_dev, int B, int RT, int MZ,
                   int64_t ms1_per_window, float w1, float w2, float* ms2_1, float* ms1_1, float* ms2_2, float* ms1_2,
                   float* ms2_cond, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* K-component mixtures with per-window weights (csrc/k_mix.hip; additive at ABI version 12): dq_pair_batch's batch
+ * formation for 1..K windows per item, K in 2..8.  idx_dev: (K, B) device int64, row j = component j of every window, row 0 the target;
+ * count_dev: (B) device int32, the components present in window b (1..K; NULL: K everywhere).  Rows j >= count[b] are never read.  A window
+ * with a used index outside [0, n_windows), or a count outside [1, K], is never dereferenced: every output of it, weights_out included, is
+ * NaN.  n_j = (x_j - lo) / (hi - lo): MS2 lo / hi over all present components, MS1 lo / hi over component 0 only, no epsilon (a constant
+ * window set gives NaN).
+ * Weights: weights_host != NULL: w_j = weights_host[j] for j < count[b] (K host floats, read before the call returns; not renormalised).
+ * weights_host == NULL: drawn.  a_j = (1 + m 2^-23) 2^e with m = r3 & 0x7fffff, e = ((r3 >> 23) * E) >> 9, E = max_ratio_log2 (E == 0:
+ * a_j = 1), r3 the FOURTH output word of Philox4x32-10 on counter (j, draw, id lo, id hi) under key (seed lo, seed hi), id =
+ * window_ids_dev[b] (NULL: b) -- the normals use words 0 and 1, dq_ms1_cond_drop word 2 of counter (0, ...).  s = ((a_0 + a_1) + a_2) + ...
+ * in fp32 over the present components, w_j = a_j / s: max w / min w < 2^E.  seed_dev: 1 uint64 of DEVICE memory.  A window decides from
+ * (seed, id, draw) alone, wherever it sits in a batch.
+ * Outputs (device): ms2_cond (B, RT, MZ) = ((n_0 w_0 + n_1 w_1) + n_2 w_2) + ..., every product and every sum rounded; ms2_rest (nullable)
+ * the same sum from j = 1 (0 for count 1); ms2_target = n_0 (scale_target == 0) or the product n_0 w_0 that entered ms2_cond; ms1_target
+ * (B, ms1_per_window) the normalised MS1 of component 0; weights_out (B, K) = w_j, 0 for absent components.  A numpy fp32 transcription of
+ * these rules gives every bit (tests/test_mix_host.py); K = 2 with fixed weights and scale_target == 0 is dq_pair_batch bit for bit.
+ * scratch: dq_mix_batch_scratch_bytes(B, K) bytes (0 for a B or K the call refuses).  Two launches, asynchronous on stream.
+ * Refused before any launch (dq_last_error), in this order: a NULL among ms2_data, ms1_data, idx_dev, ms2_target, ms1_target, ms2_cond,
+ * weights_out, scratch; K outside 2..8; max_ratio_log2 outside 0..16 (fixed weights too); draw < 0; B outside 1..65535; a non-positive
+ * size; RT*MZ % 4 != 0; weights_host == NULL without seed_dev; scratch too small. */
+int64_t dq_mix_batch_scratch_bytes(int B, int K);
+int dq_mix_batch(const float* ms2_data, const float* ms1_data, int64_t n_windows, const int64_t* idx_dev, const int32_t* count_dev, int B,
+                 int K, int RT, int MZ, int64_t ms1_per_window, const float* weights_host, int max_ratio_log2, const uint64_t* seed_dev,
+                 const int64_t* window_ids_dev, int draw, int scale_target, float* ms2_target, float* ms1_target, float* ms2_cond,
+                 float* ms2_rest, float* weights_out, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ---- CustomTransformer (dquartic/model/building_blocks.py:179-260) ----------------------------------
  * The reference's alternative noise predictor: forward(x_t (B,S1,input_dim), t (B) int64, x_cond (B,S2)) -> (B,S1,input_dim).
