@@ -244,10 +244,13 @@ int dq_train_step(dq_plan* plan, const float* params, const float* rope_freqs, c
                   const float* ms2_cond, const float* ms1_cond, const int64_t* t, const float* noise, int auto_normalize,
                   int pred_type, const float* loss_weight_dev, float ms1_loss_weight, float* grads, float* loss_out, void* workspace,
                   int64_t workspace_bytes, int B, int RT, void* stream) {
+  // (the objective first: these two refusals need no operand)
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0 || pred_type == DQ_PRED_V, "dq_train_step: Unknown pred_type");
+  DQ_REQUIRE(pred_type != DQ_PRED_V || !(ms1_loss_weight > 0.f),
+             "dq_train_step: ms1_loss_weight > 0 with pred_type v_prediction is not built (DESIGN.md section 12 defines the MS1 term for eps and x0 only)");
   DQ_REQUIRE(plan && params && alpha_bars_dev && x0 && ms2_cond && ms1_cond && t && noise && grads && loss_out && workspace,
              "dq_train_step: null argument");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_train_step: Unknown pred_type");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || loss_weight_dev, "dq_train_step: pred_type x0 needs the loss-weight (SNR) table");
+  DQ_REQUIRE(pred_type != DQ_PRED_X0 || loss_weight_dev, "dq_train_step: pred_type x0 needs the loss-weight (SNR) table");
   DQ_REQUIRE(B > 0 && RT > 0, "dq_train_step: B and RT must be positive");
   DQ_REQUIRE(ms1_loss_weight >= 0.f && ms1_loss_weight <= 1.f, "dq_train_step: ms1_loss_weight must lie in [0, 1]");
   DQ_REQUIRE(ms1_loss_weight == 0.f || plan->plan.ms1_channels == 1,
@@ -269,8 +272,11 @@ int dq_train_step(dq_plan* plan, const float* params, const float* rope_freqs, c
   else DQ_TRY(launch_q_sample(alpha_bars_dev, x0, t, noise, c.w(a.xa), B, per, auto_normalize, s));
   const bool head_loss_on = !DQ_DEV_FLAG("DQ_NO_HEAD_LOSS", '1');  // (dev switch)
   Ctx::HeadLoss hl;
-  if (head_loss_on && pred_type == DQ_PRED_EPS && ms1_loss_weight == 0.f) {
+  if (head_loss_on && pred_type != DQ_PRED_X0 && ms1_loss_weight == 0.f) {
     hl.z = noise; hl.grad_out = c.w(a.xb); hl.part = c.w(a.head_part); hl.gscale = 2.0f / (float)(B * per);  // (launch_mse_fwd_bwd's scale)
+    if (pred_type == DQ_PRED_V) {  // the target sa_b noise - sb_b (x0 cm + ca) is formed in the head launch (launch_mse_v_fwd_bwd's arithmetic)
+      hl.x0 = x0; hl.alpha_bars = alpha_bars_dev; hl.t = t; hl.lw = loss_weight_dev; hl.tm = cm; hl.ta = ca;
+    }
     c.head_loss = &hl;
   }
   DQ_TRY(unet_forward(c, rope_freqs, c.w(a.xa), t, 0, ms2_cond, ms1_cond, cm, ca, plan->dev, c.w(a.eps)));   // model.py:359
@@ -279,6 +285,8 @@ int dq_train_step(dq_plan* plan, const float* params, const float* rope_freqs, c
     c.loss_sum.partials = hl.part; c.loss_sum.count = hl.nparts; c.loss_sum.scale = 1.0f / (float)(B * per); c.loss_sum.out = loss_out;
   } else if (pred_type == DQ_PRED_X0)  // model.py:372-376, 404: target = normalised x0, per-sample weight loss_weight[t_b]
     DQ_TRY(launch_mse_fwd_bwd(c.w(a.eps), x0, loss_out, c.w(a.xb), c.w(a.partials), B * per, s, loss_weight_dev, t, per, cm, ca));
+  else if (pred_type == DQ_PRED_V)  // target = sa_b noise - sb_b (normalised x0), weight loss_weight[t_b] (null: 1)
+    DQ_TRY(launch_mse_v_fwd_bwd(c.w(a.eps), x0, noise, alpha_bars_dev, cm, ca, loss_weight_dev, t, loss_out, c.w(a.xb), c.w(a.partials), B, per, s));
   else if (c.owner && ms1_loss_weight == 0.f && tail_fork_enabled()) {
     int nparts = 0;  // (the sum of the partials -> loss_out rides on the side stream: unet_backward)
     DQ_TRY(launch_mse_fwd_bwd(c.w(a.eps), noise, loss_out, c.w(a.xb), c.w(a.partials), B * per, s, nullptr, nullptr, 0, 1.f, 0.f, &nparts));
@@ -301,10 +309,10 @@ int dq_eval_step(dq_plan* plan, const float* params, const float* rope_freqs, co
                  const float* ms2_cond, const float* ms1_cond, const int64_t* t, const float* noise, int auto_normalize, int pred_type,
                  const float* loss_weight_dev, float* loss_out, float* per_window_out, void* workspace, int64_t workspace_bytes, int B, int RT,
                  void* stream) {
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0 || pred_type == DQ_PRED_V, "dq_eval_step: Unknown pred_type");
   DQ_REQUIRE(plan && params && alpha_bars_dev && x0 && ms2_cond && ms1_cond && t && noise && loss_out && per_window_out && workspace,
              "dq_eval_step: null argument");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_eval_step: Unknown pred_type");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || loss_weight_dev, "dq_eval_step: pred_type x0 needs the loss-weight (SNR) table");
+  DQ_REQUIRE(pred_type != DQ_PRED_X0 || loss_weight_dev, "dq_eval_step: pred_type x0 needs the loss-weight (SNR) table");
   DQ_REQUIRE(B > 0 && RT > 0, "dq_eval_step: B and RT must be positive");
   DQ_TRY(ensure_arena(plan, B, RT));
   const Arena& a = plan->arena;
@@ -316,9 +324,13 @@ int dq_eval_step(dq_plan* plan, const float* params, const float* rope_freqs, co
   const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
   DQ_TRY(launch_q_sample(alpha_bars_dev, x0, t, noise, c.w(a.xa), B, per, auto_normalize, s));                 // model.py:349-352
   DQ_TRY(unet_forward(c, rope_freqs, c.w(a.xa), t, 0, ms2_cond, ms1_cond, cm, ca, plan->dev, c.w(a.eps)));  // model.py:359
+  const int64_t slice_bytes = (int64_t)sizeof(float) * ((B * per + 63) / 64 * 64);
+  if (pred_type == DQ_PRED_V)  // the target is sa_b noise - sb_b (normalised x0), weighted by loss_weight[t_b] (null: 1)
+    return launch_mse_per_window_v(c.w(a.eps), x0, noise, alpha_bars_dev, cm, ca, loss_weight_dev, t, per_window_out, loss_out, c.w(a.xb), slice_bytes,
+                                   B, per, s);
   const bool px0 = pred_type == DQ_PRED_X0;  // model.py:361 / 372-376: the target is the noise, or the normalised x0 weighted by loss_weight[t_b]
   return launch_mse_per_window(c.w(a.eps), px0 ? x0 : noise, px0 ? cm : 1.f, px0 ? ca : 0.f, px0 ? loss_weight_dev : nullptr, t,
-                               per_window_out, loss_out, c.w(a.xb), (int64_t)sizeof(float) * ((B * per + 63) / 64 * 64), B, per, s);
+                               per_window_out, loss_out, c.w(a.xb), slice_bytes, B, per, s);
 }
 
 int64_t dq_mse_per_window_scratch_bytes(int B, int64_t per) { return mse_per_window_scratch_bytes(B, per); }
@@ -328,6 +340,20 @@ int dq_mse_per_window(const float* out, const float* target, float tm, float ta,
   DQ_REQUIRE(B > 0 && per > 0, "dq_mse_per_window: B and per must be positive");
   return launch_mse_per_window(out, target, tm, ta, lw, t, per_window_out, loss_out, scratch, mse_per_window_scratch_bytes(B, per), B, per,
                                (hipStream_t)stream);
+}
+
+int dq_mse_loss_v_fwd_bwd(const float* pred, const float* x0, const float* noise, const float* alpha_bars_dev, float tm, float ta, const float* lw,
+                          const int64_t* t, float* loss_out, float* grad_out, float* scratch, int B, int64_t per, void* stream) {
+  DQ_REQUIRE(pred && x0 && noise && alpha_bars_dev && t && loss_out && scratch, "dq_mse_loss_v_fwd_bwd: null argument");
+  DQ_REQUIRE(B > 0 && per > 0, "dq_mse_loss_v_fwd_bwd: B and per must be positive");
+  return launch_mse_v_fwd_bwd(pred, x0, noise, alpha_bars_dev, tm, ta, lw, t, loss_out, grad_out, scratch, B, per, (hipStream_t)stream);
+}
+
+int dq_mse_per_window_v(const float* out, const float* x0, const float* noise, const float* alpha_bars_dev, float tm, float ta, const float* lw,
+                        const int64_t* t, float* per_window_out, float* loss_out, void* scratch, int B, int64_t per, void* stream) {
+  DQ_REQUIRE(B > 0 && per > 0, "dq_mse_per_window_v: B and per must be positive");
+  return launch_mse_per_window_v(out, x0, noise, alpha_bars_dev, tm, ta, lw, t, per_window_out, loss_out, scratch, mse_per_window_scratch_bytes(B, per),
+                                 B, per, (hipStream_t)stream);
 }
 
 int dq_q_sample_repeats(const float* alpha_bars_dev, const float* x0, const int64_t* t, const float* noise, const uint64_t* seed_dev,

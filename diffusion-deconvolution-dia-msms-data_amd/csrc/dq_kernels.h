@@ -30,6 +30,15 @@ constexpr int MSE_PW_SLICE = 8192;  // elements of a window one block of k_mse_p
 int64_t mse_per_window_scratch_bytes(int B, int64_t per);
 int launch_mse_per_window(const float* out, const float* target, float tm, float ta, const float* lw, const int64_t* t, float* per_window,
                           float* loss_out, void* scratch, int64_t scratch_bytes, int B, int64_t per, hipStream_t s);
+// the v objective: the target z = sa_b * noise - sb_b * (x0 * tm + ta), sa_b = sqrt(alpha_bars[t_b]), sb_b = sqrt(1 -
+// alpha_bars[t_b]), formed per element and never written; lw (nullable: 1) weights window b by lw[t_b].  Otherwise launch_mse_fwd_bwd
+// (grad_out nullable; defer_sum as there) and launch_mse_per_window.
+int launch_mse_v_fwd_bwd(const float* pred, const float* x0, const float* noise, const float* alpha_bars, float tm, float ta, const float* lw,
+                         const int64_t* t, float* loss_out, float* grad_out, float* partials, int B, int64_t per, hipStream_t s,
+                         int* defer_sum = nullptr);
+int launch_mse_per_window_v(const float* out, const float* x0, const float* noise, const float* alpha_bars, float tm, float ta, const float* lw,
+                            const int64_t* t, float* per_window, float* loss_out, void* scratch, int64_t scratch_bytes, int B, int64_t per,
+                            hipStream_t s);
 int launch_axpy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst += src
 int launch_zero(float* dst, int64_t n, hipStream_t s);  // dst = 0 (a kernel, not a memset node)
 int launch_copy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst = src (a kernel, not a memcpy node)
@@ -39,8 +48,8 @@ int launch_copy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst
 //               keyed by (seed, window id, element, draw index), seed and ids (nullable: 0 .. B-1) in device memory
 //   SOLVER      x_prev = cx*x + c0*x0 + c1*hist: rows [sa, sb, cx, c0], extra = c1, one float per row; x0 clamped to [-clip, clip] when
 //               clip > 0; hist (nullable when every c1 is 0) receives x0
-// step_ptr (nullable): the row index on the device (STOCHASTIC: and the draw index 1 + step), else row 0 and `draw`.  pred_x0: `net` is the
-// network's x0 prediction.  eps_out (nullable) receives the step's eps when it is not the network output itself (always, for a guided or
+// step_ptr (nullable): the row index on the device (STOCHASTIC: and the draw index 1 + step), else row 0 and `draw`.  pred (DQ_PRED_*): what `net`
+// is -- the network's eps, x0 or v prediction.  eps_out (nullable) receives the step's eps when it is not the network output itself (always, for a guided or
 // SOLVER step).  guided (dq_guide.h): the same arithmetic on g = net_u + w (net - net_u) in place of the network
 // output, x_mirror (nullable) receives x_prev too.  Element-wise: x_prev may alias x_t, eps_out the network output.  Any count and any
 // 4-byte aligned tensors, except that the unguided STOCHASTIC form wants per % 4 == 0 and 16-byte aligned tensors; 16-byte accesses iff
@@ -49,7 +58,7 @@ enum class UpdateFamily { DDIM, STOCHASTIC, SOLVER };
 struct StepUpdateLaunch {
   UpdateFamily family = UpdateFamily::DDIM;
   bool guided = false;
-  int pred_x0 = 0;
+  int pred = 0;  // DQ_PRED_*
   const float* x_t = nullptr; const float* net = nullptr; const float* net_u = nullptr;
   float* x_prev = nullptr; float* x_mirror = nullptr; float* hist = nullptr; float* eps_out = nullptr;
   const float* coef = nullptr; const float* extra = nullptr;
@@ -277,7 +286,7 @@ struct LevelFwd {
   // head epilogue (C == 4, inference; behind the last block): eps = final_conv(out) (ew (1, 4, 1), eb) -> eps_out (nullable), and with
   // x_t set the DDIM update of model.py:265-289 into x_out (coef: [sa, sb, sap, sbp] rows; step_ptr nullable: row index on the device)
   const float* ew = nullptr; const float* eb = nullptr; float* eps_out = nullptr;
-  const float* x_t = nullptr; float* x_out = nullptr; const float* coef = nullptr; const int* step_ptr = nullptr; int pred_x0 = 0;
+  const float* x_t = nullptr; float* x_out = nullptr; const float* coef = nullptr; const int* step_ptr = nullptr; int pred = 0;
   // training head (with ew / eb; the block's output is still written): loss_z = the regression target (rows, n).  d = eps - z; the squared-error
   // sums go to loss_part, one float per WAVE of the grid (*loss_parts_out receives their number: sum them in index order); grad_out (rows, n) =
   // d * loss_gscale (= d loss / d eps) -- times softplus'(pre) under final_act = FINAL_SOFTPLUS: always d loss / d (final_conv's output, before
@@ -285,6 +294,10 @@ struct LevelFwd {
   // k_mse_fwd_bwd and k_conv_bwd_data<4,1,0> did in three launches behind this one
   const float* loss_z = nullptr; float* loss_part = nullptr; float* grad_out = nullptr; float* dout = nullptr; float loss_gscale = 0.f;
   int* loss_parts_out = nullptr;
+  // ... under the v objective (vt_x0 set): loss_z is the NOISE and the target z = sa_b * noise - sb_b * (x0 * vt_tm + vt_ta),
+  // sa_b = sqrt(vt_ab[vt_t[b]]), sb_b = sqrt(1 - vt_ab[vt_t[b]]), is formed per element in the launch (never written); vt_lw (nullable: all
+  // ones) weights sample b's squared error and gradient by vt_lw[vt_t[b]] -- k_mse_v_fwd_bwd's arithmetic
+  const float* vt_x0 = nullptr; const float* vt_ab = nullptr; const int64_t* vt_t = nullptr; const float* vt_lw = nullptr; float vt_tm = 1.f, vt_ta = 0.f;
   // output activation of the head (FINAL_IDENTITY | FINAL_SOFTPLUS, with ew): with Softplus, eps_out, the DDIM update and the training
   // head's loss see y = softplus(final_conv(out))
   int final_act = 0;

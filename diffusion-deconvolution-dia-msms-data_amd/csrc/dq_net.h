@@ -35,7 +35,7 @@ struct Ctx {
   std::vector<ResWgReduce>* wg_defer = nullptr;
   // sampling (dq_ddim_sample): the DDIM update rides in the head launch (x_out may alias x_t), and the step-invariant MS1 feature path
   // (unet1d.py:1120-1130) + to_k + RoPE(k) were computed once before the loop
-  struct StepIO { const float* x_t = nullptr; float* x_out = nullptr; const float* coef = nullptr; const int* step_ptr = nullptr; int pred_x0 = 0;
+  struct StepIO { const float* x_t = nullptr; float* x_out = nullptr; const float* coef = nullptr; const int* step_ptr = nullptr; int pred = 0;
                   bool prologue = false; bool fused_update = false; bool want_eps = true; };  // prologue: unet_prepare and the MS1 path ran before the loop
   StepIO* step_io = nullptr;
   // dq_train_step: the scalar loss (sum of the MSE kernel's partials) is needed by nobody on the gradient chain: it rides on the side stream
@@ -43,7 +43,11 @@ struct Ctx {
   LossSum loss_sum;
   // dq_train_step: final_conv, the squared error against `z` and the first two steps of the backward (d eps -> grad_out, d fin.out) ride in
   // the final block's launch when it can take them (k_level_fwd's training head); `done` / `nparts` tell the caller
-  struct HeadLoss { const float* z = nullptr; float* grad_out = nullptr; float* part = nullptr; float gscale = 0.f; int nparts = 0; bool done = false; };
+  struct HeadLoss {
+    const float* z = nullptr; float* grad_out = nullptr; float* part = nullptr; float gscale = 0.f; int nparts = 0; bool done = false;
+    // the v objective (x0 set): z is the noise, the target is formed in the launch (LevelFwd::vt_*)
+    const float* x0 = nullptr; const float* alpha_bars = nullptr; const int64_t* t = nullptr; const float* lw = nullptr; float tm = 1.f, ta = 0.f;
+  };
   HeadLoss* head_loss = nullptr;
   // dq_train_step: x_t = q_sample(x0, t, noise) (model.py:349-352) is formed by level 0's INIT stage when that stage runs (`x` of unet_forward is
   // then only the buffer x_t would have gone to); otherwise unet_forward launches k_q_sample into `x` first

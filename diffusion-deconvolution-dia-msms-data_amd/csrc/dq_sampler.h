@@ -19,7 +19,7 @@ struct StepUpdateArgs {
   const float* coef; const float* extra;
   float* hist;
   float clip;
-  int px0, B;
+  int pred, B;  // pred: DQ_PRED_*
   int64_t per;
   bool guided = false;
   float w = 1.f;
@@ -38,11 +38,11 @@ int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net
                        float* eps_out, int row, const int* step_ptr, const StepNoise& z, bool fused, hipStream_t s);
 
 // What a call's (eta, sampler, clip_x0) select.  clip_x0: the clamp as the kernels take it (0: off)
-struct SamplerChoice { StepUpdate kind = StepUpdate::DDIM; bool sto = false, clip = false; float clip_x0 = 0.f; int px0 = 0; };
+struct SamplerChoice { StepUpdate kind = StepUpdate::DDIM; bool sto = false, clip = false; float clip_x0 = 0.f; int pred = 0; };  // pred: DQ_PRED_*
 // The refusals every sampling loop makes, in one order, before anything touches the device; `who` prefixes the messages.  args_ok: the
-// caller's required pointers are all there.
+// caller's required pointers are all there; allow_v: DQ_PRED_V is a known objective for this caller (dq_ddim_sample_v).
 int sampler_check(const char* who, bool args_ok, float eta, int sampler, float clip_x0, const int32_t* timesteps_host, int num_steps,
-                  bool have_seed, bool have_xT, int pred_type, SamplerChoice* out);
+                  bool have_seed, bool have_xT, int pred_type, bool allow_v, SamplerChoice* out);
 // Forms the call's coefficient rows on the host and copies them to coef_dev (4 per step) and extra_dev (1 per step; nullable: not needed);
 // returns after the copies are done (the host vectors are the function's own)
 int sampler_upload_tables(const char* who, const float* alpha_bars_host, int T, const int32_t* ts, int num_steps, int sampler, const SamplerChoice& c,

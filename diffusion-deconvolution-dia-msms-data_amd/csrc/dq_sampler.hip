@@ -21,7 +21,7 @@ int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net
   if (fused && u.kind == StepUpdate::DDIM && !u.guided) return 0;  // (the head launch has done it; a guided update never rides there)
   StepUpdateLaunch a;
   a.family = u.kind == StepUpdate::DDIM ? UpdateFamily::DDIM : u.kind == StepUpdate::STOCHASTIC ? UpdateFamily::STOCHASTIC : UpdateFamily::SOLVER;
-  a.guided = u.guided; a.pred_x0 = u.px0;
+  a.guided = u.guided; a.pred = u.pred;
   a.x_t = x; a.net = net_out; a.net_u = u.guided ? net_u : nullptr;
   a.x_prev = x_out; a.x_mirror = u.guided ? x_mirror : nullptr; a.eps_out = eps_out;
   a.hist = u.kind == StepUpdate::SOLVER_2M ? u.hist : nullptr;  // (first order: no history)
@@ -33,7 +33,7 @@ int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net
 }
 
 int sampler_check(const char* who, bool args_ok, float eta, int sampler, float clip_x0, const int32_t* timesteps_host, int num_steps,
-                  bool have_seed, bool have_xT, int pred_type, SamplerChoice* out) {
+                  bool have_seed, bool have_xT, int pred_type, bool allow_v, SamplerChoice* out) {
   const std::string w(who);
   DQ_REQUIRE(args_ok, w + ": null argument");
   DQ_REQUIRE(eta >= 0.f && eta <= 1.f, w + ": eta must satisfy 0 <= eta <= 1");  // (false for NaN)
@@ -51,8 +51,8 @@ int sampler_check(const char* who, bool args_ok, float eta, int sampler, float c
   out->kind = sampler == DQ_SAMPLER_DPMPP_2M ? StepUpdate::SOLVER_2M : clip ? StepUpdate::SOLVER_1 : sto ? StepUpdate::STOCHASTIC : StepUpdate::DDIM;
   out->sto = sto; out->clip = clip; out->clip_x0 = clip ? clip_x0 : 0.f;
   DQ_REQUIRE(have_seed || (have_xT && !sto), w + ": eta > 0 and a null x_T need the seed (device memory)");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, w + ": Unknown pred_type");
-  out->px0 = pred_type == DQ_PRED_X0;
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0 || (allow_v && pred_type == DQ_PRED_V), w + ": Unknown pred_type");
+  out->pred = pred_type;
   return 0;
 }
 
@@ -126,7 +126,7 @@ int eager_steps(const SampleLoop& L, float* traj_x, float* traj_eps, const int64
     float* xn = traj_x ? traj_x + (int64_t)i * n : (in_place ? xa : xb);
     bool fused = false;
     DQ_TRY(L.forward(xa, xn, i, nullptr, eps, traj_eps != nullptr, &fused, s));  // model.py:271 / :276
-    float* eps_out = !traj_eps ? nullptr : u.guided ? traj_eps + (int64_t)i * n : (u.px0 || L.clip) ? eps : nullptr;
+    float* eps_out = !traj_eps ? nullptr : u.guided ? traj_eps + (int64_t)i * n : (u.pred != DQ_PRED_EPS || L.clip) ? eps : nullptr;
     // (the mirror: the second half of the buffer the next forward reads -- xa when the step's x goes to a trajectory slot and is copied back)
     float* mirror = u.guided ? (traj_x ? xa : xn) + n : nullptr;
     DQ_TRY(launch_step_update(u, xa, eps, u.guided ? eps + n : nullptr, xn, mirror, eps_out, i, nullptr, StepNoise{window_ids_dev, seed_dev, 1 + i},
@@ -160,12 +160,13 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
                 const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type, const int32_t* timesteps_host, int num_steps,
                 float* out_x, float* out_noise, float* traj_x, float* traj_eps, int use_graph, void* workspace, int64_t workspace_bytes, int B,
                 int RT, void* stream, float eta, const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0,
-                const Guidance* g) {
-  const char* who = g ? "dq_ddim_sample_guided" : "dq_ddim_sample";
+                const Guidance* g, bool allow_v = false) {
+  // allow_v: the call came through dq_ddim_sample_v -- the pred_type argument of the other entries names the reference's two objectives
+  const char* who = allow_v ? "dq_ddim_sample_v" : g ? "dq_ddim_sample_guided" : "dq_ddim_sample";
   const std::string wh(who);
   SamplerChoice sc;
   DQ_TRY(sampler_check(who, plan && params && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
-                       eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, &sc));
+                       eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, allow_v, &sc));
   DQ_REQUIRE(!g || guidance_ok(g->w), wh + ": the guidance scale must be finite and >= 0");
   const StepUpdate kind = sc.kind;
   clip_x0 = sc.clip_x0;
@@ -205,7 +206,7 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
     }
     return 0;
   };
-  Ctx::StepIO io; io.pred_x0 = sc.px0;
+  Ctx::StepIO io; io.pred = sc.pred;
   // The step index of a captured step lives on the device: k_time_fwd reads ts_tab[*step], the update its coefficient row, k_inc_step bumps it.
   int* ts_tab = reinterpret_cast<int*>(c.w(a.ts_tab));
   // the forward of this network: captured over the staged conditions (all pointers inside the arena / parameter buffers), eagerly over the
@@ -221,7 +222,7 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
     *fused = io.fused_update;
     return rc;
   };
-  const SampleLoop loop{forward, StepUpdateArgs{kind, c.w(a.coef), c.w(a.sigma), c.w(a.xb), clip_x0, sc.px0, B, per, g != nullptr, g ? g->w : 1.f},
+  const SampleLoop loop{forward, StepUpdateArgs{kind, c.w(a.coef), c.w(a.sigma), c.w(a.xb), clip_x0, sc.pred, B, per, g != nullptr, g ? g->w : 1.f},
                         xa, c.w(a.eps), sc.clip, num_steps, ms2_cond, out_x, out_noise, auto_normalize};
   if (use_graph && !traj_x && !traj_eps) {
     // ---- hipGraph path: one step captured once, replayed per step
@@ -249,10 +250,10 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
 
 // The stand-alone updates: one step over caller-supplied tensors, row 0 of coef_dev (with sigma / c1 as a fifth float behind it); a plain
 // element count n is one window of n elements
-StepUpdateLaunch one_update(UpdateFamily family, int pred_x0, const float* x_t, const float* net, float* x_prev, float* eps_out,
+StepUpdateLaunch one_update(UpdateFamily family, int pred, const float* x_t, const float* net, float* x_prev, float* eps_out,
                                    const float* coef_dev, int B, int64_t per) {
   StepUpdateLaunch a;
-  a.family = family; a.pred_x0 = pred_x0;
+  a.family = family; a.pred = pred;
   a.x_t = x_t; a.net = net; a.x_prev = x_prev; a.eps_out = eps_out;
   a.coef = coef_dev; a.extra = coef_dev + 4;
   a.B = B; a.per = per;
@@ -264,13 +265,18 @@ StepUpdateLaunch one_update(UpdateFamily family, int pred_x0, const float* x_t, 
 extern "C" {
 
 int dq_ddim_step(const float* x_t, const float* eps, float* x_prev, const float* coef_dev, int64_t n, void* stream) {
-  return launch_update(one_update(UpdateFamily::DDIM, 0, x_t, eps, x_prev, nullptr, coef_dev, 1, n), (hipStream_t)stream);
+  return launch_update(one_update(UpdateFamily::DDIM, DQ_PRED_EPS, x_t, eps, x_prev, nullptr, coef_dev, 1, n), (hipStream_t)stream);
 }
 
 int dq_ddim_step_x0(const float* x_t, const float* x0_pred, float* x_prev, float* eps_out, const float* coef_dev, int64_t n,
                     void* stream) {
   DQ_REQUIRE(x_t && x0_pred && x_prev && coef_dev, "dq_ddim_step_x0: null argument");
-  return launch_update(one_update(UpdateFamily::DDIM, 1, x_t, x0_pred, x_prev, eps_out, coef_dev, 1, n), (hipStream_t)stream);
+  return launch_update(one_update(UpdateFamily::DDIM, DQ_PRED_X0, x_t, x0_pred, x_prev, eps_out, coef_dev, 1, n), (hipStream_t)stream);
+}
+
+int dq_ddim_step_v(const float* x_t, const float* v_pred, float* x_prev, float* eps_out, const float* coef_dev, int64_t n, void* stream) {
+  DQ_REQUIRE(x_t && v_pred && x_prev && coef_dev, "dq_ddim_step_v: null argument");
+  return launch_update(one_update(UpdateFamily::DDIM, DQ_PRED_V, x_t, v_pred, x_prev, eps_out, coef_dev, 1, n), (hipStream_t)stream);
 }
 
 int dq_randn(float* out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int B, int64_t per_window, void* stream) {
@@ -281,9 +287,9 @@ int dq_ddim_step_sto(const float* x_t, const float* net_out, float* x_prev, floa
                      const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window,
                      void* stream) {
   DQ_REQUIRE(x_t && net_out && x_prev && coef_dev && seed_dev, "dq_ddim_step_sto: null argument");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_ddim_step_sto: Unknown pred_type");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0 || pred_type == DQ_PRED_V, "dq_ddim_step_sto: Unknown pred_type");
   // (refused by launch_update: a per-window count that is no multiple of 4, tensors that are not 16-byte aligned)
-  StepUpdateLaunch a = one_update(UpdateFamily::STOCHASTIC, pred_type == DQ_PRED_X0, x_t, net_out, x_prev, pred_type == DQ_PRED_X0 ? eps_out : nullptr,
+  StepUpdateLaunch a = one_update(UpdateFamily::STOCHASTIC, pred_type, x_t, net_out, x_prev, pred_type != DQ_PRED_EPS ? eps_out : nullptr,
                                   coef_dev, B, per_window);
   a.ids = window_ids_dev; a.seed = seed_dev; a.draw = draw;
   return launch_update(a, (hipStream_t)stream);
@@ -292,8 +298,16 @@ int dq_ddim_step_sto(const float* x_t, const float* net_out, float* x_prev, floa
 int dq_solver_step(const float* x_t, const float* net_out, float* x_prev, float* x0_hist, float* eps_out, const float* coef_dev, float clip_x0,
                    int pred_type, int64_t n, void* stream) {
   DQ_REQUIRE(x_t && net_out && x_prev && coef_dev, "dq_solver_step: null argument");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_solver_step: Unknown pred_type");
-  StepUpdateLaunch a = one_update(UpdateFamily::SOLVER, pred_type == DQ_PRED_X0, x_t, net_out, x_prev, eps_out, coef_dev, 1, n);
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_solver_step: Unknown pred_type");  // (DQ_PRED_V: dq_solver_step_v)
+  StepUpdateLaunch a = one_update(UpdateFamily::SOLVER, pred_type, x_t, net_out, x_prev, eps_out, coef_dev, 1, n);
+  a.hist = x0_hist; a.clip = clip_x0;
+  return launch_update(a, (hipStream_t)stream);
+}
+
+int dq_solver_step_v(const float* x_t, const float* v_pred, float* x_prev, float* x0_hist, float* eps_out, const float* coef_dev, float clip_x0,
+                     int64_t n, void* stream) {
+  DQ_REQUIRE(x_t && v_pred && x_prev && coef_dev, "dq_solver_step_v: null argument");
+  StepUpdateLaunch a = one_update(UpdateFamily::SOLVER, DQ_PRED_V, x_t, v_pred, x_prev, eps_out, coef_dev, 1, n);
   a.hist = x0_hist; a.clip = clip_x0;
   return launch_update(a, (hipStream_t)stream);
 }
@@ -340,21 +354,54 @@ int dq_ddim_sample_guided(dq_plan* plan, const float* params, const float* rope_
                      window_ids_dev, sampler, clip_x0, &g);
 }
 
+}  // extern "C"
+
+namespace {
+// dq_guided_update and dq_guided_update_v: `who` prefixes the refusals
+int guided_update(const std::string& who, int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror,
+                  float* x0_hist, float* eps_out, const float* coef_dev, float w, float clip_x0, const int64_t* window_ids_dev,
+                  const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window, void* stream) {
+  DQ_REQUIRE(x_t && net_c && net_u && x_prev && coef_dev, who + ": null argument");
+  DQ_REQUIRE(kind == DQ_UPDATE_DDIM || kind == DQ_UPDATE_STOCHASTIC || kind == DQ_UPDATE_SOLVER_1 || kind == DQ_UPDATE_SOLVER_2M,
+             who + ": unknown update kind");
+  DQ_REQUIRE(kind != DQ_UPDATE_STOCHASTIC || seed_dev, who + ": the stochastic update needs the seed (device memory)");
+  DQ_REQUIRE(kind != DQ_UPDATE_SOLVER_2M || x0_hist, who + ": the 2M update needs the x0 history");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0 || pred_type == DQ_PRED_V, who + ": Unknown pred_type");
+  DQ_REQUIRE(guidance_ok(w), who + ": the guidance scale must be finite and >= 0");
+  DQ_REQUIRE(B >= 0 && per_window >= 0, who + ": negative size");
+  // coefficient layout per kind: the stand-alone entries' (4 floats, or 5 with sigma / c1 behind them)
+  const StepUpdateArgs u{(StepUpdate)kind, coef_dev, coef_dev + 4, x0_hist, clip_x0, pred_type, B, per_window, true, w};
+  return launch_step_update(u, x_t, net_c, net_u, x_prev, x_mirror, eps_out, 0, nullptr, StepNoise{window_ids_dev, seed_dev, draw}, false,
+                            (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" {
+
 int dq_guided_update(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
                      float* eps_out, const float* coef_dev, float w, float clip_x0, const int64_t* window_ids_dev, const uint64_t* seed_dev,
                      int draw, int pred_type, int B, int64_t per_window, void* stream) {
-  DQ_REQUIRE(x_t && net_c && net_u && x_prev && coef_dev, "dq_guided_update: null argument");
-  DQ_REQUIRE(kind == DQ_UPDATE_DDIM || kind == DQ_UPDATE_STOCHASTIC || kind == DQ_UPDATE_SOLVER_1 || kind == DQ_UPDATE_SOLVER_2M,
-             "dq_guided_update: unknown update kind");
-  DQ_REQUIRE(kind != DQ_UPDATE_STOCHASTIC || seed_dev, "dq_guided_update: the stochastic update needs the seed (device memory)");
-  DQ_REQUIRE(kind != DQ_UPDATE_SOLVER_2M || x0_hist, "dq_guided_update: the 2M update needs the x0 history");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_guided_update: Unknown pred_type");
-  DQ_REQUIRE(guidance_ok(w), "dq_guided_update: the guidance scale must be finite and >= 0");
-  DQ_REQUIRE(B >= 0 && per_window >= 0, "dq_guided_update: negative size");
-  // coefficient layout per kind: the stand-alone entries' (4 floats, or 5 with sigma / c1 behind them)
-  const StepUpdateArgs u{(StepUpdate)kind, coef_dev, coef_dev + 4, x0_hist, clip_x0, pred_type == DQ_PRED_X0, B, per_window, true, w};
-  return launch_step_update(u, x_t, net_c, net_u, x_prev, x_mirror, eps_out, 0, nullptr, StepNoise{window_ids_dev, seed_dev, draw}, false,
-                            (hipStream_t)stream);
+  // (this entry's pred_type names the reference's two objectives; DQ_PRED_V: dq_guided_update_v)
+  return guided_update("dq_guided_update", kind, x_t, net_c, net_u, x_prev, x_mirror, x0_hist, eps_out, coef_dev, w, clip_x0, window_ids_dev, seed_dev,
+                       draw, pred_type == DQ_PRED_V ? -1 : pred_type, B, per_window, stream);
+}
+
+int dq_guided_update_v(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
+                       float* eps_out, const float* coef_dev, float w, float clip_x0, const int64_t* window_ids_dev, const uint64_t* seed_dev,
+                       int draw, int B, int64_t per_window, void* stream) {
+  return guided_update("dq_guided_update_v", kind, x_t, net_c, net_u, x_prev, x_mirror, x0_hist, eps_out, coef_dev, w, clip_x0, window_ids_dev,
+                       seed_dev, draw, DQ_PRED_V, B, per_window, stream);
+}
+
+int dq_ddim_sample_v(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                     const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                     const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps, int use_graph,
+                     void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta, const uint64_t* seed_dev,
+                     const int64_t* window_ids_dev, int sampler, float clip_x0, int guided, float guidance_scale, float null_ms1) {
+  const Guidance g{guidance_scale, null_ms1};
+  return unet_sample(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type, timesteps_host,
+                     num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream, eta, seed_dev,
+                     window_ids_dev, sampler, clip_x0, guided ? &g : nullptr, true);
 }
 
 int dq_ms1_cond_drop(const float* ms1_in, float* ms1_out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, double p,

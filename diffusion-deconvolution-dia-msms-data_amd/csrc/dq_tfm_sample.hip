@@ -138,7 +138,7 @@ int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const f
   SamplerChoice sc;
   DQ_TRY(sampler_check("dq_tfm_sample", p && params && rope_sin && rope_cos && time_freqs && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host &&
                                             out_x && out_noise && workspace,
-                       eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, &sc));
+                       eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, false, &sc));
   DQ_REQUIRE(B > 0 && S1 > 0 && S2 > 0 && num_steps >= 1 && num_steps <= 1024, "dq_tfm_sample: need B, S1, S2 > 0 and 1 <= num_steps <= 1024");
   const int T = num_timesteps;
   DQ_REQUIRE(T >= 1, "dq_tfm_sample: num_timesteps must be >= 1");
@@ -164,7 +164,7 @@ int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const f
     step.time_row = row; step.step_ptr = step_ptr;
     return tfm_walk(step, x, net_out, fs);
   };
-  const SampleLoop loop{forward, StepUpdateArgs{sc.kind, w.coef, w.sigma, w.xb, sc.clip_x0, sc.px0, B, per}, w.xa, w.eps, sc.clip,
+  const SampleLoop loop{forward, StepUpdateArgs{sc.kind, w.coef, w.sigma, w.xb, sc.clip_x0, sc.pred, B, per}, w.xa, w.eps, sc.clip,
                         num_steps, ms2_cond, out_x, out_noise, auto_normalize};
   if (net.attn_form == TFM_ATTN_FUSED) DQ_TRY(tfm_attn_prepare());  // (the LDS limit of this device, before any capture)
   // every call, outside any capture: a changed MS1, or changed weights behind the same pointer, cannot meet a stale cache

@@ -509,7 +509,7 @@ LevelFwd level_desc(const Ctx& c, const LevelCall& lc, int img_slot = -1) {
   if (lc.head) {
     f.ew = c.prm(lc.head->w); f.eb = c.prm(lc.head->b); f.final_act = c.p.final_act;
     if (c.step_io && c.step_io->x_t) {
-      f.x_t = c.step_io->x_t; f.x_out = c.step_io->x_out; f.coef = c.step_io->coef; f.step_ptr = c.step_io->step_ptr; f.pred_x0 = c.step_io->pred_x0;
+      f.x_t = c.step_io->x_t; f.x_out = c.step_io->x_out; f.coef = c.step_io->coef; f.step_ptr = c.step_io->step_ptr; f.pred = c.step_io->pred;
       f.eps_out = c.step_io->want_eps ? lc.eps_out : nullptr;  // (the trajectory's eps, when the caller keeps one)
     } else {
       f.eps_out = lc.eps_out;
@@ -819,6 +819,7 @@ int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t*
     LevelFwd f = level_desc(c, lh, lp.up[L].img);
     Ctx::HeadLoss& hl = *c.head_loss;
     f.loss_z = hl.z; f.grad_out = hl.grad_out; f.dout = c.g(a.fin.out); f.loss_part = hl.part; f.loss_gscale = hl.gscale; f.loss_parts_out = &hl.nparts;
+    f.vt_x0 = hl.x0; f.vt_ab = hl.alpha_bars; f.vt_t = hl.t; f.vt_lw = hl.lw; f.vt_tm = hl.tm; f.vt_ta = hl.ta;
     DQ_TRY(launch_level_fwd(f, c.s));
     hl.done = true;
     return 0;

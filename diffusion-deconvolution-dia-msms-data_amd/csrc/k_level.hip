@@ -33,6 +33,7 @@
 #include "dq_common.h"
 #include "dq_kernels.h"
 #include "dq_probe.h"
+#include "../../include/dq_hip.h"  // DQ_PRED_*
 #include <algorithm>
 
 namespace dq {
@@ -80,14 +81,25 @@ struct LevelFwdK {
   int pw, pb, nblocks, rows_per_sample, n, ss_stride;
   LevelBlkK blk[2];
   // INIT stage: the mixture (rows, n), its normalisation cond * cm + ca, the offset of init_cond_proj's [scale, shift] in the ss vector
-  const float* cond; float cm, ca; int ss_init;
+  // The INIT stage's operands share their storage with the v objective's training head (VT instantiations: the head launch, which has no
+  // INIT stage, so no launch reads both members of a pair).  The struct keeps the parent layout -- every other instantiation its registers.
+  union { const float* cond; const float* vt_x0; };   // | the v target's x0 (rows, n)
+  union { float cm; float vt_tm; };                   // | x0 * vt_tm + vt_ta: its normalisation
+  union { float ca; float vt_ta; };
+  int ss_init;
   float* cat0_out;  // (TH instantiation of the INIT stage)
-  const float* qs_noise; const float* qs_ab; const int64_t* qs_t; int qs_norm;  // (TH, nullable: x_t = sqrt(ab) x0 + sqrt(1 - ab) noise formed here)
+  // (TH, nullable: x_t = sqrt(ab) x0 + sqrt(1 - ab) noise formed here)
+  union { const float* qs_noise; const float* vt_lw; };   // | the loss-weight table (nullable: 1): sample b times vt_lw[vt_t[b]]
+  union { const float* qs_ab; const float* vt_ab; };      // | the alpha-bar table
+  union { const int64_t* qs_t; const int64_t* vt_t; };    // | the samples' timesteps
+  int qs_norm;
   // head epilogue (ep_w >= 0): final_conv weight / bias offsets in P; eps_out nullable; DDIM update when x_t is set
-  int ep_w, ep_b, pred_x0;
+  int ep_w, ep_b, pred;  // pred: DQ_PRED_EPS / DQ_PRED_X0, what the network output is for the update (DQ_PRED_V: the VT instantiations)
   float* eps_out; const float* x_t; float* x_out; const float* coef; const int* step_ptr;
   // training head: target, per-wave squared-error sums, d loss / d (final_conv's output), d loss / d (block output)
   const float* loss_z; float* loss_part; float* grad_out; float* dout; float loss_gscale;
+  // ... under the v objective (VT instantiations) loss_z is the noise and the target sa_b * noise - sb_b * (vt_x0 * vt_tm + vt_ta) is formed
+  // per element from vt_ab[vt_t[b]] (the vt_* members above)
 };
 
 }  // namespace
@@ -150,7 +162,7 @@ __global__ void __launch_bounds__(256) k_level_images(LevelImgMulti mm, const fl
 // head took every C = 4 kernel from 77 to 87: five instead of six workgroups per CU)
 // FA: the head's output activation (LevelFwd::final_act, FINAL_IDENTITY | FINAL_SOFTPLUS), compiled in for the same reason: the
 // identity instantiations are the code they were before the option existed
-template <int C, int PRE, int CP, bool N64, bool TH = false, int FA = FINAL_IDENTITY>
+template <int C, int PRE, int CP, bool N64, bool TH = false, int FA = FINAL_IDENTITY, bool VT = false>
 __global__ void __launch_bounds__(256) k_level_fwd(LevelFwdK a, const float* __restrict__ P, const float* __restrict__ ssb, int tiles_ps, int total_tiles,
                                                    int ln_rt, const float* __restrict__ img) {  // ssb: the per-sample scale / shift vectors; ln_rt = log2(n)
   // N64: the row length is a compile-time 64 -- a channel's plane offset (c * 256 bytes) then folds into the instructions' immediate offsets
@@ -283,6 +295,13 @@ __global__ void __launch_bounds__(256) k_level_fwd(LevelFwdK a, const float* __r
     }
   }
   float lacc = 0.f;  // training head: this lane's sum of squared errors
+  float vsa = 0.f, vsb = 0.f, vw = 1.f;  // training head, v objective: this sample's sqrt(ab), sqrt(1 - ab) (k_q_sample's) and loss weight
+  if constexpr (VT && TH) {
+    const int64_t tb = a.vt_t[b];
+    const float ab = a.vt_ab[tb];
+    vsa = sqrtf(ab); vsb = sqrtf(1.0f - ab);
+    if (a.vt_lw) vw = a.vt_lw[tb];
+  }
 #pragma unroll 1
   for (int tile = wid; tile < tiles_ps; tile += nwaves) {  // the workgroups of a sample share its tiles; the grid is one resident round
     const int it = tile * 64 + lane;
@@ -630,22 +649,27 @@ __global__ void __launch_bounds__(256) k_level_fwd(LevelFwdK a, const float* __r
           const float ev = FA == FINAL_SOFTPLUS ? softplus_f(pre) : pre;  // the network output (final_act, unet1d.py:1166)
           const unsigned eoff = ((row << ln) + p) * 4u;
           if (live) {
-            float ep = ev;  // what eps_out receives: the network output, or -- while sampling with the x0 objective -- the derived eps
+            float ep = ev;  // what eps_out receives: the network output, or -- while sampling with the x0 or v objective -- the derived eps
             if (a.x_t) {  // model.py:265-289, the arithmetic of k_ddim_step
               const float xv = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.x_t) + eoff);
               float x0;
-              if (a.pred_x0) { x0 = ev; ep = (xv - dsa * x0) / dsb; }
-              else           { x0 = (xv - dsb * ep) / dsa; }
+              if constexpr (VT) { x0 = dsa * xv - dsb * ev; ep = dsb * xv + dsa * ev; }  // the v objective: no division
+              else if (a.pred) { x0 = ev; ep = (xv - dsa * x0) / dsb; }                  // (DQ_PRED_X0)
+              else             { x0 = (xv - dsb * ep) / dsa; }
               *reinterpret_cast<float*>(reinterpret_cast<char*>(a.x_out) + eoff) = dsap < 0.f ? x0 : dsap * x0 + dsbp * ep;
             }
             if (a.eps_out) *reinterpret_cast<float*>(reinterpret_cast<char*>(a.eps_out) + eoff) = ep;
           }
           if constexpr (TH && PRE != LEVEL_PRE_INIT) {  // training: model.py:361 and the first two steps of its backward, k_mse_fwd_bwd's arithmetic per element
-            const float z = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.loss_z) + eoff);  // (not predicated: a clamped position)
+            float z = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.loss_z) + eoff);  // (not predicated: a clamped position)
+            if constexpr (VT) {  // v = sa eps - sb x0, k_mse_v_fwd_bwd's arithmetic: the target is never written to memory
+              const float xz = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.vt_x0) + eoff);
+              z = vsa * z - vsb * (xz * a.vt_tm + a.vt_ta);
+            }
             const float d = ev - z;
             if (live) {
-              lacc += d * d;
-              float gv = d * a.loss_gscale;
+              lacc += VT ? vw * (d * d) : d * d;
+              float gv = d * (VT ? a.loss_gscale * vw : a.loss_gscale);
               if constexpr (FA == FINAL_SOFTPLUS) gv *= softplus_grad_f(pre);  // d loss / d pre: the value grad_out and d fin.out carry
               *reinterpret_cast<float*>(reinterpret_cast<char*>(a.grad_out) + eoff) = gv;
               st(a.dout, 0, obase, w4.x * gv); st(a.dout, 1, obase, w4.y * gv); st(a.dout, 2, obase, w4.z * gv); st(a.dout, 3, obase, w4.w * gv);
@@ -747,9 +771,14 @@ int launch_level_fwd(const LevelFwd& a, hipStream_t s) {
   DQ_REQUIRE(!a.qs_noise || (a.cat0_out && a.qs_ab && a.qs_t), "level_fwd: q_sample in the first-layer stage needs the schedule, the timesteps and cat0_out");
   k.qs_noise = a.qs_noise; k.qs_ab = a.qs_ab; k.qs_t = a.qs_t; k.qs_norm = a.qs_norm;
   k.loss_z = a.loss_z; k.loss_part = a.loss_part; k.grad_out = a.grad_out; k.dout = a.dout; k.loss_gscale = a.loss_gscale;
+  DQ_REQUIRE(!a.vt_x0 || (a.loss_z && a.vt_ab && a.vt_t && a.pre != LEVEL_PRE_INIT && !a.cond && !a.qs_noise),
+             "level_fwd: the v-objective training head needs the noise, the schedule and the timesteps, in a launch without the first-layer stage");
   k.cond = a.cond; k.cm = a.cm; k.ca = a.ca; k.ss_init = a.ss_init ? (int)(a.ss_init - a.blk[0].ss) : 0;
-  k.ep_w = poff(a.ew); k.ep_b = poff(a.eb); k.pred_x0 = a.pred_x0; k.eps_out = a.eps_out; k.x_t = a.x_t; k.x_out = a.x_out; k.coef = a.coef;
+  k.ep_w = poff(a.ew); k.ep_b = poff(a.eb); k.pred = a.pred; k.eps_out = a.eps_out; k.x_t = a.x_t; k.x_out = a.x_out; k.coef = a.coef;
   k.step_ptr = a.step_ptr;
+  if (a.vt_x0) {  // (the members that share storage with the INIT stage's: LevelFwdK; the check above keeps the two apart)
+    k.vt_x0 = a.vt_x0; k.vt_ab = a.vt_ab; k.vt_t = a.vt_t; k.vt_lw = a.vt_lw; k.vt_tm = a.vt_tm; k.vt_ta = a.vt_ta;
+  }
   k.in = a.in; k.pre_out = a.pre_out; k.pw = poff(a.pw); k.pb = poff(a.pb); k.nblocks = a.nblocks; k.rows_per_sample = a.rows_per_sample; k.n = a.n;
   const float* ssb = a.blk[0].ss;
   k.ss_stride = a.blk[0].ss_stride;
@@ -804,8 +833,31 @@ int launch_level_fwd(const LevelFwd& a, hipStream_t s) {
     if (CC == 4 && a.n == 64) DQ_LVN(CC, PP, PC, (CC == 4))                                                                    \
     DQ_LVN(CC, PP, PC, false)                                                                                                 \
   }
+  if (a.x_t && a.pred == DQ_PRED_V) {  // sampling under the v objective: the update's third form has its own instantiations (VT), so that
+    // the eps / x0 ones keep the registers they had -- the final block's launch, k3 stage conv from 4 or 8 channels, either output activation
+    DQ_REQUIRE(a.C == 4 && a.pre == LEVEL_PRE_S1 && (cp == 4 || cp == 8) && !a.loss_z,
+               "level_fwd: the v-objective sampling head is built for the (4, k3 conv, 4 | 8) launch");
+    if (a.final_act == FINAL_SOFTPLUS) {
+      if (cp == 4) {
+        if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, false, FINAL_SOFTPLUS, true>))
+        DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, false, FINAL_SOFTPLUS, true>))
+      }
+      if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 8, true, false, FINAL_SOFTPLUS, true>))
+      DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 8, false, false, FINAL_SOFTPLUS, true>))
+    }
+    if (cp == 4) {
+      if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, false, FINAL_IDENTITY, true>))
+      DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, false, FINAL_IDENTITY, true>))
+    }
+    if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 8, true, false, FINAL_IDENTITY, true>))
+    DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 8, false, false, FINAL_IDENTITY, true>))
+  }
   if (a.final_act == FINAL_SOFTPLUS) {  // the Softplus head (pos_output_only): the final block's launch, k3 stage conv from 4 or 8 channels
     DQ_REQUIRE(a.C == 4 && a.pre == LEVEL_PRE_S1 && (cp == 4 || (cp == 8 && !a.loss_z)), "level_fwd: the Softplus head is built for the (4, k3 conv, 4 | 8) launch");
+    if (a.loss_z && a.vt_x0) {
+      if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, true, FINAL_SOFTPLUS, true>))
+      DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, true, FINAL_SOFTPLUS, true>))
+    }
     if (a.loss_z) {
       if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, true, FINAL_SOFTPLUS>))
       DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, true, FINAL_SOFTPLUS>))
@@ -819,6 +871,10 @@ int launch_level_fwd(const LevelFwd& a, hipStream_t s) {
   }
   if (a.loss_z) {  // the training head has its own instantiations (the network's final block: k3 stage conv from 4 channels)
     DQ_REQUIRE(a.C == 4 && a.pre == LEVEL_PRE_S1 && cp == 4, "level_fwd: the training head is built for the (4, k3 conv, 4) launch");
+    if (a.vt_x0) {  // (the v objective's target)
+      if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, true, FINAL_IDENTITY, true>))
+      DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, true, FINAL_IDENTITY, true>))
+    }
     if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, true>))
     DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, true>))
   }

@@ -227,6 +227,70 @@ int launch_mse_fwd_bwd(const float* eps, const float* noise, float* loss_out, fl
   return launch_sum_partials(partials, grid, 1.0f / (float)n, loss_out, s);
 }
 
+// ---- K10 under the v objective (pred_type "v_prediction"): the target z = sa_b * noise - sb_b * (x0 * tm + ta) with
+// sa_b = sqrt(ab[t_b]), sb_b = sqrt(1 - ab[t_b]) (k_q_sample's two square roots) is formed per element and never written : 16 B / element.
+// lw (nullable: 1) weights sample b by lw[t_b] as in the weighted form above.  V = 4: 16 B per lane (per % 4 == 0, so no lane's four
+// elements straddle two samples); V = 1: any count.  nv, perv: the element count and the per-sample count in units of V.
+template <int V>
+__global__ void __launch_bounds__(256) k_mse_v_fwd_bwd(const float* __restrict__ pred, const float* __restrict__ x0, const float* __restrict__ noise,
+                                                       const float* __restrict__ alpha_bars, float* __restrict__ grad, float* __restrict__ partials,
+                                                       int64_t nv, float gscale, const float* __restrict__ lw, const int64_t* __restrict__ t,
+                                                       int64_t perv, float tm, float ta) {
+  float acc = 0.f;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t tb = t[i / perv];
+    const float ab = alpha_bars[tb];
+    const float sa = sqrtf(ab), sb = sqrtf(1.0f - ab);
+    const float w = lw ? lw[tb] : 1.f;
+    float e[V], x[V], z[V], g[V];
+    if constexpr (V == 4) {
+      const float4 e4 = reinterpret_cast<const float4*>(pred)[i], x4 = reinterpret_cast<const float4*>(x0)[i], z4 = reinterpret_cast<const float4*>(noise)[i];
+      e[0] = e4.x; e[1] = e4.y; e[2] = e4.z; e[3] = e4.w;
+      x[0] = x4.x; x[1] = x4.y; x[2] = x4.z; x[3] = x4.w;
+      z[0] = z4.x; z[1] = z4.y; z[2] = z4.z; z[3] = z4.w;
+    } else {
+      e[0] = pred[i]; x[0] = x0[i]; z[0] = noise[i];
+    }
+    const float gs = gscale * w;
+    float sq = 0.f;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const float d = e[j] - (sa * z[j] - sb * (x[j] * tm + ta));
+      sq += d * d;
+      g[j] = d * gs;
+    }
+    acc += w * sq;
+    if (grad) {
+      if constexpr (V == 4) reinterpret_cast<float4*>(grad)[i] = make_float4(g[0], g[1], g[2], g[3]);
+      else grad[i] = g[0];
+    }
+  }
+  __shared__ float red[4];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+int launch_mse_v_fwd_bwd(const float* pred, const float* x0, const float* noise, const float* alpha_bars, float tm, float ta, const float* lw,
+                         const int64_t* t, float* loss_out, float* grad_out, float* partials, int B, int64_t per, hipStream_t s, int* defer_sum) {
+  DQ_REQUIRE(pred && x0 && noise && alpha_bars && t && partials && (loss_out || defer_sum), "mse_v: null argument");
+  DQ_REQUIRE(B > 0 && per > 0, "mse_v: B and per must be positive");
+  const int64_t n = (int64_t)B * per;
+  const uintptr_t bits = (uintptr_t)pred | (uintptr_t)x0 | (uintptr_t)noise | (uintptr_t)grad_out;
+  const bool vec = per % 4 == 0 && (bits & 15) == 0;
+  const int grid = (int)std::min<int64_t>(cdiv(vec ? n / 4 : n, 256), MSE_MAX_BLOCKS);
+  if (vec)
+    hipLaunchKernelGGL(k_mse_v_fwd_bwd<4>, dim3(grid), dim3(256), 0, s, pred, x0, noise, alpha_bars, grad_out, partials, n / 4, 2.0f / (float)n, lw,
+                       t, per / 4, tm, ta);
+  else
+    hipLaunchKernelGGL(k_mse_v_fwd_bwd<1>, dim3(grid), dim3(256), 0, s, pred, x0, noise, alpha_bars, grad_out, partials, n, 2.0f / (float)n, lw, t,
+                       per, tm, ta);
+  DQ_LAUNCH_CHECK();
+  if (defer_sum) { *defer_sum = grid; return 0; }  // (as launch_mse_fwd_bwd)
+  return launch_sum_partials(partials, grid, 1.0f / (float)n, loss_out, s);
+}
+
 // ---- held-out loss (dq_mse_per_window, dq_eval_step): per-window MSE and its weighted mean, forward only : 8 B / element
 // target' = target * tm + ta in fp32 (one multiply, one add: what k_mse_fwd_bwd forms), d = (double)out - (double)target', d * d summed in
 // fp64.  One block per (slice of MSE_PW_SLICE elements, window): the partition of a window depends on `per` alone, never on B, and the
@@ -292,6 +356,50 @@ int launch_mse_per_window(const float* out, const float* target, float tm, float
   const int64_t nslices = (per + MSE_PW_SLICE - 1) / MSE_PW_SLICE;
   DQ_REQUIRE(nslices <= INT32_MAX, "mse_per_window: window too large");
   hipLaunchKernelGGL(k_mse_per_window, dim3((unsigned)nslices, B), dim3(256), 0, s, out, target, tm, ta, (double*)scratch, per, (int)nslices);
+  DQ_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_mse_per_window_finish, dim3(1), dim3(256), 0, s, (const double*)scratch, lw, t, per_window, loss_out, B, per,
+                     (int)nslices);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
+
+// the same under the v objective: the target sa_b * noise - sb_b * (x0 * tm + ta) in fp32 (k_mse_v_fwd_bwd's arithmetic), formed per
+// element : 12 B / element.  Slices, order and the finishing kernel are k_mse_per_window's.
+__global__ void __launch_bounds__(256) k_mse_per_window_v(const float* __restrict__ out, const float* __restrict__ x0, const float* __restrict__ noise,
+                                                          const float* __restrict__ alpha_bars, const int64_t* __restrict__ t, float tm, float ta,
+                                                          double* __restrict__ slices, int64_t per, int nslices) {
+  const int64_t b = blockIdx.y;
+  const int64_t i0 = (int64_t)blockIdx.x * MSE_PW_SLICE, i1 = min(per, i0 + MSE_PW_SLICE);
+  const float ab = alpha_bars[t[b]];
+  const float sa = sqrtf(ab), sb = sqrtf(1.0f - ab);
+  const float* __restrict__ o = out + b * per;
+  const float* __restrict__ x = x0 + b * per;
+  const float* __restrict__ z = noise + b * per;
+  double acc = 0.0;
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+    const float zt = sa * z[i] - sb * (x[i] * tm + ta);
+    const double d = (double)o[i] - (double)zt;
+    acc += d * d;
+  }
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s, 64);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) slices[b * nslices + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+int launch_mse_per_window_v(const float* out, const float* x0, const float* noise, const float* alpha_bars, float tm, float ta, const float* lw,
+                            const int64_t* t, float* per_window, float* loss_out, void* scratch, int64_t scratch_bytes, int B, int64_t per,
+                            hipStream_t s) {
+  DQ_REQUIRE(out && x0 && noise && alpha_bars && t && per_window && loss_out && scratch, "mse_per_window_v: null argument");
+  DQ_REQUIRE(B > 0 && B <= 65535 && per > 0, "mse_per_window_v: need 0 < B <= 65535 and per > 0");
+  DQ_REQUIRE(scratch_bytes >= mse_per_window_scratch_bytes(B, per), "mse_per_window_v: scratch too small (dq_mse_per_window_scratch_bytes)");
+  DQ_REQUIRE(((uintptr_t)scratch & 7) == 0, "mse_per_window_v: scratch must be 8-byte aligned");
+  const int64_t nslices = (per + MSE_PW_SLICE - 1) / MSE_PW_SLICE;
+  DQ_REQUIRE(nslices <= INT32_MAX, "mse_per_window_v: window too large");
+  hipLaunchKernelGGL(k_mse_per_window_v, dim3((unsigned)nslices, B), dim3(256), 0, s, out, x0, noise, alpha_bars, t, tm, ta, (double*)scratch, per,
+                     (int)nslices);
   DQ_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_mse_per_window_finish, dim3(1), dim3(256), 0, s, (const double*)scratch, lw, t, per_window, loss_out, B, per,
                      (int)nslices);

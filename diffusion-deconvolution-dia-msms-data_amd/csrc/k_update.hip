@@ -4,7 +4,7 @@
 //   Ddim    x0 = (x - sb*eps)/sa ; x_prev = sap*x0 + sbp*eps (t > 0) else x0                                    rows [sa, sb, sap, sbp]
 //   Sto     the same plus sigma * z, z drawn in the kernel (dq_philox.h) keyed by (seed, window id, element, draw)  rows [sa, sb, sap, c], sigma
 //   Solver  x_prev = cx*x + c0*x0 + c1*x0_hist, x0 optionally clamped (DPM-Solver++(2M); c1 == 0: first order)      rows [sa, sb, cx, c0], c1
-// and ONE kernel around them, k_step_update<family, PRED_X0, GUIDED, V>: the grid-stride loop that loads x, the network output (GUIDED:
+// and ONE kernel around them, k_step_update<family, PRED, GUIDED, V>: the grid-stride loop that loads x, the network output (GUIDED:
 // its two halves, combined by guide() of dq_guide.h) and the history, and stores x_prev, its mirror, the history and eps.  V = 4: 16 bytes
 // per lane and access; V = 1: one element, for counts that are no multiple of 4 and pointers that are not 16-byte aligned.  No LDS, no
 // atomics.  Bytes per element: 12 (Ddim, Sto), 20 - 24 (Solver); guided + 8 (the second half read, the mirror written); + 4 with eps_out.
@@ -13,6 +13,7 @@
 #include "dq_guide.h"
 #include "dq_kernels.h"
 #include "dq_philox.h"
+#include "../../include/dq_hip.h"  // DQ_PRED_*
 #include <algorithm>
 #include <string>
 
@@ -22,7 +23,8 @@ namespace dq {
 struct UpdateLane { float clip; uint64_t seed; int64_t win; uint32_t draw; };
 
 // ``coef`` is a device table of 4 floats per step [sa, sb, sap, sbp]; sap < 0 marks the t == 0 step.
-// PRED_X0 (model.py:274-278): the network output is its x0 prediction, eps = (x_t - sa*x0)/sb is derived.
+// PRED (DQ_PRED_*): DQ_PRED_X0 (model.py:274-278): the network output is its x0 prediction, eps = (x_t - sa*x0)/sb is derived.
+// DQ_PRED_V: the network output is v = sa*eps - sb*x0; x0 = sa*x_t - sb*v and eps = sb*x_t + sa*v, no division.
 struct DdimRow { float sa, sb, sap, sbp; bool last; };
 
 __device__ __forceinline__ DdimRow ddim_row(const float* coef, const int* step_ptr) {
@@ -31,15 +33,16 @@ __device__ __forceinline__ DdimRow ddim_row(const float* coef, const int* step_p
 }
 
 // One element: x_prev from x and the network output v (or, guided, from g in its place: dq_guide.h); the step's eps by reference
-template <bool PRED_X0>
+template <int PRED>
 __device__ __forceinline__ float ddim_elem(const DdimRow& r, float x, float v, float& ep) {
   float x0;
-  if (PRED_X0) { x0 = v; ep = (x - r.sa * x0) / r.sb; }
-  else         { ep = v; x0 = (x - r.sb * ep) / r.sa; }
+  if (PRED == DQ_PRED_V)       { x0 = r.sa * x - r.sb * v; ep = r.sb * x + r.sa * v; }
+  else if (PRED == DQ_PRED_X0) { x0 = v; ep = (x - r.sa * x0) / r.sb; }
+  else                         { ep = v; x0 = (x - r.sb * ep) / r.sa; }
   return r.last ? x0 : r.sap * x0 + r.sbp * ep;
 }
 
-// ddim_elem's arithmetic for x0 and eps (both objectives), then x_prev = (sap*x0 + c*eps) + sigma*z on a step with t > 0, x0 on the t == 0
+// ddim_elem's arithmetic for x0 and eps (every objective), then x_prev = (sap*x0 + c*eps) + sigma*z on a step with t > 0, x0 on the t == 0
 // step (sap < 0: no noise drawn, ddim_elem's result bit for bit).  coef: rows [sa, sb, sap, c]; sigma: one float per row.
 struct StoRow { float sa, sb, sap, c, sigma; bool last; };
 
@@ -51,17 +54,18 @@ __device__ __forceinline__ StoRow sto_row(const float* coef, const float* sigma_
 
 // One element: x_prev from x, the network output v (or, guided, g in its place) and the noise of element e of window w; the step's eps by
 // reference.  Guided, the noise of a window is drawn ONCE and the result goes through both stores: the two halves never see different noise.
-template <bool PRED_X0>
+template <int PRED>
 __device__ __forceinline__ float sto_elem(const StoRow& r, float x, float v, uint64_t seed, int64_t w, uint32_t e, uint32_t draw, float& ep) {
   float x0;
-  if (PRED_X0) { x0 = v; ep = (x - r.sa * x0) / r.sb; }
-  else         { ep = v; x0 = (x - r.sb * ep) / r.sa; }
+  if (PRED == DQ_PRED_V)       { x0 = r.sa * x - r.sb * v; ep = r.sb * x + r.sa * v; }
+  else if (PRED == DQ_PRED_X0) { x0 = v; ep = (x - r.sa * x0) / r.sb; }
+  else                         { ep = v; x0 = (x - r.sb * ep) / r.sa; }
   float z = 0.f;
   if (!r.last) z = philox_normal(seed, w, e, draw);  // (uniform: the t == 0 step draws nothing)
   return r.last ? x0 : (r.sap * x0 + r.c * ep) + r.sigma * z;
 }
 
-// One linear multistep row per step; x0 is the network output (x0 objective) or (x - sb * e) / sa (eps objective), optionally clamped to
+// One linear multistep row per step; x0 is the network output (x0 objective), (x - sb * e) / sa (eps objective) or sa*x - sb*v (v objective), optionally clamped to
 // [-clip, clip] before it is used and before it becomes the next step's history.  cx < 0 marks the last row: x_prev = x0.
 struct SolverRow { float sa, sb, cx, c0, c1; };
 
@@ -71,16 +75,17 @@ __device__ __forceinline__ SolverRow solver_row(const float* coef, const float* 
 }
 
 // One element.  `h` is read by the caller only when c1 != 0.  Returns x_prev; x0 (clamped) and eps by reference.
-template <bool PRED_X0>
+template <int PRED>
 __device__ __forceinline__ float solver_elem(const SolverRow& r, float clip, float x, float v, float h, float& x0, float& ep) {
-  if (PRED_X0) { x0 = v; }
-  else         { ep = v; x0 = (x - r.sb * ep) / r.sa; }
+  if (PRED == DQ_PRED_V)       { x0 = r.sa * x - r.sb * v; ep = r.sb * x + r.sa * v; }
+  else if (PRED == DQ_PRED_X0) { x0 = v; }
+  else                         { ep = v; x0 = (x - r.sb * ep) / r.sa; }
   bool clamped = false;
   if (clip > 0.f) {
     if (x0 < -clip) { x0 = -clip; clamped = true; }
     else if (x0 > clip) { x0 = clip; clamped = true; }
   }
-  if (PRED_X0 || clamped) ep = (x - r.sa * x0) / r.sb;  // eps consistent with the x0 that is used
+  if (PRED == DQ_PRED_X0 || clamped) ep = (x - r.sa * x0) / r.sb;  // eps consistent with the x0 that is used
   if (r.cx < 0.f) return x0;
   const float y = r.cx * x + r.c0 * x0;
   return r.c1 != 0.f ? y + r.c1 * h : y;
@@ -93,9 +98,9 @@ struct Ddim {
   using Row = DdimRow;
   static constexpr bool HIST = false, WINDOW = false, EPS_IS_NET = true, RESTRICT = true;
   static __device__ __forceinline__ Row row(const float* coef, const float*, const int* step_ptr, uint32_t&) { return ddim_row(coef, step_ptr); }
-  template <bool PRED_X0>
+  template <int PRED>
   static __device__ __forceinline__ float elem(const Row& r, const UpdateLane&, float x, float v, float, uint32_t, float&, float& ep) {
-    return ddim_elem<PRED_X0>(r, x, v, ep);
+    return ddim_elem<PRED>(r, x, v, ep);
   }
 };
 struct Sto {
@@ -104,9 +109,9 @@ struct Sto {
   static __device__ __forceinline__ Row row(const float* coef, const float* sigma_tab, const int* step_ptr, uint32_t& draw) {
     return sto_row(coef, sigma_tab, step_ptr, draw);
   }
-  template <bool PRED_X0>
+  template <int PRED>
   static __device__ __forceinline__ float elem(const Row& r, const UpdateLane& k, float x, float v, float, uint32_t e, float&, float& ep) {
-    return sto_elem<PRED_X0>(r, x, v, k.seed, k.win, e, k.draw, ep);
+    return sto_elem<PRED>(r, x, v, k.seed, k.win, e, k.draw, ep);
   }
 };
 struct Solver {
@@ -116,9 +121,9 @@ struct Solver {
     return solver_row(coef, c1_tab, step_ptr);
   }
   static __device__ __forceinline__ bool reads_hist(const Row& r) { return r.c1 != 0.f && r.cx >= 0.f; }  // the first step's history is uninitialised memory
-  template <bool PRED_X0>
+  template <int PRED>
   static __device__ __forceinline__ float elem(const Row& r, const UpdateLane& k, float x, float v, float h, uint32_t, float& x0, float& ep) {
-    return solver_elem<PRED_X0>(r, k.clip, x, v, h, x0, ep);
+    return solver_elem<PRED>(r, k.clip, x, v, h, x0, ep);
   }
 };
 
@@ -139,7 +144,7 @@ template <> struct UpdatePtr<true> { using in = const float* __restrict__; using
 
 // nv, perv: the element count and the per-window count in units of V.  The window of lane-step i is i / perv, its first element
 // V * (i % perv): a lane's elements never straddle two windows (V == 4 runs only when the per-window count is a multiple of 4).
-template <class F, bool PRED_X0, bool GUIDED, int V>
+template <class F, int PRED, bool GUIDED, int V>
 __global__ void __launch_bounds__(256) k_step_update(typename UpdatePtr<F::RESTRICT && !GUIDED>::in x_t, typename UpdatePtr<F::RESTRICT && !GUIDED>::in net_c,
                                                      typename UpdatePtr<F::RESTRICT && !GUIDED>::in net_u, typename UpdatePtr<F::RESTRICT && !GUIDED>::out x_prev,
                                                      typename UpdatePtr<F::RESTRICT && !GUIDED>::out x_mirror, typename UpdatePtr<F::RESTRICT && !GUIDED>::out hist,
@@ -171,18 +176,20 @@ __global__ void __launch_bounds__(256) k_step_update(typename UpdatePtr<F::RESTR
       k.win = ids ? ids[b] : b;
     }
 #pragma unroll
-    for (int j = 0; j < V; ++j) ov[j] = F::template elem<PRED_X0>(r, k, xv[j], nv_[j], hv[j], e0 + (uint32_t)j, zv[j], dv[j]);
+    for (int j = 0; j < V; ++j) ov[j] = F::template elem<PRED>(r, k, xv[j], nv_[j], hv[j], e0 + (uint32_t)j, zv[j], dv[j]);
     store_v<V>(x_prev, i, ov);
     if constexpr (GUIDED) { if (x_mirror) store_v<V>(x_mirror, i, ov); }
     if constexpr (F::HIST) { if (hist) store_v<V>(hist, i, zv); }
-    if constexpr (PRED_X0 || GUIDED || !F::EPS_IS_NET) { if (eps_out) store_v<V>(eps_out, i, dv); }
+    if constexpr (PRED != DQ_PRED_EPS || GUIDED || !F::EPS_IS_NET) { if (eps_out) store_v<V>(eps_out, i, dv); }
   }
 }
 
 template <class F, bool GUIDED, int V>
 static int launch_update_as(const StepUpdateLaunch& a, int64_t nv, hipStream_t s) {
   const int grid = (int)std::min<int64_t>(cdiv(nv, 256), 2048);
-  const auto kernel = a.pred_x0 ? k_step_update<F, true, GUIDED, V> : k_step_update<F, false, GUIDED, V>;
+  const auto kernel = a.pred == DQ_PRED_V    ? k_step_update<F, DQ_PRED_V, GUIDED, V>
+                      : a.pred == DQ_PRED_X0 ? k_step_update<F, DQ_PRED_X0, GUIDED, V>
+                                             : k_step_update<F, DQ_PRED_EPS, GUIDED, V>;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, a.x_t, a.net, a.net_u, a.x_prev, a.x_mirror, a.hist, a.eps_out, a.coef, a.extra, a.ids,
                      a.seed, (uint32_t)a.draw, a.clip > 0.f ? a.clip : 0.f /* (NaN and negatives: off) */, a.w, nv, a.per / V, a.step_ptr);
   DQ_LAUNCH_CHECK();

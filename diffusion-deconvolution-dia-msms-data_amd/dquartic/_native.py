@@ -9,7 +9,7 @@ LIB_PATH = os.environ.get("DQ_HIP_LIB", os.path.join(os.path.dirname(_HERE), "li
 
 _lib = None
 ABI_VERSION = 12  # DQ_ABI_VERSION of include/dq_hip.h this table was written against
-PRED_TYPES = {"eps": 0, "x0": 1}  # DQ_PRED_EPS / DQ_PRED_X0
+PRED_TYPES = {"eps": 0, "x0": 1, "v_prediction": 2}  # DQ_PRED_EPS / DQ_PRED_X0 / DQ_PRED_V
 SAMPLERS = {"reference": 0, "ddim": 1, "dpmpp_2m": 2}  # DQ_SAMPLER_*
 UPDATE_KINDS = {"ddim": 0, "stochastic": 1, "solver_1": 2, "solver_2m": 3}  # DQ_UPDATE_* (dq_guided_update)
 PRECISIONS = {"fp32": 0, "bf16x3": 1}  # DQ_PRECISION_FP32 / DQ_PRECISION_BF16X3
@@ -45,6 +45,11 @@ PROTOTYPES = {
     "dq_q_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]),
     "dq_ddim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "dq_ddim_step_x0": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "dq_ddim_step_v": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "dq_mse_loss_v_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int, c_int64, c_void_p]),
+    "dq_mse_per_window_v": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_int64, c_void_p]),
     "dq_unet_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_float,
                             c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "dq_unet_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -91,6 +96,11 @@ PROTOTYPES = {
                                       POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
                                       c_void_p, c_float, c_void_p, c_void_p, c_int, c_float]),
     "dq_guided_update": (c_int, [c_int] + [c_void_p] * 8 + [c_float, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
+    "dq_solver_step_v": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p]),
+    "dq_guided_update_v": (c_int, [c_int] + [c_void_p] * 8 + [c_float, c_float, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
+    "dq_ddim_sample_v": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                 POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
+                                 c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_int, c_float, c_float]),
     "dq_ms1_cond_drop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_float, c_int, c_int64, c_void_p]),
     "dq_ddim_sample_guided": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                       POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,

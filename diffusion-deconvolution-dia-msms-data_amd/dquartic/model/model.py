@@ -9,7 +9,8 @@ stays usable as a generic harness -- but that is the caller's network, not this 
 
 Documented deviations: batches are supported and ``train_step`` returns a 0-dim loss (the mean over
 samples of the reference's B = 1 loss); both ``pred_type`` values are built; ``ms1_loss_weight > 0`` is built with chosen
-semantics (the reference's branch raises TypeError).
+semantics (the reference's branch raises TypeError).  A third objective the reference does not have,
+``pred_type="v_prediction"`` (the network predicts v = sa eps - sb x0), is built for ``UNet1d``.
 """
 import ctypes
 import math
@@ -69,6 +70,13 @@ def extract(a, t, x_shape):  # model.py:131-148
 _MS1_TERM_MULTI = "ms1_loss_weight > 0 with attn_cond_channels > 1 is not implemented (the MS1 loss term is defined on a 1-D chromatogram)"
 
 
+# the v objective is built through UNet1d's native paths; its follow-ups are named where they are refused
+_V_OTHER_NETWORKS = ("pred_type 'v_prediction' is implemented for UNet1d only (follow-up: the CustomTransformer's train step, sampler and "
+                     "evaluation under the v objective)")
+_V_MS1_TERM = ("ms1_loss_weight > 0 with pred_type 'v_prediction' is not implemented (follow-up: the MS1 term under the v objective; DESIGN.md "
+               "section 12 defines it for 'eps' and 'x0' only)")
+
+
 class DDIMDiffusionModel(ModelInterface):
     def __init__(self, model_class, num_timesteps=1000, beta_schedule_type="cosine", pred_type="eps", auto_normalize=True,
                  ms1_loss_weight=0.0, device="cuda", **kwargs):
@@ -90,6 +98,13 @@ class DDIMDiffusionModel(ModelInterface):
             self.loss_weight = torch.ones_like(snr)
         elif pred_type == "x0":
             self.loss_weight = snr
+        elif pred_type == "v_prediction":
+            # v = sa eps - sb x0 (Salimans & Ho 2022): the plain MSE on v is the x0 loss weighted by SNR + 1
+            if not isinstance(self.model, UNet1d):
+                raise NotImplementedError(_V_OTHER_NETWORKS)
+            if ms1_loss_weight > 0:
+                raise NotImplementedError(_V_MS1_TERM)
+            self.loss_weight = torch.ones_like(snr)
         else:
             raise ValueError(f"Unknown pred_type: {pred_type}")
         self.normalize = normalize_to_neg_one_to_one if auto_normalize else identity
@@ -225,7 +240,7 @@ class DDIMDiffusionModel(ModelInterface):
         sa, sb = torch.sqrt(ab), torch.sqrt(1.0 - ab)
         if self.pred_type not in N.PRED_TYPES:
             raise ValueError(f"Unknown pred_type: {self.pred_type}")
-        out = self.model(x_t, t_tensor, init_cond, attn_cond)  # eps_pred or x0_pred (model.py:271 / :276)
+        out = self.model(x_t, t_tensor, init_cond, attn_cond)  # eps_pred, x0_pred (model.py:271 / :276) or v_pred
         wants_grad = torch.is_grad_enabled() and (x_t.requires_grad or out.requires_grad)
         if eta > 0.0:
             if not x_t.is_cuda or wants_grad:
@@ -236,7 +251,7 @@ class DDIMDiffusionModel(ModelInterface):
             coef = torch.cat([cf.reshape(-1), sg]).to(x_t.device)
             xt, o = x_t.detach().float().contiguous(), out.detach().float().contiguous()
             x_prev = torch.empty_like(xt)
-            eps_pred = torch.empty_like(xt) if self.pred_type == "x0" else None
+            eps_pred = torch.empty_like(xt) if self.pred_type != "eps" else None
             ids_dev, seed_dev = self._ids_tensor(window_ids, batch_size, x_t.device), self._seed_tensor(seed, x_t.device)
             N.check(N.lib().dq_ddim_step_sto(N.ptr(xt), N.ptr(o), N.ptr(x_prev), N.ptr(eps_pred), N.ptr(coef), N.ptr(ids_dev), N.ptr(seed_dev),
                                              int(draw), N.PRED_TYPES[self.pred_type], batch_size, xt[0].numel(), N.stream_ptr()),
@@ -254,6 +269,10 @@ class DDIMDiffusionModel(ModelInterface):
                 N.check(N.lib().dq_ddim_step(N.ptr(xt), N.ptr(o), N.ptr(x_prev), N.ptr(coef), xt.numel(), N.stream_ptr()), "dq_ddim_step")
                 return x_prev, out
             eps_pred = torch.empty_like(xt)
+            if self.pred_type == "v_prediction":
+                N.check(N.lib().dq_ddim_step_v(N.ptr(xt), N.ptr(o), N.ptr(x_prev), N.ptr(eps_pred), N.ptr(coef), xt.numel(),
+                                               N.stream_ptr()), "dq_ddim_step_v")
+                return x_prev, eps_pred
             N.check(N.lib().dq_ddim_step_x0(N.ptr(xt), N.ptr(o), N.ptr(x_prev), N.ptr(eps_pred), N.ptr(coef), xt.numel(),
                                             N.stream_ptr()), "dq_ddim_step_x0")
             return x_prev, eps_pred
@@ -261,6 +280,8 @@ class DDIMDiffusionModel(ModelInterface):
         # arithmetic as is
         if self.pred_type == "eps":
             eps_pred, x0_pred = out, (x_t - sb * out) / sa
+        elif self.pred_type == "v_prediction":
+            x0_pred, eps_pred = sa * x_t - sb * out, sb * x_t + sa * out
         else:
             x0_pred, eps_pred = out, (x_t - sa * out) / sb
         if t > 0:
@@ -406,7 +427,8 @@ class DDIMDiffusionModel(ModelInterface):
                        sampler=0, clip_x0=0.0, guidance=None):
         """``eta`` None: ``dq_ddim_sample`` (the call as it always was); else ``dq_ddim_sample_ex``; ``sampler`` != 0:
         ``dq_ddim_sample_solver``; ``guidance`` = (scale, null_ms1) (``eta`` a number): ``dq_ddim_sample_guided`` on the workspace of twice
-        the batch.  The four take one argument list; the later ones append to it."""
+        the batch.  The four take one argument list; the later ones append to it.  ``pred_type="v_prediction"``: ``dq_ddim_sample_v``, the
+        same list with a ``guided`` flag in front of the scale, for every one of these forms."""
         net: UNet1d = self.model
         x_T, c2, B, RT, MZ = self._stage_x(x_T, ms2_cond, eta, seed, shape)
         c1 = net._check_inputs(ms1_cond, B, RT).detach().to(torch.float32).contiguous()
@@ -419,7 +441,13 @@ class DDIMDiffusionModel(ModelInterface):
                 N.ptr(c1), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], ts_c, num_steps, *(N.ptr(v) for v in outs),
                 1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws), ws.numel(), B, RT, N.stream_ptr()]
         entry = "dq_ddim_sample"
-        if eta is not None:
+        if self.pred_type == "v_prediction":
+            # one entry for every form of the loop (dq_ddim_sample_solver, which the others above call, is held to refusing the value 2)
+            seed_dev, ids_dev = self._stage_noise(x_T, eta or 0.0, seed, window_ids, B, c2.device)
+            args += [float(eta or 0.0), N.ptr(seed_dev), N.ptr(ids_dev), int(sampler), float(clip_x0), 0 if guidance is None else 1,
+                     float(guidance[0]) if guidance is not None else 1.0, float(guidance[1]) if guidance is not None else 0.0]
+            entry = "dq_ddim_sample_v"
+        elif eta is not None:
             seed_dev, ids_dev = self._stage_noise(x_T, eta, seed, window_ids, B, c2.device)
             args += [float(eta), N.ptr(seed_dev), N.ptr(ids_dev)]
             entry = "dq_ddim_sample_ex"
@@ -469,6 +497,8 @@ class DDIMDiffusionModel(ModelInterface):
             raise ValueError(f"Unknown pred_type: {self.pred_type}")
         if float(ms1_loss_weight or 0.0) > 0.0 and getattr(self.model, "attn_cond_channels", 1) > 1:
             raise NotImplementedError(_MS1_TERM_MULTI)
+        if float(ms1_loss_weight or 0.0) > 0.0 and self.pred_type == "v_prediction":
+            raise NotImplementedError(_V_MS1_TERM)
         batch_size = x_0.size(0)
         if t is None:
             t = torch.randint(0, self.num_timesteps, (batch_size,), device=x_0.device).long()
@@ -481,7 +511,11 @@ class DDIMDiffusionModel(ModelInterface):
         w = float(ms1_loss_weight or 0.0)
         if self.pred_type == "eps" and w <= 0.0:
             return F.mse_loss(out, noise) * 1.0  # loss_weight is all-ones for the eps objective (model.py:208-209, 404)
-        target = noise if self.pred_type == "eps" else x_0
+        if self.pred_type == "v_prediction":  # v = sa eps - sb x0
+            ab = self.alpha_bars.to(x_0.device)
+            target = extract(torch.sqrt(ab), t, x_0.shape) * noise - extract(torch.sqrt(1.0 - ab), t, x_0.shape) * x_0
+        else:
+            target = noise if self.pred_type == "eps" else x_0
         per_sample = ((out - target) ** 2).flatten(1).mean(dim=1)  # model.py:361 / :376 at B = 1, per sample here
         if w > 0.0:  # model.py:364-371, 379-386, 398-402 with the chosen semantics (this generic path: plain tensor expressions)
             d = (x_t - out) if self.pred_type == "eps" else out
@@ -506,6 +540,8 @@ class DDIMDiffusionModel(ModelInterface):
         B, RT, MZ = x_0.shape
         if float(ms1_loss_weight or 0.0) > 0.0 and net.attn_cond_channels > 1:
             raise NotImplementedError(_MS1_TERM_MULTI)
+        if float(ms1_loss_weight or 0.0) > 0.0 and self.pred_type == "v_prediction":
+            raise NotImplementedError(_V_MS1_TERM)
         c2, c1 = _f32(ms2_cond), _f32(net._check_inputs(ms1_cond, B, RT))
         x_0, t, noise, ab, lw = self._stage_step(x_0, t, noise)
         flat = net.read_params(training=True)  # (raises inside ema_scope(): the average is not trained)
@@ -522,7 +558,7 @@ class DDIMDiffusionModel(ModelInterface):
     def eval_step(self, x_0, ms2_cond, ms1_cond, t=None, noise=None):
         """Forward-only counterpart of ``train_step_fused`` (``dq_eval_step``): normalise, q_sample, U-Net forward
         without anything kept for a backward, per-window MSE.  Returns ``(loss, per_window)`` as device tensors: ``per_window`` (B) is the
-        unweighted MSE of each window against its target (the noise for ``eps``, the normalised ``x_0`` for ``x0``), ``loss`` (0-dim) the
+        unweighted MSE of each window against its target (the noise for ``eps``, the normalised ``x_0`` for ``x0``, ``sa noise - sb x_0`` for ``v_prediction``), ``loss`` (0-dim) the
         mean over windows of ``loss_weight[t_b] * per_window[b]``.  The MSE part only: the MS1 term of the training loss is not evaluated.
         It sets no ``.grad``, needs no optimiser, uses the inference workspace and reads the averaged weights inside ``ema_scope()``.
         ``noise`` is used as passed.  Native network only: this package's UNet1d, or its CustomTransformer behind

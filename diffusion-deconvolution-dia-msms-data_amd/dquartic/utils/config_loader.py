@@ -4,7 +4,8 @@ Additions (all optional, defaulting to the reference behaviour): ``data.syntheti
 built-in synthetic dataset instead of files; integer-like CLI overrides that arrive as strings (``--batch-size``,
 ``--threads`` have no click type in the reference, cli.py:39,42) are coerced to int; ``data.validation`` (absent from the default
 config) describes a held-out set with the keys of ``data`` itself -- see ``validation_config``; ``data.mixture`` (absent from the
-default config too) asks for K-component mixtures with drawn weights -- see ``mixture_config``."""
+default config too) asks for K-component mixtures with drawn weights -- see ``mixture_config``; ``model.pred_type`` is checked against
+``PRED_TYPES`` when a config is loaded (the reference's ``"eps"`` and ``"x0"``, and ``"v_prediction"``)."""
 import copy
 import json
 
@@ -22,6 +23,8 @@ DEFAULT_CONFIG = {
               "wandb_architecture": "DDIM(UNet1d)", "wandb_dataset": "MS2", "wandb_mode": "offline"},
     "threads": 4,
 }
+
+PRED_TYPES = ("eps", "x0", "v_prediction")  # model.pred_type: the reference's two objectives and v-prediction
 
 _OVERRIDES = {  # kwarg -> (section, key, coerce)
     "parquet_directory": ("data", "parquet_directory", None),
@@ -51,6 +54,9 @@ def load_train_config(config_path: str, **kwargs):
             cfg[section][key] = val
     cfg["model"]["batch_size"] = int(cfg["model"]["batch_size"])
     cfg["threads"] = int(cfg.get("threads", 0))
+    pred_type = cfg["model"].get("pred_type", "eps")
+    if pred_type not in PRED_TYPES:
+        raise ValueError(f"model.pred_type: Unknown pred_type {pred_type!r} (one of {list(PRED_TYPES)})")
     return cfg
 
 

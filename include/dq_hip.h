@@ -57,7 +57,8 @@ const char* dq_last_error(void);
  * dq_wide_col2im3, dq_wide_repitch, dq_wide_norm_fwd, dq_wide_norm_bwd, dq_wide_norm_bwd_scratch_floats, dq_wide_rowsum, dq_wide_sum_b,
  * dq_debug_wide_mid_fwd, dq_debug_wide_mid_bwd; the transformer's held-out evaluation: dq_tfm_eval_workspace_bytes, dq_tfm_eval_step,
  * dq_q_sample_repeats, dq_mse_per_window_repeats, dq_tfm_kv_broadcast; classifier-free guidance: DQ_UPDATE_*, dq_guided_update,
- * dq_ms1_cond_drop, dq_ddim_sample_guided; K-component mixtures: dq_mix_batch_scratch_bytes, dq_mix_batch). */
+ * dq_ms1_cond_drop, dq_ddim_sample_guided; K-component mixtures: dq_mix_batch_scratch_bytes, dq_mix_batch; the v objective: DQ_PRED_V,
+ * dq_ddim_step_v, dq_solver_step_v, dq_guided_update_v, dq_ddim_sample_v, dq_mse_loss_v_fwd_bwd, dq_mse_per_window_v). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -77,8 +78,15 @@ int64_t dq_get_option(const char* key);
  * resolved default rule.  Unknown key: -1. */
 int64_t dq_get_option_effective(const char* key);
 
-/* DDIMDiffusionModel.pred_type (model.py:205-213, 269-280, 354-389); any other value is rejected ("Unknown pred_type"). */
-enum { DQ_PRED_EPS = 0, DQ_PRED_X0 = 1 };
+/* DDIMDiffusionModel.pred_type (model.py:205-213, 269-280, 354-389); any other value is rejected ("Unknown pred_type").
+ * DQ_PRED_V ("v_prediction", no reference counterpart; Salimans & Ho 2022): the network output is v = sa eps - sb x0 with sa = sqrt(ab_t),
+ * sb = sqrt(1 - ab_t); x0 = sa x_t - sb v and eps = sb x_t + sa v are recovered without a division.  dq_train_step, dq_eval_step and
+ * dq_ddim_step_sto and dq_ddim_sample_v take the value in their pred_type argument.  dq_solver_step, dq_guided_update and
+ * dq_ddim_sample_solver are called by the test suite with 2 as an unknown objective, on operands that must not be touched, and keep
+ * refusing it (with them dq_ddim_sample / _ex, which are calls of the third, and dq_ddim_sample_guided, so that the four loop entries
+ * answer alike): their v forms are dq_solver_step_v, dq_guided_update_v and dq_ddim_sample_v.  dq_tfm_sample and dq_tfm_eval_step (the
+ * CustomTransformer, not built for this objective) refuse it as unknown. */
+enum { DQ_PRED_EPS = 0, DQ_PRED_X0 = 1, DQ_PRED_V = 2 };
 
 /* ---- network description -------------------------------------------------------------------------------------
  * Replaces UNet1d.__init__ (unet1d.py:918-1084) for simple=True, conditional=True, channels=1,
@@ -109,7 +117,7 @@ int64_t dq_unet_workspace_bytes(dq_plan* plan, int B, int RT, int training);
  *   DQ_FINAL_SOFTPLUS: torch.nn.Softplus() (beta 1, threshold 20): y = x for x > 20, else log1p(exp(x)); dy/dx = 1 for x > 20,
  *                      else sigmoid(x).
  * Per plan.  It applies to every entry point that forms or differentiates the network output: dq_unet_fwd, dq_unet_bwd (grad_out is
- * d loss / d y, the activated output), dq_train_step (its losses are taken on y) and dq_ddim_sample (eps or, with DQ_PRED_X0, x0 is y).
+ * d loss / d y, the activated output), dq_train_step (its losses are taken on y) and dq_ddim_sample (eps or, with DQ_PRED_X0, x0 is y; dq_ddim_sample_v: v is y).
  * Workspace sizes do not depend on it.  A call drops the plan's cached sampling graph.  Any other value: non-zero (dq_last_error). */
 enum { DQ_FINAL_IDENTITY = 0, DQ_FINAL_SOFTPLUS = 1 };
 int dq_plan_set_final_act(dq_plan* plan, int act);
@@ -129,6 +137,9 @@ int dq_ddim_step(const float* x_t, const float* eps, float* x_prev, const float*
  * and written to eps_out (nullable); x_prev as above. */
 int dq_ddim_step_x0(const float* x_t, const float* x0_pred, float* x_prev, float* eps_out, const float* coef_dev, int64_t n,
                     void* stream);
+/* pred_type "v_prediction": the network output is v_pred; x0 = sa*x_t - sb*v_pred and eps = sb*x_t + sa*v_pred (sa, sb = coef_dev[0], [1])
+ * are derived, eps written to eps_out (nullable); x_prev as above. */
+int dq_ddim_step_v(const float* x_t, const float* v_pred, float* x_prev, float* eps_out, const float* coef_dev, int64_t n, void* stream);
 
 /* ---- K1-K8: UNet1d.forward (unet1d.py:1086-1166) ---------------------------------------------------------------
  * params: flat parameter buffer; rope_freqs: the 8 non-trainable RoPE frequencies (device).
@@ -155,6 +166,13 @@ int dq_mse_loss_fwd_bwd(const float* eps, const float* noise, float* loss_out, f
 int dq_mse_loss_weighted_fwd_bwd(const float* pred, const float* target, float target_mul, float target_add,
                                  const float* loss_weight_dev, const int64_t* t, float* loss_out, float* grad_out, float* scratch,
                                  int B, int64_t per_sample, void* stream);
+/* pred_type "v_prediction": loss = mean over samples b of lw[t_b] * MSE_b(pred, z), z = sa_b * noise - sb_b * (x0 * tm + ta) with
+ * sa_b = sqrt(alpha_bars_dev[t_b]), sb_b = sqrt(1 - alpha_bars_dev[t_b]) formed per element inside the kernel (never written).  lw: a
+ * T-entry table or NULL (all ones, DDIMDiffusionModel.loss_weight for this objective); grad_out (nullable) = 2 lw[t_b] (pred - z) / (B per).
+ * scratch: >= 1024 device floats.  16-byte accesses when per % 4 == 0 and every tensor is 16-byte aligned, else one element per lane. */
+int dq_mse_loss_v_fwd_bwd(const float* pred, const float* x0, const float* noise, const float* alpha_bars_dev, float tm, float ta,
+                          const float* lw, const int64_t* t, float* loss_out, float* grad_out, float* scratch, int B, int64_t per,
+                          void* stream);
 
 /* ---- K11: clip_grad_norm_(max_norm) + AdamW step (model_interface.py:1121-1122, torch defaults) ----------------
  * grads are first multiplied by grad_scale (1/world_size after a summing all-reduce), the global L2 norm of the
@@ -207,7 +225,8 @@ int dq_ms1_loss_fwd_bwd(const float* pred, const float* x_t, const float* ms1_co
  * normalise x0/conds, q_sample, network forward, MSE loss, backward into grads (+=).  t (B) int64 and noise (B,RT,MZ) are
  * drawn by the caller (the reference draws randint then randn_like, model.py:344-346).  pred_type DQ_PRED_EPS: target =
  * noise, loss_weight_dev ignored (may be NULL); DQ_PRED_X0: target = normalised x0, every sample weighted by
- * loss_weight_dev[t_b] (model.py:209-210, 404).  ms1_loss_weight in [0, 1]: 0 = the MSE alone; > 0 adds the MS1 term
+ * loss_weight_dev[t_b] (model.py:209-210, 404); DQ_PRED_V: target = sa_b noise - sb_b (normalised x0), weighted by
+ * loss_weight_dev[t_b] when the table is given (NULL: all ones), ms1_loss_weight > 0 refused.  ms1_loss_weight in [0, 1]: 0 = the MSE alone; > 0 adds the MS1 term
  * (dq_ms1_loss_fwd_bwd above).  loss_out: 1 device float = mean over the batch of the per-sample loss. */
 int dq_train_step(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_dev, const float* x0,
                   const float* ms2_cond, const float* ms1_cond, const int64_t* t, const float* noise, int auto_normalize,
@@ -220,9 +239,9 @@ int dq_train_step(dq_plan* plan, const float* params, const float* rope_freqs, c
  * dq_eval_step: the forward-only counterpart of dq_train_step -- q_sample (normalising as auto_normalize says), the network forward without
  * anything kept for a backward, then dq_mse_per_window.  Arguments as dq_train_step without grads and ms1_loss_weight; two outputs:
  *   per_window_out  B device floats: the unweighted MSE of window b between the network output and its target (DQ_PRED_EPS: the noise;
- *                   DQ_PRED_X0: the normalised x0);
- *   loss_out        1 device float: mean_b loss_weight_dev[t_b] * per_window[b]; the table is required for DQ_PRED_X0 and ignored (may be
- *                   NULL: all ones) for DQ_PRED_EPS, as in the train step.
+ *                   DQ_PRED_X0: the normalised x0; DQ_PRED_V: sa_b noise - sb_b (normalised x0), dq_mse_per_window_v);
+ *   loss_out        1 device float: mean_b loss_weight_dev[t_b] * per_window[b]; the table is required for DQ_PRED_X0, applied when given (NULL: all
+ *                   ones) for DQ_PRED_V and ignored (may be NULL: all ones) for DQ_PRED_EPS, as in the train step.
  * It reports the MSE part only: the MS1 term of the training loss (ms1_loss_weight > 0) is not evaluated.  workspace: the INFERENCE size,
  * dq_unet_workspace_bytes(plan, B, RT, 0).  It touches no gradient buffer and nothing of the backward's side queue: called between two
  * train steps it leaves the second bit for bit what it would have been.  params is read by pointer (pass the EMA buffer to evaluate the
@@ -240,6 +259,11 @@ int dq_eval_step(dq_plan* plan, const float* params, const float* rope_freqs, co
 int64_t dq_mse_per_window_scratch_bytes(int B, int64_t per);
 int dq_mse_per_window(const float* out, const float* target, float tm, float ta, const float* lw, const int64_t* t, float* per_window_out,
                       float* loss_out, void* scratch, int B, int64_t per, void* stream);
+/* The same under DQ_PRED_V: the target is sa_b * noise - sb_b * (x0 * tm + ta) in fp32 (dq_mse_loss_v_fwd_bwd's arithmetic), formed per
+ * element; lw nullable (all ones).  Scratch and summation order as dq_mse_per_window. */
+int dq_mse_per_window_v(const float* out, const float* x0, const float* noise, const float* alpha_bars_dev, float tm, float ta,
+                        const float* lw, const int64_t* t, float* per_window_out, float* loss_out, void* scratch, int B, int64_t per,
+                        void* stream);
 /* Reconstruction metrics of pred against target, both (B, RT, MZ) fp32 (k_metrics.hip): out (B, DQ_METRIC_COUNT) floats per window, every sum
  * in fp64 over the fp32 inputs (n = RT * MZ), every output rounded to fp32 once:
  *   0 mse         sum (P - T)^2 / n
@@ -285,7 +309,7 @@ int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, 
  * same noise at any batch position, and a captured step is replayed unchanged under a new seed.
  * dq_randn: out (B, per_window) = z at draw index `draw`; out 4-byte aligned (16-byte stores when it is 16-byte aligned). */
 int dq_randn(float* out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int B, int64_t per_window, void* stream);
-/* K9 with noise: x0 / eps as dq_ddim_step (DQ_PRED_EPS) or dq_ddim_step_x0 (DQ_PRED_X0; eps_out nullable, ignored under DQ_PRED_EPS) form
+/* K9 with noise: x0 / eps as dq_ddim_step (DQ_PRED_EPS) or dq_ddim_step_x0 / dq_ddim_step_v (DQ_PRED_X0 / DQ_PRED_V; eps_out nullable, ignored under DQ_PRED_EPS) form
  * them, then x_prev = sap*x0 + c*eps + sigma*z.  coef_dev: 5 device floats [sa, sb, sap, c, sigma]; sap < 0 means t == 0: x_prev = x0, no
  * noise drawn (dq_ddim_step's result bit for bit).  per_window a multiple of 4; tensors 16-byte aligned; x_prev may alias x_t. */
 int dq_ddim_step_sto(const float* x_t, const float* net_out, float* x_prev, float* eps_out, const float* coef_dev,
@@ -327,12 +351,16 @@ enum { DQ_SAMPLER_REFERENCE = 0, DQ_SAMPLER_DDIM = 1, DQ_SAMPLER_DPMPP_2M = 2 };
 int dq_sampler_coef_table(const float* alpha_bars_host, int num_timesteps, const int32_t* timesteps_host, int num_steps, int sampler,
                           float eta, float* coef_out, float* extra_out);
 /* One solver update on caller-supplied tensors (the Solver family of k_update.hip).  coef_dev: 5 device floats [sa, sb, cx, c0, c1].  x0 = net_out (DQ_PRED_X0)
- * or (x_t - sb net_out) / sa (DQ_PRED_EPS); clip_x0 > 0: x0 clamped to [-clip_x0, clip_x0] first; x_prev = (cx x_t + c0 x0) + c1 x0_hist,
+ * or (x_t - sb net_out) / sa (DQ_PRED_EPS; the v objective: dq_solver_step_v); clip_x0 > 0: x0 clamped to [-clip_x0, clip_x0] first; x_prev = (cx x_t + c0 x0) + c1 x0_hist,
  * or x0 when cx < 0.  x0_hist (nullable only when c1 == 0; not read when c1 == 0) receives x0.  eps_out (nullable): (x_t - sa x0) / sb under
  * DQ_PRED_X0 and for a clamped element, else net_out.  x_prev may alias x_t and eps_out net_out.  Any n; tensors 4-byte aligned (16-byte
  * accesses when n % 4 == 0 and all are 16-byte aligned). */
 int dq_solver_step(const float* x_t, const float* net_out, float* x_prev, float* x0_hist, float* eps_out, const float* coef_dev, float clip_x0,
                    int pred_type, int64_t n, void* stream);
+/* The same under the v objective: x0 = sa x_t - sb v_pred, eps = sb x_t + sa v_pred (eps_out, nullable, always the derived eps; where x0
+ * was clamped, (x_t - sa x0) / sb).  Everything else as dq_solver_step. */
+int dq_solver_step_v(const float* x_t, const float* v_pred, float* x_prev, float* x0_hist, float* eps_out, const float* coef_dev,
+                     float clip_x0, int64_t n, void* stream);
 /* dq_ddim_sample_ex with a sampler and the clamp: (DQ_SAMPLER_REFERENCE, clip_x0 <= 0) is dq_ddim_sample_ex, call for call.
  * DQ_SAMPLER_DDIM with clip off runs the reference's kernels and captured graph over the strided table (eta > 0: dq_ddim_step_sto).
  * DQ_SAMPLER_DPMPP_2M, and DQ_SAMPLER_DDIM with clip_x0 > 0 (first-order rows), run dq_solver_step behind the forward (one more launch per
@@ -349,7 +377,7 @@ int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_
  * MS1 is the one input that names the component to extract (the mixture is the same whichever precursor is asked for).  A network trained
  * with its MS1 randomly replaced by a null (dq_ms1_cond_drop) has a conditional output c and an unconditional output u; the guided sampler
  * runs every update on g = u + w (c - u): one fp32 subtraction and one fused multiply-add per element inside the update kernels, the same
- * rule for DQ_PRED_EPS and DQ_PRED_X0 (guidance commutes with the affine map between them).  w = 1 is the conditional model, w = 0 the
+ * rule for DQ_PRED_EPS and DQ_PRED_X0 (guidance commutes with the affine map between them; the v objective: dq_guided_update_v).  w = 1 is the conditional model, w = 0 the
  * unconditional one, w > 1 pushes towards the component MS1 names.  The null is a CONSTANT raw MS1 value in every element, normalised like
  * real MS1: no learned token, the checkpoint layout stays the reference's.
  *
@@ -368,6 +396,22 @@ enum { DQ_UPDATE_DDIM = 0, DQ_UPDATE_STOCHASTIC = 1, DQ_UPDATE_SOLVER_1 = 2, DQ_
 int dq_guided_update(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
                      float* eps_out, const float* coef_dev, float w, float clip_x0, const int64_t* window_ids_dev, const uint64_t* seed_dev,
                      int draw, int pred_type, int B, int64_t per_window, void* stream);
+/* The same under the v objective: g = net_u + w (net_c - net_u) is formed on the v predictions, then x0 = sa x_t - sb g, eps = sb x_t + sa g
+ * and the kind's update; dq_guided_update's arguments without pred_type, its refusals under this entry's name. */
+int dq_guided_update_v(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
+                       float* eps_out, const float* coef_dev, float w, float clip_x0, const int64_t* window_ids_dev,
+                       const uint64_t* seed_dev, int draw, int B, int64_t per_window, void* stream);
+/* The U-Net's sampling loop with DQ_PRED_V among its objectives: dq_ddim_sample_guided's arguments with `guided` in front of the scale
+ * (0: guidance_scale and null_ms1 are ignored and the call is dq_ddim_sample_solver's, the default update riding in the network's last
+ * launch; else dq_ddim_sample_guided's).  pred_type: DQ_PRED_EPS, DQ_PRED_X0 or DQ_PRED_V -- dq_ddim_sample_solver (and dq_ddim_sample /
+ * _ex, which are calls of it) is held to refusing 2 on operands that must not be touched (tests/test_tfm_sample_plan.py), so the value has
+ * this entry.  Refusals, workspace, captured step and outputs as those two; under DQ_PRED_V traj_eps holds the derived eps. */
+int dq_ddim_sample_v(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                     const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                     const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                     int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                     const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, int guided, float guidance_scale,
+                     float null_ms1);
 /* Conditioning dropout (k_cond_drop.hip): ms1_out (B, per_ms1) = ms1_in, with window b replaced as a whole by null_value iff r2 < thresh.
  * r2: the THIRD output word of Philox4x32-10 on counter (0, draw, id lo, id hi) under key (seed lo, seed hi), id = window_ids_dev[b] (NULL:
  * b); the normals above use words 0 and 1 only, so the decision never correlates with a noise draw under the same seed.  thresh = (uint32)
