@@ -138,7 +138,9 @@ int dq_unet_bwd(dq_plan* plan, const float* params, const float* rope_freqs, con
 int dq_mse_loss_fwd_bwd(const float* eps, const float* noise, float* loss_out, float* grad_out, float* scratch, int64_t n,
                         void* stream) {
   DQ_REQUIRE(eps && noise && loss_out && scratch, "dq_mse_loss_fwd_bwd: null argument");
-  return launch_mse_fwd_bwd(eps, noise, loss_out, grad_out, scratch, n, (hipStream_t)stream);
+  LossTarget tg;
+  tg.z = noise;
+  return launch_mse_fwd_bwd(eps, tg, loss_out, grad_out, scratch, 1, n, (hipStream_t)stream);
 }
 
 int dq_ms1_loss_fwd_bwd(const float* pred, const float* x_t, const float* ms1_cond, float cond_mul, float cond_add,
@@ -156,8 +158,9 @@ int dq_mse_loss_weighted_fwd_bwd(const float* pred, const float* target, float t
                                  int B, int64_t per_sample, void* stream) {
   DQ_REQUIRE(pred && target && loss_weight_dev && t && loss_out && scratch, "dq_mse_loss_weighted_fwd_bwd: null argument");
   DQ_REQUIRE(B > 0 && per_sample > 0, "dq_mse_loss_weighted_fwd_bwd: B and per_sample must be positive");
-  return launch_mse_fwd_bwd(pred, target, loss_out, grad_out, scratch, (int64_t)B * per_sample, (hipStream_t)stream, loss_weight_dev,
-                            t, per_sample, target_mul, target_add);
+  LossTarget tg;
+  tg.z = target; tg.tm = target_mul; tg.ta = target_add; tg.lw = loss_weight_dev; tg.t = t;
+  return launch_mse_fwd_bwd(pred, tg, loss_out, grad_out, scratch, B, per_sample, (hipStream_t)stream);
 }
 
 // The four AdamW entries: one launch_adamw (k_adamw.hip), the host's scalars or the device's, with or without the average
@@ -274,7 +277,7 @@ int dq_train_step(dq_plan* plan, const float* params, const float* rope_freqs, c
   Ctx::HeadLoss hl;
   if (head_loss_on && pred_type != DQ_PRED_X0 && ms1_loss_weight == 0.f) {
     hl.z = noise; hl.grad_out = c.w(a.xb); hl.part = c.w(a.head_part); hl.gscale = 2.0f / (float)(B * per);  // (launch_mse_fwd_bwd's scale)
-    if (pred_type == DQ_PRED_V) {  // the target sa_b noise - sb_b (x0 cm + ca) is formed in the head launch (launch_mse_v_fwd_bwd's arithmetic)
+    if (pred_type == DQ_PRED_V) {  // the target sa_b noise - sb_b (x0 cm + ca) is formed in the head launch (k_mse_fwd_bwd<MseV>'s arithmetic)
       hl.x0 = x0; hl.alpha_bars = alpha_bars_dev; hl.t = t; hl.lw = loss_weight_dev; hl.tm = cm; hl.ta = ca;
     }
     c.head_loss = &hl;
@@ -283,16 +286,14 @@ int dq_train_step(dq_plan* plan, const float* params, const float* rope_freqs, c
   // the gradient twin is zeroed inside unet_backward, so the loss gradient goes to a forward-arena buffer (xb)
   if (hl.done) {  // (loss and its gradient came with the forward's last launch; the sum of the partials rides on the side stream: unet_backward)
     c.loss_sum.partials = hl.part; c.loss_sum.count = hl.nparts; c.loss_sum.scale = 1.0f / (float)(B * per); c.loss_sum.out = loss_out;
-  } else if (pred_type == DQ_PRED_X0)  // model.py:372-376, 404: target = normalised x0, per-sample weight loss_weight[t_b]
-    DQ_TRY(launch_mse_fwd_bwd(c.w(a.eps), x0, loss_out, c.w(a.xb), c.w(a.partials), B * per, s, loss_weight_dev, t, per, cm, ca));
-  else if (pred_type == DQ_PRED_V)  // target = sa_b noise - sb_b (normalised x0), weight loss_weight[t_b] (null: 1)
-    DQ_TRY(launch_mse_v_fwd_bwd(c.w(a.eps), x0, noise, alpha_bars_dev, cm, ca, loss_weight_dev, t, loss_out, c.w(a.xb), c.w(a.partials), B, per, s));
-  else if (c.owner && ms1_loss_weight == 0.f && tail_fork_enabled()) {
-    int nparts = 0;  // (the sum of the partials -> loss_out rides on the side stream: unet_backward)
-    DQ_TRY(launch_mse_fwd_bwd(c.w(a.eps), noise, loss_out, c.w(a.xb), c.w(a.partials), B * per, s, nullptr, nullptr, 0, 1.f, 0.f, &nparts));
-    c.loss_sum.partials = c.w(a.partials); c.loss_sum.count = nparts; c.loss_sum.scale = 1.0f / (float)(B * per); c.loss_sum.out = loss_out;
-  } else
-    DQ_TRY(launch_mse_fwd_bwd(c.w(a.eps), noise, loss_out, c.w(a.xb), c.w(a.partials), B * per, s));         // model.py:361
+  } else {  // model.py:361 / 372-376, 404 / DESIGN.md section 35
+    // (eps on the fork: the sum of the partials -> loss_out rides on the side stream, unet_backward)
+    const bool defer = pred_type == DQ_PRED_EPS && c.owner && ms1_loss_weight == 0.f && tail_fork_enabled();
+    int nparts = 0;
+    DQ_TRY(launch_mse_fwd_bwd(c.w(a.eps), loss_target(pred_type, x0, noise, alpha_bars_dev, cm, ca, loss_weight_dev, t), loss_out, c.w(a.xb),
+                              c.w(a.partials), B, per, s, defer ? &nparts : nullptr));
+    if (defer) { c.loss_sum.partials = c.w(a.partials); c.loss_sum.count = nparts; c.loss_sum.scale = 1.0f / (float)(B * per); c.loss_sum.out = loss_out; }
+  }
   if (ms1_loss_weight > 0.f)  // model.py:364-371 / 379-386, 398-402 (semantics: DESIGN.md section 12)
     DQ_TRY(launch_ms1_loss(c.w(a.eps), pred_type == DQ_PRED_X0 ? nullptr : c.w(a.xa), ms1_cond, cm, ca,
                            pred_type == DQ_PRED_X0 ? loss_weight_dev : nullptr, t, ms1_loss_weight, B, RT, plan->plan.mz, c.w(a.xb), loss_out,
@@ -325,12 +326,9 @@ int dq_eval_step(dq_plan* plan, const float* params, const float* rope_freqs, co
   DQ_TRY(launch_q_sample(alpha_bars_dev, x0, t, noise, c.w(a.xa), B, per, auto_normalize, s));                 // model.py:349-352
   DQ_TRY(unet_forward(c, rope_freqs, c.w(a.xa), t, 0, ms2_cond, ms1_cond, cm, ca, plan->dev, c.w(a.eps)));  // model.py:359
   const int64_t slice_bytes = (int64_t)sizeof(float) * ((B * per + 63) / 64 * 64);
-  if (pred_type == DQ_PRED_V)  // the target is sa_b noise - sb_b (normalised x0), weighted by loss_weight[t_b] (null: 1)
-    return launch_mse_per_window_v(c.w(a.eps), x0, noise, alpha_bars_dev, cm, ca, loss_weight_dev, t, per_window_out, loss_out, c.w(a.xb), slice_bytes,
-                                   B, per, s);
-  const bool px0 = pred_type == DQ_PRED_X0;  // model.py:361 / 372-376: the target is the noise, or the normalised x0 weighted by loss_weight[t_b]
-  return launch_mse_per_window(c.w(a.eps), px0 ? x0 : noise, px0 ? cm : 1.f, px0 ? ca : 0.f, px0 ? loss_weight_dev : nullptr, t,
-                               per_window_out, loss_out, c.w(a.xb), slice_bytes, B, per, s);
+  // model.py:361 / 372-376 / DESIGN.md section 35: the objective's target, weighted as in training
+  return launch_mse_per_window(c.w(a.eps), loss_target(pred_type, x0, noise, alpha_bars_dev, cm, ca, loss_weight_dev, t), per_window_out, loss_out,
+                               c.w(a.xb), slice_bytes, B, 1, per, s);
 }
 
 int64_t dq_mse_per_window_scratch_bytes(int B, int64_t per) { return mse_per_window_scratch_bytes(B, per); }
@@ -338,37 +336,43 @@ int64_t dq_mse_per_window_scratch_bytes(int B, int64_t per) { return mse_per_win
 int dq_mse_per_window(const float* out, const float* target, float tm, float ta, const float* lw, const int64_t* t, float* per_window_out,
                       float* loss_out, void* scratch, int B, int64_t per, void* stream) {
   DQ_REQUIRE(B > 0 && per > 0, "dq_mse_per_window: B and per must be positive");
-  return launch_mse_per_window(out, target, tm, ta, lw, t, per_window_out, loss_out, scratch, mse_per_window_scratch_bytes(B, per), B, per,
-                               (hipStream_t)stream);
+  LossTarget tg;
+  tg.z = target; tg.tm = tm; tg.ta = ta; tg.lw = lw; tg.t = t;
+  return launch_mse_per_window(out, tg, per_window_out, loss_out, scratch, mse_per_window_scratch_bytes(B, per), B, 1, per, (hipStream_t)stream);
 }
 
 int dq_mse_loss_v_fwd_bwd(const float* pred, const float* x0, const float* noise, const float* alpha_bars_dev, float tm, float ta, const float* lw,
                           const int64_t* t, float* loss_out, float* grad_out, float* scratch, int B, int64_t per, void* stream) {
   DQ_REQUIRE(pred && x0 && noise && alpha_bars_dev && t && loss_out && scratch, "dq_mse_loss_v_fwd_bwd: null argument");
   DQ_REQUIRE(B > 0 && per > 0, "dq_mse_loss_v_fwd_bwd: B and per must be positive");
-  return launch_mse_v_fwd_bwd(pred, x0, noise, alpha_bars_dev, tm, ta, lw, t, loss_out, grad_out, scratch, B, per, (hipStream_t)stream);
+  return launch_mse_fwd_bwd(pred, loss_target(DQ_PRED_V, x0, noise, alpha_bars_dev, tm, ta, lw, t), loss_out, grad_out, scratch, B, per,
+                            (hipStream_t)stream);
 }
 
 int dq_mse_per_window_v(const float* out, const float* x0, const float* noise, const float* alpha_bars_dev, float tm, float ta, const float* lw,
                         const int64_t* t, float* per_window_out, float* loss_out, void* scratch, int B, int64_t per, void* stream) {
   DQ_REQUIRE(B > 0 && per > 0, "dq_mse_per_window_v: B and per must be positive");
-  return launch_mse_per_window_v(out, x0, noise, alpha_bars_dev, tm, ta, lw, t, per_window_out, loss_out, scratch, mse_per_window_scratch_bytes(B, per),
-                                 B, per, (hipStream_t)stream);
+  return launch_mse_per_window(out, loss_target(DQ_PRED_V, x0, noise, alpha_bars_dev, tm, ta, lw, t), per_window_out, loss_out, scratch,
+                               mse_per_window_scratch_bytes(B, per), B, 1, per, (hipStream_t)stream);
 }
 
 int dq_q_sample_repeats(const float* alpha_bars_dev, const float* x0, const int64_t* t, const float* noise, const uint64_t* seed_dev,
                         const int64_t* window_ids_dev, int first_draw, float* x_t, int B, int repeats, int64_t per_window, int normalize_x0,
                         void* stream) {
-  return launch_q_sample_repeats(alpha_bars_dev, x0, t, noise, window_ids_dev, seed_dev, first_draw, x_t, B, repeats, per_window, normalize_x0,
-                                 (hipStream_t)stream);
+  const NoiseStack st{repeats, window_ids_dev, seed_dev, first_draw};
+  return launch_q_sample(alpha_bars_dev, x0, t, noise, x_t, B, per_window, normalize_x0, (hipStream_t)stream, &st);
 }
 
 int dq_mse_per_window_repeats(const float* out, const float* target, int target_windows, float tm, float ta, const uint64_t* seed_dev,
                               const int64_t* window_ids_dev, int first_draw, const float* lw, const int64_t* t, float* per_window_out,
                               float* loss_out, void* scratch, int B, int repeats, int64_t per, void* stream) {
   DQ_REQUIRE(B > 0 && repeats > 0 && (int64_t)repeats * B <= 65535 && per > 0, "dq_mse_per_window_repeats: need B, repeats, per > 0 and repeats * B <= 65535");
-  return launch_mse_per_window_repeats(out, target, target_windows, tm, ta, window_ids_dev, seed_dev, first_draw, lw, t, per_window_out, loss_out,
-                                       scratch, mse_per_window_scratch_bytes(repeats * B, per), B, repeats, per, (hipStream_t)stream);
+  LossTarget tg;
+  tg.kind = target ? TargetKind::READ : TargetKind::DRAWN;
+  tg.z = target; tg.tm = tm; tg.ta = ta; tg.lw = lw; tg.t = t;
+  tg.stacked = true; tg.Bt = target_windows; tg.ids = window_ids_dev; tg.seed = seed_dev; tg.first_draw = first_draw;
+  return launch_mse_per_window(out, tg, per_window_out, loss_out, scratch, mse_per_window_scratch_bytes(repeats * B, per), B, repeats, per,
+                               (hipStream_t)stream);
 }
 
 int64_t dq_recon_metrics_scratch_bytes(int B, int RT, int MZ) { return recon_metrics_scratch_bytes(B, RT, MZ); }

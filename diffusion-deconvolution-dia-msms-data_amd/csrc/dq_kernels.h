@@ -8,37 +8,54 @@ namespace dq {
 
 constexpr int MSE_MAX_BLOCKS = 1024;  // size of the partial-sum scratch used by the loss / grad-norm reductions
 
-// ---- k_stream.hip
-int launch_q_sample(const float* alpha_bars, const float* x0, const int64_t* t, const float* noise, float* x_t, int B,
-                    int64_t per_sample, int normalize, hipStream_t s);
+// ---- k_stream.hip: q_sample, the sample epilogue, the two loss forms and the MS1 term
+// x_t (B, per) = sa_b * norm(x0) + sb_b * noise, sa_b = sqrt(alpha_bars[t_b]), sb_b = sqrt(1 - alpha_bars[t_b]); any per (16 bytes per lane
+// iff per % 4 == 0), an empty call launches nothing.  With a stack (dq_tfm_eval_step): R repeats of the B windows,
+// repeat-major (sample n = r * B + b; x0 (B, per) shared by the repeats, t and x_t (R, B)); noise (R, B, per), or nullptr: drawn in the
+// kernel at draw index first_draw + r from seed (device memory) and ids (nullable: 0 .. B-1) and never written.  The stacked form wants
+// B, R > 0, per % 4 == 0 below 2^32 and 16-byte aligned tensors.
+struct NoiseStack { int R = 1; const int64_t* ids = nullptr; const uint64_t* seed = nullptr; int first_draw = 0; };
+int launch_q_sample(const float* alpha_bars, const float* x0, const int64_t* t, const float* noise, float* x_t, int B, int64_t per,
+                    int normalize, hipStream_t s, const NoiseStack* stack = nullptr);
 int launch_sample_finish(const float* x, const float* ms2_cond, float* out_x, float* out_noise, int64_t n, int normalize,
                          hipStream_t s);
-int launch_mse_fwd_bwd(const float* eps, const float* noise, float* loss_out, float* grad_out, float* partials, int64_t n,
-                       hipStream_t s, const float* lw = nullptr, const int64_t* t = nullptr, int64_t per_sample = 0, float tm = 1.f,
-                       float ta = 0.f, int* defer_sum = nullptr);  // lw: per-timestep loss weights (x0 objective); target' = target*tm + ta
+// What a loss compares the network output with, weighted per sample by lw[t_b] (lw nullable: 1):
+//   READ   z * tm + ta.  launch_mse_fwd_bwd applies the map only when lw is given (z * 1 + 0 is not z: it loses the sign of a -0);
+//          launch_mse_per_window always does
+//   V      sa_b * z - sb_b * (x0 * tm + ta) with z the noise, formed per element and never written
+//   DRAWN  launch_mse_per_window only: z is not read but drawn again as launch_q_sample's stack drew it, then mapped like READ
+// stacked (launch_mse_per_window; READ or DRAWN): R repeats of B windows as above, t (R, B); a READ target has Bt = B windows (shared by
+// the repeats) or R * B (one each).  shared: z holds one row per window of the batch (the clean x0), not one per sample (the noise).
+enum class TargetKind { READ, V, DRAWN };
+struct LossTarget {
+  TargetKind kind = TargetKind::READ;
+  const float* z = nullptr; const float* x0 = nullptr; const float* alpha_bars = nullptr;
+  float tm = 1.f, ta = 0.f;
+  const float* lw = nullptr; const int64_t* t = nullptr;
+  bool shared = false, stacked = false; int Bt = 0; const int64_t* ids = nullptr; const uint64_t* seed = nullptr; int first_draw = 0;
+};
+// the target of an objective (DQ_PRED_*), stated once: eps -- the noise, weight 1 (a null noise: DRAWN); x0 -- x0 * cm + ca weighted by
+// lw[t_b], shared; v -- sa_b noise - sb_b (x0 * cm + ca) weighted by lw[t_b] (lw null: 1)
+LossTarget loss_target(int pred_type, const float* x0, const float* noise, const float* alpha_bars, float cm, float ca, const float* lw,
+                       const int64_t* t);
+// loss_out = mean over the B * per elements of w_b (pred - target)^2, grad_out (nullable) = its gradient; partials: MSE_MAX_BLOCKS floats.
 // defer_sum: the kernel leaves its per-block partials, *defer_sum receives their count and loss_out is NOT written -- the caller runs
 // launch_sum_partials(partials, count, 1 / n, loss_out, stream) when it suits (dq_train_step: on the side stream)
+int launch_mse_fwd_bwd(const float* pred, const LossTarget& target, float* loss_out, float* grad_out, float* partials, int B, int64_t per,
+                       hipStream_t s, int* defer_sum = nullptr);
 int launch_sum_partials(const float* partials, int count, float scale, float* out, hipStream_t s);
 // the MS1 term of train_step with ms1_loss_weight = w > 0: on entry loss_out / grad hold the MSE part, on exit the
 // combined loss (1 - w) * MSE + w * additional and its gradient w.r.t. the network output; x_t null = x0 objective;
 // scratch: 5 * B * RT + B floats
 int launch_ms1_loss(const float* out, const float* x_t, const float* ms1, float cm, float ca, const float* lw, const int64_t* t, float w,
                     int B, int RT, int MZ, float* grad, float* loss_out, float* scratch, hipStream_t s);
-// held-out loss: per_window[b] = MSE of window b against target' = target * tm + ta, loss_out = mean_b lw[t_b] * MSE_b
-// (lw null: 1), fp64 sums in a fixed order; scratch: mse_per_window_scratch_bytes = 8 * B * ceil(per / MSE_PW_SLICE) bytes
+// held-out loss, forward only: per_window[n] = MSE of window n of out (R * B, per) against the target, loss_out[r] = mean_b lw[t[r, b]] *
+// MSE[r, b], fp64 sums in a fixed order; R = 1 unless the target is stacked.  scratch: mse_per_window_scratch_bytes(R * B, per) = 8 * R * B *
+// ceil(per / MSE_PW_SLICE) bytes
 constexpr int MSE_PW_SLICE = 8192;  // elements of a window one block of k_mse_per_window sums
 int64_t mse_per_window_scratch_bytes(int B, int64_t per);
-int launch_mse_per_window(const float* out, const float* target, float tm, float ta, const float* lw, const int64_t* t, float* per_window,
-                          float* loss_out, void* scratch, int64_t scratch_bytes, int B, int64_t per, hipStream_t s);
-// the v objective: the target z = sa_b * noise - sb_b * (x0 * tm + ta), sa_b = sqrt(alpha_bars[t_b]), sb_b = sqrt(1 -
-// alpha_bars[t_b]), formed per element and never written; lw (nullable: 1) weights window b by lw[t_b].  Otherwise launch_mse_fwd_bwd
-// (grad_out nullable; defer_sum as there) and launch_mse_per_window.
-int launch_mse_v_fwd_bwd(const float* pred, const float* x0, const float* noise, const float* alpha_bars, float tm, float ta, const float* lw,
-                         const int64_t* t, float* loss_out, float* grad_out, float* partials, int B, int64_t per, hipStream_t s,
-                         int* defer_sum = nullptr);
-int launch_mse_per_window_v(const float* out, const float* x0, const float* noise, const float* alpha_bars, float tm, float ta, const float* lw,
-                            const int64_t* t, float* per_window, float* loss_out, void* scratch, int64_t scratch_bytes, int B, int64_t per,
-                            hipStream_t s);
+int launch_mse_per_window(const float* out, const LossTarget& target, float* per_window, float* loss_out, void* scratch, int64_t scratch_bytes,
+                          int B, int R, int64_t per, hipStream_t s);
 int launch_axpy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst += src
 int launch_zero(float* dst, int64_t n, hipStream_t s);  // dst = 0 (a kernel, not a memset node)
 int launch_copy(float* dst, const float* src, int64_t n, hipStream_t s);  // dst = src (a kernel, not a memcpy node)
@@ -92,17 +109,6 @@ struct AdamwStep {
   float* gnorm_out = nullptr;
 };
 int launch_adamw(const AdamwStep& a, hipStream_t s);
-// ---- k_tfm_eval.hip: the two above over R repeats of B windows stacked repeat-major (sample n = r * B + b; x0 (B, per) shared by the
-// repeats, t (R, B)); noise / target nullable: drawn in the kernel at draw index first_draw + r from seed_dev and ids (nullable: 0 .. B-1).
-// per % 4 == 0 and 16-byte aligned tensors for the head.  The tail's target has Bt windows (B: shared by the repeats, R * B: one each);
-// per_window (R, B), loss_out (R); scratch: mse_per_window_scratch_bytes(R * B, per).
-int launch_q_sample_repeats(const float* alpha_bars, const float* x0, const int64_t* t, const float* noise, const int64_t* ids,
-                            const uint64_t* seed_dev, int first_draw, float* x_t, int B, int R, int64_t per, int normalize, hipStream_t s);
-int launch_mse_per_window_repeats(const float* out, const float* target, int Bt, float tm, float ta, const int64_t* ids, const uint64_t* seed_dev,
-                                  int first_draw, const float* lw, const int64_t* t, float* per_window, float* loss_out, void* scratch,
-                                  int64_t scratch_bytes, int B, int R, int64_t per, hipStream_t s);
-// kv (R * B, Sk, 2H): rows [0, S2) of samples 0 .. B-1 copied to samples B .. R * B - 1 (R == 1: no launch)
-int launch_tfm_kv_broadcast(float* kv, int B, int R, int S2, int Sk, int H, hipStream_t s);
 // ---- k_metrics.hip: per-window reconstruction metrics of pred against target (B, RT, MZ) -> out (B, METRIC_COUNT)
 constexpr int METRIC_COUNT = 9;         // DQ_METRIC_COUNT
 constexpr int METRIC_ROW_SEG = 4096;    // m/z columns of a scan one wave of k_metric_rows sums
@@ -296,7 +302,7 @@ struct LevelFwd {
   int* loss_parts_out = nullptr;
   // ... under the v objective (vt_x0 set): loss_z is the NOISE and the target z = sa_b * noise - sb_b * (x0 * vt_tm + vt_ta),
   // sa_b = sqrt(vt_ab[vt_t[b]]), sb_b = sqrt(1 - vt_ab[vt_t[b]]), is formed per element in the launch (never written); vt_lw (nullable: all
-  // ones) weights sample b's squared error and gradient by vt_lw[vt_t[b]] -- k_mse_v_fwd_bwd's arithmetic
+  // ones) weights sample b's squared error and gradient by vt_lw[vt_t[b]] -- k_mse_fwd_bwd<MseV>'s arithmetic
   const float* vt_x0 = nullptr; const float* vt_ab = nullptr; const int64_t* vt_t = nullptr; const float* vt_lw = nullptr; float vt_tm = 1.f, vt_ta = 0.f;
   // output activation of the head (FINAL_IDENTITY | FINAL_SOFTPLUS, with ew): with Softplus, eps_out, the DDIM update and the training
   // head's loss see y = softplus(final_conv(out))

@@ -88,6 +88,8 @@ constexpr int COLSUM_BLOCKS = 64;
 int launch_colsum(const float* x, int M, int N, int64_t ld, float* out, float* scratch, hipStream_t s, int accumulate = 1);
 // out[b][n] = sum_s x[(b * S + s) * N + n]  (time-embedding gradient: plain store)
 int launch_seqsum(const float* x, int B, int S, int N, float* out, hipStream_t s);
+// kv (R * B, Sk, 2H): rows [0, S2) of samples 0 .. B-1 copied to samples B .. R * B - 1 (R == 1: no launch)
+int launch_tfm_kv_broadcast(float* kv, int B, int R, int S2, int Sk, int H, hipStream_t s);
 
 // ---- k_tfm_attn.hip: the inference attention in one launch: o (B, S1, H) = softmax(q k^T / sqrt(dh)) v per (sample, head), q (B, S1, H),
 // kv (B, Sk, 2H) = K | V halves; fp32 VALU, max-subtracted, bitwise repeatable.  tfm_attn_form: TFM_ATTN_FUSED when the kernel takes the

@@ -5,7 +5,7 @@
 // one walk of the network (tfm_walk, dq_tfm.hip) that dq_tfm_fwd makes too, here with its K | V rows cached.
 // Held-out evaluation: dq_tfm_eval_step runs the same prologue and the same forward once over R repeats of a batch
 // stacked into R * B samples -- the conditional rows computed for the B windows and copied to the other repeats, the time table one row per
-// sample -- between the stacked noising head and the stacked per-window MSE of k_tfm_eval.hip.
+// sample -- between the stacked noising head and the stacked per-window MSE of k_stream.hip.
 #include "../../include/dq_hip.h"
 #include "dq_common.h"
 #include "dq_kernels.h"
@@ -224,14 +224,16 @@ int dq_tfm_eval_step(dq_tfm* p, const float* params, const float* rope_sin, cons
   const TfmWalk net = cached_walk(p, params, rope_sin, rope_cos, w.net, w.kv.data(), w.net.time.temb, true, N, S1, S2);
   float* out = net_out ? net_out : w.out;
   if (net.attn_form == TFM_ATTN_FUSED) DQ_TRY(tfm_attn_prepare());
-  DQ_TRY(launch_q_sample_repeats(alpha_bars_dev, x0, t, noise, window_ids_dev, seed_dev, first_draw, w.xt, B, R, per, auto_normalize, s));
+  const NoiseStack st{R, window_ids_dev, seed_dev, first_draw};
+  DQ_TRY(launch_q_sample(alpha_bars_dev, x0, t, noise, w.xt, B, per, auto_normalize, s, &st));
   // every call, eagerly: nothing of it outlives the call, so a changed MS1 or changed weights behind the same pointer meet no stale state
   DQ_TRY(sample_prologue(net, B, ms1_cond, cm, ca, time_freqs, t, N, w.net.time, s));
   DQ_TRY(tfm_walk(net, w.xt, out, s));
-  const bool px0 = pred_type == DQ_PRED_X0;  // the target: the normalised x0 shared by the repeats, or the noise (read, or drawn again)
-  return launch_mse_per_window_repeats(out, px0 ? x0 : noise, px0 ? B : N, px0 ? cm : 1.f, px0 ? ca : 0.f, window_ids_dev, seed_dev, first_draw,
-                                       px0 ? loss_weight_dev : nullptr, t, per_window_out, loss_out, w.slices,
-                                       mse_per_window_scratch_bytes(N, per), B, R, per, s);
+  // the objective's target over the stack: the clean window is shared by the repeats, the noise has one row per stacked window (or none:
+  // loss_target then says DRAWN)
+  LossTarget tg = loss_target(pred_type, x0, noise, alpha_bars_dev, cm, ca, loss_weight_dev, t);
+  tg.stacked = true; tg.Bt = tg.shared ? B : N; tg.ids = window_ids_dev; tg.seed = seed_dev; tg.first_draw = first_draw;
+  return launch_mse_per_window(out, tg, per_window_out, loss_out, w.slices, mse_per_window_scratch_bytes(N, per), B, R, per, s);
 }
 
 }  // extern "C"

@@ -395,6 +395,15 @@ __global__ void __launch_bounds__(256) k_cond_embed_affine(const float* __restri
     reinterpret_cast<float2*>(c + row * H)[j] = o;
   }
 }
+// the stacked evaluation (dq_tfm_eval_step): kv (N, Sk, 2H), rows [0, S2) of sample n >= B <- the same rows of sample
+// n % B : 8 B / element copied.  row4 = S2 * 2H / 4 float4 copied per sample, sample4 = Sk * 2H / 4 float4 between two samples.  Source
+// (samples < B) and destination (samples >= B) never overlap.
+__global__ void __launch_bounds__(256) k_tfm_kv_broadcast(float4* kv, int B, int64_t total, int64_t row4, int64_t sample4) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = i / row4, e = i - m * row4, n = m + B;
+    kv[n * sample4 + e] = kv[(n % B) * sample4 + e];
+  }
+}
 
 inline unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>(cdiv(n, 256), 8192); }
 }  // namespace
@@ -528,6 +537,18 @@ int launch_colsum(const float* x, int M, int N, int64_t ld, float* out, float* s
 int launch_seqsum(const float* x, int B, int S, int N, float* out, hipStream_t s) {
   if (B * N == 0) return 0;
   hipLaunchKernelGGL(k_seqsum, dim3(cdiv((int64_t)B * N, 256)), dim3(256), 0, s, x, B, S, N, out);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_tfm_kv_broadcast(float* kv, int B, int R, int S2, int Sk, int H, hipStream_t s) {
+  DQ_REQUIRE(kv, "tfm_kv_broadcast: null buffer");
+  DQ_REQUIRE(B > 0 && R > 0 && S2 > 0 && Sk >= S2 && H > 0 && H % 2 == 0, "tfm_kv_broadcast: need B, repeats, S2 > 0, Sk >= S2 and an even H");
+  DQ_REQUIRE(((uintptr_t)kv & 15) == 0, "tfm_kv_broadcast: the buffer must be 16-byte aligned");
+  if (R == 1) return 0;  // (nothing to replicate: no launch)
+  const int64_t row4 = (int64_t)S2 * 2 * H / 4, sample4 = (int64_t)Sk * 2 * H / 4, total = (int64_t)(R - 1) * B * row4;
+  const int grid = (int)std::min<int64_t>(cdiv(total, 256), 2048);
+  hipLaunchKernelGGL(k_tfm_kv_broadcast, dim3(grid), dim3(256), 0, s, reinterpret_cast<float4*>(kv), B, total, row4, sample4);
   DQ_LAUNCH_CHECK();
   return 0;
 }

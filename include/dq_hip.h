@@ -587,7 +587,7 @@ int dq_tfm_sample(dq_tfm* tfm, const float* params, const float* rope_sin, const
                   int auto_normalize, int pred_type, const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise,
                   float* traj_x, float* traj_eps, int use_graph, void* workspace, int64_t workspace_bytes, int B, int S1, int S2,
                   void* stream, float eta, const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0);
-/* Held-out evaluation of the transformer in one call per batch (csrc/dq_tfm_sample.hip, csrc/k_tfm_eval.hip, DESIGN.md section 31;
+/* Held-out evaluation of the transformer in one call per batch (csrc/dq_tfm_sample.hip, csrc/k_stream.hip, DESIGN.md sections 31 and 36;
  * additive at ABI version 12): dq_eval_step's semantics for `repeats` = R repeats of a batch of B windows stacked into N = R * B samples,
  * sample n = r * B + b (repeat-major), through ONE forward -- dq_tfm_sample's prologue and forward, the same code.
  *   x0 (B, S1, input_dim), shared by the repeats and not replicated; ms1_cond (B, S2) raw (2c - 1 first when auto_normalize); t (R, B) int64
@@ -609,7 +609,7 @@ int dq_tfm_eval_step(dq_tfm* tfm, const float* params, const float* rope_sin, co
                      const uint64_t* seed_dev, const int64_t* window_ids_dev, int first_draw, int auto_normalize, int pred_type,
                      const float* loss_weight_dev, float* loss_out, float* per_window_out, float* net_out, void* workspace,
                      int64_t workspace_bytes, int B, int S1, int S2, int repeats, void* stream);
-/* Its three streaming kernels alone (csrc/k_tfm_eval.hip).  per_window % 4 == 0 and 16-byte aligned tensors for the first, like
+/* Its three streaming kernels alone (csrc/k_stream.hip, csrc/k_tfm.hip).  per_window % 4 == 0 and 16-byte aligned tensors for the first, like
  * dq_ddim_step_sto.
  * dq_q_sample_repeats: x_t (R, B, per_window) = sa * norm(x0[b]) + sb * z[r, b] with sa, sb from alpha_bars[t[r, b]]: dq_q_sample's
  * arithmetic on x0 (B, per_window); z read from noise (R, B, per_window) or, noise == NULL, drawn at draw index first_draw + r.

@@ -10,7 +10,7 @@ Sizes come from the launch code: T = 256 threads, V elements per thread and trip
 runs at the smallest legal size, T*V -+ V and T*V, G*T*V -+ V, and two sweeps of the capped grid plus a ragged remainder; k_sumsq also at
 n = 4 * (5 * G * T + 77) + r, r in 1..3 (its paired loop twice, then the single loop, then a scalar tail), with grads aligned and one
 float off 16 bytes (its designed scalar branch).  q_sample, the DDIM update and the MSE send an element count (q_sample, weighted MSE: a
-per-sample count) that is no multiple of 4 to forms with V = 1 (k_q_sample_1, k_step_update<..., 1>, k_mse_fwd_bwd_1): those run at the
+per-sample count) that is no multiple of 4 to forms with V = 1 (k_q_sample<1, false>, k_step_update<..., 1>, k_mse_fwd_bwd<MseRead, 1>): those run at the
 V = 1 edges that are such sizes, and at 3 x 37 x 2, the shape tests/test_level_plan.py met them at.  The DDIM update takes V = 1 for
 tensors that are not 16-byte aligned as well (n = 4 and a block + 4, every tensor one float off).  k_adamw_clip moves 16 bytes per lane
 when p, g, m, v are all 16-byte aligned and has a scalar loop for the tail and for every other alignment: both plain entries run with p, m
@@ -134,7 +134,7 @@ def timesteps(B, pattern):
 
 # (B, per_sample): per_sample = 4, blocks serving many samples, a sample spanning sweeps
 Q_CASES = [(1, 4), (7, 4), (5, 204), (4, 256), (1, 1028), (257, 4), (1, 2097148), (524287, 4), (3, 699052), (5, 839128)]
-# per_sample % 4 != 0 (k_q_sample_1, one element per thread and trip): the smallest, MZ = 2 at RT = 37, B * per_sample a multiple of 4 all
+# per_sample % 4 != 0 (k_q_sample<1, false>, one element per thread and trip): the smallest, MZ = 2 at RT = 37, B * per_sample a multiple of 4 all
 # the same, a block + 1, beyond one sweep of the capped grid
 Q_CASES += [(1, 1), (3, 74), (2, 6), (1, 257), (3, 174767)]
 
@@ -193,7 +193,7 @@ def ddim_case(n, t, fp32=False):
     return c
 
 
-MSE_SIZES = edge_sizes(4, MSE_MAX_BLOCKS, 4) + ODD(edge_sizes(1, MSE_MAX_BLOCKS, 1)) + [222]  # (n % 4 != 0: k_mse_fwd_bwd_1, V = 1)
+MSE_SIZES = edge_sizes(4, MSE_MAX_BLOCKS, 4) + ODD(edge_sizes(1, MSE_MAX_BLOCKS, 1)) + [222]  # (n % 4 != 0: k_mse_fwd_bwd<MseRead, 1>)
 # (B, per_sample): from per_sample = 4 (a block serves 256 samples) to one sample spanning several sweeps of the 1024-block grid
 WMSE_CASES = [(1, 4), (255, 4), (4, 256), (1, 1028), (3, 349524), (262145, 4), (1, 2098484), (7, 299784)]
 WMSE_CASES += [(1, 1), (3, 74), (2, 6), (257, 1), (7, 74899)]  # per_sample % 4 != 0 (V = 1), B * per_sample = 12 included
@@ -552,6 +552,38 @@ def test_mse_weighted(N, B, per, tm, ta):
     print(f"weighted mse B {B} per_sample {per} map ({tm}, {ta}): loss {loss:.8g} (float64 {c['loss']:.8g}) err / bound "
           + " ".join(f"{k} {v:.3f}" for k, v in r.items()))
     assert all(v <= 1.0 for v in r.values()), r
+
+
+def _negative_zeros(n, weighted):
+    c = {"e": torch.full((1, n), -0.0), "z": torch.full((1, n), -0.0), "n": n}
+    if weighted:
+        c["lw"], c["t"] = snr_table(), torch.tensor([500])
+    return c
+
+
+@pytest.mark.parametrize("n", [4, 5])
+def test_mse_negative_zero(N, n):
+    """pred and target -0.0 in every element (V = 4 and V = 1): the unweighted form takes the target as it lies, d = -0 - -0 = +0, and the
+    gradient is +0.0 to the sign bit.  (A target mapped as z * 1 + 0 would be +0, d = -0 - +0 = -0, and the gradient -0.0.)"""
+    loss, grad = _run_mse(N, _negative_zeros(n, False), False, 1, n, 1.0, 0.0)
+    g = grad.cpu().numpy()
+    assert loss == 0.0 and not np.signbit(np.float32(loss))
+    assert np.array_equal(g, np.zeros(n, np.float32)) and not np.signbit(g).any(), g
+
+
+@pytest.mark.parametrize("n", [4, 5])
+def test_mse_weighted_negative_zero(N, n):
+    """the same inputs through the weighted form with the map (1, 0): it applies the map, so the sign of the zero gradient is that of
+    (pred - (z * 1 + 0)) * ((2 / n) * w) evaluated in fp32"""
+    c = _negative_zeros(n, True)
+    loss, grad = _run_mse(N, c, True, 1, n, 1.0, 0.0)
+    one, zero = np.float32(1.0), np.float32(0.0)
+    d = c["e"].numpy().reshape(-1) - (c["z"].numpy().reshape(-1) * one + zero)
+    want = d * (np.float32(2.0) / np.float32(n) * c["lw"][c["t"]].numpy().astype(np.float32)[0])
+    g = grad.cpu().numpy()
+    assert want.dtype == np.float32 and np.signbit(want).all()  # (-0 - +0 = -0: the case tells the two forms apart)
+    assert loss == 0.0
+    assert np.array_equal(g, want) and np.array_equal(np.signbit(g), np.signbit(want)), (g, want)
 
 
 # ---- the MS1 term -------------------------------------------------------------------------------------------------------------------

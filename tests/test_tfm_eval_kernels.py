@@ -1,4 +1,4 @@
-"""The three streaming kernels of the transformer's held-out evaluation alone (csrc/k_tfm_eval.hip), at their loop edges.
+"""The three streaming kernels of the transformer's held-out evaluation alone (csrc/k_stream.hip, csrc/k_tfm.hip; DESIGN.md sections 31 and 36), at their loop edges.
 
 dq_q_sample_repeats and dq_mse_per_window_repeats work on R repeats of B windows stacked repeat-major.  What is asserted is bitwise, against
 the kernels that exist without them: the head equals dq_q_sample on x0 replicated R times; the tail equals dq_mse_per_window applied per

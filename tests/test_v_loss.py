@@ -1,5 +1,5 @@
-"""The loss kernels of the v objective (csrc/k_stream.hip): dq_mse_loss_v_fwd_bwd (k_mse_v_fwd_bwd<4> / <1>) and
-dq_mse_per_window_v (k_mse_per_window_v).  The target z = sa_b * noise - sb_b * (x0 * tm + ta), sa_b = sqrt(ab[t_b]), sb_b = sqrt(1 - ab[t_b]),
+"""The loss kernels of the v objective (csrc/k_stream.hip): dq_mse_loss_v_fwd_bwd (k_mse_fwd_bwd<MseV, 4> / <MseV, 1>) and
+dq_mse_per_window_v (k_mse_per_window<PwV>).  The target z = sa_b * noise - sb_b * (x0 * tm + ta), sa_b = sqrt(ab[t_b]), sb_b = sqrt(1 - ab[t_b]),
 is formed inside the kernels.
 
 Shapes: B = 3 with t = [0, 500, 999] at per = 8 (the vector form; a window boundary inside a block's float4 stride) and per = 5 (the

@@ -176,7 +176,7 @@ np.savez(sys.argv[2], loss=float(loss), grads=dm.model.flat_grads().cpu().numpy(
 
 @pytest.mark.parametrize("softplus", [0, 1])
 def test_fused_head_vs_the_unfused_path(tmp_path, softplus):
-    """the loss and the first two backward steps in the forward's last launch against k_conv_fwd / k_mse_v_fwd_bwd / k_conv_bwd_data behind it
+    """the loss and the first two backward steps in the forward's last launch against k_conv_fwd / k_mse_fwd_bwd<MseV> / k_conv_bwd_data behind it
     (the development build's DQ_NO_HEAD_LOSS=1): one child process each on build/dev/libdq_hip_dev.so, whose default paths are the product's"""
     assert os.path.exists(DEV_LIB), "build the development library first (make dev, or __graft_entry__.build())"
     res = {}
@@ -192,7 +192,7 @@ def test_fused_head_vs_the_unfused_path(tmp_path, softplus):
     print(f"fused head vs un-fused (softplus {softplus}): loss {a['loss']:.8g} / {b['loss']:.8g}, grads max |diff| {float(np.abs(a['grads'] - b['grads']).max()):.3g} "
           f"of {gmax:.3g}, bitwise {np.array_equal(a['grads'], b['grads'])}")
     assert abs(a["loss"] - b["loss"]) < 5e-5 * abs(b["loss"])  # (summed in another fixed order)
-    # the per-element arithmetic of the head is k_mse_v_fwd_bwd's and k_conv_bwd_data's: every gradient bit for bit, as
+    # the per-element arithmetic of the head is k_mse_fwd_bwd<MseV>'s and k_conv_bwd_data's: every gradient bit for bit, as
     # tests/test_tiny_levels.py finds for the eps head
     assert np.array_equal(a["grads"], b["grads"])
 

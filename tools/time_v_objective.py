@@ -1,6 +1,6 @@
 """Times the v objective (pred_type="v_prediction") beside the eps objective on the default U-Net at the bench shape
 (400 x 64 windows): the fused train step at batch 32 (the training head carries the loss for both), the v train step with the head loss
-switched off (the un-fused path: final_conv, k_mse_v_fwd_bwd and final_conv's backward data path as launches of their own), and the default
+switched off (the un-fused path: final_conv, k_mse_fwd_bwd<MseV> and final_conv's backward data path as launches of their own), and the default
 sampling step at batch 512.  It also counts the kernel launches of one train step and of one sampling step for both objectives.
 
 The un-fused path exists in the development build only (csrc/dq_dev.h, `make dev`: DQ_NO_HEAD_LOSS=1, read once per process), so it is timed
