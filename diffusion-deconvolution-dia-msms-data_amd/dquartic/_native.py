@@ -111,6 +111,11 @@ PROTOTYPES = {
     "dq_mix_batch_scratch_bytes": (c_int64, [c_int, c_int]),
     "dq_mix_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, POINTER(c_float), c_int,
                              c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int64, c_void_p]),
+    "dq_run_window_count": (c_int64, [c_int, c_int, c_int]),
+    "dq_run_windows_scratch_bytes": (c_int64, [c_int]),
+    "dq_run_windows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_int] + [c_void_p] * 4 + [c_int64, c_void_p]),
+    "dq_run_stitch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
     "dq_debug_tensor_offset": (c_int64, [c_void_p, c_char_p]),
     "dq_debug_level_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int]),
     "dq_debug_side_tail_store": (c_int, [c_void_p, c_void_p, c_float, c_int]),

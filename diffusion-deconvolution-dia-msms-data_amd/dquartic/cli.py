@@ -1,7 +1,8 @@
 """``dquartic`` command line -- same commands and options as the reference's ``dquartic/cli.py`` (:26-188):
 ``dquartic train CONFIG [--parquet_directory --ms2-data-path --ms1-data-path --batch-size --checkpoint-path --use-wandb
 --threads]`` and ``dquartic generate-config PATH``; ``dquartic evaluate CONFIG --checkpoint PATH`` (this build) prints held-out loss and
-reconstruction metrics.  A ``data.mixture`` block in the config (absent by default) makes ``train`` and ``evaluate`` form K-component
+reconstruction metrics; ``dquartic deconvolve CONFIG --checkpoint PATH --ms2 RUN.npy --ms1 RUN.npy --out OUT.npz --window W`` (this build)
+deconvolves whole chromatograms.  A ``data.mixture`` block in the config (absent by default) makes ``train`` and ``evaluate`` form K-component
 mixtures with drawn weights on the GPU (``ResidentMixLoader``).  ``generate-train-data`` (offline sqMass ETL) is outside the hot path
 and reports so.  Under ``torch.distributed.run`` (WORLD_SIZE > 1) training is data-parallel: one process per GPU, the
 dataset is sharded by rank and the flat gradient is all-reduced over RCCL."""
@@ -200,6 +201,19 @@ def enable_cond_dropout_from_config(dm, m) -> bool:
     return dm.cond_dropout_enabled
 
 
+def load_inference_checkpoint(dm, m, checkpoint, device, use_ema):
+    """A checkpoint written by ``train`` into ``dm``: the weights, and its averaged weights when it has them and ``use_ema`` is not False
+    (``use_ema`` True without an average in the file is an error)."""
+    ck = torch.load(checkpoint, map_location=device, weights_only=False)
+    dm.model.load_state_dict(ck["model_state_dict"])
+    if ck.get("ema_state_dict") is not None and use_ema is not False:
+        dm._set_lr(m["learning_rate"])
+        dm.enable_ema(float(ck.get("ema_decay", 0.999)), bool(ck.get("ema_warmup", True)))
+        dm.optimizer.load_ema_state_dict(ck["ema_state_dict"])
+    elif use_ema:
+        raise click.ClickException(f"--use-ema: {checkpoint} holds no averaged weights")
+
+
 @cli.command()
 @click.argument("config-path", type=click.Path(exists=True), required=True)
 @click.option("--checkpoint", required=True, type=click.Path(exists=True), help="Checkpoint written by train (model_state_dict; its EMA when it has one)")
@@ -232,14 +246,7 @@ def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, guidance
         val = {**config["data"], "n_pairs": None, "seed": 0, "mixture": mixture_config(config["data"].get("mixture"))}
     loader = build_validation_loader(val, m, max(1, int(m["batch_size"])))
     dm = build_model(m, device)
-    ck = torch.load(checkpoint, map_location=device, weights_only=False)
-    dm.model.load_state_dict(ck["model_state_dict"])
-    if ck.get("ema_state_dict") is not None and use_ema is not False:
-        dm._set_lr(m["learning_rate"])
-        dm.enable_ema(float(ck.get("ema_decay", 0.999)), bool(ck.get("ema_warmup", True)))
-        dm.optimizer.load_ema_state_dict(ck["ema_state_dict"])
-    elif use_ema:
-        raise click.ClickException(f"--use-ema: {checkpoint} holds no averaged weights")
+    load_inference_checkpoint(dm, m, checkpoint, device, use_ema)
     res = dm.evaluate(loader, n_t=4, seed=seed, num_steps=num_steps, eta=eta, use_ema=use_ema, max_batches=max_batches, sampler=sampler,
                       clip_x0=clip_x0, guidance_scale=guidance_scale, null_ms1=null_ms1)
     # the per-window arrays go to --out only; the printed line keeps the scalars and the buckets (val_loss_by_weight among them)
@@ -248,6 +255,75 @@ def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, guidance
     if out_path is not None:
         with open(out_path, "w") as f:
             json.dump({**res, **arrays}, f)
+
+
+@cli.command()
+@click.argument("config-path", type=click.Path(exists=True), required=True)
+@click.option("--checkpoint", required=True, type=click.Path(exists=True), help="Checkpoint written by train (model_state_dict; its EMA when it has one)")
+@click.option("--ms2", "ms2_path", required=True, type=click.Path(exists=True),
+              help="The observed run(s) as .npy: (RT_total, MZ), or (R, RT_total, MZ) for R runs processed in turn")
+@click.option("--ms1", "ms1_path", required=True, type=click.Path(exists=True),
+              help="The MS1 trace(s) as .npy: (RT_total,) or (RT_total, M1); with R runs (R, RT_total) or (R, RT_total, M1)")
+@click.option("--out", "out_path", required=True, type=click.Path(), help="Write pred, overlap_var, coverage, scales and starts as .npz")
+@click.option("--window", required=True, type=int, help="Scans per window (the window length the network was trained on)")
+@click.option("--step", default=5, type=int, help="Scans between the starts of consecutive windows (1 .. window)")
+@click.option("--taper", default="hann", type=click.Choice(["hann", "uniform"]), help="Weight of a window's scans where windows overlap")
+@click.option("--batch-size", default=32, type=int, help="Windows sampled per call (the result does not depend on it)")
+@click.option("--num-steps", default=1000, type=int, help="Sampling steps per window")
+@click.option("--eta", default=0.0, type=float, help="DDIM eta of the sampling (0: deterministic update, 1: ancestral)")
+@click.option("--sampler", default="reference", type=click.Choice(["reference", "ddim", "dpmpp_2m"]),
+              help="Update of the sampling: the reference's, strided DDIM, or DPM-Solver++(2M)")
+@click.option("--clip-x0", default=None, type=float, help="Clamp every step's x0 estimate to [-C, C] (ddim / dpmpp_2m, eta 0)")
+@click.option("--guidance-scale", default=None, type=float,
+              help="Classifier-free guidance scale W of the sampling (UNet1d trained with model.cond_drop_prob; 1: the conditional model)")
+@click.option("--null-ms1", default=0.0, type=float, help="Raw MS1 value of the null condition (the training run's model.null_ms1)")
+@click.option("--seed", default=0, type=int, help="Seed of x_T and of the sampling noise")
+@click.option("--use-ema/--no-use-ema", default=None, help="Sample from the averaged weights (default: when the checkpoint has an average)")
+def deconvolve(config_path, checkpoint, ms2_path, ms1_path, out_path, window, step, taper, batch_size, num_steps, eta, sampler, clip_x0,
+               guidance_scale, null_ms1, seed, use_ema):
+    """Deconvolve whole chromatograms with a checkpoint: every run is cut into overlapping windows, each window normalised on its own and
+    sampled, and the predictions stitched back in intensity units (``deconvolve_run``).  Window i of run r samples under the id
+    (windows of the runs before it) + i.  Prints one JSON line: runs, windows, windows per second."""
+    import time
+
+    import numpy as np
+
+    ms2, ms1 = np.load(ms2_path), np.load(ms1_path)
+    if ms2.ndim not in (2, 3):
+        raise click.ClickException(f"--ms2: expected (RT_total, MZ) or (R, RT_total, MZ), got {ms2.shape}")
+    stacked = ms2.ndim == 3
+    if not stacked:
+        ms2, ms1 = ms2[None], ms1[None]
+    if ms1.ndim not in (2, 3) or ms1.shape[:2] != ms2.shape[:2]:
+        raise click.ClickException(f"--ms1: expected {'(R, RT_total)' if stacked else '(RT_total,)'} with or without a trailing channel "
+                                   f"dimension to go with --ms2 {tuple(ms2.shape[1 - stacked:])}, got {tuple(ms1.shape[1 - stacked:])}")
+    if not 1 <= step <= window <= ms2.shape[1]:
+        raise click.ClickException(f"need 1 <= --step <= --window <= RT_total, got step {step}, window {window}, RT_total {ms2.shape[1]}")
+    if not torch.cuda.is_available():
+        raise click.ClickException("no GPU visible: this build runs the hot path on MI355X only (no CPU fallback)")
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(device)
+    m = load_train_config(config_path)["model"]
+    dm = build_model(m, device)
+    load_inference_checkpoint(dm, m, checkpoint, device, use_ema)
+    kw = {"sampler": sampler, "clip_x0": clip_x0}
+    if guidance_scale is not None:
+        kw.update(guidance_scale=guidance_scale, null_ms1=null_ms1)
+    outs, first = [], 0
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for r in range(ms2.shape[0]):
+        res = dm.deconvolve_run(torch.from_numpy(np.ascontiguousarray(ms2[r], dtype=np.float32)).to(device),
+                                torch.from_numpy(np.ascontiguousarray(ms1[r], dtype=np.float32)).to(device), window=window, step=step,
+                                taper=taper, batch_size=batch_size, id_offset=first, num_steps=num_steps, eta=eta, seed=seed, use_ema=use_ema,
+                                **kw)
+        first += res["n_windows"]
+        outs.append({k: res[k].cpu().numpy() for k in ("pred", "overlap_var", "coverage", "scales")})
+    torch.cuda.synchronize()
+    seconds = time.perf_counter() - t0
+    arrays = {k: np.stack([o[k] for o in outs]) if stacked else outs[0][k] for k in outs[0]}
+    np.savez(out_path, starts=res["starts"], **arrays)
+    click.echo(json.dumps({"runs": int(ms2.shape[0]), "windows": int(first), "windows_per_s": round(first / seconds, 2)}))
 
 
 @cli.command()

@@ -808,6 +808,92 @@ class ModelInterface(object):
             out["val_loss_by_weight"] = E.by_target_weight(tw, mse.mean(axis=0), None if num_steps is None else out["per_window"])
         return out
 
+    _RUN_SAMPLE_OPTIONS = ("num_steps", "eta", "seed", "sampler", "clip_x0", "guidance_scale", "null_ms1", "use_ema")
+
+    def deconvolve_run(self, ms2_run, ms1_run, window=None, step=5, taper="hann", batch_size=32, id_offset=0, **sample_options):
+        """Deconvolve one observed isolation-window chromatogram (new work: the reference has no such entry).
+
+        ``ms2_run`` ``(RT_total, MZ)`` and ``ms1_run`` ``(RT_total,)`` or ``(RT_total, M1)`` (M1 = the network's ``attn_cond_channels``)
+        are device tensors in raw intensity units.  The run is cut into ``n`` windows of ``window`` scans every ``step`` scans
+        (``utils.run_tiles.run_window_starts``: the last window is pulled back to end on the last scan), as the training data was cut
+        from such runs; ``window`` must be given, nothing is guessed.  For each batch of ``batch_size`` consecutive windows
+        ``dq_run_windows`` min-max normalises every window by its own statistics (a constant window, an empty stretch of the run, gives
+        zeros), ``sample(None, ms2_win, ms1_win, window_ids=ids)`` predicts them with x_T and any step noise drawn from the sampler's
+        counter-based generator -- window ``i`` under the id ``id_offset + i`` -- and ``dq_run_stitch`` folds the predictions, each
+        brought back to intensity units by its window's ``hi - lo``, into a weighted running mean and variance per scan.  The update is
+        sequential in window order, so the result does not depend on ``batch_size`` as long as the sampler's window-alone property
+        holds (it is tested at small batches).
+
+        ``taper``: the weight of a window's scan k in the blend -- ``"hann"`` (sin^2(pi (k + 1) / (W + 1)), strictly positive),
+        ``"uniform"``, or ``window`` positive numbers.  ``sample_options``: ``num_steps``, ``eta``, ``seed``, ``sampler``, ``clip_x0``,
+        ``guidance_scale``, ``null_ms1`` go to ``sample`` as they are; ``use_ema`` as in ``predict``.  ``seed=None``: drawn once from
+        torch's generator (x_T needs one), and kept in ``last_seed``.
+
+        Returns a dict: ``"pred"`` ``(RT_total, MZ)``, the deconvolved chromatogram in intensity units ABOVE each window's floor -- the
+        blend of ``p (hi - lo)``, not of ``lo + p (hi - lo)``: with ``scale_target`` mixtures the prediction is the
+        target's contribution to the mixture, and the share of the window's ``lo`` that belongs to it is not identifiable;
+        ``"overlap_var"`` ``(RT_total, MZ)``, the weighted variance among the windows that cover a scan (their disagreement; 0 where one
+        window covers it); ``"coverage"`` ``(RT_total,)``, the sum of the taper weights on a scan; ``"scales"`` ``(n, 4)`` = (MS2 lo, MS2
+        hi, MS1 lo, MS1 hi) of every window; ``"starts"`` (int64 array) and ``"n_windows"``.  The tensors stay on the device."""
+        from ..utils.run_tiles import run_window_starts, taper_table
+
+        unknown = sorted(set(sample_options) - set(self._RUN_SAMPLE_OPTIONS))
+        if unknown:
+            raise TypeError(f"deconvolve_run: unknown option(s) {unknown} (sample options: {list(self._RUN_SAMPLE_OPTIONS)})")
+        if not (torch.is_tensor(ms2_run) and torch.is_tensor(ms1_run)):
+            raise TypeError("deconvolve_run: ms2_run and ms1_run must be torch tensors")
+        if ms2_run.dim() != 2:
+            raise ValueError(f"deconvolve_run: ms2_run must be (RT_total, MZ), got {tuple(ms2_run.shape)}")
+        RT_total, MZ = (int(v) for v in ms2_run.shape)
+        if ms1_run.dim() == 1:
+            ms1_run = ms1_run[:, None]
+        if ms1_run.dim() != 2 or ms1_run.shape[0] != RT_total:
+            raise ValueError(f"deconvolve_run: ms1_run must be (RT_total,) or (RT_total, M1) with RT_total = {RT_total}, got "
+                             f"{tuple(ms1_run.shape)}")
+        M1 = int(ms1_run.shape[1])
+        net_m1 = int(getattr(self._flat_net(), "attn_cond_channels", 1))
+        if M1 != net_m1:
+            raise ValueError(f"deconvolve_run: ms1_run has {M1} channel(s), the network was built with attn_cond_channels={net_m1}")
+        if window is None:
+            raise ValueError("deconvolve_run: window (the scans per window, the length the network was trained on) must be given")
+        W, step, batch_size, id_offset = int(window), int(step), int(batch_size), int(id_offset)
+        starts = run_window_starts(RT_total, W, step)
+        n = len(starts)
+        if batch_size < 1:
+            raise ValueError(f"deconvolve_run: batch_size must be >= 1, got {batch_size}")
+        taper_host = taper_table(taper, W)
+        opts = dict(sample_options)
+        use_ema = opts.pop("use_ema", None)
+        if not (ms2_run.is_cuda and ms1_run.is_cuda):
+            raise NotImplementedError("deconvolve_run runs in the native library only (device tensors)")
+        if opts.get("seed") is None:
+            opts["seed"] = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+        dev = ms2_run.device
+        run2, run1 = ms2_run.detach().to(torch.float32).contiguous(), ms1_run.detach().to(device=dev, dtype=torch.float32).contiguous()
+        taper_dev = torch.from_numpy(taper_host).to(dev)
+        mean, m2 = torch.zeros(RT_total, MZ, device=dev), torch.zeros(RT_total, MZ, device=dev)
+        wsum, scales = torch.zeros(RT_total, device=dev), torch.empty(n, 4, device=dev)
+        nb = min(batch_size, n)
+        scratch = torch.empty(max(1, N.lib().dq_run_windows_scratch_bytes(nb) // 4), dtype=torch.float32, device=dev)
+        win2, win1 = torch.empty(nb, W, MZ, device=dev), torch.empty(nb, W, M1, device=dev)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad(), self._ema_or_null_scope(use_ema):
+                for i0 in range(0, n, batch_size):
+                    B = min(batch_size, n - i0)
+                    c2, c1, sc = win2[:B], win1[:B], scales[i0:i0 + B]
+                    N.check(N.lib().dq_run_windows(N.ptr(run2), N.ptr(run1), RT_total, MZ, M1, W, step, i0, B, N.ptr(c2), N.ptr(c1), N.ptr(sc),
+                                                   N.ptr(scratch), scratch.numel() * 4, N.stream_ptr()), "dq_run_windows")
+                    ids = torch.arange(id_offset + i0, id_offset + i0 + B, dtype=torch.int64, device=dev)
+                    pred, _ = self.sample(None, ms2_cond=c2, ms1_cond=c1, window_ids=ids, **opts)
+                    pred = pred.detach().to(torch.float32).contiguous()
+                    N.check(N.lib().dq_run_stitch(N.ptr(pred), N.ptr(sc), N.ptr(taper_dev), RT_total, MZ, W, step, i0, B, N.ptr(mean), N.ptr(m2),
+                                                  N.ptr(wsum), N.stream_ptr()), "dq_run_stitch")
+        finally:
+            self.model.train(was_training)
+        return {"pred": mean, "overlap_var": m2 / wsum[:, None], "coverage": wsum, "scales": scales, "starts": starts, "n_windows": n}
+
     # ---- internals
     def _init_for_training(self):
         self.loss_func = torch.nn.MSELoss()

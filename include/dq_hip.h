@@ -58,7 +58,8 @@ const char* dq_last_error(void);
  * dq_debug_wide_mid_fwd, dq_debug_wide_mid_bwd; the transformer's held-out evaluation: dq_tfm_eval_workspace_bytes, dq_tfm_eval_step,
  * dq_q_sample_repeats, dq_mse_per_window_repeats, dq_tfm_kv_broadcast; classifier-free guidance: DQ_UPDATE_*, dq_guided_update,
  * dq_ms1_cond_drop, dq_ddim_sample_guided; K-component mixtures: dq_mix_batch_scratch_bytes, dq_mix_batch; the v objective: DQ_PRED_V,
- * dq_ddim_step_v, dq_solver_step_v, dq_guided_update_v, dq_ddim_sample_v, dq_mse_loss_v_fwd_bwd, dq_mse_per_window_v). */
+ * dq_ddim_step_v, dq_solver_step_v, dq_guided_update_v, dq_ddim_sample_v, dq_mse_loss_v_fwd_bwd, dq_mse_per_window_v; whole
+ * chromatograms: dq_run_window_count, dq_run_windows_scratch_bytes, dq_run_windows, dq_run_stitch). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -475,6 +476,36 @@ int dq_mix_batch(const float* ms2_data, const float* ms1_data, int64_t n_windows
                  int K, int RT, int MZ, int64_t ms1_per_window, const float* weights_host, int max_ratio_log2, const uint64_t* seed_dev,
                  const int64_t* window_ids_dev, int draw, int scale_target, float* ms2_target, float* ms1_target, float* ms2_cond,
                  float* ms2_rest, float* weights_out, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* Whole chromatograms (csrc/k_run.hip; additive at ABI version 12): one observed run ms2_run (RT_total, MZ) with its
+ * MS1 trace ms1_run (RT_total, M1), fp32 on the device, cut into windows of W scans every `step` scans, and the windows' predictions
+ * folded back into one chromatogram.  Window rule: 1 <= step <= W <= RT_total; n = ceil((RT_total - W) / step) + 1 windows
+ * (dq_run_window_count; 0 for sizes outside the rule); window i starts at scan s_i = min(i * step, RT_total - W), the last one pulled
+ * back to end on the last scan.  Every scan is covered and no two starts coincide.  Both calls work on windows i0 .. i0 + B - 1 and
+ * recompute s_i themselves: no index array is passed.
+ * dq_run_windows writes ms2_win (B, W, MZ), ms1_win (B, W, M1) and scale (B, 4) = (MS2 lo, MS2 hi, MS1 lo, MS1 hi) of each window:
+ * n = (x - lo) / (hi - lo) in fp32 (dq_pair_batch's expression), MS2 lo / hi over the window's own W * MZ values, MS1 lo / hi over its
+ * W * M1 values.  Unlike dq_pair_batch a constant window (hi == lo: an empty stretch of a run) gives zeros, not NaN; scale still records
+ * lo == hi.  Any MZ >= 1 and M1 >= 1 (float4 accesses when MZ % 4 == 0, scalar ones otherwise).  Inputs are assumed finite: fminf /
+ * fmaxf return the other operand for a NaN, so a NaN does not enter lo / hi and comes out as NaN; an infinity makes the range infinite
+ * (finite values become 0, the infinity NaN).  scratch: dq_run_windows_scratch_bytes(B) bytes (0 for a B the call refuses).  Two launches.
+ * dq_run_stitch folds pred (B, W, MZ), the predictions for those windows in the windows' normalised units, into the running state mean
+ * (RT_total, MZ), m2 (RT_total, MZ), wsum (RT_total), which the caller zeroes before the first call.  scale: dq_run_windows' (B, 4) rows of
+ * the same windows; taper: W positive device floats, the weight of a window's scan k.  For output element (r, m), over the call's windows
+ * that cover r in ascending i, every operation rounded on its own (West's weighted running mean and variance):
+ *   v = pred[i, r - s_i, m] * (hi_i - lo_i);  w = taper[r - s_i];  wn = wsum + w;  d = v - mean;
+ *   mean = mean + (w / wn) * d;  m2 = m2 + (w * d) * (v - mean);  wsum = wn
+ * so windows fed in ascending order give the same bits in any grouping into calls.  mean is the prediction in intensity units ABOVE each
+ * window's floor (p * (hi - lo), not lo + p * (hi - lo)); m2 / wsum is the weighted variance among the windows that cover a scan; wsum
+ * the sum of their taper weights.  One launch; scans no window of the call covers are not touched.
+ * Both are asynchronous on stream.  Refused before any launch (dq_last_error), in this order: a NULL pointer (stream aside); MZ or M1 < 1;
+ * sizes outside 1 <= step <= W <= RT_total; i0 < 0, B < 1 or i0 + B > n; B > 65535; (dq_run_windows) scratch too small. */
+int64_t dq_run_window_count(int RT_total, int W, int step);
+int64_t dq_run_windows_scratch_bytes(int B);
+int dq_run_windows(const float* ms2_run, const float* ms1_run, int RT_total, int MZ, int M1, int W, int step, int64_t i0, int B,
+                   float* ms2_win, float* ms1_win, float* scale, void* scratch, int64_t scratch_bytes, void* stream);
+int dq_run_stitch(const float* pred, const float* scale, const float* taper, int RT_total, int MZ, int W, int step, int64_t i0, int B,
+                  float* mean, float* m2, float* wsum, void* stream);
 
 /* ---- CustomTransformer (dquartic/model/building_blocks.py:179-260) ----------------------------------
  * The reference's alternative noise predictor: forward(x_t (B,S1,input_dim), t (B) int64, x_cond (B,S2)) -> (B,S1,input_dim).
