@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <string>
 
 namespace dq {
 
@@ -83,9 +84,34 @@ struct StepUpdateLaunch {
   float clip = 0.f, w = 1.f;
   int B = 0; int64_t per = 0;  // B windows of per elements (a plain count n: B = 1, per = n)
   const int* step_ptr = nullptr;
+  const float* win = nullptr;  // the per-window form: the (B, 4) table [m_b, s_b, rho_b, -] of k_winstat.hip (guided, or the SOLVER family)
 };
 int launch_update(const StepUpdateLaunch& a, hipStream_t s);
 int launch_inc_step(int* p, hipStream_t s);
+// ---- k_winstat.hip: the per-window statistics in front of the per-window form of the update.  A window is cut
+// into chunks of WS_CHUNK elements whatever the batch.  The scratch, carved at fixed offsets (a captured step replays): the (B, 4) table
+// [m_b, s_b, rho_b, -], the select state of each radix pass, WS_MOMENTS fp64 partials per chunk, two buffers of 2 x 256 counts per chunk.
+constexpr int WS_CHUNK = 8192, WS_MOMENTS = 4;
+struct WinSelState { uint32_t prefA, rankA, prefB, rankB; };  // the key bits found so far and the rank left under them, for ranks j and j + 1
+struct WinStatScratch { float* tab; WinSelState* st; double* part; uint32_t* hist[2]; int nch; };
+int64_t win_stat_scratch_bytes(int B, int64_t per);  // 80 B + 4128 B ceil(per / WS_CHUNK); -1 for B < 1 or per < 1
+int win_stat_carve(const std::string& who, void* scratch, int64_t scratch_bytes, int B, int64_t per, WinStatScratch* out);  // refuses; no device call
+// m_b = (float)(phi * sqrt(var_c / var_g) + (1 - phi)) of c and g = guide(c, u, w) per window -> tab[4 b] (nullable) and m_out[b] (nullable);
+// init_rest: tab's row becomes [m_b, s_init, 1, 0]
+int launch_win_rescale(const float* c, const float* u, float w, double phi, int B, int64_t per, const WinStatScratch& S, float* tab, float s_init,
+                       bool init_rest, float* m_out, hipStream_t s);
+// The q-quantile Q (linear interpolation between the two exact order statistics) of |x| per window (c null), or of |x0| with x0 formed as the
+// update forms it: from x, the network output c (guided: and u, scale w, times m_tab[4 b] when m_tab is given) under objective `pred` with
+// row [sa, sb, ..] of coef (step_ptr: the row the device-side step counter names).  q_out (nullable): Q; tab (nullable): s_b = min(max(Q,
+// floor), cap) and rho_b = floor / s_b into columns 1 and 2, with init_m the whole row [1, s_b, rho_b, 0].
+struct WinQuantile {
+  const float* x = nullptr; const float* c = nullptr; const float* u = nullptr;
+  const float* coef = nullptr; const int* step_ptr = nullptr; const float* m_tab = nullptr;
+  float w = 1.f; int pred = 0; bool guided = false;
+  float q = 1.f, floor = 1.f, cap = 0.f;
+  float* q_out = nullptr; float* tab = nullptr; bool init_m = false;
+};
+int launch_win_quantile(const WinQuantile& qa, int B, int64_t per, const WinStatScratch& S, hipStream_t s);
 // ---- k_noise.hip: out (B, per_window) = the normals of draw index `draw` (the generator of the STOCHASTIC update above)
 int launch_randn(float* out, const int64_t* ids, const uint64_t* seed_dev, int draw, int B, int64_t per_window, hipStream_t s);
 // ---- k_cond_drop.hip: out (B, per) = in with window b replaced by null_value iff the third Philox word of (seed, id, draw) < floor(p 2^32)

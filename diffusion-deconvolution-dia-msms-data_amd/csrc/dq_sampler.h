@@ -14,6 +14,17 @@ namespace dq {
 // solver (updated in place), the clamp (0: off) and the shape.  guided: the forward ran at 2 B windows -- rows
 // [0, B) under the caller's condition, rows [B, 2B) under the null -- and the update combines the two outputs with the scale w inside its
 // kernel, over the B windows of the first half; x and the network output are then 2 * B * per floats each.
+// The per-window statistics of a step (k_winstat.hip), run by launch_step_update between the forward and the update:
+// rescale (guided calls): m_b of rescaled guidance at phi; q > 0: dynamic thresholding at that quantile with floor f and cap.  The scratch is
+// dq_sample_stat_scratch_bytes(B, per) bytes at a fixed address; the update then runs in its per-window form over the table at its head.
+struct StepStats {
+  double phi = 0.0;
+  float q = 0.f, floor = 1.f, cap = 0.f;
+  void* scratch = nullptr; int64_t scratch_bytes = 0;
+  bool rescale = false;
+  bool on() const { return rescale || q > 0.f; }
+};
+
 struct StepUpdateArgs {
   StepUpdate kind;
   const float* coef; const float* extra;
@@ -23,6 +34,7 @@ struct StepUpdateArgs {
   int64_t per;
   bool guided = false;
   float w = 1.f;
+  StepStats stats;
 };
 
 // The noise of the stochastic update: the windows' ids and the seed (device memory) and the draw index (the kernel adds the step counter)
@@ -39,10 +51,12 @@ int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net
 
 // What a call's (eta, sampler, clip_x0) select.  clip_x0: the clamp as the kernels take it (0: off)
 struct SamplerChoice { StepUpdate kind = StepUpdate::DDIM; bool sto = false, clip = false; float clip_x0 = 0.f; int pred = 0; };  // pred: DQ_PRED_*
+// (clip: x0 is clamped by clip_x0 or thresholded -- either way the Solver family runs and the derived eps is the trajectory's)
 // The refusals every sampling loop makes, in one order, before anything touches the device; `who` prefixes the messages.  args_ok: the
-// caller's required pointers are all there; allow_v: DQ_PRED_V is a known objective for this caller (dq_ddim_sample_v).
+// caller's required pointers are all there; allow_v: DQ_PRED_V is a known objective for this caller (dq_ddim_sample_v).  threshold: the call
+// asks for dynamic thresholding (dq_ddim_sample_adaptive), refused where clip_x0 is and selecting the update clip_x0 selects.
 int sampler_check(const char* who, bool args_ok, float eta, int sampler, float clip_x0, const int32_t* timesteps_host, int num_steps,
-                  bool have_seed, bool have_xT, int pred_type, bool allow_v, SamplerChoice* out);
+                  bool have_seed, bool have_xT, int pred_type, bool allow_v, SamplerChoice* out, bool threshold = false);
 // Forms the call's coefficient rows on the host and copies them to coef_dev (4 per step) and extra_dev (1 per step; nullable: not needed);
 // returns after the copies are done (the host vectors are the function's own)
 int sampler_upload_tables(const char* who, const float* alpha_bars_host, int T, const int32_t* ts, int num_steps, int sampler, const SamplerChoice& c,

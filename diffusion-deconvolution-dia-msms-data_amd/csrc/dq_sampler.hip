@@ -29,11 +29,27 @@ int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net
   a.ids = z.ids; a.seed = z.seed; a.draw = z.draw;
   a.clip = u.clip; a.w = u.w;
   a.B = u.B; a.per = u.per; a.step_ptr = step_ptr;
+  if (u.stats.on()) {
+    // the statistics step: m_b from the two network outputs, then s_b and rho_b from the x0 the update will form
+    const StepStats& st = u.stats;
+    WinStatScratch S;
+    DQ_TRY(win_stat_carve("sample statistics", st.scratch, st.scratch_bytes, u.B, u.per, &S));
+    const bool thr = st.q > 0.f;
+    if (st.rescale) DQ_TRY(launch_win_rescale(net_out, net_u, u.w, st.phi, u.B, u.per, S, S.tab, u.clip > 0.f ? u.clip : INFINITY, !thr, nullptr, s));
+    if (thr) {
+      WinQuantile q;
+      q.x = x; q.c = net_out; q.u = a.net_u; q.coef = a.coef; q.step_ptr = step_ptr; q.m_tab = st.rescale ? S.tab : nullptr;
+      q.w = u.w; q.pred = u.pred; q.guided = u.guided;
+      q.q = st.q; q.floor = st.floor; q.cap = st.cap; q.tab = S.tab; q.init_m = !st.rescale;
+      DQ_TRY(launch_win_quantile(q, u.B, u.per, S, s));
+    }
+    a.win = S.tab;
+  }
   return launch_update(a, s);  // model.py:273-289
 }
 
 int sampler_check(const char* who, bool args_ok, float eta, int sampler, float clip_x0, const int32_t* timesteps_host, int num_steps,
-                  bool have_seed, bool have_xT, int pred_type, bool allow_v, SamplerChoice* out) {
+                  bool have_seed, bool have_xT, int pred_type, bool allow_v, SamplerChoice* out, bool threshold) {
   const std::string w(who);
   DQ_REQUIRE(args_ok, w + ": null argument");
   DQ_REQUIRE(eta >= 0.f && eta <= 1.f, w + ": eta must satisfy 0 <= eta <= 1");  // (false for NaN)
@@ -44,12 +60,14 @@ int sampler_check(const char* who, bool args_ok, float eta, int sampler, float c
   DQ_REQUIRE(sampler != DQ_SAMPLER_DPMPP_2M || !sto, w + ": DPM-Solver++(2M) is deterministic: eta must be 0");
   DQ_REQUIRE(!clip || sampler != DQ_SAMPLER_REFERENCE, w + ": clip_x0 needs the ddim or dpmpp_2m sampler");
   DQ_REQUIRE(!clip || !sto, w + ": clip_x0 needs eta == 0");
+  DQ_REQUIRE(!threshold || sampler != DQ_SAMPLER_REFERENCE, w + ": threshold_quantile needs the ddim or dpmpp_2m sampler");
+  DQ_REQUIRE(!threshold || !sto, w + ": threshold_quantile needs eta == 0");
   if (sampler != DQ_SAMPLER_REFERENCE && num_steps <= 1024)  // (a step count out of range is the caller's refusal: its list is not read)
     for (int i = 1; i < num_steps; ++i)
       DQ_REQUIRE(timesteps_host[i] < timesteps_host[i - 1], w + ": the timesteps of this sampler must be strictly decreasing");
   // the update: the Solver family (k_update.hip) behind the forward (2M, or a clamped x0 at first order); else the reference's kernels over this sampler's table
-  out->kind = sampler == DQ_SAMPLER_DPMPP_2M ? StepUpdate::SOLVER_2M : clip ? StepUpdate::SOLVER_1 : sto ? StepUpdate::STOCHASTIC : StepUpdate::DDIM;
-  out->sto = sto; out->clip = clip; out->clip_x0 = clip ? clip_x0 : 0.f;
+  out->kind = sampler == DQ_SAMPLER_DPMPP_2M ? StepUpdate::SOLVER_2M : (clip || threshold) ? StepUpdate::SOLVER_1 : sto ? StepUpdate::STOCHASTIC : StepUpdate::DDIM;
+  out->sto = sto; out->clip = clip || threshold; out->clip_x0 = clip ? clip_x0 : 0.f;
   DQ_REQUIRE(have_seed || (have_xT && !sto), w + ": eta > 0 and a null x_T need the seed (device memory)");
   DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0 || (allow_v && pred_type == DQ_PRED_V), w + ": Unknown pred_type");
   out->pred = pred_type;
@@ -147,6 +165,8 @@ namespace {
 // Classifier-free guidance on MS1: the scale w of g = u + w (c - u) and the raw MS1 value of the null condition
 struct Guidance { float w, null_ms1; };
 bool guidance_ok(float w) { return w >= 0.f && std::isfinite(w); }  // (false for NaN)
+// Per-window sampler control: rescaled guidance at phi, dynamic thresholding at quantile q (0: off) capped at cap
+struct Adaptive { double phi; float q, cap; void* scratch; int64_t scratch_bytes; };
 
 static_assert((int)StepUpdate::DDIM == DQ_UPDATE_DDIM && (int)StepUpdate::STOCHASTIC == DQ_UPDATE_STOCHASTIC &&
               (int)StepUpdate::SOLVER_1 == DQ_UPDATE_SOLVER_1 && (int)StepUpdate::SOLVER_2M == DQ_UPDATE_SOLVER_2M, "DQ_UPDATE_* are StepUpdate's values");
@@ -160,14 +180,31 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
                 const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type, const int32_t* timesteps_host, int num_steps,
                 float* out_x, float* out_noise, float* traj_x, float* traj_eps, int use_graph, void* workspace, int64_t workspace_bytes, int B,
                 int RT, void* stream, float eta, const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0,
-                const Guidance* g, bool allow_v = false) {
+                const Guidance* g, bool allow_v = false, const Adaptive* ad = nullptr) {
   // allow_v: the call came through dq_ddim_sample_v -- the pred_type argument of the other entries names the reference's two objectives
-  const char* who = allow_v ? "dq_ddim_sample_v" : g ? "dq_ddim_sample_guided" : "dq_ddim_sample";
+  const char* who = ad ? "dq_ddim_sample_adaptive" : allow_v ? "dq_ddim_sample_v" : g ? "dq_ddim_sample_guided" : "dq_ddim_sample";
   const std::string wh(who);
   SamplerChoice sc;
+  const bool thr = ad && ad->q != 0.f;  // (NaN: on, then refused below)
   DQ_TRY(sampler_check(who, plan && params && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
-                       eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, allow_v, &sc));
+                       eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, allow_v, &sc, thr));
   DQ_REQUIRE(!g || guidance_ok(g->w), wh + ": the guidance scale must be finite and >= 0");
+  StepStats stats;
+  if (ad) {
+    DQ_REQUIRE(ad->phi >= 0.0 && ad->phi <= 1.0, wh + ": guidance_rescale must satisfy 0 <= guidance_rescale <= 1");  // (false for NaN)
+    DQ_REQUIRE(!thr || (ad->q > 0.f && ad->q <= 1.f), wh + ": threshold_quantile must satisfy 0 < threshold_quantile <= 1 (0: off)");
+    stats.floor = sc.clip_x0 > 0.f ? sc.clip_x0 : 1.f;
+    DQ_REQUIRE(!thr || ad->cap >= stats.floor, wh + ": threshold_max must be >= the floor (clip_x0, or 1 without it)");  // (false for NaN)
+    stats.phi = ad->phi; stats.rescale = g && ad->phi > 0.0;  // (unguided: g = c, m = 1 -- nothing to do)
+    stats.q = thr ? ad->q : 0.f; stats.cap = ad->cap;
+    stats.scratch = ad->scratch; stats.scratch_bytes = ad->scratch_bytes;
+    if (stats.on()) {
+      WinStatScratch S;
+      DQ_REQUIRE(ad->scratch, wh + ": null argument (stat_scratch)");
+      DQ_REQUIRE(B > 0 && RT > 0, wh + ": need B, RT > 0 and 1 <= num_steps <= 1024");
+      DQ_TRY(win_stat_carve(wh, ad->scratch, ad->scratch_bytes, B, (int64_t)RT * plan->plan.mz, &S));
+    }
+  }
   const StepUpdate kind = sc.kind;
   clip_x0 = sc.clip_x0;
   // the head launch takes the update when it can (StepIO::x_t); the others, and every guided one, run behind the forward
@@ -222,7 +259,7 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
     *fused = io.fused_update;
     return rc;
   };
-  const SampleLoop loop{forward, StepUpdateArgs{kind, c.w(a.coef), c.w(a.sigma), c.w(a.xb), clip_x0, sc.pred, B, per, g != nullptr, g ? g->w : 1.f},
+  const SampleLoop loop{forward, StepUpdateArgs{kind, c.w(a.coef), c.w(a.sigma), c.w(a.xb), clip_x0, sc.pred, B, per, g != nullptr, g ? g->w : 1.f, stats},
                         xa, c.w(a.eps), sc.clip, num_steps, ms2_cond, out_x, out_noise, auto_normalize};
   if (use_graph && !traj_x && !traj_eps) {
     // ---- hipGraph path: one step captured once, replayed per step
@@ -238,6 +275,7 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
     StepKey key;
     key.params = params; key.rope = rope_freqs; key.ws = workspace; key.B = B; key.RT = RT; key.normalize = auto_normalize; key.pred = pred_type;
     key.update = kind; key.clip = clip_x0; key.guidance = g ? g->w : -1.f; key.opt_epoch = options_epoch();
+    if (stats.on()) { key.rescale = stats.rescale ? stats.phi : 0.0; key.quantile = stats.q; key.cap = stats.cap; key.stat_scratch = stats.scratch; }
     bool captured;  // (the key only after instantiation succeeded)
     const int rc = replay_captured_step(plan->step, plan->step.exec && plan->step_key == key, loop, step, StepNoise{ids_st, seed_st, 0}, s, &captured);
     if (captured) plan->step_key = key;
@@ -402,6 +440,72 @@ int dq_ddim_sample_v(dq_plan* plan, const float* params, const float* rope_freqs
   return unet_sample(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type, timesteps_host,
                      num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream, eta, seed_dev,
                      window_ids_dev, sampler, clip_x0, guided ? &g : nullptr, true);
+}
+
+// ---- per-window sampler control
+int64_t dq_sample_stat_scratch_bytes(int B, int64_t per_window) { return win_stat_scratch_bytes(B, per_window); }
+
+int dq_window_rescale(const float* net_c, const float* net_u, float w, double phi, int B, int64_t per_window, float* m_out, void* scratch,
+                      int64_t scratch_bytes, void* stream) {
+  const std::string who = "dq_window_rescale";
+  DQ_REQUIRE(net_c && net_u && m_out && scratch, who + ": null argument");
+  DQ_REQUIRE(guidance_ok(w), who + ": the guidance scale must be finite and >= 0");
+  DQ_REQUIRE(phi >= 0.0 && phi <= 1.0, who + ": guidance_rescale must satisfy 0 <= guidance_rescale <= 1");
+  WinStatScratch S;
+  DQ_TRY(win_stat_carve(who, scratch, scratch_bytes, B, per_window, &S));
+  DQ_REQUIRE((((uintptr_t)net_c | (uintptr_t)net_u | (uintptr_t)m_out) & 3) == 0, who + ": tensors must be 4-byte aligned");
+  return launch_win_rescale(net_c, net_u, w, phi, B, per_window, S, nullptr, 0.f, false, m_out, (hipStream_t)stream);
+}
+
+int dq_window_abs_quantile(const float* x, int B, int64_t per_window, float q, float* out, void* scratch, int64_t scratch_bytes, void* stream) {
+  const std::string who = "dq_window_abs_quantile";
+  DQ_REQUIRE(x && out && scratch, who + ": null argument");
+  DQ_REQUIRE(q > 0.f && q <= 1.f, who + ": threshold_quantile must satisfy 0 < threshold_quantile <= 1");
+  WinStatScratch S;
+  DQ_TRY(win_stat_carve(who, scratch, scratch_bytes, B, per_window, &S));
+  DQ_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 3) == 0, who + ": tensors must be 4-byte aligned");
+  WinQuantile qa;
+  qa.x = x; qa.q = q; qa.q_out = out;
+  return launch_win_quantile(qa, B, per_window, S, (hipStream_t)stream);
+}
+
+int dq_step_update_adaptive(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
+                            float* eps_out, const float* coef_dev, float w, const float* table_dev, const int64_t* window_ids_dev,
+                            const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window, void* stream) {
+  const std::string who = "dq_step_update_adaptive";
+  DQ_REQUIRE(x_t && net_c && x_prev && coef_dev && table_dev, who + ": null argument");
+  DQ_REQUIRE(kind == DQ_UPDATE_DDIM || kind == DQ_UPDATE_STOCHASTIC || kind == DQ_UPDATE_SOLVER_1 || kind == DQ_UPDATE_SOLVER_2M,
+             who + ": unknown update kind");
+  const bool solver = kind == DQ_UPDATE_SOLVER_1 || kind == DQ_UPDATE_SOLVER_2M;
+  DQ_REQUIRE(net_u || solver, who + ": the unguided per-window form is the solver kinds' (thresholding); net_u is needed");
+  DQ_REQUIRE(kind != DQ_UPDATE_STOCHASTIC || seed_dev, who + ": the stochastic update needs the seed (device memory)");
+  DQ_REQUIRE(kind != DQ_UPDATE_SOLVER_2M || x0_hist, who + ": the 2M update needs the x0 history");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0 || pred_type == DQ_PRED_V, who + ": Unknown pred_type");
+  DQ_REQUIRE(!net_u || guidance_ok(w), who + ": the guidance scale must be finite and >= 0");
+  DQ_REQUIRE(B >= 0 && per_window >= 0, who + ": negative size");
+  StepUpdateLaunch a;
+  a.family = kind == DQ_UPDATE_DDIM ? UpdateFamily::DDIM : kind == DQ_UPDATE_STOCHASTIC ? UpdateFamily::STOCHASTIC : UpdateFamily::SOLVER;
+  a.guided = net_u != nullptr; a.pred = pred_type;
+  a.x_t = x_t; a.net = net_c; a.net_u = net_u; a.x_prev = x_prev; a.x_mirror = net_u ? x_mirror : nullptr; a.eps_out = eps_out;
+  a.hist = kind == DQ_UPDATE_SOLVER_2M ? x0_hist : nullptr;
+  a.coef = coef_dev; a.extra = coef_dev + 4;
+  a.ids = window_ids_dev; a.seed = seed_dev; a.draw = draw;
+  a.w = w; a.B = B; a.per = per_window; a.win = table_dev;
+  return launch_update(a, (hipStream_t)stream);
+}
+
+int dq_ddim_sample_adaptive(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                            const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                            const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                            int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                            const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, int guided, float guidance_scale,
+                            float null_ms1, double guidance_rescale, float threshold_quantile, float threshold_max, void* stat_scratch,
+                            int64_t stat_scratch_bytes) {
+  const Guidance g{guidance_scale, null_ms1};
+  const Adaptive ad{guidance_rescale, threshold_quantile, threshold_max, stat_scratch, stat_scratch_bytes};
+  return unet_sample(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type, timesteps_host,
+                     num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream, eta, seed_dev,
+                     window_ids_dev, sampler, clip_x0, guided ? &g : nullptr, true, &ad);
 }
 
 int dq_ms1_cond_drop(const float* ms1_in, float* ms1_out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, double p,

@@ -68,10 +68,13 @@ struct StepKey {
   StepUpdate update = StepUpdate::DDIM;
   float clip = 0.f;
   float guidance = -1.f;
+  // the per-window statistics step: phi, quantile, cap by value and the scratch by address (all 0: none)
+  double rescale = 0.0; float quantile = 0.f, cap = 0.f; const void* stat_scratch = nullptr;
   unsigned opt_epoch = 0;
   bool operator==(const StepKey& o) const {
     return params == o.params && rope == o.rope && ws == o.ws && B == o.B && RT == o.RT && normalize == o.normalize && pred == o.pred &&
-           update == o.update && clip == o.clip && guidance == o.guidance && opt_epoch == o.opt_epoch;
+           update == o.update && clip == o.clip && guidance == o.guidance && rescale == o.rescale && quantile == o.quantile && cap == o.cap &&
+           stat_scratch == o.stat_scratch && opt_epoch == o.opt_epoch;
   }
 };
 

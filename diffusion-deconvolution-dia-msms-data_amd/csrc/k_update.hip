@@ -9,10 +9,15 @@
 // per lane and access; V = 1: one element, for counts that are no multiple of 4 and pointers that are not 16-byte aligned.  No LDS, no
 // atomics.  Bytes per element: 12 (Ddim, Sto), 20 - 24 (Solver); guided + 8 (the second half read, the mirror written); + 4 with eps_out.
 // The fused head-launch form of the Ddim update lives in k_level.hip.
+// The per-window form (the trailing parameter pack Win = one `const float*`): a (B, 4) table [m_b, s_b, rho_b, -] of
+// k_winstat.hip, row i / perv.  Guided, g <- m_b * g (rescaled guidance); Solver, x0 <- clamp(x0, -s_b, s_b) * rho_b (dynamic thresholding;
+// s_b = +inf, rho_b = 1: no clamp).  + 16 bytes per lane-step from the table (L2: a window's lanes read one row).  With an empty pack the
+// parameter list, and so every instantiation above, is what it was.
 #include "dq_common.h"
 #include "dq_guide.h"
 #include "dq_kernels.h"
 #include "dq_philox.h"
+#include "dq_x0.h"
 #include "../../include/dq_hip.h"  // DQ_PRED_*
 #include <algorithm>
 #include <string>
@@ -20,7 +25,7 @@
 namespace dq {
 
 // What an element may need beside its row: the clamp (Solver); seed, window id and draw index (Sto)
-struct UpdateLane { float clip; uint64_t seed; int64_t win; uint32_t draw; };
+struct UpdateLane { float clip; uint64_t seed; int64_t win; uint32_t draw; float rho = 1.f; };  // rho: the per-window form's rho_b (clip is then s_b)
 
 // ``coef`` is a device table of 4 floats per step [sa, sb, sap, sbp]; sap < 0 marks the t == 0 step.
 // PRED (DQ_PRED_*): DQ_PRED_X0 (model.py:274-278): the network output is its x0 prediction, eps = (x_t - sa*x0)/sb is derived.
@@ -91,6 +96,23 @@ __device__ __forceinline__ float solver_elem(const SolverRow& r, float clip, flo
   return r.c1 != 0.f ? y + r.c1 * h : y;
 }
 
+// The per-window form of one element: the same with x0 <- clamp(x0, -s, s) * rho (s > 0; +inf: no clamp) and eps re-derived wherever x0 was
+// changed, i.e. where it was clamped or rho != 1.  (s, rho) = (clip, 1) is solver_elem bit for bit: x0 * 1 is exact.
+template <int PRED>
+__device__ __forceinline__ float solver_elem_win(const SolverRow& r, float s, float rho, float x, float v, float h, float& x0, float& ep) {
+  x0 = net_x0<PRED>(r.sa, r.sb, x, v);
+  if (PRED == DQ_PRED_V) ep = r.sb * x + r.sa * v;
+  else if (PRED == DQ_PRED_EPS) ep = v;
+  bool changed = rho != 1.f;
+  if (x0 < -s) { x0 = -s; changed = true; }
+  else if (x0 > s) { x0 = s; changed = true; }
+  x0 = x0 * rho;
+  if (PRED == DQ_PRED_X0 || changed) ep = (x - r.sa * x0) / r.sb;  // eps consistent with the x0 that is used
+  if (r.cx < 0.f) return x0;
+  const float y = r.cx * x + r.c0 * x0;
+  return r.c1 != 0.f ? y + r.c1 * h : y;
+}
+
 // The families as the kernel sees them.  HIST: the update keeps an x0 history (read when reads_hist(row), written whenever it is given);
 // WINDOW: elem needs the window and the element inside it (and the kernel the seed); EPS_IS_NET: under the eps objective the unguided
 // step's eps is the network output itself and is not stored again; RESTRICT: the unguided form's tensors never alias.
@@ -125,6 +147,10 @@ struct Solver {
   static __device__ __forceinline__ float elem(const Row& r, const UpdateLane& k, float x, float v, float h, uint32_t, float& x0, float& ep) {
     return solver_elem<PRED>(r, k.clip, x, v, h, x0, ep);
   }
+  template <int PRED>
+  static __device__ __forceinline__ float elem_win(const Row& r, const UpdateLane& k, float x, float v, float h, uint32_t, float& x0, float& ep) {
+    return solver_elem_win<PRED>(r, k.clip, k.rho, x, v, h, x0, ep);
+  }
 };
 
 // V floats of p at index i (in units of V floats)
@@ -144,13 +170,19 @@ template <> struct UpdatePtr<true> { using in = const float* __restrict__; using
 
 // nv, perv: the element count and the per-window count in units of V.  The window of lane-step i is i / perv, its first element
 // V * (i % perv): a lane's elements never straddle two windows (V == 4 runs only when the per-window count is a multiple of 4).
-template <class F, int PRED, bool GUIDED, int V>
+// Win: empty, or the per-window table (one `const float*`; V == 4 then runs only when the per-window count is a multiple of 4, as for Sto).
+__device__ __forceinline__ const float* win_table() { return nullptr; }
+__device__ __forceinline__ const float* win_table(const float* t) { return t; }
+
+template <class F, int PRED, bool GUIDED, int V, class... Win>
 __global__ void __launch_bounds__(256) k_step_update(typename UpdatePtr<F::RESTRICT && !GUIDED>::in x_t, typename UpdatePtr<F::RESTRICT && !GUIDED>::in net_c,
                                                      typename UpdatePtr<F::RESTRICT && !GUIDED>::in net_u, typename UpdatePtr<F::RESTRICT && !GUIDED>::out x_prev,
                                                      typename UpdatePtr<F::RESTRICT && !GUIDED>::out x_mirror, typename UpdatePtr<F::RESTRICT && !GUIDED>::out hist,
                                                      typename UpdatePtr<F::RESTRICT && !GUIDED>::out eps_out, const float* __restrict__ coef,
                                                      const float* __restrict__ extra, const int64_t* __restrict__ ids, const uint64_t* __restrict__ seed_p,
-                                                     uint32_t draw, float clip, float gw, int64_t nv, int64_t perv, const int* __restrict__ step_ptr) {
+                                                     uint32_t draw, float clip, float gw, int64_t nv, int64_t perv, const int* __restrict__ step_ptr, Win... win) {
+  constexpr bool WIN = sizeof...(Win) != 0;
+  const float* __restrict__ tab = win_table(win...);
   const typename F::Row r = F::row(coef, extra, step_ptr, draw);
   UpdateLane k{clip, 0, 0, draw};
   if constexpr (F::WINDOW) k.seed = seed_p[0];
@@ -166,6 +198,15 @@ __global__ void __launch_bounds__(256) k_step_update(typename UpdatePtr<F::RESTR
 #pragma unroll
       for (int j = 0; j < V; ++j) nv_[j] = guide(nv_[j], uv[j], gw);
     }
+    if constexpr (WIN) {
+      const float* __restrict__ t = tab + 4 * (i / perv);  // this window's [m, s, rho, -]
+      if constexpr (GUIDED) {
+        const float m = t[0];
+#pragma unroll
+        for (int j = 0; j < V; ++j) nv_[j] = m * nv_[j];
+      }
+      if constexpr (F::HIST) { k.clip = t[1]; k.rho = t[2]; }
+    }
 #pragma unroll
     for (int j = 0; j < V; ++j) hv[j] = 0.f;
     if constexpr (F::HIST) { if (rd_hist) load_v<V>(hist, i, hv); }
@@ -176,7 +217,10 @@ __global__ void __launch_bounds__(256) k_step_update(typename UpdatePtr<F::RESTR
       k.win = ids ? ids[b] : b;
     }
 #pragma unroll
-    for (int j = 0; j < V; ++j) ov[j] = F::template elem<PRED>(r, k, xv[j], nv_[j], hv[j], e0 + (uint32_t)j, zv[j], dv[j]);
+    for (int j = 0; j < V; ++j) {
+      if constexpr (WIN && F::HIST) ov[j] = F::template elem_win<PRED>(r, k, xv[j], nv_[j], hv[j], e0 + (uint32_t)j, zv[j], dv[j]);
+      else ov[j] = F::template elem<PRED>(r, k, xv[j], nv_[j], hv[j], e0 + (uint32_t)j, zv[j], dv[j]);
+    }
     store_v<V>(x_prev, i, ov);
     if constexpr (GUIDED) { if (x_mirror) store_v<V>(x_mirror, i, ov); }
     if constexpr (F::HIST) { if (hist) store_v<V>(hist, i, zv); }
@@ -184,20 +228,24 @@ __global__ void __launch_bounds__(256) k_step_update(typename UpdatePtr<F::RESTR
   }
 }
 
-template <class F, bool GUIDED, int V>
-static int launch_update_as(const StepUpdateLaunch& a, int64_t nv, hipStream_t s) {
+template <class F, bool GUIDED, int V, class... Win>
+static int launch_update_as(const StepUpdateLaunch& a, int64_t nv, hipStream_t s, Win... win) {
   const int grid = (int)std::min<int64_t>(cdiv(nv, 256), 2048);
-  const auto kernel = a.pred == DQ_PRED_V    ? k_step_update<F, DQ_PRED_V, GUIDED, V>
-                      : a.pred == DQ_PRED_X0 ? k_step_update<F, DQ_PRED_X0, GUIDED, V>
-                                             : k_step_update<F, DQ_PRED_EPS, GUIDED, V>;
+  const auto kernel = a.pred == DQ_PRED_V    ? k_step_update<F, DQ_PRED_V, GUIDED, V, Win...>
+                      : a.pred == DQ_PRED_X0 ? k_step_update<F, DQ_PRED_X0, GUIDED, V, Win...>
+                                             : k_step_update<F, DQ_PRED_EPS, GUIDED, V, Win...>;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, a.x_t, a.net, a.net_u, a.x_prev, a.x_mirror, a.hist, a.eps_out, a.coef, a.extra, a.ids,
-                     a.seed, (uint32_t)a.draw, a.clip > 0.f ? a.clip : 0.f /* (NaN and negatives: off) */, a.w, nv, a.per / V, a.step_ptr);
+                     a.seed, (uint32_t)a.draw, a.clip > 0.f ? a.clip : 0.f /* (NaN and negatives: off) */, a.w, nv, a.per / V, a.step_ptr, win...);
   DQ_LAUNCH_CHECK();
   return 0;
 }
 
 template <class F>
 static int launch_update_of(const StepUpdateLaunch& a, bool vec, int64_t n, hipStream_t s) {
+  if (a.win) {  // the per-window form: guided (reads m_b), or the Solver family (reads s_b, rho_b); anything else was refused
+    if (a.guided) return vec ? launch_update_as<F, true, 4>(a, n / 4, s, a.win) : launch_update_as<F, true, 1>(a, n, s, a.win);
+    if constexpr (F::HIST) return vec ? launch_update_as<F, false, 4>(a, n / 4, s, a.win) : launch_update_as<F, false, 1>(a, n, s, a.win);
+  }
   if (a.guided) return vec ? launch_update_as<F, true, 4>(a, n / 4, s) : launch_update_as<F, true, 1>(a, n, s);
   return vec ? launch_update_as<F, false, 4>(a, n / 4, s) : launch_update_as<F, false, 1>(a, n, s);
 }
@@ -213,14 +261,15 @@ int launch_update(const StepUpdateLaunch& a, hipStream_t s) {
   else DQ_REQUIRE(a.B >= 0 && a.per >= 0 && a.per % 4 == 0 && a.per <= (int64_t)0xffffffff,
                   who + ": need B >= 0 and a per-window element count that is a multiple of 4 below 2^32");
   if (sto) DQ_REQUIRE(a.draw >= 0, who + ": the draw index must be >= 0");
+  DQ_REQUIRE(!a.win || a.guided || solver, who + ": the per-window table needs a guided or a Solver update");
   const uintptr_t bits = (uintptr_t)a.x_t | (uintptr_t)a.net | (uintptr_t)a.net_u | (uintptr_t)a.x_prev | (uintptr_t)a.x_mirror | (uintptr_t)a.hist |
-                         (uintptr_t)a.eps_out;
+                         (uintptr_t)a.eps_out | ((uintptr_t)a.win & 3);
   if (sto && !a.guided) DQ_REQUIRE((bits & 15) == 0, who + ": tensors must be 16-byte aligned");
   else DQ_REQUIRE((bits & 3) == 0, who + ": tensors must be 4-byte aligned");
   const int64_t n = (int64_t)a.B * a.per;
   if (n == 0) return 0;
-  // 16 bytes per lane iff no lane's four elements straddle two windows (Sto) or the end (the others) and every tensor is 16-byte aligned
-  const bool vec = (sto ? a.per : n) % 4 == 0 && (bits & 15) == 0;
+  // 16 bytes per lane iff no lane's four elements straddle two windows (Sto, the per-window form) or the end (the others) and every tensor is 16-byte aligned
+  const bool vec = (sto || a.win ? a.per : n) % 4 == 0 && (bits & 15) == 0;
   switch (a.family) {
     case UpdateFamily::DDIM: return launch_update_of<Ddim>(a, vec, n, s);
     case UpdateFamily::STOCHASTIC: return launch_update_of<Sto>(a, vec, n, s);

@@ -101,6 +101,14 @@ PROTOTYPES = {
     "dq_ddim_sample_v": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                  POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
                                  c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_int, c_float, c_float]),
+    "dq_sample_stat_scratch_bytes": (c_int64, [c_int, c_int64]),
+    "dq_window_rescale": (c_int, [c_void_p, c_void_p, c_float, c_double, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "dq_window_abs_quantile": (c_int, [c_void_p, c_int, c_int64, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
+    "dq_step_update_adaptive": (c_int, [c_int] + [c_void_p] * 8 + [c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
+    "dq_ddim_sample_adaptive": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                        POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
+                                        c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_int, c_float, c_float, c_double, c_float, c_float,
+                                        c_void_p, c_int64]),
     "dq_ms1_cond_drop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_float, c_int, c_int64, c_void_p]),
     "dq_ddim_sample_guided": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                       POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,

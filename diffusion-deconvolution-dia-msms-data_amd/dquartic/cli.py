@@ -225,11 +225,18 @@ def load_inference_checkpoint(dm, m, checkpoint, device, use_ema):
 @click.option("--guidance-scale", default=None, type=float,
               help="Classifier-free guidance scale W of that sampling (UNet1d trained with model.cond_drop_prob; 1: the conditional model)")
 @click.option("--null-ms1", default=0.0, type=float, help="Raw MS1 value of the null condition (the training run's model.null_ms1)")
+@click.option("--guidance-rescale", default=0.0, type=float,
+              help="Rescaled guidance PHI in [0, 1]: scale each window's guided output towards the conditional output's spread (needs --guidance-scale)")
+@click.option("--threshold-quantile", default=None, type=float,
+              help="Dynamic thresholding: clamp every step's x0 estimate to the window's Q-quantile of |x0| (never below --clip-x0, or 1) and "
+                   "scale it back to that floor (ddim / dpmpp_2m, eta 0)")
+@click.option("--threshold-max", default=None, type=float, help="Upper bound of the dynamic threshold (needs --threshold-quantile)")
 @click.option("--seed", default=0, type=int, help="Seed of the evaluation noise and of the sampling")
 @click.option("--use-ema/--no-use-ema", default=None, help="Evaluate the averaged weights (default: when the checkpoint has an average)")
 @click.option("--max-batches", default=None, type=int, help="Stop after this many batches")
 @click.option("--out", "out_path", default=None, type=click.Path(), help="Write the full result, per-window metrics included, as JSON")
-def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, guidance_scale, null_ms1, seed, use_ema, max_batches, out_path):
+def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile,
+             threshold_max, seed, use_ema, max_batches, out_path):
     """Held-out loss (and, with --num-steps, reconstruction metrics) of a checkpoint on the config's data.validation set.  The pairs of
     that set come from the block's own seed, not from --seed: runs that differ in --seed, --eta, --num-steps or --use-ema score the same
     pairs.  Without a validation block the config's data section is scored, with a notice.  Prints one JSON line."""
@@ -248,7 +255,8 @@ def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, guidance
     dm = build_model(m, device)
     load_inference_checkpoint(dm, m, checkpoint, device, use_ema)
     res = dm.evaluate(loader, n_t=4, seed=seed, num_steps=num_steps, eta=eta, use_ema=use_ema, max_batches=max_batches, sampler=sampler,
-                      clip_x0=clip_x0, guidance_scale=guidance_scale, null_ms1=null_ms1)
+                      clip_x0=clip_x0, guidance_scale=guidance_scale, null_ms1=null_ms1, guidance_rescale=guidance_rescale,
+                      threshold_quantile=threshold_quantile, threshold_max=threshold_max)
     # the per-window arrays go to --out only; the printed line keeps the scalars and the buckets (val_loss_by_weight among them)
     arrays = {k: res.pop(k).tolist() for k in ("per_window", "target_weight") if k in res}
     click.echo(json.dumps(res))
@@ -277,10 +285,16 @@ def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, guidance
 @click.option("--guidance-scale", default=None, type=float,
               help="Classifier-free guidance scale W of the sampling (UNet1d trained with model.cond_drop_prob; 1: the conditional model)")
 @click.option("--null-ms1", default=0.0, type=float, help="Raw MS1 value of the null condition (the training run's model.null_ms1)")
+@click.option("--guidance-rescale", default=0.0, type=float,
+              help="Rescaled guidance PHI in [0, 1]: scale each window's guided output towards the conditional output's spread (needs --guidance-scale)")
+@click.option("--threshold-quantile", default=None, type=float,
+              help="Dynamic thresholding: clamp every step's x0 estimate to the window's Q-quantile of |x0| (never below --clip-x0, or 1) and "
+                   "scale it back to that floor (ddim / dpmpp_2m, eta 0)")
+@click.option("--threshold-max", default=None, type=float, help="Upper bound of the dynamic threshold (needs --threshold-quantile)")
 @click.option("--seed", default=0, type=int, help="Seed of x_T and of the sampling noise")
 @click.option("--use-ema/--no-use-ema", default=None, help="Sample from the averaged weights (default: when the checkpoint has an average)")
 def deconvolve(config_path, checkpoint, ms2_path, ms1_path, out_path, window, step, taper, batch_size, num_steps, eta, sampler, clip_x0,
-               guidance_scale, null_ms1, seed, use_ema):
+               guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max, seed, use_ema):
     """Deconvolve whole chromatograms with a checkpoint: every run is cut into overlapping windows, each window normalised on its own and
     sampled, and the predictions stitched back in intensity units (``deconvolve_run``).  Window i of run r samples under the id
     (windows of the runs before it) + i.  Prints one JSON line: runs, windows, windows per second."""
@@ -309,6 +323,12 @@ def deconvolve(config_path, checkpoint, ms2_path, ms1_path, out_path, window, st
     kw = {"sampler": sampler, "clip_x0": clip_x0}
     if guidance_scale is not None:
         kw.update(guidance_scale=guidance_scale, null_ms1=null_ms1)
+    if guidance_rescale:
+        kw["guidance_rescale"] = guidance_rescale
+    if threshold_quantile is not None:
+        kw["threshold_quantile"] = threshold_quantile
+    if threshold_max is not None:
+        kw["threshold_max"] = threshold_max
     outs, first = [], 0
     torch.cuda.synchronize()
     t0 = time.perf_counter()

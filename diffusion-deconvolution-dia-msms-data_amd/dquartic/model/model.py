@@ -305,8 +305,40 @@ class DDIMDiffusionModel(ModelInterface):
             raise ValueError(f"guidance_scale must be a finite number >= 0 or None, got {guidance_scale!r}")
         return None if w == 1.0 else w
 
+    @staticmethod
+    def _check_adaptive(guidance_rescale, threshold_quantile, threshold_max, sampler, eta, clip):
+        """(phi, q or 0.0, cap): the two per-window options as the library takes them.  ValueError for ``phi`` outside
+        [0, 1], ``q`` outside (0, 1] (as the float32 the kernels take it as), a cap below the floor, NaN anywhere, and thresholding with
+        the combinations ``clip_x0`` is refused with."""
+        try:
+            phi = float(guidance_rescale)
+        except (TypeError, ValueError):
+            raise ValueError(f"guidance_rescale must be a number in [0, 1], got {guidance_rescale!r}") from None
+        if not (0.0 <= phi <= 1.0):  # (NaN fails the comparison)
+            raise ValueError(f"guidance_rescale must be a number in [0, 1], got {guidance_rescale!r}")
+        if threshold_quantile is None:
+            if threshold_max is not None:
+                raise ValueError("threshold_max needs threshold_quantile")
+            return phi, 0.0, float("inf")
+        try:
+            q = float(torch.tensor(float(threshold_quantile), dtype=torch.float32))
+        except (TypeError, ValueError):
+            raise ValueError(f"threshold_quantile must be a number in (0, 1] or None, got {threshold_quantile!r}") from None
+        if not (0.0 < q <= 1.0):
+            raise ValueError(f"threshold_quantile must be a number in (0, 1] or None, got {threshold_quantile!r}")
+        if sampler == "reference":
+            raise ValueError("threshold_quantile needs sampler 'ddim' or 'dpmpp_2m'")
+        if eta > 0.0:
+            raise ValueError("threshold_quantile needs eta == 0")
+        floor = clip if clip > 0.0 else 1.0
+        cap = float("inf") if threshold_max is None else float(threshold_max)
+        if not cap >= floor:
+            raise ValueError(f"threshold_max must be >= the floor ({floor!r}: clip_x0, or 1 without it), got {threshold_max!r}")
+        return phi, q, cap
+
     def sample(self, x_t, ms2_cond=None, ms1_cond=None, num_steps=1000, return_trajectory=False, eta=0.0, seed=None, window_ids=None,
-               shape=None, sampler="reference", clip_x0=None, guidance_scale=None, null_ms1=0.0):
+               shape=None, sampler="reference", clip_x0=None, guidance_rescale=0.0, threshold_quantile=None, threshold_max=None,
+               guidance_scale=None, null_ms1=0.0):
         """model.py:293-324: returns (denoised, mixture - denoised).  Native loop when the network is UNet1d; for a CustomTransformer behind
         ``DDIMTransformerAdapter`` the library's loop (``dq_tfm_sample``) serves every call when
         ``native_tfm_sampler`` is set, and otherwise exactly the calls the generic loop refuses (the options below, ``return_trajectory``).
@@ -328,14 +360,37 @@ class DDIMDiffusionModel(ModelInterface):
         and 1.0 are the call as it is without the option, bit for bit: 1.0 *is* the conditional model, no doubled batch is run for it.
         Any other finite ``w >= 0`` (0: the unconditional model; > 1 pushes towards the component MS1 names) runs one forward at twice
         the batch per step inside the library (``dq_ddim_sample_guided``) and combines with every option above.  UNet1d on the GPU
-        only: the generic loop and the CustomTransformer raise NotImplementedError."""
+        only: the generic loop and the CustomTransformer raise NotImplementedError.
+
+        ``guidance_rescale = phi`` in [0, 1] and ``threshold_quantile = q`` in (0, 1] look at each window as a
+        whole.  Rescaled guidance (Lin et al. 2024): the guided output of a window is multiplied by ``phi * std(c) / std(g) + (1 - phi)``,
+        which takes back the spread a scale well above 1 adds; it needs ``guidance_scale`` (with ``None`` or 1.0 it is a no-op, ``g = c``)
+        and works with every sampler and ``eta``.  Dynamic thresholding (Saharia et al. 2022): every step's x0 estimate is clamped to the
+        window's ``q``-quantile ``s`` of ``|x0|`` -- never below the floor ``f = clip_x0`` (1 without it), never above ``threshold_max`` --
+        and scaled by ``f / s``, which keeps the shape of a peak the constant clamp would cut flat; it is allowed where ``clip_x0`` is
+        ('ddim' or 'dpmpp_2m', ``eta == 0``).  The defaults are the call as it is without the options, bit for bit and launch for launch.
+        UNet1d on the GPU only (``dq_ddim_sample_adaptive``)."""
         eta = self._check_eta(eta)
         sampler_id, clip = self._check_sampler(sampler, eta, clip_x0)
         guidance = self._check_guidance(guidance_scale)
+        phi, thr_q, thr_cap = self._check_adaptive(guidance_rescale, threshold_quantile, threshold_max, sampler, eta, clip)
+        if guidance is None:
+            phi = 0.0  # (g = c: m = 1)
+        adaptive = (phi, thr_q, thr_cap) if (phi > 0.0 or thr_q > 0.0) else None
         stochastic = eta > 0.0 or x_t is None or seed is not None or window_ids is not None
         if sampler_id != 0:
             self._check_decreasing(self.sampler_timesteps(self.num_timesteps, num_steps).tolist())
         on_gpu = ms2_cond is not None and ms1_cond is not None and (x_t.is_cuda if x_t is not None else ms2_cond.is_cuda)
+        if adaptive is not None:
+            if self._native_tfm:
+                raise NotImplementedError("sample: guidance_rescale and threshold_quantile are built for UNet1d (dq_ddim_sample_adaptive); the "
+                                          "per-window statistics step for the CustomTransformer's sampler (dq_tfm_sample) is the follow-up")
+            if not (self.native and on_gpu):
+                raise NotImplementedError("sample: guidance_rescale and threshold_quantile need the native sampler (this package's UNet1d on "
+                                          "the GPU with both conditions); the generic loop is the plain update only")
+            return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
+                                       shape=shape, sampler=sampler_id, clip_x0=clip,
+                                       guidance=None if guidance is None else (guidance, float(null_ms1)), adaptive=adaptive)
         if guidance is not None:
             if self._native_tfm:
                 raise NotImplementedError("sample: guidance_scale is built for UNet1d (dq_ddim_sample_guided); guidance for the "
@@ -424,8 +479,9 @@ class DDIMDiffusionModel(ModelInterface):
             torch.empty((num_steps, *dims), device=c2.device) if return_trajectory else None for _ in range(2)]
 
     def _sample_native(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False, eta=None, seed=None, window_ids=None, shape=None,
-                       sampler=0, clip_x0=0.0, guidance=None):
-        """``eta`` None: ``dq_ddim_sample`` (the call as it always was); else ``dq_ddim_sample_ex``; ``sampler`` != 0:
+                       sampler=0, clip_x0=0.0, guidance=None, adaptive=None):
+        """``adaptive`` = (phi, q, cap) (``eta`` a number): ``dq_ddim_sample_adaptive``, ``dq_ddim_sample_v``'s list plus the three and the
+        statistics scratch.  Otherwise ``eta`` None: ``dq_ddim_sample`` (the call as it always was); else ``dq_ddim_sample_ex``; ``sampler`` != 0:
         ``dq_ddim_sample_solver``; ``guidance`` = (scale, null_ms1) (``eta`` a number): ``dq_ddim_sample_guided`` on the workspace of twice
         the batch.  The four take one argument list; the later ones append to it.  ``pred_type="v_prediction"``: ``dq_ddim_sample_v``, the
         same list with a ``guided`` flag in front of the scale, for every one of these forms."""
@@ -441,12 +497,16 @@ class DDIMDiffusionModel(ModelInterface):
                 N.ptr(c1), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], ts_c, num_steps, *(N.ptr(v) for v in outs),
                 1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws), ws.numel(), B, RT, N.stream_ptr()]
         entry = "dq_ddim_sample"
-        if self.pred_type == "v_prediction":
+        if self.pred_type == "v_prediction" or adaptive is not None:
             # one entry for every form of the loop (dq_ddim_sample_solver, which the others above call, is held to refusing the value 2)
             seed_dev, ids_dev = self._stage_noise(x_T, eta or 0.0, seed, window_ids, B, c2.device)
             args += [float(eta or 0.0), N.ptr(seed_dev), N.ptr(ids_dev), int(sampler), float(clip_x0), 0 if guidance is None else 1,
                      float(guidance[0]) if guidance is not None else 1.0, float(guidance[1]) if guidance is not None else 0.0]
             entry = "dq_ddim_sample_v"
+            if adaptive is not None:
+                stat = net.stat_scratch(B, RT * MZ)
+                args += [float(adaptive[0]), float(adaptive[1]), float(adaptive[2]), N.ptr(stat), stat.numel()]
+                entry = "dq_ddim_sample_adaptive"
         elif eta is not None:
             seed_dev, ids_dev = self._stage_noise(x_T, eta, seed, window_ids, B, c2.device)
             args += [float(eta), N.ptr(seed_dev), N.ptr(ids_dev)]

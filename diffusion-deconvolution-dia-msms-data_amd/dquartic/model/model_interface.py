@@ -674,7 +674,8 @@ class ModelInterface(object):
         return self.ema_scope() if use else contextlib.nullcontext()
 
     def predict(self, dataloader, mixture_weights=(0.5, 0.5), num_steps=1000, use_ema=None, eta=0.0, seed=None, n_draws=1,
-                sampler="reference", clip_x0=None, *, guidance_scale=None, null_ms1=0.0):
+                sampler="reference", clip_x0=None, *, guidance_rescale=0.0, threshold_quantile=None, threshold_max=None,
+                guidance_scale=None, null_ms1=0.0):
         """Reference :630-668: one dict per batch with the first item's prediction (``_predict_one_batch`` returns item 0).
         ``use_ema``: sample from the averaged weights; None (default) = when EMA is enabled.
 
@@ -686,10 +687,12 @@ class ModelInterface(object):
         population form) to each dict; ``"pred"`` stays draw 0.  With ``n_draws == 1`` those two keys are absent.
 
         ``sampler`` / ``clip_x0``: passed to ``sample``; with the defaults nothing else changes.  ``guidance_scale``
-        / ``null_ms1`` (keyword-only): classifier-free guidance, passed to ``sample`` too.
+        / ``null_ms1`` (keyword-only): classifier-free guidance, passed to ``sample`` too; so are
+        ``guidance_rescale`` / ``threshold_quantile`` / ``threshold_max``.
 
         Batches that carry their weights (``ResidentMixLoader``) add ``"weights"``, the batch's ``(B, K)`` array."""
         self.model.eval()
+        sampler_kw = _sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max)
         n_draws = int(n_draws)
         if n_draws < 1:
             raise ValueError(f"n_draws must be >= 1, got {n_draws}")
@@ -705,11 +708,11 @@ class ModelInterface(object):
                 d["weights"] = weights.cpu().numpy()
             if not stochastic:
                 d["pred"], _ = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, use_ema=use_ema,
-                                                       **_sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1))
+                                                       **sampler_kw)
             else:
                 ids = torch.arange(first, first + x_0.shape[0], dtype=torch.int64)
                 out = self._predict_one_batch(x_0, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, use_ema=use_ema, eta=eta,
-                                              seed=seed, n_draws=n_draws, window_ids=ids, **_sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1))
+                                              seed=seed, n_draws=n_draws, window_ids=ids, **sampler_kw)
                 d["pred"] = out[0]
                 if n_draws > 1:
                     d["pred_mean"], d["pred_std"] = out[2], out[3]
@@ -718,7 +721,8 @@ class ModelInterface(object):
         return np.array(preds, dtype=object)
 
     def evaluate(self, dataloader, mixture_weights=(0.5, 0.5), n_t=4, seed=0, num_steps=None, eta=0.0, use_ema=None, max_batches=None,
-                 sampler="reference", clip_x0=None, *, guidance_scale=None, null_ms1=0.0):
+                 sampler="reference", clip_x0=None, *, guidance_rescale=0.0, threshold_quantile=None, threshold_max=None,
+                 guidance_scale=None, null_ms1=0.0):
         """Held-out evaluation (new work: the reference has none).  Returns a dict.
 
         Loss: every window of the loader is evaluated ``n_t`` times by ``eval_steps`` -- repeat k at the timestep
@@ -736,7 +740,8 @@ class ModelInterface(object):
         their means over the windows (``scan_sa`` / ``xic_r`` weighted by ``scan_count`` / ``xic_count``) under those names and the
         ``(n_windows, 9)`` float32 array as ``per_window``.  ``sampler`` / ``clip_x0`` go to that ``sample`` call
         and appear in the dict only when they are not the defaults; so do ``guidance_scale`` / ``null_ms1`` (keyword-only; DESIGN.md
-        section 32: the scale can be tuned against these metrics).  The loss part is always the conditional one.
+        section 32: the scale can be tuned against these metrics) and ``guidance_rescale`` / ``threshold_quantile`` / ``threshold_max``
+        (DESIGN.md section 38).  The loss part is always the conditional one.
 
         ``use_ema`` as in ``predict``; ``max_batches``: stop after that many batches.  Under ``torch.distributed`` each rank evaluates
         its own loader and the scalars are averaged over the ranks (``_global_mean``); ``per_window`` and ``n_windows`` stay the rank's.
@@ -753,6 +758,7 @@ class ModelInterface(object):
             raise ValueError(f"n_t must be >= 1, got {n_t}")
         was_training = self.model.training
         self.model.eval()
+        sampler_kw = _sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max)
         T = int(self.num_timesteps)
         lw_host = self.loss_weight.detach().to("cpu", torch.float32).numpy().astype(np.float64)
         mse, ts, rows, target_w = [[] for _ in range(n_t)], [[] for _ in range(n_t)], [], []
@@ -777,7 +783,7 @@ class ModelInterface(object):
                         ts[k].append(t[k])
                     if num_steps is not None:
                         sample, _ = self.sample(None, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=int(num_steps), eta=eta, seed=int(seed),
-                                                window_ids=ids_dev, shape=tuple(x_0.shape), **_sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1))
+                                                window_ids=ids_dev, shape=tuple(x_0.shape), **sampler_kw)
                         rows.append(E.recon_metrics(sample, x_0))
                     first += x_0.shape[0]
         finally:
@@ -800,6 +806,12 @@ class ModelInterface(object):
                 out["clip_x0"] = float(clip_x0)
             if guidance_scale is not None:
                 out.update(guidance_scale=float(guidance_scale), null_ms1=float(null_ms1))
+            if guidance_rescale:
+                out["guidance_rescale"] = float(guidance_rescale)
+            if threshold_quantile is not None:
+                out["threshold_quantile"] = float(threshold_quantile)
+            if threshold_max is not None:
+                out["threshold_max"] = float(threshold_max)
         if target_w:  # batches that carry their weights (ResidentMixLoader): the loss by the target's share of its mixture
             tw = torch.cat(target_w).cpu().numpy().astype(np.float32)
             if len(tw) != first:
@@ -808,7 +820,8 @@ class ModelInterface(object):
             out["val_loss_by_weight"] = E.by_target_weight(tw, mse.mean(axis=0), None if num_steps is None else out["per_window"])
         return out
 
-    _RUN_SAMPLE_OPTIONS = ("num_steps", "eta", "seed", "sampler", "clip_x0", "guidance_scale", "null_ms1", "use_ema")
+    _RUN_SAMPLE_OPTIONS = ("num_steps", "eta", "seed", "sampler", "clip_x0", "guidance_scale", "null_ms1", "guidance_rescale",
+                           "threshold_quantile", "threshold_max", "use_ema")
 
     def deconvolve_run(self, ms2_run, ms1_run, window=None, step=5, taper="hann", batch_size=32, id_offset=0, **sample_options):
         """Deconvolve one observed isolation-window chromatogram (new work: the reference has no such entry).
@@ -826,7 +839,8 @@ class ModelInterface(object):
 
         ``taper``: the weight of a window's scan k in the blend -- ``"hann"`` (sin^2(pi (k + 1) / (W + 1)), strictly positive),
         ``"uniform"``, or ``window`` positive numbers.  ``sample_options``: ``num_steps``, ``eta``, ``seed``, ``sampler``, ``clip_x0``,
-        ``guidance_scale``, ``null_ms1`` go to ``sample`` as they are; ``use_ema`` as in ``predict``.  ``seed=None``: drawn once from
+        ``guidance_scale``, ``null_ms1``, ``guidance_rescale``, ``threshold_quantile``, ``threshold_max`` go to ``sample`` as they are;
+        ``use_ema`` as in ``predict``.  ``seed=None``: drawn once from
         torch's generator (x_T needs one), and kept in ``last_seed``.
 
         Returns a dict: ``"pred"`` ``(RT_total, MZ)``, the deconvolved chromatogram in intensity units ABOVE each window's floor -- the
@@ -1019,16 +1033,18 @@ class ModelInterface(object):
         return loss.item() if sync else loss.detach()
 
     def _predict_one_batch(self, x_0, ms2_cond=None, ms1_cond=None, num_steps=1000, use_ema=None, eta=0.0, seed=None, n_draws=1,
-                           window_ids=None, sampler="reference", clip_x0=None, *, guidance_scale=None, null_ms1=0.0):
+                           window_ids=None, sampler="reference", clip_x0=None, *, guidance_rescale=0.0, threshold_quantile=None,
+                           threshold_max=None, guidance_scale=None, null_ms1=0.0):
         """Reference :1125-1150: eval + no_grad + sample(randn_like(x_0)); returns item 0 of the batch as numpy.  ``use_ema`` as in
         ``predict``.  With ``eta > 0``, a ``seed`` or ``n_draws > 1`` (see ``predict``): x_T and the step noise from the sampler's
         generator, draw j under ``seed + j``; ``n_draws > 1`` returns (sample, pred_noise, mean, std) of item 0, sample / pred_noise
         being draw 0's and mean / std taken per element over the draws' samples (torch reductions: this is not the hot path)."""
         self.model.eval()
+        sampler_kw = _sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max)
         if not (float(eta) > 0.0 or seed is not None or int(n_draws) > 1):
             with torch.no_grad(), self._ema_or_null_scope(use_ema):
                 sample, pred_noise = self.sample(torch.randn_like(x_0), ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps,
-                                                 **_sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1))
+                                                 **sampler_kw)
             return sample[0].cpu().detach().numpy(), pred_noise[0].cpu().detach().numpy()
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
@@ -1036,7 +1052,7 @@ class ModelInterface(object):
         with torch.no_grad(), self._ema_or_null_scope(use_ema):
             for j in range(int(n_draws)):
                 draws.append(self.sample(None, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps, eta=eta, seed=int(seed) + j,
-                                         window_ids=window_ids, shape=tuple(x_0.shape), **_sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1)))
+                                         window_ids=window_ids, shape=tuple(x_0.shape), **sampler_kw))
         first = (draws[0][0][0].cpu().numpy(), draws[0][1][0].cpu().numpy())
         if int(n_draws) == 1:
             return first
@@ -1049,9 +1065,9 @@ class ModelInterface(object):
     plot_single_prediction = log_single_prediction
 
 
-def _sampler_kwargs(sampler, clip_x0, guidance_scale=None, null_ms1=0.0):
-    """The step-consistent-sampler and guidance options as keyword arguments of ``sample`` -- none at the defaults, so that a subclass
-    whose ``sample`` predates them is still called as it always was."""
+def _sampler_kwargs(sampler, clip_x0, guidance_scale=None, null_ms1=0.0, guidance_rescale=0.0, threshold_quantile=None, threshold_max=None):
+    """The step-consistent-sampler, guidance and per-window options as keyword arguments of ``sample`` -- none at the defaults, so that a
+    subclass whose ``sample`` predates them is still called as it always was."""
     kw = {}
     if sampler != "reference":
         kw["sampler"] = sampler
@@ -1060,6 +1076,12 @@ def _sampler_kwargs(sampler, clip_x0, guidance_scale=None, null_ms1=0.0):
     if guidance_scale is not None:
         kw["guidance_scale"] = guidance_scale
         kw["null_ms1"] = null_ms1
+    if guidance_rescale:
+        kw["guidance_rescale"] = guidance_rescale
+    if threshold_quantile is not None:
+        kw["threshold_quantile"] = threshold_quantile
+    if threshold_max is not None:
+        kw["threshold_max"] = threshold_max
     return kw
 
 

@@ -319,6 +319,19 @@ class UNet1d(_FlatBuffers, nn.Module):
     def workspace(self, B: int, RT: int, training: bool) -> torch.Tensor:
         return self._cached_workspace("train" if training else "infer", (B, RT), lambda: self._workspace_bytes(B, RT, training), self._WS_FAIL)
 
+    def stat_scratch(self, B: int, per: int) -> torch.Tensor:
+        """The statistics scratch of ``sample``'s per-window options (``dq_sample_stat_scratch_bytes``): bytes, the
+        identical buffer while (B, per) and the device stay -- its address is part of a captured step.  Beside the workspaces, not one of
+        them: they and their sizes are what they were."""
+        key = (int(B), int(per), str(self._flat_buffer().device))
+        hit = getattr(self, "_stat_scratch", None)
+        if hit is None or hit[0] != key:
+            nbytes = N.lib().dq_sample_stat_scratch_bytes(int(B), int(per))
+            if nbytes < 0:
+                raise RuntimeError(f"dq_sample_stat_scratch_bytes failed for B={B}, per={per}")
+            hit = self._stat_scratch = (key, torch.empty(nbytes, dtype=torch.uint8, device=self._flat_buffer().device))
+        return hit[1]
+
     def __del__(self):
         try:
             if getattr(self, "_plan", None):

@@ -59,7 +59,8 @@ const char* dq_last_error(void);
  * dq_q_sample_repeats, dq_mse_per_window_repeats, dq_tfm_kv_broadcast; classifier-free guidance: DQ_UPDATE_*, dq_guided_update,
  * dq_ms1_cond_drop, dq_ddim_sample_guided; K-component mixtures: dq_mix_batch_scratch_bytes, dq_mix_batch; the v objective: DQ_PRED_V,
  * dq_ddim_step_v, dq_solver_step_v, dq_guided_update_v, dq_ddim_sample_v, dq_mse_loss_v_fwd_bwd, dq_mse_per_window_v; whole
- * chromatograms: dq_run_window_count, dq_run_windows_scratch_bytes, dq_run_windows, dq_run_stitch). */
+ * chromatograms: dq_run_window_count, dq_run_windows_scratch_bytes, dq_run_windows, dq_run_stitch; per-window sampler control:
+ * dq_sample_stat_scratch_bytes, dq_window_rescale, dq_window_abs_quantile, dq_step_update_adaptive, dq_ddim_sample_adaptive). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -436,6 +437,61 @@ int dq_ddim_sample_guided(dq_plan* plan, const float* params, const float* rope_
                           int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
                           const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, float guidance_scale,
                           float null_ms1);
+
+/* ---- per-window sampler control: rescaled guidance, dynamic x0 thresholding (no reference counterpart) -------
+ * Two options that need a window as a whole: a statistics pass (csrc/k_winstat.hip) between the network forward and the update leaves two
+ * scalars per window in a (B, 4) device table [m_b, s_b, rho_b, -], which the update kernel's per-window form reads.  Per window b of
+ * per = RT * MZ elements, at one step:
+ *  1. g = u + w (c - u) per element as above; unguided g = c.
+ *  2. Rescale (Lin et al. 2024, section 3.4), guidance_rescale = phi in [0, 1], guided calls only: var_c, var_g the variances of the
+ *     window's c and of its fp32 g, from fp64 sums over the fp32 values shifted by the window's first element (dq_recon_metrics' form: a
+ *     constant window has variance exactly 0); m_b = (float)(phi * sqrt(var_c / var_g) + (1 - phi)), formed in fp64 and rounded once,
+ *     m_b = 1 when var_g <= 0; g <- m_b * g, one fp32 multiply.  Defined on the network output whatever the objective; in every update kind.
+ *  3. x0 (and eps) from (x, g) by the objective, as always.
+ *  4. Threshold (Saharia et al. 2022), threshold_quantile = q, a float32 in (0, 1]; solver kinds only.  Floor f = clip_x0 if given, else
+ *     1; cap = threshold_max >= f (+inf: none).  a_0 <= .. <= a_{n-1} the window's |x0|; h = (double)q (n - 1), j = floor(h); Q = a_j if
+ *     j == n - 1, else a_j + (a_{j+1} - a_j) (h - j) in fp64, every operation rounded on its own, Q rounded to fp32 once; the two order
+ *     statistics are elements of the window, bit for bit (an exact radix select).  s_b = min(max(Q, f), cap), rho_b = f / s_b;
+ *     x0 <- clamp(x0, -s_b, s_b) * rho_b; eps is re-derived, (x_t - sa x0) / sb, wherever x0 was clamped or rho_b != 1.  The thresholded
+ *     x0 enters the update and the 2M history.  Inputs are assumed finite.
+ * Where no window's Q exceeds f the step is the clip_x0 = f step bit for bit.  m_b and s_b depend on the window's elements and on per
+ * only (the reductions are cut by per, never by B, and folded in a fixed order; no floating-point atomics): a window alone gives the bits
+ * it gives in any batch.
+ *
+ * scratch of every entry below: dq_sample_stat_scratch_bytes(B, per_window) = 80 B + 4128 B ceil(per_window / 8192) bytes (-1 for
+ * B < 1 or per_window < 1), 16-byte aligned; 1 <= B <= 65535, 1 <= per_window < 2^31. */
+int64_t dq_sample_stat_scratch_bytes(int B, int64_t per_window);
+/* Step 2 alone: m_out[b] (B floats) from net_c, net_u (B, per_window) at scale w.  Refused: a NULL, w negative, NaN or infinite, phi outside
+ * [0, 1] or NaN, the sizes above, a scratch too small or misaligned. */
+int dq_window_rescale(const float* net_c, const float* net_u, float w, double phi, int B, int64_t per_window, float* m_out, void* scratch,
+                      int64_t scratch_bytes, void* stream);
+/* Step 4's Q alone, of |x| itself: out[b] (B floats) from x (B, per_window).  Refused: a NULL, q outside (0, 1] or NaN, the sizes above,
+ * a scratch too small or misaligned. */
+int dq_window_abs_quantile(const float* x, int B, int64_t per_window, float q, float* out, void* scratch, int64_t scratch_bytes, void* stream);
+/* One update in its per-window form over a table the caller supplies: dq_guided_update's arguments (kinds, coef_dev layouts, aliasing) with
+ * table_dev (B, 4) = [m_b, s_b, rho_b, -] in place of clip_x0 (s_b > 0; +inf: no clamp).  net_u NULL: the unguided form, solver kinds only
+ * (m_b is not read).  pred_type: DQ_PRED_EPS, DQ_PRED_X0 or DQ_PRED_V.  Rows [1, f, 1, -] give dq_guided_update (dq_solver_step) at
+ * clip_x0 = f bit for bit, rows [1, +inf, 1, -] the unclamped one.  16-byte accesses when per_window % 4 == 0 and all tensors are 16-byte
+ * aligned.  Refusals as dq_guided_update's, plus a NULL table and an unguided kind that is no solver. */
+int dq_step_update_adaptive(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
+                            float* eps_out, const float* coef_dev, float w, const float* table_dev, const int64_t* window_ids_dev,
+                            const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window, void* stream);
+/* dq_ddim_sample_v with the two options: guidance_rescale = phi (0: off; without `guided` a no-op: g = c, m = 1), threshold_quantile = q
+ * (0: off) and threshold_max (ignored when q is 0).  With either on, every step runs the statistics launches between the forward and the
+ * update (rescale: 2; threshold: 5 -- four radix passes and the fold), inside the captured step too, and the update in its per-window form
+ * behind the forward, never in the head launch; thresholding selects the update clip_x0 selects (first-order solver rows under
+ * DQ_SAMPLER_DDIM).  With both off the call is dq_ddim_sample_v's, launch for launch.  The workspace and its size are dq_ddim_sample_v's;
+ * stat_scratch (dq_sample_stat_scratch_bytes(B, RT * MZ); unused and nullable with both off) holds the table, the partials and the
+ * histograms at fixed addresses; captured steps are cached by (phi, q, threshold_max, stat_scratch) as well.  Refusals: dq_ddim_sample_v's
+ * in its order, with threshold_quantile refused exactly where clip_x0 is (DQ_SAMPLER_REFERENCE, eta > 0); then phi outside [0, 1], q
+ * outside (0, 1], threshold_max below the floor (NaN fails each), the scratch. */
+int dq_ddim_sample_adaptive(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                            const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                            const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                            int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                            const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, int guided,
+                            float guidance_scale, float null_ms1, double guidance_rescale, float threshold_quantile, float threshold_max,
+                            void* stat_scratch, int64_t stat_scratch_bytes);
 
 /* ---- batch formation from an HBM-resident dataset (the step right before the hot path) ------------
  * Replaces, for B (window 1, window 2) pairs, DIAMSDataset.__getitem__'s min-max normalisation (utils/data_loader.py:70-79:
