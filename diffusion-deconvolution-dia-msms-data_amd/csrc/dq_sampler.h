@@ -1,30 +1,63 @@
-// What the sampling loops share (dq_sampler.hip): the refusals made before anything touches the device, the upload of a sampler's tables,
-// the staging of seed and window ids for a captured step, the update behind a network forward, and the loop itself -- the captured step
-// with its replay, and the eager steps.  The U-Net loop (dq_ddim_sample_solver) and the transformer loop (dq_tfm_sample, dq_tfm_sample.hip)
-// differ in the forward they put in front of the update, literally: each hands the two functions below its StepForward, and in what it stages in front
-// of the loop.  Internal: not installed.
+// What the two sampling calls share (dq_sampler.hip).  A call travels as one record, SampleCall, filled by its extern "C" entry; from it
+// come, once each, the refusals made before anything touches the device (sample_check), the sampler's tables with x_T (sample_begin) and
+// the captured-or-eager tail (sample_run).  The U-Net's call (unet_sample) and the transformer's (dq_tfm_sample) differ in their workspace
+// layout, in the forward they hand the loop as its StepForward, and in what they stage in front of it.  Internal: not installed.
 #pragma once
 #include "dq_common.h"
-#include "dq_unet.h"  // StepUpdate, StepGraph
+#include "dq_kernels.h"  // WinStatScratch
+#include "dq_unet.h"     // StepUpdate, StepGraph
 #include <functional>
 
 namespace dq {
+
+// One sampling call as its entry received it.  who: the entry's own name, the prefix of every refusal; allow_v: DQ_PRED_V is a known
+// objective of this entry (the pred_type of the older ones names the reference's two).  guided: the scale w of
+// g = u + w (c - u) and the null condition's raw MS1 value; adaptive (section 38): rescaled guidance at phi, thresholding at `quantile` (0: off)
+struct SampleCall {
+  const char* who = "";
+  bool allow_v = false;
+  const float* alpha_bars_host = nullptr; int T = 0;  // the caller's schedule and its length (DDIMDiffusionModel.num_timesteps)
+  const float* x_T = nullptr; const float* ms2_cond = nullptr; const float* ms1_cond = nullptr;
+  int normalize = 0, pred = 0;  // pred: DQ_PRED_*
+  const int32_t* ts = nullptr; int num_steps = 0;  // trunc(linspace(T-1, 0, num_steps)), formed by the caller exactly as model.py:313 does
+  float *out_x = nullptr, *out_noise = nullptr, *traj_x = nullptr, *traj_eps = nullptr;
+  int use_graph = 0;
+  void* workspace = nullptr; int64_t workspace_bytes = 0;
+  int B = 0, RT = 0;
+  hipStream_t stream = nullptr;
+  float eta = 0.f; const uint64_t* seed = nullptr; const int64_t* ids = nullptr;
+  int sampler = 0; float clip_x0 = 0.f;
+  bool guided = false; float w = 1.f, null_ms1 = 0.f;
+  bool adaptive = false; double phi = 0.0; float quantile = 0.f, cap = 0.f; void* stat_scratch = nullptr; int64_t stat_bytes = 0;
+  bool graph() const { return use_graph && !traj_x && !traj_eps; }  // one step captured and replayed; otherwise the eager steps
+};
+
+// The per-window statistics of a step (k_winstat.hip), run between the forward and the update: rescale (guided
+// calls): m_b of rescaled guidance at phi; q > 0: dynamic thresholding at that quantile with floor f and cap.  S: the call's scratch at a
+// fixed address, carved once per call by its entry (win_stat_carve); the update then runs in its per-window form over the table at its head.
+struct StepStats {
+  double phi = 0.0;
+  float q = 0.f, floor = 1.f, cap = 0.f;
+  bool rescale = false;
+  WinStatScratch S{};
+  bool on() const { return rescale || q > 0.f; }
+};
+
+// What a call's options select.  clip_x0: the clamp as the kernels take it (0: off); clip: x0 is clamped by clip_x0 or thresholded --
+// either way the Solver family runs and the derived eps is the trajectory's.  stats: the per-window step (S is the entry's to carve)
+struct SamplerChoice { StepUpdate kind = StepUpdate::DDIM; bool sto = false, clip = false; float clip_x0 = 0.f; int pred = 0; StepStats stats; };
+// Every refusal that does not need the network's shape, in one order, before anything touches the device: a null argument (net_args_ok:
+// the network's own pointers are there), eta, the sampler and what it combines with (thresholding is refused where clip_x0 is and selects
+// its update), the decreasing timesteps, the seed, the objective, the guidance scale, the per-window options' ranges and scratch pointer
+int sample_check(const SampleCall& c, bool net_args_ok, SamplerChoice* out);
+// Tables up, x_T in place: the coefficient rows formed on the host and copied to coef_dev (4 per step) and extra_dev (sigma, or the solver's
+// c1: 1 per step; nullable), the stream synchronised (a caller's pageable copy queued in front is done too), x_T copied to xa or drawn (draw 0)
+int sample_begin(const SampleCall& c, const SamplerChoice& sc, int64_t per, float* coef_dev, float* extra_dev, float* xa);
 
 // What every step's update of one sampling call shares: the tables (extra: sigma per row, or the solver's c1), the x0 history of the 2M
 // solver (updated in place), the clamp (0: off) and the shape.  guided: the forward ran at 2 B windows -- rows
 // [0, B) under the caller's condition, rows [B, 2B) under the null -- and the update combines the two outputs with the scale w inside its
 // kernel, over the B windows of the first half; x and the network output are then 2 * B * per floats each.
-// The per-window statistics of a step (k_winstat.hip), run by launch_step_update between the forward and the update:
-// rescale (guided calls): m_b of rescaled guidance at phi; q > 0: dynamic thresholding at that quantile with floor f and cap.  The scratch is
-// dq_sample_stat_scratch_bytes(B, per) bytes at a fixed address; the update then runs in its per-window form over the table at its head.
-struct StepStats {
-  double phi = 0.0;
-  float q = 0.f, floor = 1.f, cap = 0.f;
-  void* scratch = nullptr; int64_t scratch_bytes = 0;
-  bool rescale = false;
-  bool on() const { return rescale || q > 0.f; }
-};
-
 struct StepUpdateArgs {
   StepUpdate kind;
   const float* coef; const float* extra;
@@ -37,35 +70,7 @@ struct StepUpdateArgs {
   StepStats stats;
 };
 
-// The noise of the stochastic update: the windows' ids and the seed (device memory) and the draw index (the kernel adds the step counter)
-struct StepNoise { const int64_t* ids; const uint64_t* seed; int draw; };
-
-// The update of one step behind the network forward: x_out from x and the network output.  The row is `row` of the tables (the eager loop)
-// or, with step_ptr, the one the device-side step counter names (the captured step: row 0).  eps_out (nullable): where the step's eps goes
-// when it is not the network output itself; fused: the deterministic update went with the head launch (StepIO::fused_update), nothing is
-// left to do.  Guided (u.guided): net_out is the conditional output, net_u the unconditional one, x_mirror (nullable) receives x_out's values
-// as well (the unconditional half's x of the next forward), and eps_out (nullable) the guided eps; never fused (the head launch of window b
-// cannot see the output of window B + b).  Both are null otherwise.
-int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net_out, const float* net_u, float* x_out, float* x_mirror,
-                       float* eps_out, int row, const int* step_ptr, const StepNoise& z, bool fused, hipStream_t s);
-
-// What a call's (eta, sampler, clip_x0) select.  clip_x0: the clamp as the kernels take it (0: off)
-struct SamplerChoice { StepUpdate kind = StepUpdate::DDIM; bool sto = false, clip = false; float clip_x0 = 0.f; int pred = 0; };  // pred: DQ_PRED_*
-// (clip: x0 is clamped by clip_x0 or thresholded -- either way the Solver family runs and the derived eps is the trajectory's)
-// The refusals every sampling loop makes, in one order, before anything touches the device; `who` prefixes the messages.  args_ok: the
-// caller's required pointers are all there; allow_v: DQ_PRED_V is a known objective for this caller (dq_ddim_sample_v).  threshold: the call
-// asks for dynamic thresholding (dq_ddim_sample_adaptive), refused where clip_x0 is and selecting the update clip_x0 selects.
-int sampler_check(const char* who, bool args_ok, float eta, int sampler, float clip_x0, const int32_t* timesteps_host, int num_steps,
-                  bool have_seed, bool have_xT, int pred_type, bool allow_v, SamplerChoice* out, bool threshold = false);
-// Forms the call's coefficient rows on the host and copies them to coef_dev (4 per step) and extra_dev (1 per step; nullable: not needed);
-// returns after the copies are done (the host vectors are the function's own)
-int sampler_upload_tables(const char* who, const float* alpha_bars_host, int T, const int32_t* ts, int num_steps, int sampler, const SamplerChoice& c,
-                          float eta, float* coef_dev, float* extra_dev, hipStream_t s);
-// Seed and window ids (null: 0 .. B-1) copied into the workspace, so that a new seed or other windows replay the same captured step; returns
-// after the copies are done
-int sampler_stage_noise(uint64_t* seed_stage, int64_t* ids_stage, const uint64_t* seed_dev, const int64_t* window_ids_dev, int B, hipStream_t s);
-
-// One step's network forward on stream s, the one thing a loop brings of its own: the network output of x into net_out, at timestep and
+// One step's network forward on stream s, the one thing a call brings of its own: the network output of x into net_out, at timestep and
 // table row `row` (the eager loop) or, with step_ptr, at the ones the device-side step counter names (the captured step).  A forward that
 // takes the update into its own launch writes the next x to x_out and sets *fused; want_eps: net_out is read behind the step (a trajectory).
 using StepForward = std::function<int(const float* x, float* x_out, int row, const int* step_ptr, float* net_out, bool want_eps, bool* fused, hipStream_t s)>;
@@ -79,11 +84,11 @@ struct SampleLoop {
   int num_steps;
   const float* ms2_cond; float *out_x, *out_noise; int normalize;
 };
-// The captured step: unless `reusable` (the caller's g.exec && stored key == key) drops g's graph and captures forward, update (x in place,
-// the staged noise at draw 0: the kernel adds the step counter) and launch_inc_step(step) on g.cap_stream; then num_steps replays on s and
-// launch_sample_finish.  *captured: it captured anew and instantiated -- only then does the caller store its key, whatever is returned.
-int replay_captured_step(StepGraph& g, bool reusable, const SampleLoop& L, int* step, const StepNoise& staged, hipStream_t s, bool* captured);
-// The eager steps: x per step into its trajectory slot (copied back to xa), in place (the solvers) or ping-pong; eps into its trajectory slot
-// or the scratch; the caller's ids and seed, step i drawing at index 1 + i; then launch_sample_finish.
-int eager_steps(const SampleLoop& L, float* traj_x, float* traj_eps, const int64_t* window_ids_dev, const uint64_t* seed_dev, hipStream_t s);
+// What a captured step reads at fixed workspace addresses: the step counter, the staged seed and window ids (other ones replay the same step)
+struct StepStage { int* step; uint64_t* seed; int64_t* ids; };
+// The tail of a call, behind the network's own prologue.  c.graph(): the step counter zeroed, seed and ids staged (sto: the update draws;
+// null ids: 0 .. B-1), and unless `reusable` (the handle's g.exec && stored key == key) one step -- forward, update with x in place, the
+// counter's increment -- captured anew on g.cap_stream; then num_steps replays on the call's stream.  *captured: only then does the caller
+// store its key, whatever is returned.  Otherwise the eager steps, step i drawing at index 1 + i.  launch_sample_finish ends both.
+int sample_run(const SampleCall& c, const SampleLoop& L, bool sto, StepGraph& g, bool reusable, const StepStage& st, bool* captured);
 }  // namespace dq

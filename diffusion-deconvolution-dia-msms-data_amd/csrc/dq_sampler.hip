@@ -1,5 +1,6 @@
-// The sampling entry points of the C ABI (include/dq_hip.h): the stand-alone updates, and the sampling loop with its captured step -- the
-// network forward of dq_unet.hip (dq_net.h) with one of four updates in or behind its head launch, over the tables of dq_sampler_tables.cpp.
+// The U-Net's sampling entries of the C ABI (include/dq_hip.h) and what both networks' calls share (dq_sampler.h): the stand-alone updates,
+// each a StepUpdateLaunch filled by update_launch; the refusals, tables and tail of a sampling call, read from its SampleCall; and the loop
+// with its captured step -- a network forward with one of the four StepUpdate kinds in or behind its head launch, plain, guided or per window.
 #include "dq_net.h"
 #include "dq_options.h"
 #include "dq_sampler.h"
@@ -14,31 +15,52 @@
 
 using namespace dq;
 
-namespace dq {
+namespace {
 
+static_assert((int)StepUpdate::DDIM == DQ_UPDATE_DDIM && (int)StepUpdate::STOCHASTIC == DQ_UPDATE_STOCHASTIC &&
+              (int)StepUpdate::SOLVER_1 == DQ_UPDATE_SOLVER_1 && (int)StepUpdate::SOLVER_2M == DQ_UPDATE_SOLVER_2M, "DQ_UPDATE_* are StepUpdate's values");
+
+bool guidance_ok(float w) { return w >= 0.f && std::isfinite(w); }  // (false for NaN)
+
+// The noise of the stochastic update: the windows' ids and the seed (device memory) and the draw index (the kernel adds the step counter)
+struct StepNoise { const int64_t* ids = nullptr; const uint64_t* seed = nullptr; int draw = 0; };
+
+// One update launch, filled in this one place: the family of `kind` (DQ_UPDATE_* are its values), guided iff net_u is given (x_mirror is dropped
+// otherwise), the x0 history for the 2M kind alone, coef / extra the rows to read.  clip, w, step_ptr and win are left for the caller to set.
+StepUpdateLaunch update_launch(StepUpdate kind, int pred, const float* x_t, const float* net, const float* net_u, float* x_prev, float* x_mirror,
+                               float* hist, float* eps_out, const float* coef, const float* extra, const StepNoise& z, int B, int64_t per) {
+  StepUpdateLaunch a;
+  a.family = kind == StepUpdate::DDIM ? UpdateFamily::DDIM : kind == StepUpdate::STOCHASTIC ? UpdateFamily::STOCHASTIC : UpdateFamily::SOLVER;
+  a.guided = net_u != nullptr; a.pred = pred;
+  a.x_t = x_t; a.net = net; a.net_u = net_u;
+  a.x_prev = x_prev; a.x_mirror = net_u ? x_mirror : nullptr; a.eps_out = eps_out;
+  a.hist = kind == StepUpdate::SOLVER_2M ? hist : nullptr;
+  a.coef = coef; a.extra = extra;
+  a.ids = z.ids; a.seed = z.seed; a.draw = z.draw;
+  a.B = B; a.per = per;
+  return a;
+}
+
+// The update of one step behind the network forward: x_out from x and the network output.  The row is `row` of the tables (the eager loop)
+// or, with step_ptr, the one the device-side step counter names (the captured step: row 0).  eps_out (nullable): where the step's eps goes
+// when it is not the network output itself; fused: the deterministic update went with the head launch (StepIO::fused_update), nothing is
+// left to do.  Guided (u.guided): net_out is the conditional output, net_u the unconditional one, x_mirror (nullable) receives x_out's values
+// as well (the unconditional half's x of the next forward), and eps_out (nullable) the guided eps; never fused (the head launch of window b
+// cannot see the output of window B + b).  Both are null otherwise.  Nothing is refused per step: the call's checks are made before the loop.
 int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net_out, const float* net_u, float* x_out, float* x_mirror,
                        float* eps_out, int row, const int* step_ptr, const StepNoise& z, bool fused, hipStream_t s) {
   if (fused && u.kind == StepUpdate::DDIM && !u.guided) return 0;  // (the head launch has done it; a guided update never rides there)
-  StepUpdateLaunch a;
-  a.family = u.kind == StepUpdate::DDIM ? UpdateFamily::DDIM : u.kind == StepUpdate::STOCHASTIC ? UpdateFamily::STOCHASTIC : UpdateFamily::SOLVER;
-  a.guided = u.guided; a.pred = u.pred;
-  a.x_t = x; a.net = net_out; a.net_u = u.guided ? net_u : nullptr;
-  a.x_prev = x_out; a.x_mirror = u.guided ? x_mirror : nullptr; a.eps_out = eps_out;
-  a.hist = u.kind == StepUpdate::SOLVER_2M ? u.hist : nullptr;  // (first order: no history)
-  a.coef = u.coef + 4 * row; a.extra = u.extra + row;
-  a.ids = z.ids; a.seed = z.seed; a.draw = z.draw;
-  a.clip = u.clip; a.w = u.w;
-  a.B = u.B; a.per = u.per; a.step_ptr = step_ptr;
+  StepUpdateLaunch a = update_launch(u.kind, u.pred, x, net_out, net_u, x_out, x_mirror, u.hist, eps_out, u.coef + 4 * row, u.extra + row, z, u.B, u.per);
+  a.clip = u.clip; a.w = u.w; a.step_ptr = step_ptr;
   if (u.stats.on()) {
     // the statistics step: m_b from the two network outputs, then s_b and rho_b from the x0 the update will form
     const StepStats& st = u.stats;
-    WinStatScratch S;
-    DQ_TRY(win_stat_carve("sample statistics", st.scratch, st.scratch_bytes, u.B, u.per, &S));
+    const WinStatScratch& S = st.S;
     const bool thr = st.q > 0.f;
     if (st.rescale) DQ_TRY(launch_win_rescale(net_out, net_u, u.w, st.phi, u.B, u.per, S, S.tab, u.clip > 0.f ? u.clip : INFINITY, !thr, nullptr, s));
     if (thr) {
       WinQuantile q;
-      q.x = x; q.c = net_out; q.u = a.net_u; q.coef = a.coef; q.step_ptr = step_ptr; q.m_tab = st.rescale ? S.tab : nullptr;
+      q.x = x; q.c = net_out; q.u = net_u; q.coef = a.coef; q.step_ptr = step_ptr; q.m_tab = st.rescale ? S.tab : nullptr;
       q.w = u.w; q.pred = u.pred; q.guided = u.guided;
       q.q = st.q; q.floor = st.floor; q.cap = st.cap; q.tab = S.tab; q.init_m = !st.rescale;
       DQ_TRY(launch_win_quantile(q, u.B, u.per, S, s));
@@ -48,65 +70,26 @@ int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net
   return launch_update(a, s);  // model.py:273-289
 }
 
-int sampler_check(const char* who, bool args_ok, float eta, int sampler, float clip_x0, const int32_t* timesteps_host, int num_steps,
-                  bool have_seed, bool have_xT, int pred_type, bool allow_v, SamplerChoice* out, bool threshold) {
-  const std::string w(who);
-  DQ_REQUIRE(args_ok, w + ": null argument");
-  DQ_REQUIRE(eta >= 0.f && eta <= 1.f, w + ": eta must satisfy 0 <= eta <= 1");  // (false for NaN)
-  const bool sto = eta > 0.f;  // the update draws noise
-  // step-consistent samplers (DESIGN.md section 26): refused here, before anything touches the device
-  DQ_REQUIRE(sampler == DQ_SAMPLER_REFERENCE || sampler == DQ_SAMPLER_DDIM || sampler == DQ_SAMPLER_DPMPP_2M, w + ": unknown sampler");
-  const bool clip = clip_x0 > 0.f;  // (<= 0 and NaN: off)
-  DQ_REQUIRE(sampler != DQ_SAMPLER_DPMPP_2M || !sto, w + ": DPM-Solver++(2M) is deterministic: eta must be 0");
-  DQ_REQUIRE(!clip || sampler != DQ_SAMPLER_REFERENCE, w + ": clip_x0 needs the ddim or dpmpp_2m sampler");
-  DQ_REQUIRE(!clip || !sto, w + ": clip_x0 needs eta == 0");
-  DQ_REQUIRE(!threshold || sampler != DQ_SAMPLER_REFERENCE, w + ": threshold_quantile needs the ddim or dpmpp_2m sampler");
-  DQ_REQUIRE(!threshold || !sto, w + ": threshold_quantile needs eta == 0");
-  if (sampler != DQ_SAMPLER_REFERENCE && num_steps <= 1024)  // (a step count out of range is the caller's refusal: its list is not read)
-    for (int i = 1; i < num_steps; ++i)
-      DQ_REQUIRE(timesteps_host[i] < timesteps_host[i - 1], w + ": the timesteps of this sampler must be strictly decreasing");
-  // the update: the Solver family (k_update.hip) behind the forward (2M, or a clamped x0 at first order); else the reference's kernels over this sampler's table
-  out->kind = sampler == DQ_SAMPLER_DPMPP_2M ? StepUpdate::SOLVER_2M : (clip || threshold) ? StepUpdate::SOLVER_1 : sto ? StepUpdate::STOCHASTIC : StepUpdate::DDIM;
-  out->sto = sto; out->clip = clip || threshold; out->clip_x0 = clip ? clip_x0 : 0.f;
-  DQ_REQUIRE(have_seed || (have_xT && !sto), w + ": eta > 0 and a null x_T need the seed (device memory)");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0 || (allow_v && pred_type == DQ_PRED_V), w + ": Unknown pred_type");
-  out->pred = pred_type;
-  return 0;
-}
-
-int sampler_upload_tables(const char* who, const float* alpha_bars_host, int T, const int32_t* ts, int num_steps, int sampler, const SamplerChoice& c,
-                          float eta, float* coef_dev, float* extra_dev, hipStream_t s) {
-  // coefficient table, fp32 like the reference, and sigma (eta > 0) or c1 (the solver) per step
-  std::vector<float> coef(4 * (size_t)num_steps), extra((size_t)num_steps);
-  if (sampler == DQ_SAMPLER_REFERENCE) DQ_TRY(dq_ddim_coef_table(alpha_bars_host, T, ts, num_steps, eta, coef.data(), extra.data()));
-  else DQ_TRY(sampler_rows(alpha_bars_host, T, ts, num_steps, c.kind == StepUpdate::SOLVER_1 ? SOLVER_ORDER1 : sampler, eta, coef.data(), extra.data(), who));
-  DQ_HIP_OK(hipMemcpyAsync(coef_dev, coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice, s));
-  if (extra_dev) DQ_HIP_OK(hipMemcpyAsync(extra_dev, extra.data(), sizeof(float) * extra.size(), hipMemcpyHostToDevice, s));
-  // the host vector must outlive the copy: pageable H2D copies are staged synchronously by the runtime, but make it explicit
-  DQ_HIP_OK(hipStreamSynchronize(s));
-  return 0;
-}
-
-int sampler_stage_noise(uint64_t* seed_stage, int64_t* ids_stage, const uint64_t* seed_dev, const int64_t* window_ids_dev, int B, hipStream_t s) {
-  DQ_HIP_OK(hipMemcpyAsync(seed_stage, seed_dev, sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+// Seed and window ids (null: 0 .. B-1) copied into the workspace; returns after the copies are done
+int sampler_stage_noise(const StepStage& st, const uint64_t* seed_dev, const int64_t* window_ids_dev, int B, hipStream_t s) {
+  DQ_HIP_OK(hipMemcpyAsync(st.seed, seed_dev, sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
   if (window_ids_dev) {
-    DQ_HIP_OK(hipMemcpyAsync(ids_stage, window_ids_dev, sizeof(int64_t) * B, hipMemcpyDeviceToDevice, s));
+    DQ_HIP_OK(hipMemcpyAsync(st.ids, window_ids_dev, sizeof(int64_t) * B, hipMemcpyDeviceToDevice, s));
     return 0;
   }
   std::vector<int64_t> iota((size_t)B);
   for (int b = 0; b < B; ++b) iota[b] = b;
-  DQ_HIP_OK(hipMemcpyAsync(ids_stage, iota.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, s));
+  DQ_HIP_OK(hipMemcpyAsync(st.ids, iota.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, s));
   DQ_HIP_OK(hipStreamSynchronize(s));  // (the vector is this function's own)
   return 0;
 }
 
-// (the one loop of both networks, dq_tfm_sample.hip's too: dq_sampler.h)
-static int finish(const SampleLoop& L, const float* x, hipStream_t s) {
-  return launch_sample_finish(x, L.ms2_cond, L.out_x, L.out_noise, L.upd.B * L.upd.per, L.normalize, s);  // model.py:319-322
+// (the one loop of both networks, dq_tfm_sample.hip's too: sample_run)
+int finish(const SampleLoop& L, const float* x, hipStream_t s) {  // model.py:319-322
+  return launch_sample_finish(x, L.ms2_cond, L.out_x, L.out_noise, L.upd.B * L.upd.per, L.normalize, s);
 }
 
 int replay_captured_step(StepGraph& g, bool reusable, const SampleLoop& L, int* step, const StepNoise& staged, hipStream_t s, bool* captured) {
-  *captured = false;
   if (!reusable) {
     g.drop();
     // the caller's stream may be the legacy default stream, which cannot be captured: capture on a stream of our own (created on first use;
@@ -158,163 +141,205 @@ int eager_steps(const SampleLoop& L, float* traj_x, float* traj_eps, const int64
   return finish(L, xa, s);
 }
 
+}  // namespace
+
+namespace dq {
+
+int sample_check(const SampleCall& c, bool net_args_ok, SamplerChoice* out) {
+  const std::string w(c.who);
+  const float eta = c.eta;
+  const int sampler = c.sampler;
+  const bool threshold = c.adaptive && c.quantile != 0.f;  // (NaN: on, then refused below)
+  DQ_REQUIRE(net_args_ok && c.alpha_bars_host && c.ms2_cond && c.ms1_cond && c.ts && c.out_x && c.out_noise && c.workspace, w + ": null argument");
+  DQ_REQUIRE(eta >= 0.f && eta <= 1.f, w + ": eta must satisfy 0 <= eta <= 1");  // (false for NaN)
+  const bool sto = eta > 0.f;  // the update draws noise
+  // step-consistent samplers (DESIGN.md section 26): refused here, before anything touches the device
+  DQ_REQUIRE(sampler == DQ_SAMPLER_REFERENCE || sampler == DQ_SAMPLER_DDIM || sampler == DQ_SAMPLER_DPMPP_2M, w + ": unknown sampler");
+  const bool clip = c.clip_x0 > 0.f;  // (<= 0 and NaN: off)
+  DQ_REQUIRE(sampler != DQ_SAMPLER_DPMPP_2M || !sto, w + ": DPM-Solver++(2M) is deterministic: eta must be 0");
+  DQ_REQUIRE(!clip || sampler != DQ_SAMPLER_REFERENCE, w + ": clip_x0 needs the ddim or dpmpp_2m sampler");
+  DQ_REQUIRE(!clip || !sto, w + ": clip_x0 needs eta == 0");
+  DQ_REQUIRE(!threshold || sampler != DQ_SAMPLER_REFERENCE, w + ": threshold_quantile needs the ddim or dpmpp_2m sampler");
+  DQ_REQUIRE(!threshold || !sto, w + ": threshold_quantile needs eta == 0");
+  if (sampler != DQ_SAMPLER_REFERENCE && c.num_steps <= 1024)  // (a step count out of range is the entry's refusal: its list is not read)
+    for (int i = 1; i < c.num_steps; ++i)
+      DQ_REQUIRE(c.ts[i] < c.ts[i - 1], w + ": the timesteps of this sampler must be strictly decreasing");
+  // the update: the Solver family (k_update.hip) behind the forward (2M, or a clamped x0 at first order); else the reference's kernels over this sampler's table
+  out->kind = sampler == DQ_SAMPLER_DPMPP_2M ? StepUpdate::SOLVER_2M : (clip || threshold) ? StepUpdate::SOLVER_1 : sto ? StepUpdate::STOCHASTIC : StepUpdate::DDIM;
+  out->sto = sto; out->clip = clip || threshold; out->clip_x0 = clip ? c.clip_x0 : 0.f;
+  DQ_REQUIRE(c.seed || (c.x_T && !sto), w + ": eta > 0 and a null x_T need the seed (device memory)");
+  DQ_REQUIRE(c.pred == DQ_PRED_EPS || c.pred == DQ_PRED_X0 || (c.allow_v && c.pred == DQ_PRED_V), w + ": Unknown pred_type");
+  out->pred = c.pred;
+  DQ_REQUIRE(!c.guided || guidance_ok(c.w), w + ": the guidance scale must be finite and >= 0");
+  StepStats& st = out->stats = StepStats{};
+  if (!c.adaptive) return 0;
+  DQ_REQUIRE(c.phi >= 0.0 && c.phi <= 1.0, w + ": guidance_rescale must satisfy 0 <= guidance_rescale <= 1");  // (false for NaN)
+  DQ_REQUIRE(!threshold || (c.quantile > 0.f && c.quantile <= 1.f), w + ": threshold_quantile must satisfy 0 < threshold_quantile <= 1 (0: off)");
+  st.floor = clip ? c.clip_x0 : 1.f;
+  DQ_REQUIRE(!threshold || c.cap >= st.floor, w + ": threshold_max must be >= the floor (clip_x0, or 1 without it)");  // (false for NaN)
+  st.phi = c.phi; st.rescale = c.guided && c.phi > 0.0;  // (unguided: g = c, m = 1 -- nothing to do)
+  st.q = threshold ? c.quantile : 0.f; st.cap = c.cap;
+  DQ_REQUIRE(!st.on() || c.stat_scratch, w + ": null argument (stat_scratch)");
+  return 0;
+}
+
+int sample_begin(const SampleCall& c, const SamplerChoice& sc, int64_t per, float* coef_dev, float* extra_dev, float* xa) {
+  hipStream_t s = c.stream;
+  // coefficient table, fp32 like the reference, and sigma (eta > 0) or c1 (the solver) per step
+  std::vector<float> coef(4 * (size_t)c.num_steps), extra((size_t)c.num_steps);
+  if (c.sampler == DQ_SAMPLER_REFERENCE) DQ_TRY(dq_ddim_coef_table(c.alpha_bars_host, c.T, c.ts, c.num_steps, c.eta, coef.data(), extra.data()));
+  else DQ_TRY(sampler_rows(c.alpha_bars_host, c.T, c.ts, c.num_steps, sc.kind == StepUpdate::SOLVER_1 ? SOLVER_ORDER1 : c.sampler, c.eta, coef.data(),
+                           extra.data(), c.who));
+  DQ_HIP_OK(hipMemcpyAsync(coef_dev, coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice, s));
+  if (extra_dev) DQ_HIP_OK(hipMemcpyAsync(extra_dev, extra.data(), sizeof(float) * extra.size(), hipMemcpyHostToDevice, s));
+  // the host vector must outlive the copy: pageable H2D copies are staged synchronously by the runtime, but make it explicit
+  DQ_HIP_OK(hipStreamSynchronize(s));
+  if (c.x_T) DQ_HIP_OK(hipMemcpyAsync(xa, c.x_T, sizeof(float) * c.B * per, hipMemcpyDeviceToDevice, s));
+  else DQ_TRY(launch_randn(xa, c.ids, c.seed, 0, c.B, per, s));  // draw index 0 is x_T's
+  return 0;
+}
+
+int sample_run(const SampleCall& c, const SampleLoop& L, bool sto, StepGraph& g, bool reusable, const StepStage& st, bool* captured) {
+  *captured = false;
+  if (!c.graph()) return eager_steps(L, c.traj_x, c.traj_eps, c.ids, c.seed, c.stream);
+  // ---- hipGraph path: one step captured once, replayed per step; the step index lives on the device (*step, bumped by k_inc_step)
+  DQ_HIP_OK(hipMemsetAsync(st.step, 0, sizeof(int), c.stream));
+  if (sto) DQ_TRY(sampler_stage_noise(st, c.seed, c.ids, c.B, c.stream));
+  return replay_captured_step(g, reusable, L, st.step, StepNoise{st.ids, st.seed, 0}, c.stream, captured);
+}
+
 }  // namespace dq
 
 namespace {
 
-// Classifier-free guidance on MS1: the scale w of g = u + w (c - u) and the raw MS1 value of the null condition
-struct Guidance { float w, null_ms1; };
-bool guidance_ok(float w) { return w >= 0.f && std::isfinite(w); }  // (false for NaN)
-// Per-window sampler control: rescaled guidance at phi, dynamic thresholding at quantile q (0: off) capped at cap
-struct Adaptive { double phi; float q, cap; void* scratch; int64_t scratch_bytes; };
-
-static_assert((int)StepUpdate::DDIM == DQ_UPDATE_DDIM && (int)StepUpdate::STOCHASTIC == DQ_UPDATE_STOCHASTIC &&
-              (int)StepUpdate::SOLVER_1 == DQ_UPDATE_SOLVER_1 && (int)StepUpdate::SOLVER_2M == DQ_UPDATE_SOLVER_2M, "DQ_UPDATE_* are StepUpdate's values");
-
-// The U-Net's sampling call: dq_ddim_sample_solver (g null) and dq_ddim_sample_guided.  Guided, the arena and the forward run at NB = 2 B
-// windows: rows [0, B) carry the caller's MS1, rows [B, 2B) g->null_ms1 in every element (a raw value: it goes through the same cm, ca
-// normalisation); both halves see the same mixture and the same x, which the update keeps equal by writing x_prev to both (x_mirror).  The
-// conditions are staged in the workspace for every path, the update / hist / trajectories / outputs cover B windows, and the update never
-// rides in the head launch.
-int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps, const float* x_T,
-                const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type, const int32_t* timesteps_host, int num_steps,
-                float* out_x, float* out_noise, float* traj_x, float* traj_eps, int use_graph, void* workspace, int64_t workspace_bytes, int B,
-                int RT, void* stream, float eta, const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0,
-                const Guidance* g, bool allow_v = false, const Adaptive* ad = nullptr) {
-  // allow_v: the call came through dq_ddim_sample_v -- the pred_type argument of the other entries names the reference's two objectives
-  const char* who = ad ? "dq_ddim_sample_adaptive" : allow_v ? "dq_ddim_sample_v" : g ? "dq_ddim_sample_guided" : "dq_ddim_sample";
-  const std::string wh(who);
+// The U-Net's sampling call, under every dq_ddim_sample* entry.  Guided, the arena and the forward run at NB = 2 B windows: rows [0, B)
+// carry the caller's MS1, rows [B, 2B) q.null_ms1 in every element (a raw value: it goes through the same cm, ca normalisation); both
+// halves see the same mixture and the same x, which the update keeps equal by writing x_prev to both (x_mirror).  The update / hist /
+// trajectories / outputs cover B windows, and a guided update never rides in the head launch.
+int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, const SampleCall& q) {
+  const std::string wh(q.who);
   SamplerChoice sc;
-  const bool thr = ad && ad->q != 0.f;  // (NaN: on, then refused below)
-  DQ_TRY(sampler_check(who, plan && params && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host && out_x && out_noise && workspace,
-                       eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, allow_v, &sc, thr));
-  DQ_REQUIRE(!g || guidance_ok(g->w), wh + ": the guidance scale must be finite and >= 0");
-  StepStats stats;
-  if (ad) {
-    DQ_REQUIRE(ad->phi >= 0.0 && ad->phi <= 1.0, wh + ": guidance_rescale must satisfy 0 <= guidance_rescale <= 1");  // (false for NaN)
-    DQ_REQUIRE(!thr || (ad->q > 0.f && ad->q <= 1.f), wh + ": threshold_quantile must satisfy 0 < threshold_quantile <= 1 (0: off)");
-    stats.floor = sc.clip_x0 > 0.f ? sc.clip_x0 : 1.f;
-    DQ_REQUIRE(!thr || ad->cap >= stats.floor, wh + ": threshold_max must be >= the floor (clip_x0, or 1 without it)");  // (false for NaN)
-    stats.phi = ad->phi; stats.rescale = g && ad->phi > 0.0;  // (unguided: g = c, m = 1 -- nothing to do)
-    stats.q = thr ? ad->q : 0.f; stats.cap = ad->cap;
-    stats.scratch = ad->scratch; stats.scratch_bytes = ad->scratch_bytes;
-    if (stats.on()) {
-      WinStatScratch S;
-      DQ_REQUIRE(ad->scratch, wh + ": null argument (stat_scratch)");
-      DQ_REQUIRE(B > 0 && RT > 0, wh + ": need B, RT > 0 and 1 <= num_steps <= 1024");
-      DQ_TRY(win_stat_carve(wh, ad->scratch, ad->scratch_bytes, B, (int64_t)RT * plan->plan.mz, &S));
-    }
+  DQ_TRY(sample_check(q, plan && params, &sc));
+  const int B = q.B, RT = q.RT, num_steps = q.num_steps;
+  const bool g = q.guided;
+  if (sc.stats.on()) {  // the statistics scratch, carved here for every step of the call
+    DQ_REQUIRE(B > 0 && RT > 0, wh + ": need B, RT > 0 and 1 <= num_steps <= 1024");
+    DQ_TRY(win_stat_carve(wh, q.stat_scratch, q.stat_bytes, B, (int64_t)RT * plan->plan.mz, &sc.stats.S));
   }
-  const StepUpdate kind = sc.kind;
-  clip_x0 = sc.clip_x0;
-  // the head launch takes the update when it can (StepIO::x_t); the others, and every guided one, run behind the forward
-  const bool in_head = kind == StepUpdate::DDIM && !g;
   DQ_REQUIRE(B > 0 && RT > 0 && num_steps >= 1 && num_steps <= 1024, wh + ": need B, RT > 0 and 1 <= num_steps <= 1024");
   DQ_REQUIRE(!g || B <= INT32_MAX / 2, wh + ": batch too large");
   const int NB = g ? 2 * B : B;  // the windows of the arena and of the forward
   DQ_TRY(ensure_arena(plan, NB, RT));
   const Arena& a = plan->arena;
-  DQ_REQUIRE(workspace_bytes >= (int64_t)sizeof(float) * a.floats, wh + ": workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W = (float*)workspace;
+  DQ_REQUIRE(q.workspace_bytes >= (int64_t)sizeof(float) * a.floats, wh + ": workspace too small");
+  DQ_REQUIRE(q.T >= 1, wh + ": num_timesteps must be >= 1");
+  hipStream_t s = q.stream;
+  float* W = (float*)q.workspace;
   Ctx c{plan->plan, a, params, W, nullptr, nullptr, NB, RT, s};
   c.save = false;
-  const int T = num_timesteps;  // length of alpha_bars_host (DDIMDiffusionModel.num_timesteps: the schedule is the caller's)
-  DQ_REQUIRE(T >= 1, wh + ": num_timesteps must be >= 1");
   const int64_t per = (int64_t)RT * plan->plan.mz, n = B * per;
   const int64_t n1 = (int64_t)B * RT * plan->plan.ms1_channels;  // the caller's MS1
-  const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
-  const int32_t* ts = timesteps_host;  // trunc(linspace(T-1, 0, num_steps)) formed by the caller exactly as model.py:313 does
-  DQ_TRY(sampler_upload_tables(who, alpha_bars_host, T, ts, num_steps, sampler, sc, eta, c.w(a.coef), in_head ? nullptr : c.w(a.sigma), s));
+  const float cm = q.normalize ? 2.f : 1.f, ca = q.normalize ? -1.f : 0.f;
+  // the head launch takes the update when it can (StepIO::x_t); the others, and every guided one, run behind the forward
+  const bool in_head = sc.kind == StepUpdate::DDIM && !g;
   float* xa = c.w(a.xa);
-  if (x_T) DQ_HIP_OK(hipMemcpyAsync(xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-  else DQ_TRY(launch_randn(xa, window_ids_dev, seed_dev, 0, B, per, s));  // draw index 0 is x_T's
+  DQ_TRY(sample_begin(q, sc, per, c.w(a.coef), in_head ? nullptr : c.w(a.sigma), xa));
   if (g) DQ_HIP_OK(hipMemcpyAsync(xa + n, xa, sizeof(float) * n, hipMemcpyDeviceToDevice, s));  // the unconditional half starts from the same x_T
   // the conditions staged at fixed addresses: for the captured step, and for every guided call (the mixture twice; the caller's MS1, then
-  // the null's raw value in every element of the second half)
-  const auto stage_conditions = [&]() -> int {
-    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c2_stage), ms2_cond, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c1_stage), ms1_cond, sizeof(float) * n1, hipMemcpyDeviceToDevice, s));
-    if (g) {
-      uint32_t bits;
-      std::memcpy(&bits, &g->null_ms1, sizeof bits);
-      DQ_HIP_OK(hipMemcpyAsync(c.w(a.c2_stage) + n, ms2_cond, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-      DQ_HIP_OK(hipMemsetD32Async((hipDeviceptr_t)(c.w(a.c1_stage) + n1), (int)bits, (size_t)n1, s));
-    }
-    return 0;
-  };
-  Ctx::StepIO io; io.pred = sc.pred;
+  // the null's raw value in every element of the second half); an unguided eager call reads the caller's
+  const bool staged = q.graph() || g;
+  const float* c2 = staged ? c.w(a.c2_stage) : q.ms2_cond;
+  const float* c1 = staged ? c.w(a.c1_stage) : q.ms1_cond;
   // The step index of a captured step lives on the device: k_time_fwd reads ts_tab[*step], the update its coefficient row, k_inc_step bumps it.
   int* ts_tab = reinterpret_cast<int*>(c.w(a.ts_tab));
-  // the forward of this network: captured over the staged conditions (all pointers inside the arena / parameter buffers), eagerly over the
-  // caller's, or guided over the staged ones again
-  const float* c2_eager = g ? c.w(a.c2_stage) : ms2_cond;
-  const float* c1_eager = g ? c.w(a.c1_stage) : ms1_cond;
+  if (q.graph()) DQ_HIP_OK(hipMemcpyAsync(ts_tab, q.ts, sizeof(int32_t) * num_steps, hipMemcpyHostToDevice, s));
+  if (staged) {
+    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c2_stage), q.ms2_cond, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c1_stage), q.ms1_cond, sizeof(float) * n1, hipMemcpyDeviceToDevice, s));
+  }
+  if (g) {
+    uint32_t bits;
+    std::memcpy(&bits, &q.null_ms1, sizeof bits);
+    DQ_HIP_OK(hipMemcpyAsync(c.w(a.c2_stage) + n, q.ms2_cond, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    DQ_HIP_OK(hipMemsetD32Async((hipDeviceptr_t)(c.w(a.c1_stage) + n1), (int)bits, (size_t)n1, s));
+  }
+  if (q.graph()) DQ_HIP_OK(hipStreamSynchronize(s));  // ts is caller memory; also keeps the capture free of pending copies of the conditions
+  Ctx::StepIO io; io.pred = sc.pred;
+  DQ_TRY(unet_sample_prologue(c, c1, cm, ca, rope_freqs, &io.prologue));
+  // the forward of this network: captured at the step the device-side counter names (all pointers inside the arena / parameter buffers),
+  // eagerly at the caller's timestep
   const StepForward forward = [&](const float* x, float* x_out, int row, const int* step_ptr, float* net_out, bool want_eps, bool* fused, hipStream_t fs) {
     Ctx fc{plan->plan, a, params, W, nullptr, nullptr, NB, RT, fs};
     fc.save = false; fc.step_io = &io;
     io.x_t = in_head ? x : nullptr; io.x_out = x_out; io.coef = c.w(a.coef) + 4 * row; io.step_ptr = step_ptr; io.want_eps = want_eps; io.fused_update = false;
-    const int rc = step_ptr ? unet_forward(fc, rope_freqs, x, nullptr, 0, c.w(a.c2_stage), c.w(a.c1_stage), cm, ca, plan->dev, net_out, ts_tab, step_ptr)
-                            : unet_forward(fc, rope_freqs, x, nullptr, ts[row], c2_eager, c1_eager, cm, ca, plan->dev, net_out);
+    const int rc = step_ptr ? unet_forward(fc, rope_freqs, x, nullptr, 0, c2, c1, cm, ca, plan->dev, net_out, ts_tab, step_ptr)
+                            : unet_forward(fc, rope_freqs, x, nullptr, q.ts[row], c2, c1, cm, ca, plan->dev, net_out);
     *fused = io.fused_update;
     return rc;
   };
-  const SampleLoop loop{forward, StepUpdateArgs{kind, c.w(a.coef), c.w(a.sigma), c.w(a.xb), clip_x0, sc.pred, B, per, g != nullptr, g ? g->w : 1.f, stats},
-                        xa, c.w(a.eps), sc.clip, num_steps, ms2_cond, out_x, out_noise, auto_normalize};
-  if (use_graph && !traj_x && !traj_eps) {
-    // ---- hipGraph path: one step captured once, replayed per step
-    int* step = reinterpret_cast<int*>(c.w(a.step));
-    DQ_HIP_OK(hipMemcpyAsync(ts_tab, ts, sizeof(int32_t) * num_steps, hipMemcpyHostToDevice, s));
-    DQ_HIP_OK(hipMemsetAsync(step, 0, sizeof(int), s));
-    DQ_TRY(stage_conditions());
-    uint64_t* seed_st = reinterpret_cast<uint64_t*>(c.w(a.seed_stage));
-    int64_t* ids_st = reinterpret_cast<int64_t*>(c.w(a.ids_stage));
-    if (sc.sto) DQ_TRY(sampler_stage_noise(seed_st, ids_st, seed_dev, window_ids_dev, B, s));  // staged like the conditions (null ids: 0 .. B-1)
-    DQ_HIP_OK(hipStreamSynchronize(s));  // ts is caller memory; also keeps the capture below free of pending copies
-    DQ_TRY(unet_sample_prologue(c, c.w(a.c1_stage), cm, ca, rope_freqs, &io.prologue));
-    StepKey key;
-    key.params = params; key.rope = rope_freqs; key.ws = workspace; key.B = B; key.RT = RT; key.normalize = auto_normalize; key.pred = pred_type;
-    key.update = kind; key.clip = clip_x0; key.guidance = g ? g->w : -1.f; key.opt_epoch = options_epoch();
-    if (stats.on()) { key.rescale = stats.rescale ? stats.phi : 0.0; key.quantile = stats.q; key.cap = stats.cap; key.stat_scratch = stats.scratch; }
-    bool captured;  // (the key only after instantiation succeeded)
-    const int rc = replay_captured_step(plan->step, plan->step.exec && plan->step_key == key, loop, step, StepNoise{ids_st, seed_st, 0}, s, &captured);
-    if (captured) plan->step_key = key;
-    return rc;
-  }
-  if (g) DQ_TRY(stage_conditions());
-  DQ_TRY(unet_sample_prologue(c, c1_eager, cm, ca, rope_freqs, &io.prologue));
-  return eager_steps(loop, traj_x, traj_eps, window_ids_dev, seed_dev, s);
+  const SampleLoop loop{forward, StepUpdateArgs{sc.kind, c.w(a.coef), c.w(a.sigma), c.w(a.xb), sc.clip_x0, sc.pred, B, per, g, g ? q.w : 1.f, sc.stats},
+                        xa, c.w(a.eps), sc.clip, num_steps, q.ms2_cond, q.out_x, q.out_noise, q.normalize};
+  StepKey key;
+  key.params = params; key.rope = rope_freqs; key.ws = q.workspace; key.B = B; key.RT = RT; key.normalize = q.normalize; key.pred = q.pred;
+  key.update = sc.kind; key.clip = sc.clip_x0; key.guidance = g ? q.w : -1.f; key.opt_epoch = options_epoch();
+  if (sc.stats.on()) { key.rescale = sc.stats.rescale ? sc.stats.phi : 0.0; key.quantile = sc.stats.q; key.cap = sc.stats.cap; key.stat_scratch = q.stat_scratch; }
+  const StepStage stage{reinterpret_cast<int*>(c.w(a.step)), reinterpret_cast<uint64_t*>(c.w(a.seed_stage)), reinterpret_cast<int64_t*>(c.w(a.ids_stage))};
+  bool captured;
+  const int rc = sample_run(q, loop, sc.sto, plan->step, plan->step.exec && plan->step_key == key, stage, &captured);
+  if (captured) plan->step_key = key;
+  return rc;
 }
 
-// The stand-alone updates: one step over caller-supplied tensors, row 0 of coef_dev (with sigma / c1 as a fifth float behind it); a plain
-// element count n is one window of n elements
-StepUpdateLaunch one_update(UpdateFamily family, int pred, const float* x_t, const float* net, float* x_prev, float* eps_out,
-                                   const float* coef_dev, int B, int64_t per) {
-  StepUpdateLaunch a;
-  a.family = family; a.pred = pred;
-  a.x_t = x_t; a.net = net; a.x_prev = x_prev; a.eps_out = eps_out;
-  a.coef = coef_dev; a.extra = coef_dev + 4;
-  a.B = B; a.per = per;
-  return a;
+// The refusals of the stand-alone guided and per-window updates, in one order; args_ok: the entry's required pointers are all there;
+// guided: net_u is given (the per-window entry alone takes it null, and then for the solver kinds alone)
+int update_check(const std::string& who, bool args_ok, int kind, bool guided, const void* seed_dev, const void* x0_hist, int pred_type, float w,
+                 int B, int64_t per_window) {
+  DQ_REQUIRE(args_ok, who + ": null argument");
+  DQ_REQUIRE(kind == DQ_UPDATE_DDIM || kind == DQ_UPDATE_STOCHASTIC || kind == DQ_UPDATE_SOLVER_1 || kind == DQ_UPDATE_SOLVER_2M,
+             who + ": unknown update kind");
+  DQ_REQUIRE(guided || kind == DQ_UPDATE_SOLVER_1 || kind == DQ_UPDATE_SOLVER_2M,
+             who + ": the unguided per-window form is the solver kinds' (thresholding); net_u is needed");
+  DQ_REQUIRE(kind != DQ_UPDATE_STOCHASTIC || seed_dev, who + ": the stochastic update needs the seed (device memory)");
+  DQ_REQUIRE(kind != DQ_UPDATE_SOLVER_2M || x0_hist, who + ": the 2M update needs the x0 history");
+  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0 || pred_type == DQ_PRED_V, who + ": Unknown pred_type");
+  DQ_REQUIRE(!guided || guidance_ok(w), who + ": the guidance scale must be finite and >= 0");
+  DQ_REQUIRE(B >= 0 && per_window >= 0, who + ": negative size");
+  return 0;
+}
+
+// dq_guided_update and dq_guided_update_v: `who` prefixes the refusals
+int guided_update(const std::string& who, int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror,
+                  float* x0_hist, float* eps_out, const float* coef_dev, float w, float clip_x0, const int64_t* window_ids_dev,
+                  const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window, void* stream) {
+  DQ_TRY(update_check(who, x_t && net_c && net_u && x_prev && coef_dev, kind, true, seed_dev, x0_hist, pred_type, w, B, per_window));
+  StepUpdateLaunch a = update_launch((StepUpdate)kind, pred_type, x_t, net_c, net_u, x_prev, x_mirror, x0_hist, eps_out, coef_dev, coef_dev + 4,
+                                     StepNoise{window_ids_dev, seed_dev, draw}, B, per_window);
+  a.clip = clip_x0; a.w = w;
+  return launch_update(a, (hipStream_t)stream);
 }
 
 }  // namespace
 
 extern "C" {
 
+// The stand-alone updates: one step over caller-supplied tensors, row 0 of coef_dev (with sigma / c1 as a fifth float behind it); a plain
+// element count n is one window of n elements
 int dq_ddim_step(const float* x_t, const float* eps, float* x_prev, const float* coef_dev, int64_t n, void* stream) {
-  return launch_update(one_update(UpdateFamily::DDIM, DQ_PRED_EPS, x_t, eps, x_prev, nullptr, coef_dev, 1, n), (hipStream_t)stream);
+  return launch_update(update_launch(StepUpdate::DDIM, DQ_PRED_EPS, x_t, eps, nullptr, x_prev, nullptr, nullptr, nullptr, coef_dev, coef_dev + 4, {}, 1, n),
+                       (hipStream_t)stream);
 }
 
 int dq_ddim_step_x0(const float* x_t, const float* x0_pred, float* x_prev, float* eps_out, const float* coef_dev, int64_t n,
                     void* stream) {
   DQ_REQUIRE(x_t && x0_pred && x_prev && coef_dev, "dq_ddim_step_x0: null argument");
-  return launch_update(one_update(UpdateFamily::DDIM, DQ_PRED_X0, x_t, x0_pred, x_prev, eps_out, coef_dev, 1, n), (hipStream_t)stream);
+  return launch_update(update_launch(StepUpdate::DDIM, DQ_PRED_X0, x_t, x0_pred, nullptr, x_prev, nullptr, nullptr, eps_out, coef_dev, coef_dev + 4, {}, 1, n),
+                       (hipStream_t)stream);
 }
 
 int dq_ddim_step_v(const float* x_t, const float* v_pred, float* x_prev, float* eps_out, const float* coef_dev, int64_t n, void* stream) {
   DQ_REQUIRE(x_t && v_pred && x_prev && coef_dev, "dq_ddim_step_v: null argument");
-  return launch_update(one_update(UpdateFamily::DDIM, DQ_PRED_V, x_t, v_pred, x_prev, eps_out, coef_dev, 1, n), (hipStream_t)stream);
+  return launch_update(update_launch(StepUpdate::DDIM, DQ_PRED_V, x_t, v_pred, nullptr, x_prev, nullptr, nullptr, eps_out, coef_dev, coef_dev + 4, {}, 1, n),
+                       (hipStream_t)stream);
 }
 
 int dq_randn(float* out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int B, int64_t per_window, void* stream) {
@@ -327,9 +352,19 @@ int dq_ddim_step_sto(const float* x_t, const float* net_out, float* x_prev, floa
   DQ_REQUIRE(x_t && net_out && x_prev && coef_dev && seed_dev, "dq_ddim_step_sto: null argument");
   DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0 || pred_type == DQ_PRED_V, "dq_ddim_step_sto: Unknown pred_type");
   // (refused by launch_update: a per-window count that is no multiple of 4, tensors that are not 16-byte aligned)
-  StepUpdateLaunch a = one_update(UpdateFamily::STOCHASTIC, pred_type, x_t, net_out, x_prev, pred_type != DQ_PRED_EPS ? eps_out : nullptr,
-                                  coef_dev, B, per_window);
-  a.ids = window_ids_dev; a.seed = seed_dev; a.draw = draw;
+  return launch_update(update_launch(StepUpdate::STOCHASTIC, pred_type, x_t, net_out, nullptr, x_prev, nullptr, nullptr,
+                                     pred_type != DQ_PRED_EPS ? eps_out : nullptr, coef_dev, coef_dev + 4, StepNoise{window_ids_dev, seed_dev, draw},
+                                     B, per_window),
+                       (hipStream_t)stream);
+}
+
+int dq_solver_step_v(const float* x_t, const float* v_pred, float* x_prev, float* x0_hist, float* eps_out, const float* coef_dev, float clip_x0,
+                     int64_t n, void* stream) {
+  DQ_REQUIRE(x_t && v_pred && x_prev && coef_dev, "dq_solver_step_v: null argument");
+  // (a history makes it the 2M update, none the first-order one)
+  StepUpdateLaunch a = update_launch(x0_hist ? StepUpdate::SOLVER_2M : StepUpdate::SOLVER_1, DQ_PRED_V, x_t, v_pred, nullptr, x_prev, nullptr, x0_hist,
+                                     eps_out, coef_dev, coef_dev + 4, {}, 1, n);
+  a.clip = clip_x0;
   return launch_update(a, (hipStream_t)stream);
 }
 
@@ -337,16 +372,9 @@ int dq_solver_step(const float* x_t, const float* net_out, float* x_prev, float*
                    int pred_type, int64_t n, void* stream) {
   DQ_REQUIRE(x_t && net_out && x_prev && coef_dev, "dq_solver_step: null argument");
   DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0, "dq_solver_step: Unknown pred_type");  // (DQ_PRED_V: dq_solver_step_v)
-  StepUpdateLaunch a = one_update(UpdateFamily::SOLVER, pred_type, x_t, net_out, x_prev, eps_out, coef_dev, 1, n);
-  a.hist = x0_hist; a.clip = clip_x0;
-  return launch_update(a, (hipStream_t)stream);
-}
-
-int dq_solver_step_v(const float* x_t, const float* v_pred, float* x_prev, float* x0_hist, float* eps_out, const float* coef_dev, float clip_x0,
-                     int64_t n, void* stream) {
-  DQ_REQUIRE(x_t && v_pred && x_prev && coef_dev, "dq_solver_step_v: null argument");
-  StepUpdateLaunch a = one_update(UpdateFamily::SOLVER, DQ_PRED_V, x_t, v_pred, x_prev, eps_out, coef_dev, 1, n);
-  a.hist = x0_hist; a.clip = clip_x0;
+  StepUpdateLaunch a = update_launch(x0_hist ? StepUpdate::SOLVER_2M : StepUpdate::SOLVER_1, pred_type, x_t, net_out, nullptr, x_prev, nullptr, x0_hist,
+                                     eps_out, coef_dev, coef_dev + 4, {}, 1, n);
+  a.clip = clip_x0;
   return launch_update(a, (hipStream_t)stream);
 }
 
@@ -375,9 +403,12 @@ int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_
                       const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
                       int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
                       const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0) {
-  return unet_sample(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type, timesteps_host,
-                     num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream, eta, seed_dev,
-                     window_ids_dev, sampler, clip_x0, nullptr);
+  SampleCall q;  q.who = "dq_ddim_sample";  // (dq_ddim_sample and dq_ddim_sample_ex arrive here: the three refuse under the first one's name)
+  q.alpha_bars_host = alpha_bars_host; q.T = num_timesteps; q.x_T = x_T; q.ms2_cond = ms2_cond; q.ms1_cond = ms1_cond; q.normalize = auto_normalize;
+  q.pred = pred_type; q.ts = timesteps_host; q.num_steps = num_steps; q.out_x = out_x; q.out_noise = out_noise; q.traj_x = traj_x; q.traj_eps = traj_eps;
+  q.use_graph = use_graph; q.workspace = workspace; q.workspace_bytes = workspace_bytes; q.B = B; q.RT = RT; q.stream = (hipStream_t)stream;
+  q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
+  return unet_sample(plan, params, rope_freqs, q);
 }
 
 int dq_ddim_sample_guided(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
@@ -386,35 +417,14 @@ int dq_ddim_sample_guided(dq_plan* plan, const float* params, const float* rope_
                           int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
                           const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, float guidance_scale,
                           float null_ms1) {
-  const Guidance g{guidance_scale, null_ms1};
-  return unet_sample(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type, timesteps_host,
-                     num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream, eta, seed_dev,
-                     window_ids_dev, sampler, clip_x0, &g);
+  SampleCall q;  q.who = "dq_ddim_sample_guided";
+  q.alpha_bars_host = alpha_bars_host; q.T = num_timesteps; q.x_T = x_T; q.ms2_cond = ms2_cond; q.ms1_cond = ms1_cond; q.normalize = auto_normalize;
+  q.pred = pred_type; q.ts = timesteps_host; q.num_steps = num_steps; q.out_x = out_x; q.out_noise = out_noise; q.traj_x = traj_x; q.traj_eps = traj_eps;
+  q.use_graph = use_graph; q.workspace = workspace; q.workspace_bytes = workspace_bytes; q.B = B; q.RT = RT; q.stream = (hipStream_t)stream;
+  q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
+  q.guided = true; q.w = guidance_scale; q.null_ms1 = null_ms1;
+  return unet_sample(plan, params, rope_freqs, q);
 }
-
-}  // extern "C"
-
-namespace {
-// dq_guided_update and dq_guided_update_v: `who` prefixes the refusals
-int guided_update(const std::string& who, int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror,
-                  float* x0_hist, float* eps_out, const float* coef_dev, float w, float clip_x0, const int64_t* window_ids_dev,
-                  const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window, void* stream) {
-  DQ_REQUIRE(x_t && net_c && net_u && x_prev && coef_dev, who + ": null argument");
-  DQ_REQUIRE(kind == DQ_UPDATE_DDIM || kind == DQ_UPDATE_STOCHASTIC || kind == DQ_UPDATE_SOLVER_1 || kind == DQ_UPDATE_SOLVER_2M,
-             who + ": unknown update kind");
-  DQ_REQUIRE(kind != DQ_UPDATE_STOCHASTIC || seed_dev, who + ": the stochastic update needs the seed (device memory)");
-  DQ_REQUIRE(kind != DQ_UPDATE_SOLVER_2M || x0_hist, who + ": the 2M update needs the x0 history");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0 || pred_type == DQ_PRED_V, who + ": Unknown pred_type");
-  DQ_REQUIRE(guidance_ok(w), who + ": the guidance scale must be finite and >= 0");
-  DQ_REQUIRE(B >= 0 && per_window >= 0, who + ": negative size");
-  // coefficient layout per kind: the stand-alone entries' (4 floats, or 5 with sigma / c1 behind them)
-  const StepUpdateArgs u{(StepUpdate)kind, coef_dev, coef_dev + 4, x0_hist, clip_x0, pred_type, B, per_window, true, w};
-  return launch_step_update(u, x_t, net_c, net_u, x_prev, x_mirror, eps_out, 0, nullptr, StepNoise{window_ids_dev, seed_dev, draw}, false,
-                            (hipStream_t)stream);
-}
-}  // namespace
-
-extern "C" {
 
 int dq_guided_update(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
                      float* eps_out, const float* coef_dev, float w, float clip_x0, const int64_t* window_ids_dev, const uint64_t* seed_dev,
@@ -436,10 +446,14 @@ int dq_ddim_sample_v(dq_plan* plan, const float* params, const float* rope_freqs
                      const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps, int use_graph,
                      void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta, const uint64_t* seed_dev,
                      const int64_t* window_ids_dev, int sampler, float clip_x0, int guided, float guidance_scale, float null_ms1) {
-  const Guidance g{guidance_scale, null_ms1};
-  return unet_sample(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type, timesteps_host,
-                     num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream, eta, seed_dev,
-                     window_ids_dev, sampler, clip_x0, guided ? &g : nullptr, true);
+  SampleCall q;  q.who = "dq_ddim_sample_v";
+  q.alpha_bars_host = alpha_bars_host; q.T = num_timesteps; q.x_T = x_T; q.ms2_cond = ms2_cond; q.ms1_cond = ms1_cond; q.normalize = auto_normalize;
+  q.pred = pred_type; q.ts = timesteps_host; q.num_steps = num_steps; q.out_x = out_x; q.out_noise = out_noise; q.traj_x = traj_x; q.traj_eps = traj_eps;
+  q.use_graph = use_graph; q.workspace = workspace; q.workspace_bytes = workspace_bytes; q.B = B; q.RT = RT; q.stream = (hipStream_t)stream;
+  q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
+  q.allow_v = true;
+  q.guided = guided != 0; q.w = guidance_scale; q.null_ms1 = null_ms1;
+  return unet_sample(plan, params, rope_freqs, q);
 }
 
 // ---- per-window sampler control
@@ -472,25 +486,11 @@ int dq_window_abs_quantile(const float* x, int B, int64_t per_window, float q, f
 int dq_step_update_adaptive(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
                             float* eps_out, const float* coef_dev, float w, const float* table_dev, const int64_t* window_ids_dev,
                             const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window, void* stream) {
-  const std::string who = "dq_step_update_adaptive";
-  DQ_REQUIRE(x_t && net_c && x_prev && coef_dev && table_dev, who + ": null argument");
-  DQ_REQUIRE(kind == DQ_UPDATE_DDIM || kind == DQ_UPDATE_STOCHASTIC || kind == DQ_UPDATE_SOLVER_1 || kind == DQ_UPDATE_SOLVER_2M,
-             who + ": unknown update kind");
-  const bool solver = kind == DQ_UPDATE_SOLVER_1 || kind == DQ_UPDATE_SOLVER_2M;
-  DQ_REQUIRE(net_u || solver, who + ": the unguided per-window form is the solver kinds' (thresholding); net_u is needed");
-  DQ_REQUIRE(kind != DQ_UPDATE_STOCHASTIC || seed_dev, who + ": the stochastic update needs the seed (device memory)");
-  DQ_REQUIRE(kind != DQ_UPDATE_SOLVER_2M || x0_hist, who + ": the 2M update needs the x0 history");
-  DQ_REQUIRE(pred_type == DQ_PRED_EPS || pred_type == DQ_PRED_X0 || pred_type == DQ_PRED_V, who + ": Unknown pred_type");
-  DQ_REQUIRE(!net_u || guidance_ok(w), who + ": the guidance scale must be finite and >= 0");
-  DQ_REQUIRE(B >= 0 && per_window >= 0, who + ": negative size");
-  StepUpdateLaunch a;
-  a.family = kind == DQ_UPDATE_DDIM ? UpdateFamily::DDIM : kind == DQ_UPDATE_STOCHASTIC ? UpdateFamily::STOCHASTIC : UpdateFamily::SOLVER;
-  a.guided = net_u != nullptr; a.pred = pred_type;
-  a.x_t = x_t; a.net = net_c; a.net_u = net_u; a.x_prev = x_prev; a.x_mirror = net_u ? x_mirror : nullptr; a.eps_out = eps_out;
-  a.hist = kind == DQ_UPDATE_SOLVER_2M ? x0_hist : nullptr;
-  a.coef = coef_dev; a.extra = coef_dev + 4;
-  a.ids = window_ids_dev; a.seed = seed_dev; a.draw = draw;
-  a.w = w; a.B = B; a.per = per_window; a.win = table_dev;
+  DQ_TRY(update_check("dq_step_update_adaptive", x_t && net_c && x_prev && coef_dev && table_dev, kind, net_u != nullptr, seed_dev, x0_hist, pred_type,
+                      w, B, per_window));
+  StepUpdateLaunch a = update_launch((StepUpdate)kind, pred_type, x_t, net_c, net_u, x_prev, x_mirror, x0_hist, eps_out, coef_dev, coef_dev + 4,
+                                     StepNoise{window_ids_dev, seed_dev, draw}, B, per_window);
+  a.w = w; a.win = table_dev;
   return launch_update(a, (hipStream_t)stream);
 }
 
@@ -501,11 +501,16 @@ int dq_ddim_sample_adaptive(dq_plan* plan, const float* params, const float* rop
                             const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, int guided, float guidance_scale,
                             float null_ms1, double guidance_rescale, float threshold_quantile, float threshold_max, void* stat_scratch,
                             int64_t stat_scratch_bytes) {
-  const Guidance g{guidance_scale, null_ms1};
-  const Adaptive ad{guidance_rescale, threshold_quantile, threshold_max, stat_scratch, stat_scratch_bytes};
-  return unet_sample(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type, timesteps_host,
-                     num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream, eta, seed_dev,
-                     window_ids_dev, sampler, clip_x0, guided ? &g : nullptr, true, &ad);
+  SampleCall q;  q.who = "dq_ddim_sample_adaptive";
+  q.alpha_bars_host = alpha_bars_host; q.T = num_timesteps; q.x_T = x_T; q.ms2_cond = ms2_cond; q.ms1_cond = ms1_cond; q.normalize = auto_normalize;
+  q.pred = pred_type; q.ts = timesteps_host; q.num_steps = num_steps; q.out_x = out_x; q.out_noise = out_noise; q.traj_x = traj_x; q.traj_eps = traj_eps;
+  q.use_graph = use_graph; q.workspace = workspace; q.workspace_bytes = workspace_bytes; q.B = B; q.RT = RT; q.stream = (hipStream_t)stream;
+  q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
+  q.allow_v = true;
+  q.guided = guided != 0; q.w = guidance_scale; q.null_ms1 = null_ms1;
+  q.adaptive = true; q.phi = guidance_rescale; q.quantile = threshold_quantile; q.cap = threshold_max;
+  q.stat_scratch = stat_scratch; q.stat_bytes = stat_scratch_bytes;
+  return unet_sample(plan, params, rope_freqs, q);
 }
 
 int dq_ms1_cond_drop(const float* ms1_in, float* ms1_out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, double p,

@@ -1,6 +1,7 @@
-// Sampling from the CustomTransformer inside the library: dq_tfm_sample walks all timesteps -- a sampling forward of
-// the network and one update of dq_sampler.h per step, eagerly or as one captured step replayed -- and the stand-alone entry of the fused
-// inference attention (k_tfm_attn.hip).  What does not depend on the step is computed once per call, before the loop: the conditional
+// Sampling from the CustomTransformer inside the library: dq_tfm_sample fills the call's record and runs it as the
+// U-Net's entry does (dq_sampler.h: the shared refusals, tables and captured-or-eager tail around this network's layout, prologue and
+// forward), one update per step behind a sampling forward of the network -- and the stand-alone entry of the fused inference attention
+// (k_tfm_attn.hip).  What does not depend on the step is computed once per call, before the loop: the conditional
 // embedding cp of the MS1 chromatogram, every layer's K | V rows of it, and the time embedding of every step.  The forward itself is the
 // one walk of the network (tfm_walk, dq_tfm.hip) that dq_tfm_fwd makes too, here with its K | V rows cached.
 // Held-out evaluation: dq_tfm_eval_step runs the same prologue and the same forward once over R repeats of a batch
@@ -135,29 +136,31 @@ int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const f
                   int auto_normalize, int pred_type, const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x,
                   float* traj_eps, int use_graph, void* workspace, int64_t workspace_bytes, int B, int S1, int S2, void* stream, float eta,
                   const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0) {
+  SampleCall q;  q.who = "dq_tfm_sample";
+  q.alpha_bars_host = alpha_bars_host; q.T = num_timesteps; q.x_T = x_T; q.ms2_cond = ms2_cond; q.ms1_cond = ms1_cond; q.normalize = auto_normalize;
+  q.pred = pred_type; q.ts = timesteps_host; q.num_steps = num_steps; q.out_x = out_x; q.out_noise = out_noise; q.traj_x = traj_x; q.traj_eps = traj_eps;
+  q.use_graph = use_graph; q.workspace = workspace; q.workspace_bytes = workspace_bytes; q.B = B; q.RT = S1; q.stream = (hipStream_t)stream;
+  q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
   SamplerChoice sc;
-  DQ_TRY(sampler_check("dq_tfm_sample", p && params && rope_sin && rope_cos && time_freqs && alpha_bars_host && ms2_cond && ms1_cond && timesteps_host &&
-                                            out_x && out_noise && workspace,
-                       eta, sampler, clip_x0, timesteps_host, num_steps, seed_dev != nullptr, x_T != nullptr, pred_type, false, &sc));
+  DQ_TRY(sample_check(q, p && params && rope_sin && rope_cos && time_freqs, &sc));
   DQ_REQUIRE(B > 0 && S1 > 0 && S2 > 0 && num_steps >= 1 && num_steps <= 1024, "dq_tfm_sample: need B, S1, S2 > 0 and 1 <= num_steps <= 1024");
-  const int T = num_timesteps;
-  DQ_REQUIRE(T >= 1, "dq_tfm_sample: num_timesteps must be >= 1");
+  DQ_REQUIRE(q.T >= 1, "dq_tfm_sample: num_timesteps must be >= 1");
   DQ_REQUIRE(((uintptr_t)params & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "dq_tfm_sample: params and workspace must be 16-byte aligned");
   const SampleWs w = carve_sample(*p, (float*)workspace, B, S1, S2, num_steps);
   DQ_REQUIRE(workspace_bytes >= w.floats * (int64_t)sizeof(float), "dq_tfm_sample: workspace too small (dq_tfm_sample_workspace_bytes)");
   PrecisionScope prec(p->precision);
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t per = (int64_t)S1 * p->D, n = B * per;
+  hipStream_t s = q.stream;
+  const int64_t per = (int64_t)S1 * p->D;
   const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
-  const int32_t* ts = timesteps_host;
   const TfmWalk net = cached_walk(p, params, rope_sin, rope_cos, w.net, w.kv.data(), w.time.temb, false, B, S1, S2);
-  // the steps' timesteps for the time table (the copy is done when the table upload below returns: it synchronises the stream)
-  std::vector<int64_t> t64((size_t)num_steps);
-  for (int i = 0; i < num_steps; ++i) t64[i] = ts[i];
+  // the steps' timesteps for the time table (the copy is done when sample_begin returns: it synchronises the stream)
+  std::vector<int64_t> t64(timesteps_host, timesteps_host + num_steps);
   DQ_HIP_OK(hipMemcpyAsync(w.t64, t64.data(), sizeof(int64_t) * t64.size(), hipMemcpyHostToDevice, s));
-  DQ_TRY(sampler_upload_tables("dq_tfm_sample", alpha_bars_host, T, ts, num_steps, sampler, sc, eta, w.coef, w.sigma, s));
-  if (x_T) DQ_HIP_OK(hipMemcpyAsync(w.xa, x_T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-  else DQ_TRY(launch_randn(w.xa, window_ids_dev, seed_dev, 0, B, per, s));  // draw index 0 is x_T's
+  DQ_TRY(sample_begin(q, sc, per, w.coef, w.sigma, w.xa));
+  if (net.attn_form == TFM_ATTN_FUSED) DQ_TRY(tfm_attn_prepare());  // (the LDS limit of this device, before any capture)
+  // every call, outside any capture: a changed MS1, or changed weights behind the same pointer, cannot meet a stale cache
+  DQ_TRY(sample_prologue(net, B, ms1_cond, cm, ca, time_freqs, w.t64, num_steps, w.time, s));
+  // the forward of this network: a linear graph when captured (one stream, no branches); the time row is `row`, or read at *step_ptr
   const StepForward forward = [&](const float* x, float*, int row, const int* step_ptr, float* net_out, bool, bool* fused, hipStream_t fs) {
     *fused = false;  // (the update is never in this network's launches)
     TfmWalk step = net;
@@ -166,24 +169,14 @@ int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const f
   };
   const SampleLoop loop{forward, StepUpdateArgs{sc.kind, w.coef, w.sigma, w.xb, sc.clip_x0, sc.pred, B, per}, w.xa, w.eps, sc.clip,
                         num_steps, ms2_cond, out_x, out_noise, auto_normalize};
-  if (net.attn_form == TFM_ATTN_FUSED) DQ_TRY(tfm_attn_prepare());  // (the LDS limit of this device, before any capture)
-  // every call, outside any capture: a changed MS1, or changed weights behind the same pointer, cannot meet a stale cache
-  DQ_TRY(sample_prologue(net, B, ms1_cond, cm, ca, time_freqs, w.t64, num_steps, w.time, s));
-  if (use_graph && !traj_x && !traj_eps) {
-    // ---- one step captured once (every pointer inside the workspace / parameter buffers), replayed per step.  The step index lives on the
-    // device: the time row and the update's coefficient row are read at *step, k_inc_step bumps it.  A linear graph: one stream, no branches.
-    DQ_HIP_OK(hipMemsetAsync(w.step, 0, sizeof(int), s));
-    if (sc.sto) DQ_TRY(sampler_stage_noise(w.seed_stage, w.ids_stage, seed_dev, window_ids_dev, B, s));
-    TfmStepKey key;
-    key.params = params; key.ws = workspace; key.rope_sin = rope_sin; key.rope_cos = rope_cos; key.B = B; key.S1 = S1; key.S2 = S2;
-    key.num_steps = num_steps; key.normalize = auto_normalize; key.pred = pred_type; key.precision = p->precision; key.update = sc.kind; key.clip = sc.clip_x0;
-    key.opt_epoch = options_epoch();
-    bool captured;
-    const int rc = replay_captured_step(p->step, p->step.exec && p->step_key == key, loop, w.step, StepNoise{w.ids_stage, w.seed_stage, 0}, s, &captured);
-    if (captured) p->step_key = key;
-    return rc;
-  }
-  return eager_steps(loop, traj_x, traj_eps, window_ids_dev, seed_dev, s);
+  TfmStepKey key;
+  key.params = params; key.ws = workspace; key.rope_sin = rope_sin; key.rope_cos = rope_cos; key.B = B; key.S1 = S1; key.S2 = S2;
+  key.num_steps = num_steps; key.normalize = auto_normalize; key.pred = pred_type; key.precision = p->precision; key.update = sc.kind; key.clip = sc.clip_x0;
+  key.opt_epoch = options_epoch();
+  bool captured;
+  const int rc = sample_run(q, loop, sc.sto, p->step, p->step.exec && p->step_key == key, StepStage{w.step, w.seed_stage, w.ids_stage}, &captured);
+  if (captured) p->step_key = key;
+  return rc;
 }
 
 int dq_tfm_kv_broadcast(float* kv, int B, int repeats, int S2, int Sk, int H, void* stream) {

@@ -7,6 +7,8 @@ mixtures with drawn weights on the GPU (``ResidentMixLoader``).  ``generate-trai
 and reports so.  Under ``torch.distributed.run`` (WORLD_SIZE > 1) training is data-parallel: one process per GPU, the
 dataset is sharded by rank and the flat gradient is all-reduced over RCCL."""
 import ast
+import dataclasses
+import functools
 import json
 import os
 
@@ -14,7 +16,7 @@ import click
 import torch
 from torch.utils.data import DataLoader
 
-from .model.model import DDIMDiffusionModel
+from .model.model import DDIMDiffusionModel, SampleOptions
 from .model.unet1d import UNet1d
 from .utils.config_loader import generate_train_config, load_train_config, mixture_config, validation_config
 
@@ -214,29 +216,46 @@ def load_inference_checkpoint(dm, m, checkpoint, device, use_ema):
         raise click.ClickException(f"--use-ema: {checkpoint} holds no averaged weights")
 
 
+# The options of a sampling call, declared once for ``evaluate`` and ``deconvolve`` (between each command's own --num-steps and --use-ema)
+_SAMPLING_OPTIONS = (
+    click.option("--eta", default=0.0, type=float, help="DDIM eta of the sampling (0: deterministic update, 1: ancestral)"),
+    click.option("--sampler", default="reference", type=click.Choice(["reference", "ddim", "dpmpp_2m"]),
+                 help="Update of the sampling: the reference's, strided DDIM, or DPM-Solver++(2M)"),
+    click.option("--clip-x0", default=None, type=float, help="Clamp every step's x0 estimate to [-C, C] (ddim / dpmpp_2m, eta 0)"),
+    click.option("--guidance-scale", default=None, type=float,
+                 help="Classifier-free guidance scale W of the sampling (UNet1d trained with model.cond_drop_prob; 1: the conditional model)"),
+    click.option("--null-ms1", default=0.0, type=float, help="Raw MS1 value of the null condition (the training run's model.null_ms1)"),
+    click.option("--guidance-rescale", default=0.0, type=float,
+                 help="Rescaled guidance PHI in [0, 1]: scale each window's guided output towards the conditional output's spread (needs --guidance-scale)"),
+    click.option("--threshold-quantile", default=None, type=float,
+                 help="Dynamic thresholding: clamp every step's x0 estimate to the window's Q-quantile of |x0| (never below --clip-x0, or 1) and "
+                      "scale it back to that floor (ddim / dpmpp_2m, eta 0)"),
+    click.option("--threshold-max", default=None, type=float, help="Upper bound of the dynamic threshold (needs --threshold-quantile)"),
+    click.option("--seed", default=0, type=int, help="Seed of x_T, of the sampling noise and of the evaluation noise"),
+)
+
+
+def sampling_options(command):
+    """Declares ``_SAMPLING_OPTIONS`` on ``command`` and hands it ``eta``, ``seed`` and, in place of the seven options of ``SampleOptions``
+    (taken by name), ``sample_kw``: the ones that are not at their defaults, as ``evaluate`` / ``deconvolve_run`` / ``sample`` take them"""
+    @functools.wraps(command)
+    def with_sample_kw(**kw):
+        return command(sample_kw=SampleOptions(**{f.name: kw.pop(f.name) for f in dataclasses.fields(SampleOptions)}).non_default(), **kw)
+
+    for option in reversed(_SAMPLING_OPTIONS):
+        with_sample_kw = option(with_sample_kw)
+    return with_sample_kw
+
+
 @cli.command()
 @click.argument("config-path", type=click.Path(exists=True), required=True)
 @click.option("--checkpoint", required=True, type=click.Path(exists=True), help="Checkpoint written by train (model_state_dict; its EMA when it has one)")
 @click.option("--num-steps", default=None, type=int, help="Also sample every window with this many DDIM steps and report reconstruction metrics")
-@click.option("--eta", default=0.0, type=float, help="DDIM eta of that sampling (0: deterministic update, 1: ancestral)")
-@click.option("--sampler", default="reference", type=click.Choice(["reference", "ddim", "dpmpp_2m"]),
-              help="Update of that sampling: the reference's, strided DDIM, or DPM-Solver++(2M)")
-@click.option("--clip-x0", default=None, type=float, help="Clamp every step's x0 estimate to [-C, C] (ddim / dpmpp_2m, eta 0)")
-@click.option("--guidance-scale", default=None, type=float,
-              help="Classifier-free guidance scale W of that sampling (UNet1d trained with model.cond_drop_prob; 1: the conditional model)")
-@click.option("--null-ms1", default=0.0, type=float, help="Raw MS1 value of the null condition (the training run's model.null_ms1)")
-@click.option("--guidance-rescale", default=0.0, type=float,
-              help="Rescaled guidance PHI in [0, 1]: scale each window's guided output towards the conditional output's spread (needs --guidance-scale)")
-@click.option("--threshold-quantile", default=None, type=float,
-              help="Dynamic thresholding: clamp every step's x0 estimate to the window's Q-quantile of |x0| (never below --clip-x0, or 1) and "
-                   "scale it back to that floor (ddim / dpmpp_2m, eta 0)")
-@click.option("--threshold-max", default=None, type=float, help="Upper bound of the dynamic threshold (needs --threshold-quantile)")
-@click.option("--seed", default=0, type=int, help="Seed of the evaluation noise and of the sampling")
+@sampling_options
 @click.option("--use-ema/--no-use-ema", default=None, help="Evaluate the averaged weights (default: when the checkpoint has an average)")
 @click.option("--max-batches", default=None, type=int, help="Stop after this many batches")
 @click.option("--out", "out_path", default=None, type=click.Path(), help="Write the full result, per-window metrics included, as JSON")
-def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile,
-             threshold_max, seed, use_ema, max_batches, out_path):
+def evaluate(config_path, checkpoint, num_steps, eta, seed, sample_kw, use_ema, max_batches, out_path):
     """Held-out loss (and, with --num-steps, reconstruction metrics) of a checkpoint on the config's data.validation set.  The pairs of
     that set come from the block's own seed, not from --seed: runs that differ in --seed, --eta, --num-steps or --use-ema score the same
     pairs.  Without a validation block the config's data section is scored, with a notice.  Prints one JSON line."""
@@ -254,9 +273,7 @@ def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, guidance
     loader = build_validation_loader(val, m, max(1, int(m["batch_size"])))
     dm = build_model(m, device)
     load_inference_checkpoint(dm, m, checkpoint, device, use_ema)
-    res = dm.evaluate(loader, n_t=4, seed=seed, num_steps=num_steps, eta=eta, use_ema=use_ema, max_batches=max_batches, sampler=sampler,
-                      clip_x0=clip_x0, guidance_scale=guidance_scale, null_ms1=null_ms1, guidance_rescale=guidance_rescale,
-                      threshold_quantile=threshold_quantile, threshold_max=threshold_max)
+    res = dm.evaluate(loader, n_t=4, seed=seed, num_steps=num_steps, eta=eta, use_ema=use_ema, max_batches=max_batches, **sample_kw)
     # the per-window arrays go to --out only; the printed line keeps the scalars and the buckets (val_loss_by_weight among them)
     arrays = {k: res.pop(k).tolist() for k in ("per_window", "target_weight") if k in res}
     click.echo(json.dumps(res))
@@ -278,23 +295,9 @@ def evaluate(config_path, checkpoint, num_steps, eta, sampler, clip_x0, guidance
 @click.option("--taper", default="hann", type=click.Choice(["hann", "uniform"]), help="Weight of a window's scans where windows overlap")
 @click.option("--batch-size", default=32, type=int, help="Windows sampled per call (the result does not depend on it)")
 @click.option("--num-steps", default=1000, type=int, help="Sampling steps per window")
-@click.option("--eta", default=0.0, type=float, help="DDIM eta of the sampling (0: deterministic update, 1: ancestral)")
-@click.option("--sampler", default="reference", type=click.Choice(["reference", "ddim", "dpmpp_2m"]),
-              help="Update of the sampling: the reference's, strided DDIM, or DPM-Solver++(2M)")
-@click.option("--clip-x0", default=None, type=float, help="Clamp every step's x0 estimate to [-C, C] (ddim / dpmpp_2m, eta 0)")
-@click.option("--guidance-scale", default=None, type=float,
-              help="Classifier-free guidance scale W of the sampling (UNet1d trained with model.cond_drop_prob; 1: the conditional model)")
-@click.option("--null-ms1", default=0.0, type=float, help="Raw MS1 value of the null condition (the training run's model.null_ms1)")
-@click.option("--guidance-rescale", default=0.0, type=float,
-              help="Rescaled guidance PHI in [0, 1]: scale each window's guided output towards the conditional output's spread (needs --guidance-scale)")
-@click.option("--threshold-quantile", default=None, type=float,
-              help="Dynamic thresholding: clamp every step's x0 estimate to the window's Q-quantile of |x0| (never below --clip-x0, or 1) and "
-                   "scale it back to that floor (ddim / dpmpp_2m, eta 0)")
-@click.option("--threshold-max", default=None, type=float, help="Upper bound of the dynamic threshold (needs --threshold-quantile)")
-@click.option("--seed", default=0, type=int, help="Seed of x_T and of the sampling noise")
+@sampling_options
 @click.option("--use-ema/--no-use-ema", default=None, help="Sample from the averaged weights (default: when the checkpoint has an average)")
-def deconvolve(config_path, checkpoint, ms2_path, ms1_path, out_path, window, step, taper, batch_size, num_steps, eta, sampler, clip_x0,
-               guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max, seed, use_ema):
+def deconvolve(config_path, checkpoint, ms2_path, ms1_path, out_path, window, step, taper, batch_size, num_steps, eta, seed, sample_kw, use_ema):
     """Deconvolve whole chromatograms with a checkpoint: every run is cut into overlapping windows, each window normalised on its own and
     sampled, and the predictions stitched back in intensity units (``deconvolve_run``).  Window i of run r samples under the id
     (windows of the runs before it) + i.  Prints one JSON line: runs, windows, windows per second."""
@@ -320,15 +323,6 @@ def deconvolve(config_path, checkpoint, ms2_path, ms1_path, out_path, window, st
     m = load_train_config(config_path)["model"]
     dm = build_model(m, device)
     load_inference_checkpoint(dm, m, checkpoint, device, use_ema)
-    kw = {"sampler": sampler, "clip_x0": clip_x0}
-    if guidance_scale is not None:
-        kw.update(guidance_scale=guidance_scale, null_ms1=null_ms1)
-    if guidance_rescale:
-        kw["guidance_rescale"] = guidance_rescale
-    if threshold_quantile is not None:
-        kw["threshold_quantile"] = threshold_quantile
-    if threshold_max is not None:
-        kw["threshold_max"] = threshold_max
     outs, first = [], 0
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -336,7 +330,7 @@ def deconvolve(config_path, checkpoint, ms2_path, ms1_path, out_path, window, st
         res = dm.deconvolve_run(torch.from_numpy(np.ascontiguousarray(ms2[r], dtype=np.float32)).to(device),
                                 torch.from_numpy(np.ascontiguousarray(ms1[r], dtype=np.float32)).to(device), window=window, step=step,
                                 taper=taper, batch_size=batch_size, id_offset=first, num_steps=num_steps, eta=eta, seed=seed, use_ema=use_ema,
-                                **kw)
+                                **sample_kw)
         first += res["n_windows"]
         outs.append({k: res[k].cpu().numpy() for k in ("pred", "overlap_var", "coverage", "scales")})
     torch.cuda.synchronize()

@@ -13,8 +13,10 @@ semantics (the reference's branch raises TypeError; SURVEY 8f, DESIGN.md section
 ``pred_type="v_prediction"`` (the network predicts v = sa eps - sb x0), is built for ``UNet1d``.
 """
 import ctypes
+import dataclasses
 import math
 import os
+from typing import Optional
 
 import torch
 import torch.nn.functional as F
@@ -75,6 +77,50 @@ _V_OTHER_NETWORKS = ("pred_type 'v_prediction' is implemented for UNet1d only (f
                      "evaluation under the v objective)")
 _V_MS1_TERM = ("ms1_loss_weight > 0 with pred_type 'v_prediction' is not implemented (follow-up: the MS1 term under the v objective; DESIGN.md "
                "section 12 defines it for 'eps' and 'x0' only)")
+
+
+@dataclasses.dataclass(frozen=True)
+class SampleOptions:
+    """The options of a sampling call beyond ``eta`` and the seed, at ``sample``'s public defaults (DESIGN.md sections 26, 32, 38): the one
+    place that says which of them are live and what the library is handed for them."""
+    sampler: str = "reference"
+    clip_x0: Optional[float] = None
+    guidance_scale: Optional[float] = None
+    null_ms1: float = 0.0
+    guidance_rescale: float = 0.0
+    threshold_quantile: Optional[float] = None
+    threshold_max: Optional[float] = None
+
+    def non_default(self):
+        """The options that are not at their defaults, as keyword arguments of ``sample`` -- none at the defaults, so that a subclass whose
+        ``sample`` predates them is still called as it always was.  ``null_ms1`` goes with ``guidance_scale`` and never without it."""
+        live = {"sampler": self.sampler != "reference", "clip_x0": self.clip_x0 is not None, "guidance_scale": self.guidance_scale is not None,
+                "null_ms1": self.guidance_scale is not None, "guidance_rescale": bool(self.guidance_rescale),
+                "threshold_quantile": self.threshold_quantile is not None, "threshold_max": self.threshold_max is not None}
+        return {k: getattr(self, k) for k, on in live.items() if on}
+
+    def resolve(self, eta, model):
+        """What the library takes: ``(sampler id, clamp or 0.0, (w, null_ms1) or None, (phi, q, cap) or None)`` -- None where the call is
+        the one without the option (a scale of 1.0; ``phi`` without guidance, where g = c and m = 1).  ValueError as the three checks of
+        ``model`` (a ``DDIMDiffusionModel``, or a subclass with checks of its own) raise it, in their order."""
+        sampler_id, clip = model._check_sampler(self.sampler, eta, self.clip_x0)
+        w = model._check_guidance(self.guidance_scale)
+        phi, q, cap = model._check_adaptive(self.guidance_rescale, self.threshold_quantile, self.threshold_max, self.sampler, eta, clip)
+        phi = 0.0 if w is None else phi  # (g = c: m = 1)
+        return sampler_id, clip, None if w is None else (w, float(self.null_ms1)), (phi, q, cap) if (phi > 0.0 or q > 0.0) else None
+
+
+# the options only UNet1d's native sampler serves, as sample() refuses them: (on a CustomTransformer, on anything else)
+_UNET_ONLY = {
+    "adaptive": ("sample: guidance_rescale and threshold_quantile are built for UNet1d (dq_ddim_sample_adaptive); the per-window statistics "
+                 "step for the CustomTransformer's sampler (dq_tfm_sample) is the follow-up",
+                 "sample: guidance_rescale and threshold_quantile need the native sampler (this package's UNet1d on the GPU with both "
+                 "conditions); the generic loop is the plain update only"),
+    "guidance": ("sample: guidance_scale is built for UNet1d (dq_ddim_sample_guided); guidance for the CustomTransformer's sampler "
+                 "(dq_tfm_sample) is the follow-up",
+                 "sample: guidance_scale needs the native sampler (this package's UNet1d on the GPU with both conditions); the generic "
+                 "loop is the unguided update only"),
+}
 
 
 class DDIMDiffusionModel(ModelInterface):
@@ -371,42 +417,24 @@ class DDIMDiffusionModel(ModelInterface):
         ('ddim' or 'dpmpp_2m', ``eta == 0``).  The defaults are the call as it is without the options, bit for bit and launch for launch.
         UNet1d on the GPU only (``dq_ddim_sample_adaptive``)."""
         eta = self._check_eta(eta)
-        sampler_id, clip = self._check_sampler(sampler, eta, clip_x0)
-        guidance = self._check_guidance(guidance_scale)
-        phi, thr_q, thr_cap = self._check_adaptive(guidance_rescale, threshold_quantile, threshold_max, sampler, eta, clip)
-        if guidance is None:
-            phi = 0.0  # (g = c: m = 1)
-        adaptive = (phi, thr_q, thr_cap) if (phi > 0.0 or thr_q > 0.0) else None
+        sampler_id, clip, guidance, adaptive = SampleOptions(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile,
+                                                             threshold_max).resolve(eta, self)
         stochastic = eta > 0.0 or x_t is None or seed is not None or window_ids is not None
         if sampler_id != 0:
             self._check_decreasing(self.sampler_timesteps(self.num_timesteps, num_steps).tolist())
         on_gpu = ms2_cond is not None and ms1_cond is not None and (x_t.is_cuda if x_t is not None else ms2_cond.is_cuda)
-        if adaptive is not None:
-            if self._native_tfm:
-                raise NotImplementedError("sample: guidance_rescale and threshold_quantile are built for UNet1d (dq_ddim_sample_adaptive); the "
-                                          "per-window statistics step for the CustomTransformer's sampler (dq_tfm_sample) is the follow-up")
-            if not (self.native and on_gpu):
-                raise NotImplementedError("sample: guidance_rescale and threshold_quantile need the native sampler (this package's UNet1d on "
-                                          "the GPU with both conditions); the generic loop is the plain update only")
-            return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
-                                       shape=shape, sampler=sampler_id, clip_x0=clip,
-                                       guidance=None if guidance is None else (guidance, float(null_ms1)), adaptive=adaptive)
-        if guidance is not None:
-            if self._native_tfm:
-                raise NotImplementedError("sample: guidance_scale is built for UNet1d (dq_ddim_sample_guided); guidance for the "
-                                          "CustomTransformer's sampler (dq_tfm_sample) is the follow-up")
-            if not (self.native and on_gpu):
-                raise NotImplementedError("sample: guidance_scale needs the native sampler (this package's UNet1d on the GPU with both "
-                                          "conditions); the generic loop is the unguided update only")
-            return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
-                                       shape=shape, sampler=sampler_id, clip_x0=clip, guidance=(guidance, float(null_ms1)))
-        if on_gpu and self._native_tfm and (self.native_tfm_sampler or stochastic or sampler_id != 0 or return_trajectory):
-            return self._sample_native_tfm(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, seed=seed, window_ids=window_ids,
-                                           shape=shape, sampler=sampler_id, clip_x0=clip)
+        # the route, decided once: UNet1d's loop, the transformer's, or the generic one below
+        unet_only = "adaptive" if adaptive is not None else "guidance" if guidance is not None else None
+        if unet_only and not (self.native and on_gpu):
+            raise NotImplementedError(_UNET_ONLY[unet_only][0 if self._native_tfm else 1])
+        call = dict(seed=seed, window_ids=window_ids, shape=shape, sampler=sampler_id, clip_x0=clip)
         if self.native and on_gpu:
-            # (the default call passes eta=None: dq_ddim_sample, the call as it always was)
-            return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta if stochastic or sampler_id != 0 else None,
-                                       seed=seed, window_ids=window_ids, shape=shape, sampler=sampler_id, clip_x0=clip)
+            # (the default call passes eta=None: dq_ddim_sample, the call as it always was; ``adaptive`` only when it is live)
+            plain = not (unet_only or stochastic or sampler_id != 0)
+            return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=None if plain else eta, guidance=guidance,
+                                       **call, **({} if adaptive is None else {"adaptive": adaptive}))
+        if on_gpu and self._native_tfm and (self.native_tfm_sampler or stochastic or sampler_id != 0 or return_trajectory):
+            return self._sample_native_tfm(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, **call)
         if sampler_id != 0:
             raise NotImplementedError("sample: the 'ddim' and 'dpmpp_2m' samplers and clip_x0 need the native sampler (this package's "
                                       "UNet1d, or its CustomTransformer behind DDIMTransformerAdapter, on the GPU with both "
@@ -472,53 +500,49 @@ class DDIMDiffusionModel(ModelInterface):
         self.last_seed = None if seed_dev is None else int(seed_dev.item()) & (2 ** 64 - 1)  # (what a seed=None call drew)
         return seed_dev, ids_dev
 
-    @staticmethod
-    def _sample_outputs(c2, num_steps, dims, return_trajectory):
-        """[out_x, out_noise, traj_x, traj_eps]: the trajectories (num_steps, *dims), or None"""
-        return [torch.empty_like(c2), torch.empty_like(c2)] + [
+    def _run_loop(self, entry, head, B, tail, x_T, c2, c1, ws, num_steps, dims, return_trajectory, take=None):
+        """What both native calls stage alike, and the call: the int32 timesteps, [out_x, out_noise, traj_x, traj_eps] (the trajectories
+        (num_steps, *dims), or None), the graph flag (off with a trajectory), the 17 arguments both networks' entries take alike -- the
+        schedule up to the batch ``B`` -- between the network's own in front (``head``) and behind (``tail``), and what ``sample``
+        returns.  ``take``: the indices of the list that ``entry`` takes (None: all)."""
+        ts_c = (ctypes.c_int32 * num_steps)(*self.sampler_timesteps(self.num_timesteps, num_steps).to(torch.int32).tolist())
+        outs = [torch.empty_like(c2), torch.empty_like(c2)] + [
             torch.empty((num_steps, *dims), device=c2.device) if return_trajectory else None for _ in range(2)]
+        args = [*head, self._alpha_bars_host(), int(self.num_timesteps), N.ptr(x_T), N.ptr(c2), N.ptr(c1), 1 if self.auto_normalize else 0,
+                N.PRED_TYPES[self.pred_type], ts_c, num_steps, *(N.ptr(v) for v in outs), 1 if (self.use_graph and not return_trajectory) else 0,
+                N.ptr(ws), ws.numel(), B, *tail]
+        N.check(getattr(N.lib(), entry)(*(args if take is None else [args[i] for i in take])), entry)
+        return tuple(outs) if return_trajectory else tuple(outs[:2])
+
+    # Which of the full argument list -- dq_ddim_sample_adaptive's 35 -- each of the U-Net's entries takes: the 22 of dq_ddim_sample, then
+    # (eta, seed, ids), (sampler, clip_x0), the guided flag, (scale, null_ms1), (phi, q, cap, scratch, bytes)
+    _SAMPLE_ENTRY_ARGS = {"dq_ddim_sample": range(22), "dq_ddim_sample_ex": range(25), "dq_ddim_sample_solver": range(27),
+                          "dq_ddim_sample_guided": (*range(27), 28, 29), "dq_ddim_sample_v": range(30), "dq_ddim_sample_adaptive": range(35)}
 
     def _sample_native(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False, eta=None, seed=None, window_ids=None, shape=None,
                        sampler=0, clip_x0=0.0, guidance=None, adaptive=None):
-        """``adaptive`` = (phi, q, cap) (``eta`` a number): ``dq_ddim_sample_adaptive``, ``dq_ddim_sample_v``'s list plus the three and the
-        statistics scratch.  Otherwise ``eta`` None: ``dq_ddim_sample`` (the call as it always was); else ``dq_ddim_sample_ex``; ``sampler`` != 0:
-        ``dq_ddim_sample_solver``; ``guidance`` = (scale, null_ms1) (``eta`` a number): ``dq_ddim_sample_guided`` on the workspace of twice
-        the batch.  The four take one argument list; the later ones append to it.  ``pred_type="v_prediction"``: ``dq_ddim_sample_v``, the
-        same list with a ``guided`` flag in front of the scale, for every one of these forms."""
+        """The U-Net's loop in the library, through the entry that knows what is live -- ``adaptive`` = (phi, q, cap): ``dq_ddim_sample_adaptive``;
+        else ``pred_type="v_prediction"``: ``dq_ddim_sample_v``; else ``eta`` None: ``dq_ddim_sample`` (the call as it always was); else
+        ``guidance`` = (scale, null_ms1): ``dq_ddim_sample_guided`` (on the workspace of twice the batch, as every guided call); else
+        ``sampler`` != 0: ``dq_ddim_sample_solver``; else ``dq_ddim_sample_ex`` -- which takes its part of one list (``_SAMPLE_ENTRY_ARGS``)."""
         net: UNet1d = self.model
         x_T, c2, B, RT, MZ = self._stage_x(x_T, ms2_cond, eta, seed, shape)
         c1 = net._check_inputs(ms1_cond, B, RT).detach().to(torch.float32).contiguous()
         flat = net.read_params()  # (the averaged weights inside ModelInterface.ema_scope())
         ws = net.workspace(2 * B if guidance is not None else B, RT, False)
-        ts = self.sampler_timesteps(self.num_timesteps, num_steps).to(torch.int32)
-        ts_c = (ctypes.c_int32 * num_steps)(*ts.tolist())
-        outs = self._sample_outputs(c2, num_steps, (B, RT, MZ), return_trajectory)
-        args = [net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), self._alpha_bars_host(), int(self.num_timesteps), N.ptr(x_T), N.ptr(c2),
-                N.ptr(c1), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], ts_c, num_steps, *(N.ptr(v) for v in outs),
-                1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws), ws.numel(), B, RT, N.stream_ptr()]
-        entry = "dq_ddim_sample"
-        if self.pred_type == "v_prediction" or adaptive is not None:
-            # one entry for every form of the loop (dq_ddim_sample_solver, which the others above call, is held to refusing the value 2)
+        entry = ("dq_ddim_sample_adaptive" if adaptive is not None else "dq_ddim_sample_v" if self.pred_type == "v_prediction" else
+                 "dq_ddim_sample" if eta is None else "dq_ddim_sample_guided" if guidance is not None else
+                 "dq_ddim_sample_solver" if sampler else "dq_ddim_sample_ex")
+        tail = [RT, N.stream_ptr()]
+        if entry != "dq_ddim_sample":
             seed_dev, ids_dev = self._stage_noise(x_T, eta or 0.0, seed, window_ids, B, c2.device)
-            args += [float(eta or 0.0), N.ptr(seed_dev), N.ptr(ids_dev), int(sampler), float(clip_x0), 0 if guidance is None else 1,
-                     float(guidance[0]) if guidance is not None else 1.0, float(guidance[1]) if guidance is not None else 0.0]
-            entry = "dq_ddim_sample_v"
-            if adaptive is not None:
-                stat = net.stat_scratch(B, RT * MZ)
-                args += [float(adaptive[0]), float(adaptive[1]), float(adaptive[2]), N.ptr(stat), stat.numel()]
-                entry = "dq_ddim_sample_adaptive"
-        elif eta is not None:
-            seed_dev, ids_dev = self._stage_noise(x_T, eta, seed, window_ids, B, c2.device)
-            args += [float(eta), N.ptr(seed_dev), N.ptr(ids_dev)]
-            entry = "dq_ddim_sample_ex"
-            if sampler or guidance is not None:
-                args += [int(sampler), float(clip_x0)]
-                entry = "dq_ddim_sample_solver"
-            if guidance is not None:
-                args += [float(guidance[0]), float(guidance[1])]
-                entry = "dq_ddim_sample_guided"
-        N.check(getattr(N.lib(), entry)(*args), entry)
-        return tuple(outs) if return_trajectory else tuple(outs[:2])
+            tail += [float(eta or 0.0), N.ptr(seed_dev), N.ptr(ids_dev), int(sampler), float(clip_x0), 0 if guidance is None else 1,
+                     *((1.0, 0.0) if guidance is None else (float(guidance[0]), float(guidance[1])))]
+        if adaptive is not None:
+            stat = net.stat_scratch(B, RT * MZ)
+            tail += [*(float(v) for v in adaptive), N.ptr(stat), stat.numel()]
+        return self._run_loop(entry, [net._plan, N.ptr(flat), N.ptr(net.rope_freqs())], B, tail, x_T, c2, c1, ws, num_steps, (B, RT, MZ),
+                              return_trajectory, take=self._SAMPLE_ENTRY_ARGS[entry])
 
     @property
     def _native_tfm(self) -> bool:
@@ -536,15 +560,10 @@ class DDIMDiffusionModel(ModelInterface):
         flat = tfm.read_params(False)  # (the averaged weights inside ModelInterface.ema_scope())
         ws = tfm.sample_workspace(B, S1, S2, num_steps)
         sin, cos, freqs = tfm.tables(max(S1, S2), c2.device)
-        ts_c = (ctypes.c_int32 * num_steps)(*self.sampler_timesteps(self.num_timesteps, num_steps).to(torch.int32).tolist())
-        outs = self._sample_outputs(c2, num_steps, (B, S1, D), return_trajectory)
         seed_dev, ids_dev = self._stage_noise(x_T, eta, seed, window_ids, B, c2.device)
-        N.check(N.lib().dq_tfm_sample(tfm._tfm, N.ptr(flat), N.ptr(sin), N.ptr(cos), N.ptr(freqs), self._alpha_bars_host(), int(self.num_timesteps),
-                                      N.ptr(x_T), N.ptr(c2), N.ptr(c1), 1 if self.auto_normalize else 0, N.PRED_TYPES[self.pred_type], ts_c,
-                                      num_steps, *(N.ptr(v) for v in outs), 1 if (self.use_graph and not return_trajectory) else 0, N.ptr(ws),
-                                      ws.numel(), B, S1, S2, N.stream_ptr(), float(eta), N.ptr(seed_dev), N.ptr(ids_dev), int(sampler),
-                                      float(clip_x0)), "dq_tfm_sample")
-        return tuple(outs) if return_trajectory else tuple(outs[:2])
+        return self._run_loop("dq_tfm_sample", [tfm._tfm, N.ptr(flat), N.ptr(sin), N.ptr(cos), N.ptr(freqs)], B,
+                              [S1, S2, N.stream_ptr(), float(eta), N.ptr(seed_dev), N.ptr(ids_dev), int(sampler), float(clip_x0)],
+                              x_T, c2, c1, ws, num_steps, (B, S1, D), return_trajectory)
 
     # ------------------------------------------------------------------ training objective
     def train_step(self, x_0, ms2_cond=None, ms1_cond=None, noise=None, ms1_loss_weight=0.0, t=None):

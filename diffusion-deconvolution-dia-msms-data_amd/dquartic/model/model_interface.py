@@ -800,18 +800,7 @@ class ModelInterface(object):
             per_window = torch.cat(rows).cpu().numpy()
             out.update({k: self._global_mean(v) for k, v in E.aggregate_metrics(per_window).items()})
             out.update(num_steps=int(num_steps), eta=float(eta), per_window=per_window)
-            if sampler != "reference":
-                out["sampler"] = str(sampler)
-            if clip_x0 is not None:
-                out["clip_x0"] = float(clip_x0)
-            if guidance_scale is not None:
-                out.update(guidance_scale=float(guidance_scale), null_ms1=float(null_ms1))
-            if guidance_rescale:
-                out["guidance_rescale"] = float(guidance_rescale)
-            if threshold_quantile is not None:
-                out["threshold_quantile"] = float(threshold_quantile)
-            if threshold_max is not None:
-                out["threshold_max"] = float(threshold_max)
+            out.update(_reported_options(sampler_kw))
         if target_w:  # batches that carry their weights (ResidentMixLoader): the loss by the target's share of its mixture
             tw = torch.cat(target_w).cpu().numpy().astype(np.float32)
             if len(tw) != first:
@@ -1067,22 +1056,14 @@ class ModelInterface(object):
 
 def _sampler_kwargs(sampler, clip_x0, guidance_scale=None, null_ms1=0.0, guidance_rescale=0.0, threshold_quantile=None, threshold_max=None):
     """The step-consistent-sampler, guidance and per-window options as keyword arguments of ``sample`` -- none at the defaults, so that a
-    subclass whose ``sample`` predates them is still called as it always was."""
-    kw = {}
-    if sampler != "reference":
-        kw["sampler"] = sampler
-    if clip_x0 is not None:
-        kw["clip_x0"] = clip_x0
-    if guidance_scale is not None:
-        kw["guidance_scale"] = guidance_scale
-        kw["null_ms1"] = null_ms1
-    if guidance_rescale:
-        kw["guidance_rescale"] = guidance_rescale
-    if threshold_quantile is not None:
-        kw["threshold_quantile"] = threshold_quantile
-    if threshold_max is not None:
-        kw["threshold_max"] = threshold_max
-    return kw
+    subclass whose ``sample`` predates them is still called as it always was (the rule is ``SampleOptions.non_default``)."""
+    from .model import SampleOptions  # (that module imports this one)
+    return SampleOptions(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max).non_default()
+
+
+def _reported_options(sampler_kw):
+    """``_sampler_kwargs``' result as ``evaluate`` reports it: the same keys, plain str / float values"""
+    return {k: str(v) if k == "sampler" else float(v) for k, v in sampler_kw.items()}
 
 
 def _wandb():

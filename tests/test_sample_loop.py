@@ -7,10 +7,14 @@ tests do not see is the two in one process, one after the other:
 Models: test_stochastic_sampler's U-Net at batch 2 and test_tfm_sample's "two_layers" transformer, 3 steps each.
 
 Without a GPU: which entry ``DDIMDiffusionModel._sample_native`` reaches for (eta, sampler), over a recorder in place of the library -- the
-three take one argument list (the first 22 arguments), which is what lets test_sample_ex_eta0_is_dq_ddim_sample compare two entries."""
+three take one argument list (the first 22 arguments), which is what lets test_sample_ex_eta0_is_dq_ddim_sample compare two entries; and
+likewise for guidance, the v objective and the per-window options, each reaching its entry with exactly its list.  The options that are
+not at their defaults: one rule (``SampleOptions.non_default``) under ``_sampler_kwargs``, ``evaluate``'s report and the command line."""
 import ctypes
 import gc
+import inspect
 
+import numpy as np
 import pytest
 import torch
 
@@ -101,6 +105,124 @@ def _plain(v):
     if isinstance(v, ctypes.Array):
         return (type(v)._type_, list(v))
     return v
+
+
+def _host_model(monkeypatch, pred="x0"):
+    """test_entry_choice's stand-ins once more: the recorder in place of the library, an Identity carrying what _sample_native asks of
+    UNet1d (the statistics scratch too), host tensors at B, RT, MZ = 2, 4, 8.  ``pred``: set on the built model, whose constructor
+    takes the v objective for a UNet1d only"""
+    from dquartic import _native as N
+    from dquartic.model.model import DDIMDiffusionModel
+
+    rec = _Recorder(N.lib)
+    monkeypatch.setattr(N, "lib", lambda: rec)
+    monkeypatch.setattr(N, "stream_ptr", lambda: ctypes.c_void_p(0x5EED))
+    g = torch.Generator().manual_seed(3)
+    flat, ws, rope, stat = torch.rand(16, generator=g), torch.empty(64), torch.rand(4, generator=g), torch.empty(32)
+    net = torch.nn.Identity()
+    net._plan = ctypes.c_void_p(0xABC0)
+    net._check_inputs = lambda c, b, rt: c[..., None]
+    net.read_params, net.rope_freqs, net.workspace, net.stat_scratch = (lambda: flat), (lambda: rope), (lambda b, rt, training: ws), (lambda b, per: stat)
+    dm = DDIMDiffusionModel(model_class=net, num_timesteps=50, pred_type="x0", device="cpu")
+    dm.pred_type = pred
+    inputs = torch.randn(2, 4, 8, generator=g), torch.rand(2, 4, 8, generator=g), torch.rand(2, 4, generator=g)
+    return rec, dm, inputs, stat
+
+
+def _shared_22(args):
+    """the first 22 arguments as test_entry_choice compares them: all but the two outputs a call allocates"""
+    return [_plain(args[i]) for i in range(22) if i not in (12, 13)]
+
+
+def test_entry_choice_guided_and_per_window(monkeypatch):
+    """guidance -> dq_ddim_sample_guided (+ scale, null_ms1: 29 arguments); a live per-window option -> dq_ddim_sample_adaptive (35:
+    dq_ddim_sample_v's list, then phi, q, cap, scratch, its size), guided or not; the first 22 are the default call's"""
+    rec, dm, inputs, stat = _host_model(monkeypatch)
+    INF = float("inf")
+    keep = [dm._sample_native(*inputs, STEPS),
+            dm._sample_native(*inputs, STEPS, eta=0.0, sampler=1, clip_x0=1.5, guidance=(3.0, 0.25)),
+            dm._sample_native(*inputs, STEPS, eta=0.0, guidance=(0.5, 0.0)),
+            dm._sample_native(*inputs, STEPS, eta=0.0, sampler=1, clip_x0=1.5, guidance=(3.0, 0.25), adaptive=(0.7, 0.5, 2.0)),
+            dm._sample_native(*inputs, STEPS, eta=0.0, sampler=2, adaptive=(0.0, 0.5, INF))]
+    scratch = [("ptr", stat.data_ptr()), stat.numel()]
+    want = [("dq_ddim_sample", []),
+            ("dq_ddim_sample_guided", [0.0, None, None, 1, 1.5, 3.0, 0.25]),
+            ("dq_ddim_sample_guided", [0.0, None, None, 0, 0.0, 0.5, 0.0]),
+            ("dq_ddim_sample_adaptive", [0.0, None, None, 1, 1.5, 1, 3.0, 0.25, 0.7, 0.5, 2.0] + scratch),
+            ("dq_ddim_sample_adaptive", [0.0, None, None, 2, 0.0, 0, 1.0, 0.0, 0.0, 0.5, INF] + scratch)]
+    assert len(rec.calls) == len(want) == len(keep)
+    for (name, args), (entry, tail) in zip(rec.calls, want):
+        assert name == entry and len(args) == 22 + len(tail), (name, len(args))
+        assert [_plain(v) for v in args[22:]] == tail, name
+        assert _shared_22(args) == _shared_22(rec.calls[0][1]), name
+    assert [len(a) for _, a in rec.calls] == [22, 29, 29, 35, 35]
+
+
+def test_entry_choice_v_prediction(monkeypatch):
+    """a v_prediction model reaches dq_ddim_sample_v with 30 arguments in all four forms -- plain, eta, sampler, guided: the solver's
+    list, the guided flag, then the scale and null_ms1 (1.0, 0.0 unguided); a seed travels as the device word, and is recorded"""
+    from dquartic import _native as N
+
+    rec, dm, inputs, _ = _host_model(monkeypatch, "v_prediction")
+    keep = [dm._sample_native(*inputs, STEPS), dm._sample_native(*inputs, STEPS, eta=0.0), dm._sample_native(*inputs, STEPS, eta=0.0, sampler=2),
+            dm._sample_native(*inputs, STEPS, eta=0.0, sampler=1, clip_x0=1.5, guidance=(3.0, 0.25))]
+    tails = [[0.0, None, None, 0, 0.0, 0, 1.0, 0.0], [0.0, None, None, 0, 0.0, 0, 1.0, 0.0], [0.0, None, None, 2, 0.0, 0, 1.0, 0.0],
+             [0.0, None, None, 1, 1.5, 1, 3.0, 0.25]]
+    assert len(rec.calls) == len(keep) == 4
+    for (name, args), tail in zip(rec.calls, tails):
+        assert name == "dq_ddim_sample_v" and len(args) == 30
+        assert [_plain(v) for v in args[22:]] == tail
+        assert _shared_22(args) == _shared_22(rec.calls[0][1]) and args[9] == N.PRED_TYPES["v_prediction"]
+    dm._sample_native(*inputs, STEPS, eta=0.5, seed=7)
+    args = rec.calls[-1][1]
+    assert len(args) == 30 and args[22] == 0.5 and isinstance(args[23], ctypes.c_void_p) and args[24] is None and dm.last_seed == 7
+
+
+def test_one_rule_for_the_options_that_are_not_at_their_defaults():
+    """over every subset of the seven options at a live value: SampleOptions.non_default, _sampler_kwargs (predict / evaluate /
+    _predict_one_batch), the keys evaluate reports and the ``sample_kw`` that ``cli.sampling_options`` hands cli.evaluate and
+    cli.deconvolve (which forward it as it is) are one set with the same values -- an option at its default is absent, null_ms1 goes with
+    guidance_scale and never without it"""
+    import dataclasses
+    import itertools
+
+    from dquartic import cli
+    from dquartic.model.model import SampleOptions
+    from dquartic.model.model_interface import _reported_options, _sampler_kwargs
+
+    default = dict(sampler="reference", clip_x0=None, guidance_scale=None, null_ms1=0.0, guidance_rescale=0.0, threshold_quantile=None,
+                   threshold_max=None)
+    live = dict(sampler="ddim", clip_x0=1.5, guidance_scale=3.0, null_ms1=0.25, guidance_rescale=0.7, threshold_quantile=0.9, threshold_max=4.0)
+    assert [f.name for f in dataclasses.fields(SampleOptions)] == list(default) and dataclasses.asdict(SampleOptions()) == default
+    command = cli.sampling_options(lambda **kw: kw)  # what a command body is called with: the seven options gone, sample_kw in their place
+    for on in itertools.product((False, True), repeat=len(default)):
+        opts = {k: (live if o else default)[k] for k, o in zip(default, on)}
+        want = {k: opts[k] for k, o in zip(default, on) if o and k != "null_ms1"}
+        if "guidance_scale" in want:
+            want["null_ms1"] = opts["null_ms1"]
+        assert SampleOptions(**opts).non_default() == want, opts
+        assert _sampler_kwargs(opts["sampler"], opts["clip_x0"], opts["guidance_scale"], opts["null_ms1"], opts["guidance_rescale"],
+                               opts["threshold_quantile"], opts["threshold_max"]) == want, opts
+        assert _sampler_kwargs(**opts) == want
+        shown = _reported_options(want)
+        assert shown == want and all(type(v) is (str if k == "sampler" else float) for k, v in shown.items())
+        assert command(eta=0.5, seed=3, use_ema=None, **opts) == dict(eta=0.5, seed=3, use_ema=None, sample_kw=want), opts
+    # evaluate reports plain values whatever the Python caller passed: an int clamp, a numpy scale
+    shown = _reported_options(_sampler_kwargs("ddim", 2, np.float32(3.0), 1))
+    assert shown == dict(sampler="ddim", clip_x0=2.0, guidance_scale=3.0, null_ms1=1.0) and all(type(shown[k]) is float for k in list(shown)[1:])
+    # the command line declares the options once, at the record's defaults (what it forwards at its defaults is nothing), and both
+    # commands are bodies behind that decorator: they take sample_kw and none of the seven
+    for cmd in (cli.evaluate, cli.deconvolve):
+        params = {o.name: o for o in cmd.params}
+        body = inspect.signature(cmd.callback.__wrapped__).parameters
+        assert "sample_kw" in body and not set(default) & set(body), cmd.name
+        assert inspect.getsource(cmd.callback.__wrapped__).count("**sample_kw") == 1, cmd.name
+        assert {k: params[k].default for k in default} == default, cmd.name
+        assert [o.name for o in cmd.params].count("eta") == 1 and params["eta"].default == 0.0 and params["seed"].default == 0
+    source = inspect.getsource(cli)
+    for flag in ("--eta", "--sampler", "--clip-x0", "--guidance-scale", "--null-ms1", "--guidance-rescale", "--threshold-quantile",
+                 "--threshold-max", "--seed"):
+        assert source.count(f'click.option("{flag}"') == 1, flag
 
 
 def test_entry_choice(monkeypatch):
