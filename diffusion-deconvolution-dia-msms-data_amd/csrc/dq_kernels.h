@@ -112,6 +112,21 @@ struct WinQuantile {
   float* q_out = nullptr; float* tab = nullptr; bool init_m = false;
 };
 int launch_win_quantile(const WinQuantile& qa, int B, int64_t per, const WinStatScratch& S, hipStream_t s);
+// ---- k_group.hip: mixture consistency over the P members of G groups, between the forward and the update.  The batch
+// is member-major (member p of group g: row p * G + g of x_t / net / x0_out, G * per floats apart); mix: row g of the caller's ms2_cond.
+// x0_out (may alias net) receives the projected x0 estimate of every member, formed from (x_t, net) under objective `pred` with row [sa, sb]
+// of coef (step_ptr: the row the device-side step counter names); mode: DQ_CONSIST_*; 0 < strength <= 1.  Any 4-byte aligned tensors;
+// 16-byte accesses iff per % 4 == 0 and every tensor is 16-byte aligned.
+struct GroupProject {
+  const float* x_t = nullptr; const float* net = nullptr; float* x0_out = nullptr; const float* mix = nullptr;
+  const float* coef = nullptr; const int* step_ptr = nullptr;
+  int pred = 0, normalize = 0;  // pred: DQ_PRED_*, what `net` is
+  int G = 0, P = 0; int64_t per = 0;
+  int mode = 0; float strength = 1.f;
+};
+bool group_mode_ok(int mode);
+bool group_strength_ok(float strength);  // (false for NaN)
+int launch_group_project(const GroupProject& a, hipStream_t s);
 // ---- k_noise.hip: out (B, per_window) = the normals of draw index `draw` (the generator of the STOCHASTIC update above)
 int launch_randn(float* out, const int64_t* ids, const uint64_t* seed_dev, int draw, int B, int64_t per_window, hipStream_t s);
 // ---- k_cond_drop.hip: out (B, per) = in with window b replaced by null_value iff the third Philox word of (seed, id, draw) < floor(p 2^32)

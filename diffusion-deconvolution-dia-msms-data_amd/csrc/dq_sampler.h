@@ -12,7 +12,8 @@ namespace dq {
 
 // One sampling call as its entry received it.  who: the entry's own name, the prefix of every refusal; allow_v: DQ_PRED_V is a known
 // objective of this entry (the pred_type of the older ones names the reference's two).  guided: the scale w of
-// g = u + w (c - u) and the null condition's raw MS1 value; adaptive (section 38): rescaled guidance at phi, thresholding at `quantile` (0: off)
+// g = u + w (c - u) and the null condition's raw MS1 value; adaptive (section 38): rescaled guidance at phi, thresholding at `quantile` (0: off);
+// consistency (section 40; DQ_CONSIST_*, 0: off): the batch is B / group_size groups of group_size members, projected at `strength`
 struct SampleCall {
   const char* who = "";
   bool allow_v = false;
@@ -29,6 +30,7 @@ struct SampleCall {
   int sampler = 0; float clip_x0 = 0.f;
   bool guided = false; float w = 1.f, null_ms1 = 0.f;
   bool adaptive = false; double phi = 0.0; float quantile = 0.f, cap = 0.f; void* stat_scratch = nullptr; int64_t stat_bytes = 0;
+  int group_size = 1, consistency = 0; float strength = 1.f;
   bool graph() const { return use_graph && !traj_x && !traj_eps; }  // one step captured and replayed; otherwise the eager steps
 };
 
@@ -43,13 +45,28 @@ struct StepStats {
   bool on() const { return rescale || q > 0.f; }
 };
 
+// The mixture-consistency pass of a step (k_group.hip), run in place on the network output between the forward and
+// the update, which then runs in its x0-objective form: P members per group, the mode (DQ_CONSIST_*; 0: off) and the blend; pred: the
+// network's objective, what the pass reads the output as; mix: the call's ms2_cond at the address the forward reads it from
+struct StepGroup {
+  int P = 1, mode = 0, pred = 0, normalize = 0;
+  float strength = 1.f;
+  const float* mix = nullptr;
+  bool on() const { return mode != 0; }
+};
+
 // What a call's options select.  clip_x0: the clamp as the kernels take it (0: off); clip: x0 is clamped by clip_x0 or thresholded --
-// either way the Solver family runs and the derived eps is the trajectory's.  stats: the per-window step (S is the entry's to carve)
-struct SamplerChoice { StepUpdate kind = StepUpdate::DDIM; bool sto = false, clip = false; float clip_x0 = 0.f; int pred = 0; StepStats stats; };
+// either way the Solver family runs and the derived eps is the trajectory's.  stats: the per-window step (S is the entry's to carve);
+// group: the consistency pass (sample_check_group's to fill; mix is the entry's to set)
+struct SamplerChoice { StepUpdate kind = StepUpdate::DDIM; bool sto = false, clip = false; float clip_x0 = 0.f; int pred = 0; StepStats stats; StepGroup group; };
 // Every refusal that does not need the network's shape, in one order, before anything touches the device: a null argument (net_args_ok:
 // the network's own pointers are there), eta, the sampler and what it combines with (thresholding is refused where clip_x0 is and selects
 // its update), the decreasing timesteps, the seed, the objective, the guidance scale, the per-window options' ranges and scratch pointer
 int sample_check(const SampleCall& c, bool net_args_ok, SamplerChoice* out);
+// The refusals of a call over groups, made behind every other one its entry makes before anything touches the device (sample_check's, the
+// batch and step counts): group_size outside [1, 8], B % group_size != 0, an unknown mode, strength outside (0, 1] or NaN.
+// Fills out->group (off, and nothing refused, at consistency 0)
+int sample_check_group(const SampleCall& c, SamplerChoice* out);
 // Tables up, x_T in place: the coefficient rows formed on the host and copied to coef_dev (4 per step) and extra_dev (sigma, or the solver's
 // c1: 1 per step; nullable), the stream synchronised (a caller's pageable copy queued in front is done too), x_T copied to xa or drawn (draw 0)
 int sample_begin(const SampleCall& c, const SamplerChoice& sc, int64_t per, float* coef_dev, float* extra_dev, float* xa);
@@ -68,6 +85,7 @@ struct StepUpdateArgs {
   bool guided = false;
   float w = 1.f;
   StepStats stats;
+  StepGroup group;  // on: `pred` above is DQ_PRED_X0, the form the update takes over the projected estimate
 };
 
 // One step's network forward on stream s, the one thing a call brings of its own: the network output of x into net_out, at timestep and

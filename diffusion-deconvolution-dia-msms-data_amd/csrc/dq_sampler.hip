@@ -46,10 +46,19 @@ StepUpdateLaunch update_launch(StepUpdate kind, int pred, const float* x_t, cons
 // when it is not the network output itself; fused: the deterministic update went with the head launch (StepIO::fused_update), nothing is
 // left to do.  Guided (u.guided): net_out is the conditional output, net_u the unconditional one, x_mirror (nullable) receives x_out's values
 // as well (the unconditional half's x of the next forward), and eps_out (nullable) the guided eps; never fused (the head launch of window b
-// cannot see the output of window B + b).  Both are null otherwise.  Nothing is refused per step: the call's checks are made before the loop.
-int launch_step_update(const StepUpdateArgs& u, const float* x, const float* net_out, const float* net_u, float* x_out, float* x_mirror,
+// cannot see the output of window B + b).  Both are null otherwise.  Over groups (u.group.on()) net_out is first rewritten in place by the
+// consistency pass.  Nothing is refused per step: the call's checks are made before the loop.
+int launch_step_update(const StepUpdateArgs& u, const float* x, float* net_out, const float* net_u, float* x_out, float* x_mirror,
                        float* eps_out, int row, const int* step_ptr, const StepNoise& z, bool fused, hipStream_t s) {
   if (fused && u.kind == StepUpdate::DDIM && !u.guided) return 0;  // (the head launch has done it; a guided update never rides there)
+  if (u.group.on()) {
+    // the consistency pass: the network output becomes the group's projected x0 estimate in place; u.pred is DQ_PRED_X0
+    const StepGroup& g = u.group;
+    GroupProject p;
+    p.x_t = x; p.net = net_out; p.x0_out = net_out; p.mix = g.mix; p.coef = u.coef + 4 * row; p.step_ptr = step_ptr;
+    p.pred = g.pred; p.normalize = g.normalize; p.G = u.B / g.P; p.P = g.P; p.per = u.per; p.mode = g.mode; p.strength = g.strength;
+    DQ_TRY(launch_group_project(p, s));
+  }
   StepUpdateLaunch a = update_launch(u.kind, u.pred, x, net_out, net_u, x_out, x_mirror, u.hist, eps_out, u.coef + 4 * row, u.extra + row, z, u.B, u.per);
   a.clip = u.clip; a.w = u.w; a.step_ptr = step_ptr;
   if (u.stats.on()) {
@@ -183,6 +192,19 @@ int sample_check(const SampleCall& c, bool net_args_ok, SamplerChoice* out) {
   return 0;
 }
 
+int sample_check_group(const SampleCall& c, SamplerChoice* out) {
+  const std::string w(c.who);
+  out->group = StepGroup{};
+  if (c.consistency == DQ_CONSIST_NONE) return 0;
+  DQ_REQUIRE(c.group_size >= 1 && c.group_size <= DQ_GROUP_MAX, w + ": group_size must be 1..8");
+  DQ_REQUIRE(c.B % c.group_size == 0, w + ": the batch must be a whole number of groups (B % group_size == 0)");
+  DQ_REQUIRE(group_mode_ok(c.consistency), w + ": unknown consistency mode");
+  DQ_REQUIRE(group_strength_ok(c.strength), w + ": consistency strength must satisfy 0 < strength <= 1");
+  StepGroup& g = out->group;
+  g.P = c.group_size; g.mode = c.consistency; g.strength = c.strength; g.pred = out->pred; g.normalize = c.normalize;
+  return 0;
+}
+
 int sample_begin(const SampleCall& c, const SamplerChoice& sc, int64_t per, float* coef_dev, float* extra_dev, float* xa) {
   hipStream_t s = c.stream;
   // coefficient table, fp32 like the reference, and sigma (eta > 0) or c1 (the solver) per step
@@ -228,6 +250,8 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
   }
   DQ_REQUIRE(B > 0 && RT > 0 && num_steps >= 1 && num_steps <= 1024, wh + ": need B, RT > 0 and 1 <= num_steps <= 1024");
   DQ_REQUIRE(!g || B <= INT32_MAX / 2, wh + ": batch too large");
+  DQ_TRY(sample_check_group(q, &sc));  // (the last refusals made on the host alone: ensure_arena brings the plan's tables to the device)
+  const bool grp = sc.group.on();
   const int NB = g ? 2 * B : B;  // the windows of the arena and of the forward
   DQ_TRY(ensure_arena(plan, NB, RT));
   const Arena& a = plan->arena;
@@ -240,8 +264,9 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
   const int64_t per = (int64_t)RT * plan->plan.mz, n = B * per;
   const int64_t n1 = (int64_t)B * RT * plan->plan.ms1_channels;  // the caller's MS1
   const float cm = q.normalize ? 2.f : 1.f, ca = q.normalize ? -1.f : 0.f;
-  // the head launch takes the update when it can (StepIO::x_t); the others, and every guided one, run behind the forward
-  const bool in_head = sc.kind == StepUpdate::DDIM && !g;
+  // the head launch takes the update when it can (StepIO::x_t); the others, every guided one and every one over groups (the pass comes
+  // between the two) run behind the forward
+  const bool in_head = sc.kind == StepUpdate::DDIM && !g && !grp;
   float* xa = c.w(a.xa);
   DQ_TRY(sample_begin(q, sc, per, c.w(a.coef), in_head ? nullptr : c.w(a.sigma), xa));
   if (g) DQ_HIP_OK(hipMemcpyAsync(xa + n, xa, sizeof(float) * n, hipMemcpyDeviceToDevice, s));  // the unconditional half starts from the same x_T
@@ -277,12 +302,16 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
     *fused = io.fused_update;
     return rc;
   };
-  const SampleLoop loop{forward, StepUpdateArgs{sc.kind, c.w(a.coef), c.w(a.sigma), c.w(a.xb), sc.clip_x0, sc.pred, B, per, g, g ? q.w : 1.f, sc.stats},
+  sc.group.mix = c2;  // the group's mixture: row g of the tensor the network reads
+  // (over groups the update runs in its x0-objective form over the projected estimate; the pass reads the output by the network's objective)
+  const SampleLoop loop{forward, StepUpdateArgs{sc.kind, c.w(a.coef), c.w(a.sigma), c.w(a.xb), sc.clip_x0, grp ? DQ_PRED_X0 : sc.pred, B, per, g,
+                                                g ? q.w : 1.f, sc.stats, sc.group},
                         xa, c.w(a.eps), sc.clip, num_steps, q.ms2_cond, q.out_x, q.out_noise, q.normalize};
   StepKey key;
   key.params = params; key.rope = rope_freqs; key.ws = q.workspace; key.B = B; key.RT = RT; key.normalize = q.normalize; key.pred = q.pred;
   key.update = sc.kind; key.clip = sc.clip_x0; key.guidance = g ? q.w : -1.f; key.opt_epoch = options_epoch();
   if (sc.stats.on()) { key.rescale = sc.stats.rescale ? sc.stats.phi : 0.0; key.quantile = sc.stats.q; key.cap = sc.stats.cap; key.stat_scratch = q.stat_scratch; }
+  if (grp) { key.group_size = sc.group.P; key.consistency = sc.group.mode; key.strength = sc.group.strength; }
   const StepStage stage{reinterpret_cast<int*>(c.w(a.step)), reinterpret_cast<uint64_t*>(c.w(a.seed_stage)), reinterpret_cast<int64_t*>(c.w(a.ids_stage))};
   bool captured;
   const int rc = sample_run(q, loop, sc.sto, plan->step, plan->step.exec && plan->step_key == key, stage, &captured);
@@ -453,6 +482,23 @@ int dq_ddim_sample_v(dq_plan* plan, const float* params, const float* rope_freqs
   q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
   q.allow_v = true;
   q.guided = guided != 0; q.w = guidance_scale; q.null_ms1 = null_ms1;
+  return unet_sample(plan, params, rope_freqs, q);
+}
+
+// ---- joint sampling of a window's precursors
+int dq_ddim_sample_joint(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                         const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                         const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                         int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                         const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, int group_size, int consistency,
+                         float strength) {
+  SampleCall q;  q.who = "dq_ddim_sample_joint";
+  q.alpha_bars_host = alpha_bars_host; q.T = num_timesteps; q.x_T = x_T; q.ms2_cond = ms2_cond; q.ms1_cond = ms1_cond; q.normalize = auto_normalize;
+  q.pred = pred_type; q.ts = timesteps_host; q.num_steps = num_steps; q.out_x = out_x; q.out_noise = out_noise; q.traj_x = traj_x; q.traj_eps = traj_eps;
+  q.use_graph = use_graph; q.workspace = workspace; q.workspace_bytes = workspace_bytes; q.B = B; q.RT = RT; q.stream = (hipStream_t)stream;
+  q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
+  q.allow_v = true;
+  q.group_size = group_size; q.consistency = consistency; q.strength = strength;
   return unet_sample(plan, params, rope_freqs, q);
 }
 

@@ -70,11 +70,14 @@ struct StepKey {
   float guidance = -1.f;
   // the per-window statistics step: phi, quantile, cap by value and the scratch by address (all 0: none)
   double rescale = 0.0; float quantile = 0.f, cap = 0.f; const void* stat_scratch = nullptr;
+  // the consistency pass: members per group, mode (0: none) and blend by value
+  int group_size = 1, consistency = 0; float strength = 1.f;
   unsigned opt_epoch = 0;
   bool operator==(const StepKey& o) const {
     return params == o.params && rope == o.rope && ws == o.ws && B == o.B && RT == o.RT && normalize == o.normalize && pred == o.pred &&
            update == o.update && clip == o.clip && guidance == o.guidance && rescale == o.rescale && quantile == o.quantile && cap == o.cap &&
-           stat_scratch == o.stat_scratch && opt_epoch == o.opt_epoch;
+           stat_scratch == o.stat_scratch && group_size == o.group_size && consistency == o.consistency && strength == o.strength &&
+           opt_epoch == o.opt_epoch;
   }
 };
 

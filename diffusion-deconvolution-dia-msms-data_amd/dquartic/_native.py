@@ -12,6 +12,8 @@ ABI_VERSION = 12  # DQ_ABI_VERSION of include/dq_hip.h this table was written ag
 PRED_TYPES = {"eps": 0, "x0": 1, "v_prediction": 2}  # DQ_PRED_EPS / DQ_PRED_X0 / DQ_PRED_V
 SAMPLERS = {"reference": 0, "ddim": 1, "dpmpp_2m": 2}  # DQ_SAMPLER_*
 UPDATE_KINDS = {"ddim": 0, "stochastic": 1, "solver_1": 2, "solver_2m": 3}  # DQ_UPDATE_* (dq_guided_update)
+CONSISTENCY_MODES = {"bound": 1, "sum": 2}  # DQ_CONSIST_BOUND / DQ_CONSIST_SUM (dq_group_project, dq_ddim_sample_joint)
+GROUP_MAX = 8  # DQ_GROUP_MAX
 PRECISIONS = {"fp32": 0, "bf16x3": 1}  # DQ_PRECISION_FP32 / DQ_PRECISION_BF16X3
 FINAL_ACTS = {"identity": 0, "softplus": 1}  # DQ_FINAL_IDENTITY / DQ_FINAL_SOFTPLUS
 RES_FWD_FORMS = ("rt", "level", "v4", "unfused")  # DQ_RES_FWD_* (index = value)
@@ -109,6 +111,10 @@ PROTOTYPES = {
                                         POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
                                         c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_int, c_float, c_float, c_double, c_float, c_float,
                                         c_void_p, c_int64]),
+    "dq_group_project": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_int64, c_int, c_float, c_void_p]),
+    "dq_ddim_sample_joint": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                     POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
+                                     c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_int, c_int, c_float]),
     "dq_ms1_cond_drop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_float, c_int, c_int64, c_void_p]),
     "dq_ddim_sample_guided": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                       POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,

@@ -2,7 +2,8 @@
 ``dquartic train CONFIG [--parquet_directory --ms2-data-path --ms1-data-path --batch-size --checkpoint-path --use-wandb
 --threads]`` and ``dquartic generate-config PATH``; ``dquartic evaluate CONFIG --checkpoint PATH`` (this build) prints held-out loss and
 reconstruction metrics; ``dquartic deconvolve CONFIG --checkpoint PATH --ms2 RUN.npy --ms1 RUN.npy --out OUT.npz --window W`` (this build)
-deconvolves whole chromatograms.  A ``data.mixture`` block in the config (absent by default) makes ``train`` and ``evaluate`` form K-component
+deconvolves whole chromatograms (``--joint``: the P precursors of one run as groups under mixture consistency,
+section 40).  A ``data.mixture`` block in the config (absent by default) makes ``train`` and ``evaluate`` form K-component
 mixtures with drawn weights on the GPU (``ResidentMixLoader``).  ``generate-train-data`` (offline sqMass ETL) is outside the hot path
 and reports so.  Under ``torch.distributed.run`` (WORLD_SIZE > 1) training is data-parallel: one process per GPU, the
 dataset is sharded by rank and the flat gradient is all-reduced over RCCL."""
@@ -16,7 +17,7 @@ import click
 import torch
 from torch.utils.data import DataLoader
 
-from .model.model import DDIMDiffusionModel, SampleOptions
+from .model.model import DDIMDiffusionModel, JointSampleOptions
 from .model.unet1d import UNet1d
 from .utils.config_loader import generate_train_config, load_train_config, mixture_config, validation_config
 
@@ -231,16 +232,22 @@ _SAMPLING_OPTIONS = (
                  help="Dynamic thresholding: clamp every step's x0 estimate to the window's Q-quantile of |x0| (never below --clip-x0, or 1) and "
                       "scale it back to that floor (ddim / dpmpp_2m, eta 0)"),
     click.option("--threshold-max", default=None, type=float, help="Upper bound of the dynamic threshold (needs --threshold-quantile)"),
+    click.option("--consistency", default=None, type=click.Choice(["bound", "sum"]),
+                 help="Mixture consistency over the members of a group (deconvolve --joint): their positive parts never exceed the observed "
+                      "window (bound), or add up to it (sum)"),
+    click.option("--consistency-strength", default=1.0, type=float, help="Blend L in (0, 1] between each step's estimate and its projection"),
     click.option("--seed", default=0, type=int, help="Seed of x_T, of the sampling noise and of the evaluation noise"),
 )
 
 
 def sampling_options(command):
-    """Declares ``_SAMPLING_OPTIONS`` on ``command`` and hands it ``eta``, ``seed`` and, in place of the seven options of ``SampleOptions``
-    (taken by name), ``sample_kw``: the ones that are not at their defaults, as ``evaluate`` / ``deconvolve_run`` / ``sample`` take them"""
+    """Declares ``_SAMPLING_OPTIONS`` on ``command`` and hands it ``eta``, ``seed`` and, in place of the options of ``JointSampleOptions``
+    (taken by name; one that is not declared, as ``group_size``, stays at its default), ``sample_kw``: the ones that are not at their
+    defaults, as ``evaluate`` / ``deconvolve_run`` / ``deconvolve_run_joint`` / ``sample`` take them"""
     @functools.wraps(command)
     def with_sample_kw(**kw):
-        return command(sample_kw=SampleOptions(**{f.name: kw.pop(f.name) for f in dataclasses.fields(SampleOptions)}).non_default(), **kw)
+        fields = dataclasses.fields(JointSampleOptions)
+        return command(sample_kw=JointSampleOptions(**{f.name: kw.pop(f.name, f.default) for f in fields}).non_default(), **kw)
 
     for option in reversed(_SAMPLING_OPTIONS):
         with_sample_kw = option(with_sample_kw)
@@ -259,6 +266,9 @@ def evaluate(config_path, checkpoint, num_steps, eta, seed, sample_kw, use_ema, 
     """Held-out loss (and, with --num-steps, reconstruction metrics) of a checkpoint on the config's data.validation set.  The pairs of
     that set come from the block's own seed, not from --seed: runs that differ in --seed, --eta, --num-steps or --use-ema score the same
     pairs.  Without a validation block the config's data section is scored, with a notice.  Prints one JSON line."""
+    if "consistency" in sample_kw or "consistency_strength" in sample_kw:
+        raise click.ClickException("--consistency: groups inside evaluate are not implemented (follow-up: a mixture loader that carries every "
+                                   "member's MS1); use deconvolve --joint")
     if not torch.cuda.is_available():
         raise click.ClickException("no GPU visible: this build runs the hot path on MI355X only (no CPU fallback)")
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -295,23 +305,38 @@ def evaluate(config_path, checkpoint, num_steps, eta, seed, sample_kw, use_ema, 
 @click.option("--taper", default="hann", type=click.Choice(["hann", "uniform"]), help="Weight of a window's scans where windows overlap")
 @click.option("--batch-size", default=32, type=int, help="Windows sampled per call (the result does not depend on it)")
 @click.option("--num-steps", default=1000, type=int, help="Sampling steps per window")
+@click.option("--joint", is_flag=True, default=False,
+              help="One run (--ms2 (RT_total, MZ)) with the MS1 traces of its P co-eluting precursors (--ms1 (P, RT_total) or (P, RT_total, M1)), "
+                   "sampled as groups under --consistency (default: bound); pred and overlap_var gain a leading P axis")
 @sampling_options
 @click.option("--use-ema/--no-use-ema", default=None, help="Sample from the averaged weights (default: when the checkpoint has an average)")
-def deconvolve(config_path, checkpoint, ms2_path, ms1_path, out_path, window, step, taper, batch_size, num_steps, eta, seed, sample_kw, use_ema):
+def deconvolve(config_path, checkpoint, ms2_path, ms1_path, out_path, window, step, taper, batch_size, num_steps, joint, eta, seed, sample_kw,
+               use_ema):
     """Deconvolve whole chromatograms with a checkpoint: every run is cut into overlapping windows, each window normalised on its own and
     sampled, and the predictions stitched back in intensity units (``deconvolve_run``).  Window i of run r samples under the id
-    (windows of the runs before it) + i.  Prints one JSON line: runs, windows, windows per second."""
+    (windows of the runs before it) + i.  With --joint the P precursors of one run are sampled together (``deconvolve_run_joint``; member
+    p's window i under the id p * windows + i).  Prints one JSON line: runs (--joint: members), windows, windows per second."""
     import time
 
     import numpy as np
 
     ms2, ms1 = np.load(ms2_path), np.load(ms1_path)
+    if joint:
+        if ms2.ndim != 2:
+            raise click.ClickException(f"--ms2: --joint expects one run (RT_total, MZ), got {ms2.shape}")
+        if ms1.ndim not in (2, 3) or ms1.shape[1] != ms2.shape[0]:
+            raise click.ClickException(f"--ms1: --joint expects (P, RT_total) or (P, RT_total, M1) with RT_total = {ms2.shape[0]}, got {ms1.shape}")
+        if not 1 <= ms1.shape[0] <= 8:
+            raise click.ClickException(f"--ms1: --joint takes 1 .. 8 members, got {ms1.shape[0]}")
+        sample_kw.setdefault("consistency", "bound")
+    elif "consistency" in sample_kw or "consistency_strength" in sample_kw:
+        raise click.ClickException("--consistency and --consistency-strength need --joint")
     if ms2.ndim not in (2, 3):
         raise click.ClickException(f"--ms2: expected (RT_total, MZ) or (R, RT_total, MZ), got {ms2.shape}")
     stacked = ms2.ndim == 3
     if not stacked:
         ms2, ms1 = ms2[None], ms1[None]
-    if ms1.ndim not in (2, 3) or ms1.shape[:2] != ms2.shape[:2]:
+    if not joint and (ms1.ndim not in (2, 3) or ms1.shape[:2] != ms2.shape[:2]):
         raise click.ClickException(f"--ms1: expected {'(R, RT_total)' if stacked else '(RT_total,)'} with or without a trailing channel "
                                    f"dimension to go with --ms2 {tuple(ms2.shape[1 - stacked:])}, got {tuple(ms1.shape[1 - stacked:])}")
     if not 1 <= step <= window <= ms2.shape[1]:
@@ -326,18 +351,18 @@ def deconvolve(config_path, checkpoint, ms2_path, ms1_path, out_path, window, st
     outs, first = [], 0
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    run = dm.deconvolve_run_joint if joint else dm.deconvolve_run  # (--joint: ms2[None] is the one run, ms1[None] its (P, ...) traces)
     for r in range(ms2.shape[0]):
-        res = dm.deconvolve_run(torch.from_numpy(np.ascontiguousarray(ms2[r], dtype=np.float32)).to(device),
-                                torch.from_numpy(np.ascontiguousarray(ms1[r], dtype=np.float32)).to(device), window=window, step=step,
-                                taper=taper, batch_size=batch_size, id_offset=first, num_steps=num_steps, eta=eta, seed=seed, use_ema=use_ema,
-                                **sample_kw)
-        first += res["n_windows"]
+        res = run(torch.from_numpy(np.ascontiguousarray(ms2[r], dtype=np.float32)).to(device),
+                  torch.from_numpy(np.ascontiguousarray(ms1[r], dtype=np.float32)).to(device), window=window, step=step, taper=taper,
+                  batch_size=batch_size, id_offset=first, num_steps=num_steps, eta=eta, seed=seed, use_ema=use_ema, **sample_kw)
+        first += res["n_windows"] * (ms1.shape[1] if joint else 1)
         outs.append({k: res[k].cpu().numpy() for k in ("pred", "overlap_var", "coverage", "scales")})
     torch.cuda.synchronize()
     seconds = time.perf_counter() - t0
     arrays = {k: np.stack([o[k] for o in outs]) if stacked else outs[0][k] for k in outs[0]}
     np.savez(out_path, starts=res["starts"], **arrays)
-    click.echo(json.dumps({"runs": int(ms2.shape[0]), "windows": int(first), "windows_per_s": round(first / seconds, 2)}))
+    click.echo(json.dumps({"runs": int(ms1.shape[1] if joint else ms2.shape[0]), "windows": int(first), "windows_per_s": round(first / seconds, 2)}))
 
 
 @cli.command()

@@ -110,8 +110,37 @@ class SampleOptions:
         return sampler_id, clip, None if w is None else (w, float(self.null_ms1)), (phi, q, cap) if (phi > 0.0 or q > 0.0) else None
 
 
+@dataclasses.dataclass(frozen=True)
+class JointSampleOptions(SampleOptions):
+    """``SampleOptions`` with the three options of a call over groups: the batch is ``B / group_size`` groups of
+    ``group_size`` members, member-major, and every step's x0 estimates of a group are projected onto its mixture (``consistency``:
+    "bound" or "sum") at ``consistency_strength``.  ``consistency`` without ``group_size`` means groups of one."""
+    group_size: Optional[int] = None
+    consistency: Optional[str] = None
+    consistency_strength: float = 1.0
+
+    def non_default(self):
+        live = super().non_default()
+        live.update({k: getattr(self, k) for k, on in (("group_size", self.group_size is not None), ("consistency", self.consistency is not None),
+                                                       ("consistency_strength", self.consistency_strength != 1.0)) if on})
+        return live
+
+    def resolve_joint(self, model):
+        """``(P, mode id, strength)`` as the library takes them, or None where the call is the one without the pass (no ``consistency``;
+        ``group_size`` is then only checked).  ValueError as ``model._check_joint`` raises it."""
+        return model._check_joint(self.group_size, self.consistency, self.consistency_strength)
+
+
+# what sample() refuses together with a live consistency pass, by name
+_JOINT_WITH_OPTIONS = ("sample: consistency together with guidance_scale, guidance_rescale or threshold_quantile is not implemented (follow-up: the "
+                       "guided form of the group pass, which needs the mirror half written, and the per-window statistics over projected estimates)")
+
 # the options only UNet1d's native sampler serves, as sample() refuses them: (on a CustomTransformer, on anything else)
 _UNET_ONLY = {
+    "joint": ("sample: group_size / consistency are built for UNet1d (dq_ddim_sample_joint); the group pass for the CustomTransformer's sampler "
+              "(dq_tfm_sample) is the follow-up",
+              "sample: group_size / consistency need the native sampler (this package's UNet1d on the GPU with both conditions); the generic "
+              "loop is the plain update only"),
     "adaptive": ("sample: guidance_rescale and threshold_quantile are built for UNet1d (dq_ddim_sample_adaptive); the per-window statistics "
                  "step for the CustomTransformer's sampler (dq_tfm_sample) is the follow-up",
                  "sample: guidance_rescale and threshold_quantile need the native sampler (this package's UNet1d on the GPU with both "
@@ -382,9 +411,29 @@ class DDIMDiffusionModel(ModelInterface):
             raise ValueError(f"threshold_max must be >= the floor ({floor!r}: clip_x0, or 1 without it), got {threshold_max!r}")
         return phi, q, cap
 
+    @staticmethod
+    def _check_joint(group_size, consistency, consistency_strength):
+        """``(P, mode id, strength)`` of a call over groups, or None without ``consistency`` (``group_size`` is then
+        only checked).  ValueError for a ``group_size`` that is not an integer in [1, 8], an unknown ``consistency``, and a strength outside
+        (0, 1] (as the float32 the kernel takes it as; NaN included)."""
+        P = 1
+        if group_size is not None:
+            if isinstance(group_size, bool) or not isinstance(group_size, int) or not 1 <= group_size <= N.GROUP_MAX:
+                raise ValueError(f"group_size must be an integer in [1, {N.GROUP_MAX}] or None, got {group_size!r}")
+            P = int(group_size)
+        if consistency is not None and consistency not in N.CONSISTENCY_MODES:
+            raise ValueError(f"Unknown consistency: {consistency!r} (one of {sorted(N.CONSISTENCY_MODES)}, or None)")
+        try:
+            strength = float(torch.tensor(float(consistency_strength), dtype=torch.float32))
+        except (TypeError, ValueError):
+            raise ValueError(f"consistency_strength must be a number in (0, 1], got {consistency_strength!r}") from None
+        if not (0.0 < strength <= 1.0):  # (NaN fails the comparison)
+            raise ValueError(f"consistency_strength must be a number in (0, 1], got {consistency_strength!r}")
+        return None if consistency is None else (P, N.CONSISTENCY_MODES[consistency], strength)
+
     def sample(self, x_t, ms2_cond=None, ms1_cond=None, num_steps=1000, return_trajectory=False, eta=0.0, seed=None, window_ids=None,
                shape=None, sampler="reference", clip_x0=None, guidance_rescale=0.0, threshold_quantile=None, threshold_max=None,
-               guidance_scale=None, null_ms1=0.0):
+               group_size=None, consistency=None, consistency_strength=1.0, guidance_scale=None, null_ms1=0.0):
         """model.py:293-324: returns (denoised, mixture - denoised).  Native loop when the network is UNet1d; for a CustomTransformer behind
         ``DDIMTransformerAdapter`` the library's loop (``dq_tfm_sample``) serves every call when
         ``native_tfm_sampler`` is set, and otherwise exactly the calls the generic loop refuses (the options below, ``return_trajectory``).
@@ -415,24 +464,44 @@ class DDIMDiffusionModel(ModelInterface):
         window's ``q``-quantile ``s`` of ``|x0|`` -- never below the floor ``f = clip_x0`` (1 without it), never above ``threshold_max`` --
         and scaled by ``f / s``, which keeps the shape of a peak the constant clamp would cut flat; it is allowed where ``clip_x0`` is
         ('ddim' or 'dpmpp_2m', ``eta == 0``).  The defaults are the call as it is without the options, bit for bit and launch for launch.
-        UNet1d on the GPU only (``dq_ddim_sample_adaptive``)."""
+        UNet1d on the GPU only (``dq_ddim_sample_adaptive``).
+
+        ``group_size = P`` and ``consistency`` sample the P precursors of an isolation window as one group.  The
+        batch is ``B / P`` groups of P members, member-major -- member p of group g is row ``p * G + g``, the concatenation of P ordinary
+        batches that share their ``ms2_cond`` rows and differ in ``ms1_cond`` -- and the group's mixture is row g of ``ms2_cond``.  Between
+        the network forward and the update every step's x0 estimates are projected in the mixture's units: ``"bound"`` scales a group's
+        positive parts down wherever their sum exceeds the mixture (nothing is raised, negatives are not touched; with P = 1 a prediction
+        never exceeds the observation), ``"sum"`` scales them so that they add up to the mixture (negatives go to 0).
+        ``consistency_strength`` in (0, 1] blends between the estimate (towards 0) and its projection (1).  The update then runs on the
+        projected x0 whatever the objective.  ``consistency=None`` is the call as it is without the option, bit for bit (``group_size``
+        is only checked); ``consistency`` without ``group_size`` means P = 1.  Works with every sampler, ``eta``, ``clip_x0``, seeds, window
+        ids and trajectories; not together with ``guidance_scale``, ``guidance_rescale`` or ``threshold_quantile``.  UNet1d on the GPU only
+        (``dq_ddim_sample_joint``)."""
         eta = self._check_eta(eta)
-        sampler_id, clip, guidance, adaptive = SampleOptions(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile,
-                                                             threshold_max).resolve(eta, self)
+        options = JointSampleOptions(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max, group_size,
+                                     consistency, consistency_strength)
+        sampler_id, clip, guidance, adaptive = options.resolve(eta, self)
+        joint = options.resolve_joint(self)
+        if group_size is not None:
+            B = int((shape if x_t is None and shape is not None else (x_t if x_t is not None else ms2_cond).shape)[0])
+            if B % int(group_size):
+                raise ValueError(f"the batch ({B}) must be a whole number of groups of group_size = {group_size}")
+        if joint is not None and (guidance is not None or adaptive is not None):
+            raise NotImplementedError(_JOINT_WITH_OPTIONS)
         stochastic = eta > 0.0 or x_t is None or seed is not None or window_ids is not None
         if sampler_id != 0:
             self._check_decreasing(self.sampler_timesteps(self.num_timesteps, num_steps).tolist())
         on_gpu = ms2_cond is not None and ms1_cond is not None and (x_t.is_cuda if x_t is not None else ms2_cond.is_cuda)
         # the route, decided once: UNet1d's loop, the transformer's, or the generic one below
-        unet_only = "adaptive" if adaptive is not None else "guidance" if guidance is not None else None
+        unet_only = "adaptive" if adaptive is not None else "guidance" if guidance is not None else "joint" if joint is not None else None
         if unet_only and not (self.native and on_gpu):
             raise NotImplementedError(_UNET_ONLY[unet_only][0 if self._native_tfm else 1])
         call = dict(seed=seed, window_ids=window_ids, shape=shape, sampler=sampler_id, clip_x0=clip)
         if self.native and on_gpu:
-            # (the default call passes eta=None: dq_ddim_sample, the call as it always was; ``adaptive`` only when it is live)
+            # (the default call passes eta=None: dq_ddim_sample, the call as it always was; ``adaptive`` and ``joint`` only when live)
             plain = not (unet_only or stochastic or sampler_id != 0)
             return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=None if plain else eta, guidance=guidance,
-                                       **call, **({} if adaptive is None else {"adaptive": adaptive}))
+                                       **call, **({} if adaptive is None else {"adaptive": adaptive}), **({} if joint is None else {"joint": joint}))
         if on_gpu and self._native_tfm and (self.native_tfm_sampler or stochastic or sampler_id != 0 or return_trajectory):
             return self._sample_native_tfm(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=eta, **call)
         if sampler_id != 0:
@@ -515,13 +584,16 @@ class DDIMDiffusionModel(ModelInterface):
         return tuple(outs) if return_trajectory else tuple(outs[:2])
 
     # Which of the full argument list -- dq_ddim_sample_adaptive's 35 -- each of the U-Net's entries takes: the 22 of dq_ddim_sample, then
-    # (eta, seed, ids), (sampler, clip_x0), the guided flag, (scale, null_ms1), (phi, q, cap, scratch, bytes)
+    # (eta, seed, ids), (sampler, clip_x0), the guided flag, (scale, null_ms1), (phi, q, cap, scratch, bytes).  A call over groups never has
+    # the last five: its (group size, mode, strength) follow the 30 of dq_ddim_sample_v, and its entry takes them behind the solver's 27
     _SAMPLE_ENTRY_ARGS = {"dq_ddim_sample": range(22), "dq_ddim_sample_ex": range(25), "dq_ddim_sample_solver": range(27),
-                          "dq_ddim_sample_guided": (*range(27), 28, 29), "dq_ddim_sample_v": range(30), "dq_ddim_sample_adaptive": range(35)}
+                          "dq_ddim_sample_guided": (*range(27), 28, 29), "dq_ddim_sample_v": range(30), "dq_ddim_sample_adaptive": range(35),
+                          "dq_ddim_sample_joint": (*range(27), 30, 31, 32)}
 
     def _sample_native(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False, eta=None, seed=None, window_ids=None, shape=None,
-                       sampler=0, clip_x0=0.0, guidance=None, adaptive=None):
-        """The U-Net's loop in the library, through the entry that knows what is live -- ``adaptive`` = (phi, q, cap): ``dq_ddim_sample_adaptive``;
+                       sampler=0, clip_x0=0.0, guidance=None, adaptive=None, joint=None):
+        """The U-Net's loop in the library, through the entry that knows what is live -- ``joint`` = (P, mode, strength): ``dq_ddim_sample_joint``
+        (never with ``adaptive`` or ``guidance``); ``adaptive`` = (phi, q, cap): ``dq_ddim_sample_adaptive``;
         else ``pred_type="v_prediction"``: ``dq_ddim_sample_v``; else ``eta`` None: ``dq_ddim_sample`` (the call as it always was); else
         ``guidance`` = (scale, null_ms1): ``dq_ddim_sample_guided`` (on the workspace of twice the batch, as every guided call); else
         ``sampler`` != 0: ``dq_ddim_sample_solver``; else ``dq_ddim_sample_ex`` -- which takes its part of one list (``_SAMPLE_ENTRY_ARGS``)."""
@@ -530,7 +602,8 @@ class DDIMDiffusionModel(ModelInterface):
         c1 = net._check_inputs(ms1_cond, B, RT).detach().to(torch.float32).contiguous()
         flat = net.read_params()  # (the averaged weights inside ModelInterface.ema_scope())
         ws = net.workspace(2 * B if guidance is not None else B, RT, False)
-        entry = ("dq_ddim_sample_adaptive" if adaptive is not None else "dq_ddim_sample_v" if self.pred_type == "v_prediction" else
+        entry = ("dq_ddim_sample_joint" if joint is not None else "dq_ddim_sample_adaptive" if adaptive is not None else
+                 "dq_ddim_sample_v" if self.pred_type == "v_prediction" else
                  "dq_ddim_sample" if eta is None else "dq_ddim_sample_guided" if guidance is not None else
                  "dq_ddim_sample_solver" if sampler else "dq_ddim_sample_ex")
         tail = [RT, N.stream_ptr()]
@@ -541,6 +614,8 @@ class DDIMDiffusionModel(ModelInterface):
         if adaptive is not None:
             stat = net.stat_scratch(B, RT * MZ)
             tail += [*(float(v) for v in adaptive), N.ptr(stat), stat.numel()]
+        if joint is not None:
+            tail += [int(joint[0]), int(joint[1]), float(joint[2])]
         return self._run_loop(entry, [net._plan, N.ptr(flat), N.ptr(net.rope_freqs())], B, tail, x_T, c2, c1, ws, num_steps, (B, RT, MZ),
                               return_trajectory, take=self._SAMPLE_ENTRY_ARGS[entry])
 

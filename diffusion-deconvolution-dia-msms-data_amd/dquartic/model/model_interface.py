@@ -675,7 +675,7 @@ class ModelInterface(object):
 
     def predict(self, dataloader, mixture_weights=(0.5, 0.5), num_steps=1000, use_ema=None, eta=0.0, seed=None, n_draws=1,
                 sampler="reference", clip_x0=None, *, guidance_rescale=0.0, threshold_quantile=None, threshold_max=None,
-                guidance_scale=None, null_ms1=0.0):
+                group_size=None, consistency=None, consistency_strength=1.0, guidance_scale=None, null_ms1=0.0):
         """Reference :630-668: one dict per batch with the first item's prediction (``_predict_one_batch`` returns item 0).
         ``use_ema``: sample from the averaged weights; None (default) = when EMA is enabled.
 
@@ -688,11 +688,13 @@ class ModelInterface(object):
 
         ``sampler`` / ``clip_x0``: passed to ``sample``; with the defaults nothing else changes.  ``guidance_scale``
         / ``null_ms1`` (keyword-only): classifier-free guidance, passed to ``sample`` too; so are
-        ``guidance_rescale`` / ``threshold_quantile`` / ``threshold_max``.
+        ``guidance_rescale`` / ``threshold_quantile`` / ``threshold_max`` and ``group_size`` / ``consistency`` /
+        ``consistency_strength`` (every batch of the loader is then read as member-major groups).
 
         Batches that carry their weights (``ResidentMixLoader``) add ``"weights"``, the batch's ``(B, K)`` array."""
         self.model.eval()
-        sampler_kw = _sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max)
+        sampler_kw = _sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max, group_size,
+                                     consistency, consistency_strength)
         n_draws = int(n_draws)
         if n_draws < 1:
             raise ValueError(f"n_draws must be >= 1, got {n_draws}")
@@ -812,6 +814,51 @@ class ModelInterface(object):
     _RUN_SAMPLE_OPTIONS = ("num_steps", "eta", "seed", "sampler", "clip_x0", "guidance_scale", "null_ms1", "guidance_rescale",
                            "threshold_quantile", "threshold_max", "use_ema")
 
+    def _run_inputs(self, who, ms2_run, ms1_run, members, window, step, batch_size, taper, sample_options):
+        """What ``deconvolve_run`` and ``deconvolve_run_joint`` (``members``: ``ms1_run`` carries a leading axis, one trace per member) check
+        and stage alike, refusing under ``who``: the option names, the shapes, the MS1 channels against the network's, ``window``, the
+        tiling, ``batch_size``, the taper, device tensors, a seed (drawn once when None).  Returns ``(ms2_run, ms1_run`` -- contiguous
+        fp32, the MS1 with its channel axis -- ``RT_total, MZ, M1, window, step, batch_size, starts, taper (device), the sample options
+        without use_ema, use_ema)``."""
+        from ..utils.run_tiles import run_window_starts, taper_table
+
+        lead = 1 if members else 0
+        ms1_name = "ms1_runs" if members else "ms1_run"
+        ms1_shapes = "(P, RT_total) or (P, RT_total, M1)" if members else "(RT_total,) or (RT_total, M1)"
+        unknown = sorted(set(sample_options) - set(self._RUN_SAMPLE_OPTIONS))
+        if unknown:
+            raise TypeError(f"{who}: unknown option(s) {unknown} (sample options: {list(self._RUN_SAMPLE_OPTIONS)})")
+        if not (torch.is_tensor(ms2_run) and torch.is_tensor(ms1_run)):
+            raise TypeError(f"{who}: ms2_run and {ms1_name} must be torch tensors")
+        if ms2_run.dim() != 2:
+            raise ValueError(f"{who}: ms2_run must be (RT_total, MZ), got {tuple(ms2_run.shape)}")
+        RT_total, MZ = (int(v) for v in ms2_run.shape)
+        if ms1_run.dim() == lead + 1:
+            ms1_run = ms1_run[..., None]
+        if ms1_run.dim() != lead + 2 or ms1_run.shape[lead] != RT_total:
+            raise ValueError(f"{who}: {ms1_name} must be {ms1_shapes} with RT_total = {RT_total}, got "
+                             f"{tuple(ms1_run.shape)}")
+        M1 = int(ms1_run.shape[-1])
+        net_m1 = int(getattr(self._flat_net(), "attn_cond_channels", 1))
+        if M1 != net_m1:
+            raise ValueError(f"{who}: {ms1_name} has {M1} channel(s), the network was built with attn_cond_channels={net_m1}")
+        if window is None:
+            raise ValueError(f"{who}: window (the scans per window, the length the network was trained on) must be given")
+        W, step, batch_size = int(window), int(step), int(batch_size)
+        starts = run_window_starts(RT_total, W, step)
+        if batch_size < 1:
+            raise ValueError(f"{who}: batch_size must be >= 1, got {batch_size}")
+        taper_host = taper_table(taper, W)
+        opts = dict(sample_options)
+        use_ema = opts.pop("use_ema", None)
+        if not (ms2_run.is_cuda and ms1_run.is_cuda):
+            raise NotImplementedError(f"{who} runs in the native library only (device tensors)")
+        if opts.get("seed") is None:
+            opts["seed"] = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+        dev = ms2_run.device
+        run2, run1 = ms2_run.detach().to(torch.float32).contiguous(), ms1_run.detach().to(device=dev, dtype=torch.float32).contiguous()
+        return run2, run1, RT_total, MZ, M1, W, step, batch_size, starts, torch.from_numpy(taper_host).to(dev), opts, use_ema
+
     def deconvolve_run(self, ms2_run, ms1_run, window=None, step=5, taper="hann", batch_size=32, id_offset=0, **sample_options):
         """Deconvolve one observed isolation-window chromatogram (new work: the reference has no such entry).
 
@@ -838,42 +885,9 @@ class ModelInterface(object):
         ``"overlap_var"`` ``(RT_total, MZ)``, the weighted variance among the windows that cover a scan (their disagreement; 0 where one
         window covers it); ``"coverage"`` ``(RT_total,)``, the sum of the taper weights on a scan; ``"scales"`` ``(n, 4)`` = (MS2 lo, MS2
         hi, MS1 lo, MS1 hi) of every window; ``"starts"`` (int64 array) and ``"n_windows"``.  The tensors stay on the device."""
-        from ..utils.run_tiles import run_window_starts, taper_table
-
-        unknown = sorted(set(sample_options) - set(self._RUN_SAMPLE_OPTIONS))
-        if unknown:
-            raise TypeError(f"deconvolve_run: unknown option(s) {unknown} (sample options: {list(self._RUN_SAMPLE_OPTIONS)})")
-        if not (torch.is_tensor(ms2_run) and torch.is_tensor(ms1_run)):
-            raise TypeError("deconvolve_run: ms2_run and ms1_run must be torch tensors")
-        if ms2_run.dim() != 2:
-            raise ValueError(f"deconvolve_run: ms2_run must be (RT_total, MZ), got {tuple(ms2_run.shape)}")
-        RT_total, MZ = (int(v) for v in ms2_run.shape)
-        if ms1_run.dim() == 1:
-            ms1_run = ms1_run[:, None]
-        if ms1_run.dim() != 2 or ms1_run.shape[0] != RT_total:
-            raise ValueError(f"deconvolve_run: ms1_run must be (RT_total,) or (RT_total, M1) with RT_total = {RT_total}, got "
-                             f"{tuple(ms1_run.shape)}")
-        M1 = int(ms1_run.shape[1])
-        net_m1 = int(getattr(self._flat_net(), "attn_cond_channels", 1))
-        if M1 != net_m1:
-            raise ValueError(f"deconvolve_run: ms1_run has {M1} channel(s), the network was built with attn_cond_channels={net_m1}")
-        if window is None:
-            raise ValueError("deconvolve_run: window (the scans per window, the length the network was trained on) must be given")
-        W, step, batch_size, id_offset = int(window), int(step), int(batch_size), int(id_offset)
-        starts = run_window_starts(RT_total, W, step)
-        n = len(starts)
-        if batch_size < 1:
-            raise ValueError(f"deconvolve_run: batch_size must be >= 1, got {batch_size}")
-        taper_host = taper_table(taper, W)
-        opts = dict(sample_options)
-        use_ema = opts.pop("use_ema", None)
-        if not (ms2_run.is_cuda and ms1_run.is_cuda):
-            raise NotImplementedError("deconvolve_run runs in the native library only (device tensors)")
-        if opts.get("seed") is None:
-            opts["seed"] = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
-        dev = ms2_run.device
-        run2, run1 = ms2_run.detach().to(torch.float32).contiguous(), ms1_run.detach().to(device=dev, dtype=torch.float32).contiguous()
-        taper_dev = torch.from_numpy(taper_host).to(dev)
+        run2, run1, RT_total, MZ, M1, W, step, batch_size, starts, taper_dev, opts, use_ema = self._run_inputs(
+            "deconvolve_run", ms2_run, ms1_run, False, window, step, batch_size, taper, sample_options)
+        n, id_offset, dev = len(starts), int(id_offset), run2.device
         mean, m2 = torch.zeros(RT_total, MZ, device=dev), torch.zeros(RT_total, MZ, device=dev)
         wsum, scales = torch.zeros(RT_total, device=dev), torch.empty(n, 4, device=dev)
         nb = min(batch_size, n)
@@ -896,6 +910,61 @@ class ModelInterface(object):
         finally:
             self.model.train(was_training)
         return {"pred": mean, "overlap_var": m2 / wsum[:, None], "coverage": wsum, "scales": scales, "starts": starts, "n_windows": n}
+
+    @staticmethod
+    def joint_window_ids(id_offset, n_windows, members, i0, count):
+        """The window ids of one batch of ``deconvolve_run_joint``, member-major: member p, window i samples under ``id_offset + p *
+        n_windows + i`` (member 0: the ids of ``deconvolve_run``), here for windows ``i0 .. i0 + count - 1`` of every member.  int64, host."""
+        i = np.arange(int(i0), int(i0) + int(count), dtype=np.int64)
+        return (int(id_offset) + np.arange(int(members), dtype=np.int64)[:, None] * int(n_windows) + i[None, :]).reshape(-1)
+
+    def deconvolve_run_joint(self, ms2_run, ms1_runs, window=None, step=5, taper="hann", batch_size=32, id_offset=0, consistency="bound",
+                             consistency_strength=1.0, **sample_options):
+        """``deconvolve_run`` for the P precursors that co-elute in one isolation window, sampled as groups under mixture consistency
+        (DESIGN.md section 40).  ``ms2_run`` ``(RT_total, MZ)`` is the one observed run, ``ms1_runs`` ``(P, RT_total)`` or ``(P, RT_total,
+        M1)`` the P MS1 traces, 1 <= P <= 8.  Per batch of ``batch_size`` = G consecutive windows ``dq_run_windows`` runs once per member
+        (the same MS2 windows and MS2 scales each time, the member's own MS1), the P batches are concatenated member-major and sampled in
+        one call, ``sample(None, ..., group_size=P, consistency=consistency, consistency_strength=consistency_strength)`` -- member p,
+        window i under the id ``id_offset + p * n_windows + i`` (``joint_window_ids``) -- and ``dq_run_stitch`` folds each member's
+        contiguous slice into that member's running mean.  ``consistency``: ``"bound"`` (default: the members never explain more than
+        the observed window, scan by scan and m/z by m/z), ``"sum"`` (they explain all of it) or None -- then every member's result is,
+        bit for bit, what ``deconvolve_run(ms2_run, ms1_runs[p], id_offset=id_offset + p * n_windows)`` returns.  The other arguments and
+        ``sample_options`` are ``deconvolve_run``'s, minus the options a call over groups refuses (``sample``).
+
+        Returns ``deconvolve_run``'s dict with a leading P axis on ``"pred"``, ``"overlap_var"`` and ``"scales"`` (``(P, n, 4)``: the MS2
+        columns are the same for every member); ``"coverage"``, ``"starts"`` and ``"n_windows"`` (the windows of ONE member) as there."""
+        run2, runs1, RT_total, MZ, M1, W, step, batch_size, starts, taper_dev, opts, use_ema = self._run_inputs(
+            "deconvolve_run_joint", ms2_run, ms1_runs, True, window, step, batch_size, taper, sample_options)
+        P, n, dev = int(runs1.shape[0]), len(starts), run2.device
+        if not 1 <= P <= N.GROUP_MAX:
+            raise ValueError(f"deconvolve_run_joint: ms1_runs must hold 1 .. {N.GROUP_MAX} members, got {P}")
+        mean, m2 = torch.zeros(P, RT_total, MZ, device=dev), torch.zeros(P, RT_total, MZ, device=dev)
+        wsum, scales = torch.zeros(P, RT_total, device=dev), torch.empty(P, n, 4, device=dev)
+        nb = min(batch_size, n)
+        scratch = torch.empty(max(1, N.lib().dq_run_windows_scratch_bytes(nb) // 4), dtype=torch.float32, device=dev)
+        win2, win1 = torch.empty(P * nb, W, MZ, device=dev), torch.empty(P * nb, W, M1, device=dev)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad(), self._ema_or_null_scope(use_ema):
+                for i0 in range(0, n, batch_size):
+                    G = min(batch_size, n - i0)
+                    c2, c1 = win2[:P * G], win1[:P * G]
+                    for p in range(P):
+                        N.check(N.lib().dq_run_windows(N.ptr(run2), N.ptr(runs1[p]), RT_total, MZ, M1, W, step, i0, G, N.ptr(c2[p * G:]),
+                                                       N.ptr(c1[p * G:]), N.ptr(scales[p, i0:]), N.ptr(scratch), scratch.numel() * 4,
+                                                       N.stream_ptr()), "dq_run_windows")
+                    ids = torch.from_numpy(self.joint_window_ids(id_offset, n, P, i0, G)).to(dev)
+                    pred, _ = self.sample(None, ms2_cond=c2, ms1_cond=c1, window_ids=ids, group_size=P, consistency=consistency,
+                                          consistency_strength=consistency_strength, **opts)
+                    pred = pred.detach().to(torch.float32).contiguous()
+                    for p in range(P):
+                        N.check(N.lib().dq_run_stitch(N.ptr(pred[p * G:]), N.ptr(scales[p, i0:]), N.ptr(taper_dev), RT_total, MZ, W, step, i0, G,
+                                                      N.ptr(mean[p]), N.ptr(m2[p]), N.ptr(wsum[p]), N.stream_ptr()), "dq_run_stitch")
+        finally:
+            self.model.train(was_training)
+        # (every member's taper sums are the same numbers: the tiling is the members' own)
+        return {"pred": mean, "overlap_var": m2 / wsum[:, :, None], "coverage": wsum[0], "scales": scales, "starts": starts, "n_windows": n}
 
     # ---- internals
     def _init_for_training(self):
@@ -1023,13 +1092,15 @@ class ModelInterface(object):
 
     def _predict_one_batch(self, x_0, ms2_cond=None, ms1_cond=None, num_steps=1000, use_ema=None, eta=0.0, seed=None, n_draws=1,
                            window_ids=None, sampler="reference", clip_x0=None, *, guidance_rescale=0.0, threshold_quantile=None,
-                           threshold_max=None, guidance_scale=None, null_ms1=0.0):
+                           threshold_max=None, group_size=None, consistency=None, consistency_strength=1.0, guidance_scale=None,
+                           null_ms1=0.0):
         """Reference :1125-1150: eval + no_grad + sample(randn_like(x_0)); returns item 0 of the batch as numpy.  ``use_ema`` as in
         ``predict``.  With ``eta > 0``, a ``seed`` or ``n_draws > 1`` (see ``predict``): x_T and the step noise from the sampler's
         generator, draw j under ``seed + j``; ``n_draws > 1`` returns (sample, pred_noise, mean, std) of item 0, sample / pred_noise
         being draw 0's and mean / std taken per element over the draws' samples (torch reductions: this is not the hot path)."""
         self.model.eval()
-        sampler_kw = _sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max)
+        sampler_kw = _sampler_kwargs(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max, group_size,
+                                     consistency, consistency_strength)
         if not (float(eta) > 0.0 or seed is not None or int(n_draws) > 1):
             with torch.no_grad(), self._ema_or_null_scope(use_ema):
                 sample, pred_noise = self.sample(torch.randn_like(x_0), ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=num_steps,
@@ -1054,16 +1125,19 @@ class ModelInterface(object):
     plot_single_prediction = log_single_prediction
 
 
-def _sampler_kwargs(sampler, clip_x0, guidance_scale=None, null_ms1=0.0, guidance_rescale=0.0, threshold_quantile=None, threshold_max=None):
-    """The step-consistent-sampler, guidance and per-window options as keyword arguments of ``sample`` -- none at the defaults, so that a
-    subclass whose ``sample`` predates them is still called as it always was (the rule is ``SampleOptions.non_default``)."""
-    from .model import SampleOptions  # (that module imports this one)
-    return SampleOptions(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max).non_default()
+def _sampler_kwargs(sampler, clip_x0, guidance_scale=None, null_ms1=0.0, guidance_rescale=0.0, threshold_quantile=None, threshold_max=None,
+                    group_size=None, consistency=None, consistency_strength=1.0):
+    """The step-consistent-sampler, guidance, per-window and group options as keyword arguments of ``sample`` -- none at the defaults, so that
+    a subclass whose ``sample`` predates them is still called as it always was (the rule is ``SampleOptions.non_default``, with
+    ``JointSampleOptions``' three on top)."""
+    from .model import JointSampleOptions  # (that module imports this one)
+    return JointSampleOptions(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max, group_size,
+                              consistency, consistency_strength).non_default()
 
 
 def _reported_options(sampler_kw):
     """``_sampler_kwargs``' result as ``evaluate`` reports it: the same keys, plain str / float values"""
-    return {k: str(v) if k == "sampler" else float(v) for k, v in sampler_kw.items()}
+    return {k: str(v) if k in ("sampler", "consistency") else int(v) if k == "group_size" else float(v) for k, v in sampler_kw.items()}
 
 
 def _wandb():

@@ -60,7 +60,8 @@ const char* dq_last_error(void);
  * dq_ms1_cond_drop, dq_ddim_sample_guided; K-component mixtures: dq_mix_batch_scratch_bytes, dq_mix_batch; the v objective: DQ_PRED_V,
  * dq_ddim_step_v, dq_solver_step_v, dq_guided_update_v, dq_ddim_sample_v, dq_mse_loss_v_fwd_bwd, dq_mse_per_window_v; whole
  * chromatograms: dq_run_window_count, dq_run_windows_scratch_bytes, dq_run_windows, dq_run_stitch; per-window sampler control:
- * dq_sample_stat_scratch_bytes, dq_window_rescale, dq_window_abs_quantile, dq_step_update_adaptive, dq_ddim_sample_adaptive). */
+ * dq_sample_stat_scratch_bytes, dq_window_rescale, dq_window_abs_quantile, dq_step_update_adaptive, dq_ddim_sample_adaptive; joint
+ * sampling of a window's precursors: DQ_CONSIST_*, dq_group_project, dq_ddim_sample_joint). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -492,6 +493,49 @@ int dq_ddim_sample_adaptive(dq_plan* plan, const float* params, const float* rop
                             const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, int guided,
                             float guidance_scale, float null_ms1, double guidance_rescale, float threshold_quantile, float threshold_max,
                             void* stat_scratch, int64_t stat_scratch_bytes);
+
+/* ---- joint sampling of a window's precursors under mixture consistency (no reference counterpart) -------------
+ * data.mixture with scale_target trains the network to predict a precursor's contribution n_0 w_0 to the mixture it sees, and the
+ * contributions of a window's precursors add up to that mixture.  Sampling the P precursors of a window as one group lets every step use
+ * it: one streaming pass (csrc/k_group.hip) between the network forward and the update redistributes the step's x0 estimates -- the
+ * proportional soft-mask form of the mixture-consistency projection (Wisdom et al. 2019).  A batch of B = G * P windows is G groups of P
+ * members, 1 <= P <= 8, MEMBER-MAJOR: member p of group g is row p * G + g, so a joint batch is the concatenation of P ordinary batches.
+ * The group's mixture m is row g of ms2_cond in the caller's units ([0, 1] after min-max), the tensor the network reads; rows p * G + g are
+ * expected to repeat it and are not read by the pass.  Per element of a group, with the step's row [sa, sb]:
+ *  1. x0_p from (x_p, net_p) by the objective, in the update's arithmetic: eps (x - sb net) / sa; x0 net; v sa x - sb net.
+ *  2. y_p = auto_normalize ? (x0_p + 1) * 0.5f : x0_p, the image units of ms2_cond.
+ *  3. yp_p = y_p > 0 ? y_p : 0;  S = ((yp_0 + yp_1) + yp_2) + ... in member order;  m <- m > 0 ? m : 0.
+ *  4. DQ_CONSIST_BOUND: S > m: f = m / S, z_p = y_p > 0 ? y_p * f : y_p; else z_p = y_p.  Negatives are never touched, nothing is ever
+ *     raised; P = 1 is the plain physical bound "a prediction may not exceed the observation".
+ *     DQ_CONSIST_SUM: S > 0: f = m / S, z_p = yp_p * f; else z_p = m / P.  Negatives go to 0 and the group explains the whole mixture.
+ *  5. y'_p = strength == 1 ? z_p : y_p + strength * (z_p - y_p), 0 < strength <= 1.
+ *  6. x0'_p = y'_p == y_p ? x0_p : (auto_normalize ? 2 * y'_p - 1 : y'_p): an element the projection does not move keeps its x0 bits.
+ * Every operation is one rounded fp32 operation in this order (no FMA contraction, correctly rounded division); inputs are assumed finite.
+ * At strength 1, where the rule acts, sum_p max(y'_p, 0) equals m within (P + 1) 2^-24 m. */
+enum { DQ_CONSIST_NONE = 0, DQ_CONSIST_BOUND = 1, DQ_CONSIST_SUM = 2 };
+#define DQ_GROUP_MAX 8
+/* The pass alone: x0_out (P * G, per_window) = x0' from x_t, net (P * G, per_window; what pred_type says) and mix (G, per_window).
+ * coef_dev: a row whose first two floats are [sa, sb].  x0_out may alias net (element-wise); x_t and mix must not alias x0_out.  Under
+ * DQ_PRED_X0 x_t is not read.  16-byte accesses when per_window % 4 == 0 and all tensors are 16-byte aligned.  Refused, in this order and
+ * before anything touches the device: a NULL argument, an unknown pred_type, P outside [1, 8], G < 0 or per_window < 0, an unknown mode
+ * (DQ_CONSIST_NONE included), strength outside (0, 1] or NaN, tensors that are not 4-byte aligned. */
+int dq_group_project(const float* x_t, const float* net, float* x0_out, const float* mix, const float* coef_dev, int pred_type,
+                     int auto_normalize, int G, int P, int64_t per_window, int mode, float strength, void* stream);
+/* The U-Net's sampling loop over groups: dq_ddim_sample_v's arguments without guided, guidance_scale and null_ms1, then group_size = P,
+ * consistency (DQ_CONSIST_*) and strength.  consistency = DQ_CONSIST_NONE: the other two are ignored and the call is the unguided
+ * dq_ddim_sample_v, launch for launch.  Otherwise every step runs the forward, then the pass in place on the network output, then the
+ * update in its x0-objective form (DQ_PRED_X0) over x0' behind the forward, never in the head launch, whatever the network's objective:
+ * the projected estimate enters x_prev, the 2M history and the derived eps (x - sa x0') / sb, which is what traj_eps holds; clip_x0 clamps
+ * after the projection, as the update always does.  All three samplers, any eta, seeds, window ids, x_T = NULL, trajectories and the
+ * captured step (cached by (group_size, consistency, strength) as well).  Refusals: dq_ddim_sample_v's in its order; behind the ones it
+ * makes before anything touches the device (up to the batch and step counts) and in front of its workspace check: group_size outside
+ * [1, 8], B % group_size != 0, an unknown mode, strength outside (0, 1] or NaN. */
+int dq_ddim_sample_joint(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
+                         const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
+                         const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
+                         int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
+                         const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, int group_size, int consistency,
+                         float strength);
 
 /* ---- batch formation from an HBM-resident dataset (the step right before the hot path) ------------
  * Replaces, for B (window 1, window 2) pairs, DIAMSDataset.__getitem__'s min-max normalisation (utils/data_loader.py:70-79:
