@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <string>
 #include "dq_error.h"  // set_error, DQ_REQUIRE
+#include "dq_wave.h"   // row_sum16
 
 namespace dq {
 
@@ -67,15 +68,7 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // dependent ds_bpermute round trips per value and was the floor (~12 us) of every kernel that ends in a block reduction of
 // dozens of values (the weight-gradient kernels: 52 per wave).
 __device__ __forceinline__ float wave_sum(float v) {
-  int x = __float_as_int(v);
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-  x = __float_as_int(v);
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-  x = __float_as_int(v);
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, false));  // row_half_mirror
-  x = __float_as_int(v);
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, false));  // row_mirror: every lane = its row's sum
-  x = __float_as_int(v);
+  const int x = __float_as_int(row_sum16(v));  // every lane = its row's sum
   const float r0 = __int_as_float(__builtin_amdgcn_readlane(x, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(x, 16));
   const float r2 = __int_as_float(__builtin_amdgcn_readlane(x, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(x, 48));
   return (r0 + r1) + (r2 + r3);

@@ -605,6 +605,8 @@ inline LaReduceItem la_reduce_item(float* part, int slots, int C, float* dw_qkv,
 constexpr int LA_REDUCE_MAX = 16;
 int64_t la_part_reserve(int C);  // floats of slot scratch one deferred launch with C channels can use
 int launch_linattn_dw_reduce_multi(const LaReduceItem* items, int count, hipStream_t s);
+// the slots of launch_linattn_bwd_long (512 C floats per wave: dWqkv | dWo), summed into the gradient buffers (+=)
+int launch_linattn_dw_reduce(const float* part, int nslots, int C, float* dw_qkv, float* dw_out, hipStream_t s);
 
 // ---- k_attn.hip : softmax attention over RT of the bottleneck (q,k,v,o in (B, 128, RT) conv layout)
 int launch_rope(float* qk, const float* freqs, int B, int64_t batch_stride, int RT, float sign, hipStream_t s);

@@ -1,17 +1,15 @@
-// Wave-level MFMA helpers shared by the LinearAttention and bottleneck-attention kernels (v_mfma_f32_32x32x2_f32, exact fp32; and the
-// split-bf16 form on v_mfma_f32_32x32x16_bf16 at the end of the file).
+// 32x32 tile helpers shared by the LinearAttention and bottleneck-attention kernels, on the wave primitives of dq_wave.h (mfma32 =
+// v_mfma_f32_32x32x2_f32, exact fp32; and the split-bf16 form on v_mfma_f32_32x32x16_bf16 at the end of the file).
 //   A operand: lane l supplies A[i = l & 31][k = l >> 5] ; B operand: lane l supplies B[k = l >> 5][j = l & 31]
 //   C/D: register r of lane l holds D[row = rmap(r, l >> 5)][col = l & 31]
 // An accumulator X (rows in registers, column on the lane) feeds, register by register, a product that sums over X's
 // ROW index:  sum_r mfma(X.r, Y.r) = X^T Y  with rows = X's columns, cols = Y's columns.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "dq_wave.h"
 
 namespace dq {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ f32x16 mfma_f32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ constexpr int rmap(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 // Which channel x-register j of a lane of half `half` holds in the LinearAttention kernels, and how many such registers a lane
 // has.  C = 8 / 16: the accumulator row map (8 / 16 channel slots, all used).  C = 4: c = 2 * half + j over TWO registers, C = 12:
@@ -26,37 +24,71 @@ __device__ __forceinline__ constexpr int la_chan(int C, int j, int half) {
 // that a projection operand register IS the residual / output register of the same index; C = 12: i + 6 half (six full steps instead of
 // eight with a third of the slots empty; the residual is then read a second time in the row-map layout).
 __host__ __device__ __forceinline__ constexpr int sm_chan(int C, int i, int half) { return C == 12 ? i + 6 * half : (i & 3) + 8 * (i >> 2) + 4 * half; }
-// value of lane ^ 32 (ds_bpermute).  gfx950's v_permlane32_swap_b32 (tools/probe/permlane32.hip) was tried here: with the
-// two register copies and the select it needs it is four VALU instructions, and the VALU-bound forward kernel got 4 % slower
-// (the LDS pipe that serves ds_bpermute is otherwise idle there); the latency-bound backward did not change.
-__device__ __forceinline__ float swap_half(float v) { return __shfl_xor(v, 32, 64); }
+// The LinearAttention backward kernels' operand helpers (k_la_bwd.h, k_la_long.hip).
+// This lane's operand slice of a per-position / per-d channel vector: v[c = la_chan(C, j, half)] (zero beyond C)
+template <int C>
+__device__ __forceinline__ float own_of(const float (&v)[C], int j, int half) {
+  const int c0 = la_chan(C, j, 0), c1 = la_chan(C, j, 1);
+  const float lo = c0 < C ? v[c0 < C ? c0 : 0] : 0.f, hi = c1 < C ? v[c1 < C ? c1 : 0] : 0.f;
+  return half ? hi : lo;
+}
+// sum_r mfma4(A = src[(4*g + (lane&3)) * pitch + off + rmap(r, half)], B = t[r]) on two interleaved accumulator chains (a
+// dependent 4x4x1 MFMA issues every ~14.5 cycles, independent ones every ~8.5)
+__device__ __forceinline__ f32x4 chain4(const float* src, int pitch, int off, int g, const f32x16& t, int lane, int half) {
+  const float* ar = src + (g * 4 + (lane & 3)) * pitch + off + 4 * half;
+  f32x4 t0 = {0.f, 0.f, 0.f, 0.f}, t1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int q4 = 0; q4 < 4; ++q4) {
+    const float4 a4 = *reinterpret_cast<const float4*>(ar + 8 * q4);
+    t0 = mfma4(a4.x, t[q4 * 4 + 0], t0); t1 = mfma4(a4.y, t[q4 * 4 + 1], t1);
+    t0 = mfma4(a4.z, t[q4 * 4 + 2], t0); t1 = mfma4(a4.w, t[q4 * 4 + 3], t1);
+  }
+  return t0 + t1;
+}
 
 // X^T Y over all 16 registers
 __device__ __forceinline__ f32x16 xty(const f32x16& x, const f32x16& y, f32x16 acc) {
 #pragma unroll
-  for (int r = 0; r < 16; ++r) acc = mfma_f32(x[r], y[r], acc);
+  for (int r = 0; r < 16; ++r) acc = mfma32(x[r], y[r], acc);
   return acc;
 }
 
-// 32x32 transpose of an accumulator tile through a wave-private LDS tile [32][33] (conflict-free both ways), in two halves: the tile is
-// put down where its registers end their life and taken up, transposed, where the transposed form is first needed
-__device__ __forceinline__ void transpose_put(const f32x16& a, float* tile, int col, int half) {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
+// ---- 32x32 transposes of an accumulator tile through a wave-private LDS tile: two layouts, the row pitch in the name.
+// Pitch 33, [32][33] (conflict-free both ways), in two halves: the tile is put down where its registers end their life and taken up,
+// transposed, where the transposed form is first needed
+__device__ __forceinline__ void transpose_put33(const f32x16& a, float* tile, int col, int half) {
+  wave_fence();
 #pragma unroll
   for (int r = 0; r < 16; ++r) tile[rmap(r, half) * 33 + col] = a[r];
 }
-__device__ __forceinline__ f32x16 transpose_get(const float* tile, int col, int half) {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
+__device__ __forceinline__ f32x16 transpose_get33(const float* tile, int col, int half) {
+  wave_fence();
   f32x16 o;
 #pragma unroll
   for (int r = 0; r < 16; ++r) o[r] = tile[col * 33 + rmap(r, half)];
   return o;
 }
-__device__ __forceinline__ f32x16 transpose_tile(f32x16 a, float* tile, int col, int half) {
-  transpose_put(a, tile, col, half);
-  return transpose_get(tile, col, half);
+__device__ __forceinline__ f32x16 transpose_tile33(f32x16 a, float* tile, int col, int half) {
+  transpose_put33(a, tile, col, half);
+  return transpose_get33(tile, col, half);
+}
+// Pitch 36, [32][TRP36]: written as 16 dwords per lane (a row's 32 lanes are consecutive: conflict-free), read back as FOUR 16-byte
+// reads -- registers 4 q .. 4 q + 3 are rows 8 q + 4 half .. + 3 of the transposed tile, consecutive in memory; the row pitch of 36
+// floats keeps them 16-byte aligned and spreads a 16-lane phase over all 64 banks (36 col mod 64 takes every multiple of 4 once).
+// With pitch 33 the reads are eight ds_read2_b32 per transpose.
+constexpr int TRP36 = 36;
+__device__ __forceinline__ f32x16 transpose_tile36(f32x16 a, float* tile, int col, int half) {
+  wave_fence();
+#pragma unroll
+  for (int r = 0; r < 16; ++r) tile[rmap(r, half) * TRP36 + col] = a[r];
+  wave_fence();
+  f32x16 o;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float4 v = *reinterpret_cast<const float4*>(tile + col * TRP36 + 8 * q + 4 * half);
+    o[4 * q + 0] = v.x; o[4 * q + 1] = v.y; o[4 * q + 2] = v.z; o[4 * q + 3] = v.w;
+  }
+  return o;
 }
 
 // keep element (row in registers, column on the lane) only where row / N == col / N  (pairs inside one m/z row)

@@ -26,8 +26,6 @@
 namespace dq {
 
 
-constexpr float ATT_SCALE = 0.17677669529663687f;  // 32^-0.5
-constexpr float LOG2E = 1.4426950408889634f;
 
 // ---- RoPE, in place.  sign = +1 forward, -1 backward (transpose of the rotation).
 // (blockIdx.y selects one of up to two tensors: q and k of the same attention in ONE launch)
@@ -295,13 +293,13 @@ __global__ void __launch_bounds__(256, 2) k_attn_bwd_kv(const float* __restrict_
     {
       const f32x16 Qt = Qn;  // rows d, col i
       Qn = tile_ch_rows(qb, RT, min(i0 + 128, ilast), col, half, ATT_SCALE);
-      transpose_put(Qt, tq, col, half);
+      transpose_put33(Qt, tq, col, half);
       S = xty6<true>(split_tile(Qt), Ks, f32x16{0});  // rows i, col j: the transpose of the forward's S^T bit for bit
     }
     {
       const f32x16 dOt = dOn;  // rows e, col i
       dOn = tile_ch_rows(dob, RT, min(i0 + 128, ilast), col, half, 1.f);
-      transpose_put(dOt, tdo, col, half);
+      transpose_put33(dOt, tdo, col, half);
       dP = xty6<true>(split_tile(dOt), Vs, f32x16{0});  // rows i, col j
     }
 #pragma unroll
@@ -310,9 +308,9 @@ __global__ void __launch_bounds__(256, 2) k_attn_bwd_kv(const float* __restrict_
       dP[r] = S[r] * (dP[r] - dlr[r]);                         // dS
     }
     __builtin_amdgcn_sched_barrier(0);
-    dVa = xty6(split_tile(transpose_get(tdo, col, half)), split_tile(S), dVa);   // dO as rows i, col e
+    dVa = xty6(split_tile(transpose_get33(tdo, col, half)), split_tile(S), dVa);   // dO as rows i, col e
     __builtin_amdgcn_sched_barrier(0);
-    dKa = xty6(split_tile(transpose_get(tq, col, half)), split_tile(dP), dKa);   // Q as rows i, col d
+    dKa = xty6(split_tile(transpose_get33(tq, col, half)), split_tile(dP), dKa);   // Q as rows i, col d
   }
   if (wv > 0) {
 #pragma unroll

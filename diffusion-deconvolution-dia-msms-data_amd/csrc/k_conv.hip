@@ -9,6 +9,7 @@
 // are consecutive positions => coalesced 256-B wave accesses per channel.  Weights are read through
 // wave-uniform addresses (scalar loads).  No LDS.
 #include "dq_common.h"
+#include "dq_wave.h"
 #include "dq_kernels.h"
 #include <cstdlib>
 
@@ -802,7 +803,6 @@ __global__ void __launch_bounds__(256) k_wgrad_reduce_multi(WgradMulti m) {
 // and its per-lane 4-byte accesses at a row pitch of C n floats touch 32 cache lines per instruction: 30 .. 70 us per launch next to the main
 // chain's kernels for 2.4 MB of operands.  With those launches SKIPPED the train step is 0.114 ms shorter (3.472 -> 3.358 ms,
 // profiles/r05_ab_skip_deep_wgrad.log): that is what the side queue's largest tenant costs the main chain.
-typedef float wr_f32x4 __attribute__((ext_vector_type(4)));
 template <int N>
 __global__ void __launch_bounds__(256) k_wgrad_rows(WgradMulti m, int count, int ntiles) {
   const int lane = threadIdx.x & 63, g = lane >> 4, i = lane & 15, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -812,12 +812,12 @@ __global__ void __launch_bounds__(256) k_wgrad_rows(WgradMulti m, int count, int
   else if (wv == 1) { if (count > 1) jz[0] = 1; }
   else if (wv == 2) { if (count > 1 && m.c[1].cinA + m.c[1].cinB > 16) { jz[0] = 1; jt[0] = 1; } }
   else { if (count > 2) { jz[0] = 2; if (m.c[2].cinA + m.c[2].cinB > 16) { jz[1] = 2; jt[1] = 1; } } }
-  wr_f32x4 acc[2][3];
+  f32x4 acc[2][3];
   float bsum[2] = {0.f, 0.f};
 #pragma unroll
   for (int j = 0; j < 2; ++j)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) acc[j][k] = wr_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < 3; ++k) acc[j][k] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int rows = m.c[0].rows;
 #pragma unroll 1
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -850,13 +850,13 @@ __global__ void __launch_bounds__(256) k_wgrad_rows(WgradMulti m, int count, int
             const int q = p + k - 1;
             if (q < 0 || q >= N) continue;  // (zero padding at the row ends; compile time)
 #pragma unroll
-            for (int s = 0; s < 4; ++s) acc[j][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[p][s], B[q][s], acc[j][k], 0, 0, 0);
+            for (int s = 0; s < 4; ++s) acc[j][k] = mfma16(A[p][s], B[q][s], acc[j][k]);
           }
       } else {
 #pragma unroll
         for (int p = 0; p < N; ++p)
 #pragma unroll
-          for (int s = 0; s < 4; ++s) acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[p][s], B[p][s], acc[j][0], 0, 0, 0);
+          for (int s = 0; s < 4; ++s) acc[j][0] = mfma16(A[p][s], B[p][s], acc[j][0]);
       }
       if (jt[j] == 0) {
 #pragma unroll
@@ -885,11 +885,7 @@ __global__ void __launch_bounds__(256) k_wgrad_rows(WgradMulti m, int count, int
       }
     }
     if (jt[j] == 0) {  // bias: lane (g, i) holds the sum over its rows 4 s + g of channel i; the four lane groups meet through v_permlane swaps
-      float t = bsum[j];
-      const auto x1 = __builtin_amdgcn_permlane16_swap(__float_as_int(t), __float_as_int(t), false, false);
-      t = __int_as_float(x1[0]) + __int_as_float(x1[1]);
-      const auto x2 = __builtin_amdgcn_permlane32_swap(__float_as_int(t), __float_as_int(t), false, false);
-      t = __int_as_float(x2[0]) + __int_as_float(x2[1]);
+      const float t = gsum4(bsum[j]);
       if (g == 0 && i < a.cout) part[nelem_w + i] = t;
     }
   }

@@ -16,6 +16,7 @@
 // A workgroup walks several 256-position tiles of one sample and leaves [dW | dbias] in its slot; k_res_wg_reduce sums the slots in
 // block order into the flat gradient buffer (a conv's weight and bias are adjacent there).  No atomics: bitwise repeatable.
 #include "dq_common.h"
+#include "dq_wave.h"
 #include "dq_kernels.h"
 #include "k_res_common.h"
 #include "dq_probe.h"
@@ -25,8 +26,6 @@ namespace dq {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float lane_m1(float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138, 0xF, 0xF, true)); }
 __device__ __forceinline__ float lane_p1(float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x130, 0xF, 0xF, true)); }
 __device__ __forceinline__ float lane_x1(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false)); }  // lane ^ 1

@@ -224,7 +224,7 @@ __global__ void __launch_bounds__(WM * WN * 64) k_gemm(GemmK g) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int jn = 0; jn < TN; ++jn) acc[i][jn] = mfma_f32(av[i][q], bv[jn][q], acc[i][jn]);
+          for (int jn = 0; jn < TN; ++jn) acc[i][jn] = mfma32(av[i][q], bv[jn][q], acc[i][jn]);
     }
     if (more) {
       ta.store(as[(kt + 1) & 1], tid);

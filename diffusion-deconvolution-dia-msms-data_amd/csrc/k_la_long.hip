@@ -22,16 +22,6 @@ namespace dq {
 
 namespace {
 
-typedef float lf32x4 __attribute__((ext_vector_type(4)));
-// v_mfma_f32_4x4x1_16b_f32: block = lane >> 2; register i of lane (blk, j) += A_blk[i] * B_blk[j]
-__device__ __forceinline__ lf32x4 lmfma4(float a, float b, lf32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ void lfence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-constexpr float L_LOG2E = 1.4426950408889634f;
-constexpr float L_SCALE = 0.17677669529663687f;  // 32^-0.5
-
 template <int C, int NJ>
 __device__ __forceinline__ void load_block(const float* __restrict__ src, int64_t row, int N, int pos, int half, float* out) {
 #pragma unroll
@@ -74,33 +64,21 @@ template <int NJ>
 __device__ __forceinline__ f32x16 proj_a(const float* xh, const float* w) {  // A = xh, B = w  -> (rows n, col o)
   f32x16 t = {0};
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) t = mfma_f32(xh[j], w[j], t);
+  for (int j = 0; j < NJ; ++j) t = mfma32(xh[j], w[j], t);
   return t;
 }
 template <int NJ>
 __device__ __forceinline__ f32x16 proj_b(const float* w, const float* xh) {  // A = w, B = xh  -> (rows o, col n)
   f32x16 t = {0};
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) t = mfma_f32(w[j], xh[j], t);
+  for (int j = 0; j < NJ; ++j) t = mfma32(w[j], xh[j], t);
   return t;
 }
 
-// sum_r mfma4(A = src[(4*g + (lane&3)) * 32 + rmap(r, half)], B = t[r]) on two interleaved chains
-__device__ __forceinline__ lf32x4 chain32(const float* src, int g, const f32x16& t, int lane, int half) {
-  const float* ar = src + (g * 4 + (lane & 3)) * 32 + 4 * half;
-  lf32x4 t0 = {0.f, 0.f, 0.f, 0.f}, t1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int q4 = 0; q4 < 4; ++q4) {
-    const float4 a4 = *reinterpret_cast<const float4*>(ar + 8 * q4);
-    t0 = lmfma4(a4.x, t[q4 * 4 + 0], t0); t1 = lmfma4(a4.y, t[q4 * 4 + 1], t1);
-    t0 = lmfma4(a4.z, t[q4 * 4 + 2], t0); t1 = lmfma4(a4.w, t[q4 * 4 + 3], t1);
-  }
-  return t0 + t1;
-}
-
+// (the 4x4x1 operand chain over a [c][32] image -- chain4 at pitch 32, offset 0 -- and own_of: dq_mfma.h)
 // online softmax-weighted accumulation of one block into (m, ssum, mt): kT holds log2-domain logits (rows n, col d)
 template <int CG>
-__device__ __forceinline__ void online_m(f32x16 kT, const float* xs, float& m, float& ssum, lf32x4 (&mt)[CG], int lane, int half) {
+__device__ __forceinline__ void online_m(f32x16 kT, const float* xs, float& m, float& ssum, f32x4 (&mt)[CG], int lane, int half) {
   float bm = kT[0];
 #pragma unroll
   for (int r = 1; r < 16; ++r) bm = fmaxf(bm, kT[r]);
@@ -116,7 +94,7 @@ __device__ __forceinline__ void online_m(f32x16 kT, const float* xs, float& m, f
   ssum = fmaf(ssum, al, s);
   m = mn;
 #pragma unroll
-  for (int g = 0; g < CG; ++g) mt[g] = mt[g] * al + chain32(xs, g, kT, lane, half);
+  for (int g = 0; g < CG; ++g) mt[g] = mt[g] * al + chain4(xs, 32, 0, g, kT, lane, half);
 }
 
 __device__ __forceinline__ f32x16 q_exp(f32x16 q, float& qs) {  // un-normalised exps; qs = 32^-0.5 / sum
@@ -131,15 +109,8 @@ __device__ __forceinline__ f32x16 q_exp(f32x16 q, float& qs) {  // un-normalised
     s += q[r];
   }
   s += swap_half(s);
-  qs = L_SCALE * fast_rcp(s);
+  qs = ATT_SCALE * fast_rcp(s);
   return q;
-}
-
-template <int C>
-__device__ __forceinline__ float own_of(const float (&v)[C], int j, int half) {
-  const int c0 = la_chan(C, j, 0), c1 = la_chan(C, j, 1);
-  const float lo = c0 < C ? v[c0 < C ? c0 : 0] : 0.f, hi = c1 < C ? v[c1 < C ? c1 : 0] : 0.f;
-  return half ? hi : lo;
 }
 
 template <int C>
@@ -188,16 +159,16 @@ __global__ void __launch_bounds__(256) k_linattn_fwd_long(LinAttn a) {
   // ---- sweep 1: M of the four heads, online softmax over the blocks
   {
     float wk[4][NJ], m[4], ssum[4];
-    lf32x4 mt[4][CG];
+    f32x4 mt[4][CG];
 #pragma unroll
     for (int hd = 0; hd < 4; ++hd) {
       m[hd] = -INFINITY; ssum[hd] = 0.f;
 #pragma unroll
-      for (int g = 0; g < CG; ++g) mt[hd][g] = lf32x4{0.f, 0.f, 0.f, 0.f};
+      for (int g = 0; g < CG; ++g) mt[hd][g] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const int c = la_chan(C, j, half);
-        wk[hd][j] = c < C ? a.w_qkv[(128 + hd * 32 + col) * C + c] * L_LOG2E : 0.f;
+        wk[hd][j] = c < C ? a.w_qkv[(128 + hd * 32 + col) * C + c] * LOG2E : 0.f;
       }
     }
 #pragma unroll 1
@@ -205,9 +176,9 @@ __global__ void __launch_bounds__(256) k_linattn_fwd_long(LinAttn a) {
       float x[NJ], xh[NJ];
       load_block<C, NJ>(a.x, row, N, b * 32 + col, half, x);
       prenorm<C, NJ>(x, gpre, xh);
-      lfence();
+      wave_fence();
       stage_cn<C, NJ>(xs, xh, col, half);
-      lfence();
+      wave_fence();
 #pragma unroll
       for (int hd = 0; hd < 4; ++hd) {
         f32x16 kT = proj_a<NJ>(xh, wk[hd]);
@@ -226,7 +197,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd_long(LinAttn a) {
           if (half == 0) ms[(hd * C + g * 4 + i) * 32 + col] = v;
         }
     }
-    lfence();
+    wave_fence();
   }
 
   // ---- sweep 2: finish every block
@@ -236,7 +207,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd_long(LinAttn a) {
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int c = la_chan(C, j, half);
-      wq[hd][j] = c < C ? a.w_qkv[(hd * 32 + col) * C + c] * L_LOG2E : 0.f;
+      wq[hd][j] = c < C ? a.w_qkv[(hd * 32 + col) * C + c] * LOG2E : 0.f;
     }
 #pragma unroll 1
   for (int b = 0; b < NB; ++b) {
@@ -253,7 +224,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd_long(LinAttn a) {
       float P[C];
 #pragma unroll
       for (int g = 0; g < CG; ++g) {
-        const lf32x4 pp = chain32(ms + hd * C * 32, g, q, lane, half);
+        const f32x4 pp = chain4(ms + hd * C * 32, 32, 0, g, q, lane, half);
 #pragma unroll
         for (int i = 0; i < 4; ++i) P[g * 4 + i] = pp[i] + swap_half(pp[i]);
       }
@@ -335,17 +306,17 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
 
   auto chainw = [&](int m, int hd, int g, const f32x16& t) {  // A = wp_lds[m][hd][half][c = 4*g + (lane&3)][r]
     const float* wr = wp_lds + (((m * 4 + hd) * 2 + half) * C + g * 4 + (lane & 3)) * 16;
-    lf32x4 t0 = {0.f, 0.f, 0.f, 0.f}, t1 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 t0 = {0.f, 0.f, 0.f, 0.f}, t1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int r4 = 0; r4 < 4; ++r4) {
       const float4 w4 = *reinterpret_cast<const float4*>(wr + r4 * 4);
-      t0 = lmfma4(w4.x, t[r4 * 4 + 0], t0); t1 = lmfma4(w4.y, t[r4 * 4 + 1], t1);
-      t0 = lmfma4(w4.z, t[r4 * 4 + 2], t0); t1 = lmfma4(w4.w, t[r4 * 4 + 3], t1);
+      t0 = mfma4(w4.x, t[r4 * 4 + 0], t0); t1 = mfma4(w4.y, t[r4 * 4 + 1], t1);
+      t0 = mfma4(w4.z, t[r4 * 4 + 2], t0); t1 = mfma4(w4.w, t[r4 * 4 + 3], t1);
     }
     return t0 + t1;
   };
   // dxh[c][pos] (=|+=) both halves' sums of part; each lane stores its own channels
-  auto dxh_store = [&](int64_t row, int pos, const lf32x4 (&part)[CG], bool first) {
+  auto dxh_store = [&](int64_t row, int pos, const f32x4 (&part)[CG], bool first) {
     float full[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) full[c] = part[c >> 2][c & 3] + swap_half(part[c >> 2][c & 3]);
@@ -366,15 +337,15 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int c = la_chan(C, j, half);
-      wq[j] = c < C ? a.w_qkv[(hd * 32 + col) * C + c] * L_LOG2E : 0.f;
-      wk[j] = c < C ? a.w_qkv[(128 + hd * 32 + col) * C + c] * L_LOG2E : 0.f;
+      wq[j] = c < C ? a.w_qkv[(hd * 32 + col) * C + c] * LOG2E : 0.f;
+      wk[j] = c < C ? a.w_qkv[(128 + hd * 32 + col) * C + c] * LOG2E : 0.f;
     }
-    lf32x4 gq[CG], gk[CG], gw2[CG][CG];
+    f32x4 gq[CG], gk[CG], gw2[CG][CG];
 #pragma unroll
     for (int g = 0; g < CG; ++g) {
-      gq[g] = gk[g] = lf32x4{0.f, 0.f, 0.f, 0.f};
+      gq[g] = gk[g] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int g2 = 0; g2 < CG; ++g2) gw2[g][g2] = lf32x4{0.f, 0.f, 0.f, 0.f};
+      for (int g2 = 0; g2 < CG; ++g2) gw2[g][g2] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 
 #pragma unroll 1
@@ -384,24 +355,24 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
       float m = -INFINITY, ssum = 0.f;
       float Mr[C];
       {
-        lf32x4 mt[CG];
+        f32x4 mt[CG];
 #pragma unroll
-        for (int g = 0; g < CG; ++g) mt[g] = lf32x4{0.f, 0.f, 0.f, 0.f};
+        for (int g = 0; g < CG; ++g) mt[g] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
         for (int b = 0; b < NB; ++b) {
           float x[NJ], xh[NJ];
           load_block<C, NJ>(a.x, row, N, b * 32 + col, half, x);
           prenorm<C, NJ>(x, gpre, xh);
-          lfence();
+          wave_fence();
           stage_cn<C, NJ>(xs, xh, col, half);
-          lfence();
+          wave_fence();
           f32x16 kT = proj_a<NJ>(xh, wk);
           if (RAGGED) kT = mask_tail(kT, b * 32, N, half);
           online_m<CG>(kT, xs, m, ssum, mt, lane, half);
         }
         ssum += swap_half(ssum);
         const float rs = fast_rcp(ssum);
-        lfence();
+        wave_fence();
 #pragma unroll
         for (int g = 0; g < CG; ++g)
 #pragma unroll
@@ -409,12 +380,12 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
             Mr[g * 4 + i] = (mt[g][i] + swap_half(mt[g][i])) * rs;
             if (half == 0) ms[(g * 4 + i) * 32 + col] = Mr[g * 4 + i];
           }
-        lfence();
+        wave_fence();
       }
       // ---- sweep 2: q side
-      lf32x4 dmt[CG];
+      f32x4 dmt[CG];
 #pragma unroll
-      for (int g = 0; g < CG; ++g) dmt[g] = lf32x4{0.f, 0.f, 0.f, 0.f};
+      for (int g = 0; g < CG; ++g) dmt[g] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
       for (int b = 0; b < NB; ++b) {
         const int pos = b * 32 + col;
@@ -422,10 +393,10 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
         load_block<C, NJ>(a.x, row, N, pos, half, x);
         load_block<C, NJ>(a.dyp, row, N, pos, half, dy);
         prenorm<C, NJ>(x, gpre, xh);
-        lfence();
+        wave_fence();
         stage_cn<C, NJ>(xs, xh, col, half);
         stage_cn<C, NJ>(dys, dy, col, half);
-        lfence();
+        wave_fence();
         float qs;
         f32x16 q = q_exp(proj_b<NJ>(wq, xh), qs);
 #pragma unroll
@@ -449,7 +420,7 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
         }
 #pragma unroll
         for (int g = 0; g < CG; ++g) {
-          const lf32x4 pp = chain32(ms, g, q, lane, half);
+          const f32x4 pp = chain4(ms, 32, 0, g, q, lane, half);
 #pragma unroll
           for (int i = 0; i < 4; ++i) P[g * 4 + i] = pp[i] + swap_half(pp[i]);
         }
@@ -460,25 +431,25 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
         // dQ = M dP (K = C), softmax backward, Wq paths
         f32x16 dq = {0};
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) dq = mfma_f32(own_of<C>(Mr, j, half), own_of<C>(dP, j, half), dq);
+        for (int j = 0; j < NJ; ++j) dq = mfma32(own_of<C>(Mr, j, half), own_of<C>(dP, j, half), dq);
         float t = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) t = fmaf(q[r], dq[r], t);
-        t = (t + swap_half(t)) * (1.0f / L_SCALE);
+        t = (t + swap_half(t)) * (1.0f / ATT_SCALE);
         f32x16 dq_raw;
 #pragma unroll
         for (int r = 0; r < 16; ++r) dq_raw[r] = q[r] * (dq[r] - t);
-        lf32x4 part[CG];
+        f32x4 part[CG];
 #pragma unroll
         for (int g = 0; g < CG; ++g) part[g] = chainw(0, hd, g, dq_raw);
         dxh_store(row, pos, part, hd == 0);
-        const f32x16 dq_rawT = transpose_tile(dq_raw, tile, col, half);
-        const f32x16 qT = transpose_tile(q, tile, col, half);
-        lfence();  // ps / dps of this block complete
+        const f32x16 dq_rawT = transpose_tile33(dq_raw, tile, col, half);
+        const f32x16 qT = transpose_tile33(q, tile, col, half);
+        wave_fence();  // ps / dps of this block complete
 #pragma unroll
         for (int g = 0; g < CG; ++g) {
-          gq[g] += chain32(xs, g, dq_rawT, lane, half);
-          dmt[g] += chain32(dps, g, qT, lane, half);
+          gq[g] += chain4(xs, 32, 0, g, dq_rawT, lane, half);
+          dmt[g] += chain4(dps, 32, 0, g, qT, lane, half);
         }
         // dW2[c'][c] += sum_n dYpre[c'][n] P[c][n] over this block: position n = 16 * s + (lane >> 2)
 #pragma unroll
@@ -488,14 +459,14 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
           for (int g1 = 0; g1 < CG; ++g1) {
             const float av = dys[(4 * g1 + (lane & 3)) * 32 + n];
 #pragma unroll
-            for (int g2 = 0; g2 < CG; ++g2) gw2[g1][g2] = lmfma4(av, ps[(4 * g2 + (lane & 3)) * 32 + n], gw2[g1][g2]);
+            for (int g2 = 0; g2 < CG; ++g2) gw2[g1][g2] = mfma4(av, ps[(4 * g2 + (lane & 3)) * 32 + n], gw2[g1][g2]);
           }
         }
       }
       // dM (both halves), its [c][d] image, and sum_n dK K = sum_c dM M
       float dMr[C];
       float dl = 0.f;
-      lfence();
+      wave_fence();
 #pragma unroll
       for (int g = 0; g < CG; ++g)
 #pragma unroll
@@ -504,7 +475,7 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
           dl = fmaf(dMr[g * 4 + i], Mr[g * 4 + i], dl);
           if (half == 0) dms[(g * 4 + i) * 32 + col] = dMr[g * 4 + i];
         }
-      lfence();
+      wave_fence();
       const float rs = fast_rcp(ssum);
       // ---- sweep 3: k side
 #pragma unroll 1
@@ -513,26 +484,26 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
         float x[NJ], xh[NJ];
         load_block<C, NJ>(a.x, row, N, pos, half, x);
         prenorm<C, NJ>(x, gpre, xh);
-        lfence();
+        wave_fence();
         stage_cn<C, NJ>(xs, xh, col, half);
-        lfence();
+        wave_fence();
         f32x16 kT = proj_a<NJ>(xh, wk);
         if (RAGGED) kT = mask_tail(kT, b * 32, N, half);  // exp2(-inf) = 0: no key beyond the row
 #pragma unroll
         for (int r = 0; r < 16; ++r) kT[r] = __builtin_amdgcn_exp2f(kT[r] - m) * rs;  // normalised K^T
         f32x16 dkT = {0};
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) dkT = mfma_f32(xh[j], own_of<C>(dMr, j, half), dkT);
+        for (int j = 0; j < NJ; ++j) dkT = mfma32(xh[j], own_of<C>(dMr, j, half), dkT);
         f32x16 dk_rawT;
 #pragma unroll
         for (int r = 0; r < 16; ++r) dk_rawT[r] = kT[r] * (dkT[r] - dl);
 #pragma unroll
-        for (int g = 0; g < CG; ++g) gk[g] += chain32(xs, g, dk_rawT, lane, half);
-        const f32x16 dk_raw = transpose_tile(dk_rawT, tile, col, half);
-        const f32x16 Kd = transpose_tile(kT, tile, col, half);
-        lf32x4 part[CG];
+        for (int g = 0; g < CG; ++g) gk[g] += chain4(xs, 32, 0, g, dk_rawT, lane, half);
+        const f32x16 dk_raw = transpose_tile33(dk_rawT, tile, col, half);
+        const f32x16 Kd = transpose_tile33(kT, tile, col, half);
+        f32x4 part[CG];
 #pragma unroll
-        for (int g = 0; g < CG; ++g) part[g] = chainw(1, hd, g, dk_raw) + chain32(dms, g, Kd, lane, half);
+        for (int g = 0; g < CG; ++g) part[g] = chainw(1, hd, g, dk_raw) + chain4(dms, 32, 0, g, Kd, lane, half);
         dxh_store(row, pos, part, false);
       }
     }
@@ -550,7 +521,7 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
           slot[(128 + hd * 32 + col) * C + c] = vk;
         }
       }
-    lfence();
+    wave_fence();
 #pragma unroll
     for (int g1 = 0; g1 < CG; ++g1)
 #pragma unroll
@@ -561,7 +532,7 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
           v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
           if (lane < 4) w2g[(4 * g1 + i) * C + 4 * g2 + lane] = v;
         }
-    lfence();
+    wave_fence();
     {
       float wvr[C], wor[C];
 #pragma unroll

@@ -23,6 +23,7 @@
 // dWv = Wo^T dW2 and dWo = dW2 Wv^T follow once per layer from the slot sum (k_linattn_dwvo).  A workgroup leaves ONE slot in the layout of
 // k_la_bwd.hip (la_slot(C)): the ordered slot reduce is unchanged and the step stays bitwise repeatable.
 #include "dq_common.h"
+#include "dq_wave.h"
 #include "dq_kernels.h"
 #include "dq_options.h"
 #include "dq_probe.h"
@@ -33,8 +34,6 @@ namespace dq {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 // Sum over the four lanes {row, row + 16, row + 32, row + 48} (every lane receives it) ON THE MATRIX PIPE: a 16x16x4 product sums over
 // k = lane / 16, so with A = 1 every output row is sum_g B[g][row].  One MFMA (the pipe is two-thirds idle in this kernel) instead of two
 // v_permlane swaps, their register copies and two adds on the VALU, which is what bounds the kernel.
@@ -44,30 +43,9 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __bu
 template <bool ON_MFMA>
 __device__ __forceinline__ float gsum_t(float t) {
   if (ON_MFMA) return mfma16(1.0f, t, f32x4{0.f, 0.f, 0.f, 0.f})[0];
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_int(t), __float_as_int(t), false, false);
-  t = __int_as_float(a[0]) + __int_as_float(a[1]);
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_int(t), __float_as_int(t), false, false);
-  return __int_as_float(b[0]) + __int_as_float(b[1]);
+  return gsum4(t);
 }
-// the maximum stays on the VALU: v_permlane16_swap (rows 0 <-> 1, 2 <-> 3), v_permlane32_swap (halves) (tools/probe/blocks_sum.hip pins the semantics)
-__device__ __forceinline__ float gmax(float t) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_int(t), __float_as_int(t), false, false);
-  t = fmaxf(__int_as_float(a[0]), __int_as_float(a[1]));
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_int(t), __float_as_int(t), false, false);
-  return fmaxf(__int_as_float(b[0]), __int_as_float(b[1]));
-}
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-// sum over the 16 lanes of a row (every lane receives it): four DPP adds
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));  // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));  // row_mirror
-  return v;
-}
+// (the maximum stays on the VALU: gmax4, dq_wave.h)
 
 struct LaRowsBwdK {
   const float* x; const float* ypre; const float* dy; float* dx;
@@ -95,7 +73,6 @@ __global__ void __launch_bounds__(256, 2) k_la_rows_bwd(LaRowsBwdK a) {
   constexpr int LS = LA_ROWS_LANE_FLOATS;  // image floats per (head, lane)
   constexpr int UP = 17;                // pitch of the [channel][row] transposes (conflict-free both ways)
   constexpr int TP = 48;                // pitch of the [row][d] transposes: 16-byte stores, the two lane groups of a read phase 16 banks apart
-  constexpr float scale = 0.17677669529663687f;  // dim_head^-0.5 (unet1d.py:481)
   auto gsum = [](float t) __attribute__((always_inline)) { return gsum_t<N == 2>(t); };
   // LDS: the operand image of the four heads ([head][lane][LS]: a wave reads only its head's quarter, 16 bytes at a time, at the point of use --
   // held in registers the 36 values per lane cost the second wave per SIMD at 4 positions; read from global memory per tile they were five
@@ -286,13 +263,13 @@ __global__ void __launch_bounds__(256, 2) k_la_rows_bwd(LaRowsBwdK a) {
           mx = qs[n][0][0];
 #pragma unroll
           for (int e = 1; e < 8; ++e) mx = fmaxf(mx, qs[n][e >> 2][e & 3]);
-          mx = gmax(mx);
+          mx = gmax4(mx);
         }
         float sum = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) { qs[n][e >> 2][e & 3] = __builtin_amdgcn_exp2f(qs[n][e >> 2][e & 3] - mx); sum += qs[n][e >> 2][e & 3]; }
         sum = gsum(sum);
-        const float sc = scale * fast_rcp(sum);
+        const float sc = ATT_SCALE * fast_rcp(sum);
 #pragma unroll
         for (int e = 0; e < 8; ++e) qs[n][e >> 2][e & 3] *= sc;
       }
@@ -319,12 +296,12 @@ __global__ void __launch_bounds__(256, 2) k_la_rows_bwd(LaRowsBwdK a) {
 #pragma unroll
           for (int m = 0; m < N; ++m) z[r] = fmaf(Sn[m], xh[m][r], z[r]);
         float* tz = (n & 1) ? t1 : t0;
-        wsync();
+        wave_fence();
         *reinterpret_cast<float4*>(tz + row * TP + 4 * g) = make_float4(z[0], z[1], z[2], z[3]);
         f32x4 dZ = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < CPL; ++s) dZ = mfma16(aw2[s], DY[n][s], dZ);
-        wsync();
+        wave_fence();
 #pragma unroll
         for (int s = 0; s < 4; ++s) gw = mfma16(ud[(n * 16 + row) * UP + 4 * s + g], tz[(4 * s + g) * TP + row], gw);
 #pragma unroll
@@ -357,7 +334,7 @@ __global__ void __launch_bounds__(256, 2) k_la_rows_bwd(LaRowsBwdK a) {
             D += qd;
             T[t][r] += qd;
           }
-        D = gsum(D) * (1.0f / scale);
+        D = gsum(D) * (1.0f / ATT_SCALE);
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int r = 0; r < CPL; ++r) acc[r] = dxh[n][r];
@@ -372,10 +349,10 @@ __global__ void __launch_bounds__(256, 2) k_la_rows_bwd(LaRowsBwdK a) {
         for (int r = 0; r < CPL; ++r) dxh[n][r] = acc[r];
         // dql as [row][d] -> A operand of dWq (M = d, K = rows)
         float* tq = (n & 1) ? t1 : t0;
-        wsync();
+        wave_fence();
         *reinterpret_cast<float4*>(tq + row * TP + 4 * g) = make_float4(dq[0][0], dq[0][1], dq[0][2], dq[0][3]);
         *reinterpret_cast<float4*>(tq + row * TP + 16 + 4 * g) = make_float4(dq[1][0], dq[1][1], dq[1][2], dq[1][3]);
-        wsync();
+        wave_fence();
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           const float xt = ux[(n * 16 + row) * UP + 4 * s + g];  // xh[c = row][batch row 4 s + g] (read here, not held: registers)
@@ -407,10 +384,10 @@ __global__ void __launch_bounds__(256, 2) k_la_rows_bwd(LaRowsBwdK a) {
 #pragma unroll
         for (int r = 0; r < CPL; ++r) dxh[m][r] = acc[r];
         float* tk = (m & 1) ? t1 : t0;
-        wsync();
+        wave_fence();
         *reinterpret_cast<float4*>(tk + row * TP + 4 * g) = make_float4(dk[0][0], dk[0][1], dk[0][2], dk[0][3]);
         *reinterpret_cast<float4*>(tk + row * TP + 16 + 4 * g) = make_float4(dk[1][0], dk[1][1], dk[1][2], dk[1][3]);
-        wsync();
+        wave_fence();
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           const float xt = ux[(m * 16 + row) * UP + 4 * s + g];
@@ -423,7 +400,7 @@ __global__ void __launch_bounds__(256, 2) k_la_rows_bwd(LaRowsBwdK a) {
     DQ_PSTAMP((500000 + C * 100 + N), 7);
     // ---- the four heads' d xh meet: [head][lane][RUN]
     {
-      wsync();  // (this wave's last readers of its tiles are done)
+      wave_fence();  // (this wave's last readers of its tiles are done)
       float* ex = t0 + lane * RUN;
 #pragma unroll
       for (int k = 0; k < NV; ++k) {
@@ -521,7 +498,7 @@ __global__ void __launch_bounds__(256, 2) k_la_rows_bwd(LaRowsBwdK a) {
   if (hd == 0 || hd == 3) {
 #pragma unroll
     for (int r = 0; r < CPL; ++r) {
-      const float s0 = row16_sum(na[r]), s1 = row16_sum(nb[r]);
+      const float s0 = row_sum16(na[r]), s1 = row_sum16(nb[r]);
       if (row == 0) {
         const int c = CPL * g + r;
         if (hd == 0) { slot[GB + c] = s0; slot[GB + C + c] = s1; }

@@ -12,6 +12,7 @@
 // Operands: the first 16 floats per (head, lane) of the rows-backward image (k_linattn_prepare: [q: 8 | k: 8], log2(e) folded in) and the
 // plain W2 of the prepared weights.
 #include "dq_common.h"
+#include "dq_wave.h"
 #include "dq_dev.h"
 #include "dq_kernels.h"
 #include "dq_options.h"
@@ -21,21 +22,6 @@
 namespace dq {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float gsum4(float t) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_int(t), __float_as_int(t), false, false);
-  t = __int_as_float(a[0]) + __int_as_float(a[1]);
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_int(t), __float_as_int(t), false, false);
-  return __int_as_float(b[0]) + __int_as_float(b[1]);
-}
-__device__ __forceinline__ float gmax4(float t) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_int(t), __float_as_int(t), false, false);
-  t = fmaxf(__int_as_float(a[0]), __int_as_float(a[1]));
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_int(t), __float_as_int(t), false, false);
-  return fmaxf(__int_as_float(b[0]), __int_as_float(b[1]));
-}
 
 struct LaRowsFwdK {
   const float* x; float* y; float* ypre;  // ypre: nullable (saved for the backward)
@@ -50,7 +36,6 @@ __global__ void __launch_bounds__(256) k_la_rows_fwd(LaRowsFwdK a) {
   constexpr int CPL = C / 4, RUN = CPL * N;
   constexpr int VW = RUN % 4 == 0 ? 4 : 2, NV = RUN / VW;
   constexpr int LS = LA_ROWS_LANE_FLOATS;
-  constexpr float scale = 0.17677669529663687f;  // dim_head^-0.5 (unet1d.py:481)
   typedef float vecf __attribute__((ext_vector_type(VW)));
   // the heads' y_pre contributions of a tile: [head][position][lane][4]
   __shared__ __attribute__((aligned(16))) float ex[4 * N * 64 * 4];
@@ -148,7 +133,7 @@ __global__ void __launch_bounds__(256) k_la_rows_fwd(LaRowsFwdK a) {
       float sum = 0.f;
 #pragma unroll
       for (int e = 0; e < 8; ++e) { qs[e >> 2][e & 3] = __builtin_amdgcn_exp2f(qs[e >> 2][e & 3] - mx); sum += qs[e >> 2][e & 3]; }
-      const float sc = scale * fast_rcp(gsum4(sum));
+      const float sc = ATT_SCALE * fast_rcp(gsum4(sum));
       float z[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int m = 0; m < N; ++m) {

@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(256, N <= 4 ? 2 : 1) k_la_small(LaSmallK a) { 
   const float* il = img + lane;
   auto chain = [&](int g, const float* b, f32x16 acc) __attribute__((always_inline)) -> f32x16 {
 #pragma unroll
-    for (int i = 0; i < S; ++i) acc = mfma_f32(il[(g * S + i) * 64], b[i], acc);
+    for (int i = 0; i < S; ++i) acc = mfma32(il[(g * S + i) * 64], b[i], acc);
     return acc;
   };
   float gp[S];
@@ -78,7 +78,6 @@ __global__ void __launch_bounds__(256, N <= 4 ? 2 : 1) k_la_small(LaSmallK a) { 
     const int row = tile * 32 + col;
     const bool live = row < a.rows;
     const int valid = a.rows - tile * 32 < 32 ? a.rows - tile * 32 : 32;
-    auto wsync = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
     {
       const float4* g4 = reinterpret_cast<const float4*>(a.x + (int64_t)tile * 32 * E);  // (32 E floats from a 128-byte aligned tile start)
       const int lim4 = valid * E / 4;  // E is a multiple of 4
@@ -86,14 +85,14 @@ __global__ void __launch_bounds__(256, N <= 4 ? 2 : 1) k_la_small(LaSmallK a) { 
 #pragma unroll
       for (int k = 0; k < E / 8; ++k) { const int i4 = k * 64 + lane; raw[k] = g4[i4 < lim4 ? i4 : lim4 - 1]; }
       __builtin_amdgcn_sched_barrier(0);
-      wsync();  // (the previous tile's readers of xt are done)
+      wave_fence();  // (the previous tile's readers of xt are done)
 #pragma unroll
       for (int k = 0; k < E / 8; ++k) {
         const int lin = (k * 64 + lane) * 4, r = lin / E, e = lin - r * E;  // four consecutive floats of one row (E % 4 == 0)
         float* d = xt + r * EP + e;
         d[0] = raw[k].x; d[1] = raw[k].y; d[2] = raw[k].z; d[3] = raw[k].w;
       }
-      wsync();
+      wave_fence();
     }
     const float* xp = xt + col * EP;  // the lane's row: element (c, m) at c * N + m
     float xh[N][S];
@@ -161,7 +160,7 @@ __global__ void __launch_bounds__(256, N <= 4 ? 2 : 1) k_la_small(LaSmallK a) { 
 #pragma unroll
         for (int r = 0; r < 16; ++r) { q[r] = __builtin_amdgcn_exp2f(q[r] - mx); sum += q[r]; }
         sum += swap_half(sum);
-        const float sc = 0.17677669529663687f * fast_rcp(sum);  // softmax, then * dim_head^-0.5
+        const float sc = ATT_SCALE * fast_rcp(sum);  // softmax, then * dim_head^-0.5
 #pragma unroll
         for (int m = 0; m < N; ++m) {
           float t = 0.f;
@@ -212,7 +211,7 @@ __global__ void __launch_bounds__(256, N <= 4 ? 2 : 1) k_la_small(LaSmallK a) { 
       }
     }
     auto flush = [&](float* dst, float (&val)[N][NR]) __attribute__((always_inline)) {
-      wsync();
+      wave_fence();
 #pragma unroll
       for (int n = 0; n < N; ++n)
 #pragma unroll
@@ -220,7 +219,7 @@ __global__ void __launch_bounds__(256, N <= 4 ? 2 : 1) k_la_small(LaSmallK a) { 
           const int co = rmap(j, half);
           if (co < C) xt[col * EP + co * N + n] = val[n][j];
         }
-      wsync();
+      wave_fence();
       float4* g4 = reinterpret_cast<float4*>(dst + (int64_t)tile * 32 * E);
       const int lim4 = valid * E / 4;
 #pragma unroll

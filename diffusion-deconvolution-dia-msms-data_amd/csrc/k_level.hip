@@ -31,6 +31,7 @@
 // A pos_output_only network (unet1d.py:1084, 1166) applies Softplus to final_conv's output before anything reads it (FA instantiations).
 // Every global read of a tile (stage input, the skip channels of cat(x, skip), unet1d.py:1151, 1154) is requested before the first use.
 #include "dq_common.h"
+#include "dq_wave.h"
 #include "dq_kernels.h"
 #include "dq_probe.h"
 #include "../../include/dq_hip.h"  // DQ_PRED_*
@@ -40,8 +41,6 @@ namespace dq {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float lane_m1(float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138, 0xF, 0xF, true)); }
 __device__ __forceinline__ float lane_p1(float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x130, 0xF, 0xF, true)); }
 __host__ __device__ constexpr int pad4(int x) { return (x + 3) / 4 * 4; }

@@ -29,17 +29,7 @@
 
 namespace dq {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-// block = lane >> 2; a lane supplies A_blk[i = lane & 3] and B_blk[j = lane & 3]; register i of lane (blk, j) += A_blk[i] * B_blk[j]
-__device__ __forceinline__ f32x4 mfma4f(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ constexpr int rowmap(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-// (channel map of a lane's x registers: la_nj / la_chan, dq_mfma.h)
-__device__ __forceinline__ float swap32(float v) { return swap_half(v); }  // v_permlane32_swap (dq_mfma.h)
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
+// (wave primitives: dq_wave.h; row map rmap and the channel map of a lane's x registers, la_nj / la_chan: dq_mfma.h)
 
 // ---- split-bf16 form of the K = C projections (kT = xh^T Wk^T, q = Wq xh): an fp32 value is EXACTLY the sum of three bf16 values
 // (H = its top 16 bits, M = the top 16 bits of v - H, L = the rest: 8 + 8 + 8 significant bits), so x w = sum of nine part products; the
@@ -64,7 +54,7 @@ __device__ __forceinline__ void la_split_x(float v, unsigned& d0, unsigned& d1, 
 __device__ __forceinline__ unsigned la_bf16_image_dword(const float* __restrict__ w_qkv, int C, int o, int half, int u, int e) {
   const int dw = 4 * u + e, j = dw / 3, t = dw % 3;
   if (j >= C / 2) return 0u;
-  const float w = w_qkv[o * C + la_chan(C, j, half)] * 1.4426950408889634f;
+  const float w = w_qkv[o * C + la_chan(C, j, half)] * LOG2E;
   const unsigned hb = __float_as_uint(w) & 0xffff0000u;
   const float r = w - __uint_as_float(hb);
   const unsigned mb = __float_as_uint(r) & 0xffff0000u;
@@ -186,7 +176,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
       for (int i = threadIdx.x; i < WQ; i += blockDim.x) {
         const int cc = i & 31, hh = (i >> 5) & 1, j = (i >> 6) % NJ, hd = (i / (64 * NJ)) & 3, m = i / (256 * NJ);
         const int c = la_chan(C, j, hh);
-        wqk_lds[i] = c < C ? a.w_qkv[(m * 128 + hd * 32 + cc) * C + c] * 1.4426950408889634f : 0.f;
+        wqk_lds[i] = c < C ? a.w_qkv[(m * 128 + hd * 32 + cc) * C + c] * LOG2E : 0.f;
       }
     }
   }
@@ -215,14 +205,13 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
   float* xs = xs_lds[wv];
   float* ms = ms_lds[wv];
   const float sqC = sqrtf((float)C);
-  const float scale = 0.17677669529663687f;  // 32^-0.5
   bool bounded;  // (wave-uniform)
   if (a.prep) {
     bounded = __builtin_amdgcn_readfirstlane(__float_as_int(bflag)) != 0;  // (+-0.0f / 1.0f)
   } else if (N > 1) {
     float gm = 0.f;
     for (int c = 0; c < C; ++c) gm = fmaxf(gm, fabsf(a.g_pre[c]));
-    bounded = 1.4426950408889634f * sqrtf(bnd0) * sqC * gm <= 64.f;
+    bounded = LOG2E * sqrtf(bnd0) * sqC * gm <= 64.f;
   } else {
     bounded = false;
   }
@@ -252,7 +241,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
     float ssq = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) ssq = fmaf(X[blk][j], X[blk][j], ssq);
-    ssq += swap32(ssq);
+    ssq += swap_half(ssq);
     const float inv = rms_inv(ssq, sqC);  // (v_sqrt + v_rcp, 1 ulp each: the correctly rounded division / square root are ~20 instructions per use)
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -301,15 +290,15 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
       }
     }
   };
-  // sum_r mfma4(A = src[(4*g + (lane&3)) * pitch + off + rowmap(r, half)], B = t[r]): two interleaved accumulator chains
+  // sum_r mfma4(A = src[(4*g + (lane&3)) * pitch + off + rmap(r, half)], B = t[r]): two interleaved accumulator chains
   auto chain4 = [&](const float* src, int pitch, int off, int g, const f32x16& t) {
     const float* ar = src + (g * 4 + (lane & 3)) * pitch + off + 4 * half;
     f32x4 t0 = {0.f, 0.f, 0.f, 0.f}, t1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int q4 = 0; q4 < 4; ++q4) {
       const float4 a4 = *reinterpret_cast<const float4*>(ar + 8 * q4);
-      t0 = mfma4f(a4.x, t[q4 * 4 + 0], t0); t1 = mfma4f(a4.y, t[q4 * 4 + 1], t1);
-      t0 = mfma4f(a4.z, t[q4 * 4 + 2], t0); t1 = mfma4f(a4.w, t[q4 * 4 + 3], t1);
+      t0 = mfma4(a4.x, t[q4 * 4 + 0], t0); t1 = mfma4(a4.y, t[q4 * 4 + 1], t1);
+      t0 = mfma4(a4.z, t[q4 * 4 + 2], t0); t1 = mfma4(a4.w, t[q4 * 4 + 3], t1);
     }
     return t0 + t1;
   };
@@ -321,7 +310,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
       float xf[C];
 #pragma unroll
       for (int c = 0; c < C; ++c) xf[c] = xs[c * NP + col];
-      add_w2(hd, 0, xf, scale);
+      add_w2(hd, 0, xf, ATT_SCALE);
       continue;
     }
     // weight operands of this head: lane (col, half) supplies W[o_base + col][la_chan(C, j, half)]
@@ -374,7 +363,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
         for (int blk = 0; blk < NB; ++blk)
 #pragma unroll
           for (int r = s0; r < s0 + SEG; ++r) m = fmaxf(m, kT[blk][r]);
-        if (PARTNER) m = fmaxf(m, swap32(m));
+        if (PARTNER) m = fmaxf(m, swap_half(m));
 #pragma unroll
         for (int blk = 0; blk < NB; ++blk)
 #pragma unroll
@@ -384,7 +373,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
             ssum += e;
           }
       }
-      if (PARTNER) ssum += swap32(ssum);
+      if (PARTNER) ssum += swap_half(ssum);
       const float rs = fast_rcp(ssum);
       if (N >= 32) krs = rs;
       else if (SEGM) krs_seg[s0 / SEG] = rs;
@@ -417,15 +406,15 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
         float m = q[0];
 #pragma unroll
         for (int r = 1; r < 16; ++r) m = fmaxf(m, q[r]);
-        m = fmaxf(m, swap32(m));
+        m = fmaxf(m, swap_half(m));
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           q[r] = __builtin_amdgcn_exp2f(q[r] - m);
           ssum += q[r];
         }
       }
-      ssum += swap32(ssum);
-      qs = scale * fast_rcp(ssum);
+      ssum += swap_half(ssum);
+      qs = ATT_SCALE * fast_rcp(ssum);
       return q;
     };
 
@@ -439,7 +428,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
         for (int blk = 0; blk < NB; ++blk) mt += chain4(xs, NP, blk * 32, g, kT[blk]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float v = (mt[i] + swap32(mt[i])) * krs;
+          const float v = (mt[i] + swap_half(mt[i])) * krs;
           if (half == 0) ms[(g * 4 + i) * 32 + col] = v;
         }
       }
@@ -454,7 +443,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
         for (int g = 0; g < CG; ++g) {
           const f32x4 pp = chain4(ms, 32, 0, g, q);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) P[g * 4 + i] = pp[i] + swap32(pp[i]);
+          for (int i = 0; i < 4; ++i) P[g * 4 + i] = pp[i] + swap_half(pp[i]);
         }
         add_w2(hd, blk, P, qs);
       }
@@ -472,13 +461,13 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
 #pragma unroll
           for (int q4 = s * SEG / 4; q4 < (s + 1) * SEG / 4; ++q4) {
             const float4 a4 = *reinterpret_cast<const float4*>(ar + 8 * q4);
-            t0 = mfma4f(a4.x, kT[0][q4 * 4 + 0], t0); t1 = mfma4f(a4.y, kT[0][q4 * 4 + 1], t1);
-            t0 = mfma4f(a4.z, kT[0][q4 * 4 + 2], t0); t1 = mfma4f(a4.w, kT[0][q4 * 4 + 3], t1);
+            t0 = mfma4(a4.x, kT[0][q4 * 4 + 0], t0); t1 = mfma4(a4.y, kT[0][q4 * 4 + 1], t1);
+            t0 = mfma4(a4.z, kT[0][q4 * 4 + 2], t0); t1 = mfma4(a4.w, kT[0][q4 * 4 + 3], t1);
           }
           const f32x4 mt = t0 + t1;
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            const float v = (mt[i] + swap32(mt[i])) * krs_seg[s];
+            const float v = (mt[i] + swap_half(mt[i])) * krs_seg[s];
             if (half == 0) ms[s * MS_ROW + (g * 4 + i) * 32 + col] = v;
           }
         }
@@ -490,7 +479,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
       for (int g = 0; g < CG; ++g) {
         const f32x4 pp = chain4(ms + rl * MS_ROW, 32, 0, g, q);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) P[g * 4 + i] = pp[i] + swap32(pp[i]);
+        for (int i = 0; i < 4; ++i) P[g * 4 + i] = pp[i] + swap_half(pp[i]);
       }
       add_w2(hd, 0, P, qs);
     } else {
@@ -498,7 +487,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
       // pairs of the same m/z row, then R[c][n] = sum_n' xh[c][n'] S^T[n'][n]
       float qs;
       const f32x16 q = make_q(0, qs);
-      const f32x16 Kd = transpose_tile(kT[0], tile, col, half);  // rows d, col n'
+      const f32x16 Kd = transpose_tile33(kT[0], tile, col, half);  // rows d, col n'
       f32x16 st = {0};
       st = xty(Kd, q, st);
       st = mask_same_row<N>(st, col, half);
@@ -507,7 +496,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
       for (int g = 0; g < CG; ++g) {
         const f32x4 rr = chain4(xs, NP, 0, g, st);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) R[g * 4 + i] = rr[i] + swap32(rr[i]);
+        for (int i = 0; i < 4; ++i) R[g * 4 + i] = rr[i] + swap_half(rr[i]);
       }
       add_w2(hd, 0, R, qs);
     }
@@ -528,7 +517,7 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
       yv[j] = c < C ? yown[blk][j] + bout_r[j] : 0.f;
       ssq = fmaf(yv[j], yv[j], ssq);
     }
-    ssq += swap32(ssq);
+    ssq += swap_half(ssq);
     const float inv = rms_inv(ssq, sqC);  // (v_sqrt + v_rcp, 1 ulp each: the correctly rounded division / square root are ~20 instructions per use)
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -622,7 +611,7 @@ __global__ void __launch_bounds__(256) k_linattn_prepare(LaPrepMulti m) {
       const int i = u * 256 + (int)threadIdx.x;
       const int hh = (i >> 5) & 1, j = (i >> 6) % NJ;
       const int c = la_chan(C, j, hh);
-      if (i < WQ) it.prep[1024 + i] = c < C ? v[u] * 1.4426950408889634f : 0.f;
+      if (i < WQ) it.prep[1024 + i] = c < C ? v[u] * LOG2E : 0.f;
     }
   }
   if (C <= 8) {  // split-bf16 operand image of Wq | Wk (k_linattn_fwd<C, N, true>): 2048 la_nu(C) dwords, [q|k][head][u][lane][4]
@@ -639,7 +628,7 @@ __global__ void __launch_bounds__(256) k_linattn_prepare(LaPrepMulti m) {
       for (int mh = 0; mh < 8; ++mh) w[mh] = it.w_qkv[(mh * 32 + (ln & 31)) * C + c];
 #pragma unroll
       for (int mh = 0; mh < 8; ++mh) {
-        const float ws = w[mh] * 1.4426950408889634f;
+        const float ws = w[mh] * LOG2E;
         const unsigned hb = __float_as_uint(ws) & 0xffff0000u;
         const float r = ws - __uint_as_float(hb);
         const unsigned mb = __float_as_uint(r) & 0xffff0000u;
@@ -666,7 +655,7 @@ __global__ void __launch_bounds__(256) k_linattn_prepare(LaPrepMulti m) {
     if (threadIdx.x == 0) {
       float gm = 0.f;
       for (int c = 0; c < C; ++c) gm = fmaxf(gm, fabsf(it.g_pre[c]));
-      const float bound = 1.4426950408889634f * sqrtf(red[0]) * sqrtf((float)C) * gm;
+      const float bound = LOG2E * sqrtf(red[0]) * sqrtf((float)C) * gm;
       it.prep[LA_PREP_BOUNDED] = (bound <= 64.f) ? 1.f : 0.f;  // (a NaN anywhere compares false: the shifted form)
     }
   }
@@ -679,7 +668,7 @@ __global__ void __launch_bounds__(256) k_linattn_prepare(LaPrepMulti m) {
       const int l = i & 63, st = (i >> 6) % S, g = i / (64 * S);  // g: 0..3 q heads, 4..7 k heads, 8..11 W2 heads
       const int mrow = l & 31, c = sm_chan(C, st, l >> 5);
       float v = 0.f;
-      if (g < 8) v = c < C ? it.w_qkv[((g >> 2) * 128 + (g & 3) * 32 + mrow) * C + c] * 1.4426950408889634f : 0.f;
+      if (g < 8) v = c < C ? it.w_qkv[((g >> 2) * 128 + (g & 3) * 32 + mrow) * C + c] * LOG2E : 0.f;
       else v = (mrow < C && c < C) ? it.prep[((g - 8) * C + mrow) * C + c] : 0.f;
       it.prep[LA_PREP_SMALL + i] = v;
     }
@@ -705,7 +694,7 @@ __global__ void __launch_bounds__(256) k_linattn_prepare(LaPrepMulti m) {
         const int m = k >> 3, e = k & 7, t = e / CPL, s = e % CPL;
         ok = e < 2 * CPL;
         off = (m * 128 + hd * 32 + 16 * (ok ? t : 0) + ii) * C + CPL * g + s;
-        mul = 1.4426950408889634f;
+        mul = LOG2E;
       } else if (k < 20) {  // dZ = W2^T DY: M = channel c(ii) of Z, K-step s = channel c' = CPL g + s of DY
         const int s = k - 16;
         ok = s < CPL && ci >= 0;

@@ -8,6 +8,7 @@
 // res_fwd_form / res_bwd_form below choose between this kernel, the specialised ones of k_res_*.hip and k_level.hip, and the unfused
 // path of dq_ops.hip.
 #include "dq_common.h"
+#include "dq_wave.h"
 #include "dq_kernels.h"
 #include "k_res_common.h"
 #include <cstdlib>
@@ -21,8 +22,7 @@ __device__ __forceinline__ float ldg(const float* p) { return *p; }
 // wave-level fence is enough and the four waves of the block never wait for each other.
 __device__ __forceinline__ void exch_sync(bool wave_local) {
   if (wave_local) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_fence();
   } else {
     __syncthreads();
   }

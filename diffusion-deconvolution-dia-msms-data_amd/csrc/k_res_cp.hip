@@ -9,25 +9,13 @@
 // transposed, as [co/4][tap][ci][4 co] so a lane's 4 weights for 4 output channels are one ds_read_b128.  16x more waves, each
 // 16x shorter.  A block = 16 rows of ONE sample (the per-sample d(scale)/d(shift) sums need no search).
 #include "dq_common.h"
+#include "dq_wave.h"
 #include "dq_kernels.h"
 
 namespace dq {
 
 namespace {
 constexpr int GR = 16;   // rows (16-lane groups) per 256-thread block
-
-// sum over the 16 lanes of a group (all lanes receive it)
-__device__ __forceinline__ float gsum16(float v) {  // four DPP adds inside the 16-lane row, no LDS
-  int x = __float_as_int(v);
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-  x = __float_as_int(v);
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-  x = __float_as_int(v);
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, false));  // row_half_mirror
-  x = __float_as_int(v);
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, false));  // row_mirror
-  return v;
-}
 
 // stage W (cout x cin x K, row-major [co][ci][k]) with the roles of the backward data path: dst[((co4 * K + k) * 32 + ci) * 4 + (co & 3)] =
 // W[co][ci][k], zero padded to 16 x 32.  (256 threads.  Every element's load is requested before the first store, no load is predicated: as a
@@ -62,7 +50,7 @@ template <int C, bool SS>
 __device__ __forceinline__ float norm_act_bwd_cp(float u, float d, float g, float sc, float sh, bool act, float& dg, float& dsc,
                                                  float& dsh) {
   const float sqC = sqrtf((float)C);
-  const float ssq = gsum16(u * u);
+  const float ssq = row_sum16(u * u);
   const float nrm = fast_sqrt(ssq), inv = fast_rcp(fmaxf(nrm, RMS_EPS));
   const float uh = u * inv;
   const float z = uh * g * sqC;
@@ -72,7 +60,7 @@ __device__ __forceinline__ float norm_act_bwd_cp(float u, float d, float g, floa
   const float dz = SS ? dw * sc : dw;
   dg = fmaf(dz, uh * sqC, dg);
   const float gd = dz * g * sqC;
-  const float dot = gsum16(gd * uh);
+  const float dot = row_sum16(gd * uh);
   return nrm < RMS_EPS ? gd * inv : inv * (gd - uh * dot);
 }
 }  // namespace

@@ -14,6 +14,7 @@
 // Same contract as k_res_bwd / k_res_bwd_cp (ResBwd): dU1 / dU2 written for the weight-gradient kernels, d(input) stored or accumulated
 // into dA / dB, every workgroup's [d g2 | d g1 | d scale | d shift] sums in its own gpart slot (launch_part_reduce: ordered, repeatable).
 #include "dq_common.h"
+#include "dq_wave.h"
 #include "dq_kernels.h"
 #include "dq_options.h"
 #include <algorithm>
@@ -23,22 +24,6 @@
 namespace dq {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float gsum4(float t) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_int(t), __float_as_int(t), false, false);
-  t = __int_as_float(a[0]) + __int_as_float(a[1]);
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_int(t), __float_as_int(t), false, false);
-  return __int_as_float(b[0]) + __int_as_float(b[1]);
-}
-__device__ __forceinline__ float row_sum16(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));  // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));  // row_mirror
-  return v;
-}
 
 // N contiguous floats (N = 2 / 4 / 8; the launcher checks 16-byte alignment of the tensors)
 template <int N>

@@ -28,6 +28,7 @@
 // Any RT length (k_res.hip: <= 512; longer axes took the unfused five-launch path).  Weight gradients: unchanged (k_conv_wgrad_multi reads
 // the dU1 / dU2 / a1 tensors written here).
 #include "dq_common.h"
+#include "dq_wave.h"
 #include "dq_kernels.h"
 #include <algorithm>
 
@@ -35,26 +36,9 @@ namespace dq {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// sum over the four lane groups (lanes j, j + 16, j + 32, j + 48): every lane receives the total
-__device__ __forceinline__ float gsum4(float t) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_int(t), __float_as_int(t), false, false);
-  t = __int_as_float(a[0]) + __int_as_float(a[1]);
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_int(t), __float_as_int(t), false, false);
-  return __int_as_float(b[0]) + __int_as_float(b[1]);
-}
 // the value of lane - 1 / lane + 1 inside the 16-lane row (0 at the row's first / last lane); every lane takes part
 __device__ __forceinline__ float from_left(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, true)); }   // row_shr:1
 __device__ __forceinline__ float from_right(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x101, 0xF, 0xF, true)); }  // row_shl:1
-// sum over the 16 lanes of a row: every lane receives it
-__device__ __forceinline__ float row_sum16(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));  // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));  // row_mirror
-  return v;
-}
 
 constexpr int C = 16;
 constexpr int FWD_OWN = 14, BWD_OWN = 12;  // own positions of a 16-lane tile

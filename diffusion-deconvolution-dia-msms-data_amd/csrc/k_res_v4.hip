@@ -7,6 +7,7 @@
 // inputs come from the thread's own registers except at the two edges of its group (two scalar loads for x; the block-1
 // activation's edges go through LDS, ordered by a wave-level fence: a row's n/4 <= 64 threads always sit in one wave).
 #include "dq_common.h"
+#include "dq_wave.h"
 #include "dq_kernels.h"
 
 namespace dq {
@@ -138,8 +139,7 @@ __global__ void __launch_bounds__(256) k_res_fwd_v4(ResFwd a) {
   // ---- the two neighbours of this group's block-1 activation, through LDS (zero outside the row)
 #pragma unroll
   for (int co = 0; co < C; ++co) { eL[co][threadIdx.x] = acc[co][0]; eR[co][threadIdx.x] = acc[co][3]; }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
+  wave_fence();
   // ---- conv2 (k3) over the block-1 activation
   float o[C][4];
 #pragma unroll

@@ -23,6 +23,7 @@
 //     dshift] -- the order of the flat parameter buffer -- for k_res_wg_reduce to add up in block order: no atomics, bitwise
 //     repeatable.
 #include "dq_common.h"
+#include "dq_wave.h"
 #include "dq_kernels.h"
 #include "k_res_common.h"
 #include "dq_probe.h"
@@ -32,8 +33,6 @@ namespace dq {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
 
 // value of lane - 1 / lane + 1 (0 beyond the wave's ends); every lane takes part: never under control flow
 __device__ __forceinline__ float lane_m1(float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138, 0xF, 0xF, true)); }

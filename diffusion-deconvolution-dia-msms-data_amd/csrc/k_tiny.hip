@@ -90,14 +90,14 @@ __device__ __forceinline__ float tiny_img_value(const TinyLayer& L, int s, int l
       if (pm != k) return 0.f;
       float acc = 0.f;
       for (int j = 0; j < HID; ++j) acc = fmaf(P[L.w2 + s * HID + j], P[L.w + (2 * HID + j) * L.cin + co], acc);
-      return acc * 0.17677669529663687f;
+      return acc * ATT_SCALE;
     }
     default: {  // TL_LA1: scale * (Wo Wv)[co][ci]  (to_qkv (3 HID, C, 1): the v rows start at 2 HID; to_out.0 (C, HID, 1))
       if (pm != k) return 0.f;
       const int ci = s;
       float acc = 0.f;
       for (int j = 0; j < HID; ++j) acc = fmaf(P[L.w2 + co * HID + j], P[L.w + (2 * HID + j) * L.cin + ci], acc);
-      return acc * 0.17677669529663687f;  // 32^-0.5
+      return acc * ATT_SCALE;  // 32^-0.5
     }
   }
 }
@@ -208,7 +208,7 @@ __global__ void __launch_bounds__(256) k_tiny_fwd(TinyFwdK a, const float* __res
   auto dense = [&](int base, const float* breg, auto steps_c, f32x16 acc) __attribute__((always_inline)) -> f32x16 {
     constexpr int STEPS = decltype(steps_c)::value;
 #pragma unroll
-    for (int s = 0; s < STEPS; ++s) acc = mfma_f32(wlane[(base + s) * 64], breg[s], acc);
+    for (int s = 0; s < STEPS; ++s) acc = mfma32(wlane[(base + s) * 64], breg[s], acc);
     return acc;
   };
   const int rowl = N == 2 ? slot : lane, p = N == 2 ? half : 0;
@@ -221,7 +221,6 @@ __global__ void __launch_bounds__(256) k_tiny_fwd(TinyFwdK a, const float* __res
     const int64_t row = (int64_t)b * RT + rs_c;
     const int valid = RT - tile * RPT < RPT ? RT - tile * RPT : RPT;          // rows of this tile that exist
     const int64_t trow = (int64_t)b * RT + (int64_t)tile * RPT;                // the tile's first row
-    auto wsync = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
     // (rows, CH, N) tensors, E = CH * N floats per row.  lin_load: the tile's E * RPT floats as E * RPT / 64 contiguous 256-byte reads
     // (rows beyond the sample re-read its last element); to_lanes: through the staging tile into dst[c] = element (row, c, p) of the lane
     auto lin_load = [&](const float* base, auto e_c, float* raw) __attribute__((always_inline)) {
@@ -233,10 +232,10 @@ __global__ void __launch_bounds__(256) k_tiny_fwd(TinyFwdK a, const float* __res
     };
     auto lin_to_stg = [&](auto e_c, const float* raw) __attribute__((always_inline)) {
       constexpr int E = decltype(e_c)::value;
-      wsync();
+      wave_fence();
 #pragma unroll
       for (int k = 0; k < E * RPT / 64; ++k) { const int lin = k * 64 + lane; stg[lin + lin / E] = raw[k]; }
-      wsync();
+      wave_fence();
     };
     auto to_lanes = [&](auto ch_c, const float* raw, float* dst) __attribute__((always_inline)) {
       constexpr int CH = decltype(ch_c)::value, E = CH * N;
@@ -264,10 +263,10 @@ __global__ void __launch_bounds__(256) k_tiny_fwd(TinyFwdK a, const float* __res
         }
       } else if (base) {  // (wave-uniform)
         constexpr int E = C * N;
-        wsync();
+        wave_fence();
 #pragma unroll
         for (int c = 0; c < C; ++c) stg[rowl * (E + 1) + c * N + p] = v[c];
-        wsync();
+        wave_fence();
         float* g = base + trow * E;
         const int lim = valid * E;
 #pragma unroll
@@ -509,12 +508,11 @@ __global__ void __launch_bounds__(256) k_tiny_bwd(TinyBwdK a, const float* __res
   auto dense = [&](int base, const float* breg, f32x16 acc) __attribute__((always_inline)) -> f32x16 {
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int s = 0; s < C; ++s) acc = mfma_f32(wlane[(base + s) * 64], breg[s], acc);
+    for (int s = 0; s < C; ++s) acc = mfma32(wlane[(base + s) * 64], breg[s], acc);
     __builtin_amdgcn_sched_barrier(0);
     return acc;
   };
   auto zero16 = []() __attribute__((always_inline)) -> f32x16 { f32x16 z; for (int r = 0; r < 16; ++r) z[r] = 0.f; return z; };
-  auto wsync = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
   // Sums over the rows (norm gains, bias, per-sample d scale / d shift): 176 values per tile.  Kept per lane across the tiles they cost 176
   // registers (the kernel sat at 512 + 256 with ~100 spilled); added into an LDS table value by value they were 64 dependent LDS round trips
   // per block (21,700 clocks per block, probe).  Now: four DPP adds give every lane its 16-lane row's sum of value i, and lane (i mod 16) of
@@ -526,11 +524,7 @@ __global__ void __launch_bounds__(256) k_tiny_bwd(TinyBwdK a, const float* __res
     constexpr int NV = decltype(n_c)::value, OFF = decltype(off_c)::value;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      float t = v[i];
-      t += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(t), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-      t += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(t), 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-      t += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(t), 0x141, 0xF, 0xF, false));  // row_half_mirror
-      t += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(t), 0x140, 0xF, 0xF, false));  // row_mirror
+      const float t = row_sum16(v[i]);
       racc[(OFF + i) / 16] += (lane & 15) == ((OFF + i) & 15) ? t : 0.f;
       if ((i & 15) == 15) __builtin_amdgcn_sched_barrier(0);  // (keeps the scheduler from carrying dozens of row sums around)
     }
@@ -615,15 +609,15 @@ __global__ void __launch_bounds__(256) k_tiny_bwd(TinyBwdK a, const float* __res
         lacc[C + c] = DY[c];  // d b_out
       }
       // d W2[c'][c] += sum_rows dYpre[c'][row] xhat[c][row] (the 32^-0.5 is applied at the flush): K = rows = lanes, through the [c][row] tile
-      wsync();
+      wave_fence();
 #pragma unroll
       for (int c = 0; c < C; ++c) { tr[c * 65 + lane] = DY[c]; tr[(C + c) * 65 + lane] = live ? xh[c] : 0.f; }
-      wsync();
+      wave_fence();
 #pragma unroll
       for (int sgm = 0; sgm < 32; ++sgm) {
         const float av = tr[(lane & 15) * 65 + 2 * sgm + (lane >> 5)];
         const float bv = tr[(C + (lane & 15)) * 65 + 2 * sgm + (lane >> 5)];
-        w2acc = mfma_f32(av, bv, w2acc);
+        w2acc = mfma32(av, bv, w2acc);
       }
       const f32x16 dr = dense(B_LA, DY, zero16());  // 32^-0.5 (Wo Wv)^T dYpre
       const float pinv = fast_rcp(fmaxf(nrm, RMS_EPS));
@@ -757,7 +751,7 @@ __global__ void __launch_bounds__(256) k_tiny_bwd(TinyBwdK a, const float* __res
       // order per block: d g2 | d g1 | d scale | d shift  == ResBwd::gpart order
       a.blk[bi].gpart[(int64_t)wg * (4 * C) + what * C + c] = v;
     } else {
-      const float w = v * 0.17677669529663687f;
+      const float w = v * ATT_SCALE;
 #pragma unroll
       for (int hd = 0; hd < 4; ++hd) slot[256 * C + hd * C * C + (i - NACC)] = w;
     }

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Per-kernel register / LDS / spill table of a gfx950 code object (the shipped libdq_hip.so or a single build/*.o).
 
-    python tools/kernel_resources.py [path ...] [--spills] [--csv out.csv]
+    python tools/kernel_resources.py [path ...] [--spills] [--hash] [--csv out.csv]
 
 Unbundles the offload bundle (clang-offload-bundler), reads the AMDGPU metadata note (llvm-readelf --notes) and prints, per kernel:
 VGPRs (.vgpr_count), AGPRs, SGPRs, LDS bytes (.group_segment_fixed_size), scratch bytes (.private_segment_fixed_size) and
-.vgpr_spill_count / .sgpr_spill_count.  --spills lists only kernels with a spill or scratch."""
+.vgpr_spill_count / .sgpr_spill_count.  --spills lists only kernels with a spill or scratch.  --hash adds a column with a hash of each
+kernel's disassembly (llvm-objdump -d, no addresses, no raw bytes, comments dropped): equal hashes = the same machine code."""
+import hashlib
 import os
 import re
 import subprocess
@@ -56,11 +58,26 @@ def kernels_of(elf):
         blk = ".agpr_count:" + blk
         g = lambda key: (re.search(rf"\.{key}:\s*(\S+)", blk) or [None, "0"])[1]
         name = g("name")
+        sym = name
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-        rows.append({"kernel": dem, "vgpr": int(g("vgpr_count")), "agpr": int(g("agpr_count")), "sgpr": int(g("sgpr_count")),
+        rows.append({"kernel": dem, "symbol": sym, "vgpr": int(g("vgpr_count")), "agpr": int(g("agpr_count")), "sgpr": int(g("sgpr_count")),
                      "lds": int(g("group_segment_fixed_size")), "scratch": int(g("private_segment_fixed_size")),
                      "vgpr_spill": int(g("vgpr_spill_count")), "sgpr_spill": int(g("sgpr_spill_count"))})
     return rows
+
+
+def code_hashes(elf):
+    """{mangled kernel symbol: hash of its disassembled body}"""
+    txt = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", elf], capture_output=True, text=True).stdout
+    out, name = {}, None
+    for ln in txt.splitlines():
+        m = re.match(r"^(?:[0-9a-f]+ )?<(\S+)>:$", ln)
+        if m:
+            name = m[1]
+            out[name] = hashlib.sha256()
+        elif name and ln.strip() not in ("", "..."):  # ("...": zero padding behind a kernel, depends on what follows it)
+            out[name].update((ln.split("//")[0].strip() + "\n").encode())
+    return {k: h.hexdigest()[:16] for k, h in out.items()}
 
 
 def main():
@@ -75,11 +92,16 @@ def main():
     for p in args:
         elfs = so_code_objects(p) or code_objects(p)  # (.so and .o both keep their bundles in a .hip_fatbin section)
         for e in elfs:
-            rows += kernels_of(e)
+            ks = kernels_of(e)
+            if "--hash" in sys.argv:
+                hs = code_hashes(e)
+                for r in ks:
+                    r["hash"] = hs.get(r["symbol"], "?")
+            rows += ks
     rows.sort(key=lambda r: r["kernel"])
     if only_spills:
         rows = [r for r in rows if r["vgpr_spill"] or r["scratch"]]
-    hdr = ["kernel", "vgpr", "agpr", "sgpr", "lds", "scratch", "vgpr_spill", "sgpr_spill"]
+    hdr = ["kernel", "vgpr", "agpr", "sgpr", "lds", "scratch", "vgpr_spill", "sgpr_spill"] + (["hash"] if "--hash" in sys.argv else [])
     lines = [",".join(hdr)] + [",".join('"' + str(r[h]) + '"' if h == "kernel" else str(r[h]) for h in hdr) for r in rows]
     if csv:
         open(csv, "w").write("\n".join(lines) + "\n")

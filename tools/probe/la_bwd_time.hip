@@ -1,21 +1,12 @@
-// Where does the time of one LinearAttention-backward launch go?  Builds the product kernel source with -DDQ_LA_PROBE (per-wave
-// shader-clock stamps: 0 start, 1 after the weight staging, 2 after the unit loop, 10 / 11 inside the flush, 3 after it) and
-// launches single instantiations on random data.
+// Where does the time of one LinearAttention-backward launch go?  Builds the product's kernel templates (k_la_bwd.h, k_la_bwd1.h) with
+// -DDQ_LA_PROBE (per-wave shader-clock stamps: 0 start, 1 after the weight staging, 2 after the unit loop, 10 / 11 inside the flush, 3
+// after it) and launches single instantiations on random data.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form=1 -DDQ_LA_PROBE \
 //         -I include -I diffusion-deconvolution-dia-msms-data_amd/csrc tools/probe/la_bwd_time.hip -o gpurun_out/la_bwd_time
-#include "k_la_bwd.hip"
+#include "k_la_bwd.h"
+#include "k_la_bwd1.h"
 #include <algorithm>
 #include <vector>
-
-namespace dq {
-void set_error(const std::string& m) { fprintf(stderr, "error: %s\n", m.c_str()); }
-int launch_axpy(float*, const float*, int64_t, hipStream_t) { return 1; }
-int launch_block_bwd(const BlockBwd&, hipStream_t) { return 1; }
-int launch_zero(float*, int64_t, hipStream_t) { return 1; }
-int launch_linattn_bwd_long(const float*, const float*, float*, const float*, const float*, const float*, float*, int, int, int, int*,
-                            hipStream_t) { return 1; }
-void launch_linattn_bwd_big(const LinAttnBwdK&, int, int, hipStream_t) {}
-}  // namespace dq
 
 #define CK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { fprintf(stderr, "%s: %s\n", #e, hipGetErrorString(_e)); exit(1); } } while (0)
 
