@@ -227,7 +227,7 @@ struct ConvWgrad {
   float* scratch = nullptr; int64_t scratch_floats = 0;  // >= WGRAD_MAX_PARTS * (cout*cin*K + cout) floats
 };
 constexpr int WGRAD_MAX_PARTS = 512;
-// the ordered sum of nblk slots [dW (nelem_w) | dbias (cout)] into dw / dbias (+=): k_wgrad_reduce on its own
+// the ordered sum of nblk slots [dW (nelem_w) | dbias (cout)] into dw / dbias (+=): k_wgrad_reduce with one item
 int launch_wgrad_reduce(const float* part, int nblk, int nelem_w, int cout, float* dw, float* dbias, hipStream_t s);
 int launch_conv_wgrad(const ConvWgrad& a, hipStream_t s);
 bool conv_wgrad_vec4(const ConvWgrad& a);  // launch_conv_wgrad takes k_conv_wgrad_v4 (4 positions per thread and step), not k_conv_wgrad
@@ -515,7 +515,10 @@ int launch_wnorm_fwd(const float* u, const float* g, const float* ss, int ss_str
 int launch_wnorm_bwd(const float* u, const float* dy, const float* g, const float* ss, int ss_stride, int act, float* du, float* dg,
                      float* dss, float* dbias, float* scratch, int B, int C, int RT, int P, hipStream_t s);
 int launch_rowsum(const float* x, int64_t rows, int RT, int P, float* out, hipStream_t s);
-int launch_sum_b(const float* part, int B, int C, float* dst, hipStream_t s);
+int launch_sum_b(const float* part, int B, int C, float* dst, hipStream_t s);  // dst[c] += sum_b part[b][c]: launch_ordered_sum
+
+// ---- k_tfm.hip : the index-order sum  out[i] (+)= sum_b part[b * stride + i], b = 0, 1, ... from 0 (k_partial_reduce; one thread per i)
+int launch_ordered_sum(const float* part, int nb, int64_t stride, int n, float* out, int accumulate, hipStream_t s);
 
 // ---- k_time.hip (declared in dq_unet.h: needs the plan)
 

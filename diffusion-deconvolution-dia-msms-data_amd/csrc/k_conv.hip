@@ -11,6 +11,7 @@
 #include "dq_common.h"
 #include "dq_wave.h"
 #include "dq_kernels.h"
+#include "dq_slots.h"
 #include <cstdlib>
 
 namespace dq {
@@ -566,7 +567,7 @@ int launch_softplus_head_bwd(const float* fin, const float* w, const float* b, i
 // weight gradient, two deterministic stages (no atomics, fixed summation order => bitwise run-to-run repeatable):
 //  (1) block (x, y): y owns a (COB x CIB x K) sub-block of dW, x a strided share of the (row, p) items; the sub-block
 //      lives in registers, is reduced over the block (wave shuffles + LDS) and written to partials[x][element];
-//  (2) k_wgrad_reduce sums the <= 64 partials of every element in order and adds them to dW / dbias.
+//  (2) k_wgrad_reduce sums the <= WGRAD_MAX_PARTS partials of every element in order (dq_slots.h) and adds them to dW / dbias.
 // -------------------------------------------------------------------------------------------------
 // block-level reduction of the per-thread (COB x CIB x K) sub-block + bias sums -> this block's partial slot
 template <int COB, int CIB, int K>
@@ -735,61 +736,38 @@ __global__ void __launch_bounds__(256) k_conv_wgrad_multi(WgradMulti m) {
   }
 }
 
-// dW[e] += sum over the per-block partials in a fixed order (deterministic).  A block owns 16 consecutive elements x 16
-// partial groups: thread (e, g) sums partials g, g+16, ... (64-byte segments: every fetched sector is fully used), the 16
-// group sums meet in LDS.
-__global__ void __launch_bounds__(256) k_wgrad_reduce(const float* __restrict__ part, int nblk, int nelem_w, int cout,
-                                                      float* __restrict__ dw, float* __restrict__ dbias) {
-  __shared__ float red[16][17];
-  const int el = threadIdx.x & 15, g = threadIdx.x >> 4;
-  const int e = blockIdx.x * 16 + el;
-  const int nelem = nelem_w + cout;
-  float s0 = 0.f, s1 = 0.f;
-  if (e < nelem) {
-    int b = g;
-    for (; b + 16 < nblk; b += 32) {
-      s0 += part[(int64_t)b * nelem + e];
-      s1 += part[(int64_t)(b + 16) * nelem + e];
-    }
-    if (b < nblk) s0 += part[(int64_t)b * nelem + e];
-  }
-  red[g][el] = s0 + s1;
-  __syncthreads();
-  if (g == 0 && e < nelem) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s += red[k][el];
-    if (e < nelem_w) dw[e] += s;
-    else if (dbias) dbias[e - nelem_w] += s;
-  }
-}
-
-__global__ void __launch_bounds__(256) k_wgrad_reduce_multi(WgradMulti m) {
-  const int z = blockIdx.z;
-  const ConvWgrad& a = m.c[z];
-  const int nelem_w = m.nelem_w[z], nelem = nelem_w + a.cout, nblk = m.gx[z];
+// dW[e] += the ordered sum of the per-block partials (dq_slots.h), for up to three convs in one launch (blockIdx.z picks the conv).  A block
+// owns 16 consecutive elements x 16 partial groups: thread (e, g) takes partials g, g+16, ... (64-byte segments: every fetched sector is
+// fully used).
+struct WgradReduceItem { const float* part; int nblk, nelem_w, cout; float* dw; float* dbias; };
+struct WgradReduce { WgradReduceItem it[3]; };
+__global__ void __launch_bounds__(256) k_wgrad_reduce(WgradReduce m) {
+  const WgradReduceItem& a = m.it[blockIdx.z];
+  const int nelem = a.nelem_w + a.cout;
   if ((int)blockIdx.x * 16 >= nelem) return;  // uniform per block
   __shared__ float red[16][17];
   const int el = threadIdx.x & 15, g = threadIdx.x >> 4;
   const int e = blockIdx.x * 16 + el;
-  float s0 = 0.f, s1 = 0.f;
-  if (e < nelem) {
-    int b = g;
-    for (; b + 16 < nblk; b += 32) {
-      s0 += a.scratch[(int64_t)b * nelem + e];
-      s1 += a.scratch[(int64_t)(b + 16) * nelem + e];
-    }
-    if (b < nblk) s0 += a.scratch[(int64_t)b * nelem + e];
-  }
-  red[g][el] = s0 + s1;
-  __syncthreads();
+  const float s = slot_meet<16, 16>(red, e < nelem ? slot_sum<16, false>(a.part, e, nelem, a.nblk, g) : 0.f, g, el);
   if (g == 0 && e < nelem) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s += red[k][el];
-    if (e < nelem_w) a.dw[e] += s;
-    else if (a.dbias) a.dbias[e - nelem_w] += s;
+    if (e < a.nelem_w) a.dw[e] += s;
+    else if (a.dbias) a.dbias[e - a.nelem_w] += s;
   }
+}
+static int launch_wgrad_reduce(const WgradReduceItem* items, int count, hipStream_t s) {
+  WgradReduce m;
+  int nelem_max = 1;
+  for (int i = 0; i < 3; ++i) {
+    m.it[i] = items[i < count ? i : 0];
+    nelem_max = std::max(nelem_max, m.it[i].nelem_w + m.it[i].cout);
+  }
+  hipLaunchKernelGGL(k_wgrad_reduce, dim3(cdiv(nelem_max, 16), 1, count), dim3(256), 0, s, m);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
+int launch_wgrad_reduce(const float* part, int nblk, int nelem_w, int cout, float* dw, float* dbias, hipStream_t s) {
+  const WgradReduceItem it{part, nblk, nelem_w, cout, dw, dbias};
+  return launch_wgrad_reduce(&it, 1, s);
 }
 
 // ---- The same three weight gradients for the DEEP levels (m/z rows of 1 .. 8 positions, <= 16 output and <= 32 input channels) on the
@@ -798,7 +776,7 @@ __global__ void __launch_bounds__(256) k_wgrad_reduce_multi(WgradMulti m) {
 // loaded from memory ALREADY in operand order -- lane (g, i) reads dU[row 4 s + g][channel i][p] resp. x[row 4 s + g][channel i][q] for K-step
 // s: no staging, no transposes, every load of a 16-row tile in flight at once.  The four waves of a workgroup take the (conv, input-channel
 // tile) jobs of the block: conv2 | conv1, channels 0..15 | conv1, channels 16..31 | res_conv (both tiles); a workgroup walks its tiles and
-// leaves its sums in block `blockIdx.x` of each conv's scratch region, in the layout k_wgrad_reduce_multi sums.
+// leaves its sums in block `blockIdx.x` of each conv's scratch region, in the layout k_wgrad_reduce sums.
 // k_conv_wgrad_multi walks the same tensors once per (4 x 4) channel block -- 18 .. 32 passes, per-thread accumulators, a block reduction --
 // and its per-lane 4-byte accesses at a row pitch of C n floats touch 32 cache lines per instruction: 30 .. 70 us per launch next to the main
 // chain's kernels for 2.4 MB of operands.  With those launches SKIPPED the train step is 0.114 ms shorter (3.472 -> 3.358 ms,
@@ -901,18 +879,20 @@ static bool wgrad_rows_usable(const ConvWgrad* w, int count) {
 
 // blocks in flight per conv of a weight-gradient launch (2048: settled in round 2 over 512 .. 4096)
 static int wgrad_blocks() { return 2048; }
+// partial blocks of a conv of `tiles` (4 x 4) channel blocks over total = rows * n items: <= WGRAD_MAX_PARTS per element; ~4 items per
+// thread, ~2048 blocks in flight where the problem allows it
+static int wgrad_parts(int64_t total, bool vec4, int tiles) {
+  return std::max(1, std::min({cdiv(total, 256 * (vec4 ? 8 : 4)), WGRAD_MAX_PARTS, std::max(1, wgrad_blocks() / tiles)}));
+}
 
 // count <= 3 stride-1 convs with identical (rows, n_in == n_out); each descriptor carries its own scratch region
 int launch_conv_wgrad_multi(const ConvWgrad* w, int count, hipStream_t s) {
   DQ_REQUIRE(count >= 1 && count <= 3, "conv_wgrad_multi: 1..3 convs");
   WgradMulti m;
-  int gx_max = 1, tiles_max = 1, nelem_max = 1;
+  int gx_max = 1, tiles_max = 1;
   const int64_t total = (int64_t)w[0].rows * w[0].n_out;
   if (total == 0) return 0;
   DQ_REQUIRE(total < (1ll << 31), "conv_wgrad: rows*n must be below 2^31");
-  for (int i = 0; i < count; ++i)
-    DQ_REQUIRE(w[i].du && w[i].inA && w[i].dw && w[i].scratch && w[i].cout > 0 && w[i].cinA > 0 && w[i].rows == w[0].rows &&
-               w[i].n_in == w[i].n_out && w[i].n_out == w[0].n_out, "conv_wgrad_multi: missing operand / different rows");
   const bool vec4 = w[0].n_out % 4 == 0;
   for (int i = 0; i < count; ++i) {
     const ConvWgrad& a = w[i];
@@ -925,10 +905,9 @@ int launch_conv_wgrad_multi(const ConvWgrad* w, int count, hipStream_t s) {
     m.n_cib[i] = n_cib;
     m.nelem_w[i] = a.cout * cin * a.K;
     m.tiles[i] = n_cob * n_cib;
-    m.gx[i] = std::max(1, std::min({cdiv(total, 256 * (vec4 ? 8 : 4)), WGRAD_MAX_PARTS, std::max(1, wgrad_blocks() / m.tiles[i])}));
+    m.gx[i] = wgrad_parts(total, vec4, m.tiles[i]);
     DQ_REQUIRE((int64_t)m.gx[i] * (m.nelem_w[i] + a.cout) <= a.scratch_floats, "conv_wgrad_multi: scratch too small");
     gx_max = std::max(gx_max, m.gx[i]); tiles_max = std::max(tiles_max, m.tiles[i]);
-    nelem_max = std::max(nelem_max, m.nelem_w[i] + a.cout);
   }
   for (int i = count; i < 3; ++i) { m.c[i] = w[0]; m.n_cib[i] = 1; m.nelem_w[i] = 0; m.gx[i] = 0; m.tiles[i] = 0; }
   if (wgrad_rows_usable(w, count)) {  // the deep levels: 16 rows per K-step on the matrix pipe (k_wgrad_rows)
@@ -942,24 +921,15 @@ int launch_conv_wgrad_multi(const ConvWgrad* w, int count, hipStream_t s) {
     else if (n == 2) hipLaunchKernelGGL(k_wgrad_rows<2>, dim3(gx), dim3(256), 0, s, m, count, ntiles);
     else if (n == 4) hipLaunchKernelGGL(k_wgrad_rows<4>, dim3(gx), dim3(256), 0, s, m, count, ntiles);
     else hipLaunchKernelGGL(k_wgrad_rows<8>, dim3(gx), dim3(256), 0, s, m, count, ntiles);
-    DQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_wgrad_reduce_multi, dim3(cdiv(nelem_max, 16), 1, count), dim3(256), 0, s, m);
-    DQ_LAUNCH_CHECK();
-    return 0;
+  } else {
+    dim3 grid(gx_max, tiles_max, count), block(256);
+    if (vec4) hipLaunchKernelGGL(k_conv_wgrad_multi<true>, grid, block, 0, s, m);
+    else hipLaunchKernelGGL(k_conv_wgrad_multi<false>, grid, block, 0, s, m);
   }
-  dim3 grid(gx_max, tiles_max, count), block(256);
-  if (vec4) hipLaunchKernelGGL(k_conv_wgrad_multi<true>, grid, block, 0, s, m);
-  else hipLaunchKernelGGL(k_conv_wgrad_multi<false>, grid, block, 0, s, m);
   DQ_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_wgrad_reduce_multi, dim3(cdiv(nelem_max, 16), 1, count), dim3(256), 0, s, m);
-  DQ_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_wgrad_reduce(const float* part, int nblk, int nelem_w, int cout, float* dw, float* dbias, hipStream_t s) {
-  hipLaunchKernelGGL(k_wgrad_reduce, dim3(cdiv(nelem_w + cout, 16)), dim3(256), 0, s, part, nblk, nelem_w, cout, dw, dbias);
-  DQ_LAUNCH_CHECK();
-  return 0;
+  WgradReduceItem it[3];
+  for (int i = 0; i < count; ++i) it[i] = {w[i].scratch, m.gx[i], m.nelem_w[i], w[i].cout, w[i].dw, w[i].dbias};
+  return launch_wgrad_reduce(it, count, s);
 }
 
 // (K = 7 -- init_conv and the first MS1 conv -- joined in round 4: as one position per thread and step the init_conv launch was six dependent
@@ -977,37 +947,29 @@ int launch_conv_wgrad(const ConvWgrad& a, hipStream_t s) {
   constexpr int COB = 4, CIB = 4;
   const int n_cob = cdiv(a.cout, COB), n_cib = cdiv(cin, CIB);
   const int nelem_w = a.cout * cin * a.K;
-  // <= WGRAD_MAX_PARTS partial blocks per element; ~4 items per thread, ~2048 blocks in flight where the problem allows it
   const bool vec4 = conv_wgrad_vec4(a);
-  const int gx = std::max(1, std::min({cdiv(total, 256 * (vec4 ? 8 : 4)), WGRAD_MAX_PARTS, std::max(1, wgrad_blocks() / (n_cob * n_cib))}));
+  const int gx = wgrad_parts(total, vec4, n_cob * n_cib);
   DQ_REQUIRE((int64_t)gx * (nelem_w + a.cout) <= a.scratch_floats, "conv_wgrad: scratch too small");
   dim3 grid(gx, n_cob * n_cib), block(256);
   if (vec4) {
     if (a.K == 1) hipLaunchKernelGGL((k_conv_wgrad_v4<COB, CIB, 1>), grid, block, 0, s, a, n_cib, nelem_w);
     else if (a.K == 3) hipLaunchKernelGGL((k_conv_wgrad_v4<COB, CIB, 3>), grid, block, 0, s, a, n_cib, nelem_w);
     else hipLaunchKernelGGL((k_conv_wgrad_v4<COB, CIB, 7>), grid, block, 0, s, a, n_cib, nelem_w);
-    DQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3(cdiv(nelem_w + a.cout, 16)), dim3(256), 0, s, a.scratch, gx, nelem_w, a.cout, a.dw, a.dbias);
-    DQ_LAUNCH_CHECK();
-    return 0;
   }
-#define DQ_WG(KK, MM)                                                                                  \
-  if (a.K == KK && a.mode == MM) {                                                                      \
-    hipLaunchKernelGGL((k_conv_wgrad<COB, CIB, KK, MM>), grid, block, 0, s, a, n_cib, nelem_w);         \
-    DQ_LAUNCH_CHECK();                                                                                  \
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3(cdiv(nelem_w + a.cout, 16)), dim3(256), 0, s, a.scratch, gx, nelem_w, a.cout, a.dw, \
-                       a.dbias);                                                                        \
-    DQ_LAUNCH_CHECK();                                                                                  \
-    return 0;                                                                                           \
-  }
+#define DQ_WG(KK, MM) \
+  else if (a.K == KK && a.mode == MM) hipLaunchKernelGGL((k_conv_wgrad<COB, CIB, KK, MM>), grid, block, 0, s, a, n_cib, nelem_w);
   DQ_WG(1, CONV_S1)
   DQ_WG(3, CONV_S1)
   DQ_WG(7, CONV_S1)
   DQ_WG(4, CONV_DOWN)
   DQ_WG(3, CONV_UP)
 #undef DQ_WG
-  set_error("conv_wgrad: unsupported (K, mode)");
-  return 2;
+  else {
+    set_error("conv_wgrad: unsupported (K, mode)");
+    return 2;
+  }
+  DQ_LAUNCH_CHECK();
+  return launch_wgrad_reduce(a.scratch, gx, nelem_w, a.cout, a.dw, a.dbias, s);
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -6,52 +6,26 @@
 //   k_linattn_dwvo              dWv = Wo^T dW2, dWo = dW2 Wv^T from the summed dW2, once per layer
 #include "dq_common.h"
 #include "dq_kernels.h"
+#include "dq_slots.h"
 
 namespace dq {
 
-// grad[e] += sum over the wave slots in a fixed order (deterministic).  A block owns 16 consecutive elements x 16 slot
-// groups: thread (e, g) sums slots g, g+16, g+32, ... (64-byte segments per group: every fetched sector is fully used, unlike
-// a lane-per-slot gather), the 16 group sums meet in LDS.
-// Slot layout: dWqkv (384C) | dWo (128C) [| d g_out (C) | d b_out (C) | d g_pre (C) when nelem == 515C]
-__global__ void __launch_bounds__(256) k_linattn_dw_reduce(const float* __restrict__ part, int nslots, int C, int nelem,
-                                                           float* __restrict__ dw_qkv, float* __restrict__ dw_out,
-                                                           float* __restrict__ dg_out, float* __restrict__ db_out,
-                                                           float* __restrict__ dg_pre) {
+// grad[e] += the ordered sum of the wave slots (dq_slots.h).  A block owns 16 consecutive elements x 16 slot groups: thread (e, g) takes
+// slots g, g+16, g+32, ... (64-byte segments per group: every fetched sector is fully used, unlike a lane-per-slot gather).
+// Slot layout: dWqkv (384C) | dWo (128C)
+__global__ void __launch_bounds__(256) k_linattn_dw_reduce(const float* __restrict__ part, int nslots, int C, float* __restrict__ dw_qkv,
+                                                           float* __restrict__ dw_out) {
   __shared__ float red[16][17];
   const int el = threadIdx.x & 15, g = threadIdx.x >> 4;
-  const int e = blockIdx.x * 16 + el;
-  float s0 = 0.f, s1 = 0.f;
-  if (e < nelem) {
-    int b = g;
-    // (eight loads in flight, added in the order of the two-at-a-time loop: same sums bit for bit, a quarter of the memory round trips)
-    for (; b + 112 < nslots; b += 128) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = part[(int64_t)(b + 16 * u) * nelem + e];
-#pragma unroll
-      for (int u = 0; u < 8; u += 2) { s0 += v[u]; s1 += v[u + 1]; }
-    }
-    for (; b + 16 < nslots; b += 32) {
-      s0 += part[(int64_t)b * nelem + e];
-      s1 += part[(int64_t)(b + 16) * nelem + e];
-    }
-    if (b < nslots) s0 += part[(int64_t)b * nelem + e];
-  }
-  red[g][el] = s0 + s1;
-  __syncthreads();
+  const int e = blockIdx.x * 16 + el, nelem = 512 * C;
+  const float s = slot_meet<16, 16>(red, e < nelem ? slot_sum<16, true>(part, e, nelem, nslots, g) : 0.f, g, el);
   if (g == 0 && e < nelem) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s += red[k][el];
     if (e < 384 * C) dw_qkv[e] += s;
-    else if (e < 512 * C) dw_out[e - 384 * C] += s;
-    else if (e < 513 * C) dg_out[e - 512 * C] += s;
-    else if (e < 514 * C) db_out[e - 513 * C] += s;
-    else dg_pre[e - 514 * C] += s;
+    else dw_out[e - 384 * C] += s;
   }
 }
 // The slot reduction of the register-resident backward (slot layout la_slot(C)), for several LinearAttention layers at once: block ->
-// (item, 16-element group) through a prefix table.  dWq | dWk and the gains go to the gradient buffers (+=); the summed dW2 of the four
+// (item, 32-element group) through a prefix table.  dWq | dWk and the gains go to the gradient buffers (+=); the summed dW2 of the four
 // heads goes to the item's w2sum scratch, from which k_linattn_dwvo forms dWv and dWo.
 struct LaReduceMulti { LaReduceItem it[LA_REDUCE_MAX]; int first_block[LA_REDUCE_MAX + 1]; int count; };
 __global__ void __launch_bounds__(256) k_linattn_dw_reduce_multi(LaReduceMulti m) {
@@ -65,28 +39,8 @@ __global__ void __launch_bounds__(256) k_linattn_dw_reduce_multi(LaReduceMulti m
   __shared__ float red[8][33];
   const int el = threadIdx.x & 31, g = threadIdx.x >> 5;
   const int e = ((int)blockIdx.x - m.first_block[i]) * 32 + el;
-  float s0 = 0.f, s1 = 0.f;
-  if (e < nelem) {
-    int b = g;
-    for (; b + 56 < nslots; b += 64) {  // eight loads in flight, added in a fixed order
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = part[(int64_t)(b + 8 * u) * nelem + e];
-#pragma unroll
-      for (int u = 0; u < 8; u += 2) { s0 += v[u]; s1 += v[u + 1]; }
-    }
-    for (; b + 8 < nslots; b += 16) {
-      s0 += part[(int64_t)b * nelem + e];
-      s1 += part[(int64_t)(b + 8) * nelem + e];
-    }
-    if (b < nslots) s0 += part[(int64_t)b * nelem + e];
-  }
-  red[g][el] = s0 + s1;
-  __syncthreads();
+  const float s = slot_meet<32, 8>(red, e < nelem ? slot_sum<8, true>(part, e, nelem, nslots, g) : 0.f, g, el);
   if (g == 0 && e < nelem) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += red[k][el];
     const int w2b = 256 * C, gb = w2b + 4 * C * C;
     if (e < w2b) it.dw_qkv[e] += s;                 // rows 0..255 of to_qkv: q | k
     else if (e < gb) it.w2sum[e - w2b] = s;         // dW2[head][c'][c]
@@ -142,8 +96,7 @@ int launch_linattn_dw_reduce_multi(const LaReduceItem* items, int count, hipStre
 }
 // the slots of the sweep kernel (rows longer than 64 positions: 512 C floats per wave, dWqkv | dWo)
 int launch_linattn_dw_reduce(const float* part, int nslots, int C, float* dw_qkv, float* dw_out, hipStream_t s) {
-  hipLaunchKernelGGL(k_linattn_dw_reduce, dim3(cdiv(512 * C, 16)), dim3(256), 0, s, part, nslots, C, 512 * C, dw_qkv, dw_out,
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr);
+  hipLaunchKernelGGL(k_linattn_dw_reduce, dim3(cdiv(512 * C, 16)), dim3(256), 0, s, part, nslots, C, dw_qkv, dw_out);
   DQ_LAUNCH_CHECK();
   return 0;
 }

@@ -16,6 +16,7 @@
 #include "dq_common.h"
 #include "dq_wave.h"
 #include "dq_kernels.h"
+#include "dq_slots.h"
 #include "dq_options.h"
 #include <algorithm>
 #include <climits>
@@ -251,8 +252,7 @@ __global__ void __launch_bounds__(256) k_res_rows_bwd(ResBwd a) {
   if (threadIdx.x < 64) {
     const int c = threadIdx.x & 15, what = threadIdx.x >> 4;
     if (c < C)
-      a.gpart[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (4 * C) + what * C + c] =
-          (red[0][what * 16 + c] + red[1][what * 16 + c]) + (red[2][what * 16 + c] + red[3][what * 16 + c]);
+      a.gpart[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (4 * C) + what * C + c] = over_waves4(red, what * 16 + c);
   }
 }
 

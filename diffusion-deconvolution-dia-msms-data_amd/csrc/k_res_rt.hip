@@ -30,6 +30,7 @@
 #include "dq_common.h"
 #include "dq_wave.h"
 #include "dq_kernels.h"
+#include "dq_slots.h"
 #include <algorithm>
 
 namespace dq {
@@ -455,10 +456,10 @@ __global__ void __launch_bounds__(256) k_res_rt_bwd(ResBwd a, ResRtPre q, ResRtO
   __syncthreads();
   if (threadIdx.x < 4 * C) {
     const int i = threadIdx.x;
-    a.gpart[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (4 * C) + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    a.gpart[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (4 * C) + i] = over_waves4(red, i);
   } else if (PRE && threadIdx.x < 5 * C) {
     const int i = threadIdx.x;
-    q.gn_part[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * C + (i - 4 * C)] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    q.gn_part[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * C + (i - 4 * C)] = over_waves4(red, i);
   }
 }
 

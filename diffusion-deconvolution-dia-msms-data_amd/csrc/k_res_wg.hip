@@ -25,6 +25,7 @@
 #include "dq_common.h"
 #include "dq_wave.h"
 #include "dq_kernels.h"
+#include "dq_slots.h"
 #include "k_res_common.h"
 #include "dq_probe.h"
 #include <algorithm>
@@ -429,14 +430,9 @@ __global__ void __launch_bounds__(256, 2) k_res_bwd_wg(ResBwdWg a) {
     for (int k = 0; k < 3; ++k) put_w(aW1[1][k], oC1W, h11, 3, k, cin);
   }
   if (doB1) put_b(aB1, oC1B);
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const float s0 = wave_sum(dg2[c]), s1 = wave_sum(dg1[c]), s2 = wave_sum(dsc[c]), s3 = wave_sum(dsh[c]);
-    if (lane == 0) { red[wv][c] = s0; red[wv][C + c] = s1; red[wv][2 * C + c] = s2; red[wv][3 * C + c] = s3; }
-  }
-  __syncthreads();
+  slot_wave_sums<C>(red, dg2, dg1, dsc, dsh, lane, wv);
   for (int i = tid; i < 4 * C; i += 256) {
-    const float v = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    const float v = over_waves4(red, i);
     const int what = i / C, c = i % C;
     part[(what == 0 ? oG2 : what == 1 ? oG1 : what == 2 ? nglob : nglob + C) + c] = v;
   }
@@ -449,39 +445,22 @@ __global__ void __launch_bounds__(256, 2) k_res_bwd_wg(ResBwdWg a) {
 // -----------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_res_wg_reduce(ResWgReduceMulti m) {
   const ResWgReduce& r = m.it[blockIdx.y];
-  const int twoC = 2 * r.C;
+  const int twoC = 2 * r.C, nv = r.nv;  // (nv read ahead of the divergent branch: read inside it, the slot stride becomes a VGPR, 26 -> 32)
   const int nelem = r.nglob + r.B * twoC;
   if ((int)blockIdx.x * 16 >= nelem) return;  // uniform per block
   __shared__ float red[16][17];
   const int el = threadIdx.x & 15, gq = threadIdx.x >> 4;
   const int e = blockIdx.x * 16 + el;
-  float s0 = 0.f, s1 = 0.f;
+  float v = 0.f;
   if (e < nelem) {
     const bool glob = e < r.nglob;
     const int bs = glob ? 0 : (e - r.nglob) / twoC;
     const float* src = r.part + (glob ? e : (int64_t)bs * r.gx * r.nv + r.nglob + (e - r.nglob) % twoC);
     const int cnt = glob ? r.gx * r.B : r.gx;
-    int k = gq;
-    // (eight loads in flight, added in the order of the two-at-a-time loop: same sums bit for bit, a quarter of the memory round trips)
-    for (; k + 112 < cnt; k += 128) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = src[(int64_t)(k + 16 * u) * r.nv];
-#pragma unroll
-      for (int u = 0; u < 8; u += 2) { s0 += v[u]; s1 += v[u + 1]; }
-    }
-    for (; k + 16 < cnt; k += 32) {
-      s0 += src[(int64_t)k * r.nv];
-      s1 += src[(int64_t)(k + 16) * r.nv];
-    }
-    if (k < cnt) s0 += src[(int64_t)k * r.nv];
+    v = slot_sum<16, true>(src, 0, nv, cnt, gq);
   }
-  red[gq][el] = s0 + s1;
-  __syncthreads();
+  const float s = slot_meet<16, 16>(red, v, gq, el);
   if (gq == 0 && e < nelem) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s += red[k][el];
     if (e < r.nglob) r.dst[e] += s;
     else r.dss[(int64_t)((e - r.nglob) / twoC) * r.ss_stride + (e - r.nglob) % twoC] += s;
   }

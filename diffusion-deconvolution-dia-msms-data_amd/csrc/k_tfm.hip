@@ -4,6 +4,7 @@
 // bias / gain gradients.  All HBM-bound and small next to the GEMMs (k_gemm.hip); parameter-gradient sums go through per-block
 // partials and an ordered second pass (deterministic, no atomics).
 #include "dq_common.h"
+#include "dq_kernels.h"
 #include "dq_tfm.h"
 #include <algorithm>
 
@@ -408,6 +409,12 @@ __global__ void __launch_bounds__(256) k_tfm_kv_broadcast(float4* kv, int B, int
 inline unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>(cdiv(n, 256), 8192); }
 }  // namespace
 
+int launch_ordered_sum(const float* part, int nb, int64_t stride, int n, float* out, int accumulate, hipStream_t s) {
+  hipLaunchKernelGGL(k_partial_reduce, dim3(cdiv(n, 256)), dim3(256), 0, s, part, nb, stride, n, out, accumulate);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_rope_add(float* x, const float* sin_t, const float* cos_t, const float* temb, int B, int S, int H, int inverse, hipStream_t s) {
   DQ_REQUIRE(H % 2 == 0, "rope: hidden_dim must be even");
   const int64_t total = (int64_t)B * S * (H / 2);
@@ -447,8 +454,8 @@ int launch_cond_embed_bwd(const float* dc, const float* x_cond, const float* w, 
   if (rows == 0) return 0;
   const int nb = std::min(rows, 64);
   hipLaunchKernelGGL(k_cond_bwd_cols, dim3(cdiv(H / 2, 256), nb), dim3(256), 0, s, dc, x_cond, sin_t, cos_t, scratch, rows, S, H);
-  hipLaunchKernelGGL(k_partial_reduce, dim3(cdiv(H, 256)), dim3(256), 0, s, scratch, nb, (int64_t)2 * H, H, dw, accumulate);
-  hipLaunchKernelGGL(k_partial_reduce, dim3(cdiv(H, 256)), dim3(256), 0, s, scratch + H, nb, (int64_t)2 * H, H, db, accumulate);
+  if (launch_ordered_sum(scratch, nb, (int64_t)2 * H, H, dw, accumulate, s)) return 1;
+  if (launch_ordered_sum(scratch + H, nb, (int64_t)2 * H, H, db, accumulate, s)) return 1;
   if (dx_cond) hipLaunchKernelGGL(k_cond_bwd_rows, dim3(cdiv(rows, 4)), dim3(256), 0, s, dc, w, sin_t, cos_t, dx_cond, rows, S, H);
   DQ_LAUNCH_CHECK();
   return 0;
@@ -500,14 +507,10 @@ int launch_layernorm_bwd(const float* y, const float* stats, const float* g, con
   }
   const int nb = std::min(rows, LN_BWD_BLOCKS);
   hipLaunchKernelGGL(k_layernorm_bwd_cols, dim3(cdiv(H, 256), nb), dim3(256), 0, s, y, stats, dout, scratch, rows, H);
-  if (db == dg + H) {  // gain and bias adjacent (the flat parameter layout): the [dg | db] partial rows reduce in one launch
-    hipLaunchKernelGGL(k_partial_reduce, dim3(cdiv(2 * H, 256)), dim3(256), 0, s, scratch, nb, (int64_t)2 * H, 2 * H, dg, accumulate);
-  } else {
-    hipLaunchKernelGGL(k_partial_reduce, dim3(cdiv(H, 256)), dim3(256), 0, s, scratch, nb, (int64_t)2 * H, H, dg, accumulate);
-    hipLaunchKernelGGL(k_partial_reduce, dim3(cdiv(H, 256)), dim3(256), 0, s, scratch + H, nb, (int64_t)2 * H, H, db, accumulate);
-  }
-  DQ_LAUNCH_CHECK();
-  return 0;
+  // gain and bias adjacent (the flat parameter layout): the [dg | db] partial rows reduce in one launch
+  if (db == dg + H) return launch_ordered_sum(scratch, nb, (int64_t)2 * H, 2 * H, dg, accumulate, s);
+  if (launch_ordered_sum(scratch, nb, (int64_t)2 * H, H, dg, accumulate, s)) return 1;
+  return launch_ordered_sum(scratch + H, nb, (int64_t)2 * H, H, db, accumulate, s);
 }
 int launch_softmax_rows(float* p, int64_t rows, int n, int ld, float scale, hipStream_t s) {
   if (rows == 0) return 0;
@@ -523,16 +526,10 @@ int launch_softmax_rows_bwd(const float* p, float* dp, int64_t rows, int n, int 
 }
 int launch_colsum(const float* x, int M, int N, int64_t ld, float* out, float* scratch, hipStream_t s, int accumulate) {
   if (M == 0 || N == 0) return 0;
-  if (M <= COLSUM_BLOCKS) {  // a few dozen rows: they are the partial vectors already
-    hipLaunchKernelGGL(k_partial_reduce, dim3(cdiv(N, 256)), dim3(256), 0, s, x, M, ld, N, out, accumulate);
-    DQ_LAUNCH_CHECK();
-    return 0;
-  }
+  if (M <= COLSUM_BLOCKS) return launch_ordered_sum(x, M, ld, N, out, accumulate, s);  // a few dozen rows: they are the partial vectors already
   const int nb = COLSUM_BLOCKS;
   hipLaunchKernelGGL(k_colsum, dim3(cdiv(N, 256), nb), dim3(256), 0, s, x, M, N, ld, scratch);
-  hipLaunchKernelGGL(k_partial_reduce, dim3(cdiv(N, 256)), dim3(256), 0, s, scratch, nb, (int64_t)N, N, out, accumulate);
-  DQ_LAUNCH_CHECK();
-  return 0;
+  return launch_ordered_sum(scratch, nb, (int64_t)N, N, out, accumulate, s);
 }
 int launch_seqsum(const float* x, int B, int S, int N, float* out, hipStream_t s) {
   if (B * N == 0) return 0;

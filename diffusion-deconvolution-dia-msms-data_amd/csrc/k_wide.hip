@@ -12,7 +12,7 @@
 //   - du may alias dy in launch_wnorm_bwd (the PreNorm backward runs in place): k_wnorm_bwd_stats stores to the scratch alone, and in
 //     k_wnorm_bwd_apply the thread that stores du[t] is the only reader of dy[t] and has read it;
 //   - d g, d bias and the per-sample d(scale, shift) are += : dss straight from k_wnorm_bwd_apply (one wave owns a (b, c)), d g and d bias
-//     as ONE `dst += sum over b` of the per-sample partials (k_sum_b).
+//     as ONE `dst += sum over b` of the per-sample partials (launch_sum_b).
 #include "dq_common.h"
 #include "dq_kernels.h"
 
@@ -239,18 +239,9 @@ __global__ void __launch_bounds__(256) k_wnorm_bwd_apply(WideNormBwd a) {
   }
 }
 // dst[c] += sum_b part[b][c], b in order
-__global__ void __launch_bounds__(256) k_sum_b(const float* __restrict__ part, int B, int C, float* __restrict__ dst) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
-  float s = 0.f;
-  for (int b = 0; b < B; ++b) s += part[(int64_t)b * C + c];
-  dst[c] += s;
-}
 int launch_sum_b(const float* part, int B, int C, float* dst, hipStream_t s) {
   if (B == 0 || C == 0) return 0;
-  hipLaunchKernelGGL(k_sum_b, dim3(cdiv(C, 256)), dim3(256), 0, s, part, B, C, dst);
-  DQ_LAUNCH_CHECK();
-  return 0;
+  return launch_ordered_sum(part, B, C, C, dst, 1, s);
 }
 // du, d g (+=), per-sample d(scale, shift) (+=) and optionally a bias gradient (+= sum of du over (b, t)).
 // scratch: B * (2 P + 2 C) floats

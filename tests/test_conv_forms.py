@@ -346,6 +346,21 @@ WGRAD_MATRIX = [
 CAPPED = Case(4, 4, 0, 1, S1, 1, 524801, 4)         # 2 * 512 * 2048 + 2052 positions: gx capped at 512 (WGRAD_MAX_PARTS)
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# C2. the slot count of the weight-gradient reduce at every loop edge of the ordered slot sum (csrc/dq_slots.h; G = 16 groups, two slots
+# at a time: 1, G, G + 1, 2 G + 1, and the cap of 512).  K = 1, cout = cin = 4 is one channel tile, so the scalar form at n = 1 leaves
+# gx = ceil(rows / 1024) slots: rows = 1024 (slots - 1) + 1.  One v4 case (n = 4: gx = ceil(4 rows / 2048)) at 17 slots.
+# ---------------------------------------------------------------------------------------------------------------------------------
+SLOT_EDGES = [(Case(4, 4, 0, 1, S1, 1, 1024 * (k - 1) + 1, 1), "scalar", k) for k in (1, 16, 17, 33, 512)] + \
+             [(Case(4, 4, 0, 1, S1, 1, 8193, 4), "v4", 17)]
+
+
+def wgrad_slots(c, wform):
+    """gx of launch_conv_wgrad (k_conv.hip: wgrad_parts)"""
+    tiles = cdiv(c.cout, 4) * cdiv(c.cin, 4)
+    return max(1, min(cdiv(c.rows * c.n_out, 256 * (8 if wform == "v4" else 4)), 512, max(1, 2048 // tiles)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # D. the batched-GEMM data route of the bottleneck attention's projections (q | v, k, to_out -- whose bias does not enter the data gradient)
 # ---------------------------------------------------------------------------------------------------------------------------------
 GEMM_MATRIX = [Case(cout, cin, 0, 1, S1, 3, 1, n, bias=bias, acc=acc)
@@ -425,6 +440,14 @@ def test_conv_bwd_data_plain(N, c, wform, kind):
 @pytest.mark.parametrize("kind", ["exact", "normal"])
 @pytest.mark.parametrize("c,wform", WGRAD_MATRIX, ids=lambda v: repr(v) if isinstance(v, Case) else v)
 def test_conv_wgrad(N, c, wform, kind):
+    run_and_compare(N, c, kind, ("plain", wform))
+
+
+@pytest.mark.parametrize("kind", ["exact", "normal"])
+@pytest.mark.parametrize("c,wform,slots", SLOT_EDGES, ids=lambda v: repr(v) if isinstance(v, Case) else str(v))
+def test_conv_wgrad_slot_count_edges(N, c, wform, slots, kind):
+    """the ordered reduce with 1, 16, 17, 33 and 512 slots (v4: 17): no slot dropped, doubled or read past the last"""
+    assert wgrad_slots(c, wform) == slots
     run_and_compare(N, c, kind, ("plain", wform))
 
 

@@ -269,9 +269,22 @@ def _check_backward(la, ref, e, gen):
     return dx
 
 
+# Slot counts at the loop edges of the ordered slot sum (csrc/dq_slots.h; for G groups: 1, G, G + 1, 2 G + 1, 7 G, 7 G + 1, 8 G + 1,
+# 9 G + 1, 15 G + 1).
+#   k_linattn_dw_reduce_multi (G = 8): the register form at n = 32 takes one unit per row and leaves one slot per unit while the units fit
+#     one resident round (linattn_bwd_n in k_la_bwd.hip: at least 256 workgroups), so slots = rows.
+#   k_linattn_dw_reduce (G = 16): the long-row form.  launch_linattn_bwd_long (k_la_long.hip) gives a wave ceil(rows / 2048) rows and leaves
+#     a slot per wave: waves = ceil(rows / ceil(rows / 2048)) = rows up to 2,048 rows; the counts 1, 17, 113, 129 are the row counts.
+SLOT_EDGES = ([("register", 4, 32, r, 0.4) for r in (1, 8, 9, 17, 56, 57, 65, 73, 121)] + [("register", 16, 32, r, 0.4) for r in (57, 121)]
+              + [("long", 4, 128, r, 0.4) for r in (1, 17, 113, 129)])
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("form,C,n,rows,wscale", MATRIX)
+@pytest.mark.parametrize("form,C,n,rows,wscale", MATRIX + [m for m in SLOT_EDGES if m not in MATRIX])
 def test_form_vs_float64_oracle(N, force, form, C, n, rows, wscale):
+    """MATRIX, and SLOT_EDGES: the slot count of the reduce behind the backward at each loop edge of the ordered slot sum.  The long-row
+    form leaves one slot per wave, and launch_linattn_bwd_long's rule is waves = ceil(rows / ceil(rows / 2048)): up to 2,048 rows that is
+    the row count, so rows 1, 17, 113, 129 are 1, G + 1, 7 G + 1, 8 G + 1 slots at G = 16."""
     force(form)
     prepared = form != "long"
     fwd_form, bwd_form = N.linattn_forms(C, rows, n, prepared)

@@ -302,6 +302,40 @@ def test_default_rule_edges(N):
     assert blk.canaries_intact()
 
 
+# ---- the one-launch form (k_res_bwd_wg, k_res_wg.hip) at the loop edges of its slot reduce -------------------------------------------------
+# k_res_wg_reduce is the ordered slot sum of csrc/dq_slots.h with G = 16 groups, eight loads in flight: the edge counts are 1, G, G + 1,
+# 2 G + 1, 7 G, 7 G + 1, 8 G + 1, 9 G + 1, 15 G + 1.  A sample of rows_per_sample = 2 rows of 8 positions is one workgroup (res_wg_grid:
+# one 256-position tile per sample), so the weight gradients add up B slots and a sample's d(scale, shift) one; (4, 4, 0, 8, 544, 2) has 17
+# workgroups per sample (17 tiles of 256 positions), its d(scale, shift) sums then run over 17 slots and the weights' over 34.
+WG_SLOT_EDGES = [(4, 4, 0, 8, 2, B) for B in (1, 16, 17, 33, 112, 113, 129, 145, 241)] + [(4, 4, 0, 8, 544, 2), (8, 8, 4, 8, 2, 113)]
+
+
+def wg_slots(n, rps, B):
+    """(workgroups per sample, slots of a weight gradient): res_wg_grid of k_res_wg.hip"""
+    tiles_ps = -(-rps * n // 256)
+    tpb = max(1, (tiles_ps * B + 1023) // 1024)
+    gx = -(-tiles_ps // tpb)
+    return gx, gx * B
+
+
+@pytest.mark.parametrize("C,cinA,cinB,n,rps,B", WG_SLOT_EDGES)
+def test_wg_backward_slot_count_edges(N, C, cinA, cinB, n, rps, B):
+    """forward, d input, every weight gradient and each sample's d(scale, shift) of the one-launch form, under the bounds of the row form"""
+    assert wg_slots(n, rps, B) == ((17, 34) if rps == 544 else (1, B))
+    blk, wd, x, temb, gy = _case(N, C, cinA, cinB, n, rps, B=B)
+    assert blk.forms()[1] == "wg"
+    y, dx_ref, g_ref, dss_ref = reference(wd, x, temb, gy, rps)
+    out = blk.forward()
+    blk.fill("zero")
+    gd, dss = blk.backward(gy)
+    e = {"out": err(out, y), "dx": err(blk.dx(), dx_ref), "w": check_grads(gd, g_ref, "grads"), "dss": err(dss, dss_ref)}
+    print(f"wg<{C},{cinA + cinB != C}> cin {cinA}+{cinB} rps {rps} B {B}: " + " ".join(f"{k} {v:.2e}" for k, v in e.items()))
+    assert e["out"] < OUT_TOL, e
+    assert e["dx"] < DX_TOL, e
+    assert e["dss"] < DSS_TOL, e
+    assert blk.canaries_intact()
+
+
 # (C, cinA, cinB, n, rows per sample) outside res_rows_bwd_usable, and the form each takes instead
 FALL_THROUGH = [((16, 20, 0, 4, 34), "plain"),    # cinA over 16
                 ((16, 16, 6, 4, 34), "cp"),       # cinB not a multiple of 4

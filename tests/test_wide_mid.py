@@ -12,7 +12,7 @@ Kernel level (dq_wide_*: the launchers of k_wide.hip on tensors the test chooses
   C    4             four of the norm kernels' 8 channel slices stay empty
        8, 64, 80     every slice the same length (1, 8, 10 channels)
        12, 20        ragged slices (2 / 1 and 3 / 2 channels)
-  B    1, 3          k_sum_b over one sample / three; the per-sample scale / shift and its stride
+  B    1, 3          launch_sum_b over one sample / three; the per-sample scale / shift and its stride
 
   The product is thinned: every RT at C = 12 and 80 (B = 3), every C at RT = 34 and 65 (B = 3), and B = 1 at C in {4, 12, 80} x RT in
   {3, 34, 130}.  Tensors are views inside larger buffers with guard bands (checked bitwise), inputs are checked untouched, output
@@ -625,7 +625,7 @@ def test_moves(case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", KCASES, ids=_kid)
 def test_col2im_and_sums(case):
-    """k_col2im3 (store and accumulate), k_rowsum, k_sum_b (onto zero and onto non-zero contents) against float64, garbage in the input pads"""
+    """k_col2im3 (store and accumulate), k_rowsum, dq_wide_sum_b (onto zero and onto non-zero contents) against float64, garbage in the input pads"""
     from dquartic import _native as N
 
     C, B, RT = case
@@ -653,6 +653,31 @@ def test_col2im_and_sums(case):
     _kcompare(case, "rowsum", got["rows"])
     _kcompare(case, "sum_b", got["s0"])
     assert torch.equal(got["s1"], k["dst0"] + got["s0"])  # dst += ONE sum formed in registers
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [1, 7, 8, 9, 17])
+def test_sum_b_is_the_index_order_sum_bit_for_bit(B):
+    """dq_wide_sum_b (launch_ordered_sum: eight loads in flight from 8 partial rows on, a tail loop) against a float32 numpy loop in index
+    order from 0, then ONE dst + s: exact, at C around a 256-thread block"""
+    import numpy as np
+
+    from dquartic import _native as N
+
+    for C in (1, 255, 256, 257):
+        gen = torch.Generator().manual_seed(1000 * B + C)
+        part, dst0 = torch.randn(B, C, generator=gen), torch.randn(C, generator=gen)
+        s = np.zeros(C, dtype=np.float32)
+        for b in range(B):
+            s = s + part[b].numpy()
+        assert s.dtype == np.float32
+        want = dst0.numpy() + s
+        dv = _Dev()
+        pd, dst = dv.inp(part), dv.out((C,))
+        dst.copy_(dst0)
+        N.check(N.lib().dq_wide_sum_b(N.ptr(pd), B, C, N.ptr(dst), N.stream_ptr()), "dq_wide_sum_b")
+        dv.check()
+        assert np.array_equal(dst.cpu().numpy(), want), (B, C)
 
 
 def _ss_buffer(dv, k, C, B, fill=None):
@@ -696,7 +721,7 @@ def test_norm_forward(case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", KCASES, ids=_kid)
 def test_norm_backward(case):
-    """k_wnorm_bwd_stats / _apply / k_sum_b: ss and dbias null / present, act none / SiLU; du == dy against du != dy bitwise; d g, d scale /
+    """k_wnorm_bwd_stats / _apply / launch_sum_b: ss and dbias null / present, act none / SiLU; du == dy against du != dy bitwise; d g, d scale /
     shift and d bias as `+=` onto non-zero contents (bitwise fl(contents + the sum onto zero)); the special columns, the clamp among them"""
     from dquartic import _native as N
 
