@@ -1,7 +1,9 @@
 // The C ABI (include/dq_hip.h) but the samplers (dq_sampler.hip, dq_sampler_tables.cpp), the stand-alone op entry points (dq_ops_api.hip) and
-// the debug entry points that need the network file's private types (dq_unet.hip): errors and the occupancy cache, plan lifetime and queries,
+// the debug entry points that need the network file's private types (dq_unet.hip): errors, the device queries of dq_launch.h (CU count, occupancy
+// cache, one resident round, the dynamic-LDS limit), plan lifetime and queries,
 // options, the thin wrappers of the stream kernels, and the network passes -- forward, backward, the fused train step and the evaluation step.
 #include "dq_dev.h"
+#include "dq_launch.h"
 #include "dq_net.h"
 #include "dq_options.h"
 #include "../../include/dq_hip.h"
@@ -35,6 +37,34 @@ int occ_blocks_per_cu(const void* fn, int threads, size_t lds) {
   if (e != hipSuccess) { set_error(std::string("hipOccupancyMaxActiveBlocksPerMultiprocessor failed: ") + hipGetErrorString(e)); return -1; }
   cache.push_back({{fn, lds, threads, dev}, std::max(1, nb)});
   return std::max(1, nb);
+}
+
+int device_cus() {
+  static const int v = [] {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    return cus;
+  }();
+  return v;
+}
+
+int resident_blocks(const void* fn, int threads, size_t lds) {
+  const int nb = occ_blocks_per_cu(fn, threads, lds);
+  return nb < 0 ? -1 : nb * device_cus();
+}
+
+int ensure_dynamic_lds(const void* fn, size_t bytes) {
+  struct Ent { const void* fn; int dev; };
+  static std::mutex mu;
+  static std::vector<Ent> done;
+  int dev = 0;
+  DQ_HIP_OK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  for (const Ent& e : done)
+    if (e.fn == fn && e.dev == dev) return 0;
+  DQ_HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  done.push_back({fn, dev});
+  return 0;
 }
 }  // namespace dq
 

@@ -353,10 +353,15 @@ struct LevelFwd {
   // parameter values -- the kernel's workgroups then copy it to LDS instead of gathering it from the parameter tensors themselves
   const float* img = nullptr;
 };
-// the shapes launch_level_fwd takes: block b's input is cat(x of C channels, cinB[b] skip channels), has_wr[b]: it has a res_conv
+// the shapes launch_level_fwd takes (the (C, stage, stage input width) triples: k_level.hip's table of built instantiations): block b's
+// input is cat(x of C channels, cinB[b] skip channels), has_wr[b]: it has a res_conv
 bool level_fwd_usable(int C, int rows, int n, int rows_per_sample, int pre_mode, int cp, int nblocks, const int* cinB, const bool* has_wr);
 bool level_fwd_usable(const LevelFwd& a);
 int launch_level_fwd(const LevelFwd& a, hipStream_t s);
+// what launch_level_fwd and launch_tiny_fwd (`who`: the message prefix) ask of a block: operands present, its scale / shift vector in the buffer
+// at ssb with that stride, parameters inside the flat buffer.  poff: a parameter's offset in the flat buffer, -1 for null.  (k_level.hip)
+int check_level_block(const char* who, const ResFwd& r, const float* params, const float* ssb, int ss_stride);
+inline int poff(const float* params, const float* ptr) { return ptr ? (int)(ptr - params) : -1; }
 constexpr int LEVEL_LOSS_PARTS = 8192;     // floats behind LevelFwd::loss_part (one per wave of a resident round: 6 x 256 workgroups x 4)
 constexpr int LEVEL_IMG_MAX = 20;          // launches per launch_level_images call
 constexpr int LEVEL_IMG_FLOATS = 8192;     // upper bound of level_img_floats over the built instantiations (16 channels, 32-channel blocks)

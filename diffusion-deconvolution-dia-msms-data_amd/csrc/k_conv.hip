@@ -11,6 +11,7 @@
 #include "dq_common.h"
 #include "dq_wave.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 #include "dq_slots.h"
 #include <cstdlib>
 
@@ -150,26 +151,20 @@ __global__ void __launch_bounds__(256) k_conv_fwd(ConvFwd a) {
   for (int co = 0; co < COUT; ++co) a.y_out[((int64_t)row * cout_total + co_base + co) * a.n_out + p] = acc[co];
 }
 
-template <int COUT>
-static int conv_fwd_dispatch(const ConvFwd& a, int chunks, hipStream_t s) {
-  const int64_t total = (int64_t)a.rows * a.n_out;
-  if (total == 0) return 0;
-  dim3 grid(cdiv(total, 256), chunks), block(256);
-#define DQ_CF(KK, MM)                                                                   \
-  if (a.K == KK && a.mode == MM) {                                                       \
-    hipLaunchKernelGGL((k_conv_fwd<COUT, KK, MM>), grid, block, 0, s, a);                \
-    DQ_LAUNCH_CHECK();                                                                   \
-    return 0;                                                                            \
-  }
-  DQ_CF(1, CONV_S1)
-  DQ_CF(3, CONV_S1)
-  DQ_CF(7, CONV_S1)
-  DQ_CF(4, CONV_DOWN)
-  DQ_CF(3, CONV_UP)
-#undef DQ_CF
-  set_error("conv_fwd: unsupported (K, mode) = (" + std::to_string(a.K) + ", " + std::to_string(a.mode) + ")");
-  return 2;
-}
+using ConvFwdFn = decltype(&k_conv_fwd<1, 1, CONV_S1>);
+static const Inst<ConvFwdFn, 3> CONV_FWD_BUILT[] = {  // <COUT, K, MODE>
+    DQ_INST(k_conv_fwd, 1, 1, CONV_S1), DQ_INST(k_conv_fwd, 1, 3, CONV_S1), DQ_INST(k_conv_fwd, 1, 7, CONV_S1), DQ_INST(k_conv_fwd, 1, 4, CONV_DOWN),
+    DQ_INST(k_conv_fwd, 1, 3, CONV_UP),
+    DQ_INST(k_conv_fwd, 4, 1, CONV_S1), DQ_INST(k_conv_fwd, 4, 3, CONV_S1), DQ_INST(k_conv_fwd, 4, 7, CONV_S1), DQ_INST(k_conv_fwd, 4, 4, CONV_DOWN),
+    DQ_INST(k_conv_fwd, 4, 3, CONV_UP),
+    DQ_INST(k_conv_fwd, 8, 1, CONV_S1), DQ_INST(k_conv_fwd, 8, 3, CONV_S1), DQ_INST(k_conv_fwd, 8, 7, CONV_S1), DQ_INST(k_conv_fwd, 8, 4, CONV_DOWN),
+    DQ_INST(k_conv_fwd, 8, 3, CONV_UP),
+    DQ_INST(k_conv_fwd, 12, 1, CONV_S1), DQ_INST(k_conv_fwd, 12, 3, CONV_S1), DQ_INST(k_conv_fwd, 12, 7, CONV_S1), DQ_INST(k_conv_fwd, 12, 4, CONV_DOWN),
+    DQ_INST(k_conv_fwd, 12, 3, CONV_UP),
+    DQ_INST(k_conv_fwd, 16, 1, CONV_S1), DQ_INST(k_conv_fwd, 16, 3, CONV_S1), DQ_INST(k_conv_fwd, 16, 7, CONV_S1), DQ_INST(k_conv_fwd, 16, 4, CONV_DOWN),
+    DQ_INST(k_conv_fwd, 16, 3, CONV_UP),
+    DQ_INST(k_conv_fwd, 32, 1, CONV_S1), DQ_INST(k_conv_fwd, 32, 3, CONV_S1), DQ_INST(k_conv_fwd, 32, 7, CONV_S1), DQ_INST(k_conv_fwd, 32, 4, CONV_DOWN),
+    DQ_INST(k_conv_fwd, 32, 3, CONV_UP)};
 
 int launch_conv_fwd(const ConvFwd& a, hipStream_t s) {
   DQ_REQUIRE(a.inA && a.w && a.y_out && a.cout > 0 && a.cinA > 0, "conv_fwd: missing operand");
@@ -180,19 +175,19 @@ int launch_conv_fwd(const ConvFwd& a, hipStream_t s) {
   if (a.resA && !a.res_w) DQ_REQUIRE(a.rcinA == a.cout && a.rcinB == 0, "conv_fwd: identity residual needs cout channels");
   DQ_REQUIRE(a.act != ACT_SOFTPLUS || (a.cout == 1 && a.K == 1 && a.mode == CONV_S1), "conv_fwd: Softplus is built for the 1x1 conv to one channel");
   const bool chunkable = !a.g && !a.ss && !(a.resA && a.res_w);
-  switch (a.cout) {
-    case 1: return conv_fwd_dispatch<1>(a, 1, s);
-    case 4: return conv_fwd_dispatch<4>(a, 1, s);
-    case 8: return conv_fwd_dispatch<8>(a, 1, s);
-    case 12: return conv_fwd_dispatch<12>(a, 1, s);
-    case 16: return conv_fwd_dispatch<16>(a, 1, s);
-    case 32: return conv_fwd_dispatch<32>(a, 1, s);
-    // (64 output channels in one thread -- the 64-channel bottleneck of BASELINE configs[4] until round 4 -- went to the im2col + GEMM path: k_wide.hip)
-    default:
-      if (chunkable && a.cout % 32 == 0) return conv_fwd_dispatch<32>(a, a.cout / 32, s);
-      set_error("conv_fwd: unsupported cout " + std::to_string(a.cout));
-      return 2;
+  int cout = a.cout, chunks = 1;
+  // (64 output channels in one thread -- the 64-channel bottleneck of BASELINE configs[4] until round 4 -- went to the im2col + GEMM path: k_wide.hip)
+  if (!find_inst(CONV_FWD_BUILT, {cout, 1, CONV_S1})) {  // (every built width has the 1x1 row) wider: chunks of 32 output channels
+    if (!(chunkable && a.cout % 32 == 0)) { set_error("conv_fwd: unsupported cout " + std::to_string(a.cout)); return 2; }
+    cout = 32; chunks = a.cout / 32;
   }
+  const int64_t total = (int64_t)a.rows * a.n_out;
+  if (total == 0) return 0;
+  const auto* inst = find_inst(CONV_FWD_BUILT, {cout, a.K, a.mode});
+  if (!inst) { set_error("conv_fwd: unsupported (K, mode) = (" + std::to_string(a.K) + ", " + std::to_string(a.mode) + ")"); return 2; }
+  hipLaunchKernelGGL(inst->fn, dim3(cdiv(total, 256), chunks), dim3(256), 0, s, a);
+  DQ_LAUNCH_CHECK();
+  return 0;
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -353,6 +348,10 @@ int launch_part_reduce(const PartReduce& a, hipStream_t s) {
   return 0;
 }
 
+using BlockBwdFn = decltype(&k_block_bwd<1>);
+static const Inst<BlockBwdFn, 1> BLOCK_BWD_BUILT[] = {DQ_INST(k_block_bwd, 1), DQ_INST(k_block_bwd, 4), DQ_INST(k_block_bwd, 8), DQ_INST(k_block_bwd, 12),
+                                                      DQ_INST(k_block_bwd, 16), DQ_INST(k_block_bwd, 32)};  // <C>
+
 int launch_block_bwd(const BlockBwd& a, hipStream_t s) {
   DQ_REQUIRE(a.u && a.dy && a.du && a.rows > 0 && a.n > 0, "block_bwd: missing operand");
   DQ_REQUIRE(!a.ss || a.rows % a.rows_per_sample == 0, "block_bwd: rows must be a multiple of rows_per_sample");
@@ -372,17 +371,9 @@ int launch_block_bwd(const BlockBwd& a, hipStream_t s) {
   dim3 grid(bps, B), block(256);
   DQ_REQUIRE(!need_sums || (a.part && a.part_floats >= (int64_t)bps * B * 4 * a.C), "block_bwd: partial-sum slot missing or too small");
   if (!need_sums) a2.part = nullptr;
-#define DQ_BB(CC)                                                     \
-  case CC:                                                            \
-    hipLaunchKernelGGL((k_block_bwd<CC>), grid, block, 0, s, a_);     \
-    break;
-  switch (a.C) {
-    DQ_BB(1) DQ_BB(4) DQ_BB(8) DQ_BB(12) DQ_BB(16) DQ_BB(32)
-    default:
-      set_error("block_bwd: unsupported channel count " + std::to_string(a.C));
-      return 2;
-  }
-#undef DQ_BB
+  const auto* inst = find_inst(BLOCK_BWD_BUILT, {a.C});
+  if (!inst) { set_error("block_bwd: unsupported channel count " + std::to_string(a.C)); return 2; }
+  hipLaunchKernelGGL(inst->fn, grid, block, 0, s, a_);
   DQ_LAUNCH_CHECK();
   if (!need_sums) return 0;
   // the ordered sums of the per-block partials, right behind the kernel on the same stream (the slot is free again afterwards)
@@ -514,6 +505,11 @@ __global__ void __launch_bounds__(256) k_conv_bwd_data(ConvBwdData a) {
     if (dsts[i]) *dsts[i] = oldv[i] + acc[i];
 }
 
+using ConvBwdDataFn = decltype(&k_conv_bwd_data<4, 1, CONV_S1>);
+static const Inst<ConvBwdDataFn, 3> CONV_BWD_DATA_BUILT[] = {  // <NCI, K, MODE>
+    DQ_INST(k_conv_bwd_data, 4, 1, CONV_S1), DQ_INST(k_conv_bwd_data, 4, 3, CONV_S1), DQ_INST(k_conv_bwd_data, 4, 7, CONV_S1),
+    DQ_INST(k_conv_bwd_data, 4, 4, CONV_DOWN), DQ_INST(k_conv_bwd_data, 4, 3, CONV_UP)};
+
 int launch_conv_bwd_data(const ConvBwdData& a, hipStream_t s) {
   DQ_REQUIRE(a.du && a.w && a.cout > 0 && a.cinA > 0, "conv_bwd_data: missing operand");
   const int cin = a.cinA + a.cinB;
@@ -521,18 +517,11 @@ int launch_conv_bwd_data(const ConvBwdData& a, hipStream_t s) {
   if (total == 0) return 0;
   constexpr int NCI = 4;
   dim3 grid(cdiv(total, 256), cdiv(cin, NCI)), block(256);
-#define DQ_BD(KK, MM)                                                                     \
-  if (a.K == KK && a.mode == MM) {                                                         \
-    hipLaunchKernelGGL((k_conv_bwd_data<NCI, KK, MM>), grid, block, 0, s, a);              \
-    DQ_LAUNCH_CHECK();                                                                     \
-    return 0;                                                                              \
+  if (const auto* inst = find_inst(CONV_BWD_DATA_BUILT, {NCI, a.K, a.mode})) {
+    hipLaunchKernelGGL(inst->fn, grid, block, 0, s, a);
+    DQ_LAUNCH_CHECK();
+    return 0;
   }
-  DQ_BD(1, CONV_S1)
-  DQ_BD(3, CONV_S1)
-  DQ_BD(7, CONV_S1)
-  DQ_BD(4, CONV_DOWN)
-  DQ_BD(3, CONV_UP)
-#undef DQ_BD
   set_error("conv_bwd_data: unsupported (K, mode)");
   return 2;
 }
@@ -938,6 +927,11 @@ bool conv_wgrad_vec4(const ConvWgrad& a) {
   return a.mode == CONV_S1 && (a.K == 1 || a.K == 3 || a.K == 7) && a.n_out % 4 == 0 && a.n_in == a.n_out;
 }
 
+using ConvWgradFn = decltype(&k_conv_wgrad<4, 4, 1, CONV_S1>);
+static const Inst<ConvWgradFn, 4> CONV_WGRAD_BUILT[] = {  // <COB, CIB, K, MODE>
+    DQ_INST(k_conv_wgrad, 4, 4, 1, CONV_S1), DQ_INST(k_conv_wgrad, 4, 4, 3, CONV_S1), DQ_INST(k_conv_wgrad, 4, 4, 7, CONV_S1),
+    DQ_INST(k_conv_wgrad, 4, 4, 4, CONV_DOWN), DQ_INST(k_conv_wgrad, 4, 4, 3, CONV_UP)};
+
 int launch_conv_wgrad(const ConvWgrad& a, hipStream_t s) {
   DQ_REQUIRE(a.du && a.inA && a.dw && a.scratch && a.cout > 0 && a.cinA > 0, "conv_wgrad: missing operand");
   const int cin = a.cinA + a.cinB;
@@ -956,14 +950,7 @@ int launch_conv_wgrad(const ConvWgrad& a, hipStream_t s) {
     else if (a.K == 3) hipLaunchKernelGGL((k_conv_wgrad_v4<COB, CIB, 3>), grid, block, 0, s, a, n_cib, nelem_w);
     else hipLaunchKernelGGL((k_conv_wgrad_v4<COB, CIB, 7>), grid, block, 0, s, a, n_cib, nelem_w);
   }
-#define DQ_WG(KK, MM) \
-  else if (a.K == KK && a.mode == MM) hipLaunchKernelGGL((k_conv_wgrad<COB, CIB, KK, MM>), grid, block, 0, s, a, n_cib, nelem_w);
-  DQ_WG(1, CONV_S1)
-  DQ_WG(3, CONV_S1)
-  DQ_WG(7, CONV_S1)
-  DQ_WG(4, CONV_DOWN)
-  DQ_WG(3, CONV_UP)
-#undef DQ_WG
+  else if (const auto* inst = find_inst(CONV_WGRAD_BUILT, {COB, CIB, a.K, a.mode})) hipLaunchKernelGGL(inst->fn, grid, block, 0, s, a, n_cib, nelem_w);
   else {
     set_error("conv_wgrad: unsupported (K, mode)");
     return 2;

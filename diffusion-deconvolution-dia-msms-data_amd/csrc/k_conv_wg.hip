@@ -18,6 +18,7 @@
 #include "dq_common.h"
 #include "dq_wave.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 #include "k_res_common.h"
 #include "dq_probe.h"
 #include <algorithm>
@@ -298,14 +299,20 @@ __global__ void __launch_bounds__(256) k_conv_bwd_wg(ConvBwdWg a) {
   DQ_PSTAMP(200000 + C * 1000 + PRE * 100 + CP, 8);
 }
 
-static bool conv_wg_built(int C, int pre, int cp) {
-  if (pre == LEVEL_PRE_DOWN) return cp == C || (cp == C - 4 && cp >= 4);
-  if (pre == LEVEL_PRE_UP || pre == LEVEL_PRE_S1) return cp == C || (cp == C + 4 && cp <= 16);
-  return false;
-}
+// The built instantiations <C, PRE, CP>: a Downsample from C - 4 or C channels, an Upsample / k3 conv from C or C + 4 (k_level.hip's stages).
+using ConvWgFn = decltype(&k_conv_bwd_wg<4, LEVEL_PRE_DOWN, 4>);
+static const Inst<ConvWgFn, 3> CONV_WG_BUILT[] = {
+    DQ_INST(k_conv_bwd_wg, 4, LEVEL_PRE_DOWN, 4), DQ_INST(k_conv_bwd_wg, 8, LEVEL_PRE_DOWN, 4), DQ_INST(k_conv_bwd_wg, 8, LEVEL_PRE_DOWN, 8),
+    DQ_INST(k_conv_bwd_wg, 12, LEVEL_PRE_DOWN, 8), DQ_INST(k_conv_bwd_wg, 12, LEVEL_PRE_DOWN, 12), DQ_INST(k_conv_bwd_wg, 16, LEVEL_PRE_DOWN, 12),
+    DQ_INST(k_conv_bwd_wg, 16, LEVEL_PRE_DOWN, 16),
+    DQ_INST(k_conv_bwd_wg, 4, LEVEL_PRE_UP, 4), DQ_INST(k_conv_bwd_wg, 4, LEVEL_PRE_UP, 8), DQ_INST(k_conv_bwd_wg, 8, LEVEL_PRE_UP, 8),
+    DQ_INST(k_conv_bwd_wg, 8, LEVEL_PRE_UP, 12), DQ_INST(k_conv_bwd_wg, 12, LEVEL_PRE_UP, 12), DQ_INST(k_conv_bwd_wg, 12, LEVEL_PRE_UP, 16),
+    DQ_INST(k_conv_bwd_wg, 16, LEVEL_PRE_UP, 16),
+    DQ_INST(k_conv_bwd_wg, 4, LEVEL_PRE_S1, 4), DQ_INST(k_conv_bwd_wg, 4, LEVEL_PRE_S1, 8), DQ_INST(k_conv_bwd_wg, 8, LEVEL_PRE_S1, 8),
+    DQ_INST(k_conv_bwd_wg, 8, LEVEL_PRE_S1, 12), DQ_INST(k_conv_bwd_wg, 12, LEVEL_PRE_S1, 12), DQ_INST(k_conv_bwd_wg, 12, LEVEL_PRE_S1, 16),
+    DQ_INST(k_conv_bwd_wg, 16, LEVEL_PRE_S1, 16)};
 bool conv_wg_usable(int C, int pre, int cp, int n, int rows_per_sample) {
-  return (C == 4 || C == 8 || C == 12 || C == 16) && conv_wg_built(C, pre, cp) && n >= 1 && n <= 64 && (n & (n - 1)) == 0 && rows_per_sample > 1 &&
-         !(pre == LEVEL_PRE_UP && n < 2);
+  return find_inst(CONV_WG_BUILT, {C, pre, cp}) && n >= 1 && n <= 64 && (n & (n - 1)) == 0 && rows_per_sample > 1 && !(pre == LEVEL_PRE_UP && n < 2);
 }
 static void conv_wg_grid(int B, int rows_per_sample, int n, int* tiles_ps, int* tpb, int* gx) {
   *tiles_ps = cdiv((int64_t)rows_per_sample * n, TILE);
@@ -333,24 +340,11 @@ int launch_conv_bwd_wg(const ConvBwdWg& a_in, hipStream_t s, ResWgReduce* red_ou
   const size_t lds = sizeof(float) * ((size_t)pad4(a.C * (a.cp / 4) * K) * 4 + img_floats(a.C) + (size_t)K * img_floats(a.cp));
   DQ_REQUIRE(lds <= 160 * 1024, "conv_bwd_wg: LDS images too large");
   dim3 grid(gx, B), block(256);
-#define DQ_CW(CC, PP, PC)                                                                                              \
-  if (a.C == CC && a.pre == PP && a.cp == PC) {                                                                        \
-    static bool attr = false;                                                                                          \
-    if (!attr) {                                                                                                       \
-      DQ_HIP_OK(hipFuncSetAttribute((const void*)k_conv_bwd_wg<CC, PP, PC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-      attr = true;                                                                                                     \
-    }                                                                                                                  \
-    hipLaunchKernelGGL((k_conv_bwd_wg<CC, PP, PC>), grid, block, lds, s, a);                                           \
-    DQ_LAUNCH_CHECK();                                                                                                 \
-  } else
-  DQ_CW(4, LEVEL_PRE_DOWN, 4) DQ_CW(8, LEVEL_PRE_DOWN, 4) DQ_CW(8, LEVEL_PRE_DOWN, 8) DQ_CW(12, LEVEL_PRE_DOWN, 8) DQ_CW(12, LEVEL_PRE_DOWN, 12)
-  DQ_CW(16, LEVEL_PRE_DOWN, 12) DQ_CW(16, LEVEL_PRE_DOWN, 16)
-  DQ_CW(4, LEVEL_PRE_UP, 4) DQ_CW(4, LEVEL_PRE_UP, 8) DQ_CW(8, LEVEL_PRE_UP, 8) DQ_CW(8, LEVEL_PRE_UP, 12) DQ_CW(12, LEVEL_PRE_UP, 12) DQ_CW(12, LEVEL_PRE_UP, 16)
-  DQ_CW(16, LEVEL_PRE_UP, 16)
-  DQ_CW(4, LEVEL_PRE_S1, 4) DQ_CW(4, LEVEL_PRE_S1, 8) DQ_CW(8, LEVEL_PRE_S1, 8) DQ_CW(8, LEVEL_PRE_S1, 12) DQ_CW(12, LEVEL_PRE_S1, 12) DQ_CW(12, LEVEL_PRE_S1, 16)
-  DQ_CW(16, LEVEL_PRE_S1, 16)
-  { set_error("conv_bwd_wg: unsupported (C, stage, input width)"); return 2; }
-#undef DQ_CW
+  const auto* inst = find_inst(CONV_WG_BUILT, {a.C, a.pre, a.cp});
+  if (!inst) { set_error("conv_bwd_wg: unsupported (C, stage, input width)"); return 2; }
+  if (ensure_dynamic_lds((const void*)inst->fn, 160 * 1024)) return 1;
+  hipLaunchKernelGGL(inst->fn, grid, block, lds, s, a);
+  DQ_LAUNCH_CHECK();
   if (red_out) {
     ResWgReduce r;
     r.part = a.part; r.B = B; r.gx = gx; r.nv = a.nv; r.nglob = a.nv; r.C = 0;

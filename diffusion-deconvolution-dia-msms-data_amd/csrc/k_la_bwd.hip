@@ -1,67 +1,51 @@
 // Host dispatch of the LinearAttention backward: which kernel form takes a call (la_bwd_form: k_la_long.hip, k_la_rows_bwd.hip or the
 // register-resident kernels), the launch geometry of the register-resident kernels (k_la_bwd.h, k_la_bwd1.h: one resident round of
 // workgroups, a partial slot each) and the slot reduction behind them (k_la_reduce.hip).  This file instantiates k_linattn_bwd<C, N> for every
-// (C, N) but <12,64> and <16,64> (k_la_bwd_big.hip).
+// (C, N) but <12,64> and <16,64> (k_la_bwd_big.hip): LINATTN_BWD_BUILT is the list.
 #include "k_la_bwd.h"
 #include "k_la_bwd1.h"
+#include "dq_launch.h"
 #include <algorithm>
 #include <cstdlib>
 
 namespace dq {
 
-template <int C, int NN>
-static void launch_one(const LinAttnBwdK& kk, int waves, hipStream_t s) {
-  if constexpr (C >= 12 && NN == 64) launch_linattn_bwd_big(kk, C, waves, s);
-  else hipLaunchKernelGGL((k_linattn_bwd<C, NN>), dim3(cdiv(waves, 4)), dim3(256), 0, s, kk);
-}
+// The register-resident kernels built in this translation unit: k_linattn_bwd<C, N>, and k_linattn_bwd1<C> for rows of one position.
+using LinAttnBwdFn = decltype(&k_linattn_bwd<4, 2>);
+static const Inst<LinAttnBwdFn, 2> LINATTN_BWD_BUILT[] = {
+    DQ_INST(k_linattn_bwd, 4, 2), DQ_INST(k_linattn_bwd, 4, 4), DQ_INST(k_linattn_bwd, 4, 8), DQ_INST(k_linattn_bwd, 4, 16), DQ_INST(k_linattn_bwd, 4, 32),
+    DQ_INST(k_linattn_bwd, 4, 64),
+    DQ_INST(k_linattn_bwd, 8, 2), DQ_INST(k_linattn_bwd, 8, 4), DQ_INST(k_linattn_bwd, 8, 8), DQ_INST(k_linattn_bwd, 8, 16), DQ_INST(k_linattn_bwd, 8, 32),
+    DQ_INST(k_linattn_bwd, 8, 64),
+    DQ_INST(k_linattn_bwd, 12, 2), DQ_INST(k_linattn_bwd, 12, 4), DQ_INST(k_linattn_bwd, 12, 8), DQ_INST(k_linattn_bwd, 12, 16), DQ_INST(k_linattn_bwd, 12, 32),
+    DQ_INST(k_linattn_bwd, 16, 2), DQ_INST(k_linattn_bwd, 16, 4), DQ_INST(k_linattn_bwd, 16, 8), DQ_INST(k_linattn_bwd, 16, 16), DQ_INST(k_linattn_bwd, 16, 32)};
+static const Inst<LinAttnBwdFn, 1> LINATTN_BWD1_BUILT[] = {DQ_INST(k_linattn_bwd1, 4), DQ_INST(k_linattn_bwd1, 8), DQ_INST(k_linattn_bwd1, 12), DQ_INST(k_linattn_bwd1, 16)};
 
-// workgroups of k_linattn_bwd<C, NN> one resident round holds on this device
-template <int C, int NN>
-static int la_resident_blocks() {
-  if constexpr (C >= 12 && NN == 64) return 256;  // (the second translation unit's kernels: one wave per SIMD)
-  else {
-    static const int v = [] {
-      int occ = 1, dev = 0, cus = 256;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_linattn_bwd<C, NN>, 256, 0) != hipSuccess) occ = 1;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-      return std::max(1, occ) * std::max(1, cus);
-    }();
-    return v;
-  }
-}
-
-template <int C>
-static int linattn_bwd_n(const LinAttnBwdK& k, int n, const LinAttnBwd& g, hipStream_t s) {
+static int linattn_bwd_reg(const LinAttnBwdK& k, int C, int n, const LinAttnBwd& g, hipStream_t s) {
   // one resident round of blocks of four waves (= the four heads): 1-3 per CU, as the kernel's registers / LDS allow; a partial slot per
   // block.  Rows of one position: a wave per 32 rows, a slot per wave.
-  const int64_t k_part_floats = g.part_floats;
-  const int slots_max = (int)((k_part_floats - 4 * C * C) / la_slot(C));
+  const auto* inst1 = find_inst(LINATTN_BWD1_BUILT, {C});
+  if (!inst1) { set_error("linattn_bwd: unsupported channel count " + std::to_string(C)); return 2; }
+  const bool big = C >= 12 && n == 64;  // (k_la_bwd_big.hip's two kernels: one wave per SIMD, 256 resident blocks)
+  const auto* inst = find_inst(LINATTN_BWD_BUILT, {C, n});
+  if (n != 1 && !big && !inst) { set_error("linattn_bwd: m/z length " + std::to_string(n) + " is not built (powers of two up to 64)"); return 2; }
+  const int slots_max = (int)((g.part_floats - 4 * C * C) / la_slot(C));
   LinAttnBwdK kk = k;
   int slots = 0;
-#define DQ_LB(NN)                                                                                  \
-  case NN: {                                                                                       \
-    constexpr int RW = NN >= 32 ? 1 : 32 / NN;                                                     \
-    const int units = cdiv(k.rows, RW);                                                            \
-    const int max_blocks = std::min(la_resident_blocks<C, NN>(), slots_max);                       \
-    kk.units_per_wave = std::max(1, cdiv(units, max_blocks));                                      \
-    slots = cdiv(units, kk.units_per_wave);                                                        \
-    launch_one<C, NN>(kk, 4 * slots, s);                                                           \
-    break;                                                                                         \
+  if (n == 1) {
+    const int units = cdiv(k.rows, 32);
+    kk.units_per_wave = std::max(1, cdiv(units, std::min(1024, slots_max)));
+    slots = cdiv(units, kk.units_per_wave);
+    hipLaunchKernelGGL(inst1->fn, dim3(cdiv(slots, 4)), dim3(256), 0, s, kk);
+  } else {
+    const int units = cdiv(k.rows, n >= 32 ? 1 : 32 / n);
+    const int resident = big ? 256 : resident_blocks((const void*)inst->fn, 256, 0);
+    if (resident < 0) return 1;
+    kk.units_per_wave = std::max(1, cdiv(units, std::min(resident, slots_max)));
+    slots = cdiv(units, kk.units_per_wave);
+    if (big) launch_linattn_bwd_big(kk, C, 4 * slots, s);
+    else hipLaunchKernelGGL(inst->fn, dim3(slots), dim3(256), 0, s, kk);
   }
-  switch (n) {
-    case 1: {
-      const int units = cdiv(k.rows, 32);
-      kk.units_per_wave = std::max(1, cdiv(units, std::min(1024, slots_max)));
-      slots = cdiv(units, kk.units_per_wave);
-      hipLaunchKernelGGL((k_linattn_bwd1<C>), dim3(cdiv(slots, 4)), dim3(256), 0, s, kk);
-      break;
-    }
-    DQ_LB(2) DQ_LB(4) DQ_LB(8) DQ_LB(16) DQ_LB(32) DQ_LB(64)
-    default:
-      set_error("linattn_bwd: m/z length " + std::to_string(n) + " is not built (powers of two up to 64)");
-      return 2;
-  }
-#undef DQ_LB
   DQ_LAUNCH_CHECK();
   /* (4 C C floats behind the slots hold the summed dW2 between the reduce and k_linattn_dwvo) */
   if (g.defer_reduce) {
@@ -136,13 +120,7 @@ int launch_linattn_bwd(const LinAttnBwd& a, hipStream_t s) {
   k.x = a.f.x; k.ypre = a.ypre; k.dy = a.dy; k.dx = a.dx; k.w_qkv = a.f.w_qkv; k.w_out = a.f.w_out;
   k.g_pre = a.f.g_pre; k.g_out = a.f.g_out; k.part = a.part; k.rows = rows; k.units_per_wave = 1;
   k.prep = a.f.prep; k.dx_store = a.dx_store;
-  switch (C) {
-    case 4: return linattn_bwd_n<4>(k, n, a, s);
-    case 8: return linattn_bwd_n<8>(k, n, a, s);
-    case 12: return linattn_bwd_n<12>(k, n, a, s);
-    case 16: return linattn_bwd_n<16>(k, n, a, s);
-    default: set_error("linattn_bwd: unsupported channel count " + std::to_string(C)); return 2;
-  }
+  return linattn_bwd_reg(k, C, n, a, s);
 }
 
 }  // namespace dq

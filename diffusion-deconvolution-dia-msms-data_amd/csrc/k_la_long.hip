@@ -16,6 +16,7 @@
 // (so xh, dYpre and with them every gradient contribution vanish there), their k-softmax logits are -inf, and nothing is stored.
 #include "dq_common.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 #include "dq_mfma.h"
 
 namespace dq {
@@ -558,24 +559,26 @@ __global__ void __launch_bounds__(256, 2) k_linattn_bwd_long(LinAttnBwdLongK a) 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The built instantiations <C, N>.  N = LA_LONG_ANY_N: the same kernel with the row length read from the launch (ragged last block masked) --
+// those rows match any other length, and stand after the exact ones.
+constexpr int LA_LONG_ANY_N = 0;
+using LaLongFwdFn = decltype(&k_linattn_fwd_long<4, 128>);
+static const Inst<LaLongFwdFn, 2> LA_LONG_FWD_BUILT[] = {
+    DQ_INST(k_linattn_fwd_long, 4, 128), DQ_INST(k_linattn_fwd_long, 4, 256), DQ_INST(k_linattn_fwd_long, 8, 128), DQ_INST(k_linattn_fwd_long, 8, 256),
+    DQ_INST(k_linattn_fwd_long, 12, 128), DQ_INST(k_linattn_fwd_long, 16, 128),
+    DQ_INST(k_linattn_fwd_long, 4, LA_LONG_ANY_N), DQ_INST(k_linattn_fwd_long, 8, LA_LONG_ANY_N), DQ_INST(k_linattn_fwd_long, 12, LA_LONG_ANY_N),
+    DQ_INST(k_linattn_fwd_long, 16, LA_LONG_ANY_N)};
+using LaLongBwdFn = decltype(&k_linattn_bwd_long<4, 128>);
+static const Inst<LaLongBwdFn, 2> LA_LONG_BWD_BUILT[] = {
+    DQ_INST(k_linattn_bwd_long, 4, 128), DQ_INST(k_linattn_bwd_long, 4, 256), DQ_INST(k_linattn_bwd_long, 8, 128), DQ_INST(k_linattn_bwd_long, 8, 256),
+    DQ_INST(k_linattn_bwd_long, 12, 128), DQ_INST(k_linattn_bwd_long, 16, 128),
+    DQ_INST(k_linattn_bwd_long, 4, LA_LONG_ANY_N), DQ_INST(k_linattn_bwd_long, 8, LA_LONG_ANY_N), DQ_INST(k_linattn_bwd_long, 12, LA_LONG_ANY_N),
+    DQ_INST(k_linattn_bwd_long, 16, LA_LONG_ANY_N)};
+
 int launch_linattn_fwd_long(const LinAttn& a, hipStream_t s) {
-  dim3 grid(cdiv(a.rows, 4)), block(256);
-#define DQ_LF(CC, NN)                                                              \
-  if (a.C == CC && a.n == NN) {                                                    \
-    hipLaunchKernelGGL((k_linattn_fwd_long<CC, NN>), grid, block, 0, s, a);        \
-    DQ_LAUNCH_CHECK();                                                             \
-    return 0;                                                                      \
-  }
-  DQ_LF(4, 128) DQ_LF(4, 256) DQ_LF(8, 128) DQ_LF(8, 256) DQ_LF(12, 128) DQ_LF(16, 128)
-#undef DQ_LF
-  // any other row length: the same kernel with the length read from the launch (ragged last block masked)
-  switch (a.C) {
-    case 4: hipLaunchKernelGGL((k_linattn_fwd_long<4, 0>), grid, block, 0, s, a); break;
-    case 8: hipLaunchKernelGGL((k_linattn_fwd_long<8, 0>), grid, block, 0, s, a); break;
-    case 12: hipLaunchKernelGGL((k_linattn_fwd_long<12, 0>), grid, block, 0, s, a); break;
-    case 16: hipLaunchKernelGGL((k_linattn_fwd_long<16, 0>), grid, block, 0, s, a); break;
-    default: set_error("linattn_fwd: channel count " + std::to_string(a.C) + " is not built (4, 8, 12, 16)"); return 2;
-  }
+  const auto* inst = find_inst(LA_LONG_FWD_BUILT, {a.C, a.n}, LA_LONG_ANY_N);
+  if (!inst) { set_error("linattn_fwd: channel count " + std::to_string(a.C) + " is not built (4, 8, 12, 16)"); return 2; }
+  hipLaunchKernelGGL(inst->fn, dim3(cdiv(a.rows, 4)), dim3(256), 0, s, a);
   DQ_LAUNCH_CHECK();
   return 0;
 }
@@ -586,22 +589,9 @@ int launch_linattn_bwd_long(const float* x, const float* dyp, float* dxh, const 
   LinAttnBwdLongK k{x, dyp, dxh, w_qkv, w_out, g_pre, part, rows, std::max(1, cdiv(rows, 2048)), n};
   const int waves = cdiv(rows, k.units_per_wave);
   *waves_out = waves;
-  dim3 grid(cdiv(waves, 4)), block(256);
-#define DQ_LBL(CC, NN)                                                             \
-  if (C == CC && n == NN) {                                                        \
-    hipLaunchKernelGGL((k_linattn_bwd_long<CC, NN>), grid, block, 0, s, k);        \
-    DQ_LAUNCH_CHECK();                                                             \
-    return 0;                                                                      \
-  }
-  DQ_LBL(4, 128) DQ_LBL(4, 256) DQ_LBL(8, 128) DQ_LBL(8, 256) DQ_LBL(12, 128) DQ_LBL(16, 128)
-#undef DQ_LBL
-  switch (C) {  // any other row length (see launch_linattn_fwd_long)
-    case 4: hipLaunchKernelGGL((k_linattn_bwd_long<4, 0>), grid, block, 0, s, k); break;
-    case 8: hipLaunchKernelGGL((k_linattn_bwd_long<8, 0>), grid, block, 0, s, k); break;
-    case 12: hipLaunchKernelGGL((k_linattn_bwd_long<12, 0>), grid, block, 0, s, k); break;
-    case 16: hipLaunchKernelGGL((k_linattn_bwd_long<16, 0>), grid, block, 0, s, k); break;
-    default: set_error("linattn_bwd: channel count " + std::to_string(C) + " is not built (4, 8, 12, 16)"); return 2;
-  }
+  const auto* inst = find_inst(LA_LONG_BWD_BUILT, {C, n}, LA_LONG_ANY_N);
+  if (!inst) { set_error("linattn_bwd: channel count " + std::to_string(C) + " is not built (4, 8, 12, 16)"); return 2; }
+  hipLaunchKernelGGL(inst->fn, dim3(cdiv(waves, 4)), dim3(256), 0, s, k);
   DQ_LAUNCH_CHECK();
   return 0;
 }

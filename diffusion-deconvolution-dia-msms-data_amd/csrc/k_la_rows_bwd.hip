@@ -25,6 +25,7 @@
 #include "dq_common.h"
 #include "dq_wave.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 #include "dq_options.h"
 #include "dq_probe.h"
 #include <algorithm>
@@ -511,7 +512,11 @@ __global__ void __launch_bounds__(256, 2) k_la_rows_bwd(LaRowsBwdK a) {
 
 }  // namespace
 
-bool la_rows_bwd_usable(int C, int n) { return (n == 2 || n == 4) && (C == 8 || C == 12 || C == 16); }
+using LaRowsBwdFn = decltype(&k_la_rows_bwd<8, 2>);
+static const Inst<LaRowsBwdFn, 2> LA_ROWS_BWD_BUILT[] = {  // <C, N>
+    DQ_INST(k_la_rows_bwd, 8, 2), DQ_INST(k_la_rows_bwd, 8, 4), DQ_INST(k_la_rows_bwd, 12, 2), DQ_INST(k_la_rows_bwd, 12, 4), DQ_INST(k_la_rows_bwd, 16, 2),
+    DQ_INST(k_la_rows_bwd, 16, 4)};
+bool la_rows_bwd_usable(int C, int n) { return find_inst(LA_ROWS_BWD_BUILT, {C, n}) != nullptr; }
 int la_rows_bwd_min_rows() {
   const int64_t o = option(OPT_LA_ROWS_BWD_MIN_ROWS);
   return o < 0 ? 0 : (int)std::min<int64_t>(o, INT32_MAX);
@@ -525,20 +530,16 @@ int launch_la_rows_bwd(const LinAttnBwd& a, int max_slots, int* slots_out, hipSt
   DQ_REQUIRE(max_slots >= 1, "la_rows_bwd: slot scratch too small");
   DQ_REQUIRE((int64_t)rows * C * n * 4 < (1ll << 32), "la_rows_bwd: tensors of 4 GB or more are not built (32-bit byte offsets)");
   const int ntiles = cdiv(rows, 16);
-  static const int cus = [] { int d = 0; hipDeviceProp_t pr; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) ? pr.multiProcessorCount : 256; }();
   LaRowsBwdK k{a.f.x, a.ypre, a.dy, a.dx, a.f.prep, a.f.g_pre, a.f.g_out, a.part, rows, ntiles, a.dx_store};
-#define DQ_LRB(CC, NN)                                                                                   \
-  if (C == CC && n == NN) {                                                                              \
-    const int nb = occ_blocks_per_cu((const void*)k_la_rows_bwd<CC, NN>, 256, 0);                        \
-    if (nb < 0) return 1;                                                                                \
-    const int grid = std::max(1, std::min(ntiles, std::min(max_slots, nb * cus)));  /* one resident round, a slot per workgroup */ \
-    hipLaunchKernelGGL((k_la_rows_bwd<CC, NN>), dim3(grid), dim3(256), 0, s, k);                         \
-    DQ_LAUNCH_CHECK();                                                                                   \
-    *slots_out = grid;                                                                                   \
-    return 0;                                                                                            \
+  if (const auto* inst = find_inst(LA_ROWS_BWD_BUILT, {C, n})) {
+    const int resident = resident_blocks((const void*)inst->fn, 256, 0);
+    if (resident < 0) return 1;
+    const int grid = std::max(1, std::min(ntiles, std::min(max_slots, resident)));  // one resident round, a slot per workgroup
+    hipLaunchKernelGGL(inst->fn, dim3(grid), dim3(256), 0, s, k);
+    DQ_LAUNCH_CHECK();
+    *slots_out = grid;
+    return 0;
   }
-  DQ_LRB(8, 2) DQ_LRB(8, 4) DQ_LRB(12, 2) DQ_LRB(12, 4) DQ_LRB(16, 2) DQ_LRB(16, 4)
-#undef DQ_LRB
   set_error("la_rows_bwd: unsupported (C, n)");
   return 2;
 }

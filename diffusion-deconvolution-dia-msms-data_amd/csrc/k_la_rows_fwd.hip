@@ -15,6 +15,7 @@
 #include "dq_wave.h"
 #include "dq_dev.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 #include "dq_options.h"
 #include <algorithm>
 #include <cstdint>
@@ -179,22 +180,15 @@ __global__ void __launch_bounds__(256) k_la_rows_fwd(LaRowsFwdK a) {
   }
 }
 
-template <int C, int N>
-int la_rows_fwd_blocks() {
-  static const int v = [] {
-    int occ = 1, dev = 0, cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_la_rows_fwd<C, N>, 256, 0) != hipSuccess) occ = 1;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    return std::max(1, occ) * std::max(1, cus);
-  }();
-  return v;
-}
-
 }  // namespace
 
+using LaRowsFwdFn = decltype(&k_la_rows_fwd<8, 2>);
+static const Inst<LaRowsFwdFn, 2> LA_ROWS_FWD_BUILT[] = {  // <C, N>
+    DQ_INST(k_la_rows_fwd, 8, 2), DQ_INST(k_la_rows_fwd, 8, 4), DQ_INST(k_la_rows_fwd, 12, 2), DQ_INST(k_la_rows_fwd, 12, 4), DQ_INST(k_la_rows_fwd, 16, 2),
+    DQ_INST(k_la_rows_fwd, 16, 4)};
 bool la_rows_fwd_usable(int C, int n) {
   if (DQ_DEV_FLAG("DQ_NO_LA_ROWS_FWD", '1')) return false;  // (dev switch)
-  return (C == 8 || C == 12 || C == 16) && (n == 2 || n == 4);
+  return find_inst(LA_ROWS_FWD_BUILT, {C, n}) != nullptr;
 }
 
 int launch_la_rows_fwd(const LinAttn& a, hipStream_t s) {
@@ -202,15 +196,13 @@ int launch_la_rows_fwd(const LinAttn& a, hipStream_t s) {
   DQ_REQUIRE((((uintptr_t)a.x | (uintptr_t)a.prep) & 15) == 0, "la_rows_fwd: 16-byte aligned x and prepared weights");
   if (a.rows == 0) return 0;
   LaRowsFwdK k{a.x, a.y, a.ypre, a.prep, a.g_pre, a.g_out, a.b_out, a.rows, (int)cdiv(a.rows, 16)};
-#define DQ_LRF(CC, NN)                                                                              \
-  if (a.C == CC && a.n == NN) {                                                                     \
-    const int grid = std::min(k.ntiles, la_rows_fwd_blocks<CC, NN>());                              \
-    hipLaunchKernelGGL((k_la_rows_fwd<CC, NN>), dim3(grid), dim3(256), 0, s, k);                    \
-    DQ_LAUNCH_CHECK();                                                                              \
-    return 0;                                                                                       \
+  if (const auto* inst = find_inst(LA_ROWS_FWD_BUILT, {a.C, a.n})) {
+    const int resident = resident_blocks((const void*)inst->fn, 256, 0);
+    if (resident < 0) return 1;
+    hipLaunchKernelGGL(inst->fn, dim3(std::min(k.ntiles, resident)), dim3(256), 0, s, k);
+    DQ_LAUNCH_CHECK();
+    return 0;
   }
-  DQ_LRF(8, 2) DQ_LRF(8, 4) DQ_LRF(12, 2) DQ_LRF(12, 4) DQ_LRF(16, 2) DQ_LRF(16, 4)
-#undef DQ_LRF
   set_error("la_rows_fwd: unsupported (C, n)");
   return 2;
 }

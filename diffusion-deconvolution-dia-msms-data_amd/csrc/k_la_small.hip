@@ -15,6 +15,7 @@
 // (LA_PREP_BOUNDED), as in k_linattn.hip.
 #include "dq_common.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 #include "dq_mfma.h"
 #include "dq_options.h"
 #include <climits>
@@ -239,9 +240,10 @@ __global__ void __launch_bounds__(256, N <= 4 ? 2 : 1) k_la_small(LaSmallK a) { 
 
 }  // namespace
 
-bool la_small_usable(int C, int n) {
-  return ((n == 2 || n == 4) && (C == 12 || C == 16)) || (n == 8 && C == 12);  // (8 channels at 8 positions measured slower than the register-resident kernel: 297 vs 276 us at batch 512; 12 channels: 371 vs 429)
-}
+using LaSmallFn = decltype(&k_la_small<12, 2>);
+static const Inst<LaSmallFn, 2> LA_SMALL_BUILT[] = {  // <C, N>  (8 channels at 8 positions measured slower than the register-resident kernel: 297 vs 276 us at batch 512; 12 channels: 371 vs 429)
+    DQ_INST(k_la_small, 12, 2), DQ_INST(k_la_small, 16, 2), DQ_INST(k_la_small, 12, 4), DQ_INST(k_la_small, 16, 4), DQ_INST(k_la_small, 12, 8)};
+bool la_small_usable(int C, int n) { return find_inst(LA_SMALL_BUILT, {C, n}) != nullptr; }
 // Below one 32-row tile per SIMD the launch is a latency chain (a training batch of 32 windows: 400 tiles for 1,024 SIMDs) and the
 // register-resident kernel's shorter prologue wins (measured at 12,800 rows: 4 launches +35 us per step); above it the matrix pipe is the limit
 // and this form's ~3x fewer MFMA cycles per position pay.  The rule comes from the device (4 SIMDs per compute unit x 32 rows);
@@ -249,8 +251,7 @@ bool la_small_usable(int C, int n) {
 int la_small_min_rows() {
   const int64_t o = option(OPT_LA_SMALL_MIN_ROWS);
   if (o >= 0) return (int)std::min<int64_t>(o, INT32_MAX);
-  static const int rule = [] { int d = 0; hipDeviceProp_t pr; return 32 * 4 * ((hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) ? pr.multiProcessorCount : 256); }();
-  return rule;
+  return 32 * 4 * device_cus();
 }
 
 int launch_la_small_fwd(const LinAttn& a, hipStream_t s) {
@@ -258,19 +259,15 @@ int launch_la_small_fwd(const LinAttn& a, hipStream_t s) {
   DQ_REQUIRE((((uintptr_t)a.prep | (uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)a.ypre) & 15) == 0, "la_small: misaligned tensor / prepared-weights buffer");
   if (a.rows == 0) return 0;
   LaSmallK k{a.x, a.y, a.ypre, a.prep, a.b_out, a.g_pre, a.g_out, a.rows, cdiv(a.rows, 32)};
-  static const int cus = [] { int d = 0; hipDeviceProp_t pr; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) ? pr.multiProcessorCount : 256; }();
-#define DQ_LAS(CC, NN)                                                                                        \
-  if (a.C == CC && a.n == NN) {                                                                               \
-    const size_t lds = (size_t)4 * 32 * (CC * NN + 1) * 4;                                                   \
-    const int nb = occ_blocks_per_cu((const void*)k_la_small<CC, NN>, 256, lds);                              \
-    if (nb < 0) return 1;                                                                                     \
-    const int grid = std::max(1, std::min(nb * cus, (k.ntiles + 3) / 4));                                     \
-    hipLaunchKernelGGL((k_la_small<CC, NN>), dim3(grid), dim3(256), lds, s, k);                               \
-    DQ_LAUNCH_CHECK();                                                                                        \
-    return 0;                                                                                                 \
+  if (const auto* inst = find_inst(LA_SMALL_BUILT, {a.C, a.n})) {
+    const size_t lds = (size_t)4 * 32 * (a.C * a.n + 1) * 4;
+    const int resident = resident_blocks((const void*)inst->fn, 256, lds);
+    if (resident < 0) return 1;
+    const int grid = std::max(1, std::min(resident, (k.ntiles + 3) / 4));
+    hipLaunchKernelGGL(inst->fn, dim3(grid), dim3(256), lds, s, k);
+    DQ_LAUNCH_CHECK();
+    return 0;
   }
-  DQ_LAS(12, 2) DQ_LAS(16, 2) DQ_LAS(12, 4) DQ_LAS(16, 4) DQ_LAS(12, 8)
-#undef DQ_LAS
   set_error("la_small: unsupported (C, n)");
   return 2;
 }

@@ -33,6 +33,7 @@
 #include "dq_common.h"
 #include "dq_wave.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 #include "dq_probe.h"
 #include "../../include/dq_hip.h"  // DQ_PRED_*
 #include <algorithm>
@@ -688,24 +689,42 @@ __global__ void __launch_bounds__(256) k_level_fwd(LevelFwdK a, const float* __r
   DQ_PSTAMP(C * 1000 + PRE * 100 + CP, 6);
 }
 
-// stage input widths that are instantiated: a Downsample from C - 4 or C channels, an Upsample / k3 conv from C or C + 4 (channel
-// widths that move by at most one step of 4 per level, as in the reference's configurations; anything else keeps the per-op path)
-static bool level_cp_built(int C, int pre, int cp) {
-  if (pre == LEVEL_PRE_NONE) return true;
-  if (pre == LEVEL_PRE_INIT) return C == 4 && cp == 2;
-  if (pre == LEVEL_PRE_DOWN) return cp == C || (cp == C - 4 && cp >= 4);
-  return cp == C || (cp == C + 4 && cp <= 16);
-}
-
-static int num_cus() {
-  static const int v = [] { int d = 0; hipDeviceProp_t pr; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) ? pr.multiProcessorCount : 256; }();
-  return v;
-}
+// Every built instantiation, keyed by the seven template arguments <C, PRE, CP, N64, TH, FA, VT>: level_fwd_usable and launch_level_fwd both
+// read this table.  Stage input widths: a Downsample from C - 4 or C channels, an Upsample / k3 conv from C or C + 4
+// (channel widths that move by at most one step of 4 per level, as in the reference's configurations; anything else keeps the per-op path);
+// a launch without a stage (NONE) is built at CP = 4.  N64 (rows of 64 positions) exists at C = 4 only.
+using LevelFwdFn = decltype(&k_level_fwd<4, LEVEL_PRE_NONE, 4, false, false, FINAL_IDENTITY, false>);
+enum : int { NONE = LEVEL_PRE_NONE, DOWN = LEVEL_PRE_DOWN, UP = LEVEL_PRE_UP, S1 = LEVEL_PRE_S1, INIT = LEVEL_PRE_INIT, ID = FINAL_IDENTITY, SP = FINAL_SOFTPLUS };
+static const Inst<LevelFwdFn, 7> LEVEL_FWD_BUILT[] = {
+    // plain levels: no head, no first-layer store
+    DQ_INST(k_level_fwd, 4, NONE, 4, false, false, ID, false), DQ_INST(k_level_fwd, 4, NONE, 4, true, false, ID, false), DQ_INST(k_level_fwd, 8, NONE, 4, false, false, ID, false),
+    DQ_INST(k_level_fwd, 12, NONE, 4, false, false, ID, false), DQ_INST(k_level_fwd, 16, NONE, 4, false, false, ID, false), DQ_INST(k_level_fwd, 4, DOWN, 4, false, false, ID, false),
+    DQ_INST(k_level_fwd, 4, DOWN, 4, true, false, ID, false), DQ_INST(k_level_fwd, 8, DOWN, 4, false, false, ID, false), DQ_INST(k_level_fwd, 8, DOWN, 8, false, false, ID, false),
+    DQ_INST(k_level_fwd, 12, DOWN, 8, false, false, ID, false), DQ_INST(k_level_fwd, 12, DOWN, 12, false, false, ID, false), DQ_INST(k_level_fwd, 16, DOWN, 12, false, false, ID, false),
+    DQ_INST(k_level_fwd, 16, DOWN, 16, false, false, ID, false), DQ_INST(k_level_fwd, 4, UP, 4, false, false, ID, false), DQ_INST(k_level_fwd, 4, UP, 4, true, false, ID, false),
+    DQ_INST(k_level_fwd, 4, UP, 8, false, false, ID, false), DQ_INST(k_level_fwd, 4, UP, 8, true, false, ID, false), DQ_INST(k_level_fwd, 8, UP, 8, false, false, ID, false),
+    DQ_INST(k_level_fwd, 8, UP, 12, false, false, ID, false), DQ_INST(k_level_fwd, 12, UP, 12, false, false, ID, false), DQ_INST(k_level_fwd, 12, UP, 16, false, false, ID, false),
+    DQ_INST(k_level_fwd, 16, UP, 16, false, false, ID, false), DQ_INST(k_level_fwd, 4, INIT, 2, false, false, ID, false), DQ_INST(k_level_fwd, 4, INIT, 2, true, false, ID, false),
+    DQ_INST(k_level_fwd, 4, S1, 4, false, false, ID, false), DQ_INST(k_level_fwd, 4, S1, 4, true, false, ID, false), DQ_INST(k_level_fwd, 4, S1, 8, false, false, ID, false),
+    DQ_INST(k_level_fwd, 4, S1, 8, true, false, ID, false), DQ_INST(k_level_fwd, 8, S1, 8, false, false, ID, false), DQ_INST(k_level_fwd, 8, S1, 12, false, false, ID, false),
+    DQ_INST(k_level_fwd, 12, S1, 12, false, false, ID, false), DQ_INST(k_level_fwd, 12, S1, 16, false, false, ID, false), DQ_INST(k_level_fwd, 16, S1, 16, false, false, ID, false),
+    // the first level of a train step: the INIT stage that also stores its input (cat0_out)
+    DQ_INST(k_level_fwd, 4, INIT, 2, false, true, ID, false), DQ_INST(k_level_fwd, 4, INIT, 2, true, true, ID, false),
+    // the training head (the network's final block: k3 stage conv from 4 channels), then with the v objective's target (VT)
+    DQ_INST(k_level_fwd, 4, S1, 4, false, true, ID, false), DQ_INST(k_level_fwd, 4, S1, 4, true, true, ID, false), DQ_INST(k_level_fwd, 4, S1, 4, false, true, ID, true), DQ_INST(k_level_fwd, 4, S1, 4, true, true, ID, true),
+    // the Softplus head (pos_output_only): the final block's launch, k3 stage conv from 4 or 8 channels; its training head, and that under v
+    DQ_INST(k_level_fwd, 4, S1, 4, false, false, SP, false), DQ_INST(k_level_fwd, 4, S1, 4, true, false, SP, false), DQ_INST(k_level_fwd, 4, S1, 8, false, false, SP, false), DQ_INST(k_level_fwd, 4, S1, 8, true, false, SP, false),
+    DQ_INST(k_level_fwd, 4, S1, 4, false, true, SP, false), DQ_INST(k_level_fwd, 4, S1, 4, true, true, SP, false), DQ_INST(k_level_fwd, 4, S1, 4, false, true, SP, true), DQ_INST(k_level_fwd, 4, S1, 4, true, true, SP, true),
+    // sampling under the v objective: the update's third form has its own instantiations (VT), so that the eps / x0 ones keep the registers
+    // they had -- the final block's launch, k3 stage conv from 4 or 8 channels, either output activation
+    DQ_INST(k_level_fwd, 4, S1, 4, false, false, ID, true), DQ_INST(k_level_fwd, 4, S1, 4, true, false, ID, true), DQ_INST(k_level_fwd, 4, S1, 8, false, false, ID, true), DQ_INST(k_level_fwd, 4, S1, 8, true, false, ID, true),
+    DQ_INST(k_level_fwd, 4, S1, 4, false, false, SP, true), DQ_INST(k_level_fwd, 4, S1, 4, true, false, SP, true), DQ_INST(k_level_fwd, 4, S1, 8, false, false, SP, true), DQ_INST(k_level_fwd, 4, S1, 8, true, false, SP, true),
+};
 
 bool level_fwd_usable(int C, int rows, int n, int rows_per_sample, int pre_mode, int cp, int nblocks, const int* cinB, const bool* has_wr) {
-  if (!(C == 4 || C == 8 || C == 12 || C == 16) || n < 1 || n > 64 || (n & (n - 1)) != 0 || rows_per_sample <= 1) return false;
+  if (n < 1 || n > 64 || (n & (n - 1)) != 0 || rows_per_sample <= 1) return false;
   if (nblocks < 1 || nblocks > 2) return false;
-  if (!level_cp_built(C, pre_mode, cp)) return false;
+  if (!find_inst(LEVEL_FWD_BUILT, {C, pre_mode, pre_mode == NONE ? 4 : cp, false, false, ID, false})) return false;
   if (pre_mode == LEVEL_PRE_UP && n < 2) return false;
   for (int b = 0; b < nblocks; ++b)
     if (cinB[b] % 4 != 0 || cinB[b] < 0 || cinB[b] > C || (cinB[b] > 0) != has_wr[b]) return false;
@@ -719,13 +738,13 @@ bool level_fwd_usable(const LevelFwd& a) {
 }
 
 static int level_img_item(const LevelFwd& a, LevelImgSrc* m) {
-  auto poff = [&](const float* ptr) -> int { return ptr ? (int)(ptr - a.params) : -1; };
+  const float* P = a.params;
   m->pre = a.pre; m->G = a.C / 4; m->C = a.C; m->cp = a.pre == LEVEL_PRE_NONE ? 4 : a.cp;
   m->kp = a.pre == LEVEL_PRE_DOWN ? 4 : (a.pre == LEVEL_PRE_INIT ? 7 : 3);
-  m->nblocks = a.nblocks; m->pw = poff(a.pw);
+  m->nblocks = a.nblocks; m->pw = poff(P, a.pw);
   for (int b = 0; b < 2; ++b) {
     const ResFwd& r = a.blk[b < a.nblocks ? b : 0];
-    m->w1[b] = poff(r.w1); m->w2[b] = poff(r.w2); m->wr[b] = poff(r.wr); m->cin[b] = a.C + (b < a.nblocks ? r.cinB : 0);
+    m->w1[b] = poff(P, r.w1); m->w2[b] = poff(P, r.w2); m->wr[b] = poff(P, r.wr); m->cin[b] = a.C + (b < a.nblocks ? r.cinB : 0);
   }
   return 0;
 }
@@ -755,12 +774,21 @@ int launch_level_images(const LevelFwd* calls, int count, hipStream_t s) {
   return 0;
 }
 
+int check_level_block(const char* who, const ResFwd& r, const float* params, const float* ssb, int ss_stride) {
+  const std::string w(who);
+  DQ_REQUIRE(r.w1 && r.b1 && r.g1 && r.w2 && r.b2 && r.g2 && r.ss && (r.cinB == 0 || (r.inB && r.wr && r.br)), w + ": missing block operand");
+  DQ_REQUIRE(r.ss_stride == ss_stride && r.ss >= ssb - (1 << 20) && r.ss <= ssb + (1 << 20), w + ": the blocks' scale / shift vectors must share one buffer");
+  for (const float* q : {r.w1, r.b1, r.g1, r.w2, r.b2, r.g2, r.wr, r.br})
+    DQ_REQUIRE(!q || (q >= params && q - params < (1ll << 31)), w + ": a parameter lies outside the flat parameter buffer");
+  return 0;
+}
+
 int launch_level_fwd(const LevelFwd& a, hipStream_t s) {
   DQ_REQUIRE(level_fwd_usable(a), "level_fwd: unsupported shape");
   DQ_REQUIRE(a.rows % a.rows_per_sample == 0 && a.in && a.params, "level_fwd: bad rows / missing input");
   DQ_REQUIRE(a.pre == LEVEL_PRE_NONE || (a.pw && a.pb), "level_fwd: the input stage needs its conv weight and bias");
   LevelFwdK k;
-  auto poff = [&](const float* ptr) -> int { return ptr ? (int)(ptr - a.params) : -1; };
+  const float* P = a.params;
   DQ_REQUIRE(a.pre != LEVEL_PRE_INIT || (a.cond && a.ss_init && a.pre_out), "level_fwd: the first-layer stage needs the mixture, its scale / shift and h0");
   DQ_REQUIRE(!a.ew || (a.C == 4 && a.eb && (a.eps_out || a.x_t || a.loss_z) && (!a.x_t || (a.x_out && a.coef))), "level_fwd: incomplete head epilogue");
   DQ_REQUIRE(!a.loss_z || (a.ew && !a.x_t && a.loss_part && a.grad_out && a.dout && a.loss_parts_out), "level_fwd: incomplete training head");
@@ -773,22 +801,19 @@ int launch_level_fwd(const LevelFwd& a, hipStream_t s) {
   DQ_REQUIRE(!a.vt_x0 || (a.loss_z && a.vt_ab && a.vt_t && a.pre != LEVEL_PRE_INIT && !a.cond && !a.qs_noise),
              "level_fwd: the v-objective training head needs the noise, the schedule and the timesteps, in a launch without the first-layer stage");
   k.cond = a.cond; k.cm = a.cm; k.ca = a.ca; k.ss_init = a.ss_init ? (int)(a.ss_init - a.blk[0].ss) : 0;
-  k.ep_w = poff(a.ew); k.ep_b = poff(a.eb); k.pred = a.pred; k.eps_out = a.eps_out; k.x_t = a.x_t; k.x_out = a.x_out; k.coef = a.coef;
+  k.ep_w = poff(P, a.ew); k.ep_b = poff(P, a.eb); k.pred = a.pred; k.eps_out = a.eps_out; k.x_t = a.x_t; k.x_out = a.x_out; k.coef = a.coef;
   k.step_ptr = a.step_ptr;
   if (a.vt_x0) {  // (the members that share storage with the INIT stage's: LevelFwdK; the check above keeps the two apart)
     k.vt_x0 = a.vt_x0; k.vt_ab = a.vt_ab; k.vt_t = a.vt_t; k.vt_lw = a.vt_lw; k.vt_tm = a.vt_tm; k.vt_ta = a.vt_ta;
   }
-  k.in = a.in; k.pre_out = a.pre_out; k.pw = poff(a.pw); k.pb = poff(a.pb); k.nblocks = a.nblocks; k.rows_per_sample = a.rows_per_sample; k.n = a.n;
+  k.in = a.in; k.pre_out = a.pre_out; k.pw = poff(P, a.pw); k.pb = poff(P, a.pb); k.nblocks = a.nblocks; k.rows_per_sample = a.rows_per_sample; k.n = a.n;
   const float* ssb = a.blk[0].ss;
   k.ss_stride = a.blk[0].ss_stride;
   for (int b = 0; b < 2; ++b) {
     const ResFwd& r = a.blk[b < a.nblocks ? b : 0];
-    DQ_REQUIRE(r.w1 && r.b1 && r.g1 && r.w2 && r.b2 && r.g2 && r.ss && (r.cinB == 0 || (r.inB && r.wr && r.br)), "level_fwd: missing block operand");
-    DQ_REQUIRE(r.ss_stride == k.ss_stride && r.ss >= ssb - (1 << 20) && r.ss <= ssb + (1 << 20), "level_fwd: the blocks' scale / shift vectors must share one buffer");
-    for (const float* q : {r.w1, r.b1, r.g1, r.w2, r.b2, r.g2, r.wr, r.br})
-      DQ_REQUIRE(!q || (q >= a.params && q - a.params < (1ll << 31)), "level_fwd: a parameter lies outside the flat parameter buffer");
+    if (const int rc = check_level_block("level_fwd", r, P, ssb, k.ss_stride)) return rc;
     LevelBlkK& d = k.blk[b];
-    d.w1 = poff(r.w1); d.b1 = poff(r.b1); d.g1 = poff(r.g1); d.w2 = poff(r.w2); d.b2 = poff(r.b2); d.g2 = poff(r.g2); d.wr = poff(r.wr); d.br = poff(r.br);
+    d.w1 = poff(P, r.w1); d.b1 = poff(P, r.b1); d.g1 = poff(P, r.g1); d.w2 = poff(P, r.w2); d.b2 = poff(P, r.b2); d.g2 = poff(P, r.g2); d.wr = poff(P, r.wr); d.br = poff(P, r.br);
     d.ss_off = (int)(r.ss - ssb); d.cinB = b < a.nblocks ? r.cinB : 0;
     d.inB = r.inB; d.u1 = r.u1; d.a1 = r.a1; d.u2 = r.u2; d.out = r.out;
   }
@@ -810,89 +835,34 @@ int launch_level_fwd(const LevelFwd& a, hipStream_t s) {
     lds = (size_t)rounds * 4096 + 256 * 4;
   }
   DQ_REQUIRE(lds <= 64 * 1024, "level_fwd: weight image too large");
-  // one resident round: blocks per CU from the occupancy query, capped at 6 (at this kernel's ~106 scalar registers the hardware admits six
-  // 256-thread blocks per CU where the query can say seven: MI355X_MICROARCH.md, Residency), never more blocks than tiles need
-#define DQ_LVN(CC, PP, PC, NN) DQ_LVK((k_level_fwd<CC, PP, PC, NN>))
-#define DQ_LVK(KERNEL)                                                                                                        \
-  {                                                                                                                           \
-    const int nb = occ_blocks_per_cu((const void*)KERNEL, 256, lds);  /* keyed on (instantiation, lds, device) */              \
-    if (nb < 0) return 1;                                                                                                     \
-    const int occ = std::min(nb, 6);                                                                                          \
-    const int gx = std::max(1, std::min(occ * num_cus() / B, (tiles_ps + 3) / 4));  /* workgroups per sample */                \
-    if (a.loss_z) {                                                                                                           \
-      DQ_REQUIRE((int64_t)gx * B * 4 <= LEVEL_LOSS_PARTS, "level_fwd: more waves than the loss partial-sum scratch holds");      \
-      *a.loss_parts_out = gx * B * 4;                                                                                         \
-    }                                                                                                                         \
-    hipLaunchKernelGGL(KERNEL, dim3(gx, B), dim3(256), lds, s, k, a.params, ssb, tiles_ps, (int)total, ln, a.img);             \
-    DQ_LAUNCH_CHECK();                                                                                                        \
-    return 0;                                                                                                                 \
-  }
-#define DQ_LV(CC, PP, PC)                                                                                                     \
-  if (a.C == CC && a.pre == PP && cp == PC) {                                                                                 \
-    if (CC == 4 && a.n == 64) DQ_LVN(CC, PP, PC, (CC == 4))                                                                    \
-    DQ_LVN(CC, PP, PC, false)                                                                                                 \
-  }
-  if (a.x_t && a.pred == DQ_PRED_V) {  // sampling under the v objective: the update's third form has its own instantiations (VT), so that
-    // the eps / x0 ones keep the registers they had -- the final block's launch, k3 stage conv from 4 or 8 channels, either output activation
+  // the instantiation: the existing refusals of each head first, then ONE key from the call
+  const bool vt_sample = a.x_t && a.pred == DQ_PRED_V;
+  if (vt_sample) {
     DQ_REQUIRE(a.C == 4 && a.pre == LEVEL_PRE_S1 && (cp == 4 || cp == 8) && !a.loss_z,
                "level_fwd: the v-objective sampling head is built for the (4, k3 conv, 4 | 8) launch");
-    if (a.final_act == FINAL_SOFTPLUS) {
-      if (cp == 4) {
-        if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, false, FINAL_SOFTPLUS, true>))
-        DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, false, FINAL_SOFTPLUS, true>))
-      }
-      if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 8, true, false, FINAL_SOFTPLUS, true>))
-      DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 8, false, false, FINAL_SOFTPLUS, true>))
-    }
-    if (cp == 4) {
-      if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, false, FINAL_IDENTITY, true>))
-      DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, false, FINAL_IDENTITY, true>))
-    }
-    if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 8, true, false, FINAL_IDENTITY, true>))
-    DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 8, false, false, FINAL_IDENTITY, true>))
-  }
-  if (a.final_act == FINAL_SOFTPLUS) {  // the Softplus head (pos_output_only): the final block's launch, k3 stage conv from 4 or 8 channels
+  } else if (a.final_act == FINAL_SOFTPLUS) {
     DQ_REQUIRE(a.C == 4 && a.pre == LEVEL_PRE_S1 && (cp == 4 || (cp == 8 && !a.loss_z)), "level_fwd: the Softplus head is built for the (4, k3 conv, 4 | 8) launch");
-    if (a.loss_z && a.vt_x0) {
-      if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, true, FINAL_SOFTPLUS, true>))
-      DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, true, FINAL_SOFTPLUS, true>))
-    }
-    if (a.loss_z) {
-      if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, true, FINAL_SOFTPLUS>))
-      DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, true, FINAL_SOFTPLUS>))
-    }
-    if (cp == 4) {
-      if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, false, FINAL_SOFTPLUS>))
-      DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, false, FINAL_SOFTPLUS>))
-    }
-    if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 8, true, false, FINAL_SOFTPLUS>))
-    DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 8, false, false, FINAL_SOFTPLUS>))
-  }
-  if (a.loss_z) {  // the training head has its own instantiations (the network's final block: k3 stage conv from 4 channels)
+  } else if (a.loss_z) {
     DQ_REQUIRE(a.C == 4 && a.pre == LEVEL_PRE_S1 && cp == 4, "level_fwd: the training head is built for the (4, k3 conv, 4) launch");
-    if (a.vt_x0) {  // (the v objective's target)
-      if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, true, FINAL_IDENTITY, true>))
-      DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, true, FINAL_IDENTITY, true>))
-    }
-    if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, true, true>))
-    DQ_LVK((k_level_fwd<4, LEVEL_PRE_S1, 4, false, true>))
-  }
-  if (a.cat0_out) {  // the first level of a train step: the INIT stage that also stores its input
+  } else if (a.cat0_out) {
     DQ_REQUIRE(a.C == 4 && cp == 2, "level_fwd: the first-layer stage is built for (4, init conv, 2)");
-    if (a.n == 64) DQ_LVK((k_level_fwd<4, LEVEL_PRE_INIT, 2, true, true>))
-    DQ_LVK((k_level_fwd<4, LEVEL_PRE_INIT, 2, false, true>))
   }
-  DQ_LV(4, LEVEL_PRE_NONE, 4) DQ_LV(8, LEVEL_PRE_NONE, 4) DQ_LV(12, LEVEL_PRE_NONE, 4) DQ_LV(16, LEVEL_PRE_NONE, 4)
-  DQ_LV(4, LEVEL_PRE_DOWN, 4) DQ_LV(8, LEVEL_PRE_DOWN, 4) DQ_LV(8, LEVEL_PRE_DOWN, 8) DQ_LV(12, LEVEL_PRE_DOWN, 8) DQ_LV(12, LEVEL_PRE_DOWN, 12)
-  DQ_LV(16, LEVEL_PRE_DOWN, 12) DQ_LV(16, LEVEL_PRE_DOWN, 16)
-  DQ_LV(4, LEVEL_PRE_UP, 4) DQ_LV(4, LEVEL_PRE_UP, 8) DQ_LV(8, LEVEL_PRE_UP, 8) DQ_LV(8, LEVEL_PRE_UP, 12) DQ_LV(12, LEVEL_PRE_UP, 12) DQ_LV(12, LEVEL_PRE_UP, 16)
-  DQ_LV(16, LEVEL_PRE_UP, 16)
-  DQ_LV(4, LEVEL_PRE_INIT, 2)
-  DQ_LV(4, LEVEL_PRE_S1, 4) DQ_LV(4, LEVEL_PRE_S1, 8) DQ_LV(8, LEVEL_PRE_S1, 8) DQ_LV(8, LEVEL_PRE_S1, 12) DQ_LV(12, LEVEL_PRE_S1, 12) DQ_LV(12, LEVEL_PRE_S1, 16)
-  DQ_LV(16, LEVEL_PRE_S1, 16)
-#undef DQ_LV
-#undef DQ_LVN
-#undef DQ_LVK
+  const auto* inst = find_inst(LEVEL_FWD_BUILT, {a.C, a.pre, cp, a.n == 64 && a.C == 4, a.loss_z || a.cat0_out, a.final_act, vt_sample || a.vt_x0});
+  if (inst) {
+    // one resident round: blocks per CU from the occupancy query, capped at 6 (at this kernel's ~106 scalar registers the hardware admits six
+    // 256-thread blocks per CU where the query can say seven: MI355X_MICROARCH.md, Residency), never more blocks than tiles need
+    const int nb = occ_blocks_per_cu((const void*)inst->fn, 256, lds);  // keyed on (instantiation, lds, device)
+    if (nb < 0) return 1;
+    const int occ = std::min(nb, 6);
+    const int gx = std::max(1, std::min(occ * device_cus() / B, (tiles_ps + 3) / 4));  // workgroups per sample
+    if (a.loss_z) {
+      DQ_REQUIRE((int64_t)gx * B * 4 <= LEVEL_LOSS_PARTS, "level_fwd: more waves than the loss partial-sum scratch holds");
+      *a.loss_parts_out = gx * B * 4;
+    }
+    hipLaunchKernelGGL(inst->fn, dim3(gx, B), dim3(256), lds, s, k, a.params, ssb, tiles_ps, (int)total, ln, a.img);
+    DQ_LAUNCH_CHECK();
+    return 0;
+  }
   set_error("level_fwd: unsupported (C, stage, stage input width)");
   return 2;
 }

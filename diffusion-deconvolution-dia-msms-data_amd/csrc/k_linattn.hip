@@ -21,6 +21,7 @@
 //   The W2 contraction and the post-norm run on the VALU for this lane's own channels; HBM traffic: x in, y out (+ ypre).
 #include "dq_common.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 #include "dq_mfma.h"
 #include "dq_probe.h"
 #include <algorithm>
@@ -533,30 +534,25 @@ __global__ void __launch_bounds__(256) k_linattn_fwd(LinAttn a) {
   DQ_PSTAMP(300000 + C * 100 + N, 4);
 }
 
-static int la_num_cus() {
-  static const int v = [] { int d = 0; hipDeviceProp_t pr; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) ? pr.multiProcessorCount : 256; }();
-  return v;
-}
-// split-bf16 K = C projections for 4 / 8 channels
-template <int C>
-static int linattn_fwd_n(const LinAttn& a, hipStream_t s) {
-#define DQ_LA(NN)                                                                      \
-  case NN: {                                                                           \
-    constexpr int RW = NN >= 32 ? 1 : 32 / NN;                                         \
-    /* 8 channels, rows of <= 8 positions: the 24 KB bf16 image costs the fourth workgroup per CU (278 -> 296 us at batch 512): fp32 form */ \
-    constexpr bool CAN_BF = C <= 8 && NN > 1 && !(C == 8 && NN <= 8);                  \
-    const int units = cdiv(a.rows, RW);                                                \
-    const int grid = cdiv(units, 4);  /* one unit per wave: a wave walking several units with the next unit's x in flight was measured slower */ \
-    hipLaunchKernelGGL((k_linattn_fwd<C, NN, CAN_BF>), dim3(grid), dim3(256), 0, s, a); \
-    break;                                                                             \
-  }
-  switch (a.n) {
-    DQ_LA(1) DQ_LA(2) DQ_LA(4) DQ_LA(8) DQ_LA(16) DQ_LA(32) DQ_LA(64)
-    default:
-      set_error("linattn_fwd: m/z length " + std::to_string(a.n) + " is not built (powers of two up to 64)");
-      return 2;
-  }
-#undef DQ_LA
+// The built instantiations <C, N, BF>.  BF: split-bf16 K = C projections for 4 / 8 channels, but not at 8 channels with rows of
+// <= 8 positions, where the 24 KB bf16 image costs the fourth workgroup per CU (278 -> 296 us at batch 512): fp32 form.
+using LinAttnFwdFn = decltype(&k_linattn_fwd<4, 1, false>);
+static const Inst<LinAttnFwdFn, 3> LINATTN_FWD_BUILT[] = {
+    DQ_INST(k_linattn_fwd, 4, 1, false), DQ_INST(k_linattn_fwd, 4, 2, true), DQ_INST(k_linattn_fwd, 4, 4, true), DQ_INST(k_linattn_fwd, 4, 8, true),
+    DQ_INST(k_linattn_fwd, 4, 16, true), DQ_INST(k_linattn_fwd, 4, 32, true), DQ_INST(k_linattn_fwd, 4, 64, true),
+    DQ_INST(k_linattn_fwd, 8, 1, false), DQ_INST(k_linattn_fwd, 8, 2, false), DQ_INST(k_linattn_fwd, 8, 4, false), DQ_INST(k_linattn_fwd, 8, 8, false),
+    DQ_INST(k_linattn_fwd, 8, 16, true), DQ_INST(k_linattn_fwd, 8, 32, true), DQ_INST(k_linattn_fwd, 8, 64, true),
+    DQ_INST(k_linattn_fwd, 12, 1, false), DQ_INST(k_linattn_fwd, 12, 2, false), DQ_INST(k_linattn_fwd, 12, 4, false), DQ_INST(k_linattn_fwd, 12, 8, false),
+    DQ_INST(k_linattn_fwd, 12, 16, false), DQ_INST(k_linattn_fwd, 12, 32, false), DQ_INST(k_linattn_fwd, 12, 64, false),
+    DQ_INST(k_linattn_fwd, 16, 1, false), DQ_INST(k_linattn_fwd, 16, 2, false), DQ_INST(k_linattn_fwd, 16, 4, false), DQ_INST(k_linattn_fwd, 16, 8, false),
+    DQ_INST(k_linattn_fwd, 16, 16, false), DQ_INST(k_linattn_fwd, 16, 32, false), DQ_INST(k_linattn_fwd, 16, 64, false)};
+static int linattn_fwd_reg(const LinAttn& a, hipStream_t s) {
+  if (!find_inst(LINATTN_FWD_BUILT, {a.C, 1, false})) { set_error("linattn_fwd: unsupported channel count " + std::to_string(a.C)); return 2; }
+  const auto* inst = find_inst(LINATTN_FWD_BUILT, {a.C, a.n, a.C <= 8 && a.n > 1 && !(a.C == 8 && a.n <= 8)});
+  if (!inst) { set_error("linattn_fwd: m/z length " + std::to_string(a.n) + " is not built (powers of two up to 64)"); return 2; }
+  const int units = cdiv(a.rows, a.n >= 32 ? 1 : 32 / a.n);
+  const int grid = cdiv(units, 4);  // one unit per wave: a wave walking several units with the next unit's x in flight was measured slower
+  hipLaunchKernelGGL(inst->fn, dim3(grid), dim3(256), 0, s, a);
   DQ_LAUNCH_CHECK();
   return 0;
 }
@@ -750,13 +746,7 @@ int launch_linattn_fwd(const LinAttn& a, hipStream_t s) {
     case LA_FWD_ROWS: return launch_la_rows_fwd(a, s);
     case LA_FWD_REG: break;
   }
-  switch (a.C) {
-    case 4: return linattn_fwd_n<4>(a, s);
-    case 8: return linattn_fwd_n<8>(a, s);
-    case 12: return linattn_fwd_n<12>(a, s);
-    case 16: return linattn_fwd_n<16>(a, s);
-    default: set_error("linattn_fwd: unsupported channel count " + std::to_string(a.C)); return 2;
-  }
+  return linattn_fwd_reg(a, s);
 }
 
 }  // namespace dq

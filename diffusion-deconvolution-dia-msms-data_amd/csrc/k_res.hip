@@ -10,6 +10,7 @@
 #include "dq_common.h"
 #include "dq_wave.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 #include "k_res_common.h"
 #include <cstdlib>
 
@@ -220,6 +221,11 @@ __global__ void __launch_bounds__(BS) k_res_bwd(ResBwd a) {
   }
 }
 
+using ResBwdFn = decltype(&k_res_bwd<4, 256>);
+static const Inst<ResBwdFn, 2> RES_BWD_BUILT[] = {  // <C, BS>
+    DQ_INST(k_res_bwd, 4, 256), DQ_INST(k_res_bwd, 4, 512), DQ_INST(k_res_bwd, 8, 256), DQ_INST(k_res_bwd, 8, 512),
+    DQ_INST(k_res_bwd, 12, 256), DQ_INST(k_res_bwd, 12, 512), DQ_INST(k_res_bwd, 16, 256), DQ_INST(k_res_bwd, 16, 512)};
+
 ResBwdForm res_bwd_form(const ResBwd& a, bool wg) {
   if (wg) return RES_BWD_WG;
   if (res_rt_usable(a.C, a.cinA, a.cinB, a.wr != nullptr, a.rows_per_sample)) return RES_BWD_RT;  // the bottleneck's blocks
@@ -245,13 +251,9 @@ int launch_res_bwd(const ResBwd& a, hipStream_t s) {
   ResBwd k = a;
   DQ_REQUIRE(k.gpart && k.gblocks && k.gpart_floats >= (int64_t)grid.x * grid.y * 4 * a.C, "res_bwd: partial-sum slot missing or too small");
   *k.gblocks = (int)grid.x;  // blocks per sample
-#define DQ_RB(CC)                                                                \
-  case CC:                                                                       \
-    if (BS == 512) hipLaunchKernelGGL((k_res_bwd<CC, 512>), grid, block, 0, s, k); \
-    else hipLaunchKernelGGL((k_res_bwd<CC, 256>), grid, block, 0, s, k);          \
-    break;
-  switch (a.C) { DQ_RB(4) DQ_RB(8) DQ_RB(12) DQ_RB(16) }
-#undef DQ_RB
+  const auto* inst = find_inst(RES_BWD_BUILT, {a.C, BS});
+  DQ_REQUIRE(inst, "res_bwd: unsupported (C, block size)");
+  hipLaunchKernelGGL(inst->fn, grid, block, 0, s, k);
   DQ_LAUNCH_CHECK();
   return 0;
 }

@@ -11,6 +11,7 @@
 #include "dq_common.h"
 #include "dq_wave.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 
 namespace dq {
 
@@ -221,9 +222,11 @@ __global__ void __launch_bounds__(256) k_res_bwd_cp(ResBwd a) {
   }
 }
 
-bool res_cp_usable(int n, int C, int cinA, int cinB) {
-  return (C == 12 || C == 16) && (n == 1 || n == 2 || n == 4 || n == 8) && cinA <= 16 && cinB <= 16;
-}
+using ResCpFn = decltype(&k_res_bwd_cp<12, 1>);
+static const Inst<ResCpFn, 2> RES_CP_BUILT[] = {  // <C, N>
+    DQ_INST(k_res_bwd_cp, 12, 1), DQ_INST(k_res_bwd_cp, 12, 2), DQ_INST(k_res_bwd_cp, 12, 4), DQ_INST(k_res_bwd_cp, 12, 8),
+    DQ_INST(k_res_bwd_cp, 16, 1), DQ_INST(k_res_bwd_cp, 16, 2), DQ_INST(k_res_bwd_cp, 16, 4), DQ_INST(k_res_bwd_cp, 16, 8)};
+bool res_cp_usable(int n, int C, int cinA, int cinB) { return find_inst(RES_CP_BUILT, {C, n}) && cinA <= 16 && cinB <= 16; }
 
 int launch_res_bwd_cp(const ResBwd& a, hipStream_t s) {
   DQ_REQUIRE(a.rows_per_sample > 1 && res_cp_usable(a.n, a.C, a.cinA, a.cinB), "res_bwd_cp: unsupported shape");
@@ -232,10 +235,11 @@ int launch_res_bwd_cp(const ResBwd& a, hipStream_t s) {
   ResBwd k = a;  // partial sums of the norm gains and scale / shift (see ResBwd::gpart)
   DQ_REQUIRE(k.gpart && k.gblocks && k.gpart_floats >= (int64_t)grid.x * grid.y * 4 * a.C, "res_bwd_cp: partial-sum slot missing or too small");
   *k.gblocks = (int)grid.x;  // blocks per sample
-#define DQ_CP(CC, NN) \
-  if (a.C == CC && a.n == NN) { hipLaunchKernelGGL((k_res_bwd_cp<CC, NN>), grid, block, 0, s, k); DQ_LAUNCH_CHECK(); return 0; }
-  DQ_CP(12, 1) DQ_CP(12, 2) DQ_CP(12, 4) DQ_CP(12, 8) DQ_CP(16, 1) DQ_CP(16, 2) DQ_CP(16, 4) DQ_CP(16, 8)
-#undef DQ_CP
+  if (const auto* inst = find_inst(RES_CP_BUILT, {a.C, a.n})) {
+    hipLaunchKernelGGL(inst->fn, grid, block, 0, s, k);
+    DQ_LAUNCH_CHECK();
+    return 0;
+  }
   set_error("res_bwd_cp: unsupported (C, n)");
   return 2;
 }

@@ -16,6 +16,7 @@
 #include "dq_common.h"
 #include "dq_wave.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 #include "dq_slots.h"
 #include "dq_options.h"
 #include <algorithm>
@@ -257,15 +258,6 @@ __global__ void __launch_bounds__(256) k_res_rows_bwd(ResBwd a) {
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-int device_cus() {
-  static const int v = [] {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    return cus;
-  }();
-  return v;
-}
-
 }  // namespace
 
 // One wave does a 16-row tile here where k_res_cp.hip spreads it over four (lane = channel): 4x fewer wave-instructions, but a 1.2 - 1.5x
@@ -273,6 +265,12 @@ int device_cus() {
 // dq_set_option("res_rows_bwd_min_rows", rows) overrides the rule (tests run this form at a few rows).  The grid is (cdiv(rows_per_sample, 64),
 // B) workgroups with no resident-round sizing, and its partial-sum slots fit the block's gpart at every row count (ResBuf: >= cdiv(rps, 16)
 // per sample), so any threshold is safe.
+using ResRowsFn = decltype(&k_res_rows_bwd<12, 2, true>);
+static const Inst<ResRowsFn, 3> RES_ROWS_BUILT[] = {  // <C, N, WR>
+    DQ_INST(k_res_rows_bwd, 12, 2, true), DQ_INST(k_res_rows_bwd, 12, 2, false), DQ_INST(k_res_rows_bwd, 12, 4, true), DQ_INST(k_res_rows_bwd, 12, 4, false),
+    DQ_INST(k_res_rows_bwd, 12, 8, true), DQ_INST(k_res_rows_bwd, 12, 8, false), DQ_INST(k_res_rows_bwd, 16, 2, true), DQ_INST(k_res_rows_bwd, 16, 2, false),
+    DQ_INST(k_res_rows_bwd, 16, 4, true), DQ_INST(k_res_rows_bwd, 16, 4, false), DQ_INST(k_res_rows_bwd, 16, 8, true), DQ_INST(k_res_rows_bwd, 16, 8, false)};
+
 int res_rows_bwd_min_rows() {
   const int64_t o = option(OPT_RES_ROWS_BWD_MIN_ROWS);
   if (o >= 0) return (int)std::min<int64_t>(o, INT32_MAX);
@@ -280,7 +278,7 @@ int res_rows_bwd_min_rows() {
 }
 
 bool res_rows_bwd_usable(const ResBwd& a) {
-  if (!(a.C == 12 || a.C == 16) || !(a.n == 2 || a.n == 4 || a.n == 8) || a.rows_per_sample < 2) return false;
+  if (!find_inst(RES_ROWS_BUILT, {a.C, a.n, a.wr != nullptr}) || a.rows_per_sample < 2) return false;
   if (a.rows < res_rows_bwd_min_rows()) return false;
   if (a.cinA < 4 || a.cinA > 16 || (a.cinA & 3) || a.cinB < 0 || a.cinB > 16 || (a.cinB & 3)) return false;
   if (!a.wr && !(a.cinA == a.C && a.cinB == 0)) return false;
@@ -296,15 +294,11 @@ int launch_res_rows_bwd(const ResBwd& a, hipStream_t s) {
   const dim3 grid(cdiv(a.rows_per_sample, 64), B);
   DQ_REQUIRE(a.gpart && a.gblocks && a.gpart_floats >= (int64_t)grid.x * grid.y * 4 * a.C, "res_rows_bwd: partial-sum slot missing or too small");
   *a.gblocks = (int)grid.x;  // workgroups per sample
-#define DQ_RR(CC, NN)                                                                                        \
-  if (a.C == CC && a.n == NN) {                                                                              \
-    if (a.wr) hipLaunchKernelGGL((k_res_rows_bwd<CC, NN, true>), grid, dim3(256), 0, s, a);                  \
-    else hipLaunchKernelGGL((k_res_rows_bwd<CC, NN, false>), grid, dim3(256), 0, s, a);                      \
-    DQ_LAUNCH_CHECK();                                                                                       \
-    return 0;                                                                                                \
+  if (const auto* inst = find_inst(RES_ROWS_BUILT, {a.C, a.n, a.wr != nullptr})) {
+    hipLaunchKernelGGL(inst->fn, grid, dim3(256), 0, s, a);
+    DQ_LAUNCH_CHECK();
+    return 0;
   }
-  DQ_RR(12, 2) DQ_RR(12, 4) DQ_RR(12, 8) DQ_RR(16, 2) DQ_RR(16, 4) DQ_RR(16, 8)
-#undef DQ_RR
   set_error("res_rows_bwd: unsupported (C, n)");
   return 2;
 }

@@ -25,6 +25,7 @@
 #include "dq_common.h"
 #include "dq_wave.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 #include "dq_slots.h"
 #include "k_res_common.h"
 #include "dq_probe.h"
@@ -466,22 +467,25 @@ __global__ void __launch_bounds__(256) k_res_wg_reduce(ResWgReduceMulti m) {
   }
 }
 
+using ResWgFn = decltype(&k_res_bwd_wg<4, true>);
+static const Inst<ResWgFn, 2> RES_WG_BUILT[] = {  // <C, WR>
+    DQ_INST(k_res_bwd_wg, 4, true), DQ_INST(k_res_bwd_wg, 4, false), DQ_INST(k_res_bwd_wg, 8, true), DQ_INST(k_res_bwd_wg, 8, false)};
+
 bool res_wg_usable(int n, int C, int cinA, int cinB, int rows_per_sample) {
   // (rows of up to 64 positions: a row lives inside one wave, whose DPP shifts are the conv's neighbours; rows of 8 or more: the run-of-16
   // walk of the weight-gradient phases special-cases only rows of 8)
   // 4 / 8 channels only.  A 12 / 16-channel form was built and measured slower inside the train step (B = 32): 496 us for its 14 launches
   // against 279 us of k_res_bwd_cp + their weight-gradient launches on the side stream -- one 256-position tile per workgroup left staging,
   // the channel-strided loads of rows of 2 positions and the flush of 47 accumulator quads with nothing to overlap them.
-  if (!(C == 4 || C == 8)) return false;
+  if (!find_inst(RES_WG_BUILT, {C, cinB != 0})) return false;
   return n >= 8 && n <= 64 && (n & (n - 1)) == 0 && rows_per_sample > 1 && cinA == C && (cinB == 0 || (cinB % 4 == 0 && cinB <= C));
 }
 
-template <int C, bool WR>
-static size_t res_wg_lds_bytes() {
-  constexpr int CQ = C / 4, GI = WR ? 2 * CQ : CQ;
-  constexpr int JT2 = C * CQ * 3, JT1 = C * GI * 3, JTR = WR ? C * GI : 0;
-  constexpr int JTT = pad4(JT2) + pad4(JT1) + pad4(JTR);
-  return sizeof(float) * ((size_t)(WR ? 6 : 4) * Img<C>::FLOATS + (WR ? 0 : 8) + 16 * C + (size_t)JTT * 4 + 4 * C);
+static size_t res_wg_lds_bytes(int C, bool WR) {  // of k_res_bwd_wg<C, WR>
+  const int CQ = C / 4, GI = WR ? 2 * CQ : CQ;
+  const int JT2 = C * CQ * 3, JT1 = C * GI * 3, JTR = WR ? C * GI : 0;
+  const int JTT = pad4(JT2) + pad4(JT1) + pad4(JTR);
+  return sizeof(float) * ((size_t)(WR ? 6 : 4) * (C == 4 ? Img<4>::FLOATS : Img<8>::FLOATS) + (WR ? 0 : 8) + 16 * C + (size_t)JTT * 4 + 4 * C);
 }
 
 // grid of a launch: a workgroup takes `tpb` consecutive tiles of one sample; about 1024 workgroups in all (one resident round at
@@ -513,25 +517,13 @@ int launch_res_bwd_wg(const ResBwdWg& a_in, hipStream_t s, ResWgReduce* red_out)
   const bool wr = a.wr != nullptr;
   // ONE resident round: with more workgroups than the CUs hold (1-4 each: the LDS images), the few left over ran as a second round
   // behind the first -- up to twice the time.  More tiles per workgroup instead (never fewer than the arena's slot count assumes).
-  const void* fn = nullptr;
-  size_t lds = 0;
-#define DQ_WGK(CC, WW) if (a.C == CC && wr == WW) { fn = (const void*)k_res_bwd_wg<CC, WW>; lds = res_wg_lds_bytes<CC, WW>(); }
-  DQ_WGK(4, true) DQ_WGK(4, false) DQ_WGK(8, true) DQ_WGK(8, false)
-#undef DQ_WGK
-  DQ_REQUIRE(fn && lds <= 160 * 1024, "res_bwd_wg: no kernel for this shape");
+  const auto* inst = find_inst(RES_WG_BUILT, {a.C, wr});
+  const size_t lds = inst ? res_wg_lds_bytes(a.C, wr) : 0;
+  DQ_REQUIRE(inst && lds <= 160 * 1024, "res_bwd_wg: no kernel for this shape");
   {
-    static int occ[2][2] = {{0, 0}, {0, 0}};
-    int& o = occ[a.C / 4 - 1][wr];
-    if (!o) {
-      if (lds > 48 * 1024) DQ_HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      int nb = 0;
-      DQ_HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, lds));
-      o = std::max(1, std::min(nb, 6));
-    }
-    int dev = 0;
-    hipDeviceProp_t pr;
-    static const int cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
-    const int64_t resident = (int64_t)o * cus, total = (int64_t)a.tiles_ps * B;
+    const int nb = occ_blocks_per_cu((const void*)inst->fn, 256, lds);  // (raises the dynamic-LDS limit above 48 KB)
+    if (nb < 0) return 1;
+    const int64_t resident = (int64_t)std::min(nb, 6) * device_cus(), total = (int64_t)a.tiles_ps * B;
     a.tpb = std::max(a.tpb, (int)((total + resident - 1) / resident));
     while (a.tpb < a.tiles_ps && (int64_t)cdiv(a.tiles_ps, a.tpb) * B > resident) ++a.tpb;  // (the per-sample rounding can still overshoot)
     gx = cdiv(a.tiles_ps, a.tpb);
@@ -539,9 +531,7 @@ int launch_res_bwd_wg(const ResBwdWg& a_in, hipStream_t s, ResWgReduce* red_out)
   a.nv = res_wg_nv(a.C, a.cinA + a.cinB, wr);
   DQ_REQUIRE(a.part_floats >= (int64_t)gx * B * a.nv, "res_bwd_wg: slot scratch too small");
   dim3 grid(gx, B), block(256);
-#define DQ_WGL(CC, WW) if (a.C == CC && wr == WW) hipLaunchKernelGGL((k_res_bwd_wg<CC, WW>), grid, block, lds, s, a);
-  DQ_WGL(4, true) DQ_WGL(4, false) DQ_WGL(8, true) DQ_WGL(8, false)
-#undef DQ_WGL
+  hipLaunchKernelGGL(inst->fn, grid, block, lds, s, a);
   DQ_LAUNCH_CHECK();
   if (red_out) {
     ResWgReduce r;

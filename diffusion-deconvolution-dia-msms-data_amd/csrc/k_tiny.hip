@@ -21,6 +21,7 @@
 #include "dq_common.h"
 #include "dq_dev.h"
 #include "dq_kernels.h"
+#include "dq_launch.h"
 #include "dq_mfma.h"
 #include "dq_plan.h"
 #include "dq_probe.h"
@@ -824,6 +825,22 @@ bool tiny_enabled() {
 
 }  // namespace
 
+// the built instantiations <C, N, PRE, CP, CS> of the forward and <C, PRE, CP, CS, UPT> of the backward (a launch without a stage: CP = 0)
+using TinyFwdFn = decltype(&k_tiny_fwd<12, 2, LEVEL_PRE_DOWN, 12, 0>);
+static const Inst<TinyFwdFn, 5> TINY_FWD_BUILT[] = {
+    DQ_INST(k_tiny_fwd, 12, 2, LEVEL_PRE_DOWN, 12, 0), DQ_INST(k_tiny_fwd, 16, 1, LEVEL_PRE_DOWN, 12, 0),
+    DQ_INST(k_tiny_fwd, 16, 1, LEVEL_PRE_NONE, 0, 16), DQ_INST(k_tiny_fwd, 16, 2, LEVEL_PRE_UP, 16, 12)};
+using TinyBwdFn = decltype(&k_tiny_bwd<16, LEVEL_PRE_DOWN, 12, 0, false>);
+static const Inst<TinyBwdFn, 5> TINY_BWD_BUILT[] = {
+    DQ_INST(k_tiny_bwd, 16, LEVEL_PRE_DOWN, 12, 0, false), DQ_INST(k_tiny_bwd, 16, LEVEL_PRE_NONE, 0, 16, false),
+    DQ_INST(k_tiny_bwd, 16, LEVEL_PRE_NONE, 0, 16, true)};
+static const Inst<TinyFwdFn, 5>* tiny_fwd_inst(const LevelFwd& a) {
+  return find_inst(TINY_FWD_BUILT, {a.C, a.n, a.pre, a.pre == LEVEL_PRE_NONE ? 0 : a.cp, a.blk[0].cinB});
+}
+static const Inst<TinyBwdFn, 5>* tiny_bwd_inst(const TinyBwd& t) {
+  return find_inst(TINY_BWD_BUILT, {t.C, t.pre, t.pre == LEVEL_PRE_NONE ? 0 : t.cp, t.cs, t.up_w != nullptr});
+}
+
 bool tiny_fwd_usable(const TinyFwd& t) {
   const LevelFwd& a = t.lv;
   if (!tiny_enabled()) return false;
@@ -834,11 +851,7 @@ bool tiny_fwd_usable(const TinyFwd& t) {
   const bool extras = t.la || t.post_w || t.in_folded;
   if (extras && a.n != 1) return false;
   if (t.post_w && !t.la) return false;  // (the post conv's steps sit behind the LinearAttention's in the image)
-  if (a.C == 12 && a.n == 2 && a.pre == LEVEL_PRE_DOWN && a.cp == 12 && cs == 0) return true;
-  if (a.C == 16 && a.n == 1 && a.pre == LEVEL_PRE_DOWN && a.cp == 12 && cs == 0) return true;
-  if (a.C == 16 && a.n == 1 && a.pre == LEVEL_PRE_NONE && cs == 16) return true;
-  if (a.C == 16 && a.n == 2 && a.pre == LEVEL_PRE_UP && a.cp == 16 && cs == 12) return true;
-  return false;
+  return tiny_fwd_inst(a) != nullptr;
 }
 
 int64_t tiny_img_floats(const TinyFwd& t) {
@@ -872,11 +885,6 @@ int launch_tiny_images(const TinyFwd* calls, int count, hipStream_t s) {
   return 0;
 }
 
-static int tiny_num_cus() {
-  static const int v = [] { int d = 0; hipDeviceProp_t pr; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) ? pr.multiProcessorCount : 256; }();
-  return v;
-}
-
 int launch_tiny_fwd(const TinyFwd& t, hipStream_t s) {
   const LevelFwd& a = t.lv;
   DQ_REQUIRE(tiny_fwd_usable(t), "tiny_fwd: unsupported shape");
@@ -884,24 +892,21 @@ int launch_tiny_fwd(const TinyFwd& t, hipStream_t s) {
   DQ_REQUIRE(a.pre == LEVEL_PRE_NONE || (a.pw && a.pb), "tiny_fwd: the input stage needs its conv weight and bias");
   DQ_REQUIRE(!t.la || (t.w_qkv && t.w_out && t.b_out && t.g_pre && t.g_out && t.la_y), "tiny_fwd: incomplete LinearAttention operands");
   DQ_REQUIRE(!t.post_w || (t.post_b && t.post_out), "tiny_fwd: incomplete post conv");
-  auto poff = [&](const float* ptr) -> int { return ptr ? (int)(ptr - a.params) : -1; };
+  const float* P = a.params;
   TinyFwdK k;
-  k.in = a.in; k.pre_out = a.pre_out; k.in_copy = t.in_copy; k.pb = poff(a.pb); k.rows_per_sample = a.rows_per_sample; k.in_folded = t.in_folded;
+  k.in = a.in; k.pre_out = a.pre_out; k.in_copy = t.in_copy; k.pb = poff(P, a.pb); k.rows_per_sample = a.rows_per_sample; k.in_folded = t.in_folded;
   const float* ssb = a.blk[0].ss;
   k.ss_stride = a.blk[0].ss_stride;
   for (int b = 0; b < 2; ++b) {
     const ResFwd& r = a.blk[b];
-    DQ_REQUIRE(r.w1 && r.b1 && r.g1 && r.w2 && r.b2 && r.g2 && r.ss && (r.cinB == 0 || (r.inB && r.wr && r.br)), "tiny_fwd: missing block operand");
-    DQ_REQUIRE(r.ss_stride == k.ss_stride && r.ss >= ssb - (1 << 20) && r.ss <= ssb + (1 << 20), "tiny_fwd: the blocks' scale / shift vectors must share one buffer");
-    for (const float* q : {r.w1, r.b1, r.g1, r.w2, r.b2, r.g2, r.wr, r.br})
-      DQ_REQUIRE(!q || (q >= a.params && q - a.params < (1ll << 31)), "tiny_fwd: a parameter lies outside the flat parameter buffer");
+    if (const int rc = check_level_block("tiny_fwd", r, P, ssb, k.ss_stride)) return rc;
     TinyBlkK& d = k.blk[b];
-    d.b1 = poff(r.b1); d.g1 = poff(r.g1); d.b2 = poff(r.b2); d.g2 = poff(r.g2); d.br = poff(r.br);
+    d.b1 = poff(P, r.b1); d.g1 = poff(P, r.g1); d.b2 = poff(P, r.b2); d.g2 = poff(P, r.g2); d.br = poff(P, r.br);
     d.ss_off = (int)(r.ss - ssb);
     d.inB = r.inB; d.u1 = r.u1; d.a1 = r.a1; d.u2 = r.u2; d.out = r.out;
   }
-  k.la = t.la; k.la_gpre = poff(t.g_pre); k.la_bo = poff(t.b_out); k.la_go = poff(t.g_out); k.la_y = t.la_y; k.la_ypre = t.la_ypre;
-  k.post = t.post_w ? 1 : 0; k.post_b = poff(t.post_b); k.post_out = t.post_out;
+  k.la = t.la; k.la_gpre = poff(P, t.g_pre); k.la_bo = poff(P, t.b_out); k.la_go = poff(P, t.g_out); k.la_y = t.la_y; k.la_ypre = t.la_ypre;
+  k.post = t.post_w ? 1 : 0; k.post_b = poff(P, t.post_b); k.post_out = t.post_out;
   k.total_steps = (int)(tiny_img_floats(t) / 64);
   const int B = a.rows / a.rows_per_sample;
   const int rpt = 64 / a.n;
@@ -912,21 +917,14 @@ int launch_tiny_fwd(const TinyFwd& t, hipStream_t s) {
   const size_t lds = (size_t)tiny_rounds(max_steps) * 4096 + 32 * 16 * 4 + (size_t)4 * tiny_stg_floats(a.n, e_in, a.C, a.blk[0].cinB) * 4;
   DQ_REQUIRE((int64_t)tiny_rounds(max_steps) * 1024 <= TINY_IMG_FLOATS, "tiny_fwd: image slot too small for the padded copy");
   DQ_REQUIRE(lds <= 96 * 1024, "tiny_fwd: weight image too large");
-  const int cs = a.blk[0].cinB;
-#define DQ_TINY(CC, NN, PP, PC, SS)                                                                                           \
-  if (a.C == CC && a.n == NN && a.pre == PP && (PP == LEVEL_PRE_NONE || a.cp == PC) && cs == SS) {                            \
-    const int nb = occ_blocks_per_cu((const void*)k_tiny_fwd<CC, NN, PP, PC, SS>, 256, lds);                                  \
-    if (nb < 0) return 1;                                                                                                     \
-    const int gx = std::max(1, std::min(nb * tiny_num_cus() / B, (tiles_ps + 3) / 4));                                        \
-    hipLaunchKernelGGL((k_tiny_fwd<CC, NN, PP, PC, SS>), dim3(gx, B), dim3(256), lds, s, k, a.params, ssb, t.img, tiles_ps);  \
-    DQ_LAUNCH_CHECK();                                                                                                        \
-    return 0;                                                                                                                 \
+  if (const auto* inst = tiny_fwd_inst(a)) {
+    const int nb = occ_blocks_per_cu((const void*)inst->fn, 256, lds);
+    if (nb < 0) return 1;
+    const int gx = std::max(1, std::min(nb * device_cus() / B, (tiles_ps + 3) / 4));
+    hipLaunchKernelGGL(inst->fn, dim3(gx, B), dim3(256), lds, s, k, a.params, ssb, t.img, tiles_ps);
+    DQ_LAUNCH_CHECK();
+    return 0;
   }
-  DQ_TINY(12, 2, LEVEL_PRE_DOWN, 12, 0)
-  DQ_TINY(16, 1, LEVEL_PRE_DOWN, 12, 0)
-  DQ_TINY(16, 1, LEVEL_PRE_NONE, 0, 16)
-  DQ_TINY(16, 2, LEVEL_PRE_UP, 16, 12)
-#undef DQ_TINY
   set_error("tiny_fwd: unsupported (C, n, stage, stage input width, skip width)");
   return 2;
 }
@@ -935,17 +933,15 @@ int launch_tiny_fwd(const TinyFwd& t, hipStream_t s) {
 static int tiny_bwd_gx(const TinyBwd& t);
 bool tiny_bwd_usable(const TinyBwd& t) {
   if (!tiny_enabled() || !tiny_bwd_enabled()) return false;
-  if (t.C != 16 || t.rows_per_sample <= 1 || !t.params || t.rows <= 0 || t.rows % t.rows_per_sample) return false;
+  if (!tiny_bwd_inst(t) || t.rows_per_sample <= 1 || !t.params || t.rows <= 0 || t.rows % t.rows_per_sample) return false;
   // one LinearAttention slot per workgroup: a layer's reservation (la_part_reserve: 1024 slots at 16 channels) must hold them -- batches
   // beyond ~1000 samples keep the per-kernel backward
   if ((int64_t)tiny_bwd_gx(t) * (t.rows / t.rows_per_sample) > 1000) return false;
-  if (t.pre == LEVEL_PRE_DOWN) return t.cp == 12 && t.cs == 0;
-  if (t.pre == LEVEL_PRE_NONE) return t.cs == 16 && !(t.dup && !t.up_w);
-  return false;
+  return !(t.pre == LEVEL_PRE_NONE && t.dup && !t.up_w);  // (the up level's d rs needs the Upsample stage)
 }
 static int tiny_bwd_gx(const TinyBwd& t) {
   const int B = t.rows / t.rows_per_sample, tiles_ps = cdiv(t.rows_per_sample, 64);
-  return std::max(1, std::min(tiny_num_cus() / std::max(1, B), (tiles_ps + 3) / 4));
+  return std::max(1, std::min(device_cus() / std::max(1, B), (tiles_ps + 3) / 4));
 }
 int tiny_bwd_slots(const TinyBwd& t) { return tiny_bwd_gx(t) * (t.rows / t.rows_per_sample); }
 int64_t tiny_bwd_img_floats(const TinyBwd& t) {
@@ -1008,18 +1004,13 @@ int launch_tiny_bwd(const TinyBwd& t, hipStream_t s) {
   const int total = (t.pre == LEVEL_PRE_DOWN ? C : 0) + C + 2 * blkt + (t.pre == LEVEL_PRE_DOWN ? 2 * C : 0) + (t.up_w ? 2 * C : 0);
   DQ_REQUIRE((int64_t)total * 64 == tiny_bwd_img_floats(t), "tiny_bwd: image layout mismatch");
   const size_t lds = (size_t)tiny_rounds(total) * 4096 + 256 * 4 + (size_t)4 * (2 * C * 65) * 4 + (size_t)(16 * 11 * C + 4 * C * C) * 4;
-#define DQ_TINYB(PP, PC, SS, UU)                                                                                              \
-  if (t.pre == PP && t.cs == SS && (t.up_w != nullptr) == UU) {                                                               \
-    const int nb = occ_blocks_per_cu((const void*)k_tiny_bwd<16, PP, PC, SS, UU>, 256, lds);                                  \
-    if (nb < 0) return 1;                                                                                                     \
-    hipLaunchKernelGGL((k_tiny_bwd<16, PP, PC, SS, UU>), dim3(gx, B), dim3(256), lds, s, k, t.params, ssb, t.img, tiles_ps);  \
-    DQ_LAUNCH_CHECK();                                                                                                        \
-    return 0;                                                                                                                 \
+  if (const auto* inst = tiny_bwd_inst(t)) {
+    const int nb = occ_blocks_per_cu((const void*)inst->fn, 256, lds);
+    if (nb < 0) return 1;
+    hipLaunchKernelGGL(inst->fn, dim3(gx, B), dim3(256), lds, s, k, t.params, ssb, t.img, tiles_ps);
+    DQ_LAUNCH_CHECK();
+    return 0;
   }
-  DQ_TINYB(LEVEL_PRE_DOWN, 12, 0, false)
-  DQ_TINYB(LEVEL_PRE_NONE, 0, 16, false)
-  DQ_TINYB(LEVEL_PRE_NONE, 0, 16, true)
-#undef DQ_TINYB
   set_error("tiny_bwd: unsupported (stage, skip width)");
   return 2;
 }
