@@ -67,6 +67,7 @@ struct Ctx {
 
 // Lays out the arena for (B, RT) and, on the first call of a plan, uploads the offset tables of the scale/shift heads
 int ensure_arena(dq_plan* plan, int B, int RT);
+int ensure_dev_tables(dq_plan* plan);  // (the tables alone)
 int unet_forward(const Ctx& c, const float* rope, const float* x, const int64_t* t, int t_scalar, const float* init_cond,
                  const float* attn_cond, float cm, float ca, const DevTables& dt, float* out, const int* step_tab = nullptr,
                  const int* step_ptr = nullptr);

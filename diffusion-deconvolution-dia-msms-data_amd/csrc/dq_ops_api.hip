@@ -134,6 +134,19 @@ int dq_prep_inputs_fwd(const float* x, const float* cond, const float* ms1, cons
   return launch_prep_inputs(x, cond, ms1, ss, 2, 0, cond_mul, cond_add, cat0, ms1n, B, RT, MZ, (hipStream_t)stream);
 }
 
+// the partial-sum slot of launch_prep_inputs_bwd: [dscale, dshift] per block, at most 32 blocks per sample
+int64_t dq_prep_inputs_bwd_scratch_floats(int B, int RT, int MZ) {
+  if (B <= 0 || RT <= 0 || MZ <= 0) return -1;
+  return (int64_t)B * 2 * std::max(1, std::min(32, cdiv((int64_t)RT * MZ, 1024)));
+}
+int dq_prep_inputs_bwd(const float* dcat0, const float* cond, float cond_mul, float cond_add, float* dss, int ss_stride, int ss_off, int B,
+                       int RT, int MZ, float* scratch, int64_t scratch_floats, void* stream) {
+  DQ_REQUIRE(dcat0 && cond && dss && scratch, "dq_prep_inputs_bwd: null argument");
+  DQ_REQUIRE(B > 0 && RT > 0 && MZ > 0, "dq_prep_inputs_bwd: B, RT and MZ must be positive");
+  DQ_REQUIRE(ss_off >= 0 && ss_stride >= ss_off + 2, "dq_prep_inputs_bwd: a sample's [scale, shift] lies inside its stride: ss_stride >= ss_off + 2");
+  return launch_prep_inputs_bwd(dcat0, cond, cond_mul, cond_add, dss, ss_stride, ss_off, B, RT, MZ, scratch, scratch_floats, (hipStream_t)stream);
+}
+
 int dq_conv_fwd(const float* x, const float* w, const float* bias, const float* norm_g, int act, float* y, int cout, int cin, int K, int mode,
                 int rows, int n_in, int n_out, void* stream) {
   DQ_REQUIRE(x && w && y && rows > 0 && n_in > 0 && n_out > 0, "dq_conv_fwd: null argument");

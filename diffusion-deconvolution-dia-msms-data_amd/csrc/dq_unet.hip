@@ -1014,6 +1014,11 @@ int unet_sample_prologue(const Ctx& c, const float* ms1, float cm, float ca, con
 // heads (the only device allocation the library ever makes; dq_plan_create itself never touches the GPU).
 int ensure_arena(dq_plan* plan, int B, int RT) {
   if (plan->arena.B != B || plan->arena.RT != RT) layout_arena(plan->plan, B, RT, plan->arena);
+  return ensure_dev_tables(plan);
+}
+
+// the offset tables alone (dq_debug_time_fwd / _bwd run the time-embedding launches without an arena)
+int ensure_dev_tables(dq_plan* plan) {
   if (!plan->dev.ss_w_off) {
     const Plan& p = plan->plan;
     std::vector<int64_t> woff(p.ss_total), boff(p.ss_total);
@@ -1156,6 +1161,24 @@ int dq_debug_wide_mid_fwd(dq_plan* plan, const float* params, const float* rope_
 int dq_debug_wide_mid_bwd(dq_plan* plan, const float* params, const float* rope_freqs, float* grads, int grad_x_mode, void* workspace,
                           int64_t workspace_bytes, int B, int RT, void* stream) {
   return debug_mid_bwd("dq_debug_wide_mid_bwd", true, plan, params, rope_freqs, grads, grad_x_mode, workspace, workspace_bytes, B, RT, stream);
+}
+
+// The time embedding alone (k_time.hip), on caller buffers: the two launchers every pass calls first (forward) and last (backward), with the
+// plan's head-offset tables.  No arena, no workspace.
+static_assert(TBUF_FLOATS == DQ_TBUF_FLOATS && DQ_TBUF_DH_PRE + 16 == DQ_TBUF_FLOATS, "the tbuf slots of include/dq_hip.h mirror k_time.hip");
+int dq_debug_time_fwd(dq_plan* plan, const float* params, const int64_t* t, int t_scalar, const int* step_tab, const int* step_ptr, float* tbuf,
+                      float* ss, int B, void* stream) {
+  DQ_REQUIRE(plan && params && tbuf, "dq_debug_time_fwd: null argument");
+  DQ_REQUIRE(B > 0, "dq_debug_time_fwd: B must be positive");
+  DQ_REQUIRE(!step_tab || step_ptr, "dq_debug_time_fwd: a step table needs the step it is read at");
+  DQ_TRY(ensure_dev_tables(plan));
+  return launch_time_embed_fwd(plan->plan, plan->dev, params, t, t_scalar, tbuf, ss, B, step_tab, step_ptr, (hipStream_t)stream);
+}
+int dq_debug_time_bwd(dq_plan* plan, const float* params, float* grads, float* tbuf, const float* dss, int B, void* stream) {
+  DQ_REQUIRE(plan && params && grads && tbuf && dss, "dq_debug_time_bwd: null argument");
+  DQ_REQUIRE(B > 0, "dq_debug_time_bwd: B must be positive");
+  DQ_TRY(ensure_dev_tables(plan));
+  return launch_time_embed_bwd(plan->plan, plan->dev, params, grads, tbuf, dss, B, (hipStream_t)stream);
 }
 
 int64_t dq_debug_tensor_offset(dq_plan* plan, const char* name) {

@@ -28,6 +28,8 @@ LEVEL_FORM_FIELDS = ("kind", "img", "la", "post_w", "in_folded", "resample")  # 
 METRIC_NAMES = ("mse", "mae", "cosine", "sa", "pearson", "scan_sa", "scan_count", "xic_r", "xic_count")  # DQ_METRIC_* (index = column of dq_recon_metrics' output)
 GEMM_PLAN_PART_FIELDS = ("tile_base", "ntiles", "splits", "k_per_split")  # of `full`, then of `rest`, after bm and kv (DQ_GEMM_PLAN_INTS)
 MID_FORMS_FIELDS = ("qkv_fused", "out_fused", "pre_fused", "wide_mid", "mid_c", "cond_dim", "prep_ok", "ss_mid1", "ss_mid2", "ss_total")  # DQ_MID_FORMS_INTS, in dq_debug_mid_forms' order
+TBUF_FLOATS = 100  # DQ_TBUF_FLOATS: a sample's scratch of the time-embedding kernels (dq_debug_time_fwd / _bwd)
+TBUF_SLOTS = {"sinu": 0, "h_pre": 4, "h_act": 20, "temb": 36, "silu": 52, "dtemb": 68, "dh_pre": 84}  # DQ_TBUF_* (tests/test_time_embed.py reads the header)
 LEVEL_PLAN_FLAGS = ("prep_ok", "init_fused", "head_shape", "head_train", "use_tb_up", "use_tb_dn", "tb_up_w")  # DQ_LEVEL_PLAN_FLAG_INTS
 
 # name -> (restype, argtypes); this table is checked against include/dq_hip.h by tests/test_abi.py
@@ -196,6 +198,10 @@ PROTOTYPES = {
     "dq_ms1_feat_wgrad_scratch_floats": (c_int64, [c_int, c_int, c_int]),
     "dq_ms1_feat_wgrad": (c_int, [c_void_p] * 5 + [c_int64, c_int, c_int, c_int, c_void_p]),
     "dq_prep_inputs_fwd": (c_int, [c_void_p] * 4 + [c_float, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "dq_prep_inputs_bwd_scratch_floats": (c_int64, [c_int, c_int, c_int]),
+    "dq_prep_inputs_bwd": (c_int, [c_void_p, c_void_p, c_float, c_float, c_void_p] + [c_int] * 5 + [c_void_p, c_int64, c_void_p]),
+    "dq_debug_time_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_void_p]),
+    "dq_debug_time_bwd": (c_int, [c_void_p] * 5 + [c_int, c_void_p]),
     "dq_conv_fwd": (c_int, [c_void_p] * 4 + [c_int, c_void_p] + [c_int] * 7 + [c_void_p]),
     "dq_conv_bwd_workspace_floats": (c_int64, [c_int] * 9),
     "dq_conv_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 9 + [c_void_p, c_int64, c_void_p]),

@@ -61,7 +61,8 @@ const char* dq_last_error(void);
  * dq_ddim_step_v, dq_solver_step_v, dq_guided_update_v, dq_ddim_sample_v, dq_mse_loss_v_fwd_bwd, dq_mse_per_window_v; whole
  * chromatograms: dq_run_window_count, dq_run_windows_scratch_bytes, dq_run_windows, dq_run_stitch; per-window sampler control:
  * dq_sample_stat_scratch_bytes, dq_window_rescale, dq_window_abs_quantile, dq_step_update_adaptive, dq_ddim_sample_adaptive; joint
- * sampling of a window's precursors: DQ_CONSIST_*, dq_group_project, dq_ddim_sample_joint). */
+ * sampling of a window's precursors: DQ_CONSIST_*, dq_group_project, dq_ddim_sample_joint; the time embedding and the input affine alone:
+ * DQ_TBUF_*, dq_debug_time_fwd, dq_debug_time_bwd, dq_prep_inputs_bwd, dq_prep_inputs_bwd_scratch_floats). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -860,6 +861,13 @@ int dq_ms1_feat_wgrad(const float* ms1n, const float* du, float* dw, float* dbia
  * shift_b , x ], ms1n (B, RT) = ms1*cond_mul+cond_add; ss (B, 2) = [scale, shift] per sample. */
 int dq_prep_inputs_fwd(const float* x, const float* cond, const float* ms1, const float* ss, float cond_mul, float cond_add, float* cat0,
                        float* ms1n, int B, int RT, int MZ, void* stream);
+/* Its backward for the per-sample [scale, shift] (k_prep_inputs_bwd + the ordered sum of its per-block partials): from dcat0 (B*RT, 2, MZ),
+ * of which channel 0 is read, and the RAW cond (B, RT, MZ):  dss[b * ss_stride + ss_off] += sum d * (cond*cond_mul+cond_add),
+ * dss[b * ss_stride + ss_off + 1] += sum d, the sums over sample b's RT * MZ elements in a fixed order (bitwise repeatable).  ss_stride >=
+ * ss_off + 2.  scratch: dq_prep_inputs_bwd_scratch_floats(B, RT, MZ) floats (-1 for arguments out of range). */
+int64_t dq_prep_inputs_bwd_scratch_floats(int B, int RT, int MZ);
+int dq_prep_inputs_bwd(const float* dcat0, const float* cond, float cond_mul, float cond_add, float* dss, int ss_stride, int ss_off, int B,
+                       int RT, int MZ, float* scratch, int64_t scratch_floats, void* stream);
 /* Conv1d (+ optional fused RMSNorm with gain norm_g, + optional activation) on (rows, cin, n_in) -> (rows, cout, n_out):
  * mode 0 = stride 1 'same' (K in {1,3,7}), 1 = Downsample k4 s2 p1 (unet1d.py:99-110), 2 = Upsample nearest x2 then k3 p1
  * (:82-96).  act: 0 none, 1 SiLU, 2 GELU.  bias / norm_g nullable. */
@@ -1015,6 +1023,23 @@ int dq_debug_wide_mid_fwd(dq_plan* plan, const float* params, const float* rope_
                           int64_t workspace_bytes, int B, int RT, void* stream);
 int dq_debug_wide_mid_bwd(dq_plan* plan, const float* params, const float* rope_freqs, float* grads, int grad_x_mode, void* workspace,
                           int64_t workspace_bytes, int B, int RT, void* stream);
+
+/* Test hooks: the time embedding alone (k_time.hip), through the two launchers every pass calls first and last, on caller buffers.  Both
+ * upload the plan's head-offset tables on first use, as the first pass on a plan does; neither needs a workspace.
+ *
+ * tbuf: B x DQ_TBUF_FLOATS floats, per sample the slots DQ_TBUF_* below (16 floats each but the `dim` sinusoidal features).  ss: B x ss_total
+ * (dq_debug_mid_forms), row r of a sample = the r-th SiLU -> Linear(16, .) output in the plan's parameter order.
+ *
+ * dq_debug_time_fwd: the timestep of sample b is t[b] (B int64 on the device), or with t = NULL step_tab[*step_ptr] (both on the device, as
+ * a captured sampling graph reads it), or with both NULL t_scalar.  Fills the forward slots of tbuf and, unless ss = NULL, every head row.
+ *
+ * dq_debug_time_bwd: behind it, from dss (B x ss_total): tbuf gains d temb and d h_pre; grads (the flat layout) receives += of every head's
+ * weight and bias and of time_mlp.{1,3}.*. */
+enum { DQ_TBUF_FLOATS = 100, DQ_TBUF_SINU = 0, DQ_TBUF_H_PRE = 4, DQ_TBUF_H_ACT = 20, DQ_TBUF_TEMB = 36, DQ_TBUF_SILU = 52, DQ_TBUF_DTEMB = 68,
+       DQ_TBUF_DH_PRE = 84 };
+int dq_debug_time_fwd(dq_plan* plan, const float* params, const int64_t* t, int t_scalar, const int* step_tab, const int* step_ptr, float* tbuf,
+                      float* ss, int B, void* stream);
+int dq_debug_time_bwd(dq_plan* plan, const float* params, float* grads, float* tbuf, const float* dss, int B, void* stream);
 
 /* Test hook: which launch takes each U-Net level in a pass over (B, RT) windows -- the plan unet_forward / unet_backward / the sampler's
  * prologue build for themselves (the same rules, evaluated by the same function), without a workspace, a launch or a device.

@@ -2,7 +2,9 @@
 captured from the REFERENCE's own modules (tests/golden/blocks.npz: RMSNorm with the eps-clamp column, SinusoidalPosEmb + time_mlp,
 ConditionalScaleShift, ResnetBlock with / without res_conv, Downsample / Upsample) go straight into the HIP kernels; the
 backward of the ResnetBlock and the bottleneck attention (RT = 400 / 2000 and ragged tails) are checked against the oracle's
-autograd; RoPE (parity unpinned: third-party rotary_embedding_torch) gets property tests."""
+autograd; RoPE (parity unpinned: third-party rotary_embedding_torch) gets property tests.  The time embedding and the
+input affine here are the reference's fixture alone (forward, one shape); their heads, backward and loop edges against float64:
+tests/test_time_embed.py."""
 import numpy as np
 import pytest
 import torch
