@@ -20,6 +20,7 @@
 // present components of an element are in flight together.
 // HBM-bound; algorithmic bytes per window: read count windows + write ms2_target, ms2_cond (and ms2_rest) = (count + 2 or 3) * RT*MZ*4 B
 // (+ MS1 rows); the second read of the components in (2) comes from L2 / Infinity Cache.  No LDS beyond the block reduce, no atomics.
+// dq_mix_group_batch (below) is the same rule for groups: one mixture, P targets, member-major outputs.
 #include "dq_common.h"
 #include "dq_kernels.h"
 #include "dq_philox.h"
@@ -247,9 +248,207 @@ __global__ void __launch_bounds__(256) k_mix(const float* __restrict__ ms2, cons
                               t4, c4, r4});
 }
 
+// ---- groups: one mixture of count[g] components whose first P are the MEMBERS that joint sampling asks for.  The same
+// rule as above for lo / hi, the weights and ms2_cond; every member gets its own target n_p (or n_p w_p), its own MS1 under its own MS1
+// lo / hi, and a copy of the mixture; ms2_rest is what no member explains.  Outputs are member-major: member p of group g is row p * G + g.
+// A group's count must lie in [P, K].  part: G * (MIX_CHUNKS + P) * 2 floats ((min, max) per chunk, then one pair per member's MS1).
+
+__device__ __forceinline__ int mix_group_indices(const int64_t* __restrict__ idx, const int32_t* __restrict__ count_p, int64_t n_windows,
+                                                 int G, int K, int P, int g, MixIdx& ix) {
+  const int count = mix_window_indices(idx, count_p, n_windows, G, K, g, ix);
+  return count >= P ? count : 0;
+}
+
+__global__ void __launch_bounds__(256) k_mix_group_minmax(const float* __restrict__ ms2, const float* __restrict__ ms1,
+                                                          const int64_t* __restrict__ idx, const int32_t* __restrict__ count_p,
+                                                          int64_t n_windows, int G, int K, int P, int64_t per4, int64_t ms1_per,
+                                                          MixWeights fixed, int drawn, uint32_t E, const uint64_t* __restrict__ seed_p,
+                                                          const int64_t* __restrict__ ids, uint32_t draw, float* __restrict__ part,
+                                                          float* __restrict__ wout) {
+  const int g = blockIdx.y, c = blockIdx.x;
+  MixIdx ix;
+  const int count = mix_group_indices(idx, count_p, n_windows, G, K, P, g, ix);
+  float* pg = part + (int64_t)g * (MIX_CHUNKS + P) * 2;
+  float* pp = pg + c * 2;
+  if (count == 0) {  // never read out of bounds: poison the group instead
+    if (threadIdx.x == 0) {
+      pp[0] = pp[1] = NAN;
+      if (c == 0) {
+        for (int p = 0; p < P; ++p) pg[2 * (MIX_CHUNKS + p)] = pg[2 * (MIX_CHUNKS + p) + 1] = NAN;
+        for (int j = 0; j < K; ++j) wout[(int64_t)g * K + j] = NAN;
+      }
+    }
+    return;
+  }
+  float mn = INFINITY, mx = -INFINITY;
+  mix_dispatch(count, MixMinMaxBody{reinterpret_cast<const float4*>(ms2), ix, per4, per4 * c / MIX_CHUNKS, per4 * (c + 1) / MIX_CHUNKS, mn, mx});
+  __shared__ float red[2][4];
+  mn = mix_wave_min(mn); mx = mix_wave_max(mx);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = mn; red[1][threadIdx.x >> 6] = mx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    pp[0] = fminf(fminf(red[0][0], red[0][1]), fminf(red[0][2], red[0][3]));
+    pp[1] = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+  }
+  if (c != 0) return;
+  // the group's weights, once: k_mix_minmax's, keyed by the group's id
+  if (threadIdx.x == 0) {
+    float a[MIX_MAX_K];
+    float* wb = wout + (int64_t)g * K;
+    if (drawn) {
+      const uint64_t seed = seed_p[0];
+      const int64_t id = ids ? ids[g] : (int64_t)g;
+      float s = 0.0f;
+      for (int j = 0; j < count; ++j) {
+        a[j] = mix_abundance(seed, id, draw, (uint32_t)j, E);
+        s = j == 0 ? a[0] : s + a[j];
+      }
+      for (int j = 0; j < K; ++j) wb[j] = j < count ? a[j] / s : 0.0f;
+    } else {
+      for (int j = 0; j < K; ++j) wb[j] = j < count ? fixed.w[j] : 0.0f;
+    }
+  }
+  // MS1 of every member, each under its own lo / hi
+  for (int p = 0; p < P; ++p) {
+    __syncthreads();
+    const float* m = ms1 + idx[(int64_t)p * G + g] * ms1_per;  // (checked above; ix[p] with a run-time p would make ix an indexed array)
+    mn = INFINITY; mx = -INFINITY;
+    for (int64_t i = threadIdx.x; i < ms1_per; i += blockDim.x) { mn = fminf(mn, m[i]); mx = fmaxf(mx, m[i]); }
+    mn = mix_wave_min(mn); mx = mix_wave_max(mx);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = mn; red[1][threadIdx.x >> 6] = mx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      pg[2 * (MIX_CHUNKS + p)] = fminf(fminf(red[0][0], red[0][1]), fminf(red[0][2], red[0][3]));
+      pg[2 * (MIX_CHUNKS + p) + 1] = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+    }
+  }
+}
+
+struct MixGroupBody {
+  const float4* base;
+  MixIdx ix;
+  const float* wb;  // this group's row of weights_out
+  float lo, rng;
+  int64_t per4, first, stride, member;  // member: the float4 between two members of a group, G * per4
+  int P, scale_target;
+  float4 *o_target, *o_cond, *o_rest;  // member 0's slice of this group; o_rest (nullable) the group's
+  template <int C>
+  __device__ __forceinline__ void operator()() const {
+    float w[C];
+#pragma unroll
+    for (int j = 0; j < C; ++j) w[j] = wb[j];
+    for (int64_t e = first; e < per4; e += stride) {
+      float4 v[C];
+#pragma unroll
+      for (int j = 0; j < C; ++j) v[j] = base[ix[j] * per4 + e];
+      float4 cond = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rest = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+      for (int j = 0; j < C; ++j) {
+        const float4 n = mix_norm4(v[j], lo, rng);
+        const float4 p = mul4(n, w[j]);
+        cond = j == 0 ? p : add4(cond, p);
+        if (j < P) {  // (P is uniform over the block: a scalar branch around one store)
+          o_target[j * member + e] = make_float4(scale_target ? p.x : n.x, scale_target ? p.y : n.y, scale_target ? p.z : n.z,
+                                                 scale_target ? p.w : n.w);
+        } else if (j == P) {
+          rest = p;
+        } else {
+          rest = add4(rest, p);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < C; ++j)
+        if (j < P) o_cond[j * member + e] = cond;
+      if (o_rest) o_rest[e] = rest;
+    }
+  }
+};
+
+__global__ void __launch_bounds__(256) k_mix_group(const float* __restrict__ ms2, const float* __restrict__ ms1,
+                                                   const int64_t* __restrict__ idx, const int32_t* __restrict__ count_p, int64_t n_windows,
+                                                   int G, int K, int P, int64_t per4, int64_t ms1_per, const float* __restrict__ part,
+                                                   const float* __restrict__ wout, int scale_target, float* __restrict__ o_target,
+                                                   float* __restrict__ o_ms1, float* __restrict__ o_cond, float* __restrict__ o_rest) {
+  const int g = blockIdx.y;
+  const int64_t first = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  MixIdx ix;
+  const int count = mix_group_indices(idx, count_p, n_windows, G, K, P, g, ix);
+  const int64_t member = (int64_t)G * per4;
+  float4* t4 = reinterpret_cast<float4*>(o_target) + (int64_t)g * per4;
+  float4* c4 = reinterpret_cast<float4*>(o_cond) + (int64_t)g * per4;
+  float4* r4 = o_rest ? reinterpret_cast<float4*>(o_rest) + (int64_t)g * per4 : nullptr;
+  float* m1 = o_ms1 + (int64_t)g * ms1_per;
+  if (count == 0) {
+    const float4 nan4 = make_float4(NAN, NAN, NAN, NAN);
+    for (int64_t e = first; e < per4; e += stride) {
+      for (int p = 0; p < P; ++p) {
+        t4[p * member + e] = nan4;
+        c4[p * member + e] = nan4;
+      }
+      if (r4) r4[e] = nan4;
+    }
+    for (int p = 0; p < P; ++p)
+      for (int64_t e = first; e < ms1_per; e += stride) m1[(int64_t)p * G * ms1_per + e] = NAN;
+    return;
+  }
+  const float* pg = part + (int64_t)g * (MIX_CHUNKS + P) * 2;
+  float lo = pg[0], hi = pg[1];
+#pragma unroll
+  for (int c = 1; c < MIX_CHUNKS; ++c) { lo = fminf(lo, pg[2 * c]); hi = fmaxf(hi, pg[2 * c + 1]); }
+  for (int p = 0; p < P; ++p) {
+    const float lo1 = pg[2 * (MIX_CHUNKS + p)], rng1 = pg[2 * (MIX_CHUNKS + p) + 1] - lo1;
+    const float* src = ms1 + idx[(int64_t)p * G + g] * ms1_per;
+    float* dst = m1 + (int64_t)p * G * ms1_per;
+    for (int64_t e = first; e < ms1_per; e += stride) dst[e] = (src[e] - lo1) / rng1;
+  }
+  mix_dispatch(count, MixGroupBody{reinterpret_cast<const float4*>(ms2), ix, wout + (int64_t)g * K, lo, hi - lo, per4, first, stride, member, P,
+                                   scale_target, t4, c4, r4});
+}
+
 }  // namespace dq
 
 extern "C" {
+
+int64_t dq_mix_group_batch_scratch_bytes(int G, int K, int P) {
+  if (G <= 0 || G > 65535 || K < 2 || K > dq::MIX_MAX_K || P < 1 || P > K) return 0;
+  return (int64_t)G * (dq::MIX_CHUNKS + P) * 2 * (int64_t)sizeof(float);
+}
+
+int dq_mix_group_batch(const float* ms2_data, const float* ms1_data, int64_t n_windows, const int64_t* idx_dev, const int32_t* count_dev,
+                       int G, int K, int P, int RT, int MZ, int64_t ms1_per_window, const float* weights_host, int max_ratio_log2,
+                       const uint64_t* seed_dev, const int64_t* window_ids_dev, int draw, int scale_target, float* ms2_target,
+                       float* ms1_target, float* ms2_cond, float* ms2_rest, float* weights_out, void* scratch, int64_t scratch_bytes,
+                       void* stream) {
+  using namespace dq;
+  DQ_REQUIRE(ms2_data && ms1_data && idx_dev && ms2_target && ms1_target && ms2_cond && weights_out && scratch,
+             "dq_mix_group_batch: null argument");
+  DQ_REQUIRE(K >= 2 && K <= MIX_MAX_K, "dq_mix_group_batch: K must be 2..8 components");
+  DQ_REQUIRE(P >= 1 && P <= K, "dq_mix_group_batch: group_size must be 1..K members");
+  DQ_REQUIRE(max_ratio_log2 >= 0 && max_ratio_log2 <= 16, "dq_mix_group_batch: max_ratio_log2 must be 0..16");
+  DQ_REQUIRE(draw >= 0, "dq_mix_group_batch: the draw index must be >= 0");
+  DQ_REQUIRE(G >= 1 && G <= 65535, "dq_mix_group_batch: 1..65535 groups per call");
+  DQ_REQUIRE(RT > 0 && MZ > 0 && ms1_per_window > 0 && n_windows > 0, "dq_mix_group_batch: sizes must be positive");
+  const int64_t per = (int64_t)RT * MZ;
+  DQ_REQUIRE(per % 4 == 0, "dq_mix_group_batch: RT*MZ must be a multiple of 4");
+  DQ_REQUIRE(weights_host || seed_dev, "dq_mix_group_batch: drawn weights need the seed (seed_dev)");
+  DQ_REQUIRE(scratch_bytes >= dq_mix_group_batch_scratch_bytes(G, K, P),
+             "dq_mix_group_batch: scratch too small (dq_mix_group_batch_scratch_bytes)");
+  hipStream_t s = (hipStream_t)stream;
+  float* part = reinterpret_cast<float*>(scratch);
+  MixWeights fixed{};
+  if (weights_host)
+    for (int j = 0; j < K; ++j) fixed.w[j] = weights_host[j];
+  hipLaunchKernelGGL(k_mix_group_minmax, dim3(MIX_CHUNKS, G), dim3(256), 0, s, ms2_data, ms1_data, idx_dev, count_dev, n_windows, G, K, P,
+                     per / 4, ms1_per_window, fixed, weights_host ? 0 : 1, (uint32_t)max_ratio_log2, seed_dev, window_ids_dev, (uint32_t)draw,
+                     part, weights_out);
+  DQ_LAUNCH_CHECK();
+  // k_mix's grid: a block's group is blockIdx.y; the members' MS1 rows ride in the same blocks as the group's per / 4 float4
+  const int gx = (int)std::min<int64_t>(cdiv(std::max(per / 4, ms1_per_window), 256), MIX_MAX_BLOCKS_X);
+  hipLaunchKernelGGL(k_mix_group, dim3(gx, G), dim3(256), 0, s, ms2_data, ms1_data, idx_dev, count_dev, n_windows, G, K, P, per / 4,
+                     ms1_per_window, part, weights_out, scale_target, ms2_target, ms1_target, ms2_cond, ms2_rest);
+  DQ_LAUNCH_CHECK();
+  return 0;
+}
 
 // (the partials do not depend on K: the weights live in weights_out.  K is part of the signature so that a form that needs it can ask.)
 int64_t dq_mix_batch_scratch_bytes(int B, int K) {

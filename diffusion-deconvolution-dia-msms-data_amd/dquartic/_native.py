@@ -25,6 +25,7 @@ CONV_BWD_DATA_FORMS = ("wg", "gemm", "plain")  # DQ_CONV_BWD_DATA_*
 CONV_WGRAD_FORMS = ("wg", "v4", "scalar")  # DQ_CONV_WGRAD_*
 LEVEL_KINDS = ("unfused", "kernel", "tiny")  # DQ_LEVEL_* (index = value)
 LEVEL_FORM_FIELDS = ("kind", "img", "la", "post_w", "in_folded", "resample")  # DQ_LEVEL_PLAN_FORM_INTS, in the order dq_debug_level_plan writes them
+GROUP_METRIC_NAMES = ("excess", "unexplained", "mix_total")  # DQ_GROUP_* (index = column of dq_group_metrics' `group` output)
 METRIC_NAMES = ("mse", "mae", "cosine", "sa", "pearson", "scan_sa", "scan_count", "xic_r", "xic_count")  # DQ_METRIC_* (index = column of dq_recon_metrics' output)
 GEMM_PLAN_PART_FIELDS = ("tile_base", "ntiles", "splits", "k_per_split")  # of `full`, then of `rest`, after bm and kv (DQ_GEMM_PLAN_INTS)
 MID_FORMS_FIELDS = ("qkv_fused", "out_fused", "pre_fused", "wide_mid", "mid_c", "cond_dim", "prep_ok", "ss_mid1", "ss_mid2", "ss_total")  # DQ_MID_FORMS_INTS, in dq_debug_mid_forms' order
@@ -127,6 +128,11 @@ PROTOTYPES = {
     "dq_mix_batch_scratch_bytes": (c_int64, [c_int, c_int]),
     "dq_mix_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, POINTER(c_float), c_int,
                              c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int64, c_void_p]),
+    "dq_mix_group_batch_scratch_bytes": (c_int64, [c_int, c_int, c_int]),
+    "dq_mix_group_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, POINTER(c_float),
+                                   c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int64, c_void_p]),
+    "dq_group_metrics_scratch_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "dq_group_metrics": (c_int, [c_void_p] * 6 + [c_int64, c_int, c_int, c_int, c_int, c_void_p]),
     "dq_run_window_count": (c_int64, [c_int, c_int, c_int]),
     "dq_run_windows_scratch_bytes": (c_int64, [c_int]),
     "dq_run_windows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_int] + [c_void_p] * 4 + [c_int64, c_void_p]),

@@ -3,7 +3,8 @@
 --threads]`` and ``dquartic generate-config PATH``; ``dquartic evaluate CONFIG --checkpoint PATH`` (this build) prints held-out loss and
 reconstruction metrics; ``dquartic deconvolve CONFIG --checkpoint PATH --ms2 RUN.npy --ms1 RUN.npy --out OUT.npz --window W`` (this build)
 deconvolves whole chromatograms (``--joint``: the P precursors of one run as groups under mixture consistency,
-section 40).  A ``data.mixture`` block in the config (absent by default) makes ``train`` and ``evaluate`` form K-component
+section 40); ``dquartic evaluate-joint CONFIG --checkpoint PATH --num-steps N --group-size P`` (this build) scores joint sampling on
+held-out groups against P independent calls (section 45).  A ``data.mixture`` block in the config (absent by default) makes ``train`` and ``evaluate`` form K-component
 mixtures with drawn weights on the GPU (``ResidentMixLoader``).  ``generate-train-data`` (offline sqMass ETL) is outside the hot path
 and reports so.  Under ``torch.distributed.run`` (WORLD_SIZE > 1) training is data-parallel: one process per GPU, the
 dataset is sharded by rank and the flat gradient is all-reduced over RCCL."""
@@ -290,6 +291,79 @@ def evaluate(config_path, checkpoint, num_steps, eta, seed, sample_kw, use_ema, 
     if out_path is not None:
         with open(out_path, "w") as f:
             json.dump({**res, **arrays}, f)
+
+
+def build_group_loader(val, m, groups_per_batch, group_size, rank=0, world=1):
+    """The held-out loader of ``evaluate-joint``: ``build_validation_loader``'s frozen mixtures of a completed ``data.validation`` block,
+    served as groups whose first ``group_size`` components are the members (``ResidentGroupLoader``; group k is item k of the loader
+    ``evaluate`` scores)."""
+    from .utils.data_loader import ResidentGroupLoader
+
+    dataset = build_dataset(val, m, rank, world)
+    return ResidentGroupLoader(dataset, groups_per_batch, group_size, frozen_items=len(dataset) if val["n_pairs"] is None else val["n_pairs"],
+                               device=torch.device("cuda", torch.cuda.current_device()), **val["mixture"])
+
+
+@cli.command("evaluate-joint")
+@click.argument("config-path", type=click.Path(exists=True), required=True)
+@click.option("--checkpoint", required=True, type=click.Path(exists=True), help="Checkpoint written by train (model_state_dict; its EMA when it has one)")
+@click.option("--num-steps", required=True, type=int, help="Sampling steps per member")
+@click.option("--group-size", required=True, type=int, help="Members P of a group: the first P components of every held-out mixture (1 .. kmin)")
+@sampling_options
+@click.option("--independent/--no-independent", default=True, help="Also sample every group without consistency (P independent calls) and score it")
+@click.option("--use-ema/--no-use-ema", default=None, help="Evaluate the averaged weights (default: when the checkpoint has an average)")
+@click.option("--max-batches", default=None, type=int, help="Stop after this many batches")
+@click.option("--out", "out_path", default=None, type=click.Path(), help="Write the full result, the per-member and per-group arrays included, as JSON")
+def evaluate_joint(config_path, checkpoint, num_steps, eta, seed, sample_kw, independent, use_ema, max_batches, out_path):
+    """Score joint sampling (sample(group_size=P, consistency=...); deconvolve --joint) on the mixtures of the config's data.validation
+    block: every mixture's first P components are sampled as one group under --consistency (default: bound) and, unless
+    --no-independent, as P independent calls.  Reports the window metrics over all members, how far the members together exceed (excess)
+    or miss (unexplained) the mixture, and how often a member's prediction looks most like its own target (id_acc; leak: how much it
+    looks like another member's).  This is the route for --consistency inside an evaluation; `evaluate` scores one target per mixture.
+    Prints one JSON line."""
+    from .model.model import _JOINT_WITH_OPTIONS
+
+    group_size = sample_kw.pop("group_size")  # (--group-size is one of JointSampleOptions' names: sampling_options hands it over in sample_kw)
+    refused = [k for k in ("guidance_scale", "guidance_rescale", "threshold_quantile", "threshold_max") if k in sample_kw]
+    if refused:
+        raise click.ClickException(_JOINT_WITH_OPTIONS)
+    config = load_train_config(config_path)
+    m = config["model"]
+    val = validation_config(config)
+    if val is None or val.get("mixture") is None:
+        raise click.ClickException("evaluate-joint needs a data.validation block with a mixture (data.mixture or data.validation.mixture): "
+                                   "groups are the first --group-size components of its mixtures")
+    kmin = int(val["mixture"]["n_components"][0])
+    if not 1 <= group_size <= kmin:
+        raise click.ClickException(f"--group-size {group_size}: the validation mixtures hold kmin = {kmin} .. {int(val['mixture']['n_components'][1])} "
+                                   f"components (mixture.n_components); every group needs its members, so 1 <= --group-size <= kmin")
+    if m["use_model"] != "UNet1d":
+        raise click.ClickException("evaluate-joint: groups are built for UNet1d (dq_ddim_sample_joint); other networks are not implemented")
+    sample_kw.setdefault("consistency", "bound")
+    if not torch.cuda.is_available():
+        raise click.ClickException("no GPU visible: this build runs the hot path on MI355X only (no CPU fallback)")
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(device)
+    loader = build_group_loader(val, m, max(1, int(m["batch_size"])), group_size)
+    dm = build_model(m, device)
+    load_inference_checkpoint(dm, m, checkpoint, device, use_ema)
+    try:
+        res = dm.evaluate_joint(loader, num_steps, independent=independent, eta=eta, seed=seed, use_ema=use_ema, max_batches=max_batches, **sample_kw)
+    except (NotImplementedError, ValueError) as e:  # what sample refuses, in its own words
+        raise click.ClickException(str(e))
+    # the arrays go to --out only; the printed line keeps the scalars and the buckets
+    arrays = {"member_weight": res.pop("member_weight").tolist()}
+    for leg in ("joint", "independent"):
+        if leg in res:
+            arrays[leg] = {k: res[leg].pop(k).tolist() for k in ("per_window", "cross", "group")}
+    click.echo(json.dumps(res))
+    if out_path is not None:
+        full = {**res, "member_weight": arrays["member_weight"]}
+        for leg in ("joint", "independent"):
+            if leg in res:
+                full[leg] = {**res[leg], **arrays[leg]}
+        with open(out_path, "w") as f:
+            json.dump(full, f)
 
 
 @cli.command()

@@ -90,3 +90,61 @@ def recon_metrics(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     out = torch.empty((B, len(N.METRIC_NAMES)), dtype=torch.float32, device=p.device)
     N.check(N.lib().dq_recon_metrics(N.ptr(p), N.ptr(t), N.ptr(out), N.ptr(scratch), nbytes, B, RT, MZ, N.stream_ptr()), "dq_recon_metrics")
     return out
+
+
+# ---- groups: what the P predictions of a group do together
+def group_metrics(pred: torch.Tensor, target: torch.Tensor, mix: torch.Tensor, group_size: int):
+    """``dq_group_metrics``: ``(cross (G, P, P), group (G, 3))`` float32 device tensors for ``pred`` / ``target`` ``(P*G, RT, MZ)``,
+    member-major, and ``mix`` with at least G rows, of which rows 0 .. G-1 are read (a joint batch's ``ms2_cond`` as it is).  ``cross[g, p,
+    q]`` is the cosine of member p's prediction against member q's target; ``group`` holds ``_native.GROUP_METRIC_NAMES``."""
+    P = int(group_size)
+    if pred.shape != target.shape or pred.dim() != 3 or P < 1 or pred.shape[0] % P:
+        raise ValueError(f"group_metrics: pred and target must both be (P*G, RT, MZ) with P = {group_size}, got {tuple(pred.shape)} and "
+                         f"{tuple(target.shape)}")
+    G, RT, MZ = pred.shape[0] // P, pred.shape[1], pred.shape[2]
+    if mix.dim() != 3 or mix.shape[0] < G or tuple(mix.shape[1:]) != (RT, MZ):
+        raise ValueError(f"group_metrics: mix must be (>= {G}, {RT}, {MZ}), got {tuple(mix.shape)}")
+    if not pred.is_cuda:
+        raise NotImplementedError("group_metrics runs in the native library only (device tensors)")
+    conv = lambda a: a.detach().to(device=pred.device, dtype=torch.float32).contiguous()
+    p, t, m = conv(pred), conv(target), conv(mix)
+    nbytes = N.lib().dq_group_metrics_scratch_bytes(G, P, RT, MZ)
+    if nbytes < 0:
+        raise ValueError(f"group_metrics: group_size must be 1..{N.GROUP_MAX} and the sizes positive, got P = {P}, (G, RT, MZ) = {(G, RT, MZ)}")
+    scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=p.device)
+    cross = torch.empty((G, P, P), dtype=torch.float32, device=p.device)
+    group = torch.empty((G, len(N.GROUP_METRIC_NAMES)), dtype=torch.float32, device=p.device)
+    N.check(N.lib().dq_group_metrics(N.ptr(p), N.ptr(t), N.ptr(m), N.ptr(cross), N.ptr(group), N.ptr(scratch), nbytes, G, P, RT, MZ,
+                                     N.stream_ptr()), "dq_group_metrics")
+    return cross, group
+
+
+def identification(cross) -> dict:
+    """From a ``(groups, P, P)`` array of ``dq_group_metrics``' ``cross``: ``id_acc``, the share of members p whose prediction looks most
+    like their own target, ``argmax_q cross[p, q] == p`` with ties going to the lowest q (over groups of one it is 1), and -- for P > 1 --
+    ``leak``, the mean over the members of ``max_{q != p} cross[p, q]``: how much a member's prediction looks like another member's
+    target.  float64."""
+    c = np.asarray(cross, dtype=np.float64)
+    if c.ndim != 3 or c.shape[1] != c.shape[2] or c.shape[0] < 1 or c.shape[1] < 1:
+        raise ValueError(f"identification: need a (groups >= 1, P, P) array, got shape {c.shape}")
+    P = c.shape[1]
+    out = {"id_acc": float((np.argmax(c, axis=2) == np.arange(P)[None, :]).mean())}  # (numpy's argmax returns the first maximum)
+    if P > 1:
+        off = np.where(np.eye(P, dtype=bool)[None], -np.inf, c)
+        out["leak"] = float(off.max(axis=2).mean())
+    return out
+
+
+def aggregate_joint(per_window, cross, group, member_weight) -> dict:
+    """The scalars of one leg of ``evaluate_joint``: the nine window metrics over all members (``aggregate_metrics``), the means of
+    ``excess`` and ``unexplained`` over the groups, ``id_acc`` / ``leak`` (``identification``) and ``sa_by_weight``, the spectral angle by
+    the members' own share w_p of their mixture (``by_target_weight``'s buckets).  ``per_window`` (n, 9), ``cross`` (groups, P, P),
+    ``group`` (groups, 3), ``member_weight`` (n,), all in the same member-major order."""
+    pw, g = np.asarray(per_window, dtype=np.float64), np.asarray(group, dtype=np.float64)
+    out = aggregate_metrics(pw)
+    out["excess"] = float(g[:, N.GROUP_METRIC_NAMES.index("excess")].mean())
+    out["unexplained"] = float(g[:, N.GROUP_METRIC_NAMES.index("unexplained")].mean())
+    out.update(identification(cross))
+    by = by_target_weight(member_weight, pw[:, N.METRIC_NAMES.index("mse")], pw)
+    out["sa_by_weight"] = {"edges": by["edges"], "sa": by["sa"], "n": by["n"]}
+    return out

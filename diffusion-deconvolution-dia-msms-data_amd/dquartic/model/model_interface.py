@@ -811,6 +811,80 @@ class ModelInterface(object):
             out["val_loss_by_weight"] = E.by_target_weight(tw, mse.mean(axis=0), None if num_steps is None else out["per_window"])
         return out
 
+    def evaluate_joint(self, loader, num_steps, consistency="bound", consistency_strength=1.0, independent=True, eta=0.0, seed=0,
+                       sampler="reference", clip_x0=None, use_ema=None, max_batches=None):
+        """Held-out evaluation of joint sampling: does sampling the P precursors of a mixture as one group under
+        ``consistency`` beat P independent calls?  ``loader`` yields ``GroupBatch``es (``ResidentGroupLoader``: member-major, group size
+        P, ``n_groups`` groups per pass).  Per batch of G groups there is one ``sample(None, ..., group_size=P, consistency=consistency,
+        consistency_strength=consistency_strength, window_ids=ids)`` call and, with ``independent``, a second one with
+        ``consistency=None`` on the same batch and ids -- bit for bit P plain calls.  Member p of running group k samples under the id
+        ``p * n_groups + k`` (``joint_window_ids`` with ``n_windows = loader.n_groups``), so member 0 has the id ``evaluate`` gives the
+        same window of a ``ResidentMixLoader`` with the same arguments.  Each result goes through ``dq_recon_metrics`` against the
+        members' targets and ``dq_group_metrics`` against the targets and the mixture.
+
+        Returns a dict with ``"joint"`` and, with ``independent``, ``"independent"``, each holding the nine window metrics over all members
+        (``aggregate_metrics``), the means of ``excess`` and ``unexplained``, ``id_acc``, ``leak`` (absent for P = 1) and ``sa_by_weight``
+        (``evaluation.aggregate_joint``), and the arrays ``per_window`` ``(P * n, 9)``, ``cross`` ``(n, P, P)`` and ``group`` ``(n, 3)`` over
+        the n groups seen; ``per_window`` and the dict's ``member_weight`` ``(P * n,)`` are member-major over ALL groups (member p of group k
+        in row ``p * n + k``), so nothing in the result depends on the batch size.  Also ``n_groups`` (= n), ``group_size``, ``num_steps``,
+        ``eta``, ``seed``, ``consistency``, ``consistency_strength`` and, where they are not the defaults, ``sampler`` / ``clip_x0``.
+
+        UNet1d on the device only; no loss part (``evaluate`` has the loss).  ``use_ema`` / ``max_batches`` as in ``evaluate``."""
+        from . import evaluation as E
+        from .unet1d import UNet1d
+
+        if not isinstance(self.model, UNet1d):
+            raise NotImplementedError("evaluate_joint: groups are built for UNet1d (dq_ddim_sample_joint); other networks are not implemented")
+        if consistency is None:
+            raise ValueError("evaluate_joint: consistency must be 'bound' or 'sum' (independent=True adds the calls without it)")
+        n_total = getattr(loader, "n_groups", None)
+        if n_total is None:
+            raise ValueError("evaluate_joint: the loader must say how many groups a pass holds (ResidentGroupLoader.n_groups)")
+        sampler_kw = _sampler_kwargs(sampler, clip_x0)
+        legs = {"joint": dict(consistency=consistency, consistency_strength=float(consistency_strength))}
+        if independent:
+            legs["independent"] = dict(consistency=None)
+        rows = {k: ([], [], []) for k in legs}
+        member_w, first, P = [], 0, None
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad(), self._ema_or_null_scope(use_ema):
+                for batch_idx, batch in enumerate(loader):
+                    if max_batches is not None and batch_idx >= int(max_batches):
+                        break
+                    if not hasattr(batch, "group_size") or (P is not None and batch.group_size != P):
+                        raise ValueError("evaluate_joint: every batch must be a GroupBatch of one group size")
+                    P = batch.group_size
+                    x_0, ms2_cond, ms1_cond = batch[0], batch.ms2_cond, batch[1]
+                    if not x_0.is_cuda:
+                        raise NotImplementedError("evaluate_joint runs in the native library only (device tensors)")
+                    G = x_0.shape[0] // P
+                    ids = torch.from_numpy(self.joint_window_ids(0, n_total, P, first, G)).to(x_0.device)
+                    for name, kw in legs.items():
+                        sample, _ = self.sample(None, ms2_cond=ms2_cond, ms1_cond=ms1_cond, num_steps=int(num_steps), eta=eta, seed=int(seed),
+                                                window_ids=ids, shape=tuple(x_0.shape), group_size=P, **kw, **sampler_kw)
+                        cross, group = E.group_metrics(sample, x_0, ms2_cond, P)
+                        rows[name][0].append(E.recon_metrics(sample, x_0).view(P, G, -1))
+                        rows[name][1].append(cross)
+                        rows[name][2].append(group)
+                    member_w.append(batch.member_weights().view(P, G))
+                    first += G
+        finally:
+            self.model.train(was_training)
+        if first == 0:
+            raise ValueError("evaluate_joint: the loader yielded no batch")
+        # one host copy per array after the loop; member-major over all groups, float64 means in that order (no batch in them)
+        mw = torch.cat(member_w, dim=1).reshape(-1).cpu().numpy().astype(np.float32)
+        out = {"n_groups": int(first), "group_size": int(P), "num_steps": int(num_steps), "eta": float(eta), "seed": int(seed),
+               "consistency": str(consistency), "consistency_strength": float(consistency_strength), "member_weight": mw}
+        out.update(_reported_options(sampler_kw))
+        for name, (pw, cross, group) in rows.items():
+            pw = torch.cat(pw, dim=1).reshape(P * first, -1).cpu().numpy()
+            cross, group = torch.cat(cross).cpu().numpy(), torch.cat(group).cpu().numpy()
+            out[name] = {**E.aggregate_joint(pw, cross, group, mw), "per_window": pw, "cross": cross, "group": group}
+        return out
+
     _RUN_SAMPLE_OPTIONS = ("num_steps", "eta", "seed", "sampler", "clip_x0", "guidance_scale", "null_ms1", "guidance_rescale",
                            "threshold_quantile", "threshold_max", "use_ema")
 

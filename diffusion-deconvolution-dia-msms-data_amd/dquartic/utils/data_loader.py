@@ -378,3 +378,78 @@ class ResidentMixLoader:
             batch = self.form(idx, count, draw=self._draw)
             self._draw += 1
             yield batch
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Groups: one mixture, P targets (csrc/k_mix.hip: dq_mix_group_batch).  What joint sampling (section 40) is scored
+# on: the first P components of a mixture are the members that ``sample(group_size=P)`` is asked for, each with its own target and MS1.
+# ----------------------------------------------------------------------------------------------------------------------
+class GroupBatch(MixBatch):
+    """A ``MixBatch`` whose items are member-major: ``(ms2_target (P*G, RT, MZ), ms1_target (P*G, ...), ms2_rest (G, RT, MZ), None)`` with
+    member p of group g in row ``p * G + g`` -- the layout ``sample(group_size=P)`` takes.  ``ms2_cond`` ``(P*G, RT, MZ)`` repeats the
+    group's mixture in every member's slice, ``weights`` is ``(G, K)`` (one mixture per group), ``rest`` the part of the mixture that no
+    member explains (0 where the group has exactly P components) and ``group_size`` P."""
+
+    def __new__(cls, items, ms2_cond, weights, group_size):
+        self = super().__new__(cls, items, ms2_cond, weights)
+        self.group_size = int(group_size)
+        self.rest = items[2]
+        return self
+
+    @property
+    def n_groups(self):
+        return self[0].shape[0] // self.group_size
+
+    def member_weights(self):
+        """``(P*G,)``: every member's own share w_p of its group's mixture, member-major"""
+        return self.weights[:, :self.group_size].t().reshape(-1)
+
+
+class ResidentGroupLoader(ResidentMixLoader):
+    """``ResidentMixLoader`` for groups: batches of ``groups_per_batch`` mixtures whose first ``group_size`` components are the members,
+    one ``dq_mix_group_batch`` call each.  The arguments and their rules are ``ResidentMixLoader``'s, with
+    ``group_size <= kmin`` on top (every mixture must hold its members).  The indices and the weights are drawn exactly as that loader draws
+    them, so with ``frozen_items`` group k IS item k of a ``ResidentMixLoader`` built with the same arguments: the same mixture, the same
+    weights, and member 0 is that loader's window bit for bit; members 1 .. P-1 are the next components of the same mixture, each with the
+    target and the MS1 it would have as the target of its own window."""
+
+    def __init__(self, dataset_or_arrays, groups_per_batch, group_size, n_components=(2, 4), max_ratio_log2=3, seed=0, scale_target=True,
+                 weights=None, frozen_items=None, device="cuda", drop_last=False, rank=0, world_size=1):
+        kmin, _ = _mix_components(n_components)
+        if isinstance(group_size, bool) or not isinstance(group_size, (int, np.integer)) or not 1 <= int(group_size) <= kmin:
+            raise ValueError(f"group_size must be an integer in [1, kmin = {kmin}] (every mixture holds its members), got {group_size!r}")
+        super().__init__(dataset_or_arrays, groups_per_batch, n_components=n_components, max_ratio_log2=max_ratio_log2, seed=seed,
+                         scale_target=scale_target, weights=weights, frozen_items=frozen_items, device=device, drop_last=drop_last, rank=rank,
+                         world_size=world_size)
+        self.group_size = int(group_size)
+        self._group_scratch = torch.empty(max(1, self._N.lib().dq_mix_group_batch_scratch_bytes(self.batch_size, self.K, self.group_size) // 4),
+                                          dtype=torch.float32, device=self.device)
+
+    @property
+    def n_groups(self):
+        """the groups of one pass over the loader"""
+        return self._items()
+
+    def form(self, idx, count=None, draw=0, window_ids=None):
+        """One native call for explicit indices ``(K, G)`` and counts ``(G,)`` (None: K everywhere) -> ``GroupBatch``."""
+        N, P = self._N, self.group_size
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        if idx.ndim != 2 or idx.shape[0] != self.K or not 1 <= idx.shape[1] <= self.batch_size:
+            raise ValueError(f"need a ({self.K}, 1..{self.batch_size}) index array, got shape {idx.shape}")
+        G = idx.shape[1]
+        idx_dev = torch.from_numpy(idx).to(self.device, non_blocking=True)
+        count_dev = None if count is None else torch.from_numpy(np.ascontiguousarray(count, dtype=np.int32)).to(self.device, non_blocking=True)
+        if count_dev is not None and count_dev.shape != (G,):
+            raise ValueError(f"need {G} counts, got shape {tuple(count_dev.shape)}")
+        ids_dev = None if window_ids is None else torch.as_tensor(np.ascontiguousarray(window_ids, dtype=np.int64)).to(self.device, non_blocking=True)
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
+        tgt, cond, rest = new(P * G, self.RT, self.MZ), new(P * G, self.RT, self.MZ), new(G, self.RT, self.MZ)
+        m1, w = new(P * G, *self.ms1_shape), new(G, self.K)
+        import ctypes
+
+        fixed = None if self.weights is None else (ctypes.c_float * self.K)(*self.weights)
+        N.check(N.lib().dq_mix_group_batch(N.ptr(self.ms2), N.ptr(self.ms1), self.n, N.ptr(idx_dev), N.ptr(count_dev), G, self.K, P, self.RT,
+                                           self.MZ, self.ms1_per, fixed, self.max_ratio_log2, N.ptr(self._seed_dev), N.ptr(ids_dev), int(draw),
+                                           int(self.scale_target), N.ptr(tgt), N.ptr(m1), N.ptr(cond), N.ptr(rest), N.ptr(w),
+                                           N.ptr(self._group_scratch), self._group_scratch.numel() * 4, N.stream_ptr()), "dq_mix_group_batch")
+        return GroupBatch((tgt, m1, rest, None), cond, w, P)

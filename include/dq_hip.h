@@ -62,7 +62,8 @@ const char* dq_last_error(void);
  * chromatograms: dq_run_window_count, dq_run_windows_scratch_bytes, dq_run_windows, dq_run_stitch; per-window sampler control:
  * dq_sample_stat_scratch_bytes, dq_window_rescale, dq_window_abs_quantile, dq_step_update_adaptive, dq_ddim_sample_adaptive; joint
  * sampling of a window's precursors: DQ_CONSIST_*, dq_group_project, dq_ddim_sample_joint; the time embedding and the input affine alone:
- * DQ_TBUF_*, dq_debug_time_fwd, dq_debug_time_bwd, dq_prep_inputs_bwd, dq_prep_inputs_bwd_scratch_floats). */
+ * DQ_TBUF_*, dq_debug_time_fwd, dq_debug_time_bwd, dq_prep_inputs_bwd, dq_prep_inputs_bwd_scratch_floats; evaluating joint sampling:
+ * dq_mix_group_batch_scratch_bytes, dq_mix_group_batch, DQ_GROUP_*, dq_group_metrics_scratch_bytes, dq_group_metrics). */
 int dq_abi_version(void);
 #define DQ_ABI_VERSION 12
 
@@ -577,6 +578,56 @@ int dq_mix_batch(const float* ms2_data, const float* ms1_data, int64_t n_windows
                  int K, int RT, int MZ, int64_t ms1_per_window, const float* weights_host, int max_ratio_log2, const uint64_t* seed_dev,
                  const int64_t* window_ids_dev, int draw, int scale_target, float* ms2_target, float* ms1_target, float* ms2_cond,
                  float* ms2_rest, float* weights_out, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* Group mixtures (csrc/k_mix.hip; additive at ABI version 12): dq_mix_batch's rule for G groups.  A group is ONE
+ * mixture of count[g] components whose first P are the members that joint sampling (dq_ddim_sample_joint, group_size = P) is asked for:
+ * 1 <= P <= K, K in 2..8.  Arguments as dq_mix_batch with G in place of B, plus P.  idx_dev (K, G): rows 0 .. P-1 are the members.  A group
+ * whose count lies outside [P, K], or that uses an index outside [0, n_windows), is never dereferenced: every output of it is NaN, and no
+ * output of another group is affected.  MS2 lo / hi over all present components (symmetric in the members); the weights are exactly
+ * dq_mix_batch's, drawn or fixed, keyed by (seed, id, draw, j) with id = window_ids_dev[g] (NULL: g); MS1 of member p is normalised by that
+ * member's own lo / hi -- what the member would see as the target of its own window.
+ * Outputs (device), member-major -- member p of group g is row p * G + g, the layout dq_ddim_sample_joint takes:
+ *   ms2_cond    (P*G, RT, MZ)  the mixture ((n_0 w_0 + n_1 w_1) + ...), written to all P member slices (the network reads every row)
+ *   ms2_target  (P*G, RT, MZ)  n_p, or under scale_target the product n_p w_p that entered the mixture
+ *   ms1_target  (P*G, ms1_per_window)
+ *   ms2_rest    (G, RT, MZ), nullable: (n_P w_P + n_{P+1} w_{P+1}) + ..., the part no member explains; 0 when count == P
+ *   weights_out (G, K)
+ * Every operation is one rounded fp32 operation in this order, so a numpy fp32 transcription gives every bit (tests/group_eval_ref.py).
+ * ms2_cond in every slice, weights_out and member 0's target and MS1 are dq_mix_batch's outputs on the same arguments bit for bit; with
+ * fixed weights member p's are dq_mix_batch's with rows 0 and p of idx and weights_host[0] / [p] swapped; with scale_target and count == P
+ * the members' targets added in order are ms2_cond.
+ * Two launches, no atomics, asynchronous on stream.  Algorithmic bytes per group: (count + 2 P + 1) * RT*MZ*4 + the MS1 rows.
+ * scratch: dq_mix_group_batch_scratch_bytes(G, K, P) = 8 * G * (8 + P) bytes (0 for arguments the call refuses).
+ * Refused before any launch (dq_last_error), in dq_mix_batch's order with P directly behind K: a NULL among ms2_data, ms1_data, idx_dev,
+ * ms2_target, ms1_target, ms2_cond, weights_out, scratch; K outside 2..8; P outside 1..K; max_ratio_log2 outside 0..16; draw < 0; G outside
+ * 1..65535; a non-positive size; RT*MZ % 4 != 0; weights_host == NULL without seed_dev; scratch too small. */
+int64_t dq_mix_group_batch_scratch_bytes(int G, int K, int P);
+int dq_mix_group_batch(const float* ms2_data, const float* ms1_data, int64_t n_windows, const int64_t* idx_dev, const int32_t* count_dev,
+                       int G, int K, int P, int RT, int MZ, int64_t ms1_per_window, const float* weights_host, int max_ratio_log2,
+                       const uint64_t* seed_dev, const int64_t* window_ids_dev, int draw, int scale_target, float* ms2_target,
+                       float* ms1_target, float* ms2_cond, float* ms2_rest, float* weights_out, void* scratch, int64_t scratch_bytes,
+                       void* stream);
+
+/* What a group's P predictions do together (csrc/k_group_metrics.hip; additive at ABI version 12).  pred, target
+ * (P*G, RT, MZ) fp32, member-major; mix (G, RT, MZ): row g is read, the members' repeats are not.  All in the caller's image units.  Every
+ * sum in fp64 over the fp32 inputs, every output rounded to fp32 once:
+ *   cross (G, P, P)  cross[g, p, q] = sum pred_p target_q / sqrt(sum pred_p^2 * sum target_q^2); 0 if either norm is 0.  The diagonal is
+ *                    dq_recon_metrics' cosine of window p G + g.
+ *   group (G, 3)     with S = sum_p max(pred_p, 0) (p ascending) and m+ = max(mix, 0) per element:
+ *                    0 excess       sum max(S - m+, 0) / sum m+
+ *                    1 unexplained  sum max(m+ - S, 0) / sum m+
+ *                    2 mix_total    sum m+                          (the two ratios are 0 when sum m+ == 0)
+ * P in 1..8; RT, MZ any positive values; any 4-byte alignment (16-byte accesses where RT*MZ % 4 == 0 and pred, target and mix are 16-byte
+ * aligned, 4-byte ones otherwise: the same bits either way).  No atomics; the work partition depends on (RT, MZ, P) only and partials are
+ * folded in index order: a group's rows are bit for bit the same in any batch and on every repeat.
+ * scratch: dq_group_metrics_scratch_bytes(G, P, RT, MZ) = 8 * G * (P + 1) * (P + 2) * ceil(RT*MZ / 4096) bytes, 8-byte aligned (-1 for a
+ * size < 1 or P outside 1..8).
+ * Refused before anything touches the device, in this order: a NULL argument; P outside 1..8; a size below 1; scratch too small; pred,
+ * target, mix, cross or group not 4-byte aligned (scratch: 8-byte). */
+enum { DQ_GROUP_EXCESS = 0, DQ_GROUP_UNEXPLAINED = 1, DQ_GROUP_MIX_TOTAL = 2, DQ_GROUP_METRIC_COUNT = 3 };
+int64_t dq_group_metrics_scratch_bytes(int G, int P, int RT, int MZ);
+int dq_group_metrics(const float* pred, const float* target, const float* mix, float* cross, float* group, void* scratch,
+                     int64_t scratch_bytes, int G, int P, int RT, int MZ, void* stream);
 
 /* Whole chromatograms (csrc/k_run.hip; additive at ABI version 12): one observed run ms2_run (RT_total, MZ) with its
  * MS1 trace ms1_run (RT_total, M1), fp32 on the device, cut into windows of W scans every `step` scans, and the windows' predictions
