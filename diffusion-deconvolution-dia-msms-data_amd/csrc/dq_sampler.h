@@ -1,8 +1,9 @@
-// What the two sampling calls share (dq_sampler.hip).  A call travels as one record, SampleCall, filled by its extern "C" entry; from it
+// What the two sampling calls share (dq_sampler.hip).  A call travels as one record, the dq_sample_call its caller filled; from it
 // come, once each, the refusals made before anything touches the device (sample_check), the sampler's tables with x_T (sample_begin) and
 // the captured-or-eager tail (sample_run).  The U-Net's call (unet_sample) and the transformer's (dq_tfm_sample) differ in their workspace
 // layout, in the forward they hand the loop as its StepForward, and in what they stage in front of it.  Internal: not installed.
 #pragma once
+#include "../../include/dq_hip.h"  // dq_sample_call
 #include "dq_common.h"
 #include "dq_kernels.h"  // WinStatScratch
 #include "dq_unet.h"     // StepUpdate, StepGraph
@@ -10,29 +11,19 @@
 
 namespace dq {
 
-// One sampling call as its entry received it.  who: the entry's own name, the prefix of every refusal; allow_v: DQ_PRED_V is a known
-// objective of this entry (the pred_type of the older ones names the reference's two).  guided: the scale w of
-// g = u + w (c - u) and the null condition's raw MS1 value; adaptive (section 38): rescaled guidance at phi, thresholding at `quantile` (0: off);
-// consistency (section 40; DQ_CONSIST_*, 0: off): the batch is B / group_size groups of group_size members, projected at `strength`
-struct SampleCall {
+// One sampling call inside the library: the caller's record itself (dq_sample_call, include/dq_hip.h: its fields and their off values are
+// described there, once), with what is not the caller's: who, the entry's name and the prefix of every refusal; allow_v: DQ_PRED_V is an
+// objective of this entry's network.  Made by sample_call_open from the entry's pointer; nothing is copied field by field.
+struct SampleCall : dq_sample_call {
   const char* who = "";
   bool allow_v = false;
-  const float* alpha_bars_host = nullptr; int T = 0;  // the caller's schedule and its length (DDIMDiffusionModel.num_timesteps)
-  const float* x_T = nullptr; const float* ms2_cond = nullptr; const float* ms1_cond = nullptr;
-  int normalize = 0, pred = 0;  // pred: DQ_PRED_*
-  const int32_t* ts = nullptr; int num_steps = 0;  // trunc(linspace(T-1, 0, num_steps)), formed by the caller exactly as model.py:313 does
-  float *out_x = nullptr, *out_noise = nullptr, *traj_x = nullptr, *traj_eps = nullptr;
-  int use_graph = 0;
-  void* workspace = nullptr; int64_t workspace_bytes = 0;
-  int B = 0, RT = 0;
-  hipStream_t stream = nullptr;
-  float eta = 0.f; const uint64_t* seed = nullptr; const int64_t* ids = nullptr;
-  int sampler = 0; float clip_x0 = 0.f;
-  bool guided = false; float w = 1.f, null_ms1 = 0.f;
-  bool adaptive = false; double phi = 0.0; float quantile = 0.f, cap = 0.f; void* stat_scratch = nullptr; int64_t stat_bytes = 0;
-  int group_size = 1, consistency = 0; float strength = 1.f;
+  hipStream_t s() const { return (hipStream_t)stream; }
+  bool per_window() const { return guidance_rescale != 0.0 || threshold_quantile != 0.f; }  // a live per-window option (NaN: set, refused by sample_check)
   bool graph() const { return use_graph && !traj_x && !traj_eps; }  // one step captured and replayed; otherwise the eager steps
 };
+// An entry's first two refusals, before any other field is read: a null record, then a struct_bytes that is not this library's
+// sizeof(dq_sample_call) (the message names both); *out is then the record under the entry's name
+int sample_call_open(const dq_sample_call* call, const char* who, bool allow_v, SampleCall* out);
 
 // The per-window statistics of a step (k_winstat.hip), run between the forward and the update: rescale (guided
 // calls): m_b of rescaled guidance at phi; q > 0: dynamic thresholding at that quantile with floor f and cap.  S: the call's scratch at a

@@ -1,5 +1,5 @@
-// The U-Net's sampling entries of the C ABI (include/dq_hip.h) and what both networks' calls share (dq_sampler.h): the stand-alone updates,
-// each a StepUpdateLaunch filled by update_launch; the refusals, tables and tail of a sampling call, read from its SampleCall; and the loop
+// The U-Net's sampling entry of the C ABI (include/dq_hip.h) and what both networks' calls share (dq_sampler.h): the stand-alone updates,
+// each a StepUpdateLaunch filled by update_launch; the refusals, tables and tail of a sampling call, read from its record; and the loop
 // with its captured step -- a network forward with one of the four StepUpdate kinds in or behind its head launch, plain, guided or per window.
 #include "dq_net.h"
 #include "dq_options.h"
@@ -154,12 +154,22 @@ int eager_steps(const SampleLoop& L, float* traj_x, float* traj_eps, const int64
 
 namespace dq {
 
+int sample_call_open(const dq_sample_call* call, const char* who, bool allow_v, SampleCall* out) {
+  const std::string w(who);
+  DQ_REQUIRE(call, w + ": null argument (call)");
+  DQ_REQUIRE(call->struct_bytes == (int32_t)sizeof(dq_sample_call),
+             w + ": call->struct_bytes is " + std::to_string(call->struct_bytes) + ", sizeof(dq_sample_call) of this library is " +
+                 std::to_string(sizeof(dq_sample_call)) + " (a binding of another ABI version?)");
+  *out = SampleCall{*call, who, allow_v};
+  return 0;
+}
+
 int sample_check(const SampleCall& c, bool net_args_ok, SamplerChoice* out) {
   const std::string w(c.who);
   const float eta = c.eta;
   const int sampler = c.sampler;
-  const bool threshold = c.adaptive && c.quantile != 0.f;  // (NaN: on, then refused below)
-  DQ_REQUIRE(net_args_ok && c.alpha_bars_host && c.ms2_cond && c.ms1_cond && c.ts && c.out_x && c.out_noise && c.workspace, w + ": null argument");
+  const bool threshold = c.threshold_quantile != 0.f;  // (NaN: on, then refused below)
+  DQ_REQUIRE(net_args_ok && c.alpha_bars_host && c.ms2_cond && c.ms1_cond && c.timesteps_host && c.out_x && c.out_noise && c.workspace, w + ": null argument");
   DQ_REQUIRE(eta >= 0.f && eta <= 1.f, w + ": eta must satisfy 0 <= eta <= 1");  // (false for NaN)
   const bool sto = eta > 0.f;  // the update draws noise
   // step-consistent samplers: refused here, before anything touches the device
@@ -172,22 +182,22 @@ int sample_check(const SampleCall& c, bool net_args_ok, SamplerChoice* out) {
   DQ_REQUIRE(!threshold || !sto, w + ": threshold_quantile needs eta == 0");
   if (sampler != DQ_SAMPLER_REFERENCE && c.num_steps <= 1024)  // (a step count out of range is the entry's refusal: its list is not read)
     for (int i = 1; i < c.num_steps; ++i)
-      DQ_REQUIRE(c.ts[i] < c.ts[i - 1], w + ": the timesteps of this sampler must be strictly decreasing");
+      DQ_REQUIRE(c.timesteps_host[i] < c.timesteps_host[i - 1], w + ": the timesteps of this sampler must be strictly decreasing");
   // the update: the Solver family (k_update.hip) behind the forward (2M, or a clamped x0 at first order); else the reference's kernels over this sampler's table
   out->kind = sampler == DQ_SAMPLER_DPMPP_2M ? StepUpdate::SOLVER_2M : (clip || threshold) ? StepUpdate::SOLVER_1 : sto ? StepUpdate::STOCHASTIC : StepUpdate::DDIM;
   out->sto = sto; out->clip = clip || threshold; out->clip_x0 = clip ? c.clip_x0 : 0.f;
-  DQ_REQUIRE(c.seed || (c.x_T && !sto), w + ": eta > 0 and a null x_T need the seed (device memory)");
-  DQ_REQUIRE(c.pred == DQ_PRED_EPS || c.pred == DQ_PRED_X0 || (c.allow_v && c.pred == DQ_PRED_V), w + ": Unknown pred_type");
-  out->pred = c.pred;
-  DQ_REQUIRE(!c.guided || guidance_ok(c.w), w + ": the guidance scale must be finite and >= 0");
+  DQ_REQUIRE(c.seed_dev || (c.x_T && !sto), w + ": eta > 0 and a null x_T need the seed (device memory)");
+  DQ_REQUIRE(c.pred_type == DQ_PRED_EPS || c.pred_type == DQ_PRED_X0 || (c.allow_v && c.pred_type == DQ_PRED_V), w + ": Unknown pred_type");
+  out->pred = c.pred_type;
+  DQ_REQUIRE(!c.guided || guidance_ok(c.guidance_scale), w + ": the guidance scale must be finite and >= 0");
   StepStats& st = out->stats = StepStats{};
-  if (!c.adaptive) return 0;
-  DQ_REQUIRE(c.phi >= 0.0 && c.phi <= 1.0, w + ": guidance_rescale must satisfy 0 <= guidance_rescale <= 1");  // (false for NaN)
-  DQ_REQUIRE(!threshold || (c.quantile > 0.f && c.quantile <= 1.f), w + ": threshold_quantile must satisfy 0 < threshold_quantile <= 1 (0: off)");
+  if (!c.per_window()) return 0;  // (both at their off value: threshold_max is not looked at, stat_scratch may be null)
+  DQ_REQUIRE(c.guidance_rescale >= 0.0 && c.guidance_rescale <= 1.0, w + ": guidance_rescale must satisfy 0 <= guidance_rescale <= 1");  // (false for NaN)
+  DQ_REQUIRE(!threshold || (c.threshold_quantile > 0.f && c.threshold_quantile <= 1.f), w + ": threshold_quantile must satisfy 0 < threshold_quantile <= 1 (0: off)");
   st.floor = clip ? c.clip_x0 : 1.f;
-  DQ_REQUIRE(!threshold || c.cap >= st.floor, w + ": threshold_max must be >= the floor (clip_x0, or 1 without it)");  // (false for NaN)
-  st.phi = c.phi; st.rescale = c.guided && c.phi > 0.0;  // (unguided: g = c, m = 1 -- nothing to do)
-  st.q = threshold ? c.quantile : 0.f; st.cap = c.cap;
+  DQ_REQUIRE(!threshold || c.threshold_max >= st.floor, w + ": threshold_max must be >= the floor (clip_x0, or 1 without it)");  // (false for NaN)
+  st.phi = c.guidance_rescale; st.rescale = c.guided && c.guidance_rescale > 0.0;  // (unguided: g = c, m = 1 -- nothing to do)
+  st.q = threshold ? c.threshold_quantile : 0.f; st.cap = c.threshold_max;
   DQ_REQUIRE(!st.on() || c.stat_scratch, w + ": null argument (stat_scratch)");
   return 0;
 }
@@ -196,45 +206,48 @@ int sample_check_group(const SampleCall& c, SamplerChoice* out) {
   const std::string w(c.who);
   out->group = StepGroup{};
   if (c.consistency == DQ_CONSIST_NONE) return 0;
+  DQ_REQUIRE(!c.guided && !c.per_window(),
+             w + ": consistency together with guided, guidance_rescale or threshold_quantile is not implemented (follow-up: the guided form of "
+                 "the group pass, which needs the mirror half written, and the per-window statistics over projected estimates)");
   DQ_REQUIRE(c.group_size >= 1 && c.group_size <= DQ_GROUP_MAX, w + ": group_size must be 1..8");
   DQ_REQUIRE(c.B % c.group_size == 0, w + ": the batch must be a whole number of groups (B % group_size == 0)");
   DQ_REQUIRE(group_mode_ok(c.consistency), w + ": unknown consistency mode");
-  DQ_REQUIRE(group_strength_ok(c.strength), w + ": consistency strength must satisfy 0 < strength <= 1");
+  DQ_REQUIRE(group_strength_ok(c.consistency_strength), w + ": consistency strength must satisfy 0 < strength <= 1");
   StepGroup& g = out->group;
-  g.P = c.group_size; g.mode = c.consistency; g.strength = c.strength; g.pred = out->pred; g.normalize = c.normalize;
+  g.P = c.group_size; g.mode = c.consistency; g.strength = c.consistency_strength; g.pred = out->pred; g.normalize = c.auto_normalize;
   return 0;
 }
 
 int sample_begin(const SampleCall& c, const SamplerChoice& sc, int64_t per, float* coef_dev, float* extra_dev, float* xa) {
-  hipStream_t s = c.stream;
+  hipStream_t s = c.s();
   // coefficient table, fp32 like the reference, and sigma (eta > 0) or c1 (the solver) per step
   std::vector<float> coef(4 * (size_t)c.num_steps), extra((size_t)c.num_steps);
-  if (c.sampler == DQ_SAMPLER_REFERENCE) DQ_TRY(dq_ddim_coef_table(c.alpha_bars_host, c.T, c.ts, c.num_steps, c.eta, coef.data(), extra.data()));
-  else DQ_TRY(sampler_rows(c.alpha_bars_host, c.T, c.ts, c.num_steps, sc.kind == StepUpdate::SOLVER_1 ? SOLVER_ORDER1 : c.sampler, c.eta, coef.data(),
+  if (c.sampler == DQ_SAMPLER_REFERENCE) DQ_TRY(dq_ddim_coef_table(c.alpha_bars_host, c.num_timesteps, c.timesteps_host, c.num_steps, c.eta, coef.data(), extra.data()));
+  else DQ_TRY(sampler_rows(c.alpha_bars_host, c.num_timesteps, c.timesteps_host, c.num_steps, sc.kind == StepUpdate::SOLVER_1 ? SOLVER_ORDER1 : c.sampler, c.eta, coef.data(),
                            extra.data(), c.who));
   DQ_HIP_OK(hipMemcpyAsync(coef_dev, coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice, s));
   if (extra_dev) DQ_HIP_OK(hipMemcpyAsync(extra_dev, extra.data(), sizeof(float) * extra.size(), hipMemcpyHostToDevice, s));
   // the host vector must outlive the copy: pageable H2D copies are staged synchronously by the runtime, but make it explicit
   DQ_HIP_OK(hipStreamSynchronize(s));
   if (c.x_T) DQ_HIP_OK(hipMemcpyAsync(xa, c.x_T, sizeof(float) * c.B * per, hipMemcpyDeviceToDevice, s));
-  else DQ_TRY(launch_randn(xa, c.ids, c.seed, 0, c.B, per, s));  // draw index 0 is x_T's
+  else DQ_TRY(launch_randn(xa, c.window_ids_dev, c.seed_dev, 0, c.B, per, s));  // draw index 0 is x_T's
   return 0;
 }
 
 int sample_run(const SampleCall& c, const SampleLoop& L, bool sto, StepGraph& g, bool reusable, const StepStage& st, bool* captured) {
   *captured = false;
-  if (!c.graph()) return eager_steps(L, c.traj_x, c.traj_eps, c.ids, c.seed, c.stream);
+  if (!c.graph()) return eager_steps(L, c.traj_x, c.traj_eps, c.window_ids_dev, c.seed_dev, c.s());
   // ---- hipGraph path: one step captured once, replayed per step; the step index lives on the device (*step, bumped by k_inc_step)
-  DQ_HIP_OK(hipMemsetAsync(st.step, 0, sizeof(int), c.stream));
-  if (sto) DQ_TRY(sampler_stage_noise(st, c.seed, c.ids, c.B, c.stream));
-  return replay_captured_step(g, reusable, L, st.step, StepNoise{st.ids, st.seed, 0}, c.stream, captured);
+  DQ_HIP_OK(hipMemsetAsync(st.step, 0, sizeof(int), c.s()));
+  if (sto) DQ_TRY(sampler_stage_noise(st, c.seed_dev, c.window_ids_dev, c.B, c.s()));
+  return replay_captured_step(g, reusable, L, st.step, StepNoise{st.ids, st.seed, 0}, c.s(), captured);
 }
 
 }  // namespace dq
 
 namespace {
 
-// The U-Net's sampling call, under every dq_ddim_sample* entry.  Guided, the arena and the forward run at NB = 2 B windows: rows [0, B)
+// The U-Net's sampling call, under dq_ddim_sample.  Guided, the arena and the forward run at NB = 2 B windows: rows [0, B)
 // carry the caller's MS1, rows [B, 2B) q.null_ms1 in every element (a raw value: it goes through the same cm, ca normalisation); both
 // halves see the same mixture and the same x, which the update keeps equal by writing x_prev to both (x_mirror).  The update / hist /
 // trajectories / outputs cover B windows, and a guided update never rides in the head launch.
@@ -243,10 +256,10 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
   SamplerChoice sc;
   DQ_TRY(sample_check(q, plan && params, &sc));
   const int B = q.B, RT = q.RT, num_steps = q.num_steps;
-  const bool g = q.guided;
+  const bool g = q.guided != 0;
   if (sc.stats.on()) {  // the statistics scratch, carved here for every step of the call
     DQ_REQUIRE(B > 0 && RT > 0, wh + ": need B, RT > 0 and 1 <= num_steps <= 1024");
-    DQ_TRY(win_stat_carve(wh, q.stat_scratch, q.stat_bytes, B, (int64_t)RT * plan->plan.mz, &sc.stats.S));
+    DQ_TRY(win_stat_carve(wh, q.stat_scratch, q.stat_scratch_bytes, B, (int64_t)RT * plan->plan.mz, &sc.stats.S));
   }
   DQ_REQUIRE(B > 0 && RT > 0 && num_steps >= 1 && num_steps <= 1024, wh + ": need B, RT > 0 and 1 <= num_steps <= 1024");
   DQ_REQUIRE(!g || B <= INT32_MAX / 2, wh + ": batch too large");
@@ -256,14 +269,14 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
   DQ_TRY(ensure_arena(plan, NB, RT));
   const Arena& a = plan->arena;
   DQ_REQUIRE(q.workspace_bytes >= (int64_t)sizeof(float) * a.floats, wh + ": workspace too small");
-  DQ_REQUIRE(q.T >= 1, wh + ": num_timesteps must be >= 1");
-  hipStream_t s = q.stream;
+  DQ_REQUIRE(q.num_timesteps >= 1, wh + ": num_timesteps must be >= 1");
+  hipStream_t s = q.s();
   float* W = (float*)q.workspace;
   Ctx c{plan->plan, a, params, W, nullptr, nullptr, NB, RT, s};
   c.save = false;
   const int64_t per = (int64_t)RT * plan->plan.mz, n = B * per;
   const int64_t n1 = (int64_t)B * RT * plan->plan.ms1_channels;  // the caller's MS1
-  const float cm = q.normalize ? 2.f : 1.f, ca = q.normalize ? -1.f : 0.f;
+  const float cm = q.auto_normalize ? 2.f : 1.f, ca = q.auto_normalize ? -1.f : 0.f;
   // the head launch takes the update when it can (StepIO::x_t); the others, every guided one and every one over groups (the pass comes
   // between the two) run behind the forward
   const bool in_head = sc.kind == StepUpdate::DDIM && !g && !grp;
@@ -277,7 +290,7 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
   const float* c1 = staged ? c.w(a.c1_stage) : q.ms1_cond;
   // The step index of a captured step lives on the device: k_time_fwd reads ts_tab[*step], the update its coefficient row, k_inc_step bumps it.
   int* ts_tab = reinterpret_cast<int*>(c.w(a.ts_tab));
-  if (q.graph()) DQ_HIP_OK(hipMemcpyAsync(ts_tab, q.ts, sizeof(int32_t) * num_steps, hipMemcpyHostToDevice, s));
+  if (q.graph()) DQ_HIP_OK(hipMemcpyAsync(ts_tab, q.timesteps_host, sizeof(int32_t) * num_steps, hipMemcpyHostToDevice, s));
   if (staged) {
     DQ_HIP_OK(hipMemcpyAsync(c.w(a.c2_stage), q.ms2_cond, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
     DQ_HIP_OK(hipMemcpyAsync(c.w(a.c1_stage), q.ms1_cond, sizeof(float) * n1, hipMemcpyDeviceToDevice, s));
@@ -298,18 +311,18 @@ int unet_sample(dq_plan* plan, const float* params, const float* rope_freqs, con
     fc.save = false; fc.step_io = &io;
     io.x_t = in_head ? x : nullptr; io.x_out = x_out; io.coef = c.w(a.coef) + 4 * row; io.step_ptr = step_ptr; io.want_eps = want_eps; io.fused_update = false;
     const int rc = step_ptr ? unet_forward(fc, rope_freqs, x, nullptr, 0, c2, c1, cm, ca, plan->dev, net_out, ts_tab, step_ptr)
-                            : unet_forward(fc, rope_freqs, x, nullptr, q.ts[row], c2, c1, cm, ca, plan->dev, net_out);
+                            : unet_forward(fc, rope_freqs, x, nullptr, q.timesteps_host[row], c2, c1, cm, ca, plan->dev, net_out);
     *fused = io.fused_update;
     return rc;
   };
   sc.group.mix = c2;  // the group's mixture: row g of the tensor the network reads
   // (over groups the update runs in its x0-objective form over the projected estimate; the pass reads the output by the network's objective)
   const SampleLoop loop{forward, StepUpdateArgs{sc.kind, c.w(a.coef), c.w(a.sigma), c.w(a.xb), sc.clip_x0, grp ? DQ_PRED_X0 : sc.pred, B, per, g,
-                                                g ? q.w : 1.f, sc.stats, sc.group},
-                        xa, c.w(a.eps), sc.clip, num_steps, q.ms2_cond, q.out_x, q.out_noise, q.normalize};
+                                                g ? q.guidance_scale : 1.f, sc.stats, sc.group},
+                        xa, c.w(a.eps), sc.clip, num_steps, q.ms2_cond, q.out_x, q.out_noise, q.auto_normalize};
   StepKey key;
-  key.params = params; key.rope = rope_freqs; key.ws = q.workspace; key.B = B; key.RT = RT; key.normalize = q.normalize; key.pred = q.pred;
-  key.update = sc.kind; key.clip = sc.clip_x0; key.guidance = g ? q.w : -1.f; key.opt_epoch = options_epoch();
+  key.params = params; key.rope = rope_freqs; key.ws = q.workspace; key.B = B; key.RT = RT; key.normalize = q.auto_normalize; key.pred = q.pred_type;
+  key.update = sc.kind; key.clip = sc.clip_x0; key.guidance = g ? q.guidance_scale : -1.f; key.opt_epoch = options_epoch();
   if (sc.stats.on()) { key.rescale = sc.stats.rescale ? sc.stats.phi : 0.0; key.quantile = sc.stats.q; key.cap = sc.stats.cap; key.stat_scratch = q.stat_scratch; }
   if (grp) { key.group_size = sc.group.P; key.consistency = sc.group.mode; key.strength = sc.group.strength; }
   const StepStage stage{reinterpret_cast<int*>(c.w(a.step)), reinterpret_cast<uint64_t*>(c.w(a.seed_stage)), reinterpret_cast<int64_t*>(c.w(a.ids_stage))};
@@ -407,52 +420,27 @@ int dq_solver_step(const float* x_t, const float* net_out, float* x_prev, float*
   return launch_update(a, (hipStream_t)stream);
 }
 
-int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                   const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                   const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                   int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream) {
-  DQ_REQUIRE(x_T, "dq_ddim_sample: null argument");
-  return dq_ddim_sample_ex(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type,
-                           timesteps_host, num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT, stream,
-                           0.f, nullptr, nullptr);
-}
-
-int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                      const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                      const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                      int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                      const uint64_t* seed_dev, const int64_t* window_ids_dev) {
-  return dq_ddim_sample_solver(plan, params, rope_freqs, alpha_bars_host, num_timesteps, x_T, ms2_cond, ms1_cond, auto_normalize, pred_type,
-                               timesteps_host, num_steps, out_x, out_noise, traj_x, traj_eps, use_graph, workspace, workspace_bytes, B, RT,
-                               stream, eta, seed_dev, window_ids_dev, DQ_SAMPLER_REFERENCE, 0.f);
-}
-
-int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                      const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                      const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                      int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                      const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0) {
-  SampleCall q;  q.who = "dq_ddim_sample";  // (dq_ddim_sample and dq_ddim_sample_ex arrive here: the three refuse under the first one's name)
-  q.alpha_bars_host = alpha_bars_host; q.T = num_timesteps; q.x_T = x_T; q.ms2_cond = ms2_cond; q.ms1_cond = ms1_cond; q.normalize = auto_normalize;
-  q.pred = pred_type; q.ts = timesteps_host; q.num_steps = num_steps; q.out_x = out_x; q.out_noise = out_noise; q.traj_x = traj_x; q.traj_eps = traj_eps;
-  q.use_graph = use_graph; q.workspace = workspace; q.workspace_bytes = workspace_bytes; q.B = B; q.RT = RT; q.stream = (hipStream_t)stream;
-  q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
+int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, const dq_sample_call* call) {
+  SampleCall q;
+  DQ_TRY(sample_call_open(call, "dq_ddim_sample", true, &q));
   return unet_sample(plan, params, rope_freqs, q);
 }
 
-int dq_ddim_sample_guided(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                          const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                          const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                          int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                          const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, float guidance_scale,
-                          float null_ms1) {
-  SampleCall q;  q.who = "dq_ddim_sample_guided";
-  q.alpha_bars_host = alpha_bars_host; q.T = num_timesteps; q.x_T = x_T; q.ms2_cond = ms2_cond; q.ms1_cond = ms1_cond; q.normalize = auto_normalize;
-  q.pred = pred_type; q.ts = timesteps_host; q.num_steps = num_steps; q.out_x = out_x; q.out_noise = out_noise; q.traj_x = traj_x; q.traj_eps = traj_eps;
-  q.use_graph = use_graph; q.workspace = workspace; q.workspace_bytes = workspace_bytes; q.B = B; q.RT = RT; q.stream = (hipStream_t)stream;
-  q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
-  q.guided = true; q.w = guidance_scale; q.null_ms1 = null_ms1;
-  return unet_sample(plan, params, rope_freqs, q);
+// The record's layout as compiled here: sizeof, then (offsetof, size) per field in declaration order
+int dq_debug_sample_call_layout(int32_t* out, int cap) {
+  int n = 0;
+  int32_t v[1 + 2 * 64];
+  v[n++] = (int32_t)sizeof(dq_sample_call);
+#define DQ_F(f) v[n++] = (int32_t)offsetof(dq_sample_call, f); v[n++] = (int32_t)sizeof(((dq_sample_call*)nullptr)->f);
+  DQ_F(struct_bytes) DQ_F(alpha_bars_host) DQ_F(num_timesteps) DQ_F(x_T) DQ_F(ms2_cond) DQ_F(ms1_cond) DQ_F(auto_normalize) DQ_F(pred_type)
+  DQ_F(timesteps_host) DQ_F(num_steps) DQ_F(out_x) DQ_F(out_noise) DQ_F(traj_x) DQ_F(traj_eps) DQ_F(use_graph) DQ_F(workspace)
+  DQ_F(workspace_bytes) DQ_F(B) DQ_F(RT) DQ_F(stream) DQ_F(eta) DQ_F(seed_dev) DQ_F(window_ids_dev) DQ_F(sampler) DQ_F(clip_x0) DQ_F(guided)
+  DQ_F(guidance_scale) DQ_F(null_ms1) DQ_F(guidance_rescale) DQ_F(threshold_quantile) DQ_F(threshold_max) DQ_F(stat_scratch)
+  DQ_F(stat_scratch_bytes) DQ_F(group_size) DQ_F(consistency) DQ_F(consistency_strength)
+#undef DQ_F
+  if (!out || cap < n) return -1;
+  std::memcpy(out, v, sizeof(int32_t) * n);
+  return n;
 }
 
 int dq_guided_update(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
@@ -468,38 +456,6 @@ int dq_guided_update_v(int kind, const float* x_t, const float* net_c, const flo
                        int draw, int B, int64_t per_window, void* stream) {
   return guided_update("dq_guided_update_v", kind, x_t, net_c, net_u, x_prev, x_mirror, x0_hist, eps_out, coef_dev, w, clip_x0, window_ids_dev,
                        seed_dev, draw, DQ_PRED_V, B, per_window, stream);
-}
-
-int dq_ddim_sample_v(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                     const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                     const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps, int use_graph,
-                     void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta, const uint64_t* seed_dev,
-                     const int64_t* window_ids_dev, int sampler, float clip_x0, int guided, float guidance_scale, float null_ms1) {
-  SampleCall q;  q.who = "dq_ddim_sample_v";
-  q.alpha_bars_host = alpha_bars_host; q.T = num_timesteps; q.x_T = x_T; q.ms2_cond = ms2_cond; q.ms1_cond = ms1_cond; q.normalize = auto_normalize;
-  q.pred = pred_type; q.ts = timesteps_host; q.num_steps = num_steps; q.out_x = out_x; q.out_noise = out_noise; q.traj_x = traj_x; q.traj_eps = traj_eps;
-  q.use_graph = use_graph; q.workspace = workspace; q.workspace_bytes = workspace_bytes; q.B = B; q.RT = RT; q.stream = (hipStream_t)stream;
-  q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
-  q.allow_v = true;
-  q.guided = guided != 0; q.w = guidance_scale; q.null_ms1 = null_ms1;
-  return unet_sample(plan, params, rope_freqs, q);
-}
-
-// ---- joint sampling of a window's precursors
-int dq_ddim_sample_joint(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                         const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                         const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                         int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                         const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, int group_size, int consistency,
-                         float strength) {
-  SampleCall q;  q.who = "dq_ddim_sample_joint";
-  q.alpha_bars_host = alpha_bars_host; q.T = num_timesteps; q.x_T = x_T; q.ms2_cond = ms2_cond; q.ms1_cond = ms1_cond; q.normalize = auto_normalize;
-  q.pred = pred_type; q.ts = timesteps_host; q.num_steps = num_steps; q.out_x = out_x; q.out_noise = out_noise; q.traj_x = traj_x; q.traj_eps = traj_eps;
-  q.use_graph = use_graph; q.workspace = workspace; q.workspace_bytes = workspace_bytes; q.B = B; q.RT = RT; q.stream = (hipStream_t)stream;
-  q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
-  q.allow_v = true;
-  q.group_size = group_size; q.consistency = consistency; q.strength = strength;
-  return unet_sample(plan, params, rope_freqs, q);
 }
 
 // ---- per-window sampler control
@@ -538,25 +494,6 @@ int dq_step_update_adaptive(int kind, const float* x_t, const float* net_c, cons
                                      StepNoise{window_ids_dev, seed_dev, draw}, B, per_window);
   a.w = w; a.win = table_dev;
   return launch_update(a, (hipStream_t)stream);
-}
-
-int dq_ddim_sample_adaptive(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                            const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                            const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                            int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                            const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, int guided, float guidance_scale,
-                            float null_ms1, double guidance_rescale, float threshold_quantile, float threshold_max, void* stat_scratch,
-                            int64_t stat_scratch_bytes) {
-  SampleCall q;  q.who = "dq_ddim_sample_adaptive";
-  q.alpha_bars_host = alpha_bars_host; q.T = num_timesteps; q.x_T = x_T; q.ms2_cond = ms2_cond; q.ms1_cond = ms1_cond; q.normalize = auto_normalize;
-  q.pred = pred_type; q.ts = timesteps_host; q.num_steps = num_steps; q.out_x = out_x; q.out_noise = out_noise; q.traj_x = traj_x; q.traj_eps = traj_eps;
-  q.use_graph = use_graph; q.workspace = workspace; q.workspace_bytes = workspace_bytes; q.B = B; q.RT = RT; q.stream = (hipStream_t)stream;
-  q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
-  q.allow_v = true;
-  q.guided = guided != 0; q.w = guidance_scale; q.null_ms1 = null_ms1;
-  q.adaptive = true; q.phi = guidance_rescale; q.quantile = threshold_quantile; q.cap = threshold_max;
-  q.stat_scratch = stat_scratch; q.stat_bytes = stat_scratch_bytes;
-  return unet_sample(plan, params, rope_freqs, q);
 }
 
 int dq_ms1_cond_drop(const float* ms1_in, float* ms1_out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, double p,

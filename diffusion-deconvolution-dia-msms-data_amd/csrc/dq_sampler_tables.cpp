@@ -1,5 +1,5 @@
 // The samplers' per-step coefficient tables: dq_ddim_coef_table, dq_sampler_coef_table (include/dq_hip.h) and the one row builder behind
-// them and behind dq_ddim_sample_solver (dq_sampler.hip).  Host C++ alone: no HIP call, and it compiles with a plain host compiler.
+// them and behind dq_ddim_sample (dq_sampler.hip).  Host C++ alone: no HIP call, and it compiles with a plain host compiler.
 #include "dq_sampler_tables.h"
 #include "dq_error.h"
 #include "../../include/dq_hip.h"

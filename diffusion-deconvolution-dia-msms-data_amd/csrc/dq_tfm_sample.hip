@@ -1,4 +1,4 @@
-// Sampling from the CustomTransformer inside the library: dq_tfm_sample fills the call's record and runs it as the
+// Sampling from the CustomTransformer inside the library: dq_tfm_sample runs the call's record as the
 // U-Net's entry does (dq_sampler.h: the shared refusals, tables and captured-or-eager tail around this network's layout, prologue and
 // forward), one update per step behind a sampling forward of the network -- and the stand-alone entry of the fused inference attention
 // (k_tfm_attn.hip).  What does not depend on the step is computed once per call, before the loop: the conditional
@@ -131,35 +131,35 @@ int64_t dq_tfm_sample_workspace_bytes(const dq_tfm* p, int B, int S1, int S2, in
   return carve_sample(*p, nullptr, B, S1, S2, num_steps).floats * (int64_t)sizeof(float);
 }
 
-int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const float* rope_cos, const float* time_freqs,
-                  const float* alpha_bars_host, int num_timesteps, const float* x_T, const float* ms2_cond, const float* ms1_cond,
-                  int auto_normalize, int pred_type, const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x,
-                  float* traj_eps, int use_graph, void* workspace, int64_t workspace_bytes, int B, int S1, int S2, void* stream, float eta,
-                  const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0) {
-  SampleCall q;  q.who = "dq_tfm_sample";
-  q.alpha_bars_host = alpha_bars_host; q.T = num_timesteps; q.x_T = x_T; q.ms2_cond = ms2_cond; q.ms1_cond = ms1_cond; q.normalize = auto_normalize;
-  q.pred = pred_type; q.ts = timesteps_host; q.num_steps = num_steps; q.out_x = out_x; q.out_noise = out_noise; q.traj_x = traj_x; q.traj_eps = traj_eps;
-  q.use_graph = use_graph; q.workspace = workspace; q.workspace_bytes = workspace_bytes; q.B = B; q.RT = S1; q.stream = (hipStream_t)stream;
-  q.eta = eta; q.seed = seed_dev; q.ids = window_ids_dev; q.sampler = sampler; q.clip_x0 = clip_x0;
+int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const float* rope_cos, const float* time_freqs, int S2,
+                  const dq_sample_call* call) {
+  SampleCall q;
+  DQ_TRY(sample_call_open(call, "dq_tfm_sample", false, &q));
+  const int B = q.B, S1 = q.RT, num_steps = q.num_steps, auto_normalize = q.auto_normalize;
   SamplerChoice sc;
   DQ_TRY(sample_check(q, p && params && rope_sin && rope_cos && time_freqs, &sc));
+  // what the record can say and this network's loop is not built for: refused, never silently ignored
+  DQ_REQUIRE(!q.guided, "dq_tfm_sample: guided sampling is built for the U-Net (dq_ddim_sample); guidance for this network is the follow-up");
+  DQ_REQUIRE(!q.per_window(), "dq_tfm_sample: guidance_rescale and threshold_quantile are built for the U-Net (dq_ddim_sample); the per-window "
+                              "statistics step for this network is the follow-up");
+  DQ_REQUIRE(q.consistency == DQ_CONSIST_NONE, "dq_tfm_sample: consistency is built for the U-Net (dq_ddim_sample); the group pass for this network is the follow-up");
   DQ_REQUIRE(B > 0 && S1 > 0 && S2 > 0 && num_steps >= 1 && num_steps <= 1024, "dq_tfm_sample: need B, S1, S2 > 0 and 1 <= num_steps <= 1024");
-  DQ_REQUIRE(q.T >= 1, "dq_tfm_sample: num_timesteps must be >= 1");
-  DQ_REQUIRE(((uintptr_t)params & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "dq_tfm_sample: params and workspace must be 16-byte aligned");
-  const SampleWs w = carve_sample(*p, (float*)workspace, B, S1, S2, num_steps);
-  DQ_REQUIRE(workspace_bytes >= w.floats * (int64_t)sizeof(float), "dq_tfm_sample: workspace too small (dq_tfm_sample_workspace_bytes)");
+  DQ_REQUIRE(q.num_timesteps >= 1, "dq_tfm_sample: num_timesteps must be >= 1");
+  DQ_REQUIRE(((uintptr_t)params & 15) == 0 && ((uintptr_t)q.workspace & 15) == 0, "dq_tfm_sample: params and workspace must be 16-byte aligned");
+  const SampleWs w = carve_sample(*p, (float*)q.workspace, B, S1, S2, num_steps);
+  DQ_REQUIRE(q.workspace_bytes >= w.floats * (int64_t)sizeof(float), "dq_tfm_sample: workspace too small (dq_tfm_sample_workspace_bytes)");
   PrecisionScope prec(p->precision);
-  hipStream_t s = q.stream;
+  hipStream_t s = q.s();
   const int64_t per = (int64_t)S1 * p->D;
   const float cm = auto_normalize ? 2.f : 1.f, ca = auto_normalize ? -1.f : 0.f;
   const TfmWalk net = cached_walk(p, params, rope_sin, rope_cos, w.net, w.kv.data(), w.time.temb, false, B, S1, S2);
   // the steps' timesteps for the time table (the copy is done when sample_begin returns: it synchronises the stream)
-  std::vector<int64_t> t64(timesteps_host, timesteps_host + num_steps);
+  std::vector<int64_t> t64(q.timesteps_host, q.timesteps_host + num_steps);
   DQ_HIP_OK(hipMemcpyAsync(w.t64, t64.data(), sizeof(int64_t) * t64.size(), hipMemcpyHostToDevice, s));
   DQ_TRY(sample_begin(q, sc, per, w.coef, w.sigma, w.xa));
   if (net.attn_form == TFM_ATTN_FUSED) DQ_TRY(tfm_attn_prepare());  // (the LDS limit of this device, before any capture)
   // every call, outside any capture: a changed MS1, or changed weights behind the same pointer, cannot meet a stale cache
-  DQ_TRY(sample_prologue(net, B, ms1_cond, cm, ca, time_freqs, w.t64, num_steps, w.time, s));
+  DQ_TRY(sample_prologue(net, B, q.ms1_cond, cm, ca, time_freqs, w.t64, num_steps, w.time, s));
   // the forward of this network: a linear graph when captured (one stream, no branches); the time row is `row`, or read at *step_ptr
   const StepForward forward = [&](const float* x, float*, int row, const int* step_ptr, float* net_out, bool, bool* fused, hipStream_t fs) {
     *fused = false;  // (the update is never in this network's launches)
@@ -168,10 +168,10 @@ int dq_tfm_sample(dq_tfm* p, const float* params, const float* rope_sin, const f
     return tfm_walk(step, x, net_out, fs);
   };
   const SampleLoop loop{forward, StepUpdateArgs{sc.kind, w.coef, w.sigma, w.xb, sc.clip_x0, sc.pred, B, per}, w.xa, w.eps, sc.clip,
-                        num_steps, ms2_cond, out_x, out_noise, auto_normalize};
+                        num_steps, q.ms2_cond, q.out_x, q.out_noise, auto_normalize};
   TfmStepKey key;
-  key.params = params; key.ws = workspace; key.rope_sin = rope_sin; key.rope_cos = rope_cos; key.B = B; key.S1 = S1; key.S2 = S2;
-  key.num_steps = num_steps; key.normalize = auto_normalize; key.pred = pred_type; key.precision = p->precision; key.update = sc.kind; key.clip = sc.clip_x0;
+  key.params = params; key.ws = q.workspace; key.rope_sin = rope_sin; key.rope_cos = rope_cos; key.B = B; key.S1 = S1; key.S2 = S2;
+  key.num_steps = num_steps; key.normalize = auto_normalize; key.pred = q.pred_type; key.precision = p->precision; key.update = sc.kind; key.clip = sc.clip_x0;
   key.opt_epoch = options_epoch();
   bool captured;
   const int rc = sample_run(q, loop, sc.sto, p->step, p->step.exec && p->step_key == key, StepStage{w.step, w.seed_stage, w.ids_stage}, &captured);

@@ -8,11 +8,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DQ_HIP_LIB", os.path.join(os.path.dirname(_HERE), "libdq_hip.so"))
 
 _lib = None
-ABI_VERSION = 12  # DQ_ABI_VERSION of include/dq_hip.h this table was written against
+ABI_VERSION = 13  # DQ_ABI_VERSION of include/dq_hip.h this table was written against
 PRED_TYPES = {"eps": 0, "x0": 1, "v_prediction": 2}  # DQ_PRED_EPS / DQ_PRED_X0 / DQ_PRED_V
 SAMPLERS = {"reference": 0, "ddim": 1, "dpmpp_2m": 2}  # DQ_SAMPLER_*
 UPDATE_KINDS = {"ddim": 0, "stochastic": 1, "solver_1": 2, "solver_2m": 3}  # DQ_UPDATE_* (dq_guided_update)
-CONSISTENCY_MODES = {"bound": 1, "sum": 2}  # DQ_CONSIST_BOUND / DQ_CONSIST_SUM (dq_group_project, dq_ddim_sample_joint)
+CONSISTENCY_MODES = {"bound": 1, "sum": 2}  # DQ_CONSIST_BOUND / DQ_CONSIST_SUM (dq_group_project, dq_sample_call.consistency)
 GROUP_MAX = 8  # DQ_GROUP_MAX
 PRECISIONS = {"fp32": 0, "bf16x3": 1}  # DQ_PRECISION_FP32 / DQ_PRECISION_BF16X3
 FINAL_ACTS = {"identity": 0, "softplus": 1}  # DQ_FINAL_IDENTITY / DQ_FINAL_SOFTPLUS
@@ -85,43 +85,22 @@ PROTOTYPES = {
     "dq_recon_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "dq_ms1_loss_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
                                     c_void_p, c_int, c_int, c_int, c_void_p]),
-    "dq_ddim_sample": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                               POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
-                               c_void_p]),
+    "dq_ddim_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),  # (plan, params, rope_freqs, const dq_sample_call*)
     "dq_randn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
     "dq_ddim_step_sto": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64,
                                  c_void_p]),
     "dq_ddim_coef_table": (c_int, [POINTER(c_float), c_int, POINTER(c_int32), c_int, c_float, POINTER(c_float), POINTER(c_float)]),
-    "dq_ddim_sample_ex": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                  POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
-                                  c_void_p, c_float, c_void_p, c_void_p]),
     "dq_sampler_coef_table": (c_int, [POINTER(c_float), c_int, POINTER(c_int32), c_int, c_int, c_float, POINTER(c_float), POINTER(c_float)]),
     "dq_solver_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int64, c_void_p]),
-    "dq_ddim_sample_solver": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                      POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
-                                      c_void_p, c_float, c_void_p, c_void_p, c_int, c_float]),
     "dq_guided_update": (c_int, [c_int] + [c_void_p] * 8 + [c_float, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
     "dq_solver_step_v": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p]),
     "dq_guided_update_v": (c_int, [c_int] + [c_void_p] * 8 + [c_float, c_float, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
-    "dq_ddim_sample_v": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                 POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
-                                 c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_int, c_float, c_float]),
     "dq_sample_stat_scratch_bytes": (c_int64, [c_int, c_int64]),
     "dq_window_rescale": (c_int, [c_void_p, c_void_p, c_float, c_double, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "dq_window_abs_quantile": (c_int, [c_void_p, c_int, c_int64, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
     "dq_step_update_adaptive": (c_int, [c_int] + [c_void_p] * 8 + [c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
-    "dq_ddim_sample_adaptive": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                        POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
-                                        c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_int, c_float, c_float, c_double, c_float, c_float,
-                                        c_void_p, c_int64]),
     "dq_group_project": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_int64, c_int, c_float, c_void_p]),
-    "dq_ddim_sample_joint": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                     POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
-                                     c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_int, c_int, c_float]),
     "dq_ms1_cond_drop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_float, c_int, c_int64, c_void_p]),
-    "dq_ddim_sample_guided": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                      POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
-                                      c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_float, c_float]),
     "dq_pair_batch_scratch_bytes": (c_int64, [c_int]),
     "dq_pair_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int64, c_float, c_float, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -143,6 +122,7 @@ PROTOTYPES = {
     "dq_debug_side_tail_store": (c_int, [c_void_p, c_void_p, c_float, c_int]),
     "dq_debug_layout": (c_int, [c_void_p, c_int, c_int]),
     "dq_debug_mid_forms": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32), c_int]),
+    "dq_debug_sample_call_layout": (c_int, [POINTER(c_int32), c_int]),
     "dq_debug_mid_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "dq_debug_mid_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "dq_debug_wide_mid_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
@@ -182,8 +162,7 @@ PROTOTYPES = {
     "dq_tfm_attn_form": (c_int, [c_int, c_int, c_int]),
     "dq_tfm_attn_fwd": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
     "dq_tfm_sample_workspace_bytes": (c_int64, [c_void_p, c_int, c_int, c_int, c_int]),
-    "dq_tfm_sample": (c_int, [c_void_p] * 5 + [POINTER(c_float), c_int] + [c_void_p] * 3 + [c_int, c_int, POINTER(c_int32), c_int] + [c_void_p] * 4
-                      + [c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_float]),
+    "dq_tfm_sample": (c_int, [c_void_p] * 5 + [c_int, c_void_p]),  # (..., S2, const dq_sample_call*)
     "dq_tfm_eval_workspace_bytes": (c_int64, [c_void_p, c_int, c_int, c_int, c_int]),
     "dq_tfm_eval_step": (c_int, [c_void_p] * 12 + [c_int] * 3 + [c_void_p] * 5 + [c_int64] + [c_int] * 4 + [c_void_p]),
     "dq_q_sample_repeats": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
@@ -364,6 +343,39 @@ def gemm_desc(**fields) -> GemmDesc:
             raise AttributeError(f"dq_gemm_desc has no field {k!r}")
         setattr(d, k, v)
     return d
+
+
+class SampleCall(ctypes.Structure):
+    """``dq_sample_call`` of include/dq_hip.h, field for field (``dq_debug_sample_call_layout`` is the library's side of the layout)."""
+    _fields_ = [("struct_bytes", c_int32), ("alpha_bars_host", c_void_p), ("num_timesteps", c_int32), ("x_T", c_void_p), ("ms2_cond", c_void_p),
+                ("ms1_cond", c_void_p), ("auto_normalize", c_int32), ("pred_type", c_int32), ("timesteps_host", c_void_p), ("num_steps", c_int32),
+                ("out_x", c_void_p), ("out_noise", c_void_p), ("traj_x", c_void_p), ("traj_eps", c_void_p), ("use_graph", c_int32),
+                ("workspace", c_void_p), ("workspace_bytes", c_int64), ("B", c_int32), ("RT", c_int32), ("stream", c_void_p), ("eta", c_float),
+                ("seed_dev", c_void_p), ("window_ids_dev", c_void_p), ("sampler", c_int32), ("clip_x0", c_float), ("guided", c_int32),
+                ("guidance_scale", c_float), ("null_ms1", c_float), ("guidance_rescale", c_double), ("threshold_quantile", c_float),
+                ("threshold_max", c_float), ("stat_scratch", c_void_p), ("stat_scratch_bytes", c_int64), ("group_size", c_int32),
+                ("consistency", c_int32), ("consistency_strength", c_float)]
+
+
+def sample_call(**fields) -> SampleCall:
+    """A ``dq_sample_call`` with ``struct_bytes`` set and every option at its off value (all zero / NULL, ``group_size`` 1), then ``fields``;
+    pointers are given as integers (``tensor.data_ptr()``, ``ctypes.addressof`` of a host array the caller keeps alive) or None."""
+    q = SampleCall(struct_bytes=ctypes.sizeof(SampleCall), group_size=1)
+    for k, v in fields.items():
+        if not hasattr(q, k):
+            raise AttributeError(f"dq_sample_call has no field {k!r}")
+        setattr(q, k, v)
+    return q
+
+
+def sample_call_layout():
+    """``dq_debug_sample_call_layout``: ``(sizeof, [(offset, size), ...])`` of ``dq_sample_call`` as the library was compiled."""
+    cap = 1 + 2 * len(SampleCall._fields_) + 16
+    buf = (c_int32 * cap)()
+    n = lib().dq_debug_sample_call_layout(buf, cap)
+    if n < 1 or n % 2 != 1:
+        raise RuntimeError("dq_debug_sample_call_layout failed")
+    return int(buf[0]), [(int(buf[i]), int(buf[i + 1])) for i in range(1, n, 2)]
 
 
 def gemm_ex(desc: GemmDesc, stream=None) -> int:

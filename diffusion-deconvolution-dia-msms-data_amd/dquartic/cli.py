@@ -338,7 +338,7 @@ def evaluate_joint(config_path, checkpoint, num_steps, eta, seed, sample_kw, ind
         raise click.ClickException(f"--group-size {group_size}: the validation mixtures hold kmin = {kmin} .. {int(val['mixture']['n_components'][1])} "
                                    f"components (mixture.n_components); every group needs its members, so 1 <= --group-size <= kmin")
     if m["use_model"] != "UNet1d":
-        raise click.ClickException("evaluate-joint: groups are built for UNet1d (dq_ddim_sample_joint); other networks are not implemented")
+        raise click.ClickException("evaluate-joint: groups are built for UNet1d (dq_ddim_sample); other networks are not implemented")
     sample_kw.setdefault("consistency", "bound")
     if not torch.cuda.is_available():
         raise click.ClickException("no GPU visible: this build runs the hot path on MI355X only (no CPU fallback)")

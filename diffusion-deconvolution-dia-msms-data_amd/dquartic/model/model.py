@@ -137,15 +137,15 @@ _JOINT_WITH_OPTIONS = ("sample: consistency together with guidance_scale, guidan
 
 # the options only UNet1d's native sampler serves, as sample() refuses them: (on a CustomTransformer, on anything else)
 _UNET_ONLY = {
-    "joint": ("sample: group_size / consistency are built for UNet1d (dq_ddim_sample_joint); the group pass for the CustomTransformer's sampler "
+    "joint": ("sample: group_size / consistency are built for UNet1d (dq_ddim_sample); the group pass for the CustomTransformer's sampler "
               "(dq_tfm_sample) is the follow-up",
               "sample: group_size / consistency need the native sampler (this package's UNet1d on the GPU with both conditions); the generic "
               "loop is the plain update only"),
-    "adaptive": ("sample: guidance_rescale and threshold_quantile are built for UNet1d (dq_ddim_sample_adaptive); the per-window statistics "
+    "adaptive": ("sample: guidance_rescale and threshold_quantile are built for UNet1d (dq_ddim_sample); the per-window statistics "
                  "step for the CustomTransformer's sampler (dq_tfm_sample) is the follow-up",
                  "sample: guidance_rescale and threshold_quantile need the native sampler (this package's UNet1d on the GPU with both "
                  "conditions); the generic loop is the plain update only"),
-    "guidance": ("sample: guidance_scale is built for UNet1d (dq_ddim_sample_guided); guidance for the CustomTransformer's sampler "
+    "guidance": ("sample: guidance_scale is built for UNet1d (dq_ddim_sample); guidance for the CustomTransformer's sampler "
                  "(dq_tfm_sample) is the follow-up",
                  "sample: guidance_scale needs the native sampler (this package's UNet1d on the GPU with both conditions); the generic "
                  "loop is the unguided update only"),
@@ -454,7 +454,7 @@ class DDIMDiffusionModel(ModelInterface):
         condition -- MS1 equal to the raw value ``null_ms1`` in every element, what ``set_cond_dropout`` trains the network on.  ``None``
         and 1.0 are the call as it is without the option, bit for bit: 1.0 *is* the conditional model, no doubled batch is run for it.
         Any other finite ``w >= 0`` (0: the unconditional model; > 1 pushes towards the component MS1 names) runs one forward at twice
-        the batch per step inside the library (``dq_ddim_sample_guided``) and combines with every option above.  UNet1d on the GPU
+        the batch per step inside the library and combines with every option above.  UNet1d on the GPU
         only: the generic loop and the CustomTransformer raise NotImplementedError.
 
         ``guidance_rescale = phi`` in [0, 1] and ``threshold_quantile = q`` in (0, 1] look at each window as a
@@ -464,7 +464,7 @@ class DDIMDiffusionModel(ModelInterface):
         window's ``q``-quantile ``s`` of ``|x0|`` -- never below the floor ``f = clip_x0`` (1 without it), never above ``threshold_max`` --
         and scaled by ``f / s``, which keeps the shape of a peak the constant clamp would cut flat; it is allowed where ``clip_x0`` is
         ('ddim' or 'dpmpp_2m', ``eta == 0``).  The defaults are the call as it is without the options, bit for bit and launch for launch.
-        UNet1d on the GPU only (``dq_ddim_sample_adaptive``).
+        UNet1d on the GPU only.
 
         ``group_size = P`` and ``consistency`` sample the P precursors of an isolation window as one group.  The
         batch is ``B / P`` groups of P members, member-major -- member p of group g is row ``p * G + g``, the concatenation of P ordinary
@@ -475,8 +475,7 @@ class DDIMDiffusionModel(ModelInterface):
         ``consistency_strength`` in (0, 1] blends between the estimate (towards 0) and its projection (1).  The update then runs on the
         projected x0 whatever the objective.  ``consistency=None`` is the call as it is without the option, bit for bit (``group_size``
         is only checked); ``consistency`` without ``group_size`` means P = 1.  Works with every sampler, ``eta``, ``clip_x0``, seeds, window
-        ids and trajectories; not together with ``guidance_scale``, ``guidance_rescale`` or ``threshold_quantile``.  UNet1d on the GPU only
-        (``dq_ddim_sample_joint``)."""
+        ids and trajectories; not together with ``guidance_scale``, ``guidance_rescale`` or ``threshold_quantile``.  UNet1d on the GPU only."""
         eta = self._check_eta(eta)
         options = JointSampleOptions(sampler, clip_x0, guidance_scale, null_ms1, guidance_rescale, threshold_quantile, threshold_max, group_size,
                                      consistency, consistency_strength)
@@ -498,7 +497,7 @@ class DDIMDiffusionModel(ModelInterface):
             raise NotImplementedError(_UNET_ONLY[unet_only][0 if self._native_tfm else 1])
         call = dict(seed=seed, window_ids=window_ids, shape=shape, sampler=sampler_id, clip_x0=clip)
         if self.native and on_gpu:
-            # (the default call passes eta=None: dq_ddim_sample, the call as it always was; ``adaptive`` and ``joint`` only when live)
+            # (the default call passes eta=None: the call as it always was; ``adaptive`` and ``joint`` only when live)
             plain = not (unet_only or stochastic or sampler_id != 0)
             return self._sample_native(x_t, ms2_cond, ms1_cond, num_steps, return_trajectory, eta=None if plain else eta, guidance=guidance,
                                        **call, **({} if adaptive is None else {"adaptive": adaptive}), **({} if joint is None else {"joint": joint}))
@@ -569,55 +568,48 @@ class DDIMDiffusionModel(ModelInterface):
         self.last_seed = None if seed_dev is None else int(seed_dev.item()) & (2 ** 64 - 1)  # (what a seed=None call drew)
         return seed_dev, ids_dev
 
-    def _run_loop(self, entry, head, B, tail, x_T, c2, c1, ws, num_steps, dims, return_trajectory, take=None):
+    def _run_loop(self, entry, head, call, x_T, c2, c1, ws, num_steps, dims, return_trajectory):
         """What both native calls stage alike, and the call: the int32 timesteps, [out_x, out_noise, traj_x, traj_eps] (the trajectories
-        (num_steps, *dims), or None), the graph flag (off with a trajectory), the 17 arguments both networks' entries take alike -- the
-        schedule up to the batch ``B`` -- between the network's own in front (``head``) and behind (``tail``), and what ``sample``
-        returns.  ``take``: the indices of the list that ``entry`` takes (None: all)."""
+        (num_steps, *dims), or None), the graph flag (off with a trajectory) and the fields of the record (``N.sample_call``) that both
+        networks fill alike -- the schedule, the tensors, the workspace, the batch, the stream -- then the caller's own by name (``call``);
+        the entry takes the network's arguments (``head``) and the record.  Returns what ``sample`` returns."""
         ts_c = (ctypes.c_int32 * num_steps)(*self.sampler_timesteps(self.num_timesteps, num_steps).to(torch.int32).tolist())
         outs = [torch.empty_like(c2), torch.empty_like(c2)] + [
             torch.empty((num_steps, *dims), device=c2.device) if return_trajectory else None for _ in range(2)]
-        args = [*head, self._alpha_bars_host(), int(self.num_timesteps), N.ptr(x_T), N.ptr(c2), N.ptr(c1), 1 if self.auto_normalize else 0,
-                N.PRED_TYPES[self.pred_type], ts_c, num_steps, *(N.ptr(v) for v in outs), 1 if (self.use_graph and not return_trajectory) else 0,
-                N.ptr(ws), ws.numel(), B, *tail]
-        N.check(getattr(N.lib(), entry)(*(args if take is None else [args[i] for i in take])), entry)
+        q = N.sample_call(alpha_bars_host=ctypes.addressof(self._alpha_bars_host()), num_timesteps=int(self.num_timesteps), x_T=N.ptr(x_T),
+                          ms2_cond=N.ptr(c2), ms1_cond=N.ptr(c1), auto_normalize=1 if self.auto_normalize else 0,
+                          pred_type=N.PRED_TYPES[self.pred_type], timesteps_host=ctypes.addressof(ts_c), num_steps=num_steps,
+                          out_x=N.ptr(outs[0]), out_noise=N.ptr(outs[1]), traj_x=N.ptr(outs[2]), traj_eps=N.ptr(outs[3]),
+                          use_graph=1 if (self.use_graph and not return_trajectory) else 0, workspace=N.ptr(ws), workspace_bytes=ws.numel(),
+                          B=dims[0], RT=dims[1], stream=N.stream_ptr(), **call)
+        N.check(getattr(N.lib(), entry)(*head, ctypes.byref(q)), entry)
         return tuple(outs) if return_trajectory else tuple(outs[:2])
-
-    # Which of the full argument list -- dq_ddim_sample_adaptive's 35 -- each of the U-Net's entries takes: the 22 of dq_ddim_sample, then
-    # (eta, seed, ids), (sampler, clip_x0), the guided flag, (scale, null_ms1), (phi, q, cap, scratch, bytes).  A call over groups never has
-    # the last five: its (group size, mode, strength) follow the 30 of dq_ddim_sample_v, and its entry takes them behind the solver's 27
-    _SAMPLE_ENTRY_ARGS = {"dq_ddim_sample": range(22), "dq_ddim_sample_ex": range(25), "dq_ddim_sample_solver": range(27),
-                          "dq_ddim_sample_guided": (*range(27), 28, 29), "dq_ddim_sample_v": range(30), "dq_ddim_sample_adaptive": range(35),
-                          "dq_ddim_sample_joint": (*range(27), 30, 31, 32)}
 
     def _sample_native(self, x_T, ms2_cond, ms1_cond, num_steps, return_trajectory=False, eta=None, seed=None, window_ids=None, shape=None,
                        sampler=0, clip_x0=0.0, guidance=None, adaptive=None, joint=None):
-        """The U-Net's loop in the library, through the entry that knows what is live -- ``joint`` = (P, mode, strength): ``dq_ddim_sample_joint``
-        (never with ``adaptive`` or ``guidance``); ``adaptive`` = (phi, q, cap): ``dq_ddim_sample_adaptive``;
-        else ``pred_type="v_prediction"``: ``dq_ddim_sample_v``; else ``eta`` None: ``dq_ddim_sample`` (the call as it always was); else
-        ``guidance`` = (scale, null_ms1): ``dq_ddim_sample_guided`` (on the workspace of twice the batch, as every guided call); else
-        ``sampler`` != 0: ``dq_ddim_sample_solver``; else ``dq_ddim_sample_ex`` -- which takes its part of one list (``_SAMPLE_ENTRY_ARGS``)."""
+        """The U-Net's loop in the library (``dq_ddim_sample``); the record holds what is live and leaves every other option off.  ``eta``
+        None: the call as it always was (eta 0, no seed, no ids; ``last_seed`` untouched); ``guidance`` = (scale, null_ms1): on the
+        workspace of twice the batch; ``adaptive`` = (phi, q, cap): with the statistics scratch; ``joint`` = (P, mode, strength): never
+        with ``adaptive`` or ``guidance``."""
         net: UNet1d = self.model
         x_T, c2, B, RT, MZ = self._stage_x(x_T, ms2_cond, eta, seed, shape)
         c1 = net._check_inputs(ms1_cond, B, RT).detach().to(torch.float32).contiguous()
         flat = net.read_params()  # (the averaged weights inside ModelInterface.ema_scope())
         ws = net.workspace(2 * B if guidance is not None else B, RT, False)
-        entry = ("dq_ddim_sample_joint" if joint is not None else "dq_ddim_sample_adaptive" if adaptive is not None else
-                 "dq_ddim_sample_v" if self.pred_type == "v_prediction" else
-                 "dq_ddim_sample" if eta is None else "dq_ddim_sample_guided" if guidance is not None else
-                 "dq_ddim_sample_solver" if sampler else "dq_ddim_sample_ex")
-        tail = [RT, N.stream_ptr()]
-        if entry != "dq_ddim_sample":
-            seed_dev, ids_dev = self._stage_noise(x_T, eta or 0.0, seed, window_ids, B, c2.device)
-            tail += [float(eta or 0.0), N.ptr(seed_dev), N.ptr(ids_dev), int(sampler), float(clip_x0), 0 if guidance is None else 1,
-                     *((1.0, 0.0) if guidance is None else (float(guidance[0]), float(guidance[1])))]
+        call = {}
+        if eta is not None:
+            seed_dev, ids_dev = self._stage_noise(x_T, eta, seed, window_ids, B, c2.device)
+            call.update(eta=float(eta), seed_dev=N.ptr(seed_dev), window_ids_dev=N.ptr(ids_dev), sampler=int(sampler), clip_x0=float(clip_x0))
+        if guidance is not None:
+            call.update(guided=1, guidance_scale=float(guidance[0]), null_ms1=float(guidance[1]))
         if adaptive is not None:
             stat = net.stat_scratch(B, RT * MZ)
-            tail += [*(float(v) for v in adaptive), N.ptr(stat), stat.numel()]
+            call.update(guidance_rescale=float(adaptive[0]), threshold_quantile=float(adaptive[1]), threshold_max=float(adaptive[2]),
+                        stat_scratch=N.ptr(stat), stat_scratch_bytes=stat.numel())
         if joint is not None:
-            tail += [int(joint[0]), int(joint[1]), float(joint[2])]
-        return self._run_loop(entry, [net._plan, N.ptr(flat), N.ptr(net.rope_freqs())], B, tail, x_T, c2, c1, ws, num_steps, (B, RT, MZ),
-                              return_trajectory, take=self._SAMPLE_ENTRY_ARGS[entry])
+            call.update(group_size=int(joint[0]), consistency=int(joint[1]), consistency_strength=float(joint[2]))
+        return self._run_loop("dq_ddim_sample", [net._plan, N.ptr(flat), N.ptr(net.rope_freqs())], call, x_T, c2, c1, ws, num_steps,
+                              (B, RT, MZ), return_trajectory)
 
     @property
     def _native_tfm(self) -> bool:
@@ -636,9 +628,9 @@ class DDIMDiffusionModel(ModelInterface):
         ws = tfm.sample_workspace(B, S1, S2, num_steps)
         sin, cos, freqs = tfm.tables(max(S1, S2), c2.device)
         seed_dev, ids_dev = self._stage_noise(x_T, eta, seed, window_ids, B, c2.device)
-        return self._run_loop("dq_tfm_sample", [tfm._tfm, N.ptr(flat), N.ptr(sin), N.ptr(cos), N.ptr(freqs)], B,
-                              [S1, S2, N.stream_ptr(), float(eta), N.ptr(seed_dev), N.ptr(ids_dev), int(sampler), float(clip_x0)],
-                              x_T, c2, c1, ws, num_steps, (B, S1, D), return_trajectory)
+        call = dict(eta=float(eta), seed_dev=N.ptr(seed_dev), window_ids_dev=N.ptr(ids_dev), sampler=int(sampler), clip_x0=float(clip_x0))
+        return self._run_loop("dq_tfm_sample", [tfm._tfm, N.ptr(flat), N.ptr(sin), N.ptr(cos), N.ptr(freqs), S2], call, x_T, c2, c1, ws,
+                              num_steps, (B, S1, D), return_trajectory)
 
     # ------------------------------------------------------------------ training objective
     def train_step(self, x_0, ms2_cond=None, ms1_cond=None, noise=None, ms1_loss_weight=0.0, t=None):

@@ -834,7 +834,7 @@ class ModelInterface(object):
         from .unet1d import UNet1d
 
         if not isinstance(self.model, UNet1d):
-            raise NotImplementedError("evaluate_joint: groups are built for UNet1d (dq_ddim_sample_joint); other networks are not implemented")
+            raise NotImplementedError("evaluate_joint: groups are built for UNet1d (dq_ddim_sample); other networks are not implemented")
         if consistency is None:
             raise ValueError("evaluate_joint: consistency must be 'bound' or 'sum' (independent=True adds the calls without it)")
         n_total = getattr(loader, "n_groups", None)

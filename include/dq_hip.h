@@ -63,9 +63,11 @@ const char* dq_last_error(void);
  * dq_sample_stat_scratch_bytes, dq_window_rescale, dq_window_abs_quantile, dq_step_update_adaptive, dq_ddim_sample_adaptive; joint
  * sampling of a window's precursors: DQ_CONSIST_*, dq_group_project, dq_ddim_sample_joint; the time embedding and the input affine alone:
  * DQ_TBUF_*, dq_debug_time_fwd, dq_debug_time_bwd, dq_prep_inputs_bwd, dq_prep_inputs_bwd_scratch_floats; evaluating joint sampling:
- * dq_mix_group_batch_scratch_bytes, dq_mix_group_batch, DQ_GROUP_*, dq_group_metrics_scratch_bytes, dq_group_metrics). */
+ * dq_mix_group_batch_scratch_bytes, dq_mix_group_batch, DQ_GROUP_*, dq_group_metrics_scratch_bytes, dq_group_metrics).  13: a sampling call
+ * crosses as one record, dq_sample_call: dq_ddim_sample and dq_tfm_sample take it, dq_ddim_sample_ex / _solver / _guided / _v / _adaptive /
+ * _joint are gone (their arguments are the record's fields); dq_debug_sample_call_layout. */
 int dq_abi_version(void);
-#define DQ_ABI_VERSION 12
+#define DQ_ABI_VERSION 13
 
 /* Process-wide tuning options (no reference counterpart: the reference has one code path per op).  The library reads NO environment
  * variable for its dispatch; what can be tuned is set here, takes effect from the next call on, and invalidates cached sampling graphs.
@@ -86,11 +88,9 @@ int64_t dq_get_option_effective(const char* key);
 /* DDIMDiffusionModel.pred_type (model.py:205-213, 269-280, 354-389); any other value is rejected ("Unknown pred_type").
  * DQ_PRED_V ("v_prediction", no reference counterpart; Salimans & Ho 2022): the network output is v = sa eps - sb x0 with sa = sqrt(ab_t),
  * sb = sqrt(1 - ab_t); x0 = sa x_t - sb v and eps = sb x_t + sa v are recovered without a division.  dq_train_step, dq_eval_step and
- * dq_ddim_step_sto and dq_ddim_sample_v take the value in their pred_type argument.  dq_solver_step, dq_guided_update and
- * dq_ddim_sample_solver are called by the test suite with 2 as an unknown objective, on operands that must not be touched, and keep
- * refusing it (with them dq_ddim_sample / _ex, which are calls of the third, and dq_ddim_sample_guided, so that the four loop entries
- * answer alike): their v forms are dq_solver_step_v, dq_guided_update_v and dq_ddim_sample_v.  dq_tfm_sample and dq_tfm_eval_step (the
- * CustomTransformer, not built for this objective) refuse it as unknown. */
+ * dq_ddim_step_sto and dq_ddim_sample take the value as their pred_type.  dq_solver_step and dq_guided_update are called by the test suite
+ * with 2 as an unknown objective, on operands that must not be touched, and keep refusing it: their v forms are dq_solver_step_v and
+ * dq_guided_update_v.  dq_tfm_sample and dq_tfm_eval_step (the CustomTransformer, not built for this objective) refuse it as unknown. */
 enum { DQ_PRED_EPS = 0, DQ_PRED_X0 = 1, DQ_PRED_V = 2 };
 
 /* ---- network description -------------------------------------------------------------------------------------
@@ -122,7 +122,7 @@ int64_t dq_unet_workspace_bytes(dq_plan* plan, int B, int RT, int training);
  *   DQ_FINAL_SOFTPLUS: torch.nn.Softplus() (beta 1, threshold 20): y = x for x > 20, else log1p(exp(x)); dy/dx = 1 for x > 20,
  *                      else sigmoid(x).
  * Per plan.  It applies to every entry point that forms or differentiates the network output: dq_unet_fwd, dq_unet_bwd (grad_out is
- * d loss / d y, the activated output), dq_train_step (its losses are taken on y) and dq_ddim_sample (eps or, with DQ_PRED_X0, x0 is y; dq_ddim_sample_v: v is y).
+ * d loss / d y, the activated output), dq_train_step (its losses are taken on y) and dq_ddim_sample (eps or, with DQ_PRED_X0, x0 is y; DQ_PRED_V: v is y).
  * Workspace sizes do not depend on it.  A call drops the plan's cached sampling graph.  Any other value: non-zero (dq_last_error). */
 enum { DQ_FINAL_IDENTITY = 0, DQ_FINAL_SOFTPLUS = 1 };
 int dq_plan_set_final_act(dq_plan* plan, int act);
@@ -292,20 +292,6 @@ int64_t dq_recon_metrics_scratch_bytes(int B, int RT, int MZ);
 int dq_recon_metrics(const float* pred, const float* target, float* out, void* scratch, int64_t scratch_bytes, int B, int RT, int MZ,
                      void* stream);
 
-/* ---- DDIMDiffusionModel.sample (model.py:293-324) --------------------------------------------------------------
- * Runs the whole strided loop natively over timesteps_host[num_steps] (host ints; the caller forms them as
- * trunc(linspace(T-1, 0, num_steps)), model.py:313): each step = network forward + K9 (landing on alpha_bars[t-1],
- * model.py:284), then the epilogue (model.py:319-322).  alpha_bars_host: num_timesteps host floats (DDIMDiffusionModel.alpha_bars;
- * every timestep must lie in [0, num_timesteps)); num_steps <= 1024.  x_T (B,RT,MZ) is not modified.  out_x = denoised in [0,1]; out_noise = mixture -
- * denoised.  traj_x / traj_eps (nullable): (num_steps,B,RT,MZ) per-step x_{t-1} and eps.  use_graph != 0 (and no trajectory
- * requested; traj_eps always holds eps_pred, derived from the x0 prediction under DQ_PRED_X0): one step is captured
- * into a hipGraph (cached in the plan while params/workspace/B/RT stay the same) and
- * replayed num_steps times; the conditions are staged inside the workspace, the step index lives on the device. */
-int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                   const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                   const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                   int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream);
-
 /* ---- stochastic sampling (no reference counterpart) -----------------------------------------
  * Noise is Philox4x32-10 (Random123 constants) evaluated inside the kernels: for element e of its window (0 <= e < per_window < 2^32),
  * draw index d, window id w (int64) and seed s (uint64): counter (e, d, w lo, w hi), key (s lo, s hi); output words r0, r1 give
@@ -320,22 +306,13 @@ int dq_randn(float* out, const int64_t* window_ids_dev, const uint64_t* seed_dev
 int dq_ddim_step_sto(const float* x_t, const float* net_out, float* x_prev, float* eps_out, const float* coef_dev,
                      const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window,
                      void* stream);
-/* The sampler's coefficient rows (host only, no GPU call; the function dq_ddim_sample / _ex use): per step i at t = timesteps_host[i],
+/* The sampler's coefficient rows (host only, no GPU call; the function dq_ddim_sample uses under DQ_SAMPLER_REFERENCE): per step i at t = timesteps_host[i],
  * coef_out[4i..] = [sqrt(ab), sqrt(1-ab), sqrt(abp), c] and sigma_out[i], ab = alpha_bars[t], abp = alpha_bars[t-1];
  *   sigma = eta sqrt((1-abp)/(1-ab)) sqrt(1 - ab/abp), c = sqrt(max(0, 1 - abp - sigma^2))   (double, from the fp32 table values);
- * eta == 0: c = sqrt(1-abp) in fp32 (model.py:284-286, what dq_ddim_sample always used) and sigma = 0.  t == 0: [.., -1, 0], sigma 0.
+ * eta == 0: c = sqrt(1-abp) in fp32 (model.py:284-286, what the sampling loop always used) and sigma = 0.  t == 0: [.., -1, 0], sigma 0.
  * 0 <= eta <= 1, anything else (NaN included): non-zero (dq_last_error). */
 int dq_ddim_coef_table(const float* alpha_bars_host, int num_timesteps, const int32_t* timesteps_host, int num_steps, float eta,
                        float* coef_out, float* sigma_out);
-/* dq_ddim_sample with the DDIM eta (Song et al. 2021, eq. 16; eta = 1: ancestral DDPM-like sampling): dq_ddim_sample is this call with
- * eta = 0 and NULL seed / ids.  eta > 0: the update runs as dq_ddim_step_sto behind the forward (one more launch per step); needs seed_dev.
- * x_T may be NULL (needs seed_dev): x_T = dq_randn at draw index 0.  The graph path stages seed and ids inside the workspace; graphs
- * captured with eta > 0 and eta == 0 are cached apart, the value of eta itself lives in the coefficient tables. */
-int dq_ddim_sample_ex(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                      const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                      const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                      int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                      const uint64_t* seed_dev, const int64_t* window_ids_dev);
 
 /* ---- step-consistent sampling (no reference counterpart) ------------------------------------
  * The reference's update at timestep t lands on alpha_bars[t-1] while the next step relabels the state as the next entry of the strided
@@ -366,17 +343,6 @@ int dq_solver_step(const float* x_t, const float* net_out, float* x_prev, float*
  * was clamped, (x_t - sa x0) / sb).  Everything else as dq_solver_step. */
 int dq_solver_step_v(const float* x_t, const float* v_pred, float* x_prev, float* x0_hist, float* eps_out, const float* coef_dev,
                      float clip_x0, int64_t n, void* stream);
-/* dq_ddim_sample_ex with a sampler and the clamp: (DQ_SAMPLER_REFERENCE, clip_x0 <= 0) is dq_ddim_sample_ex, call for call.
- * DQ_SAMPLER_DDIM with clip off runs the reference's kernels and captured graph over the strided table (eta > 0: dq_ddim_step_sto).
- * DQ_SAMPLER_DPMPP_2M, and DQ_SAMPLER_DDIM with clip_x0 > 0 (first-order rows), run dq_solver_step behind the forward (one more launch per
- * step), x in place and the x0 history in the workspace.  Refused before any device call: eta > 0 with DQ_SAMPLER_DPMPP_2M or with
- * clip_x0 > 0, clip_x0 > 0 with DQ_SAMPLER_REFERENCE, timesteps that do not strictly decrease (samplers 1, 2).  Captured steps are cached
- * by update kind and clip value. */
-int dq_ddim_sample_solver(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                          const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                          const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                          int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                          const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0);
 
 /* ---- classifier-free guidance on MS1 (no reference counterpart) ------------------------------
  * MS1 is the one input that names the component to extract (the mixture is the same whichever precursor is asked for).  A network trained
@@ -406,17 +372,6 @@ int dq_guided_update(int kind, const float* x_t, const float* net_c, const float
 int dq_guided_update_v(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
                        float* eps_out, const float* coef_dev, float w, float clip_x0, const int64_t* window_ids_dev,
                        const uint64_t* seed_dev, int draw, int B, int64_t per_window, void* stream);
-/* The U-Net's sampling loop with DQ_PRED_V among its objectives: dq_ddim_sample_guided's arguments with `guided` in front of the scale
- * (0: guidance_scale and null_ms1 are ignored and the call is dq_ddim_sample_solver's, the default update riding in the network's last
- * launch; else dq_ddim_sample_guided's).  pred_type: DQ_PRED_EPS, DQ_PRED_X0 or DQ_PRED_V -- dq_ddim_sample_solver (and dq_ddim_sample /
- * _ex, which are calls of it) is held to refusing 2 on operands that must not be touched (tests/test_tfm_sample_plan.py), so the value has
- * this entry.  Refusals, workspace, captured step and outputs as those two; under DQ_PRED_V traj_eps holds the derived eps. */
-int dq_ddim_sample_v(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                     const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                     const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                     int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                     const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, int guided, float guidance_scale,
-                     float null_ms1);
 /* Conditioning dropout (k_cond_drop.hip): ms1_out (B, per_ms1) = ms1_in, with window b replaced as a whole by null_value iff r2 < thresh.
  * r2: the THIRD output word of Philox4x32-10 on counter (0, draw, id lo, id hi) under key (seed lo, seed hi), id = window_ids_dev[b] (NULL:
  * b); the normals above use words 0 and 1 only, so the decision never correlates with a noise draw under the same seed.  thresh = (uint32)
@@ -425,21 +380,6 @@ int dq_ddim_sample_v(dq_plan* plan, const float* params, const float* rope_freqs
  * 16-byte aligned).  A window decides alone: the same under its id in any batch. */
 int dq_ms1_cond_drop(const float* ms1_in, float* ms1_out, const int64_t* window_ids_dev, const uint64_t* seed_dev, int draw, double p,
                      float null_value, int B, int64_t per_ms1, void* stream);
-/* dq_ddim_sample_solver sampling from g: every option of that call (eta, seed, ids, x_T = NULL, the three samplers, clip_x0, trajectories,
- * the captured step) with guidance_scale = w and the null's raw MS1 value null_ms1.  The arena and the forward run at 2B windows -- rows
- * [0, B) carry ms1_cond, rows [B, 2B) null_ms1 in every element; both see the same mixture and the same x -- so workspace_bytes must be
- * at least dq_unet_workspace_bytes(plan, 2 * B, RT, 0).  One forward and one update launch per step: the update runs behind the forward
- * (never in the head launch) in its guided form (dq_guided_update) over the B windows of the first half and keeps the second half's x
- * equal to the first's.  x_T, the outputs and the trajectories are B windows; traj_eps holds the guided eps.  w travels by value: captured
- * steps are cached by it (the same w replays, another w captures again).  Refusals as dq_ddim_sample_solver's, in its order, then
- * guidance_scale negative, NaN or infinite.  guidance_scale = 1 is the conditional model at twice the cost: callers wanting that call
- * dq_ddim_sample_solver. */
-int dq_ddim_sample_guided(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                          const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                          const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                          int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                          const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, float guidance_scale,
-                          float null_ms1);
 
 /* ---- per-window sampler control: rescaled guidance, dynamic x0 thresholding (no reference counterpart) -------
  * Two options that need a window as a whole: a statistics pass (csrc/k_winstat.hip) between the network forward and the update leaves two
@@ -479,22 +419,6 @@ int dq_window_abs_quantile(const float* x, int B, int64_t per_window, float q, f
 int dq_step_update_adaptive(int kind, const float* x_t, const float* net_c, const float* net_u, float* x_prev, float* x_mirror, float* x0_hist,
                             float* eps_out, const float* coef_dev, float w, const float* table_dev, const int64_t* window_ids_dev,
                             const uint64_t* seed_dev, int draw, int pred_type, int B, int64_t per_window, void* stream);
-/* dq_ddim_sample_v with the two options: guidance_rescale = phi (0: off; without `guided` a no-op: g = c, m = 1), threshold_quantile = q
- * (0: off) and threshold_max (ignored when q is 0).  With either on, every step runs the statistics launches between the forward and the
- * update (rescale: 2; threshold: 5 -- four radix passes and the fold), inside the captured step too, and the update in its per-window form
- * behind the forward, never in the head launch; thresholding selects the update clip_x0 selects (first-order solver rows under
- * DQ_SAMPLER_DDIM).  With both off the call is dq_ddim_sample_v's, launch for launch.  The workspace and its size are dq_ddim_sample_v's;
- * stat_scratch (dq_sample_stat_scratch_bytes(B, RT * MZ); unused and nullable with both off) holds the table, the partials and the
- * histograms at fixed addresses; captured steps are cached by (phi, q, threshold_max, stat_scratch) as well.  Refusals: dq_ddim_sample_v's
- * in its order, with threshold_quantile refused exactly where clip_x0 is (DQ_SAMPLER_REFERENCE, eta > 0); then phi outside [0, 1], q
- * outside (0, 1], threshold_max below the floor (NaN fails each), the scratch. */
-int dq_ddim_sample_adaptive(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                            const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                            const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                            int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                            const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, int guided,
-                            float guidance_scale, float null_ms1, double guidance_rescale, float threshold_quantile, float threshold_max,
-                            void* stat_scratch, int64_t stat_scratch_bytes);
 
 /* ---- joint sampling of a window's precursors under mixture consistency (no reference counterpart) -------------
  * data.mixture with scale_target trains the network to predict a precursor's contribution n_0 w_0 to the mixture it sees, and the
@@ -523,21 +447,97 @@ enum { DQ_CONSIST_NONE = 0, DQ_CONSIST_BOUND = 1, DQ_CONSIST_SUM = 2 };
  * (DQ_CONSIST_NONE included), strength outside (0, 1] or NaN, tensors that are not 4-byte aligned. */
 int dq_group_project(const float* x_t, const float* net, float* x0_out, const float* mix, const float* coef_dev, int pred_type,
                      int auto_normalize, int G, int P, int64_t per_window, int mode, float strength, void* stream);
-/* The U-Net's sampling loop over groups: dq_ddim_sample_v's arguments without guided, guidance_scale and null_ms1, then group_size = P,
- * consistency (DQ_CONSIST_*) and strength.  consistency = DQ_CONSIST_NONE: the other two are ignored and the call is the unguided
- * dq_ddim_sample_v, launch for launch.  Otherwise every step runs the forward, then the pass in place on the network output, then the
- * update in its x0-objective form (DQ_PRED_X0) over x0' behind the forward, never in the head launch, whatever the network's objective:
- * the projected estimate enters x_prev, the 2M history and the derived eps (x - sa x0') / sb, which is what traj_eps holds; clip_x0 clamps
- * after the projection, as the update always does.  All three samplers, any eta, seeds, window ids, x_T = NULL, trajectories and the
- * captured step (cached by (group_size, consistency, strength) as well).  Refusals: dq_ddim_sample_v's in its order; behind the ones it
- * makes before anything touches the device (up to the batch and step counts) and in front of its workspace check: group_size outside
- * [1, 8], B % group_size != 0, an unknown mode, strength outside (0, 1] or NaN. */
-int dq_ddim_sample_joint(dq_plan* plan, const float* params, const float* rope_freqs, const float* alpha_bars_host, int num_timesteps,
-                         const float* x_T, const float* ms2_cond, const float* ms1_cond, int auto_normalize, int pred_type,
-                         const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise, float* traj_x, float* traj_eps,
-                         int use_graph, void* workspace, int64_t workspace_bytes, int B, int RT, void* stream, float eta,
-                         const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0, int group_size, int consistency,
-                         float strength);
+
+/* ---- DDIMDiffusionModel.sample (model.py:293-324): one sampling call, one record -----------------------
+ * Runs the whole strided loop natively over timesteps_host[num_steps]: each step = network forward + update, then the epilogue
+ * (model.py:319-322): out_x = denoised in [0, 1], out_noise = mixture - denoised.  The call crosses the ABI as the record below; both
+ * networks' entries read the same one.  The caller sets struct_bytes = sizeof(dq_sample_call), the required fields, and leaves every
+ * option it does not use at its "off" value (a zero-initialised record with group_size = 1 has every option off): the call is then the
+ * reference's loop, the default update riding in the network's last launch.  Options combine freely except where a refusal says
+ * otherwise.  The entry synchronises the stream twice on entry (its host-side tables must be on the device before the caller's arrays go
+ * out of scope, and a capture must not see pending copies).
+ * Refused, in this order and before anything touches the device: a NULL record; struct_bytes != sizeof(dq_sample_call) (the message
+ * names both sizes; no other field is read before it); a NULL required argument; then each field's own refusals in the order of the
+ * fields' paragraphs below (eta, sampler and what it combines with, the timesteps' order, the seed, pred_type, guidance_scale, the
+ * per-window options); the per-window scratch; B, RT, num_steps; the group options; last the workspace size and num_timesteps. */
+typedef struct dq_sample_call {
+  int32_t struct_bytes;            /* sizeof(dq_sample_call) */
+  const float* alpha_bars_host;    /* num_timesteps HOST floats (DDIMDiffusionModel.alpha_bars); every timestep must lie in [0, num_timesteps) */
+  int32_t num_timesteps;           /* >= 1 */
+  const float* x_T;                /* (B, RT, MZ), not modified; NULL (needs seed_dev): drawn, dq_randn at draw index 0 */
+  const float* ms2_cond;           /* (B, RT, MZ) the mixture */
+  const float* ms1_cond;           /* (B, RT, M1) the U-Net's, (B, S2) the transformer's */
+  int32_t auto_normalize;
+  int32_t pred_type;               /* DQ_PRED_EPS, DQ_PRED_X0; dq_ddim_sample also DQ_PRED_V (traj_eps then holds the derived eps); else "Unknown pred_type" */
+  const int32_t* timesteps_host;   /* num_steps HOST ints; the caller forms them as trunc(linspace(T-1, 0, num_steps)), model.py:313 */
+  int32_t num_steps;               /* 1 .. 1024 */
+  float* out_x;
+  float* out_noise;
+  /* traj_x / traj_eps (nullable; off: NULL): (num_steps, B, RT, MZ) per-step x_{t-1} and eps (the derived eps where the network predicts
+   * x0 or v or x0 is clamped; the guided eps under guidance; (x - sa x0') / sb over groups) */
+  float* traj_x;
+  float* traj_eps;
+  /* use_graph != 0 and no trajectory: one step is captured into a hipGraph, cached on the handle (by params, workspace, shape, objective,
+   * update kind, clip value, and every live option's values) and replayed num_steps times; the conditions, seed and ids are staged inside
+   * the workspace, the step index lives on the device. */
+  int32_t use_graph;
+  void* workspace;                 /* dq_unet_workspace_bytes(plan, guided ? 2 * B : B, RT, 0) / dq_tfm_sample_workspace_bytes bytes */
+  int64_t workspace_bytes;
+  int32_t B;
+  int32_t RT;                      /* the transformer's S1 */
+  void* stream;
+  /* eta (off: 0): the DDIM eta (Song et al. 2021, eq. 16; 1: ancestral DDPM-like sampling), 0 <= eta <= 1.
+   * eta > 0: the update runs as dq_ddim_step_sto behind the forward (one more launch per step) and needs seed_dev; step i draws at index
+   * 1 + i.  seed_dev (1 uint64) and window_ids_dev (B int64; NULL: 0 .. B-1) are DEVICE memory (off: NULL both).  Graphs captured with
+   * eta > 0 and eta == 0 are cached apart, the value of eta itself lives in the coefficient tables. */
+  float eta;
+  const uint64_t* seed_dev;
+  const int64_t* window_ids_dev;
+  /* sampler (off: DQ_SAMPLER_REFERENCE = 0) and clip_x0 (off: <= 0 or NaN).  DQ_SAMPLER_DDIM with the clamp off runs
+   * the reference's kernels and captured graph over the strided table.  DQ_SAMPLER_DPMPP_2M, and DQ_SAMPLER_DDIM with clip_x0 > 0
+   * (first-order rows), run dq_solver_step behind the forward (one more launch per step), x in place and the x0 history in the
+   * workspace.  Refused: an unknown sampler, eta > 0 with DQ_SAMPLER_DPMPP_2M or with clip_x0 > 0, clip_x0 > 0 with DQ_SAMPLER_REFERENCE,
+   * timesteps that do not strictly decrease (samplers 1, 2). */
+  int32_t sampler;
+  float clip_x0;
+  /* guided (off: 0): sampling from g = u + w (c - u) with guidance_scale = w (finite, >= 0) and the null's raw MS1
+   * value null_ms1; both are ignored at guided == 0.  The arena and the forward run at 2 B windows -- rows [0, B) carry ms1_cond, rows
+   * [B, 2B) null_ms1 in every element; both see the same mixture and the same x -- so the workspace is that of 2 * B windows.  One
+   * forward and one update launch per step: the update runs behind the forward (never in the head launch) in its guided form
+   * (dq_guided_update) over the B windows of the first half and keeps the second half's x equal to the first's.  x_T, the outputs and
+   * the trajectories are B windows.  w = 1 is the conditional model at twice the cost: callers wanting that leave guided at 0. */
+  int32_t guided;
+  float guidance_scale;
+  float null_ms1;
+  /* The per-window options (off: guidance_rescale == 0 and threshold_quantile == 0; NaN counts as set):
+   * guidance_rescale = phi in [0, 1] (without `guided` a no-op: g = c, m = 1), threshold_quantile = q in (0, 1] and threshold_max >= the
+   * floor (not looked at when both are 0).  With either live, every step runs the statistics launches between the forward and the update
+   * (rescale: 2; threshold: 5 -- four radix passes and the fold), inside the captured step too, and the update in its per-window form
+   * behind the forward; thresholding selects the update clip_x0 selects and is refused exactly where clip_x0 is (DQ_SAMPLER_REFERENCE,
+   * eta > 0).  stat_scratch (dq_sample_stat_scratch_bytes(B, RT * MZ) bytes; nullable with both off) holds the table, the partials and
+   * the histograms at fixed addresses. */
+  double guidance_rescale;
+  float threshold_quantile;
+  float threshold_max;
+  void* stat_scratch;
+  int64_t stat_scratch_bytes;
+  /* Sampling over groups (off: consistency == DQ_CONSIST_NONE, group_size 1 -- the other two are then ignored):
+   * group_size = P in [1, 8] dividing B, consistency a DQ_CONSIST_* mode, consistency_strength in (0, 1].  Every step runs the forward,
+   * then the pass above in place on the network output, then the update in its x0-objective form over x0' behind the forward, whatever
+   * the network's objective: the projected estimate enters x_prev, the 2M history and the derived eps; clip_x0 clamps after the
+   * projection.  Refused: group_size outside [1, 8], B % group_size != 0, an unknown mode, a strength outside (0, 1] or NaN; and, first
+   * of them, consistency together with `guided` or a live per-window option -- not implemented (follow-up: the guided form of the group
+   * pass, which needs the mirror half written, and the per-window statistics over projected estimates). */
+  int32_t group_size;
+  int32_t consistency;
+  float consistency_strength;
+} dq_sample_call;
+/* The U-Net's only sampling entry (x_T (B, RT, MZ), mz the plan's).  The captured step is cached in the plan. */
+int dq_ddim_sample(dq_plan* plan, const float* params, const float* rope_freqs, const dq_sample_call* call);
+/* Test hook: the record's layout as this library was compiled -- sizeof(dq_sample_call), then (offsetof, size) of every field in
+ * declaration order -- so that a binding's mirror can be checked on any machine without a compiler.  Returns the number of ints written
+ * (1 + 2 * fields), or -1 when cap is smaller. */
+int dq_debug_sample_call_layout(int32_t* out, int cap);
 
 /* ---- batch formation from an HBM-resident dataset (the step right before the hot path) ------------
  * Replaces, for B (window 1, window 2) pairs, DIAMSDataset.__getitem__'s min-max normalisation (utils/data_loader.py:70-79:
@@ -580,13 +580,13 @@ int dq_mix_batch(const float* ms2_data, const float* ms1_data, int64_t n_windows
                  float* ms2_rest, float* weights_out, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* Group mixtures (csrc/k_mix.hip; additive at ABI version 12): dq_mix_batch's rule for G groups.  A group is ONE
- * mixture of count[g] components whose first P are the members that joint sampling (dq_ddim_sample_joint, group_size = P) is asked for:
+ * mixture of count[g] components whose first P are the members that joint sampling (dq_ddim_sample, group_size = P) is asked for:
  * 1 <= P <= K, K in 2..8.  Arguments as dq_mix_batch with G in place of B, plus P.  idx_dev (K, G): rows 0 .. P-1 are the members.  A group
  * whose count lies outside [P, K], or that uses an index outside [0, n_windows), is never dereferenced: every output of it is NaN, and no
  * output of another group is affected.  MS2 lo / hi over all present components (symmetric in the members); the weights are exactly
  * dq_mix_batch's, drawn or fixed, keyed by (seed, id, draw, j) with id = window_ids_dev[g] (NULL: g); MS1 of member p is normalised by that
  * member's own lo / hi -- what the member would see as the target of its own window.
- * Outputs (device), member-major -- member p of group g is row p * G + g, the layout dq_ddim_sample_joint takes:
+ * Outputs (device), member-major -- member p of group g is row p * G + g, the layout dq_ddim_sample takes over groups:
  *   ms2_cond    (P*G, RT, MZ)  the mixture ((n_0 w_0 + n_1 w_1) + ...), written to all P member slices (the network reads every row)
  *   ms2_target  (P*G, RT, MZ)  n_p, or under scale_target the product n_p w_p that entered the mixture
  *   ms1_target  (P*G, ms1_per_window)
@@ -755,7 +755,7 @@ enum { DQ_TFM_ATTN_GEMM = 0, DQ_TFM_ATTN_FUSED = 1 };
 int dq_tfm_attn_form(int S1, int Sk, int dh);
 int dq_tfm_attn_fwd(const float* q, const float* kv, float* o, float* prob_scratch, int B, int S1, int Sk, int H, int heads, int form,
                     void* stream);
-/* Sampling from the transformer in one call (csrc/dq_tfm_sample.hip): dq_ddim_sample_solver's loop -- the same
+/* Sampling from the transformer in one call (csrc/dq_tfm_sample.hip): dq_ddim_sample's loop -- the same record, the same
  * tables, updates, draw indexing (x_T at 0, step i at 1 + i), refusals (worded alike, before anything touches the device) and final
  * un-normalisation -- around a sampling forward of this network; the same code, not a copy (csrc/dq_sampler.h: the captured step and the
  * eager steps take the network's forward as a callable).  x_T (B, S1, input_dim; NULL: drawn from the seed), ms2_cond like x_T (the
@@ -763,13 +763,12 @@ int dq_tfm_attn_fwd(const float* q, const float* kv, float* o, float* prob_scrat
  * (2c - 1 first when auto_normalize), every layer's K | V rows of it, and the time embedding of every step; a step then projects only the x_t
  * rows and runs the attention by dq_tfm_attn_form.  use_graph != 0 without trajectories: one step is captured once, cached on the handle
  * (dropped by dq_tfm_set_precision and dq_tfm_destroy) and replayed num_steps times; seed and ids are staged in the workspace.
- * workspace: dq_tfm_sample_workspace_bytes(tfm, B, S1, S2, num_steps) bytes, 16-byte aligned. */
+ * workspace: dq_tfm_sample_workspace_bytes(tfm, B, S1, S2, num_steps) bytes, 16-byte aligned.  call->RT is S1.  eta, seed, ids, the sampler
+ * and clip_x0 are served; `guided`, a live per-window option and consistency != DQ_CONSIST_NONE are refused (not built for this network
+ * yet), behind the refusals the shared checks make and in front of the size checks -- never silently ignored. */
 int64_t dq_tfm_sample_workspace_bytes(const dq_tfm* tfm, int B, int S1, int S2, int num_steps);
-int dq_tfm_sample(dq_tfm* tfm, const float* params, const float* rope_sin, const float* rope_cos, const float* time_freqs,
-                  const float* alpha_bars_host, int num_timesteps, const float* x_T, const float* ms2_cond, const float* ms1_cond,
-                  int auto_normalize, int pred_type, const int32_t* timesteps_host, int num_steps, float* out_x, float* out_noise,
-                  float* traj_x, float* traj_eps, int use_graph, void* workspace, int64_t workspace_bytes, int B, int S1, int S2,
-                  void* stream, float eta, const uint64_t* seed_dev, const int64_t* window_ids_dev, int sampler, float clip_x0);
+int dq_tfm_sample(dq_tfm* tfm, const float* params, const float* rope_sin, const float* rope_cos, const float* time_freqs, int S2,
+                  const dq_sample_call* call);
 /* Held-out evaluation of the transformer in one call per batch (csrc/dq_tfm_sample.hip, csrc/k_stream.hip, DESIGN.md sections 31 and 36;
  * additive at ABI version 12): dq_eval_step's semantics for `repeats` = R repeats of a batch of B windows stacked into N = R * B samples,
  * sample n = r * B + b (repeat-major), through ONE forward -- dq_tfm_sample's prologue and forward, the same code.

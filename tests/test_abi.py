@@ -31,7 +31,68 @@ def test_header_symbols_exported_and_bound():
         assert name in N.PROTOTYPES, f"{name} has no ctypes prototype"
         assert len(N.PROTOTYPES[name][1]) == nargs, f"{name}: header has {nargs} parameters, binding {len(N.PROTOTYPES[name][1])}"
     assert set(N.PROTOTYPES) == set(decl), set(N.PROTOTYPES) ^ set(decl)
-    assert lib.dq_abi_version() == N.ABI_VERSION == 12  # DQ_ABI_VERSION in include/dq_hip.h
+    assert lib.dq_abi_version() == N.ABI_VERSION == 13  # DQ_ABI_VERSION in include/dq_hip.h
+
+
+def record_fields():
+    """the field names of the header's ``dq_sample_call`` typedef, in declaration order"""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = re.search(r"typedef struct dq_sample_call \{(.*?)\} dq_sample_call;", src, flags=re.S).group(1)
+    return [re.search(r"(\w+)$", decl.strip()).group(1) for decl in body.split(";") if decl.strip()]
+
+
+def test_sample_call_layout_is_the_librarys():
+    """``_native.SampleCall`` against ``dq_debug_sample_call_layout``: the total size, every field's offset and size, and the header's
+    field names in order -- the check of the binding that needs no compiler"""
+    from dquartic import _native as N
+
+    size, fields = N.sample_call_layout()
+    names = [k for k, _ in N.SampleCall._fields_]
+    assert names == record_fields() and names[0] == "struct_bytes" and len(names) == 36
+    assert size == ctypes.sizeof(N.SampleCall)
+    assert fields == [(getattr(N.SampleCall, k).offset, getattr(N.SampleCall, k).size) for k in names]
+    # fixed-width members only: 4-byte ints and floats, 8-byte pointers, int64 sizes and the one double
+    assert all(n in (4, 8) for _, n in fields) and dict(zip(names, fields))["workspace_bytes"][1] == 8
+    assert dict(N.SampleCall._fields_)["guidance_rescale"] is ctypes.c_double and dict(N.SampleCall._fields_)["struct_bytes"] is ctypes.c_int32
+    lib = N.lib()
+    small = (ctypes.c_int32 * 8)()
+    assert lib.dq_debug_sample_call_layout(small, 8) == -1 and lib.dq_debug_sample_call_layout(None, 128) == -1
+
+
+def test_sample_call_defaults():
+    """``sample_call()``: struct_bytes set, every option at its off value (eta 0, null seed and ids, sampler 0, clip 0, guided 0, rescale
+    and quantile 0, DQ_CONSIST_NONE with group_size 1), every other field zero; an unknown keyword raises"""
+    from dquartic import _native as N
+
+    q = N.sample_call()
+    got = {k: getattr(q, k) for k, _ in N.SampleCall._fields_}
+    want = {k: (None if t is ctypes.c_void_p else 0) for k, t in N.SampleCall._fields_}
+    want.update(struct_bytes=ctypes.sizeof(N.SampleCall), group_size=1)
+    assert got == want
+    assert (q.eta, q.seed_dev, q.window_ids_dev, q.sampler, q.clip_x0, q.guided, q.guidance_rescale, q.threshold_quantile, q.consistency,
+            q.group_size) == (0.0, None, None, 0, 0.0, 0, 0.0, 0.0, 0, 1)
+    q = N.sample_call(B=3, eta=0.5, x_T=4096, seed_dev=None, guidance_rescale=0.1)
+    assert (q.B, q.eta, q.x_T, q.seed_dev, q.guidance_rescale, q.group_size) == (3, 0.5, 4096, None, 0.1, 1)
+    with pytest.raises(AttributeError, match="no field 'strength'"):
+        N.sample_call(strength=1.0)
+
+
+def test_a_record_of_another_size_is_refused_first():
+    """both entries: a null record, then struct_bytes off by 4 either way, refused with both sizes in the message before any other field
+    or argument is looked at (every other pointer is null here: the null-argument refusal would be next)"""
+    from dquartic import _native as N
+
+    lib, size = N.lib(), ctypes.sizeof(N.SampleCall)
+    entries = {"dq_ddim_sample": lambda q: lib.dq_ddim_sample(None, None, None, q),
+               "dq_tfm_sample": lambda q: lib.dq_tfm_sample(None, None, None, None, None, 0, q)}
+    for who, entry in entries.items():
+        assert entry(None) != 0 and lib.dq_last_error().startswith(f"{who}: null argument (call) [".encode())
+        for off in (-4, 4):
+            q = N.sample_call(struct_bytes=size + off)
+            assert entry(ctypes.byref(q)) != 0
+            err = lib.dq_last_error().decode()
+            assert err.startswith(f"{who}: call->struct_bytes is {size + off}, sizeof(dq_sample_call) of this library is {size}"), err
+        assert entry(ctypes.byref(N.sample_call())) != 0 and lib.dq_last_error().startswith(f"{who}: null argument [".encode())  # the next
 
 
 def test_plan_layout_without_a_gpu():

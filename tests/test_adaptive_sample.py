@@ -1,5 +1,5 @@
 """Rescaled guidance and dynamic x0 thresholding through the whole sampler: ``sample(..., guidance_rescale=phi,
-threshold_quantile=q, threshold_max=cap)`` = ``dq_ddim_sample_adaptive`` on the small network of tests/test_guided_sample.py, 4 steps.
+threshold_quantile=q, threshold_max=cap)`` = ``dq_ddim_sample`` with its per-window fields on the small network of tests/test_guided_sample.py, 4 steps.
 
 Trajectory: tests/test_guided_sample.py's construction -- per step, from the GPU's own previous state, the float64 oracle network under the
 caller's MS1 and under the null, then the step in float64 -- with the two steps added: m_b from the population standard deviations of a
@@ -294,13 +294,14 @@ def test_the_scratch_between_canaries():
     flat = net.read_params()
     ts_c = (ctypes.c_int32 * NS)(*dm.sampler_timesteps(T, NS).to(torch.int32).tolist())
     out, noise = torch.empty_like(a), torch.empty_like(a)
-    f = ctypes.c_float
 
     def call(nbytes, graph):
-        return N.lib().dq_ddim_sample_adaptive(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), dm._alpha_bars_host(), T, N.ptr(x), N.ptr(a), N.ptr(c1),
-                                               1, 0, ts_c, NS, N.ptr(out), N.ptr(noise), None, None, graph, N.ptr(ws), ws.numel(), B, RT,
-                                               N.stream_ptr(), f(0.0), None, None, 2, f(0.0), 1, f(3.0), f(NULL), ctypes.c_double(0.7), f(0.9),
-                                               f(float("inf")), ctypes.c_void_p(buf.data_ptr() + 256), nbytes)
+        q = N.sample_call(alpha_bars_host=ctypes.addressof(dm._alpha_bars_host()), num_timesteps=T, x_T=N.ptr(x), ms2_cond=N.ptr(a), ms1_cond=N.ptr(c1),
+                          auto_normalize=1, pred_type=0, timesteps_host=ctypes.addressof(ts_c), num_steps=NS, out_x=N.ptr(out), out_noise=N.ptr(noise),
+                          use_graph=graph, workspace=N.ptr(ws), workspace_bytes=ws.numel(), B=B, RT=RT, stream=N.stream_ptr(), sampler=2, guided=1,
+                          guidance_scale=3.0, null_ms1=NULL, guidance_rescale=0.7, threshold_quantile=0.9, threshold_max=float("inf"),
+                          stat_scratch=buf.data_ptr() + 256, stat_scratch_bytes=nbytes)
+        return N.lib().dq_ddim_sample(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), ctypes.byref(q))
 
     assert call(need - 1, 0) != 0 and b"scratch too small" in N.lib().dq_last_error()
     with torch.no_grad():

@@ -1,5 +1,5 @@
 """Classifier-free guidance on MS1, everything that needs no device: the refusals of ``dq_guided_update``,
-``dq_ms1_cond_drop`` and ``dq_ddim_sample_guided`` (dummy pointers, never dereferenced: each refusal names its reason and nothing is
+``dq_ms1_cond_drop`` and ``dq_ddim_sample`` with the guidance fields (dummy pointers, never dereferenced: each refusal names its reason and nothing is
 launched), the Python surface's refusals, the train config's ``model.cond_drop_prob``, the unchanged ``generate-config`` output and
 checkpoint key set, and this file's numpy transcription of the drop rule of ``k_cond_drop`` (over the Philox transcription of
 tests/test_stochastic_sampler.py), which the GPU tests compare the kernel with.
@@ -97,24 +97,24 @@ def test_native_refusals_come_before_the_device():
     plan = lib.dq_plan_create(4, 2, dims, 8, 1000)
     assert plan
     try:
-        from test_sampler_tables import alpha_bars
+        from test_sampler_tables import alpha_bars, dummy_record
 
         ab = alpha_bars("cosine")
         ab_c = (ctypes.c_float * len(ab))(*ab.tolist())
 
         def call(ts=(999, 0), eta=0.0, sampler=0, clip=0.0, w=2.0, params=d):
             ts_c = (ctypes.c_int32 * len(ts))(*ts)
-            return lib.dq_ddim_sample_guided(plan, params, d, ab_c, len(ab), d, d, d, 1, 0, ts_c, len(ts), d, d, None, None, 0, d, 1 << 40, 1, 8,
-                                             None, f(eta), d, None, sampler, f(clip), f(w), f(0.0))
+            q = dummy_record(ab_c, ts_c, eta=eta, sampler=sampler, clip_x0=clip, guided=1, guidance_scale=w)
+            return lib.dq_ddim_sample(plan, params, d, ctypes.byref(q))
 
-        # sampler_check's refusals, in its order, under this entry's name; then the scale
+        # sampler_check's refusals, in its order, under the entry's name; then the scale
         for kw, word in ((dict(params=None), b"null argument"), (dict(eta=1.5), b"eta must satisfy"), (dict(sampler=7), b"unknown sampler"),
                          (dict(eta=0.5, sampler=2), b"eta must be 0"), (dict(clip=1.0), b"clip_x0 needs the ddim"),
                          (dict(ts=(999, 999), sampler=1), b"strictly decreasing"), (dict(w=-1.0), b"guidance scale"),
                          (dict(w=float("nan")), b"guidance scale"), (dict(w=float("inf")), b"guidance scale")):
             assert call(**kw) != 0, kw
             err = lib.dq_last_error()
-            assert word in err and b"dq_ddim_sample_guided" in err, (kw, err)
+            assert word in err and err.startswith(b"dq_ddim_sample: "), (kw, err)
         assert call(sampler=7, w=-1.0) != 0 and b"unknown sampler" in lib.dq_last_error()  # (the sampler's refusal comes first)
         # the workspace a guided call needs is the unguided one of twice the batch; the entry point for it is unchanged
         assert lib.dq_unet_workspace_bytes(plan, 6, 4, 0) > lib.dq_unet_workspace_bytes(plan, 3, 4, 0) > 0

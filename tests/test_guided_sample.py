@@ -1,5 +1,5 @@
 """Classifier-free guidance through the whole sampler and the training loop: ``sample(..., guidance_scale=w)`` =
-``dq_ddim_sample_guided`` against a float64 oracle built here from ``oracle/dq_oracle.py`` -- two ``Diffusion.net`` calls per step (the
+``dq_ddim_sample`` with its guidance fields against a float64 oracle built here from ``oracle/dq_oracle.py`` -- two ``Diffusion.net`` calls per step (the
 caller's MS1, and the null's constant), g = u + w (c - u), then the update as the existing sampler tests restate it -- and conditioning
 dropout in ``_train_one_batch`` / ``TrainStepGraph`` against ``train_step_fused`` on MS1 dropped by hand with the transcription of
 tests/test_guidance_host.py.
@@ -308,9 +308,10 @@ def test_workspace_rule():
     out, noise = torch.empty_like(a), torch.empty_like(a)
 
     def call(nbytes, w=3.0):
-        return N.lib().dq_ddim_sample_guided(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), dm._alpha_bars_host(), T, N.ptr(x), N.ptr(a), N.ptr(b),
-                                             1, 0, ts_c, NS, N.ptr(out), N.ptr(noise), None, None, 0, N.ptr(ws), nbytes, B, RT, N.stream_ptr(),
-                                             ctypes.c_float(0.0), None, None, 0, ctypes.c_float(0.0), ctypes.c_float(w), ctypes.c_float(NULL))
+        q = N.sample_call(alpha_bars_host=ctypes.addressof(dm._alpha_bars_host()), num_timesteps=T, x_T=N.ptr(x), ms2_cond=N.ptr(a), ms1_cond=N.ptr(b),
+                          auto_normalize=1, pred_type=0, timesteps_host=ctypes.addressof(ts_c), num_steps=NS, out_x=N.ptr(out), out_noise=N.ptr(noise),
+                          workspace=N.ptr(ws), workspace_bytes=nbytes, B=B, RT=RT, stream=N.stream_ptr(), guided=1, guidance_scale=w, null_ms1=NULL)
+        return N.lib().dq_ddim_sample(net._plan, N.ptr(flat), N.ptr(net.rope_freqs()), ctypes.byref(q))
 
     assert call(need - 4) != 0 and b"workspace too small" in N.lib().dq_last_error()
     assert call(N.lib().dq_unet_workspace_bytes(net._plan, B, RT, 0)) != 0  # the unguided size is not enough

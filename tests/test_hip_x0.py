@@ -145,7 +145,11 @@ def test_unknown_pred_type_rejected():
     with pytest.raises(ValueError, match="Unknown pred_type"):
         DDIMDiffusionModel(model_class=net, pred_type="v", device="cuda")
     # the C ABI rejects an unknown enum value too (no silent default)
-    rc = N.lib().dq_ddim_sample(None, None, None, None, 1000, None, None, None, 1, 7, None, 1, None, None, None, None, 0, None, 0, 1, 1, None)
-    assert rc != 0
+    ab, ts = (ctypes.c_float * 4)(0.9, 0.8, 0.7, 0.6), (ctypes.c_int32 * 1)(3)
+    q = N.sample_call(alpha_bars_host=ctypes.addressof(ab), num_timesteps=4, x_T=4096, ms2_cond=4096, ms1_cond=4096, auto_normalize=1, pred_type=7,
+                      timesteps_host=ctypes.addressof(ts), num_steps=1, out_x=4096, out_noise=4096, workspace=4096, workspace_bytes=1 << 40, B=1, RT=1)
+    d = ctypes.c_void_p(4096)  # (dummy pointers, never dereferenced: the objective is what is refused)
+    rc = N.lib().dq_ddim_sample(d, d, d, ctypes.byref(q))
+    assert rc != 0 and b"dq_ddim_sample: Unknown pred_type" in N.lib().dq_last_error()
     assert isinstance(N.lib().dq_last_error(), (bytes, type(None)))
     assert ctypes.c_int(N.lib().dq_abi_version()).value == N.ABI_VERSION

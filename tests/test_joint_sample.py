@@ -1,4 +1,4 @@
-"""``dq_ddim_sample_joint``, ``sample(group_size=, consistency=)``, ``deconvolve_run_joint`` and ``dquartic deconvolve --joint`` on the GPU
+"""``dq_ddim_sample`` over groups, ``sample(group_size=, consistency=)``, ``deconvolve_run_joint`` and ``dquartic deconvolve --joint`` on the GPU
 (DESIGN.md section 40).
 
 Network: the small one of tests/test_deconvolve_gpu.py (dim_mults = (1, 2), downsample_dim = 8), every parameter moved off its init, one
@@ -9,7 +9,7 @@ What the call IS: with ``return_trajectory`` every step equals, bit for bit, ``d
 in place on its output, then the stand-alone update of the sampler's kind at DQ_PRED_X0 over the projected estimate -- ``dq_ddim_step_x0``
 (eta = 0), ``dq_ddim_step_sto`` (eta = 1), ``dq_solver_step`` with a history (dpmpp_2m) -- over the rows of the sampler's own table;
 ``traj_eps`` is that update's derived eps.  Then: captured == eager, repeat == repeat, a mixture nothing reaches leaves the plain call's bits
-(x0 objective, bound), consistency = 0 is ``dq_ddim_sample_v`` in result and launch count, and the members' positive parts end within the
+(x0 objective, bound), consistency = 0 is the call without the group fields in result and launch count, and the members' positive parts end within the
 mixture."""
 import ctypes
 import json
@@ -223,7 +223,7 @@ def test_consistency_0_is_dq_ddim_sample_v(pred):
     dm = model(pred)
     xT, c2, c1 = inputs(0.6)
     for kw, extra in ((dict(), 2), (dict(sampler=2), 1)):
-        v = lambda: dm._sample_native(xT, c2, c1, NS, eta=0.0, **kw)[0]                                    # noqa: E731  (dq_ddim_sample_v / _solver)
+        v = lambda: dm._sample_native(xT, c2, c1, NS, eta=0.0, **kw)[0]                                    # noqa: E731  (the call without the group fields)
         off = lambda: dm._sample_native(xT, c2, c1, NS, eta=0.0, joint=(7, 0, float("nan")), **kw)[0]     # noqa: E731
         on = lambda: dm._sample_native(xT, c2, c1, NS, eta=0.0, joint=(P, 1, 1.0), **kw)[0]               # noqa: E731
         for graph in (True, False):

@@ -6,9 +6,10 @@ tests do not see is the two in one process, one after the other:
   * a handle destroyed with a live graph and capture stream, and the same model built again from the same seed: the same result.
 Models: test_stochastic_sampler's U-Net at batch 2 and test_tfm_sample's "two_layers" transformer, 3 steps each.
 
-Without a GPU: which entry ``DDIMDiffusionModel._sample_native`` reaches for (eta, sampler), over a recorder in place of the library -- the
-three take one argument list (the first 22 arguments), which is what lets test_sample_ex_eta0_is_dq_ddim_sample compare two entries; and
-likewise for guidance, the v objective and the per-window options, each reaching its entry with exactly its list.  The options that are
+Without a GPU: what ``DDIMDiffusionModel._sample_native`` writes into the call's record (``dq_sample_call``) for (eta, sampler), over a
+recorder in place of the library -- the fields that are no option are the same in every call, which is what lets
+test_sample_ex_eta0_is_dq_ddim_sample compare two calls; and likewise for guidance, the v objective and the per-window options, each
+setting exactly its own fields and leaving every other option at its off value.  The options that are
 not at their defaults: one rule (``SampleOptions.non_default``) under ``_sampler_kwargs``, ``evaluate``'s report and the command line."""
 import ctypes
 import gc
@@ -87,24 +88,58 @@ def test_handles_die_with_a_live_graph():
 
 
 class _Recorder:
-    """stands in for the library: a sampling entry returns 0 and leaves its name and arguments.  Anything else is a handle of an earlier test
-    that the collector frees meanwhile: that goes to the library the handle came from"""
+    """stands in for the library: a sampling entry returns 0 and leaves ``(name, fields)`` -- the record it received, field by name as it
+    stood at the call (pointers as integers or None), with ``_head`` (the network's own arguments in front of the record) and
+    ``_timesteps`` (the host list behind ``timesteps_host``).  Anything else is a handle of an earlier test that the collector frees
+    meanwhile: that goes to the library the handle came from"""
 
     def __init__(self, real):
         self.calls, self.real = [], real
 
     def __getattr__(self, name):
-        if not name.startswith("dq_ddim_sample"):
+        if not (name.startswith("dq_ddim_sample") or name == "dq_tfm_sample"):
             return getattr(self.real(), name)
-        return lambda *args: self.calls.append((name, args)) or 0
+
+        def entry(*args):
+            q = args[-1]._obj
+            fields = {k: getattr(q, k) for k, _ in type(q)._fields_}
+            fields["_head"] = [_plain(v) for v in args[:-1]]
+            fields["_timesteps"] = list((ctypes.c_int32 * q.num_steps).from_address(q.timesteps_host))
+            self.calls.append((name, fields))
+            return 0
+        return entry
 
 
 def _plain(v):
     if isinstance(v, ctypes.c_void_p):
         return ("ptr", v.value)
-    if isinstance(v, ctypes.Array):
-        return (type(v)._type_, list(v))
     return v
+
+
+# every option of the record by the group it belongs to, at its off value (include/dq_hip.h)
+OPTIONS_OFF = {
+    "noise": dict(eta=0.0, seed_dev=None, window_ids_dev=None),
+    "sampler": dict(sampler=0, clip_x0=0.0),
+    "guided": dict(guided=0, guidance_scale=0.0, null_ms1=0.0),
+    "per_window": dict(guidance_rescale=0.0, threshold_quantile=0.0, threshold_max=0.0, stat_scratch=None, stat_scratch_bytes=0),
+    "joint": dict(group_size=1, consistency=0, consistency_strength=0.0),
+}
+ALLOCATED = ("out_x", "out_noise", "traj_x", "traj_eps", "timesteps_host")  # what a call allocates itself (the list's values: _timesteps)
+
+
+def _options(fields, **live):
+    """the record's option fields are exactly ``live`` (group -> its fields' values) and, in every other group, the off values"""
+    assert set(live) <= set(OPTIONS_OFF)
+    for group, off in OPTIONS_OFF.items():
+        want = live.get(group, off)
+        assert set(want) == set(off), group
+        assert {k: fields[k] for k in off} == want, (group, {k: fields[k] for k in off})
+
+
+def _shared(fields):
+    """what every call of one model on the same inputs fills alike: all but the options and what a call allocates"""
+    opt = {k for off in OPTIONS_OFF.values() for k in off}
+    return {k: v for k, v in fields.items() if k not in opt and k not in ALLOCATED}
 
 
 def _host_model(monkeypatch, pred="x0"):
@@ -129,14 +164,9 @@ def _host_model(monkeypatch, pred="x0"):
     return rec, dm, inputs, stat
 
 
-def _shared_22(args):
-    """the first 22 arguments as test_entry_choice compares them: all but the two outputs a call allocates"""
-    return [_plain(args[i]) for i in range(22) if i not in (12, 13)]
-
-
 def test_entry_choice_guided_and_per_window(monkeypatch):
-    """guidance -> dq_ddim_sample_guided (+ scale, null_ms1: 29 arguments); a live per-window option -> dq_ddim_sample_adaptive (35:
-    dq_ddim_sample_v's list, then phi, q, cap, scratch, its size), guided or not; the first 22 are the default call's"""
+    """every call reaches dq_ddim_sample; guidance sets (guided, scale, null_ms1), a live per-window option (phi, q, cap, the scratch and
+    its size), guided or not; every option that is not live holds its off value, and what is not an option is the default call's"""
     rec, dm, inputs, stat = _host_model(monkeypatch)
     INF = float("inf")
     keep = [dm._sample_native(*inputs, STEPS),
@@ -144,38 +174,41 @@ def test_entry_choice_guided_and_per_window(monkeypatch):
             dm._sample_native(*inputs, STEPS, eta=0.0, guidance=(0.5, 0.0)),
             dm._sample_native(*inputs, STEPS, eta=0.0, sampler=1, clip_x0=1.5, guidance=(3.0, 0.25), adaptive=(0.7, 0.5, 2.0)),
             dm._sample_native(*inputs, STEPS, eta=0.0, sampler=2, adaptive=(0.0, 0.5, INF))]
-    scratch = [("ptr", stat.data_ptr()), stat.numel()]
-    want = [("dq_ddim_sample", []),
-            ("dq_ddim_sample_guided", [0.0, None, None, 1, 1.5, 3.0, 0.25]),
-            ("dq_ddim_sample_guided", [0.0, None, None, 0, 0.0, 0.5, 0.0]),
-            ("dq_ddim_sample_adaptive", [0.0, None, None, 1, 1.5, 1, 3.0, 0.25, 0.7, 0.5, 2.0] + scratch),
-            ("dq_ddim_sample_adaptive", [0.0, None, None, 2, 0.0, 0, 1.0, 0.0, 0.0, 0.5, INF] + scratch)]
-    assert len(rec.calls) == len(want) == len(keep)
-    for (name, args), (entry, tail) in zip(rec.calls, want):
-        assert name == entry and len(args) == 22 + len(tail), (name, len(args))
-        assert [_plain(v) for v in args[22:]] == tail, name
-        assert _shared_22(args) == _shared_22(rec.calls[0][1]), name
-    assert [len(a) for _, a in rec.calls] == [22, 29, 29, 35, 35]
+    scratch = dict(stat_scratch=stat.data_ptr(), stat_scratch_bytes=stat.numel())
+    f32 = lambda v: ctypes.c_float(v).value  # noqa: E731  (phi travels as a double, the rest as floats)
+    want = [dict(),
+            dict(sampler=dict(sampler=1, clip_x0=1.5), guided=dict(guided=1, guidance_scale=3.0, null_ms1=0.25)),
+            dict(guided=dict(guided=1, guidance_scale=0.5, null_ms1=0.0)),
+            dict(sampler=dict(sampler=1, clip_x0=1.5), guided=dict(guided=1, guidance_scale=3.0, null_ms1=0.25),
+                 per_window=dict(guidance_rescale=0.7, threshold_quantile=0.5, threshold_max=2.0, **scratch)),
+            dict(sampler=dict(sampler=2, clip_x0=0.0), per_window=dict(guidance_rescale=0.0, threshold_quantile=0.5, threshold_max=INF, **scratch))]
+    assert len(rec.calls) == len(want) == len(keep) and f32(0.25) == 0.25
+    for (name, fields), live in zip(rec.calls, want):
+        assert name == "dq_ddim_sample", name
+        _options(fields, **live)
+        assert _shared(fields) == _shared(rec.calls[0][1]), live
 
 
 def test_entry_choice_v_prediction(monkeypatch):
-    """a v_prediction model reaches dq_ddim_sample_v with 30 arguments in all four forms -- plain, eta, sampler, guided: the solver's
-    list, the guided flag, then the scale and null_ms1 (1.0, 0.0 unguided); a seed travels as the device word, and is recorded"""
+    """a v_prediction model reaches dq_ddim_sample with pred_type DQ_PRED_V in all four forms -- plain, eta, sampler, guided -- and
+    nothing but the live options set; a seed travels as the device word, and is recorded"""
     from dquartic import _native as N
 
     rec, dm, inputs, _ = _host_model(monkeypatch, "v_prediction")
     keep = [dm._sample_native(*inputs, STEPS), dm._sample_native(*inputs, STEPS, eta=0.0), dm._sample_native(*inputs, STEPS, eta=0.0, sampler=2),
             dm._sample_native(*inputs, STEPS, eta=0.0, sampler=1, clip_x0=1.5, guidance=(3.0, 0.25))]
-    tails = [[0.0, None, None, 0, 0.0, 0, 1.0, 0.0], [0.0, None, None, 0, 0.0, 0, 1.0, 0.0], [0.0, None, None, 2, 0.0, 0, 1.0, 0.0],
-             [0.0, None, None, 1, 1.5, 1, 3.0, 0.25]]
+    lives = [dict(), dict(), dict(sampler=dict(sampler=2, clip_x0=0.0)),
+             dict(sampler=dict(sampler=1, clip_x0=1.5), guided=dict(guided=1, guidance_scale=3.0, null_ms1=0.25))]
     assert len(rec.calls) == len(keep) == 4
-    for (name, args), tail in zip(rec.calls, tails):
-        assert name == "dq_ddim_sample_v" and len(args) == 30
-        assert [_plain(v) for v in args[22:]] == tail
-        assert _shared_22(args) == _shared_22(rec.calls[0][1]) and args[9] == N.PRED_TYPES["v_prediction"]
+    for (name, fields), live in zip(rec.calls, lives):
+        assert name == "dq_ddim_sample"
+        _options(fields, **live)
+        assert _shared(fields) == _shared(rec.calls[0][1]) and fields["pred_type"] == N.PRED_TYPES["v_prediction"] == 2
     dm._sample_native(*inputs, STEPS, eta=0.5, seed=7)
-    args = rec.calls[-1][1]
-    assert len(args) == 30 and args[22] == 0.5 and isinstance(args[23], ctypes.c_void_p) and args[24] is None and dm.last_seed == 7
+    fields = rec.calls[-1][1]
+    assert fields["eta"] == 0.5 and isinstance(fields["seed_dev"], int) and fields["seed_dev"] != 0 and fields["window_ids_dev"] is None
+    assert dm.last_seed == 7
+    _options(fields, noise=dict(eta=0.5, seed_dev=fields["seed_dev"], window_ids_dev=None))
 
 
 def test_one_rule_for_the_options_that_are_not_at_their_defaults():
@@ -226,8 +259,8 @@ def test_one_rule_for_the_options_that_are_not_at_their_defaults():
 
 
 def test_entry_choice(monkeypatch):
-    """eta=None -> dq_ddim_sample, eta=0.0 -> dq_ddim_sample_ex (+ eta, seed, ids), sampler=1 -> dq_ddim_sample_solver (+ sampler, clip_x0);
-    the first 22 arguments of the three calls are the same"""
+    """eta=None, eta=0.0 and sampler=1 all reach dq_ddim_sample: the first two with every option off (eta 0, null seed and ids), the third
+    with (sampler, clip_x0) alone; what is not an option is the same in the three records"""
     from dquartic import _native as N
     from dquartic.model.model import DDIMDiffusionModel
 
@@ -247,24 +280,24 @@ def test_entry_choice(monkeypatch):
     keep.append(dm._sample_native(xT, c2, c1, STEPS))
     keep.append(dm._sample_native(xT, c2, c1, STEPS, eta=0.0))
     keep.append(dm._sample_native(xT, c2, c1, STEPS, eta=0.0, sampler=1, clip_x0=1.5))
-    assert [name for name, _ in rec.calls] == ["dq_ddim_sample", "dq_ddim_sample_ex", "dq_ddim_sample_solver"]
-    a0, a1, a2 = (args for _, args in rec.calls)
-    assert (len(a0), len(a1), len(a2)) == (22, 25, 27)
-    assert [_plain(v) for v in a1[22:]] == [0.0, None, None] and [_plain(v) for v in a2[22:]] == [0.0, None, None, 1, 1.5]
-    # the shared list: what the caller owns is the same object or address in all three, what a call allocates (out_x, out_noise) differs
-    own = [i for i in range(22) if i not in (12, 13)]
-    for other in (a1, a2):
-        assert [_plain(other[i]) for i in own] == [_plain(a0[i]) for i in own]
-        assert other[0] is a0[0] and other[3] is a0[3]  # the plan handle, the host schedule
-    want = [("ptr", 0xABC0), ("ptr", flat.data_ptr()), ("ptr", rope.data_ptr()), None, 50, ("ptr", xT.data_ptr()), ("ptr", c2.data_ptr()), None,
-            1, N.PRED_TYPES["x0"], (ctypes.c_int32, [49, 24, 0]), STEPS, None, None, None, None, 1, ("ptr", ws.data_ptr()), ws.numel(), B, RT,
-            ("ptr", 0x5EED)]
-    for i, w in enumerate(want):
-        if w is not None:
-            assert _plain(a0[i]) == w, i
-    for (x, n), args in zip(keep, (a0, a1, a2)):
-        assert (args[12].value, args[13].value) == (x.data_ptr(), n.data_ptr()) and args[14] is None and args[15] is None
+    assert [name for name, _ in rec.calls] == ["dq_ddim_sample"] * 3
+    a0, a1, a2 = (fields for _, fields in rec.calls)
+    _options(a0)
+    _options(a1)
+    _options(a2, sampler=dict(sampler=1, clip_x0=1.5))
+    # the shared fields: what the caller owns is the same value or address in all three, what a call allocates (out_x, out_noise) differs
+    assert _shared(a1) == _shared(a0) and _shared(a2) == _shared(a0)
+    want = dict(struct_bytes=ctypes.sizeof(N.SampleCall), alpha_bars_host=ctypes.addressof(dm._alpha_bars_host()), num_timesteps=50,
+                x_T=xT.data_ptr(), ms2_cond=c2.data_ptr(), auto_normalize=1, pred_type=N.PRED_TYPES["x0"], num_steps=STEPS, use_graph=1,
+                workspace=ws.data_ptr(), workspace_bytes=ws.numel(), B=B, RT=RT, stream=0x5EED, _timesteps=[49, 24, 0],
+                _head=[("ptr", 0xABC0), ("ptr", flat.data_ptr()), ("ptr", rope.data_ptr())])
+    assert set(_shared(a0)) == set(want) | {"ms1_cond"}  # (the staged MS1 is the call's own)
+    for k, w in want.items():
+        assert a0[k] == w, k
+    for (x, n), fields in zip(keep, (a0, a1, a2)):
+        assert (fields["out_x"], fields["out_noise"]) == (x.data_ptr(), n.data_ptr()) and fields["traj_x"] is None and fields["traj_eps"] is None
     # return_trajectory: the trajectories go in, the graph flag goes off
     x, n, tx, te = dm._sample_native(xT, c2, c1, STEPS, True, eta=0.0)
-    args = rec.calls[-1][1]
-    assert (args[14].value, args[15].value, args[16]) == (tx.data_ptr(), te.data_ptr(), 0) and tx.shape == (STEPS, B, RT, MZ) == te.shape
+    fields = rec.calls[-1][1]
+    assert (fields["traj_x"], fields["traj_eps"], fields["use_graph"]) == (tx.data_ptr(), te.data_ptr(), 0)
+    assert tx.shape == (STEPS, B, RT, MZ) == te.shape

@@ -214,9 +214,22 @@ def test_python_surface_refusals():
     assert torch.equal(r0, r1) and torch.equal(s0, s1)
 
 
+def dummy_record(ab_c, ts_c, **fields):
+    """a ``dq_sample_call`` over the host schedule ``ab_c`` and list ``ts_c`` whose required device pointers (and the seed) are the dummy
+    address 4096, never dereferenced: a call that passed its checks would fault, so every use refuses something first.  B = 1, RT = 8,
+    a workspace of 2^40 bytes; then ``fields``"""
+    from dquartic import _native as N
+
+    base = dict(alpha_bars_host=ctypes.addressof(ab_c), num_timesteps=len(ab_c), x_T=4096, ms2_cond=4096, ms1_cond=4096, auto_normalize=1,
+                timesteps_host=ctypes.addressof(ts_c), num_steps=len(ts_c), out_x=4096, out_noise=4096, workspace=4096, workspace_bytes=1 << 40,
+                B=1, RT=8, seed_dev=4096)
+    base.update(fields)
+    return N.sample_call(**base)
+
+
 def test_sample_solver_refusals_come_before_the_device():
-    """dq_ddim_sample_solver with dummy (never dereferenced) pointers: each refusal names its reason and nothing is launched -- the
-    process has no GPU context here and must not need one"""
+    """dq_ddim_sample's sampler and clamp fields with dummy (never dereferenced) pointers: each refusal names its reason and nothing is
+    launched -- the process has no GPU context here and must not need one"""
     from dquartic import _native as N
 
     lib = N.lib()
@@ -230,14 +243,13 @@ def test_sample_solver_refusals_come_before_the_device():
 
         def call(ts, eta, sampler, clip):
             ts_c = (ctypes.c_int32 * len(ts))(*ts)
-            return lib.dq_ddim_sample_solver(plan, dummy, dummy, ab_c, len(ab), dummy, dummy, dummy, 1, 0, ts_c, len(ts), dummy, dummy, None, None,
-                                             0, dummy, 1 << 40, 1, 8, None, ctypes.c_float(eta), dummy, None, sampler, ctypes.c_float(clip))
+            return lib.dq_ddim_sample(plan, dummy, dummy, ctypes.byref(dummy_record(ab_c, ts_c, eta=eta, sampler=sampler, clip_x0=clip)))
 
         for args, word in ((([999, 0], 0.0, 7, 0.0), b"unknown sampler"), (([999, 0], 0.5, 2, 0.0), b"eta must be 0"),
                            (([999, 0], 0.5, 1, 1.0), b"clip_x0 needs eta"), (([999, 0], 0.0, 0, 1.0), b"clip_x0 needs the ddim"),
                            (([999, 999], 0.0, 1, 0.0), b"strictly decreasing"), (([0, 999], 0.0, 2, 0.0), b"strictly decreasing")):
             assert call(*args) != 0
-            assert word in lib.dq_last_error(), (args, lib.dq_last_error())
+            assert word in lib.dq_last_error() and lib.dq_last_error().startswith(b"dq_ddim_sample: "), (args, lib.dq_last_error())
     finally:
         lib.dq_plan_destroy(plan)
 

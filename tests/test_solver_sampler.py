@@ -1,5 +1,5 @@
 """Step-consistent samplers on the GPU: ``dq_solver_step`` against float64 at its loop and path edges, the float64 toy
-of tests/test_sampler_tables.py run through the kernel, ``dq_ddim_sample_solver`` per step against the float64 oracle network and the float64
+of tests/test_sampler_tables.py run through the kernel, ``dq_ddim_sample`` with a sampler per step against the float64 oracle network and the float64
 update (graph == eager == trajectory, the captured-step cache keyed by update kind and clamp), and ``predict`` / ``evaluate``.
 
 Bounds.  An update is compared with the float64 expression over the SAME fp32 inputs and coefficients; the bound is K 2^-24 sum |terms|, the

@@ -2,8 +2,8 @@
 
 Without a GPU: this file's numpy transcription of Philox4x32-10 / Box-Muller against the Random123 known-answer vectors, and the host-only
 coefficient table ``dq_ddim_coef_table`` (eta = 0: the sampler's fp32 expressions bit for bit; eta > 0: the float64 formula to 1 ulp).
-On the GPU: ``dq_randn`` and ``dq_ddim_step_sto`` against the transcription in float64, ``dq_ddim_sample_ex`` at eta = 0 against
-``dq_ddim_sample`` bit for bit, an eta = 1 trajectory against a loop over the oracle's network with transcription noise, graph == eager,
+On the GPU: ``dq_randn`` and ``dq_ddim_step_sto`` against the transcription in float64, ``dq_ddim_sample`` with eta = 0 set by name against
+the plain ``dq_ddim_sample`` call bit for bit, an eta = 1 trajectory against a loop over the oracle's network with transcription noise, graph == eager,
 seed and window-placement properties, and the Python surface (``sample`` / ``predict``).
 
 Tolerances.  TOL_Z and K_STEP are four times the worst figure the MI355X showed on exactly these cases (the tests print the figure before
@@ -329,15 +329,15 @@ def _model(pred):
 @gpu
 @pytest.mark.parametrize("pred", ["eps", "x0"])
 def test_sample_ex_eta0_is_dq_ddim_sample(pred):
-    """dq_ddim_sample_ex(eta = 0) against dq_ddim_sample, bit for bit: graph and eager, both objectives"""
+    """the record with eta = 0 and null seed and ids written by name against the plain call, bit for bit: graph and eager, both objectives"""
     dm, _, xT, c2, c1 = _model(pred)
     x, a, b = xT[:2].cuda(), c2[:2].cuda(), c1[:2].cuda()
     try:
         for graph in (True, False):
             dm.use_graph = graph
             with torch.no_grad():
-                s0, n0 = dm.sample(x, a, b, num_steps=3)                                  # dq_ddim_sample
-                s1, n1 = dm._sample_native(x, a, b, 3, eta=0.0)                          # dq_ddim_sample_ex, NULL seed and ids
+                s0, n0 = dm.sample(x, a, b, num_steps=3)                                  # the plain call
+                s1, n1 = dm._sample_native(x, a, b, 3, eta=0.0)                          # eta, seed and ids written: 0, NULL, NULL
                 s2, n2 = dm.sample(x, a, b, num_steps=3, eta=0.0, seed=5, window_ids=[4, 9])  # ... with a seed it never reads
             assert torch.equal(s0, s1) and torch.equal(n0, n1) and torch.equal(s0, s2) and torch.equal(n0, n2)
         with torch.no_grad():

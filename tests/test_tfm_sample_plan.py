@@ -1,5 +1,5 @@
 """The host-only side of the CustomTransformer's native sampler; no device is touched: the attention form query, the
-sampling workspace size, every refusal of dq_tfm_sample (worded like dq_ddim_sample_solver's, which refuses the same calls), the Python
+sampling workspace size, every refusal of dq_tfm_sample (worded like dq_ddim_sample's, which refuses the same calls), the Python
 argument checks of sample() on the adapter, and the config key that switches the sampler on."""
 import ctypes
 import re
@@ -65,7 +65,7 @@ def test_sample_workspace_bytes():
 
 
 class _Call:
-    """dq_tfm_sample / dq_ddim_sample_solver on dummy non-null HOST pointers: a call that passed its checks would fault, so every case here
+    """dq_tfm_sample / dq_ddim_sample on one record of dummy non-null HOST pointers: a call that passed its checks would fault, so every case here
     must be refused before anything touches the device."""
 
     def __init__(self):
@@ -91,20 +91,25 @@ class _Call:
         if a["num_steps"] is None:
             a["num_steps"] = len(a["ts"])
         a["ts_c"] = (ctypes.c_int32 * max(1, len(a["ts"])))(*a["ts"])
-        return a, d
+        ptr = lambda v: None if v is None else v.value  # noqa: E731
+        fields = dict(alpha_bars_host=ctypes.addressof(self.ab), num_timesteps=a["T"], x_T=ptr(a["x_T"]), ms2_cond=ptr(a["ms2"]),
+                      ms1_cond=ptr(a["ms1"]), auto_normalize=1, pred_type=a["pred"], timesteps_host=ctypes.addressof(a["ts_c"]),
+                      out_x=ptr(a["out"]), out_noise=d.value, use_graph=1, workspace=ptr(a["ws"]), workspace_bytes=a["ws_bytes"],
+                      clip_x0=a["clip"], seed_dev=ptr(a["seed"]))
+        fields.update({k: a[k] for k, _ in self.N.SampleCall._fields_ if k in a})  # (the keywords that are the record's own names)
+        q = self.N.sample_call(**fields)
+        return a, d, q
 
     def tfm_sample(self, **kw):
-        a, d = self.args(**kw)
-        rc = self.lib.dq_tfm_sample(self.tfm if a["handle"] else None, a["params"], d, d, d, self.ab, a["T"], a["x_T"], a["ms2"], a["ms1"], 1, a["pred"],
-                                    a["ts_c"], a["num_steps"], a["out"], d, None, None, 1, a["ws"], a["ws_bytes"], a["B"], a["S1"], a["S2"], None,
-                                    a["eta"], a["seed"], None, a["sampler"], a["clip"])
+        a, d, q = self.args(**kw)
+        q.RT = a["S1"]
+        rc = self.lib.dq_tfm_sample(self.tfm if a["handle"] else None, a["params"], d, d, d, a["S2"], ctypes.byref(q))
         return rc, self.N.last_error()
 
     def unet_sample(self, **kw):
-        a, d = self.args(**kw)
-        rc = self.lib.dq_ddim_sample_solver(self.plan if a["handle"] else None, a["params"], d, self.ab, a["T"], a["x_T"], a["ms2"], a["ms1"], 1,
-                                            a["pred"], a["ts_c"], a["num_steps"], a["out"], d, None, None, 1, a["ws"], a["ws_bytes"], a["B"], 16, None,
-                                            a["eta"], a["seed"], None, a["sampler"], a["clip"])
+        a, d, q = self.args(**kw)
+        q.RT = 16
+        rc = self.lib.dq_ddim_sample(self.plan if a["handle"] else None, a["params"], d, ctypes.byref(q))
         return rc, self.N.last_error()
 
 
@@ -137,7 +142,7 @@ SHARED_REFUSALS = [  # (keyword arguments, the message behind the function name)
     (dict(sampler=1, clip=1.0, eta=0.5), "clip_x0 needs eta == 0"),
     (dict(sampler=1, ts=[999, 500, 500]), "the timesteps of this sampler must be strictly decreasing"),
     (dict(sampler=2, ts=[10, 500, 0]), "the timesteps of this sampler must be strictly decreasing"),
-    (dict(pred=2), "Unknown pred_type"),
+    (dict(pred=3), "Unknown pred_type"),  # (DQ_PRED_V = 2 is the U-Net's objective, not the transformer's: test_v_is_the_unets_objective_alone)
     (dict(eta=0.5, seed=None), "eta > 0 and a null x_T need the seed (device memory)"),
     (dict(x_T=None, seed=None), "eta > 0 and a null x_T need the seed (device memory)"),
 ]
@@ -149,6 +154,46 @@ def test_refusals_worded_like_the_unet_loop(call, kw, what):
     assert rc != 0 and _text(msg) == "dq_tfm_sample: " + what, msg
     rc_u, msg_u = call.unet_sample(**kw)
     assert rc_u != 0 and _text(msg_u) == "dq_ddim_sample: " + what, msg_u  # the same wording apart from the function name
+
+
+def test_v_is_the_unets_objective_alone(call):
+    """the transformer's entry refuses DQ_PRED_V as unknown; the U-Net's takes it: the same record gets to the refusal behind the objective"""
+    rc, msg = call.tfm_sample(pred=2)
+    assert rc != 0 and _text(msg) == "dq_tfm_sample: Unknown pred_type", msg
+    rc, msg = call.unet_sample(pred=2, B=0)
+    assert rc != 0 and _text(msg) == "dq_ddim_sample: need B, RT > 0 and 1 <= num_steps <= 1024", msg
+
+
+NOT_THE_TRANSFORMERS = [  # what the record can say and dq_tfm_sample is not built for: refused by name, never ignored
+    (dict(guided=1, guidance_scale=2.0), "guided sampling is built for the U-Net (dq_ddim_sample); guidance for this network is the follow-up"),
+    (dict(guidance_rescale=0.5), "guidance_rescale and threshold_quantile are built for the U-Net (dq_ddim_sample); the per-window statistics step for "
+                                 "this network is the follow-up"),
+    (dict(sampler=1, threshold_quantile=0.5, threshold_max=2.0, stat_scratch=4096, stat_scratch_bytes=1 << 30),
+     "guidance_rescale and threshold_quantile are built for the U-Net (dq_ddim_sample); the per-window statistics step for this network is the "
+     "follow-up"),
+    (dict(consistency=1, group_size=3), "consistency is built for the U-Net (dq_ddim_sample); the group pass for this network is the follow-up"),
+]
+
+
+@pytest.mark.parametrize("kw,what", NOT_THE_TRANSFORMERS, ids=["guided", "rescale", "threshold", "consistency"])
+def test_refuses_what_only_the_unet_serves(call, kw, what):
+    """behind every refusal the shared checks make (SHARED_REFUSALS: each still comes first) and in front of the size checks"""
+    rc, msg = call.tfm_sample(**kw)
+    assert rc != 0 and _text(msg) == "dq_tfm_sample: " + what, msg
+    rc, msg = call.tfm_sample(B=0, S2=-1, ws_bytes=0, T=0, **kw)  # in front of the sizes, the workspace and the schedule length
+    assert rc != 0 and _text(msg) == "dq_tfm_sample: " + what, msg
+    for kw2, first in SHARED_REFUSALS:
+        if set(kw2) & set(kw):
+            continue
+        if "threshold_quantile" in kw and kw2.get("eta", 0.0) > 0.0 and first.startswith("eta > 0 and a null"):
+            first = "threshold_quantile needs eta == 0"  # (thresholding is refused where clip_x0 is, in front of the seed)
+        rc, msg = call.tfm_sample(**kw2, **kw)
+        assert rc != 0 and _text(msg) == "dq_tfm_sample: " + first, (kw2, msg)
+    # a field's own refusal is one of those that come first
+    rc, msg = call.tfm_sample(guided=1, guidance_scale=-1.0)
+    assert rc != 0 and "the guidance scale must be finite" in msg
+    rc, msg = call.tfm_sample(guidance_rescale=1.5)
+    assert rc != 0 and "guidance_rescale must satisfy" in msg
 
 
 @pytest.mark.parametrize("kw", [dict(ts=[], num_steps=0), dict(ts=[5], num_steps=1025), dict(ts=[5], num_steps=1 << 30, sampler=1),  # (its list is not read)

@@ -67,7 +67,7 @@ def test_the_c_entries_refuse_by_message():
         assert rc() != 0
         assert word in lib.dq_last_error(), lib.dq_last_error()
     d = ctypes.c_void_p(4096)
-    # the entries whose pred_type names the reference's two objectives refuse DQ_PRED_V (2) as they always did: the v forms are entries of their own
+    # the stand-alone updates whose pred_type names the reference's two objectives refuse DQ_PRED_V (2) as they always did: their v forms are entries of their own
     named = {
         "dq_solver_step": lambda p: lib.dq_solver_step(d, d, d, None, None, d, f(0.0), p, 8, None),
         "dq_guided_update": lambda p: lib.dq_guided_update(0, d, d, d, d, None, None, None, d, f(1.0), f(0.0), None, d, 1, p, 1, 8, None),
@@ -79,24 +79,33 @@ def test_the_c_entries_refuse_by_message():
     for p in (3, 7, -1):  # (this one takes the value 2)
         assert lib.dq_ddim_step_sto(d, d, d, None, d, None, d, 1, p, 1, 8, None) != 0
         assert b"dq_ddim_step_sto: Unknown pred_type" in lib.dq_last_error()
-    assert lib.dq_ddim_sample(None, None, None, None, 1000, None, None, None, 1, 2, None, 1, None, None, None, None, 0, None, 0, 1, 1, None) != 0
+    from test_sampler_tables import dummy_record
+
     ab = (ctypes.c_float * 4)(0.9, 0.8, 0.7, 0.6)
     ts = (ctypes.c_int32 * 1)(3)
 
-    def loop_v(pred):  # every required pointer there (never read: the objective is refused first), so the objective is what is refused
-        return lib.dq_ddim_sample_v(d, d, d, ab, 4, d, d, d, 1, pred, ts, 1, d, d, None, None, 0, d, 1 << 40, 1, 1, None, f(0.0), None, None, 0, f(0.0),
-                                    0, f(1.0), f(0.0))
+    # every required pointer there (never read: the objective is refused first), so the objective is what is refused
+    def loop_v(pred, **kw):
+        return lib.dq_ddim_sample(d, d, d, ctypes.byref(dummy_record(ab, ts, pred_type=pred, RT=1, seed_dev=None, **kw)))
+
+    def loop_tfm(pred):
+        return lib.dq_tfm_sample(d, d, d, d, d, 4, ctypes.byref(dummy_record(ab, ts, pred_type=pred, RT=1, seed_dev=None)))
 
     for p in (3, 7, -1):
         assert loop_v(p) != 0
-        assert b"dq_ddim_sample_v: Unknown pred_type" in lib.dq_last_error(), lib.dq_last_error()
+        assert b"dq_ddim_sample: Unknown pred_type" in lib.dq_last_error(), lib.dq_last_error()
+    # the transformer's entry refuses v, the U-Net's takes it: the same record gets past the objective there, to the next refusal
+    for p in (2, 3, 7, -1):
+        assert loop_tfm(p) != 0
+        assert b"dq_tfm_sample: Unknown pred_type" in lib.dq_last_error(), lib.dq_last_error()
+    assert loop_v(2, B=0) != 0 and b"dq_ddim_sample: need B, RT > 0" in lib.dq_last_error(), lib.dq_last_error()
+    assert loop_v(2, guided=1, guidance_scale=-1.0) != 0 and b"dq_ddim_sample: the guidance scale" in lib.dq_last_error()
     # the v entries refuse like the entries they mirror, under their own names
     nulls = {
         "dq_ddim_step_v": lambda: lib.dq_ddim_step_v(None, None, None, None, None, 8, None),
         "dq_solver_step_v": lambda: lib.dq_solver_step_v(None, None, None, None, None, None, f(0.0), 8, None),
         "dq_guided_update_v": lambda: lib.dq_guided_update_v(0, None, None, None, None, None, None, None, None, f(1.0), f(0.0), None, None, 1, 1, 8, None),
-        "dq_ddim_sample_v": lambda: lib.dq_ddim_sample_v(None, None, None, None, 1000, None, None, None, 1, 2, None, 1, None, None, None, None, 0, None, 0,
-                                                         1, 1, None, f(0.0), None, None, 0, f(0.0), 0, f(1.0), f(0.0)),
+        "dq_ddim_sample": lambda: lib.dq_ddim_sample(None, None, None, ctypes.byref(N.sample_call(num_timesteps=1000, pred_type=2, num_steps=1, B=1, RT=1))),
         "dq_mse_loss_v_fwd_bwd": lambda: lib.dq_mse_loss_v_fwd_bwd(None, None, None, None, f(2.0), f(-1.0), None, None, None, None, None, 3, 8, None),
     }
     for name, fn in nulls.items():
@@ -111,7 +120,7 @@ def test_the_c_entries_refuse_by_message():
         assert word in lib.dq_last_error(), (kw, lib.dq_last_error())
     assert lib.dq_mse_loss_v_fwd_bwd(d, d, d, d, f(1.0), f(0.0), None, d, d, None, d, 0, 8, None) != 0
     assert b"B and per must be positive" in lib.dq_last_error()
-    assert ctypes.c_int(lib.dq_abi_version()).value == N.ABI_VERSION == 12
+    assert ctypes.c_int(lib.dq_abi_version()).value == N.ABI_VERSION == 13
 
 
 def test_the_config_loader_knows_the_objective(tmp_path):

@@ -1,5 +1,5 @@
 """Per-window sampler control, everything that needs no device: the refusals of ``dq_window_rescale``,
-``dq_window_abs_quantile``, ``dq_step_update_adaptive`` and ``dq_ddim_sample_adaptive`` (dummy pointers, never dereferenced: each refusal
+``dq_window_abs_quantile``, ``dq_step_update_adaptive`` and ``dq_ddim_sample`` with the per-window fields (dummy pointers, never dereferenced: each refusal
 names its reason and nothing is launched), the scratch size rule, the Python surface's argument checks and routing, the command line, and
 this file's numpy transcription of the quantile rule (``abs_quantile_ref``, which tests/test_winstat_kernels.py holds the kernels to bit
 for bit) against ``np.quantile(..., method="linear")``."""
@@ -108,7 +108,7 @@ def test_the_stand_alone_entries_refuse_by_message():
         err = lib.dq_last_error()
         assert word in err, (kw, err)
     assert upd(B=0) == 0 and upd(per=0) == 0 and upd(kind=2, u=None, B=0) == 0  # nothing to do: no launch
-    assert ctypes.c_int(lib.dq_abi_version()).value == N.ABI_VERSION == 12
+    assert ctypes.c_int(lib.dq_abi_version()).value == N.ABI_VERSION == 13
 
 
 def test_the_sampling_entry_refuses_in_sampler_checks_order():
@@ -116,8 +116,7 @@ def test_the_sampling_entry_refuses_in_sampler_checks_order():
     from test_sampler_tables import alpha_bars
 
     lib = N.lib()
-    f, dbl = ctypes.c_float, ctypes.c_double
-    d = ctypes.c_void_p(4096)
+    d, D = ctypes.c_void_p(4096), 4096
     dims = (ctypes.c_int * 2)(1, 2)
     plan = lib.dq_plan_create(4, 2, dims, 8, 1000)
     assert plan
@@ -125,14 +124,18 @@ def test_the_sampling_entry_refuses_in_sampler_checks_order():
         ab = alpha_bars("cosine")
         ab_c = (ctypes.c_float * len(ab))(*ab.tolist())
 
-        def call(ts=(999, 0), eta=0.0, sampler=1, clip=0.0, guided=1, w=3.0, phi=0.0, q=0.0, cap=INF, params=d, pred=0, scratch=d, nbytes=1 << 40,
+        def call(ts=(999, 0), eta=0.0, sampler=1, clip=0.0, guided=1, w=3.0, phi=0.0, q=0.0, cap=INF, params=d, pred=0, scratch=D, nbytes=1 << 40,
                  B=1):
             ts_c = (ctypes.c_int32 * len(ts))(*ts)
-            return lib.dq_ddim_sample_adaptive(plan, params, d, ab_c, len(ab), d, d, d, 1, pred, ts_c, len(ts), d, d, None, None, 0, d, 1 << 40, B, 8,
-                                               None, f(eta), d, None, sampler, f(clip), guided, f(w), f(0.0), dbl(phi), f(q), f(cap), scratch, nbytes)
+            rec = N.sample_call(alpha_bars_host=ctypes.addressof(ab_c), num_timesteps=len(ab), x_T=D, ms2_cond=D, ms1_cond=D, auto_normalize=1,
+                                pred_type=pred, timesteps_host=ctypes.addressof(ts_c), num_steps=len(ts), out_x=D, out_noise=D, workspace=D,
+                                workspace_bytes=1 << 40, B=B, RT=8, eta=eta, seed_dev=D, sampler=sampler, clip_x0=clip, guided=guided,
+                                guidance_scale=w, guidance_rescale=phi, threshold_quantile=q, threshold_max=cap, stat_scratch=scratch,
+                                stat_scratch_bytes=nbytes)
+            return lib.dq_ddim_sample(plan, params, d, ctypes.byref(rec))
 
         cases = (
-            # sampler_check's refusals, in its order, under this entry's name
+            # sampler_check's refusals, in its order, under the entry's name
             (dict(params=None), b"null argument"), (dict(eta=1.5), b"eta must satisfy"), (dict(sampler=7), b"unknown sampler"),
             (dict(eta=0.5, sampler=2), b"eta must be 0"), (dict(clip=1.0, sampler=0), b"clip_x0 needs the ddim or dpmpp_2m sampler"),
             (dict(clip=1.0, eta=0.5), b"clip_x0 needs eta == 0"),
@@ -148,14 +151,18 @@ def test_the_sampling_entry_refuses_in_sampler_checks_order():
             (dict(q=0.9, scratch=None), b"null argument"), (dict(phi=0.5, scratch=None), b"null argument"),
             (dict(q=0.9, nbytes=stat_scratch_bytes(1, 64) - 1), b"scratch too small"),
             (dict(phi=0.5, B=3, nbytes=stat_scratch_bytes(3, 64) - 1), b"scratch too small"),
-            (dict(q=0.9, scratch=ctypes.c_void_p(4104)), b"16-byte aligned"),
+            (dict(q=0.9, scratch=4104), b"16-byte aligned"),
         )
         for kw, word in cases:
             assert call(**kw) != 0, kw
             err = lib.dq_last_error()
-            assert word in err and b"dq_ddim_sample_adaptive" in err, (kw, err)
+            assert word in err and err.startswith(b"dq_ddim_sample: "), (kw, err)
         assert call(sampler=7, phi=2.0) != 0 and b"unknown sampler" in lib.dq_last_error()  # (the sampler's refusal comes first)
         assert call(q=0.9, sampler=0, cap=0.5) != 0 and b"threshold_quantile needs the ddim" in lib.dq_last_error()
+        # with both options at 0 the per-window checks are not made: threshold_max is not looked at and the scratch may be null -- the call
+        # gets as far as the refusal behind them (the batch count)
+        for guided in (0, 1):
+            assert call(cap=NAN, scratch=None, nbytes=0, guided=guided, B=0) != 0 and b"need B, RT > 0" in lib.dq_last_error()
         # the workspace and its size query are what they were
         assert lib.dq_unet_workspace_bytes(plan, 3, 4, 1) == 2 * lib.dq_unet_workspace_bytes(plan, 3, 4, 0)
     finally:
@@ -207,15 +214,16 @@ def test_python_argument_checks():
             dm.sample(x, c2, c1, num_steps=2, **kw)
     tfm = DDIMDiffusionModel(model_class=DDIMTransformerAdapter(CustomTransformer(input_dim=8, hidden_dim=8, num_heads=1, num_layers=1)),
                              device="cpu")
-    with pytest.raises(NotImplementedError, match="dq_ddim_sample_adaptive.*follow-up"):
+    with pytest.raises(NotImplementedError, match=r"dq_ddim_sample\).*follow-up"):
         tfm.sample(x, c2, c1, num_steps=2, sampler="ddim", threshold_quantile=0.9)
     with pytest.raises(NotImplementedError, match="follow-up"):
         tfm.sample(x, c2, c1, num_steps=2, guidance_scale=3.0, guidance_rescale=0.5)  # (guidance itself is the transformer's follow-up too)
 
 
 def test_the_defaults_route_to_the_existing_entries(monkeypatch):
-    """phi = 0 with q unset -- and phi > 0 without guidance, where g = c and m = 1 -- is the call as it is today: the same C entry with the
-    same arguments; only a live option reaches dq_ddim_sample_adaptive, with the three values and the scratch behind dq_ddim_sample_v's list"""
+    """phi = 0 with q unset -- and phi > 0 without guidance, where g = c and m = 1 -- is the call as it is today: the same
+    record; only a live option sets the three values and the scratch (the fields behind null_ms1: test_abi's layout test; what
+    _sample_native writes for them: test_sample_loop.test_entry_choice_guided_and_per_window)"""
     from dquartic import _native as N
     from dquartic.model.model import DDIMDiffusionModel
 
@@ -249,9 +257,11 @@ def test_the_defaults_route_to_the_existing_entries(monkeypatch):
         dm.sample(t, t, t, **base, **extra)
         assert seen[0]["adaptive"] == want, (extra, seen)
         assert (seen[0]["guidance"] is None) == ("guidance_scale" not in extra)
-    # the entry takes dq_ddim_sample_v's list plus (phi, q, cap, scratch, bytes)
-    v, ad = N.PROTOTYPES["dq_ddim_sample_v"][1], N.PROTOTYPES["dq_ddim_sample_adaptive"][1]
-    assert ad[:len(v)] == v and ad[len(v):] == [ctypes.c_double, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64]
+    # the record takes (phi, q, cap, scratch, bytes) behind the guidance fields
+    names = [k for k, _ in N.SampleCall._fields_]
+    i = names.index("null_ms1") + 1
+    assert N.SampleCall._fields_[i:i + 5] == [("guidance_rescale", ctypes.c_double), ("threshold_quantile", ctypes.c_float), ("threshold_max", ctypes.c_float),
+                                              ("stat_scratch", ctypes.c_void_p), ("stat_scratch_bytes", ctypes.c_int64)]
 
 
 def test_signatures_and_pass_through():

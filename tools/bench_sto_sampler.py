@@ -2,16 +2,17 @@
 interleaved (the order rotates every round), median and 10th-90th percentile over the rounds; B = 512 windows of (400, 64), 50 steps,
 graph path:
 
-  a  dq_ddim_sample as it was before this feature -- from the library given with --parent-lib (the parent commit's libdq_hip.so, loaded
-     next to this tree's; it shares the parameters, inputs and nothing else).  Without --parent-lib the form is left out.
-  b  dq_ddim_sample_ex at eta = 0
-  c  dq_ddim_sample_ex at eta = 1
+  b  dq_ddim_sample at eta = 0 (eta, seed and ids written into the record)
+  c  dq_ddim_sample at eta = 1
   d  eta = 1 the torch way: per step the network forward, the deterministic update (dq_ddim_step) and x += sigma * torch.randn_like(x)
      (no graph: a fresh torch.randn per step is what a captured step cannot hold)
 
-    python tools/bench_sto_sampler.py [--parent-lib PATH] [--rounds N] [--out FILE]      (run it twice: the spread of two runs is the yardstick)"""
+Form "a" -- dq_ddim_sample of the commit before stochastic sampling, loaded from a second library through its 22-argument signature -- is
+gone: since ABI version 13 a sampling call crosses as a record (dq_sample_call), and a library that old cannot be called through this
+tree's bindings.  Its recorded results stay (profiles/sto_sampler_run1.json, run2.json).
+
+    python tools/bench_sto_sampler.py [--rounds N] [--out FILE]      (run it twice: the spread of two runs is the yardstick)"""
 import argparse
-import ctypes
 import json
 import os
 import statistics
@@ -25,30 +26,8 @@ sys.path[:0] = [REPO, os.path.join(REPO, "diffusion-deconvolution-dia-msms-data_
 from dquartic import _native as N  # noqa: E402
 
 
-def parent_sampler(path, net, dm, x, c2, c1, ts_c, ns, out_x, out_n):
-    """dq_ddim_sample of another build of the library on this network's parameters: its own plan and workspace"""
-    L = ctypes.CDLL(path)
-    for name in ("dq_plan_create", "dq_unet_workspace_bytes", "dq_ddim_sample", "dq_last_error"):
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = N.PROTOTYPES[name]
-    mults = (ctypes.c_int * len(net.dim_mults))(*net.dim_mults)
-    plan = L.dq_plan_create(net.dim, len(net.dim_mults), mults, net.downsample_dim, 1000)
-    assert plan, L.dq_last_error()
-    B, RT, _ = x.shape
-    ws = torch.empty(L.dq_unet_workspace_bytes(plan, B, RT, 0), dtype=torch.uint8, device=x.device)
-    flat, rope = net.read_params(), net.rope_freqs()
-
-    def run():
-        rc = L.dq_ddim_sample(plan, N.ptr(flat), N.ptr(rope), dm._alpha_bars_host(), int(dm.num_timesteps), N.ptr(x), N.ptr(c2), N.ptr(c1), 1, 0,
-                              ts_c, ns, N.ptr(out_x), N.ptr(out_n), None, None, 1, N.ptr(ws), ws.numel(), B, RT, N.stream_ptr())
-        assert rc == 0, L.dq_last_error()
-
-    return run
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--parent-lib")
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--steps", type=int, default=50)
@@ -63,10 +42,8 @@ def main():
     x = torch.randn(a.batch, RT, MZ, device="cuda")
     ns = a.steps
     ts = [int(v) for v in dm.sampler_timesteps(dm.num_timesteps, ns)]
-    ts_c = (ctypes.c_int32 * ns)(*ts)
     _, sigma = dm.ddim_coef_table(ts, 1.0)
     c2n, c1n = dm.normalize(c2), dm.normalize(c1)
-    out_x, out_n = torch.empty_like(x), torch.empty_like(x)
     res = {}
 
     def ex(eta):
@@ -85,8 +62,6 @@ def main():
             res["d"] = xt
 
     forms = {}
-    if a.parent_lib:
-        forms["a_parent_dq_ddim_sample"] = parent_sampler(a.parent_lib, net, dm, x, c2, c1, ts_c, ns, out_x, out_n)
     forms["b_ex_eta0"] = ex(0.0)
     forms["c_ex_eta1"] = ex(1.0)
     forms["d_torch_randn_unfused"] = torch_way
@@ -95,9 +70,6 @@ def main():
         for f in forms.values():
             f()
     torch.cuda.synchronize()
-    same = None
-    if a.parent_lib:  # the two deterministic forms compute the same thing
-        same = bool(torch.equal(out_x, res[0.0][0]))
     times = {k: [] for k in forms}
     for r in range(a.rounds):
         k0 = r % len(names)
@@ -109,7 +81,7 @@ def main():
             torch.cuda.synchronize()
             times[k].append(s.elapsed_time(e))
     out = {"build_id": N.build_id(), "device": torch.cuda.get_device_name(0), "shape": [a.batch, RT, MZ], "steps": ns, "rounds": a.rounds,
-           "parent_equals_ex_eta0_bitwise": same, "bytes_per_step_of_k_ddim_step_sto": 12 * a.batch * RT * MZ}
+           "bytes_per_step_of_k_ddim_step_sto": 12 * a.batch * RT * MZ}
     for k, t in times.items():
         t.sort()
         out[k] = {"median_ms": statistics.median(t), "p10_ms": t[len(t) // 10], "p90_ms": t[(9 * len(t)) // 10],

@@ -1,7 +1,7 @@
 """Times classifier-free guided sampling of the default U-Net at the bench shape (400 x 64 windows, 50 steps) three
 ways, at batch B = 256 and B = 1:
 
-  guided        sample(..., guidance_scale=w) at batch B: dq_ddim_sample_guided -- one captured step per timestep, the forward at 2 B
+  guided        sample(..., guidance_scale=w) at batch B: dq_ddim_sample with `guided` set -- one captured step per timestep, the forward at 2 B
                 windows, the combination inside the update kernel
   unguided_2B   sample(...) at batch 2 B: the same forward size without guidance (the update in the head launch) -- what the guided call
                 should cost

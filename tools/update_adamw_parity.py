@@ -7,7 +7,7 @@
 
 What is dumped: dq_ddim_step, dq_ddim_step_x0, dq_ddim_step_sto and dq_solver_step on caller-supplied tensors; dq_guided_update for the four
 kinds x both objectives x (16-byte aligned | every tensor one float off | a count that is no multiple of 4); DDIMDiffusionModel.sample on a
-tiny U-Net (dq_ddim_sample_solver / dq_ddim_sample_guided) for every update kind, unguided and guided, as the eager loop, the captured step
+tiny U-Net (dq_ddim_sample) for every update kind, unguided and guided, as the eager loop, the captured step
 and with trajectories; the same for a tiny CustomTransformer (dq_tfm_sample); the four AdamW entries over two steps with the scratch
 (partial sums and the device variant's scalars) and the norm.  Arrays of more than 65536 elements are kept as the SHA-256 of their bytes.  Inputs come from seeded CPU generators, so two processes see the same ones."""
 import hashlib
